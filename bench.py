@@ -11,13 +11,15 @@ Launch contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 the dr
 torch.distributed.run with one rank per GPU. Every rank tessellates its own contiguous range of Tiger
 instances (independent path instances shard embarrassingly, no data-path collective) => weak scaling;
 `value` = vertices produced by ALL ranks per second of the slowest rank. With more than one rank the RCCL gather of
-the streams to rank 0 (vg-renderer_amd/dist.py; SURVEY 8e counts it into the scaling target) is timed too, by default,
+the streams to rank 0 (vg-renderer_amd/dist.py; SURVEY 8e counts it into the scaling target) is timed too with --full,
 and reported as `gather_ms` / `value_with_gather` beside `value`.
 
-Rank 0 prints ONE JSON line (fields documented in DESIGN.md "Measurement"): the headline (Tiger x10k = BASELINE's
-metric) with `roofline` and `cpu_baseline`, and -- on 1-GPU runs -- the other two single-GPU BASELINE configs (1M
-cubics flatten-only, 10k x 1k-segment Round/Round polylines) under `configs`, each with its own roofline object.
-`--config NAME` makes another config the headline of the line.
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps and prints the headline (Tiger x10k = BASELINE's
+metric): `value`, `ms_per_step` (wall time of one timed step) and the batch it was measured on. `--full` adds everything
+else (fields documented in DESIGN.md "Measurement"): `roofline` and `cpu_baseline`, the companion legs, and -- on 1-GPU runs --
+the other BASELINE configs (1M cubics flatten-only, 10k x 1k-segment Round/Round polylines, ...) under `configs` in the
+record written to --details. `--config NAME` makes another config the headline of the line. `--dump-outputs DIR` writes what
+the last timed step computed (dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -319,10 +321,11 @@ def hetero_leg(rt, torch, wl, dev, local_rank, rank, world, red_dev, instances=4
     return info
 
 
-def run_config(rt, torch, ctx, local_rank, name, ps, draws, kind, steps, warmup, barrier, placements=1):
+def run_config(rt, torch, ctx, local_rank, name, ps, draws, kind, steps, warmup, barrier, placements=1, full=True, dump_dir=None):
     """Times `steps` steps of one workload (inputs resident in HBM) between barriers. Returns a dict with the wall time,
     the output sizes, the per-kernel HIP-event times (averaged over a few extra steps outside the timed region) and the
-    algorithmic bytes per kernel."""
+    algorithmic bytes per kernel. full=False: the wall time and the output sizes only (no companion legs, no HIP events).
+    dump_dir: what the last timed step computed goes there (dump_outputs) before anything else runs."""
     import numpy as np
     dev = torch.device("cuda", local_rank)
     ndraws = draws.shape[0]
@@ -379,7 +382,9 @@ def run_config(rt, torch, ctx, local_rank, name, ps, draws, kind, steps, warmup,
                 torch.cuda.synchronize()
                 collect.update(dict(ctx.stage_times()))
         step = step2 if two_phase else step1
-        if not two_phase:
+        fp, fs, fd = (poly, subs, dinfo) if two_phase else (fb.poly, fb.subs, fb.dinfo)
+        outs = {"poly": (fp, npv), "subpaths": (fs.view(torch.int32).view(-1, 4), nsp), "draw_info": (fd.view(torch.int32).view(-1, 10), ndraws)}
+        if not two_phase and full:
             # the companion number: the two-phase entry on the same batch, a few steps, outside the timed region
             for _ in range(2):
                 step2()
@@ -426,19 +431,31 @@ def run_config(rt, torch, ctx, local_rank, name, ps, draws, kind, steps, warmup,
                 collect.update(dict(ctx.stage_times()))
         units = sizes["num_vertices"]
         unit_name = "output vertices"
+        outs = {"pos": (bufs.pos, sizes["num_vertices"]), "color": (bufs.color, sizes["num_vertices"]), "idx": (bufs.idx, sizes["num_indices"]),
+                "meshes": (bufs.meshes.view(torch.int32).view(-1, 8), sizes["num_meshes"])}
     for _ in range(warmup):
         step()
     barrier()
     if bufs is not None:
         status = int(bufs.dev_status.item())
         assert status == 0, "device status %d" % status
-    ctx.set_profiling(True)  # HIP events between kernels on the launch stream (cheap; part of the timed region)
+    if full:
+        ctx.set_profiling(True)  # HIP events between kernels on the launch stream (cheap; part of the timed region)
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
     barrier()
     dt = time.perf_counter() - t0
+    chk = bufs if bufs is not None else (None if two_phase else fb)
+    if chk is not None:
+        assert int(chk.dev_status.item()) == 0, "device status %d" % int(chk.dev_status.item())
+    if dump_dir is not None:
+        dump_outputs(dump_dir, outs)
+    if not full:
+        del pinned
+        res.update(dt=dt, sizes=sizes, units=units, unit_name=unit_name, bufs=bufs, pset=pset, dd=dd)
+        return res
     if kind == "flatten":
         # two entry points per step with a host synchronisation inside the first: the per-kernel times come from a few extra steps
         samples = []
@@ -853,6 +870,42 @@ def roofline(res, steps, traffic_for=None):
             "pipeline_achieved": round(ab["pipeline"] / (ms_per_step * 1e-3) / 1e9, 1)}
 
 
+DUMP_ROWS = 1 << 18  # rows kept per output by --dump-outputs: the whole dump stays well under 64 MB at every config
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: what the timed path handed its caller in the last step, `outs` = name -> (device tensor, rows in use), written as
+    <path>/<name>.npy. Float data stays float32; integer data (colours, indices, mesh / sub-path / draw records) is read as unsigned
+    integers of its width and stored as float32 (16 bit) or float64 (32 bit), which holds every value exactly. An output of more than
+    DUMP_ROWS rows is cut to the rows np.unique(RandomState(0).randint(0, rows, DUMP_ROWS)), listed in <path>/<name>_rows.npy: the same rows
+    for the same sizes, so that two builds compare element for element. <path>/sizes.npy holds every output's row count, in name order."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    names = sorted(outs)
+    for name in names:
+        t, n = outs[name]
+        t = t[:n]
+        if n > DUMP_ROWS:
+            rows = np.unique(np.random.RandomState(0).randint(0, n, DUMP_ROWS, dtype=np.int64))
+            t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        a = t.cpu().numpy()
+        if a.dtype != np.float32:
+            a = a.view(np.dtype("u%d" % a.dtype.itemsize)).astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+    np.save(os.path.join(path, "sizes.npy"), np.array([outs[k][1] for k in names], dtype=np.float64))
+
+
+def _flush_c_stdout():
+    """RCCL writes a version banner to the C stdout at communicator creation: get it out BEFORE the JSON line."""
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except OSError:
+        pass
+
+
 def _finite(x):
     """NaN / infinities -> None, recursively: the printed line must load with a strict JSON parser."""
     if isinstance(x, float):
@@ -872,12 +925,16 @@ def main():
     ap.add_argument("--instances", type=int, default=10000, help="Tiger instances PER GPU (BASELINE config: 10000)")
     ap.add_argument("--config", default="tiger10k", choices=sorted(k for k in WORKLOADS if k != "tiger10k_animated"), help="workload of the headline line (default: the BASELINE metric's)")
     ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configs reported under 'configs' (1-GPU runs)")
-    ap.add_argument("--gather", action="store_true", help="(default for --gpus > 1) also time the RCCL gather of the streams to rank 0")
+    ap.add_argument("--gather", action="store_true", help="(default for --gpus > 1 with --full) also time the RCCL gather of the streams to rank 0")
     ap.add_argument("--no-gather", action="store_true", help="multi-GPU: skip the gather leg")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--details", default=os.path.join(ROOT, "bench_details.json"), help="where the full record goes (every config, stage times, sweeps); stdout carries the short line only")
+    ap.add_argument("--details", default=os.path.join(ROOT, "bench_details.json"), help="--full: where the full record goes (every config, stage times, sweeps); stdout carries the short line only")
     ap.add_argument("--placements", type=int, default=1, help="output-buffer allocations to probe before the warm-up (default 1 = the first allocation is the one that is timed; "
                                                                "N > 1 reports every candidate and times the fastest -- a tuning aid, not the headline)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the CPU baselines, the other configs, the companion legs (sustained, cold and one-shot "
+                                                        "steps, partition, frame, gather), per-kernel times and the roofline; the full record goes to --details. "
+                                                        "Without it a run sets up, warms up, times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     import numpy as np
@@ -905,12 +962,12 @@ def main():
 
     cpu = None
     other_cpu = {}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu = cpu_baseline()  # before any GPU work, in separate processes
         if not args.no_configs:
             for name, which in CONFIG_CPU.items():  # the reference beside every BASELINE config, on a bounded sample (4 s each)
                 other_cpu[name] = cpu_baseline(budget_seconds=CONFIG_CPU_BUDGET.get(which, 2.5), which=which)
-    genv = gpu_environment() if rank == 0 else None
+    genv = gpu_environment() if rank == 0 and args.full else None
 
     def barrier():
         if world > 1:
@@ -923,7 +980,8 @@ def main():
     if args.config in CONFIG_ENV:  # library options are read at vgx_create
         os.environ.update(CONFIG_ENV[args.config])
     ctx = rt.Context(local_rank)
-    res = run_config(rt, torch, ctx, local_rank, args.config, ps, draws, kind, args.steps, args.warmup, barrier, placements=max(1, args.placements))
+    res = run_config(rt, torch, ctx, local_rank, args.config, ps, draws, kind, args.steps, args.warmup, barrier, placements=max(1, args.placements),
+                     full=args.full, dump_dir=args.dump_outputs if rank == 0 else None)
     del draws
     sizes, bufs, pset, dd, ndraws = res["sizes"], res["bufs"], res["pset"], res["dd"], res["ndraws"]
     dt = res["dt"]
@@ -949,7 +1007,7 @@ def main():
     # equal-count split. One rank: the parts are timed one after the other on the one GPU (what each rank of an 8-GPU run would do).
     # Runs right after the headline's timing, while all ranks are still in step (the gather legs below can time out on a rank).
     hetero = None
-    if args.config == "tiger10k" and not args.no_configs:
+    if args.config == "tiger10k" and args.full and not args.no_configs:
         try:
             hetero = hetero_leg(rt, torch, wl, dev, local_rank, rank, world, red_dev)
         except Exception as e:  # noqa: BLE001 -- a diagnostic leg must not take the headline line with it
@@ -962,7 +1020,7 @@ def main():
     gather_ms = None
     gather_via = None
     bail = False  # the C-ABI gather leg got stuck: print the line with what is measured and leave without touching the communicators again
-    if (world > 1 or os.environ.get("VGX_BENCH_FORCE_GATHER") == "1") and not args.no_gather and bufs is not None:
+    if (world > 1 or os.environ.get("VGX_BENCH_FORCE_GATHER") == "1") and (args.full or args.gather) and not args.no_gather and bufs is not None:
         dm = importlib.import_module("vg-renderer_amd.dist")
         import threading
         if world == 1:
@@ -1114,7 +1172,7 @@ def main():
 
     # ---- next rows, measured beside the headline on rank 0 of a 1-GPU run: not part of `value` ----
     next_rows = None
-    if rank == 0 and world == 1 and args.config == "tiger10k" and not args.no_configs:
+    if rank == 0 and world == 1 and args.config == "tiger10k" and args.full and not args.no_configs:
         nv_all, ni_all = sizes["num_vertices"], sizes["num_indices"]
         # draw-command assembly armed: cost of the partition kernels inside one step
         cap = 2 * (nv_all // 65536) + 2
@@ -1173,7 +1231,7 @@ def main():
 
     # ---- the other BASELINE configs north_star names ("N cubics, M-segment strokes"), 1-GPU runs, beside the headline ----
     other = None
-    if rank == 0 and world == 1 and not args.no_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_configs:
         other = {}
         del bufs
         res["bufs"] = None
@@ -1252,6 +1310,19 @@ def main():
         metric = "M tessellated verts/sec (stroke+fill AA), Tiger×10k batch, 1/2/4/8 GPUs"
         if args.config != "tiger10k":
             metric = "M %s/sec, %s" % (res["unit_name"], WORKLOADS[args.config])
+    if rank == 0 and not args.full:
+        # a plain run: the headline figure and the batch it was measured on; everything else is --full's
+        line = {"metric": metric, "value": round(value, 2), "unit": "M verts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                "config": {"workload": workload_desc, "name": args.config, "instances_per_gpu": K if args.config == "tiger10k" else None, "draws_per_gpu": ndraws,
+                           "parallelism": "shard%d" % world, "verts_per_gpu": sizes.get("num_vertices", 0), "indices_per_gpu": sizes.get("num_indices", 0),
+                           "meshes_per_gpu": sizes.get("num_meshes", 0), "poly_verts_per_gpu": sizes["num_poly_vertices"]}}
+        if by_rank is not None:
+            line["ms_per_step_by_rank"] = by_rank
+        line = json.dumps(_finite(line), allow_nan=False)
+        _flush_c_stdout()
+        print(line, flush=True)
+    if rank == 0 and args.full:
         out = {
             "metric": metric,
             "value": round(value, 2), "unit": "M verts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1427,11 +1498,7 @@ def main():
                 f.write(details + "\n")
         except OSError as e:
             sys.stderr.write("bench_details: could not write %s: %r\n" % (args.details, e))
-        try:  # RCCL writes a version banner to the C stdout at communicator creation: get it out BEFORE the JSON line
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except OSError:
-            pass
+        _flush_c_stdout()
         sys.stderr.write("bench_details: " + details + "\n")
         sys.stderr.flush()
         print(line, flush=True)  # the LAST line of stdout

@@ -1,7 +1,7 @@
 TAG=r05_f; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 for CFG in round10k; do
   SFX="_$CFG"
-  BENCH="python bench.py --config $CFG --no-cpu --no-configs --steps 8 --warmup 2 --placements 1"
+  BENCH="python bench.py --full --config $CFG --no-cpu --no-configs --steps 8 --warmup 2 --placements 1"
   timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $BENCH > $OUT/trace$SFX.log 2>&1
   timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o fetch -- $BENCH > $OUT/fetch$SFX.log 2>&1
   timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o write -- $BENCH > $OUT/write$SFX.log 2>&1

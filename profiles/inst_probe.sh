@@ -11,7 +11,7 @@ done
 echo "--- VGX_INST=0"; VGX_INST=0 timeout 120 python profiles/stage_times.py 2>/dev/null | tail -1
 for w in $WAVES; do echo "--- waves $w"; VGX_INST_WAVES=$w timeout 120 python profiles/stage_times.py 2>/dev/null | tail -1; done
 if [ -n "$PMC" ]; then
-BENCH="python bench.py --no-cpu --no-configs --steps 6 --warmup 2 --placements 1"
+BENCH="python bench.py --full --no-cpu --no-configs --steps 6 --warmup 2 --placements 1"
 i=0
 for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES SQ_WAVE_CYCLES" "SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_THREAD_CYCLES_VALU" "SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_ANY"; do
   i=$((i+1))

@@ -1,5 +1,5 @@
 OUT=gpurun_out/r02_g_sq; mkdir -p $OUT; export TMPDIR=/tmp
-BENCH="python bench.py --no-cpu --no-configs --steps 6 --warmup 2 --placements 1"
+BENCH="python bench.py --full --no-cpu --no-configs --steps 6 --warmup 2 --placements 1"
 i=0
 for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES SQ_WAVE_CYCLES" "SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_THREAD_CYCLES_VALU"; do
   i=$((i+1))

@@ -3,7 +3,7 @@
 # (kernel trace only), summarised by profiles/pmc_dump.py.   usage (on the GPU box, repo root): bash profiles/pmc_stroke_round10k.sh r06_sq_round10k [config]
 TAG=${1:-r06_sq_round10k}; CFG=${2:-round10k}
 OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-BENCH="python bench.py --config $CFG --no-cpu --no-configs --steps 6 --warmup 2"
+BENCH="python bench.py --full --config $CFG --no-cpu --no-configs --steps 6 --warmup 2"
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY" \
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR" \

@@ -13,13 +13,13 @@ if [ "$1" == "--tests" ]; then
   tail -3 $OUT/pytest.log
 fi
 CONFIGS=${@:-tiger10k}
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; cp bench_details.json $OUT/bench_details.json 2>/dev/null
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; cp bench_details.json $OUT/bench_details.json 2>/dev/null
 tail -c 400 $OUT/bench.json
 PARTS=""
 for CFG in $CONFIGS; do
   SFX=""; [ "$CFG" != "tiger10k" ] && SFX="_$CFG"
   # one workload per profile: per-kernel averages must not mix batch sizes
-  BENCH="python bench.py --config $CFG --no-cpu --no-configs --steps 8 --warmup 2 --placements 1"
+  BENCH="python bench.py --full --config $CFG --no-cpu --no-configs --steps 8 --warmup 2 --placements 1"
   timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $BENCH > $OUT/trace$SFX.log 2>&1
   timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o fetch -- $BENCH > $OUT/fetch$SFX.log 2>&1
   timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o write -- $BENCH > $OUT/write$SFX.log 2>&1

@@ -1,7 +1,7 @@
-"""bench.py's output contract, on small batches: the one-rank line (metric, value, roofline with traffic_ratio, cpu_baseline
-when asked, configs) and the multi-rank code path -- two ranks launched the way the driver launches them (torch.distributed.run,
-one process per rank), both on cuda:0 over gloo (VGX_BENCH_SHARE_GPU=1: RCCL refuses two ranks on one device, the GPU test
-boxes have one): weak scaling, max over ranks, per-rank times, the gather leg through vg-renderer_amd/dist.py."""
+"""bench.py's output contract, on small batches: the plain line (the headline keys only) with --dump-outputs, the one-rank
+--full line (metric, value, roofline with traffic_ratio, cpu_baseline when asked, configs) and the multi-rank code path -- two
+ranks launched the way the driver launches them (torch.distributed.run, one process per rank), both on cuda:0 over gloo
+(VGX_BENCH_SHARE_GPU=1: RCCL refuses two ranks on one device, the GPU test boxes have one): weak scaling, max over ranks, per-rank times, the gather leg through vg-renderer_amd/dist.py."""
 import json
 import os
 import subprocess
@@ -26,10 +26,48 @@ def _line(out):
     return _strict(last)
 
 
+HEAD_KEYS = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"]
+
+
+def test_plain_line_and_dumped_outputs(tmp_path, oracle):
+    """Without --full: the headline keys and the batch, no details file; --dump-outputs holds what the last timed step computed --
+    the same arrays on a second run, and what the reference computes for the same seeded batch."""
+    import importlib
+    import numpy as np
+    import bench
+    det = tmp_path / "details.json"
+    dumps = [tmp_path / "dump0", tmp_path / "dump1"]
+    for d in dumps:
+        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--instances", "2",
+                                       "--details", str(det), "--dump-outputs", str(d)], text=True, timeout=600, cwd=ROOT)
+        short = _line(out)
+        assert list(short) == HEAD_KEYS + ["config"], list(short)
+        assert short["steps"] == 3 and short["warmup"] == 1 and short["n_gpus"] == 1 and short["ms_per_step"] > 0
+        assert short["metric"].startswith("M tessellated verts/sec") and short["unit"] == "M verts/s" and short["dtype"] == "f32" and short["higher_is_better"] is True
+        assert abs(short["value"] - short["config"]["verts_per_gpu"] / short["ms_per_step"] / 1e3) / short["value"] < 0.02
+        assert not det.exists()
+    names = ["color", "idx", "idx_rows", "meshes", "pos", "sizes"]  # two instances: 83 k vertices, 363 k indices (more than bench.DUMP_ROWS: sampled)
+    assert sorted(os.listdir(dumps[0])) == [n + ".npy" for n in names]
+    for n in names:
+        a, b = np.load(dumps[0] / (n + ".npy")), np.load(dumps[1] / (n + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    wl = importlib.import_module("vg-renderer_amd.workloads")
+    ps, draws, _, _ = bench.make_workload(wl, "tiger10k", 2, 0)
+    ref = oracle.tessellate(ps, draws, kind="reference" if oracle.available("reference") else "port")
+    nv, ni, nm = ref.sizes["num_vertices"], ref.sizes["num_indices"], ref.sizes["num_meshes"]
+    assert np.load(dumps[0] / "sizes.npy").tolist() == [nv, ni, nm, nv] == [short["config"][k] for k in ("verts_per_gpu", "indices_per_gpu", "meshes_per_gpu", "verts_per_gpu")]
+    assert np.array_equal(np.load(dumps[0] / "pos.npy").view(np.uint32), ref.pos.view(np.uint32))
+    assert np.array_equal(np.load(dumps[0] / "color.npy"), ref.color.astype(np.float64))
+    rows = np.load(dumps[0] / "idx_rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.unique(rows)) and rows[-1] < ni and np.array_equal(np.load(dumps[0] / "idx.npy"), ref.idx[rows].astype(np.float32))
+    meshes = np.load(dumps[0] / "meshes.npy")
+    assert meshes.shape == (nm, 8) and meshes[:, 4].sum() == nv and meshes[:, 5].sum() == ni  # vertex / index counts of every mesh record
+
+
 def test_one_rank_line(tmp_path):
     det = str(tmp_path / "details.json")
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--instances", "300", "--no-cpu",
-                                   "--placements", "1", "--details", det], text=True, timeout=600, cwd=ROOT)
+                                   "--placements", "1", "--details", det, "--full"], text=True, timeout=600, cwd=ROOT)
     short = _line(out)
     # the short line: contract keys first, then roofline + cpu_baseline; the BASELINE configs readable from `config`
     assert list(short.keys())[:15] == ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
@@ -84,7 +122,7 @@ def test_two_ranks_share_one_gpu(tmp_path):
     env = dict(os.environ, VGX_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     out = subprocess.check_output([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                    "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                                   "--instances", "200", "--no-cpu", "--placements", "1", "--details", str(tmp_path / "details2.json")], text=True, timeout=900, cwd=ROOT, env=env,
+                                   "--instances", "200", "--no-cpu", "--placements", "1", "--details", str(tmp_path / "details2.json"), "--full"], text=True, timeout=900, cwd=ROOT, env=env,
                                   stderr=subprocess.DEVNULL)
     d = _line(out)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak"
