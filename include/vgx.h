@@ -45,9 +45,11 @@ typedef enum vgx_status {
 	VGX_E_NO_DEVICE = 7,     /* no gfx950 device / HIP runtime unavailable */
 	VGX_E_RANGE = 8,         /* batch exceeds 2^32-1 polyline vertices or commands; split the batch */
 	VGX_E_INTERNAL = 9,      /* device-side protocol error (a wait inside the single-pass kernel timed out): a bug, report it */
-	VGX_E_STALE = 10         /* vgx_tessellate: the draws no longer have the structure the last vgx_tessellate_count found (template
+	VGX_E_STALE = 10,        /* vgx_tessellate: the draws no longer have the structure the last vgx_tessellate_count found (template
 	                          * mode, see vgx_tessellate): a field other than mtx / colours / state_key of some draw differs from the
 	                          * counted batch. Outputs are undefined; call vgx_tessellate_count on the new draws */
+	VGX_E_GROWN = 11         /* vgx_tessellate_immediate (dev_status): the batch outgrew a scratch table of the context. Nothing was written past
+	                          * any table; the need went to the context, the next immediate call grows its scratch first: call again */
 } vgx_status;
 
 /* Path commands. One opcode per vg::pathXXX builder call (reference include/vg/path.h:24-35).
@@ -313,6 +315,40 @@ int vgx_tessellate_emit(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* dra
  * THIS call's totals, and a call whose output outgrows the caller's buffers ends with VGX_E_NOSPACE in dev_status (the need in dev_sizes,
  * nothing written) although the counted batch fitted. Templates of one class only; VGX_TMPL_ROUND=0 keeps such batches on the ordinary path. */
 int vgx_tessellate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
+
+/* ---- immediate mode: batches that were never counted -----------------------------------------
+ * The reference works in immediate mode: every frame is new content, appended into arrays that grow when they fill up (Path
+ * src/path.cpp:748-759, Stroker src/stroker.cpp:2316-2347, vg::Mesh src/vg.cpp:5344-5357). vgx_tessellate_immediate is the batch
+ * form of that: flatten + transformPath + the stroker calls for a batch the context may never have seen -- the same output, in the
+ * same order, with the same draw-command assembly (vgx_set_assembly) as vgx_tessellate_count + vgx_tessellate_emit -- with no count.
+ *   - No prior count is needed: it works on a fresh context and after counts, tessellations or flattens of other batches.
+ *   - It fits: VGX_OK in dev_status, dev_sizes holds this batch's totals. Asynchronous: nothing on the host waits for the stream.
+ *   - The caller's buffers are too small: VGX_E_NOSPACE; num_vertices, num_indices and num_meshes in dev_sizes are exact. While assembly
+ *     is armed, num_drawcmds is exact when those fit and only the draw-command table is too small (the partition runs once the streams
+ *     fit: 0 otherwise). Nothing is written past a capacity (as vgx_tessellate).
+ *   - The context's scratch is too small: VGX_E_GROWN. Nothing is written past any scratch table. dev_sizes holds the exact flatten
+ *     totals (num_cmd_instances, num_poly_vertices, num_subpaths, num_meshes); output totals that were not reached are 0. The need
+ *     (with the long sub-paths the heap of the single-pass flatten is sized for) goes to a pinned host mirror of the context by an
+ *     asynchronous copy; the NEXT immediate call on the context grows its scratch from it before it launches anything, with the
+ *     formulas of vgx_tessellate_count. It reads the mirror only once the copy has completed (an event query): it never blocks on it.
+ *   - Convergence: calling again with the same arguments -- reading dev_status in between and, after VGX_E_NOSPACE, growing the
+ *     output buffers to dev_sizes -- reaches VGX_OK within three calls (one more when an armed assembly's draw-command table is too small
+ *     as well); within one when vgx_reserve was big enough. A batch beyond 2^32 - 16 polyline vertices or command instances ends with
+ *     VGX_E_RANGE instead of VGX_E_GROWN: split it.
+ *   - Routes: frame-sized batches (<= 2048 draws) take the frame-sized pipeline; larger ones k_flatten_build first, and from the second
+ *     call on the same (path set, number of draws) -- once the last call's totals have reached the mirror -- the instanced flatten
+ *     when the draws repeat a sequence of paths (checked on the device every call) or the one-walk flatten for long curves, chosen
+ *     with vgx_tessellate_count's rules. Template and static-batch modes stay with the counted calls.
+ *   - Ends any counted state of the context, as vgx_flatten does: the template, the static batch and the _count / _emit pairing
+ *     (count again before the next vgx_tessellate_emit or template-mode vgx_tessellate).
+ * Host return values: VGX_OK once the work is enqueued, VGX_E_INVALID_ARG for null ctx / ps / out / stream pointers, VGX_E_HIP when
+ * growing the scratch fails; the batch's own verdict is in dev_status. */
+int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out,
+                             vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
+/* Size the context's scratch for batches up to these totals without counting anything (host; allocates, may block): ndraws draws
+ * and, of `totals`, num_cmd_instances, num_poly_vertices, num_subpaths and num_meshes (the other fields are ignored). A batch within
+ * them takes one vgx_tessellate_immediate call (the caller's buffers permitting). */
+int vgx_reserve(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals);
 
 /* ---- stroker level: polylines in, meshes out ----------------------------------------------------- */
 /* What the reference hands to strokerConvexFill[AA] / strokerPolylineStroke[AA|AAThin] (include/vg/stroker.h:29-72):

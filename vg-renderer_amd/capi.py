@@ -18,6 +18,7 @@ VGX_E_NO_DEVICE = 7
 VGX_E_RANGE = 8
 VGX_E_INTERNAL = 9
 VGX_E_STALE = 10
+VGX_E_GROWN = 11  # vgx_tessellate_immediate: the batch outgrew the context's scratch (the next immediate call grows it)
 FILL_TRILIST = 0x40  # vgx_draw.fill_flags: a user mesh (IndexedTriList): the decoder's tri_* arrays + vgx_merge_uv
 FILL_CONCAVE, FILL_EVEN_ODD = 0x10, 0x20  # vgx_draw.fill_flags: a concave fill (no GPU mesh: libtess2 + vgx_concave_* + vgx_merge)
 
@@ -199,6 +200,8 @@ VGX_SYMBOLS = {
     "vgx_tessellate_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Sizes), C.c_void_p]),
     "vgx_tessellate_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p]),
     "vgx_tessellate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_tessellate_immediate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_reserve": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(Sizes)]),
     "vgx_stroke_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(Sizes), C.c_void_p]),
     "vgx_stroke_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p]),
     "vgx_concave_move": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

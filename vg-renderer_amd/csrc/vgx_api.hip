@@ -153,6 +153,12 @@ struct vgx_ctx
 	VgxCaps caps; // element capacities matching the buffers above
 	uint64_t capDraws;
 	VgxTotals* hostTotals; // pinned
+	// vgx_tessellate_immediate: pinned mirror of the last immediate call's totals, the event behind its copy (the next call reads the mirror
+	// only once that copy has landed) and the batch it belongs to (tag = path set generation, draw count; was the detection pass run)
+	VgxTotals* immHost; hipEvent_t immEv; bool immEvPending; uint64_t immPendTag; uint64_t immPendNDraws; bool immPendDetect;
+	// ... and what the host learned from the last mirror it read: the batch, its polyline vertices / command instances, the period of its
+	// paths (0: none), how many different paths it uses and, after VGX_E_GROWN, its long sub-paths
+	bool immKnown, immLongKnown; uint64_t immTag, immV, immCmd, immLong, immInstLong, immDistinct; uint32_t immPeriod;
 	// state of the last *_count call (what _emit continues from)
 	const vgx_pathset* lastPs;
 	const vgx_draw* lastDraws;
@@ -601,7 +607,7 @@ void runFlattenOneWalk(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draw
 	const uint64_t segBound = ctx->f1RouteSegBound;
 	VgxF1Args x;
 	x.seg_draw = (uint64_t*)ctx->f1SegDraw.p; x.segs = (VgxF1Seg*)ctx->f1Segs.p; x.grps = x.segs + segBound;
-	x.cap_poly = ctx->caps.poly_vertices; x.cap_subs = ctx->caps.subpaths; x.pass = 0; x.read_flags = 0; x.has_empty = ps->hasEmpty ? 1 : 0;
+	x.cap_poly = ctx->caps.poly_vertices; x.cap_subs = ctx->caps.subpaths; x.cap_meshes = ctx->caps.meshes; x.pass = 0; x.read_flags = 0; x.has_empty = ps->hasEmpty ? 1 : 0;
 	x.seg_max = ctx->f1RouteSegMax; x.tag = 0;
 	if (ps->hasSerial) { // statically serial paths: the exact builder counts their draws first (it marks them in dinfo)
 		noteHip(ctx, hipMemsetAsync(ctx->dinfo.p, 0, ndraws * sizeof(vgx_draw_info), s));
@@ -785,6 +791,7 @@ const char* vgx_status_string(int status)
 	case VGX_E_RANGE: return "VGX_E_RANGE";
 	case VGX_E_INTERNAL: return "VGX_E_INTERNAL";
 	case VGX_E_STALE: return "VGX_E_STALE";
+	case VGX_E_GROWN: return "VGX_E_GROWN";
 	default: return "VGX_E_UNKNOWN";
 	}
 }
@@ -871,6 +878,7 @@ int vgx_destroy(vgx_ctx* ctx)
 	}
 	if (ctx->hostTotals) { (void)hipHostFree(ctx->hostTotals); }
 	if (ctx->hostF1) { (void)hipHostFree(ctx->hostF1); }
+	if (ctx->immHost) { (void)hipHostFree(ctx->immHost); (void)hipEventDestroy(ctx->immEv); }
 	if (ctx->hostPs) { (void)hipHostFree(ctx->hostPs); }
 	if (ctx->psImage) { (void)hipHostFree(ctx->psImage); }
 	for (int i = 0; i < VGX_PS_POOL; ++i) { if (ctx->psPool[i].p) { (void)hipFree(ctx->psPool[i].p); } }
@@ -1180,7 +1188,22 @@ int vgx_pathset_destroy(vgx_ctx* ctx, vgx_pathset* ps)
 
 // ---- flatten ------------------------------------------------------------------------------------------
 // detectInst: look for reused paths (instanced flatten kernel of vgx_tessellate); the flatten-only entry points have no use for it
+static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s, bool detectInst);
+// The per-command scratch's bound as its buffers stand (the count lifts it for its sizing pass)
+static void cmdCapFromBuffers(vgx_ctx* ctx)
+{
+	uint64_t c = ctx->cmdCnt.p ? ctx->cmdCnt.cap / sizeof(uint32_t) - 1 : 0;
+	const uint64_t c2 = ctx->subFirst.p ? ctx->subFirst.cap / sizeof(VgxSubRec) - 1 : 0;
+	if (c2 < c) { c = c2; }
+	ctx->caps.cmd_instances = c;
+}
 static int flattenCountCommon(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s, bool detectInst)
+{
+	const int st = flattenCountBody(ctx, ps, draws, ndraws, s, detectInst);
+	if (st != VGX_OK) { cmdCapFromBuffers(ctx); } // a count that failed part-way leaves no lifted bound behind (later calls trust it)
+	return st;
+}
+static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s, bool detectInst)
 {
 	int st;
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
@@ -1402,7 +1425,7 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	a.caps.poly_vertices = ~0ull; a.caps.subpaths = ~0ull; a.caps.meshes = ~0ull;
 	VgxF1Args x;
 	x.seg_draw = (uint64_t*)ctx->f1SegDraw.p; x.segs = (VgxF1Seg*)ctx->f1Segs.p; x.grps = x.segs + segBound;
-	x.cap_poly = out->cap_poly_vertices; x.cap_subs = out->cap_subpaths; x.pass = 0; x.read_flags = 0; x.has_empty = ps->hasEmpty ? 1 : 0; x.seg_max = segMax; x.tag = tag;
+	x.cap_poly = out->cap_poly_vertices; x.cap_subs = out->cap_subpaths; x.cap_meshes = ~0ull; x.pass = 0; x.read_flags = 0; x.has_empty = ps->hasEmpty ? 1 : 0; x.seg_max = segMax; x.tag = tag;
 	if (ps->hasSerial) { // statically serial paths: the exact builder counts their draws first (it marks them in dinfo)
 		noteHip(ctx, hipMemsetAsync(ctx->dinfo.p, 0, ndraws * sizeof(vgx_draw_info), s));
 		vgx_launch_flatten_serial(false, a, s);
@@ -2067,6 +2090,224 @@ int vgx_tessellate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 	if (dev_sizes || dev_status) {
 		hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status);
 	}
+	return launchStatus(ctx);
+}
+
+// ---- immediate mode: vgx_tessellate_immediate / vgx_reserve -------------------------------------------------------------
+// The heap of the single-pass flatten for a batch of V polyline vertices, `longV` of them in sub-paths longer than VGX_LONG_SUBPATH, `ncmd`
+// command instances: vgx_tessellate_count's formula (see there), with the lineTo-only layout's one slot per command
+static uint64_t immHeapBuild(const vgx_pathset* ps, uint64_t V, uint64_t ncmd, uint64_t longV)
+{
+	uint64_t h = V * 9 / 4 + 4 * longV + 2 * (uint64_t)VGX_BUILD_WAVES * VGX_BUILD_BLOCK;
+	if ((!ps || ps->thinStatic) && h < 2 * ncmd + 4096) { h = 2 * ncmd + 4096; }
+	return h;
+}
+
+// ... of k_flatten_inst's lane-private blocks (vgx_tessellate_count's formula; instLong = vertices in sub-paths longer than VGX_INST_LONG_SUBPATH)
+static uint64_t immHeapInst(const vgx_ctx* ctx, uint64_t V, uint64_t instLong)
+{
+	const uint64_t grown = (ctx->optInstBlock >= VGX_INST_BLOCK) ? V * 9 / 4 + 8 * instLong : V * 10;
+	return grown + (uint64_t)ctx->optInstWaves * 64 * ctx->optInstBlock + 4096;
+}
+
+// per-command scratch of the flatten kernels (+ the leaf overflow area of k_flatten_build), as vgx_tessellate_count sizes it
+static int immEnsureCmd(vgx_ctx* ctx, uint64_t ncmd)
+{
+	int st;
+	if ((st = ensure(ctx, ctx->cmdCnt, (ncmd + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->subFirst, (ncmd + 1) * sizeof(VgxSubRec))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->leafOverflow, (size_t)VGX_BUILD_WAVES * VGX_BUILD_OVERFLOW * 64 * 2 * sizeof(float))) != VGX_OK) { return st; }
+	ctx->caps.cmd_instances = ctx->cmdCnt.cap / sizeof(uint32_t) - 1;
+	{ const uint64_t c2 = ctx->subFirst.cap / sizeof(VgxSubRec) - 1; if (c2 < ctx->caps.cmd_instances) { ctx->caps.cmd_instances = c2; } }
+	return VGX_OK;
+}
+
+static int immInit(vgx_ctx* ctx)
+{
+	if (ctx->immHost) { return VGX_OK; }
+	HIPCHK(ctx, hipHostMalloc((void**)&ctx->immHost, sizeof(VgxTotals), hipHostMallocDefault));
+	const hipError_t e = hipEventCreateWithFlags(&ctx->immEv, hipEventDisableTiming);
+	if (e != hipSuccess) { (void)hipHostFree(ctx->immHost); ctx->immHost = nullptr; ctx->lastHipError = (int)e; return VGX_E_HIP; }
+	memset(ctx->immHost, 0, sizeof(VgxTotals));
+	ctx->immEvPending = false; ctx->immKnown = false; ctx->immLongKnown = false;
+	return VGX_OK;
+}
+
+// The mirror of the last immediate call, if its copy has landed (never waited for): what the batch was, and after VGX_E_GROWN the scratch it
+// needs -- grown here, with vgx_tessellate_count's formulas, the instanced flatten's heap included when its draws repeat a sequence of paths
+static int immConsume(vgx_ctx* ctx, const vgx_pathset* ps)
+{
+	if (!ctx->immEvPending || hipEventQuery(ctx->immEv) != hipSuccess) { return VGX_OK; }
+	ctx->immEvPending = false;
+	const VgxTotals& h = *ctx->immHost;
+	if (h.status != VGX_OK && h.status != VGX_E_NOSPACE && h.status != VGX_E_GROWN) { return VGX_OK; } // (no totals to learn from)
+	const bool same = ctx->immKnown && ctx->immTag == ctx->immPendTag;
+	uint32_t P = 0;
+	if (ctx->immPendDetect && h.inst_detect_inv != 0 && !h.inst_detect_bad) {
+		const unsigned long long p = ~0ull - h.inst_detect_inv;
+		if (p <= 0xFFFFFFFFull) { P = (uint32_t)p; }
+	}
+	if (ctx->immPendDetect || !same) { ctx->immPeriod = P; ctx->immDistinct = ctx->immPendDetect ? h.inst_distinct : 0; } else { P = ctx->immPeriod; }
+	ctx->immKnown = true; ctx->immTag = ctx->immPendTag;
+	ctx->immV = h.sizes.num_poly_vertices; ctx->immCmd = h.sizes.num_cmd_instances;
+	if (h.status != VGX_E_GROWN) {
+		if (!same) { ctx->immLongKnown = false; }
+		return VGX_OK;
+	}
+	ctx->immLong = h.imm_long_subpath_vertices; ctx->immInstLong = h.imm_inst_long_subpath_vertices; ctx->immLongKnown = true;
+	if (h.sizes.num_poly_vertices > 0xFFFFFFF0ull) { return VGX_OK; } // (VGX_E_RANGE territory: nothing sensible to grow to)
+	int st;
+	if ((st = immEnsureCmd(ctx, h.sizes.num_cmd_instances)) != VGX_OK) { return st; }
+	uint64_t heap = immHeapBuild(ps, h.sizes.num_poly_vertices, h.sizes.num_cmd_instances, h.imm_long_subpath_vertices);
+	const uint64_t n = ctx->immPendNDraws;
+	const bool reused = ctx->immDistinct != 0 && n < 0xFFFFFFFFull && n / ctx->immDistinct >= VGX_INST_MIN_INSTANCES; // (grouped mode)
+	if (ctx->optInst && ((P && n % P == 0 && n / P >= VGX_INST_MIN_INSTANCES) || reused)) {
+		const uint64_t hi = immHeapInst(ctx, h.sizes.num_poly_vertices, h.imm_inst_long_subpath_vertices);
+		if (hi > heap) { heap = hi; }
+	}
+	return ensureMeshBuffers(ctx, heap, h.sizes.num_subpaths, h.sizes.num_meshes);
+}
+
+int vgx_reserve(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals)
+{
+	if (!ctx || !totals) { // (before the context is touched)
+		return VGX_E_INVALID_ARG;
+	}
+	DeviceGuard guard(ctx);
+	if (totals->num_poly_vertices > 0xFFFFFFF0ull || totals->num_cmd_instances > 0xFFFFFFF0ull) { return VGX_E_RANGE; }
+	int st;
+	if ((st = immInit(ctx)) != VGX_OK) { return st; }
+	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
+	if ((st = immEnsureCmd(ctx, totals->num_cmd_instances)) != VGX_OK) { return st; }
+	// the long sub-paths are not known: every vertex counted as one of them (the heap then holds any batch within these totals)
+	const uint64_t V = totals->num_poly_vertices;
+	return ensureMeshBuffers(ctx, immHeapBuild(nullptr, V, totals->num_cmd_instances, V), totals->num_subpaths, totals->num_meshes);
+}
+
+int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out,
+                             vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+{
+	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx) { // (before the context is touched)
+		return VGX_E_INVALID_ARG;
+	}
+	DeviceGuard guard(ctx);
+	hipStream_t s = (hipStream_t)stream;
+	int st;
+	if ((st = immInit(ctx)) != VGX_OK) { return st; }
+	// counted state ends here (as with vgx_flatten): the _emit pairing, the template, the routes the last count chose
+	ctx->lastStage = 0; ctx->tmplOn = false; ctx->f1Route = false;
+	ctx->instPeriod = 0; ctx->instGrouped = 0; ctx->instClasses = 1; ctx->instPermOn = 0;
+	// (1) the last immediate call's need, when it has reached the mirror; (2) the tables every route needs (a fresh context gets small ones:
+	// its first call ends with VGX_E_GROWN and the exact need)
+	if ((st = immConsume(ctx, ps)) != VGX_OK) { return st; }
+	// Every bound this call trusts is recomputed from the buffers as they stand (allocating only what is missing): whatever another entry point
+	// left in ctx->caps -- a count lifts them for its sizing passes -- never decides how far a kernel of this call may write
+	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
+	if ((st = immEnsureCmd(ctx, 4096)) != VGX_OK) { return st; }
+	if ((st = ensureMeshBuffers(ctx, 4096, 1024, 1024)) != VGX_OK) { return st; }
+	markBegin(ctx, s);
+	const uint64_t tag = ps->gen * 0x9E3779B97F4A7C15ull + ndraws;
+	const bool known = ctx->immKnown && ctx->immTag == tag;
+	VgxTotals* T = (VgxTotals*)ctx->totals.p;
+	VgxCaps outCaps = ctx->caps;
+	outCaps.vertices = out->cap_vertices;
+	outCaps.indices = out->cap_indices;
+	if (out->meshes && out->cap_meshes < outCaps.meshes) { outCaps.meshes = out->cap_meshes; }
+	bool detect = false;
+	if (ndraws <= VGX_SMALL_DRAWS && !ctx->optNoSmall) {
+		// frame-sized: vgx_tessellate's five launches; the scan over the draws flags a batch that outgrew the context's tables
+		OpCmdPrefix opC;
+		opC.draws = draws; opC.pathCmdBegin = ps->dev.path_cmd_begin; opC.npaths = ps->dev.npaths; opC.ndraws = ndraws;
+		opC.prefix = (uint64_t*)ctx->cmdPrefix.p; opC.totals = T; opC.cap = ctx->caps.cmd_instances;
+		opC.period = 0; opC.pathSubBegin = ps->dev.path_sub_begin; opC.subPrefix = (uint64_t*)ctx->subPrefix.p;
+		mark(ctx, s, "route_frame"); // (a stage of no length: which route the call took, for the profile)
+		vgx_launch_small_front(&opC, (vgx_draw_info*)ctx->dinfo.p, s);
+		mark(ctx, s, "small_front");
+		VgxFlattenArgs f = flattenArgs(ctx, ps, draws, ndraws, 1);
+		f.build_mode = 1;
+		f.mprep = (VgxMeshPrep*)ctx->mprep.p;
+		vgx_launch_flatten_build(f, ctx->optBuildWaves, s, false);
+		mark(ctx, s, "flatten_build");
+		VgxStrokeArgs sa;
+		sa.draws = draws; sa.poly = (const float*)ctx->poly.p; sa.mdesc = (const VgxMeshDesc*)ctx->mdesc.p;
+		sa.elem_prefix = nullptr; sa.elem_prefix_fill = (const uint64_t*)ctx->elemPrefix.p; sa.elem_prefix_stroke = (const uint64_t*)ctx->elemPrefixS.p;
+		sa.mprep = (VgxMeshPrep*)ctx->mprep.p; sa.mtab = (vgx_mesh*)ctx->mtab.p;
+		sa.pos = nullptr; sa.color = nullptr; sa.idx = nullptr; sa.meshes_out = nullptr; sa.mesh_base = nullptr;
+		sa.totals = T; sa.caps = outCaps; sa.tile_mode = 0; sa.no_long = 1;
+		OpDrawInfo opD;
+		opD.dinfo = (vgx_draw_info*)ctx->dinfo.p; opD.ndraws = ndraws; opD.totals = T; opD.caps = ctx->caps; opD.keepPolyBase = 1; opD.markScratch = 1;
+		OpMeshAll opM;
+		opM.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; opM.mtab = (vgx_mesh*)ctx->mtab.p; opM.meshesOut = out->meshes;
+		opM.prefixFill = (uint64_t*)ctx->elemPrefix.p; opM.prefixStroke = (uint64_t*)ctx->elemPrefixS.p;
+		opM.totals = T; opM.caps = outCaps; opM.checkCaps = 1; opM.fixedSize = 0; opM.fixedCount = 0;
+		vgx_launch_small_middle(f, sa, &opD, &opM, nullptr, nullptr, s);
+		mark(ctx, s, "small_middle");
+		if ((st = runStrokeEmit(ctx, draws, out, s, nullptr, true)) != VGX_OK) { return st; }
+		vgx_launch_imm_size(ps->dev, draws, ndraws, T, 0, true, dev_sizes, dev_status, s); // (+ the verdict)
+		mark(ctx, s, "imm_size");
+	} else {
+		// Routes from what the last immediate call on this (path set, number of draws) found, with vgx_tessellate_count's rules: draws that
+		// repeat a sequence of paths -> k_flatten_inst (re-checked on the device: k_flatten_build takes over when they stop repeating), when
+		// the heap holds its lane-private blocks; long curves -> the one-walk flatten; else k_flatten_build
+		uint32_t P = 0;
+		if (known && ctx->immPeriod && ctx->optInst && ndraws % ctx->immPeriod == 0 && ndraws / ctx->immPeriod >= VGX_INST_MIN_INSTANCES
+			&& immHeapInst(ctx, ctx->immV, ctx->immLongKnown ? ctx->immInstLong : ctx->immV) <= ctx->caps.poly_vertices) {
+			P = ctx->immPeriod;
+		}
+		// paths reused without a period (>= 32 draws per used path): grouped mode, the draws sorted by path on the device every call
+		if (!P && known && ctx->optInst && ctx->immDistinct != 0 && ndraws < 0xFFFFFFFFull && ndraws / ctx->immDistinct >= VGX_INST_MIN_INSTANCES
+			&& immHeapInst(ctx, ctx->immV, ctx->immLongKnown ? ctx->immInstLong : ctx->immV) <= ctx->caps.poly_vertices) {
+			if ((st = ensureInstGroup(ctx, ps->dev.npaths, 1, ndraws, true)) != VGX_OK) { return st; }
+			ctx->instGrouped = 1;
+			if (!instGroupedFor(ctx, ps, ndraws)) { ctx->instGrouped = 0; }
+		}
+		bool oneWalk = false;
+		if (!P && !ctx->instGrouped && known && ctx->optTessFlat1 && !(ps->thinStatic && ctx->optThinStatic) && ctx->immCmd != 0
+			&& (ctx->optTessFlat1 == 2 || ctx->immV >= 10 * ctx->immCmd)) {
+			int cap = 1664; uint32_t segMax = 64; // (as vgx_tessellate_count picks them)
+			const double perChunk = (double)ctx->immV / (double)ctx->immCmd * 64.0;
+			if (perChunk <= 800.0) { cap = 1024; }
+			else if (perChunk > 1500.0) {
+				cap = 3072;
+				const double m = 0.8 * 3072.0 / (perChunk / 64.0);
+				segMax = m >= 64.0 ? 64u : (m >= 32.0 ? 32u : (m >= 16.0 ? 16u : 8u));
+			}
+			if (ctx->optF1Cap) { cap = ctx->optF1Cap; }
+			if (ctx->optF1Seg) { segMax = (uint32_t)ctx->optF1Seg; }
+			const uint64_t segBound = f1RouteSegmentsFor(ps, ndraws, segMax);
+			if (segBound <= (1ull << 24)) {
+				if ((st = ensure(ctx, ctx->f1SegDraw, (segBound + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
+				if ((st = ensure(ctx, ctx->f1Segs, (segBound + segBound / 64 + 2) * sizeof(VgxF1Seg))) != VGX_OK) { return st; }
+				ctx->f1RoutePs = ps; ctx->f1RoutePsGen = ps->gen; ctx->f1RouteCap = cap; ctx->f1RouteSegMax = segMax; ctx->f1RouteSegBound = segBound;
+				oneWalk = true;
+			}
+		}
+		ctx->instPeriod = P;
+		mark(ctx, s, P ? "route_periodic" : (ctx->instGrouped ? "route_grouped" : (oneWalk ? "route_one_walk" : "route_build"))); // (no length)
+		if (oneWalk) {
+			runFlattenOneWalk(ctx, ps, draws, ndraws, s);
+		} else {
+			runCmdPrefix(ctx, ps, draws, ndraws, s, P);
+			runFlattenBuild(ctx, ps, draws, ndraws, s);
+		}
+		detect = !known && ctx->optInst; // the period of the paths and how many of them the draws use, for the next call on this batch
+		if (detect) {
+			vgx_launch_inst_detect(draws, ndraws, T, s);
+			if ((st = ensureInstGroup(ctx, ps->dev.npaths, 1, ndraws, false)) != VGX_OK) { return st; }
+			vgx_launch_inst_group(draws, ndraws, ps->dev.npaths, 1, (uint32_t*)ctx->instHist.p, nullptr, nullptr, (uint64_t*)ctx->instStart.p, (uint64_t*)ctx->instTaskStart.p,
+				nullptr, 0, nullptr, T, ctx->partial.p, s);
+		}
+		// the flatten stage checks the context's tables only: a VGX_E_NOSPACE here is the scratch's
+		vgx_launch_imm_size(ps->dev, draws, ndraws, T, 1, false, nullptr, nullptr, s);
+		mark(ctx, s, "imm_size");
+		runStrokeCount(ctx, draws, outCaps, 1, s, nullptr, true, out->meshes);
+		if ((st = runStrokeEmit(ctx, draws, out, s, nullptr, true)) != VGX_OK) { return st; }
+		vgx_launch_imm_publish(T, dev_sizes, dev_status, s);
+	}
+	// the totals to the mirror, for the next call (never waited for)
+	noteHip(ctx, hipMemcpyAsync(ctx->immHost, T, sizeof(VgxTotals), hipMemcpyDeviceToHost, s));
+	noteHip(ctx, hipEventRecord(ctx->immEv, s));
+	ctx->immEvPending = true; ctx->immPendTag = tag; ctx->immPendNDraws = ndraws; ctx->immPendDetect = detect;
 	return launchStatus(ctx);
 }
 

@@ -16,6 +16,7 @@ struct VgxF1Args
 	VgxF1Seg* grps;       // [segments / 64 + 1] ... of the groups of 64 tickets
 	uint64_t cap_poly;    // the caller's capacities (vertices / sub-path records)
 	uint64_t cap_subs;
+	uint64_t cap_meshes;  // mesh descriptors / tables of vgx_tessellate's one-walk route (vgx_flatten: ~0, it writes none)
 	int pass;             // 0: the normal run; 1: the second run of a batch in which the first one found degenerate draws
 	int read_flags;       // dinfo[d].flags may already mark serial draws
 	int has_empty;        // the path set has paths without commands: their draws' records are written by the neighbours

@@ -873,7 +873,7 @@ __global__ __launch_bounds__(VGX_WAVE, (CAP > 2048 ? 1 : F1_MIN_WAVES_PER_EU)) v
 							F1_FLUSH();
 							return;
 						}
-						if (endV > X.cap_poly || endS > X.cap_subs) {
+						if (endV > X.cap_poly || endS > X.cap_subs || endM > X.cap_meshes) {
 							writeOk = false;
 							if (lane == 0) { atomicCAS(&T->status, (uint32_t)VGX_OK, (uint32_t)VGX_E_NOSPACE); }
 						}
@@ -932,7 +932,7 @@ __global__ __launch_bounds__(VGX_WAVE, (CAP > 2048 ? 1 : F1_MIN_WAVES_PER_EU)) v
 					F1_FLUSH();
 					return;
 				}
-				if (endV > X.cap_poly || endS > X.cap_subs) {
+				if (endV > X.cap_poly || endS > X.cap_subs || endM > X.cap_meshes) {
 					writeOk = false;
 					if (lane == 0) { atomicCAS(&T->status, (uint32_t)VGX_OK, (uint32_t)VGX_E_NOSPACE); }
 				}

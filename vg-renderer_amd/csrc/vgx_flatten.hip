@@ -1106,6 +1106,101 @@ __global__ __launch_bounds__(256) void k_flatten_serial(VgxFlattenArgs A)
 	flatten_serial_body<EMIT, XFORM>(A, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, (uint64_t)gridDim.x * blockDim.x);
 }
 
+// ---- vgx_tessellate_immediate: what a batch needs when it outgrew the context's scratch ---------------------------------------
+// Launched behind the flatten stage of every immediate call; exits at once unless the stage ran out of context scratch:
+// from_status = any VGX_E_NOSPACE in the status word (the large-batch routes launch it right behind their flatten stage, which checks
+// the context's tables only), else the flag the scan over the draws set (frame-sized route: its one kernel also checks the caller's
+// buffers). Then every draw goes through the exact serial builder in count mode -- PathSim, the reference's own algorithm: no
+// per-command scratch, no heap -- and the inputs of vgx_tessellate_count's sizing formulas land in VgxTotals::imm_*. Sub-paths longer
+// than VGX_LONG_SUBPATH / VGX_INST_LONG_SUBPATH are summed over every draw (the count pass skips the serial ones: an upper bound).
+__device__ __forceinline__ unsigned long long imm_wave_sum(unsigned long long v)
+{
+	for (int o = VGX_WAVE / 2; o > 0; o >>= 1) { v += __shfl_xor(v, o); }
+	return v;
+}
+
+__device__ __forceinline__ void imm_sub_done(uint32_t n, unsigned long long& lg, unsigned long long& ilg)
+{
+	if (n > VGX_LONG_SUBPATH) { lg += n; }
+	if (n > VGX_INST_LONG_SUBPATH) { ilg += n; }
+}
+
+// The verdict of an immediate call: scratch too small -> VGX_E_GROWN with the flatten totals k_imm_size counted (output totals that were
+// never reached: 0); otherwise what the pipeline left (VGX_OK, VGX_E_NOSPACE with the exact output totals, ...). Also into the totals
+// themselves, which the host copies to its mirror behind the call. Words other workgroups added atomically are read with atomic loads.
+__device__ __forceinline__ unsigned long long imm_load(const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ void imm_publish(VgxTotals* T, vgx_sizes* devSizes, uint32_t* devStatus)
+{
+	if (__hip_atomic_load(&T->scratch_short, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+		// (a batch beyond 2^32 - 16 polyline vertices cannot be tessellated in one call, whatever the scratch: VGX_E_RANGE, as the count says)
+		const bool range = imm_load(&T->imm_poly_vertices) > 0xFFFFFFF0ull || T->sizes.num_cmd_instances > 0xFFFFFFF0ull;
+		vgx_sizes z;
+		z.num_cmd_instances = T->sizes.num_cmd_instances; // (the scan over the draws' commands always completes)
+		z.num_poly_vertices = imm_load(&T->imm_poly_vertices); z.num_subpaths = imm_load(&T->imm_subpaths); z.num_meshes = imm_load(&T->imm_meshes);
+		z.num_vertices = 0; z.num_indices = 0; z.num_serial_draws = 0; z.num_elements = 0; z.num_fill_elements = 0; z.num_drawcmds = 0;
+		T->sizes = z;
+		T->status = range ? VGX_E_RANGE : VGX_E_GROWN;
+	}
+	const uint32_t st = __hip_atomic_load(&T->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	if (devSizes) { *devSizes = T->sizes; }
+	if (devStatus) { *devStatus = st; }
+}
+
+__global__ __launch_bounds__(256) void k_imm_size(VgxPathSetDev ps, const vgx_draw* draws, uint64_t ndraws, VgxTotals* T, int fromStatus, int publish,
+                                                  vgx_sizes* devSizes, uint32_t* devStatus)
+{
+	const uint32_t st = __hip_atomic_load(&T->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	const uint32_t flagged = __hip_atomic_load(&T->scratch_short, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	if (!flagged && !(fromStatus && st == (uint32_t)VGX_E_NOSPACE)) { // the batch fitted the context (uniform: nothing else runs on the stream)
+		if (publish && blockIdx.x == 0 && threadIdx.x == 0) { imm_publish(T, devSizes, devStatus); }
+		return;
+	}
+	if (!flagged && blockIdx.x == 0 && threadIdx.x == 0) { __hip_atomic_store(&T->scratch_short, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+	unsigned long long v = 0, sp = 0, m = 0, lg = 0, ilg = 0;
+	PrivStack stack;
+	for (uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; d < ndraws; d += (uint64_t)gridDim.x * blockDim.x) {
+		const vgx_draw* dr = draws + d;
+		const uint32_t path = dr->path;
+		if (path >= ps.npaths) { continue; }
+		const uint32_t pc0 = ps.path_cmd_begin[path], pc1 = ps.path_cmd_begin[path + 1];
+		PathSim<false, false> sim;
+		sim.scale = dr->scale; sim.tol = dr->tess_tol; sim.mtx = dr->mtx; sim.poly = nullptr;
+		sim.drawIndex = (uint32_t)d; sim.fillFlags = dr->fill_flags; sim.strokeFlags = dr->stroke_flags; sim.draw = dr;
+		sim.polyBase = 0; sim.subs = nullptr; sim.subBase = 0; sim.mdesc = nullptr; sim.mprep = nullptr; sim.mtab = nullptr; sim.meshBase = 0;
+		sim.numFillTotal = 0; sim.limit = 0;
+		sim.init();
+		// PathSim::run, command by command: a sub-path ends where the next one opens (every writer opens it with moveTo, whose endSub
+		// comes first) or at the end of the draw
+		for (uint32_t c = pc0; c < pc1; ++c) {
+			const uint32_t subs0 = sim.nsubs, n0 = sim.spN;
+			sim.step(ps, c, stack);
+			if (sim.nsubs != subs0 && subs0 != 0) { imm_sub_done(n0, lg, ilg); }
+		}
+		sim.endSub();
+		if (sim.nsubs != 0) { imm_sub_done(sim.spN, lg, ilg); }
+		v += sim.nverts; sp += sim.nsubs; m += sim.nfill + sim.nstroke;
+	}
+	v = imm_wave_sum(v); sp = imm_wave_sum(sp); m = imm_wave_sum(m); lg = imm_wave_sum(lg); ilg = imm_wave_sum(ilg);
+	if ((threadIdx.x & (VGX_WAVE - 1)) == 0) {
+		if (v) { atomicAdd(&T->imm_poly_vertices, v); }
+		if (sp) { atomicAdd(&T->imm_subpaths, sp); }
+		if (m) { atomicAdd(&T->imm_meshes, m); }
+		if (lg) { atomicAdd(&T->imm_long_subpath_vertices, lg); }
+		if (ilg) { atomicAdd(&T->imm_inst_long_subpath_vertices, ilg); }
+	}
+	if (!publish) { return; }
+	// the last workgroup to finish publishes (its waves' sums are in: the barrier; every other workgroup's: the counter)
+	__threadfence();
+	__syncthreads();
+	if (threadIdx.x == 0 && atomicAdd(&T->imm_blocks_done, 1u) == gridDim.x - 1) {
+		__threadfence();
+		imm_publish(T, devSizes, devStatus);
+	}
+}
+
+__global__ void k_imm_publish(VgxTotals* T, vgx_sizes* devSizes, uint32_t* devStatus) { imm_publish(T, devSizes, devStatus); }
+
 // ------------------------------------------------------------------------------------------------
 // Frame-sized batches (at most VGX_SMALL_DRAWS draws: one vg-renderer frame is a few hundred paths) are bound by the
 // number of DEPENDENT launches, ~7 us each on this platform whether launched or graph-replayed: 17 of them made a
@@ -1207,6 +1302,19 @@ void vgx_launch_small_middle(const VgxFlattenArgs& f, const VgxStrokeArgs& st, c
 	VgxSmallArgs k;
 	k.F = f; k.S = st; k.opDraws = *(const OpDrawInfo*)opDraws; k.opMeshes = *(const OpMeshAll*)opMeshes; k.dev_sizes = devSizes; k.dev_status = devStatus;
 	hipLaunchKernelGGL(k_small_middle, dim3(1), dim3(VGX_SMALL_THREADS), 0, s, k);
+}
+
+void vgx_launch_imm_size(const VgxPathSetDev& ps, const vgx_draw* draws, uint64_t ndraws, VgxTotals* totals, int fromStatus, bool publish, vgx_sizes* devSizes, uint32_t* devStatus, hipStream_t s)
+{
+	uint64_t blocks = (ndraws + 255) / 256; // (one draw per thread up to 2048 workgroups: the exit-at-once launch stays small for frame-sized batches)
+	if (blocks > 2048) { blocks = 2048; }
+	if (blocks == 0) { blocks = 1; }
+	hipLaunchKernelGGL(k_imm_size, dim3((unsigned)blocks), dim3(256), 0, s, ps, draws, ndraws, totals, fromStatus, publish ? 1 : 0, devSizes, devStatus);
+}
+
+void vgx_launch_imm_publish(VgxTotals* totals, vgx_sizes* devSizes, uint32_t* devStatus, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_imm_publish, dim3(1), dim3(1), 0, s, totals, devSizes, devStatus);
 }
 
 void vgx_launch_flatten_build(const VgxFlattenArgs& a, int waves, hipStream_t s, bool serialCount)

@@ -236,6 +236,11 @@ struct VgxStrokeArgs;
 void vgx_launch_small_front(const void* opCmdPrefix, vgx_draw_info* dinfo, hipStream_t s);
 void vgx_launch_small_middle(const VgxFlattenArgs& f, const VgxStrokeArgs& st, const void* opDraws, const void* opMeshes, vgx_sizes* devSizes, uint32_t* devStatus, hipStream_t s);
 void vgx_launch_flatten_gather(const VgxFlattenArgs& a, hipStream_t s);  // after the draw scan: ordered mesh descriptors
+// vgx_tessellate_immediate (vgx_flatten.hip): the sizing pass behind the flatten stage (exits at once unless the batch outgrew the
+// context's scratch; with `publish` it ends the call: the verdict as vgx_launch_imm_publish) and the verdict (VGX_E_GROWN / what the
+// pipeline left) into dev_sizes / dev_status and the totals
+void vgx_launch_imm_size(const VgxPathSetDev& ps, const vgx_draw* draws, uint64_t ndraws, VgxTotals* totals, int fromStatus, bool publish, vgx_sizes* devSizes, uint32_t* devStatus, hipStream_t s);
+void vgx_launch_imm_publish(VgxTotals* totals, vgx_sizes* devSizes, uint32_t* devStatus, hipStream_t s);
 void vgx_launch_flatten_gather_ordered(const VgxFlattenArgs& a, hipStream_t s); // vgx_tessellate's one-walk route: mesh descriptors from k_flat1's ordered records
 #ifndef VGX_BUILD_WAVES
 #define VGX_BUILD_WAVES 4096

@@ -144,6 +144,11 @@ struct VgxTotals
 	unsigned long long flat_ticket;      // vgx_flatten: next segment (ticket order = output order)
 	unsigned long long flat_serial_draws;// vgx_flatten: draws that went through the exact serial builder
 	unsigned long long flat_tag;         // vgx_flatten: the batch these totals belong to (VgxF1Args::tag)
+	// vgx_tessellate_immediate: the batch outgrew a scratch table of the context (the flatten stage stopped with VGX_E_NOSPACE before the
+	// caller's buffers were looked at), and what it needs -- counted by k_imm_size with the exact builder, the inputs of the count formulas
+	uint32_t scratch_short;
+	uint32_t imm_blocks_done;            // k_imm_size: workgroups that have added their sums (the last one publishes)
+	unsigned long long imm_poly_vertices, imm_subpaths, imm_meshes, imm_long_subpath_vertices, imm_inst_long_subpath_vertices;
 	// diagnostics of the first failure (vgx_get_failure_info)
 	uint32_t fail_reason;  // VGX_FAIL_*
 	uint32_t fail_aux;

@@ -351,25 +351,29 @@ struct PathSim
 		}
 	}
 	// a whole draw, command after command (serial path)
+	// one command of the path set
+	template<class STACK>
+	VGX_HDM void step(const VgxPathSetDev& ps, uint32_t c, STACK& st)
+	{
+		const float* a = ps.args + ps.cmd_arg_off[c];
+		const uint32_t na = ps.cmd_arg_off[c + 1] - ps.cmd_arg_off[c];
+		const uint32_t type = ps.cmd_type[c];
+		switch (type) {
+		case VGX_CMD_MOVE_TO: moveTo(a[0], a[1]); break;
+		case VGX_CMD_LINE_TO: lineTo(a[0], a[1]); break;
+		case VGX_CMD_CUBIC_TO: cubicTo(a[0], a[1], a[2], a[3], a[4], a[5], st); break;
+		case VGX_CMD_QUAD_TO: quadTo(a[0], a[1], a[2], a[3], st); break;
+		case VGX_CMD_CLOSE: close(); break;
+		case VGX_CMD_ARC_TO: arcTo(a[0], a[1], a[2], a[3], a[4]); break;
+		case VGX_CMD_ARC: arc(a[0], a[1], a[2], a[3], a[4], a[5] != 0.0f); break;
+		case VGX_CMD_POLYLINE: polyline(a, na >> 1); break;
+		default: shape(type, a); break;
+		}
+	}
 	template<class STACK>
 	VGX_HDM void run(const VgxPathSetDev& ps, uint32_t c0, uint32_t c1, STACK& st)
 	{
-		for (uint32_t c = c0; c < c1; ++c) {
-			const float* a = ps.args + ps.cmd_arg_off[c];
-			const uint32_t na = ps.cmd_arg_off[c + 1] - ps.cmd_arg_off[c];
-			const uint32_t type = ps.cmd_type[c];
-			switch (type) {
-			case VGX_CMD_MOVE_TO: moveTo(a[0], a[1]); break;
-			case VGX_CMD_LINE_TO: lineTo(a[0], a[1]); break;
-			case VGX_CMD_CUBIC_TO: cubicTo(a[0], a[1], a[2], a[3], a[4], a[5], st); break;
-			case VGX_CMD_QUAD_TO: quadTo(a[0], a[1], a[2], a[3], st); break;
-			case VGX_CMD_CLOSE: close(); break;
-			case VGX_CMD_ARC_TO: arcTo(a[0], a[1], a[2], a[3], a[4]); break;
-			case VGX_CMD_ARC: arc(a[0], a[1], a[2], a[3], a[4], a[5] != 0.0f); break;
-			case VGX_CMD_POLYLINE: polyline(a, na >> 1); break;
-			default: shape(type, a); break;
-			}
-		}
+		for (uint32_t c = c0; c < c1; ++c) { step(ps, c, st); }
 		endSub();
 	}
 };

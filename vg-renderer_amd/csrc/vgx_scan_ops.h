@@ -90,6 +90,8 @@ struct OpDrawInfo // per-draw polyline / sub-path / mesh counts -> first_* field
 	VgxTotals* totals;
 	VgxCaps caps;
 	int keepPolyBase; // BUILD mode: first_poly_vertex already holds the draw's heap position
+	int markScratch = 0; // vgx_tessellate_immediate: a batch that outgrew the context's tables (here, or earlier in the flatten stage:
+	                     // every VGX_E_NOSPACE in front of this scan is one) sets VgxTotals::scratch_short
 	__device__ uint64_t size() const { return totals->status == VGX_OK ? ndraws : 0; }
 	__device__ Sum3 load(uint64_t i) const
 	{
@@ -110,7 +112,9 @@ struct OpDrawInfo // per-draw polyline / sub-path / mesh counts -> first_* field
 		totals->sizes.num_subpaths = t.b;
 		totals->sizes.num_meshes = t.c;
 		totals->sizes.num_serial_draws = t.d;
-		if ((!keepPolyBase && t.a > caps.poly_vertices) || t.b > caps.subpaths || t.c > caps.meshes) { set_status(totals, VGX_E_NOSPACE); }
+		const bool over = (!keepPolyBase && t.a > caps.poly_vertices) || t.b > caps.subpaths || t.c > caps.meshes;
+		if (over) { set_status(totals, VGX_E_NOSPACE); }
+		if (markScratch && (over || __hip_atomic_load(&totals->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)VGX_E_NOSPACE)) { totals->scratch_short = 1u; }
 	}
 };
 

@@ -74,6 +74,16 @@ class Context:
     def scratch_bytes(self):
         return int(lib().vgx_scratch_bytes(self._h))
 
+    def reserve(self, ndraws, sizes):
+        """vgx_reserve: size the scratch for batches up to `sizes` (a dict or capi.Sizes: num_cmd_instances, num_poly_vertices,
+        num_subpaths, num_meshes) of `ndraws` draws, so that such a batch takes one tessellate_immediate call."""
+        if isinstance(sizes, dict):
+            z = capi.Sizes()
+            for k in ("num_cmd_instances", "num_poly_vertices", "num_subpaths", "num_meshes"):
+                setattr(z, k, int(sizes.get(k, 0)))
+            sizes = z
+        _check(lib().vgx_reserve(self._h, int(ndraws), C.byref(sizes)), "vgx_reserve")
+
     def set_profiling(self, on):
         _check(lib().vgx_set_profiling(self._h, 1 if on else 0), "vgx_set_profiling")
 
@@ -334,6 +344,55 @@ def tessellate_async(ctx, pset, draws_dev, ndraws, bufs):
     out = bufs.out_struct()
     _check(lib().vgx_tessellate(ctx.handle, pset.handle, draws_dev.data_ptr(), ndraws, C.byref(out),
                                 bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_tessellate")
+
+
+def tessellate_immediate(ctx, pset, draws_dev, ndraws, bufs):
+    """vgx_tessellate_immediate: a batch the context need never have counted, asynchronous like tessellate_async. The verdict
+    lands in bufs.dev_status (VGX_OK / VGX_E_NOSPACE: grow the buffers to bufs.dev_sizes / VGX_E_GROWN: call again), the
+    totals in bufs.dev_sizes."""
+    out = bufs.out_struct()
+    _check(lib().vgx_tessellate_immediate(ctx.handle, pset.handle, draws_dev.data_ptr(), ndraws, C.byref(out),
+                                          bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_tessellate_immediate")
+
+
+class ImmediateResult:
+    """What tessellate_grow ends with: the status of every call (the last one VGX_OK) and the batch's totals."""
+
+    def __init__(self, statuses, sizes):
+        self.statuses = statuses
+        self.sizes = sizes
+
+    @property
+    def calls(self):
+        return len(self.statuses)
+
+
+def _grown(cap, need, growth):
+    return cap if need <= cap else max(int(need), int(cap * growth))
+
+
+def tessellate_grow(ctx, pset, draws_dev, ndraws, bufs=None, growth=1.5, max_calls=3):
+    """The immediate-mode loop: tessellate_immediate until VGX_OK. After VGX_E_NOSPACE the buffers grow to the totals in
+    dev_sizes, by at least `growth` times (as the reference's allocIndices / allocVertices grow theirs, src/vg.cpp:5321-5357);
+    after VGX_E_GROWN the context grows its own scratch at the next call. Synchronises the stream once per call (to read the
+    verdict). Returns (ImmediateResult, buffers) -- the buffers may be new ones."""
+    if bufs is None:
+        bufs = MeshBuffers(draws_dev.device, 1024, 1024, 64)
+    statuses = []
+    for _ in range(max_calls):
+        tessellate_immediate(ctx, pset, draws_dev, ndraws, bufs)
+        st = int(bufs.dev_status.item())  # (synchronises)
+        statuses.append(st)
+        sizes = capi.Sizes.from_buffer_copy(bufs.dev_sizes.cpu().numpy().tobytes()).as_dict()
+        if st == capi.VGX_OK:
+            return ImmediateResult(statuses, sizes), bufs
+        if st == capi.VGX_E_NOSPACE:
+            nv, ni, nm = bufs.cap
+            bufs = MeshBuffers(draws_dev.device, _grown(nv, sizes["num_vertices"], growth), _grown(ni, sizes["num_indices"], growth),
+                               _grown(nm, sizes["num_meshes"], growth))
+        elif st != capi.VGX_E_GROWN:
+            raise VgxError(st, "vgx_tessellate_immediate (device)")
+    raise VgxError(statuses[-1], "tessellate_grow: no VGX_OK within %d calls (%s)" % (max_calls, statuses))
 
 
 def tessellate(ctx, pset, draws_dev, ndraws, to_host=True):
