@@ -98,7 +98,7 @@ struct vgx_ctx
 	DevBuf partBounds;                   // vgx_partition: [nparts + 1] bounds + [nparts] weights
 	struct VgxRccl* rccl;                // RCCL entry points, bound at the first vgx_gather* call
 	// options, read from the environment ONCE at vgx_create (tuning / testing knobs)
-	int optTwoPass, optBuildWaves, optPoolWalk, optNoSmall, optConcurrentEmit;
+	int optTwoPass, optBuildWaves, optPoolWalk, optNoSmall;
 	int optTessFlat1;                    // VGX_TESS_FLAT1: 1 (default) = vgx_tessellate flattens batches of long curves with the one-walk kernel (k_flat1), 0 = never, 2 = every eligible batch
 	// vgx_tessellate's one-walk route, decided and sized by the last vgx_tessellate_count (f1Route*): the path set it is for, the kernel
 	// instance / bucket size, the segments the look-back tables hold
@@ -149,8 +149,9 @@ struct vgx_ctx
 	uint64_t tmplRelemWords;             // several classes: table words of the whole batch (sum over the instances of their class's Round-join elements)
 	DevBuf tmplTrmesh, tmplTmsz;         // template: the Round-join meshes (mesh, first element among the Round-join elements); per mesh its sizes (VgxTmplArgs::tmsz)
 	DevBuf tmplRsz, tmplRelem, tmplMplace, tmplItot, tmplIplace; // the per-step tables of such a template (VgxTmplArgs)
-	hipStream_t sideStream; hipEvent_t forkEv, joinEv; // optConcurrentEmit only
-	VgxCaps caps; // element capacities matching the buffers above
+	// element capacities of the buffers above. Never lifted: only ensureMeshBuffers and ensureCmdScratch write it, from the buffers'
+	// capacities, so every launch may trust it; a launch that needs other bounds (a sizing pass, the caller's capacities) is given them
+	VgxCaps caps;
 	uint64_t capDraws;
 	VgxTotals* hostTotals; // pinned
 	// vgx_tessellate_immediate: pinned mirror of the last immediate call's totals, the event behind its copy (the next call reads the mirror
@@ -459,13 +460,31 @@ VgxFlattenArgs flattenArgs(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* 
 	return a;
 }
 
+// Can the instanced kernel assume that `ndraws` draws repeat a sequence of P paths (enough whole instances of it)?
+bool periodUsable(const vgx_ctx* ctx, uint64_t P, uint64_t ndraws)
+{
+	return P && ctx->optInst && ndraws % P == 0 && ndraws / P >= VGX_INST_MIN_INSTANCES;
+}
+
+// Do `ndraws` draws over `distinct` different paths reuse them (>= VGX_INST_MIN_INSTANCES draws per used path on average)? Then grouped
+// mode sorts them by path when they do not repeat one sequence.
+bool pathsReused(const vgx_ctx* ctx, uint64_t ndraws, uint64_t distinct)
+{
+	return ctx->optInst && distinct != 0 && ndraws < 0xFFFFFFFFull && ndraws / distinct >= VGX_INST_MIN_INSTANCES;
+}
+
 // Period the instanced kernel may assume for a batch of `ndraws` draws (0: command-parallel kernel). The device checks
 // draws[i].path == draws[i % period].path again on every call (OpCmdPrefix).
 uint32_t instPeriodFor(const vgx_ctx* ctx, uint64_t ndraws)
 {
-	const uint32_t P = ctx->instPeriod;
-	if (!P || !ctx->optInst || ndraws % P != 0 || ndraws / P < VGX_INST_MIN_INSTANCES) { return 0; }
-	return P;
+	return periodUsable(ctx, ctx->instPeriod, ndraws) ? ctx->instPeriod : 0;
+}
+
+// The flatten modes and the template the last count chose no longer hold
+void forgetRoutes(vgx_ctx* ctx)
+{
+	ctx->instPeriod = 0; ctx->instGrouped = 0; ctx->instClasses = 1; ctx->instPermOn = 0;
+	ctx->tmplOn = false;
 }
 
 // Grouped mode for this call: the count pass chose it and the sort buffers hold a batch of this size over this path set.
@@ -535,28 +554,35 @@ int readTotals(vgx_ctx* ctx, hipStream_t s)
 	return VGX_OK;
 }
 
-// stage 1: command-instance prefix
-void runCmdPrefix(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s, uint32_t instPeriod = 0)
+// the command-instance scan; `cmdCap`: the command instances the per-command scratch holds for this launch (~0: not checked)
+OpCmdPrefix cmdPrefixOp(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, uint64_t cmdCap, uint32_t instPeriod)
 {
-	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
 	OpCmdPrefix op;
 	op.draws = draws; op.pathCmdBegin = ps->dev.path_cmd_begin; op.npaths = ps->dev.npaths; op.ndraws = ndraws;
-	op.prefix = (uint64_t*)ctx->cmdPrefix.p; op.totals = (VgxTotals*)ctx->totals.p; op.cap = ctx->caps.cmd_instances;
+	op.prefix = (uint64_t*)ctx->cmdPrefix.p; op.totals = (VgxTotals*)ctx->totals.p; op.cap = cmdCap;
 	op.pathSubBegin = ps->dev.path_sub_begin; op.subPrefix = (uint64_t*)ctx->subPrefix.p;
 	op.period = instPeriod;
-	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, ndraws);
+	return op;
+}
+
+// stage 1: command-instance prefix
+void runCmdPrefix(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, uint64_t cmdCap, hipStream_t s, uint32_t instPeriod = 0)
+{
+	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
+	vgx_device_scan(cmdPrefixOp(ctx, ps, draws, ndraws, cmdCap, instPeriod), (Sum3*)ctx->partial.p, s, ndraws);
 	mark(ctx, s, "scan_cmd_prefix");
 }
 
-// stage 2: flatten count + draw scan
-void runFlattenCount(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s)
+// stage 2: flatten count + draw scan, both checked against `caps`
+void runFlattenCount(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const VgxCaps& caps, hipStream_t s)
 {
 	noteHip(ctx, hipMemsetAsync(ctx->dinfo.p, 0, ndraws * sizeof(vgx_draw_info), s));
 	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, 1);
+	a.caps = caps;
 	vgx_launch_flatten(false, a, VGX_GRID_BLOCKS, s);
 	mark(ctx, s, "flatten_count");
 	OpDrawInfo op;
-	op.dinfo = (vgx_draw_info*)ctx->dinfo.p; op.ndraws = ndraws; op.totals = (VgxTotals*)ctx->totals.p; op.caps = ctx->caps; op.keepPolyBase = 0;
+	op.dinfo = (vgx_draw_info*)ctx->dinfo.p; op.ndraws = ndraws; op.totals = (VgxTotals*)ctx->totals.p; op.caps = caps; op.keepPolyBase = 0;
 	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, ndraws);
 	mark(ctx, s, "scan_draws");
 }
@@ -596,12 +622,7 @@ void runFlattenBuild(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws,
 // their leaves past the LDS slots and walk in lock-step with the deepest cubic of the chunk (the count decides: >= 10 polyline vertices per command instance).
 void runFlattenOneWalk(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s)
 {
-	{
-		const uint64_t savedCmdCap = ctx->caps.cmd_instances; // k_flat1 needs no per-command scratch (see vgx_flatten)
-		ctx->caps.cmd_instances = ~0ull;
-		runCmdPrefix(ctx, ps, draws, ndraws, s);
-		ctx->caps.cmd_instances = savedCmdCap;
-	}
+	runCmdPrefix(ctx, ps, draws, ndraws, ~0ull, s); // k_flat1 needs no per-command scratch
 	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, 1);
 	a.mprep = (VgxMeshPrep*)ctx->mprep.p; // k_flatten_serial / the gather write the per-mesh constants with the descriptors
 	const uint64_t segBound = ctx->f1RouteSegBound;
@@ -632,15 +653,38 @@ static uint64_t f1RouteSegmentsFor(const vgx_pathset* ps, uint64_t ndraws, uint3
 	return ndraws * (uint64_t)(ps->maxCmdsPerPath ? ps->maxCmdsPerPath : 1) / minItems + 2;
 }
 
-// prepDone: the flatten stage already wrote the per-mesh constants (single-pass pipeline), no k_mesh_prepare pass
-void runStrokeCount(vgx_ctx* ctx, const vgx_draw* draws, const VgxCaps& outCaps, int checkCaps, hipStream_t s, const float* poly = nullptr, bool prepDone = false, vgx_mesh* meshesOut = nullptr)
+// the stroke / fill kernels' arguments over the context's scratch, no output buffers yet
+VgxStrokeArgs strokeArgs(vgx_ctx* ctx, const vgx_draw* draws, const float* poly, const VgxCaps& caps)
 {
 	VgxStrokeArgs a;
 	a.draws = draws; a.poly = poly ? poly : (const float*)ctx->poly.p; a.mdesc = (const VgxMeshDesc*)ctx->mdesc.p;
 	a.elem_prefix = nullptr; a.elem_prefix_fill = (const uint64_t*)ctx->elemPrefix.p; a.elem_prefix_stroke = (const uint64_t*)ctx->elemPrefixS.p;
 	a.mprep = (VgxMeshPrep*)ctx->mprep.p; a.mtab = (vgx_mesh*)ctx->mtab.p;
 	a.pos = nullptr; a.color = nullptr; a.idx = nullptr; a.meshes_out = nullptr; a.mesh_base = nullptr;
-	a.totals = (VgxTotals*)ctx->totals.p; a.caps = outCaps; a.tile_mode = 0; a.no_long = 0;
+	a.totals = (VgxTotals*)ctx->totals.p; a.caps = caps; a.tile_mode = 0; a.no_long = 0;
+	return a;
+}
+
+// The bounds of a call that writes into `out`: the context's scratch, the caller's vertex / index / mesh-table capacities
+VgxCaps outCapsFor(const vgx_ctx* ctx, const vgx_mesh_out* out)
+{
+	VgxCaps c = ctx->caps;
+	c.vertices = out->cap_vertices;
+	c.indices = out->cap_indices;
+	if (out->meshes && out->cap_meshes < c.meshes) { c.meshes = out->cap_meshes; }
+	return c;
+}
+
+// the call's totals into the caller's device words, if it asked for them
+void publish(vgx_ctx* ctx, vgx_sizes* dev_sizes, uint32_t* dev_status, hipStream_t s)
+{
+	if (dev_sizes || dev_status) { hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status); }
+}
+
+// prepDone: the flatten stage already wrote the per-mesh constants (single-pass pipeline), no k_mesh_prepare pass
+void runStrokeCount(vgx_ctx* ctx, const vgx_draw* draws, const VgxCaps& outCaps, int checkCaps, hipStream_t s, const float* poly = nullptr, bool prepDone = false, vgx_mesh* meshesOut = nullptr)
+{
+	VgxStrokeArgs a = strokeArgs(ctx, draws, poly, outCaps);
 	if (!prepDone) { vgx_launch_mesh_prepare(a, s); }
 	vgx_launch_stroke(false, a, 32768, s); // k_round_sizes: Round-join mesh sizes (exits immediately without Round joins); one wave per mesh: 10 000 long polylines want more than 4 096 waves
 	mark(ctx, s, "mesh_prepare");
@@ -696,44 +740,18 @@ int runStrokeEmit(vgx_ctx* ctx, const vgx_draw* draws, const vgx_mesh_out* out, 
 		const int st = runAssemble(ctx, out, s, draws);
 		if (st != VGX_OK) { return st; }
 	}
-	VgxStrokeArgs a;
+	VgxStrokeArgs a = strokeArgs(ctx, draws, poly, ctx->caps);
 	a.mesh_base = ctx->asmArmed ? (const uint32_t*)ctx->meshBase.p : nullptr;
-	a.draws = draws; a.poly = poly ? poly : (const float*)ctx->poly.p; a.mdesc = (const VgxMeshDesc*)ctx->mdesc.p;
-	a.elem_prefix = nullptr; a.elem_prefix_fill = (const uint64_t*)ctx->elemPrefix.p; a.elem_prefix_stroke = (const uint64_t*)ctx->elemPrefixS.p;
-	a.mprep = (VgxMeshPrep*)ctx->mprep.p; a.mtab = (vgx_mesh*)ctx->mtab.p;
 	a.pos = out->pos; a.color = out->color; a.idx = out->idx; a.meshes_out = tableDone ? nullptr : out->meshes;
-	a.totals = (VgxTotals*)ctx->totals.p;
-	a.caps = ctx->caps;
-	a.tile_mode = 0;
 	a.no_long = (out->cap_vertices < ctx->optBigEmitMin || !ctx->optStrokeLong) ? 1 : 0; // frame-sized: one stroke kernel less to launch
 	// Batches of fills and closed Miter AA / Thin strokes (the scan over the meshes decides, on the device): one draw-ordered tile
 	// kernel instead of k_fill + k_stroke_simple (vgx_tile.hip). Not for frame-sized calls (two more launches than they are worth).
 	uint64_t capTiles = 0;
-	if (ctx->optTileEmit && ctx->tileHint && !ctx->optConcurrentEmit && out->cap_vertices >= ctx->optBigEmitMin && out->cap_vertices / VGX_TILE_ELEMS + 2 < 0x7FFFFFFFull) {
+	if (ctx->optTileEmit && ctx->tileHint && out->cap_vertices >= ctx->optBigEmitMin && out->cap_vertices / VGX_TILE_ELEMS + 2 < 0x7FFFFFFFull) {
 		capTiles = out->cap_vertices / VGX_TILE_ELEMS + 2; // every element emits at least one vertex
 		const int st = ensure(ctx, ctx->tileTab, capTiles * sizeof(VgxTileRec));
 		if (st != VGX_OK) { return st; }
 		a.tile_mode = 1;
-	}
-	if (ctx->optConcurrentEmit) {
-		// tuning experiment (VGX_EXP_CONCURRENT_EMIT=1 at vgx_create): k_stroke on a side stream beside k_fill (they write disjoint
-		// meshes); joined before the call returns control of `s`
-		if (!ctx->sideStream) {
-			(void)hipStreamCreateWithFlags(&ctx->sideStream, hipStreamNonBlocking);
-			(void)hipEventCreateWithFlags(&ctx->forkEv, hipEventDisableTiming);
-			(void)hipEventCreateWithFlags(&ctx->joinEv, hipEventDisableTiming);
-		}
-		(void)hipEventRecord(ctx->forkEv, s);
-		(void)hipStreamWaitEvent(ctx->sideStream, ctx->forkEv, 0);
-		VgxStrokeArgs b = a;
-		b.elem_prefix = a.elem_prefix_stroke;
-		vgx_launch_stroke(true, b, vgxElementGrid(out->cap_vertices), ctx->sideStream);
-		(void)hipEventRecord(ctx->joinEv, ctx->sideStream);
-		a.elem_prefix = a.elem_prefix_fill;
-		vgx_launch_fill(a, vgxElementGrid(out->cap_vertices), s);
-		(void)hipStreamWaitEvent(s, ctx->joinEv, 0);
-		mark(ctx, s, "fill_emit");
-		return launchStatus(ctx);
 	}
 	a.elem_prefix = a.elem_prefix_fill;
 	vgx_launch_fill(a, vgxElementGrid(out->cap_vertices), s); // (tile mode: the mesh-table copy, and the kernel exits at once for the batches the tile kernel takes)
@@ -769,6 +787,114 @@ int ensureMeshBuffers(vgx_ctx* ctx, uint64_t polyVerts, uint64_t subpaths, uint6
 	if (m3 < m) { m = m3; }
 	ctx->caps.meshes = m;
 	return VGX_OK;
+}
+
+// per-command scratch of the flatten kernels for `ncmd` command instances (+ the leaf overflow area of k_flatten_build)
+int ensureCmdScratch(vgx_ctx* ctx, uint64_t ncmd)
+{
+	int st;
+	if ((st = ensure(ctx, ctx->cmdCnt, (ncmd + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->subFirst, (ncmd + 1) * sizeof(VgxSubRec))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->leafOverflow, (size_t)VGX_BUILD_WAVES * VGX_BUILD_OVERFLOW * 64 * 2 * sizeof(float))) != VGX_OK) { return st; }
+	ctx->caps.cmd_instances = ctx->cmdCnt.cap / sizeof(uint32_t) - 1;
+	{ const uint64_t c2 = ctx->subFirst.cap / sizeof(VgxSubRec) - 1; if (c2 < ctx->caps.cmd_instances) { ctx->caps.cmd_instances = c2; } }
+	return VGX_OK;
+}
+
+// Polyline scratch doubles as the heap of the single-pass path (k_flatten_build), for a batch of V polyline vertices, `longV` of them in
+// sub-paths longer than VGX_LONG_SUBPATH, `ncmd` command instances. Its waves switch to a fresh block when a chunk does not fit: the unused
+// tail of the old block is smaller than that chunk (<= 1x the real vertices over the whole batch), the moved prefix of a spanning sub-path
+// is < VGX_LONG_SUBPATH per >= VGX_BUILD_BLOCK block (<= 1/4), and longer sub-paths grow geometrically (<= 4x their own size). Plus every
+// wave's last open block. k_flatten_thin (lineTo-only path sets; ps == nullptr: any set) places draw d at its command prefix -- one slot
+// per command instance -- and the exact builder's draws behind that.
+uint64_t heapBuildVerts(const vgx_pathset* ps, uint64_t V, uint64_t ncmd, uint64_t longV)
+{
+	uint64_t h = V * 9 / 4 + 4 * longV + 2 * (uint64_t)VGX_BUILD_WAVES * VGX_BUILD_BLOCK;
+	if ((!ps || ps->thinStatic) && h < 2 * ncmd + 4096) { h = 2 * ncmd + 4096; }
+	return h;
+}
+
+// ... of k_flatten_inst's lane-private blocks (vgx_inst.h; instLong = vertices in sub-paths longer than VGX_INST_LONG_SUBPATH): a block
+// left behind wastes less than the one sub-path that did not fit (< the block's useful vertices while sub-paths are at most half a block
+// long), longer sub-paths grow geometrically (<= 4x their size + a block, counted with head room), plus every lane's last open block
+uint64_t heapInstVerts(const vgx_ctx* ctx, uint64_t V, uint64_t instLong)
+{
+	const uint64_t grown = (ctx->optInstBlock >= VGX_INST_BLOCK) ? V * 9 / 4 + 8 * instLong : V * 10;
+	return grown + (uint64_t)ctx->optInstWaves * 64 * ctx->optInstBlock + 4096;
+}
+
+// Leaf-list capacity of the one-walk kernel instance and commands per segment bucket, for a batch of V polyline vertices over `ncmd`
+// command instances (ncmd == 0: not known). A 64-command chunk of ~45-segment cubics stages ~1450 leaves (the 1664-entry instance: six
+// waves per CU); lighter batches take the 1024-entry instance (eight waves per CU), heavier ones (long curves: 145 segments per cubic)
+// the 3072-entry instance with smaller buckets, so that a chunk's leaves still fit (a chunk that overflows the list is placed by walking
+// its cubics a second time). VGX_F1_CAP / VGX_F1_SEG override both.
+void f1Shape(const vgx_ctx* ctx, uint64_t V, uint64_t ncmd, int* cap, uint32_t* segMax)
+{
+	*cap = 1664; *segMax = 64;
+	if (ncmd) {
+		const double perCmd = (double)V / (double)ncmd;
+		if (perCmd * 64.0 <= 800.0) { *cap = 1024; }
+		else if (perCmd * 64.0 > 1500.0) {
+			// long curves (145 segments per cubic at box 10 000): the 3072-entry instance with buckets of a power of two -- 2^k cubics
+			// become 64 tasks after whole rounds of cutting (17 cubics would stay at 34 half-cubic tasks). Measured on 1 M such
+			// cubics: 3072 entries x 32 commands 3.4 ms, 1664 x 16 4.1 ms, 1664 x 8 6.2 ms (two-phase entry: 6.0 ms).
+			*cap = 3072;
+			const double m = 0.8 * 3072.0 / perCmd;
+			*segMax = m >= 64.0 ? 64u : (m >= 32.0 ? 32u : (m >= 16.0 ? 16u : 8u));
+		}
+	}
+	if (ctx->optF1Cap) { *cap = ctx->optF1Cap; }
+	if (ctx->optF1Seg) { *segMax = (uint32_t)ctx->optF1Seg; }
+}
+
+// look-back tables of the one-walk kernel for `segBound` segments: segment table, records (+ one group record per 64)
+int ensureF1Tables(vgx_ctx* ctx, uint64_t segBound)
+{
+	int st;
+	if ((st = ensure(ctx, ctx->f1SegDraw, (segBound + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
+	return ensure(ctx, ctx->f1Segs, (segBound + segBound / 64 + 2) * sizeof(VgxF1Seg));
+}
+
+// vgx_tessellate's one-walk route sized for any draw list of up to `segDraws` draws on `ps` (f1Route*); *ok = false: more than 2^24
+// segments, the route is not taken
+int f1Reserve(vgx_ctx* ctx, const vgx_pathset* ps, uint64_t segDraws, int cap, uint32_t segMax, bool* ok)
+{
+	*ok = false;
+	const uint64_t segBound = f1RouteSegmentsFor(ps, segDraws, segMax);
+	if (segBound > (1ull << 24)) { return VGX_OK; }
+	const int st = ensureF1Tables(ctx, segBound);
+	if (st != VGX_OK) { return st; }
+	ctx->f1RoutePs = ps; ctx->f1RoutePsGen = ps->gen; ctx->f1RouteCap = cap; ctx->f1RouteSegMax = segMax; ctx->f1RouteSegBound = segBound;
+	*ok = true;
+	return VGX_OK;
+}
+
+// A frame-sized batch (ndraws <= VGX_SMALL_DRAWS): five launches instead of seventeen (vgx_flatten.hip, "Frame-sized batches") --
+// small_front -> flatten_build -> small_middle (which publishes its verdict to dev_sizes / dev_status) -> the emit kernels.
+// markScratch: the scan over the draws flags a batch that outgrew the context's tables (vgx_tessellate_immediate).
+int runFrameSized(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out, int markScratch,
+                  vgx_sizes* dev_sizes, uint32_t* dev_status, hipStream_t s)
+{
+	const VgxCaps outCaps = outCapsFor(ctx, out);
+	const OpCmdPrefix opC = cmdPrefixOp(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, 0);
+	vgx_launch_small_front(&opC, (vgx_draw_info*)ctx->dinfo.p, s);
+	mark(ctx, s, "small_front");
+	VgxFlattenArgs f = flattenArgs(ctx, ps, draws, ndraws, 1);
+	f.build_mode = 1;
+	f.mprep = (VgxMeshPrep*)ctx->mprep.p;
+	vgx_launch_flatten_build(f, ctx->optBuildWaves, s, false);
+	mark(ctx, s, "flatten_build");
+	VgxStrokeArgs sa = strokeArgs(ctx, draws, nullptr, outCaps);
+	sa.no_long = 1;
+	OpDrawInfo opD;
+	opD.dinfo = (vgx_draw_info*)ctx->dinfo.p; opD.ndraws = ndraws; opD.totals = (VgxTotals*)ctx->totals.p; opD.caps = ctx->caps; opD.keepPolyBase = 1; opD.markScratch = markScratch;
+	OpMeshAll opM;
+	opM.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; opM.mtab = (vgx_mesh*)ctx->mtab.p; opM.meshesOut = out->meshes;
+	opM.prefixFill = (uint64_t*)ctx->elemPrefix.p; opM.prefixStroke = (uint64_t*)ctx->elemPrefixS.p;
+	opM.totals = (VgxTotals*)ctx->totals.p; opM.caps = outCaps; opM.checkCaps = 1; opM.fixedSize = 0; opM.fixedCount = 0;
+	vgx_launch_small_middle(f, sa, &opD, &opM, dev_sizes, dev_status, s);
+	mark(ctx, s, "small_middle");
+	return runStrokeEmit(ctx, draws, out, s, nullptr, true);
 }
 
 } // namespace
@@ -833,7 +959,6 @@ int vgx_create(int device, vgx_ctx** out_ctx)
 	if (const char* e = getenv("VGX_TILE_EMIT")) { ctx->optTileEmit = atoi(e) != 0; }
 	ctx->optPsNoSmall = getenv("VGX_PS_NO_SMALL") ? 1 : 0; // testing knob: frame-sized path sets through the large-set launch sequence
 	ctx->optBuildWaves = VGX_BUILD_WAVES;
-	ctx->optConcurrentEmit = getenv("VGX_EXP_CONCURRENT_EMIT") ? 1 : 0;
 	ctx->optNoSmall = getenv("VGX_NO_SMALL") ? 1 : 0; // testing knob: frame-sized batches through the large-batch launch sequence
 	ctx->optInst = 1; ctx->optInstWaves = VGX_INST_WAVES; ctx->optInstBlock = VGX_INST_BLOCK; // VGX_INST=0: instanced batches through k_flatten_build as well
 	if (const char* e = getenv("VGX_INST")) { ctx->optInst = atoi(e) != 0; }
@@ -885,7 +1010,6 @@ int vgx_destroy(vgx_ctx* ctx)
 	if (ctx->psStream) { (void)hipStreamDestroy(ctx->psStream); }
 	for (int i = 0; i < 2; ++i) { if (ctx->psStage[i]) { (void)hipHostFree(ctx->psStage[i]); (void)hipEventDestroy(ctx->psStageEv[i]); } }
 	vgx_rccl_release(ctx);
-	if (ctx->sideStream) { (void)hipStreamDestroy(ctx->sideStream); (void)hipEventDestroy(ctx->forkEv); (void)hipEventDestroy(ctx->joinEv); }
 	if (ctx->evCreated) {
 		for (int r = 0; r < VGX_PROF_RING; ++r) { for (int i = 0; i <= VGX_MAX_STAGES; ++i) { (void)hipEventDestroy(ctx->ev[r][i]); } }
 	}
@@ -1188,30 +1312,13 @@ int vgx_pathset_destroy(vgx_ctx* ctx, vgx_pathset* ps)
 
 // ---- flatten ------------------------------------------------------------------------------------------
 // detectInst: look for reused paths (instanced flatten kernel of vgx_tessellate); the flatten-only entry points have no use for it
-static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s, bool detectInst);
-// The per-command scratch's bound as its buffers stand (the count lifts it for its sizing pass)
-static void cmdCapFromBuffers(vgx_ctx* ctx)
-{
-	uint64_t c = ctx->cmdCnt.p ? ctx->cmdCnt.cap / sizeof(uint32_t) - 1 : 0;
-	const uint64_t c2 = ctx->subFirst.p ? ctx->subFirst.cap / sizeof(VgxSubRec) - 1 : 0;
-	if (c2 < c) { c = c2; }
-	ctx->caps.cmd_instances = c;
-}
-static int flattenCountCommon(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s, bool detectInst)
-{
-	const int st = flattenCountBody(ctx, ps, draws, ndraws, s, detectInst);
-	if (st != VGX_OK) { cmdCapFromBuffers(ctx); } // a count that failed part-way leaves no lifted bound behind (later calls trust it)
-	return st;
-}
 static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s, bool detectInst)
 {
 	int st;
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
-	// pass 1: command instances (sizes the per-command scratch)
-	ctx->caps.cmd_instances = ~0ull; // not known yet: never trips the check in this sizing pass
-	ctx->instPeriod = 0; ctx->instGrouped = 0; ctx->instClasses = 1; ctx->instPermOn = 0;
-	ctx->tmplOn = false; // the scratch is re-sized for this batch; a template belongs to the count call that built it
-	runCmdPrefix(ctx, ps, draws, ndraws, s);
+	forgetRoutes(ctx); // the scratch is re-sized for this batch; a template belongs to the count call that built it
+	// pass 1: command instances (sizes the per-command scratch; not known yet: no bound)
+	runCmdPrefix(ctx, ps, draws, ndraws, ~0ull, s);
 	if (detectInst && ctx->optInst && ndraws > VGX_SMALL_DRAWS) {
 		vgx_launch_inst_detect(draws, ndraws, (VgxTotals*)ctx->totals.p, s);
 		// ... and how many different paths the draws use (grouped mode, when the sequence does not repeat)
@@ -1227,7 +1334,7 @@ static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw*
 		if (P <= 0xFFFFFFFFull) { ctx->instPeriod = (uint32_t)P; }
 	}
 	const VgxTotals& ht = *ctx->hostTotals;
-	const bool reused = ctx->optInst && ndraws > VGX_SMALL_DRAWS && ndraws < 0xFFFFFFFFull && ht.inst_distinct != 0 && ndraws / ht.inst_distinct >= VGX_INST_MIN_INSTANCES;
+	const bool reused = ndraws > VGX_SMALL_DRAWS && pathsReused(ctx, ndraws, ht.inst_distinct);
 	if (reused && ctx->optInstClasses > 1 && (instPeriodFor(ctx, ndraws) ? ht.inst_tol_varies != 0 : (uint32_t)~ht.inst_tol_lo_inv != ht.inst_tol_hi)) {
 		// The instances of a path differ in scale: in the periodic mapping (lane = instance) the lanes of a wave would
 		// disagree about nearly every cubic. Grouped mode sorted by (path, tolerance class) instead.
@@ -1246,23 +1353,16 @@ static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw*
 			if (nc > 1) { ctx->instPeriod = 0; }
 		}
 	}
-	if (!instPeriodFor(ctx, ndraws) && ctx->optInst && ndraws > VGX_SMALL_DRAWS && ndraws < 0xFFFFFFFFull && ctx->hostTotals->inst_distinct != 0
-		&& ndraws / ctx->hostTotals->inst_distinct >= VGX_INST_MIN_INSTANCES) {
-		// paths are reused (>= 32 draws per used path on average) but not as a repeating sequence: grouped mode
+	if (reused && !instPeriodFor(ctx, ndraws)) {
+		// paths are reused but not as a repeating sequence: grouped mode
 		if ((st = ensureInstGroup(ctx, ps->dev.npaths, ctx->instClasses, ndraws, true)) != VGX_OK) { return st; }
 		ctx->instGrouped = 1;
 	}
-	const uint64_t ncmdInst = ctx->hostTotals->sizes.num_cmd_instances;
-	if ((st = ensure(ctx, ctx->cmdCnt, (ncmdInst + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->subFirst, (ncmdInst + 1) * sizeof(VgxSubRec))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->leafOverflow, (size_t)VGX_BUILD_WAVES * VGX_BUILD_OVERFLOW * 64 * 2 * sizeof(float))) != VGX_OK) { return st; }
-	ctx->caps.cmd_instances = ctx->cmdCnt.cap / sizeof(uint32_t) - 1;
-	{ const uint64_t c2 = ctx->subFirst.cap / sizeof(VgxSubRec) - 1; if (c2 < ctx->caps.cmd_instances) { ctx->caps.cmd_instances = c2; } }
-	// pass 2: per-draw counts (sizes polyline / sub-path / mesh scratch)
-	const VgxCaps saved = ctx->caps;
-	ctx->caps.poly_vertices = ~0ull; ctx->caps.subpaths = ~0ull; ctx->caps.meshes = ~0ull;
-	runFlattenCount(ctx, ps, draws, ndraws, s);
-	ctx->caps = saved;
+	if ((st = ensureCmdScratch(ctx, ctx->hostTotals->sizes.num_cmd_instances)) != VGX_OK) { return st; }
+	// pass 2: per-draw counts (sizes polyline / sub-path / mesh scratch: no bound on those)
+	VgxCaps sizing = ctx->caps;
+	sizing.poly_vertices = ~0ull; sizing.subpaths = ~0ull; sizing.meshes = ~0ull;
+	runFlattenCount(ctx, ps, draws, ndraws, sizing, s);
 	if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
 	if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
 	if (ctx->hostTotals->sizes.num_poly_vertices > 0xFFFFFFF0ull) { return VGX_E_RANGE; }
@@ -1278,7 +1378,7 @@ int vgx_flatten_count(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
 	ctx->lastStage = 0;
-	const int st = flattenCountCommon(ctx, ps, draws, ndraws, s, false);
+	const int st = flattenCountBody(ctx, ps, draws, ndraws, s, false);
 	if (st != VGX_OK) { return st; }
 	*out_sizes = ctx->hostTotals->sizes;
 	out_sizes->num_vertices = 0;
@@ -1334,32 +1434,16 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	ctx->tmplOn = false;
 	int st;
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->serialList, (ndraws + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	// Leaf-list capacity of the kernel instance and commands per segment bucket. A 64-command chunk of ~45-segment cubics stages
-	// ~1450 leaves (the 1664-entry instance: six waves per CU); lighter batches take the 1024-entry instance (eight waves per CU),
-	// heavier ones (long curves: 145 segments per cubic) the 3072-entry instance with smaller buckets, so that a chunk's leaves
-	// still fit (a chunk that overflows the list is placed by walking its cubics a second time). The batch's leaves per command are
-	// taken from the LAST call on this context with the same path set and draw count, when that call's result has arrived.
-	int cap = 1664; uint32_t segMax = 64;
+	// The kernel instance and segment bucket (f1Shape) from the batch's leaves per command, taken from the LAST call on this context with
+	// the same path set and draw count, when that call's result has arrived.
 	const uint64_t tag = ps->gen * 0x9E3779B97F4A7C15ull + ndraws;
 	if (!ctx->hostF1) {
 		if (hipHostMalloc((void**)&ctx->hostF1, 4 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess) { ctx->hostF1[0] = 0; ctx->hostF1[1] = 0; ctx->hostF1[2] = 0; ctx->hostF1[3] = 0; }
 		else { ctx->hostF1 = nullptr; }
 	}
-	if (ctx->hostF1 && ctx->f1Tag == tag && ctx->hostF1[1] != 0 && ctx->hostF1[2] == tag) {
-		const double perCmd = (double)ctx->hostF1[0] / (double)ctx->hostF1[1];
-		if (perCmd * 64.0 <= 800.0) { cap = 1024; }
-		else if (perCmd * 64.0 > 1500.0) {
-			// long curves (145 segments per cubic at box 10 000): the 3072-entry instance with buckets of a power of two -- 2^k cubics
-			// become 64 tasks after whole rounds of cutting (17 cubics would stay at 34 half-cubic tasks). Measured on 1 M such
-			// cubics: 3072 entries x 32 commands 3.4 ms, 1664 x 16 4.1 ms, 1664 x 8 6.2 ms (two-phase entry: 6.0 ms).
-			cap = 3072;
-			const double m = 0.8 * 3072.0 / perCmd;
-			segMax = m >= 64.0 ? 64u : (m >= 32.0 ? 32u : (m >= 16.0 ? 16u : 8u));
-		}
-	}
-	if (ctx->optF1Cap) { cap = ctx->optF1Cap; }
-	if (ctx->optF1Seg) { segMax = (uint32_t)ctx->optF1Seg; }
+	const bool known = ctx->hostF1 && ctx->f1Tag == tag && ctx->hostF1[1] != 0 && ctx->hostF1[2] == tag;
+	int cap; uint32_t segMax;
+	f1Shape(ctx, known ? ctx->hostF1[0] : 0, known ? ctx->hostF1[1] : 0, &cap, &segMax);
 	// Very short curves (a handful of segments per cubic: a chunk of 64 commands yields a few hundred vertices) are bound by what
 	// a SEGMENT costs in the one-walk kernel -- its dependent loads and its place in the order, ~40 000 cycles whatever it holds --
 	// not by the walk: the two-walk kernels (count -> scan over draws -> emit, vgx_flatten.hip) are faster there (1 M cubics of
@@ -1369,27 +1453,21 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	// set (the tag only says that the set and the number of draws are the last call's -- the draws' paths may have changed).
 	// A set whose longest path is far above its mean (the bound above twice the last call's total) takes the one-walk route instead.
 	const uint64_t cmdBoundAll = ndraws * (uint64_t)(ps->maxCmdsPerPath ? ps->maxCmdsPerPath : 1);
-	if (ctx->hostF1 && ctx->f1Tag == tag && ctx->hostF1[1] != 0 && ctx->hostF1[2] == tag && !ctx->optF1Cap && !ctx->optF1Seg && !ps->hasEmpty
+	if (known && !ctx->optF1Cap && !ctx->optF1Seg && !ps->hasEmpty
 		&& (double)ctx->hostF1[0] / (double)ctx->hostF1[1] * 64.0 <= 384.0 && cmdBoundAll <= 2 * ctx->hostF1[1] + 4096) {
-		const uint64_t ncmdInst = cmdBoundAll;
-		if ((st = ensure(ctx, ctx->cmdCnt, (ncmdInst + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-		// The device-side guard of THIS call only (a batch that grew: VGX_E_NOSPACE); the context's persistent cap -- what
-		// vgx_tessellate relies on for the scratch sized by the last count -- is put back right after the launch.
-		const uint64_t savedCmdCap = ctx->caps.cmd_instances;
-		ctx->caps.cmd_instances = ctx->cmdCnt.cap / sizeof(uint32_t) - 1;
-		// (the two-walk kernels write per-command words only -- no sub-path records: cmdCnt alone bounds this launch)
-		runCmdPrefix(ctx, ps, draws, ndraws, s);
-		ctx->caps.cmd_instances = savedCmdCap;
-		const VgxCaps saved = ctx->caps;
-		ctx->caps.poly_vertices = out->cap_poly_vertices; ctx->caps.subpaths = out->cap_subpaths; ctx->caps.meshes = ~0ull;
-		runFlattenCount(ctx, ps, draws, ndraws, s); // the scan over the draws compares the totals with the caller's capacities
-		ctx->caps = saved;
+		if ((st = ensure(ctx, ctx->cmdCnt, (cmdBoundAll + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
+		// The device-side guard of THIS call only (a batch that grew: VGX_E_NOSPACE). The two-walk kernels write per-command words
+		// only -- no sub-path records: cmdCnt alone bounds this launch. ctx->caps stays what vgx_tessellate relies on.
+		runCmdPrefix(ctx, ps, draws, ndraws, ctx->cmdCnt.cap / sizeof(uint32_t) - 1, s);
+		VgxCaps countCaps = ctx->caps; // the scan over the draws compares the totals with the caller's capacities
+		countCaps.poly_vertices = out->cap_poly_vertices; countCaps.subpaths = out->cap_subpaths; countCaps.meshes = ~0ull;
+		runFlattenCount(ctx, ps, draws, ndraws, countCaps, s);
 		VgxFlattenArgs a2 = flattenArgs(ctx, ps, draws, ndraws, apply_transform);
 		a2.poly = out->poly; a2.subs = out->subpaths; a2.mdesc = nullptr; a2.mtab = nullptr;
 		a2.caps.poly_vertices = ~0ull; a2.caps.subpaths = ~0ull; a2.caps.meshes = ~0ull;
 		vgx_launch_flatten(true, a2, VGX_GRID_BLOCKS, s);
 		mark(ctx, s, "flatten_emit");
-		hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status);
+		publish(ctx, dev_sizes, dev_status, s);
 		{
 			VgxTotals* T = (VgxTotals*)ctx->totals.p;
 			noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[0], &T->sizes.num_poly_vertices, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -1403,21 +1481,15 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	// Segments: buckets of at least min(32, segMax) command instances. The command total is not known on the host without a round
 	// trip; ndraws x (longest path) bounds it (a batch whose bound is absurdly far above its real size asks once, synchronously).
 	const uint64_t minItems = segMax < 32 ? segMax : 32;
-	uint64_t cmdBound = ndraws * (uint64_t)(ps->maxCmdsPerPath ? ps->maxCmdsPerPath : 1);
-	{
-		const uint64_t savedCmdCap = ctx->caps.cmd_instances; // k_flat1 needs no per-command scratch: no guard for this launch, the
-		ctx->caps.cmd_instances = ~0ull;                       // persistent cap (vgx_tessellate's guard) stays what the last count made it
-		runCmdPrefix(ctx, ps, draws, ndraws, s);
-		ctx->caps.cmd_instances = savedCmdCap;
-	}
+	uint64_t cmdBound = cmdBoundAll;
+	runCmdPrefix(ctx, ps, draws, ndraws, ~0ull, s); // k_flat1 needs no per-command scratch: no guard for this launch
 	if (cmdBound / minItems > (1ull << 26)) {
 		if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
 		if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
 		cmdBound = ctx->hostTotals->sizes.num_cmd_instances;
 	}
 	const uint64_t segBound = cmdBound / minItems + 2;
-	if ((st = ensure(ctx, ctx->f1SegDraw, (segBound + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->f1Segs, (segBound + segBound / 64 + 2) * sizeof(VgxF1Seg))) != VGX_OK) { return st; }
+	if ((st = ensureF1Tables(ctx, segBound)) != VGX_OK) { return st; }
 	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, apply_transform);
 	a.poly = out->poly;
 	a.subs = out->subpaths;
@@ -1497,7 +1569,7 @@ int vgx_partition(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, ui
 			if (P > 1 && ndraws % P == 0 && ndraws / P >= nparts) { align = P; }
 		}
 	}
-	st = flattenCountCommon(ctx, ps, draws, ndraws, s, false); // per-draw polyline vertex counts in dinfo
+	st = flattenCountBody(ctx, ps, draws, ndraws, s, false); // per-draw polyline vertex counts in dinfo
 	if (st != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partBounds, ((size_t)nparts + 1) * 2 * sizeof(uint64_t))) != VGX_OK) { return st; }
 	OpPartWeight op;
@@ -1590,7 +1662,7 @@ static int runTmpl(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 		if (aux) {
 			const vgx_sizes z = a.total;
 			hipLaunchKernelGGL(k_tmpl_nospace, dim3(1), dim3(1), 0, s, (VgxTotals*)ctx->totals.p, z, aux);
-			if (dev_sizes || dev_status) { hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status); }
+			publish(ctx, dev_sizes, dev_status, s);
 			return launchStatus(ctx);
 		}
 	}
@@ -1607,9 +1679,7 @@ static int runTmpl(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 	}
 	vgx_launch_tmpl_emit(a, s);
 	mark(ctx, s, "tmpl_emit");
-	if (dev_sizes || dev_status) {
-		hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status);
-	}
+	publish(ctx, dev_sizes, dev_status, s);
 	return launchStatus(ctx);
 }
 
@@ -1624,7 +1694,7 @@ static bool tmplFor(const vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws)
 static int tmplPipeline(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* d, uint64_t n, hipStream_t s)
 {
 	int st;
-	if ((st = flattenCountCommon(ctx, ps, d, n, s, false)) != VGX_OK) { return st; }
+	if ((st = flattenCountBody(ctx, ps, d, n, s, false)) != VGX_OK) { return st; }
 	const vgx_sizes fsz = ctx->hostTotals->sizes;
 	if ((st = ensureMeshBuffers(ctx, fsz.num_poly_vertices, fsz.num_subpaths, fsz.num_meshes)) != VGX_OK) { return st; }
 	{
@@ -1933,24 +2003,12 @@ int vgx_tessellate_count(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* dr
 		ctx->lastPs = ps; ctx->lastDraws = draws; ctx->lastNDraws = ndraws; ctx->lastStage = 2;
 		return VGX_OK;
 	}
-	st = flattenCountCommon(ctx, ps, draws, ndraws, s, true);
+	st = flattenCountBody(ctx, ps, draws, ndraws, s, true);
 	if (st != VGX_OK) { return st; }
 	const vgx_sizes sz = ctx->hostTotals->sizes;
-	// Polyline scratch doubles as the heap of the single-pass path (k_flatten_build). Its waves switch to a fresh block
-	// when a chunk does not fit: the unused tail of the old block is smaller than that chunk (<= 1x the real vertices
-	// over the whole batch), the moved prefix of a spanning sub-path is < VGX_LONG_SUBPATH per >= VGX_BUILD_BLOCK block
-	// (<= 1/4), and longer sub-paths grow geometrically (<= 4x their own size). Plus every wave's last open block.
-	uint64_t heapVerts = sz.num_poly_vertices * 9 / 4 + 4 * ctx->hostTotals->long_subpath_vertices + 2 * (uint64_t)VGX_BUILD_WAVES * VGX_BUILD_BLOCK;
-	// k_flatten_thin (lineTo-only path sets) places draw d at its command prefix -- one slot per command instance -- and the exact
-	// builder's draws behind that
-	if (ps->thinStatic && heapVerts < 2 * sz.num_cmd_instances + 4096) { heapVerts = 2 * sz.num_cmd_instances + 4096; }
+	uint64_t heapVerts = heapBuildVerts(ps, sz.num_poly_vertices, sz.num_cmd_instances, ctx->hostTotals->long_subpath_vertices);
 	if (instPeriodFor(ctx, ndraws) || instGroupedFor(ctx, ps, ndraws)) {
-		// k_flatten_inst's lane-private blocks (vgx_inst.h): a block left behind wastes less than the one sub-path that did
-		// not fit (< the block's useful vertices while sub-paths are at most half a block long), longer sub-paths grow
-		// geometrically (<= 4x their size + a block, counted with head room), plus every lane's last open block
-		const uint64_t V = sz.num_poly_vertices;
-		const uint64_t grown = (ctx->optInstBlock >= VGX_INST_BLOCK) ? V * 9 / 4 + 8 * ctx->hostTotals->inst_long_subpath_vertices : V * 10;
-		const uint64_t instVerts = grown + (uint64_t)ctx->optInstWaves * 64 * ctx->optInstBlock + 4096;
+		const uint64_t instVerts = heapInstVerts(ctx, sz.num_poly_vertices, ctx->hostTotals->inst_long_subpath_vertices);
 		if (instVerts > heapVerts) { heapVerts = instVerts; }
 	}
 	if ((st = ensureMeshBuffers(ctx, heapVerts, sz.num_subpaths, sz.num_meshes)) != VGX_OK) { return st; }
@@ -1960,23 +2018,11 @@ int vgx_tessellate_count(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* dr
 	if (ctx->optTessFlat1 && !ctx->optTwoPass && ndraws > VGX_SMALL_DRAWS && !instPeriodFor(ctx, ndraws) && !instGroupedFor(ctx, ps, ndraws)
 		&& !(ps->thinStatic && ctx->optThinStatic) && sz.num_cmd_instances != 0
 		&& (ctx->optTessFlat1 == 2 || sz.num_poly_vertices >= 10 * sz.num_cmd_instances)) {
-		int cap = 1664; uint32_t segMax = 64; // as vgx_flatten picks them, from the count's own figures
-		const double perChunk = (double)sz.num_poly_vertices / (double)sz.num_cmd_instances * 64.0;
-		if (perChunk <= 800.0) { cap = 1024; }
-		else if (perChunk > 1500.0) {
-			cap = 3072;
-			const double m = 0.8 * 3072.0 / (perChunk / 64.0);
-			segMax = m >= 64.0 ? 64u : (m >= 32.0 ? 32u : (m >= 16.0 ? 16u : 8u));
-		}
-		if (ctx->optF1Cap) { cap = ctx->optF1Cap; }
-		if (ctx->optF1Seg) { segMax = (uint32_t)ctx->optF1Seg; }
-		const uint64_t segBound = f1RouteSegmentsFor(ps, ctx->capDraws > ndraws ? ctx->capDraws : ndraws, segMax);
-		if (segBound <= (1ull << 24)) {
-			if ((st = ensure(ctx, ctx->f1SegDraw, (segBound + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
-			if ((st = ensure(ctx, ctx->f1Segs, (segBound + segBound / 64 + 2) * sizeof(VgxF1Seg))) != VGX_OK) { return st; }
-			if ((st = ensure(ctx, ctx->serialList, (ctx->capDraws + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-			ctx->f1Route = true; ctx->f1RoutePs = ps; ctx->f1RoutePsGen = ps->gen; ctx->f1RouteCap = cap; ctx->f1RouteSegMax = segMax; ctx->f1RouteSegBound = segBound;
-		}
+		int cap; uint32_t segMax;
+		f1Shape(ctx, sz.num_poly_vertices, sz.num_cmd_instances, &cap, &segMax);
+		bool ok;
+		if ((st = f1Reserve(ctx, ps, ctx->capDraws > ndraws ? ctx->capDraws : ndraws, cap, segMax, &ok)) != VGX_OK) { return st; }
+		ctx->f1Route = ok;
 	}
 	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, 1);
 	vgx_launch_flatten(true, a, VGX_GRID_BLOCKS, s);
@@ -2031,97 +2077,35 @@ int vgx_tessellate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
 	ctx->lastStage = 0;
-	VgxCaps outCaps = ctx->caps;
-	outCaps.vertices = out->cap_vertices;
-	outCaps.indices = out->cap_indices;
-	if (out->meshes && out->cap_meshes < outCaps.meshes) { outCaps.meshes = out->cap_meshes; }
 	if (ndraws <= VGX_SMALL_DRAWS && !ctx->optTwoPass && !ctx->optNoSmall) { // (round 6: also with draw-command assembly armed -- runStrokeEmit runs the partition kernels in front of the emit either way)
-		// frame-sized batch: five launches instead of seventeen (vgx_flatten.hip, "Frame-sized batches")
-		OpCmdPrefix opC;
-		opC.draws = draws; opC.pathCmdBegin = ps->dev.path_cmd_begin; opC.npaths = ps->dev.npaths; opC.ndraws = ndraws;
-		opC.prefix = (uint64_t*)ctx->cmdPrefix.p; opC.totals = (VgxTotals*)ctx->totals.p; opC.cap = ctx->caps.cmd_instances;
-		opC.period = 0; opC.pathSubBegin = ps->dev.path_sub_begin; opC.subPrefix = (uint64_t*)ctx->subPrefix.p;
-		vgx_launch_small_front(&opC, (vgx_draw_info*)ctx->dinfo.p, s);
-		mark(ctx, s, "small_front");
-		VgxFlattenArgs f = flattenArgs(ctx, ps, draws, ndraws, 1);
-		f.build_mode = 1;
-		f.mprep = (VgxMeshPrep*)ctx->mprep.p;
-		vgx_launch_flatten_build(f, ctx->optBuildWaves, s, false);
-		mark(ctx, s, "flatten_build");
-		VgxStrokeArgs sa;
-		sa.draws = draws; sa.poly = (const float*)ctx->poly.p; sa.mdesc = (const VgxMeshDesc*)ctx->mdesc.p;
-		sa.elem_prefix = nullptr; sa.elem_prefix_fill = (const uint64_t*)ctx->elemPrefix.p; sa.elem_prefix_stroke = (const uint64_t*)ctx->elemPrefixS.p;
-		sa.mprep = (VgxMeshPrep*)ctx->mprep.p; sa.mtab = (vgx_mesh*)ctx->mtab.p;
-		sa.pos = nullptr; sa.color = nullptr; sa.idx = nullptr; sa.meshes_out = nullptr; sa.mesh_base = nullptr;
-		sa.totals = (VgxTotals*)ctx->totals.p; sa.caps = outCaps; sa.tile_mode = 0; sa.no_long = 1;
-		OpDrawInfo opD;
-		opD.dinfo = (vgx_draw_info*)ctx->dinfo.p; opD.ndraws = ndraws; opD.totals = (VgxTotals*)ctx->totals.p; opD.caps = ctx->caps; opD.keepPolyBase = 1;
-		OpMeshAll opM;
-		opM.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; opM.mtab = (vgx_mesh*)ctx->mtab.p; opM.meshesOut = out->meshes;
-		opM.prefixFill = (uint64_t*)ctx->elemPrefix.p; opM.prefixStroke = (uint64_t*)ctx->elemPrefixS.p;
-		opM.totals = (VgxTotals*)ctx->totals.p; opM.caps = outCaps; opM.checkCaps = 1; opM.fixedSize = 0; opM.fixedCount = 0;
-		vgx_launch_small_middle(f, sa, &opD, &opM, dev_sizes, dev_status, s);
-		mark(ctx, s, "small_middle");
-		const int est = runStrokeEmit(ctx, draws, out, s, nullptr, true);
+		const int est = runFrameSized(ctx, ps, draws, ndraws, out, 0, dev_sizes, dev_status, s);
 		if (est != VGX_OK) { return est; }
-		if (ctx->asmArmed && (dev_sizes || dev_status)) { // the partition kernels may have ended the call (a mesh beyond any vertex buffer, the command table full): the verdict once more
-			hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status);
-		}
+		if (ctx->asmArmed) { publish(ctx, dev_sizes, dev_status, s); } // the partition kernels may have ended the call (a mesh beyond any vertex buffer, the command table full): the verdict once more
 		return launchStatus(ctx);
 	}
 	const bool oneWalk = ctx->f1Route && ps == ctx->f1RoutePs && ps->gen == ctx->f1RoutePsGen && !ctx->optTwoPass && !instPeriodFor(ctx, ndraws) && !instGroupedFor(ctx, ps, ndraws)
 		&& f1RouteSegmentsFor(ps, ndraws, ctx->f1RouteSegMax) <= ctx->f1RouteSegBound; // (what the last count decided and sized, for this path set)
-	if (!oneWalk) { runCmdPrefix(ctx, ps, draws, ndraws, s, ctx->optTwoPass ? 0u : instPeriodFor(ctx, ndraws)); }
+	if (!oneWalk) { runCmdPrefix(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, s, ctx->optTwoPass ? 0u : instPeriodFor(ctx, ndraws)); }
 	if (oneWalk) {
 		runFlattenOneWalk(ctx, ps, draws, ndraws, s);
 	} else if (ctx->optTwoPass) { // tuning / debugging knob: the ordered two-pass flatten
-		runFlattenCount(ctx, ps, draws, ndraws, s);
+		runFlattenCount(ctx, ps, draws, ndraws, ctx->caps, s);
 		VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, 1);
 		vgx_launch_flatten(true, a, VGX_GRID_BLOCKS, s);
 		mark(ctx, s, "flatten_emit");
 	} else {
 		runFlattenBuild(ctx, ps, draws, ndraws, s);
 	}
-	runStrokeCount(ctx, draws, outCaps, 1, s, nullptr, !ctx->optTwoPass, out->meshes);
+	runStrokeCount(ctx, draws, outCapsFor(ctx, out), 1, s, nullptr, !ctx->optTwoPass, out->meshes);
 	{
 		const int st = runStrokeEmit(ctx, draws, out, s, nullptr, true);
 		if (st != VGX_OK) { return st; }
 	}
-	if (dev_sizes || dev_status) {
-		hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status);
-	}
+	publish(ctx, dev_sizes, dev_status, s);
 	return launchStatus(ctx);
 }
 
 // ---- immediate mode: vgx_tessellate_immediate / vgx_reserve -------------------------------------------------------------
-// The heap of the single-pass flatten for a batch of V polyline vertices, `longV` of them in sub-paths longer than VGX_LONG_SUBPATH, `ncmd`
-// command instances: vgx_tessellate_count's formula (see there), with the lineTo-only layout's one slot per command
-static uint64_t immHeapBuild(const vgx_pathset* ps, uint64_t V, uint64_t ncmd, uint64_t longV)
-{
-	uint64_t h = V * 9 / 4 + 4 * longV + 2 * (uint64_t)VGX_BUILD_WAVES * VGX_BUILD_BLOCK;
-	if ((!ps || ps->thinStatic) && h < 2 * ncmd + 4096) { h = 2 * ncmd + 4096; }
-	return h;
-}
-
-// ... of k_flatten_inst's lane-private blocks (vgx_tessellate_count's formula; instLong = vertices in sub-paths longer than VGX_INST_LONG_SUBPATH)
-static uint64_t immHeapInst(const vgx_ctx* ctx, uint64_t V, uint64_t instLong)
-{
-	const uint64_t grown = (ctx->optInstBlock >= VGX_INST_BLOCK) ? V * 9 / 4 + 8 * instLong : V * 10;
-	return grown + (uint64_t)ctx->optInstWaves * 64 * ctx->optInstBlock + 4096;
-}
-
-// per-command scratch of the flatten kernels (+ the leaf overflow area of k_flatten_build), as vgx_tessellate_count sizes it
-static int immEnsureCmd(vgx_ctx* ctx, uint64_t ncmd)
-{
-	int st;
-	if ((st = ensure(ctx, ctx->cmdCnt, (ncmd + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->subFirst, (ncmd + 1) * sizeof(VgxSubRec))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->leafOverflow, (size_t)VGX_BUILD_WAVES * VGX_BUILD_OVERFLOW * 64 * 2 * sizeof(float))) != VGX_OK) { return st; }
-	ctx->caps.cmd_instances = ctx->cmdCnt.cap / sizeof(uint32_t) - 1;
-	{ const uint64_t c2 = ctx->subFirst.cap / sizeof(VgxSubRec) - 1; if (c2 < ctx->caps.cmd_instances) { ctx->caps.cmd_instances = c2; } }
-	return VGX_OK;
-}
-
 static int immInit(vgx_ctx* ctx)
 {
 	if (ctx->immHost) { return VGX_OK; }
@@ -2134,7 +2118,7 @@ static int immInit(vgx_ctx* ctx)
 }
 
 // The mirror of the last immediate call, if its copy has landed (never waited for): what the batch was, and after VGX_E_GROWN the scratch it
-// needs -- grown here, with vgx_tessellate_count's formulas, the instanced flatten's heap included when its draws repeat a sequence of paths
+// needs -- grown here, the instanced flatten's heap included when its draws reuse paths
 static int immConsume(vgx_ctx* ctx, const vgx_pathset* ps)
 {
 	if (!ctx->immEvPending || hipEventQuery(ctx->immEv) != hipSuccess) { return VGX_OK; }
@@ -2157,12 +2141,11 @@ static int immConsume(vgx_ctx* ctx, const vgx_pathset* ps)
 	ctx->immLong = h.imm_long_subpath_vertices; ctx->immInstLong = h.imm_inst_long_subpath_vertices; ctx->immLongKnown = true;
 	if (h.sizes.num_poly_vertices > 0xFFFFFFF0ull) { return VGX_OK; } // (VGX_E_RANGE territory: nothing sensible to grow to)
 	int st;
-	if ((st = immEnsureCmd(ctx, h.sizes.num_cmd_instances)) != VGX_OK) { return st; }
-	uint64_t heap = immHeapBuild(ps, h.sizes.num_poly_vertices, h.sizes.num_cmd_instances, h.imm_long_subpath_vertices);
+	if ((st = ensureCmdScratch(ctx, h.sizes.num_cmd_instances)) != VGX_OK) { return st; }
+	uint64_t heap = heapBuildVerts(ps, h.sizes.num_poly_vertices, h.sizes.num_cmd_instances, h.imm_long_subpath_vertices);
 	const uint64_t n = ctx->immPendNDraws;
-	const bool reused = ctx->immDistinct != 0 && n < 0xFFFFFFFFull && n / ctx->immDistinct >= VGX_INST_MIN_INSTANCES; // (grouped mode)
-	if (ctx->optInst && ((P && n % P == 0 && n / P >= VGX_INST_MIN_INSTANCES) || reused)) {
-		const uint64_t hi = immHeapInst(ctx, h.sizes.num_poly_vertices, h.imm_inst_long_subpath_vertices);
+	if (periodUsable(ctx, P, n) || pathsReused(ctx, n, ctx->immDistinct)) {
+		const uint64_t hi = heapInstVerts(ctx, h.sizes.num_poly_vertices, h.imm_inst_long_subpath_vertices);
 		if (hi > heap) { heap = hi; }
 	}
 	return ensureMeshBuffers(ctx, heap, h.sizes.num_subpaths, h.sizes.num_meshes);
@@ -2178,10 +2161,10 @@ int vgx_reserve(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals)
 	int st;
 	if ((st = immInit(ctx)) != VGX_OK) { return st; }
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
-	if ((st = immEnsureCmd(ctx, totals->num_cmd_instances)) != VGX_OK) { return st; }
+	if ((st = ensureCmdScratch(ctx, totals->num_cmd_instances)) != VGX_OK) { return st; }
 	// the long sub-paths are not known: every vertex counted as one of them (the heap then holds any batch within these totals)
 	const uint64_t V = totals->num_poly_vertices;
-	return ensureMeshBuffers(ctx, immHeapBuild(nullptr, V, totals->num_cmd_instances, V), totals->num_subpaths, totals->num_meshes);
+	return ensureMeshBuffers(ctx, heapBuildVerts(nullptr, V, totals->num_cmd_instances, V), totals->num_subpaths, totals->num_meshes);
 }
 
 int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out,
@@ -2195,68 +2178,33 @@ int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw
 	int st;
 	if ((st = immInit(ctx)) != VGX_OK) { return st; }
 	// counted state ends here (as with vgx_flatten): the _emit pairing, the template, the routes the last count chose
-	ctx->lastStage = 0; ctx->tmplOn = false; ctx->f1Route = false;
-	ctx->instPeriod = 0; ctx->instGrouped = 0; ctx->instClasses = 1; ctx->instPermOn = 0;
+	ctx->lastStage = 0; ctx->f1Route = false;
+	forgetRoutes(ctx);
 	// (1) the last immediate call's need, when it has reached the mirror; (2) the tables every route needs (a fresh context gets small ones:
 	// its first call ends with VGX_E_GROWN and the exact need)
 	if ((st = immConsume(ctx, ps)) != VGX_OK) { return st; }
-	// Every bound this call trusts is recomputed from the buffers as they stand (allocating only what is missing): whatever another entry point
-	// left in ctx->caps -- a count lifts them for its sizing passes -- never decides how far a kernel of this call may write
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
-	if ((st = immEnsureCmd(ctx, 4096)) != VGX_OK) { return st; }
+	if ((st = ensureCmdScratch(ctx, 4096)) != VGX_OK) { return st; }
 	if ((st = ensureMeshBuffers(ctx, 4096, 1024, 1024)) != VGX_OK) { return st; }
 	markBegin(ctx, s);
 	const uint64_t tag = ps->gen * 0x9E3779B97F4A7C15ull + ndraws;
 	const bool known = ctx->immKnown && ctx->immTag == tag;
 	VgxTotals* T = (VgxTotals*)ctx->totals.p;
-	VgxCaps outCaps = ctx->caps;
-	outCaps.vertices = out->cap_vertices;
-	outCaps.indices = out->cap_indices;
-	if (out->meshes && out->cap_meshes < outCaps.meshes) { outCaps.meshes = out->cap_meshes; }
 	bool detect = false;
 	if (ndraws <= VGX_SMALL_DRAWS && !ctx->optNoSmall) {
 		// frame-sized: vgx_tessellate's five launches; the scan over the draws flags a batch that outgrew the context's tables
-		OpCmdPrefix opC;
-		opC.draws = draws; opC.pathCmdBegin = ps->dev.path_cmd_begin; opC.npaths = ps->dev.npaths; opC.ndraws = ndraws;
-		opC.prefix = (uint64_t*)ctx->cmdPrefix.p; opC.totals = T; opC.cap = ctx->caps.cmd_instances;
-		opC.period = 0; opC.pathSubBegin = ps->dev.path_sub_begin; opC.subPrefix = (uint64_t*)ctx->subPrefix.p;
 		mark(ctx, s, "route_frame"); // (a stage of no length: which route the call took, for the profile)
-		vgx_launch_small_front(&opC, (vgx_draw_info*)ctx->dinfo.p, s);
-		mark(ctx, s, "small_front");
-		VgxFlattenArgs f = flattenArgs(ctx, ps, draws, ndraws, 1);
-		f.build_mode = 1;
-		f.mprep = (VgxMeshPrep*)ctx->mprep.p;
-		vgx_launch_flatten_build(f, ctx->optBuildWaves, s, false);
-		mark(ctx, s, "flatten_build");
-		VgxStrokeArgs sa;
-		sa.draws = draws; sa.poly = (const float*)ctx->poly.p; sa.mdesc = (const VgxMeshDesc*)ctx->mdesc.p;
-		sa.elem_prefix = nullptr; sa.elem_prefix_fill = (const uint64_t*)ctx->elemPrefix.p; sa.elem_prefix_stroke = (const uint64_t*)ctx->elemPrefixS.p;
-		sa.mprep = (VgxMeshPrep*)ctx->mprep.p; sa.mtab = (vgx_mesh*)ctx->mtab.p;
-		sa.pos = nullptr; sa.color = nullptr; sa.idx = nullptr; sa.meshes_out = nullptr; sa.mesh_base = nullptr;
-		sa.totals = T; sa.caps = outCaps; sa.tile_mode = 0; sa.no_long = 1;
-		OpDrawInfo opD;
-		opD.dinfo = (vgx_draw_info*)ctx->dinfo.p; opD.ndraws = ndraws; opD.totals = T; opD.caps = ctx->caps; opD.keepPolyBase = 1; opD.markScratch = 1;
-		OpMeshAll opM;
-		opM.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; opM.mtab = (vgx_mesh*)ctx->mtab.p; opM.meshesOut = out->meshes;
-		opM.prefixFill = (uint64_t*)ctx->elemPrefix.p; opM.prefixStroke = (uint64_t*)ctx->elemPrefixS.p;
-		opM.totals = T; opM.caps = outCaps; opM.checkCaps = 1; opM.fixedSize = 0; opM.fixedCount = 0;
-		vgx_launch_small_middle(f, sa, &opD, &opM, nullptr, nullptr, s);
-		mark(ctx, s, "small_middle");
-		if ((st = runStrokeEmit(ctx, draws, out, s, nullptr, true)) != VGX_OK) { return st; }
+		if ((st = runFrameSized(ctx, ps, draws, ndraws, out, 1, nullptr, nullptr, s)) != VGX_OK) { return st; }
 		vgx_launch_imm_size(ps->dev, draws, ndraws, T, 0, true, dev_sizes, dev_status, s); // (+ the verdict)
 		mark(ctx, s, "imm_size");
 	} else {
 		// Routes from what the last immediate call on this (path set, number of draws) found, with vgx_tessellate_count's rules: draws that
 		// repeat a sequence of paths -> k_flatten_inst (re-checked on the device: k_flatten_build takes over when they stop repeating), when
 		// the heap holds its lane-private blocks; long curves -> the one-walk flatten; else k_flatten_build
-		uint32_t P = 0;
-		if (known && ctx->immPeriod && ctx->optInst && ndraws % ctx->immPeriod == 0 && ndraws / ctx->immPeriod >= VGX_INST_MIN_INSTANCES
-			&& immHeapInst(ctx, ctx->immV, ctx->immLongKnown ? ctx->immInstLong : ctx->immV) <= ctx->caps.poly_vertices) {
-			P = ctx->immPeriod;
-		}
-		// paths reused without a period (>= 32 draws per used path): grouped mode, the draws sorted by path on the device every call
-		if (!P && known && ctx->optInst && ctx->immDistinct != 0 && ndraws < 0xFFFFFFFFull && ndraws / ctx->immDistinct >= VGX_INST_MIN_INSTANCES
-			&& immHeapInst(ctx, ctx->immV, ctx->immLongKnown ? ctx->immInstLong : ctx->immV) <= ctx->caps.poly_vertices) {
+		const bool instFits = heapInstVerts(ctx, ctx->immV, ctx->immLongKnown ? ctx->immInstLong : ctx->immV) <= ctx->caps.poly_vertices;
+		const uint32_t P = known && instFits && periodUsable(ctx, ctx->immPeriod, ndraws) ? ctx->immPeriod : 0;
+		// paths reused without a period: grouped mode, the draws sorted by path on the device every call
+		if (!P && known && instFits && pathsReused(ctx, ndraws, ctx->immDistinct)) {
 			if ((st = ensureInstGroup(ctx, ps->dev.npaths, 1, ndraws, true)) != VGX_OK) { return st; }
 			ctx->instGrouped = 1;
 			if (!instGroupedFor(ctx, ps, ndraws)) { ctx->instGrouped = 0; }
@@ -2264,30 +2212,16 @@ int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw
 		bool oneWalk = false;
 		if (!P && !ctx->instGrouped && known && ctx->optTessFlat1 && !(ps->thinStatic && ctx->optThinStatic) && ctx->immCmd != 0
 			&& (ctx->optTessFlat1 == 2 || ctx->immV >= 10 * ctx->immCmd)) {
-			int cap = 1664; uint32_t segMax = 64; // (as vgx_tessellate_count picks them)
-			const double perChunk = (double)ctx->immV / (double)ctx->immCmd * 64.0;
-			if (perChunk <= 800.0) { cap = 1024; }
-			else if (perChunk > 1500.0) {
-				cap = 3072;
-				const double m = 0.8 * 3072.0 / (perChunk / 64.0);
-				segMax = m >= 64.0 ? 64u : (m >= 32.0 ? 32u : (m >= 16.0 ? 16u : 8u));
-			}
-			if (ctx->optF1Cap) { cap = ctx->optF1Cap; }
-			if (ctx->optF1Seg) { segMax = (uint32_t)ctx->optF1Seg; }
-			const uint64_t segBound = f1RouteSegmentsFor(ps, ndraws, segMax);
-			if (segBound <= (1ull << 24)) {
-				if ((st = ensure(ctx, ctx->f1SegDraw, (segBound + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
-				if ((st = ensure(ctx, ctx->f1Segs, (segBound + segBound / 64 + 2) * sizeof(VgxF1Seg))) != VGX_OK) { return st; }
-				ctx->f1RoutePs = ps; ctx->f1RoutePsGen = ps->gen; ctx->f1RouteCap = cap; ctx->f1RouteSegMax = segMax; ctx->f1RouteSegBound = segBound;
-				oneWalk = true;
-			}
+			int cap; uint32_t segMax;
+			f1Shape(ctx, ctx->immV, ctx->immCmd, &cap, &segMax);
+			if ((st = f1Reserve(ctx, ps, ndraws, cap, segMax, &oneWalk)) != VGX_OK) { return st; }
 		}
 		ctx->instPeriod = P;
 		mark(ctx, s, P ? "route_periodic" : (ctx->instGrouped ? "route_grouped" : (oneWalk ? "route_one_walk" : "route_build"))); // (no length)
 		if (oneWalk) {
 			runFlattenOneWalk(ctx, ps, draws, ndraws, s);
 		} else {
-			runCmdPrefix(ctx, ps, draws, ndraws, s, P);
+			runCmdPrefix(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, s, P);
 			runFlattenBuild(ctx, ps, draws, ndraws, s);
 		}
 		detect = !known && ctx->optInst; // the period of the paths and how many of them the draws use, for the next call on this batch
@@ -2300,7 +2234,7 @@ int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw
 		// the flatten stage checks the context's tables only: a VGX_E_NOSPACE here is the scratch's
 		vgx_launch_imm_size(ps->dev, draws, ndraws, T, 1, false, nullptr, nullptr, s);
 		mark(ctx, s, "imm_size");
-		runStrokeCount(ctx, draws, outCaps, 1, s, nullptr, true, out->meshes);
+		runStrokeCount(ctx, draws, outCapsFor(ctx, out), 1, s, nullptr, true, out->meshes);
 		if ((st = runStrokeEmit(ctx, draws, out, s, nullptr, true)) != VGX_OK) { return st; }
 		vgx_launch_imm_publish(T, dev_sizes, dev_status, s);
 	}
@@ -2420,9 +2354,7 @@ int vgx_cache_submit(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_
 	}
 	vgx_launch_cache_copy(a, vgxElementGrid(out->cap_vertices), s);
 	mark(ctx, s, "cache_copy");
-	if (dev_sizes || dev_status) {
-		hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status);
-	}
+	publish(ctx, dev_sizes, dev_status, s);
 	return launchStatus(ctx);
 }
 
@@ -2471,9 +2403,7 @@ int vgx_merge_uv(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b,
 	}
 	vgx_launch_merge_copy(m, s);
 	mark(ctx, s, "merge_copy");
-	if (dev_sizes || dev_status) {
-		hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status);
-	}
+	publish(ctx, dev_sizes, dev_status, s);
 	return launchStatus(ctx);
 }
 
@@ -2545,9 +2475,7 @@ int vgx_concave_emit(vgx_ctx* ctx, const float* contour_verts, uint64_t num_cont
 	a.totals = (VgxTotals*)ctx->totals.p;
 	vgx_launch_concave_emit(a, s);
 	mark(ctx, s, "concave_emit");
-	if (dev_sizes || dev_status) {
-		hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status);
-	}
+	publish(ctx, dev_sizes, dev_status, s);
 	return launchStatus(ctx);
 }
 
