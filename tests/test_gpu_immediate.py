@@ -48,8 +48,9 @@ def sizes_of(rt, b):
     return rt.capi.Sizes.from_buffer_copy(b.dev_sizes.cpu().numpy().tobytes()).as_dict()
 
 
-def immediate_loop(rt, ctx, pset, dd, n, bufs, check_canaries=True):
-    """The growth loop by hand (tessellate_grow without its buffer swap): guarded buffers, canaries checked after every call."""
+def immediate_loop(rt, ctx, pset, dd, n, bufs, check_canaries=True, after_call=None):
+    """The growth loop by hand (tessellate_grow without its buffer swap): guarded buffers, canaries checked after every call.
+    after_call(status): called after every call once its verdict has been read (test_gpu_immediate_sequences.py collects the stages)."""
     statuses, sizes_seen = [], []
     for _ in range(3):
         rt.tessellate_immediate(ctx, pset, dd, n, bufs)
@@ -57,6 +58,8 @@ def immediate_loop(rt, ctx, pset, dd, n, bufs, check_canaries=True):
         sz = sizes_of(rt, bufs)
         statuses.append(st)
         sizes_seen.append(sz)
+        if after_call:
+            after_call(st)
         if check_canaries:
             assert canaries_intact(bufs), ("overrun", statuses)
         if st == rt.capi.VGX_OK:
