@@ -95,6 +95,10 @@ enum { VGX_JOIN_MITER = 0, VGX_JOIN_ROUND = 1, VGX_JOIN_BEVEL = 2 };
  * itself over in vgx_cmdlist_out::tri_* (positions already through the state transform, as ctxIndexedTriList does with
  * batchTransformPositions) and vgx_merge puts it at the draw's place in the frame. */
 #define VGX_FILL_TRILIST 0x40u
+/* A Text / TextBox command (vg::text, vg::textBox; ctxText src/vg.cpp:4177-4232): the draw has no path and no mesh from
+ * vgx_tessellate; vgx_cmdlist_decode_text hands the command over as a vgx_text_cmd, the caller's FontStash makes the glyph quads,
+ * vgx_text_quads makes the mesh(es) and vgx_merge_uv puts them at the draw's place in the frame. */
+#define VGX_FILL_TEXT 0x80u
 /* vgx_draw.stroke_flags */
 #define VGX_STROKE_ENABLE 0x1u
 #define VGX_STROKE_AA 0x2u
@@ -167,7 +171,8 @@ typedef struct vgx_mesh {
 	uint32_t subpath_kind; /* bits 0-27 sub-path index within the draw, bits 28-31 VGX_MESH_* */
 } vgx_mesh;
 enum { VGX_MESH_FILL = 0, VGX_MESH_FILL_AA = 1, VGX_MESH_STROKE = 2, VGX_MESH_STROKE_AA = 3, VGX_MESH_STROKE_AA_THIN = 4,
-       VGX_MESH_CONCAVE_FILL_AA = 5 /* vgx_concave_emit */, VGX_MESH_TRILIST = 6 /* vgx_cmdlist_out::tri_meshes */ };
+       VGX_MESH_CONCAVE_FILL_AA = 5 /* vgx_concave_emit */, VGX_MESH_TRILIST = 6 /* vgx_cmdlist_out::tri_meshes */,
+       VGX_MESH_TEXT = 7 /* vgx_text_quads */ };
 
 /* Totals of a batch. Filled by the *_count calls (host struct). */
 typedef struct vgx_sizes {
@@ -460,6 +465,48 @@ int vgx_merge(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, co
 int vgx_merge_uv(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, const uint32_t* b_draw, const void* b_uv, const vgx_draw* draws, uint64_t ndraws,
                  const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
 
+/* ---- text: the device half of renderTextQuads (src/vg.cpp:5541-5621) ------------------------------------------
+ * Glyph layout and the atlas (FontStash + stb_truetype) stay with the caller, as libtess2 does for concave fills. What the
+ * reference does AFTER FontStash produced the glyph quads of a string is done here for a batch of strings ("runs"):
+ *   the matrix: ctxText's pushState + transformTranslate(x + dx / scale, y + dy / scale) (:4228-4229, 4055-4062), then the inverse
+ *     font scale folded into m[0..3] (1.0f / scale, :5545-5558);
+ *   vgutil::batchTransformTextQuads (src/vg_util.cpp:332-445): corners (x0,y0) (x1,y0) (x1,y1) (x0,y1) through transformPos2D;
+ *   the colour replicated (memset32, :5575), the UVs (s0,t0) (s1,t0) (s1,t1) (s0,t1) as float pairs or as
+ *     (int16_t)(s * INT16_MAX) pairs (:5577-5613; truncation towards zero, defined for the 0..1 FontStash produces);
+ *   vgutil::genQuadIndices_unaligned (vg_util.cpp:275-330): b, b+1, b+2, b, b+2, b+3 with b = 4 * (quad - first_quad), mesh-local.
+ * One run = one renderTextQuads call = one ctxText = one mesh; a TextBox is one run per row (ctxTextBox, :4234-4271).
+ * The PLACES of a run's vertices and indices are the caller's: a frame's external meshes (`b` of vgx_merge_uv) are one sequence
+ * sorted by draw that may hold user meshes (vgx_cmdlist_out::tri_*) and text runs in any order; the sizes of both are known on
+ * the host (4 and 6 per quad), so the host lays the sequence out and each producer writes at its places.
+ * Not done here: shaping, the atlas and its growth, measureText*, draw-command assembly (that stays vgx_merge_uv's job; this call
+ * ignores vgx_set_assembly). */
+typedef struct vgx_text_run {      /* one renderTextQuads call. 80 bytes */
+	uint64_t first_quad;           /* into quads */
+	uint32_t num_quads;            /* numBakedChars */
+	uint32_t color;                /* colour with the global alpha already folded in (vgx_text_cmd::color) */
+	float mtx[6];                  /* State::m_TransformMtx at the Text command (vgx_text_cmd::mtx) */
+	float x, y;                    /* ctxText's x, y (TextBox: the row's) */
+	float dx, dy;                  /* fonsAlignString's result */
+	float scale;                   /* State::m_FontScale * devicePixelRatio (vgx_text_cmd::scale) */
+	uint32_t draw;                 /* frame draw of the Text command -> vgx_mesh.draw */
+	uint64_t first_vertex;         /* where the mesh goes in out->pos / color (and out_uv); 4 * num_quads vertices */
+	uint64_t first_index;          /* where its 6 * num_quads indices go in out->idx */
+} vgx_text_run;
+/* quads: DEVICE [nquads][8] = FONSquad in its FONS_QUAD_SIMD layout {x0, y0, x1, y1, s0, t0, s1, t1}, 16-byte aligned.
+ * runs: DEVICE [nruns], in quad order without overlap (runs[r + 1].first_quad >= runs[r].first_quad + runs[r].num_quads, the last
+ * one ending inside nquads; else VGX_E_INVALID_ARG in dev_status, the places of the runs then hold undefined data and nothing
+ * outside them is touched); quads between runs are ignored. out_uv: DEVICE
+ * [out->cap_vertices][uv_bytes] or NULL; uv_bytes 0 (none), 4 (int16 x 2) or 8 (float x 2).
+ * One vgx_mesh per run at out->meshes[first_mesh + r] (out->meshes may be NULL): the run's places, 4 n / 6 n, its draw,
+ * subpath_kind = VGX_MESH_TEXT << 28; a run of zero quads writes an empty record. Asynchronous like vgx_concave_emit / vgx_cache_submit
+ * (capacities checked on the device, nothing written past one, no host round trip). dev_status: a run of more than 16 384 quads sets
+ * VGX_E_MESH_TOO_LARGE (the reference VG_CHECKs a command's vertex count, vg.cpp:5323; the uint16 indices would wrap), a place
+ * beyond a capacity VGX_E_NOSPACE, a non-finite matrix or scale (0 included) VGX_E_NONFINITE; such a run writes no vertex and no
+ * index (its record says 0 / 0), the others are written (also one whose RECORD has no room in out->meshes). dev_sizes: num_meshes = first_mesh + nruns, num_vertices / num_indices =
+ * the capacities the placement needs (the highest end of a run: the totals for a dense layout), num_elements = quads in runs. */
+int vgx_text_quads(vgx_ctx* ctx, const float* quads, uint64_t nquads, const vgx_text_run* runs, uint64_t nruns, uint64_t first_mesh,
+                   const vgx_mesh_out* out, void* out_uv, uint32_t uv_bytes, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
+
 /* ---- command-list byte-code as input ---------------------------------------------
  * vg::CommandList::m_CommandBuffer as the reference's cl* functions write it (src/vg.cpp:243-247, 2403-2690, 5694-5723):
  * {CommandHeader{uint32 type, uint32 size}, 16-byte aligned}{payload, 16-byte aligned}... in HOST memory.
@@ -479,8 +526,8 @@ int vgx_merge_uv(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b,
  * VGX_FILL_ENABLE: vgx_tessellate makes no mesh for them, the caller builds it (vgx_flatten_* -> libtess2 -> vgx_concave_move /
  * vgx_concave_emit) and vgx_merge puts it at the draw's place in the frame.
  * IndexedTriList commands become draws with VGX_FILL_TRILIST; their meshes come back in vgx_cmdlist_out::tri_*.
- * Commands without an equivalent here are counted in num_skipped and otherwise ignored: Text / TextBox,
- * path commands issued after a path's first fill / stroke
+ * Commands without an equivalent here are counted in num_skipped and otherwise ignored: Text / TextBox (vgx_cmdlist_decode_text
+ * below turns them into draws), path commands issued after a path's first fill / stroke
  * without a new BeginPath (the reference VG_CHECKs this, :2984-3059), nested lists without a table entry.
  * Host only, no device needed; re-entrant (no shared state between calls). `bytes` must be 4-byte aligned (the reference's
  * buffers are 16-byte aligned). Call with the array members NULL to get the counts, allocate, call again. */
@@ -584,6 +631,49 @@ typedef struct vgx_cmdlist_out {
 	uint32_t num_tri_vertices, num_tri_indices, num_tri_meshes; /* out */
 } vgx_cmdlist_out;
 int vgx_cmdlist_decode(const void* bytes, uint32_t size, const vgx_cmdlist_state* state, vgx_cmdlist_out* out);
+
+/* The same interpreter with Text / TextBox commands (clText / clTextBox, vg.cpp:2914-2957; interpreter :4505-4533) as draws:
+ * vgx_cmdlist_decode is this call with text = NULL. Each command that survives the reference's early-outs -- font_size * scale <
+ * min_font_size (:4184, 4241), an empty string (:4189), colour alpha 0 after the global alpha (:5547-5550) -- becomes one vgx_draw
+ * with VGX_FILL_TEXT and no VGX_FILL_ENABLE (no mesh from vgx_tessellate, like VGX_FILL_TRILIST), state_key = Textured | font_image
+ * with the current generation, its vgx_draw_state record (scissor, clip) and one vgx_text_cmd; the ones dropped are neither draws nor
+ * skipped. Text always folds the global alpha, also in a VGX_CL_CACHEABLE list; command culling does not touch it (:4338 skips the
+ * six fill / stroke commands only); between BeginClip and EndClip it is an ordinary Textured draw (renderTextQuads calls
+ * allocDrawCommand whatever m_RecordClipCommands says); a path being built is left alone. ctxText's own pushState / popState
+ * restore the state they found and no scissor changes in between, so no generation changes. String ranges outside strings_size
+ * return VGX_E_INVALID_ARG (the reference only VG_CHECKs, :4512-4513). Count pass with texts = NULL (num_texts), VGX_E_NOSPACE for
+ * a too small array. Nested lists (SubmitCommandList) share `strings` with their parent here: offsets of a nested list's text
+ * must be relative to the same buffer.
+ * From a vgx_text_cmd to vgx_text_run records: the caller's shaper (fonsSetSize(font_size * scale), fonsBakeString,
+ * fonsAlignString) makes the quads and dx / dy; a Text command is one run at (x, y); a TextBox is handed over whole -- the
+ * shaper breaks the rows (textBreakLines) and makes one run per row with ctxTextBox's per-row x / y and the FONS_ALIGN_LEFT | valign
+ * alignment (:4245-4267); the runs of one command share its draw, which vgx_merge accepts (non-decreasing b_draw).
+ * Out of scope: shaping, the atlas and its growth (allocTextAtlas switches m_FontImageID mid-frame; a decode has ONE font_image,
+ * a caller whose atlas grew rewrites the handle in the state_key of later text draws), measureText*, text inside a Cacheable
+ * list's shape cache. */
+typedef struct vgx_text_cmd {      /* one Text / TextBox command. 76 bytes */
+	uint32_t draw;                 /* its draw in this decode */
+	uint32_t kind;                 /* 0 Text, 1 TextBox */
+	uint32_t font;                 /* TextConfig as recorded: m_FontHandle.idx, m_FontSize, m_Alignment */
+	float font_size;
+	uint32_t alignment;
+	uint32_t color;                /* colorSetAlpha(cfg.color, (uint8_t)(globalAlpha * alpha)), vg.cpp:5547 */
+	float x, y, break_width;       /* break_width: TextBox only */
+	uint32_t textbox_flags;
+	uint32_t string_offset, string_len; /* into CommandList::m_StringBuffer */
+	float scale;                   /* State::m_FontScale (updateState's 0.1 quantisation, vg.cpp:4937-4942) * device_pixel_ratio */
+	float mtx[6];                  /* State::m_TransformMtx at the command */
+} vgx_text_cmd;
+typedef struct vgx_cmdlist_text {
+	const char* strings;           /* in: HOST CommandList::m_StringBuffer (only the ranges are checked, the bytes are not read) */
+	uint32_t strings_size;         /* in: m_StringBufferPos */
+	float device_pixel_ratio;      /* in: Context::m_DevicePixelRatio */
+	float min_font_size;           /* in: VG_CONFIG_MIN_FONT_SIZE; 0 = 4.0 */
+	vgx_text_cmd* texts;           /* out: HOST [cap_texts]; NULL = count */
+	uint32_t cap_texts;            /* in */
+	uint32_t num_texts;            /* out */
+} vgx_cmdlist_text;
+int vgx_cmdlist_decode_text(const void* bytes, uint32_t size, const vgx_cmdlist_state* state, vgx_cmdlist_out* out, vgx_cmdlist_text* text);
 
 /* Diagnostics of the last asynchronous call on this context: the device status word and, when a kernel of
  * vgx_tessellate gave up, why (reason = one of the VGX_FAIL_* codes of csrc/vgx_internal_types.h: a table of

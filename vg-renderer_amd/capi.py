@@ -20,6 +20,7 @@ VGX_E_INTERNAL = 9
 VGX_E_STALE = 10
 VGX_E_GROWN = 11  # vgx_tessellate_immediate: the batch outgrew the context's scratch (the next immediate call grows it)
 FILL_TRILIST = 0x40  # vgx_draw.fill_flags: a user mesh (IndexedTriList): the decoder's tri_* arrays + vgx_merge_uv
+FILL_TEXT = 0x80  # vgx_draw.fill_flags: a Text / TextBox command (vgx_cmdlist_decode_text): caller's shaper + vgx_text_quads + vgx_merge_uv
 FILL_CONCAVE, FILL_EVEN_ODD = 0x10, 0x20  # vgx_draw.fill_flags: a concave fill (no GPU mesh: libtess2 + vgx_concave_* + vgx_merge)
 
 CMD_MOVE_TO, CMD_LINE_TO, CMD_CUBIC_TO, CMD_QUAD_TO, CMD_CLOSE = 0, 1, 2, 3, 4
@@ -35,6 +36,7 @@ FILL_INDEX_ORDER_SSE = 0x100  # strokerConvexFillAA indices in the order of the 
 STROKE_ENABLE, STROKE_AA, STROKE_THIN = 0x1, 0x2, 0x4
 
 MESH_FILL, MESH_FILL_AA, MESH_STROKE, MESH_STROKE_AA, MESH_STROKE_AA_THIN, MESH_CONCAVE_FILL_AA, MESH_TRILIST = 0, 1, 2, 3, 4, 5, 6
+MESH_TEXT = 7  # vgx_text_quads
 
 
 def stroke_flags(cap, join, aa=True, thin=False):
@@ -70,6 +72,13 @@ concave_fill_dtype = np.dtype([("first_contour", "<u8"), ("num_contours", "<u4")
                                ("num_tess_vertices", "<u4"), ("num_tess_indices", "<u4"), ("reserved", "<u4"),
                                ("first_tess_vertex", "<u8"), ("first_tess_index", "<u8")])
 assert concave_fill_dtype.itemsize == 48
+text_run_dtype = np.dtype([("first_quad", "<u8"), ("num_quads", "<u4"), ("color", "<u4"), ("mtx", "<f4", (6,)), ("x", "<f4"), ("y", "<f4"),
+                           ("dx", "<f4"), ("dy", "<f4"), ("scale", "<f4"), ("draw", "<u4"), ("first_vertex", "<u8"), ("first_index", "<u8")])
+assert text_run_dtype.itemsize == 80
+text_cmd_dtype = np.dtype([("draw", "<u4"), ("kind", "<u4"), ("font", "<u4"), ("font_size", "<f4"), ("alignment", "<u4"), ("color", "<u4"),
+                           ("x", "<f4"), ("y", "<f4"), ("break_width", "<f4"), ("textbox_flags", "<u4"), ("string_offset", "<u4"),
+                           ("string_len", "<u4"), ("scale", "<f4"), ("mtx", "<f4", (6,))])
+assert text_cmd_dtype.itemsize == 76
 drawcmd_dtype = np.dtype([
     ("first_vertex", "<u8"), ("first_index", "<u8"), ("first_mesh", "<u8"), ("num_vertices", "<u4"), ("num_indices", "<u4"),
     ("num_meshes", "<u4"), ("vertex_buffer", "<u4"), ("first_vertex_in_vb", "<u4"), ("state_key", "<u4")])
@@ -154,6 +163,11 @@ class CmdListOut(C.Structure):
                 ("num_tri_vertices", C.c_uint32), ("num_tri_indices", C.c_uint32), ("num_tri_meshes", C.c_uint32)]
 
 
+class CmdListText(C.Structure):
+    _fields_ = [("strings", C.c_void_p), ("strings_size", C.c_uint32), ("device_pixel_ratio", C.c_float), ("min_font_size", C.c_float),
+                ("texts", C.c_void_p), ("cap_texts", C.c_uint32), ("num_texts", C.c_uint32)]
+
+
 draw_state_dtype = np.dtype([("scissor", "<u2", (4,)), ("clip_rule", "<u4"), ("clip_first_draw", "<u4"), ("clip_num_draws", "<u4"), ("raw_color", "<u4")])
 paint_dtype = np.dtype([("type", "<u4"), ("handle", "<u4"), ("matrix", "<f4", (9,)), ("params", "<f4", (4,)), ("inner_color", "<f4", (4,)),
                         ("outer_color", "<f4", (4,)), ("image", "<u4")])
@@ -208,6 +222,9 @@ VGX_SYMBOLS = {
     "vgx_concave_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_cmdlist_decode": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CmdListState), C.POINTER(CmdListOut)]),
+    "vgx_cmdlist_decode_text": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CmdListState), C.POINTER(CmdListOut), C.POINTER(CmdListText)]),
+    "vgx_text_quads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_uint32,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_get_failure_info": (C.c_int, [C.c_void_p, C.POINTER(FailureInfo), C.c_void_p]),
     "vgx_gather_sizes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RankSizes), C.POINTER(RankSizes), C.c_void_p]),
     "vgx_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(MeshOut), C.POINTER(RankSizes), C.POINTER(MeshOut), C.c_void_p]),

@@ -6,9 +6,11 @@ import numpy as np
 
 def decode(rt, data, mtx=(1, 0, 0, 1, 0, 0), global_alpha=1.0, tess_tol=0.25, fringe=1.0, canvas=(1280.0, 720.0), flags=0,
            lists=None, first_gradient=0, first_image_pattern=0, extra=None, scissor=None, prev_cmd_scissor=None, first_generation=0, clip=None, draw_base=0,
-           white_uv=None, font_image=0, uv_float=False, time_reps=0):
+           white_uv=None, font_image=0, uv_float=False, time_reps=0, text=None):
     """vgx_cmdlist_decode, count pass + store pass. Returns (status, PathSetArrays or None, draws ndarray, info dict).
-    lists: {handle: (bytes, flags)} for SubmitCommandList. extra: dict that receives draw_state / paints / the out struct."""
+    lists: {handle: (bytes, flags)} for SubmitCommandList. extra: dict that receives draw_state / paints / the out struct.
+    text: None = vgx_cmdlist_decode (Text / TextBox are skipped); a dict(strings_size=..., device_pixel_ratio=1.0, min_font_size=0.0) =
+    vgx_cmdlist_decode_text: Text / TextBox become VGX_FILL_TEXT draws and extra["texts"] receives their vgx_text_cmd records."""
     import ctypes as C
     import importlib
     capi = rt.capi
@@ -48,7 +50,17 @@ def decode(rt, data, mtx=(1, 0, 0, 1, 0, 0), global_alpha=1.0, tess_tol=0.25, fr
         st.lists = arr; st.num_lists = n
     out = capi.CmdListOut()
     buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
-    rc = rt.lib().vgx_cmdlist_decode(buf, len(data), C.byref(st), C.byref(out))
+    txt = None
+    if text is not None:
+        txt = capi.CmdListText()
+        txt.strings_size = int(text.get("strings_size", 0))
+        txt.device_pixel_ratio = float(text.get("device_pixel_ratio", 1.0)); txt.min_font_size = float(text.get("min_font_size", 0.0))
+
+    def call():
+        if txt is None:
+            return rt.lib().vgx_cmdlist_decode(buf, len(data), C.byref(st), C.byref(out))
+        return rt.lib().vgx_cmdlist_decode_text(buf, len(data), C.byref(st), C.byref(out), C.byref(txt))
+    rc = call()
     if rc != 0:
         return rc, None, None, None
     n = {k: int(getattr(out, "num_" + k)) for k in ("cmds", "args", "paths", "draws", "skipped")}
@@ -70,12 +82,16 @@ def decode(rt, data, mtx=(1, 0, 0, 1, 0, 0), global_alpha=1.0, tess_tol=0.25, fr
     if tm:
         out.tri_pos, out.tri_color, out.tri_uv, out.tri_idx, out.tri_meshes = (tri[k].ctypes.data for k in ("pos", "color", "uv", "idx", "meshes"))
         out.cap_tri_vertices, out.cap_tri_indices, out.cap_tri_meshes = tv, ti, tm
-    rc = rt.lib().vgx_cmdlist_decode(buf, len(data), C.byref(st), C.byref(out))
+    ntexts = int(txt.num_texts) if txt is not None else 0
+    texts = np.zeros(max(ntexts, 1), capi.text_cmd_dtype)
+    if txt is not None:
+        txt.texts, txt.cap_texts = texts.ctypes.data, ntexts
+    rc = call()
     if time_reps and extra is not None:  # the store pass again, timed (the C call alone: what a host pays per frame for the decode)
         import time
         t0 = time.perf_counter()
         for _ in range(int(time_reps)):
-            rt.lib().vgx_cmdlist_decode(buf, len(data), C.byref(st), C.byref(out))
+            call()
         extra["decode_seconds"] = (time.perf_counter() - t0) / int(time_reps)
     ps = pathset.PathSetArrays(cmd_type[:n["cmds"]], arg_off, args[:n["args"]], pcb)
     if extra is not None:
@@ -83,4 +99,6 @@ def decode(rt, data, mtx=(1, 0, 0, 1, 0, 0), global_alpha=1.0, tess_tol=0.25, fr
         extra["paints"] = paints[:npaints]
         extra["out"] = out
         extra["tri"] = dict(pos=tri["pos"][:tv], color=tri["color"][:tv], uv=tri["uv"][:tv], idx=tri["idx"][:ti], meshes=tri["meshes"][:tm])
+        if txt is not None:
+            extra["texts"] = texts[:ntexts]
     return rc, ps, draws[:n["draws"]], n

@@ -23,7 +23,7 @@
 #include <string.h>
 #include <vector>
 
-static_assert(sizeof(vgx_draw_state) == 24 && sizeof(vgx_paint) == 96 && sizeof(vgx_cmdlist_ref) == 16, "vgx.h layout");
+static_assert(sizeof(vgx_draw_state) == 24 && sizeof(vgx_paint) == 96 && sizeof(vgx_cmdlist_ref) == 16 && sizeof(vgx_text_cmd) == 76 && sizeof(vgx_cmdlist_text) == 40, "vgx.h layout");
 
 namespace {
 
@@ -43,13 +43,15 @@ const uint32_t kAlign = 16;       // VG_CONFIG_COMMAND_LIST_ALIGNMENT, vg.cpp:40
 const uint32_t kHeaderSize = 16;  // alignSize(sizeof(CommandHeader), 16), vg.cpp:708
 const uint32_t kBlack = 0xFF000000u; // Colors::Black
 
-struct St { float m[6]; float scissor[4]; float alpha; float avgScale; }; // vg::State, vg.cpp:62-69
+struct St { float m[6]; float scissor[4]; float alpha; float avgScale; float fontScale; }; // vg::State, vg.cpp:62-69
 
-void updateState(St& s) // vg.cpp:4927-4935
+void updateState(St& s) // vg.cpp:4927-4944
 {
 	const float sx = vgm_sqrt(s.m[0] * s.m[0] + s.m[2] * s.m[2]);
 	const float sy = vgm_sqrt(s.m[1] * s.m[1] + s.m[3] * s.m[3]);
 	s.avgScale = (sx + sy) * 0.5f;
+	const float quantFactor = 0.1f; // m_FontScale: the average scale in steps of 0.1 (:4937-4942)
+	s.fontScale = (vgm_floor((s.avgScale / quantFactor) + 0.5f)) * quantFactor;
 }
 
 void mul3(const float* a, const float* b, float* r) // vgutil::multiplyMatrix3, vg_util.h:36-44
@@ -145,6 +147,8 @@ struct Decoder
 	uint32_t rawColor = 0; // Color operand of the paint command being decoded (vgx_draw_state::raw_color)
 	bool emitHasMesh = false; // the draw being emitted certainly allocates a draw command (IndexedTriList)
 	uint32_t ntriM = 0, ntriV = 0, ntriI = 0; // IndexedTriList meshes / vertices / indices so far
+	vgx_cmdlist_text* text = nullptr; // vgx_cmdlist_decode_text: Text / TextBox commands become draws + records
+	uint32_t ntexts = 0;
 	void emit(uint32_t type, uint32_t handle, uint32_t fillFlags, uint32_t fillColor, uint32_t strokeFlags, uint32_t strokeColor, float strokeWidth)
 	{
 		const St& s = S();
@@ -557,7 +561,44 @@ int Decoder::run(const uint8_t* p, uint32_t size, uint32_t listFlags)
 			// the draw record carries the state transform (informative: the positions above are already transformed)
 			if (store && ndraws - 1 < out->cap_draws) { memcpy(out->draws[ndraws - 1].mtx, S().m, sizeof(float) * 6); }
 		} break;
-		default: ++nskipped; break; // Text, TextBox
+		case CT_Text: case CT_TextBox: { // TextConfig{uint16 font, float size, uint32 alignment, Color}, float x, y[, breakWidth], uint32 offset, len[, flags]
+			// (clText / clTextBox vg.cpp:2914-2957; interpreter :4505-4533 -> ctxText :4177-4232 / ctxTextBox :4234-4271)
+			if (!text) { ++nskipped; break; }
+			const bool box = type == CT_TextBox;
+			if (!need(box ? 40u : 32u)) { return VGX_E_INVALID_ARG; }
+			const uint32_t color = u32at(12);
+			const uint32_t o = box ? 28u : 24u;
+			const uint32_t strOff = u32at(o), strLen = u32at(o + 4);
+			if (strOff >= text->strings_size || strLen > text->strings_size - strOff) { return VGX_E_INVALID_ARG; } // VG_CHECKs, :4512-4513
+			const St& s = S();
+			const float scale = s.fontScale * text->device_pixel_ratio;
+			const float minSize = text->min_font_size != 0.0f ? text->min_font_size : 4.0f; // VG_CONFIG_MIN_FONT_SIZE
+			if (f32at(4) * scale < minSize) { break; }   // :4183-4186, 4240-4243
+			if (strLen == 0) { break; }                  // :4189-4191
+			const uint32_t c = setAlpha(color, (uint8_t)(s.alpha * (float)(color >> 24))); // renderTextQuads :5547: always the state's alpha
+			if ((c >> 24) == 0) { break; }               // :5548-5550
+			if (store) {
+				if (!text->texts || ntexts >= text->cap_texts) { overflow = true; }
+				else {
+					vgx_text_cmd& tc = text->texts[ntexts];
+					memset(&tc, 0, sizeof(tc));
+					tc.draw = ndraws; tc.kind = box ? 1u : 0u;
+					tc.font = u16at(0); tc.font_size = f32at(4); tc.alignment = u32at(8); tc.color = c;
+					tc.x = f32at(16); tc.y = f32at(20); tc.break_width = box ? f32at(24) : 0.0f; tc.textbox_flags = box ? u32at(36) : 0u;
+					tc.string_offset = strOff; tc.string_len = strLen;
+					tc.scale = scale;
+					memcpy(tc.mtx, s.m, sizeof(float) * 6);
+				}
+			}
+			++ntexts;
+			rawColor = color;
+			if (!havePath) { beginPath(); } // as for IndexedTriList: the draw record needs a valid path index; an open path is left alone
+			emitHasMesh = true; // renderTextQuads calls allocDrawCommand (:5566): the PopState rule sees a draw command
+			emit(DT_Textured, st0->font_image, VGX_FILL_TEXT, c, 0, 0, 0.0f);
+			emitHasMesh = false;
+			if (store && ndraws - 1 < out->cap_draws) { memcpy(out->draws[ndraws - 1].mtx, S().m, sizeof(float) * 6); }
+		} break;
+		default: ++nskipped; break;
 		}
 	}
 	--depth;
@@ -568,11 +609,16 @@ int Decoder::run(const uint8_t* p, uint32_t size, uint32_t listFlags)
 
 extern "C" int vgx_cmdlist_decode(const void* bytes, uint32_t size, const vgx_cmdlist_state* st0, vgx_cmdlist_out* out)
 {
+	return vgx_cmdlist_decode_text(bytes, size, st0, out, nullptr);
+}
+
+extern "C" int vgx_cmdlist_decode_text(const void* bytes, uint32_t size, const vgx_cmdlist_state* st0, vgx_cmdlist_out* out, vgx_cmdlist_text* text)
+{
 	if ((!bytes && size) || !st0 || !out || (size % kAlign) != 0 || ((uintptr_t)bytes & 3u) != 0) { // float operands are read in place: 4-byte aligned buffer
 		return VGX_E_INVALID_ARG;
 	}
 	Decoder D;
-	D.st0 = st0; D.out = out;
+	D.st0 = st0; D.out = out; D.text = text;
 	D.store = out->cmd_type && out->cmd_arg_off && out->args && out->path_cmd_begin && out->draws; // else: count only
 	D.overflow = false;
 	D.npaths = D.ncmd = D.nargs = D.ndraws = D.nskipped = D.npaints = 0;
@@ -606,6 +652,7 @@ extern "C" int vgx_cmdlist_decode(const void* bytes, uint32_t size, const vgx_cm
 	D.closePathRecord();
 	out->num_paths = D.npaths; out->num_cmds = D.ncmd; out->num_args = D.nargs; out->num_draws = D.ndraws; out->num_paints = D.npaints;
 	out->num_skipped = D.nskipped;
+	if (text) { text->num_texts = D.ntexts; }
 	out->num_tri_meshes = D.ntriM; out->num_tri_vertices = D.ntriV; out->num_tri_indices = D.ntriI;
 	out->next_gradient = D.nextGradient; out->next_image_pattern = D.nextImagePattern;
 	out->next_generation = D.generation + (D.forceNew ? 1u : 0u);

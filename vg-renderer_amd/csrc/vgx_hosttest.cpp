@@ -247,3 +247,60 @@ int64_t vgxt_pathset_table(const vgx_pathset_desc* d, int which, void* dst, uint
 }
 
 }
+
+#include "vgx_text.h"
+
+extern "C" {
+
+// the matrix vgx_text_quads hands to the per-quad transform for one run (vgx_text.h); returns 1 when it is finite
+int vgxt_text_run_matrix(const vgx_text_run* run, float* m) { return vgx_text_run_matrix(*run, m) ? 1 : 0; }
+
+// vgx_text_quads on the host: the functions of vgx_text.h (the ones the kernel of vgx_text.hip runs one quad per lane) run after run,
+// quad after quad, with the call's contract -- places and capacities as given, nothing written for a run that is too large, not
+// finite or out of place, one mesh record per run, the totals in `sizes` (may be NULL). Returns the status the device call leaves in
+// dev_status (the first failing run's; the device reports one of the failing runs').
+int vgxt_text_quads(const float* quads, uint64_t nquads, const vgx_text_run* runs, uint64_t nruns, uint64_t first_mesh,
+                    const vgx_mesh_out* out, void* out_uv, uint32_t uv_bytes, vgx_sizes* sizes)
+{
+	int status = VGX_OK;
+	uint64_t endV = 0, endI = 0, total = 0;
+	for (uint64_t r = 0; r < nruns; ++r) {
+		const vgx_text_run& run = runs[r];
+		float m[6];
+		int st = vgx_text_run_status(run, m);
+		bool ordered = run.first_quad <= nquads && run.num_quads <= nquads - run.first_quad;
+		if (r > 0) { ordered = ordered && runs[r - 1].first_quad <= run.first_quad && runs[r - 1].num_quads <= run.first_quad - runs[r - 1].first_quad; }
+		if (st == VGX_OK && !ordered) { st = VGX_E_INVALID_ARG; }
+		bool write = false;
+		if (st == VGX_OK) {
+			const uint64_t ev = run.first_vertex + 4ull * run.num_quads, ei = run.first_index + 6ull * run.num_quads;
+			if (ev > endV) { endV = ev; }
+			if (ei > endI) { endI = ei; }
+			total += run.num_quads;
+			write = vgx_text_run_fits(run, out->cap_vertices, out->cap_indices);
+			if (!write) { st = VGX_E_NOSPACE; }
+		}
+		if (out->meshes) {
+			if (first_mesh + r < out->cap_meshes) { out->meshes[first_mesh + r] = vgx_text_run_mesh(run, st == VGX_OK); }
+			else if (st == VGX_OK) { st = VGX_E_NOSPACE; }
+		}
+		if (status == VGX_OK) { status = st; }
+		if (!write) { continue; }
+		for (uint32_t k = 0; k < run.num_quads; ++k) {
+			const float* q = quads + 8 * (run.first_quad + k);
+			const uint64_t v = run.first_vertex + 4ull * k;
+			vgx_text_quad_pos(q, m, out->pos + 2 * v);
+			for (int c = 0; c < 4; ++c) { out->color[v + c] = run.color; }
+			if (out_uv && uv_bytes == 4) { vgx_text_quad_uv16(q, (uint32_t*)out_uv + v); }
+			else if (out_uv && uv_bytes == 8) { vgx_text_quad_uvf(q, (float*)out_uv + 2 * v); }
+			vgx_text_quad_idx(k, out->idx + run.first_index + 6ull * k);
+		}
+	}
+	if (sizes) {
+		memset(sizes, 0, sizeof(*sizes));
+		sizes->num_meshes = first_mesh + nruns; sizes->num_vertices = endV; sizes->num_indices = endI; sizes->num_elements = total;
+	}
+	return status;
+}
+
+}

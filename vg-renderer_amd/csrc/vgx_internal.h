@@ -219,6 +219,26 @@ struct VgxConcaveArgs
 void vgx_launch_concave_move(const VgxConcaveArgs& a, hipStream_t s);
 void vgx_launch_concave_emit(const VgxConcaveArgs& a, hipStream_t s);
 
+// text runs (vgx_text.hip)
+struct VgxTextArgs
+{
+	const float* quads;
+	uint64_t nquads;
+	const vgx_text_run* runs;
+	uint64_t nruns;
+	uint64_t first_mesh;
+	float* pos;
+	uint32_t* color;
+	uint16_t* idx;
+	vgx_mesh* meshes;          // may be null
+	void* uv;                  // may be null
+	uint32_t uv_bytes;         // 4 or 8 when uv is set
+	uint64_t cap_vertices, cap_indices, cap_meshes;
+	uint32_t* tile_run;        // [tiles of quads] scratch: the first run of every tile; null = one launch, the tiles search
+	VgxTotals* totals;
+};
+void vgx_launch_text_quads(const VgxTextArgs& a, hipStream_t s);
+
 // launchers (defined in the .hip files)
 void vgx_launch_flatten(bool emit, const VgxFlattenArgs& a, int numBlocks, hipStream_t s);
 void vgx_launch_flatten_build(const VgxFlattenArgs& a, int waves, hipStream_t s, bool serialCount = true);   // single-pass: subdivide once, polyline -> heap

@@ -484,6 +484,31 @@ def concave_emit(ctx, contour_verts_dev, contours_dev, ncontours, fills_dev, nfi
                                   bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_concave_emit")
 
 
+# ---- text runs (vgx_text_quads): glyph layout and the atlas stay with the caller -------------------------------------
+def text_runs_dense(runs, first_vertex=0, first_index=0):
+    """The dense layout for a vgx_text_run array (capi.text_run_dtype, first_quad / num_quads set): every run's vertices and
+    indices directly behind its predecessor's, the first at (first_vertex, first_index). With runs that cover the quads
+    without gaps from quad 0 this is first_vertex = 4 * first_quad, first_index = 6 * first_quad. In place; returns
+    (vertices, indices) = the end of the last run."""
+    import numpy as np
+    n = runs["num_quads"].astype(np.uint64)
+    before = np.cumsum(n) - n
+    runs["first_vertex"] = np.uint64(first_vertex) + np.uint64(4) * before
+    runs["first_index"] = np.uint64(first_index) + np.uint64(6) * before
+    total = int(n.sum())
+    return int(first_vertex) + 4 * total, int(first_index) + 6 * total
+
+
+def text_quads(ctx, quads_dev, nquads, runs_dev, nruns, bufs, first_mesh=0, uv_dev=None, uv_bytes=0):
+    """One mesh per run at the run's places in `bufs` (see include/vgx.h). quads_dev: float32 [nquads, 8] device tensor
+    (FONSquad), runs_dev: uint8 device tensor of 80-byte vgx_text_run records, uv_dev: the UV stream ([cap_vertices] x
+    uv_bytes) or None. Asynchronous; totals / status land in bufs.dev_*."""
+    out = bufs.out_struct()
+    _check(lib().vgx_text_quads(ctx.handle, quads_dev.data_ptr() if nquads else None, nquads, runs_dev.data_ptr() if nruns else None, nruns,
+                                first_mesh, C.byref(out), uv_dev.data_ptr() if uv_dev is not None else None, uv_bytes if uv_dev is not None else 0,
+                                bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_text_quads")
+
+
 # ---- merging external meshes into a frame (vgx_merge) ---------------------------------------------------------------
 def mesh_seq(bufs, nv, ni, nm):
     """A finished mesh sequence (what vgx_tessellate / vgx_concave_emit wrote into `bufs`) as a vgx_cache_desc."""
