@@ -365,6 +365,82 @@ int vgx_reserve(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals);
 int vgx_stroke_count(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths, const vgx_draw* draws, uint64_t ndraws, vgx_sizes* out_sizes, void* stream);
 int vgx_stroke_emit(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out, void* stream);
 
+/* ---- dashed strokes (beyond the reference): vgx_flatten -> vgx_subpath_draws -> vgx_dash -> vgx_stroke_* ----------
+ * SVG stroke-dasharray / stroke-dashoffset for the stroker-level boundary: vgx_dash cuts every vertex list of a dashed draw into
+ * its "on" pieces, on the device; the pieces are ordinary open vertex lists for vgx_stroke_count / vgx_stroke_emit. The reference
+ * has no dashes, so the pass is pinned to the specification below (tests/dash_model.py is its sequential model).
+ * Units: the lists are the TRANSFORMED polylines, so pattern and phase are device units: multiply user-space lengths by
+ * vgx_draw::scale, as ctxStrokePath* does for the stroke width (vg.cpp:3416).
+ * Fills: dashing concerns the stroke only. vgx_stroke_* fills any list of >= 3 vertices whose draw has VGX_FILL_ENABLE, so stroke
+ * the dashed lists with draws whose fill_flags are 0 and fill from the undashed lists.
+ *
+ * Specification, for a source list V_0 .. V_{n-1} with closed flag c whose draw has count > 0:
+ *   Segments       m = n when closed, else n - 1; segment i runs from V_i to V_{(i+1) mod n}. n < 2: no output.
+ *   Segment length dx = bx - ax, dy = by - ay, len_i = sqrtf(dx*dx + dy*dy): every operation rounded to float32, no FMA.
+ *   Fixed point    q(x) = (uint64)((double)x * 65536.0 + 0.5). S_0 = 0, S_{i+1} = S_i + q(len_i), T = S_m, in uint64: integer
+ *                  prefix sums, any scan order gives the same values.
+ *   Pattern        p_k = q(pattern[first + k]), A_k = sum of p_j for j < k, P = A_count, f = q(phase) mod P.
+ *   Validation     entries finite, >= 0 and below 2^40; P > 0; count even and <= VGX_DASH_MAX; first + count <= npattern; phase finite,
+ *                  >= 0 and below 2^40; reserved == 0 (records with count == 0 obey all rules but P > 0). Every entry of pattern[],
+ *                  referenced or not, must be finite, >= 0 and below 2^40.
+ *   "On" intervals for integer r and even k: [r P + A_k - f, r P + A_{k+1} - f) intersected with [0, T].
+ *   Snapping       each of the two ends c, with D = 256 (2^-8 units) and i the largest index < m with S_i <= c:
+ *                  c - S_i <= D: c := S_i; otherwise S_{i+1} - c <= D: c := S_{i+1}. An interval with e <= s after snapping produces
+ *                  nothing. Cuts stay off the vertices: no piece starts or ends with a segment below the reference's VG_EPSILON.
+ *   Pieces         X(s), then every V_{j mod n} with s < S_j < e for j = 1 .. m in order, then X(e): an open list, flags = 0.
+ *   X(c)           c equals some S_j: the vertex itself, bit for bit (several such j, from zero-length segments: the largest for a
+ *                  start, the smallest for an end). Otherwise, inside segment i: t = (float)((double)(c - S_i) / (double)(S_{i+1} - S_i)),
+ *                  X = (ax + (bx - ax)*t, ay + (by - ay)*t) in float32 without FMA.
+ *   Output order   source lists in input order, pieces by increasing s, vertices contiguous; subpath_draw = the source list's draw,
+ *                  subpath_src = its index.
+ *   Undashed draws a list whose draw has count == 0 is copied verbatim, with its closed flag and any n.
+ *   Closed lists   the last piece is not merged with the first.
+ * Example: the closed square (0,0)(10,0)(10,10)(0,10), pattern [4,2], phase 1: (0,0)(3,0) | (5,0)(9,0) | (10,1)(10,5) |
+ * (10,7)(10,10)(9,10) | (7,10)(3,10) | (1,10)(0,10)(0,7) | (0,5)(0,1). */
+#define VGX_DASH_MAX 32
+struct vgx_dash {           /* one per draw, 16 bytes. No typedef: the name vgx_dash is the call's; write `struct vgx_dash` */
+	uint32_t first;         /* into pattern[] */
+	uint32_t count;         /* 0: the draw is not dashed (its lists pass through); else even, 2..VGX_DASH_MAX */
+	float    phase;         /* >= 0, finite; same units as pattern */
+	uint32_t reserved;      /* 0 */
+};
+typedef struct vgx_dash_out {
+	float*       poly;          /* DEVICE [cap_poly_vertices][2] */
+	vgx_subpath* subpaths;      /* DEVICE [cap_subpaths] */
+	uint32_t*    subpath_draw;  /* DEVICE [cap_subpaths]: draw of the source list */
+	uint32_t*    subpath_src;   /* DEVICE [cap_subpaths], may be NULL: index of the source list */
+	uint64_t cap_poly_vertices, cap_subpaths;
+} vgx_dash_out;
+/* The validation rules above for HOST arrays (needs no device): VGX_OK or VGX_E_INVALID_ARG. */
+int vgx_dash_validate(const struct vgx_dash* dashes, uint64_t ndraws, const float* pattern, uint64_t npattern);
+/* poly / subpaths / subpath_draw: the triple vgx_stroke_* takes; dashes [ndraws] and pattern [npattern]: all DEVICE pointers.
+ * _count fills num_poly_vertices and num_subpaths of a host vgx_sizes, with one stream sync, and returns the batch's verdict
+ * (VGX_E_INVALID_ARG / VGX_E_RANGE as below). It also sizes the context's scratch for the batch.
+ * vgx_dash is the asynchronous steady-state form, like vgx_flatten: capacities are checked on the device, dev_sizes (DEVICE, may be
+ * NULL) receives the totals and dev_status (DEVICE uint32, may be NULL)
+ *   VGX_OK;
+ *   VGX_E_NOSPACE      a capacity of `out` is too small: dev_sizes is exact, nothing is written past a capacity (nothing at all);
+ *   VGX_E_INVALID_ARG  a dash record or pattern entry breaks the rules, or a subpath_draw entry is >= ndraws: found by a flagged
+ *                      reduction, as the path-set grammar check is; nothing is written;
+ *   VGX_E_RANGE        a non-finite segment length, a list longer than 2^62 fixed units (or of 2^31 vertices), or more than 2^32 - 1 "on"
+ *                      intervals in the call -- counted as the pairs (r, k) with r P + A_k - f < T and r P + A_{k+1} - f > 0 over the dashed
+ *                      lists, plus one per undashed list; a pattern far finer than the lists are long: split the batch; nothing is written;
+ *   VGX_E_GROWN        the lists have more segments than the context's scratch holds (8 + 8 bytes per segment: S and an overflow guard).
+ *                      The scratch is sized by vgx_dash_count, else from out->cap_poly_vertices; as with vgx_tessellate_immediate nothing is
+ *                      written, the need goes to the context and the next vgx_dash grows the scratch first: call again. A
+ *                      vgx_dash_count of the same batch on the context beforehand rules this out.
+ * Work is distributed by OUTPUT: one lane per "on" interval, then one lane per output vertex, whatever the lengths of the segments.
+ * Counted state: both calls end any counted state of the context, as vgx_flatten does (count again before the next
+ * vgx_tessellate_emit, vgx_stroke_emit or template-mode vgx_tessellate). */
+int vgx_dash_count(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths,
+                   const struct vgx_dash* dashes, uint64_t ndraws, const float* pattern, uint64_t npattern, vgx_sizes* out_sizes, void* stream);
+int vgx_dash(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths,
+             const struct vgx_dash* dashes, uint64_t ndraws, const float* pattern, uint64_t npattern,
+             const vgx_dash_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
+/* vgx_flat_out::draw_info -> the subpath_draw array vgx_stroke_* and vgx_dash take: subpath_draw[i] = the draw whose sub-paths
+ * [first_subpath, first_subpath + num_subpaths) hold i, for i < nsubpaths. All DEVICE pointers; asynchronous. */
+int vgx_subpath_draws(vgx_ctx* ctx, const vgx_draw_info* draw_info, uint64_t ndraws, uint32_t* subpath_draw, uint64_t nsubpaths, void* stream);
+
 /* ---- draw-command assembly (see vgx_drawcmd / vgx_assembly above) ------------
  * Arms (asm_ != NULL) or disarms (NULL) assembly for the following vgx_tessellate_emit / vgx_tessellate calls on this
  * context. While armed, the uint16 indices in `idx` are vertex-buffer relative (mesh-local index + vertices in front of

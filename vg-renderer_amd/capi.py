@@ -79,6 +79,9 @@ text_cmd_dtype = np.dtype([("draw", "<u4"), ("kind", "<u4"), ("font", "<u4"), ("
                            ("x", "<f4"), ("y", "<f4"), ("break_width", "<f4"), ("textbox_flags", "<u4"), ("string_offset", "<u4"),
                            ("string_len", "<u4"), ("scale", "<f4"), ("mtx", "<f4", (6,))])
 assert text_cmd_dtype.itemsize == 76
+dash_dtype = np.dtype([("first", "<u4"), ("count", "<u4"), ("phase", "<f4"), ("reserved", "<u4")])  # struct vgx_dash
+assert dash_dtype.itemsize == 16
+DASH_MAX = 32
 drawcmd_dtype = np.dtype([
     ("first_vertex", "<u8"), ("first_index", "<u8"), ("first_mesh", "<u8"), ("num_vertices", "<u4"), ("num_indices", "<u4"),
     ("num_meshes", "<u4"), ("vertex_buffer", "<u4"), ("first_vertex_in_vb", "<u4"), ("state_key", "<u4")])
@@ -104,6 +107,11 @@ class PathSetDesc(C.Structure):
 
 class FlatOut(C.Structure):
     _fields_ = [("poly", C.c_void_p), ("subpaths", C.c_void_p), ("draw_info", C.c_void_p),
+                ("cap_poly_vertices", C.c_uint64), ("cap_subpaths", C.c_uint64)]
+
+
+class DashOut(C.Structure):
+    _fields_ = [("poly", C.c_void_p), ("subpaths", C.c_void_p), ("subpath_draw", C.c_void_p), ("subpath_src", C.c_void_p),
                 ("cap_poly_vertices", C.c_uint64), ("cap_subpaths", C.c_uint64)]
 
 
@@ -218,6 +226,12 @@ VGX_SYMBOLS = {
     "vgx_reserve": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(Sizes)]),
     "vgx_stroke_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(Sizes), C.c_void_p]),
     "vgx_stroke_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p]),
+    "vgx_dash_validate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "vgx_dash_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                 C.POINTER(Sizes), C.c_void_p]),
+    "vgx_dash": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                           C.POINTER(DashOut), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_subpath_draws": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vgx_concave_move": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "vgx_concave_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),

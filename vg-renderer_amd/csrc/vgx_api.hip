@@ -16,6 +16,7 @@
 #include "vgx_pathset_dev.h"
 #include "vgx_tile.h"
 #include "vgx_mscan.h"
+#include "vgx_dash.h"
 #include <vector>
 #include <atomic>
 #include <unordered_map>
@@ -78,6 +79,11 @@ struct vgx_ctx
 	DevBuf subPrefix; // exclusive scan of the draws' static sub-path counts
 	DevBuf cmdPrefix, cmdCnt, subFirst, leafOverflow, serialList, dinfo, poly, subs, mdesc, elemPrefix, elemPrefixS, mprep, mtab, partial, totals;
 	DevBuf textTiles;                    // vgx_text_quads: first run of every tile of quads (vgx_text.hip)
+	// vgx_dash (vgx_dash.hip): per-draw patterns, per-list records, per-segment prefix sums (S and the overflow guard), per-range sums; the
+	// segment count of the last call in pinned memory (copied behind the call, read by the next call once its event has passed: a call
+	// whose lists outgrew dashG ends with VGX_E_GROWN and the next one grows first, as vgx_tessellate_immediate does)
+	DevBuf dashPat, dashLists, dashG, dashGhi, dashRange;
+	unsigned long long* dashHost; hipEvent_t dashEv; bool dashEvPending;
 	DevBuf tileTab;                      // k_emit_tiles (vgx_tile.hip): the tile table of the current call
 	bool tileHint;                       // the last ordinary vgx_tessellate_count saw fills and closed Miter AA / Thin strokes only (the tile kernel's batches)
 	uint64_t optBigEmitMin;              // vertex capacity from which a call launches the tile kernel / k_stroke_long (2^18; VGX_BIG_EMIT_MIN: testing knob, 0 = every call)
@@ -998,13 +1004,14 @@ int vgx_destroy(vgx_ctx* ctx)
 		return VGX_E_INVALID_ARG;
 	}
 	DeviceGuard guard(ctx);
-	DevBuf* bufs[] = { &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
+	DevBuf* bufs[] = { &ctx->dashPat, &ctx->dashLists, &ctx->dashG, &ctx->dashGhi, &ctx->dashRange, &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
 	for (DevBuf* b : bufs) {
 		if (b->p) { (void)hipFree(b->p); }
 	}
 	if (ctx->hostTotals) { (void)hipHostFree(ctx->hostTotals); }
 	if (ctx->hostF1) { (void)hipHostFree(ctx->hostF1); }
 	if (ctx->immHost) { (void)hipHostFree(ctx->immHost); (void)hipEventDestroy(ctx->immEv); }
+	if (ctx->dashHost) { (void)hipHostFree(ctx->dashHost); (void)hipEventDestroy(ctx->dashEv); }
 	if (ctx->hostPs) { (void)hipHostFree(ctx->hostPs); }
 	if (ctx->psImage) { (void)hipHostFree(ctx->psImage); }
 	for (int i = 0; i < VGX_PS_POOL; ++i) { if (ctx->psPool[i].p) { (void)hipFree(ctx->psPool[i].p); } }
@@ -1025,7 +1032,7 @@ uint64_t vgx_scratch_bytes(const vgx_ctx* ctx)
 	if (!ctx) {
 		return 0;
 	}
-	return ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
+	return ctx->dashPat.cap + ctx->dashLists.cap + ctx->dashG.cap + ctx->dashGhi.cap + ctx->dashRange.cap + ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
 }
 
 // ---- path set ---------------------------------------------------------------------------------------
@@ -2294,6 +2301,138 @@ int vgx_stroke_emit(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
 	return runStrokeEmit(ctx, draws, out, s, poly);
+}
+
+// ---- dashed strokes -----------------------------------------------------------------------------------
+int vgx_dash_validate(const struct vgx_dash* dashes, uint64_t ndraws, const float* pattern, uint64_t npattern)
+{
+	if ((ndraws && !dashes) || (npattern && !pattern)) { return VGX_E_INVALID_ARG; }
+	for (uint64_t k = 0; k < npattern; ++k) {
+		if (!vgx_dash_entry_ok(pattern[k])) { return VGX_E_INVALID_ARG; }
+	}
+	for (uint64_t d = 0; d < ndraws; ++d) {
+		VgxDashPat p;
+		if (!vgx_dash_pat_build(dashes[d], pattern, npattern, &p)) { return VGX_E_INVALID_ARG; }
+	}
+	return VGX_OK;
+}
+
+namespace {
+
+int dashHostMirror(vgx_ctx* ctx)
+{
+	if (ctx->dashHost) { return VGX_OK; }
+	HIPCHK(ctx, hipHostMalloc((void**)&ctx->dashHost, sizeof(unsigned long long), hipHostMallocDefault));
+	const hipError_t e = hipEventCreateWithFlags(&ctx->dashEv, hipEventDisableTiming);
+	if (e != hipSuccess) { (void)hipHostFree(ctx->dashHost); ctx->dashHost = nullptr; ctx->lastHipError = (int)e; return VGX_E_HIP; }
+	*ctx->dashHost = 0;
+	return VGX_OK;
+}
+
+int dashEnsureSegments(vgx_ctx* ctx, uint64_t segments)
+{
+	int st;
+	if ((st = ensure(ctx, ctx->dashG, (segments + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
+	return ensure(ctx, ctx->dashGhi, (segments + 1) * sizeof(uint64_t));
+}
+
+// everything but the launch: argument checks, scratch, the argument block
+int dashPrepare(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths,
+                const struct vgx_dash* dashes, uint64_t ndraws, const float* pattern, uint64_t npattern, uint64_t segGuess, VgxDashArgs* a)
+{
+	if ((nsubpaths && (!poly || !subpaths || !subpath_draw || !dashes || !ndraws)) || (ndraws && !dashes) || (npattern && !pattern)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)poly & 7u) || ((uintptr_t)subpaths & 7u) || ((uintptr_t)subpath_draw & 3u) || ((uintptr_t)dashes & 3u) || ((uintptr_t)pattern & 3u)) { return VGX_E_INVALID_ARG; }
+	if (nsubpaths > 0x7FFFFFFFull || ndraws > 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	ctx->lastStage = 0;
+	ctx->tmplOn = false;
+	int st;
+	if ((st = dashHostMirror(ctx)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dashPat, (ndraws + 1) * sizeof(VgxDashPat))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dashLists, (nsubpaths + 1) * sizeof(VgxDashListRec))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dashRange, (4 * VGX_DASH_RANGES + 4) * sizeof(uint64_t))) != VGX_OK) { return st; }
+	// the segment tables: what the last call measured (once that has arrived), else what they hold, else a guess
+	uint64_t segments = segGuess;
+	if (ctx->dashEvPending && hipEventQuery(ctx->dashEv) == hipSuccess) {
+		ctx->dashEvPending = false;
+		if (*ctx->dashHost > segments) { segments = *ctx->dashHost; }
+	}
+	if (ctx->dashG.cap == 0 || segments + 1 > ctx->dashG.cap / sizeof(uint64_t)) {
+		if ((st = dashEnsureSegments(ctx, segments)) != VGX_OK) { return st; }
+	}
+	memset(a, 0, sizeof(*a));
+	a->poly = poly; a->subs = subpaths; a->sub_draw = subpath_draw; a->nsubs = nsubpaths;
+	a->dashes = dashes; a->ndraws = ndraws; a->pattern = pattern; a->npattern = npattern;
+	a->pat = (VgxDashPat*)ctx->dashPat.p; a->lists = (VgxDashListRec*)ctx->dashLists.p;
+	a->G = (uint64_t*)ctx->dashG.p; a->Ghi = (uint64_t*)ctx->dashGhi.p;
+	const size_t capG = ctx->dashG.cap < ctx->dashGhi.cap ? ctx->dashG.cap : ctx->dashGhi.cap;
+	a->seg_cap = capG / sizeof(uint64_t) - 1;
+	a->range_sum = (uint64_t*)ctx->dashRange.p; a->range_off = a->range_sum + 2 * VGX_DASH_RANGES; a->tot = a->range_off + 2 * VGX_DASH_RANGES;
+	a->totals = (VgxTotals*)ctx->totals.p; a->partial = (Sum3*)ctx->partial.p;
+	return VGX_OK;
+}
+
+void dashLaunch(vgx_ctx* ctx, const VgxDashArgs& a, bool emit, hipStream_t s)
+{
+	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
+	noteHip(ctx, hipMemsetAsync(a.tot, 0, 4 * sizeof(uint64_t), s));
+	vgx_launch_dash(a, emit, s);
+	mark(ctx, s, emit ? "dash" : "dash_count");
+	// the segment count to the mirror, for the next call (never waited for)
+	noteHip(ctx, hipMemcpyAsync(ctx->dashHost, a.tot, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+	noteHip(ctx, hipEventRecord(ctx->dashEv, s));
+	ctx->dashEvPending = true;
+}
+
+} // namespace
+
+int vgx_dash_count(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths,
+                   const struct vgx_dash* dashes, uint64_t ndraws, const float* pattern, uint64_t npattern, vgx_sizes* out_sizes, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || !out_sizes) { return VGX_E_INVALID_ARG; }
+	hipStream_t s = (hipStream_t)stream;
+	markBegin(ctx, s);
+	for (int attempt = 0; ; ++attempt) { // a second round only when the lists outgrew the segment tables (the first count of a larger batch)
+		VgxDashArgs a;
+		int st = dashPrepare(ctx, poly, subpaths, subpath_draw, nsubpaths, dashes, ndraws, pattern, npattern, 65536, &a);
+		if (st != VGX_OK) { return st; }
+		dashLaunch(ctx, a, false, s);
+		if ((st = launchStatus(ctx)) != VGX_OK) { return st; }
+		if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
+		if (ctx->hostTotals->status == VGX_E_GROWN && attempt == 0) { continue; } // the mirror holds the need, dashPrepare grows from it
+		*out_sizes = ctx->hostTotals->sizes;
+		return (int)ctx->hostTotals->status;
+	}
+}
+
+int vgx_dash(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths,
+             const struct vgx_dash* dashes, uint64_t ndraws, const float* pattern, uint64_t npattern,
+             const vgx_dash_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || !out || !out->poly || !out->subpaths || !out->subpath_draw) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)out->poly & 7u) || ((uintptr_t)out->subpaths & 7u) || ((uintptr_t)out->subpath_draw & 3u) || ((uintptr_t)out->subpath_src & 3u)) { return VGX_E_INVALID_ARG; }
+	hipStream_t s = (hipStream_t)stream;
+	markBegin(ctx, s);
+	VgxDashArgs a;
+	const int st = dashPrepare(ctx, poly, subpaths, subpath_draw, nsubpaths, dashes, ndraws, pattern, npattern,
+	                           out->cap_poly_vertices > 65536 ? out->cap_poly_vertices : 65536, &a);
+	if (st != VGX_OK) { return st; }
+	a.out_poly = out->poly; a.out_subs = out->subpaths; a.out_draw = out->subpath_draw; a.out_src = out->subpath_src;
+	a.cap_poly = out->cap_poly_vertices; a.cap_subs = out->cap_subpaths; a.check_caps = 1;
+	dashLaunch(ctx, a, true, s);
+	publish(ctx, dev_sizes, dev_status, s);
+	return launchStatus(ctx);
+}
+
+int vgx_subpath_draws(vgx_ctx* ctx, const vgx_draw_info* draw_info, uint64_t ndraws, uint32_t* subpath_draw, uint64_t nsubpaths, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || (nsubpaths && (!draw_info || !subpath_draw || !ndraws)) || ((uintptr_t)draw_info & 7u) || ((uintptr_t)subpath_draw & 3u)) { return VGX_E_INVALID_ARG; }
+	if (nsubpaths) { vgx_launch_subpath_draws(draw_info, ndraws, subpath_draw, nsubpaths, (hipStream_t)stream); }
+	return launchStatus(ctx);
 }
 
 // ---- shape cache ------------------------------------------------------------------------------------

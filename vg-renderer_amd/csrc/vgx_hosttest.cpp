@@ -304,3 +304,109 @@ int vgxt_text_quads(const float* quads, uint64_t nquads, const vgx_text_run* run
 }
 
 }
+
+#include "vgx_dash.h"
+#include <vector>
+
+extern "C" {
+
+// the closed-form interval range of one record on a list of length T fixed units (vgx_dash_intervals); ~0 for an invalid record
+uint64_t vgxt_dash_intervals(const struct vgx_dash* d, const float* pattern, uint64_t npattern, uint64_t T, uint64_t* jlo)
+{
+	VgxDashPat p;
+	if (!vgx_dash_pat_build(*d, pattern, npattern, &p)) { return ~0ull; }
+	return vgx_dash_intervals(p, T, jlo);
+}
+
+// vgx_dash on the host: the functions of vgx_dash.h (the ones the kernels of vgx_dash.hip run one lane per segment / "on" interval /
+// output vertex) list after list, interval after interval, vertex after vertex, with the call's contract: nothing written unless
+// everything is valid, in range and fits; the totals in `sizes` (may be NULL; exact for VGX_OK and VGX_E_NOSPACE). Returns the status
+// the device call leaves in dev_status. `out` may be NULL (the count alone).
+int vgxt_dash(const float* poly, const vgx_subpath* subs, const uint32_t* sub_draw, uint64_t nsubs, const struct vgx_dash* dashes, uint64_t ndraws,
+              const float* pattern, uint64_t npattern, const vgx_dash_out* out, vgx_sizes* sizes)
+{
+	if (sizes) { memset(sizes, 0, sizeof(*sizes)); }
+	std::vector<VgxDashPat> pat(ndraws ? ndraws : 1);
+	bool valid = true;
+	for (uint64_t k = 0; k < npattern; ++k) { valid = valid && vgx_dash_entry_ok(pattern[k]); }
+	for (uint64_t d = 0; d < ndraws; ++d) { valid = vgx_dash_pat_build(dashes[d], pattern, npattern, &pat[d]) && valid; }
+	for (uint64_t l = 0; l < nsubs; ++l) { valid = valid && sub_draw[l] < ndraws; }
+	if (!valid) { return VGX_E_INVALID_ARG; }
+	// the prefix sums of every dashed list, back to back
+	std::vector<uint64_t> G(1, 0), base(nsubs + 1, 0);
+	for (uint64_t l = 0; l < nsubs; ++l) {
+		base[l] = G.size() - 1;
+		if (subs[l].num_vertices > 0x7FFFFFFFu) { return VGX_E_RANGE; }
+		if (pat[sub_draw[l]].count == 0) { continue; }
+		const uint32_t n = subs[l].num_vertices, m = vgx_dash_num_segments(n, subs[l].flags);
+		const float* v = poly + 2 * subs[l].first_vertex;
+		uint64_t hi = 0;
+		for (uint32_t i = 0; i < m; ++i) {
+			const uint32_t i1 = i + 1u == n ? 0u : i + 1u;
+			uint64_t q;
+			if (!vgx_dash_seg_q(v[2 * i], v[2 * i + 1], v[2 * i1], v[2 * i1 + 1], &q)) { return VGX_E_RANGE; }
+			hi += q >> 31;
+			G.push_back(G.back() + q);
+		}
+		if (hi > (1ull << 31) || G.back() - G[base[l]] > VGX_DASH_MAX_T) { return VGX_E_RANGE; }
+	}
+	base[nsubs] = G.size() - 1;
+	// the call's "on" intervals (the scan OpDashCand), before any of them is walked
+	{
+		uint64_t nint = 0;
+		for (uint64_t l = 0; l < nsubs; ++l) {
+			const VgxDashPat& P = pat[sub_draw[l]];
+			uint64_t nc = 1, jlo;
+			if (P.count != 0) {
+				const uint32_t m = vgx_dash_num_segments(subs[l].num_vertices, subs[l].flags);
+				nc = m ? vgx_dash_intervals(P, G[base[l] + m] - G[base[l]], &jlo) : 0;
+			}
+			if (nc > VGX_DASH_MAX_INTERVALS || (nint += nc) > VGX_DASH_MAX_INTERVALS) { return VGX_E_RANGE; }
+		}
+	}
+	// pass 0 counts (what k_dash_count does), pass 1 writes (k_dash_emit)
+	for (int pass = 0; pass < 2; ++pass) {
+		uint64_t np = 0, nv = 0;
+		for (uint64_t l = 0; l < nsubs; ++l) {
+			const VgxDashPat& P = pat[sub_draw[l]];
+			const uint32_t n = subs[l].num_vertices;
+			const float* v = poly + 2 * subs[l].first_vertex;
+			if (P.count == 0) { // verbatim
+				if (pass) {
+					vgx_subpath rec; rec.first_vertex = nv; rec.num_vertices = n; rec.flags = subs[l].flags;
+					out->subpaths[np] = rec; out->subpath_draw[np] = sub_draw[l];
+					if (out->subpath_src) { out->subpath_src[np] = (uint32_t)l; }
+					for (uint32_t k = 0; k < 2 * n; ++k) { out->poly[2 * nv + k] = v[k]; }
+				}
+				++np; nv += n;
+				continue;
+			}
+			VgxDashList L;
+			L.v = v; L.G = G.data() + base[l]; L.n = n; L.m = vgx_dash_num_segments(n, subs[l].flags);
+			if (L.m == 0) { continue; }
+			L.T = L.G[L.m] - L.G[0];
+			uint64_t jlo;
+			const uint64_t nc = vgx_dash_intervals(P, L.T, &jlo);
+			for (uint64_t c = 0; c < nc; ++c) {
+				VgxDashPiece p;
+				if (!vgx_dash_piece(L, P, jlo + c, &p)) { continue; }
+				const uint32_t k = vgx_dash_piece_vertices(p);
+				if (pass) {
+					vgx_subpath rec; rec.first_vertex = nv; rec.num_vertices = k; rec.flags = 0;
+					out->subpaths[np] = rec; out->subpath_draw[np] = sub_draw[l];
+					if (out->subpath_src) { out->subpath_src[np] = (uint32_t)l; }
+					for (uint32_t i = 0; i < k; ++i) { const V2 x = vgx_dash_piece_vertex(L, p, i); out->poly[2 * (nv + i)] = x.x; out->poly[2 * (nv + i) + 1] = x.y; }
+				}
+				++np; nv += k;
+			}
+		}
+		if (!pass) {
+			if (sizes) { sizes->num_subpaths = np; sizes->num_poly_vertices = nv; }
+			if (!out) { return VGX_OK; }
+			if (np > out->cap_subpaths || nv > out->cap_poly_vertices) { return VGX_E_NOSPACE; }
+		}
+	}
+	return VGX_OK;
+}
+
+}

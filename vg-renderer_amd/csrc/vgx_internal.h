@@ -239,6 +239,46 @@ struct VgxTextArgs
 };
 void vgx_launch_text_quads(const VgxTextArgs& a, hipStream_t s);
 
+// dashed strokes (vgx_dash.hip)
+#define VGX_DASH_RANGES 1024 /* workgroups of k_dash_count / k_dash_emit = threads of k_dash_ranges */
+struct VgxDashPat;
+struct VgxDashListRec        // per source list. 32 bytes
+{
+	uint64_t seg_base;       // its first segment in G (undashed lists and lists of < 2 vertices own none)
+	uint64_t cand_off;       // its first "on" interval among the call's
+	uint64_t jlo;            // number of that interval in the list's own pattern space (vgx_dash.h)
+	uint64_t T;              // its length, fixed units
+};
+struct VgxDashArgs
+{
+	const float* poly;
+	const vgx_subpath* subs;
+	const uint32_t* sub_draw;
+	uint64_t nsubs;
+	const struct vgx_dash* dashes;
+	uint64_t ndraws;
+	const float* pattern;
+	uint64_t npattern;
+	VgxDashPat* pat;           // [ndraws]
+	VgxDashListRec* lists;     // [nsubs + 1]
+	uint64_t* G;               // [seg_cap + 1] exclusive sums of q(len) over the segments of the batch, modulo 2^64
+	uint64_t* Ghi;             // [seg_cap + 1] ... of q(len) >> 31: decides whether a list's length fits
+	uint64_t seg_cap;
+	uint64_t* range_sum;       // [VGX_DASH_RANGES][2] pieces, vertices per range
+	uint64_t* range_off;       // [VGX_DASH_RANGES][2] ... in front of it
+	uint64_t* tot;             // [4] segments, "on" intervals, out-of-range flag (zeroed by the caller)
+	float* out_poly;
+	vgx_subpath* out_subs;
+	uint32_t* out_draw;
+	uint32_t* out_src;         // may be null
+	uint64_t cap_poly, cap_subs;
+	int check_caps;
+	VgxTotals* totals;
+	struct Sum3* partial;
+};
+void vgx_launch_dash(const VgxDashArgs& a, bool emit, hipStream_t s);
+void vgx_launch_subpath_draws(const vgx_draw_info* dinfo, uint64_t ndraws, uint32_t* subDraw, uint64_t nsubs, hipStream_t s);
+
 // launchers (defined in the .hip files)
 void vgx_launch_flatten(bool emit, const VgxFlattenArgs& a, int numBlocks, hipStream_t s);
 void vgx_launch_flatten_build(const VgxFlattenArgs& a, int waves, hipStream_t s, bool serialCount = true);   // single-pass: subdivide once, polyline -> heap

@@ -439,6 +439,83 @@ def stroke(ctx, poly_dev, subs_dev, subdraw_dev, nsubs, draws_dev, ndraws, to_ho
     return r
 
 
+# ---- dashed strokes (vgx_dash): between flatten and the stroker-level entry ---------------------------------------------
+class DashBuffers:
+    """Caller-owned output buffers of vgx_dash in HBM (vgx_dash_out) + the device-side totals / status words."""
+
+    def __init__(self, device, npoly, nsubs):
+        import torch
+        self.cap = (int(npoly), int(nsubs))
+        self.poly = torch.empty((max(int(npoly), 1), 2), dtype=torch.float32, device=device)
+        self.subs = torch.empty(max(int(nsubs), 1) * 16, dtype=torch.uint8, device=device)
+        self.sub_draw = torch.empty(max(int(nsubs), 1), dtype=torch.int32, device=device)
+        self.sub_src = torch.empty(max(int(nsubs), 1), dtype=torch.int32, device=device)
+        self.dev_sizes = torch.zeros(10, dtype=torch.int64, device=device)
+        self.dev_status = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def out_struct(self):
+        return capi.DashOut(self.poly.data_ptr(), self.subs.data_ptr(), self.sub_draw.data_ptr(), self.sub_src.data_ptr(), self.cap[0], self.cap[1])
+
+
+class DashResult:
+    pass
+
+
+def dash_validate(dashes, pattern):
+    """vgx_dash_validate on host arrays (capi.dash_dtype records, float32 pattern). Returns the status."""
+    d = np.ascontiguousarray(dashes)
+    p = np.ascontiguousarray(pattern, dtype=np.float32)
+    return int(lib().vgx_dash_validate(d.ctypes.data if d.size else None, d.shape[0], p.ctypes.data if p.size else None, p.shape[0]))
+
+
+def subpath_draws(ctx, dinfo_dev, ndraws, nsubs):
+    """vgx_subpath_draws: the draw of every sub-path of a flatten result (dinfo_dev: its 40-byte vgx_draw_info records). int32 [nsubs]."""
+    import torch
+    out = torch.empty(max(int(nsubs), 1), dtype=torch.int32, device=dinfo_dev.device)
+    _check(lib().vgx_subpath_draws(ctx.handle, dinfo_dev.data_ptr(), ndraws, out.data_ptr(), nsubs, _stream_ptr()), "vgx_subpath_draws")
+    return out
+
+
+def dash_count(ctx, poly_dev, subs_dev, subdraw_dev, nsubs, dashes_dev, ndraws, pattern_dev, npattern):
+    sizes = capi.Sizes()
+    _check(lib().vgx_dash_count(ctx.handle, poly_dev.data_ptr(), subs_dev.data_ptr(), subdraw_dev.data_ptr(), nsubs, dashes_dev.data_ptr(), ndraws,
+                                pattern_dev.data_ptr() if npattern else None, npattern, C.byref(sizes), _stream_ptr()), "vgx_dash_count")
+    return sizes.as_dict()
+
+
+def dash_async(ctx, poly_dev, subs_dev, subdraw_dev, nsubs, dashes_dev, ndraws, pattern_dev, npattern, bufs):
+    """vgx_dash: single asynchronous call; totals / status land in bufs.dev_*."""
+    out = bufs.out_struct()
+    _check(lib().vgx_dash(ctx.handle, poly_dev.data_ptr(), subs_dev.data_ptr(), subdraw_dev.data_ptr(), nsubs, dashes_dev.data_ptr(), ndraws,
+                          pattern_dev.data_ptr() if npattern else None, npattern, C.byref(out), bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(),
+                          _stream_ptr()), "vgx_dash")
+
+
+def dash(ctx, poly_dev, subs_dev, subdraw_dev, nsubs, dashes_dev, ndraws, pattern_dev, npattern, to_host=True):
+    """count -> allocate exact -> vgx_dash. poly_dev float32 [n,2], subs_dev uint8 (16-byte vgx_subpath records), subdraw_dev int32
+    [nsubs], dashes_dev uint8 (16-byte struct vgx_dash records, one per draw), pattern_dev float32 [npattern]. The pieces stay on
+    the device (.poly_dev / .subs_dev / .sub_draw_dev / .sub_src_dev: what `stroke` takes) and come back as numpy copies when to_host."""
+    import torch
+    sizes = dash_count(ctx, poly_dev, subs_dev, subdraw_dev, nsubs, dashes_dev, ndraws, pattern_dev, npattern)
+    npv, nsp = sizes["num_poly_vertices"], sizes["num_subpaths"]
+    bufs = DashBuffers(poly_dev.device, npv, nsp)
+    dash_async(ctx, poly_dev, subs_dev, subdraw_dev, nsubs, dashes_dev, ndraws, pattern_dev, npattern, bufs)
+    torch.cuda.synchronize()
+    st = int(bufs.dev_status.item())
+    if st != capi.VGX_OK:
+        raise VgxError(st, "vgx_dash (device)")
+    r = DashResult()
+    r.sizes = sizes
+    r.bufs = bufs
+    r.poly_dev, r.subs_dev, r.sub_draw_dev, r.sub_src_dev = bufs.poly, bufs.subs, bufs.sub_draw, bufs.sub_src
+    if to_host:
+        r.poly = bufs.poly[:npv].cpu().numpy()
+        r.subpaths = bufs.subs[:nsp * 16].cpu().numpy().view(capi.subpath_dtype)
+        r.sub_draw = bufs.sub_draw[:nsp].cpu().numpy().view(np.uint32)
+        r.sub_src = bufs.sub_src[:nsp].cpu().numpy().view(np.uint32)
+    return r
+
+
 # ---- shape cache (vgx_cache_localize / vgx_cache_submit) ---------------------------------------------
 class MeshCache:
     """A tessellated drawing kept in HBM in local space (the reference's CommandListCache, vg.cpp:249-256)."""
