@@ -365,6 +365,14 @@ int vgx_reserve(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals);
 int vgx_stroke_count(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths, const vgx_draw* draws, uint64_t ndraws, vgx_sizes* out_sizes, void* stream);
 int vgx_stroke_emit(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out, void* stream);
 
+/* The same in ONE asynchronous call, like vgx_tessellate: the bytes and the mesh order of vgx_stroke_count + vgx_stroke_emit with no host round
+ * trip (scratch needs at most two meshes per list, which the host knows). Capacities of `out` are checked on the device: dev_sizes (DEVICE,
+ * may be NULL) receives the totals, dev_status (DEVICE uint32, may be NULL) VGX_OK / VGX_E_NOSPACE (exact totals, nothing written past a
+ * capacity) / VGX_E_INVALID_ARG (a subpath_draw entry >= ndraws, a cap / join above 2). With it the chain vgx_flatten -> vgx_subpath_draws ->
+ * vgx_dash -> vgx_stroke never visits the host. Ends any counted state of the context. */
+int vgx_stroke(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths, const vgx_draw* draws, uint64_t ndraws,
+               const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
+
 /* ---- dashed strokes (beyond the reference): vgx_flatten -> vgx_subpath_draws -> vgx_dash -> vgx_stroke_* ----------
  * SVG stroke-dasharray / stroke-dashoffset for the stroker-level boundary: vgx_dash cuts every vertex list of a dashed draw into
  * its "on" pieces, on the device; the pieces are ordinary open vertex lists for vgx_stroke_count / vgx_stroke_emit. The reference
@@ -440,6 +448,41 @@ int vgx_dash(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const
 /* vgx_flat_out::draw_info -> the subpath_draw array vgx_stroke_* and vgx_dash take: subpath_draw[i] = the draw whose sub-paths
  * [first_subpath, first_subpath + num_subpaths) hold i, for i < nsubpaths. All DEVICE pointers; asynchronous. */
 int vgx_subpath_draws(vgx_ctx* ctx, const vgx_draw_info* draw_info, uint64_t ndraws, uint32_t* subpath_draw, uint64_t nsubpaths, void* stream);
+
+/* ---- dashed strokes in frames: draws in, the frame's meshes out, one asynchronous call ----------------------------------------
+ * The batch form of vgx_tessellate_immediate with one `struct vgx_dash` per draw (dashes: DEVICE [ndraws], may be NULL = no draw is dashed;
+ * pattern: DEVICE [npattern]). The record, the rules of vgx_dash_validate and the units are those of vgx_dash: device units, the caller
+ * multiplies user lengths by vgx_draw::scale. Output, per draw d in order:
+ *   1. the fill meshes of d, exactly as vgx_tessellate_immediate writes them (fills always come from the undashed sub-paths);
+ *   2. stroke enabled and dashes[d].count == 0: the stroke meshes of d, exactly as today;
+ *   3. stroke enabled and count > 0: for every sub-path s of d in order, the pieces the specification above gives for the transformed
+ *      vertex list of s, by increasing start, one mesh per piece: what vgx_stroke writes for that open list with d's stroke fields (caps on
+ *      both ends of every piece; AA, non-AA and Thin as for any open list). vgx_mesh::draw = d, subpath_kind = the SOURCE sub-path's index
+ *      inside the draw | kind << 28: the pieces of one sub-path share the index;
+ *   4. a stroke-disabled draw produces no pieces whatever its record says (the record is still validated);
+ *   5. draws of kind VGX_FILL_CONCAVE / _TRILIST / _TEXT behave as in vgx_tessellate_immediate.
+ * dev_sizes: the call's totals with vgx_tessellate_immediate's meanings (the flatten totals are those of the source paths). dev_dash_sizes
+ * (DEVICE, may be NULL): num_subpaths = pieces of the dashed, stroke-enabled draws, num_poly_vertices = their vertices, other fields 0.
+ * With dashes == NULL or every count == 0 the output equals vgx_tessellate_immediate's byte for byte. vgx_set_assembly is honoured as there.
+ * dev_status, the union of vgx_tessellate_immediate's and vgx_dash's protocols (the host returns VGX_OK once the work is enqueued):
+ *   VGX_E_INVALID_ARG  a dash record, a pattern entry or a cap / join above 2 breaks the rules (a flagged reduction): nothing is written;
+ *   VGX_E_RANGE        as for vgx_dash, and beyond 2^32 - 16 polyline vertices or command instances;
+ *   VGX_E_NOSPACE      the caller's buffers are too small: num_vertices, num_indices, num_meshes are exact, nothing is written past a capacity;
+ *   VGX_E_GROWN        a scratch table of the context is too small: nothing is written past any table, the need goes to pinned mirrors by
+ *                      asynchronous copies and the next call grows from them after an event query. The call never blocks.
+ * Convergence: repeating the call with the same arguments -- reading dev_status in between and, after VGX_E_NOSPACE, growing the output to
+ * dev_sizes -- reaches VGX_OK within four calls; each call can fail for at most one new reason: (1) the flatten scratch is too small (its
+ * totals are exact and bound the segment tables), (2) the piece scratch is too small, (3) the caller's buffers are too small. An armed
+ * assembly whose draw-command table is too small adds one call. After vgx_reserve_dashed with totals >= the batch's (`totals`: the call's
+ * dev_sizes, as for vgx_reserve; `dash_totals`: its dev_dash_sizes) it takes one call.
+ * The flatten stage is k_flatten_build's for any number of draws (its mesh descriptors are complete and in frame order, the exact serial
+ * builder's included); the dash pass reads the polylines where that stage left them and writes the pieces behind them in the same scratch
+ * allocation; the frame's mesh slots are closed-form (csrc/vgx_dashframe.h). Ends any counted state of the context, like
+ * vgx_tessellate_immediate; works for any ndraws, on a fresh context and after any other call. */
+int vgx_tessellate_dashed(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws,
+                          const struct vgx_dash* dashes, const float* pattern, uint64_t npattern,
+                          const vgx_mesh_out* out, vgx_sizes* dev_sizes, vgx_sizes* dev_dash_sizes, uint32_t* dev_status, void* stream);
+int vgx_reserve_dashed(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals, const vgx_sizes* dash_totals);
 
 /* ---- draw-command assembly (see vgx_drawcmd / vgx_assembly above) ------------
  * Arms (asm_ != NULL) or disarms (NULL) assembly for the following vgx_tessellate_emit / vgx_tessellate calls on this

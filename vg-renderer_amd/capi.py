@@ -226,6 +226,10 @@ VGX_SYMBOLS = {
     "vgx_reserve": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(Sizes)]),
     "vgx_stroke_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(Sizes), C.c_void_p]),
     "vgx_stroke_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p]),
+    "vgx_stroke": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_tessellate_dashed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut),
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_reserve_dashed": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(Sizes), C.POINTER(Sizes)]),
     "vgx_dash_validate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     "vgx_dash_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                  C.POINTER(Sizes), C.c_void_p]),

@@ -84,6 +84,13 @@ struct vgx_ctx
 	// whose lists outgrew dashG ends with VGX_E_GROWN and the next one grows first, as vgx_tessellate_immediate does)
 	DevBuf dashPat, dashLists, dashG, dashGhi, dashRange;
 	unsigned long long* dashHost; hipEvent_t dashEv; bool dashEvPending;
+	// vgx_tessellate_dashed (vgx_dashframe.hip): the second set of mesh tables (the flatten stage writes one set, the frame's meshes go to the
+	// other; the two swap roles behind the call), per source mesh the list of the dash pass and D(m), the pieces' records, the dash pass's
+	// totals, and the need of the last call (pieces, their vertices, source meshes) with its pinned mirror, as immHost. The pieces' vertices
+	// lie BEHIND the flatten stage's heap in `poly`: pieceVerts of its vertices are theirs (ensureMeshBuffers keeps them out of caps)
+	DevBuf mdesc2, mprep2, mtab2, dfLists, dfListDraw, dfDashedBefore, dfPieceSubs, dfPieceDraw, dfPieceSrc, dfTotals, dfNeed;
+	uint64_t pieceVerts;
+	unsigned long long* dfHost; hipEvent_t dfEv; bool dfEvPending;
 	DevBuf tileTab;                      // k_emit_tiles (vgx_tile.hip): the tile table of the current call
 	bool tileHint;                       // the last ordinary vgx_tessellate_count saw fills and closed Miter AA / Thin strokes only (the tile kernel's batches)
 	uint64_t optBigEmitMin;              // vertex capacity from which a call launches the tile kernel / k_stroke_long (2^18; VGX_BIG_EMIT_MIN: testing knob, 0 = every call)
@@ -777,14 +784,14 @@ int runStrokeEmit(vgx_ctx* ctx, const vgx_draw* draws, const vgx_mesh_out* out, 
 int ensureMeshBuffers(vgx_ctx* ctx, uint64_t polyVerts, uint64_t subpaths, uint64_t meshes)
 {
 	int st;
-	if ((st = ensure(ctx, ctx->poly, (polyVerts + 1) * 2 * sizeof(float))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->poly, (polyVerts + 1 + ctx->pieceVerts) * 2 * sizeof(float))) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->subs, (subpaths + 1) * sizeof(vgx_subpath))) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->mdesc, (meshes + 1) * sizeof(VgxMeshDesc))) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->elemPrefix, (meshes + 2) * sizeof(uint64_t))) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->elemPrefixS, (meshes + 2) * sizeof(uint64_t))) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->mprep, (meshes + 1) * sizeof(VgxMeshPrep))) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->mtab, (meshes + 1) * sizeof(vgx_mesh))) != VGX_OK) { return st; }
-	ctx->caps.poly_vertices = ctx->poly.cap / (2 * sizeof(float)) - 1;
+	ctx->caps.poly_vertices = ctx->poly.cap / (2 * sizeof(float)) - 1 - ctx->pieceVerts; // (the tail belongs to vgx_tessellate_dashed's pieces)
 	ctx->caps.subpaths = ctx->subs.cap / sizeof(vgx_subpath) - 1;
 	uint64_t m = ctx->mdesc.cap / sizeof(VgxMeshDesc) - 1;
 	uint64_t m2 = ctx->elemPrefix.cap / sizeof(uint64_t) - 2;
@@ -1004,7 +1011,7 @@ int vgx_destroy(vgx_ctx* ctx)
 		return VGX_E_INVALID_ARG;
 	}
 	DeviceGuard guard(ctx);
-	DevBuf* bufs[] = { &ctx->dashPat, &ctx->dashLists, &ctx->dashG, &ctx->dashGhi, &ctx->dashRange, &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
+	DevBuf* bufs[] = { &ctx->mdesc2, &ctx->mprep2, &ctx->mtab2, &ctx->dfLists, &ctx->dfListDraw, &ctx->dfDashedBefore, &ctx->dfPieceSubs, &ctx->dfPieceDraw, &ctx->dfPieceSrc, &ctx->dfTotals, &ctx->dfNeed, &ctx->dashPat, &ctx->dashLists, &ctx->dashG, &ctx->dashGhi, &ctx->dashRange, &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
 	for (DevBuf* b : bufs) {
 		if (b->p) { (void)hipFree(b->p); }
 	}
@@ -1012,6 +1019,7 @@ int vgx_destroy(vgx_ctx* ctx)
 	if (ctx->hostF1) { (void)hipHostFree(ctx->hostF1); }
 	if (ctx->immHost) { (void)hipHostFree(ctx->immHost); (void)hipEventDestroy(ctx->immEv); }
 	if (ctx->dashHost) { (void)hipHostFree(ctx->dashHost); (void)hipEventDestroy(ctx->dashEv); }
+	if (ctx->dfHost) { (void)hipHostFree(ctx->dfHost); (void)hipEventDestroy(ctx->dfEv); }
 	if (ctx->hostPs) { (void)hipHostFree(ctx->hostPs); }
 	if (ctx->psImage) { (void)hipHostFree(ctx->psImage); }
 	for (int i = 0; i < VGX_PS_POOL; ++i) { if (ctx->psPool[i].p) { (void)hipFree(ctx->psPool[i].p); } }
@@ -1032,7 +1040,7 @@ uint64_t vgx_scratch_bytes(const vgx_ctx* ctx)
 	if (!ctx) {
 		return 0;
 	}
-	return ctx->dashPat.cap + ctx->dashLists.cap + ctx->dashG.cap + ctx->dashGhi.cap + ctx->dashRange.cap + ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
+	return ctx->mdesc2.cap + ctx->mprep2.cap + ctx->mtab2.cap + ctx->dfLists.cap + ctx->dfListDraw.cap + ctx->dfDashedBefore.cap + ctx->dfPieceSubs.cap + ctx->dfPieceDraw.cap + ctx->dfPieceSrc.cap + ctx->dfTotals.cap + ctx->dfNeed.cap + ctx->dashPat.cap + ctx->dashLists.cap + ctx->dashG.cap + ctx->dashGhi.cap + ctx->dashRange.cap + ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
 }
 
 // ---- path set ---------------------------------------------------------------------------------------
@@ -2142,7 +2150,7 @@ static int immConsume(vgx_ctx* ctx, const vgx_pathset* ps)
 	if (ctx->immPendDetect || !same) { ctx->immPeriod = P; ctx->immDistinct = ctx->immPendDetect ? h.inst_distinct : 0; } else { P = ctx->immPeriod; }
 	ctx->immKnown = true; ctx->immTag = ctx->immPendTag;
 	ctx->immV = h.sizes.num_poly_vertices; ctx->immCmd = h.sizes.num_cmd_instances;
-	if (h.status != VGX_E_GROWN) {
+	if (h.status != VGX_E_GROWN || !h.scratch_short) { // (VGX_E_GROWN without the flag: vgx_tessellate_dashed's pieces outgrew their scratch, the flatten stage fitted)
 		if (!same) { ctx->immLongKnown = false; }
 		return VGX_OK;
 	}
@@ -2303,6 +2311,35 @@ int vgx_stroke_emit(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths
 	return runStrokeEmit(ctx, draws, out, s, poly);
 }
 
+
+int vgx_stroke(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths, const vgx_draw* draws, uint64_t ndraws,
+               const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+{
+	if (!ctx || !out || !out->pos || !out->color || !out->idx || (nsubpaths && (!poly || !subpaths || !subpath_draw || !draws))) { // (before the context is touched)
+		return VGX_E_INVALID_ARG;
+	}
+	DeviceGuard guard(ctx);
+	hipStream_t s = (hipStream_t)stream;
+	markBegin(ctx, s);
+	ctx->lastStage = 0; // counted state ends here
+	ctx->tmplOn = false;
+	int st;
+	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	// at most two meshes per vertex list: scratch is sized without a device round trip
+	if ((st = ensureMeshBuffers(ctx, 0, 0, 2 * nsubpaths)) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
+	OpSubMeshes op;
+	op.subs = subpaths; op.subDraw = subpath_draw; op.draws = draws; op.nsubs = nsubpaths; op.ndraws = ndraws;
+	op.mdesc = (VgxMeshDesc*)ctx->mdesc.p; op.mtab = (vgx_mesh*)ctx->mtab.p; op.totals = (VgxTotals*)ctx->totals.p;
+	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, nsubpaths);
+	mark(ctx, s, "scan_subpath_meshes");
+	runStrokeCount(ctx, draws, outCapsFor(ctx, out), 1, s, poly, false, out->meshes); // sizes, places, the caller's capacities, its mesh table
+	if ((st = runStrokeEmit(ctx, draws, out, s, poly, true)) != VGX_OK) { return st; }
+	publish(ctx, dev_sizes, dev_status, s);
+	return launchStatus(ctx);
+}
+
 // ---- dashed strokes -----------------------------------------------------------------------------------
 int vgx_dash_validate(const struct vgx_dash* dashes, uint64_t ndraws, const float* pattern, uint64_t npattern)
 {
@@ -2375,7 +2412,7 @@ int dashPrepare(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, co
 
 void dashLaunch(vgx_ctx* ctx, const VgxDashArgs& a, bool emit, hipStream_t s)
 {
-	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
+	noteHip(ctx, hipMemsetAsync(a.totals, 0, sizeof(VgxTotals), s));
 	noteHip(ctx, hipMemsetAsync(a.tot, 0, 4 * sizeof(uint64_t), s));
 	vgx_launch_dash(a, emit, s);
 	mark(ctx, s, emit ? "dash" : "dash_count");
@@ -2424,6 +2461,159 @@ int vgx_dash(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const
 	a.cap_poly = out->cap_poly_vertices; a.cap_subs = out->cap_subpaths; a.check_caps = 1;
 	dashLaunch(ctx, a, true, s);
 	publish(ctx, dev_sizes, dev_status, s);
+	return launchStatus(ctx);
+}
+
+
+// ---- dashed strokes in frames: vgx_tessellate_dashed / vgx_reserve_dashed -------------------------------------------------------
+namespace {
+
+int dfInit(vgx_ctx* ctx)
+{
+	if (ctx->dfHost) { return VGX_OK; }
+	HIPCHK(ctx, hipHostMalloc((void**)&ctx->dfHost, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+	const hipError_t e = hipEventCreateWithFlags(&ctx->dfEv, hipEventDisableTiming);
+	if (e != hipSuccess) { (void)hipHostFree(ctx->dfHost); ctx->dfHost = nullptr; ctx->lastHipError = (int)e; return VGX_E_HIP; }
+	memset(ctx->dfHost, 0, 4 * sizeof(unsigned long long));
+	ctx->dfEvPending = false;
+	return VGX_OK;
+}
+
+// The context's scratch for frames of `meshes` meshes (source meshes that stay + pieces), `pieces` pieces of `pieceVerts` vertices: the
+// tail of the polyline scratch (the flatten stage's heap keeps the vertices it has), both sets of mesh tables, the per-mesh lists, the
+// pieces' records. Grow-only, like every table of the context.
+int dfEnsure(vgx_ctx* ctx, uint64_t meshes, uint64_t pieces, uint64_t pieceVerts)
+{
+	int st;
+	const uint64_t heap = ctx->poly.cap ? ctx->caps.poly_vertices : 4096;
+	if (pieceVerts > ctx->pieceVerts) { ctx->pieceVerts = pieceVerts + pieceVerts / 8; }
+	if ((st = ensureMeshBuffers(ctx, heap, 1024, meshes > 1024 ? meshes : 1024)) != VGX_OK) { return st; }
+	const uint64_t m = ctx->caps.meshes + 1;
+	if ((st = ensure(ctx, ctx->mdesc2, m * sizeof(VgxMeshDesc))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mprep2, m * sizeof(VgxMeshPrep))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mtab2, m * sizeof(vgx_mesh))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfLists, m * sizeof(vgx_subpath))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfListDraw, m * sizeof(uint32_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfDashedBefore, m * sizeof(uint64_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfPieceSubs, (pieces + 1) * sizeof(vgx_subpath))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfPieceDraw, (pieces + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfPieceSrc, (pieces + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfTotals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	return ensure(ctx, ctx->dfNeed, 4 * sizeof(uint64_t));
+}
+
+uint64_t dfPieceCap(const vgx_ctx* ctx)
+{
+	uint64_t c = ctx->dfPieceSubs.cap / sizeof(vgx_subpath);
+	{ const uint64_t c2 = ctx->dfPieceDraw.cap / sizeof(uint32_t), c3 = ctx->dfPieceSrc.cap / sizeof(uint32_t); if (c2 < c) { c = c2; } if (c3 < c) { c = c3; } }
+	return c - 1;
+}
+
+} // namespace
+
+int vgx_reserve_dashed(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals, const vgx_sizes* dash_totals)
+{
+	if (!ctx || !totals || !dash_totals) { return VGX_E_INVALID_ARG; }
+	int st;
+	if ((st = vgx_reserve(ctx, ndraws, totals)) != VGX_OK) { return st; }
+	DeviceGuard guard(ctx);
+	if ((st = dfInit(ctx)) != VGX_OK) { return st; }
+	if ((st = dashHostMirror(ctx)) != VGX_OK) { return st; }
+	// every source mesh may stay (the frame's meshes + at most one dashed mesh without pieces per sub-path) and every piece is a mesh; a list
+	// has at most as many segments as vertices
+	if ((st = dfEnsure(ctx, totals->num_meshes + totals->num_subpaths + dash_totals->num_subpaths, dash_totals->num_subpaths, dash_totals->num_poly_vertices)) != VGX_OK) { return st; }
+	if (totals->num_poly_vertices + 1 > ctx->dashG.cap / sizeof(uint64_t) || totals->num_poly_vertices + 1 > ctx->dashGhi.cap / sizeof(uint64_t)) {
+		if ((st = dashEnsureSegments(ctx, totals->num_poly_vertices)) != VGX_OK) { return st; }
+	}
+	return VGX_OK;
+}
+
+int vgx_tessellate_dashed(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const struct vgx_dash* dashes, const float* pattern, uint64_t npattern,
+                          const vgx_mesh_out* out, vgx_sizes* dev_sizes, vgx_sizes* dev_dash_sizes, uint32_t* dev_status, void* stream)
+{
+	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx || (npattern && !pattern)) { // (before the context is touched)
+		return VGX_E_INVALID_ARG;
+	}
+	if (((uintptr_t)dashes & 3u) || ((uintptr_t)pattern & 3u)) { return VGX_E_INVALID_ARG; }
+	if (!dashes || !ndraws) { // no dash records: the immediate call itself
+		const int st0 = vgx_tessellate_immediate(ctx, ps, draws, ndraws, out, dev_sizes, dev_status, stream);
+		if (st0 != VGX_OK) { return st0; }
+		DeviceGuard guard0(ctx);
+		if (dev_dash_sizes) { noteHip(ctx, hipMemsetAsync(dev_dash_sizes, 0, sizeof(vgx_sizes), (hipStream_t)stream)); }
+		return launchStatus(ctx);
+	}
+	DeviceGuard guard(ctx);
+	hipStream_t s = (hipStream_t)stream;
+	int st;
+	if ((st = immInit(ctx)) != VGX_OK) { return st; }
+	if ((st = dfInit(ctx)) != VGX_OK) { return st; }
+	// counted state ends here, as with vgx_tessellate_immediate
+	ctx->lastStage = 0; ctx->f1Route = false;
+	forgetRoutes(ctx);
+	// (1) what the last calls left in the mirrors, once it has arrived: the flatten stage's need (immConsume), the pieces', the segments'
+	// (dashPrepare); (2) the tables every call needs (a fresh context gets small ones and learns the need from its first calls)
+	if ((st = immConsume(ctx, ps)) != VGX_OK) { return st; }
+	uint64_t needMeshes = 1024, needPieces = 4096, needPieceVerts = 16384;
+	if (ctx->dfEvPending && hipEventQuery(ctx->dfEv) == hipSuccess) {
+		ctx->dfEvPending = false;
+		if (ctx->dfHost[3]) { needPieces = ctx->dfHost[0]; needPieceVerts = ctx->dfHost[1]; needMeshes = ctx->dfHost[2] + ctx->dfHost[0]; }
+	}
+	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
+	if ((st = ensureCmdScratch(ctx, 4096)) != VGX_OK) { return st; }
+	if ((st = dfEnsure(ctx, needMeshes, needPieces, needPieceVerts)) != VGX_OK) { return st; }
+	const uint64_t tag = ps->gen * 0x9E3779B97F4A7C15ull + ndraws;
+	const uint64_t segGuess = (ctx->immKnown && ctx->immTag == tag && ctx->immV > 65536) ? ctx->immV : 65536; // (segments <= vertices of the source lists)
+	VgxDashArgs a;
+	if ((st = dashPrepare(ctx, (const float*)ctx->poly.p, (const vgx_subpath*)ctx->dfLists.p, (const uint32_t*)ctx->dfListDraw.p, ctx->caps.meshes,
+	                      dashes, ndraws, pattern, npattern, segGuess, &a)) != VGX_OK) { return st; }
+	markBegin(ctx, s);
+	VgxTotals* T = (VgxTotals*)ctx->totals.p;
+	// the flatten stage: k_flatten_build for any number of draws (its descriptors are complete and in frame order, the exact builder's included)
+	ctx->instPeriod = 0;
+	mark(ctx, s, "route_build");
+	runCmdPrefix(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, s, 0);
+	runFlattenBuild(ctx, ps, draws, ndraws, s);
+	vgx_launch_imm_size(ps->dev, draws, ndraws, T, 1, false, nullptr, nullptr, s); // (a VGX_E_NOSPACE here is the scratch's)
+	mark(ctx, s, "imm_size");
+	// the dash pass over the stroke meshes of the dashed draws, pieces into the tail of the polyline scratch
+	VgxDashFrameArgs f;
+	memset(&f, 0, sizeof(f));
+	f.draws = draws; f.dashes = dashes;
+	f.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; f.mtab = (const vgx_mesh*)ctx->mtab.p; f.mprep = (const VgxMeshPrep*)ctx->mprep.p;
+	f.mdesc2 = (VgxMeshDesc*)ctx->mdesc2.p; f.mtab2 = (vgx_mesh*)ctx->mtab2.p; f.mprep2 = (VgxMeshPrep*)ctx->mprep2.p;
+	f.lists = (vgx_subpath*)ctx->dfLists.p; f.list_draw = (uint32_t*)ctx->dfListDraw.p; f.dashed_before = (uint64_t*)ctx->dfDashedBefore.p;
+	f.need = (uint64_t*)ctx->dfNeed.p; f.nlists = f.need + 2; // (the join writes the same value there)
+	f.piece_subs = (const vgx_subpath*)ctx->dfPieceSubs.p; f.piece_src = (const uint32_t*)ctx->dfPieceSrc.p;
+	f.piece_base = ctx->caps.poly_vertices + 1;
+	f.cap_meshes = ctx->caps.meshes;
+	f.totals = T; f.dash_totals = (VgxTotals*)ctx->dfTotals.p;
+	f.dev_dash_sizes = dev_dash_sizes;
+	f.partial = (Sum3*)ctx->partial.p;
+	vgx_launch_dashframe_lists(f, s);
+	mark(ctx, s, "dashframe_lists");
+	a.totals = f.dash_totals;
+	a.nsubs_dev = f.nlists; a.frame = 1;
+	a.out_poly = (float*)ctx->poly.p + 2 * f.piece_base; a.out_subs = (vgx_subpath*)ctx->dfPieceSubs.p;
+	a.out_draw = (uint32_t*)ctx->dfPieceDraw.p; a.out_src = (uint32_t*)ctx->dfPieceSrc.p;
+	a.cap_poly = ctx->pieceVerts; a.cap_subs = dfPieceCap(ctx); a.check_caps = 1;
+	dashLaunch(ctx, a, true, s);
+	// the frame's meshes by slot; from here on the second set of tables is the context's
+	vgx_launch_dashframe_place(f, s);
+	mark(ctx, s, "dashframe_place");
+	{ DevBuf t = ctx->mdesc; ctx->mdesc = ctx->mdesc2; ctx->mdesc2 = t; }
+	{ DevBuf t = ctx->mprep; ctx->mprep = ctx->mprep2; ctx->mprep2 = t; }
+	{ DevBuf t = ctx->mtab; ctx->mtab = ctx->mtab2; ctx->mtab2 = t; }
+	if ((st = ensureMeshBuffers(ctx, 0, 0, 0)) != VGX_OK) { return st; } // (caps from the swapped tables: the sets may differ in head room)
+	runStrokeCount(ctx, draws, outCapsFor(ctx, out), 1, s, nullptr, true, out->meshes);
+	if ((st = runStrokeEmit(ctx, draws, out, s, nullptr, true)) != VGX_OK) { return st; }
+	vgx_launch_imm_publish(T, dev_sizes, dev_status, s);
+	// the totals and the pieces' need to the mirrors, for the next call (never waited for)
+	noteHip(ctx, hipMemcpyAsync(ctx->immHost, T, sizeof(VgxTotals), hipMemcpyDeviceToHost, s));
+	noteHip(ctx, hipEventRecord(ctx->immEv, s));
+	ctx->immEvPending = true; ctx->immPendTag = tag; ctx->immPendNDraws = ndraws; ctx->immPendDetect = false;
+	noteHip(ctx, hipMemcpyAsync(ctx->dfHost, ctx->dfNeed.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+	noteHip(ctx, hipEventRecord(ctx->dfEv, s));
+	ctx->dfEvPending = true;
 	return launchStatus(ctx);
 }
 

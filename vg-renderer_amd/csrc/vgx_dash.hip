@@ -34,6 +34,9 @@ template <class KEY> __device__ __forceinline__ uint64_t dash_find(uint64_t n, u
 	return lo;
 }
 
+// lists of the call: a host value, or (vgx_tessellate_dashed) a word an earlier launch wrote
+__device__ __forceinline__ uint64_t dash_nsubs(const VgxDashArgs& A) { return A.nsubs_dev ? *A.nsubs_dev : A.nsubs; }
+
 __device__ __forceinline__ bool dash_list_dashed(const VgxDashArgs& A, uint64_t l, uint32_t* draw)
 {
 	const uint32_t d = A.sub_draw[l];
@@ -59,7 +62,7 @@ __global__ __launch_bounds__(256) void k_dash_draws(VgxDashArgs A)
 struct OpDashSegs // segments per list -> seg_base
 {
 	VgxDashArgs A;
-	__device__ uint64_t size() const { return A.nsubs; }
+	__device__ uint64_t size() const { return dash_nsubs(A); }
 	__device__ Sum3 load(uint64_t l) const
 	{
 		Sum3 r = sum3_zero();
@@ -74,7 +77,7 @@ struct OpDashSegs // segments per list -> seg_base
 	__device__ void store(uint64_t l, Sum3 e) const { A.lists[l].seg_base = e.a; }
 	__device__ void finish(Sum3 t) const
 	{
-		A.lists[A.nsubs].seg_base = t.a;
+		A.lists[dash_nsubs(A)].seg_base = t.a;
 		A.tot[0] = t.a;
 		if (t.a > A.seg_cap) { dash_fail(A.totals, VGX_E_GROWN); }
 	}
@@ -88,7 +91,7 @@ struct OpDashLen // q(len) per segment -> G (and the guard sums)
 	{
 		Sum3 r = sum3_zero();
 		const VgxDashListRec* lists = A.lists;
-		const uint64_t l = dash_find(A.nsubs, i, [lists](uint64_t k) { return lists[k].seg_base; });
+		const uint64_t l = dash_find(dash_nsubs(A), i, [lists](uint64_t k) { return lists[k].seg_base; });
 		const vgx_subpath sp = A.subs[l];
 		const uint32_t k = (uint32_t)(i - lists[l].seg_base);
 		const uint32_t k1 = k + 1u == sp.num_vertices ? 0u : k + 1u;
@@ -112,7 +115,7 @@ __device__ __forceinline__ bool dash_list_eval(const VgxDashArgs& A, uint64_t l,
 {
 	*ncand = 0; *jlo = 0; *T = 0;
 	uint32_t d;
-	if (!dash_list_dashed(A, l, &d)) { *ncand = 1; return true; }
+	if (!dash_list_dashed(A, l, &d)) { *ncand = A.frame ? 0u : 1u; return true; } // (a frame keeps the mesh descriptor of such a list: no copy)
 	const vgx_subpath sp = A.subs[l];
 	const uint32_t m = vgx_dash_num_segments(sp.num_vertices, sp.flags);
 	if (m == 0) { return true; }
@@ -129,7 +132,7 @@ __device__ __forceinline__ bool dash_list_eval(const VgxDashArgs& A, uint64_t l,
 struct OpDashCand // "on" intervals per list -> cand_off, jlo, T
 {
 	VgxDashArgs A;
-	__device__ uint64_t size() const { return A.totals->status == VGX_OK ? A.nsubs : 0ull; }
+	__device__ uint64_t size() const { return A.totals->status == VGX_OK ? dash_nsubs(A) : 0ull; }
 	__device__ Sum3 load(uint64_t l) const
 	{
 		Sum3 r = sum3_zero();
@@ -145,7 +148,7 @@ struct OpDashCand // "on" intervals per list -> cand_off, jlo, T
 	}
 	__device__ void finish(Sum3 t) const
 	{
-		A.lists[A.nsubs].cand_off = t.a;
+		A.lists[dash_nsubs(A)].cand_off = t.a;
 		A.tot[1] = t.a;
 		if (t.a > VGX_DASH_MAX_INTERVALS || A.tot[2]) { dash_fail(A.totals, VGX_E_RANGE); }
 	}
@@ -176,7 +179,7 @@ __device__ __forceinline__ VgxDashList dash_list_of(const VgxDashArgs& A, uint64
 __device__ __forceinline__ void dash_item(const VgxDashArgs& A, uint64_t c, DashItem* it)
 {
 	const VgxDashListRec* lists = A.lists;
-	const uint64_t l = dash_find(A.nsubs, c, [lists](uint64_t k) { return lists[k].cand_off; });
+	const uint64_t l = dash_find(dash_nsubs(A), c, [lists](uint64_t k) { return lists[k].cand_off; });
 	const vgx_subpath sp = A.subs[l];
 	it->list = l;
 	it->copy = !dash_list_dashed(A, l, &it->draw);

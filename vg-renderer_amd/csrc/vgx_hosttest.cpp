@@ -410,3 +410,23 @@ int vgxt_dash(const float* poly, const vgx_subpath* subs, const uint32_t* sub_dr
 }
 
 }
+
+#include "vgx_dashframe.h"
+
+extern "C" {
+
+// The slots of a frame with dashed strokes (vgx_dashframe.h), as k_dashframe_place finds them: dashed[m] != 0 marks the source meshes the
+// dash pass cut, piece_src[p] the source mesh of every piece (non-decreasing). slot_kept[m] = the frame slot of source mesh m (~0 for a
+// dashed one), slot_piece[p] = the slot of piece p. Returns the number of meshes of the frame.
+uint64_t vgxt_dashframe_ranks(const uint8_t* dashed, uint64_t nsource, const uint32_t* piece_src, uint64_t npieces, uint64_t* slot_kept, uint64_t* slot_piece)
+{
+	std::vector<uint64_t> before(nsource + 1, 0); // D(m): the scan OpDashFrameLists
+	for (uint64_t m = 0; m < nsource; ++m) { before[m + 1] = before[m] + (dashed[m] ? 1u : 0u); }
+	for (uint64_t m = 0; m < nsource; ++m) {
+		slot_kept[m] = dashed[m] ? ~0ull : vgx_df_slot_kept(m, before[m], before[m] ? vgx_df_pieces_before(piece_src, npieces, m) : 0ull);
+	}
+	for (uint64_t p = 0; p < npieces; ++p) { slot_piece[p] = vgx_df_slot_piece(piece_src[p], before[piece_src[p]], p); }
+	return vgx_df_num_meshes(nsource, before[nsource], npieces);
+}
+
+}

@@ -275,8 +275,40 @@ struct VgxDashArgs
 	int check_caps;
 	VgxTotals* totals;
 	struct Sum3* partial;
+	// vgx_tessellate_dashed (vgx_dashframe.hip): the lists are the flatten stage's own mesh descriptors, so their number is a device
+	// word (nsubs is then the host's bound of it), and a list of an undashed draw produces nothing (its mesh descriptor is used as it is)
+	const uint64_t* nsubs_dev; // null: nsubs
+	int frame;
 };
 void vgx_launch_dash(const VgxDashArgs& a, bool emit, hipStream_t s);
+
+// a frame with dashed strokes (vgx_dashframe.hip; the slots: vgx_dashframe.h)
+struct VgxDashFrameArgs
+{
+	const vgx_draw* draws;
+	const struct vgx_dash* dashes;  // [ndraws]
+	const VgxMeshDesc* mdesc;       // the flatten stage's meshes, frame order (source)
+	const vgx_mesh* mtab;
+	const VgxMeshPrep* mprep;
+	VgxMeshDesc* mdesc2;            // the frame's meshes: kept source meshes + one per piece
+	vgx_mesh* mtab2;
+	VgxMeshPrep* mprep2;
+	vgx_subpath* lists;             // [cap_meshes + 1] per source mesh: the list the dash pass cuts (dashed stroke meshes; else empty)
+	uint32_t* list_draw;            // [cap_meshes + 1]
+	uint64_t* dashed_before;        // [cap_meshes + 1] D(m)
+	uint64_t* nlists;               // device word: source meshes (0 when the flatten stage failed)
+	const vgx_subpath* piece_subs;  // the dash pass's records: first_vertex relative to piece_base
+	const uint32_t* piece_src;      // source mesh of every piece
+	uint64_t piece_base;            // first piece vertex in the polyline scratch (behind the flatten stage's heap: one allocation holds both)
+	uint64_t cap_meshes;            // what the mesh tables hold
+	VgxTotals* totals;              // the call's
+	VgxTotals* dash_totals;         // the dash pass's (pieces, their vertices, its verdict)
+	uint64_t* need;                 // [4] device: pieces, piece vertices, source meshes, 1 -> the host's mirror
+	vgx_sizes* dev_dash_sizes;      // caller's, may be null
+	struct Sum3* partial;
+};
+void vgx_launch_dashframe_lists(const VgxDashFrameArgs& a, hipStream_t s);
+void vgx_launch_dashframe_place(const VgxDashFrameArgs& a, hipStream_t s);
 void vgx_launch_subpath_draws(const vgx_draw_info* dinfo, uint64_t ndraws, uint32_t* subDraw, uint64_t nsubs, hipStream_t s);
 
 // launchers (defined in the .hip files)

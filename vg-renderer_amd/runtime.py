@@ -84,6 +84,20 @@ class Context:
             sizes = z
         _check(lib().vgx_reserve(self._h, int(ndraws), C.byref(sizes)), "vgx_reserve")
 
+    def reserve_dashed(self, ndraws, sizes, dash_sizes):
+        """vgx_reserve_dashed: size the scratch for frames up to `sizes` (what tessellate_dashed leaves in dev_sizes) whose dashed
+        strokes make up to `dash_sizes` (its dev_dash_sizes: num_subpaths pieces of num_poly_vertices vertices), so that such a
+        frame takes one tessellate_dashed call. Dicts or capi.Sizes."""
+        def as_sizes(d):
+            if not isinstance(d, dict):
+                return d
+            z = capi.Sizes()
+            for k in ("num_cmd_instances", "num_poly_vertices", "num_subpaths", "num_meshes"):
+                setattr(z, k, int(d.get(k, 0)))
+            return z
+        sizes, dash_sizes = as_sizes(sizes), as_sizes(dash_sizes)
+        _check(lib().vgx_reserve_dashed(self._h, int(ndraws), C.byref(sizes), C.byref(dash_sizes)), "vgx_reserve_dashed")
+
     def set_profiling(self, on):
         _check(lib().vgx_set_profiling(self._h, 1 if on else 0), "vgx_set_profiling")
 
@@ -514,6 +528,58 @@ def dash(ctx, poly_dev, subs_dev, subdraw_dev, nsubs, dashes_dev, ndraws, patter
         r.sub_draw = bufs.sub_draw[:nsp].cpu().numpy().view(np.uint32)
         r.sub_src = bufs.sub_src[:nsp].cpu().numpy().view(np.uint32)
     return r
+
+
+def stroke_async(ctx, poly_dev, subs_dev, subdraw_dev, nsubs, draws_dev, ndraws, bufs):
+    """vgx_stroke: the stroker-level entry as one asynchronous call (the bytes of stroke()); totals / status land in bufs.dev_*."""
+    out = bufs.out_struct()
+    _check(lib().vgx_stroke(ctx.handle, poly_dev.data_ptr(), subs_dev.data_ptr(), subdraw_dev.data_ptr(), nsubs, draws_dev.data_ptr(), ndraws,
+                            C.byref(out), bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_stroke")
+
+
+# ---- dashed strokes in frames (vgx_tessellate_dashed): draws + one dash record per draw in, the frame's meshes out ----------
+def tessellate_dashed_async(ctx, pset, draws_dev, ndraws, dashes_dev, pattern_dev, npattern, bufs, dev_dash_sizes=None):
+    """vgx_tessellate_dashed: asynchronous like tessellate_immediate. dashes_dev uint8 (16-byte struct vgx_dash records, one per
+    draw) or None, pattern_dev float32 [npattern]. The verdict lands in bufs.dev_status (VGX_OK / VGX_E_NOSPACE: grow the buffers
+    to bufs.dev_sizes / VGX_E_GROWN: call again), the totals in bufs.dev_sizes, the pieces' totals in dev_dash_sizes (int64 [10])."""
+    out = bufs.out_struct()
+    _check(lib().vgx_tessellate_dashed(ctx.handle, pset.handle, draws_dev.data_ptr(), ndraws, dashes_dev.data_ptr() if dashes_dev is not None else None,
+                                       pattern_dev.data_ptr() if npattern else None, npattern, C.byref(out), bufs.dev_sizes.data_ptr(),
+                                       dev_dash_sizes.data_ptr() if dev_dash_sizes is not None else None, bufs.dev_status.data_ptr(), _stream_ptr()),
+           "vgx_tessellate_dashed")
+
+
+def tessellate_dashed(ctx, pset, draws_dev, ndraws, dashes_dev, pattern_dev, npattern, bufs=None, growth=1.5, max_calls=4, to_host=True):
+    """The immediate-mode loop over tessellate_dashed_async (as tessellate_grow): until VGX_OK, growing the buffers after
+    VGX_E_NOSPACE. Returns a MeshResult with .statuses (one per call), .sizes, .dash_sizes, .bufs and numpy copies when to_host."""
+    import torch
+    if bufs is None:
+        bufs = MeshBuffers(draws_dev.device, 1024, 1024, 64)
+    dds = torch.zeros(10, dtype=torch.int64, device=draws_dev.device)
+    statuses = []
+    for _ in range(max_calls):
+        tessellate_dashed_async(ctx, pset, draws_dev, ndraws, dashes_dev, pattern_dev, npattern, bufs, dds)
+        st = int(bufs.dev_status.item())  # (synchronises)
+        statuses.append(st)
+        sizes = capi.Sizes.from_buffer_copy(bufs.dev_sizes.cpu().numpy().tobytes()).as_dict()
+        if st == capi.VGX_OK:
+            r = MeshResult()
+            r.statuses, r.sizes, r.bufs = statuses, sizes, bufs
+            r.dash_sizes = capi.Sizes.from_buffer_copy(dds.cpu().numpy().tobytes()).as_dict()
+            if to_host:
+                nv, ni, nm = sizes["num_vertices"], sizes["num_indices"], sizes["num_meshes"]
+                r.pos = bufs.pos[:nv].cpu().numpy()
+                r.color = bufs.color[:nv].cpu().numpy().view(np.uint32)
+                r.idx = bufs.idx[:ni].cpu().numpy().view(np.uint16)
+                r.meshes = bufs.meshes[:nm * 32].cpu().numpy().view(capi.mesh_dtype)
+            return r
+        if st == capi.VGX_E_NOSPACE:
+            nv, ni, nm = bufs.cap
+            bufs = MeshBuffers(draws_dev.device, _grown(nv, sizes["num_vertices"], growth), _grown(ni, sizes["num_indices"], growth),
+                               _grown(nm, sizes["num_meshes"], growth))
+        elif st != capi.VGX_E_GROWN:
+            raise VgxError(st, "vgx_tessellate_dashed (device)")
+    raise VgxError(statuses[-1], "tessellate_dashed: no VGX_OK within %d calls (%s)" % (max_calls, statuses))
 
 
 # ---- shape cache (vgx_cache_localize / vgx_cache_submit) ---------------------------------------------
