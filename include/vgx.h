@@ -528,6 +528,63 @@ int vgx_cache_localize(vgx_ctx* ctx, const vgx_draw* draws, uint64_t ndraws, flo
  * dev_status); honours vgx_set_assembly (createDrawCommand_VertexColor is what submitCachedMesh calls). */
 int vgx_cache_submit(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_instance* instances, uint64_t ninst, const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
 
+/* ---- bounding boxes and view culling (beyond the reference): vgx_mesh_bounds -> vgx_cache_cull -> vgx_cache_submit ----------
+ * The reference culls a command only on an empty scissor rectangle (src/vg.cpp:4543-4567). A cached mesh is finished geometry, so
+ * its box is an exact min / max, and the box of an instance follows from it exactly (below): instances that miss the view can be
+ * dropped on the device before vgx_cache_submit pays 21 bytes per vertex for them. Draws that go through vgx_tessellate* are NOT
+ * culled by anything here: no path-level box bounds a Miter stroke, whose joins the reference extrudes up to 200 half widths
+ * (kMaxExtrusionScale, src/stroker.cpp:45).
+ *
+ * vgx_mesh_bounds: bounds[m] = minx, miny, maxx, maxy, the exact minimum and maximum over pos[first_vertex .. first_vertex + num_vertices)
+ * of meshes[m], for any mesh stream the library wrote (vgx_tessellate*, vgx_stroke, vgx_cache_submit, vgx_merge, vgx_text_quads:
+ * boxes in device space; a localized cache: boxes in local space). Minimum and maximum do not depend on the order of evaluation:
+ * the values are the same on every run and for every decomposition of the work. -0 and +0 compare equal and either may be stored.
+ * A mesh of 0 vertices gets the empty box (+inf, +inf, -inf, -inf). Positions are never NaN in what the library writes from valid
+ * input (path sets reject NaN); the result for a NaN position is unspecified.
+ * PRECONDITION, not checked: the mesh table is ascending in first_vertex with disjoint vertex ranges (0-vertex records share their
+ * successor's first_vertex or the end of the stream). vgx_tessellate*, vgx_stroke, vgx_cache_submit and vgx_merge write such tables.
+ * vgx_text_quads places every run where its record says and writes a 0 / 0 record for a failed run: its table qualifies when the
+ * caller laid the runs out ascending (the dense layout does) and no run failed; that is the caller's duty. A table that breaks the
+ * rule gets wrong boxes and no status. Only the vertices inside the meshes' ranges are read, whatever the order. All pointers are DEVICE pointers, `pos` 8-byte and `bounds` 16-byte aligned; `bounds` has
+ * [num_meshes][4] floats. Asynchronous, no scratch of the context is used, no counted state is ended or disturbed. */
+int vgx_mesh_bounds(vgx_ctx* ctx, const float* pos, const vgx_mesh* meshes, uint64_t num_meshes, float* bounds, void* stream);
+
+/* vgx_cache_cull: instances of a cache against view rectangles. views[v] = x0, y0, x1, y1 in device space, closed (the state's
+ * scissor, or the canvas); inst_view[i] picks the view of instance i (NULL: view 0 for all), so one call covers a frame whose scissor
+ * changes. mesh_bounds = what vgx_mesh_bounds gave for the localized cache. For instance i, in this order:
+ *   - Validity. The range [first_mesh, first_mesh + num_meshes) must lie inside the cache and the view index below nviews; else
+ *     dev_status receives VGX_E_INVALID_ARG, the record is written with num_meshes = 0, its box is the empty box, it is not kept.
+ *   - Local box. L = the union of mesh_bounds[first_mesh .. first_mesh + num_meshes). If L is empty (minx > maxx or miny > maxy: an
+ *     empty range, or nothing but 0-vertex meshes) the instance draws nothing: it is culled and its box is the empty box.
+ *   - Device box. B = minimum / maximum over the four corners of L, (minx,miny) (maxx,miny) (maxx,maxy) (minx,maxy), each moved
+ *     through the very function vgx_cache_submit moves a vertex through: (m0*x + m2*y) + m4, (m1*x + m3*y) + m5 in binary32 without
+ *     FMA. Every operation in it is monotone in x and in y, so B contains every vertex the instance submits EXACTLY: no margin, no
+ *     tolerance. With m1 == m2 == 0 it is the exact box of those vertices. A NaN among the four corners makes the bound it enters NaN.
+ *   - Cull rule. With v = the instance's view: culled iff x0 > x1 || y0 > y1 (an empty view culls everything: the reference's
+ *     empty-scissor rule), or B.maxx < x0 || B.minx > x1 || B.maxy < y0 || B.miny > y1. Written this way a NaN bound from a wild
+ *     matrix compares false: such an instance is kept (vgx_cache_submit then writes what the reference would).
+ * Outputs (all DEVICE):
+ *   out->inst[i]    the input record byte for byte when the instance is kept; the same record with num_meshes = 0 when it is not.
+ *                   The array keeps its length and order: the next call is vgx_cache_submit with out->inst and ninst, no count
+ *                   comes back from the device, and vgx_mesh::draw of the frame still names the original instance. May be the
+ *                   input array itself (in place).
+ *   out->bounds[i]  B (the empty box for a culled-as-empty or invalid instance). May be NULL.
+ *   out->kept       the indices of the kept instances, ascending and dense; out->num_kept their count. Either may be NULL; with
+ *                   both NULL the compaction pass is skipped.
+ * dev_status (DEVICE uint32, may be NULL): VGX_OK or VGX_E_INVALID_ARG as above. Nothing is written outside the ninst entries of
+ * each array (num_kept entries of `kept`). Asynchronous; uses a small scratch of its own, so a counted state survives the call:
+ * vgx_tessellate_count -> vgx_mesh_bounds / vgx_cache_cull -> vgx_tessellate_emit works. mesh_bounds and out->bounds are 16-byte
+ * aligned. Host return values: VGX_OK once the work is enqueued, VGX_E_INVALID_ARG for null or misaligned pointers or nviews == 0
+ * with ninst != 0, VGX_E_RANGE for ninst >= 2^32, VGX_E_HIP. */
+typedef struct vgx_cull_out {
+	vgx_cache_instance* inst;  /* [ninst]; may be the input array itself */
+	float*    bounds;          /* [ninst][4], may be NULL */
+	uint32_t* kept;            /* [ninst], may be NULL */
+	uint64_t* num_kept;        /* may be NULL */
+} vgx_cull_out;
+int vgx_cache_cull(vgx_ctx* ctx, const vgx_cache_desc* cache, const float* mesh_bounds, const vgx_cache_instance* inst, uint64_t ninst,
+                   const float* views, uint32_t nviews, const uint32_t* inst_view, const vgx_cull_out* out, uint32_t* dev_status, void* stream);
+
 /* ---- concave fills with AA fringes -------------------------------------------------
  * strokerConcaveFillEndAA (src/stroker.cpp:868-1006) alternates libtess2 and the stroker's own loops:
  *   (1) tessTesselate(TESS_BOUNDARY_CONTOURS) of the contours added with strokerConcaveFillAddContour     [caller, CPU]

@@ -124,6 +124,10 @@ class CacheDesc(C.Structure):
                 ("num_meshes", C.c_uint64), ("num_vertices", C.c_uint64), ("num_indices", C.c_uint64)]
 
 
+class CullOut(C.Structure):  # vgx_cull_out: device pointers, any but `inst` may be None
+    _fields_ = [("inst", C.c_void_p), ("bounds", C.c_void_p), ("kept", C.c_void_p), ("num_kept", C.c_void_p)]
+
+
 class Assembly(C.Structure):
     _fields_ = [("drawcmds", C.c_void_p), ("cap_drawcmds", C.c_uint64), ("dev_num_drawcmds", C.c_void_p),
                 ("max_vb_vertices", C.c_uint32), ("flags", C.c_uint32), ("uv", C.c_void_p), ("uv_bytes", C.c_uint32),
@@ -207,6 +211,9 @@ VGX_SYMBOLS = {
     "vgx_merge": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_merge_uv": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_cache_submit": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_mesh_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "vgx_cache_cull": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                 C.POINTER(CullOut), C.c_void_p, C.c_void_p]),
     "vgx_last_hip_error": (C.c_int, [C.c_void_p]),
     "vgx_status_string": (C.c_char_p, [C.c_int]),
     "vgx_version": (C.c_uint32, []),

@@ -79,6 +79,8 @@ struct vgx_ctx
 	DevBuf subPrefix; // exclusive scan of the draws' static sub-path counts
 	DevBuf cmdPrefix, cmdCnt, subFirst, leafOverflow, serialList, dinfo, poly, subs, mdesc, elemPrefix, elemPrefixS, mprep, mtab, partial, totals;
 	DevBuf textTiles;                    // vgx_text_quads: first run of every tile of quads (vgx_text.hip)
+	DevBuf cullFlags, cullPartial;       // vgx_cache_cull (vgx_bounds.hip): kept flag per instance, the compaction scan's slice sums. Its own: a counted state survives the call
+	uint32_t optCullWaveMin;             // mesh ranges of at least this many boxes are united by the whole wave; >= 1, 2^32 - 1 = never = the default (VGX_CULL_WAVE_MIN)
 	// vgx_dash (vgx_dash.hip): per-draw patterns, per-list records, per-segment prefix sums (S and the overflow guard), per-range sums; the
 	// segment count of the last call in pinned memory (copied behind the call, read by the next call once its event has passed: a call
 	// whose lists outgrew dashG ends with VGX_E_GROWN and the next one grows first, as vgx_tessellate_immediate does)
@@ -969,6 +971,10 @@ int vgx_create(int device, vgx_ctx** out_ctx)
 	if (const char* e = getenv("VGX_BIG_EMIT_MIN")) { ctx->optBigEmitMin = strtoull(e, nullptr, 10); }
 	ctx->optStrokeLong = 1;
 	if (const char* e = getenv("VGX_STROKE_LONG")) { ctx->optStrokeLong = atoi(e) != 0; }
+	// never, unless asked: on 10 000 instances of 435 meshes one lane per range took 0.067 ms and the wave-reduced form (threshold 32) 0.101 ms;
+	// ranges of 1-3 meshes do not care (profiles/cache_cull_timing.json). VGX_CULL_WAVE_MIN=N > 0 turns the wave form on for ranges >= N
+	ctx->optCullWaveMin = 0xFFFFFFFFu;
+	if (const char* e = getenv("VGX_CULL_WAVE_MIN")) { const int v = atoi(e); ctx->optCullWaveMin = v <= 0 ? 0xFFFFFFFFu : (uint32_t)v; }
 	ctx->optTileEmit = 1;
 	if (const char* e = getenv("VGX_TILE_EMIT")) { ctx->optTileEmit = atoi(e) != 0; }
 	ctx->optPsNoSmall = getenv("VGX_PS_NO_SMALL") ? 1 : 0; // testing knob: frame-sized path sets through the large-set launch sequence
@@ -1011,7 +1017,7 @@ int vgx_destroy(vgx_ctx* ctx)
 		return VGX_E_INVALID_ARG;
 	}
 	DeviceGuard guard(ctx);
-	DevBuf* bufs[] = { &ctx->mdesc2, &ctx->mprep2, &ctx->mtab2, &ctx->dfLists, &ctx->dfListDraw, &ctx->dfDashedBefore, &ctx->dfPieceSubs, &ctx->dfPieceDraw, &ctx->dfPieceSrc, &ctx->dfTotals, &ctx->dfNeed, &ctx->dashPat, &ctx->dashLists, &ctx->dashG, &ctx->dashGhi, &ctx->dashRange, &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
+	DevBuf* bufs[] = { &ctx->cullFlags, &ctx->cullPartial, &ctx->mdesc2, &ctx->mprep2, &ctx->mtab2, &ctx->dfLists, &ctx->dfListDraw, &ctx->dfDashedBefore, &ctx->dfPieceSubs, &ctx->dfPieceDraw, &ctx->dfPieceSrc, &ctx->dfTotals, &ctx->dfNeed, &ctx->dashPat, &ctx->dashLists, &ctx->dashG, &ctx->dashGhi, &ctx->dashRange, &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
 	for (DevBuf* b : bufs) {
 		if (b->p) { (void)hipFree(b->p); }
 	}
@@ -1040,7 +1046,7 @@ uint64_t vgx_scratch_bytes(const vgx_ctx* ctx)
 	if (!ctx) {
 		return 0;
 	}
-	return ctx->mdesc2.cap + ctx->mprep2.cap + ctx->mtab2.cap + ctx->dfLists.cap + ctx->dfListDraw.cap + ctx->dfDashedBefore.cap + ctx->dfPieceSubs.cap + ctx->dfPieceDraw.cap + ctx->dfPieceSrc.cap + ctx->dfTotals.cap + ctx->dfNeed.cap + ctx->dashPat.cap + ctx->dashLists.cap + ctx->dashG.cap + ctx->dashGhi.cap + ctx->dashRange.cap + ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
+	return ctx->cullFlags.cap + ctx->cullPartial.cap + ctx->mdesc2.cap + ctx->mprep2.cap + ctx->mtab2.cap + ctx->dfLists.cap + ctx->dfListDraw.cap + ctx->dfDashedBefore.cap + ctx->dfPieceSubs.cap + ctx->dfPieceDraw.cap + ctx->dfPieceSrc.cap + ctx->dfTotals.cap + ctx->dfNeed.cap + ctx->dashPat.cap + ctx->dashLists.cap + ctx->dashG.cap + ctx->dashGhi.cap + ctx->dashRange.cap + ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
 }
 
 // ---- path set ---------------------------------------------------------------------------------------
@@ -2685,6 +2691,48 @@ int vgx_cache_submit(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_
 	vgx_launch_cache_copy(a, vgxElementGrid(out->cap_vertices), s);
 	mark(ctx, s, "cache_copy");
 	publish(ctx, dev_sizes, dev_status, s);
+	return launchStatus(ctx);
+}
+
+// ---- mesh bounds, view culling of cached instances (vgx_bounds.hip) -----------------------------------
+// Neither call touches the totals, the mesh tables or the stage of a counted state: count -> these -> emit still works.
+int vgx_mesh_bounds(vgx_ctx* ctx, const float* pos, const vgx_mesh* meshes, uint64_t num_meshes, float* bounds, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || (num_meshes && (!pos || !meshes || !bounds)) || ((uintptr_t)pos & 7u) || ((uintptr_t)meshes & 7u) || ((uintptr_t)bounds & 15u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	if (num_meshes > 0xFFFFFFFFull * 256ull) { return VGX_E_RANGE; }
+	if (num_meshes) { vgx_launch_mesh_bounds(pos, meshes, num_meshes, bounds, (hipStream_t)stream); }
+	return launchStatus(ctx);
+}
+
+int vgx_cache_cull(vgx_ctx* ctx, const vgx_cache_desc* cache, const float* mesh_bounds, const vgx_cache_instance* inst, uint64_t ninst,
+                   const float* views, uint32_t nviews, const uint32_t* inst_view, const vgx_cull_out* out, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || !cache || !out || (ninst && (!inst || !out->inst || !views || !nviews)) || (cache->num_meshes && !mesh_bounds)) {
+		return VGX_E_INVALID_ARG;
+	}
+	if (((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)inst & 7u) || ((uintptr_t)out->inst & 7u) || ((uintptr_t)out->bounds & 15u) || ((uintptr_t)views & 3u)
+		|| ((uintptr_t)inst_view & 3u) || ((uintptr_t)out->kept & 3u) || ((uintptr_t)out->num_kept & 7u) || ((uintptr_t)dev_status & 3u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	if (ninst > 0xFFFFFFFFull) { return VGX_E_RANGE; } // `kept` holds 32-bit indices
+	hipStream_t s = (hipStream_t)stream;
+	const bool compact = out->kept || out->num_kept;
+	int st;
+	if (compact) {
+		if ((st = ensure(ctx, ctx->cullFlags, ninst + 1)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->cullPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	}
+	if (dev_status) { noteHip(ctx, hipMemsetAsync(dev_status, 0, sizeof(uint32_t), s)); } // VGX_OK
+	VgxCullArgs a;
+	memset(&a, 0, sizeof(a));
+	a.cache_meshes = cache->num_meshes; a.mesh_bounds = mesh_bounds; a.inst = inst; a.ninst = ninst;
+	a.views = views; a.nviews = nviews; a.wave_min = ctx->optCullWaveMin; a.inst_view = inst_view;
+	a.out_inst = out->inst; a.out_bounds = out->bounds; a.flags = compact ? (uint8_t*)ctx->cullFlags.p : nullptr; a.status = dev_status;
+	vgx_launch_cache_cull(a, out->kept, out->num_kept, ctx->cullPartial.p, s);
 	return launchStatus(ctx);
 }
 

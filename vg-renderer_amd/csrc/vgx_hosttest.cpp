@@ -430,3 +430,58 @@ uint64_t vgxt_dashframe_ranks(const uint8_t* dashed, uint64_t nsource, const uin
 }
 
 }
+
+#include "vgx_bounds.h"
+
+extern "C" {
+
+// vgx_mesh_bounds on the host: the order-preserving images of vgx_bounds.h (the ones the kernel of vgx_bounds.hip reduces and combines)
+// vertex after vertex, decoded at the end as the call's last kernel does.
+void vgxt_mesh_bounds(const float* pos, const vgx_mesh* meshes, uint64_t num_meshes, float* bounds)
+{
+	for (uint64_t m = 0; m < num_meshes; ++m) {
+		uint32_t lox = VGX_ORD_POS_INF, loy = VGX_ORD_POS_INF, hix = VGX_ORD_NEG_INF, hiy = VGX_ORD_NEG_INF;
+		const float* p = pos + 2 * meshes[m].first_vertex;
+		for (uint32_t v = 0; v < meshes[m].num_vertices; ++v) {
+			const uint32_t x = vgx_ord_from_float(p[2 * v]), y = vgx_ord_from_float(p[2 * v + 1]);
+			if (x < lox) { lox = x; }
+			if (y < loy) { loy = y; }
+			if (x > hix) { hix = x; }
+			if (y > hiy) { hiy = y; }
+		}
+		bounds[4 * m] = vgx_float_from_ord(lox); bounds[4 * m + 1] = vgx_float_from_ord(loy);
+		bounds[4 * m + 2] = vgx_float_from_ord(hix); bounds[4 * m + 3] = vgx_float_from_ord(hiy);
+	}
+}
+
+uint32_t vgxt_ord_from_float(float f) { return vgx_ord_from_float(f); }
+float vgxt_float_from_ord(uint32_t o) { return vgx_float_from_ord(o); }
+
+// vgx_cache_cull on the host: the functions of vgx_bounds.h instance after instance, with the call's contract (out->inst may be `inst`;
+// bounds / kept / num_kept may be NULL). Returns the status the device call leaves in dev_status.
+int vgxt_cache_cull(uint64_t cache_meshes, const float* mesh_bounds, const vgx_cache_instance* inst, uint64_t ninst,
+                    const float* views, uint32_t nviews, const uint32_t* inst_view, const vgx_cull_out* out)
+{
+	int status = VGX_OK;
+	uint64_t nk = 0;
+	for (uint64_t i = 0; i < ninst; ++i) {
+		vgx_cache_instance in = inst[i];
+		const uint32_t view = inst_view ? inst_view[i] : 0u;
+		VgxBox B = vgx_box_empty();
+		bool keep = false;
+		if (vgx_cull_valid(in, cache_meshes, view, nviews)) {
+			keep = vgx_cull_decide(vgx_box_union_range(mesh_bounds, in.first_mesh, in.num_meshes), in.mtx, views + 4 * (uint64_t)view, &B);
+		} else {
+			status = VGX_E_INVALID_ARG;
+		}
+		if (!keep) { in.num_meshes = 0; }
+		if (!keep || out->inst != inst) { out->inst[i] = in; }
+		if (out->bounds) { vgx_box_store(out->bounds + 4 * i, B); }
+		if (keep && out->kept) { out->kept[nk] = (uint32_t)i; }
+		nk += keep ? 1u : 0u;
+	}
+	if (out->num_kept) { *out->num_kept = nk; }
+	return status;
+}
+
+}

@@ -391,4 +391,23 @@ void vgx_launch_cache_meshes(const VgxCacheArgs& a, hipStream_t s);
 void vgx_launch_cache_copy(const VgxCacheArgs& a, int numBlocks, hipStream_t s);
 void vgx_launch_fill(const VgxStrokeArgs& a, int numBlocks, hipStream_t s);
 
+// mesh bounds and view culling of cached instances (vgx_bounds.hip)
+struct VgxCullArgs
+{
+	uint64_t cache_meshes;            // meshes of the cache = entries of mesh_bounds
+	const float* mesh_bounds;         // [cache_meshes][4], 16-byte aligned
+	const vgx_cache_instance* inst;
+	uint64_t ninst;
+	const float* views;               // [nviews][4]
+	uint32_t nviews;
+	uint32_t wave_min;                // ranges of at least this many meshes are reduced by the whole wave (>= 1)
+	const uint32_t* inst_view;        // [ninst] or null: view 0
+	vgx_cache_instance* out_inst;     // [ninst]; may be `inst`
+	float* out_bounds;                // [ninst][4] or null
+	uint8_t* flags;                   // [ninst] 1 = kept (context scratch), null when no compaction follows
+	uint32_t* status;                 // the caller's dev_status (already VGX_OK) or null
+};
+void vgx_launch_mesh_bounds(const float* pos, const vgx_mesh* meshes, uint64_t numMeshes, float* bounds, hipStream_t s);
+void vgx_launch_cache_cull(const VgxCullArgs& a, uint32_t* kept, uint64_t* numKept, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, hipStream_t s);
+
 #endif

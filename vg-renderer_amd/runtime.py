@@ -591,10 +591,19 @@ class MeshCache:
         self.bufs = bufs
         self.nv, self.ni, self.nm = int(sizes["num_vertices"]), int(sizes["num_indices"]), int(sizes["num_meshes"])
         _check(lib().vgx_cache_localize(ctx.handle, draws_dev.data_ptr(), ndraws, bufs.pos.data_ptr(), bufs.meshes.data_ptr(), self.nm, _stream_ptr()), "vgx_cache_localize")
+        self._ctx = ctx
+        self._bounds = None
 
     def desc(self):
         b = self.bufs
         return capi.CacheDesc(b.pos.data_ptr(), b.color.data_ptr(), b.idx.data_ptr(), b.meshes.data_ptr(), self.nm, self.nv, self.ni)
+
+    @property
+    def bounds(self):
+        """float32 [nm, 4] device tensor: every mesh's local-space box (vgx_mesh_bounds), computed at the first use."""
+        if self._bounds is None:
+            self._bounds = mesh_bounds(self._ctx, self.bufs.pos, self.bufs.meshes, self.nm)
+        return self._bounds
 
 
 def cache_submit(ctx, cache, instances_dev, ninst, bufs):
@@ -603,6 +612,50 @@ def cache_submit(ctx, cache, instances_dev, ninst, bufs):
     out = bufs.out_struct()
     _check(lib().vgx_cache_submit(ctx.handle, C.byref(d), instances_dev.data_ptr(), ninst, C.byref(out),
                                   bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_cache_submit")
+
+
+# ---- bounding boxes and view culling (vgx_mesh_bounds / vgx_cache_cull) ------------------------------------------------
+def mesh_bounds(ctx, pos, meshes, nm):
+    """pos: float32 device tensor [nv, 2]; meshes: uint8 device tensor of 32-byte vgx_mesh records. Returns a float32 [nm, 4] device
+    tensor (minx, miny, maxx, maxy per mesh). Asynchronous."""
+    import torch
+    out = torch.empty((max(int(nm), 1), 4), dtype=torch.float32, device=pos.device)[:nm]
+    _check(lib().vgx_mesh_bounds(ctx.handle, pos.data_ptr(), meshes.data_ptr(), nm, out.data_ptr(), _stream_ptr()), "vgx_mesh_bounds")
+    return out
+
+
+class CullResult:
+    """What vgx_cache_cull wrote, all on the device: inst (uint8 tensor of 40-byte records, same length and order as the input; the
+    input tensor itself when in_place), bounds (float32 [ninst, 4] or None), kept (int32 [ninst] holding uint32 indices, the first
+    num_kept are valid, or None), num_kept (int64 [1] or None), dev_status (int32 [1])."""
+
+
+def cache_cull(ctx, cache, bounds_dev, inst_dev, ninst, views_dev, inst_view_dev=None, in_place=False, want_bounds=True, want_kept=True, reuse=None):
+    """bounds_dev: the cache's per-mesh boxes (MeshCache.bounds); inst_dev: uint8 device tensor of 40-byte vgx_cache_instance records;
+    views_dev: float32 [nviews, 4] (x0, y0, x1, y1); inst_view_dev: int32 / uint32 [ninst] or None (view 0). Asynchronous: hand
+    result.inst to cache_submit with the same ninst. reuse: the CullResult of an earlier call for as many instances, written again
+    instead of allocating (a frame loop); it decides which outputs exist, so in_place / want_bounds / want_kept must be left alone."""
+    import torch
+    dev = views_dev.device
+    r = reuse
+    if r is not None and (in_place or not want_bounds or not want_kept):
+        raise ValueError("cache_cull: reuse= takes its outputs from the earlier result; do not combine it with in_place / want_*")
+    if r is None:
+        r = CullResult()
+        r.inst = inst_dev if in_place else torch.empty(max(int(ninst), 1) * 40, dtype=torch.uint8, device=dev)
+        r.bounds = torch.empty((max(int(ninst), 1), 4), dtype=torch.float32, device=dev) if want_bounds else None
+        r.kept = torch.empty(max(int(ninst), 1), dtype=torch.int32, device=dev) if want_kept else None
+        r.num_kept = torch.empty(1, dtype=torch.int64, device=dev) if want_kept else None
+        r.dev_status = torch.empty(1, dtype=torch.int32, device=dev)
+    d = cache.desc()
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+    out = capi.CullOut(r.inst.data_ptr(), ptr(r.bounds), ptr(r.kept), ptr(r.num_kept))
+    _check(lib().vgx_cache_cull(ctx.handle, C.byref(d), bounds_dev.data_ptr() if cache.nm else None, inst_dev.data_ptr() if ninst else None, ninst,
+                                views_dev.data_ptr(), int(views_dev.shape[0]), ptr(inst_view_dev), C.byref(out), r.dev_status.data_ptr(), _stream_ptr()),
+           "vgx_cache_cull")
+    return r
 
 
 # ---- concave fills (vgx_concave_move / vgx_concave_emit): libtess2 stays with the caller -----------------------------
