@@ -585,6 +585,57 @@ typedef struct vgx_cull_out {
 int vgx_cache_cull(vgx_ctx* ctx, const vgx_cache_desc* cache, const float* mesh_bounds, const vgx_cache_instance* inst, uint64_t ninst,
                    const float* views, uint32_t nviews, const uint32_t* inst_view, const vgx_cull_out* out, uint32_t* dev_status, void* stream);
 
+/* ---- hit testing (beyond the reference): vgx_mesh_bounds -> vgx_pick ----------------------------------------------------------
+ * Which drawing is under this point? The reference has no hit testing; its users rebuild their shapes on the CPU. Here a frame
+ * lives in device memory only, so the library that wrote it answers. `frame` is any mesh stream the library wrote with mesh-LOCAL
+ * indices: vgx_tessellate*, vgx_stroke, vgx_cache_submit, vgx_merge and vgx_text_quads without an armed assembly, and a cache
+ * (points in local space then). Streams written under vgx_set_assembly carry command-relative indices and are OUT OF SCOPE: the
+ * call cannot tell and would test wrong triangles. All pointers are DEVICE pointers. The mesh table must satisfy the ascending
+ * precondition of vgx_mesh_bounds (it is what the boxes are computed under).
+ *
+ * Triangles. Triangle t of mesh m is idx[first_index + 3t .. +3), for t < num_indices / 3.
+ *   - A trailing remainder of the index list (num_indices % 3) is ignored.
+ *   - A triangle with an index >= num_vertices is skipped, so nothing outside the mesh's own vertex range is ever read.
+ *   - With VGX_PICK_SKIP_TRANSPARENT in the query's flags, a triangle with at least one vertex whose colour has alpha 0 (bits 24-31
+ *     of the colour word) is skipped. That is the outer ring of an AA fringe, so a pick lands on the solid part only. An AAThin
+ *     stroke (VGX_MESH_STROKE_AA_THIN) is nothing but two such rings: it has NO solid triangle under this flag and is never hit.
+ * Point in triangle. Let the vertices be a, b, c and the point p, all binary32.
+ *   - First the closed box test in binary32 compares: px >= min(ax,bx,cx) && px <= max(ax,bx,cx) && py >= min(ay,by,cy) &&
+ *     py <= max(ay,by,cy). A NaN anywhere makes it false.
+ *   - Then in binary64 WITHOUT FMA, every difference taken after widening:
+ *       A  = (bx-ax)*(cy-ay) - (by-ay)*(cx-ax)
+ *       e0 = (bx-ax)*(py-ay) - (by-ay)*(px-ax)        e1, e2: the same for the edges b->c and c->a
+ *     A == 0 or NaN: no hit. A > 0: hit iff e0 >= 0 && e1 >= 0 && e2 >= 0. A < 0: hit iff all three are <= 0.
+ *   - Why binary64. The difference of two binary32 values whose exponents lie within 29 of each other is exact in binary64
+ *     (anything of screen magnitude). Where the two differences of a product have no more than 53 significant bits together -- 24 + 24
+ *     = 48 when the four values share a binade, as the corners of a tessellated triangle and a point near them do -- the product is
+ *     exact as well, and the sign of a rounded difference of two exact values is its exact sign. Then a point on a shared edge hits
+ *     both triangles, no point falls through a seam, and a vertex of a triangle with A != 0 hits it (for p = a: e0 is 0 - 0, e2 is
+ *     the difference of one product with itself written both ways round = 0, and e1 equals A as a real number). Outside that range the
+ *     expressions still round the same way everywhere under IEEE 754, so every implementation agrees bit for bit; only the
+ *     geometric guarantee is lost.
+ * Result. Among the meshes m < min(mesh_end, num_meshes), hits[q] takes the LARGEST m that has a hit triangle, and within it the
+ *   largest t. Painter's order: the last thing drawn is on top. draw and subpath_kind are copied from that mesh record (draw names
+ *   the draw, or the cache instance for a vgx_cache_submit frame). No hit: mesh = triangle = draw = subpath_kind = 0xFFFFFFFF.
+ *   mesh_end = 0xFFFFFFFF means all meshes; passing the previous hit's `mesh` walks a stack of overlapping drawings from the top down
+ *   (click-through). A maximum does not depend on the order of evaluation: results are identical on every run.
+ * mesh_bounds. What vgx_mesh_bounds gave for this stream ([num_meshes][4]), or NULL: then the call computes the boxes itself into
+ *   scratch of its own. A mesh whose box does not contain the point (closed, binary32 compares) is never opened. This changes no
+ *   result: the triangle test starts with the triangle's own box, and every indexed vertex lies inside the mesh box. For a mesh with
+ *   a NaN position, whether its OTHER triangles are found is unspecified, because its box is.
+ * Host return values. VGX_OK once the work is enqueued. VGX_E_INVALID_ARG for null or misaligned pointers (queries, hits, mesh_bounds
+ *   16-byte; pos 8-byte; color 4-byte; idx 2-byte; meshes 8-byte). VGX_E_RANGE for nqueries > VGX_PICK_MAX_QUERIES or num_meshes >=
+ *   2^32 - 1. VGX_E_HIP for a HIP failure. nqueries == 0 or num_meshes == 0 is valid; every hit is "none".
+ * Side effects. Exactly nqueries hit records are written and nothing else of the caller's. Asynchronous. Uses scratch of its own
+ *   (16 bytes per mesh, 32 with mesh_bounds == NULL), so a counted state survives: vgx_tessellate_count -> vgx_pick ->
+ *   vgx_tessellate_emit works. */
+#define VGX_PICK_MAX_QUERIES 256
+enum { VGX_PICK_SKIP_TRANSPARENT = 1u };
+typedef struct vgx_pick_query { float x, y; uint32_t mesh_end; uint32_t flags; } vgx_pick_query;          /* 16 bytes */
+typedef struct vgx_pick_hit   { uint32_t mesh, triangle, draw, subpath_kind; } vgx_pick_hit;              /* 16 bytes */
+int vgx_pick(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
+             const vgx_pick_query* queries, uint32_t nqueries, vgx_pick_hit* hits, void* stream);
+
 /* ---- concave fills with AA fringes -------------------------------------------------
  * strokerConcaveFillEndAA (src/stroker.cpp:868-1006) alternates libtess2 and the stroker's own loops:
  *   (1) tessTesselate(TESS_BOUNDARY_CONTOURS) of the contours added with strokerConcaveFillAddContour     [caller, CPU]

@@ -128,6 +128,14 @@ class CullOut(C.Structure):  # vgx_cull_out: device pointers, any but `inst` may
     _fields_ = [("inst", C.c_void_p), ("bounds", C.c_void_p), ("kept", C.c_void_p), ("num_kept", C.c_void_p)]
 
 
+pick_query_dtype = np.dtype([("x", "<f4"), ("y", "<f4"), ("mesh_end", "<u4"), ("flags", "<u4")])  # struct vgx_pick_query
+pick_hit_dtype = np.dtype([("mesh", "<u4"), ("triangle", "<u4"), ("draw", "<u4"), ("subpath_kind", "<u4")])  # struct vgx_pick_hit
+assert pick_query_dtype.itemsize == 16 and pick_hit_dtype.itemsize == 16
+PICK_MAX_QUERIES = 256
+PICK_SKIP_TRANSPARENT = 1
+PICK_NONE = 0xFFFFFFFF  # every word of a hit record that hit nothing; vgx_pick_query.mesh_end: all meshes
+
+
 class Assembly(C.Structure):
     _fields_ = [("drawcmds", C.c_void_p), ("cap_drawcmds", C.c_uint64), ("dev_num_drawcmds", C.c_void_p),
                 ("max_vb_vertices", C.c_uint32), ("flags", C.c_uint32), ("uv", C.c_void_p), ("uv_bytes", C.c_uint32),
@@ -214,6 +222,7 @@ VGX_SYMBOLS = {
     "vgx_mesh_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "vgx_cache_cull": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
                                  C.POINTER(CullOut), C.c_void_p, C.c_void_p]),
+    "vgx_pick": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vgx_last_hip_error": (C.c_int, [C.c_void_p]),
     "vgx_status_string": (C.c_char_p, [C.c_int]),
     "vgx_version": (C.c_uint32, []),

@@ -80,6 +80,8 @@ struct vgx_ctx
 	DevBuf cmdPrefix, cmdCnt, subFirst, leafOverflow, serialList, dinfo, poly, subs, mdesc, elemPrefix, elemPrefixS, mprep, mtab, partial, totals;
 	DevBuf textTiles;                    // vgx_text_quads: first run of every tile of quads (vgx_text.hip)
 	DevBuf cullFlags, cullPartial;       // vgx_cache_cull (vgx_bounds.hip): kept flag per instance, the compaction scan's slice sums. Its own: a counted state survives the call
+	DevBuf pickKeys, pickTris, pickCand, pickPrefix, pickTotals, pickPartial, pickBounds; // vgx_pick (vgx_pick.hip). Its own: a counted state survives the call
+	uint32_t optPickGrid;                // workgroups of k_pick_tris (VGX_PICK_GRID)
 	uint32_t optCullWaveMin;             // mesh ranges of at least this many boxes are united by the whole wave; >= 1, 2^32 - 1 = never = the default (VGX_CULL_WAVE_MIN)
 	// vgx_dash (vgx_dash.hip): per-draw patterns, per-list records, per-segment prefix sums (S and the overflow guard), per-range sums; the
 	// segment count of the last call in pinned memory (copied behind the call, read by the next call once its event has passed: a call
@@ -975,6 +977,10 @@ int vgx_create(int device, vgx_ctx** out_ctx)
 	// ranges of 1-3 meshes do not care (profiles/cache_cull_timing.json). VGX_CULL_WAVE_MIN=N > 0 turns the wave form on for ranges >= N
 	ctx->optCullWaveMin = 0xFFFFFFFFu;
 	if (const char* e = getenv("VGX_CULL_WAVE_MIN")) { const int v = atoi(e); ctx->optCullWaveMin = v <= 0 ? 0xFFFFFFFFu : (uint32_t)v; }
+	// k_pick_tris strides a fixed grid over the candidate triangles (their count stays on the device): four workgroups per CU of a
+	// 256-CU part; workgroups without a tile exit at once. VGX_PICK_GRID=N > 0 sets another (the tests force many tiles per workgroup)
+	ctx->optPickGrid = 1024;
+	if (const char* e = getenv("VGX_PICK_GRID")) { const int v = atoi(e); if (v > 0) { ctx->optPickGrid = (uint32_t)(v > 65536 ? 65536 : v); } }
 	ctx->optTileEmit = 1;
 	if (const char* e = getenv("VGX_TILE_EMIT")) { ctx->optTileEmit = atoi(e) != 0; }
 	ctx->optPsNoSmall = getenv("VGX_PS_NO_SMALL") ? 1 : 0; // testing knob: frame-sized path sets through the large-set launch sequence
@@ -1017,7 +1023,7 @@ int vgx_destroy(vgx_ctx* ctx)
 		return VGX_E_INVALID_ARG;
 	}
 	DeviceGuard guard(ctx);
-	DevBuf* bufs[] = { &ctx->cullFlags, &ctx->cullPartial, &ctx->mdesc2, &ctx->mprep2, &ctx->mtab2, &ctx->dfLists, &ctx->dfListDraw, &ctx->dfDashedBefore, &ctx->dfPieceSubs, &ctx->dfPieceDraw, &ctx->dfPieceSrc, &ctx->dfTotals, &ctx->dfNeed, &ctx->dashPat, &ctx->dashLists, &ctx->dashG, &ctx->dashGhi, &ctx->dashRange, &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
+	DevBuf* bufs[] = { &ctx->pickKeys, &ctx->pickTris, &ctx->pickCand, &ctx->pickPrefix, &ctx->pickTotals, &ctx->pickPartial, &ctx->pickBounds, &ctx->cullFlags, &ctx->cullPartial, &ctx->mdesc2, &ctx->mprep2, &ctx->mtab2, &ctx->dfLists, &ctx->dfListDraw, &ctx->dfDashedBefore, &ctx->dfPieceSubs, &ctx->dfPieceDraw, &ctx->dfPieceSrc, &ctx->dfTotals, &ctx->dfNeed, &ctx->dashPat, &ctx->dashLists, &ctx->dashG, &ctx->dashGhi, &ctx->dashRange, &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
 	for (DevBuf* b : bufs) {
 		if (b->p) { (void)hipFree(b->p); }
 	}
@@ -1046,7 +1052,7 @@ uint64_t vgx_scratch_bytes(const vgx_ctx* ctx)
 	if (!ctx) {
 		return 0;
 	}
-	return ctx->cullFlags.cap + ctx->cullPartial.cap + ctx->mdesc2.cap + ctx->mprep2.cap + ctx->mtab2.cap + ctx->dfLists.cap + ctx->dfListDraw.cap + ctx->dfDashedBefore.cap + ctx->dfPieceSubs.cap + ctx->dfPieceDraw.cap + ctx->dfPieceSrc.cap + ctx->dfTotals.cap + ctx->dfNeed.cap + ctx->dashPat.cap + ctx->dashLists.cap + ctx->dashG.cap + ctx->dashGhi.cap + ctx->dashRange.cap + ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
+	return ctx->pickKeys.cap + ctx->pickTris.cap + ctx->pickCand.cap + ctx->pickPrefix.cap + ctx->pickTotals.cap + ctx->pickPartial.cap + ctx->pickBounds.cap + ctx->cullFlags.cap + ctx->cullPartial.cap + ctx->mdesc2.cap + ctx->mprep2.cap + ctx->mtab2.cap + ctx->dfLists.cap + ctx->dfListDraw.cap + ctx->dfDashedBefore.cap + ctx->dfPieceSubs.cap + ctx->dfPieceDraw.cap + ctx->dfPieceSrc.cap + ctx->dfTotals.cap + ctx->dfNeed.cap + ctx->dashPat.cap + ctx->dashLists.cap + ctx->dashG.cap + ctx->dashGhi.cap + ctx->dashRange.cap + ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
 }
 
 // ---- path set ---------------------------------------------------------------------------------------
@@ -2733,6 +2739,44 @@ int vgx_cache_cull(vgx_ctx* ctx, const vgx_cache_desc* cache, const float* mesh_
 	a.views = views; a.nviews = nviews; a.wave_min = ctx->optCullWaveMin; a.inst_view = inst_view;
 	a.out_inst = out->inst; a.out_bounds = out->bounds; a.flags = compact ? (uint8_t*)ctx->cullFlags.p : nullptr; a.status = dev_status;
 	vgx_launch_cache_cull(a, out->kept, out->num_kept, ctx->cullPartial.p, s);
+	return launchStatus(ctx);
+}
+
+// ---- hit testing (vgx_pick.hip) ------------------------------------------------------------------------------------------
+// Scratch of its own, like the culling call: count -> vgx_pick -> emit still works.
+int vgx_pick(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, const vgx_pick_query* queries, uint32_t nqueries,
+             vgx_pick_hit* hits, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || !frame || (nqueries && (!queries || !hits))) { return VGX_E_INVALID_ARG; }
+	if (nqueries && frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)queries & 15u) || ((uintptr_t)hits & 15u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
+		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	if (nqueries > VGX_PICK_MAX_QUERIES || frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	if (!nqueries) { return VGX_OK; } // nothing to write
+	hipStream_t s = (hipStream_t)stream;
+	const uint64_t nm = frame->num_meshes;
+	int st;
+	if ((st = ensure(ctx, ctx->pickKeys, VGX_PICK_MAX_QUERIES * sizeof(uint64_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickTris, (nm + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickCand, (nm + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickPrefix, (nm + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickTotals, 2 * sizeof(uint64_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if (!mesh_bounds && nm) {
+		if ((st = ensure(ctx, ctx->pickBounds, nm * 4 * sizeof(float))) != VGX_OK) { return st; }
+		vgx_launch_mesh_bounds(frame->pos, frame->meshes, nm, (float*)ctx->pickBounds.p, s);
+		mesh_bounds = (const float*)ctx->pickBounds.p;
+	}
+	VgxPickArgs a;
+	memset(&a, 0, sizeof(a));
+	a.pos = frame->pos; a.color = frame->color; a.idx = frame->idx; a.meshes = frame->meshes; a.num_meshes = nm;
+	a.mesh_bounds = mesh_bounds; a.queries = queries; a.nqueries = nqueries; a.hits = hits;
+	a.keys = (uint64_t*)ctx->pickKeys.p; a.cand_tris = (uint32_t*)ctx->pickTris.p; a.cand_mesh = (uint32_t*)ctx->pickCand.p;
+	a.cand_prefix = (uint64_t*)ctx->pickPrefix.p; a.totals = (uint64_t*)ctx->pickTotals.p;
+	vgx_launch_pick(a, ctx->pickPartial.p, ctx->optPickGrid, s);
 	return launchStatus(ctx);
 }
 

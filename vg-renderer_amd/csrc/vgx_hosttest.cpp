@@ -485,3 +485,50 @@ int vgxt_cache_cull(uint64_t cache_meshes, const float* mesh_bounds, const vgx_c
 }
 
 }
+
+#include "vgx_pick.h"
+#include <stdlib.h>
+
+extern "C" {
+
+// vgx_pick on the host: the functions of vgx_pick.h in a plain sequential loop over queries, meshes and triangles, with the call's
+// contract (mesh_bounds may be NULL: the boxes are computed first, as the device call does). HOST pointers. Returns the status the
+// device call returns for these arguments.
+int vgxt_pick(const vgx_cache_desc* frame, const float* mesh_bounds, const vgx_pick_query* queries, uint32_t nqueries, vgx_pick_hit* hits)
+{
+	if (!frame || (nqueries && (!queries || !hits))) { return VGX_E_INVALID_ARG; }
+	if (nqueries > VGX_PICK_MAX_QUERIES || frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	const uint64_t nm = frame->num_meshes;
+	float* own = nullptr;
+	if (!mesh_bounds && nm) {
+		own = (float*)malloc(nm * 4 * sizeof(float));
+		if (!own) { return VGX_E_INTERNAL; }
+		vgxt_mesh_bounds(frame->pos, frame->meshes, nm, own);
+		mesh_bounds = own;
+	}
+	for (uint32_t q = 0; q < nqueries; ++q) {
+		const vgx_pick_query Q = queries[q];
+		uint64_t best = 0;
+		for (uint64_t m = 0; m < nm && m < (uint64_t)Q.mesh_end; ++m) {
+			const float* bx = mesh_bounds + 4 * m;
+			if (!vgx_pick_in_box(Q.x, Q.y, bx[0], bx[1], bx[2], bx[3])) { continue; }
+			const vgx_mesh me = frame->meshes[m];
+			const uint16_t* ip = frame->idx + me.first_index;
+			const float* pp = frame->pos + 2 * me.first_vertex;
+			const uint32_t* cp = frame->color + me.first_vertex;
+			for (uint32_t t = 0; t < me.num_indices / 3u; ++t) {
+				const uint32_t i0 = ip[3 * t], i1 = ip[3 * t + 1], i2 = ip[3 * t + 2];
+				if (!vgx_pick_tri_valid(i0, i1, i2, me.num_vertices)) { continue; }
+				if ((Q.flags & VGX_PICK_SKIP_TRANSPARENT) && vgx_pick_tri_transparent(cp[i0], cp[i1], cp[i2])) { continue; }
+				if (!vgx_pick_tri(v2(pp[2 * i0], pp[2 * i0 + 1]), v2(pp[2 * i1], pp[2 * i1 + 1]), v2(pp[2 * i2], pp[2 * i2 + 1]), Q.x, Q.y)) { continue; }
+				const uint64_t key = vgx_pick_key((uint32_t)m, t);
+				if (key > best) { best = key; }
+			}
+		}
+		hits[q] = vgx_pick_decode(best, frame->meshes);
+	}
+	free(own);
+	return VGX_OK;
+}
+
+}

@@ -410,4 +410,21 @@ struct VgxCullArgs
 void vgx_launch_mesh_bounds(const float* pos, const vgx_mesh* meshes, uint64_t numMeshes, float* bounds, hipStream_t s);
 void vgx_launch_cache_cull(const VgxCullArgs& a, uint32_t* kept, uint64_t* numKept, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, hipStream_t s);
 
+// hit testing (vgx_pick.hip)
+struct VgxPickArgs
+{
+	const float* pos; const uint32_t* color; const uint16_t* idx; const vgx_mesh* meshes; // the frame
+	uint64_t num_meshes;              // < 2^32 - 1
+	const float* mesh_bounds;         // [num_meshes][4], 16-byte aligned: the caller's, or the context's own
+	const vgx_pick_query* queries;
+	uint32_t nqueries;                // <= VGX_PICK_MAX_QUERIES
+	vgx_pick_hit* hits;
+	uint64_t* keys;                   // [VGX_PICK_MAX_QUERIES] (context scratch, as everything below)
+	uint32_t* cand_tris;              // [num_meshes] triangle count of a candidate, 0 for any other mesh
+	uint32_t* cand_mesh;              // [num_meshes] the candidates, dense and ascending
+	uint64_t* cand_prefix;            // [num_meshes + 1] exclusive prefix of the candidates' triangle counts, the total behind it
+	uint64_t* totals;                 // candidates, candidate triangles
+};
+void vgx_launch_pick(const VgxPickArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, uint32_t grid, hipStream_t s);
+
 #endif

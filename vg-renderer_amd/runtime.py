@@ -658,6 +658,20 @@ def cache_cull(ctx, cache, bounds_dev, inst_dev, ninst, views_dev, inst_view_dev
     return r
 
 
+# ---- hit testing (vgx_pick) ---------------------------------------------------------------------------------------------
+def pick(ctx, frame, queries_dev, nqueries, bounds_dev=None, hits_dev=None):
+    """frame: a capi.CacheDesc of device pointers, or anything with .desc() (a MeshCache); queries_dev: uint8 device tensor of 16-byte
+    vgx_pick_query records; bounds_dev: what mesh_bounds gave for the frame, or None (the call computes the boxes itself). Returns a
+    uint8 device tensor of nqueries 16-byte vgx_pick_hit records (hits_dev when given). Asynchronous."""
+    import torch
+    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
+    if hits_dev is None:
+        hits_dev = torch.empty(max(int(nqueries), 1) * 16, dtype=torch.uint8, device=queries_dev.device)
+    _check(lib().vgx_pick(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, queries_dev.data_ptr(), nqueries,
+                          hits_dev.data_ptr(), _stream_ptr()), "vgx_pick")
+    return hits_dev
+
+
 # ---- concave fills (vgx_concave_move / vgx_concave_emit): libtess2 stays with the caller -----------------------------
 def concave_move(ctx, contour_verts_dev, contours_dev, ncontours, fills_dev, nfills):
     """Inner fringe vertex of every boundary-contour vertex (what the reference writes back into the contour before the
