@@ -636,6 +636,74 @@ typedef struct vgx_pick_hit   { uint32_t mesh, triangle, draw, subpath_kind; } v
 int vgx_pick(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
              const vgx_pick_query* queries, uint32_t nqueries, vgx_pick_hit* hits, void* stream);
 
+/* ---- incremental update (beyond the reference): vgx_cache_submit -> vgx_cache_layout -> [vgx_pick -> edit -> vgx_cache_update]* ----
+ * Moving or recolouring an instance of a submitted frame changes nothing of the frame's structure: a cached mesh has a fixed size, so
+ * the instance keeps its vertex, index and mesh ranges; indices, mesh records, draw commands and UVs do not depend on the transform.
+ * Only its positions change, and the colours of its non-AA meshes, which take the instance's colour. vgx_cache_layout tells where
+ * every instance lives in the frame; vgx_cache_update rewrites the slices of a few listed instances and keeps the caller's
+ * vgx_mesh_bounds table current, so that pick -> edit -> update -> pick needs no pass over the whole frame. All pointers are DEVICE
+ * pointers unless marked HOST.
+ *
+ * vgx_cache_layout: slots[i] = the exclusive prefix sums of meshes, vertices and indices over instances 0 .. i-1, which are exactly
+ * the offsets vgx_cache_submit(cache, inst, ninst) writes instance i to (both run the same per-instance function), and the record's
+ * first_mesh; slots[ninst] = the totals, with cache_first_mesh = 0. An instance whose range [first_mesh, first_mesh + num_meshes) lies
+ * outside the cache contributes zero and sets dev_status (DEVICE uint32, may be NULL) to VGX_E_INVALID_ARG; else VGX_OK. Exactly
+ * ninst + 1 records are written. Asynchronous; capacities are not checked (no frame is written). vgx_set_assembly is ignored: the
+ * vertex streams of an assembled frame are in the same order, so first_mesh and first_vertex hold for it (first_index then names the
+ * position in the index stream, whose VALUES are command-relative). Uses scratch of its own, like vgx_cache_cull and vgx_pick:
+ * vgx_tessellate_count -> vgx_cache_layout / vgx_cache_update -> vgx_tessellate_emit works.
+ * Host return values: VGX_OK once the work is enqueued; VGX_E_INVALID_ARG for null or misaligned pointers (inst, slots 8-byte,
+ * dev_status 4-byte); VGX_E_RANGE for ninst >= 2^32; VGX_E_HIP.
+ *
+ * vgx_cache_update: `inst` is the instance array with the edited records (mtx, color), `slots` what vgx_cache_layout gave for the
+ * array the frame was submitted from. The effective list is dirty[0 .. min(ndirty, *dev_ndirty)); with dev_ndirty == NULL it is
+ * dirty[0 .. ndirty), so a list a kernel compacted needs no count on the host. The list may be in any order and may hold duplicates;
+ * the result is as if each index were listed once. For each listed d, in this order:
+ *   1. d >= ninst, or the range of inst[d] lies outside the cache: the entry is INVALID and is skipped.
+ *   2. inst[d].first_mesh != slots[d].cache_first_mesh, or inst[d].num_meshes != slots[d+1].first_mesh - slots[d].first_mesh, or the
+ *      range's vertex count in the cache != slots[d+1].first_vertex - slots[d].first_vertex: the entry is STALE and is skipped. The
+ *      structure changed, or the slots belong to another array: the caller must submit again.
+ *   3. slots[d+1].first_vertex > frame->num_vertices or slots[d+1].first_mesh > frame->num_meshes: INVALID, skipped.
+ *   4. Otherwise the slice is rewritten: for every vertex v of the range, frame->pos[slots[d].first_vertex + (v - first vertex of the
+ *      range)] = cache.pos[v] moved through the function vgx_cache_submit uses, (m0*x + m2*y) + m4, (m1*x + m3*y) + m5 in binary32
+ *      without FMA: the bytes a fresh submit of the edited array would write.
+ *   5. Every vertex colour of a mesh of kind VGX_MESH_FILL or VGX_MESH_STROKE is set to inst[d].color.
+ *   6. Colours of all other meshes are not written (they do not depend on the instance).
+ *   7. Indices, mesh records, draw commands and UVs are never touched.
+ *   8. Nothing outside the slices of valid, non-stale listed instances is written.
+ * dev_status (DEVICE uint32, may be NULL) does not depend on the order of the work: VGX_E_INVALID_ARG if any listed entry is invalid,
+ * otherwise VGX_E_STALE if any is stale, otherwise VGX_OK. Entries that pass are written in every case.
+ * frame->mesh_bounds, when given, is the table vgx_mesh_bounds computed for this frame: every frame mesh of an updated instance gets
+ * its exact min / max box over the new positions, with the bytes vgx_mesh_bounds would produce on the updated frame (the minimum of
+ * -0 and +0 is -0, the maximum +0, as the integer images order them); a 0-vertex mesh gets the empty box; every other entry is
+ * untouched. The result for a NaN position is unspecified, as in vgx_mesh_bounds.
+ * Culled frames. A frame written from records vgx_cache_cull zeroed (num_meshes = 0) updates like any other: a culled instance has an
+ * empty slice, and listing it writes nothing. An instance that ENTERS or LEAVES the view changes the structure (its num_meshes differs
+ * from what the slots say: VGX_E_STALE) and needs a new submit. The bounds / kept outputs of vgx_cache_cull are not refreshed here.
+ * Host return values: VGX_OK once the work is enqueued; VGX_E_INVALID_ARG for null or misaligned pointers (inst, slots, dev_ndirty
+ * 8-byte; frame->pos 8-byte; frame->mesh_bounds 16-byte; dirty, frame->color, dev_status 4-byte); VGX_E_RANGE for ninst or ndirty >=
+ * 2^32; VGX_E_HIP. ndirty == 0 is valid and writes nothing but VGX_OK to dev_status. Asynchronous; scratch of its own (16 bytes per
+ * listed entry), so a counted state survives. Two calls on one stream take effect in order. */
+typedef struct vgx_cache_slot {   /* where instance i lives in the frame vgx_cache_submit writes. 32 bytes */
+	uint64_t first_mesh;          /* first FRAME mesh of the instance */
+	uint64_t first_vertex;        /* into the frame's pos / color streams */
+	uint64_t first_index;         /* into the frame's idx stream */
+	uint64_t cache_first_mesh;    /* the record's vgx_cache_instance::first_mesh (0 in the closing entry) */
+} vgx_cache_slot;
+int vgx_cache_layout(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_instance* inst, uint64_t ninst,
+                     vgx_cache_slot* slots /* DEVICE [ninst + 1] */, uint32_t* dev_status, void* stream);
+
+typedef struct vgx_update_frame {
+	float*    pos;                /* DEVICE: the frame's streams as vgx_cache_submit wrote them */
+	uint32_t* color;
+	uint64_t  num_vertices, num_meshes;   /* HOST: the frame's totals; nothing is written at or beyond them */
+	float*    mesh_bounds;        /* DEVICE [num_meshes][4], may be NULL: vgx_mesh_bounds' table for this frame, refreshed */
+} vgx_update_frame;
+int vgx_cache_update(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_instance* inst, uint64_t ninst,
+                     const vgx_cache_slot* slots, const uint32_t* dirty /* DEVICE [ndirty] */, uint64_t ndirty,
+                     const uint64_t* dev_ndirty /* DEVICE, may be NULL */, const vgx_update_frame* frame,
+                     uint32_t* dev_status, void* stream);
+
 /* ---- concave fills with AA fringes -------------------------------------------------
  * strokerConcaveFillEndAA (src/stroker.cpp:868-1006) alternates libtess2 and the stroker's own loops:
  *   (1) tessTesselate(TESS_BOUNDARY_CONTOURS) of the contours added with strokerConcaveFillAddContour     [caller, CPU]

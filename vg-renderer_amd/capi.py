@@ -136,6 +136,14 @@ PICK_SKIP_TRANSPARENT = 1
 PICK_NONE = 0xFFFFFFFF  # every word of a hit record that hit nothing; vgx_pick_query.mesh_end: all meshes
 
 
+cache_slot_dtype = np.dtype([("first_mesh", "<u8"), ("first_vertex", "<u8"), ("first_index", "<u8"), ("cache_first_mesh", "<u8")])  # struct vgx_cache_slot
+assert cache_slot_dtype.itemsize == 32
+
+
+class UpdateFrame(C.Structure):  # vgx_update_frame: device pointers (mesh_bounds may be None) and the frame's totals
+    _fields_ = [("pos", C.c_void_p), ("color", C.c_void_p), ("num_vertices", C.c_uint64), ("num_meshes", C.c_uint64), ("mesh_bounds", C.c_void_p)]
+
+
 class Assembly(C.Structure):
     _fields_ = [("drawcmds", C.c_void_p), ("cap_drawcmds", C.c_uint64), ("dev_num_drawcmds", C.c_void_p),
                 ("max_vb_vertices", C.c_uint32), ("flags", C.c_uint32), ("uv", C.c_void_p), ("uv_bytes", C.c_uint32),
@@ -223,6 +231,9 @@ VGX_SYMBOLS = {
     "vgx_cache_cull": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
                                  C.POINTER(CullOut), C.c_void_p, C.c_void_p]),
     "vgx_pick": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vgx_cache_layout": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_cache_update": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                   C.POINTER(UpdateFrame), C.c_void_p, C.c_void_p]),
     "vgx_last_hip_error": (C.c_int, [C.c_void_p]),
     "vgx_status_string": (C.c_char_p, [C.c_int]),
     "vgx_version": (C.c_uint32, []),

@@ -17,6 +17,7 @@
 #include "vgx_tile.h"
 #include "vgx_mscan.h"
 #include "vgx_dash.h"
+#include "vgx_update.h"
 #include <vector>
 #include <atomic>
 #include <unordered_map>
@@ -81,6 +82,7 @@ struct vgx_ctx
 	DevBuf textTiles;                    // vgx_text_quads: first run of every tile of quads (vgx_text.hip)
 	DevBuf cullFlags, cullPartial;       // vgx_cache_cull (vgx_bounds.hip): kept flag per instance, the compaction scan's slice sums. Its own: a counted state survives the call
 	DevBuf pickKeys, pickTris, pickCand, pickPrefix, pickTotals, pickPartial, pickBounds; // vgx_pick (vgx_pick.hip). Its own: a counted state survives the call
+	DevBuf updPrefix, updPartial;        // vgx_cache_layout / vgx_cache_update (vgx_update.hip): the listed entries' prefix sums + the flag word, slice sums. Their own: a counted state survives the calls
 	uint32_t optPickGrid;                // workgroups of k_pick_tris (VGX_PICK_GRID)
 	uint32_t optCullWaveMin;             // mesh ranges of at least this many boxes are united by the whole wave; >= 1, 2^32 - 1 = never = the default (VGX_CULL_WAVE_MIN)
 	// vgx_dash (vgx_dash.hip): per-draw patterns, per-list records, per-segment prefix sums (S and the overflow guard), per-range sums; the
@@ -306,16 +308,13 @@ struct OpCacheInst // shape cache: vertices / indices / meshes of every instance
 	VgxTotals* totals;
 	VgxCaps caps;
 	__device__ uint64_t size() const { return ninst; }
-	__device__ uint64_t cv(uint64_t k) const { return k < cache.num_meshes ? cache.meshes[k].first_vertex : cache.num_vertices; }
-	__device__ uint64_t ci(uint64_t k) const { return k < cache.num_meshes ? cache.meshes[k].first_index : cache.num_indices; }
 	__device__ Sum3 load(uint64_t i) const
 	{
 		Sum3 r = sum3_zero();
+		VgxRangeCounts n; // the per-instance rule vgx_cache_layout shares (vgx_update.h)
 		const vgx_cache_instance in = inst[i];
-		if (in.first_mesh > cache.num_meshes || (uint64_t)in.num_meshes > cache.num_meshes - in.first_mesh) { set_status(totals, VGX_E_INVALID_ARG); return r; }
-		r.a = in.num_meshes;
-		r.b = cv(in.first_mesh + in.num_meshes) - cv(in.first_mesh);
-		r.c = ci(in.first_mesh + in.num_meshes) - ci(in.first_mesh);
+		if (!vgx_cache_range_counts(cache, in, &n)) { set_status(totals, VGX_E_INVALID_ARG); return r; }
+		r.a = n.meshes; r.b = n.vertices; r.c = n.indices;
 		return r;
 	}
 	__device__ void store(uint64_t i, Sum3 e) const { meshPrefix[i] = e.a; vertPrefix[i] = e.b; idxPrefix[i] = e.c; }
@@ -1023,7 +1022,7 @@ int vgx_destroy(vgx_ctx* ctx)
 		return VGX_E_INVALID_ARG;
 	}
 	DeviceGuard guard(ctx);
-	DevBuf* bufs[] = { &ctx->pickKeys, &ctx->pickTris, &ctx->pickCand, &ctx->pickPrefix, &ctx->pickTotals, &ctx->pickPartial, &ctx->pickBounds, &ctx->cullFlags, &ctx->cullPartial, &ctx->mdesc2, &ctx->mprep2, &ctx->mtab2, &ctx->dfLists, &ctx->dfListDraw, &ctx->dfDashedBefore, &ctx->dfPieceSubs, &ctx->dfPieceDraw, &ctx->dfPieceSrc, &ctx->dfTotals, &ctx->dfNeed, &ctx->dashPat, &ctx->dashLists, &ctx->dashG, &ctx->dashGhi, &ctx->dashRange, &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
+	DevBuf* bufs[] = { &ctx->updPrefix, &ctx->updPartial, &ctx->pickKeys, &ctx->pickTris, &ctx->pickCand, &ctx->pickPrefix, &ctx->pickTotals, &ctx->pickPartial, &ctx->pickBounds, &ctx->cullFlags, &ctx->cullPartial, &ctx->mdesc2, &ctx->mprep2, &ctx->mtab2, &ctx->dfLists, &ctx->dfListDraw, &ctx->dfDashedBefore, &ctx->dfPieceSubs, &ctx->dfPieceDraw, &ctx->dfPieceSrc, &ctx->dfTotals, &ctx->dfNeed, &ctx->dashPat, &ctx->dashLists, &ctx->dashG, &ctx->dashGhi, &ctx->dashRange, &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
 	for (DevBuf* b : bufs) {
 		if (b->p) { (void)hipFree(b->p); }
 	}
@@ -1052,7 +1051,7 @@ uint64_t vgx_scratch_bytes(const vgx_ctx* ctx)
 	if (!ctx) {
 		return 0;
 	}
-	return ctx->pickKeys.cap + ctx->pickTris.cap + ctx->pickCand.cap + ctx->pickPrefix.cap + ctx->pickTotals.cap + ctx->pickPartial.cap + ctx->pickBounds.cap + ctx->cullFlags.cap + ctx->cullPartial.cap + ctx->mdesc2.cap + ctx->mprep2.cap + ctx->mtab2.cap + ctx->dfLists.cap + ctx->dfListDraw.cap + ctx->dfDashedBefore.cap + ctx->dfPieceSubs.cap + ctx->dfPieceDraw.cap + ctx->dfPieceSrc.cap + ctx->dfTotals.cap + ctx->dfNeed.cap + ctx->dashPat.cap + ctx->dashLists.cap + ctx->dashG.cap + ctx->dashGhi.cap + ctx->dashRange.cap + ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
+	return ctx->updPrefix.cap + ctx->updPartial.cap + ctx->pickKeys.cap + ctx->pickTris.cap + ctx->pickCand.cap + ctx->pickPrefix.cap + ctx->pickTotals.cap + ctx->pickPartial.cap + ctx->pickBounds.cap + ctx->cullFlags.cap + ctx->cullPartial.cap + ctx->mdesc2.cap + ctx->mprep2.cap + ctx->mtab2.cap + ctx->dfLists.cap + ctx->dfListDraw.cap + ctx->dfDashedBefore.cap + ctx->dfPieceSubs.cap + ctx->dfPieceDraw.cap + ctx->dfPieceSrc.cap + ctx->dfTotals.cap + ctx->dfNeed.cap + ctx->dashPat.cap + ctx->dashLists.cap + ctx->dashG.cap + ctx->dashGhi.cap + ctx->dashRange.cap + ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
 }
 
 // ---- path set ---------------------------------------------------------------------------------------
@@ -2777,6 +2776,53 @@ int vgx_pick(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds
 	a.keys = (uint64_t*)ctx->pickKeys.p; a.cand_tris = (uint32_t*)ctx->pickTris.p; a.cand_mesh = (uint32_t*)ctx->pickCand.p;
 	a.cand_prefix = (uint64_t*)ctx->pickPrefix.p; a.totals = (uint64_t*)ctx->pickTotals.p;
 	vgx_launch_pick(a, ctx->pickPartial.p, ctx->optPickGrid, s);
+	return launchStatus(ctx);
+}
+
+// ---- incremental update of a submitted frame (vgx_update.hip) -------------------------------------------------------------
+// Scratch of their own, like the culling and picking calls: count -> vgx_cache_layout / vgx_cache_update -> emit still works.
+int vgx_cache_layout(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_instance* inst, uint64_t ninst, vgx_cache_slot* slots,
+                     uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || !cache || !slots || (ninst && !inst) || (cache->num_meshes && !cache->meshes)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)inst & 7u) || ((uintptr_t)slots & 7u) || ((uintptr_t)cache->meshes & 7u) || ((uintptr_t)dev_status & 3u)) { return VGX_E_INVALID_ARG; }
+	if (ninst > 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	hipStream_t s = (hipStream_t)stream;
+	int st;
+	if ((st = ensure(ctx, ctx->updPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if (dev_status) { noteHip(ctx, hipMemsetAsync(dev_status, 0, sizeof(uint32_t), s)); } // VGX_OK
+	vgx_launch_cache_layout(*cache, inst, ninst, slots, dev_status, ctx->updPartial.p, s);
+	return launchStatus(ctx);
+}
+
+int vgx_cache_update(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_instance* inst, uint64_t ninst, const vgx_cache_slot* slots,
+                     const uint32_t* dirty, uint64_t ndirty, const uint64_t* dev_ndirty, const vgx_update_frame* frame, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || !cache || !frame || (ndirty && (!dirty || !slots || !frame->pos || !frame->color)) || (ndirty && ninst && !inst)) { return VGX_E_INVALID_ARG; }
+	if (ndirty && cache->num_meshes && (!cache->pos || !cache->meshes)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)inst & 7u) || ((uintptr_t)slots & 7u) || ((uintptr_t)dirty & 3u) || ((uintptr_t)dev_ndirty & 7u) || ((uintptr_t)frame->pos & 7u)
+		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->mesh_bounds & 15u) || ((uintptr_t)dev_status & 3u) || ((uintptr_t)cache->pos & 7u)
+		|| ((uintptr_t)cache->meshes & 7u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	if (ninst > 0xFFFFFFFFull || ndirty > 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	hipStream_t s = (hipStream_t)stream;
+	int st;
+	// [flag word, padded to 16 bytes][vertex prefix: ndirty + 1][mesh prefix: ndirty + 1]
+	if ((st = ensure(ctx, ctx->updPrefix, 16 + 2 * (ndirty + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->updPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->updPrefix.p, 0, 16, s));
+	VgxUpdateArgs a;
+	memset(&a, 0, sizeof(a));
+	a.cache = *cache; a.inst = inst; a.ninst = ninst; a.slots = slots; a.dirty = dirty; a.ndirty = ndirty; a.dev_ndirty = dev_ndirty;
+	a.pos = frame->pos; a.color = frame->color; a.frame_vertices = frame->num_vertices; a.frame_meshes = frame->num_meshes;
+	a.mesh_bounds = frame->mesh_bounds;
+	a.flags = (uint32_t*)ctx->updPrefix.p;
+	a.vert_prefix = (uint64_t*)((char*)ctx->updPrefix.p + 16); a.mesh_prefix = a.vert_prefix + (ndirty + 1);
+	a.status = dev_status;
+	vgx_launch_cache_update(a, ctx->updPartial.p, s);
 	return launchStatus(ctx);
 }
 

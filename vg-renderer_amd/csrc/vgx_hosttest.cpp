@@ -532,3 +532,76 @@ int vgxt_pick(const vgx_cache_desc* frame, const float* mesh_bounds, const vgx_p
 }
 
 }
+
+#include "vgx_update.h"
+
+extern "C" {
+
+// vgx_cache_layout on the host: the per-instance function of vgx_update.h summed instance after instance. HOST pointers. Returns the
+// status the device call leaves in dev_status.
+int vgxt_cache_layout(const vgx_cache_desc* cache, const vgx_cache_instance* inst, uint64_t ninst, vgx_cache_slot* slots)
+{
+	int status = VGX_OK;
+	vgx_cache_slot s;
+	s.first_mesh = 0; s.first_vertex = 0; s.first_index = 0; s.cache_first_mesh = 0;
+	for (uint64_t i = 0; i < ninst; ++i) {
+		VgxRangeCounts n = { 0, 0, 0 };
+		if (!vgx_cache_range_counts(*cache, inst[i], &n)) { status = VGX_E_INVALID_ARG; }
+		s.cache_first_mesh = inst[i].first_mesh;
+		slots[i] = s;
+		s.first_mesh += n.meshes; s.first_vertex += n.vertices; s.first_index += n.indices;
+	}
+	s.cache_first_mesh = 0;
+	slots[ninst] = s;
+	return status;
+}
+
+// vgx_cache_update on the host: the listed entries one after the other in the order given (duplicates included), each through the
+// functions the kernels of vgx_update.hip call. HOST pointers, `ndirty_limit` included (NULL: the whole list). Returns the status the
+// device call leaves in dev_status.
+int vgxt_cache_update(const vgx_cache_desc* cache, const vgx_cache_instance* inst, uint64_t ninst, const vgx_cache_slot* slots,
+                      const uint32_t* dirty, uint64_t ndirty, const uint64_t* ndirty_limit, const vgx_update_frame* frame)
+{
+	uint32_t flags = 0;
+	const uint64_t nlist = (ndirty_limit && *ndirty_limit < ndirty) ? *ndirty_limit : ndirty;
+	for (uint64_t j = 0; j < nlist; ++j) {
+		const uint64_t d = dirty[j];
+		VgxRangeCounts n;
+		const uint32_t bad = vgx_update_classify(*cache, inst, ninst, slots, d, frame->num_vertices, frame->num_meshes, &n);
+		flags |= bad;
+		if (bad) { continue; }
+		const vgx_cache_instance in = inst[d];
+		const vgx_cache_slot s0 = slots[d];
+		const uint64_t rangeFirst = vgx_cache_first_vertex(*cache, in.first_mesh);
+		for (uint64_t v = 0; v < n.vertices; ++v) { // k_update_pos
+			const float* c = cache->pos + 2 * (rangeFirst + v);
+			const V2 r = v2xform(v2(c[0], c[1]), in.mtx);
+			frame->pos[2 * (s0.first_vertex + v)] = r.x; frame->pos[2 * (s0.first_vertex + v) + 1] = r.y;
+		}
+		for (uint64_t k = 0; k < n.meshes; ++k) { // k_update_meshes
+			const vgx_mesh src = cache->meshes[in.first_mesh + k];
+			uint64_t off;
+			const uint32_t nv = vgx_update_mesh_span(src, rangeFirst, n.vertices, &off);
+			if (vgx_mesh_takes_instance_colour(src.subpath_kind)) {
+				for (uint32_t v = 0; v < nv; ++v) { frame->color[s0.first_vertex + off + v] = in.color; }
+			}
+			if (frame->mesh_bounds) {
+				uint32_t lox = VGX_ORD_POS_INF, loy = VGX_ORD_POS_INF, hix = VGX_ORD_NEG_INF, hiy = VGX_ORD_NEG_INF;
+				for (uint32_t v = 0; v < nv; ++v) {
+					const float* c = cache->pos + 2 * (rangeFirst + off + v);
+					const V2 r = v2xform(v2(c[0], c[1]), in.mtx);
+					const uint32_t x = vgx_ord_from_float(r.x), y = vgx_ord_from_float(r.y);
+					if (x < lox) { lox = x; }
+					if (y < loy) { loy = y; }
+					if (x > hix) { hix = x; }
+					if (y > hiy) { hiy = y; }
+				}
+				float* b = frame->mesh_bounds + 4 * (s0.first_mesh + k);
+				b[0] = vgx_float_from_ord(lox); b[1] = vgx_float_from_ord(loy); b[2] = vgx_float_from_ord(hix); b[3] = vgx_float_from_ord(hiy);
+			}
+		}
+	}
+	return vgx_update_status(flags);
+}
+
+}

@@ -427,4 +427,26 @@ struct VgxPickArgs
 };
 void vgx_launch_pick(const VgxPickArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, uint32_t grid, hipStream_t s);
 
+// incremental update of a submitted frame (vgx_update.hip)
+struct VgxUpdateArgs
+{
+	vgx_cache_desc cache;
+	const vgx_cache_instance* inst;   // the edited array
+	uint64_t ninst;
+	const vgx_cache_slot* slots;      // [ninst + 1]
+	const uint32_t* dirty;            // [ndirty]
+	uint64_t ndirty;
+	const uint64_t* dev_ndirty;       // or null: the list is dirty[0 .. min(ndirty, *dev_ndirty))
+	float* pos; uint32_t* color;      // the frame
+	uint64_t frame_vertices, frame_meshes;
+	float* mesh_bounds;               // [frame_meshes][4] or null
+	uint64_t* vert_prefix;            // [ndirty + 1] exclusive scans over the listed entries (context scratch, as the next two)
+	uint64_t* mesh_prefix;            // [ndirty + 1]
+	uint32_t* flags;                  // one word, zeroed: VGX_UPD_* of every listed entry, ORed
+	uint32_t* status;                 // the caller's dev_status or null
+};
+void vgx_launch_cache_layout(const vgx_cache_desc& cache, const vgx_cache_instance* inst, uint64_t ninst, vgx_cache_slot* slots, uint32_t* status,
+                             void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, hipStream_t s);
+void vgx_launch_cache_update(const VgxUpdateArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, hipStream_t s);
+
 #endif

@@ -672,6 +672,40 @@ def pick(ctx, frame, queries_dev, nqueries, bounds_dev=None, hits_dev=None):
     return hits_dev
 
 
+# ---- incremental update (vgx_cache_layout / vgx_cache_update) ------------------------------------------------------------
+def cache_layout(ctx, cache, inst_dev, ninst, slots_dev=None):
+    """Where every instance of `inst_dev` (uint8 device tensor of 40-byte vgx_cache_instance records) lives in the frame cache_submit
+    writes for it. Returns (slots, dev_status): a uint8 device tensor of ninst + 1 32-byte vgx_cache_slot records (slots_dev when
+    given) and an int32 [1] device tensor. Asynchronous."""
+    import torch
+    dev = cache.bufs.pos.device
+    if slots_dev is None:
+        slots_dev = torch.empty((int(ninst) + 1) * 32, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    d = cache.desc()
+    _check(lib().vgx_cache_layout(ctx.handle, C.byref(d), inst_dev.data_ptr() if ninst else None, ninst, slots_dev.data_ptr(), status.data_ptr(),
+                                  _stream_ptr()), "vgx_cache_layout")
+    return slots_dev, status
+
+
+def cache_update(ctx, cache, inst_dev, ninst, slots_dev, dirty_dev, ndirty, pos, color, num_vertices, num_meshes, mesh_bounds=None,
+                 dev_ndirty=None, dev_status=None):
+    """Rewrites the slices of the listed instances in a frame cache_submit wrote. inst_dev: the EDITED instance array; slots_dev: what
+    cache_layout gave for the submitted one; dirty_dev: int32 / uint32 device tensor of instance indices, the first ndirty (or
+    min(ndirty, dev_ndirty[0]), dev_ndirty an int64 [1] device tensor) are used; pos / color: the frame's streams (MeshBuffers.pos /
+    .color); mesh_bounds: the float32 [num_meshes, 4] table mesh_bounds() gave for the frame, refreshed in place, or None. Returns
+    dev_status (int32 [1] device tensor: VGX_OK, VGX_E_INVALID_ARG or VGX_E_STALE). Asynchronous."""
+    import torch
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=pos.device)
+    d = cache.desc()
+    fr = capi.UpdateFrame(pos.data_ptr(), color.data_ptr(), int(num_vertices), int(num_meshes), mesh_bounds.data_ptr() if mesh_bounds is not None else None)
+    _check(lib().vgx_cache_update(ctx.handle, C.byref(d), inst_dev.data_ptr() if ninst else None, ninst, slots_dev.data_ptr(),
+                                  dirty_dev.data_ptr() if ndirty else None, ndirty, dev_ndirty.data_ptr() if dev_ndirty is not None else None,
+                                  C.byref(fr), dev_status.data_ptr(), _stream_ptr()), "vgx_cache_update")
+    return dev_status
+
+
 # ---- concave fills (vgx_concave_move / vgx_concave_emit): libtess2 stays with the caller -----------------------------
 def concave_move(ctx, contour_verts_dev, contours_dev, ncontours, fills_dev, nfills):
     """Inner fringe vertex of every boundary-contour vertex (what the reference writes back into the contour before the
