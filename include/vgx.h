@@ -500,6 +500,10 @@ int vgx_set_assembly(vgx_ctx* ctx, const vgx_assembly* asm_);
  * src/vg.cpp:5808-5841: positions times the inverse of the state transform at record time) and a later submission
  * only transforms them with the current state transform and appends positions, colours and indices to the frame
  * (submitCachedMesh, vg.cpp:6137-6166). All pointers below are DEVICE pointers. */
+/* vgx_cache_submit requires PACKED streams in mesh order, which is what vgx_tessellate[_emit] writes: meshes[0] starts at vertex 0 /
+ * index 0 and meshes[k + 1].first_vertex == meshes[k].first_vertex + meshes[k].num_vertices (first_index likewise), up to num_vertices /
+ * num_indices. It copies an instance's mesh range as ONE block of each stream and sizes it from the first_vertex / first_index of the
+ * range's ends. The other readers of this struct (vgx_merge's sequences, vgx_pick, vgx_mesh_bounds) go mesh by mesh. */
 typedef struct vgx_cache_desc {   /* CommandListCache::m_Meshes as four streams: what vgx_tessellate[_emit] wrote */
 	const float* pos;             /* [num_vertices][2], local space (after vgx_cache_localize) */
 	const uint32_t* color;        /* [num_vertices] */
@@ -751,7 +755,9 @@ int vgx_concave_emit(vgx_ctx* ctx, const float* contour_verts, uint64_t num_cont
  * first_index = the merged offsets, draw = the frame draw). Honours vgx_set_assembly like vgx_tessellate does (`draws` / ndraws:
  * the frame's draw records, DEVICE, only read for VGX_ASM_SPLIT_STATE; may be NULL otherwise). All pointers are DEVICE pointers;
  * the num_* members of `a` / `b` are host values. Asynchronous (capacities checked on the device, totals in dev_sizes, status in
- * dev_status); a sequence that is not sorted by draw sets VGX_E_INVALID_ARG. */
+ * dev_status); a sequence that is not sorted by draw sets VGX_E_INVALID_ARG.
+ * `b` may have HOLES: its meshes are read one by one through first_vertex / first_index, so vertices and indices that no mesh of `b`
+ * owns may lie between them (vgx_text_quads writes runs at caller-chosen places); they are not copied. The output is packed. */
 int vgx_merge(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, const uint32_t* b_draw, const vgx_draw* draws, uint64_t ndraws,
               const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
 /* The same with per-vertex UVs for the meshes of `b` (user meshes with texture coordinates): b_uv (DEVICE, [b->num_vertices] x the
