@@ -253,7 +253,8 @@ int vgx_destroy(vgx_ctx* ctx);
 int vgx_last_hip_error(const vgx_ctx* ctx);
 const char* vgx_status_string(int status);
 uint32_t vgx_version(void);
-/* Bytes of device scratch currently held by the context (polyline staging, tables, scan temp). */
+/* Bytes of device scratch currently held by the context: every buffer it has grown (polyline staging, tables, scan temp).
+   Path-set blobs waiting to be recycled are not scratch and not counted. */
 uint64_t vgx_scratch_bytes(const vgx_ctx* ctx);
 
 /* ---- path definitions --------------------------------------------------------------------- */

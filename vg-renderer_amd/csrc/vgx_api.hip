@@ -18,7 +18,9 @@
 #include "vgx_mscan.h"
 #include "vgx_dash.h"
 #include "vgx_update.h"
+#include "vgx_scratch.h"
 #include <vector>
+#include <algorithm>
 #include <atomic>
 #include <unordered_map>
 #include <string.h>
@@ -62,60 +64,88 @@ struct vgx_pathset
 
 #define VGX_PS_POOL 8
 #define VGX_PS_POOL_MAX ((size_t)8 << 20)
-struct DevBuf
+
+// A small pinned host block that follows a device value without the host ever waiting for it: a call pushes a copy and an event
+// behind its work, a later call reads the block only once the event says the copy has landed (else it goes without)
+template<class T> struct HostMirror
 {
-	void* p;
-	size_t cap;
+	T* host; // [n]
+	uint32_t n;
+	hipEvent_t ev;
+	bool pending;
+	int create(vgx_ctx* ctx, uint32_t count); // at first use (zeroed); no-op afterwards
+	void push(vgx_ctx* ctx, const void* dev, hipStream_t s); // copy of the n device elements + event record
+	bool landed(); // true once per push, when its copy has arrived
+	void release();
 };
+
+struct VgxGatherWire { vgx_rank_sizes z; uint64_t chunk; }; // vgx_gather_sizes: what every rank tells the others
 
 struct vgx_ctx
 {
 	int device;
 	int lastHipError;
 	int pendingHipError; // first failure of an asynchronous helper call (memset) inside the current entry point
-	// grow-only device scratch
-	DevBuf asmJump0, asmJump1, asmStart, meshBase; // draw-command assembly scratch (only when armed)
+	// grow-only device scratch (vgx_scratch.h). A new buffer is declared Buf<T> and grown with ensure(ctx, buf, items): that is all --
+	// it joins `scratch`, which vgx_destroy frees and vgx_scratch_bytes sums. A buffer seen under several types stays a DevBuf, its
+	// views named at the declaration
+	DevBufList scratch;
+	Buf<uint32_t> asmJump0, asmJump1, asmStart, meshBase; // draw-command assembly scratch (only when armed)
 	vgx_assembly asmCfg;
 	bool asmArmed;
-	DevBuf subPrefix; // exclusive scan of the draws' static sub-path counts
-	DevBuf cmdPrefix, cmdCnt, subFirst, leafOverflow, serialList, dinfo, poly, subs, mdesc, elemPrefix, elemPrefixS, mprep, mtab, partial, totals;
-	DevBuf textTiles;                    // vgx_text_quads: first run of every tile of quads (vgx_text.hip)
-	DevBuf cullFlags, cullPartial;       // vgx_cache_cull (vgx_bounds.hip): kept flag per instance, the compaction scan's slice sums. Its own: a counted state survives the call
-	DevBuf pickKeys, pickTris, pickCand, pickPrefix, pickTotals, pickPartial, pickBounds; // vgx_pick (vgx_pick.hip). Its own: a counted state survives the call
-	DevBuf updPrefix, updPartial;        // vgx_cache_layout / vgx_cache_update (vgx_update.hip): the listed entries' prefix sums + the flag word, slice sums. Their own: a counted state survives the calls
+	Buf<uint64_t> subPrefix; // exclusive scan of the draws' static sub-path counts
+	DevBuf cmdPrefix;                    // views: uint64_t[ndraws + 1] command prefix (vgx_partition: the weight prefix), 3 x uint64_t[ninst + 1] (vgx_cache_submit), uint32_t order (vgx_merge)
+	DevBuf poly;                         // views: float[2 x vertices] / float2 polyline heap, behind it the pieces of vgx_tessellate_dashed
+	DevBuf partial;                      // views: the slice sums of whichever scan runs (Sum3[VGX_SCAN_BLOCKS] sizes it)
+	Buf<uint32_t> cmdCnt, serialList;
+	Buf<VgxSubRec> subFirst;
+	Buf<float> leafOverflow;
+	Buf<vgx_draw_info> dinfo;
+	Buf<vgx_subpath> subs;
+	Buf<VgxMeshDesc> mdesc;
+	Buf<uint64_t> elemPrefix, elemPrefixS;
+	Buf<VgxMeshPrep> mprep;
+	Buf<vgx_mesh> mtab;
+	Buf<VgxTotals> totals;
+	Buf<uint32_t> textTiles;             // vgx_text_quads: first run of every tile of quads (vgx_text.hip)
+	Buf<uint8_t> cullFlags; DevBuf cullPartial; // vgx_cache_cull (vgx_bounds.hip): kept flag per instance, the compaction scan's slice sums (views: as `partial`). Its own: a counted state survives the call
+	Buf<uint64_t> pickKeys, pickPrefix, pickTotals; Buf<uint32_t> pickTris, pickCand; Buf<float> pickBounds; DevBuf pickPartial; // vgx_pick (vgx_pick.hip); pickPartial: slice sums (views: as `partial`). Its own: a counted state survives the call
+	DevBuf updPrefix, updPartial;        // vgx_cache_layout / vgx_cache_update (vgx_update.hip); views: updPrefix = uint32_t flag word in 16 bytes, then 2 x uint64_t[ndirty + 1] prefix sums of the listed entries; updPartial = slice sums, as `partial`. Their own: a counted state survives the calls
 	uint32_t optPickGrid;                // workgroups of k_pick_tris (VGX_PICK_GRID)
 	uint32_t optCullWaveMin;             // mesh ranges of at least this many boxes are united by the whole wave; >= 1, 2^32 - 1 = never = the default (VGX_CULL_WAVE_MIN)
 	// vgx_dash (vgx_dash.hip): per-draw patterns, per-list records, per-segment prefix sums (S and the overflow guard), per-range sums; the
 	// segment count of the last call in pinned memory (copied behind the call, read by the next call once its event has passed: a call
 	// whose lists outgrew dashG ends with VGX_E_GROWN and the next one grows first, as vgx_tessellate_immediate does)
-	DevBuf dashPat, dashLists, dashG, dashGhi, dashRange;
-	unsigned long long* dashHost; hipEvent_t dashEv; bool dashEvPending;
+	Buf<VgxDashPat> dashPat; Buf<VgxDashListRec> dashLists; Buf<uint64_t> dashG, dashGhi;
+	DevBuf dashRange;                    // views: uint64_t range sums, range offsets [2 x VGX_DASH_RANGES each], totals [4]
+	HostMirror<unsigned long long> dash;
 	// vgx_tessellate_dashed (vgx_dashframe.hip): the second set of mesh tables (the flatten stage writes one set, the frame's meshes go to the
 	// other; the two swap roles behind the call), per source mesh the list of the dash pass and D(m), the pieces' records, the dash pass's
-	// totals, and the need of the last call (pieces, their vertices, source meshes) with its pinned mirror, as immHost. The pieces' vertices
+	// totals, and the need of the last call (pieces, their vertices, source meshes) with its pinned mirror, as `imm`. The pieces' vertices
 	// lie BEHIND the flatten stage's heap in `poly`: pieceVerts of its vertices are theirs (ensureMeshBuffers keeps them out of caps)
-	DevBuf mdesc2, mprep2, mtab2, dfLists, dfListDraw, dfDashedBefore, dfPieceSubs, dfPieceDraw, dfPieceSrc, dfTotals, dfNeed;
+	Buf<VgxMeshDesc> mdesc2; Buf<VgxMeshPrep> mprep2; Buf<vgx_mesh> mtab2; Buf<vgx_subpath> dfLists, dfPieceSubs; Buf<uint32_t> dfListDraw, dfPieceDraw, dfPieceSrc;
+	Buf<uint64_t> dfDashedBefore, dfNeed; Buf<VgxTotals> dfTotals;
 	uint64_t pieceVerts;
-	unsigned long long* dfHost; hipEvent_t dfEv; bool dfEvPending;
-	DevBuf tileTab;                      // k_emit_tiles (vgx_tile.hip): the tile table of the current call
+	HostMirror<unsigned long long> df;
+	Buf<VgxTileRec> tileTab;             // k_emit_tiles (vgx_tile.hip): the tile table of the current call
 	bool tileHint;                       // the last ordinary vgx_tessellate_count saw fills and closed Miter AA / Thin strokes only (the tile kernel's batches)
 	uint64_t optBigEmitMin;              // vertex capacity from which a call launches the tile kernel / k_stroke_long (2^18; VGX_BIG_EMIT_MIN: testing knob, 0 = every call)
 	int optStrokeLong;                   // VGX_STROKE_LONG=0: batches of long polylines through k_stroke like any other (no LDS-staged stores)
 	int optTileEmit;                     // VGX_TILE_EMIT=0: ordinary batches through k_fill + k_stroke_simple as before round 6
-	DevBuf psTemp;                       // vgx_pathset_create: temporaries of the device-side build (vgx_pathset.hip)
+	DevBuf psTemp;                       // vgx_pathset_create: temporaries of the device-side build (vgx_pathset.hip); views: VgxPsTotals, uint32_t words, VgxPsM and Sum3 slice sums at byte offsets
 	hipStream_t psStream;                // ... its stream (created at the first call)
 	struct VgxPsTotals* hostPs;          // ... pinned: what the build reports
 	void* psImage; size_t psImageCap;    // ... pinned: the raw part of a frame-sized set, assembled here and uploaded in one copy
-	DevBuf psPool[VGX_PS_POOL];          // ... blobs of dropped frame-sized sets, recycled (hipFree synchronises)
+	DevBuf psPool[VGX_PS_POOL];          // ... blobs of dropped frame-sized sets, recycled (hipFree synchronises). Not scratch: never grown, not on the list
 	void* psStage[2]; hipEvent_t psStageEv[2]; bool psStageBusy[2]; uint64_t psStageK; int optPsStage, optPsNoSmall; // VGX_PS_UPLOAD=stage: own pinned staging
-	DevBuf f1SegDraw, f1Segs;            // vgx_flatten (vgx_flat1.hip): segment table, look-back records
+	Buf<uint64_t> f1SegDraw; Buf<VgxF1Seg> f1Segs; // vgx_flatten (vgx_flat1.hip): segment table, look-back records
 	int optF1Waves, optF1Cap, optF1Seg;  // its grid (persistent one-wave workgroups), the leaf-list capacity of the kernel instance and the segment bucket (0 = chosen per batch)
 	// what the last vgx_flatten call produced (copied to pinned memory behind the call, read by the next call WITHOUT waiting for
 	// it): polyline vertices per command instance decide how many commands a segment may hold before its leaves overflow the list
 	unsigned long long* hostF1;          // pinned: [0] vertices, [1] command instances, [2] tag of the batch they belong to
 	uint64_t f1Tag;
-	DevBuf gatherSizes;                  // vgx_gather_sizes: [nranks][4] uint64
-	DevBuf partBounds;                   // vgx_partition: [nparts + 1] bounds + [nparts] weights
+	Buf<VgxGatherWire> gatherSizes;      // vgx_gather_sizes: one record per rank
+	DevBuf partBounds;                   // vgx_partition; views: uint64_t [nparts + 1] bounds, behind them [nparts] weights
 	struct VgxRccl* rccl;                // RCCL entry points, bound at the first vgx_gather* call
 	// options, read from the environment ONCE at vgx_create (tuning / testing knobs)
 	int optTwoPass, optBuildWaves, optPoolWalk, optNoSmall;
@@ -136,22 +166,22 @@ struct vgx_ctx
 	// grouped mode, instances of different scales: the sort key is (path, tolerance class) with this many classes per path
 	// (1 = by path only), so that the lanes of a wave flatten with nearly the same tolerance and stay in lock-step
 	uint32_t instClasses;
-	DevBuf instHist, instCursor, instKeyStart, instStart, instTaskStart, instTaskPath, instOrder;
+	Buf<uint32_t> instHist, instCursor, instTaskPath, instOrder; Buf<uint64_t> instKeyStart, instStart, instTaskStart;
 	// periodic mode, instances of different scales: every vgx_tessellate sorts the INSTANCES by tolerance class (vgx_launch_inst_perm)
 	int instPermOn;
-	DevBuf instPerm, instPermHist;
+	Buf<uint32_t> instPerm, instPermHist;
 	uint64_t instCapPaths, instCapKeys, instCapTasks, instCapDraws;
 	// template mode (vgx_tmpl.hip): the first period of an instanced batch whose instances differ in transform / colours only,
 	// flattened once in local space by the last vgx_tessellate_count
 	int optTmpl; uint32_t optTmplTile;
 	uint32_t tmplTileSize;               // elements per tile of the current template
-	DevBuf tmplTile;                     // [tiles] VgxTmplTile
+	Buf<VgxTmplTile> tmplTile;           // [tiles]
 	bool tmplOn;
 	const vgx_pathset* tmplPs;
 	uint64_t tmplPsGen;                  // generation id of tmplPs when the template was built (an address can be reused by a later path set)
 	uint32_t tmplPeriod;
 	vgx_sizes tmplInst;                  // sizes of one instance
-	DevBuf tmplPoly, tmplMesh, tmplMtab, tmplElem, tmplDraws;
+	Buf<float2> tmplPoly; Buf<VgxTmplMesh> tmplMesh; Buf<vgx_mesh> tmplMtab; Buf<VgxTmplElem> tmplElem; Buf<vgx_draw> tmplDraws;
 	// ... in several flavours ("classes", e.g. the same drawing at a few scales): one template over the concatenated class
 	// representatives, a per-instance table of output places, a per-workgroup table (instance, tile)
 	int optTmplClasses;
@@ -162,13 +192,13 @@ struct vgx_ctx
 	uint32_t tmplGeneral;                // stroke styles of the template: 0 closed Miter AA / Thin only, 1 + open Miter with Butt / Square caps, 2 + general
 	uint64_t tmplNumWg, tmplNDraws;      // several classes: workgroups of one step; the batch size the per-instance table was built for
 	vgx_sizes tmplTotal;                 // sizes of the whole batch
-	DevBuf tmplHash, tmplInstCls, tmplClsRep, tmplCls, tmplIinfo, tmplWg, tmplClsSum;
+	Buf<unsigned long long> tmplHash, tmplClsSum; Buf<uint32_t> tmplInstCls, tmplClsRep; Buf<VgxTmplClass> tmplCls; Buf<VgxTmplInst> tmplIinfo; Buf<uint2> tmplWg;
 	uint32_t tmplRound;                  // Round-join stroke meshes per instance (tmplGeneral == 3): their sizes, and every place behind them, are counted per step
 	uint32_t tmplRoundElems;             // their elements per instance
 	uint32_t tmplRoundLds;               // Round-join meshes of the largest class (several classes; else = tmplRound)
 	uint64_t tmplRelemWords;             // several classes: table words of the whole batch (sum over the instances of their class's Round-join elements)
-	DevBuf tmplTrmesh, tmplTmsz;         // template: the Round-join meshes (mesh, first element among the Round-join elements); per mesh its sizes (VgxTmplArgs::tmsz)
-	DevBuf tmplRsz, tmplRelem, tmplMplace, tmplItot, tmplIplace; // the per-step tables of such a template (VgxTmplArgs)
+	Buf<VgxTmplRoundMesh> tmplTrmesh; Buf<uint2> tmplTmsz; // template: the Round-join meshes (mesh, first element among the Round-join elements); per mesh its sizes (VgxTmplArgs::tmsz)
+	Buf<unsigned long long> tmplRsz, tmplItot, tmplIplace; Buf<uint2> tmplRelem; Buf<VgxTmplMeshPlace> tmplMplace; // the per-step tables of such a template (VgxTmplArgs)
 	// element capacities of the buffers above. Never lifted: only ensureMeshBuffers and ensureCmdScratch write it, from the buffers'
 	// capacities, so every launch may trust it; a launch that needs other bounds (a sizing pass, the caller's capacities) is given them
 	VgxCaps caps;
@@ -176,7 +206,7 @@ struct vgx_ctx
 	VgxTotals* hostTotals; // pinned
 	// vgx_tessellate_immediate: pinned mirror of the last immediate call's totals, the event behind its copy (the next call reads the mirror
 	// only once that copy has landed) and the batch it belongs to (tag = path set generation, draw count; was the detection pass run)
-	VgxTotals* immHost; hipEvent_t immEv; bool immEvPending; uint64_t immPendTag; uint64_t immPendNDraws; bool immPendDetect;
+	HostMirror<VgxTotals> imm; uint64_t immPendTag; uint64_t immPendNDraws; bool immPendDetect;
 	// ... and what the host learned from the last mirror it read: the batch, its polyline vertices / command instances, the period of its
 	// paths (0: none), how many different paths it uses and, after VGX_E_GROWN, its long sub-paths
 	bool immKnown, immLongKnown; uint64_t immTag, immV, immCmd, immLong, immInstLong, immDistinct; uint32_t immPeriod;
@@ -211,30 +241,9 @@ namespace {
 		}                                                 \
 	} while (0)
 
-int ensure(vgx_ctx* ctx, DevBuf& b, size_t bytes)
-{
-	if (bytes <= b.cap) {
-		return VGX_OK;
-	}
-	// grow with 12.5 % head room so that near-identical batches do not reallocate
-	size_t want = bytes + bytes / 8 + 256;
-	void* fresh = nullptr;
-	hipError_t e = hipMalloc(&fresh, want);
-	if (e != hipSuccess && b.p) { // not enough room for old + new at once: release the old block first (contents are scratch)
-		(void)hipFree(b.p);
-		b.p = nullptr;
-		b.cap = 0;
-		e = hipMalloc(&fresh, want);
-	}
-	if (e != hipSuccess) {
-		ctx->lastHipError = (int)e;
-		return VGX_E_HIP;
-	}
-	if (b.p) { (void)hipFree(b.p); }
-	b.p = fresh;
-	b.cap = want;
-	return VGX_OK;
-}
+// the context's scratch grows here (vgx_scratch.h): a raw buffer by bytes, a typed one by elements
+int ensure(vgx_ctx* ctx, DevBuf& b, size_t bytes) { return vgx_scratch_grow(ctx->scratch, b, bytes, &ctx->lastHipError); }
+template<class T> int ensure(vgx_ctx* ctx, Buf<T>& b, uint64_t items) { return b.grow(ctx->scratch, items, &ctx->lastHipError); }
 
 // Every entry point that takes a context runs on the context's device, whatever device is current on the calling
 // thread (a torch rank, another context), and leaves the caller's current device as it found it.
@@ -270,6 +279,41 @@ void noteHip(vgx_ctx* ctx, hipError_t e)
 {
 	if (e != hipSuccess && !ctx->pendingHipError) { ctx->pendingHipError = (int)e; }
 }
+
+} // namespace
+
+template<class T> int HostMirror<T>::create(vgx_ctx* ctx, uint32_t count)
+{
+	if (host) { return VGX_OK; }
+	HIPCHK(ctx, hipHostMalloc((void**)&host, count * sizeof(T), hipHostMallocDefault));
+	const hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+	if (e != hipSuccess) { (void)hipHostFree(host); host = nullptr; ctx->lastHipError = (int)e; return VGX_E_HIP; }
+	memset(host, 0, count * sizeof(T));
+	n = count;
+	pending = false;
+	return VGX_OK;
+}
+
+template<class T> void HostMirror<T>::push(vgx_ctx* ctx, const void* dev, hipStream_t s)
+{
+	noteHip(ctx, hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
+	noteHip(ctx, hipEventRecord(ev, s));
+	pending = true;
+}
+
+template<class T> bool HostMirror<T>::landed()
+{
+	if (!pending || hipEventQuery(ev) != hipSuccess) { return false; }
+	pending = false;
+	return true;
+}
+
+template<class T> void HostMirror<T>::release()
+{
+	if (host) { (void)hipHostFree(host); (void)hipEventDestroy(ev); }
+}
+
+namespace {
 
 void mark(vgx_ctx* ctx, hipStream_t s, const char* name)
 {
@@ -455,23 +499,23 @@ VgxFlattenArgs flattenArgs(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* 
 	a.draws = draws;
 	a.ndraws = ndraws;
 	a.cmd_prefix = (const uint64_t*)ctx->cmdPrefix.p;
-	a.sub_prefix = (const uint64_t*)ctx->subPrefix.p;
-	a.cmd_cnt = (uint32_t*)ctx->cmdCnt.p;
-	a.dinfo = (vgx_draw_info*)ctx->dinfo.p;
+	a.sub_prefix = ctx->subPrefix.ptr();
+	a.cmd_cnt = ctx->cmdCnt.ptr();
+	a.dinfo = ctx->dinfo.ptr();
 	a.poly = (float*)ctx->poly.p;
-	a.subs = (vgx_subpath*)ctx->subs.p;
-	a.mdesc = (VgxMeshDesc*)ctx->mdesc.p;
+	a.subs = ctx->subs.ptr();
+	a.mdesc = ctx->mdesc.ptr();
 	a.mprep = nullptr;
-	a.mtab = (vgx_mesh*)ctx->mtab.p;
-	a.totals = (VgxTotals*)ctx->totals.p;
+	a.mtab = ctx->mtab.ptr();
+	a.totals = ctx->totals.ptr();
 	a.caps = ctx->caps;
 	a.apply_transform = applyTransform;
-	a.sub_rec = (VgxSubRec*)ctx->subFirst.p;
+	a.sub_rec = ctx->subFirst.ptr();
 	a.build_mode = 0;
 	a.pool_walk = ctx->optPoolWalk;
 	a.thin_static = ps->thinStatic ? ctx->optThinStatic : 0;
-	a.leaf_overflow = (float*)ctx->leafOverflow.p;
-	a.serial_list = (uint32_t*)ctx->serialList.p;
+	a.leaf_overflow = ctx->leafOverflow.ptr();
+	a.serial_list = ctx->serialList.ptr();
 	a.inst_period = 0; a.inst_block = ctx->optInstBlock; a.inst_waves = ctx->optInstWaves; a.inst_perm = nullptr;
 	a.inst_order = nullptr; a.inst_start = nullptr; a.inst_task_start = nullptr; a.inst_task_path = nullptr;
 	return a;
@@ -512,27 +556,26 @@ bool instGroupedFor(const vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws)
 }
 
 // scratch of the grouped mode: histogram / cursor / ranges per path, task table, draw order
+// the smallest of several capacities: what a group of buffers that are indexed alike holds
+uint64_t minOf(std::initializer_list<uint64_t> caps) { return std::min(caps); }
+
 int ensureInstGroup(vgx_ctx* ctx, uint32_t npaths, uint32_t nc, uint64_t ndraws, bool full)
 {
 	int st;
 	const size_t nkeys = (size_t)npaths * nc;
-	if ((st = ensure(ctx, ctx->instHist, (nkeys + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->instStart, ((size_t)npaths + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->instTaskStart, ((size_t)npaths + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->instHist, nkeys + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->instStart, (size_t)npaths + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->instTaskStart, (size_t)npaths + 1)) != VGX_OK) { return st; }
 	if (full) {
 		const uint64_t tasks = ndraws / 64 + (uint64_t)npaths + 2; // every used path rounds up once
-		if ((st = ensure(ctx, ctx->instCursor, (nkeys + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-		if ((st = ensure(ctx, ctx->instKeyStart, (nkeys + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
-		if ((st = ensure(ctx, ctx->instTaskPath, tasks * sizeof(uint32_t))) != VGX_OK) { return st; }
-		if ((st = ensure(ctx, ctx->instOrder, (ndraws + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-		ctx->instCapTasks = ctx->instTaskPath.cap / sizeof(uint32_t);
-		ctx->instCapDraws = ctx->instOrder.cap / sizeof(uint32_t) - 1;
-		uint64_t ck = ctx->instHist.cap / sizeof(uint32_t) - 1;
-		{ const uint64_t c2 = ctx->instCursor.cap / sizeof(uint32_t) - 1, c3 = ctx->instKeyStart.cap / sizeof(uint64_t) - 1; if (c2 < ck) { ck = c2; } if (c3 < ck) { ck = c3; } }
-		ctx->instCapKeys = ck;
-		uint64_t cp = ctx->instStart.cap / sizeof(uint64_t) - 1;
-		{ const uint64_t c4 = ctx->instTaskStart.cap / sizeof(uint64_t) - 1; if (c4 < cp) { cp = c4; } }
-		ctx->instCapPaths = cp;
+		if ((st = ensure(ctx, ctx->instCursor, nkeys + 1)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->instKeyStart, nkeys + 1)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->instTaskPath, tasks)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->instOrder, ndraws + 1)) != VGX_OK) { return st; }
+		ctx->instCapTasks = ctx->instTaskPath.items();
+		ctx->instCapDraws = ctx->instOrder.items() - 1;
+		ctx->instCapKeys = minOf({ ctx->instHist.items() - 1, ctx->instCursor.items() - 1, ctx->instKeyStart.items() - 1 });
+		ctx->instCapPaths = minOf({ ctx->instStart.items() - 1, ctx->instTaskStart.items() - 1 });
 	}
 	return VGX_OK;
 }
@@ -541,10 +584,10 @@ void setInstArgs(vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws, VgxFlatte
 {
 	a.inst_period = instPeriodFor(ctx, ndraws);
 	a.inst_perm = nullptr;
-	if (a.inst_period && ctx->instPermOn && ndraws / a.inst_period <= ctx->instPerm.cap / sizeof(uint32_t)) { a.inst_perm = (const uint32_t*)ctx->instPerm.p; }
+	if (a.inst_period && ctx->instPermOn && ndraws / a.inst_period <= ctx->instPerm.items()) { a.inst_perm = ctx->instPerm.ptr(); }
 	if (instGroupedFor(ctx, ps, ndraws)) {
-		a.inst_order = (const uint32_t*)ctx->instOrder.p; a.inst_start = (const uint64_t*)ctx->instStart.p;
-		a.inst_task_start = (const uint64_t*)ctx->instTaskStart.p; a.inst_task_path = (const uint32_t*)ctx->instTaskPath.p;
+		a.inst_order = ctx->instOrder.ptr(); a.inst_start = ctx->instStart.ptr();
+		a.inst_task_start = ctx->instTaskStart.ptr(); a.inst_task_path = ctx->instTaskPath.ptr();
 	}
 }
 
@@ -552,15 +595,13 @@ int ensureDrawBuffers(vgx_ctx* ctx, uint64_t ndraws)
 {
 	int st;
 	if ((st = ensure(ctx, ctx->cmdPrefix, (ndraws + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->subPrefix, (ndraws + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->dinfo, (ndraws + 1) * sizeof(vgx_draw_info))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->serialList, (ndraws + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->subPrefix, ndraws + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dinfo, ndraws + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->serialList, ndraws + 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	// what the grow-only buffers hold, not the last batch's size
-	uint64_t cap = ctx->cmdPrefix.cap / sizeof(uint64_t) - 1;
-	{ const uint64_t c2 = ctx->dinfo.cap / sizeof(vgx_draw_info) - 1, c3 = ctx->serialList.cap / sizeof(uint32_t) - 1, c4 = ctx->subPrefix.cap / sizeof(uint64_t) - 1; if (c2 < cap) { cap = c2; } if (c3 < cap) { cap = c3; } if (c4 < cap) { cap = c4; } }
-	ctx->capDraws = cap;
+	ctx->capDraws = minOf({ ctx->cmdPrefix.cap / sizeof(uint64_t) - 1, ctx->dinfo.items() - 1, ctx->serialList.items() - 1, ctx->subPrefix.items() - 1 });
 	return VGX_OK;
 }
 
@@ -576,8 +617,8 @@ OpCmdPrefix cmdPrefixOp(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* dra
 {
 	OpCmdPrefix op;
 	op.draws = draws; op.pathCmdBegin = ps->dev.path_cmd_begin; op.npaths = ps->dev.npaths; op.ndraws = ndraws;
-	op.prefix = (uint64_t*)ctx->cmdPrefix.p; op.totals = (VgxTotals*)ctx->totals.p; op.cap = cmdCap;
-	op.pathSubBegin = ps->dev.path_sub_begin; op.subPrefix = (uint64_t*)ctx->subPrefix.p;
+	op.prefix = (uint64_t*)ctx->cmdPrefix.p; op.totals = ctx->totals.ptr(); op.cap = cmdCap;
+	op.pathSubBegin = ps->dev.path_sub_begin; op.subPrefix = ctx->subPrefix.ptr();
 	op.period = instPeriod;
 	return op;
 }
@@ -599,7 +640,7 @@ void runFlattenCount(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws,
 	vgx_launch_flatten(false, a, VGX_GRID_BLOCKS, s);
 	mark(ctx, s, "flatten_count");
 	OpDrawInfo op;
-	op.dinfo = (vgx_draw_info*)ctx->dinfo.p; op.ndraws = ndraws; op.totals = (VgxTotals*)ctx->totals.p; op.caps = caps; op.keepPolyBase = 0;
+	op.dinfo = ctx->dinfo.ptr(); op.ndraws = ndraws; op.totals = ctx->totals.ptr(); op.caps = caps; op.keepPolyBase = 0;
 	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, ndraws);
 	mark(ctx, s, "scan_draws");
 }
@@ -612,20 +653,20 @@ void runFlattenBuild(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws,
 	a.build_mode = 1;
 	setInstArgs(ctx, ps, ndraws, a); // periodic: the same value runCmdPrefix checked the draws against
 	if (a.inst_perm) { // periodic mode, instances of different scales: this batch's instances sorted by tolerance class
-		vgx_launch_inst_perm(draws, ndraws / a.inst_period, a.inst_period, ctx->instClasses, (uint32_t*)ctx->instPermHist.p, (uint32_t*)ctx->instPerm.p, (VgxTotals*)ctx->totals.p, ctx->optInstPerm == 2, s);
+		vgx_launch_inst_perm(draws, ndraws / a.inst_period, a.inst_period, ctx->instClasses, ctx->instPermHist.ptr(), ctx->instPerm.ptr(), ctx->totals.ptr(), ctx->optInstPerm == 2, s);
 		mark(ctx, s, "inst_group");
 	}
 	if (a.inst_order) { // grouped mode: this batch's draws sorted by path
-		vgx_launch_inst_group(draws, ndraws, ps->dev.npaths, ctx->instClasses, (uint32_t*)ctx->instHist.p, (uint32_t*)ctx->instCursor.p, (uint64_t*)ctx->instKeyStart.p,
-			(uint64_t*)ctx->instStart.p, (uint64_t*)ctx->instTaskStart.p, (uint32_t*)ctx->instTaskPath.p, ctx->instCapTasks, (uint32_t*)ctx->instOrder.p,
-			(VgxTotals*)ctx->totals.p, ctx->partial.p, s);
+		vgx_launch_inst_group(draws, ndraws, ps->dev.npaths, ctx->instClasses, ctx->instHist.ptr(), ctx->instCursor.ptr(), ctx->instKeyStart.ptr(),
+			ctx->instStart.ptr(), ctx->instTaskStart.ptr(), ctx->instTaskPath.ptr(), ctx->instCapTasks, ctx->instOrder.ptr(),
+			ctx->totals.ptr(), ctx->partial.p, s);
 		mark(ctx, s, "inst_group");
 	}
-	a.mprep = (VgxMeshPrep*)ctx->mprep.p; // k_flatten_gather / k_flatten_serial write the per-mesh constants with the descriptors
+	a.mprep = ctx->mprep.ptr(); // k_flatten_gather / k_flatten_serial write the per-mesh constants with the descriptors
 	vgx_launch_flatten_build(a, ctx->optBuildWaves, s);
 	mark(ctx, s, "flatten_build");
 	OpDrawInfo op;
-	op.dinfo = (vgx_draw_info*)ctx->dinfo.p; op.ndraws = ndraws; op.totals = (VgxTotals*)ctx->totals.p; op.caps = ctx->caps; op.keepPolyBase = 1;
+	op.dinfo = ctx->dinfo.ptr(); op.ndraws = ndraws; op.totals = ctx->totals.ptr(); op.caps = ctx->caps; op.keepPolyBase = 1;
 	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, ndraws);
 	mark(ctx, s, "scan_draws");
 	vgx_launch_flatten_gather(a, s);
@@ -641,10 +682,10 @@ void runFlattenOneWalk(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draw
 {
 	runCmdPrefix(ctx, ps, draws, ndraws, ~0ull, s); // k_flat1 needs no per-command scratch
 	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, 1);
-	a.mprep = (VgxMeshPrep*)ctx->mprep.p; // k_flatten_serial / the gather write the per-mesh constants with the descriptors
+	a.mprep = ctx->mprep.ptr(); // k_flatten_serial / the gather write the per-mesh constants with the descriptors
 	const uint64_t segBound = ctx->f1RouteSegBound;
 	VgxF1Args x;
-	x.seg_draw = (uint64_t*)ctx->f1SegDraw.p; x.segs = (VgxF1Seg*)ctx->f1Segs.p; x.grps = x.segs + segBound;
+	x.seg_draw = ctx->f1SegDraw.ptr(); x.segs = ctx->f1Segs.ptr(); x.grps = x.segs + segBound;
 	x.cap_poly = ctx->caps.poly_vertices; x.cap_subs = ctx->caps.subpaths; x.cap_meshes = ctx->caps.meshes; x.pass = 0; x.read_flags = 0; x.has_empty = ps->hasEmpty ? 1 : 0;
 	x.seg_max = ctx->f1RouteSegMax; x.tag = 0;
 	if (ps->hasSerial) { // statically serial paths: the exact builder counts their draws first (it marks them in dinfo)
@@ -674,11 +715,11 @@ static uint64_t f1RouteSegmentsFor(const vgx_pathset* ps, uint64_t ndraws, uint3
 VgxStrokeArgs strokeArgs(vgx_ctx* ctx, const vgx_draw* draws, const float* poly, const VgxCaps& caps)
 {
 	VgxStrokeArgs a;
-	a.draws = draws; a.poly = poly ? poly : (const float*)ctx->poly.p; a.mdesc = (const VgxMeshDesc*)ctx->mdesc.p;
-	a.elem_prefix = nullptr; a.elem_prefix_fill = (const uint64_t*)ctx->elemPrefix.p; a.elem_prefix_stroke = (const uint64_t*)ctx->elemPrefixS.p;
-	a.mprep = (VgxMeshPrep*)ctx->mprep.p; a.mtab = (vgx_mesh*)ctx->mtab.p;
+	a.draws = draws; a.poly = poly ? poly : (const float*)ctx->poly.p; a.mdesc = ctx->mdesc.ptr();
+	a.elem_prefix = nullptr; a.elem_prefix_fill = ctx->elemPrefix.ptr(); a.elem_prefix_stroke = ctx->elemPrefixS.ptr();
+	a.mprep = ctx->mprep.ptr(); a.mtab = ctx->mtab.ptr();
 	a.pos = nullptr; a.color = nullptr; a.idx = nullptr; a.meshes_out = nullptr; a.mesh_base = nullptr;
-	a.totals = (VgxTotals*)ctx->totals.p; a.caps = caps; a.tile_mode = 0; a.no_long = 0;
+	a.totals = ctx->totals.ptr(); a.caps = caps; a.tile_mode = 0; a.no_long = 0;
 	return a;
 }
 
@@ -695,7 +736,7 @@ VgxCaps outCapsFor(const vgx_ctx* ctx, const vgx_mesh_out* out)
 // the call's totals into the caller's device words, if it asked for them
 void publish(vgx_ctx* ctx, vgx_sizes* dev_sizes, uint32_t* dev_status, hipStream_t s)
 {
-	if (dev_sizes || dev_status) { hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, (const VgxTotals*)ctx->totals.p, dev_sizes, dev_status); }
+	if (dev_sizes || dev_status) { hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, ctx->totals.ptr(), dev_sizes, dev_status); }
 }
 
 // prepDone: the flatten stage already wrote the per-mesh constants (single-pass pipeline), no k_mesh_prepare pass
@@ -706,9 +747,9 @@ void runStrokeCount(vgx_ctx* ctx, const vgx_draw* draws, const VgxCaps& outCaps,
 	vgx_launch_stroke(false, a, 32768, s); // k_round_sizes: Round-join mesh sizes (exits immediately without Round joins); one wave per mesh: 10 000 long polylines want more than 4 096 waves
 	mark(ctx, s, "mesh_prepare");
 	OpMeshAll op;
-	op.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; op.mtab = (vgx_mesh*)ctx->mtab.p;
-	op.prefixFill = (uint64_t*)ctx->elemPrefix.p; op.prefixStroke = (uint64_t*)ctx->elemPrefixS.p;
-	op.totals = (VgxTotals*)ctx->totals.p; op.caps = outCaps; op.checkCaps = checkCaps;
+	op.mdesc = ctx->mdesc.ptr(); op.mtab = ctx->mtab.ptr();
+	op.prefixFill = ctx->elemPrefix.ptr(); op.prefixStroke = ctx->elemPrefixS.ptr();
+	op.totals = ctx->totals.ptr(); op.caps = outCaps; op.checkCaps = checkCaps;
 	op.meshesOut = meshesOut; op.fixedSize = 0; op.fixedCount = 0;
 	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, ctx->caps.meshes);
 	mark(ctx, s, "scan_meshes");
@@ -719,27 +760,27 @@ void runStrokeCount(vgx_ctx* ctx, const vgx_draw* draws, const VgxCaps& outCaps,
 int runAssemble(vgx_ctx* ctx, const vgx_mesh_out* out, hipStream_t s, const vgx_draw* draws = nullptr)
 {
 	const uint32_t maxVB = ctx->asmCfg.max_vb_vertices ? ctx->asmCfg.max_vb_vertices : 65536u;
-	const uint64_t meshCap = ctx->mtab.cap / sizeof(vgx_mesh);
+	const uint64_t meshCap = ctx->mtab.items();
 	uint64_t need = 2 * (out->cap_vertices / maxVB) + 4; // two consecutive vertex buffers always hold > maxVB vertices
 	if (need > meshCap + 1) { need = meshCap + 1; }
 	if (meshCap >= 0xFFFFFFFFull) { return VGX_E_RANGE; } // the jump tables hold 32-bit mesh indices
 	uint64_t capStart = 2;
 	while (capStart < need) { capStart <<= 1; }
 	int st;
-	if ((st = ensure(ctx, ctx->asmJump0, (meshCap + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->asmJump1, (meshCap + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->asmStart, capStart * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->meshBase, (meshCap + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->asmJump0, meshCap + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->asmJump1, meshCap + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->asmStart, capStart)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->meshBase, meshCap + 1)) != VGX_OK) { return st; }
 	VgxAsmArgs a;
-	a.mtab = (const vgx_mesh*)ctx->mtab.p;
-	a.jump0 = (uint32_t*)ctx->asmJump0.p; a.jump1 = (uint32_t*)ctx->asmJump1.p;
-	a.start = (uint32_t*)ctx->asmStart.p; a.cap_start = capStart;
-	a.mesh_base = (uint32_t*)ctx->meshBase.p;
+	a.mtab = ctx->mtab.ptr();
+	a.jump0 = ctx->asmJump0.ptr(); a.jump1 = ctx->asmJump1.ptr();
+	a.start = ctx->asmStart.ptr(); a.cap_start = capStart;
+	a.mesh_base = ctx->meshBase.ptr();
 	a.drawcmds = ctx->asmCfg.drawcmds; a.cap_drawcmds = ctx->asmCfg.cap_drawcmds; a.dev_num_drawcmds = ctx->asmCfg.dev_num_drawcmds;
 	a.max_vb = maxVB;
-	a.totals = (VgxTotals*)ctx->totals.p;
+	a.totals = ctx->totals.ptr();
 	a.flags = draws ? ctx->asmCfg.flags : 0u; // no draw records at this level (shape cache): one state
-	a.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; a.draws = draws;
+	a.mdesc = ctx->mdesc.ptr(); a.draws = draws;
 	a.mesh_cmd = a.jump0;
 	a.partial = ctx->partial.p;
 	a.max_meshes = meshCap;
@@ -758,7 +799,7 @@ int runStrokeEmit(vgx_ctx* ctx, const vgx_draw* draws, const vgx_mesh_out* out, 
 		if (st != VGX_OK) { return st; }
 	}
 	VgxStrokeArgs a = strokeArgs(ctx, draws, poly, ctx->caps);
-	a.mesh_base = ctx->asmArmed ? (const uint32_t*)ctx->meshBase.p : nullptr;
+	a.mesh_base = ctx->asmArmed ? ctx->meshBase.ptr() : nullptr;
 	a.pos = out->pos; a.color = out->color; a.idx = out->idx; a.meshes_out = tableDone ? nullptr : out->meshes;
 	a.no_long = (out->cap_vertices < ctx->optBigEmitMin || !ctx->optStrokeLong) ? 1 : 0; // frame-sized: one stroke kernel less to launch
 	// Batches of fills and closed Miter AA / Thin strokes (the scan over the meshes decides, on the device): one draw-ordered tile
@@ -766,7 +807,7 @@ int runStrokeEmit(vgx_ctx* ctx, const vgx_draw* draws, const vgx_mesh_out* out, 
 	uint64_t capTiles = 0;
 	if (ctx->optTileEmit && ctx->tileHint && out->cap_vertices >= ctx->optBigEmitMin && out->cap_vertices / VGX_TILE_ELEMS + 2 < 0x7FFFFFFFull) {
 		capTiles = out->cap_vertices / VGX_TILE_ELEMS + 2; // every element emits at least one vertex
-		const int st = ensure(ctx, ctx->tileTab, capTiles * sizeof(VgxTileRec));
+		const int st = ensure(ctx, ctx->tileTab, capTiles);
 		if (st != VGX_OK) { return st; }
 		a.tile_mode = 1;
 	}
@@ -778,7 +819,7 @@ int runStrokeEmit(vgx_ctx* ctx, const vgx_draw* draws, const vgx_mesh_out* out, 
 	mark(ctx, s, "stroke_emit");
 	if (a.tile_mode) {
 		a.elem_prefix = nullptr;
-		vgx_launch_emit_tiles(a, (VgxTileRec*)ctx->tileTab.p, capTiles, s);
+		vgx_launch_emit_tiles(a, ctx->tileTab.ptr(), capTiles, s);
 		mark(ctx, s, "tile_emit");
 	}
 	return launchStatus(ctx);
@@ -788,21 +829,15 @@ int ensureMeshBuffers(vgx_ctx* ctx, uint64_t polyVerts, uint64_t subpaths, uint6
 {
 	int st;
 	if ((st = ensure(ctx, ctx->poly, (polyVerts + 1 + ctx->pieceVerts) * 2 * sizeof(float))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->subs, (subpaths + 1) * sizeof(vgx_subpath))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->mdesc, (meshes + 1) * sizeof(VgxMeshDesc))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->elemPrefix, (meshes + 2) * sizeof(uint64_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->elemPrefixS, (meshes + 2) * sizeof(uint64_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->mprep, (meshes + 1) * sizeof(VgxMeshPrep))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->mtab, (meshes + 1) * sizeof(vgx_mesh))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->subs, subpaths + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mdesc, meshes + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->elemPrefix, meshes + 2)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->elemPrefixS, meshes + 2)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mprep, meshes + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mtab, meshes + 1)) != VGX_OK) { return st; }
 	ctx->caps.poly_vertices = ctx->poly.cap / (2 * sizeof(float)) - 1 - ctx->pieceVerts; // (the tail belongs to vgx_tessellate_dashed's pieces)
-	ctx->caps.subpaths = ctx->subs.cap / sizeof(vgx_subpath) - 1;
-	uint64_t m = ctx->mdesc.cap / sizeof(VgxMeshDesc) - 1;
-	uint64_t m2 = ctx->elemPrefix.cap / sizeof(uint64_t) - 2;
-	{ const uint64_t m4 = ctx->elemPrefixS.cap / sizeof(uint64_t) - 2, m5 = ctx->mprep.cap / sizeof(VgxMeshPrep) - 1; if (m4 < m2) { m2 = m4; } if (m5 < m2) { m2 = m5; } }
-	const uint64_t m3 = ctx->mtab.cap / sizeof(vgx_mesh) - 1;
-	if (m2 < m) { m = m2; }
-	if (m3 < m) { m = m3; }
-	ctx->caps.meshes = m;
+	ctx->caps.subpaths = ctx->subs.items() - 1;
+	ctx->caps.meshes = minOf({ ctx->mdesc.items() - 1, ctx->elemPrefix.items() - 2, ctx->elemPrefixS.items() - 2, ctx->mprep.items() - 1, ctx->mtab.items() - 1 });
 	return VGX_OK;
 }
 
@@ -810,11 +845,10 @@ int ensureMeshBuffers(vgx_ctx* ctx, uint64_t polyVerts, uint64_t subpaths, uint6
 int ensureCmdScratch(vgx_ctx* ctx, uint64_t ncmd)
 {
 	int st;
-	if ((st = ensure(ctx, ctx->cmdCnt, (ncmd + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->subFirst, (ncmd + 1) * sizeof(VgxSubRec))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->leafOverflow, (size_t)VGX_BUILD_WAVES * VGX_BUILD_OVERFLOW * 64 * 2 * sizeof(float))) != VGX_OK) { return st; }
-	ctx->caps.cmd_instances = ctx->cmdCnt.cap / sizeof(uint32_t) - 1;
-	{ const uint64_t c2 = ctx->subFirst.cap / sizeof(VgxSubRec) - 1; if (c2 < ctx->caps.cmd_instances) { ctx->caps.cmd_instances = c2; } }
+	if ((st = ensure(ctx, ctx->cmdCnt, ncmd + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->subFirst, ncmd + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->leafOverflow, (size_t)VGX_BUILD_WAVES * VGX_BUILD_OVERFLOW * 64 * 2)) != VGX_OK) { return st; }
+	ctx->caps.cmd_instances = minOf({ ctx->cmdCnt.items() - 1, ctx->subFirst.items() - 1 });
 	return VGX_OK;
 }
 
@@ -868,8 +902,8 @@ void f1Shape(const vgx_ctx* ctx, uint64_t V, uint64_t ncmd, int* cap, uint32_t* 
 int ensureF1Tables(vgx_ctx* ctx, uint64_t segBound)
 {
 	int st;
-	if ((st = ensure(ctx, ctx->f1SegDraw, (segBound + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
-	return ensure(ctx, ctx->f1Segs, (segBound + segBound / 64 + 2) * sizeof(VgxF1Seg));
+	if ((st = ensure(ctx, ctx->f1SegDraw, segBound + 1)) != VGX_OK) { return st; }
+	return ensure(ctx, ctx->f1Segs, segBound + segBound / 64 + 2);
 }
 
 // vgx_tessellate's one-walk route sized for any draw list of up to `segDraws` draws on `ps` (f1Route*); *ok = false: more than 2^24
@@ -894,21 +928,21 @@ int runFrameSized(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, ui
 {
 	const VgxCaps outCaps = outCapsFor(ctx, out);
 	const OpCmdPrefix opC = cmdPrefixOp(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, 0);
-	vgx_launch_small_front(&opC, (vgx_draw_info*)ctx->dinfo.p, s);
+	vgx_launch_small_front(&opC, ctx->dinfo.ptr(), s);
 	mark(ctx, s, "small_front");
 	VgxFlattenArgs f = flattenArgs(ctx, ps, draws, ndraws, 1);
 	f.build_mode = 1;
-	f.mprep = (VgxMeshPrep*)ctx->mprep.p;
+	f.mprep = ctx->mprep.ptr();
 	vgx_launch_flatten_build(f, ctx->optBuildWaves, s, false);
 	mark(ctx, s, "flatten_build");
 	VgxStrokeArgs sa = strokeArgs(ctx, draws, nullptr, outCaps);
 	sa.no_long = 1;
 	OpDrawInfo opD;
-	opD.dinfo = (vgx_draw_info*)ctx->dinfo.p; opD.ndraws = ndraws; opD.totals = (VgxTotals*)ctx->totals.p; opD.caps = ctx->caps; opD.keepPolyBase = 1; opD.markScratch = markScratch;
+	opD.dinfo = ctx->dinfo.ptr(); opD.ndraws = ndraws; opD.totals = ctx->totals.ptr(); opD.caps = ctx->caps; opD.keepPolyBase = 1; opD.markScratch = markScratch;
 	OpMeshAll opM;
-	opM.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; opM.mtab = (vgx_mesh*)ctx->mtab.p; opM.meshesOut = out->meshes;
-	opM.prefixFill = (uint64_t*)ctx->elemPrefix.p; opM.prefixStroke = (uint64_t*)ctx->elemPrefixS.p;
-	opM.totals = (VgxTotals*)ctx->totals.p; opM.caps = outCaps; opM.checkCaps = 1; opM.fixedSize = 0; opM.fixedCount = 0;
+	opM.mdesc = ctx->mdesc.ptr(); opM.mtab = ctx->mtab.ptr(); opM.meshesOut = out->meshes;
+	opM.prefixFill = ctx->elemPrefix.ptr(); opM.prefixStroke = ctx->elemPrefixS.ptr();
+	opM.totals = ctx->totals.ptr(); opM.caps = outCaps; opM.checkCaps = 1; opM.fixedSize = 0; opM.fixedCount = 0;
 	vgx_launch_small_middle(f, sa, &opD, &opM, dev_sizes, dev_status, s);
 	mark(ctx, s, "small_middle");
 	return runStrokeEmit(ctx, draws, out, s, nullptr, true);
@@ -1022,15 +1056,10 @@ int vgx_destroy(vgx_ctx* ctx)
 		return VGX_E_INVALID_ARG;
 	}
 	DeviceGuard guard(ctx);
-	DevBuf* bufs[] = { &ctx->updPrefix, &ctx->updPartial, &ctx->pickKeys, &ctx->pickTris, &ctx->pickCand, &ctx->pickPrefix, &ctx->pickTotals, &ctx->pickPartial, &ctx->pickBounds, &ctx->cullFlags, &ctx->cullPartial, &ctx->mdesc2, &ctx->mprep2, &ctx->mtab2, &ctx->dfLists, &ctx->dfListDraw, &ctx->dfDashedBefore, &ctx->dfPieceSubs, &ctx->dfPieceDraw, &ctx->dfPieceSrc, &ctx->dfTotals, &ctx->dfNeed, &ctx->dashPat, &ctx->dashLists, &ctx->dashG, &ctx->dashGhi, &ctx->dashRange, &ctx->tmplClsSum, &ctx->tileTab, &ctx->textTiles, &ctx->psTemp, &ctx->f1SegDraw, &ctx->f1Segs, &ctx->tmplHash, &ctx->tmplInstCls, &ctx->tmplClsRep, &ctx->tmplCls, &ctx->tmplIinfo, &ctx->tmplWg, &ctx->tmplTrmesh, &ctx->tmplTmsz, &ctx->tmplRsz, &ctx->tmplRelem, &ctx->tmplMplace, &ctx->tmplItot, &ctx->tmplIplace, &ctx->tmplTile, &ctx->tmplPoly, &ctx->tmplMesh, &ctx->tmplMtab, &ctx->tmplElem, &ctx->tmplDraws, &ctx->partBounds, &ctx->instPerm, &ctx->instPermHist, &ctx->instHist, &ctx->instCursor, &ctx->instKeyStart, &ctx->instStart, &ctx->instTaskStart, &ctx->instTaskPath, &ctx->instOrder, &ctx->gatherSizes, &ctx->asmJump0, &ctx->asmJump1, &ctx->asmStart, &ctx->meshBase, &ctx->subPrefix, &ctx->cmdPrefix, &ctx->cmdCnt, &ctx->subFirst, &ctx->leafOverflow, &ctx->serialList, &ctx->dinfo, &ctx->poly, &ctx->subs, &ctx->mdesc, &ctx->elemPrefix, &ctx->elemPrefixS, &ctx->mprep, &ctx->mtab, &ctx->partial, &ctx->totals };
-	for (DevBuf* b : bufs) {
-		if (b->p) { (void)hipFree(b->p); }
-	}
+	vgx_scratch_release(ctx->scratch);
 	if (ctx->hostTotals) { (void)hipHostFree(ctx->hostTotals); }
 	if (ctx->hostF1) { (void)hipHostFree(ctx->hostF1); }
-	if (ctx->immHost) { (void)hipHostFree(ctx->immHost); (void)hipEventDestroy(ctx->immEv); }
-	if (ctx->dashHost) { (void)hipHostFree(ctx->dashHost); (void)hipEventDestroy(ctx->dashEv); }
-	if (ctx->dfHost) { (void)hipHostFree(ctx->dfHost); (void)hipEventDestroy(ctx->dfEv); }
+	ctx->imm.release(); ctx->dash.release(); ctx->df.release();
 	if (ctx->hostPs) { (void)hipHostFree(ctx->hostPs); }
 	if (ctx->psImage) { (void)hipHostFree(ctx->psImage); }
 	for (int i = 0; i < VGX_PS_POOL; ++i) { if (ctx->psPool[i].p) { (void)hipFree(ctx->psPool[i].p); } }
@@ -1051,7 +1080,7 @@ uint64_t vgx_scratch_bytes(const vgx_ctx* ctx)
 	if (!ctx) {
 		return 0;
 	}
-	return ctx->updPrefix.cap + ctx->updPartial.cap + ctx->pickKeys.cap + ctx->pickTris.cap + ctx->pickCand.cap + ctx->pickPrefix.cap + ctx->pickTotals.cap + ctx->pickPartial.cap + ctx->pickBounds.cap + ctx->cullFlags.cap + ctx->cullPartial.cap + ctx->mdesc2.cap + ctx->mprep2.cap + ctx->mtab2.cap + ctx->dfLists.cap + ctx->dfListDraw.cap + ctx->dfDashedBefore.cap + ctx->dfPieceSubs.cap + ctx->dfPieceDraw.cap + ctx->dfPieceSrc.cap + ctx->dfTotals.cap + ctx->dfNeed.cap + ctx->dashPat.cap + ctx->dashLists.cap + ctx->dashG.cap + ctx->dashGhi.cap + ctx->dashRange.cap + ctx->tmplClsSum.cap + ctx->tileTab.cap + ctx->textTiles.cap + ctx->psTemp.cap + ctx->f1SegDraw.cap + ctx->f1Segs.cap + ctx->tmplHash.cap + ctx->tmplInstCls.cap + ctx->tmplClsRep.cap + ctx->tmplCls.cap + ctx->tmplIinfo.cap + ctx->tmplWg.cap + ctx->tmplTrmesh.cap + ctx->tmplTmsz.cap + ctx->tmplRsz.cap + ctx->tmplRelem.cap + ctx->tmplMplace.cap + ctx->tmplItot.cap + ctx->tmplIplace.cap + ctx->tmplTile.cap + ctx->tmplPoly.cap + ctx->tmplMesh.cap + ctx->tmplMtab.cap + ctx->tmplElem.cap + ctx->tmplDraws.cap + ctx->gatherSizes.cap + ctx->asmJump0.cap + ctx->asmJump1.cap + ctx->asmStart.cap + ctx->meshBase.cap + ctx->subPrefix.cap + ctx->cmdPrefix.cap + ctx->cmdCnt.cap + ctx->subFirst.cap + ctx->leafOverflow.cap + ctx->serialList.cap + ctx->dinfo.cap + ctx->poly.cap + ctx->subs.cap + ctx->mdesc.cap + ctx->elemPrefix.cap + ctx->elemPrefixS.cap + ctx->mprep.cap + ctx->mtab.cap + ctx->partial.cap + ctx->totals.cap;
+	return vgx_scratch_bytes(ctx->scratch);
 }
 
 // ---- path set ---------------------------------------------------------------------------------------
@@ -1347,11 +1376,11 @@ static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw*
 	// pass 1: command instances (sizes the per-command scratch; not known yet: no bound)
 	runCmdPrefix(ctx, ps, draws, ndraws, ~0ull, s);
 	if (detectInst && ctx->optInst && ndraws > VGX_SMALL_DRAWS) {
-		vgx_launch_inst_detect(draws, ndraws, (VgxTotals*)ctx->totals.p, s);
+		vgx_launch_inst_detect(draws, ndraws, ctx->totals.ptr(), s);
 		// ... and how many different paths the draws use (grouped mode, when the sequence does not repeat)
 		if ((st = ensureInstGroup(ctx, ps->dev.npaths, 1, ndraws, false)) != VGX_OK) { return st; }
-		vgx_launch_inst_group(draws, ndraws, ps->dev.npaths, 1, (uint32_t*)ctx->instHist.p, nullptr, nullptr, (uint64_t*)ctx->instStart.p, (uint64_t*)ctx->instTaskStart.p,
-			nullptr, 0, nullptr, (VgxTotals*)ctx->totals.p, ctx->partial.p, s);
+		vgx_launch_inst_group(draws, ndraws, ps->dev.npaths, 1, ctx->instHist.ptr(), nullptr, nullptr, ctx->instStart.ptr(), ctx->instTaskStart.ptr(),
+			nullptr, 0, nullptr, ctx->totals.ptr(), ctx->partial.p, s);
 	}
 	if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
 	if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
@@ -1370,8 +1399,8 @@ static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw*
 			// the sequence repeats: keep the periodic mapping (closed-form offsets, no per-draw sort) and permute the INSTANCES
 			const uint64_t ninst = ndraws / ctx->instPeriod;
 			if (nc > 1024u) { nc = 1024u; }
-			if ((st = ensure(ctx, ctx->instPerm, (ninst + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-			if ((st = ensure(ctx, ctx->instPermHist, ((size_t)nc + 2) * sizeof(uint32_t))) != VGX_OK) { return st; }
+			if ((st = ensure(ctx, ctx->instPerm, ninst + 1)) != VGX_OK) { return st; }
+			if ((st = ensure(ctx, ctx->instPermHist, (size_t)nc + 2)) != VGX_OK) { return st; }
 			ctx->instClasses = nc;
 			ctx->instPermOn = 1;
 		} else {
@@ -1432,10 +1461,10 @@ int vgx_flatten_emit(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws,
 	int st;
 	// outputs the caller does not want still need somewhere to go
 	if (!out->poly) { if ((st = ensure(ctx, ctx->poly, (sz.num_poly_vertices + 1) * 2 * sizeof(float))) != VGX_OK) { return st; } }
-	if (!out->subpaths) { if ((st = ensure(ctx, ctx->subs, (sz.num_subpaths + 1) * sizeof(vgx_subpath))) != VGX_OK) { return st; } }
+	if (!out->subpaths) { if ((st = ensure(ctx, ctx->subs, sz.num_subpaths + 1)) != VGX_OK) { return st; } }
 	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, apply_transform);
 	a.poly = out->poly ? out->poly : (float*)ctx->poly.p;
-	a.subs = out->subpaths ? out->subpaths : (vgx_subpath*)ctx->subs.p;
+	a.subs = out->subpaths ? out->subpaths : ctx->subs.ptr();
 	a.mdesc = nullptr;
 	a.mtab = nullptr;
 	a.caps.poly_vertices = ~0ull; a.caps.subpaths = ~0ull; a.caps.meshes = ~0ull;
@@ -1482,10 +1511,10 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	const uint64_t cmdBoundAll = ndraws * (uint64_t)(ps->maxCmdsPerPath ? ps->maxCmdsPerPath : 1);
 	if (known && !ctx->optF1Cap && !ctx->optF1Seg && !ps->hasEmpty
 		&& (double)ctx->hostF1[0] / (double)ctx->hostF1[1] * 64.0 <= 384.0 && cmdBoundAll <= 2 * ctx->hostF1[1] + 4096) {
-		if ((st = ensure(ctx, ctx->cmdCnt, (cmdBoundAll + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->cmdCnt, cmdBoundAll + 1)) != VGX_OK) { return st; }
 		// The device-side guard of THIS call only (a batch that grew: VGX_E_NOSPACE). The two-walk kernels write per-command words
 		// only -- no sub-path records: cmdCnt alone bounds this launch. ctx->caps stays what vgx_tessellate relies on.
-		runCmdPrefix(ctx, ps, draws, ndraws, ctx->cmdCnt.cap / sizeof(uint32_t) - 1, s);
+		runCmdPrefix(ctx, ps, draws, ndraws, ctx->cmdCnt.items() - 1, s);
 		VgxCaps countCaps = ctx->caps; // the scan over the draws compares the totals with the caller's capacities
 		countCaps.poly_vertices = out->cap_poly_vertices; countCaps.subpaths = out->cap_subpaths; countCaps.meshes = ~0ull;
 		runFlattenCount(ctx, ps, draws, ndraws, countCaps, s);
@@ -1496,7 +1525,7 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 		mark(ctx, s, "flatten_emit");
 		publish(ctx, dev_sizes, dev_status, s);
 		{
-			VgxTotals* T = (VgxTotals*)ctx->totals.p;
+			VgxTotals* T = ctx->totals.ptr();
 			noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[0], &T->sizes.num_poly_vertices, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 			noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[1], &T->sizes.num_cmd_instances, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 		}
@@ -1523,7 +1552,7 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	a.mdesc = nullptr; a.mtab = nullptr;
 	a.caps.poly_vertices = ~0ull; a.caps.subpaths = ~0ull; a.caps.meshes = ~0ull;
 	VgxF1Args x;
-	x.seg_draw = (uint64_t*)ctx->f1SegDraw.p; x.segs = (VgxF1Seg*)ctx->f1Segs.p; x.grps = x.segs + segBound;
+	x.seg_draw = ctx->f1SegDraw.ptr(); x.segs = ctx->f1Segs.ptr(); x.grps = x.segs + segBound;
 	x.cap_poly = out->cap_poly_vertices; x.cap_subs = out->cap_subpaths; x.cap_meshes = ~0ull; x.pass = 0; x.read_flags = 0; x.has_empty = ps->hasEmpty ? 1 : 0; x.seg_max = segMax; x.tag = tag;
 	if (ps->hasSerial) { // statically serial paths: the exact builder counts their draws first (it marks them in dinfo)
 		noteHip(ctx, hipMemsetAsync(ctx->dinfo.p, 0, ndraws * sizeof(vgx_draw_info), s));
@@ -1538,7 +1567,7 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	vgx_launch_flat1_publish(a, x, dev_sizes, dev_status, s);
 	mark(ctx, s, "flatten_one_walk");
 	if (ctx->hostF1) { // for the next call's choice of instance / bucket (never waited for)
-		VgxTotals* T = (VgxTotals*)ctx->totals.p;
+		VgxTotals* T = ctx->totals.ptr();
 		ctx->f1Tag = tag;
 		noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[0], &T->sizes.num_poly_vertices, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 		noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[1], &T->sizes.num_cmd_instances, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -1587,9 +1616,9 @@ int vgx_partition(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, ui
 	int st;
 	uint64_t align = 1;
 	if (ctx->optInst && ndraws > VGX_SMALL_DRAWS) { // a drawing submitted for many instances? Then the cuts fall between instances
-		if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 		noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
-		vgx_launch_inst_detect(draws, ndraws, (VgxTotals*)ctx->totals.p, s);
+		vgx_launch_inst_detect(draws, ndraws, ctx->totals.ptr(), s);
 		if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
 		if (ctx->hostTotals->inst_detect_inv != 0 && !ctx->hostTotals->inst_detect_bad) {
 			const unsigned long long P = ~0ull - ctx->hostTotals->inst_detect_inv;
@@ -1600,7 +1629,7 @@ int vgx_partition(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, ui
 	if (st != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partBounds, ((size_t)nparts + 1) * 2 * sizeof(uint64_t))) != VGX_OK) { return st; }
 	OpPartWeight op;
-	op.draws = draws; op.dinfo = (const vgx_draw_info*)ctx->dinfo.p; op.ndraws = ndraws; op.prefix = (uint64_t*)ctx->cmdPrefix.p; // the command prefix is not needed any more
+	op.draws = draws; op.dinfo = ctx->dinfo.ptr(); op.ndraws = ndraws; op.prefix = (uint64_t*)ctx->cmdPrefix.p; // the command prefix is not needed any more
 	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, ndraws);
 	uint64_t* dBounds = (uint64_t*)ctx->partBounds.p;
 	uint64_t* dWeights = dBounds + nparts + 1;
@@ -1620,19 +1649,19 @@ static int tmplRoundSizes(vgx_ctx* ctx, VgxTmplArgs& a, hipStream_t s)
 	int st;
 	const uint64_t n = a.ninst;
 	a.num_round = ctx->tmplRound; a.num_round_elems = ctx->tmplRoundElems;
-	a.trmesh = (const VgxTmplRoundMesh*)ctx->tmplTrmesh.p; a.tmsz = (const uint2*)ctx->tmplTmsz.p;
+	a.trmesh = ctx->tmplTrmesh.ptr(); a.tmsz = ctx->tmplTmsz.ptr();
 	if (n * a.num_round >= (1ull << 31)) { return VGX_E_RANGE; } // one wave (long meshes: one workgroup) per (instance, Round-join mesh)
 	const bool classes = a.cls != nullptr; // several classes: the tables' rows are the instances' own (VgxTmplInst::m / ::rel), the sizes stay in LDS
-	if (!classes && (st = ensure(ctx, ctx->tmplRsz, (n * a.num_round + 1) * 2 * sizeof(unsigned long long))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplRelem, ((classes ? ctx->tmplRelemWords : n * a.num_round_elems) + 1) * sizeof(uint2))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplMplace, ((classes ? a.total.num_meshes : n * a.inst.num_meshes) + 1) * sizeof(VgxTmplMeshPlace))) != VGX_OK) { return st; }
+	if (!classes && (st = ensure(ctx, ctx->tmplRsz, (n * a.num_round + 1) * 2)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmplRelem, (classes ? ctx->tmplRelemWords : n * a.num_round_elems) + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmplMplace, (classes ? a.total.num_meshes : n * a.inst.num_meshes) + 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
-	a.rsz = classes ? nullptr : (unsigned long long*)ctx->tmplRsz.p; a.relem = (uint2*)ctx->tmplRelem.p;
-	a.mplace = (VgxTmplMeshPlace*)ctx->tmplMplace.p;
+	a.rsz = classes ? nullptr : ctx->tmplRsz.ptr(); a.relem = ctx->tmplRelem.ptr();
+	a.mplace = ctx->tmplMplace.ptr();
 	if (vgx_tmpl_round_per_instance(a)) {
-		if ((st = ensure(ctx, ctx->tmplItot, (n + 1) * 2 * sizeof(unsigned long long))) != VGX_OK) { return st; }
-		if ((st = ensure(ctx, ctx->tmplIplace, (n + 1) * 2 * sizeof(unsigned long long))) != VGX_OK) { return st; }
-		a.itot = (unsigned long long*)ctx->tmplItot.p; a.iplace = (unsigned long long*)ctx->tmplIplace.p;
+		if ((st = ensure(ctx, ctx->tmplItot, (n + 1) * 2)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->tmplIplace, (n + 1) * 2)) != VGX_OK) { return st; }
+		a.itot = ctx->tmplItot.ptr(); a.iplace = ctx->tmplIplace.ptr();
 	}
 	vgx_launch_tmpl_round_sizes(a, (Sum3*)ctx->partial.p, s);
 	mark(ctx, s, "tmpl_round_sizes");
@@ -1643,18 +1672,18 @@ static int tmplRoundSizes(vgx_ctx* ctx, VgxTmplArgs& a, hipStream_t s)
 static void tmplArgs(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, VgxTmplArgs& a)
 {
 	a.draws = draws; a.ndraws = ndraws; a.period = ctx->tmplPeriod; a.ninst = ndraws / ctx->tmplPeriod; a.npaths = ps->dev.npaths;
-	a.tdraws = (const vgx_draw*)ctx->tmplDraws.p; a.tpoly = (const float2*)ctx->tmplPoly.p; a.tmesh = (const VgxTmplMesh*)ctx->tmplMesh.p;
-	a.tmtab = (const vgx_mesh*)ctx->tmplMtab.p; a.telem = (const VgxTmplElem*)ctx->tmplElem.p;
+	a.tdraws = ctx->tmplDraws.ptr(); a.tpoly = ctx->tmplPoly.ptr(); a.tmesh = ctx->tmplMesh.ptr();
+	a.tmtab = ctx->tmplMtab.ptr(); a.telem = ctx->tmplElem.ptr();
 	a.inst = ctx->tmplInst;
-	a.ttile = (const VgxTmplTile*)ctx->tmplTile.p;
+	a.ttile = ctx->tmplTile.ptr();
 	a.tile = ctx->tmplTileSize;
 	a.tiles_per_inst = (uint32_t)((ctx->tmplInst.num_elements + a.tile - 1) / a.tile);
 	a.caps = ctx->caps;
-	a.totals = (VgxTotals*)ctx->totals.p;
+	a.totals = ctx->totals.ptr();
 	a.general = ctx->tmplGeneral;
 	if (ctx->tmplClasses > 1) {
-		a.iinfo = (const VgxTmplInst*)ctx->tmplIinfo.p; a.wg = (const uint2*)ctx->tmplWg.p; a.num_wg = ctx->tmplNumWg;
-		a.cls = (const VgxTmplClass*)ctx->tmplCls.p; a.round_lds = ctx->tmplRoundLds;
+		a.iinfo = ctx->tmplIinfo.ptr(); a.wg = ctx->tmplWg.ptr(); a.num_wg = ctx->tmplNumWg;
+		a.cls = ctx->tmplCls.ptr(); a.round_lds = ctx->tmplRoundLds;
 		a.total = ctx->tmplTotal;
 	} else {
 		const vgx_sizes& i1 = ctx->tmplInst;
@@ -1688,7 +1717,7 @@ static int runTmpl(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 		const uint32_t aux = (nv > out->cap_vertices ? 1u : 0u) | (ni > out->cap_indices ? 2u : 0u) | ((out->meshes && nm > out->cap_meshes) ? 4u : 0u);
 		if (aux) {
 			const vgx_sizes z = a.total;
-			hipLaunchKernelGGL(k_tmpl_nospace, dim3(1), dim3(1), 0, s, (VgxTotals*)ctx->totals.p, z, aux);
+			hipLaunchKernelGGL(k_tmpl_nospace, dim3(1), dim3(1), 0, s, ctx->totals.ptr(), z, aux);
 			publish(ctx, dev_sizes, dev_status, s);
 			return launchStatus(ctx);
 		}
@@ -1697,12 +1726,12 @@ static int runTmpl(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 		// draw-command assembly: the partition kernels need the whole batch's mesh table and every mesh's draw in memory
 		const uint64_t nm = a.total.num_meshes;
 		int st;
-		if ((st = ensure(ctx, ctx->mtab, (nm + 1) * sizeof(vgx_mesh))) != VGX_OK) { return st; }
-		if ((st = ensure(ctx, ctx->mdesc, (nm + 1) * sizeof(VgxMeshDesc))) != VGX_OK) { return st; }
-		vgx_launch_tmpl_mtab(a, (vgx_mesh*)ctx->mtab.p, (VgxMeshDesc*)ctx->mdesc.p, s);
+		if ((st = ensure(ctx, ctx->mtab, nm + 1)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->mdesc, nm + 1)) != VGX_OK) { return st; }
+		vgx_launch_tmpl_mtab(a, ctx->mtab.ptr(), ctx->mdesc.ptr(), s);
 		mark(ctx, s, "tmpl_mesh_table");
 		if ((st = runAssemble(ctx, out, s, draws)) != VGX_OK) { return st; }
-		a.mesh_base = (const uint32_t*)ctx->meshBase.p;
+		a.mesh_base = ctx->meshBase.ptr();
 	}
 	vgx_launch_tmpl_emit(a, s);
 	mark(ctx, s, "tmpl_emit");
@@ -1754,10 +1783,10 @@ static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draw
 	ctx->tmplOn = false;
 	if (!ctx->optTmpl || !ctx->optInst || ctx->optTwoPass || (ndraws <= VGX_SMALL_DRAWS && !ctx->optTmplBatch) || ndraws == 0) { return VGX_OK; } // (static batches: frame-sized draw lists too)
 	int st;
-	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
-	vgx_launch_inst_detect(draws, ndraws, (VgxTotals*)ctx->totals.p, s);
-	vgx_launch_tmpl_check(draws, ndraws, ps->dev.npaths, (VgxTotals*)ctx->totals.p, s);
+	vgx_launch_inst_detect(draws, ndraws, ctx->totals.ptr(), s);
+	vgx_launch_tmpl_check(draws, ndraws, ps->dev.npaths, ctx->totals.ptr(), s);
 	if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
 	if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
 	ctx->tmplIsBatch = false;
@@ -1778,9 +1807,9 @@ static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draw
 	if (ctx->hostTotals->tmpl_bad) {
 		// not ONE period repeated. A few flavours of it? Candidates by hash of the template fields, then compared bit by bit.
 		if (!ctx->optTmplClasses || ninst > (1ull << 24)) { return VGX_OK; } // (per-instance tables: 40 bytes per instance and tile on host and device)
-		if ((st = ensure(ctx, ctx->tmplHash, ninst * sizeof(unsigned long long))) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->tmplHash, ninst)) != VGX_OK) { return st; }
 		noteHip(ctx, hipMemsetAsync(ctx->tmplHash.p, 0, ninst * sizeof(unsigned long long), s));
-		vgx_launch_tmpl_hash(draws, ndraws, P, (unsigned long long*)ctx->tmplHash.p, s);
+		vgx_launch_tmpl_hash(draws, ndraws, P, ctx->tmplHash.ptr(), s);
 		std::vector<unsigned long long> hashes(ninst);
 		HIPCHK(ctx, hipMemcpyAsync(hashes.data(), ctx->tmplHash.p, ninst * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 		HIPCHK(ctx, hipStreamSynchronize(s));
@@ -1800,22 +1829,22 @@ static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draw
 			instCls[k] = c;
 		}
 		T = (uint32_t)reps.size();
-		if ((st = ensure(ctx, ctx->tmplInstCls, ninst * sizeof(uint32_t))) != VGX_OK) { return st; }
-		if ((st = ensure(ctx, ctx->tmplClsRep, (size_t)T * sizeof(uint32_t))) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->tmplInstCls, ninst)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->tmplClsRep, (size_t)T)) != VGX_OK) { return st; }
 		HIPCHK(ctx, hipMemcpyAsync(ctx->tmplInstCls.p, instCls.data(), ninst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
 		HIPCHK(ctx, hipMemcpyAsync(ctx->tmplClsRep.p, reps.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-		noteHip(ctx, hipMemsetAsync(&((VgxTotals*)ctx->totals.p)->tmpl_bad, 0, sizeof(uint32_t), s));
-		vgx_launch_tmpl_check_cls(draws, ndraws, P, (const uint32_t*)ctx->tmplInstCls.p, (const uint32_t*)ctx->tmplClsRep.p, (VgxTotals*)ctx->totals.p, s);
+		noteHip(ctx, hipMemsetAsync(&ctx->totals.ptr()->tmpl_bad, 0, sizeof(uint32_t), s));
+		vgx_launch_tmpl_check_cls(draws, ndraws, P, ctx->tmplInstCls.ptr(), ctx->tmplClsRep.ptr(), ctx->totals.ptr(), s);
 		if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
 		if (ctx->hostTotals->tmpl_bad) { return VGX_OK; } // equal hashes, different records
 	}
 	// the class representatives' draw records, back to back (the saved records every step verifies the batch against)
 	const uint64_t PT = P * T;
-	if ((st = ensure(ctx, ctx->tmplDraws, (size_t)PT * sizeof(vgx_draw))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmplDraws, (size_t)PT)) != VGX_OK) { return st; }
 	for (uint32_t c = 0; c < T; ++c) {
-		HIPCHK(ctx, hipMemcpyAsync((vgx_draw*)ctx->tmplDraws.p + (uint64_t)c * P, draws + (uint64_t)reps[c] * P, (size_t)P * sizeof(vgx_draw), hipMemcpyDeviceToDevice, s));
+		HIPCHK(ctx, hipMemcpyAsync(ctx->tmplDraws.ptr() + (uint64_t)c * P, draws + (uint64_t)reps[c] * P, (size_t)P * sizeof(vgx_draw), hipMemcpyDeviceToDevice, s));
 	}
-	const vgx_draw* rdraws = (const vgx_draw*)ctx->tmplDraws.p;
+	const vgx_draw* rdraws = ctx->tmplDraws.ptr();
 	// sizes of one instance of every class (several classes: each representative through the pipeline on its own first)
 	// (several classes, round 6: NOT one pipeline per representative -- their sizes are differences of the prefixes the one concatenated
 	// run leaves behind, k_tmpl_class_sums below; the Tiger at seven scales = 18 classes: count 4.2 -> ~1 ms)
@@ -1835,16 +1864,16 @@ static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draw
 	const vgx_sizes all = ctx->hostTotals->sizes;
 	const bool general = ctx->hostTotals->has_general_stroke != 0;
 	const uint64_t M = all.num_meshes, E = all.num_elements, V = all.num_poly_vertices;
-	if ((st = ensure(ctx, ctx->tmplCls, ((size_t)T + 1) * sizeof(VgxTmplClass))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmplCls, (size_t)T + 1)) != VGX_OK) { return st; }
 	VgxTmplBuild b;
 	memset(&b, 0, sizeof(b));
 	// which stroke styles does the template hold? (decides the emit kernel and, with it, the tile size)
 	uint32_t styles = 0;
 	if (general) {
-		b.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; b.num_meshes = M; b.nclasses = T; b.cls = (VgxTmplClass*)ctx->tmplCls.p;
+		b.mdesc = ctx->mdesc.ptr(); b.num_meshes = M; b.nclasses = T; b.cls = ctx->tmplCls.ptr();
 		noteHip(ctx, hipMemsetAsync(ctx->tmplCls.p, 0, ((size_t)T + 1) * sizeof(VgxTmplClass), s));
 		vgx_launch_tmpl_styles(b, s);
-		HIPCHK(ctx, hipMemcpyAsync(&styles, &((VgxTmplClass*)ctx->tmplCls.p)[T].pad[0], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+		HIPCHK(ctx, hipMemcpyAsync(&styles, &ctx->tmplCls.ptr()[T].pad[0], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
 		HIPCHK(ctx, hipStreamSynchronize(s));
 	} else {
 		noteHip(ctx, hipMemsetAsync(ctx->tmplCls.p, 0, ((size_t)T + 1) * sizeof(VgxTmplClass), s));
@@ -1857,16 +1886,16 @@ static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draw
 	// sizes pass runs in its workgroup-per-instance shape; a batch that does not fit that shape takes the ordinary pipeline, see below)
 	uint32_t tileSize = ((kernelKind == 2u || kernelKind == 3u) && ctx->optTmplTile > VGX_TMPL_GENERAL_TILE) ? (uint32_t)VGX_TMPL_GENERAL_TILE : ctx->optTmplTile;
 	if ((kernelKind == 5u || kernelKind == 6u) && ctx->optTmplTile == VGX_TMPL_MAX_TILE) { tileSize = VGX_TMPL_RC_TILE; } // (its own workgroup shape; a VGX_TMPL_TILE override stands)
-	b.draws = rdraws; b.poly = (const float2*)ctx->poly.p; b.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; b.mprep = (const VgxMeshPrep*)ctx->mprep.p; b.mtab = (const vgx_mesh*)ctx->mtab.p;
-	b.prefix_fill = (const uint64_t*)ctx->elemPrefix.p; b.prefix_stroke = (const uint64_t*)ctx->elemPrefixS.p;
+	b.draws = rdraws; b.poly = (const float2*)ctx->poly.p; b.mdesc = ctx->mdesc.ptr(); b.mprep = ctx->mprep.ptr(); b.mtab = ctx->mtab.ptr();
+	b.prefix_fill = ctx->elemPrefix.ptr(); b.prefix_stroke = ctx->elemPrefixS.ptr();
 	b.num_meshes = M; b.num_elems = E; b.tile = tileSize; b.period = (uint32_t)P; b.nclasses = T;
-	b.num_vertices = all.num_vertices; b.num_indices = all.num_indices; b.cls = (VgxTmplClass*)ctx->tmplCls.p;
+	b.num_vertices = all.num_vertices; b.num_indices = all.num_indices; b.cls = ctx->tmplCls.ptr();
 	vgx_launch_tmpl_classes(b, s);
 	std::vector<VgxTmplClass> cls((size_t)T + 1);
 	std::vector<unsigned long long> csum(((size_t)T + 1) * 5, 0ull);
 	if (T > 1) {
-		if ((st = ensure(ctx, ctx->tmplClsSum, ((size_t)T + 1) * 5 * sizeof(unsigned long long))) != VGX_OK) { return st; }
-		vgx_launch_tmpl_class_sums(b, (const vgx_draw_info*)ctx->dinfo.p, (const uint64_t*)ctx->cmdPrefix.p, PT, all, (unsigned long long*)ctx->tmplClsSum.p, s);
+		if ((st = ensure(ctx, ctx->tmplClsSum, ((size_t)T + 1) * 5)) != VGX_OK) { return st; }
+		vgx_launch_tmpl_class_sums(b, ctx->dinfo.ptr(), (const uint64_t*)ctx->cmdPrefix.p, PT, all, ctx->tmplClsSum.ptr(), s);
 		HIPCHK(ctx, hipMemcpyAsync(csum.data(), ctx->tmplClsSum.p, csum.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 	}
 	HIPCHK(ctx, hipMemcpyAsync(cls.data(), ctx->tmplCls.p, ((size_t)T + 1) * sizeof(VgxTmplClass), hipMemcpyDeviceToHost, s));
@@ -1888,20 +1917,20 @@ static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draw
 		}
 	}
 	const uint64_t tiles = cls[T].tile0;
-	if ((st = ensure(ctx, ctx->tmplPoly, (V + 1) * 2 * sizeof(float))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplMesh, (M + 1) * sizeof(VgxTmplMesh))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplMtab, (M + 1) * sizeof(vgx_mesh))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplElem, (tiles * tileSize + 64) * sizeof(VgxTmplElem))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplTile, (tiles + 1) * sizeof(VgxTmplTile))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplTrmesh, (M + 2) * sizeof(VgxTmplRoundMesh))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplTmsz, (M + 1) * sizeof(uint2))) != VGX_OK) { return st; }
-	b.tmsz = (uint2*)ctx->tmplTmsz.p;
-	b.trmesh = (VgxTmplRoundMesh*)ctx->tmplTrmesh.p;
+	if ((st = ensure(ctx, ctx->tmplPoly, V + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmplMesh, M + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmplMtab, M + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmplElem, tiles * tileSize + 64)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmplTile, tiles + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmplTrmesh, M + 2)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmplTmsz, M + 1)) != VGX_OK) { return st; }
+	b.tmsz = ctx->tmplTmsz.ptr();
+	b.trmesh = ctx->tmplTrmesh.ptr();
 	b.has_round = roundTmpl ? 1u : 0u;
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
 	b.partial = (Sum3*)ctx->partial.p;
-	b.ttile = (VgxTmplTile*)ctx->tmplTile.p;
-	b.tmesh = (VgxTmplMesh*)ctx->tmplMesh.p; b.tmtab = (vgx_mesh*)ctx->tmplMtab.p; b.telem = (VgxTmplElem*)ctx->tmplElem.p;
+	b.ttile = ctx->tmplTile.ptr();
+	b.tmesh = ctx->tmplMesh.ptr(); b.tmtab = ctx->tmplMtab.ptr(); b.telem = ctx->tmplElem.ptr();
 	vgx_launch_tmpl_build(b, s);
 	HIPCHK(ctx, hipMemcpyAsync(ctx->tmplPoly.p, ctx->poly.p, V * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
 	// Round joins: how many such meshes the template holds and their elements; several classes: where each class's begin (k_tmpl_round_classes)
@@ -1913,7 +1942,7 @@ static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draw
 		roundWord = cls[T].pad[1];
 		if (roundWord == 0) { return VGX_OK; }
 		VgxTmplRoundMesh last;
-		HIPCHK(ctx, hipMemcpyAsync(&last, (const VgxTmplRoundMesh*)ctx->tmplTrmesh.p + roundWord, sizeof(last), hipMemcpyDeviceToHost, s));
+		HIPCHK(ctx, hipMemcpyAsync(&last, ctx->tmplTrmesh.ptr() + roundWord, sizeof(last), hipMemcpyDeviceToHost, s));
 		HIPCHK(ctx, hipStreamSynchronize(s));
 		roundElems = last.elem0;
 		roundLds = roundWord;
@@ -1966,8 +1995,8 @@ static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draw
 			const uint32_t c = instCls[k];
 			for (uint32_t t = cls[c].tile0; t < cls[c + 1].tile0; ++t) { wg[(size_t)cursor[c]++] = make_uint2((uint32_t)k, t); }
 		}
-		if ((st = ensure(ctx, ctx->tmplIinfo, (ninst + 1) * sizeof(VgxTmplInst))) != VGX_OK) { return st; }
-		if ((st = ensure(ctx, ctx->tmplWg, ((size_t)numWg + 1) * sizeof(uint2))) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->tmplIinfo, ninst + 1)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->tmplWg, (size_t)numWg + 1)) != VGX_OK) { return st; }
 		HIPCHK(ctx, hipMemcpyAsync(ctx->tmplIinfo.p, ii.data(), (ninst + 1) * sizeof(VgxTmplInst), hipMemcpyHostToDevice, s));
 		HIPCHK(ctx, hipMemcpyAsync(ctx->tmplWg.p, wg.data(), (size_t)numWg * sizeof(uint2), hipMemcpyHostToDevice, s));
 		HIPCHK(ctx, hipStreamSynchronize(s)); // the host vectors go away
@@ -2133,24 +2162,12 @@ int vgx_tessellate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 }
 
 // ---- immediate mode: vgx_tessellate_immediate / vgx_reserve -------------------------------------------------------------
-static int immInit(vgx_ctx* ctx)
-{
-	if (ctx->immHost) { return VGX_OK; }
-	HIPCHK(ctx, hipHostMalloc((void**)&ctx->immHost, sizeof(VgxTotals), hipHostMallocDefault));
-	const hipError_t e = hipEventCreateWithFlags(&ctx->immEv, hipEventDisableTiming);
-	if (e != hipSuccess) { (void)hipHostFree(ctx->immHost); ctx->immHost = nullptr; ctx->lastHipError = (int)e; return VGX_E_HIP; }
-	memset(ctx->immHost, 0, sizeof(VgxTotals));
-	ctx->immEvPending = false; ctx->immKnown = false; ctx->immLongKnown = false;
-	return VGX_OK;
-}
-
 // The mirror of the last immediate call, if its copy has landed (never waited for): what the batch was, and after VGX_E_GROWN the scratch it
 // needs -- grown here, the instanced flatten's heap included when its draws reuse paths
 static int immConsume(vgx_ctx* ctx, const vgx_pathset* ps)
 {
-	if (!ctx->immEvPending || hipEventQuery(ctx->immEv) != hipSuccess) { return VGX_OK; }
-	ctx->immEvPending = false;
-	const VgxTotals& h = *ctx->immHost;
+	if (!ctx->imm.landed()) { return VGX_OK; }
+	const VgxTotals& h = *ctx->imm.host;
 	if (h.status != VGX_OK && h.status != VGX_E_NOSPACE && h.status != VGX_E_GROWN) { return VGX_OK; } // (no totals to learn from)
 	const bool same = ctx->immKnown && ctx->immTag == ctx->immPendTag;
 	uint32_t P = 0;
@@ -2186,7 +2203,7 @@ int vgx_reserve(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals)
 	DeviceGuard guard(ctx);
 	if (totals->num_poly_vertices > 0xFFFFFFF0ull || totals->num_cmd_instances > 0xFFFFFFF0ull) { return VGX_E_RANGE; }
 	int st;
-	if ((st = immInit(ctx)) != VGX_OK) { return st; }
+	if ((st = ctx->imm.create(ctx, 1)) != VGX_OK) { return st; }
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
 	if ((st = ensureCmdScratch(ctx, totals->num_cmd_instances)) != VGX_OK) { return st; }
 	// the long sub-paths are not known: every vertex counted as one of them (the heap then holds any batch within these totals)
@@ -2203,7 +2220,7 @@ int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw
 	DeviceGuard guard(ctx);
 	hipStream_t s = (hipStream_t)stream;
 	int st;
-	if ((st = immInit(ctx)) != VGX_OK) { return st; }
+	if ((st = ctx->imm.create(ctx, 1)) != VGX_OK) { return st; }
 	// counted state ends here (as with vgx_flatten): the _emit pairing, the template, the routes the last count chose
 	ctx->lastStage = 0; ctx->f1Route = false;
 	forgetRoutes(ctx);
@@ -2216,7 +2233,7 @@ int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw
 	markBegin(ctx, s);
 	const uint64_t tag = ps->gen * 0x9E3779B97F4A7C15ull + ndraws;
 	const bool known = ctx->immKnown && ctx->immTag == tag;
-	VgxTotals* T = (VgxTotals*)ctx->totals.p;
+	VgxTotals* T = ctx->totals.ptr();
 	bool detect = false;
 	if (ndraws <= VGX_SMALL_DRAWS && !ctx->optNoSmall) {
 		// frame-sized: vgx_tessellate's five launches; the scan over the draws flags a batch that outgrew the context's tables
@@ -2255,7 +2272,7 @@ int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw
 		if (detect) {
 			vgx_launch_inst_detect(draws, ndraws, T, s);
 			if ((st = ensureInstGroup(ctx, ps->dev.npaths, 1, ndraws, false)) != VGX_OK) { return st; }
-			vgx_launch_inst_group(draws, ndraws, ps->dev.npaths, 1, (uint32_t*)ctx->instHist.p, nullptr, nullptr, (uint64_t*)ctx->instStart.p, (uint64_t*)ctx->instTaskStart.p,
+			vgx_launch_inst_group(draws, ndraws, ps->dev.npaths, 1, ctx->instHist.ptr(), nullptr, nullptr, ctx->instStart.ptr(), ctx->instTaskStart.ptr(),
 				nullptr, 0, nullptr, T, ctx->partial.p, s);
 		}
 		// the flatten stage checks the context's tables only: a VGX_E_NOSPACE here is the scratch's
@@ -2266,9 +2283,8 @@ int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw
 		vgx_launch_imm_publish(T, dev_sizes, dev_status, s);
 	}
 	// the totals to the mirror, for the next call (never waited for)
-	noteHip(ctx, hipMemcpyAsync(ctx->immHost, T, sizeof(VgxTotals), hipMemcpyDeviceToHost, s));
-	noteHip(ctx, hipEventRecord(ctx->immEv, s));
-	ctx->immEvPending = true; ctx->immPendTag = tag; ctx->immPendNDraws = ndraws; ctx->immPendDetect = detect;
+	ctx->imm.push(ctx, T, s);
+	ctx->immPendTag = tag; ctx->immPendNDraws = ndraws; ctx->immPendDetect = detect;
 	return launchStatus(ctx);
 }
 
@@ -2284,13 +2300,13 @@ int vgx_stroke_count(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpath
 	ctx->lastStage = 0;
 	int st;
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	// at most two meshes per vertex list: scratch can be sized without a device round trip
 	if ((st = ensureMeshBuffers(ctx, 0, 0, 2 * nsubpaths)) != VGX_OK) { return st; }
 	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
 	OpSubMeshes op;
 	op.subs = subpaths; op.subDraw = subpath_draw; op.draws = draws; op.nsubs = nsubpaths; op.ndraws = ndraws;
-	op.mdesc = (VgxMeshDesc*)ctx->mdesc.p; op.mtab = (vgx_mesh*)ctx->mtab.p; op.totals = (VgxTotals*)ctx->totals.p;
+	op.mdesc = ctx->mdesc.ptr(); op.mtab = ctx->mtab.ptr(); op.totals = ctx->totals.ptr();
 	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, nsubpaths);
 	mark(ctx, s, "scan_subpath_meshes");
 	VgxCaps outCaps = ctx->caps;
@@ -2336,13 +2352,13 @@ int vgx_stroke(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, con
 	ctx->tmplOn = false;
 	int st;
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	// at most two meshes per vertex list: scratch is sized without a device round trip
 	if ((st = ensureMeshBuffers(ctx, 0, 0, 2 * nsubpaths)) != VGX_OK) { return st; }
 	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
 	OpSubMeshes op;
 	op.subs = subpaths; op.subDraw = subpath_draw; op.draws = draws; op.nsubs = nsubpaths; op.ndraws = ndraws;
-	op.mdesc = (VgxMeshDesc*)ctx->mdesc.p; op.mtab = (vgx_mesh*)ctx->mtab.p; op.totals = (VgxTotals*)ctx->totals.p;
+	op.mdesc = ctx->mdesc.ptr(); op.mtab = ctx->mtab.ptr(); op.totals = ctx->totals.ptr();
 	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, nsubpaths);
 	mark(ctx, s, "scan_subpath_meshes");
 	runStrokeCount(ctx, draws, outCapsFor(ctx, out), 1, s, poly, false, out->meshes); // sizes, places, the caller's capacities, its mesh table
@@ -2367,21 +2383,11 @@ int vgx_dash_validate(const struct vgx_dash* dashes, uint64_t ndraws, const floa
 
 namespace {
 
-int dashHostMirror(vgx_ctx* ctx)
-{
-	if (ctx->dashHost) { return VGX_OK; }
-	HIPCHK(ctx, hipHostMalloc((void**)&ctx->dashHost, sizeof(unsigned long long), hipHostMallocDefault));
-	const hipError_t e = hipEventCreateWithFlags(&ctx->dashEv, hipEventDisableTiming);
-	if (e != hipSuccess) { (void)hipHostFree(ctx->dashHost); ctx->dashHost = nullptr; ctx->lastHipError = (int)e; return VGX_E_HIP; }
-	*ctx->dashHost = 0;
-	return VGX_OK;
-}
-
 int dashEnsureSegments(vgx_ctx* ctx, uint64_t segments)
 {
 	int st;
-	if ((st = ensure(ctx, ctx->dashG, (segments + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
-	return ensure(ctx, ctx->dashGhi, (segments + 1) * sizeof(uint64_t));
+	if ((st = ensure(ctx, ctx->dashG, segments + 1)) != VGX_OK) { return st; }
+	return ensure(ctx, ctx->dashGhi, segments + 1);
 }
 
 // everything but the launch: argument checks, scratch, the argument block
@@ -2394,30 +2400,26 @@ int dashPrepare(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, co
 	ctx->lastStage = 0;
 	ctx->tmplOn = false;
 	int st;
-	if ((st = dashHostMirror(ctx)) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	if ((st = ctx->dash.create(ctx, 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->dashPat, (ndraws + 1) * sizeof(VgxDashPat))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->dashLists, (nsubpaths + 1) * sizeof(VgxDashListRec))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dashPat, ndraws + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dashLists, nsubpaths + 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->dashRange, (4 * VGX_DASH_RANGES + 4) * sizeof(uint64_t))) != VGX_OK) { return st; }
 	// the segment tables: what the last call measured (once that has arrived), else what they hold, else a guess
 	uint64_t segments = segGuess;
-	if (ctx->dashEvPending && hipEventQuery(ctx->dashEv) == hipSuccess) {
-		ctx->dashEvPending = false;
-		if (*ctx->dashHost > segments) { segments = *ctx->dashHost; }
-	}
-	if (ctx->dashG.cap == 0 || segments + 1 > ctx->dashG.cap / sizeof(uint64_t)) {
+	if (ctx->dash.landed() && *ctx->dash.host > segments) { segments = *ctx->dash.host; }
+	if (ctx->dashG.cap == 0 || segments + 1 > ctx->dashG.items()) {
 		if ((st = dashEnsureSegments(ctx, segments)) != VGX_OK) { return st; }
 	}
 	memset(a, 0, sizeof(*a));
 	a->poly = poly; a->subs = subpaths; a->sub_draw = subpath_draw; a->nsubs = nsubpaths;
 	a->dashes = dashes; a->ndraws = ndraws; a->pattern = pattern; a->npattern = npattern;
-	a->pat = (VgxDashPat*)ctx->dashPat.p; a->lists = (VgxDashListRec*)ctx->dashLists.p;
-	a->G = (uint64_t*)ctx->dashG.p; a->Ghi = (uint64_t*)ctx->dashGhi.p;
-	const size_t capG = ctx->dashG.cap < ctx->dashGhi.cap ? ctx->dashG.cap : ctx->dashGhi.cap;
-	a->seg_cap = capG / sizeof(uint64_t) - 1;
+	a->pat = ctx->dashPat.ptr(); a->lists = ctx->dashLists.ptr();
+	a->G = ctx->dashG.ptr(); a->Ghi = ctx->dashGhi.ptr();
+	a->seg_cap = minOf({ ctx->dashG.items(), ctx->dashGhi.items() }) - 1;
 	a->range_sum = (uint64_t*)ctx->dashRange.p; a->range_off = a->range_sum + 2 * VGX_DASH_RANGES; a->tot = a->range_off + 2 * VGX_DASH_RANGES;
-	a->totals = (VgxTotals*)ctx->totals.p; a->partial = (Sum3*)ctx->partial.p;
+	a->totals = ctx->totals.ptr(); a->partial = (Sum3*)ctx->partial.p;
 	return VGX_OK;
 }
 
@@ -2428,9 +2430,7 @@ void dashLaunch(vgx_ctx* ctx, const VgxDashArgs& a, bool emit, hipStream_t s)
 	vgx_launch_dash(a, emit, s);
 	mark(ctx, s, emit ? "dash" : "dash_count");
 	// the segment count to the mirror, for the next call (never waited for)
-	noteHip(ctx, hipMemcpyAsync(ctx->dashHost, a.tot, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-	noteHip(ctx, hipEventRecord(ctx->dashEv, s));
-	ctx->dashEvPending = true;
+	ctx->dash.push(ctx, a.tot, s);
 }
 
 } // namespace
@@ -2479,17 +2479,6 @@ int vgx_dash(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const
 // ---- dashed strokes in frames: vgx_tessellate_dashed / vgx_reserve_dashed -------------------------------------------------------
 namespace {
 
-int dfInit(vgx_ctx* ctx)
-{
-	if (ctx->dfHost) { return VGX_OK; }
-	HIPCHK(ctx, hipHostMalloc((void**)&ctx->dfHost, 4 * sizeof(unsigned long long), hipHostMallocDefault));
-	const hipError_t e = hipEventCreateWithFlags(&ctx->dfEv, hipEventDisableTiming);
-	if (e != hipSuccess) { (void)hipHostFree(ctx->dfHost); ctx->dfHost = nullptr; ctx->lastHipError = (int)e; return VGX_E_HIP; }
-	memset(ctx->dfHost, 0, 4 * sizeof(unsigned long long));
-	ctx->dfEvPending = false;
-	return VGX_OK;
-}
-
 // The context's scratch for frames of `meshes` meshes (source meshes that stay + pieces), `pieces` pieces of `pieceVerts` vertices: the
 // tail of the polyline scratch (the flatten stage's heap keeps the vertices it has), both sets of mesh tables, the per-mesh lists, the
 // pieces' records. Grow-only, like every table of the context.
@@ -2500,24 +2489,22 @@ int dfEnsure(vgx_ctx* ctx, uint64_t meshes, uint64_t pieces, uint64_t pieceVerts
 	if (pieceVerts > ctx->pieceVerts) { ctx->pieceVerts = pieceVerts + pieceVerts / 8; }
 	if ((st = ensureMeshBuffers(ctx, heap, 1024, meshes > 1024 ? meshes : 1024)) != VGX_OK) { return st; }
 	const uint64_t m = ctx->caps.meshes + 1;
-	if ((st = ensure(ctx, ctx->mdesc2, m * sizeof(VgxMeshDesc))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->mprep2, m * sizeof(VgxMeshPrep))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->mtab2, m * sizeof(vgx_mesh))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->dfLists, m * sizeof(vgx_subpath))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->dfListDraw, m * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->dfDashedBefore, m * sizeof(uint64_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->dfPieceSubs, (pieces + 1) * sizeof(vgx_subpath))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->dfPieceDraw, (pieces + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->dfPieceSrc, (pieces + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->dfTotals, sizeof(VgxTotals))) != VGX_OK) { return st; }
-	return ensure(ctx, ctx->dfNeed, 4 * sizeof(uint64_t));
+	if ((st = ensure(ctx, ctx->mdesc2, m)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mprep2, m)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mtab2, m)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfLists, m)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfListDraw, m)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfDashedBefore, m)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfPieceSubs, pieces + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfPieceDraw, pieces + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfPieceSrc, pieces + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dfTotals, 1)) != VGX_OK) { return st; }
+	return ensure(ctx, ctx->dfNeed, 4);
 }
 
 uint64_t dfPieceCap(const vgx_ctx* ctx)
 {
-	uint64_t c = ctx->dfPieceSubs.cap / sizeof(vgx_subpath);
-	{ const uint64_t c2 = ctx->dfPieceDraw.cap / sizeof(uint32_t), c3 = ctx->dfPieceSrc.cap / sizeof(uint32_t); if (c2 < c) { c = c2; } if (c3 < c) { c = c3; } }
-	return c - 1;
+	return minOf({ ctx->dfPieceSubs.items(), ctx->dfPieceDraw.items(), ctx->dfPieceSrc.items() }) - 1;
 }
 
 } // namespace
@@ -2528,12 +2515,12 @@ int vgx_reserve_dashed(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals, c
 	int st;
 	if ((st = vgx_reserve(ctx, ndraws, totals)) != VGX_OK) { return st; }
 	DeviceGuard guard(ctx);
-	if ((st = dfInit(ctx)) != VGX_OK) { return st; }
-	if ((st = dashHostMirror(ctx)) != VGX_OK) { return st; }
+	if ((st = ctx->df.create(ctx, 4)) != VGX_OK) { return st; }
+	if ((st = ctx->dash.create(ctx, 1)) != VGX_OK) { return st; }
 	// every source mesh may stay (the frame's meshes + at most one dashed mesh without pieces per sub-path) and every piece is a mesh; a list
 	// has at most as many segments as vertices
 	if ((st = dfEnsure(ctx, totals->num_meshes + totals->num_subpaths + dash_totals->num_subpaths, dash_totals->num_subpaths, dash_totals->num_poly_vertices)) != VGX_OK) { return st; }
-	if (totals->num_poly_vertices + 1 > ctx->dashG.cap / sizeof(uint64_t) || totals->num_poly_vertices + 1 > ctx->dashGhi.cap / sizeof(uint64_t)) {
+	if (totals->num_poly_vertices + 1 > ctx->dashG.items() || totals->num_poly_vertices + 1 > ctx->dashGhi.items()) {
 		if ((st = dashEnsureSegments(ctx, totals->num_poly_vertices)) != VGX_OK) { return st; }
 	}
 	return VGX_OK;
@@ -2556,8 +2543,8 @@ int vgx_tessellate_dashed(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* d
 	DeviceGuard guard(ctx);
 	hipStream_t s = (hipStream_t)stream;
 	int st;
-	if ((st = immInit(ctx)) != VGX_OK) { return st; }
-	if ((st = dfInit(ctx)) != VGX_OK) { return st; }
+	if ((st = ctx->imm.create(ctx, 1)) != VGX_OK) { return st; }
+	if ((st = ctx->df.create(ctx, 4)) != VGX_OK) { return st; }
 	// counted state ends here, as with vgx_tessellate_immediate
 	ctx->lastStage = 0; ctx->f1Route = false;
 	forgetRoutes(ctx);
@@ -2565,20 +2552,17 @@ int vgx_tessellate_dashed(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* d
 	// (dashPrepare); (2) the tables every call needs (a fresh context gets small ones and learns the need from its first calls)
 	if ((st = immConsume(ctx, ps)) != VGX_OK) { return st; }
 	uint64_t needMeshes = 1024, needPieces = 4096, needPieceVerts = 16384;
-	if (ctx->dfEvPending && hipEventQuery(ctx->dfEv) == hipSuccess) {
-		ctx->dfEvPending = false;
-		if (ctx->dfHost[3]) { needPieces = ctx->dfHost[0]; needPieceVerts = ctx->dfHost[1]; needMeshes = ctx->dfHost[2] + ctx->dfHost[0]; }
-	}
+	if (ctx->df.landed() && ctx->df.host[3]) { needPieces = ctx->df.host[0]; needPieceVerts = ctx->df.host[1]; needMeshes = ctx->df.host[2] + ctx->df.host[0]; }
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
 	if ((st = ensureCmdScratch(ctx, 4096)) != VGX_OK) { return st; }
 	if ((st = dfEnsure(ctx, needMeshes, needPieces, needPieceVerts)) != VGX_OK) { return st; }
 	const uint64_t tag = ps->gen * 0x9E3779B97F4A7C15ull + ndraws;
 	const uint64_t segGuess = (ctx->immKnown && ctx->immTag == tag && ctx->immV > 65536) ? ctx->immV : 65536; // (segments <= vertices of the source lists)
 	VgxDashArgs a;
-	if ((st = dashPrepare(ctx, (const float*)ctx->poly.p, (const vgx_subpath*)ctx->dfLists.p, (const uint32_t*)ctx->dfListDraw.p, ctx->caps.meshes,
+	if ((st = dashPrepare(ctx, (const float*)ctx->poly.p, ctx->dfLists.ptr(), ctx->dfListDraw.ptr(), ctx->caps.meshes,
 	                      dashes, ndraws, pattern, npattern, segGuess, &a)) != VGX_OK) { return st; }
 	markBegin(ctx, s);
-	VgxTotals* T = (VgxTotals*)ctx->totals.p;
+	VgxTotals* T = ctx->totals.ptr();
 	// the flatten stage: k_flatten_build for any number of draws (its descriptors are complete and in frame order, the exact builder's included)
 	ctx->instPeriod = 0;
 	mark(ctx, s, "route_build");
@@ -2590,41 +2574,38 @@ int vgx_tessellate_dashed(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* d
 	VgxDashFrameArgs f;
 	memset(&f, 0, sizeof(f));
 	f.draws = draws; f.dashes = dashes;
-	f.mdesc = (const VgxMeshDesc*)ctx->mdesc.p; f.mtab = (const vgx_mesh*)ctx->mtab.p; f.mprep = (const VgxMeshPrep*)ctx->mprep.p;
-	f.mdesc2 = (VgxMeshDesc*)ctx->mdesc2.p; f.mtab2 = (vgx_mesh*)ctx->mtab2.p; f.mprep2 = (VgxMeshPrep*)ctx->mprep2.p;
-	f.lists = (vgx_subpath*)ctx->dfLists.p; f.list_draw = (uint32_t*)ctx->dfListDraw.p; f.dashed_before = (uint64_t*)ctx->dfDashedBefore.p;
-	f.need = (uint64_t*)ctx->dfNeed.p; f.nlists = f.need + 2; // (the join writes the same value there)
-	f.piece_subs = (const vgx_subpath*)ctx->dfPieceSubs.p; f.piece_src = (const uint32_t*)ctx->dfPieceSrc.p;
+	f.mdesc = ctx->mdesc.ptr(); f.mtab = ctx->mtab.ptr(); f.mprep = ctx->mprep.ptr();
+	f.mdesc2 = ctx->mdesc2.ptr(); f.mtab2 = ctx->mtab2.ptr(); f.mprep2 = ctx->mprep2.ptr();
+	f.lists = ctx->dfLists.ptr(); f.list_draw = ctx->dfListDraw.ptr(); f.dashed_before = ctx->dfDashedBefore.ptr();
+	f.need = ctx->dfNeed.ptr(); f.nlists = f.need + 2; // (the join writes the same value there)
+	f.piece_subs = ctx->dfPieceSubs.ptr(); f.piece_src = ctx->dfPieceSrc.ptr();
 	f.piece_base = ctx->caps.poly_vertices + 1;
 	f.cap_meshes = ctx->caps.meshes;
-	f.totals = T; f.dash_totals = (VgxTotals*)ctx->dfTotals.p;
+	f.totals = T; f.dash_totals = ctx->dfTotals.ptr();
 	f.dev_dash_sizes = dev_dash_sizes;
 	f.partial = (Sum3*)ctx->partial.p;
 	vgx_launch_dashframe_lists(f, s);
 	mark(ctx, s, "dashframe_lists");
 	a.totals = f.dash_totals;
 	a.nsubs_dev = f.nlists; a.frame = 1;
-	a.out_poly = (float*)ctx->poly.p + 2 * f.piece_base; a.out_subs = (vgx_subpath*)ctx->dfPieceSubs.p;
-	a.out_draw = (uint32_t*)ctx->dfPieceDraw.p; a.out_src = (uint32_t*)ctx->dfPieceSrc.p;
+	a.out_poly = (float*)ctx->poly.p + 2 * f.piece_base; a.out_subs = ctx->dfPieceSubs.ptr();
+	a.out_draw = ctx->dfPieceDraw.ptr(); a.out_src = ctx->dfPieceSrc.ptr();
 	a.cap_poly = ctx->pieceVerts; a.cap_subs = dfPieceCap(ctx); a.check_caps = 1;
 	dashLaunch(ctx, a, true, s);
 	// the frame's meshes by slot; from here on the second set of tables is the context's
 	vgx_launch_dashframe_place(f, s);
 	mark(ctx, s, "dashframe_place");
-	{ DevBuf t = ctx->mdesc; ctx->mdesc = ctx->mdesc2; ctx->mdesc2 = t; }
-	{ DevBuf t = ctx->mprep; ctx->mprep = ctx->mprep2; ctx->mprep2 = t; }
-	{ DevBuf t = ctx->mtab; ctx->mtab = ctx->mtab2; ctx->mtab2 = t; }
+	vgx_scratch_swap(ctx->scratch, ctx->mdesc, ctx->mdesc2);
+	vgx_scratch_swap(ctx->scratch, ctx->mprep, ctx->mprep2);
+	vgx_scratch_swap(ctx->scratch, ctx->mtab, ctx->mtab2);
 	if ((st = ensureMeshBuffers(ctx, 0, 0, 0)) != VGX_OK) { return st; } // (caps from the swapped tables: the sets may differ in head room)
 	runStrokeCount(ctx, draws, outCapsFor(ctx, out), 1, s, nullptr, true, out->meshes);
 	if ((st = runStrokeEmit(ctx, draws, out, s, nullptr, true)) != VGX_OK) { return st; }
 	vgx_launch_imm_publish(T, dev_sizes, dev_status, s);
 	// the totals and the pieces' need to the mirrors, for the next call (never waited for)
-	noteHip(ctx, hipMemcpyAsync(ctx->immHost, T, sizeof(VgxTotals), hipMemcpyDeviceToHost, s));
-	noteHip(ctx, hipEventRecord(ctx->immEv, s));
-	ctx->immEvPending = true; ctx->immPendTag = tag; ctx->immPendNDraws = ndraws; ctx->immPendDetect = false;
-	noteHip(ctx, hipMemcpyAsync(ctx->dfHost, ctx->dfNeed.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-	noteHip(ctx, hipEventRecord(ctx->dfEv, s));
-	ctx->dfEvPending = true;
+	ctx->imm.push(ctx, T, s);
+	ctx->immPendTag = tag; ctx->immPendNDraws = ndraws; ctx->immPendDetect = false;
+	ctx->df.push(ctx, ctx->dfNeed.p, s);
 	return launchStatus(ctx);
 }
 
@@ -2660,22 +2641,22 @@ int vgx_cache_submit(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_
 	markBegin(ctx, s);
 	ctx->lastStage = 0;
 	int st;
-	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
 	// the three instance prefix arrays share one scratch buffer; the output mesh table lives in the mesh-table scratch
 	if ((st = ensure(ctx, ctx->cmdPrefix, 3 * (ninst + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
 	// the internal mesh table must hold every output mesh even when the caller does not want the table
 	uint64_t meshCap = out->meshes ? out->cap_meshes : cache->num_meshes * ninst;
 	if (meshCap == 0) { meshCap = 1; }
-	if ((st = ensure(ctx, ctx->mtab, (meshCap + 1) * sizeof(vgx_mesh))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mtab, meshCap + 1)) != VGX_OK) { return st; }
 	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
 	uint64_t* prefix = (uint64_t*)ctx->cmdPrefix.p;
 	OpCacheInst op;
 	op.cache = *cache; op.inst = instances; op.ninst = ninst;
 	op.meshPrefix = prefix; op.vertPrefix = prefix + (ninst + 1); op.idxPrefix = prefix + 2 * (ninst + 1);
-	op.totals = (VgxTotals*)ctx->totals.p;
+	op.totals = ctx->totals.ptr();
 	op.caps = ctx->caps;
-	op.caps.meshes = ctx->mtab.cap / sizeof(vgx_mesh) - 1;
+	op.caps.meshes = ctx->mtab.items() - 1;
 	if (out->meshes && out->cap_meshes < op.caps.meshes) { op.caps.meshes = out->cap_meshes; }
 	op.caps.vertices = out->cap_vertices; op.caps.indices = out->cap_indices;
 	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, ninst);
@@ -2683,15 +2664,15 @@ int vgx_cache_submit(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_
 	VgxCacheArgs a;
 	a.cache = *cache; a.inst = instances; a.ninst = ninst;
 	a.inst_mesh_prefix = op.meshPrefix; a.inst_vert_prefix = op.vertPrefix; a.inst_idx_prefix = op.idxPrefix;
-	a.mtab = (vgx_mesh*)ctx->mtab.p; a.meshes_out = out->meshes;
+	a.mtab = ctx->mtab.ptr(); a.meshes_out = out->meshes;
 	a.pos = out->pos; a.color = out->color; a.idx = out->idx;
 	a.mesh_base = nullptr;
-	a.totals = (VgxTotals*)ctx->totals.p;
+	a.totals = ctx->totals.ptr();
 	vgx_launch_cache_meshes(a, s);
 	mark(ctx, s, "cache_meshes");
 	if (ctx->asmArmed) {
 		if ((st = runAssemble(ctx, out, s)) != VGX_OK) { return st; }
-		a.mesh_base = (const uint32_t*)ctx->meshBase.p;
+		a.mesh_base = ctx->meshBase.ptr();
 	}
 	vgx_launch_cache_copy(a, vgxElementGrid(out->cap_vertices), s);
 	mark(ctx, s, "cache_copy");
@@ -2736,7 +2717,7 @@ int vgx_cache_cull(vgx_ctx* ctx, const vgx_cache_desc* cache, const float* mesh_
 	memset(&a, 0, sizeof(a));
 	a.cache_meshes = cache->num_meshes; a.mesh_bounds = mesh_bounds; a.inst = inst; a.ninst = ninst;
 	a.views = views; a.nviews = nviews; a.wave_min = ctx->optCullWaveMin; a.inst_view = inst_view;
-	a.out_inst = out->inst; a.out_bounds = out->bounds; a.flags = compact ? (uint8_t*)ctx->cullFlags.p : nullptr; a.status = dev_status;
+	a.out_inst = out->inst; a.out_bounds = out->bounds; a.flags = compact ? ctx->cullFlags.ptr() : nullptr; a.status = dev_status;
 	vgx_launch_cache_cull(a, out->kept, out->num_kept, ctx->cullPartial.p, s);
 	return launchStatus(ctx);
 }
@@ -2758,23 +2739,23 @@ int vgx_pick(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds
 	hipStream_t s = (hipStream_t)stream;
 	const uint64_t nm = frame->num_meshes;
 	int st;
-	if ((st = ensure(ctx, ctx->pickKeys, VGX_PICK_MAX_QUERIES * sizeof(uint64_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->pickTris, (nm + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->pickCand, (nm + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->pickPrefix, (nm + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->pickTotals, 2 * sizeof(uint64_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickKeys, VGX_PICK_MAX_QUERIES)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickTris, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickCand, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickPrefix, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickTotals, 2)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->pickPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
 	if (!mesh_bounds && nm) {
-		if ((st = ensure(ctx, ctx->pickBounds, nm * 4 * sizeof(float))) != VGX_OK) { return st; }
-		vgx_launch_mesh_bounds(frame->pos, frame->meshes, nm, (float*)ctx->pickBounds.p, s);
-		mesh_bounds = (const float*)ctx->pickBounds.p;
+		if ((st = ensure(ctx, ctx->pickBounds, nm * 4)) != VGX_OK) { return st; }
+		vgx_launch_mesh_bounds(frame->pos, frame->meshes, nm, ctx->pickBounds.ptr(), s);
+		mesh_bounds = ctx->pickBounds.ptr();
 	}
 	VgxPickArgs a;
 	memset(&a, 0, sizeof(a));
 	a.pos = frame->pos; a.color = frame->color; a.idx = frame->idx; a.meshes = frame->meshes; a.num_meshes = nm;
 	a.mesh_bounds = mesh_bounds; a.queries = queries; a.nqueries = nqueries; a.hits = hits;
-	a.keys = (uint64_t*)ctx->pickKeys.p; a.cand_tris = (uint32_t*)ctx->pickTris.p; a.cand_mesh = (uint32_t*)ctx->pickCand.p;
-	a.cand_prefix = (uint64_t*)ctx->pickPrefix.p; a.totals = (uint64_t*)ctx->pickTotals.p;
+	a.keys = ctx->pickKeys.ptr(); a.cand_tris = ctx->pickTris.ptr(); a.cand_mesh = ctx->pickCand.ptr();
+	a.cand_prefix = ctx->pickPrefix.ptr(); a.totals = ctx->pickTotals.ptr();
 	vgx_launch_pick(a, ctx->pickPartial.p, ctx->optPickGrid, s);
 	return launchStatus(ctx);
 }
@@ -2848,25 +2829,25 @@ int vgx_merge_uv(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b,
 	ctx->lastStage = 0;
 	ctx->tmplOn = false; // the mesh-table scratch is re-sized below
 	int st;
-	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->mtab, (n + 1) * sizeof(vgx_mesh))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->mdesc, (n + 1) * sizeof(VgxMeshDesc))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mtab, n + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mdesc, n + 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->cmdPrefix, (n + 1) * sizeof(uint64_t))) != VGX_OK) { return st; } // the merged order lives in the command-prefix scratch
 	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
 	VgxMergeArgs m;
 	memset(&m, 0, sizeof(m));
 	m.a = *a; m.b = *b; m.b_draw = b_draw;
-	m.order = (uint32_t*)ctx->cmdPrefix.p; m.mtab = (vgx_mesh*)ctx->mtab.p; m.mdesc = (VgxMeshDesc*)ctx->mdesc.p;
+	m.order = (uint32_t*)ctx->cmdPrefix.p; m.mtab = ctx->mtab.ptr(); m.mdesc = ctx->mdesc.ptr();
 	m.meshes_out = out->meshes; m.pos = out->pos; m.color = out->color; m.idx = out->idx; m.mesh_base = nullptr;
-	m.totals = (VgxTotals*)ctx->totals.p;
+	m.totals = ctx->totals.ptr();
 	m.caps = ctx->caps; m.caps.vertices = out->cap_vertices; m.caps.indices = out->cap_indices; m.caps.meshes = out->cap_meshes;
 	vgx_launch_merge_rank(m, s);
 	vgx_launch_merge_scan(m, ctx->partial.p, s);
 	mark(ctx, s, "merge_scan");
 	if (ctx->asmArmed) {
 		if ((st = runAssemble(ctx, out, s, draws)) != VGX_OK) { return st; }
-		m.mesh_base = (const uint32_t*)ctx->meshBase.p;
+		m.mesh_base = ctx->meshBase.ptr();
 		if (b_uv && ctx->asmCfg.uv && ctx->asmCfg.uv_bytes) { m.b_uv = b_uv; m.uv_out = ctx->asmCfg.uv; m.uv_bytes = ctx->asmCfg.uv_bytes; }
 	}
 	vgx_launch_merge_copy(m, s);
@@ -2924,13 +2905,13 @@ int vgx_concave_emit(vgx_ctx* ctx, const float* contour_verts, uint64_t num_cont
 	markBegin(ctx, s);
 	ctx->lastStage = 0;
 	int st;
-	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->mtab, (nfills + 1) * sizeof(vgx_mesh))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->mtab, nfills + 1)) != VGX_OK) { return st; }
 	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
 	OpConcaveFills op;
 	op.contours = contours; op.ncontours = ncontours; op.fills = fills; op.nfills = nfills;
-	op.mtab = (vgx_mesh*)ctx->mtab.p; op.meshesOut = out->meshes; op.totals = (VgxTotals*)ctx->totals.p;
+	op.mtab = ctx->mtab.ptr(); op.meshesOut = out->meshes; op.totals = ctx->totals.ptr();
 	op.caps = ctx->caps;
 	op.caps.vertices = out->cap_vertices; op.caps.indices = out->cap_indices; op.caps.meshes = out->meshes ? out->cap_meshes : ~0ull;
 	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, nfills);
@@ -2939,8 +2920,8 @@ int vgx_concave_emit(vgx_ctx* ctx, const float* contour_verts, uint64_t num_cont
 	memset(&a, 0, sizeof(a));
 	a.contour_verts = contour_verts; a.contours = contours; a.ncontours = ncontours; a.num_contour_vertices = num_contour_vertices;
 	a.fills = fills; a.nfills = nfills; a.tess_pos = tess_pos; a.tess_idx = tess_idx;
-	a.mtab = (const vgx_mesh*)ctx->mtab.p; a.pos = out->pos; a.color = out->color; a.idx = out->idx;
-	a.totals = (VgxTotals*)ctx->totals.p;
+	a.mtab = ctx->mtab.ptr(); a.pos = out->pos; a.color = out->color; a.idx = out->idx;
+	a.totals = ctx->totals.ptr();
 	vgx_launch_concave_emit(a, s);
 	mark(ctx, s, "concave_emit");
 	publish(ctx, dev_sizes, dev_status, s);
@@ -2966,17 +2947,17 @@ int vgx_text_quads(vgx_ctx* ctx, const float* quads, uint64_t nquads, const vgx_
 	markBegin(ctx, s);
 	ctx->lastStage = 0;
 	int st;
-	if ((st = ensure(ctx, ctx->totals, sizeof(VgxTotals))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	VgxTextArgs a;
 	memset(&a, 0, sizeof(a));
 	a.quads = quads; a.nquads = nquads; a.runs = runs; a.nruns = nruns; a.first_mesh = first_mesh;
 	a.pos = out->pos; a.color = out->color; a.idx = out->idx; a.meshes = out->meshes;
 	a.uv = uv_bytes ? out_uv : nullptr; a.uv_bytes = uv_bytes;
 	a.cap_vertices = out->cap_vertices; a.cap_indices = out->cap_indices; a.cap_meshes = out->cap_meshes;
-	a.totals = (VgxTotals*)ctx->totals.p;
+	a.totals = ctx->totals.ptr();
 	if (nruns > 4096 || nquads > 65536) { // beyond a frame's size: the run kernel writes the first run of every tile of 256 quads
-		if ((st = ensure(ctx, ctx->textTiles, (nquads / 256 + 1) * sizeof(uint32_t))) != VGX_OK) { return st; }
-		a.tile_run = (uint32_t*)ctx->textTiles.p;
+		if ((st = ensure(ctx, ctx->textTiles, nquads / 256 + 1)) != VGX_OK) { return st; }
+		a.tile_run = ctx->textTiles.ptr();
 	}
 	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
 	vgx_launch_text_quads(a, s);
@@ -3187,15 +3168,14 @@ extern "C" int vgx_gather_sizes(vgx_ctx* ctx, void* rccl_comm, const vgx_rank_si
 	// five words per rank: the four totals + the rank's transfer piece size. The piece size is part of the wire protocol of
 	// vgx_gather_at (sender and root must cut a stream into the same pieces) but comes from each process's own environment
 	// (VGX_GATHER_CHUNK_MB): ranks that disagree are told here, before a gather could hang on mismatched Send / Recv sizes.
-	struct Wire { vgx_rank_sizes z; uint64_t chunk; };
-	if ((st = ensure(ctx, ctx->gatherSizes, (size_t)nranks * sizeof(Wire))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->gatherSizes, (size_t)nranks)) != VGX_OK) { return st; }
 	hipStream_t s = (hipStream_t)stream;
-	Wire* dev = (Wire*)ctx->gatherSizes.p;
-	std::vector<Wire> host((size_t)nranks);
+	VgxGatherWire* dev = ctx->gatherSizes.ptr();
+	std::vector<VgxGatherWire> host((size_t)nranks);
 	host[(size_t)rank].z = *mine; host[(size_t)rank].chunk = gatherChunkBytes();
-	HIPCHK(ctx, hipMemcpyAsync(dev + rank, &host[(size_t)rank], sizeof(Wire), hipMemcpyHostToDevice, s));
+	HIPCHK(ctx, hipMemcpyAsync(dev + rank, &host[(size_t)rank], sizeof(VgxGatherWire), hipMemcpyHostToDevice, s));
 	RCCLCHK(ctx, ctx->rccl->AllGather(dev + rank, dev, 5, kNcclUint64, rccl_comm, s)); // in place: my slot is my send buffer
-	HIPCHK(ctx, hipMemcpyAsync(host.data(), dev, (size_t)nranks * sizeof(Wire), hipMemcpyDeviceToHost, s));
+	HIPCHK(ctx, hipMemcpyAsync(host.data(), dev, (size_t)nranks * sizeof(VgxGatherWire), hipMemcpyDeviceToHost, s));
 	HIPCHK(ctx, hipStreamSynchronize(s));
 	for (int r = 0; r < nranks; ++r) {
 		all[r] = host[(size_t)r].z;
