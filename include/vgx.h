@@ -641,6 +641,81 @@ typedef struct vgx_pick_hit   { uint32_t mesh, triangle, draw, subpath_kind; } v
 int vgx_pick(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
              const vgx_pick_query* queries, uint32_t nqueries, vgx_pick_hit* hits, void* stream);
 
+/* ---- rendering to an image (beyond the reference): vgx_mesh_bounds -> vgx_raster ------------------------------------------------
+ * What does this frame look like? The reference hands its triangles to bgfx (src/vg.cpp:1221-1290); a compute part has no graphics
+ * pipeline, and the frame lives in device memory only. vgx_raster draws the meshes [mesh_begin, min(mesh_end, num_meshes)) of `frame`
+ * into an RGBA8 image in device memory. `frame` is what vgx_pick accepts: any mesh stream the library wrote with mesh-LOCAL indices
+ * (streams written under vgx_set_assembly are OUT OF SCOPE), under the ascending precondition of vgx_mesh_bounds. With the mesh range
+ * and the scissor a caller replays draw commands one after another. The rule below is written so that every implementation gives the
+ * same bytes; there is no tolerance anywhere. All pointers of the frame and the target are DEVICE pointers.
+ *
+ * Triangles. Enumerated as in vgx_pick: triangle t of mesh m is idx[first_index + 3t .. +3), t < num_indices / 3.
+ *   - A trailing remainder of the index list (num_indices % 3) is ignored.
+ *   - A triangle with an index >= num_vertices is skipped, so nothing outside the mesh's own vertex range is ever read.
+ *   - Meshes of kind VGX_MESH_TEXT and VGX_MESH_TRILIST are skipped whole: they need a texture. Atlas sampling, gradients, image
+ *     patterns and stencil clips stay with the display path.
+ * Sample. Pixel (i, j) of the image samples the frame at px = (double)(x0 + i) + 0.5, py = (double)(y0 + j) + 0.5. Both are exact.
+ * Coverage. Everything in binary64 WITHOUT FMA, vertex coordinates widened first. Let the vertices be a, b, c (binary32).
+ *   - Box: px >= min(ax,bx,cx) && px <= max(ax,bx,cx) && py >= min(ay,by,cy) && py <= max(ay,by,cy). A NaN makes it false.
+ *   - Canonical edge function of a directed edge u->v. Let lo, hi be the two endpoints ordered by (x, then y) as binary32 values
+ *     (lo = u when u.x < v.x, or u.x == v.x and u.y <= v.y). g = (hi.x-lo.x)*(py-lo.y) - (hi.y-lo.y)*(px-lo.x). The edge value is
+ *     g when u is lo, else -g; it is 0 when u == v bit for bit. Two triangles that share an edge compute the SAME g, so their two
+ *     values are exact negatives of each other whatever rounds: no sample on or near a shared edge is covered twice or not at all
+ *     along that edge.
+ *   - When is the sign also the exact geometric sign? By the argument of vgx_pick: each difference of two binary32 values whose
+ *     exponents lie within 29 of each other is exact in binary64 (the sample is a binary32 value too while |x0 + i| < 2^23), and
+ *     where the two differences of a product have no more than 53 significant bits together (24 + 24 when the four values share
+ *     a binade, as the corners of a tessellated triangle and a pixel centre near them do) both products are exact; the sign of the
+ *     rounded difference of two exact values is its exact sign. Outside that range every implementation still rounds the same way;
+ *     only the geometric guarantee is lost, the seam property above is not.
+ *   - A = (bx-ax)*(cy-ay) - (by-ay)*(cx-ax). A == 0 or NaN: the triangle covers nothing. s = +1 for A > 0, else -1.
+ *     E0 = s * value(a->b), E1 = s * value(b->c), E2 = s * value(c->a).
+ *   - Edge k with oriented direction (dx, dy) = s * (v - u) accepts the sample iff Ek > 0, or Ek == 0 && (dy > 0 || (dy == 0 &&
+ *     dx < 0)). Of the two directions of a shared edge exactly one takes the tie.
+ *   - S = (E0 + E1) + E2. Covered iff the box holds, all three edges accept, and S > 0.
+ * Colour at a covered sample. For each of the four 8-bit channels with the vertex values ca, cb, cc: v = ((E1*ca + E2*cb) + E0*cc) / S,
+ *   q = min((uint32)(v + 0.5), 255). A mesh with one colour on all vertices (the non-AA kinds) gets exactly that colour: every
+ *   operation rounds within 2^-53, so v = c * (1 + e) with |e| < 2^-49, |v - c| < 2^-41, far below the 0.5 that would change q.
+ * Blend. The reference's state, BLEND_FUNC_SEPARATE(SRC_ALPHA, INV_SRC_ALPHA, ONE, INV_SRC_ALPHA) (src/vg.cpp:1244-1247), on UNORM8 in
+ *   integers, a = the source alpha q, div255(x) = (x + 127) / 255:   RGB d' = div255(s*a + d*(255-a))   A d' = div255(255*a + d*(255-a)).
+ *   That is round-to-nearest of the real value (255 is odd: no ties). a == 0 leaves the pixel as it is.
+ * Order. A pixel receives its covering triangles in ascending (mesh, triangle) order: painter's order. The image is a function of
+ *   that order alone, so every run gives the same bytes.
+ * mesh_bounds. As in vgx_pick: what vgx_mesh_bounds gave for this stream, or NULL (the call computes the boxes of the range into
+ *   scratch of its own). A prefilter that changes no result, because the rule starts with the triangle's own box; a NaN bound is
+ *   taken as no bound.
+ * Target. pixels[j * stride + i], 0xAABBGGRR like every colour of this ABI. Only pixels inside image and scissor are ever written;
+ *   with VGX_RASTER_CLEAR every such pixel is set to clear_color first.
+ * dev_status (DEVICE uint32, may be NULL).
+ *   VGX_OK       done.
+ *   VGX_E_GROWN  the context's bin scratch was too small (4 x 4 bytes per bin entry = per pair of a mesh and a 16 x 16 tile its box
+ *                reaches inside the scissor). NOTHING of the image was written, the clear included. The need went to the context
+ *                through a pinned mirror, the next call grows the scratch first: the same call repeated -- dev_status read in
+ *                between -- reaches VGX_OK on the second try, or on the first after vgx_raster_reserve. A fresh context holds one
+ *                entry per mesh of the range (and the 12.5 % head room of every scratch table).
+ *   VGX_E_RANGE  more than 2^32 - 1 triangles or bin entries in the range. Nothing was written.
+ * Host return values. VGX_OK once the work is enqueued. VGX_E_INVALID_ARG for null ctx / frame / target, null or misaligned pointers
+ *   (mesh_bounds 16-byte; pos 8-byte; pixels, color, dev_status 4-byte; idx 2-byte; meshes 8-byte), stride < width, width or height
+ *   above 16384, |x0| or |y0| above 2^23, a scissor outside the image or inverted. VGX_E_RANGE for num_meshes >= 2^32 - 1. VGX_E_HIP
+ *   for a HIP failure. An empty scissor, width * height == 0 or an empty mesh range is valid and writes nothing, or only the clear.
+ * Side effects. Nothing but pixels inside image and scissor and dev_status is written. Asynchronous. Uses scratch of its own (12 bytes
+ *   per mesh of the range, 28 with mesh_bounds == NULL, 16 per bin entry and the sort's temporary storage; vgx_scratch_bytes counts
+ *   it), so a counted state survives: vgx_tessellate_count -> vgx_raster of another stream -> vgx_tessellate_emit works.
+ * vgx_raster_reserve sizes that scratch ahead for ranges of up to num_meshes meshes and num_bin_entries bin entries. */
+enum { VGX_RASTER_CLEAR = 1u };
+typedef struct vgx_raster_target {
+	uint32_t* pixels;          /* DEVICE [height][stride], 0xAABBGGRR like every colour of this ABI; 4-byte aligned */
+	uint32_t width, height, stride;   /* pixels; stride >= width; width, height <= 16384 */
+	int32_t  x0, y0;           /* pixel (i, j) samples the frame at (x0 + i + 0.5, y0 + j + 0.5); |x0|, |y0| <= 2^23 */
+	uint32_t scissor[4];       /* sx0, sy0, sx1, sy1 in image pixels, half open; pixels outside are never written */
+	uint32_t flags;            /* VGX_RASTER_CLEAR: every pixel inside the scissor is set to clear_color first */
+	uint32_t clear_color;
+} vgx_raster_target;
+int vgx_raster(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
+               uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_target* target,
+               uint32_t* dev_status, void* stream);
+int vgx_raster_reserve(vgx_ctx* ctx, uint64_t num_meshes, uint64_t num_bin_entries);
+
 /* ---- incremental update (beyond the reference): vgx_cache_submit -> vgx_cache_layout -> [vgx_pick -> edit -> vgx_cache_update]* ----
  * Moving or recolouring an instance of a submitted frame changes nothing of the frame's structure: a cached mesh has a fixed size, so
  * the instance keeps its vertex, index and mesh ranges; indices, mesh records, draw commands and UVs do not depend on the transform.

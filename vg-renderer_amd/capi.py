@@ -136,6 +136,16 @@ PICK_SKIP_TRANSPARENT = 1
 PICK_NONE = 0xFFFFFFFF  # every word of a hit record that hit nothing; vgx_pick_query.mesh_end: all meshes
 
 
+class RasterTarget(C.Structure):  # vgx_raster_target: `pixels` is a device pointer
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("stride", C.c_uint32), ("x0", C.c_int32), ("y0", C.c_int32),
+                ("scissor", C.c_uint32 * 4), ("flags", C.c_uint32), ("clear_color", C.c_uint32)]
+
+
+assert C.sizeof(RasterTarget) == 56
+RASTER_CLEAR = 1
+RASTER_TILE = 16  # a bin entry is a pair of a mesh and a tile of this many pixels a side
+
+
 cache_slot_dtype = np.dtype([("first_mesh", "<u8"), ("first_vertex", "<u8"), ("first_index", "<u8"), ("cache_first_mesh", "<u8")])  # struct vgx_cache_slot
 assert cache_slot_dtype.itemsize == 32
 
@@ -231,6 +241,8 @@ VGX_SYMBOLS = {
     "vgx_cache_cull": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
                                  C.POINTER(CullOut), C.c_void_p, C.c_void_p]),
     "vgx_pick": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vgx_raster": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
+    "vgx_raster_reserve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
     "vgx_cache_layout": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_cache_update": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                    C.POINTER(UpdateFrame), C.c_void_p, C.c_void_p]),

@@ -18,6 +18,7 @@
 #include "vgx_mscan.h"
 #include "vgx_dash.h"
 #include "vgx_update.h"
+#include "vgx_raster.h"
 #include "vgx_scratch.h"
 #include <vector>
 #include <algorithm>
@@ -111,6 +112,12 @@ struct vgx_ctx
 	Buf<uint8_t> cullFlags; DevBuf cullPartial; // vgx_cache_cull (vgx_bounds.hip): kept flag per instance, the compaction scan's slice sums (views: as `partial`). Its own: a counted state survives the call
 	Buf<uint64_t> pickKeys, pickPrefix, pickTotals; Buf<uint32_t> pickTris, pickCand; Buf<float> pickBounds; DevBuf pickPartial; // vgx_pick (vgx_pick.hip); pickPartial: slice sums (views: as `partial`). Its own: a counted state survives the call
 	DevBuf updPrefix, updPartial;        // vgx_cache_layout / vgx_cache_update (vgx_update.hip); views: updPrefix = uint32_t flag word in 16 bytes, then 2 x uint64_t[ndirty + 1] prefix sums of the listed entries; updPartial = slice sums, as `partial`. Their own: a counted state survives the calls
+	// vgx_raster (vgx_raster.hip): per mesh of the range its bin entries and its first entry; the (tile, mesh) entries in mesh order and
+	// in tile order; the sort's temporary storage; status and entry count of the last call with their pinned mirror (as `dash`: a call
+	// whose entries outgrew the tables ends with VGX_E_GROWN and the next one grows first). Its own: a counted state survives the call
+	Buf<uint32_t> rasMeshEntries, rasKeys, rasVals, rasSortedKeys, rasSortedVals; Buf<uint64_t> rasMeshFirst; Buf<unsigned long long> rasState; Buf<float> rasBounds;
+	DevBuf rasSortTemp, rasPartial;      // rasPartial: slice sums (views: as `partial`)
+	HostMirror<unsigned long long> ras;
 	uint32_t optPickGrid;                // workgroups of k_pick_tris (VGX_PICK_GRID)
 	uint32_t optCullWaveMin;             // mesh ranges of at least this many boxes are united by the whole wave; >= 1, 2^32 - 1 = never = the default (VGX_CULL_WAVE_MIN)
 	// vgx_dash (vgx_dash.hip): per-draw patterns, per-list records, per-segment prefix sums (S and the overflow guard), per-range sums; the
@@ -1059,7 +1066,7 @@ int vgx_destroy(vgx_ctx* ctx)
 	vgx_scratch_release(ctx->scratch);
 	if (ctx->hostTotals) { (void)hipHostFree(ctx->hostTotals); }
 	if (ctx->hostF1) { (void)hipHostFree(ctx->hostF1); }
-	ctx->imm.release(); ctx->dash.release(); ctx->df.release();
+	ctx->imm.release(); ctx->dash.release(); ctx->df.release(); ctx->ras.release();
 	if (ctx->hostPs) { (void)hipHostFree(ctx->hostPs); }
 	if (ctx->psImage) { (void)hipHostFree(ctx->psImage); }
 	for (int i = 0; i < VGX_PS_POOL; ++i) { if (ctx->psPool[i].p) { (void)hipFree(ctx->psPool[i].p); } }
@@ -2757,6 +2764,98 @@ int vgx_pick(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds
 	a.keys = ctx->pickKeys.ptr(); a.cand_tris = ctx->pickTris.ptr(); a.cand_mesh = ctx->pickCand.ptr();
 	a.cand_prefix = ctx->pickPrefix.ptr(); a.totals = ctx->pickTotals.ptr();
 	vgx_launch_pick(a, ctx->pickPartial.p, ctx->optPickGrid, s);
+	return launchStatus(ctx);
+}
+
+// ---- rendering to an image (vgx_raster.hip) ---------------------------------------------------------------------------------
+// Scratch of its own, like the picking call: count -> vgx_raster -> emit still works.
+namespace {
+
+int rasterEnsure(vgx_ctx* ctx, uint64_t meshes, uint64_t entries)
+{
+	int st;
+	if ((st = ensure(ctx, ctx->rasState, 2)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rasPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rasMeshEntries, meshes + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rasMeshFirst, meshes + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rasKeys, entries + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rasVals, entries + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rasSortedKeys, entries + 1)) != VGX_OK) { return st; }
+	return ensure(ctx, ctx->rasSortedVals, entries + 1);
+}
+
+} // namespace
+
+int vgx_raster_reserve(vgx_ctx* ctx, uint64_t num_meshes, uint64_t num_bin_entries)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx) { return VGX_E_INVALID_ARG; }
+	if (num_meshes >= 0xFFFFFFFFull || num_bin_entries > 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	return rasterEnsure(ctx, num_meshes, num_bin_entries);
+}
+
+int vgx_raster(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
+               const vgx_raster_target* target, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || !frame || !target) { return VGX_E_INVALID_ARG; }
+	const vgx_raster_target& t = *target;
+	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
+	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
+	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)dev_status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
+		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
+	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
+	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	hipStream_t s = (hipStream_t)stream;
+	if (empty) { // no pixel to write
+		if (dev_status) { noteHip(ctx, hipMemsetAsync(dev_status, 0, sizeof(uint32_t), s)); } // VGX_OK
+		return launchStatus(ctx);
+	}
+	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
+	const uint64_t nrange = mesh_begin < end ? end - mesh_begin : 0;
+	VgxRasterArgs a;
+	memset(&a, 0, sizeof(a));
+	a.tiles_w = (t.width + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE;
+	a.tile_x0 = t.scissor[0] / VGX_RASTER_TILE; a.tile_y0 = t.scissor[1] / VGX_RASTER_TILE;
+	a.tiles_x = (t.scissor[2] - 1) / VGX_RASTER_TILE - a.tile_x0 + 1; a.tiles_y = (t.scissor[3] - 1) / VGX_RASTER_TILE - a.tile_y0 + 1;
+	a.sentinel = a.tiles_w * ((t.height + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE); // <= 2^20
+	for (a.sort_bits = 1; (a.sentinel >> a.sort_bits) != 0; ++a.sort_bits) { }
+	int st;
+	if ((st = ctx->ras.create(ctx, 2)) != VGX_OK) { return st; }
+	// the entry tables: what the last call measured (once that has arrived), else what they hold, else one entry per mesh
+	uint64_t entries = ctx->rasKeys.cap ? ctx->rasKeys.items() - 1 : nrange;
+	if (ctx->ras.landed() && ctx->ras.host[0] == VGX_E_GROWN && ctx->ras.host[1] > entries) { entries = ctx->ras.host[1]; }
+	if ((st = rasterEnsure(ctx, nrange, entries)) != VGX_OK) { return st; }
+	a.entry_cap = minOf({ ctx->rasKeys.items(), ctx->rasVals.items(), ctx->rasSortedKeys.items(), ctx->rasSortedVals.items() }) - 1;
+	// no mesh has more entries than the scissor has tiles: the sort need not look further
+	const uint64_t bound = nrange * ((uint64_t)a.tiles_x * a.tiles_y);
+	a.sort_n = bound < a.entry_cap ? bound : a.entry_cap;
+	size_t sortBytes = 0;
+	if (a.sort_n) {
+		sortBytes = vgx_raster_sort_bytes(a.sort_n, a.sort_bits);
+		if (!sortBytes) { return VGX_E_INTERNAL; }
+		if ((st = ensure(ctx, ctx->rasSortTemp, sortBytes)) != VGX_OK) { return st; }
+	}
+	if (!mesh_bounds && nrange) {
+		if ((st = ensure(ctx, ctx->rasBounds, frame->num_meshes * 4)) != VGX_OK) { return st; }
+		vgx_launch_mesh_bounds(frame->pos, frame->meshes + mesh_begin, nrange, ctx->rasBounds.ptr() + 4 * mesh_begin, s); // the range's boxes only
+		mesh_bounds = ctx->rasBounds.ptr();
+	}
+	a.pos = frame->pos; a.color = frame->color; a.idx = frame->idx; a.meshes = frame->meshes; a.mesh_bounds = mesh_bounds;
+	a.mesh_begin = mesh_begin; a.nrange = nrange;
+	a.pixels = t.pixels; a.stride = t.stride; a.x0 = t.x0; a.y0 = t.y0;
+	for (int k = 0; k < 4; ++k) { a.scissor[k] = t.scissor[k]; }
+	a.flags = t.flags; a.clear_color = t.clear_color;
+	a.mesh_entries = ctx->rasMeshEntries.ptr(); a.mesh_first = ctx->rasMeshFirst.ptr();
+	a.keys = ctx->rasKeys.ptr(); a.vals = ctx->rasVals.ptr(); a.sorted_keys = ctx->rasSortedKeys.ptr(); a.sorted_vals = ctx->rasSortedVals.ptr();
+	a.state = ctx->rasState.ptr(); a.status = dev_status;
+	noteHip(ctx, vgx_launch_raster(a, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+	// status and entry count to the mirror, for the next call (never waited for)
+	ctx->ras.push(ctx, a.state, s);
 	return launchStatus(ctx);
 }
 

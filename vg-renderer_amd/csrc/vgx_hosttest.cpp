@@ -533,6 +533,90 @@ int vgxt_pick(const vgx_cache_desc* frame, const float* mesh_bounds, const vgx_p
 
 }
 
+#include "vgx_raster.h"
+
+extern "C" {
+
+// vgx_raster on the host: the functions of vgx_raster.h in a plain loop over the meshes of the range, their triangles and the pixels
+// of each triangle's box inside the scissor; with the call's contract (mesh_bounds may be NULL: the boxes are computed first; given,
+// they are the prefilter they are on the device). HOST pointers, the target's pixels included. Returns the status the device call
+// returns for these arguments; *status (may be NULL) receives what it leaves in dev_status. There is no scratch to outgrow here.
+int vgxt_raster(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_target* target,
+                uint32_t* status)
+{
+	if (!frame || !target) { return VGX_E_INVALID_ARG; }
+	const vgx_raster_target& t = *target;
+	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
+	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
+	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
+		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
+	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
+	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	if (status) { *status = VGX_OK; }
+	if (empty) { return VGX_OK; }
+	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
+	float* own = nullptr;
+	if (!mesh_bounds && mesh_begin < end) {
+		own = (float*)malloc(frame->num_meshes * 4 * sizeof(float));
+		if (!own) { return VGX_E_INTERNAL; }
+		vgxt_mesh_bounds(frame->pos, frame->meshes, frame->num_meshes, own);
+	}
+	if (t.flags & VGX_RASTER_CLEAR) {
+		for (uint32_t j = t.scissor[1]; j < t.scissor[3]; ++j) {
+			for (uint32_t i = t.scissor[0]; i < t.scissor[2]; ++i) { t.pixels[(uint64_t)j * t.stride + i] = t.clear_color; }
+		}
+	}
+	for (uint64_t m = mesh_begin; m < end; ++m) {
+		const vgx_mesh me = frame->meshes[m];
+		VgxRasterRect r;
+		if (!vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, t.scissor, &r)) { continue; }
+		const uint16_t* ip = frame->idx + me.first_index;
+		const float* pp = frame->pos + 2 * me.first_vertex;
+		const uint32_t* cp = frame->color + me.first_vertex;
+		for (uint32_t k = 0; k < me.num_indices / 3u; ++k) {
+			const uint32_t i0 = ip[3 * k], i1 = ip[3 * k + 1], i2 = ip[3 * k + 2];
+			if (i0 >= me.num_vertices || i1 >= me.num_vertices || i2 >= me.num_vertices) { continue; }
+			VgxRasterTri T;
+			if (!vgx_raster_setup(v2(pp[2 * i0], pp[2 * i0 + 1]), v2(pp[2 * i1], pp[2 * i1 + 1]), v2(pp[2 * i2], pp[2 * i2 + 1]), cp[i0], cp[i1], cp[i2], &T)) { continue; }
+			uint32_t a0, a1, b0, b1;
+			if (!vgx_raster_span(T.minx, T.maxx, t.x0, t.scissor[0], t.scissor[2], &a0, &a1) || !vgx_raster_span(T.miny, T.maxy, t.y0, t.scissor[1], t.scissor[3], &b0, &b1)) { continue; }
+			for (uint32_t j = b0; j <= b1; ++j) {
+				for (uint32_t i = a0; i <= a1; ++i) {
+					uint32_t* const p = t.pixels + (uint64_t)j * t.stride + i;
+					const uint32_t d = vgx_raster_pixel(T, (double)(t.x0 + (int32_t)i) + 0.5, (double)(t.y0 + (int32_t)j) + 0.5, *p);
+					if (d != *p) { *p = d; }
+				}
+			}
+		}
+	}
+	free(own);
+	return VGX_OK;
+}
+
+// the pieces, for the tests of the predicate: the two canonical values of one directed edge u->v in a triangle of orientation
+// `positive`, at (px, py), and whether the edge takes a tie
+double vgxt_raster_edge(const float* u, const float* v, int positive, double px, double py, int* tie)
+{
+	VgxRasterEdge e;
+	const uint32_t f = vgx_raster_edge(v2(u[0], u[1]), v2(v[0], v[1]), positive != 0, 0, &e);
+	*tie = (f & VGX_RT_TIE(0)) != 0;
+	return vgx_raster_edge_value(e, f, 0, px, py);
+}
+
+// coverage of one sample by one triangle (a, b, c: 2 floats each)
+int vgxt_raster_cover(const float* a, const float* b, const float* c, double px, double py)
+{
+	VgxRasterTri T;
+	double E[3], S;
+	return vgx_raster_setup(v2(a[0], a[1]), v2(b[0], b[1]), v2(c[0], c[1]), 0, 0, 0, &T) && vgx_raster_cover(T, px, py, E, &S);
+}
+
+}
+
 #include "vgx_update.h"
 
 extern "C" {

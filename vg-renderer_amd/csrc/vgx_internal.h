@@ -449,4 +449,30 @@ void vgx_launch_cache_layout(const vgx_cache_desc& cache, const vgx_cache_instan
                              void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, hipStream_t s);
 void vgx_launch_cache_update(const VgxUpdateArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, hipStream_t s);
 
+// rendering to an image (vgx_raster.hip)
+struct VgxRasterArgs
+{
+	const float* pos; const uint32_t* color; const uint16_t* idx; const vgx_mesh* meshes; // the frame
+	const float* mesh_bounds;         // [num_meshes][4], 16-byte aligned: the caller's, or the context's own
+	uint64_t mesh_begin, nrange;      // the meshes drawn: [mesh_begin, mesh_begin + nrange), the end < 2^32 - 1
+	uint32_t* pixels;                 // the target, checked by the host
+	uint32_t stride;
+	int32_t x0, y0;
+	uint32_t scissor[4];              // inside the image, not inverted
+	uint32_t flags, clear_color;
+	uint32_t tiles_w;                 // tiles per row of the IMAGE: tile number = ty * tiles_w + tx
+	uint32_t tile_x0, tile_y0, tiles_x, tiles_y; // the tiles the scissor touches = the grid of k_raster_tiles (0 x 0: nothing to write)
+	uint32_t sentinel, sort_bits;     // tiles of the image = the key behind every tile; its bits
+	uint64_t entry_cap;               // entries keys / vals hold (each of the four arrays)
+	uint64_t sort_n;                  // <= entry_cap: what the sort looks at (the host's bound of the entry count)
+	uint32_t* mesh_entries;           // [nrange] (context scratch, as everything below)
+	uint64_t* mesh_first;             // [nrange]
+	uint32_t* keys; uint32_t* vals;   // [entry_cap] in mesh order
+	uint32_t* sorted_keys; uint32_t* sorted_vals; // [entry_cap] in tile order
+	unsigned long long* state;        // [0] the call's status, [1] its entries: what the pinned mirror carries to the next call
+	uint32_t* status;                 // the caller's dev_status or null
+};
+size_t vgx_raster_sort_bytes(uint64_t n, uint32_t bits); // temporary storage the sort of n entries wants; 0: the query failed
+hipError_t vgx_launch_raster(const VgxRasterArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
+
 #endif

@@ -1,0 +1,166 @@
+// vgx_raster.h -- the arithmetic of vgx_raster for ONE triangle, ONE sample and ONE pixel: host + device.
+// The tile kernel of vgx_raster.hip runs it one triangle per lane (setup) and one pixel per lane (coverage, colour, blend);
+// libvgx_hosttest.so (vgx_hosttest.cpp: vgxt_raster) runs the same functions mesh after mesh, triangle after triangle and pixel after
+// pixel so that the CPU suite pins the arithmetic without a GPU.
+//
+// The specification is in include/vgx.h (vgx_raster). The build compiles with -ffp-contract=off on both sides: nothing may contract the
+// binary64 expressions below into FMAs, or host and device would round differently. Division is the correctly rounded one.
+#ifndef VGX_RASTER_H
+#define VGX_RASTER_H
+
+#include "vgx_lane.h"
+#include <math.h>
+
+#define VGX_RASTER_TILE 16 // pixels per tile side: one workgroup of 256 lanes, one pixel per lane
+
+// ---- the setup record of a triangle: what a pixel needs, computed once ---------------------------------------------------
+// Edge k (0: a->b, 1: b->c, 2: c->a) in its canonical form: lo = the smaller endpoint by (x, then y), d = hi - lo in binary64.
+// g = d.x * (py - lo.y) - d.y * (px - lo.x) is the same number for both triangles that share the edge.
+struct VgxRasterEdge { float lox, loy; double dx, dy; };
+#define VGX_RT_NEG(k)  (1u << (k))        // E_k = -g_k (orientation and direction together)
+#define VGX_RT_ZERO(k) (8u << (k))        // u == v bit for bit: E_k = 0
+#define VGX_RT_TIE(k)  (64u << (k))       // the oriented edge takes E_k == 0
+#define VGX_RT_FLAT(ch) (512u << (ch))    // channel ch (0 = R .. 3 = A) is the same on all three vertices
+struct VgxRasterTri
+{
+	float minx, miny, maxx, maxy; // the triangle's own box
+	VgxRasterEdge e[3];
+	uint32_t col[3];              // ca, cb, cc
+	uint32_t flags;               // VGX_RT_*
+};                                // 104 bytes
+
+VGX_HD bool vgx_raster_bits_equal(V2 u, V2 v)
+{
+	union { float f; uint32_t u; } a, b, c, d;
+	a.f = u.x; b.f = v.x; c.f = u.y; d.f = v.y;
+	return a.u == b.u && c.u == d.u;
+}
+
+// the directed edge u->v of a triangle of orientation s (+1 / -1)
+VGX_HD uint32_t vgx_raster_edge(V2 u, V2 v, bool positive, int k, VgxRasterEdge* e)
+{
+	const bool uIsLo = u.x < v.x || (u.x == v.x && u.y <= v.y);
+	const V2 lo = uIsLo ? u : v, hi = uIsLo ? v : u;
+	e->lox = lo.x; e->loy = lo.y;
+	e->dx = (double)hi.x - (double)lo.x; e->dy = (double)hi.y - (double)lo.y;
+	uint32_t f = 0;
+	if (positive != uIsLo) { f |= VGX_RT_NEG(k); }
+	if (vgx_raster_bits_equal(u, v)) { f |= VGX_RT_ZERO(k); }
+	// oriented direction (dx, dy) = s * (v - u): the tie goes to dy > 0, or dy == 0 && dx < 0
+	const bool tie = positive ? (v.y > u.y || (v.y == u.y && v.x < u.x)) : (v.y < u.y || (v.y == u.y && v.x > u.x));
+	if (tie) { f |= VGX_RT_TIE(k); }
+	return f;
+}
+
+// false: the triangle covers nothing (A == 0 or NaN)
+VGX_HD bool vgx_raster_setup(V2 a, V2 b, V2 c, uint32_t ca, uint32_t cb, uint32_t cc, VgxRasterTri* T)
+{
+	const double ax = a.x, ay = a.y, bx = b.x, by = b.y, cx = c.x, cy = c.y;
+	const double A = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
+	if (!(A > 0.0 || A < 0.0)) { return false; }
+	const bool positive = A > 0.0;
+	T->minx = a.x < b.x ? (a.x < c.x ? a.x : c.x) : (b.x < c.x ? b.x : c.x);
+	T->maxx = a.x > b.x ? (a.x > c.x ? a.x : c.x) : (b.x > c.x ? b.x : c.x);
+	T->miny = a.y < b.y ? (a.y < c.y ? a.y : c.y) : (b.y < c.y ? b.y : c.y);
+	T->maxy = a.y > b.y ? (a.y > c.y ? a.y : c.y) : (b.y > c.y ? b.y : c.y);
+	uint32_t f = vgx_raster_edge(a, b, positive, 0, &T->e[0]) | vgx_raster_edge(b, c, positive, 1, &T->e[1]) | vgx_raster_edge(c, a, positive, 2, &T->e[2]);
+	for (int ch = 0; ch < 4; ++ch) {
+		const uint32_t x = (ca >> (8 * ch)) & 255u;
+		if (x == ((cb >> (8 * ch)) & 255u) && x == ((cc >> (8 * ch)) & 255u)) { f |= VGX_RT_FLAT(ch); }
+	}
+	T->col[0] = ca; T->col[1] = cb; T->col[2] = cc;
+	T->flags = f;
+	return true;
+}
+
+VGX_HD double vgx_raster_edge_value(const VgxRasterEdge& e, uint32_t flags, int k, double px, double py)
+{
+	const double g = e.dx * (py - (double)e.loy) - e.dy * (px - (double)e.lox);
+	if (flags & VGX_RT_ZERO(k)) { return 0.0; }
+	return (flags & VGX_RT_NEG(k)) ? -g : g;
+}
+
+VGX_HD bool vgx_raster_accepts(double E, uint32_t flags, int k) { return E > 0.0 || (E == 0.0 && (flags & VGX_RT_TIE(k)) != 0); }
+
+// Coverage of the sample (px, py); E[0..2] and S are what the colour needs
+VGX_HD bool vgx_raster_cover(const VgxRasterTri& T, double px, double py, double* E, double* S)
+{
+	if (!(px >= (double)T.minx && px <= (double)T.maxx && py >= (double)T.miny && py <= (double)T.maxy)) { return false; }
+	E[0] = vgx_raster_edge_value(T.e[0], T.flags, 0, px, py);
+	if (!vgx_raster_accepts(E[0], T.flags, 0)) { return false; }
+	E[1] = vgx_raster_edge_value(T.e[1], T.flags, 1, px, py);
+	if (!vgx_raster_accepts(E[1], T.flags, 1)) { return false; }
+	E[2] = vgx_raster_edge_value(T.e[2], T.flags, 2, px, py);
+	if (!vgx_raster_accepts(E[2], T.flags, 2)) { return false; }
+	*S = (E[0] + E[1]) + E[2];
+	return *S > 0.0;
+}
+
+// One channel at a covered sample. A channel that is the same on all three vertices IS that value: the rule below would give
+// v = x * (1 + e), |e| < 2^-49 (three products, two sums, one sum for S, one division, each within 2^-53), so |v - x| < 2^-41 and
+// (uint32)(v + 0.5) = x; the division is skipped, the result is the rule's.
+VGX_HD uint32_t vgx_raster_channel(const VgxRasterTri& T, int ch, const double* E, double S)
+{
+	const uint32_t xa = (T.col[0] >> (8 * ch)) & 255u;
+	if (T.flags & VGX_RT_FLAT(ch)) { return xa; }
+	const uint32_t xb = (T.col[1] >> (8 * ch)) & 255u, xc = (T.col[2] >> (8 * ch)) & 255u;
+	const double v = ((E[1] * (double)xa + E[2] * (double)xb) + E[0] * (double)xc) / S;
+	const uint32_t q = (uint32_t)(v + 0.5);
+	return q < 255u ? q : 255u;
+}
+
+VGX_HD uint32_t vgx_raster_div255(uint32_t x) { return (x + 127u) / 255u; }
+
+// BLEND_FUNC_SEPARATE(SRC_ALPHA, INV_SRC_ALPHA, ONE, INV_SRC_ALPHA) on UNORM8 in integers: src over dst, both 0xAABBGGRR
+VGX_HD uint32_t vgx_raster_blend(uint32_t dst, uint32_t r, uint32_t g, uint32_t b, uint32_t a)
+{
+	const uint32_t ia = 255u - a;
+	const uint32_t dr = dst & 255u, dg = (dst >> 8) & 255u, db = (dst >> 16) & 255u, da = dst >> 24;
+	return vgx_raster_div255(r * a + dr * ia) | (vgx_raster_div255(g * a + dg * ia) << 8) | (vgx_raster_div255(b * a + db * ia) << 16)
+	     | (vgx_raster_div255(255u * a + da * ia) << 24);
+}
+
+// The triangle on the pixel whose sample is (px, py): the pixel's new value
+VGX_HD uint32_t vgx_raster_pixel(const VgxRasterTri& T, double px, double py, uint32_t dst)
+{
+	double E[3], S;
+	if (!vgx_raster_cover(T, px, py, E, &S)) { return dst; }
+	const uint32_t a = vgx_raster_channel(T, 3, E, S);
+	if (a == 0u) { return dst; }
+	return vgx_raster_blend(dst, vgx_raster_channel(T, 0, E, S), vgx_raster_channel(T, 1, E, S), vgx_raster_channel(T, 2, E, S), a);
+}
+
+// ---- which pixels can a box reach? --------------------------------------------------------------------------------------
+// Pixel i samples at origin + i + 0.5. The pixels of [c0, c1) whose sample MAY lie in [lo, hi], as an inclusive range: a superset
+// (rounding is monotone, floor / ceil take the outer integer), which is all a prefilter needs -- the rule starts with the triangle's
+// own box. A NaN bound compares false and bounds nothing. false: none.
+VGX_HD bool vgx_raster_span(float lo, float hi, int32_t origin, uint32_t c0, uint32_t c1, uint32_t* i0, uint32_t* i1)
+{
+	const double base = (double)origin + 0.5;
+	const double dlo = (double)lo - base, dhi = (double)hi - base;
+	double fa = (double)c0, fb = (double)c1 - 1.0;
+	if (dlo > fa) { fa = floor(dlo); }
+	if (dhi < fb) { fb = ceil(dhi); }
+	if (!(fa <= fb)) { return false; }
+	*i0 = (uint32_t)fa; *i1 = (uint32_t)fb;
+	return true;
+}
+
+VGX_HD bool vgx_raster_kind_drawn(uint32_t subpathKind)
+{
+	const uint32_t k = subpathKind >> 28;
+	return k != VGX_MESH_TEXT && k != VGX_MESH_TRILIST;
+}
+
+// Bin entries of a mesh: the tiles its box can reach inside the scissor (a rectangle of tiles)
+struct VgxRasterRect { uint32_t tx0, ty0, tx1, ty1; }; // inclusive
+VGX_HD bool vgx_raster_mesh_tiles(const vgx_mesh& me, const float* box, int32_t x0, int32_t y0, const uint32_t* scissor, VgxRasterRect* r)
+{
+	if (!vgx_raster_kind_drawn(me.subpath_kind) || me.num_indices < 3u) { return false; }
+	uint32_t i0, i1, j0, j1;
+	if (!vgx_raster_span(box[0], box[2], x0, scissor[0], scissor[2], &i0, &i1) || !vgx_raster_span(box[1], box[3], y0, scissor[1], scissor[3], &j0, &j1)) { return false; }
+	r->tx0 = i0 / VGX_RASTER_TILE; r->tx1 = i1 / VGX_RASTER_TILE; r->ty0 = j0 / VGX_RASTER_TILE; r->ty1 = j1 / VGX_RASTER_TILE;
+	return true;
+}
+
+#endif

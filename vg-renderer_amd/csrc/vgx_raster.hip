@@ -1,0 +1,199 @@
+// vgx_raster.hip -- a frame's mesh streams to an RGBA8 image on gfx950 (include/vgx.h: vgx_raster; the arithmetic: vgx_raster.h).
+//
+// Blending is not commutative: a pixel must see its triangles in ascending (mesh, triangle) order, and no atomic on a pixel gives
+// that. So a pixel belongs to ONE lane for the whole call: the image is cut into tiles of 16 x 16 pixels, a tile is one workgroup of
+// 256 lanes, and the work in front of the tile kernel only finds, per tile, the meshes that can reach it, in ascending order.
+//   k_raster_count    one lane per mesh of the range: the mesh's box (vgx_mesh_bounds) clipped to image and scissor -> a rectangle of
+//                     tiles -> its number of (tile, mesh) entries and its triangles
+//   scan OpRasterBin  (vgx_scan.h) every mesh's first entry and the totals. finish() is where the call decides ON THE DEVICE: more
+//                     entries than the scratch holds -> VGX_E_GROWN, more than 2^32 - 1 entries or triangles -> VGX_E_RANGE. Every
+//                     kernel behind it looks at the state word and does nothing unless it says VGX_OK, the clear included
+//   k_raster_entries  one lane per mesh writes its entries, key = tile number, value = mesh: ascending by mesh. One lane per slot of
+//                     the sorted range behind the total writes the sentinel key (the entry count is known on the device only)
+//   radix_sort_pairs  rocprim's, on bits [0, bits of the sentinel): stable, so every tile's run stays ascending by mesh
+//   k_raster_tiles    the hot path. The workgroup finds its run by two searches in the sorted keys, takes the run's meshes 256 at a
+//                     time (mesh records -> exclusive scan of their triangle counts in LDS) and the triangles of those meshes 256 at
+//                     a time, whatever mesh they belong to: a lane finds its triangle's mesh by a search in the LDS prefix, loads
+//                     three uint16 indices, three positions and three colours, does the setup once (orientation, the three canonical
+//                     edges, tie flags, box) and tests the box against the tile; the survivors are compacted IN ORDER (ballot + prefix
+//                     count per wave, the wave counts through LDS) into 104-byte setup records in LDS. Then every pixel lane walks the
+//                     records in LDS order -- all lanes read the same address, a broadcast -- with coverage, colour and blend in
+//                     registers. The pixel is read once (after the clear decision) and written once, when something changed.
+// No host round trip, nothing comes back but the status and, through the context's pinned mirror, the entry count for the next call.
+#include "vgx_internal.h"
+#include "vgx_wave.h"
+#include "vgx_scan.h"
+#include "vgx_raster.h"
+#include <rocprim/device/device_radix_sort.hpp>
+
+namespace {
+
+__device__ __forceinline__ bool raster_rect(const VgxRasterArgs& A, uint64_t k, VgxRasterRect* r)
+{
+	const uint64_t m = A.mesh_begin + k;
+	const float4 box = ((const float4*)A.mesh_bounds)[m];
+	const float b[4] = { box.x, box.y, box.z, box.w };
+	return vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, A.scissor, r);
+}
+
+__global__ __launch_bounds__(256) void k_raster_count(VgxRasterArgs A)
+{
+	const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= A.nrange) { return; }
+	VgxRasterRect r;
+	A.mesh_entries[k] = raster_rect(A, k, &r) ? (r.tx1 - r.tx0 + 1u) * (r.ty1 - r.ty0 + 1u) : 0u;
+}
+
+struct OpRasterBin
+{
+	VgxRasterArgs A;
+	__device__ uint64_t size() const { return A.nrange; }
+	__device__ Sum3 load(uint64_t i) const
+	{
+		Sum3 r = sum3_zero();
+		r.a = A.mesh_entries[i];
+		r.b = r.a ? A.meshes[A.mesh_begin + i].num_indices / 3u : 0u;
+		return r;
+	}
+	__device__ void store(uint64_t i, Sum3 e) const { A.mesh_first[i] = e.a; }
+	__device__ void finish(Sum3 t) const
+	{
+		uint32_t st = VGX_OK;
+		if (t.a > A.entry_cap) { st = VGX_E_GROWN; }
+		if (t.a > 0xFFFFFFFFull || t.b > 0xFFFFFFFFull) { st = VGX_E_RANGE; }
+		A.state[0] = st; A.state[1] = t.a;
+		if (A.status) { *A.status = st; }
+	}
+};
+
+__global__ __launch_bounds__(256) void k_raster_entries(VgxRasterArgs A)
+{
+	if (A.state[0] != VGX_OK) { return; }
+	const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	// the unused tail of what the sort will look at
+	if (k >= A.state[1] && k < A.sort_n) { A.keys[k] = A.sentinel; A.vals[k] = 0u; }
+	if (k >= A.nrange || A.mesh_entries[k] == 0u) { return; }
+	VgxRasterRect r;
+	(void)raster_rect(A, k, &r);
+	uint64_t at = A.mesh_first[k]; // + the mesh's entries <= the total <= entry_cap: checked by finish()
+	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
+		for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx, ++at) { A.keys[at] = ty * A.tiles_w + tx; A.vals[at] = (uint32_t)(A.mesh_begin + k); }
+	}
+}
+
+// first index of [0, n) whose key is >= x, else n
+__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t n, uint32_t x)
+{
+	uint32_t lo = 0, hi = n;
+	while (lo < hi) {
+		const uint32_t mid = lo + ((hi - lo) >> 1);
+		if (a[mid] < x) { lo = mid + 1u; } else { hi = mid; }
+	}
+	return lo;
+}
+
+__global__ __launch_bounds__(256) void k_raster_tiles(VgxRasterArgs A)
+{
+	__shared__ VgxRasterTri s_tri[256];
+	__shared__ uint64_t s_first[257];   // exclusive prefix of the triangle counts of the (at most 256) meshes in hand
+	__shared__ uint32_t s_mesh[256];
+	__shared__ Sum3 s_wave[4];
+	__shared__ uint32_t s_count[4];
+	if (A.state[0] != VGX_OK) { return; }
+	const uint32_t tid = threadIdx.x;
+	const int lane = tid & (VGX_WAVE - 1);
+	const uint32_t wave = tid >> 6;
+	const uint32_t tx = A.tile_x0 + blockIdx.x, ty = A.tile_y0 + blockIdx.y;
+	const uint32_t i = tx * VGX_RASTER_TILE + (tid & 15u), j = ty * VGX_RASTER_TILE + (tid >> 4);
+	const bool inside = i >= A.scissor[0] && i < A.scissor[2] && j >= A.scissor[1] && j < A.scissor[3];
+	// the pixels of this tile inside the scissor, for the triangles' box test
+	const uint32_t cx0 = max(tx * VGX_RASTER_TILE, A.scissor[0]), cx1 = min((tx + 1u) * VGX_RASTER_TILE, A.scissor[2]);
+	const uint32_t cy0 = max(ty * VGX_RASTER_TILE, A.scissor[1]), cy1 = min((ty + 1u) * VGX_RASTER_TILE, A.scissor[3]);
+	const uint32_t key = ty * A.tiles_w + tx;
+	const uint32_t r0 = lower_bound_u32(A.sorted_keys, A.sort_n, key), r1 = lower_bound_u32(A.sorted_keys, A.sort_n, key + 1u);
+	const bool clear = (A.flags & VGX_RASTER_CLEAR) != 0;
+	if (r0 == r1 && !clear) { return; }
+	uint32_t* const pixel = A.pixels + (uint64_t)j * A.stride + i;
+	const uint32_t before = inside ? (clear ? A.clear_color : *pixel) : 0u;
+	uint32_t d = before;
+	const double px = (double)(A.x0 + (int32_t)i) + 0.5, py = (double)(A.y0 + (int32_t)j) + 0.5;
+	for (uint32_t eb = r0; eb < r1; eb += 256u) { // block-uniform loops throughout
+		const uint32_t ne = min(256u, r1 - eb);
+		Sum3 v = sum3_zero();
+		if (tid < ne) {
+			const uint32_t m = A.sorted_vals[eb + tid];
+			s_mesh[tid] = m;
+			v.a = A.meshes[m].num_indices / 3u;
+		}
+		Sum3 tot;
+		const Sum3 incl = block_incl_scan<256>(v, s_wave, &tot);
+		s_first[tid + 1u] = incl.a;
+		if (tid == 0u) { s_first[0] = 0; }
+		__syncthreads();
+		for (uint64_t tb = 0; tb < tot.a; tb += 256u) {
+			const uint64_t g = tb + tid;
+			bool keep = false;
+			VgxRasterTri T;
+			if (g < tot.a) {
+				uint32_t lo = 0, hi = ne; // the last mesh whose first triangle is <= g
+				while (hi - lo > 1u) {
+					const uint32_t mid = (lo + hi) >> 1;
+					if (s_first[mid] <= g) { lo = mid; } else { hi = mid; }
+				}
+				const vgx_mesh me = A.meshes[s_mesh[lo]];
+				const uint16_t* ip = A.idx + me.first_index + 3ull * (g - s_first[lo]);
+				const uint32_t i0 = ip[0], i1 = ip[1], i2 = ip[2];
+				if (i0 < me.num_vertices && i1 < me.num_vertices && i2 < me.num_vertices) {
+					const float2* pp = (const float2*)A.pos + me.first_vertex;
+					const uint32_t* cp = A.color + me.first_vertex;
+					const float2 p0 = pp[i0], p1 = pp[i1], p2 = pp[i2];
+					uint32_t a0, a1, b0, b1;
+					keep = vgx_raster_setup(v2(p0.x, p0.y), v2(p1.x, p1.y), v2(p2.x, p2.y), cp[i0], cp[i1], cp[i2], &T)
+					    && vgx_raster_span(T.minx, T.maxx, A.x0, cx0, cx1, &a0, &a1) && vgx_raster_span(T.miny, T.maxy, A.y0, cy0, cy1, &b0, &b1);
+				}
+			}
+			const uint64_t kept = wave_ballot(keep);
+			if (lane == 0) { s_count[wave] = (uint32_t)__popcll(kept); }
+			__syncthreads();
+			uint32_t base = 0, n = 0;
+#pragma unroll
+			for (uint32_t w = 0; w < 4u; ++w) { const uint32_t c = s_count[w]; base += w < wave ? c : 0u; n += c; }
+			if (keep) { s_tri[base + (uint32_t)__popcll(kept & lanemask_lt(lane))] = T; }
+			__syncthreads();
+			if (inside) {
+				for (uint32_t t = 0; t < n; ++t) { d = vgx_raster_pixel(s_tri[t], px, py, d); }
+			}
+			__syncthreads(); // s_tri and s_count are written again
+		}
+	}
+	if (inside && (clear || d != before)) { *pixel = d; }
+}
+
+} // namespace
+
+size_t vgx_raster_sort_bytes(uint64_t n, uint32_t bits)
+{
+	size_t bytes = 0;
+	if (n == 0 || rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+	                                        (size_t)n, 0u, bits, (hipStream_t)0) != hipSuccess) {
+		return 0;
+	}
+	return bytes ? bytes : 1;
+}
+
+hipError_t vgx_launch_raster(const VgxRasterArgs& a, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
+{
+	if (a.nrange) { hipLaunchKernelGGL(k_raster_count, dim3((unsigned)((a.nrange + 255) / 256)), dim3(256), 0, s, a); }
+	OpRasterBin op;
+	op.A = a;
+	vgx_device_scan(op, (Sum3*)partial, s, a.nrange);
+	const uint64_t items = a.nrange > a.sort_n ? a.nrange : a.sort_n;
+	if (items) { hipLaunchKernelGGL(k_raster_entries, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a); }
+	if (a.sort_n) {
+		const hipError_t e = rocprim::radix_sort_pairs(sortTemp, sortBytes, (const uint32_t*)a.keys, a.sorted_keys, (const uint32_t*)a.vals, a.sorted_vals,
+		                                               (size_t)a.sort_n, 0u, a.sort_bits, s);
+		if (e != hipSuccess) { return e; }
+	}
+	if (a.tiles_x && a.tiles_y) { hipLaunchKernelGGL(k_raster_tiles, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, a); }
+	return hipSuccess;
+}

@@ -672,6 +672,34 @@ def pick(ctx, frame, queries_dev, nqueries, bounds_dev=None, hits_dev=None):
     return hits_dev
 
 
+# ---- rendering to an image (vgx_raster) -----------------------------------------------------------------------------------
+def raster(ctx, frame, width, height, x0=0, y0=0, scissor=None, clear_color=None, bounds_dev=None, mesh_begin=0, mesh_end=None, image=None,
+           dev_status=None):
+    """Draws the meshes [mesh_begin, mesh_end) of `frame` (a capi.CacheDesc of device pointers, or anything with .desc()) into an RGBA8
+    image on the device: pixel (i, j) samples the frame at (x0 + i + 0.5, y0 + j + 0.5). scissor: (sx0, sy0, sx1, sy1) in image pixels,
+    None = the whole image; clear_color: 0xAABBGGRR the scissor is set to first, None = drawn over what `image` holds (zeros for a new
+    one); bounds_dev: what mesh_bounds gave for the frame, or None. image: an int32 [height, stride] device tensor to draw into
+    (stride = its row length). Returns (image, dev_status): the int32 tensor whose words are 0xAABBGGRR and an int32 [1] tensor that
+    holds VGX_OK, VGX_E_GROWN (call again) or VGX_E_RANGE once the work is done. Asynchronous."""
+    import torch
+    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
+    if image is None:
+        image = torch.zeros((max(int(height), 1), max(int(width), 1)), dtype=torch.int32, device="cuda:%d" % ctx.device)[:height, :width]
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
+    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
+    t = capi.RasterTarget(image.data_ptr(), int(width), int(height), int(image.stride(0)) if image.dim() == 2 and height else int(width), int(x0), int(y0),
+                          (C.c_uint32 * 4)(*sc), capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
+    _check(lib().vgx_raster(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
+                            0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(t), dev_status.data_ptr(), _stream_ptr()), "vgx_raster")
+    return image, dev_status
+
+
+def raster_reserve(ctx, num_meshes, num_bin_entries):
+    """Sizes the scratch of raster() ahead, so that a first call does not end with VGX_E_GROWN."""
+    _check(lib().vgx_raster_reserve(ctx.handle, int(num_meshes), int(num_bin_entries)), "vgx_raster_reserve")
+
+
 # ---- incremental update (vgx_cache_layout / vgx_cache_update) ------------------------------------------------------------
 def cache_layout(ctx, cache, inst_dev, ninst, slots_dev=None):
     """Where every instance of `inst_dev` (uint8 device tensor of 40-byte vgx_cache_instance records) lives in the frame cache_submit
