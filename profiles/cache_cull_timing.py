@@ -4,7 +4,8 @@ drawings, the benchmark's size), once as one instance per DRAW (2.4 M instances 
   (a) baseline: vgx_cache_submit of all instances (the behaviour before culling existed; that code is unchanged);
   (b) culled:   vgx_cache_cull + vgx_cache_submit, the view showing 1/16, 1/4 and all of the grid ("all" = the overhead of the pass);
   (c) kernels:  vgx_mesh_bounds over the all-instances frame, and vgx_cache_cull alone (out of place, no boxes, no list; a call of a 10 000-instance pass is mostly launch + synchronise) for both range
-                shapes, one lane per range and long ranges reduced by the wave (VGX_CULL_WAVE_MIN = 0 / 32: a context of its own each), as bytes
+                shapes (keys *_cull_lane_*: one lane per range; the *_cull_wave32_* keys of the recorded cache_cull_timing.json are
+                the wave-reduced form that was removed), as bytes
                 read + written per second beside a plain device-to-device copy of 1 GiB timed in the same job.
 Every sample is a host clock around `call(s); synchronise`. Buffers and scratch are sized before the clock starts.
 
@@ -139,23 +140,18 @@ def main():
             stats("%s_%s" % (shape, k), t[k])
         for k in views:
             res["%s_b_%s_over_a" % (shape, k)] = res["%s_b_%s_ms_median" % (shape, k)] / res["%s_a_all_ms_median" % shape]
-        # (c) the cull pass alone: one lane per range (the default) against long ranges (>= 32 boxes) reduced by the wave
-        for knob in ("lane", "wave32"):
-            os.environ["VGX_CULL_WAVE_MIN"] = "0" if knob == "lane" else "32"
-            c2 = rt.Context(0)
-            os.environ.pop("VGX_CULL_WAVE_MIN", None)
-            vd = views["quarter"]
+        # (c) the cull pass alone
+        vd = views["quarter"]
 
-            def cull_only():  # out of place into the array allocated above: every record read and written once, nothing to restore
-                rt.cache_cull(c2, cache, mb, src, n, vd, reuse=keep)
-            for _ in range(3):
-                cull_only()
-            stats("%s_cull_%s" % (shape, knob), [sample(cull_only) for _ in range(args.rounds)])
-            ms = res["%s_cull_%s_ms_median" % (shape, knob)]
-            moved = 2 * n * 40 + int(inst["num_meshes"].astype(np.int64).sum()) * 16  # records in and out, the boxes of every range (L2)
-            res["%s_cull_%s_bytes" % (shape, knob)] = moved
-            res["%s_cull_%s_TBps" % (shape, knob)] = moved / ms / 1e9
-            c2.close()
+        def cull_only():  # out of place into the array allocated above: every record read and written once, nothing to restore
+            rt.cache_cull(ctx, cache, mb, src, n, vd, reuse=keep)
+        for _ in range(3):
+            cull_only()
+        stats("%s_cull_lane" % shape, [sample(cull_only) for _ in range(args.rounds)])
+        ms = res["%s_cull_lane_ms_median" % shape]
+        moved = 2 * n * 40 + int(inst["num_meshes"].astype(np.int64).sum()) * 16  # records in and out, the boxes of every range (L2)
+        res["%s_cull_lane_bytes" % shape] = moved
+        res["%s_cull_lane_TBps" % shape] = moved / ms / 1e9
         del src
 
     # (c) vgx_mesh_bounds over the all-instances frame (what the per-drawing baseline left in `out`)

@@ -74,6 +74,23 @@ def test_no_cpu_fallback_without_device(rt):
         rt.Context(0)
 
 
+def test_environment_knobs_are_the_documented_ones():
+    """Every VGX_* variable the native sources read (csrc/, host/) plus the runtime's VGX_LIB is listed in README's "Environment
+    knobs" paragraph, and the paragraph lists nothing else: a removed knob lingers in neither place, a new one is documented."""
+    read = set()
+    for base in ("csrc", "host"):
+        for dp, _, files in os.walk(os.path.join(ROOT, "vg-renderer_amd", base)):
+            for f in files:
+                if f.endswith((".h", ".hpp", ".hip", ".cpp")):
+                    read |= set(re.findall(r'getenv\(\s*"(VGX_[A-Z0-9_]+)"', open(os.path.join(dp, f), errors="ignore").read()))
+    assert 'os.environ.get("VGX_LIB"' in open(os.path.join(ROOT, "vg-renderer_amd", "runtime.py")).read()
+    read.add("VGX_LIB")
+    paragraphs = [p for p in open(os.path.join(ROOT, "README.md")).read().split("\n\n") if p.startswith("Environment knobs")]
+    assert len(paragraphs) == 1
+    documented = set(re.findall(r"VGX_[A-Z0-9_]+", paragraphs[0]))
+    assert read == documented, sorted(read ^ documented)
+
+
 def test_product_code_never_touches_the_oracle():
     """The oracle is test infrastructure: nothing under vg-renderer_amd/ or include/ may reference it."""
     bad = []

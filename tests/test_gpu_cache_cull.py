@@ -215,26 +215,6 @@ def test_submission_of_the_culled_list(rt, gpu_ctx, n, armed):
     assert np.array_equal(np.unique(ref.meshes["draw"]), np.nonzero(kept_mask)[0])  # `draw` still names the original instance
 
 
-def test_wave_reduced_ranges_give_the_same_answer(rt, gpu_ctx):
-    """VGX_CULL_WAVE_MIN=32 (read when the context is created): whole-cache ranges are united by the wave, short ones by their lane. The
-    assertions of the default form hold unchanged."""
-    import os
-    c, inst, special, t = M.scene("tiger", 257)
-    views, iv = M.make_views(c), M.make_inst_view(257)
-    cache = gpu_cache(rt, gpu_ctx, "tiger")
-    os.environ["VGX_CULL_WAVE_MIN"] = "32"
-    try:
-        ctx2 = rt.Context(0)
-    finally:
-        del os.environ["VGX_CULL_WAVE_MIN"]
-    try:
-        st, gi, gb, gk, nk, untouched, _ = gpu_cull(rt, ctx2, cache, cache.bounds, inst, views, iv)
-    finally:
-        ctx2.close()
-    assert untouched
-    M.check_cull(c, c.mesh_boxes, inst, special, views, iv, t, st, gi, gb, gk, nk)
-
-
 def test_invalid_arguments(rt, gpu_ctx):
     c, inst, special, _ = M.scene("tiger", 65)
     cache = gpu_cache(rt, gpu_ctx, "tiger")

@@ -370,15 +370,12 @@ def test_async_very_long_subpaths(rt, wl, oracle, waves, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("workload", ["tiger", "fuzz", "bigcubics"])
-def test_async_pooled_walk(rt, wl, oracle, workload, monkeypatch):
-    """VGX_WALK=pool: the wave subdivides all cubics of a chunk together (task LIFO in LDS, ballot + popcount compaction,
-    leaf ranks from per-command bit masks) instead of one cubic per lane; deeper cubics fall back to the per-lane walk."""
-    monkeypatch.setenv("VGX_WALK", "pool")
+@pytest.mark.parametrize("workload", ["fuzz", "bigcubics"])
+def test_async_default_walk(rt, wl, oracle, workload):
+    """The default flatten routes (one cubic per lane, vgx_walk.h) on two curve-heavy batches that no other test draws: 1500 draws
+    of 200 fuzzed paths without shapes, and 3000 large cubics, filled and stroked."""
     ctx = rt.Context(0)
-    if workload == "tiger":
-        ps, d = wl.tiger(24)
-    elif workload == "fuzz":
+    if workload == "fuzz":
         ps = wl.fuzz_paths(512, npaths=200, with_shapes=False, degenerate=False)
         d = wl.fuzz_draws(ps, 512, ndraws=1500)
     else:
@@ -388,7 +385,7 @@ def test_async_pooled_walk(rt, wl, oracle, workload, monkeypatch):
     ref = oracle.tessellate(ps, d)
     got = _async_result(rt, ctx, ps, d)
     assert got.status == 0
-    assert_mesh_equal(got, ref, "pooled walk, %s" % workload)
+    assert_mesh_equal(got, ref, "default walk, %s" % workload)
     ctx.close()
 
 
@@ -546,9 +543,7 @@ def test_async_thin_path_sets_static_layout(rt, wl, oracle, seed, npaths, degene
     d = wl.fuzz_draws(ps, seed)
     d = d[np.random.RandomState(seed).permutation(d.shape[0])]
     ref = oracle.tessellate(ps, d)
-    import os
-    on = os.environ.get("VGX_THIN_STATIC", "1")  # ("2": the kernel instance with two command instances per thread)
-    for static in (on if on != "0" else "1", "0"):
+    for static in ("1", "0"):
         monkeypatch.setenv("VGX_THIN_STATIC", static)
         ctx = rt.Context(0)
         got = _async_result(rt, ctx, ps, d)

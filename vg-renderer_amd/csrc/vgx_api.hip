@@ -28,17 +28,9 @@
 #include <math.h>
 #include <new>
 #include <stdlib.h>
-#include <time.h>
-#include <stdio.h>
 
 
-static int vgxGridBlocks()
-{
-	static int g = 0;
-	if (!g) { const char* e = getenv("VGX_GRID_BLOCKS"); g = e ? atoi(e) : 32768; if (g < 256) { g = 256; } }
-	return g;
-}
-#define VGX_GRID_BLOCKS vgxGridBlocks() // one-wave workgroups, each owning a contiguous run of segments (>> resident waves: no tail)
+#define VGX_GRID_BLOCKS 32768 // one-wave workgroups, each owning a contiguous run of segments (>> resident waves: no tail)
 
 // Grid of the element kernels for a batch whose element count is at most `maxElements` (a bound the host knows: the
 // caller's vertex capacity -- every element emits at least one vertex). Frame-sized batches should not pay for
@@ -119,7 +111,6 @@ struct vgx_ctx
 	DevBuf rasSortTemp, rasPartial;      // rasPartial: slice sums (views: as `partial`)
 	HostMirror<unsigned long long> ras;
 	uint32_t optPickGrid;                // workgroups of k_pick_tris (VGX_PICK_GRID)
-	uint32_t optCullWaveMin;             // mesh ranges of at least this many boxes are united by the whole wave; >= 1, 2^32 - 1 = never = the default (VGX_CULL_WAVE_MIN)
 	// vgx_dash (vgx_dash.hip): per-draw patterns, per-list records, per-segment prefix sums (S and the overflow guard), per-range sums; the
 	// segment count of the last call in pinned memory (copied behind the call, read by the next call once its event has passed: a call
 	// whose lists outgrew dashG ends with VGX_E_GROWN and the next one grows first, as vgx_tessellate_immediate does)
@@ -137,14 +128,13 @@ struct vgx_ctx
 	Buf<VgxTileRec> tileTab;             // k_emit_tiles (vgx_tile.hip): the tile table of the current call
 	bool tileHint;                       // the last ordinary vgx_tessellate_count saw fills and closed Miter AA / Thin strokes only (the tile kernel's batches)
 	uint64_t optBigEmitMin;              // vertex capacity from which a call launches the tile kernel / k_stroke_long (2^18; VGX_BIG_EMIT_MIN: testing knob, 0 = every call)
-	int optStrokeLong;                   // VGX_STROKE_LONG=0: batches of long polylines through k_stroke like any other (no LDS-staged stores)
 	int optTileEmit;                     // VGX_TILE_EMIT=0: ordinary batches through k_fill + k_stroke_simple as before round 6
 	DevBuf psTemp;                       // vgx_pathset_create: temporaries of the device-side build (vgx_pathset.hip); views: VgxPsTotals, uint32_t words, VgxPsM and Sum3 slice sums at byte offsets
 	hipStream_t psStream;                // ... its stream (created at the first call)
 	struct VgxPsTotals* hostPs;          // ... pinned: what the build reports
 	void* psImage; size_t psImageCap;    // ... pinned: the raw part of a frame-sized set, assembled here and uploaded in one copy
 	DevBuf psPool[VGX_PS_POOL];          // ... blobs of dropped frame-sized sets, recycled (hipFree synchronises). Not scratch: never grown, not on the list
-	void* psStage[2]; hipEvent_t psStageEv[2]; bool psStageBusy[2]; uint64_t psStageK; int optPsStage, optPsNoSmall; // VGX_PS_UPLOAD=stage: own pinned staging
+	int optPsNoSmall;                    // VGX_PS_NO_SMALL: frame-sized path sets through the large-set launch sequence
 	Buf<uint64_t> f1SegDraw; Buf<VgxF1Seg> f1Segs; // vgx_flatten (vgx_flat1.hip): segment table, look-back records
 	int optF1Waves, optF1Cap, optF1Seg;  // its grid (persistent one-wave workgroups), the leaf-list capacity of the kernel instance and the segment bucket (0 = chosen per batch)
 	// what the last vgx_flatten call produced (copied to pinned memory behind the call, read by the next call WITHOUT waiting for
@@ -155,7 +145,7 @@ struct vgx_ctx
 	DevBuf partBounds;                   // vgx_partition; views: uint64_t [nparts + 1] bounds, behind them [nparts] weights
 	struct VgxRccl* rccl;                // RCCL entry points, bound at the first vgx_gather* call
 	// options, read from the environment ONCE at vgx_create (tuning / testing knobs)
-	int optTwoPass, optBuildWaves, optPoolWalk, optNoSmall;
+	int optBuildWaves, optNoSmall;
 	int optTessFlat1;                    // VGX_TESS_FLAT1: 1 (default) = vgx_tessellate flattens batches of long curves with the one-walk kernel (k_flat1), 0 = never, 2 = every eligible batch
 	// vgx_tessellate's one-walk route, decided and sized by the last vgx_tessellate_count (f1Route*): the path set it is for, the kernel
 	// instance / bucket size, the segments the look-back tables hold
@@ -519,7 +509,6 @@ VgxFlattenArgs flattenArgs(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* 
 	a.apply_transform = applyTransform;
 	a.sub_rec = ctx->subFirst.ptr();
 	a.build_mode = 0;
-	a.pool_walk = ctx->optPoolWalk;
 	a.thin_static = ps->thinStatic ? ctx->optThinStatic : 0;
 	a.leaf_overflow = ctx->leafOverflow.ptr();
 	a.serial_list = ctx->serialList.ptr();
@@ -808,7 +797,7 @@ int runStrokeEmit(vgx_ctx* ctx, const vgx_draw* draws, const vgx_mesh_out* out, 
 	VgxStrokeArgs a = strokeArgs(ctx, draws, poly, ctx->caps);
 	a.mesh_base = ctx->asmArmed ? ctx->meshBase.ptr() : nullptr;
 	a.pos = out->pos; a.color = out->color; a.idx = out->idx; a.meshes_out = tableDone ? nullptr : out->meshes;
-	a.no_long = (out->cap_vertices < ctx->optBigEmitMin || !ctx->optStrokeLong) ? 1 : 0; // frame-sized: one stroke kernel less to launch
+	a.no_long = out->cap_vertices < ctx->optBigEmitMin ? 1 : 0; // frame-sized: one stroke kernel less to launch
 	// Batches of fills and closed Miter AA / Thin strokes (the scan over the meshes decides, on the device): one draw-ordered tile
 	// kernel instead of k_fill + k_stroke_simple (vgx_tile.hip). Not for frame-sized calls (two more launches than they are worth).
 	uint64_t capTiles = 0;
@@ -1007,16 +996,8 @@ int vgx_create(int device, vgx_ctx** out_ctx)
 		return VGX_E_HIP;
 	}
 	// tuning / testing knobs: read once here, never on the call path
-	ctx->optTwoPass = getenv("VGX_TWO_PASS_FLATTEN") ? 1 : 0;
-	if (const char* e = getenv("VGX_PS_UPLOAD")) { ctx->optPsStage = strcmp(e, "stage") == 0; }
 	ctx->optBigEmitMin = 1ull << 18;
 	if (const char* e = getenv("VGX_BIG_EMIT_MIN")) { ctx->optBigEmitMin = strtoull(e, nullptr, 10); }
-	ctx->optStrokeLong = 1;
-	if (const char* e = getenv("VGX_STROKE_LONG")) { ctx->optStrokeLong = atoi(e) != 0; }
-	// never, unless asked: on 10 000 instances of 435 meshes one lane per range took 0.067 ms and the wave-reduced form (threshold 32) 0.101 ms;
-	// ranges of 1-3 meshes do not care (profiles/cache_cull_timing.json). VGX_CULL_WAVE_MIN=N > 0 turns the wave form on for ranges >= N
-	ctx->optCullWaveMin = 0xFFFFFFFFu;
-	if (const char* e = getenv("VGX_CULL_WAVE_MIN")) { const int v = atoi(e); ctx->optCullWaveMin = v <= 0 ? 0xFFFFFFFFu : (uint32_t)v; }
 	// k_pick_tris strides a fixed grid over the candidate triangles (their count stays on the device): four workgroups per CU of a
 	// 256-CU part; workgroups without a tile exit at once. VGX_PICK_GRID=N > 0 sets another (the tests force many tiles per workgroup)
 	ctx->optPickGrid = 1024;
@@ -1044,14 +1025,12 @@ int vgx_create(int device, vgx_ctx** out_ctx)
 	if (const char* e = getenv("VGX_TMPL_TILE")) { const int v = atoi(e); if (v >= 64 && v <= VGX_TMPL_MAX_TILE) { ctx->optTmplTile = (uint32_t)v / 64u * 64u; } } // testing: elements per tile (<= the LDS stage of k_tmpl_emit)
 	ctx->optTessFlat1 = 1; ctx->f1Route = false; ctx->f1RoutePs = nullptr; ctx->f1RoutePsGen = 0; ctx->f1RouteCap = 1664; ctx->f1RouteSegMax = 64; ctx->f1RouteSegBound = 0;
 	if (const char* e = getenv("VGX_TESS_FLAT1")) { const int v = atoi(e); if (v >= 0 && v <= 2) { ctx->optTessFlat1 = v; } }
-	ctx->optPoolWalk = 0; // VGX_WALK=pool: the wave-cooperative walk of vgx_walk.h (same output, same speed: DESIGN.md section 4)
-	if (const char* e = getenv("VGX_WALK")) { ctx->optPoolWalk = strcmp(e, "pool") == 0; }
 	ctx->optF1Waves = 0; ctx->optF1Cap = 0; ctx->optF1Seg = 0;
 	if (const char* e = getenv("VGX_F1_SEG")) { const int v = atoi(e); if (v >= 2 && v <= 64) { ctx->optF1Seg = v; } }
 	if (const char* e = getenv("VGX_F1_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 65536) { ctx->optF1Waves = v; } }
 	if (const char* e = getenv("VGX_F1_CAP")) { ctx->optF1Cap = atoi(e); }
 	ctx->optThinStatic = 1;
-	if (const char* e = getenv("VGX_THIN_STATIC")) { const int v = atoi(e); ctx->optThinStatic = v == 2 ? 2 : (v != 0 ? 1 : 0); } // (2: the kernel instance with two command instances per thread)
+	if (const char* e = getenv("VGX_THIN_STATIC")) { ctx->optThinStatic = atoi(e) != 0; }
 	if (const char* e = getenv("VGX_BUILD_WAVES")) { const int v = atoi(e); if (v >= 1 && v < VGX_BUILD_WAVES) { ctx->optBuildWaves = v; } }
 	*out_ctx = ctx;
 	return VGX_OK;
@@ -1071,7 +1050,6 @@ int vgx_destroy(vgx_ctx* ctx)
 	if (ctx->psImage) { (void)hipHostFree(ctx->psImage); }
 	for (int i = 0; i < VGX_PS_POOL; ++i) { if (ctx->psPool[i].p) { (void)hipFree(ctx->psPool[i].p); } }
 	if (ctx->psStream) { (void)hipStreamDestroy(ctx->psStream); }
-	for (int i = 0; i < 2; ++i) { if (ctx->psStage[i]) { (void)hipHostFree(ctx->psStage[i]); (void)hipEventDestroy(ctx->psStageEv[i]); } }
 	vgx_rccl_release(ctx);
 	if (ctx->evCreated) {
 		for (int r = 0; r < VGX_PROF_RING; ++r) { for (int i = 0; i <= VGX_MAX_STAGES; ++i) { (void)hipEventDestroy(ctx->ev[r][i]); } }
@@ -1108,32 +1086,10 @@ int vgx_pathset_validate(const vgx_pathset_desc* desc)
 }
 
 // The caller's arrays are ordinary host memory: hipMemcpyAsync moves them (the runtime pins pageable ranges in place for large
-// copies: 22 GB/s cold, 55 GB/s for a range it has seen, profiles/micro/h2d_probe.hip), or -- VGX_PS_UPLOAD=stage at vgx_create --
-// two 8 MB pinned buffers of the context, filled by memcpy while the other one is on the wire (28 GB/s whatever the runtime does).
+// copies: 22 GB/s cold, 55 GB/s for a range it has seen, profiles/micro/h2d_probe.hip).
 static int psUpload(vgx_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s)
 {
-	if (!bytes) { return VGX_OK; }
-	if (!ctx->optPsStage) {
-		HIPCHK(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-		return VGX_OK;
-	}
-	const size_t chunk = (size_t)8 << 20;
-	for (int i = 0; i < 2; ++i) {
-		if (!ctx->psStage[i]) {
-			HIPCHK(ctx, hipHostMalloc(&ctx->psStage[i], chunk, hipHostMallocDefault));
-			HIPCHK(ctx, hipEventCreateWithFlags(&ctx->psStageEv[i], hipEventDisableTiming));
-			ctx->psStageBusy[i] = false;
-		}
-	}
-	for (size_t o = 0; o < bytes; o += chunk) {
-		const int i = (int)(ctx->psStageK++ & 1u);
-		const size_t n = bytes - o < chunk ? bytes - o : chunk;
-		if (ctx->psStageBusy[i]) { HIPCHK(ctx, hipEventSynchronize(ctx->psStageEv[i])); }
-		memcpy(ctx->psStage[i], (const uint8_t*)src + o, n);
-		HIPCHK(ctx, hipMemcpyAsync((uint8_t*)dst + o, ctx->psStage[i], n, hipMemcpyHostToDevice, s));
-		HIPCHK(ctx, hipEventRecord(ctx->psStageEv[i], s));
-		ctx->psStageBusy[i] = true;
-	}
+	if (bytes) { HIPCHK(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s)); }
 	return VGX_OK;
 }
 
@@ -1210,10 +1166,6 @@ int vgx_pathset_create(vgx_ctx* ctx, const vgx_pathset_desc* desc, vgx_pathset**
 	if (nargs && !desc->args) { return VGX_E_INVALID_ARG; }
 	const VgxPsLayout L = psLayout(ncmd, npaths, nargs);
 	int st;
-	static const bool timing = getenv("VGX_PS_TIMING") != nullptr; // tuning aid: host clock after each stage of the call, to stderr
-	double tq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-	auto now = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; };
-	if (timing) { tq[0] = now(); }
 	// temporaries of the build (grow-only context scratch): four words per command, the scans' partials, the totals
 	auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
 	// layout: [totals (256 B) | pathAt] (cleared by ONE memset) | pathOf | lastSubEx | nvEx | partials
@@ -1238,7 +1190,6 @@ int vgx_pathset_create(vgx_ctx* ctx, const vgx_pathset_desc* desc, vgx_pathset**
 		delete ps;
 		return VGX_E_HIP;
 	}
-	if (timing) { tq[1] = now(); }
 	uint8_t* b = (uint8_t*)ps->blob;
 	uint8_t* t = (uint8_t*)ctx->psTemp.p;
 	auto fail = [&](int code) { (void)hipStreamSynchronize(s); (void)hipFree(ps->blob); delete ps; return code; };
@@ -1264,7 +1215,6 @@ int vgx_pathset_create(vgx_ctx* ctx, const vgx_pathset_desc* desc, vgx_pathset**
 		memcpy(im + L.oPathBegin, desc->path_cmd_begin, ((size_t)npaths + 1) * sizeof(uint32_t));
 		if (ncmd) { memcpy(im + L.oType, desc->cmd_type, ncmd); }
 		im[L.oType + ncmd] = 0;
-		if (timing) { tq[2] = now(); }
 		e = hipMemcpyAsync(b, im, L.rawEnd, hipMemcpyHostToDevice, s);
 		if (e != hipSuccess) { ctx->lastHipError = (int)e; return fail(VGX_E_HIP); }
 	} else {
@@ -1281,18 +1231,10 @@ int vgx_pathset_create(vgx_ctx* ctx, const vgx_pathset_desc* desc, vgx_pathset**
 	B.subBegin = (uint32_t*)(b + L.oSubBegin); B.subLast = (uint32_t*)(b + L.oSubLast); B.tp = (VgxThinPath*)(b + L.oThinPath); B.ts = (VgxThinSub*)(b + L.oThinSub);
 	B.pathAt = (uint32_t*)(t + tW); B.pathOf = (uint32_t*)(t + tW + words); B.lastSubEx = (uint32_t*)(t + tW + 2 * words); B.nvEx = (uint32_t*)(t + tW + 3 * words);
 	B.partialA = (VgxPsM*)(t + tPartA); B.partialB = (Sum3*)(t + tPartB); B.tot = (VgxPsTotals*)(t + tTot);
-	if (timing) { tq[3] = now(); }
 	vgx_launch_pathset_build(B, maybeThin, s);
 	e = hipGetLastError();
-	if (timing) { tq[4] = now(); }
 	if (e == hipSuccess) { e = hipMemcpyAsync(ctx->hostPs, B.tot, sizeof(VgxPsTotals), hipMemcpyDeviceToHost, s); }
-	if (timing) { tq[5] = now(); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(s); }
-	if (timing) {
-		tq[6] = now();
-		fprintf(stderr, "vgx_pathset_create ncmd=%u small=%d: alloc %.1f  image %.1f  h2d %.1f  launch %.1f  d2h %.1f  sync %.1f  total %.1f us\n", ncmd, (int)small,
-			tq[1] - tq[0], tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4], tq[6] - tq[5], tq[6] - tq[0]);
-	}
 	if (e != hipSuccess) { ctx->lastHipError = (int)e; return fail(VGX_E_HIP); }
 	const VgxPsTotals T = *ctx->hostPs;
 	if (T.err) {
@@ -1788,7 +1730,7 @@ static bool tmplEligible(const VgxTotals& ht, bool roundOk)
 static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, vgx_sizes* out_sizes, hipStream_t s)
 {
 	ctx->tmplOn = false;
-	if (!ctx->optTmpl || !ctx->optInst || ctx->optTwoPass || (ndraws <= VGX_SMALL_DRAWS && !ctx->optTmplBatch) || ndraws == 0) { return VGX_OK; } // (static batches: frame-sized draw lists too)
+	if (!ctx->optTmpl || !ctx->optInst || (ndraws <= VGX_SMALL_DRAWS && !ctx->optTmplBatch) || ndraws == 0) { return VGX_OK; } // (static batches: frame-sized draw lists too)
 	int st;
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
@@ -2078,7 +2020,7 @@ int vgx_tessellate_count(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* dr
 	// the one-walk route for vgx_tessellate's flatten stage? Unrelated draws (no instancing), curves (not a lineTo-only set), and long ones:
 	// >= 10 polyline vertices per command instance (VGX_TESS_FLAT1=2: whatever their length; the two routes cross between 7.5 and 12.6, profiles/experiments/r06_cubics_tessellate_boxes.txt). Sized here, so that the steady state allocates nothing.
 	ctx->f1Route = false;
-	if (ctx->optTessFlat1 && !ctx->optTwoPass && ndraws > VGX_SMALL_DRAWS && !instPeriodFor(ctx, ndraws) && !instGroupedFor(ctx, ps, ndraws)
+	if (ctx->optTessFlat1 && ndraws > VGX_SMALL_DRAWS && !instPeriodFor(ctx, ndraws) && !instGroupedFor(ctx, ps, ndraws)
 		&& !(ps->thinStatic && ctx->optThinStatic) && sz.num_cmd_instances != 0
 		&& (ctx->optTessFlat1 == 2 || sz.num_poly_vertices >= 10 * sz.num_cmd_instances)) {
 		int cap; uint32_t segMax;
@@ -2140,26 +2082,21 @@ int vgx_tessellate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
 	ctx->lastStage = 0;
-	if (ndraws <= VGX_SMALL_DRAWS && !ctx->optTwoPass && !ctx->optNoSmall) { // (round 6: also with draw-command assembly armed -- runStrokeEmit runs the partition kernels in front of the emit either way)
+	if (ndraws <= VGX_SMALL_DRAWS && !ctx->optNoSmall) { // (round 6: also with draw-command assembly armed -- runStrokeEmit runs the partition kernels in front of the emit either way)
 		const int est = runFrameSized(ctx, ps, draws, ndraws, out, 0, dev_sizes, dev_status, s);
 		if (est != VGX_OK) { return est; }
 		if (ctx->asmArmed) { publish(ctx, dev_sizes, dev_status, s); } // the partition kernels may have ended the call (a mesh beyond any vertex buffer, the command table full): the verdict once more
 		return launchStatus(ctx);
 	}
-	const bool oneWalk = ctx->f1Route && ps == ctx->f1RoutePs && ps->gen == ctx->f1RoutePsGen && !ctx->optTwoPass && !instPeriodFor(ctx, ndraws) && !instGroupedFor(ctx, ps, ndraws)
+	const bool oneWalk = ctx->f1Route && ps == ctx->f1RoutePs && ps->gen == ctx->f1RoutePsGen && !instPeriodFor(ctx, ndraws) && !instGroupedFor(ctx, ps, ndraws)
 		&& f1RouteSegmentsFor(ps, ndraws, ctx->f1RouteSegMax) <= ctx->f1RouteSegBound; // (what the last count decided and sized, for this path set)
-	if (!oneWalk) { runCmdPrefix(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, s, ctx->optTwoPass ? 0u : instPeriodFor(ctx, ndraws)); }
+	if (!oneWalk) { runCmdPrefix(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, s, instPeriodFor(ctx, ndraws)); }
 	if (oneWalk) {
 		runFlattenOneWalk(ctx, ps, draws, ndraws, s);
-	} else if (ctx->optTwoPass) { // tuning / debugging knob: the ordered two-pass flatten
-		runFlattenCount(ctx, ps, draws, ndraws, ctx->caps, s);
-		VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, 1);
-		vgx_launch_flatten(true, a, VGX_GRID_BLOCKS, s);
-		mark(ctx, s, "flatten_emit");
 	} else {
 		runFlattenBuild(ctx, ps, draws, ndraws, s);
 	}
-	runStrokeCount(ctx, draws, outCapsFor(ctx, out), 1, s, nullptr, !ctx->optTwoPass, out->meshes);
+	runStrokeCount(ctx, draws, outCapsFor(ctx, out), 1, s, nullptr, true, out->meshes);
 	{
 		const int st = runStrokeEmit(ctx, draws, out, s, nullptr, true);
 		if (st != VGX_OK) { return st; }
@@ -2723,7 +2660,7 @@ int vgx_cache_cull(vgx_ctx* ctx, const vgx_cache_desc* cache, const float* mesh_
 	VgxCullArgs a;
 	memset(&a, 0, sizeof(a));
 	a.cache_meshes = cache->num_meshes; a.mesh_bounds = mesh_bounds; a.inst = inst; a.ninst = ninst;
-	a.views = views; a.nviews = nviews; a.wave_min = ctx->optCullWaveMin; a.inst_view = inst_view;
+	a.views = views; a.nviews = nviews; a.inst_view = inst_view;
 	a.out_inst = out->inst; a.out_bounds = out->bounds; a.flags = compact ? ctx->cullFlags.ptr() : nullptr; a.status = dev_status;
 	vgx_launch_cache_cull(a, out->kept, out->num_kept, ctx->cullPartial.p, s);
 	return launchStatus(ctx);

@@ -11,9 +11,7 @@
 // The caller's `bounds` array is the only table: no scratch, no host synchronisation, nothing of the context is touched.
 //
 // vgx_cache_cull:
-//   k_cache_cull     one lane per instance (vgx_bounds.h: range union -> corners through v2xform -> cull rule). A range of at least
-//                    `waveMin` meshes can be reduced by the whole wave instead, 64 boxes (1 KB) per step; measured, that does not pay
-//                    (10 000 ranges of 435 boxes: 0.101 against 0.067 ms), so it is off unless VGX_CULL_WAVE_MIN asks for it
+//   k_cache_cull     one lane per instance (vgx_bounds.h: range union -> corners through v2xform -> cull rule)
 //   scan OpCullKept  (vgx_scan.h) the dense ascending list of the kept instances, skipped when the caller wants neither list nor count
 #include "vgx_internal.h"
 #include "vgx_wave.h"
@@ -124,49 +122,14 @@ __global__ __launch_bounds__(VGX_WAVE) void k_bounds_flat(const float2* pos, con
 }
 
 // ---- vgx_cache_cull ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float shfl_xor_f(float v, int d) { return __shfl_xor(v, d); }
-
 __global__ __launch_bounds__(256) void k_cache_cull(VgxCullArgs A)
 {
 	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	const int lane = threadIdx.x & (VGX_WAVE - 1);
-	const bool live = i < A.ninst;
-	vgx_cache_instance in;
-	in.first_mesh = 0; in.num_meshes = 0; in.color = 0;
-	for (int k = 0; k < 6; ++k) { in.mtx[k] = 0.0f; }
-	uint32_t view = 0;
-	bool valid = false;
-	if (live) {
-		in = A.inst[i];
-		view = A.inst_view ? A.inst_view[i] : 0u;
-		valid = vgx_cull_valid(in, A.cache_meshes, view, A.nviews);
-	}
-	const uint32_t n = valid ? in.num_meshes : 0u;
-	const bool byWave = n >= A.wave_min; // wave_min >= 1
-	VgxBox L = vgx_box_empty();
-	if (!byWave) { L = vgx_box_union_range(A.mesh_bounds, in.first_mesh, n); }
-	// long ranges, one after the other, by every lane of the wave (dead lanes included: the loop is wave-uniform)
-	uint64_t todo = wave_ballot(byWave);
-	while (todo) {
-		const int src = __ffsll((long long)todo) - 1;
-		todo &= todo - 1;
-		const uint64_t first = wave_bcast_u64(in.first_mesh, src);
-		const uint32_t cnt = wave_bcast_u32(n, src);
-		VgxBox P = vgx_box_empty();
-		const float4* mb = (const float4*)A.mesh_bounds + first;
-		for (uint32_t k = lane; k < cnt; k += VGX_WAVE) {
-			const float4 q = mb[k];
-			VgxBox b; b.minx = q.x; b.miny = q.y; b.maxx = q.z; b.maxy = q.w;
-			P = vgx_box_union(P, b);
-		}
-#pragma unroll
-		for (int d = 32; d >= 1; d >>= 1) {
-			VgxBox o; o.minx = shfl_xor_f(P.minx, d); o.miny = shfl_xor_f(P.miny, d); o.maxx = shfl_xor_f(P.maxx, d); o.maxy = shfl_xor_f(P.maxy, d);
-			P = vgx_box_union(P, o);
-		}
-		if (lane == src) { L = P; }
-	}
-	if (!live) { return; }
+	if (i >= A.ninst) { return; }
+	vgx_cache_instance in = A.inst[i];
+	const uint32_t view = A.inst_view ? A.inst_view[i] : 0u;
+	const bool valid = vgx_cull_valid(in, A.cache_meshes, view, A.nviews);
+	const VgxBox L = vgx_box_union_range(A.mesh_bounds, in.first_mesh, valid ? in.num_meshes : 0u);
 	VgxBox B = vgx_box_empty();
 	bool keep = false;
 	if (valid) { keep = vgx_cull_decide(L, in.mtx, A.views + 4 * (uint64_t)view, &B); }

@@ -364,8 +364,6 @@ __global__ __launch_bounds__(VGX_WAVE) void k_flatten(VgxFlattenArgs A)
 //     mesh descriptors in the reference's call order.
 // Degenerate / serial draws are flagged exactly as in the two-pass kernel and handled by k_flatten_serial.
 // ------------------------------------------------------------------------------------------------
-// POOL: the cubics of a chunk are subdivided by the whole wave together (pool_sweep, vgx_walk.h) instead of one cubic per
-// lane in lock-step; same LDS footprint (the pool's task LIFO takes the place of the per-lane stack + leaf slots).
 // Leaves of the per-lane walk kept in LDS per lane before they spill to the wave's global staging area (L2-resident:
 // written and read back by the same wave within one chunk). Fewer LDS bytes per wave = more resident waves.
 #ifndef VGX_BUILD_LEAF_SLOTS
@@ -401,13 +399,11 @@ struct BuildDec // what a lane of k_flatten_build knows about its command instan
 	bool drawHead;
 };
 
-template<bool POOL>
 __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFlattenArgs A)
 {
-	__shared__ __attribute__((aligned(16))) unsigned char s_mem[POOL ? ((VGX_LDS_LEVELS * 3 + BLS) * VGX_WAVE * 8 > VGX_POOL_BYTES ? (VGX_LDS_LEVELS * 3 + BLS) * VGX_WAVE * 8 : VGX_POOL_BYTES) : (VGX_LDS_LEVELS * 3 + BLS) * VGX_WAVE * 8];
+	__shared__ __attribute__((aligned(16))) unsigned char s_mem[(VGX_LDS_LEVELS * 3 + BLS) * VGX_WAVE * 8];
 	float2* s_stack = (float2*)s_mem;                            // per-lane walk: pending stack, then the leaf slots
 	float2* s_leaf = s_stack + VGX_LDS_LEVELS * 3 * VGX_WAVE;
-	const PoolLds pool = pool_carve(s_mem);                      // pooled walk: the same memory
 	const int lane = threadIdx.x;
 	LdsStack stack;
 	stack.base = &s_stack[lane];
@@ -558,49 +554,22 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 				const float tessTol = tol / (scale * scale);
 				v2f q1, q2, q3, q4;
 				q1.x = start.x; q1.y = start.y; q2.x = c1x; q2.y = c1y; q3.x = c2x; q3.y = c2y; q4.x = ex; q4.y = ey;
-				bool poolDeep = false; // POOL: my cubic left the pooled path (deeper than VGX_POOL_MAXD / lists full)
-				uint32_t poolMask = 0;
-				int poolLeaves = 0;
-				if (POOL) {
-					const uint64_t rootMask = wave_ballot(isCubic);
-					if (rootMask) {
-						poolLeaves = pool_walk(pool, lane, rootMask, q1, q2, q3, q4, tessTol);
-						if (isCubic) {
-							const uint32_t fl = pool.flags[lane];
-							poolDeep = (fl & VGX_POOL_F_DEEP) != 0;
-							poolMask = pool.mask[lane];
-							cnt = __popc(poolMask);
-							slow = (fl & VGX_POOL_F_SLOW) != 0;
-						}
-					}
-				}
 				if (valid && !serialDraw) {
 					switch (type) {
 					case VGX_CMD_MOVE_TO: cnt = 1; exists = true; break;
 					case VGX_CMD_LINE_TO: cnt = 1; slow = v2near(start, v2(a[0], a[1])); break;
 					case VGX_CMD_CUBIC_TO:
 					case VGX_CMD_QUAD_TO: {
-						if (POOL) {
-							if (poolDeep) { // count with the per-lane walk; the emit below walks it again, straight to memory
-								FastCubicSink<false, false> sink;
-								sink.prev = start; sink.n = 0; sink.slow = false;
-								wave_flatten_cubic(start.x, start.y, c1x, c1y, c2x, c2y, ex, ey, tessTol, stack, sink);
-								sink.flush();
-								cnt = (int)sink.n;
-								slow = sink.slow;
-							}
-						} else {
-							float2* over = (float2*)A.leaf_overflow + (size_t)blockIdx.x * VGX_BUILD_OVERFLOW * VGX_WAVE + lane;
-							uint32_t nLeaves = 0;
-							if (!build_flatten_hot<VGX_LDS_LEVELS>(q1, q2, q3, q4, tessTol, &s_stack[lane], &s_leaf[lane], over, &nLeaves, &slow)) {
-								BuildCubicSink sink; // nests deeper than the LDS levels: full-depth walk from the root
-								sink.prev = start; sink.n = 0; sink.slow = false; sink.slots = &s_leaf[lane]; sink.over = over;
-								vgx_flatten_cubic(start.x, start.y, c1x, c1y, c2x, c2y, ex, ey, tessTol, stack, sink);
-								nLeaves = sink.n;
-								slow = sink.slow;
-							}
-							cnt = (int)nLeaves;
+						float2* over = (float2*)A.leaf_overflow + (size_t)blockIdx.x * VGX_BUILD_OVERFLOW * VGX_WAVE + lane;
+						uint32_t nLeaves = 0;
+						if (!build_flatten_hot<VGX_LDS_LEVELS>(q1, q2, q3, q4, tessTol, &s_stack[lane], &s_leaf[lane], over, &nLeaves, &slow)) {
+							BuildCubicSink sink; // nests deeper than the LDS levels: full-depth walk from the root
+							sink.prev = start; sink.n = 0; sink.slow = false; sink.slots = &s_leaf[lane]; sink.over = over;
+							vgx_flatten_cubic(start.x, start.y, c1x, c1y, c2x, c2y, ex, ey, tessTol, stack, sink);
+							nLeaves = sink.n;
+							slow = sink.slow;
 						}
+						cnt = (int)nLeaves;
 					} break;
 					case VGX_CMD_POLYLINE: {
 						const uint32_t npts = na >> 1;
@@ -684,11 +653,6 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 						const V2 endp = (type == VGX_CMD_POLYLINE) ? v2(pa[na - 2], pa[na - 1]) : (type == VGX_CMD_CUBIC_TO ? v2(a[4], a[5]) : (type == VGX_CMD_QUAD_TO ? v2(a[2], a[3]) : v2(a[0], a[1])));
 						if (v2near(endp, v2(rec.a[6], rec.a[7]))) { --limit; }
 					}
-					if (POOL && poolLeaves > 0) { // the listed leaves go straight to their places in the heap
-						PoolOutGlobal o;
-						o.p = (float2*)A.poly + cur - 64; // excl is -1 at most (a pathClose pop at the chunk's start)
-						pool_place(pool, lane, poolLeaves, poolMask, isCubic && !poolDeep, (uint32_t)(excl + 64), limit, mtx, o);
-					}
 					if (valid && !serialDraw) {
 						float* out = A.poly + 2 * g;
 						if (type == VGX_CMD_MOVE_TO || type == VGX_CMD_LINE_TO) {
@@ -697,14 +661,7 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 								*(float2*)out = make_float2(p.x, p.y);
 							}
 						} else if (type == VGX_CMD_CUBIC_TO || type == VGX_CMD_QUAD_TO) {
-							if (POOL) {
-								if (poolDeep) {
-									FastCubicSink<true, true> sink;
-									sink.prev = start; sink.n = 0; sink.slow = false; sink.out = out; sink.writeLimit = limit; sink.mtx = mtx; sink.begin();
-									wave_flatten_cubic(start.x, start.y, c1x, c1y, c2x, c2y, ex, ey, tol / (scale * scale), stack, sink);
-									sink.flush();
-								}
-							} else if ((uint32_t)rawCnt <= VGX_LEAF_SLOTS + VGX_BUILD_OVERFLOW) {
+							if ((uint32_t)rawCnt <= VGX_LEAF_SLOTS + VGX_BUILD_OVERFLOW) {
 								const uint32_t nl = limit < VGX_LEAF_SLOTS ? limit : VGX_LEAF_SLOTS;
 #if VGX_BUILD_UNROLL
 								float2 lq[VGX_LEAF_SLOTS]; // every slot requested before the first store (one LDS round trip instead of one per leaf)
@@ -829,7 +786,7 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 // among them) and a search in LDS per lane. Vertex v of draw d goes to poly[cmd_prefix[d] + v]; the exact builder's draws
 // (degenerate paths) are listed and allocate behind poly_heap_cursor = the batch's command instances.
 #define VGX_THIN_THREADS 256
-template<int VGX_THIN_ITEMS>
+#define VGX_THIN_ITEMS 4
 __global__ __launch_bounds__(VGX_THIN_THREADS) void k_flatten_thin(VgxFlattenArgs A)
 {
 	constexpr uint32_t VGX_THIN_CHUNK = VGX_THIN_THREADS * VGX_THIN_ITEMS;
@@ -1324,13 +1281,10 @@ void vgx_launch_flatten_build(const VgxFlattenArgs& a, int waves, hipStream_t s,
 	// small batches run through the heap's block switches and sub-path moves that otherwise need > 8192 vertices per wave
 	if (a.thin_static) { // a set of MOVE_TO / LINE_TO / CLOSE paths: the static layout (vgx_thin.h)
 		const dim3 grid(a.ndraws <= VGX_SMALL_DRAWS ? 64 : 2048); // (frame-sized batches: workgroups that find no chunk still cost their first loads)
-		if (a.thin_static == 2) { hipLaunchKernelGGL(k_flatten_thin<2>, grid, dim3(VGX_THIN_THREADS), 0, s, a); } // (VGX_THIN_STATIC=2: two command instances per thread)
-		else { hipLaunchKernelGGL(k_flatten_thin<4>, grid, dim3(VGX_THIN_THREADS), 0, s, a); }
-		hipLaunchKernelGGL(k_flatten_build<false>, dim3(a.ndraws <= VGX_SMALL_DRAWS ? 64 : waves), dim3(VGX_WAVE), 0, s, a); // (exits at once unless the scratch holds fewer vertices than the batch has commands)
-	} else if (a.pool_walk) {
-		hipLaunchKernelGGL(k_flatten_build<true>, dim3(waves), dim3(VGX_WAVE), 0, s, a);
+		hipLaunchKernelGGL(k_flatten_thin, grid, dim3(VGX_THIN_THREADS), 0, s, a);
+		hipLaunchKernelGGL(k_flatten_build, dim3(a.ndraws <= VGX_SMALL_DRAWS ? 64 : waves), dim3(VGX_WAVE), 0, s, a); // (exits at once unless the scratch holds fewer vertices than the batch has commands)
 	} else {
-		hipLaunchKernelGGL(k_flatten_build<false>, dim3(waves), dim3(VGX_WAVE), 0, s, a);
+		hipLaunchKernelGGL(k_flatten_build, dim3(waves), dim3(VGX_WAVE), 0, s, a);
 	}
 	if (serialCount) { hipLaunchKernelGGL((k_flatten_serial<false, false>), dim3(1024), dim3(256), 0, s, a); } // count + heap allocation
 }

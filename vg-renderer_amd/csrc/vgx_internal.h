@@ -33,7 +33,6 @@ struct VgxFlattenArgs
 	int build_mode;                // k_flatten_serial<count>: allocate the draw's vertices from the polyline heap
 	uint32_t* serial_list;         // BUILD mode: draws for k_flatten_serial (static serial paths + degenerate draws), unordered
 	float* leaf_overflow;          // [VGX_BUILD_WAVES][VGX_BUILD_OVERFLOW][64][2] leaves that did not fit the LDS slots
-	int pool_walk;                 // k_flatten_build: pooled cubic walk (vgx_walk.h) instead of one cubic per lane
 	int thin_static;               // every path of the set is MOVE_TO / LINE_TO / CLOSE only: k_flatten_thin (vgx_thin.h) in k_flatten_build's place
 	// instanced batches (vgx_inst.hip): draws[i].path == draws[i % inst_period].path; 0 = not instanced. When set and the
 	// device-side check of this call agrees, k_flatten_inst builds the batch and k_flatten_build exits at once.
@@ -400,7 +399,6 @@ struct VgxCullArgs
 	uint64_t ninst;
 	const float* views;               // [nviews][4]
 	uint32_t nviews;
-	uint32_t wave_min;                // ranges of at least this many meshes are reduced by the whole wave (>= 1)
 	const uint32_t* inst_view;        // [ninst] or null: view 0
 	vgx_cache_instance* out_inst;     // [ninst]; may be `inst`
 	float* out_bounds;                // [ninst][4] or null
