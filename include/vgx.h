@@ -716,6 +716,54 @@ int vgx_raster(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_boun
                uint32_t* dev_status, void* stream);
 int vgx_raster_reserve(vgx_ctx* ctx, uint64_t num_meshes, uint64_t num_bin_entries);
 
+/* ---- a decoded frame to an image: per-draw scissors and clip regions (vgx_cmdlist_decode -> ... -> vgx_raster_frame) -----------------
+ * vgx_raster draws every mesh of its range under one scissor. vgx_raster_frame is the same call with the state the reference's submit
+ * loop applies between its draw-command table and bgfx: the scissor of each draw command (src/vg.cpp:1226-1235) and the stencil test
+ * against the clip region the draw names (:1162-1219). Everything vgx_raster specifies -- triangles, sample, coverage, colour, blend,
+ * order, mesh_bounds, target, the skipped kinds VGX_MESH_TEXT and VGX_MESH_TRILIST -- holds here word for word; what follows is added
+ * to it, and like it gives the same bytes in every implementation for every input. `state` names two DEVICE arrays indexed by
+ * vgx_mesh::draw: the draws (only state_key is read: type = (state_key >> 16) & 0xF, 3 = Clip) and the vgx_draw_state records as
+ * vgx_cmdlist_decode wrote them.
+ *
+ * Draw scissor. Let d = meshes[m].draw and {x, y, w, h} = draw_state[d].scissor. Pixel (i, j) of the image is frame pixel (X, Y) =
+ *   (x0 + i, y0 + j); it lies inside the draw's scissor iff x <= X < x + w && y <= Y < y + h, in 64-bit integers (device pixel ratio
+ *   1, as in bgfx::setScissor of x, y, w, h). A sample of mesh m takes effect only inside the target's scissor AND the draw's scissor;
+ *   w == 0 or h == 0: the mesh does nothing.
+ * Stamp. Every pixel carries one word S for the duration of the call: the reference's stencil value without its 8-bit wrap. S is NONE
+ *   (0xFFFFFFFF) at the start of every call. Meshes are taken in ascending order, triangles ascending within a mesh, exactly as the
+ *   colour order is specified.
+ * Clip draws. A mesh whose draw has type 3 writes no colour, whatever its vertex colours are: every sample it covers (the coverage
+ *   rule of vgx_raster, the tie rule included) inside both scissors sets S = d. Kind, alpha and winding play no part beyond that rule.
+ * Other draws. Let f = clip_first_draw, n = clip_num_draws, rule = clip_rule of draw d. If f == 0xFFFFFFFF or n == 0 there is no test
+ *   (the reference's BGFX_STENCIL_NONE for a region that is empty or still open). Otherwise the sample passes iff
+ *   (S != NONE && S >= f && S - f < n) == (rule == 0): under Out (rule != 0) a pixel no clip mesh ever touched passes, under In it
+ *   fails. A sample that fails is treated as not covered; one that passes is coloured and blended as in vgx_raster.
+ *   This is the reference's stencil: regions receive ascending reference values, the last writer of a pixel wins, and the users of a
+ *   region all precede the next BeginClip, so "the value the last clip mesh left lies in my region's range" is the EQUAL / NOTEQUAL
+ *   test of src/vg.cpp:1207-1213 against the value of :1162-1219 and 3670-3709.
+ * Range. S does not survive the call: the mesh range must contain the clip meshes of every region its draws use.
+ * Out of scope. Draws of type 1 (ColorGradient) and 2 (ImagePattern) are drawn with their vertex colours, as vgx_raster draws them.
+ *   TEXT and TRILIST meshes are skipped and leave S alone.
+ * dev_status. As vgx_raster, and VGX_E_INVALID_ARG when a mesh of the range (of any kind) has draw >= num_draws: NOTHING was written,
+ *   the clear included. It ranks above VGX_E_GROWN, and VGX_E_RANGE above both; all three are decided in one reduction over the
+ *   meshes, so the status does not depend on the order of the work. A bin entry is a pair of a mesh and a 16 x 16 tile its box
+ *   reaches inside the target's scissor cut by the draw's; the VGX_E_GROWN protocol is the one of vgx_raster, on the same tables, and
+ *   vgx_raster_reserve sizes them for both calls. With an empty target scissor no mesh is looked at and dev_status is VGX_OK.
+ * Host return values. As vgx_raster, and VGX_E_INVALID_ARG for a null `state`, null arrays with num_draws > 0, a misaligned `draws`
+ *   or `draw_state` (4-byte each), reserved != 0.
+ * Side effects. As vgx_raster; beyond its scratch the call keeps 32 bytes per mesh of the range (mode, region, and the two scissors
+ *   cut into one rectangle) in a buffer only this call allocates; vgx_scratch_bytes counts it. A counted state survives:
+ *   vgx_tessellate_count -> vgx_raster_frame -> vgx_tessellate_emit works. */
+typedef struct vgx_raster_draws {
+	const vgx_draw*       draws;       /* DEVICE [num_draws]; only state_key is read: type = (state_key >> 16) & 0xF, 3 = Clip */
+	const struct vgx_draw_state* draw_state; /* DEVICE [num_draws], as vgx_cmdlist_decode wrote them (declared with that call, below) */
+	uint32_t              num_draws;   /* both arrays are indexed by vgx_mesh::draw */
+	uint32_t              reserved;    /* 0 */
+} vgx_raster_draws;
+int vgx_raster_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
+                     uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                     const vgx_raster_target* target, uint32_t* dev_status, void* stream);
+
 /* ---- incremental update (beyond the reference): vgx_cache_submit -> vgx_cache_layout -> [vgx_pick -> edit -> vgx_cache_update]* ----
  * Moving or recolouring an instance of a submitted frame changes nothing of the frame's structure: a cached mesh has a fixed size, so
  * the instance keeps its vertex, index and mesh ranges; indices, mesh records, draw commands and UVs do not depend on the transform.

@@ -142,6 +142,15 @@ class RasterTarget(C.Structure):  # vgx_raster_target: `pixels` is a device poin
 
 
 assert C.sizeof(RasterTarget) == 56
+
+
+class RasterDraws(C.Structure):  # vgx_raster_draws: device arrays of vgx_draw and vgx_draw_state records, indexed by vgx_mesh::draw
+    _fields_ = [("draws", C.c_void_p), ("draw_state", C.c_void_p), ("num_draws", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(RasterDraws) == 24
+DRAW_TYPE_CLIP = 3      # (vgx_draw::state_key >> 16) & 0xF of a clip draw
+CLIP_NONE = 0xFFFFFFFF  # vgx_draw_state::clip_first_draw of a draw without a region
 RASTER_CLEAR = 1
 RASTER_TILE = 16  # a bin entry is a pair of a mesh and a tile of this many pixels a side
 
@@ -243,6 +252,8 @@ VGX_SYMBOLS = {
     "vgx_pick": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vgx_raster": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
     "vgx_raster_reserve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "vgx_raster_frame": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.POINTER(RasterTarget), C.c_void_p,
+                                  C.c_void_p]),
     "vgx_cache_layout": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_cache_update": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                    C.POINTER(UpdateFrame), C.c_void_p, C.c_void_p]),

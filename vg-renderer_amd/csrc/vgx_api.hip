@@ -108,6 +108,7 @@ struct vgx_ctx
 	// in tile order; the sort's temporary storage; status and entry count of the last call with their pinned mirror (as `dash`: a call
 	// whose entries outgrew the tables ends with VGX_E_GROWN and the next one grows first). Its own: a counted state survives the call
 	Buf<uint32_t> rasMeshEntries, rasKeys, rasVals, rasSortedKeys, rasSortedVals; Buf<uint64_t> rasMeshFirst; Buf<unsigned long long> rasState; Buf<float> rasBounds;
+	Buf<VgxRasterMeshState> rasFrameMesh; // vgx_raster_frame alone: what every mesh of the range does under its draw (vgx_raster.h)
 	DevBuf rasSortTemp, rasPartial;      // rasPartial: slice sums (views: as `partial`)
 	HostMirror<unsigned long long> ras;
 	uint32_t optPickGrid;                // workgroups of k_pick_tris (VGX_PICK_GRID)
@@ -2731,11 +2732,18 @@ int vgx_raster_reserve(vgx_ctx* ctx, uint64_t num_meshes, uint64_t num_bin_entri
 	return rasterEnsure(ctx, num_meshes, num_bin_entries);
 }
 
-int vgx_raster(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
+namespace {
+
+// vgx_raster (state == nullptr) and vgx_raster_frame: one body, the kernels differ
+int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
                const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
 	if (!ctx || !frame || !target) { return VGX_E_INVALID_ARG; }
+	if (state) {
+		if (state->reserved != 0u || (state->num_draws && (!state->draws || !state->draw_state))) { return VGX_E_INVALID_ARG; }
+		if (((uintptr_t)state->draws & 3u) || ((uintptr_t)state->draw_state & 3u)) { return VGX_E_INVALID_ARG; }
+	}
 	const vgx_raster_target& t = *target;
 	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
 	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
@@ -2790,10 +2798,33 @@ int vgx_raster(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_boun
 	a.mesh_entries = ctx->rasMeshEntries.ptr(); a.mesh_first = ctx->rasMeshFirst.ptr();
 	a.keys = ctx->rasKeys.ptr(); a.vals = ctx->rasVals.ptr(); a.sorted_keys = ctx->rasSortedKeys.ptr(); a.sorted_vals = ctx->rasSortedVals.ptr();
 	a.state = ctx->rasState.ptr(); a.status = dev_status;
-	noteHip(ctx, vgx_launch_raster(a, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+	if (state) {
+		if ((st = ensure(ctx, ctx->rasFrameMesh, nrange + 1)) != VGX_OK) { return st; }
+		VgxRasterFrameArgs f;
+		memset(&f, 0, sizeof(f));
+		f.R = a; f.draws = state->draws; f.draw_state = state->draw_state; f.num_draws = state->num_draws; f.mesh_state = ctx->rasFrameMesh.ptr();
+		noteHip(ctx, vgx_launch_raster_frame(f, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+	} else {
+		noteHip(ctx, vgx_launch_raster(a, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+	}
 	// status and entry count to the mirror, for the next call (never waited for)
 	ctx->ras.push(ctx, a.state, s);
 	return launchStatus(ctx);
+}
+
+} // namespace
+
+int vgx_raster(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
+               const vgx_raster_target* target, uint32_t* dev_status, void* stream)
+{
+	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, nullptr, target, dev_status, stream);
+}
+
+int vgx_raster_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
+                     const vgx_raster_draws* state, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
+{
+	if (!state) { return VGX_E_INVALID_ARG; }
+	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, target, dev_status, stream);
 }
 
 // ---- incremental update of a submitted frame (vgx_update.hip) -------------------------------------------------------------

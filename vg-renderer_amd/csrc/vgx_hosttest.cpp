@@ -597,6 +597,79 @@ int vgxt_raster(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t 
 	return VGX_OK;
 }
 
+// vgx_raster_frame on the host: vgxt_raster's loop with the per-draw state of vgx_raster.h and a stamp image of its own. HOST pointers
+// throughout. The meshes are looked at twice: first for a draw index outside the table (nothing may be written then), then drawn.
+int vgxt_raster_frame(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                      const vgx_raster_target* target, uint32_t* status)
+{
+	if (!frame || !target || !state) { return VGX_E_INVALID_ARG; }
+	if (state->reserved != 0u || (state->num_draws && (!state->draws || !state->draw_state))) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)state->draws & 3u) || ((uintptr_t)state->draw_state & 3u)) { return VGX_E_INVALID_ARG; }
+	const vgx_raster_target& t = *target;
+	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
+	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
+	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
+		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
+	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
+	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	if (status) { *status = VGX_OK; }
+	if (empty) { return VGX_OK; }
+	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
+	for (uint64_t m = mesh_begin; m < end; ++m) {
+		if (frame->meshes[m].draw >= state->num_draws) {
+			if (status) { *status = VGX_E_INVALID_ARG; }
+			return VGX_OK;
+		}
+	}
+	float* own = nullptr;
+	if (!mesh_bounds && mesh_begin < end) {
+		own = (float*)malloc(frame->num_meshes * 4 * sizeof(float));
+		if (!own) { return VGX_E_INTERNAL; }
+		vgxt_mesh_bounds(frame->pos, frame->meshes, frame->num_meshes, own);
+	}
+	uint32_t* stamp = (uint32_t*)malloc((size_t)t.width * t.height * sizeof(uint32_t));
+	if (!stamp) { free(own); return VGX_E_INTERNAL; }
+	for (size_t k = 0; k < (size_t)t.width * t.height; ++k) { stamp[k] = VGX_RASTER_STAMP_NONE; }
+	if (t.flags & VGX_RASTER_CLEAR) {
+		for (uint32_t j = t.scissor[1]; j < t.scissor[3]; ++j) {
+			for (uint32_t i = t.scissor[0]; i < t.scissor[2]; ++i) { t.pixels[(uint64_t)j * t.stride + i] = t.clear_color; }
+		}
+	}
+	for (uint64_t m = mesh_begin; m < end; ++m) {
+		const vgx_mesh me = frame->meshes[m];
+		VgxRasterMeshState ms;
+		vgx_raster_mesh_state(me.draw, state->draws[me.draw].state_key, state->draw_state[me.draw], t.x0, t.y0, t.scissor, &ms);
+		VgxRasterRect r;
+		if (ms.mode == VGX_RF_NOTHING || !vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, ms.rect, &r)) { continue; }
+		const uint16_t* ip = frame->idx + me.first_index;
+		const float* pp = frame->pos + 2 * me.first_vertex;
+		const uint32_t* cp = frame->color + me.first_vertex;
+		for (uint32_t k = 0; k < me.num_indices / 3u; ++k) {
+			const uint32_t i0 = ip[3 * k], i1 = ip[3 * k + 1], i2 = ip[3 * k + 2];
+			if (i0 >= me.num_vertices || i1 >= me.num_vertices || i2 >= me.num_vertices) { continue; }
+			VgxRasterTri T;
+			if (!vgx_raster_setup(v2(pp[2 * i0], pp[2 * i0 + 1]), v2(pp[2 * i1], pp[2 * i1 + 1]), v2(pp[2 * i2], pp[2 * i2 + 1]), cp[i0], cp[i1], cp[i2], &T)) { continue; }
+			uint32_t a0, a1, b0, b1;
+			if (!vgx_raster_span(T.minx, T.maxx, t.x0, ms.rect[0], ms.rect[2], &a0, &a1) || !vgx_raster_span(T.miny, T.maxy, t.y0, ms.rect[1], ms.rect[3], &b0, &b1)) { continue; }
+			for (uint32_t j = b0; j <= b1; ++j) {
+				for (uint32_t i = a0; i <= a1; ++i) {
+					uint32_t* const p = t.pixels + (uint64_t)j * t.stride + i;
+					const uint32_t d = vgx_raster_frame_pixel(T, ms.mode, ms.f, ms.n, (double)(t.x0 + (int32_t)i) + 0.5, (double)(t.y0 + (int32_t)j) + 0.5,
+					                                          stamp + (size_t)j * t.width + i, *p);
+					if (d != *p) { *p = d; }
+				}
+			}
+		}
+	}
+	free(stamp);
+	free(own);
+	return VGX_OK;
+}
+
 // the pieces, for the tests of the predicate: the two canonical values of one directed edge u->v in a triangle of orientation
 // `positive`, at (px, py), and whether the edge takes a tie
 double vgxt_raster_edge(const float* u, const float* v, int positive, double px, double py, int* tie)

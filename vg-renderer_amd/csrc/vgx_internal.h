@@ -473,4 +473,16 @@ struct VgxRasterArgs
 size_t vgx_raster_sort_bytes(uint64_t n, uint32_t bits); // temporary storage the sort of n entries wants; 0: the query failed
 hipError_t vgx_launch_raster(const VgxRasterArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
 
+// ... with per-draw scissors and clip regions (vgx_raster_frame): the same arguments and tables, the draw state, and per mesh of the
+// range what k_rasterf_count made of it (vgx_raster.h)
+struct VgxRasterMeshState;
+struct VgxRasterFrameArgs
+{
+	VgxRasterArgs R;
+	const vgx_draw* draws; const vgx_draw_state* draw_state; // [num_draws], checked by the host
+	uint32_t num_draws;
+	VgxRasterMeshState* mesh_state;   // [nrange] (context scratch)
+};
+hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
+
 #endif

@@ -163,4 +163,59 @@ VGX_HD bool vgx_raster_mesh_tiles(const vgx_mesh& me, const float* box, int32_t 
 	return true;
 }
 
+// ---- vgx_raster_frame: per-draw scissors and clip regions (include/vgx.h) -------------------------------------------------
+#define VGX_RASTER_STAMP_NONE 0xFFFFFFFFu // S of a pixel no clip mesh has touched; clip_first_draw of a draw without a region
+// what a mesh does with the stamp
+enum { VGX_RF_PLAIN = 0, VGX_RF_IN = 1, VGX_RF_OUT = 2, VGX_RF_STAMP = 3, VGX_RF_NOTHING = 4, VGX_RF_INVALID = 5 };
+// Per mesh of the range (context scratch of vgx_raster_frame only). rect = the target's scissor cut by the draw's, in image pixels,
+// half open; f, n = the region of a tested mesh, f = the mesh's draw for VGX_RF_STAMP
+struct VgxRasterMeshState { uint32_t mode, f, n, pad; uint32_t rect[4]; }; // 32 bytes
+
+VGX_HD uint32_t vgx_raster_draw_type(uint32_t stateKey) { return (stateKey >> 16) & 0xFu; } // 3 = Clip
+
+// Frame pixels [s, s + w) as pixels of the image (pixel i is frame pixel origin + i) inside [c0, c1): 64-bit integers. false: none
+VGX_HD bool vgx_raster_draw_span(uint16_t s, uint16_t w, int32_t origin, uint32_t c0, uint32_t c1, uint32_t* i0, uint32_t* i1)
+{
+	int64_t a = (int64_t)s - (int64_t)origin, b = a + (int64_t)w;
+	if (a < (int64_t)c0) { a = (int64_t)c0; }
+	if (b > (int64_t)c1) { b = (int64_t)c1; }
+	if (a >= b) { return false; }
+	*i0 = (uint32_t)a; *i1 = (uint32_t)b;
+	return true;
+}
+
+VGX_HD bool vgx_raster_stamp_pass(uint32_t S, uint32_t f, uint32_t n, uint32_t rule)
+{
+	return (S != VGX_RASTER_STAMP_NONE && S >= f && S - f < n) == (rule == 0u);
+}
+
+// The state of mesh `me` under its draw (d < num_draws is the caller's check)
+VGX_HD void vgx_raster_mesh_state(uint32_t d, uint32_t stateKey, const vgx_draw_state& ds, int32_t x0, int32_t y0, const uint32_t* scissor, VgxRasterMeshState* st)
+{
+	st->pad = 0u; st->f = 0u; st->n = 0u;
+	if (!vgx_raster_draw_span(ds.scissor[0], ds.scissor[2], x0, scissor[0], scissor[2], &st->rect[0], &st->rect[2])
+	 || !vgx_raster_draw_span(ds.scissor[1], ds.scissor[3], y0, scissor[1], scissor[3], &st->rect[1], &st->rect[3])) {
+		st->rect[0] = st->rect[1] = st->rect[2] = st->rect[3] = 0u;
+		st->mode = VGX_RF_NOTHING;
+		return;
+	}
+	if (vgx_raster_draw_type(stateKey) == 3u) { st->mode = VGX_RF_STAMP; st->f = d; return; }
+	if (ds.clip_first_draw == VGX_RASTER_STAMP_NONE || ds.clip_num_draws == 0u) { st->mode = VGX_RF_PLAIN; return; }
+	st->mode = ds.clip_rule == 0u ? VGX_RF_IN : VGX_RF_OUT;
+	st->f = ds.clip_first_draw; st->n = ds.clip_num_draws;
+}
+
+// The triangle of a mesh of state (mode, f, n) on the pixel whose sample is (px, py) and lies inside the mesh's rect: the pixel's
+// new value; *S is the pixel's stamp
+VGX_HD uint32_t vgx_raster_frame_pixel(const VgxRasterTri& T, uint32_t mode, uint32_t f, uint32_t n, double px, double py, uint32_t* S, uint32_t dst)
+{
+	if (mode == VGX_RF_STAMP) {
+		double E[3], sum;
+		if (vgx_raster_cover(T, px, py, E, &sum)) { *S = f; }
+		return dst;
+	}
+	if (mode != VGX_RF_PLAIN && !vgx_raster_stamp_pass(*S, f, n, mode == VGX_RF_IN ? 0u : 1u)) { return dst; }
+	return vgx_raster_pixel(T, px, py, dst);
+}
+
 #endif

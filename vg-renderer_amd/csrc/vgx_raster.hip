@@ -169,6 +169,185 @@ __global__ __launch_bounds__(256) void k_raster_tiles(VgxRasterArgs A)
 	if (inside && (clear || d != before)) { *pixel = d; }
 }
 
+// ---- vgx_raster_frame: the same four steps with the state of every mesh's draw ------------------------------------------------
+//   k_rasterf_count    also decides what the mesh does (VgxRasterMeshState: stamp / test In / test Out / untested / nothing, its region,
+//                      the target's scissor cut by its draw's) and keeps that per mesh of the range; the tiles are those of the box
+//                      inside that rectangle. A draw index outside the table marks the mesh, the scan's third lane carries the mark
+//                      to finish(), which ends the call with VGX_E_INVALID_ARG before anything is written
+//   k_rasterf_tiles    k_raster_tiles with one more register per pixel, the stamp S, carried across all batches; the state of the
+//                      meshes in hand lies in LDS beside s_mesh (12 bytes: mode and the rectangle cut to the tile in one word, f, n),
+//                      a setup record names its mesh's slot there and carries the mode and the rectangle as row / column masks. A triangle is tested against the tile cut by BOTH scissors, so
+//                      what a cut draw cannot write never reaches the pixel loop; clip triangles take the same ordered compaction
+__global__ __launch_bounds__(256) void k_rasterf_count(VgxRasterFrameArgs F)
+{
+	const VgxRasterArgs& A = F.R;
+	const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= A.nrange) { return; }
+	const uint64_t m = A.mesh_begin + k;
+	const vgx_mesh me = A.meshes[m];
+	VgxRasterMeshState st;
+	uint32_t entries = 0;
+	if (me.draw >= F.num_draws) {
+		st.mode = VGX_RF_INVALID; st.f = st.n = st.pad = 0u;
+		st.rect[0] = st.rect[1] = st.rect[2] = st.rect[3] = 0u;
+	} else {
+		vgx_raster_mesh_state(me.draw, F.draws[me.draw].state_key, F.draw_state[me.draw], A.x0, A.y0, A.scissor, &st);
+		const float4 box = ((const float4*)A.mesh_bounds)[m];
+		const float b[4] = { box.x, box.y, box.z, box.w };
+		VgxRasterRect r;
+		if (st.mode != VGX_RF_NOTHING && vgx_raster_mesh_tiles(me, b, A.x0, A.y0, st.rect, &r)) { entries = (r.tx1 - r.tx0 + 1u) * (r.ty1 - r.ty0 + 1u); }
+	}
+	F.mesh_state[k] = st;
+	A.mesh_entries[k] = entries;
+}
+
+struct OpRasterFrameBin
+{
+	VgxRasterFrameArgs F;
+	__device__ uint64_t size() const { return F.R.nrange; }
+	__device__ Sum3 load(uint64_t i) const
+	{
+		Sum3 r = sum3_zero();
+		r.a = F.R.mesh_entries[i];
+		r.b = r.a ? F.R.meshes[F.R.mesh_begin + i].num_indices / 3u : 0u;
+		r.c = F.mesh_state[i].mode == VGX_RF_INVALID ? 1u : 0u;
+		return r;
+	}
+	__device__ void store(uint64_t i, Sum3 e) const { F.R.mesh_first[i] = e.a; }
+	__device__ void finish(Sum3 t) const
+	{
+		const VgxRasterArgs& A = F.R;
+		uint32_t st = VGX_OK;
+		if (t.a > A.entry_cap) { st = VGX_E_GROWN; }
+		if (t.c != 0u) { st = VGX_E_INVALID_ARG; }
+		if (t.a > 0xFFFFFFFFull || t.b > 0xFFFFFFFFull) { st = VGX_E_RANGE; }
+		A.state[0] = st; A.state[1] = t.a;
+		if (A.status) { *A.status = st; }
+	}
+};
+
+__global__ __launch_bounds__(256) void k_rasterf_entries(VgxRasterFrameArgs F)
+{
+	const VgxRasterArgs& A = F.R;
+	if (A.state[0] != VGX_OK) { return; }
+	const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= A.state[1] && k < A.sort_n) { A.keys[k] = A.sentinel; A.vals[k] = 0u; }
+	if (k >= A.nrange || A.mesh_entries[k] == 0u) { return; }
+	const uint64_t m = A.mesh_begin + k;
+	const float4 box = ((const float4*)A.mesh_bounds)[m];
+	const float b[4] = { box.x, box.y, box.z, box.w };
+	const VgxRasterMeshState st = F.mesh_state[k];
+	VgxRasterRect r;
+	if (!vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, st.rect, &r)) { return; } // (not taken: the count found entries)
+	uint64_t at = A.mesh_first[k]; // + the mesh's entries <= the total <= entry_cap: checked by finish()
+	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
+		for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx, ++at) { A.keys[at] = ty * A.tiles_w + tx; A.vals[at] = (uint32_t)m; }
+	}
+}
+
+// 112 bytes: the record; its mesh's slot in s_state | mode << 8; the mesh's rectangle in this tile as a mask of columns (bits 0 .. 15)
+// and a mask of rows (bits 16 .. 31), so that a pixel's test is two shifts and an AND
+struct VgxRasterFrameTri { VgxRasterTri T; uint32_t slot_mode, mask; };
+struct VgxRasterTileState { uint32_t mode_rect, f, n; };          // mode << 20 | y1 << 15 | x1 << 10 | y0 << 5 | x0, tile-local, half open
+
+__global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
+{
+	__shared__ VgxRasterFrameTri s_tri[256];
+	__shared__ uint64_t s_first[257];   // exclusive prefix of the triangle counts of the (at most 256) meshes in hand
+	__shared__ uint32_t s_mesh[256];
+	__shared__ VgxRasterTileState s_state[256];
+	__shared__ Sum3 s_wave[4];
+	__shared__ uint32_t s_count[4];
+	const VgxRasterArgs& A = F.R;
+	if (A.state[0] != VGX_OK) { return; }
+	const uint32_t tid = threadIdx.x;
+	const int lane = tid & (VGX_WAVE - 1);
+	const uint32_t wave = tid >> 6;
+	const uint32_t tx = A.tile_x0 + blockIdx.x, ty = A.tile_y0 + blockIdx.y;
+	const uint32_t lx = tid & 15u, ly = tid >> 4;
+	const uint32_t ox = tx * VGX_RASTER_TILE, oy = ty * VGX_RASTER_TILE;
+	const uint32_t i = ox + lx, j = oy + ly;
+	const bool inside = i >= A.scissor[0] && i < A.scissor[2] && j >= A.scissor[1] && j < A.scissor[3];
+	const uint32_t key = ty * A.tiles_w + tx;
+	const uint32_t r0 = lower_bound_u32(A.sorted_keys, A.sort_n, key), r1 = lower_bound_u32(A.sorted_keys, A.sort_n, key + 1u);
+	const bool clear = (A.flags & VGX_RASTER_CLEAR) != 0;
+	if (r0 == r1 && !clear) { return; } // block-uniform
+	uint32_t* const pixel = A.pixels + (uint64_t)j * A.stride + i;
+	const uint32_t before = inside ? (clear ? A.clear_color : *pixel) : 0u;
+	uint32_t d = before;
+	uint32_t S = VGX_RASTER_STAMP_NONE;
+	const double px = (double)(A.x0 + (int32_t)i) + 0.5, py = (double)(A.y0 + (int32_t)j) + 0.5;
+	for (uint32_t eb = r0; eb < r1; eb += 256u) { // block-uniform loops throughout
+		const uint32_t ne = min(256u, r1 - eb);
+		Sum3 v = sum3_zero();
+		if (tid < ne) {
+			const uint32_t m = A.sorted_vals[eb + tid];
+			s_mesh[tid] = m;
+			v.a = A.meshes[m].num_indices / 3u;
+			// the mesh's rectangle cut to this tile (an entry means its box reaches the tile inside the rectangle: not empty)
+			const VgxRasterMeshState ms = F.mesh_state[m - A.mesh_begin];
+			const uint32_t cx0 = max(ox, ms.rect[0]), cx1 = min(ox + VGX_RASTER_TILE, ms.rect[2]);
+			const uint32_t cy0 = max(oy, ms.rect[1]), cy1 = min(oy + VGX_RASTER_TILE, ms.rect[3]);
+			VgxRasterTileState ts;
+			ts.f = ms.f; ts.n = ms.n;
+			ts.mode_rect = cx0 < cx1 && cy0 < cy1 ? (ms.mode << 20) | ((cy1 - oy) << 15) | ((cx1 - ox) << 10) | ((cy0 - oy) << 5) | (cx0 - ox) : (uint32_t)VGX_RF_NOTHING << 20;
+			s_state[tid] = ts;
+		}
+		Sum3 tot;
+		const Sum3 incl = block_incl_scan<256>(v, s_wave, &tot);
+		s_first[tid + 1u] = incl.a;
+		if (tid == 0u) { s_first[0] = 0; }
+		__syncthreads();
+		for (uint64_t tb = 0; tb < tot.a; tb += 256u) {
+			const uint64_t g = tb + tid;
+			bool keep = false;
+			VgxRasterFrameTri R;
+			if (g < tot.a) {
+				uint32_t lo = 0, hi = ne; // the last mesh whose first triangle is <= g
+				while (hi - lo > 1u) {
+					const uint32_t mid = (lo + hi) >> 1;
+					if (s_first[mid] <= g) { lo = mid; } else { hi = mid; }
+				}
+				const uint32_t mr = s_state[lo].mode_rect;
+				const vgx_mesh me = A.meshes[s_mesh[lo]];
+				const uint16_t* ip = A.idx + me.first_index + 3ull * (g - s_first[lo]);
+				const uint32_t i0 = ip[0], i1 = ip[1], i2 = ip[2];
+				if ((mr >> 20) != VGX_RF_NOTHING && i0 < me.num_vertices && i1 < me.num_vertices && i2 < me.num_vertices) {
+					const float2* pp = (const float2*)A.pos + me.first_vertex;
+					const uint32_t* cp = A.color + me.first_vertex;
+					const float2 p0 = pp[i0], p1 = pp[i1], p2 = pp[i2];
+					uint32_t a0, a1, b0, b1;
+					const uint32_t cols = ((1u << ((mr >> 10) & 31u)) - 1u) & ~((1u << (mr & 31u)) - 1u), rows = ((1u << ((mr >> 15) & 31u)) - 1u) & ~((1u << ((mr >> 5) & 31u)) - 1u);
+					R.slot_mode = lo | ((mr >> 20) << 8); R.mask = cols | (rows << 16);
+					keep = vgx_raster_setup(v2(p0.x, p0.y), v2(p1.x, p1.y), v2(p2.x, p2.y), cp[i0], cp[i1], cp[i2], &R.T)
+					    && vgx_raster_span(R.T.minx, R.T.maxx, A.x0, ox + (mr & 31u), ox + ((mr >> 10) & 31u), &a0, &a1)
+					    && vgx_raster_span(R.T.miny, R.T.maxy, A.y0, oy + ((mr >> 5) & 31u), oy + ((mr >> 15) & 31u), &b0, &b1);
+				}
+			}
+			const uint64_t kept = wave_ballot(keep);
+			if (lane == 0) { s_count[wave] = (uint32_t)__popcll(kept); }
+			__syncthreads();
+			uint32_t base = 0, n = 0;
+#pragma unroll
+			for (uint32_t w = 0; w < 4u; ++w) { const uint32_t c = s_count[w]; base += w < wave ? c : 0u; n += c; }
+			if (keep) { s_tri[base + (uint32_t)__popcll(kept & lanemask_lt(lane))] = R; }
+			__syncthreads();
+			for (uint32_t t = 0; t < n; ++t) { // every lane walks the records: no lane leaves between the barriers
+				const uint32_t mk = s_tri[t].mask; // beside the record: an untested mesh needs no second, dependent LDS read
+				if (((mk >> lx) & (mk >> (16u + ly)) & 1u) != 0u) {
+					const uint32_t sm = s_tri[t].slot_mode;
+					uint32_t f = 0u, n = 0u;
+					if ((sm >> 8) != VGX_RF_PLAIN) { const VgxRasterTileState ts = s_state[sm & 255u]; f = ts.f; n = ts.n; }
+					d = vgx_raster_frame_pixel(s_tri[t].T, sm >> 8, f, n, px, py, &S, d);
+				}
+			}
+			__syncthreads(); // s_tri and s_count are written again
+		}
+		__syncthreads(); // s_mesh, s_state and s_first are written again
+	}
+	if (inside && (clear || d != before)) { *pixel = d; }
+}
+
 } // namespace
 
 size_t vgx_raster_sort_bytes(uint64_t n, uint32_t bits)
@@ -195,5 +374,23 @@ hipError_t vgx_launch_raster(const VgxRasterArgs& a, void* partial, void* sortTe
 		if (e != hipSuccess) { return e; }
 	}
 	if (a.tiles_x && a.tiles_y) { hipLaunchKernelGGL(k_raster_tiles, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, a); }
+	return hipSuccess;
+}
+
+hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& f, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
+{
+	const VgxRasterArgs& a = f.R;
+	if (a.nrange) { hipLaunchKernelGGL(k_rasterf_count, dim3((unsigned)((a.nrange + 255) / 256)), dim3(256), 0, s, f); }
+	OpRasterFrameBin op;
+	op.F = f;
+	vgx_device_scan(op, (Sum3*)partial, s, a.nrange);
+	const uint64_t items = a.nrange > a.sort_n ? a.nrange : a.sort_n;
+	if (items) { hipLaunchKernelGGL(k_rasterf_entries, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, f); }
+	if (a.sort_n) {
+		const hipError_t e = rocprim::radix_sort_pairs(sortTemp, sortBytes, (const uint32_t*)a.keys, a.sorted_keys, (const uint32_t*)a.vals, a.sorted_vals,
+		                                               (size_t)a.sort_n, 0u, a.sort_bits, s);
+		if (e != hipSuccess) { return e; }
+	}
+	if (a.tiles_x && a.tiles_y) { hipLaunchKernelGGL(k_rasterf_tiles, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, f); }
 	return hipSuccess;
 }

@@ -695,8 +695,31 @@ def raster(ctx, frame, width, height, x0=0, y0=0, scissor=None, clear_color=None
     return image, dev_status
 
 
+def raster_frame(ctx, frame, draws_dev, draw_state_dev, num_draws, width, height, x0=0, y0=0, scissor=None, clear_color=None, bounds_dev=None,
+                 mesh_begin=0, mesh_end=None, image=None, dev_status=None):
+    """raster() under the state of a decoded frame: draws_dev / draw_state_dev are uint8 device tensors of num_draws 64-byte vgx_draw and
+    24-byte vgx_draw_state records (what cmdlist decoding gave), indexed by the meshes' draw. Every mesh is cut by its draw's scissor,
+    clip draws stamp their region, the other draws are tested against the region they name (vgx_raster_frame in include/vgx.h). The
+    mesh range must hold the clip meshes of every region it uses. dev_status may also come out as VGX_E_INVALID_ARG: a mesh names a
+    draw >= num_draws, nothing was written. Returns (image, dev_status) as raster() does. Asynchronous."""
+    import torch
+    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
+    if image is None:
+        image = torch.zeros((max(int(height), 1), max(int(width), 1)), dtype=torch.int32, device="cuda:%d" % ctx.device)[:height, :width]
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
+    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
+    t = capi.RasterTarget(image.data_ptr(), int(width), int(height), int(image.stride(0)) if image.dim() == 2 and height else int(width), int(x0), int(y0),
+                          (C.c_uint32 * 4)(*sc), capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
+    st = capi.RasterDraws(draws_dev.data_ptr() if num_draws else None, draw_state_dev.data_ptr() if num_draws else None, int(num_draws), 0)
+    _check(lib().vgx_raster_frame(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
+                                  0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), C.byref(t), dev_status.data_ptr(), _stream_ptr()),
+           "vgx_raster_frame")
+    return image, dev_status
+
+
 def raster_reserve(ctx, num_meshes, num_bin_entries):
-    """Sizes the scratch of raster() ahead, so that a first call does not end with VGX_E_GROWN."""
+    """Sizes the scratch of raster() and raster_frame() ahead, so that a first call does not end with VGX_E_GROWN."""
     _check(lib().vgx_raster_reserve(ctx.handle, int(num_meshes), int(num_bin_entries)), "vgx_raster_reserve")
 
 
