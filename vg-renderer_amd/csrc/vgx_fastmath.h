@@ -3,11 +3,15 @@
 // The arithmetic contract of the path (vgmath.h) is IEEE binary32 with correctly rounded + - * / sqrt. The compiler's
 // generic sequences for `/` and `sqrtf` (-fhip-fp32-correctly-rounded-divide-sqrt) cost ~11 and ~15 VALU instructions
 // because they must survive denormals, infinities and the whole exponent range (v_div_scale / v_div_fmas / v_div_fixup,
-// range scaling around v_sqrt_f32). The element kernels only ever take
-//     vec2Dir:              1 / sqrt(lenSqr)   with lenSqr in [1e-5, FLT_MAX]         (stroker.cpp:31-38)
+// range scaling around v_sqrt_f32). The element kernels take
+//     vec2Dir:              1 / sqrt(lenSqr)   with lenSqr in [1e-5, +inf]            (stroker.cpp:31-38)
 //     calcExtrusionVector:  1 / cross          with |cross| in (0.01, ~1]            (stroker.cpp:40-53)
-// i.e. normal numbers far from both ends of the exponent range, where one hardware estimate (v_rcp_f32 / v_sqrt_f32, 1 ulp)
-// plus FMA residual steps gives the correctly rounded result. "Gives" is not argued, it is CHECKED: the functions below are
+// The functions below are valid for normal numbers in [2^-100, 2^100], far from both ends of the exponent range, where one hardware
+// estimate (v_rcp_f32 / v_sqrt_f32, 1 ulp) plus FMA residual steps gives the correctly rounded result. Their callers (v2dir / v2extrude,
+// vgx_lane.h) take the generic sequence behind `if (!(x <= 0x1p100f))`: segments longer than 2^50 -- lenSqr beyond 2^100, or +inf with
+// finite positions -- are valid input with a defined answer; that fallback is covered by tests/test_gpu_transform_extremes.py (the
+// grow_1e14 and grow_3e18 matrices of tests/transform_extremes.py, on every emit route). Anything below 1e-5 is discarded by the
+// epsilon test of vec2Dir whatever the estimate returned. "Gives" is not argued, it is CHECKED: the functions below are
 // compared with the compiler's correctly rounded `/` and sqrtf over EVERY float of their domain by
 // tests/native/exact_math_test.hip (run by tests/test_gpu_exact_math.py on the GPU). The FMAs are explicit builtins: they
 // are part of these algorithms, not contractions of the reference's expressions (-ffp-contract=off stays in force).

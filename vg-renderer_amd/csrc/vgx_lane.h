@@ -38,7 +38,8 @@ VGX_HD float v2cross(V2 a, V2 b) { return a.x * b.y - b.x * a.y; }
 // vec2Dir, stroker.cpp:31-38
 // Device code takes 1 / sqrt(lenSqr) from vgx_fastmath.h: the same correctly rounded value as vgm_rsqrt in a third of the
 // instructions (checked over every float of its domain by tests/native/exact_math_test.hip); values outside the checked
-// domain -- coordinates beyond 1e15, NaN / Inf -- take the generic sequence under a branch that never runs.
+// domain -- segments longer than 2^50, lenSqr = +inf -- take the generic sequence under a branch that ordinary drawings never take
+// (tests/test_gpu_transform_extremes.py does: the grow_1e14 / grow_3e18 matrices).
 VGX_HD V2 v2dir(V2 a, V2 b)
 {
 	const float dx = b.x - a.x;
