@@ -764,6 +764,66 @@ int vgx_raster_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mes
                      uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
                      const vgx_raster_target* target, uint32_t* dev_status, void* stream);
 
+/* ---- text and user meshes in the image: vgx_text_quads -> vgx_merge_uv_stream -> vgx_raster_textured ----------------------------------
+ * vgx_raster and vgx_raster_frame skip the two kinds that carry texture coordinates. vgx_raster_textured is vgx_raster_frame word for
+ * word -- triangles, sample, coverage, tie rule, draw scissor, stamp, In / Out, order, mesh_bounds, target, and the VGX_E_GROWN /
+ * VGX_E_RANGE / VGX_E_INVALID_ARG protocol and ranking -- with ONE difference: a mesh of kind VGX_MESH_TEXT or VGX_MESH_TRILIST is no
+ * longer skipped. Such a mesh whose draw has type 0 (Textured; type = (state_key >> 16) & 0xF) is a SAMPLED mesh: its colour is the
+ * reference's fs_textured.sc, gl_FragColor = v_color0 * texture2D(s_tex, uv), on the RGBA8 image its draw names (handle =
+ * state_key & 0xFFFF, an index into tex->images), under the blend state of vgx_raster. Such a mesh whose draw has type 3 stamps like
+ * any clip mesh; one whose draw has type 1 or 2 is drawn with its vertex colours; a mesh of any other kind is drawn exactly as
+ * vgx_raster_frame draws it and no UV of it is read.
+ * Why is there no second rule for unsampled kinds? The reference samples its white pixel for them, texel 255 in every channel, and
+ * the modulate step below gives div255(vc * 255) = vc back exactly: the colour of vgx_raster IS the textured rule on a white image.
+ * Like the rest of this section the rule is written so that every implementation gives the same bytes, without a tolerance. None of
+ * its constants is a measured number; they are choices that make the result a function of the input alone.
+ *
+ * UV at a covered sample. With E0, E1, E2, S of the coverage rule and the vertex values ua, ub, uc, per component, in binary64
+ *   WITHOUT FMA: u = ((E1*ua + E2*ub) + E0*uc) / S, the form of the colour rule. A vertex value is the binary32 value widened
+ *   (uv_bytes 8), or (double)s / 32767.0 of the int16 s (uv_bytes 4: what vgx_text_quads wrote as (int16_t)(s * INT16_MAX)).
+ * Texel coordinates. U = u * (double)width, V = v * (double)height. If !(fabs(U) < 2147483648.0) or the same for V (NaN included),
+ *   the sample leaves the pixel alone, with the stamp test's result unused: it is treated as not covered.
+ * Nearest filter (flags bit 0). ix = (int64)floor(U), iy = (int64)floor(V); the texel is image(wrap(ix), wrap(iy)).
+ * Linear filter. T = (int64)floor((U - 0.5) * 256.0 + 0.5): a 24.8 fixed-point coordinate, rounded to nearest. i0 = T >> 8 (floor),
+ *   wx = T & 255, i1 = i0 + 1; the same for y with V. Rounding here, not truncating, is what makes a 1:1 blit exact: the
+ *   interpolated u may be off by an ulp either way, T still lands on the integer and wx = 0.
+ * Wrap, per axis and per index. With the clamp flag of the axis (bit 10 Clamp_U, bit 11 Clamp_V): min(max(i, 0), W - 1); otherwise
+ *   the Euclidean remainder of i mod W (in 0 .. W - 1 for negative i too).
+ * Filtered channel (linear), in integers, with the four wrapped texels c00 (i0, j0), c10 (i1, j0), c01 (i0, j1), c11 (i1, j1):
+ *   (c00*(256-wx)*(256-wy) + c10*wx*(256-wy) + c01*(256-wx)*wy + c11*wx*wy + 32768) >> 16: round-to-nearest of the bilinear value
+ *   over 2^16 (the weights sum to 2^16, so the sum stays below 2^32).
+ * Modulate, per channel. q = div255(vc * tc): vc the 8-bit vertex channel of vgx_raster's colour rule (already rounded), tc the
+ *   texel channel (filtered for linear), div255 the one of the blend.
+ * Blend. a = q of the alpha channel. a == 0 leaves the pixel; otherwise the blend of vgx_raster with the four q.
+ * Validity. A sampled mesh of the range -- whatever it covers -- is invalid when its handle is >= num_images, or its image has null
+ *   or misaligned (4-byte) pixels, a width or height of 0 or above 16384, or stride < width. An invalid sampled mesh ends the call with
+ *   VGX_E_INVALID_ARG in dev_status and NOTHING is written, the clear included: decided in the same one reduction as draw >= num_draws,
+ *   with the same rank. Image records that no sampled mesh of the range names are not looked at; with num_images == 0 a frame without
+ *   sampled meshes is valid.
+ * Host return values. As vgx_raster_frame, and VGX_E_INVALID_ARG for a null `tex`, uv_bytes other than 4 or 8, a null or misaligned
+ *   `uv` (uv_bytes-aligned) with a non-empty mesh range, null `images` with num_images > 0, a misaligned `images` (8-byte).
+ * Out of scope. Gradients and image patterns (draw types 1 and 2, with their paint matrices), mips (the reference creates none),
+ *   streams written under vgx_set_assembly, shaping and the atlas itself.
+ * Side effects. As vgx_raster_frame, on the same scratch, and one bit per 16 x 16 tile of the image (which tiles a sampled mesh reaches)
+ *   in a buffer only this call allocates; vgx_scratch_bytes counts it. Texels are only read inside [0, height) x [0, width) of a
+ *   valid image. */
+typedef struct vgx_raster_image {      /* 24 bytes */
+	const uint32_t* pixels;            /* DEVICE [height][stride], 0xAABBGGRR, 4-byte aligned */
+	uint32_t width, height, stride;    /* 1 .. 16384, stride >= width */
+	uint32_t flags;                    /* the reference's ImageFlags bits as Image::m_Flags holds them: bit 0 nearest (Filter_NearestUV),
+	                                      bit 10 Clamp_U, bit 11 Clamp_V; every other bit ignored (the reference creates no mips) */
+} vgx_raster_image;
+enum { VGX_IMAGE_NEAREST = 1u << 0, VGX_IMAGE_CLAMP_U = 1u << 10, VGX_IMAGE_CLAMP_V = 1u << 11 };
+typedef struct vgx_raster_textures {
+	const void* uv;                    /* DEVICE [frame->num_vertices][uv_bytes]: a stream beside pos / color; read ONLY for vertices of sampled meshes */
+	const vgx_raster_image* images;    /* DEVICE [num_images], indexed by state_key & 0xFFFF */
+	uint32_t uv_bytes;                 /* 4 (int16 x 2) or 8 (float x 2) */
+	uint32_t num_images;
+} vgx_raster_textures;
+int vgx_raster_textured(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
+                        uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state, const vgx_raster_textures* tex,
+                        const vgx_raster_target* target, uint32_t* dev_status, void* stream);
+
 /* ---- incremental update (beyond the reference): vgx_cache_submit -> vgx_cache_layout -> [vgx_pick -> edit -> vgx_cache_update]* ----
  * Moving or recolouring an instance of a submitted frame changes nothing of the frame's structure: a cached mesh has a fixed size, so
  * the instance keeps its vertex, index and mesh ranges; indices, mesh records, draw commands and UVs do not depend on the transform.
@@ -889,6 +949,15 @@ int vgx_merge(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, co
  * assembly with a UV stream to have an effect. */
 int vgx_merge_uv(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, const uint32_t* b_draw, const void* b_uv, const vgx_draw* draws, uint64_t ndraws,
                  const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
+/* vgx_merge with a UV stream of the caller's beside pos / color, for the calls that read one without draw-command assembly
+ * (vgx_raster_textured): b_uv (DEVICE, [b->num_vertices][uv_bytes]) is copied to out_uv (DEVICE, [out->cap_vertices][uv_bytes]) at
+ * the merged places of the vertices of b's meshes; out_uv is written nowhere else (the vertices of a's meshes keep what they held:
+ * no sampled mesh is among them). uv_bytes is 4 or 8. The call ignores vgx_set_assembly for the UV stream: an armed assembly does
+ * its part as in vgx_merge, but its own UV stream is neither written nor read here. VGX_E_INVALID_ARG for a null b_uv or out_uv,
+ * another uv_bytes, or pointers that are not 4-byte aligned. */
+int vgx_merge_uv_stream(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, const uint32_t* b_draw, const void* b_uv, uint32_t uv_bytes,
+                        const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out, void* out_uv, vgx_sizes* dev_sizes, uint32_t* dev_status,
+                        void* stream);
 
 /* ---- text: the device half of renderTextQuads (src/vg.cpp:5541-5621) ------------------------------------------
  * Glyph layout and the atlas (FontStash + stb_truetype) stay with the caller, as libtess2 does for concave fills. What the

@@ -149,6 +149,19 @@ class RasterDraws(C.Structure):  # vgx_raster_draws: device arrays of vgx_draw a
 
 
 assert C.sizeof(RasterDraws) == 24
+
+
+class RasterImage(C.Structure):  # vgx_raster_image: `pixels` is a device pointer; an array of these lives in device memory
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("stride", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RasterTextures(C.Structure):  # vgx_raster_textures: the UV stream beside pos / color and the image table, both in device memory
+    _fields_ = [("uv", C.c_void_p), ("images", C.c_void_p), ("uv_bytes", C.c_uint32), ("num_images", C.c_uint32)]
+
+
+raster_image_dtype = np.dtype([("pixels", "<u8"), ("width", "<u4"), ("height", "<u4"), ("stride", "<u4"), ("flags", "<u4")])  # struct vgx_raster_image
+assert C.sizeof(RasterImage) == 24 and C.sizeof(RasterTextures) == 24 and raster_image_dtype.itemsize == 24
+IMAGE_NEAREST, IMAGE_CLAMP_U, IMAGE_CLAMP_V = 1 << 0, 1 << 10, 1 << 11  # vgx_raster_image.flags: the reference's ImageFlags bits
 DRAW_TYPE_CLIP = 3      # (vgx_draw::state_key >> 16) & 0xF of a clip draw
 CLIP_NONE = 0xFFFFFFFF  # vgx_draw_state::clip_first_draw of a draw without a region
 RASTER_CLEAR = 1
@@ -245,6 +258,8 @@ VGX_SYMBOLS = {
     "vgx_cache_localize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vgx_merge": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_merge_uv": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_merge_uv_stream": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                     C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_cache_submit": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_mesh_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "vgx_cache_cull": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
@@ -254,6 +269,8 @@ VGX_SYMBOLS = {
     "vgx_raster_reserve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
     "vgx_raster_frame": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.POINTER(RasterTarget), C.c_void_p,
                                   C.c_void_p]),
+    "vgx_raster_textured": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.POINTER(RasterTextures),
+                                     C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
     "vgx_cache_layout": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_cache_update": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                    C.POINTER(UpdateFrame), C.c_void_p, C.c_void_p]),

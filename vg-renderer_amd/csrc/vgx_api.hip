@@ -109,6 +109,7 @@ struct vgx_ctx
 	// whose entries outgrew the tables ends with VGX_E_GROWN and the next one grows first). Its own: a counted state survives the call
 	Buf<uint32_t> rasMeshEntries, rasKeys, rasVals, rasSortedKeys, rasSortedVals; Buf<uint64_t> rasMeshFirst; Buf<unsigned long long> rasState; Buf<float> rasBounds;
 	Buf<VgxRasterMeshState> rasFrameMesh; // vgx_raster_frame alone: what every mesh of the range does under its draw (vgx_raster.h)
+	Buf<uint32_t> rasTileTex;             // vgx_raster_textured alone: one bit per tile of the image, "a sampled mesh reaches it"
 	DevBuf rasSortTemp, rasPartial;      // rasPartial: slice sums (views: as `partial`)
 	HostMirror<unsigned long long> ras;
 	uint32_t optPickGrid;                // workgroups of k_pick_tris (VGX_PICK_GRID)
@@ -2734,12 +2735,17 @@ int vgx_raster_reserve(vgx_ctx* ctx, uint64_t num_meshes, uint64_t num_bin_entri
 
 namespace {
 
-// vgx_raster (state == nullptr) and vgx_raster_frame: one body, the kernels differ
+// vgx_raster (state == nullptr), vgx_raster_frame (tex == nullptr) and vgx_raster_textured: one body, the kernels differ
 int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
-               const vgx_raster_target* target, uint32_t* dev_status, void* stream)
+               const vgx_raster_textures* tex, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
 	if (!ctx || !frame || !target) { return VGX_E_INVALID_ARG; }
+	if (tex) {
+		if ((tex->uv_bytes != 4u && tex->uv_bytes != 8u) || (tex->num_images && !tex->images) || ((uintptr_t)tex->images & 7u)) { return VGX_E_INVALID_ARG; }
+		const uint64_t e = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
+		if (mesh_begin < e && (!tex->uv || ((uintptr_t)tex->uv & (tex->uv_bytes - 1u)))) { return VGX_E_INVALID_ARG; }
+	}
 	if (state) {
 		if (state->reserved != 0u || (state->num_draws && (!state->draws || !state->draw_state))) { return VGX_E_INVALID_ARG; }
 		if (((uintptr_t)state->draws & 3u) || ((uintptr_t)state->draw_state & 3u)) { return VGX_E_INVALID_ARG; }
@@ -2803,7 +2809,18 @@ int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_boun
 		VgxRasterFrameArgs f;
 		memset(&f, 0, sizeof(f));
 		f.R = a; f.draws = state->draws; f.draw_state = state->draw_state; f.num_draws = state->num_draws; f.mesh_state = ctx->rasFrameMesh.ptr();
-		noteHip(ctx, vgx_launch_raster_frame(f, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+		if (tex) {
+			VgxRasterTexArgs x;
+			memset(&x, 0, sizeof(x));
+			x.F = f; x.uv = tex->uv; x.images = tex->images; x.uv_bytes = tex->uv_bytes; x.num_images = tex->num_images;
+			const uint64_t words = ((uint64_t)a.sentinel + 31u) / 32u;
+			if ((st = ensure(ctx, ctx->rasTileTex, words + 1)) != VGX_OK) { return st; }
+			noteHip(ctx, hipMemsetAsync(ctx->rasTileTex.p, 0, words * sizeof(uint32_t), s));
+			x.tile_tex = ctx->rasTileTex.ptr();
+			noteHip(ctx, vgx_launch_raster_textured(x, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+		} else {
+			noteHip(ctx, vgx_launch_raster_frame(f, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+		}
 	} else {
 		noteHip(ctx, vgx_launch_raster(a, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
 	}
@@ -2817,14 +2834,21 @@ int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_boun
 int vgx_raster(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
-	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, nullptr, target, dev_status, stream);
+	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, nullptr, nullptr, target, dev_status, stream);
 }
 
 int vgx_raster_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                      const vgx_raster_draws* state, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
 	if (!state) { return VGX_E_INVALID_ARG; }
-	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, target, dev_status, stream);
+	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, nullptr, target, dev_status, stream);
+}
+
+int vgx_raster_textured(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
+                        const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
+{
+	if (!state || !tex) { return VGX_E_INVALID_ARG; }
+	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, target, dev_status, stream);
 }
 
 // ---- incremental update of a submitted frame (vgx_update.hip) -------------------------------------------------------------
@@ -2880,8 +2904,12 @@ int vgx_merge(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, co
 	return vgx_merge_uv(ctx, a, b, b_draw, nullptr, draws, ndraws, out, dev_sizes, dev_status, stream);
 }
 
-int vgx_merge_uv(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, const uint32_t* b_draw, const void* b_uv, const vgx_draw* draws, uint64_t ndraws,
-                 const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+namespace {
+
+// vgx_merge_uv (out_uv == nullptr: b_uv goes into the armed assembly's UV stream) and vgx_merge_uv_stream (b_uv goes to out_uv, and the
+// assembly's UV stream is left alone): one body
+int mergeCall(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, const uint32_t* b_draw, const void* b_uv, void* out_uv, uint32_t uv_bytes,
+              const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
 	(void)ndraws;
@@ -2913,14 +2941,35 @@ int vgx_merge_uv(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b,
 	vgx_launch_merge_scan(m, ctx->partial.p, s);
 	mark(ctx, s, "merge_scan");
 	if (ctx->asmArmed) {
-		if ((st = runAssemble(ctx, out, s, draws)) != VGX_OK) { return st; }
+		void* const asmUv = ctx->asmCfg.uv;
+		if (out_uv) { ctx->asmCfg.uv = nullptr; } // the assembly step writes no UV stream of its own
+		st = runAssemble(ctx, out, s, draws);
+		ctx->asmCfg.uv = asmUv;
+		if (st != VGX_OK) { return st; }
 		m.mesh_base = ctx->meshBase.ptr();
-		if (b_uv && ctx->asmCfg.uv && ctx->asmCfg.uv_bytes) { m.b_uv = b_uv; m.uv_out = ctx->asmCfg.uv; m.uv_bytes = ctx->asmCfg.uv_bytes; }
+		if (!out_uv && b_uv && ctx->asmCfg.uv && ctx->asmCfg.uv_bytes) { m.b_uv = b_uv; m.uv_out = ctx->asmCfg.uv; m.uv_bytes = ctx->asmCfg.uv_bytes; }
 	}
+	if (out_uv) { m.b_uv = b_uv; m.uv_out = out_uv; m.uv_bytes = uv_bytes; }
 	vgx_launch_merge_copy(m, s);
 	mark(ctx, s, "merge_copy");
 	publish(ctx, dev_sizes, dev_status, s);
 	return launchStatus(ctx);
+}
+
+} // namespace
+
+int vgx_merge_uv(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, const uint32_t* b_draw, const void* b_uv, const vgx_draw* draws, uint64_t ndraws,
+                 const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+{
+	return mergeCall(ctx, a, b, b_draw, b_uv, nullptr, 0u, draws, ndraws, out, dev_sizes, dev_status, stream);
+}
+
+int vgx_merge_uv_stream(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, const uint32_t* b_draw, const void* b_uv, uint32_t uv_bytes,
+                        const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out, void* out_uv, vgx_sizes* dev_sizes, uint32_t* dev_status,
+                        void* stream)
+{
+	if (!b_uv || !out_uv || (uv_bytes != 4u && uv_bytes != 8u) || ((uintptr_t)b_uv & 3u) || ((uintptr_t)out_uv & 3u)) { return VGX_E_INVALID_ARG; }
+	return mergeCall(ctx, a, b, b_draw, b_uv, out_uv, uv_bytes, draws, ndraws, out, dev_sizes, dev_status, stream);
 }
 
 int vgx_set_assembly(vgx_ctx* ctx, const vgx_assembly* asm_)

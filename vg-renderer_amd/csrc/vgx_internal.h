@@ -485,4 +485,15 @@ struct VgxRasterFrameArgs
 };
 hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
 
+// ... with text and user meshes sampled from images (vgx_raster_textured): the same again, the UV stream and the image table
+struct VgxRasterTexArgs
+{
+	VgxRasterFrameArgs F;
+	const void* uv;                   // [num_vertices][uv_bytes], checked by the host; read for the vertices of sampled meshes only
+	const vgx_raster_image* images;   // [num_images]; a record is read (and checked, by k_rastert_count) only when a sampled mesh names it
+	uint32_t uv_bytes, num_images;
+	uint32_t* tile_tex;               // [(sentinel + 31) / 32] one bit per tile of the image, zero at the launch: a sampled mesh has an entry there (context scratch)
+};
+hipError_t vgx_launch_raster_textured(const VgxRasterTexArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
+
 #endif

@@ -218,4 +218,124 @@ VGX_HD uint32_t vgx_raster_frame_pixel(const VgxRasterTri& T, uint32_t mode, uin
 	return vgx_raster_pixel(T, px, py, dst);
 }
 
+// ---- vgx_raster_textured: text and user meshes sampled from an RGBA8 image (include/vgx.h) ------------------------------------
+// Every kind is drawn; a mesh of kind TEXT / TRILIST under a draw of type 0 is sampled, the image = the low 16 bits of the state key
+#define VGX_RT_SAMPLED 0x10000u // in VgxRasterMeshState::pad beside the handle (bits 0 .. 15)
+VGX_HD bool vgx_raster_kind_has_uv(uint32_t subpathKind)
+{
+	const uint32_t k = subpathKind >> 28;
+	return k == VGX_MESH_TEXT || k == VGX_MESH_TRILIST;
+}
+VGX_HD bool vgx_raster_mesh_sampled(uint32_t subpathKind, uint32_t stateKey) { return vgx_raster_kind_has_uv(subpathKind) && vgx_raster_draw_type(stateKey) == 0u; }
+
+// vgx_raster_mesh_tiles without the test of the kind
+VGX_HD bool vgx_raster_any_mesh_tiles(const vgx_mesh& me, const float* box, int32_t x0, int32_t y0, const uint32_t* scissor, VgxRasterRect* r)
+{
+	if (me.num_indices < 3u) { return false; }
+	uint32_t i0, i1, j0, j1;
+	if (!vgx_raster_span(box[0], box[2], x0, scissor[0], scissor[2], &i0, &i1) || !vgx_raster_span(box[1], box[3], y0, scissor[1], scissor[3], &j0, &j1)) { return false; }
+	r->tx0 = i0 / VGX_RASTER_TILE; r->tx1 = i1 / VGX_RASTER_TILE; r->ty0 = j0 / VGX_RASTER_TILE; r->ty1 = j1 / VGX_RASTER_TILE;
+	return true;
+}
+
+VGX_HD bool vgx_raster_image_valid(const vgx_raster_image& im)
+{
+	return im.pixels != nullptr && ((uintptr_t)im.pixels & 3u) == 0u && im.width >= 1u && im.width <= 16384u && im.height >= 1u && im.height <= 16384u
+	    && im.stride >= im.width;
+}
+
+// The state of a mesh under vgx_raster_textured: vgx_raster_mesh_state, and for a sampled mesh the handle in `pad`, or
+// VGX_RF_INVALID when the handle or its image record is no good. `images` is only read for a sampled mesh
+VGX_HD void vgx_raster_textured_mesh_state(const vgx_mesh& me, uint32_t stateKey, const vgx_draw_state& ds, int32_t x0, int32_t y0, const uint32_t* scissor,
+                                           const vgx_raster_image* images, uint32_t numImages, VgxRasterMeshState* st)
+{
+	vgx_raster_mesh_state(me.draw, stateKey, ds, x0, y0, scissor, st);
+	if (!vgx_raster_mesh_sampled(me.subpath_kind, stateKey)) { return; }
+	const uint32_t handle = stateKey & 0xFFFFu;
+	if (handle >= numImages || !vgx_raster_image_valid(images[handle])) { st->mode = VGX_RF_INVALID; return; }
+	st->pad = VGX_RT_SAMPLED | handle;
+}
+
+// the UV of vertex v of the stream as two binary64 values: binary32 widened, or int16 / 32767
+VGX_HD void vgx_raster_uv_widen(const void* uv, uint32_t uvBytes, uint64_t v, double* out)
+{
+	if (uvBytes == 8u) {
+		const float* p = (const float*)uv + 2u * v;
+		out[0] = (double)p[0]; out[1] = (double)p[1];
+	} else {
+		const int16_t* p = (const int16_t*)uv + 2u * v;
+		out[0] = (double)p[0] / 32767.0; out[1] = (double)p[1] / 32767.0;
+	}
+}
+
+// one UV component at a covered sample: the form of vgx_raster_channel
+VGX_HD double vgx_raster_uv_at(double ua, double ub, double uc, const double* E, double S) { return ((E[1] * ua + E[2] * ub) + E[0] * uc) / S; }
+
+// texel coordinate; false: the sample leaves the pixel alone
+VGX_HD bool vgx_raster_texcoord(double u, uint32_t W, double* U)
+{
+	*U = u * (double)W;
+	return fabs(*U) < 2147483648.0;
+}
+
+VGX_HD uint32_t vgx_raster_wrap(int64_t i, uint32_t W, bool clamp)
+{
+	if (clamp) { return i < 0 ? 0u : (i > (int64_t)W - 1 ? W - 1u : (uint32_t)i); }
+	int64_t r = i % (int64_t)W;
+	if (r < 0) { r += (int64_t)W; }
+	return (uint32_t)r;
+}
+
+// the linear filter's index pair and weight of one axis
+VGX_HD void vgx_raster_linear_axis(double U, uint32_t W, bool clamp, uint32_t* i0, uint32_t* i1, uint32_t* w)
+{
+	const int64_t T = (int64_t)floor((U - 0.5) * 256.0 + 0.5);
+	const int64_t lo = T >> 8;
+	*w = (uint32_t)(T & 255);
+	*i0 = vgx_raster_wrap(lo, W, clamp); *i1 = vgx_raster_wrap(lo + 1, W, clamp);
+}
+
+VGX_HD uint32_t vgx_raster_bilinear(uint32_t c00, uint32_t c10, uint32_t c01, uint32_t c11, uint32_t wx, uint32_t wy)
+{
+	return (c00 * (256u - wx) * (256u - wy) + c10 * wx * (256u - wy) + c01 * (256u - wx) * wy + c11 * wx * wy + 32768u) >> 16;
+}
+
+// The texel of image `im` at the texel coordinates (U, V), both already in range. fetch(x, y), x < width, y < height, reads a texel
+template <class Fetch>
+VGX_HD uint32_t vgx_raster_sample(const vgx_raster_image& im, double U, double V, Fetch fetch)
+{
+	const bool cu = (im.flags & VGX_IMAGE_CLAMP_U) != 0u, cv = (im.flags & VGX_IMAGE_CLAMP_V) != 0u;
+	if (im.flags & VGX_IMAGE_NEAREST) {
+		return fetch(vgx_raster_wrap((int64_t)floor(U), im.width, cu), vgx_raster_wrap((int64_t)floor(V), im.height, cv));
+	}
+	uint32_t x0, x1, wx, y0, y1, wy;
+	vgx_raster_linear_axis(U, im.width, cu, &x0, &x1, &wx);
+	vgx_raster_linear_axis(V, im.height, cv, &y0, &y1, &wy);
+	const uint32_t c00 = fetch(x0, y0), c10 = fetch(x1, y0), c01 = fetch(x0, y1), c11 = fetch(x1, y1);
+	uint32_t r = 0;
+	for (int ch = 0; ch < 4; ++ch) {
+		const int sh = 8 * ch;
+		r |= vgx_raster_bilinear((c00 >> sh) & 255u, (c10 >> sh) & 255u, (c01 >> sh) & 255u, (c11 >> sh) & 255u, wx, wy) << sh;
+	}
+	return r;
+}
+
+// The triangle of a SAMPLED mesh (mode is never VGX_RF_STAMP: its draw has type 0) with the vertex UVs uv[0 .. 5] = ua, va, ub, vb,
+// uc, vc on the pixel whose sample is (px, py): the pixel's new value
+template <class Fetch>
+VGX_HD uint32_t vgx_raster_textured_pixel(const VgxRasterTri& T, const double* uv, const vgx_raster_image& im, uint32_t mode, uint32_t f, uint32_t n,
+                                          double px, double py, uint32_t S, uint32_t dst, Fetch fetch)
+{
+	if (mode != VGX_RF_PLAIN && !vgx_raster_stamp_pass(S, f, n, mode == VGX_RF_IN ? 0u : 1u)) { return dst; }
+	double E[3], sum, U, V;
+	if (!vgx_raster_cover(T, px, py, E, &sum)) { return dst; }
+	if (!vgx_raster_texcoord(vgx_raster_uv_at(uv[0], uv[2], uv[4], E, sum), im.width, &U)
+	 || !vgx_raster_texcoord(vgx_raster_uv_at(uv[1], uv[3], uv[5], E, sum), im.height, &V)) { return dst; }
+	const uint32_t tc = vgx_raster_sample(im, U, V, fetch);
+	const uint32_t a = vgx_raster_div255(vgx_raster_channel(T, 3, E, sum) * (tc >> 24));
+	if (a == 0u) { return dst; }
+	return vgx_raster_blend(dst, vgx_raster_div255(vgx_raster_channel(T, 0, E, sum) * (tc & 255u)), vgx_raster_div255(vgx_raster_channel(T, 1, E, sum) * ((tc >> 8) & 255u)),
+	                        vgx_raster_div255(vgx_raster_channel(T, 2, E, sum) * ((tc >> 16) & 255u)), a);
+}
+
 #endif

@@ -718,8 +718,44 @@ def raster_frame(ctx, frame, draws_dev, draw_state_dev, num_draws, width, height
     return image, dev_status
 
 
+def raster_images(images, device):
+    """The image table of raster_textured() in device memory: `images` is a list of (pixels, flags) with pixels an int32 [height, stride]
+    device tensor of 0xAABBGGRR texels (width = its column count; a view of a wider tensor gives stride > width) and flags the
+    capi.IMAGE_* bits. Returns a uint8 device tensor of 24-byte vgx_raster_image records; the caller keeps the pixel tensors alive."""
+    import numpy as np
+    import torch
+    rec = np.zeros(len(images), dtype=capi.raster_image_dtype)
+    for k, (px, flags) in enumerate(images):
+        rec[k] = (px.data_ptr(), int(px.shape[1]), int(px.shape[0]), int(px.stride(0)), int(flags))
+    return torch.from_numpy(rec.view(np.uint8).copy()).to(device)
+
+
+def raster_textured(ctx, frame, draws_dev, draw_state_dev, num_draws, uv_dev, uv_bytes, images_dev, num_images, width, height, x0=0, y0=0, scissor=None,
+                    clear_color=None, bounds_dev=None, mesh_begin=0, mesh_end=None, image=None, dev_status=None):
+    """raster_frame() that also draws text and user meshes: a mesh of kind TEXT or TRILIST under a draw of type 0 is sampled from the
+    image its draw names (state_key & 0xFFFF indexes images_dev, what raster_images() gave) with the UVs of uv_dev, a device tensor
+    of uv_bytes (4: int16 x 2, 8: float x 2) per vertex of the frame, read only at the vertices of sampled meshes
+    (vgx_raster_textured in include/vgx.h). dev_status may also come out as VGX_E_INVALID_ARG for a sampled mesh whose handle or
+    image record is no good: nothing was written. Returns (image, dev_status) as raster() does. Asynchronous."""
+    import torch
+    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
+    if image is None:
+        image = torch.zeros((max(int(height), 1), max(int(width), 1)), dtype=torch.int32, device="cuda:%d" % ctx.device)[:height, :width]
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
+    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
+    t = capi.RasterTarget(image.data_ptr(), int(width), int(height), int(image.stride(0)) if image.dim() == 2 and height else int(width), int(x0), int(y0),
+                          (C.c_uint32 * 4)(*sc), capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
+    st = capi.RasterDraws(draws_dev.data_ptr() if num_draws else None, draw_state_dev.data_ptr() if num_draws else None, int(num_draws), 0)
+    tx = capi.RasterTextures(uv_dev.data_ptr() if uv_dev is not None else None, images_dev.data_ptr() if num_images else None, int(uv_bytes), int(num_images))
+    _check(lib().vgx_raster_textured(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
+                                     0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), C.byref(tx), C.byref(t), dev_status.data_ptr(),
+                                     _stream_ptr()), "vgx_raster_textured")
+    return image, dev_status
+
+
 def raster_reserve(ctx, num_meshes, num_bin_entries):
-    """Sizes the scratch of raster() and raster_frame() ahead, so that a first call does not end with VGX_E_GROWN."""
+    """Sizes the scratch of raster(), raster_frame() and raster_textured() ahead, so that a first call does not end with VGX_E_GROWN."""
     _check(lib().vgx_raster_reserve(ctx.handle, int(num_meshes), int(num_bin_entries)), "vgx_raster_reserve")
 
 
@@ -819,3 +855,13 @@ def merge(ctx, seq_a, seq_b, b_draw_dev, draws_dev, ndraws, bufs, b_uv_dev=None)
                               b_uv_dev.data_ptr() if b_uv_dev is not None else None,
                               draws_dev.data_ptr() if draws_dev is not None else None, ndraws, C.byref(out),
                               bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_merge_uv")
+
+
+def merge_uv_stream(ctx, seq_a, seq_b, b_draw_dev, b_uv_dev, uv_bytes, draws_dev, ndraws, bufs, out_uv_dev):
+    """merge() with a UV stream of the caller's: b_uv_dev (uv_bytes per vertex of seq_b, 4 or 8) lands in out_uv_dev ([capacity of
+    bufs in vertices] x uv_bytes) at the merged places of seq_b's vertices; out_uv_dev is written nowhere else, and an armed
+    assembly's own UV stream is left alone. What raster_textured() reads. Asynchronous; totals / status land in bufs.dev_*."""
+    out = bufs.out_struct()
+    _check(lib().vgx_merge_uv_stream(ctx.handle, C.byref(seq_a), C.byref(seq_b), b_draw_dev.data_ptr() if b_draw_dev is not None else None,
+                                     b_uv_dev.data_ptr(), int(uv_bytes), draws_dev.data_ptr() if draws_dev is not None else None, ndraws, C.byref(out),
+                                     out_uv_dev.data_ptr(), bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_merge_uv_stream")
