@@ -802,8 +802,8 @@ int vgx_raster_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mes
  *   sampled meshes is valid.
  * Host return values. As vgx_raster_frame, and VGX_E_INVALID_ARG for a null `tex`, uv_bytes other than 4 or 8, a null or misaligned
  *   `uv` (uv_bytes-aligned) with a non-empty mesh range, null `images` with num_images > 0, a misaligned `images` (8-byte).
- * Out of scope. Gradients and image patterns (draw types 1 and 2, with their paint matrices), mips (the reference creates none),
- *   streams written under vgx_set_assembly, shaping and the atlas itself.
+ * Out of scope. Gradients and image patterns (draw types 1 and 2, with their paint matrices: vgx_raster_painted, below), mips (the
+ *   reference creates none), streams written under vgx_set_assembly, shaping and the atlas itself.
  * Side effects. As vgx_raster_frame, on the same scratch, and one bit per 16 x 16 tile of the image (which tiles a sampled mesh reaches)
  *   in a buffer only this call allocates; vgx_scratch_bytes counts it. Texels are only read inside [0, height) x [0, width) of a
  *   valid image. */
@@ -823,6 +823,61 @@ typedef struct vgx_raster_textures {
 int vgx_raster_textured(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
                         uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state, const vgx_raster_textures* tex,
                         const vgx_raster_target* target, uint32_t* dev_status, void* stream);
+
+/* ---- gradient and image-pattern paints in the image: vgx_cmdlist_decode -> vgx_paint_tables -> vgx_raster_painted --------------------------
+ * vgx_raster_frame and vgx_raster_textured draw a mesh of a ColorGradient or ImagePattern draw with its vertex colours: black with the
+ * global alpha for a gradient, the flat tint for a pattern. vgx_raster_painted is vgx_raster_textured word for word -- triangles, sample,
+ * coverage, tie rule, draw scissor, stamp, In / Out, sampled meshes, order, mesh_bounds, target, and the VGX_E_GROWN / VGX_E_RANGE /
+ * VGX_E_INVALID_ARG protocol and ranking -- with ONE difference: a mesh whose draw has type 1 (ColorGradient) or 2 (ImagePattern) is a
+ * PAINTED mesh, whatever its kind (the reference picks the program by the draw type alone, src/vg.cpp:1251-1283). Its colour is the
+ * fragment stage of fs_color_gradient.sc / fs_image_pattern.sc on the vgx_paint record its draw names: handle = state_key & 0xFFFF, an
+ * index into paints->gradients (type 1) or paints->patterns (type 2), the records as vgx_cmdlist_decode wrote them (declared with that
+ * call, below) and vgx_paint_tables scattered them. Clip draws (type 3) stamp as before. A frame with no draw of type 1 or 2 gives
+ * vgx_raster_textured's bytes and status.
+ * The reference computes the paint coordinate per vertex (vs_color_gradient.sc: u_paintMat * (pos, 1)) and interpolates it; the map is
+ * affine, so it is a function of the sample position alone, and the rule evaluates it at the pixel's sample.
+ * Everything below is in binary64 WITHOUT FMA, floats widened first. max(a, b) = a > b ? a : b and min(a, b) = a < b ? a : b, so a NaN
+ * has one defined path. px, py are the sample of the coverage rule; m[k] is the paint's matrix[k].
+ *
+ * Paint coordinate. qx = (m0*px + m3*py) + m6, qy = (m1*px + m4*py) + m7.
+ * Gradient (type 1). With ex, ey, rad, fe = params[0..3]:
+ *   ax = fabs(qx) - (ex - rad), ay = fabs(qy) - (ey - rad), in = min(max(ax, ay), 0.0), ox = max(ax, 0.0), oy = max(ay, 0.0),
+ *   len = sqrt(ox*ox + oy*oy), correctly rounded (IEEE squareRoot), sd = (in + len) - rad, t = (sd + fe*0.5) / fe,
+ *   t = t > 0.0 ? t : 0.0 (a NaN gives 0), t = t < 1.0 ? t : 1.0.
+ * Gradient ends. Taken as 8-bit values, per channel: x = (double)c * 255.0 + 0.5; q8(c) is 0 when !(x > 0), 255 when x >= 256, else
+ *   (uint32)x. The decoder's c / 255.0f gives c back exactly. I = q8(inner_color[k]), O = q8(outer_color[k]).
+ * Gradient colour and alpha. Channel: v = I*(1.0 - t) + O*t (GLSL mix), g = min((uint32)(v + 0.5), 255). Alpha: a = div255(g_A * vc_A),
+ *   vc_A the vertex alpha of vgx_raster's colour rule, already rounded: the shader's gradient.w * v_color0.w. Vertex RGB is not used.
+ *   a == 0 leaves the pixel; otherwise the blend of vgx_raster with (g_R, g_G, g_B, a).
+ * Image pattern (type 2). (u, v) = (qx, qy). From there the texel rule of vgx_raster_textured unchanged, on images[paint.image & 0xFFFF]:
+ *   texel coordinates with the 2^31 / NaN rule (the sample leaves the pixel), nearest or linear, wrap, modulate div255(vc * tc) on all
+ *   four channels with the interpolated vertex colour (the pattern's tint), blend. No UV of the stream is read for a painted mesh.
+ * Validity. A painted mesh of the range -- whatever it covers -- is invalid when its handle is at or beyond the table of its type, or
+ *   the entry's `type` is not the draw's type, or, for a pattern, image & 0xFFFF >= num_images or that image record is invalid by
+ *   vgx_raster_textured's test. An invalid painted mesh is decided in the same one reduction as draw >= num_draws and has the same
+ *   rank: VGX_E_INVALID_ARG in dev_status, NOTHING written, the clear included. Entries that no painted mesh of the range names are
+ *   not looked at.
+ * Host return values. As vgx_raster_textured, and VGX_E_INVALID_ARG for a null `paints`, a null table with a count above 0, a
+ *   misaligned table (4-byte).
+ * Out of scope. Mips, streams written under vgx_set_assembly.
+ * Side effects. As vgx_raster_textured, on the same scratch (the 32 bytes per mesh of the range now also name the paint), and a second
+ *   bit per 16 x 16 tile of the image (which tiles a painted mesh reaches) in a buffer only this call allocates; vgx_scratch_bytes
+ *   counts it. A counted state survives: vgx_tessellate_count -> vgx_raster_painted -> vgx_tessellate_emit works.
+ *
+ * vgx_paint_tables (HOST only, no context) scatters the list vgx_cmdlist_decode wrote into the two tables: table[p.handle] = p goes
+ * into the table of p.type, a later record with the same handle wins, and every entry no record names gets type = 0xFFFFFFFF (an
+ * entry a painted mesh must not name). VGX_E_NOSPACE when a handle is at or beyond its table's capacity, VGX_E_INVALID_ARG for a type
+ * other than 1 or 2 or a null array with a count above 0; the tables' contents are then unspecified. */
+typedef struct vgx_raster_paints {
+	const struct vgx_paint* gradients; /* DEVICE [num_gradients], indexed by state_key & 0xFFFF of draws of type 1 */
+	const struct vgx_paint* patterns;  /* DEVICE [num_patterns],  indexed by state_key & 0xFFFF of draws of type 2; .image & 0xFFFF indexes tex->images */
+	uint32_t num_gradients, num_patterns;
+} vgx_raster_paints;
+int vgx_raster_painted(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
+                       uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state, const vgx_raster_textures* tex,
+                       const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* dev_status, void* stream);
+int vgx_paint_tables(const struct vgx_paint* paints, uint32_t n, struct vgx_paint* gradients, uint32_t cap_gradients,
+                     struct vgx_paint* patterns, uint32_t cap_patterns);
 
 /* ---- incremental update (beyond the reference): vgx_cache_submit -> vgx_cache_layout -> [vgx_pick -> edit -> vgx_cache_update]* ----
  * Moving or recolouring an instance of a submitted frame changes nothing of the frame's structure: a cached mesh has a fixed size, so

@@ -1,0 +1,417 @@
+"""CPU: the lane code of vgx_raster_painted (csrc/vgx_raster.h through libvgx_hosttest.so: vgxt_raster_painted, vgxt_raster_textured's loop
+with the paint functions) against the numpy statement (tests/raster_painted_model.py), and against six things that do not rest on that
+model: two closed forms of a gradient, a gradient of one colour against vgxt_raster_textured, a 1:1 pattern blit computed from div255
+alone, a pattern against a sampled quad with the same map, and the frames without a painted draw. vgx_paint_tables is checked here too
+(host only). Exact everywhere: np.array_equal on the uint32 images, the stride padding and everything outside the scissor included.
+tests/test_gpu_raster_painted.py makes the same comparisons on the kernels, with the `checks` of this file run through the device."""
+import ctypes as C
+import importlib
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import raster_frame_model as M
+import raster_model as R
+import raster_painted_model as P
+import raster_textured_model as T
+import test_raster_cpu as base
+import test_raster_frame_cpu as fcpu
+import test_raster_textured_cpu as tcpu
+
+capi = R.capi
+CLEAR = P.CLEAR
+F = np.float32
+BAD = capi.VGX_E_INVALID_ARG
+
+
+def load_host():
+    lib = tcpu.load_host()
+    if not hasattr(lib, "vgxt_raster_painted"):  # a library from before this call: build again
+        import __graft_entry__ as g
+        g.build()
+        lib = tcpu.load_host()
+    lib.vgxt_raster_painted.restype = C.c_int
+    lib.vgxt_raster_painted.argtypes = [C.POINTER(capi.CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(capi.RasterDraws),
+                                        C.POINTER(capi.RasterTextures), C.POINTER(capi.RasterPaints), C.POINTER(capi.RasterTarget), C.c_void_p]
+    lib.vgxt_raster_gradient_t.restype = C.c_double
+    lib.vgxt_raster_gradient_t.argtypes = [C.c_void_p, C.c_double, C.c_double]
+    lib.vgxt_raster_q8.restype = C.c_uint32
+    lib.vgxt_raster_q8.argtypes = [C.c_float]
+    lib.vgxt_raster_sqrt.restype = C.c_double
+    lib.vgxt_raster_sqrt.argtypes = [C.c_double]
+    return lib
+
+
+@pytest.fixture(scope="module")
+def host():
+    return load_host()
+
+
+@pytest.fixture(scope="module")
+def rt():
+    return importlib.import_module("vg-renderer_amd.runtime")
+
+
+def paints_struct(g, p):
+    return capi.RasterPaints(g.ctypes.data if len(g) else None, p.ctypes.data if len(p) else None, len(g), len(p))
+
+
+def host_painted(host, f, tgt, image=None, images=None, gradients=None, patterns=None, with_bounds=False, begin=0, end=2**64 - 1, want=capi.VGX_OK,
+                 records=None):
+    """vgxt_raster_painted over the target's background (or `image`, changed in place); returns the image. images / records /
+    gradients / patterns: instead of the frame's."""
+    img = tgt.background() if image is None else image
+    images = f.images if images is None else images
+    g = np.ascontiguousarray(f.gradients if gradients is None else gradients)
+    p = np.ascontiguousarray(f.patterns if patterns is None else patterns)
+    rec = tcpu.image_records(images) if records is None else records
+    mb = base.host_bounds(host, f) if with_bounds else None
+    d, s, t = f.desc(), fcpu.draws_struct(f), tgt.struct(img.ctypes.data)
+    x = capi.RasterTextures(f.uv.ctypes.data, rec.ctypes.data if len(images) else None, 8 if f.uv.dtype == np.float32 else 4, len(images))
+    pt = paints_struct(g, p)
+    status = np.full(1, 77, dtype=np.uint32)
+    assert host.vgxt_raster_painted(C.byref(d), None if mb is None else mb.ctypes.data, begin, end, C.byref(s), C.byref(x), C.byref(pt), C.byref(t),
+                                    status.ctypes.data) == capi.VGX_OK
+    assert status[0] == want
+    return img
+
+
+class HostRunner:
+    """What the model-independent checks call: the new call and vgx_raster_textured on the same kind of inputs."""
+
+    def __init__(self, host):
+        self.host = host
+
+    def painted(self, f, tgt, **kw):
+        return host_painted(self.host, f, tgt, **kw)
+
+    def textured(self, f, tgt, end=2**64 - 1, want=capi.VGX_OK):
+        return tcpu.host_textured(self.host, f, tgt, end=end, want=want)
+
+
+@pytest.fixture(scope="module")
+def run(host):
+    return HostRunner(host)
+
+
+@pytest.mark.parametrize("clear", [False, True])
+@pytest.mark.parametrize("name", P.NAMES)
+def test_lane_code_equals_model(host, rt, name, clear):
+    P.check_conditions(name, rt)
+    f = P.frame(name, rt)
+    tgt = f.target.with_clear(CLEAR) if clear else f.target
+    want = P.expected(name, clear, rt)
+    got = host_painted(host, f, tgt)
+    assert np.array_equal(got, want), base.where(got, want)
+    assert R.guards_intact(tgt, got)
+    assert np.array_equal(host_painted(host, f, tgt, with_bounds=True), got)  # the boxes handed in: the same bytes
+
+
+def test_the_paint_shows(host, rt):
+    """What the call is for: vgxt_raster_textured draws these frames black or in their flat tint."""
+    for name in ("linear", "pattern_linear_repeat", "decoded"):
+        f = P.frame(name, rt)
+        assert not np.array_equal(tcpu.host_textured(host, f, f.target), P.expected(name, rt=rt))
+
+
+# ---- checks that do not rest on the model: shared with the GPU test, which hands in a runner over the kernels ----------------------
+def decoded_paint(rt, record):
+    """The vgx_paint the decoder builds for one Create* command under the identity."""
+    r = P.Rec()
+    record(r)
+    extra = {}
+    rc, _, _, _ = P.cu.decode(rt, r.bytes(), canvas=(512.0, 512.0), extra=extra)
+    assert rc == capi.VGX_OK and extra["paints"].shape[0] == 1
+    return extra["paints"][0].copy()
+
+
+def gradient_quad(name, paint, x0, y0, x1, y1, tgt, color=0xFF000000):
+    """One non-AA quad of a gradient draw, as a non-AA FillPathGradient leaves it: black vertices with the global alpha."""
+    b = R.Builder()
+    b.mesh(M.quad(x0, y0, x1, y1), color, M.QUAD)
+    return P.finish(b.frame(name, tgt), [0], [P.GRADIENT], [M.state()], [0], np.full((4, 2), np.nan, dtype=F), [], [paint], [])
+
+
+def check_linear_ramp(run, rt):
+    """(1) black -> white over 256 units along x: t = (2x + 1) / 512 at column x, every step exact in binary64."""
+    g = decoded_paint(rt, lambda r: r.linear_gradient(0.0, 0.0, 256.0, 0.0, 0xFF000000, 0xFFFFFFFF))
+    seen = set()
+    for x0 in (0, 96, 170):
+        tgt = R.Target(96, 4, 97, x0, 0, clear=0x00000000)
+        f = gradient_quad("ramp", g, -8.0, 0.0, 300.0, 4.0, tgt)
+        got = run.painted(f, tgt)
+        for i in range(96):
+            x = x0 + i
+            v = (255 * (2 * x + 1) + 256) // 512 if x < 256 else 255
+            assert (got[:, i] == (0xFF000000 | v | (v << 8) | (v << 16))).all(), (x, hex(int(got[0, i])))
+            seen.add(v)
+    assert seen == set(range(256))
+
+
+def check_radial_distances(run, rt):
+    """(2) a radial gradient centred on a pixel centre: t = (d - 2) / 16 at distance d, exact for the Pythagorean offsets."""
+    inner, outer = 0xFF2040C0, 0xFFE0A010
+    g = decoded_paint(rt, lambda r: r.radial_gradient(20.5, 14.5, 2.0, 18.0, inner, outer))
+    tgt = R.Target(40, 30, 41, 0, 0, clear=0x00000000)
+    f = gradient_quad("radial_check", g, 0.0, 0.0, 40.0, 30.0, tgt)
+    got = run.painted(f, tgt)
+    for (dx, dy), dist in (((3, 4), 5), ((6, 8), 10), ((5, 12), 13), ((0, 7), 7)):
+        t = Fraction(dist - 2, 16)
+        px = 0xFF000000
+        for ch in range(3):
+            i_, o_ = (inner >> (8 * ch)) & 255, (outer >> (8 * ch)) & 255
+            px |= int(i_ * (1 - t) + o_ * t + Fraction(1, 2)) << (8 * ch)
+        for sx, sy in ((1, 1), (-1, 1), (1, -1), (-1, -1)):
+            assert int(got[14 + sy * dy, 20 + sx * dx]) == px, (dx, dy, hex(int(got[14 + sy * dy, 20 + sx * dx])), hex(px))
+
+
+def check_one_colour_gradient(run, rt):
+    """(3) inner == outer, opaque: vgx_raster_textured's image of the same streams with the draw's type 0 and the vertex RGB that colour."""
+    col = 0xFF3CA1E7
+    for name in ("linear", "radial"):
+        f = P.frame(name, rt)
+        g = f.gradients.copy()
+        g["inner_color"][0] = g["outer_color"][0] = np.array(P.unit(col), dtype=F)
+        flat = P.as_flat(f)
+        flat.color = ((f.color & np.uint32(0xFF000000)) | np.uint32(col & 0xFFFFFF)).astype(np.uint32)
+        for tgt in (f.target, f.target.with_clear(CLEAR)):
+            got = run.painted(f, tgt, gradients=g)
+            want = run.textured(flat, tgt)
+            assert np.array_equal(got, want), base.where(got, want)
+            assert not np.array_equal(got, tgt.background())
+
+
+def check_pattern_blit(run):
+    """(4) matrix diag(1 / W, 1 / H) (and the translation to the quad's corner), white tint, over a clear: every texel on its pixel."""
+    W, H = 5, 3
+    for flags in (P.NEAREST, 0):
+        b = R.Builder()
+        b.mesh(M.quad(3.0, 2.0, 3.0 + W, 2.0 + H), 0xFFFFFFFF, M.QUAD)
+        tgt = R.Target(12, 9, 14, 0, 0, clear=CLEAR)
+        im = P.Image(T.texels(W, H, 7, 1, [255, 0, 128, 1, 254, 77]), W, flags)
+        p = P.paint(P.PATTERN, [1.0 / W, 0.0, 0.0, 1.0 / H, -3.0 / W, -2.0 / H])
+        f = P.finish(b.frame("pattern_blit", tgt), [0], [P.PATTERN], [M.state()], [0], np.full((4, 2), np.nan, dtype=F), [im], [], [p])
+        want = tgt.background()
+        want[:, :tgt.width] = CLEAR
+        for y in range(H):
+            for x in range(W):
+                s = int(im.pixels[y, x])
+                a = s >> 24
+                if a:
+                    ch = [tcpu.div255(((s >> (8 * k)) & 255) * a + ((CLEAR >> (8 * k)) & 255) * (255 - a)) for k in range(3)]
+                    want[2 + y, 3 + x] = ch[0] | (ch[1] << 8) | (ch[2] << 16) | (tcpu.div255(255 * a + (CLEAR >> 24) * (255 - a)) << 24)
+        got = run.painted(f, tgt)
+        assert np.array_equal(got, want), base.where(got, want)
+        assert int((got[:, :tgt.width] != CLEAR).sum()) >= 10
+
+
+def check_pattern_equals_sampled_quad(run):
+    """(5) a pattern draw and a sampled TRILIST quad whose float UVs are the same affine map: 8 x 8 texels over 8 x 8 and 16 x 16 pixels,
+    every number a dyadic rational, so both routes are exact."""
+    for scale in (1, 2):
+        for flags in (P.NEAREST, 0, P.CLAMP_U | P.CLAMP_V):
+            n = 8 * scale
+            verts = M.quad(5.0, 3.0, 5.0 + n + 4, 3.0 + n + 2)   # a little past the image: the wrap is in it too
+            cols = [0xFFFFFFFF, 0xC0FF8040, 0xFF40FF80, 0x80FFFFFF]
+            tgt = R.Target(32, 24, 33, 0, 0)
+            im = P.Image(T.texels(8, 8, 9, 3, [255, 96, 200, 40]), 8, flags)
+            b = R.Builder()
+            b.mesh(verts, cols, M.QUAD)
+            p = P.paint(P.PATTERN, [1.0 / n, 0.0, 0.0, 1.0 / n, -5.0 / n, -3.0 / n])
+            fp = P.finish(b.frame("pattern_side", tgt), [0], [P.PATTERN], [M.state()], [0], np.full((4, 2), np.nan, dtype=F), [im], [], [p])
+            b = R.Builder()
+            b.mesh(verts, cols, M.QUAD, kind=R.TRILIST)
+            uv = np.array([((x - 5.0) / n, (y - 3.0) / n) for x, y in verts], dtype=F)
+            fs = P.finish(b.frame("sampled_side", tgt), [0], [0], [M.state()], [0], uv, [im], [], [])
+            got, want = run.painted(fp, tgt), run.textured(fs, tgt)
+            assert np.array_equal(got, want), (scale, flags, base.where(got, want))
+            assert int((got != tgt.background()).sum()) > 60 * scale
+
+
+def check_no_painted_draw(run, name):
+    """(6) the frames of raster_textured_model through the new call with empty paint tables: vgx_raster_textured's bytes and status.
+    One of them, `state`, does hold a draw of type 1 -- its last mesh, a user mesh that vgx_raster_textured draws with its vertex
+    colours -- so that frame is compared on the range in front of that mesh, and the whole of it must be refused."""
+    f = T.frame(name)
+    none = np.zeros(0, dtype=capi.paint_dtype)
+    types = (f.draws["state_key"] >> 16) & 0xF
+    painted = [m for m in range(f.nm) if int(types[int(f.meshes["draw"][m])]) in (1, 2)]
+    assert (name == "state") == bool(painted)
+    end = min(painted) if painted else 2**64 - 1
+    assert end >= 6
+    for tgt in (f.target, f.target.with_clear(CLEAR)):
+        got = run.painted(f, tgt, gradients=none, patterns=none, end=end)
+        want = run.textured(f, tgt, end=end)
+        assert np.array_equal(got, want), base.where(got, want)
+        assert not np.array_equal(got, tgt.background())
+        if painted:
+            assert np.array_equal(run.painted(f, tgt, gradients=none, patterns=none, want=BAD), tgt.background())
+
+
+def test_linear_ramp_closed_form(run, rt):
+    check_linear_ramp(run, rt)
+
+
+def test_radial_distances_closed_form(run, rt):
+    check_radial_distances(run, rt)
+
+
+def test_one_colour_gradient_equals_textured(run, rt):
+    check_one_colour_gradient(run, rt)
+
+
+def test_pattern_blit_from_div255(run):
+    check_pattern_blit(run)
+
+
+def test_pattern_equals_sampled_quad(run):
+    check_pattern_equals_sampled_quad(run)
+
+
+@pytest.mark.parametrize("name", T.NAMES)
+def test_no_painted_draw_equals_textured(run, name):
+    check_no_painted_draw(run, name)
+
+
+# ---- the pieces ---------------------------------------------------------------------------------------------------------
+def test_q8_and_gradient_t_pieces(host):
+    for c in (0.0, 1.0, -0.5, 1.5, 0.5, 0.25, 1e30, -1e30, np.nan, np.inf, -np.inf, 0.999, 1.001, -1e-3, 1e-3):
+        assert host.vgxt_raster_q8(C.c_float(c)) == P.q8(F(c)), c
+    for k in range(256):
+        assert host.vgxt_raster_q8(C.c_float(float(F(k) / F(255.0)))) == k   # the decoder's c / 255.0f gives c back
+    rs = np.random.RandomState(5)
+    for _ in range(400):
+        params = rs.uniform(-3, 40, 4).astype(F)
+        if rs.rand() < 0.2:
+            params[rs.randint(4)] = rs.choice([0.0, np.nan, np.inf, -np.inf])
+        qx, qy = rs.uniform(-60, 60, 2)
+        if rs.rand() < 0.1:
+            qx = rs.choice([np.nan, np.inf, -np.inf])
+        p = np.zeros(1, dtype=capi.paint_dtype)[0]
+        p["params"] = params
+        with np.errstate(all="ignore"):
+            want, _ = P.gradient_t(p, np.float64(qx), np.float64(qy))
+        got = host.vgxt_raster_gradient_t(params.ctypes.data, qx, qy)
+        assert np.float64(got).tobytes() == np.float64(want).tobytes(), (params, qx, qy)
+
+
+def test_host_sqrt_is_correctly_rounded(host):
+    """x86-64's sqrtsd against integer arithmetic: r = sqrt(x) is correctly rounded iff (r - u/2)^2 < x < (r + u/2)^2 (ties cannot occur)."""
+    rs = np.random.RandomState(6)
+    xs = list(rs.uniform(0, 1e6, 200)) + [float(a * a + b * b) for a, b in rs.uniform(0, 300, (200, 2)).astype(F).astype(float)] + [4.0, 2.0, 1e-300, 1e300]
+    for x in xs:
+        r = host.vgxt_raster_sqrt(x)
+        X, Rr = Fraction(x), Fraction(r)
+        lo, hi = Fraction(np.nextafter(r, 0.0)), Fraction(np.nextafter(r, np.inf))
+        assert ((Rr + lo) / 2) ** 2 <= X <= ((Rr + hi) / 2) ** 2, x
+
+
+# ---- protocol ---------------------------------------------------------------------------------------------------------------
+def invalid_cases(f):
+    """(what, keyword arguments of the runner) for every way a painted mesh of `state` is invalid."""
+    g, p = f.gradients, f.patterns
+    wrong_g, wrong_p, unused_g, far_image = g.copy(), p.copy(), g.copy(), p.copy()
+    wrong_g["type"][1] = P.PATTERN
+    wrong_p["type"][0] = P.GRADIENT
+    unused_g["type"][0] = P.UNUSED
+    far_image["image"][0] = 1
+    bad_rec = tcpu.image_records(f.images)
+    bad_rec["stride"][0] = bad_rec["width"][0] - 1
+    return [("handle beyond the gradient table", dict(gradients=g[:1])), ("handle beyond the pattern table", dict(patterns=p[:0])),
+            ("a pattern in the gradient table", dict(gradients=wrong_g)), ("a gradient in the pattern table", dict(patterns=wrong_p)),
+            ("an entry no record names", dict(gradients=unused_g)), ("the pattern's image beyond the image table", dict(patterns=far_image)),
+            ("the pattern's image record invalid", dict(records=bad_rec))]
+
+
+def test_invalid_paint_writes_nothing(host):
+    f = P.frame("state")
+    for tgt in (f.target, f.target.with_clear(CLEAR)):
+        for what, kw in invalid_cases(f):
+            got = host_painted(host, f, tgt, want=BAD, **kw)
+            assert np.array_equal(got, tgt.background()), what
+    assert P.status(f, gradients=f.gradients[:1]) == BAD and P.status(f, patterns=f.patterns[:0]) == BAD
+    # entries no painted mesh of the range names may be garbage: meshes 0 .. 3 name gradient 1 alone
+    junk_g = f.gradients.copy()
+    junk_g[0] = np.frombuffer(bytes(range(96)), dtype=capi.paint_dtype)[0]
+    junk_p = np.frombuffer(bytes(range(7, 103)), dtype=capi.paint_dtype).copy()
+    got = host_painted(host, f, f.target, gradients=junk_g, patterns=junk_p, end=4)
+    assert np.array_equal(got, P.render(f, f.target, f.target.background(), mesh_end=4))
+    assert not np.array_equal(got, f.target.background())
+    # a path-kind mesh of a type-0 draw with a handle outside every table is no painted mesh
+    g = P.state_frame()
+    g.draws["state_key"][0] |= 0xFFFF
+    assert np.array_equal(host_painted(host, g, g.target), P.expected("state"))
+
+
+def test_mesh_range_and_split_calls(host):
+    f = P.frame("crowd")
+    img = host_painted(host, f, f.target, end=150)
+    assert np.array_equal(img, P.render(f, f.target, f.target.background(), mesh_end=150))
+    img = host_painted(host, f, f.target, image=img, begin=150)
+    assert np.array_equal(img, P.expected("crowd"))
+
+
+def test_host_argument_checks(host):
+    f = P.frame("state")
+    img = f.target.background()
+    d, s = f.desc(), fcpu.draws_struct(f)
+    rec = tcpu.image_records(f.images)
+    x = capi.RasterTextures(f.uv.ctypes.data, rec.ctypes.data, 8, 1)
+    gp, pp = f.gradients.ctypes.data, f.patterns.ctypes.data
+
+    def call(paints):
+        t = f.target.struct(img.ctypes.data)
+        return host.vgxt_raster_painted(C.byref(d), None, 0, f.nm, C.byref(s), C.byref(x), None if paints is None else C.byref(paints), C.byref(t), None)
+
+    assert call(None) == BAD
+    assert call(capi.RasterPaints(None, pp, 2, 1)) == BAD and call(capi.RasterPaints(gp, None, 2, 1)) == BAD
+    assert call(capi.RasterPaints(gp + 2, pp, 2, 1)) == BAD and call(capi.RasterPaints(gp, pp + 1, 2, 1)) == BAD
+    assert np.array_equal(img, f.target.background())  # none of them wrote
+    assert call(capi.RasterPaints(gp, pp, 2, 1)) == capi.VGX_OK
+    assert np.array_equal(img, P.expected("state"))
+
+
+# ---- vgx_paint_tables (host only) -----------------------------------------------------------------------------------------------
+def test_paint_tables_scatter(rt):
+    f = P.frame("decoded", rt)
+    g, p = rt.paint_tables(f.paints)
+    assert g.tobytes() == f.gradients.tobytes() and p.tobytes() == f.patterns.tobytes()   # the model's scatter
+    assert g["handle"].tolist() == [0, 1, 2] and p["handle"].tolist() == [0, 1]
+    # holes marked, capacity beyond the records, a later record with the same handle wins
+    recs = np.zeros(4, dtype=capi.paint_dtype)
+    recs["type"] = [1, 2, 1, 1]
+    recs["handle"] = [3, 1, 0, 3]
+    recs["image"] = [10, 11, 12, 13]
+    g, p = rt.paint_tables(recs, num_gradients=6, num_patterns=2)
+    assert g["type"].tolist() == [1, P.UNUSED, P.UNUSED, 1, P.UNUSED, P.UNUSED] and p["type"].tolist() == [P.UNUSED, 2]
+    assert int(g["image"][3]) == 13 and int(g["image"][0]) == 12 and int(p["image"][1]) == 11
+    assert g[1].tobytes() == P.table([None])[0].tobytes()                                  # a hole is zeros behind its type
+    g, p = rt.paint_tables(recs[:0])
+    assert g.shape[0] == 0 and p.shape[0] == 0
+
+
+def test_paint_tables_refusals(rt):
+    lib = rt.lib()
+    recs = np.zeros(2, dtype=capi.paint_dtype)
+    recs["type"] = [1, 2]
+    recs["handle"] = [2, 0]
+    g, p = np.zeros(4, dtype=capi.paint_dtype), np.zeros(4, dtype=capi.paint_dtype)
+
+    def call(n, cg, cp, r=recs, gg=g, pp=p):
+        return lib.vgx_paint_tables(r.ctypes.data if r is not None else None, n, gg.ctypes.data if gg is not None else None, cg,
+                                    pp.ctypes.data if pp is not None else None, cp)
+
+    assert call(2, 3, 1) == capi.VGX_OK
+    assert call(2, 2, 1) == capi.VGX_E_NOSPACE and call(2, 3, 0) == capi.VGX_E_NOSPACE
+    for t in (0, 3, P.UNUSED):
+        bad = recs.copy()
+        bad["type"][1] = t
+        assert call(2, 3, 1, r=bad) == BAD
+    assert call(2, 3, 1, r=None) == BAD and call(2, 3, 1, gg=None) == BAD and call(2, 3, 1, pp=None) == BAD
+    assert call(0, 0, 0, r=None, gg=None, pp=None) == capi.VGX_OK
+
+
+def test_struct_sizes():
+    assert C.sizeof(capi.RasterPaints) == 24 and capi.paint_dtype.itemsize == 96
+    assert capi.paint_dtype.fields["matrix"][1] == 8 and capi.paint_dtype.fields["params"][1] == 44 and capi.paint_dtype.fields["image"][1] == 92

@@ -162,6 +162,15 @@ class RasterTextures(C.Structure):  # vgx_raster_textures: the UV stream beside 
 raster_image_dtype = np.dtype([("pixels", "<u8"), ("width", "<u4"), ("height", "<u4"), ("stride", "<u4"), ("flags", "<u4")])  # struct vgx_raster_image
 assert C.sizeof(RasterImage) == 24 and C.sizeof(RasterTextures) == 24 and raster_image_dtype.itemsize == 24
 IMAGE_NEAREST, IMAGE_CLAMP_U, IMAGE_CLAMP_V = 1 << 0, 1 << 10, 1 << 11  # vgx_raster_image.flags: the reference's ImageFlags bits
+
+
+class RasterPaints(C.Structure):  # vgx_raster_paints: the two tables of vgx_paint records (paint_dtype, below) in device memory
+    _fields_ = [("gradients", C.c_void_p), ("patterns", C.c_void_p), ("num_gradients", C.c_uint32), ("num_patterns", C.c_uint32)]
+
+
+assert C.sizeof(RasterPaints) == 24
+DRAW_TYPE_GRADIENT, DRAW_TYPE_PATTERN = 1, 2  # (vgx_draw::state_key >> 16) & 0xF of a painted draw; vgx_paint.type
+PAINT_UNUSED = 0xFFFFFFFF  # vgx_paint.type of a table entry no record names (vgx_paint_tables)
 DRAW_TYPE_CLIP = 3      # (vgx_draw::state_key >> 16) & 0xF of a clip draw
 CLIP_NONE = 0xFFFFFFFF  # vgx_draw_state::clip_first_draw of a draw without a region
 RASTER_CLEAR = 1
@@ -271,6 +280,9 @@ VGX_SYMBOLS = {
                                   C.c_void_p]),
     "vgx_raster_textured": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.POINTER(RasterTextures),
                                      C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
+    "vgx_raster_painted": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.POINTER(RasterTextures),
+                                    C.POINTER(RasterPaints), C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
+    "vgx_paint_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "vgx_cache_layout": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_cache_update": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                    C.POINTER(UpdateFrame), C.c_void_p, C.c_void_p]),

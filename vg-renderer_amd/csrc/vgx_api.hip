@@ -109,7 +109,8 @@ struct vgx_ctx
 	// whose entries outgrew the tables ends with VGX_E_GROWN and the next one grows first). Its own: a counted state survives the call
 	Buf<uint32_t> rasMeshEntries, rasKeys, rasVals, rasSortedKeys, rasSortedVals; Buf<uint64_t> rasMeshFirst; Buf<unsigned long long> rasState; Buf<float> rasBounds;
 	Buf<VgxRasterMeshState> rasFrameMesh; // vgx_raster_frame alone: what every mesh of the range does under its draw (vgx_raster.h)
-	Buf<uint32_t> rasTileTex;             // vgx_raster_textured alone: one bit per tile of the image, "a sampled mesh reaches it"
+	Buf<uint32_t> rasTileTex;             // vgx_raster_textured and vgx_raster_painted: one bit per tile of the image, "a sampled mesh reaches it"
+	Buf<uint32_t> rasTilePaint;           // vgx_raster_painted alone: the same for "a painted mesh reaches it"
 	DevBuf rasSortTemp, rasPartial;      // rasPartial: slice sums (views: as `partial`)
 	HostMirror<unsigned long long> ras;
 	uint32_t optPickGrid;                // workgroups of k_pick_tris (VGX_PICK_GRID)
@@ -2735,12 +2736,17 @@ int vgx_raster_reserve(vgx_ctx* ctx, uint64_t num_meshes, uint64_t num_bin_entri
 
 namespace {
 
-// vgx_raster (state == nullptr), vgx_raster_frame (tex == nullptr) and vgx_raster_textured: one body, the kernels differ
+// vgx_raster (state == nullptr), vgx_raster_frame (tex == nullptr), vgx_raster_textured (paints == nullptr) and vgx_raster_painted: one
+// body, the kernels differ
 int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
-               const vgx_raster_textures* tex, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
+               const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
 	if (!ctx || !frame || !target) { return VGX_E_INVALID_ARG; }
+	if (paints) {
+		if ((paints->num_gradients && !paints->gradients) || (paints->num_patterns && !paints->patterns)) { return VGX_E_INVALID_ARG; }
+		if (((uintptr_t)paints->gradients & 3u) || ((uintptr_t)paints->patterns & 3u)) { return VGX_E_INVALID_ARG; }
+	}
 	if (tex) {
 		if ((tex->uv_bytes != 4u && tex->uv_bytes != 8u) || (tex->num_images && !tex->images) || ((uintptr_t)tex->images & 7u)) { return VGX_E_INVALID_ARG; }
 		const uint64_t e = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
@@ -2817,7 +2823,17 @@ int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_boun
 			if ((st = ensure(ctx, ctx->rasTileTex, words + 1)) != VGX_OK) { return st; }
 			noteHip(ctx, hipMemsetAsync(ctx->rasTileTex.p, 0, words * sizeof(uint32_t), s));
 			x.tile_tex = ctx->rasTileTex.ptr();
-			noteHip(ctx, vgx_launch_raster_textured(x, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+			if (paints) {
+				VgxRasterPaintArgs p;
+				memset(&p, 0, sizeof(p));
+				p.X = x; p.gradients = paints->gradients; p.patterns = paints->patterns; p.num_gradients = paints->num_gradients; p.num_patterns = paints->num_patterns;
+				if ((st = ensure(ctx, ctx->rasTilePaint, words + 1)) != VGX_OK) { return st; }
+				noteHip(ctx, hipMemsetAsync(ctx->rasTilePaint.p, 0, words * sizeof(uint32_t), s));
+				p.tile_paint = ctx->rasTilePaint.ptr();
+				noteHip(ctx, vgx_launch_raster_painted(p, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+			} else {
+				noteHip(ctx, vgx_launch_raster_textured(x, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+			}
 		} else {
 			noteHip(ctx, vgx_launch_raster_frame(f, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
 		}
@@ -2834,21 +2850,44 @@ int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_boun
 int vgx_raster(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
-	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, nullptr, nullptr, target, dev_status, stream);
+	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, nullptr, nullptr, nullptr, target, dev_status, stream);
 }
 
 int vgx_raster_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                      const vgx_raster_draws* state, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
 	if (!state) { return VGX_E_INVALID_ARG; }
-	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, nullptr, target, dev_status, stream);
+	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, nullptr, nullptr, target, dev_status, stream);
 }
 
 int vgx_raster_textured(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                         const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
 	if (!state || !tex) { return VGX_E_INVALID_ARG; }
-	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, target, dev_status, stream);
+	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, nullptr, target, dev_status, stream);
+}
+
+int vgx_raster_painted(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
+                       const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target,
+                       uint32_t* dev_status, void* stream)
+{
+	if (!state || !tex || !paints) { return VGX_E_INVALID_ARG; }
+	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, dev_status, stream);
+}
+
+// HOST only, no context: the decoder's paint list scattered by handle into the two tables vgx_raster_painted indexes; holes marked
+int vgx_paint_tables(const vgx_paint* paints, uint32_t n, vgx_paint* gradients, uint32_t cap_gradients, vgx_paint* patterns, uint32_t cap_patterns)
+{
+	if ((n && !paints) || (cap_gradients && !gradients) || (cap_patterns && !patterns)) { return VGX_E_INVALID_ARG; }
+	for (uint32_t k = 0; k < cap_gradients; ++k) { memset(&gradients[k], 0, sizeof(vgx_paint)); gradients[k].type = 0xFFFFFFFFu; }
+	for (uint32_t k = 0; k < cap_patterns; ++k) { memset(&patterns[k], 0, sizeof(vgx_paint)); patterns[k].type = 0xFFFFFFFFu; }
+	for (uint32_t k = 0; k < n; ++k) {
+		const vgx_paint& p = paints[k];
+		if (p.type != 1u && p.type != 2u) { return VGX_E_INVALID_ARG; }
+		if (p.handle >= (p.type == 1u ? cap_gradients : cap_patterns)) { return VGX_E_NOSPACE; }
+		(p.type == 1u ? gradients : patterns)[p.handle] = p;
+	}
+	return VGX_OK;
 }
 
 // ---- incremental update of a submitted frame (vgx_update.hip) -------------------------------------------------------------

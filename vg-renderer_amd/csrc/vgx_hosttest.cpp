@@ -765,6 +765,116 @@ int vgxt_raster_textured(const vgx_cache_desc* frame, const float* mesh_bounds, 
 	return VGX_OK;
 }
 
+// vgx_raster_painted on the host: vgxt_raster_textured's loop with the paint functions of vgx_raster.h for the meshes of gradient and
+// image-pattern draws. HOST pointers throughout, the paint tables included.
+int vgxt_raster_painted(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                        const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status)
+{
+	if (!frame || !target || !state || !tex || !paints) { return VGX_E_INVALID_ARG; }
+	if ((paints->num_gradients && !paints->gradients) || (paints->num_patterns && !paints->patterns)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)paints->gradients & 3u) || ((uintptr_t)paints->patterns & 3u)) { return VGX_E_INVALID_ARG; }
+	if ((tex->uv_bytes != 4u && tex->uv_bytes != 8u) || (tex->num_images && !tex->images) || ((uintptr_t)tex->images & 7u)) { return VGX_E_INVALID_ARG; }
+	{
+		const uint64_t e = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
+		if (mesh_begin < e && (!tex->uv || ((uintptr_t)tex->uv & (tex->uv_bytes - 1u)))) { return VGX_E_INVALID_ARG; }
+	}
+	if (state->reserved != 0u || (state->num_draws && (!state->draws || !state->draw_state))) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)state->draws & 3u) || ((uintptr_t)state->draw_state & 3u)) { return VGX_E_INVALID_ARG; }
+	const vgx_raster_target& t = *target;
+	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
+	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
+	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
+		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
+	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
+	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	if (status) { *status = VGX_OK; }
+	if (empty) { return VGX_OK; }
+	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
+	for (uint64_t m = mesh_begin; m < end; ++m) {
+		const vgx_mesh me = frame->meshes[m];
+		VgxRasterMeshState ms;
+		ms.mode = VGX_RF_INVALID;
+		if (me.draw < state->num_draws) {
+			vgx_raster_painted_mesh_state(me, state->draws[me.draw].state_key, state->draw_state[me.draw], t.x0, t.y0, t.scissor, tex->images, tex->num_images,
+			                              paints->gradients, paints->num_gradients, paints->patterns, paints->num_patterns, &ms);
+		}
+		if (ms.mode == VGX_RF_INVALID) {
+			if (status) { *status = VGX_E_INVALID_ARG; }
+			return VGX_OK;
+		}
+	}
+	float* own = nullptr;
+	if (!mesh_bounds && mesh_begin < end) {
+		own = (float*)malloc(frame->num_meshes * 4 * sizeof(float));
+		if (!own) { return VGX_E_INTERNAL; }
+		vgxt_mesh_bounds(frame->pos, frame->meshes, frame->num_meshes, own);
+	}
+	uint32_t* stamp = (uint32_t*)malloc((size_t)t.width * t.height * sizeof(uint32_t));
+	if (!stamp) { free(own); return VGX_E_INTERNAL; }
+	for (size_t k = 0; k < (size_t)t.width * t.height; ++k) { stamp[k] = VGX_RASTER_STAMP_NONE; }
+	if (t.flags & VGX_RASTER_CLEAR) {
+		for (uint32_t j = t.scissor[1]; j < t.scissor[3]; ++j) {
+			for (uint32_t i = t.scissor[0]; i < t.scissor[2]; ++i) { t.pixels[(uint64_t)j * t.stride + i] = t.clear_color; }
+		}
+	}
+	for (uint64_t m = mesh_begin; m < end; ++m) {
+		const vgx_mesh me = frame->meshes[m];
+		VgxRasterMeshState ms;
+		vgx_raster_painted_mesh_state(me, state->draws[me.draw].state_key, state->draw_state[me.draw], t.x0, t.y0, t.scissor, tex->images, tex->num_images,
+			                              paints->gradients, paints->num_gradients, paints->patterns, paints->num_patterns, &ms);
+		const bool sampled = (ms.pad & VGX_RT_SAMPLED) != 0u;
+		const vgx_raster_image im = sampled ? tex->images[ms.pad & 0xFFFFu] : vgx_raster_image();
+		const auto fetch = [&im](uint32_t x, uint32_t y) { return im.pixels[(uint64_t)y * im.stride + x]; };
+		VgxRasterPaint pr;
+		memset(&pr, 0, sizeof(pr));
+		if (ms.pad & VGX_RT_PAINTED) { vgx_raster_paint_record(((ms.pad & VGX_RT_GRADIENT) ? paints->gradients : paints->patterns)[ms.pad & 0xFFFFu], tex->images, &pr); }
+		const auto pfetch = [&pr](uint32_t x, uint32_t y) { return pr.im.pixels[(uint64_t)y * pr.im.stride + x]; };
+		VgxRasterRect r;
+		if (ms.mode == VGX_RF_NOTHING || !vgx_raster_any_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, ms.rect, &r)) { continue; }
+		const uint16_t* ip = frame->idx + me.first_index;
+		const float* pp = frame->pos + 2 * me.first_vertex;
+		const uint32_t* cp = frame->color + me.first_vertex;
+		for (uint32_t k = 0; k < me.num_indices / 3u; ++k) {
+			const uint32_t i0 = ip[3 * k], i1 = ip[3 * k + 1], i2 = ip[3 * k + 2];
+			if (i0 >= me.num_vertices || i1 >= me.num_vertices || i2 >= me.num_vertices) { continue; }
+			VgxRasterTri T;
+			if (!vgx_raster_setup(v2(pp[2 * i0], pp[2 * i0 + 1]), v2(pp[2 * i1], pp[2 * i1 + 1]), v2(pp[2 * i2], pp[2 * i2 + 1]), cp[i0], cp[i1], cp[i2], &T)) { continue; }
+			double uv[6];
+			if (sampled) {
+				vgx_raster_uv_widen(tex->uv, tex->uv_bytes, me.first_vertex + i0, uv);
+				vgx_raster_uv_widen(tex->uv, tex->uv_bytes, me.first_vertex + i1, uv + 2);
+				vgx_raster_uv_widen(tex->uv, tex->uv_bytes, me.first_vertex + i2, uv + 4);
+			}
+			uint32_t a0, a1, b0, b1;
+			if (!vgx_raster_span(T.minx, T.maxx, t.x0, ms.rect[0], ms.rect[2], &a0, &a1) || !vgx_raster_span(T.miny, T.maxy, t.y0, ms.rect[1], ms.rect[3], &b0, &b1)) { continue; }
+			for (uint32_t j = b0; j <= b1; ++j) {
+				for (uint32_t i = a0; i <= a1; ++i) {
+					uint32_t* const p = t.pixels + (uint64_t)j * t.stride + i;
+					const double px = (double)(t.x0 + (int32_t)i) + 0.5, py = (double)(t.y0 + (int32_t)j) + 0.5;
+					uint32_t* const sp = stamp + (size_t)j * t.width + i;
+					const uint32_t d = sampled ? vgx_raster_textured_pixel(T, uv, im, ms.mode, ms.f, ms.n, px, py, *sp, *p, fetch)
+					                 : (ms.pad & VGX_RT_GRADIENT) ? vgx_raster_gradient_pixel(T, pr, ms.mode, ms.f, ms.n, px, py, *sp, *p)
+					                 : (ms.pad & VGX_RT_PATTERN) ? vgx_raster_pattern_pixel(T, pr, ms.mode, ms.f, ms.n, px, py, *sp, *p, pfetch)
+					                                             : vgx_raster_frame_pixel(T, ms.mode, ms.f, ms.n, px, py, sp, *p);
+					if (d != *p) { *p = d; }
+				}
+			}
+		}
+	}
+	free(stamp);
+	free(own);
+	return VGX_OK;
+}
+
+// the pieces of the paint rule, for the tests: t of a gradient at a paint coordinate, an end's channel as 8 bits, the square root
+double vgxt_raster_gradient_t(const float* params, double qx, double qy) { return vgx_raster_gradient_t(params, qx, qy); }
+uint32_t vgxt_raster_q8(float c) { return vgx_raster_q8(c); }
+double vgxt_raster_sqrt(double x) { return vgx_raster_sqrt(x); }
+
 // the pieces, for the tests of the predicate: the two canonical values of one directed edge u->v in a triangle of orientation
 // `positive`, at (px, py), and whether the edge takes a tie
 double vgxt_raster_edge(const float* u, const float* v, int positive, double px, double py, int* tie)

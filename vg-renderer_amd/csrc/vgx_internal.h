@@ -496,4 +496,15 @@ struct VgxRasterTexArgs
 };
 hipError_t vgx_launch_raster_textured(const VgxRasterTexArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
 
+// ... with gradient and image-pattern paints (vgx_raster_painted): the same again and the two paint tables
+struct VgxRasterPaintArgs
+{
+	VgxRasterTexArgs X;
+	const vgx_paint* gradients;       // [num_gradients]; an entry is read (and checked, by k_rasterp_count) only when a painted mesh names it
+	const vgx_paint* patterns;        // [num_patterns]
+	uint32_t num_gradients, num_patterns;
+	uint32_t* tile_paint;             // [(sentinel + 31) / 32] as tile_tex: a painted mesh has an entry there (context scratch)
+};
+hipError_t vgx_launch_raster_painted(const VgxRasterPaintArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
+
 #endif

@@ -338,4 +338,141 @@ VGX_HD uint32_t vgx_raster_textured_pixel(const VgxRasterTri& T, const double* u
 	                        vgx_raster_div255(vgx_raster_channel(T, 2, E, sum) * ((tc >> 16) & 255u)), a);
 }
 
+// ---- vgx_raster_painted: gradient and image-pattern paints (include/vgx.h) --------------------------------------------------------
+// A mesh whose draw has type 1 (ColorGradient) or 2 (ImagePattern) is painted, whatever its kind: the handle in the low 16 bits of the
+// state key indexes the table of that type. Beside VGX_RT_SAMPLED in VgxRasterMeshState::pad
+#define VGX_RT_GRADIENT 0x20000u
+#define VGX_RT_PATTERN  0x40000u
+#define VGX_RT_PAINTED  (VGX_RT_GRADIENT | VGX_RT_PATTERN)
+VGX_HD uint32_t vgx_raster_mesh_painted(uint32_t stateKey)
+{
+	const uint32_t type = vgx_raster_draw_type(stateKey);
+	return type == 1u ? VGX_RT_GRADIENT : (type == 2u ? VGX_RT_PATTERN : 0u);
+}
+
+// What a pixel needs of a paint: 48 bytes. m = matrix[0], [1], [3], [4], [6], [7] of the vgx_paint; a gradient keeps its four params and
+// its two ends as 8-bit channels (0xAABBGGRR), a pattern the record of its image
+struct VgxRasterPaint
+{
+	float m[6];
+	union {
+		struct { float params[4]; uint32_t inner, outer; } g;
+		vgx_raster_image im;
+	};
+};
+
+// the paint coordinate of the sample (px, py): affine, so a function of the sample alone
+VGX_HD void vgx_raster_paint_coord(const float* m, double px, double py, double* qx, double* qy)
+{
+	*qx = ((double)m[0] * px + (double)m[2] * py) + (double)m[4];
+	*qy = ((double)m[1] * px + (double)m[3] * py) + (double)m[5];
+}
+
+// The square root of the rule: IEEE squareRoot. x86-64's sqrtsd is; the device's is shown to be by tests/native/exact_sqrt64_test.hip
+VGX_HD double vgx_raster_sqrt(double x) { return sqrt(x); }
+
+// fs_color_gradient.sc's sdroundrect and the feather ramp, clamped to [0, 1]; a NaN gives 0
+VGX_HD double vgx_raster_gradient_t(const float* params, double qx, double qy)
+{
+	const double ex = (double)params[0], ey = (double)params[1], rad = (double)params[2], fe = (double)params[3];
+	const double ax = fabs(qx) - (ex - rad);
+	const double ay = fabs(qy) - (ey - rad);
+	const double mx = ax > ay ? ax : ay;
+	const double in = mx < 0.0 ? mx : 0.0;
+	const double ox = ax > 0.0 ? ax : 0.0;
+	const double oy = ay > 0.0 ? ay : 0.0;
+	const double len = vgx_raster_sqrt(ox * ox + oy * oy);
+	const double sd = (in + len) - rad;
+	double t = (sd + fe * 0.5) / fe;
+	t = t > 0.0 ? t : 0.0;
+	t = t < 1.0 ? t : 1.0;
+	return t;
+}
+
+// a gradient end's channel as 8 bits: what the decoder's c / 255.0f came from
+VGX_HD uint32_t vgx_raster_q8(float c)
+{
+	const double x = (double)c * 255.0 + 0.5;
+	if (!(x > 0.0)) { return 0u; }
+	if (x >= 256.0) { return 255u; }
+	return (uint32_t)x;
+}
+VGX_HD uint32_t vgx_raster_q8x4(const float* c) { return vgx_raster_q8(c[0]) | (vgx_raster_q8(c[1]) << 8) | (vgx_raster_q8(c[2]) << 16) | (vgx_raster_q8(c[3]) << 24); }
+
+// GLSL mix of two 8-bit ends, rounded to 8 bits
+VGX_HD uint32_t vgx_raster_mix8(uint32_t I, uint32_t O, double t)
+{
+	const double v = (double)I * (1.0 - t) + (double)O * t;
+	const uint32_t g = (uint32_t)(v + 0.5);
+	return g < 255u ? g : 255u;
+}
+
+// The compact record of paint p. `images` is read for a pattern only (its index is inside the table: the mesh state's check)
+VGX_HD void vgx_raster_paint_record(const vgx_paint& p, const vgx_raster_image* images, VgxRasterPaint* r)
+{
+	r->m[0] = p.matrix[0]; r->m[1] = p.matrix[1]; r->m[2] = p.matrix[3]; r->m[3] = p.matrix[4]; r->m[4] = p.matrix[6]; r->m[5] = p.matrix[7];
+	if (p.type == 1u) {
+		for (int k = 0; k < 4; ++k) { r->g.params[k] = p.params[k]; }
+		r->g.inner = vgx_raster_q8x4(p.inner_color); r->g.outer = vgx_raster_q8x4(p.outer_color);
+	} else {
+		r->im = images[p.image & 0xFFFFu];
+	}
+}
+
+// The triangle of a mesh of a GRADIENT draw on the pixel whose sample is (px, py): fs_color_gradient.sc, mix(inner, outer, t) with the
+// alpha times the vertex alpha; vertex RGB is not used
+VGX_HD uint32_t vgx_raster_gradient_pixel(const VgxRasterTri& T, const VgxRasterPaint& P, uint32_t mode, uint32_t f, uint32_t n, double px, double py, uint32_t S, uint32_t dst)
+{
+	if (mode != VGX_RF_PLAIN && !vgx_raster_stamp_pass(S, f, n, mode == VGX_RF_IN ? 0u : 1u)) { return dst; }
+	double E[3], sum, qx, qy;
+	if (!vgx_raster_cover(T, px, py, E, &sum)) { return dst; }
+	const uint32_t va = vgx_raster_channel(T, 3, E, sum);
+	if (va == 0u) { return dst; } // a == div255(g_A * 0) == 0
+	vgx_raster_paint_coord(P.m, px, py, &qx, &qy);
+	const double t = vgx_raster_gradient_t(P.g.params, qx, qy);
+	const uint32_t a = vgx_raster_div255(vgx_raster_mix8(P.g.inner >> 24, P.g.outer >> 24, t) * va);
+	if (a == 0u) { return dst; }
+	return vgx_raster_blend(dst, vgx_raster_mix8(P.g.inner & 255u, P.g.outer & 255u, t), vgx_raster_mix8((P.g.inner >> 8) & 255u, (P.g.outer >> 8) & 255u, t),
+	                        vgx_raster_mix8((P.g.inner >> 16) & 255u, (P.g.outer >> 16) & 255u, t), a);
+}
+
+// The triangle of a mesh of an IMAGE PATTERN draw: fs_image_pattern.sc, the texel rule of vgx_raster_textured at (u, v) = the paint
+// coordinate, modulated by the interpolated vertex colour (the pattern's tint). No UV of the stream is read
+template <class Fetch>
+VGX_HD uint32_t vgx_raster_pattern_pixel(const VgxRasterTri& T, const VgxRasterPaint& P, uint32_t mode, uint32_t f, uint32_t n, double px, double py, uint32_t S,
+                                         uint32_t dst, Fetch fetch)
+{
+	if (mode != VGX_RF_PLAIN && !vgx_raster_stamp_pass(S, f, n, mode == VGX_RF_IN ? 0u : 1u)) { return dst; }
+	double E[3], sum, qx, qy, U, V;
+	if (!vgx_raster_cover(T, px, py, E, &sum)) { return dst; }
+	vgx_raster_paint_coord(P.m, px, py, &qx, &qy);
+	if (!vgx_raster_texcoord(qx, P.im.width, &U) || !vgx_raster_texcoord(qy, P.im.height, &V)) { return dst; }
+	const uint32_t tc = vgx_raster_sample(P.im, U, V, fetch);
+	const uint32_t a = vgx_raster_div255(vgx_raster_channel(T, 3, E, sum) * (tc >> 24));
+	if (a == 0u) { return dst; }
+	return vgx_raster_blend(dst, vgx_raster_div255(vgx_raster_channel(T, 0, E, sum) * (tc & 255u)), vgx_raster_div255(vgx_raster_channel(T, 1, E, sum) * ((tc >> 8) & 255u)),
+	                        vgx_raster_div255(vgx_raster_channel(T, 2, E, sum) * ((tc >> 16) & 255u)), a);
+}
+
+// The state of a mesh under vgx_raster_painted: vgx_raster_textured_mesh_state, and for a painted mesh the table and the handle in
+// `pad`, or VGX_RF_INVALID when the handle, the entry or a pattern's image is no good. The tables are only read for a painted mesh
+VGX_HD void vgx_raster_painted_mesh_state(const vgx_mesh& me, uint32_t stateKey, const vgx_draw_state& ds, int32_t x0, int32_t y0, const uint32_t* scissor,
+                                          const vgx_raster_image* images, uint32_t numImages, const vgx_paint* gradients, uint32_t numGradients,
+                                          const vgx_paint* patterns, uint32_t numPatterns, VgxRasterMeshState* st)
+{
+	vgx_raster_textured_mesh_state(me, stateKey, ds, x0, y0, scissor, images, numImages, st);
+	const uint32_t painted = vgx_raster_mesh_painted(stateKey);
+	if (!painted) { return; }
+	const uint32_t handle = stateKey & 0xFFFFu;
+	const bool grad = painted == VGX_RT_GRADIENT;
+	if (handle >= (grad ? numGradients : numPatterns)) { st->mode = VGX_RF_INVALID; return; }
+	const vgx_paint* const p = (grad ? gradients : patterns) + handle;
+	if (p->type != (grad ? 1u : 2u)) { st->mode = VGX_RF_INVALID; return; }
+	if (!grad) {
+		const uint32_t im = p->image & 0xFFFFu;
+		if (im >= numImages || !vgx_raster_image_valid(images[im])) { st->mode = VGX_RF_INVALID; return; }
+	}
+	st->pad = painted | handle;
+}
+
 #endif

@@ -570,6 +570,250 @@ __global__ __launch_bounds__(256) void k_rastert_tiles(VgxRasterTexArgs X)
 	if (inside && (clear || d != before)) { *pixel = d; }
 }
 
+// ---- vgx_raster_painted: once more, with the meshes of gradient and image-pattern draws painted -------------------------------------
+//   k_rasterp_count    k_rastert_count, plus the paint check (handle inside the table of the draw's type, the entry of that type, a
+//                      pattern's image inside the image table and valid) with the same mark for a bad one; a good one leaves the table
+//                      and the handle in the state's pad word (a pattern's image is the entry's: read again where the slot is loaded)
+//   k_rasterp_entries  sets a second bit per tile: a painted mesh has an entry here
+//   k_rasterp_tiles    four instantiations <TEX, PAINT> over the same grid; a tile runs the one its two bits name, the others leave at
+//                      once. <false, false> is k_rasterf_tiles' body, LDS and records. PAINT adds, per slot of s_state, a 48-byte paint
+//                      record in LDS (six matrix floats and either four params and the two ends packed to 8 bits, or the image record),
+//                      built from the 96-byte table entry once per batch of meshes by the lane that loads the slot; with PAINT a sampled
+//                      slot keeps its image in the same record, so TEX and PAINT together need no second table. Nothing per triangle is
+//                      added: a record carries two more flag bits in slot_mode. The pixel loop reads the slot from LDS -- one address, a
+//                      broadcast -- and only texels from global memory; every lane walks every record, so the loop stays barrier-uniform.
+__global__ __launch_bounds__(256) void k_rasterp_count(VgxRasterPaintArgs P)
+{
+	const VgxRasterTexArgs& X = P.X;
+	const VgxRasterFrameArgs& F = X.F;
+	const VgxRasterArgs& A = F.R;
+	const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= A.nrange) { return; }
+	const uint64_t m = A.mesh_begin + k;
+	const vgx_mesh me = A.meshes[m];
+	VgxRasterMeshState st;
+	uint32_t entries = 0;
+	if (me.draw >= F.num_draws) {
+		st.mode = VGX_RF_INVALID; st.f = st.n = st.pad = 0u;
+		st.rect[0] = st.rect[1] = st.rect[2] = st.rect[3] = 0u;
+	} else {
+		vgx_raster_painted_mesh_state(me, F.draws[me.draw].state_key, F.draw_state[me.draw], A.x0, A.y0, A.scissor, X.images, X.num_images,
+		                              P.gradients, P.num_gradients, P.patterns, P.num_patterns, &st);
+		const float4 box = ((const float4*)A.mesh_bounds)[m];
+		const float b[4] = { box.x, box.y, box.z, box.w };
+		VgxRasterRect r;
+		if (st.mode != VGX_RF_NOTHING && st.mode != VGX_RF_INVALID && vgx_raster_any_mesh_tiles(me, b, A.x0, A.y0, st.rect, &r)) {
+			entries = (r.tx1 - r.tx0 + 1u) * (r.ty1 - r.ty0 + 1u);
+		}
+	}
+	F.mesh_state[k] = st;
+	A.mesh_entries[k] = entries;
+}
+
+// the tiles of rectangle r in a bitmap of one bit per tile: a row's tiles are consecutive bits, one atomic per word of 32, not per tile
+__device__ __forceinline__ void mark_tiles(uint32_t* bits, const VgxRasterRect& r, uint32_t tilesW)
+{
+	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
+		const uint32_t k0 = ty * tilesW + r.tx0, k1 = ty * tilesW + r.tx1; // < sentinel: the rectangle lies inside the image
+		for (uint32_t w = k0 >> 5; w <= (k1 >> 5); ++w) {
+			const uint32_t lo = w == (k0 >> 5) ? (k0 & 31u) : 0u, hi = w == (k1 >> 5) ? (k1 & 31u) : 31u;
+			atomicOr(&bits[w], (0xFFFFFFFFu >> (31u - hi)) & (0xFFFFFFFFu << lo));
+		}
+	}
+}
+
+__global__ __launch_bounds__(256) void k_rasterp_entries(VgxRasterPaintArgs P)
+{
+	const VgxRasterFrameArgs& F = P.X.F;
+	const VgxRasterArgs& A = F.R;
+	if (A.state[0] != VGX_OK) { return; }
+	const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= A.state[1] && k < A.sort_n) { A.keys[k] = A.sentinel; A.vals[k] = 0u; }
+	if (k >= A.nrange || A.mesh_entries[k] == 0u) { return; }
+	const uint64_t m = A.mesh_begin + k;
+	const float4 box = ((const float4*)A.mesh_bounds)[m];
+	const float b[4] = { box.x, box.y, box.z, box.w };
+	const VgxRasterMeshState st = F.mesh_state[k];
+	VgxRasterRect r;
+	if (!vgx_raster_any_mesh_tiles(A.meshes[m], b, A.x0, A.y0, st.rect, &r)) { return; } // (not taken: the count found entries)
+	uint64_t at = A.mesh_first[k]; // + the mesh's entries <= the total <= entry_cap: checked by finish()
+	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
+		for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx, ++at) { A.keys[at] = ty * A.tiles_w + tx; A.vals[at] = (uint32_t)m; }
+	}
+	if (st.pad & VGX_RT_SAMPLED) { mark_tiles(P.X.tile_tex, r, A.tiles_w); }
+	if (st.pad & VGX_RT_PAINTED) { mark_tiles(P.tile_paint, r, A.tiles_w); }
+}
+
+// what a slot of s_state keeps beside it: nothing, the image of a sampled mesh, or the paint record (whose image part serves a sampled mesh)
+template <bool TEX, bool PAINT> struct RasterPaintSlot { typedef uint32_t type; enum { N = 1 }; };
+template <> struct RasterPaintSlot<true, false> { typedef vgx_raster_image type; enum { N = 256 }; };
+template <bool TEX> struct RasterPaintSlot<TEX, true> { typedef VgxRasterPaint type; enum { N = 256 }; };
+__device__ __forceinline__ vgx_raster_image& slot_image(vgx_raster_image& s) { return s; }
+__device__ __forceinline__ vgx_raster_image& slot_image(VgxRasterPaint& s) { return s.im; }
+// slot_mode of a record: the slot (bits 0 .. 7), the mode (8 .. 15), VGX_RTT_SAMPLED, and the two paint bits
+#define VGX_RTP_GRADIENT 0x20000u
+#define VGX_RTP_PATTERN  0x40000u
+
+template <bool TEX, bool PAINT>
+__global__ __launch_bounds__(256) void k_rasterp_tiles(VgxRasterPaintArgs P)
+{
+	typedef typename RasterTexRecord<TEX>::type Record;
+	typedef typename RasterPaintSlot<TEX, PAINT>::type Slot;
+	__shared__ Record s_tri[256];
+	__shared__ uint64_t s_first[257];   // exclusive prefix of the triangle counts of the (at most 256) meshes in hand
+	__shared__ uint32_t s_mesh[256];
+	__shared__ VgxRasterTileState s_state[256];
+	__shared__ Slot s_slot[RasterPaintSlot<TEX, PAINT>::N]; // written for the sampled and the painted slots only, and not read for the others
+	__shared__ uint32_t s_flags[TEX || PAINT ? 256 : 1];   // VGX_RTT_SAMPLED / VGX_RTP_* or 0 per slot
+	__shared__ Sum3 s_wave[4];
+	__shared__ uint32_t s_count[4];
+	const VgxRasterTexArgs& X = P.X;
+	const VgxRasterFrameArgs& F = X.F;
+	const VgxRasterArgs& A = F.R;
+	if (A.state[0] != VGX_OK) { return; }
+	const uint32_t tx = A.tile_x0 + blockIdx.x, ty = A.tile_y0 + blockIdx.y;
+	const uint32_t key = ty * A.tiles_w + tx;
+	// block-uniform: the tile of another instantiation
+	if ((((X.tile_tex[key >> 5] >> (key & 31u)) & 1u) != 0u) != TEX || (((P.tile_paint[key >> 5] >> (key & 31u)) & 1u) != 0u) != PAINT) { return; }
+	const uint32_t tid = threadIdx.x;
+	const int lane = tid & (VGX_WAVE - 1);
+	const uint32_t wave = tid >> 6;
+	const uint32_t lx = tid & 15u, ly = tid >> 4;
+	const uint32_t ox = tx * VGX_RASTER_TILE, oy = ty * VGX_RASTER_TILE;
+	const uint32_t i = ox + lx, j = oy + ly;
+	const bool inside = i >= A.scissor[0] && i < A.scissor[2] && j >= A.scissor[1] && j < A.scissor[3];
+	const uint32_t r0 = lower_bound_u32(A.sorted_keys, A.sort_n, key), r1 = lower_bound_u32(A.sorted_keys, A.sort_n, key + 1u);
+	const bool clear = (A.flags & VGX_RASTER_CLEAR) != 0;
+	if (r0 == r1 && !clear) { return; } // block-uniform
+	uint32_t* const pixel = A.pixels + (uint64_t)j * A.stride + i;
+	const uint32_t before = inside ? (clear ? A.clear_color : *pixel) : 0u;
+	uint32_t d = before;
+	uint32_t S = VGX_RASTER_STAMP_NONE;
+	const double px = (double)(A.x0 + (int32_t)i) + 0.5, py = (double)(A.y0 + (int32_t)j) + 0.5;
+	for (uint32_t eb = r0; eb < r1; eb += 256u) { // block-uniform loops throughout
+		const uint32_t ne = min(256u, r1 - eb);
+		Sum3 v = sum3_zero();
+		if (tid < ne) {
+			const uint32_t m = A.sorted_vals[eb + tid];
+			s_mesh[tid] = m;
+			v.a = A.meshes[m].num_indices / 3u;
+			// the mesh's rectangle cut to this tile (an entry means its box reaches the tile inside the rectangle: not empty)
+			const VgxRasterMeshState ms = F.mesh_state[m - A.mesh_begin];
+			const uint32_t cx0 = max(ox, ms.rect[0]), cx1 = min(ox + VGX_RASTER_TILE, ms.rect[2]);
+			const uint32_t cy0 = max(oy, ms.rect[1]), cy1 = min(oy + VGX_RASTER_TILE, ms.rect[3]);
+			VgxRasterTileState ts;
+			ts.f = ms.f; ts.n = ms.n;
+			ts.mode_rect = cx0 < cx1 && cy0 < cy1 ? (ms.mode << 20) | ((cy1 - oy) << 15) | ((cx1 - ox) << 10) | ((cy0 - oy) << 5) | (cx0 - ox) : (uint32_t)VGX_RF_NOTHING << 20;
+			s_state[tid] = ts;
+			if constexpr (TEX || PAINT) {
+				uint32_t fl = 0u;
+				// handles and records are inside their tables and valid: k_rasterp_count
+				if constexpr (TEX) {
+					if (ms.pad & VGX_RT_SAMPLED) { fl = VGX_RTT_SAMPLED; slot_image(s_slot[tid]) = X.images[ms.pad & 0xFFFFu]; }
+				}
+				if constexpr (PAINT) {
+					if (ms.pad & VGX_RT_PAINTED) {
+						const bool grad = (ms.pad & VGX_RT_GRADIENT) != 0u;
+						fl = grad ? VGX_RTP_GRADIENT : VGX_RTP_PATTERN;
+						VgxRasterPaint rec;
+						vgx_raster_paint_record((grad ? P.gradients : P.patterns)[ms.pad & 0xFFFFu], X.images, &rec);
+						s_slot[tid] = rec;
+					}
+				}
+				s_flags[tid] = fl;
+			}
+		}
+		Sum3 tot;
+		const Sum3 incl = block_incl_scan<256>(v, s_wave, &tot);
+		s_first[tid + 1u] = incl.a;
+		if (tid == 0u) { s_first[0] = 0; }
+		__syncthreads();
+		for (uint64_t tb = 0; tb < tot.a; tb += 256u) {
+			const uint64_t g = tb + tid;
+			bool keep = false;
+			Record R;
+			VgxRasterFrameTri& RF = frame_part(R);
+			double uv[6];
+			if (g < tot.a) {
+				uint32_t lo = 0, hi = ne; // the last mesh whose first triangle is <= g
+				while (hi - lo > 1u) {
+					const uint32_t mid = (lo + hi) >> 1;
+					if (s_first[mid] <= g) { lo = mid; } else { hi = mid; }
+				}
+				const uint32_t mr = s_state[lo].mode_rect;
+				const uint32_t fl = TEX || PAINT ? s_flags[lo] : 0u;
+				const vgx_mesh me = A.meshes[s_mesh[lo]];
+				const uint16_t* ip = A.idx + me.first_index + 3ull * (g - s_first[lo]);
+				const uint32_t i0 = ip[0], i1 = ip[1], i2 = ip[2];
+				if ((mr >> 20) != VGX_RF_NOTHING && i0 < me.num_vertices && i1 < me.num_vertices && i2 < me.num_vertices) {
+					const float2* pp = (const float2*)A.pos + me.first_vertex;
+					const uint32_t* cp = A.color + me.first_vertex;
+					const float2 p0 = pp[i0], p1 = pp[i1], p2 = pp[i2];
+					uint32_t a0, a1, b0, b1;
+					const uint32_t cols = ((1u << ((mr >> 10) & 31u)) - 1u) & ~((1u << (mr & 31u)) - 1u), rows = ((1u << ((mr >> 15) & 31u)) - 1u) & ~((1u << ((mr >> 5) & 31u)) - 1u);
+					RF.slot_mode = lo | ((mr >> 20) << 8) | fl; RF.mask = cols | (rows << 16);
+					keep = vgx_raster_setup(v2(p0.x, p0.y), v2(p1.x, p1.y), v2(p2.x, p2.y), cp[i0], cp[i1], cp[i2], &RF.T)
+					    && vgx_raster_span(RF.T.minx, RF.T.maxx, A.x0, ox + (mr & 31u), ox + ((mr >> 10) & 31u), &a0, &a1)
+					    && vgx_raster_span(RF.T.miny, RF.T.maxy, A.y0, oy + ((mr >> 5) & 31u), oy + ((mr >> 15) & 31u), &b0, &b1);
+					if (TEX && keep && (fl & VGX_RTT_SAMPLED)) {
+						vgx_raster_uv_widen(X.uv, X.uv_bytes, me.first_vertex + i0, uv);
+						vgx_raster_uv_widen(X.uv, X.uv_bytes, me.first_vertex + i1, uv + 2);
+						vgx_raster_uv_widen(X.uv, X.uv_bytes, me.first_vertex + i2, uv + 4);
+					}
+				}
+			}
+			const uint64_t kept = wave_ballot(keep);
+			if (lane == 0) { s_count[wave] = (uint32_t)__popcll(kept); }
+			__syncthreads();
+			uint32_t base = 0, n = 0;
+#pragma unroll
+			for (uint32_t w = 0; w < 4u; ++w) { const uint32_t c = s_count[w]; base += w < wave ? c : 0u; n += c; }
+			if (keep) {
+				Record* const dst = &s_tri[base + (uint32_t)__popcll(kept & lanemask_lt(lane))];
+				frame_part(*dst) = RF;
+				if (TEX && (RF.slot_mode & VGX_RTT_SAMPLED)) { store_uv(dst, uv); }
+			}
+			__syncthreads();
+			for (uint32_t t = 0; t < n; ++t) { // every lane walks the records: no lane leaves between the barriers
+				const VgxRasterFrameTri& rec = frame_part(s_tri[t]);
+				const uint32_t mk = rec.mask; // beside the record: an untested mesh needs no second, dependent LDS read
+				if (((mk >> lx) & (mk >> (16u + ly)) & 1u) != 0u) {
+					const uint32_t sm = rec.slot_mode;
+					const uint32_t mode = (sm >> 8) & 255u;
+					uint32_t f = 0u, n = 0u;
+					if (mode != VGX_RF_PLAIN) { const VgxRasterTileState ts = s_state[sm & 255u]; f = ts.f; n = ts.n; }
+					bool done = false;
+					if constexpr (TEX) {
+						if (sm & VGX_RTT_SAMPLED) {
+							const vgx_raster_image im = slot_image(s_slot[sm & 255u]);
+							VgxRasterTexelFetch fetch;
+							fetch.pixels = im.pixels; fetch.stride = im.stride;
+							d = vgx_raster_textured_pixel(rec.T, record_uv(s_tri[t]), im, mode, f, n, px, py, S, d, fetch);
+							done = true;
+						}
+					}
+					if constexpr (PAINT) {
+						if (sm & VGX_RTP_GRADIENT) {
+							d = vgx_raster_gradient_pixel(rec.T, s_slot[sm & 255u], mode, f, n, px, py, S, d);
+							done = true;
+						} else if (sm & VGX_RTP_PATTERN) {
+							const VgxRasterPaint pr = s_slot[sm & 255u];
+							VgxRasterTexelFetch fetch;
+							fetch.pixels = pr.im.pixels; fetch.stride = pr.im.stride;
+							d = vgx_raster_pattern_pixel(rec.T, pr, mode, f, n, px, py, S, d, fetch);
+							done = true;
+						}
+					}
+					if (!done) { d = vgx_raster_frame_pixel(rec.T, mode, f, n, px, py, &S, d); }
+				}
+			}
+			__syncthreads(); // s_tri and s_count are written again
+		}
+		__syncthreads(); // s_mesh, s_state, s_slot, s_flags and s_first are written again
+	}
+	if (inside && (clear || d != before)) { *pixel = d; }
+}
+
 } // namespace
 
 size_t vgx_raster_sort_bytes(uint64_t n, uint32_t bits)
@@ -634,6 +878,29 @@ hipError_t vgx_launch_raster_textured(const VgxRasterTexArgs& x, void* partial, 
 	if (a.tiles_x && a.tiles_y) {
 		hipLaunchKernelGGL(k_rastert_tiles<false>, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, x);
 		hipLaunchKernelGGL(k_rastert_tiles<true>, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, x);
+	}
+	return hipSuccess;
+}
+
+hipError_t vgx_launch_raster_painted(const VgxRasterPaintArgs& p, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
+{
+	const VgxRasterArgs& a = p.X.F.R;
+	if (a.nrange) { hipLaunchKernelGGL(k_rasterp_count, dim3((unsigned)((a.nrange + 255) / 256)), dim3(256), 0, s, p); }
+	OpRasterFrameBin op; // the marks of k_rasterp_count are the ones of k_rasterf_count
+	op.F = p.X.F;
+	vgx_device_scan(op, (Sum3*)partial, s, a.nrange);
+	const uint64_t items = a.nrange > a.sort_n ? a.nrange : a.sort_n;
+	if (items) { hipLaunchKernelGGL(k_rasterp_entries, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p); }
+	if (a.sort_n) {
+		const hipError_t e = rocprim::radix_sort_pairs(sortTemp, sortBytes, (const uint32_t*)a.keys, a.sorted_keys, (const uint32_t*)a.vals, a.sorted_vals,
+		                                               (size_t)a.sort_n, 0u, a.sort_bits, s);
+		if (e != hipSuccess) { return e; }
+	}
+	if (a.tiles_x && a.tiles_y) {
+		hipLaunchKernelGGL((k_rasterp_tiles<false, false>), dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, p);
+		hipLaunchKernelGGL((k_rasterp_tiles<true, false>), dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, p);
+		hipLaunchKernelGGL((k_rasterp_tiles<false, true>), dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, p);
+		hipLaunchKernelGGL((k_rasterp_tiles<true, true>), dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, p);
 	}
 	return hipSuccess;
 }

@@ -754,8 +754,51 @@ def raster_textured(ctx, frame, draws_dev, draw_state_dev, num_draws, uv_dev, uv
     return image, dev_status
 
 
+def paint_tables(paints, num_gradients=None, num_patterns=None):
+    """vgx_paint_tables: scatters the vgx_paint records vgx_cmdlist_decode wrote (a capi.paint_dtype array) into the gradient table and
+    the pattern table raster_painted() indexes by handle; entries no record names have type capi.PAINT_UNUSED. The sizes default to
+    the highest handle of each type plus one. Returns (gradients, patterns) as capi.paint_dtype arrays. Host only."""
+    import numpy as np
+    paints = np.ascontiguousarray(paints, dtype=capi.paint_dtype)
+    caps = []
+    for given, t in ((num_gradients, capi.DRAW_TYPE_GRADIENT), (num_patterns, capi.DRAW_TYPE_PATTERN)):
+        h = paints["handle"][paints["type"] == t]
+        caps.append(int(given) if given is not None else (int(h.max()) + 1 if h.size else 0))
+    g, p = np.zeros(max(caps[0], 1), capi.paint_dtype), np.zeros(max(caps[1], 1), capi.paint_dtype)
+    _check(lib().vgx_paint_tables(paints.ctypes.data if paints.shape[0] else None, int(paints.shape[0]), g.ctypes.data, caps[0], p.ctypes.data, caps[1]),
+           "vgx_paint_tables")
+    return g[:caps[0]], p[:caps[1]]
+
+
+def raster_painted(ctx, frame, draws_dev, draw_state_dev, num_draws, uv_dev, uv_bytes, images_dev, num_images, gradients_dev, num_gradients, patterns_dev,
+                   num_patterns, width, height, x0=0, y0=0, scissor=None, clear_color=None, bounds_dev=None, mesh_begin=0, mesh_end=None, image=None,
+                   dev_status=None):
+    """raster_textured() that also paints: a mesh whose draw has type 1 (ColorGradient) or 2 (ImagePattern) takes its colour from the
+    vgx_paint record its draw names (state_key & 0xFFFF indexes gradients_dev / patterns_dev, the tables of paint_tables() as uint8
+    device tensors; a pattern's .image indexes images_dev) by the fragment rule of vgx_raster_painted in include/vgx.h. dev_status may
+    also come out as VGX_E_INVALID_ARG for a painted mesh whose handle, table entry or image is no good: nothing was written.
+    Returns (image, dev_status) as raster() does. Asynchronous."""
+    import torch
+    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
+    if image is None:
+        image = torch.zeros((max(int(height), 1), max(int(width), 1)), dtype=torch.int32, device="cuda:%d" % ctx.device)[:height, :width]
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
+    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
+    t = capi.RasterTarget(image.data_ptr(), int(width), int(height), int(image.stride(0)) if image.dim() == 2 and height else int(width), int(x0), int(y0),
+                          (C.c_uint32 * 4)(*sc), capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
+    st = capi.RasterDraws(draws_dev.data_ptr() if num_draws else None, draw_state_dev.data_ptr() if num_draws else None, int(num_draws), 0)
+    tx = capi.RasterTextures(uv_dev.data_ptr() if uv_dev is not None else None, images_dev.data_ptr() if num_images else None, int(uv_bytes), int(num_images))
+    pt = capi.RasterPaints(gradients_dev.data_ptr() if num_gradients else None, patterns_dev.data_ptr() if num_patterns else None, int(num_gradients),
+                           int(num_patterns))
+    _check(lib().vgx_raster_painted(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
+                                    0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), C.byref(tx), C.byref(pt), C.byref(t),
+                                    dev_status.data_ptr(), _stream_ptr()), "vgx_raster_painted")
+    return image, dev_status
+
+
 def raster_reserve(ctx, num_meshes, num_bin_entries):
-    """Sizes the scratch of raster(), raster_frame() and raster_textured() ahead, so that a first call does not end with VGX_E_GROWN."""
+    """Sizes the scratch of raster(), raster_frame(), raster_textured() and raster_painted() ahead, so that a first call does not end with VGX_E_GROWN."""
     _check(lib().vgx_raster_reserve(ctx.handle, int(num_meshes), int(num_bin_entries)), "vgx_raster_reserve")
 
 
