@@ -1,4 +1,5 @@
-"""GPU: vgx_raster_frame (csrc/vgx_raster.hip: k_rasterf_count / k_rasterf_entries / k_rasterf_tiles) against the numpy statement
+"""GPU: vgx_raster_frame (csrc/vgx_raster.hip: the frame family k_rasterf_count / k_rasterf_entries / k_rasterf_tiles<false, false> at
+the frame level) against the numpy statement
 (tests/raster_frame_model.py) on its four frames -- `decoded` after GPU tessellation of the decoded batch -- and against vgx_raster
 where the new state must change nothing or amounts to a scissor. Every comparison is np.array_equal on the whole uint32 buffer: the
 stride padding and everything outside the scissor included."""

@@ -1,4 +1,5 @@
-"""GPU: vgx_raster_painted (csrc/vgx_raster.hip: k_rasterp_count / k_rasterp_entries / k_rasterp_tiles) against the numpy statement
+"""GPU: vgx_raster_painted (csrc/vgx_raster.hip: the frame family k_rasterf_count / k_rasterf_entries / k_rasterf_tiles<TEX, PAINT> at
+the painted level) against the numpy statement
 (tests/raster_painted_model.py) on its frames, against the six checks of tests/test_raster_painted_cpu.py that do not rest on that
 model (run here through the kernels, with the GPU's own vgx_raster_textured where they compare against it), the statuses and the
 VGX_E_GROWN protocol, and end to end from command-list bytes: vgx_cmdlist_decode -> vgx_paint_tables -> the tessellator on the device

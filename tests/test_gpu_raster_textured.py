@@ -1,4 +1,5 @@
-"""GPU: vgx_raster_textured (csrc/vgx_raster.hip: k_rastert_count / k_rastert_entries / k_rastert_tiles) against the numpy statement
+"""GPU: vgx_raster_textured (csrc/vgx_raster.hip: the frame family k_rasterf_count / k_rasterf_entries / k_rasterf_tiles<TEX, false> at
+the textured level) against the numpy statement
 (tests/raster_textured_model.py) on its frames, against the GPU's own vgx_raster_frame where the images are white or no mesh is
 sampled, and end to end from command-list bytes: vgx_text_quads -> vgx_merge_uv_stream -> vgx_raster_textured. Every comparison is
 np.array_equal on the whole uint32 buffer: the stride padding and everything outside the scissor included."""

@@ -1,5 +1,5 @@
-"""CPU: the lane code of vgx_raster_painted (csrc/vgx_raster.h through libvgx_hosttest.so: vgxt_raster_painted, vgxt_raster_textured's loop
-with the paint functions) against the numpy statement (tests/raster_painted_model.py), and against six things that do not rest on that
+"""CPU: the lane code of vgx_raster_painted (csrc/vgx_raster.h through libvgx_hosttest.so: vgxt_raster_painted, the host loop of the
+frame-level calls at the painted level) against the numpy statement (tests/raster_painted_model.py), and against six things that do not rest on that
 model: two closed forms of a gradient, a gradient of one colour against vgxt_raster_textured, a 1:1 pattern blit computed from div255
 alone, a pattern against a sampled quad with the same map, and the frames without a painted draw. vgx_paint_tables is checked here too
 (host only). Exact everywhere: np.array_equal on the uint32 images, the stride padding and everything outside the scissor included.

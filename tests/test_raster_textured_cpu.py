@@ -1,5 +1,5 @@
-"""CPU: the lane code of vgx_raster_textured (csrc/vgx_raster.h through libvgx_hosttest.so: vgxt_raster_textured, vgxt_raster_frame's
-loop with the sampling functions) against the numpy statement (tests/raster_textured_model.py), and against three things that do
+"""CPU: the lane code of vgx_raster_textured (csrc/vgx_raster.h through libvgx_hosttest.so: vgxt_raster_textured, the host loop of
+the frame-level calls at the textured level) against the numpy statement (tests/raster_textured_model.py), and against three things that do
 not rest on that model: a blit computed here from div255, vgxt_raster_frame on white images, and vgxt_raster_frame on frames without
 a sampled mesh. Exact everywhere: np.array_equal on the uint32 images, the stride padding and everything outside the scissor
 included. tests/test_gpu_raster_textured.py makes the same comparisons on the kernels."""

@@ -108,7 +108,7 @@ struct vgx_ctx
 	// in tile order; the sort's temporary storage; status and entry count of the last call with their pinned mirror (as `dash`: a call
 	// whose entries outgrew the tables ends with VGX_E_GROWN and the next one grows first). Its own: a counted state survives the call
 	Buf<uint32_t> rasMeshEntries, rasKeys, rasVals, rasSortedKeys, rasSortedVals; Buf<uint64_t> rasMeshFirst; Buf<unsigned long long> rasState; Buf<float> rasBounds;
-	Buf<VgxRasterMeshState> rasFrameMesh; // vgx_raster_frame alone: what every mesh of the range does under its draw (vgx_raster.h)
+	Buf<VgxRasterMeshState> rasFrameMesh; // the frame-level calls: what every mesh of the range does under its draw (vgx_raster.h)
 	Buf<uint32_t> rasTileTex;             // vgx_raster_textured and vgx_raster_painted: one bit per tile of the image, "a sampled mesh reaches it"
 	Buf<uint32_t> rasTilePaint;           // vgx_raster_painted alone: the same for "a painted mesh reaches it"
 	DevBuf rasSortTemp, rasPartial;      // rasPartial: slice sums (views: as `partial`)
@@ -2736,37 +2736,16 @@ int vgx_raster_reserve(vgx_ctx* ctx, uint64_t num_meshes, uint64_t num_bin_entri
 
 namespace {
 
-// vgx_raster (state == nullptr), vgx_raster_frame (tex == nullptr), vgx_raster_textured (paints == nullptr) and vgx_raster_painted: one
-// body, the kernels differ
-int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+// The four calls are one body; `level` (VGX_RL_*, vgx_raster.h) says which pointers count and which kernel family runs
+int rasterCall(int level, vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
                const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
-	if (!ctx || !frame || !target) { return VGX_E_INVALID_ARG; }
-	if (paints) {
-		if ((paints->num_gradients && !paints->gradients) || (paints->num_patterns && !paints->patterns)) { return VGX_E_INVALID_ARG; }
-		if (((uintptr_t)paints->gradients & 3u) || ((uintptr_t)paints->patterns & 3u)) { return VGX_E_INVALID_ARG; }
-	}
-	if (tex) {
-		if ((tex->uv_bytes != 4u && tex->uv_bytes != 8u) || (tex->num_images && !tex->images) || ((uintptr_t)tex->images & 7u)) { return VGX_E_INVALID_ARG; }
-		const uint64_t e = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
-		if (mesh_begin < e && (!tex->uv || ((uintptr_t)tex->uv & (tex->uv_bytes - 1u)))) { return VGX_E_INVALID_ARG; }
-	}
-	if (state) {
-		if (state->reserved != 0u || (state->num_draws && (!state->draws || !state->draw_state))) { return VGX_E_INVALID_ARG; }
-		if (((uintptr_t)state->draws & 3u) || ((uintptr_t)state->draw_state & 3u)) { return VGX_E_INVALID_ARG; }
-	}
+	if (!ctx) { return VGX_E_INVALID_ARG; }
+	int st = vgx_raster_check_args(level, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, dev_status);
+	if (st != VGX_OK) { return st; }
 	const vgx_raster_target& t = *target;
-	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
-	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
-	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)dev_status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
-		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
-		return VGX_E_INVALID_ARG;
-	}
 	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
-	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
-	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
 	hipStream_t s = (hipStream_t)stream;
 	if (empty) { // no pixel to write
 		if (dev_status) { noteHip(ctx, hipMemsetAsync(dev_status, 0, sizeof(uint32_t), s)); } // VGX_OK
@@ -2781,7 +2760,6 @@ int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_boun
 	a.tiles_x = (t.scissor[2] - 1) / VGX_RASTER_TILE - a.tile_x0 + 1; a.tiles_y = (t.scissor[3] - 1) / VGX_RASTER_TILE - a.tile_y0 + 1;
 	a.sentinel = a.tiles_w * ((t.height + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE); // <= 2^20
 	for (a.sort_bits = 1; (a.sentinel >> a.sort_bits) != 0; ++a.sort_bits) { }
-	int st;
 	if ((st = ctx->ras.create(ctx, 2)) != VGX_OK) { return st; }
 	// the entry tables: what the last call measured (once that has arrived), else what they hold, else one entry per mesh
 	uint64_t entries = ctx->rasKeys.cap ? ctx->rasKeys.items() - 1 : nrange;
@@ -2810,35 +2788,29 @@ int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_boun
 	a.mesh_entries = ctx->rasMeshEntries.ptr(); a.mesh_first = ctx->rasMeshFirst.ptr();
 	a.keys = ctx->rasKeys.ptr(); a.vals = ctx->rasVals.ptr(); a.sorted_keys = ctx->rasSortedKeys.ptr(); a.sorted_vals = ctx->rasSortedVals.ptr();
 	a.state = ctx->rasState.ptr(); a.status = dev_status;
-	if (state) {
+	if (level == VGX_RL_PLAIN) {
+		noteHip(ctx, vgx_launch_raster(a, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+	} else {
 		if ((st = ensure(ctx, ctx->rasFrameMesh, nrange + 1)) != VGX_OK) { return st; }
 		VgxRasterFrameArgs f;
 		memset(&f, 0, sizeof(f));
-		f.R = a; f.draws = state->draws; f.draw_state = state->draw_state; f.num_draws = state->num_draws; f.mesh_state = ctx->rasFrameMesh.ptr();
-		if (tex) {
-			VgxRasterTexArgs x;
-			memset(&x, 0, sizeof(x));
-			x.F = f; x.uv = tex->uv; x.images = tex->images; x.uv_bytes = tex->uv_bytes; x.num_images = tex->num_images;
-			const uint64_t words = ((uint64_t)a.sentinel + 31u) / 32u;
+		f.R = a; f.level = level;
+		f.draws = state->draws; f.draw_state = state->draw_state; f.num_draws = state->num_draws; f.mesh_state = ctx->rasFrameMesh.ptr();
+		// a tile bitmap exists, zeroed, at the levels that can set a bit in it; below them the pointer stays null: "no bit set"
+		const uint64_t words = ((uint64_t)a.sentinel + 31u) / 32u;
+		if (level >= VGX_RL_TEXTURED) {
+			f.uv = tex->uv; f.images = tex->images; f.uv_bytes = tex->uv_bytes; f.num_images = tex->num_images;
 			if ((st = ensure(ctx, ctx->rasTileTex, words + 1)) != VGX_OK) { return st; }
 			noteHip(ctx, hipMemsetAsync(ctx->rasTileTex.p, 0, words * sizeof(uint32_t), s));
-			x.tile_tex = ctx->rasTileTex.ptr();
-			if (paints) {
-				VgxRasterPaintArgs p;
-				memset(&p, 0, sizeof(p));
-				p.X = x; p.gradients = paints->gradients; p.patterns = paints->patterns; p.num_gradients = paints->num_gradients; p.num_patterns = paints->num_patterns;
-				if ((st = ensure(ctx, ctx->rasTilePaint, words + 1)) != VGX_OK) { return st; }
-				noteHip(ctx, hipMemsetAsync(ctx->rasTilePaint.p, 0, words * sizeof(uint32_t), s));
-				p.tile_paint = ctx->rasTilePaint.ptr();
-				noteHip(ctx, vgx_launch_raster_painted(p, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
-			} else {
-				noteHip(ctx, vgx_launch_raster_textured(x, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
-			}
-		} else {
-			noteHip(ctx, vgx_launch_raster_frame(f, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+			f.tile_tex = ctx->rasTileTex.ptr();
 		}
-	} else {
-		noteHip(ctx, vgx_launch_raster(a, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+		if (level >= VGX_RL_PAINTED) {
+			f.gradients = paints->gradients; f.patterns = paints->patterns; f.num_gradients = paints->num_gradients; f.num_patterns = paints->num_patterns;
+			if ((st = ensure(ctx, ctx->rasTilePaint, words + 1)) != VGX_OK) { return st; }
+			noteHip(ctx, hipMemsetAsync(ctx->rasTilePaint.p, 0, words * sizeof(uint32_t), s));
+			f.tile_paint = ctx->rasTilePaint.ptr();
+		}
+		noteHip(ctx, vgx_launch_raster_frame(f, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
 	}
 	// status and entry count to the mirror, for the next call (never waited for)
 	ctx->ras.push(ctx, a.state, s);
@@ -2850,29 +2822,26 @@ int rasterCall(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_boun
 int vgx_raster(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
-	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, nullptr, nullptr, nullptr, target, dev_status, stream);
+	return rasterCall(VGX_RL_PLAIN, ctx, frame, mesh_bounds, mesh_begin, mesh_end, nullptr, nullptr, nullptr, target, dev_status, stream);
 }
 
 int vgx_raster_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                      const vgx_raster_draws* state, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
-	if (!state) { return VGX_E_INVALID_ARG; }
-	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, nullptr, nullptr, target, dev_status, stream);
+	return rasterCall(VGX_RL_FRAME, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, nullptr, nullptr, target, dev_status, stream);
 }
 
 int vgx_raster_textured(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                         const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
-	if (!state || !tex) { return VGX_E_INVALID_ARG; }
-	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, nullptr, target, dev_status, stream);
+	return rasterCall(VGX_RL_TEXTURED, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, nullptr, target, dev_status, stream);
 }
 
 int vgx_raster_painted(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                        const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target,
                        uint32_t* dev_status, void* stream)
 {
-	if (!state || !tex || !paints) { return VGX_E_INVALID_ARG; }
-	return rasterCall(ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, dev_status, stream);
+	return rasterCall(VGX_RL_PAINTED, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, dev_status, stream);
 }
 
 // HOST only, no context: the decoder's paint list scattered by handle into the two tables vgx_raster_painted indexes; holes marked

@@ -544,20 +544,11 @@ extern "C" {
 int vgxt_raster(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_target* target,
                 uint32_t* status)
 {
-	if (!frame || !target) { return VGX_E_INVALID_ARG; }
+	const int rc = vgx_raster_check_args(VGX_RL_PLAIN, frame, mesh_bounds, mesh_begin, mesh_end, nullptr, nullptr, nullptr, target, status);
+	if (rc != VGX_OK) { return rc; }
 	const vgx_raster_target& t = *target;
-	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
-	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
-	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
-		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
-		return VGX_E_INVALID_ARG;
-	}
-	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
-	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
-	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
 	if (status) { *status = VGX_OK; }
-	if (empty) { return VGX_OK; }
+	if (t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3]) { return VGX_OK; }
 	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
 	float* own = nullptr;
 	if (!mesh_bounds && mesh_begin < end) {
@@ -573,7 +564,7 @@ int vgxt_raster(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t 
 	for (uint64_t m = mesh_begin; m < end; ++m) {
 		const vgx_mesh me = frame->meshes[m];
 		VgxRasterRect r;
-		if (!vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, t.scissor, &r)) { continue; }
+		if (!vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, t.scissor, true, &r)) { continue; }
 		const uint16_t* ip = frame->idx + me.first_index;
 		const float* pp = frame->pos + 2 * me.first_vertex;
 		const uint32_t* cp = frame->color + me.first_vertex;
@@ -597,112 +588,33 @@ int vgxt_raster(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t 
 	return VGX_OK;
 }
 
-// vgx_raster_frame on the host: vgxt_raster's loop with the per-draw state of vgx_raster.h and a stamp image of its own. HOST pointers
-// throughout. The meshes are looked at twice: first for a draw index outside the table (nothing may be written then), then drawn.
-int vgxt_raster_frame(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
-                      const vgx_raster_target* target, uint32_t* status)
-{
-	if (!frame || !target || !state) { return VGX_E_INVALID_ARG; }
-	if (state->reserved != 0u || (state->num_draws && (!state->draws || !state->draw_state))) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)state->draws & 3u) || ((uintptr_t)state->draw_state & 3u)) { return VGX_E_INVALID_ARG; }
-	const vgx_raster_target& t = *target;
-	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
-	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
-	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
-		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
-		return VGX_E_INVALID_ARG;
-	}
-	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
-	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
-	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
-	if (status) { *status = VGX_OK; }
-	if (empty) { return VGX_OK; }
-	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
-	for (uint64_t m = mesh_begin; m < end; ++m) {
-		if (frame->meshes[m].draw >= state->num_draws) {
-			if (status) { *status = VGX_E_INVALID_ARG; }
-			return VGX_OK;
-		}
-	}
-	float* own = nullptr;
-	if (!mesh_bounds && mesh_begin < end) {
-		own = (float*)malloc(frame->num_meshes * 4 * sizeof(float));
-		if (!own) { return VGX_E_INTERNAL; }
-		vgxt_mesh_bounds(frame->pos, frame->meshes, frame->num_meshes, own);
-	}
-	uint32_t* stamp = (uint32_t*)malloc((size_t)t.width * t.height * sizeof(uint32_t));
-	if (!stamp) { free(own); return VGX_E_INTERNAL; }
-	for (size_t k = 0; k < (size_t)t.width * t.height; ++k) { stamp[k] = VGX_RASTER_STAMP_NONE; }
-	if (t.flags & VGX_RASTER_CLEAR) {
-		for (uint32_t j = t.scissor[1]; j < t.scissor[3]; ++j) {
-			for (uint32_t i = t.scissor[0]; i < t.scissor[2]; ++i) { t.pixels[(uint64_t)j * t.stride + i] = t.clear_color; }
-		}
-	}
-	for (uint64_t m = mesh_begin; m < end; ++m) {
-		const vgx_mesh me = frame->meshes[m];
-		VgxRasterMeshState ms;
-		vgx_raster_mesh_state(me.draw, state->draws[me.draw].state_key, state->draw_state[me.draw], t.x0, t.y0, t.scissor, &ms);
-		VgxRasterRect r;
-		if (ms.mode == VGX_RF_NOTHING || !vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, ms.rect, &r)) { continue; }
-		const uint16_t* ip = frame->idx + me.first_index;
-		const float* pp = frame->pos + 2 * me.first_vertex;
-		const uint32_t* cp = frame->color + me.first_vertex;
-		for (uint32_t k = 0; k < me.num_indices / 3u; ++k) {
-			const uint32_t i0 = ip[3 * k], i1 = ip[3 * k + 1], i2 = ip[3 * k + 2];
-			if (i0 >= me.num_vertices || i1 >= me.num_vertices || i2 >= me.num_vertices) { continue; }
-			VgxRasterTri T;
-			if (!vgx_raster_setup(v2(pp[2 * i0], pp[2 * i0 + 1]), v2(pp[2 * i1], pp[2 * i1 + 1]), v2(pp[2 * i2], pp[2 * i2 + 1]), cp[i0], cp[i1], cp[i2], &T)) { continue; }
-			uint32_t a0, a1, b0, b1;
-			if (!vgx_raster_span(T.minx, T.maxx, t.x0, ms.rect[0], ms.rect[2], &a0, &a1) || !vgx_raster_span(T.miny, T.maxy, t.y0, ms.rect[1], ms.rect[3], &b0, &b1)) { continue; }
-			for (uint32_t j = b0; j <= b1; ++j) {
-				for (uint32_t i = a0; i <= a1; ++i) {
-					uint32_t* const p = t.pixels + (uint64_t)j * t.stride + i;
-					const uint32_t d = vgx_raster_frame_pixel(T, ms.mode, ms.f, ms.n, (double)(t.x0 + (int32_t)i) + 0.5, (double)(t.y0 + (int32_t)j) + 0.5,
-					                                          stamp + (size_t)j * t.width + i, *p);
-					if (d != *p) { *p = d; }
-				}
-			}
-		}
-	}
-	free(stamp);
-	free(own);
-	return VGX_OK;
 }
 
-// vgx_raster_textured on the host: vgxt_raster_frame's loop with the sampling functions of vgx_raster.h for the sampled meshes. HOST
-// pointers throughout, the images' pixels and the UV stream included.
-int vgxt_raster_textured(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
-                         const vgx_raster_textures* tex, const vgx_raster_target* target, uint32_t* status)
+// The frame-level calls on the host: vgxt_raster's loop with the per-draw state of vgx_raster.h, a stamp image of its own and, as far as
+// the level (VGX_RL_*) goes, the sampling and the paint functions. HOST pointers throughout, the images' pixels, the UV stream and the
+// paint tables included. The meshes are looked at twice: first for an invalid one (nothing may be written then), then drawn.
+static int raster_frame_loop(int level, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                             const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status)
 {
-	if (!frame || !target || !state || !tex) { return VGX_E_INVALID_ARG; }
-	if ((tex->uv_bytes != 4u && tex->uv_bytes != 8u) || (tex->num_images && !tex->images) || ((uintptr_t)tex->images & 7u)) { return VGX_E_INVALID_ARG; }
-	{
-		const uint64_t e = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
-		if (mesh_begin < e && (!tex->uv || ((uintptr_t)tex->uv & (tex->uv_bytes - 1u)))) { return VGX_E_INVALID_ARG; }
-	}
-	if (state->reserved != 0u || (state->num_draws && (!state->draws || !state->draw_state))) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)state->draws & 3u) || ((uintptr_t)state->draw_state & 3u)) { return VGX_E_INVALID_ARG; }
+	const int rc = vgx_raster_check_args(level, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, status);
+	if (rc != VGX_OK) { return rc; }
 	const vgx_raster_target& t = *target;
-	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
-	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
-	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
-		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
-		return VGX_E_INVALID_ARG;
-	}
-	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
-	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
-	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
 	if (status) { *status = VGX_OK; }
-	if (empty) { return VGX_OK; }
+	if (t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3]) { return VGX_OK; }
+	// the tables of the level: the others are not there
+	const vgx_raster_image* const images = level >= VGX_RL_TEXTURED ? tex->images : nullptr;
+	const uint32_t numImages = level >= VGX_RL_TEXTURED ? tex->num_images : 0u;
+	const vgx_paint* const gradients = level >= VGX_RL_PAINTED ? paints->gradients : nullptr;
+	const vgx_paint* const patterns = level >= VGX_RL_PAINTED ? paints->patterns : nullptr;
+	const uint32_t numGradients = level >= VGX_RL_PAINTED ? paints->num_gradients : 0u, numPatterns = level >= VGX_RL_PAINTED ? paints->num_patterns : 0u;
 	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
 	for (uint64_t m = mesh_begin; m < end; ++m) {
 		const vgx_mesh me = frame->meshes[m];
 		VgxRasterMeshState ms;
 		ms.mode = VGX_RF_INVALID;
 		if (me.draw < state->num_draws) {
-			vgx_raster_textured_mesh_state(me, state->draws[me.draw].state_key, state->draw_state[me.draw], t.x0, t.y0, t.scissor, tex->images, tex->num_images, &ms);
+			vgx_raster_mesh_state(level, me, state->draws[me.draw].state_key, state->draw_state[me.draw], t.x0, t.y0, t.scissor, images, numImages,
+			                      gradients, numGradients, patterns, numPatterns, &ms);
 		}
 		if (ms.mode == VGX_RF_INVALID) {
 			if (status) { *status = VGX_E_INVALID_ARG; }
@@ -726,115 +638,17 @@ int vgxt_raster_textured(const vgx_cache_desc* frame, const float* mesh_bounds, 
 	for (uint64_t m = mesh_begin; m < end; ++m) {
 		const vgx_mesh me = frame->meshes[m];
 		VgxRasterMeshState ms;
-		vgx_raster_textured_mesh_state(me, state->draws[me.draw].state_key, state->draw_state[me.draw], t.x0, t.y0, t.scissor, tex->images, tex->num_images, &ms);
+		vgx_raster_mesh_state(level, me, state->draws[me.draw].state_key, state->draw_state[me.draw], t.x0, t.y0, t.scissor, images, numImages,
+		                      gradients, numGradients, patterns, numPatterns, &ms);
 		const bool sampled = (ms.pad & VGX_RT_SAMPLED) != 0u;
-		const vgx_raster_image im = sampled ? tex->images[ms.pad & 0xFFFFu] : vgx_raster_image();
-		const auto fetch = [&im](uint32_t x, uint32_t y) { return im.pixels[(uint64_t)y * im.stride + x]; };
-		VgxRasterRect r;
-		if (ms.mode == VGX_RF_NOTHING || !vgx_raster_any_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, ms.rect, &r)) { continue; }
-		const uint16_t* ip = frame->idx + me.first_index;
-		const float* pp = frame->pos + 2 * me.first_vertex;
-		const uint32_t* cp = frame->color + me.first_vertex;
-		for (uint32_t k = 0; k < me.num_indices / 3u; ++k) {
-			const uint32_t i0 = ip[3 * k], i1 = ip[3 * k + 1], i2 = ip[3 * k + 2];
-			if (i0 >= me.num_vertices || i1 >= me.num_vertices || i2 >= me.num_vertices) { continue; }
-			VgxRasterTri T;
-			if (!vgx_raster_setup(v2(pp[2 * i0], pp[2 * i0 + 1]), v2(pp[2 * i1], pp[2 * i1 + 1]), v2(pp[2 * i2], pp[2 * i2 + 1]), cp[i0], cp[i1], cp[i2], &T)) { continue; }
-			double uv[6];
-			if (sampled) {
-				vgx_raster_uv_widen(tex->uv, tex->uv_bytes, me.first_vertex + i0, uv);
-				vgx_raster_uv_widen(tex->uv, tex->uv_bytes, me.first_vertex + i1, uv + 2);
-				vgx_raster_uv_widen(tex->uv, tex->uv_bytes, me.first_vertex + i2, uv + 4);
-			}
-			uint32_t a0, a1, b0, b1;
-			if (!vgx_raster_span(T.minx, T.maxx, t.x0, ms.rect[0], ms.rect[2], &a0, &a1) || !vgx_raster_span(T.miny, T.maxy, t.y0, ms.rect[1], ms.rect[3], &b0, &b1)) { continue; }
-			for (uint32_t j = b0; j <= b1; ++j) {
-				for (uint32_t i = a0; i <= a1; ++i) {
-					uint32_t* const p = t.pixels + (uint64_t)j * t.stride + i;
-					const double px = (double)(t.x0 + (int32_t)i) + 0.5, py = (double)(t.y0 + (int32_t)j) + 0.5;
-					uint32_t* const sp = stamp + (size_t)j * t.width + i;
-					const uint32_t d = sampled ? vgx_raster_textured_pixel(T, uv, im, ms.mode, ms.f, ms.n, px, py, *sp, *p, fetch)
-					                           : vgx_raster_frame_pixel(T, ms.mode, ms.f, ms.n, px, py, sp, *p);
-					if (d != *p) { *p = d; }
-				}
-			}
-		}
-	}
-	free(stamp);
-	free(own);
-	return VGX_OK;
-}
-
-// vgx_raster_painted on the host: vgxt_raster_textured's loop with the paint functions of vgx_raster.h for the meshes of gradient and
-// image-pattern draws. HOST pointers throughout, the paint tables included.
-int vgxt_raster_painted(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
-                        const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status)
-{
-	if (!frame || !target || !state || !tex || !paints) { return VGX_E_INVALID_ARG; }
-	if ((paints->num_gradients && !paints->gradients) || (paints->num_patterns && !paints->patterns)) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)paints->gradients & 3u) || ((uintptr_t)paints->patterns & 3u)) { return VGX_E_INVALID_ARG; }
-	if ((tex->uv_bytes != 4u && tex->uv_bytes != 8u) || (tex->num_images && !tex->images) || ((uintptr_t)tex->images & 7u)) { return VGX_E_INVALID_ARG; }
-	{
-		const uint64_t e = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
-		if (mesh_begin < e && (!tex->uv || ((uintptr_t)tex->uv & (tex->uv_bytes - 1u)))) { return VGX_E_INVALID_ARG; }
-	}
-	if (state->reserved != 0u || (state->num_draws && (!state->draws || !state->draw_state))) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)state->draws & 3u) || ((uintptr_t)state->draw_state & 3u)) { return VGX_E_INVALID_ARG; }
-	const vgx_raster_target& t = *target;
-	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
-	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
-	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
-		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
-		return VGX_E_INVALID_ARG;
-	}
-	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
-	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
-	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
-	if (status) { *status = VGX_OK; }
-	if (empty) { return VGX_OK; }
-	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
-	for (uint64_t m = mesh_begin; m < end; ++m) {
-		const vgx_mesh me = frame->meshes[m];
-		VgxRasterMeshState ms;
-		ms.mode = VGX_RF_INVALID;
-		if (me.draw < state->num_draws) {
-			vgx_raster_painted_mesh_state(me, state->draws[me.draw].state_key, state->draw_state[me.draw], t.x0, t.y0, t.scissor, tex->images, tex->num_images,
-			                              paints->gradients, paints->num_gradients, paints->patterns, paints->num_patterns, &ms);
-		}
-		if (ms.mode == VGX_RF_INVALID) {
-			if (status) { *status = VGX_E_INVALID_ARG; }
-			return VGX_OK;
-		}
-	}
-	float* own = nullptr;
-	if (!mesh_bounds && mesh_begin < end) {
-		own = (float*)malloc(frame->num_meshes * 4 * sizeof(float));
-		if (!own) { return VGX_E_INTERNAL; }
-		vgxt_mesh_bounds(frame->pos, frame->meshes, frame->num_meshes, own);
-	}
-	uint32_t* stamp = (uint32_t*)malloc((size_t)t.width * t.height * sizeof(uint32_t));
-	if (!stamp) { free(own); return VGX_E_INTERNAL; }
-	for (size_t k = 0; k < (size_t)t.width * t.height; ++k) { stamp[k] = VGX_RASTER_STAMP_NONE; }
-	if (t.flags & VGX_RASTER_CLEAR) {
-		for (uint32_t j = t.scissor[1]; j < t.scissor[3]; ++j) {
-			for (uint32_t i = t.scissor[0]; i < t.scissor[2]; ++i) { t.pixels[(uint64_t)j * t.stride + i] = t.clear_color; }
-		}
-	}
-	for (uint64_t m = mesh_begin; m < end; ++m) {
-		const vgx_mesh me = frame->meshes[m];
-		VgxRasterMeshState ms;
-		vgx_raster_painted_mesh_state(me, state->draws[me.draw].state_key, state->draw_state[me.draw], t.x0, t.y0, t.scissor, tex->images, tex->num_images,
-			                              paints->gradients, paints->num_gradients, paints->patterns, paints->num_patterns, &ms);
-		const bool sampled = (ms.pad & VGX_RT_SAMPLED) != 0u;
-		const vgx_raster_image im = sampled ? tex->images[ms.pad & 0xFFFFu] : vgx_raster_image();
+		const vgx_raster_image im = sampled ? images[ms.pad & 0xFFFFu] : vgx_raster_image();
 		const auto fetch = [&im](uint32_t x, uint32_t y) { return im.pixels[(uint64_t)y * im.stride + x]; };
 		VgxRasterPaint pr;
 		memset(&pr, 0, sizeof(pr));
-		if (ms.pad & VGX_RT_PAINTED) { vgx_raster_paint_record(((ms.pad & VGX_RT_GRADIENT) ? paints->gradients : paints->patterns)[ms.pad & 0xFFFFu], tex->images, &pr); }
+		if (ms.pad & VGX_RT_PAINTED) { vgx_raster_paint_record(((ms.pad & VGX_RT_GRADIENT) ? gradients : patterns)[ms.pad & 0xFFFFu], images, &pr); }
 		const auto pfetch = [&pr](uint32_t x, uint32_t y) { return pr.im.pixels[(uint64_t)y * pr.im.stride + x]; };
 		VgxRasterRect r;
-		if (ms.mode == VGX_RF_NOTHING || !vgx_raster_any_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, ms.rect, &r)) { continue; }
+		if (ms.mode == VGX_RF_NOTHING || !vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, ms.rect, level == VGX_RL_FRAME, &r)) { continue; }
 		const uint16_t* ip = frame->idx + me.first_index;
 		const float* pp = frame->pos + 2 * me.first_vertex;
 		const uint32_t* cp = frame->color + me.first_vertex;
@@ -868,6 +682,26 @@ int vgxt_raster_painted(const vgx_cache_desc* frame, const float* mesh_bounds, u
 	free(stamp);
 	free(own);
 	return VGX_OK;
+}
+
+extern "C" {
+
+int vgxt_raster_frame(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                      const vgx_raster_target* target, uint32_t* status)
+{
+	return raster_frame_loop(VGX_RL_FRAME, frame, mesh_bounds, mesh_begin, mesh_end, state, nullptr, nullptr, target, status);
+}
+
+int vgxt_raster_textured(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                         const vgx_raster_textures* tex, const vgx_raster_target* target, uint32_t* status)
+{
+	return raster_frame_loop(VGX_RL_TEXTURED, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, nullptr, target, status);
+}
+
+int vgxt_raster_painted(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                        const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status)
+{
+	return raster_frame_loop(VGX_RL_PAINTED, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, status);
 }
 
 // the pieces of the paint rule, for the tests: t of a gradient at a paint coordinate, an end's channel as 8 bits, the square root

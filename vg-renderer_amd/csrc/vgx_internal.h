@@ -473,38 +473,27 @@ struct VgxRasterArgs
 size_t vgx_raster_sort_bytes(uint64_t n, uint32_t bits); // temporary storage the sort of n entries wants; 0: the query failed
 hipError_t vgx_launch_raster(const VgxRasterArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
 
-// ... with per-draw scissors and clip regions (vgx_raster_frame): the same arguments and tables, the draw state, and per mesh of the
-// range what k_rasterf_count made of it (vgx_raster.h)
+// ... of the frame-level calls (vgx_raster_frame, vgx_raster_textured, vgx_raster_painted): the same arguments and tables, the level
+// (VGX_RL_*, vgx_raster.h), the draw state, per mesh of the range what k_rasterf_count made of it, and what the wider levels read
 struct VgxRasterMeshState;
 struct VgxRasterFrameArgs
 {
 	VgxRasterArgs R;
-	const vgx_draw* draws; const vgx_draw_state* draw_state; // [num_draws], checked by the host
+	int32_t level;                    // VGX_RL_FRAME, VGX_RL_TEXTURED or VGX_RL_PAINTED
 	uint32_t num_draws;
+	const vgx_draw* draws; const vgx_draw_state* draw_state; // [num_draws], checked by the host
 	VgxRasterMeshState* mesh_state;   // [nrange] (context scratch)
-};
-hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
-
-// ... with text and user meshes sampled from images (vgx_raster_textured): the same again, the UV stream and the image table
-struct VgxRasterTexArgs
-{
-	VgxRasterFrameArgs F;
+	// from VGX_RL_TEXTURED on, else zero
 	const void* uv;                   // [num_vertices][uv_bytes], checked by the host; read for the vertices of sampled meshes only
-	const vgx_raster_image* images;   // [num_images]; a record is read (and checked, by k_rastert_count) only when a sampled mesh names it
+	const vgx_raster_image* images;   // [num_images]; a record is read (and checked, by k_rasterf_count) only when a mesh names it
 	uint32_t uv_bytes, num_images;
 	uint32_t* tile_tex;               // [(sentinel + 31) / 32] one bit per tile of the image, zero at the launch: a sampled mesh has an entry there (context scratch)
-};
-hipError_t vgx_launch_raster_textured(const VgxRasterTexArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
-
-// ... with gradient and image-pattern paints (vgx_raster_painted): the same again and the two paint tables
-struct VgxRasterPaintArgs
-{
-	VgxRasterTexArgs X;
-	const vgx_paint* gradients;       // [num_gradients]; an entry is read (and checked, by k_rasterp_count) only when a painted mesh names it
+	// at VGX_RL_PAINTED, else zero
+	const vgx_paint* gradients;       // [num_gradients]; an entry is read (and checked, by k_rasterf_count) only when a painted mesh names it
 	const vgx_paint* patterns;        // [num_patterns]
 	uint32_t num_gradients, num_patterns;
 	uint32_t* tile_paint;             // [(sentinel + 31) / 32] as tile_tex: a painted mesh has an entry there (context scratch)
 };
-hipError_t vgx_launch_raster_painted(const VgxRasterPaintArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
+hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
 
 #endif

@@ -146,29 +146,42 @@ VGX_HD bool vgx_raster_span(float lo, float hi, int32_t origin, uint32_t c0, uin
 	return true;
 }
 
-VGX_HD bool vgx_raster_kind_drawn(uint32_t subpathKind)
+// the kinds that carry UVs: vgx_raster and vgx_raster_frame skip them, the wider calls draw them
+VGX_HD bool vgx_raster_kind_has_uv(uint32_t subpathKind)
 {
 	const uint32_t k = subpathKind >> 28;
-	return k != VGX_MESH_TEXT && k != VGX_MESH_TRILIST;
+	return k == VGX_MESH_TEXT || k == VGX_MESH_TRILIST;
 }
 
-// Bin entries of a mesh: the tiles its box can reach inside the scissor (a rectangle of tiles)
+// Bin entries of a mesh: the tiles its box can reach inside the scissor (a rectangle of tiles). skipUvKinds: a mesh of kind TEXT /
+// TRILIST has none
 struct VgxRasterRect { uint32_t tx0, ty0, tx1, ty1; }; // inclusive
-VGX_HD bool vgx_raster_mesh_tiles(const vgx_mesh& me, const float* box, int32_t x0, int32_t y0, const uint32_t* scissor, VgxRasterRect* r)
+VGX_HD bool vgx_raster_mesh_tiles(const vgx_mesh& me, const float* box, int32_t x0, int32_t y0, const uint32_t* scissor, bool skipUvKinds, VgxRasterRect* r)
 {
-	if (!vgx_raster_kind_drawn(me.subpath_kind) || me.num_indices < 3u) { return false; }
+	if ((skipUvKinds && vgx_raster_kind_has_uv(me.subpath_kind)) || me.num_indices < 3u) { return false; }
 	uint32_t i0, i1, j0, j1;
 	if (!vgx_raster_span(box[0], box[2], x0, scissor[0], scissor[2], &i0, &i1) || !vgx_raster_span(box[1], box[3], y0, scissor[1], scissor[3], &j0, &j1)) { return false; }
 	r->tx0 = i0 / VGX_RASTER_TILE; r->tx1 = i1 / VGX_RASTER_TILE; r->ty0 = j0 / VGX_RASTER_TILE; r->ty1 = j1 / VGX_RASTER_TILE;
 	return true;
 }
 
-// ---- vgx_raster_frame: per-draw scissors and clip regions (include/vgx.h) -------------------------------------------------
+// ---- the frame-level calls: vgx_raster_frame < vgx_raster_textured < vgx_raster_painted (include/vgx.h) --------------------------
+// One loop on the host and one kernel family on the device serve the three; what differs is the level: which kinds are drawn, which
+// meshes are sampled or painted, and which tables are read (vgx_raster_mesh_state below). VGX_RL_PLAIN is vgx_raster, for the
+// argument check alone
+enum { VGX_RL_PLAIN = 0, VGX_RL_FRAME = 1, VGX_RL_TEXTURED = 2, VGX_RL_PAINTED = 3 };
+
+// ---- per-draw scissors and clip regions (every level) ---------------------------------------------------------------------------
 #define VGX_RASTER_STAMP_NONE 0xFFFFFFFFu // S of a pixel no clip mesh has touched; clip_first_draw of a draw without a region
 // what a mesh does with the stamp
 enum { VGX_RF_PLAIN = 0, VGX_RF_IN = 1, VGX_RF_OUT = 2, VGX_RF_STAMP = 3, VGX_RF_NOTHING = 4, VGX_RF_INVALID = 5 };
-// Per mesh of the range (context scratch of vgx_raster_frame only). rect = the target's scissor cut by the draw's, in image pixels,
-// half open; f, n = the region of a tested mesh, f = the mesh's draw for VGX_RF_STAMP
+// what a mesh is drawn with, beside the handle (bits 0 .. 15) in VgxRasterMeshState::pad and beside slot and mode in a tile record
+#define VGX_RT_SAMPLED  0x10000u // kind TEXT / TRILIST under a draw of type 0: the handle names an image
+#define VGX_RT_GRADIENT 0x20000u // a draw of type 1: the handle names a gradient
+#define VGX_RT_PATTERN  0x40000u // a draw of type 2: the handle names a pattern
+#define VGX_RT_PAINTED  (VGX_RT_GRADIENT | VGX_RT_PATTERN)
+// Per mesh of the range (context scratch of the frame-level calls only). rect = the target's scissor cut by the draw's, in image
+// pixels, half open; f, n = the region of a tested mesh, f = the mesh's draw for VGX_RF_STAMP
 struct VgxRasterMeshState { uint32_t mode, f, n, pad; uint32_t rect[4]; }; // 32 bytes
 
 VGX_HD uint32_t vgx_raster_draw_type(uint32_t stateKey) { return (stateKey >> 16) & 0xFu; } // 3 = Clip
@@ -189,22 +202,6 @@ VGX_HD bool vgx_raster_stamp_pass(uint32_t S, uint32_t f, uint32_t n, uint32_t r
 	return (S != VGX_RASTER_STAMP_NONE && S >= f && S - f < n) == (rule == 0u);
 }
 
-// The state of mesh `me` under its draw (d < num_draws is the caller's check)
-VGX_HD void vgx_raster_mesh_state(uint32_t d, uint32_t stateKey, const vgx_draw_state& ds, int32_t x0, int32_t y0, const uint32_t* scissor, VgxRasterMeshState* st)
-{
-	st->pad = 0u; st->f = 0u; st->n = 0u;
-	if (!vgx_raster_draw_span(ds.scissor[0], ds.scissor[2], x0, scissor[0], scissor[2], &st->rect[0], &st->rect[2])
-	 || !vgx_raster_draw_span(ds.scissor[1], ds.scissor[3], y0, scissor[1], scissor[3], &st->rect[1], &st->rect[3])) {
-		st->rect[0] = st->rect[1] = st->rect[2] = st->rect[3] = 0u;
-		st->mode = VGX_RF_NOTHING;
-		return;
-	}
-	if (vgx_raster_draw_type(stateKey) == 3u) { st->mode = VGX_RF_STAMP; st->f = d; return; }
-	if (ds.clip_first_draw == VGX_RASTER_STAMP_NONE || ds.clip_num_draws == 0u) { st->mode = VGX_RF_PLAIN; return; }
-	st->mode = ds.clip_rule == 0u ? VGX_RF_IN : VGX_RF_OUT;
-	st->f = ds.clip_first_draw; st->n = ds.clip_num_draws;
-}
-
 // The triangle of a mesh of state (mode, f, n) on the pixel whose sample is (px, py) and lies inside the mesh's rect: the pixel's
 // new value; *S is the pixel's stamp
 VGX_HD uint32_t vgx_raster_frame_pixel(const VgxRasterTri& T, uint32_t mode, uint32_t f, uint32_t n, double px, double py, uint32_t* S, uint32_t dst)
@@ -218,42 +215,14 @@ VGX_HD uint32_t vgx_raster_frame_pixel(const VgxRasterTri& T, uint32_t mode, uin
 	return vgx_raster_pixel(T, px, py, dst);
 }
 
-// ---- vgx_raster_textured: text and user meshes sampled from an RGBA8 image (include/vgx.h) ------------------------------------
+// ---- from the textured level on: text and user meshes sampled from an RGBA8 image (include/vgx.h) --------------------------------
 // Every kind is drawn; a mesh of kind TEXT / TRILIST under a draw of type 0 is sampled, the image = the low 16 bits of the state key
-#define VGX_RT_SAMPLED 0x10000u // in VgxRasterMeshState::pad beside the handle (bits 0 .. 15)
-VGX_HD bool vgx_raster_kind_has_uv(uint32_t subpathKind)
-{
-	const uint32_t k = subpathKind >> 28;
-	return k == VGX_MESH_TEXT || k == VGX_MESH_TRILIST;
-}
 VGX_HD bool vgx_raster_mesh_sampled(uint32_t subpathKind, uint32_t stateKey) { return vgx_raster_kind_has_uv(subpathKind) && vgx_raster_draw_type(stateKey) == 0u; }
-
-// vgx_raster_mesh_tiles without the test of the kind
-VGX_HD bool vgx_raster_any_mesh_tiles(const vgx_mesh& me, const float* box, int32_t x0, int32_t y0, const uint32_t* scissor, VgxRasterRect* r)
-{
-	if (me.num_indices < 3u) { return false; }
-	uint32_t i0, i1, j0, j1;
-	if (!vgx_raster_span(box[0], box[2], x0, scissor[0], scissor[2], &i0, &i1) || !vgx_raster_span(box[1], box[3], y0, scissor[1], scissor[3], &j0, &j1)) { return false; }
-	r->tx0 = i0 / VGX_RASTER_TILE; r->tx1 = i1 / VGX_RASTER_TILE; r->ty0 = j0 / VGX_RASTER_TILE; r->ty1 = j1 / VGX_RASTER_TILE;
-	return true;
-}
 
 VGX_HD bool vgx_raster_image_valid(const vgx_raster_image& im)
 {
 	return im.pixels != nullptr && ((uintptr_t)im.pixels & 3u) == 0u && im.width >= 1u && im.width <= 16384u && im.height >= 1u && im.height <= 16384u
 	    && im.stride >= im.width;
-}
-
-// The state of a mesh under vgx_raster_textured: vgx_raster_mesh_state, and for a sampled mesh the handle in `pad`, or
-// VGX_RF_INVALID when the handle or its image record is no good. `images` is only read for a sampled mesh
-VGX_HD void vgx_raster_textured_mesh_state(const vgx_mesh& me, uint32_t stateKey, const vgx_draw_state& ds, int32_t x0, int32_t y0, const uint32_t* scissor,
-                                           const vgx_raster_image* images, uint32_t numImages, VgxRasterMeshState* st)
-{
-	vgx_raster_mesh_state(me.draw, stateKey, ds, x0, y0, scissor, st);
-	if (!vgx_raster_mesh_sampled(me.subpath_kind, stateKey)) { return; }
-	const uint32_t handle = stateKey & 0xFFFFu;
-	if (handle >= numImages || !vgx_raster_image_valid(images[handle])) { st->mode = VGX_RF_INVALID; return; }
-	st->pad = VGX_RT_SAMPLED | handle;
 }
 
 // the UV of vertex v of the stream as two binary64 values: binary32 widened, or int16 / 32767
@@ -338,12 +307,9 @@ VGX_HD uint32_t vgx_raster_textured_pixel(const VgxRasterTri& T, const double* u
 	                        vgx_raster_div255(vgx_raster_channel(T, 2, E, sum) * ((tc >> 16) & 255u)), a);
 }
 
-// ---- vgx_raster_painted: gradient and image-pattern paints (include/vgx.h) --------------------------------------------------------
+// ---- at the painted level: gradient and image-pattern paints (include/vgx.h) ------------------------------------------------------
 // A mesh whose draw has type 1 (ColorGradient) or 2 (ImagePattern) is painted, whatever its kind: the handle in the low 16 bits of the
-// state key indexes the table of that type. Beside VGX_RT_SAMPLED in VgxRasterMeshState::pad
-#define VGX_RT_GRADIENT 0x20000u
-#define VGX_RT_PATTERN  0x40000u
-#define VGX_RT_PAINTED  (VGX_RT_GRADIENT | VGX_RT_PATTERN)
+// state key indexes the table of that type
 VGX_HD uint32_t vgx_raster_mesh_painted(uint32_t stateKey)
 {
 	const uint32_t type = vgx_raster_draw_type(stateKey);
@@ -454,16 +420,36 @@ VGX_HD uint32_t vgx_raster_pattern_pixel(const VgxRasterTri& T, const VgxRasterP
 	                        vgx_raster_div255(vgx_raster_channel(T, 2, E, sum) * ((tc >> 16) & 255u)), a);
 }
 
-// The state of a mesh under vgx_raster_painted: vgx_raster_textured_mesh_state, and for a painted mesh the table and the handle in
-// `pad`, or VGX_RF_INVALID when the handle, the entry or a pattern's image is no good. The tables are only read for a painted mesh
-VGX_HD void vgx_raster_painted_mesh_state(const vgx_mesh& me, uint32_t stateKey, const vgx_draw_state& ds, int32_t x0, int32_t y0, const uint32_t* scissor,
-                                          const vgx_raster_image* images, uint32_t numImages, const vgx_paint* gradients, uint32_t numGradients,
-                                          const vgx_paint* patterns, uint32_t numPatterns, VgxRasterMeshState* st)
+// ---- what a mesh does at a level -----------------------------------------------------------------------------------------------------
+// The state of mesh `me` under its draw (me.draw < num_draws is the caller's check, at every level and whatever the kind). Every level:
+// mode, region and rectangle. From VGX_RL_TEXTURED on a sampled mesh leaves VGX_RT_SAMPLED and its handle in `pad`; at VGX_RL_PAINTED
+// a painted mesh leaves its table and handle there. VGX_RF_INVALID: the handle, the record it names or a pattern's image is no good.
+// A table is read only at a level that uses it, and only the record a mesh names; below that level it may be null
+VGX_HD void vgx_raster_mesh_state(int level, const vgx_mesh& me, uint32_t stateKey, const vgx_draw_state& ds, int32_t x0, int32_t y0, const uint32_t* scissor,
+                                  const vgx_raster_image* images, uint32_t numImages, const vgx_paint* gradients, uint32_t numGradients,
+                                  const vgx_paint* patterns, uint32_t numPatterns, VgxRasterMeshState* st)
 {
-	vgx_raster_textured_mesh_state(me, stateKey, ds, x0, y0, scissor, images, numImages, st);
-	const uint32_t painted = vgx_raster_mesh_painted(stateKey);
-	if (!painted) { return; }
+	st->pad = 0u; st->f = 0u; st->n = 0u;
+	if (!vgx_raster_draw_span(ds.scissor[0], ds.scissor[2], x0, scissor[0], scissor[2], &st->rect[0], &st->rect[2])
+	 || !vgx_raster_draw_span(ds.scissor[1], ds.scissor[3], y0, scissor[1], scissor[3], &st->rect[1], &st->rect[3])) {
+		st->rect[0] = st->rect[1] = st->rect[2] = st->rect[3] = 0u;
+		st->mode = VGX_RF_NOTHING;
+	} else if (vgx_raster_draw_type(stateKey) == 3u) {
+		st->mode = VGX_RF_STAMP; st->f = me.draw;
+	} else if (ds.clip_first_draw == VGX_RASTER_STAMP_NONE || ds.clip_num_draws == 0u) {
+		st->mode = VGX_RF_PLAIN;
+	} else {
+		st->mode = ds.clip_rule == 0u ? VGX_RF_IN : VGX_RF_OUT;
+		st->f = ds.clip_first_draw; st->n = ds.clip_num_draws;
+	}
 	const uint32_t handle = stateKey & 0xFFFFu;
+	if (level >= VGX_RL_TEXTURED && vgx_raster_mesh_sampled(me.subpath_kind, stateKey)) { // a draw of type 0: not painted
+		if (handle >= numImages || !vgx_raster_image_valid(images[handle])) { st->mode = VGX_RF_INVALID; return; }
+		st->pad = VGX_RT_SAMPLED | handle;
+		return;
+	}
+	const uint32_t painted = level >= VGX_RL_PAINTED ? vgx_raster_mesh_painted(stateKey) : 0u;
+	if (!painted) { return; }
 	const bool grad = painted == VGX_RT_GRADIENT;
 	if (handle >= (grad ? numGradients : numPatterns)) { st->mode = VGX_RF_INVALID; return; }
 	const vgx_paint* const p = (grad ? gradients : patterns) + handle;
@@ -473,6 +459,42 @@ VGX_HD void vgx_raster_painted_mesh_state(const vgx_mesh& me, uint32_t stateKey,
 		if (im >= numImages || !vgx_raster_image_valid(images[im])) { st->mode = VGX_RF_INVALID; return; }
 	}
 	st->pad = painted | handle;
+}
+
+// ---- the arguments of the four calls (host only) ---------------------------------------------------------------------------------
+// What vgx_raster (VGX_RL_PLAIN: state, tex and paints are not looked at), vgx_raster_frame, vgx_raster_textured and vgx_raster_painted
+// refuse before anything runs, for the device calls and for the vgxt_* host loops alike: VGX_OK, VGX_E_INVALID_ARG or VGX_E_RANGE.
+// `status` is where the call leaves its status (may be null). The first failing check of this order decides
+static inline int vgx_raster_check_args(int level, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
+                                        const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints,
+                                        const vgx_raster_target* target, const uint32_t* status)
+{
+	if (!frame || !target || (level >= VGX_RL_FRAME && !state) || (level >= VGX_RL_TEXTURED && !tex) || (level >= VGX_RL_PAINTED && !paints)) { return VGX_E_INVALID_ARG; }
+	if (level >= VGX_RL_PAINTED) {
+		if ((paints->num_gradients && !paints->gradients) || (paints->num_patterns && !paints->patterns)) { return VGX_E_INVALID_ARG; }
+		if (((uintptr_t)paints->gradients & 3u) || ((uintptr_t)paints->patterns & 3u)) { return VGX_E_INVALID_ARG; }
+	}
+	if (level >= VGX_RL_TEXTURED) {
+		if ((tex->uv_bytes != 4u && tex->uv_bytes != 8u) || (tex->num_images && !tex->images) || ((uintptr_t)tex->images & 7u)) { return VGX_E_INVALID_ARG; }
+		const uint64_t e = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
+		if (mesh_begin < e && (!tex->uv || ((uintptr_t)tex->uv & (tex->uv_bytes - 1u)))) { return VGX_E_INVALID_ARG; }
+	}
+	if (level >= VGX_RL_FRAME) {
+		if (state->reserved != 0u || (state->num_draws && (!state->draws || !state->draw_state))) { return VGX_E_INVALID_ARG; }
+		if (((uintptr_t)state->draws & 3u) || ((uintptr_t)state->draw_state & 3u)) { return VGX_E_INVALID_ARG; }
+	}
+	const vgx_raster_target& t = *target;
+	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
+	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
+	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
+		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
+	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
+	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	return VGX_OK;
 }
 
 #endif

@@ -1,4 +1,7 @@
-// vgx_raster.hip -- a frame's mesh streams to an RGBA8 image on gfx950 (include/vgx.h: vgx_raster; the arithmetic: vgx_raster.h).
+// vgx_raster.hip -- a frame's mesh streams to an RGBA8 image on gfx950 (include/vgx.h: vgx_raster, vgx_raster_frame, vgx_raster_textured,
+// vgx_raster_painted; the arithmetic: vgx_raster.h). Two kernel families and one launch sequence (count, scan, entries, sort, tiles):
+// the plain family (k_raster_*) serves vgx_raster and carries no draw state, which measurably keeps it the faster one; the frame family
+// (k_rasterf_*, further down) serves the three frame-level calls, which differ in a level carried in the arguments.
 //
 // Blending is not commutative: a pixel must see its triangles in ascending (mesh, triangle) order, and no atomic on a pixel gives
 // that. So a pixel belongs to ONE lane for the whole call: the image is cut into tiles of 16 x 16 pixels, a tile is one workgroup of
@@ -33,7 +36,7 @@ __device__ __forceinline__ bool raster_rect(const VgxRasterArgs& A, uint64_t k, 
 	const uint64_t m = A.mesh_begin + k;
 	const float4 box = ((const float4*)A.mesh_bounds)[m];
 	const float b[4] = { box.x, box.y, box.z, box.w };
-	return vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, A.scissor, r);
+	return vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, A.scissor, true, r);
 }
 
 __global__ __launch_bounds__(256) void k_raster_count(VgxRasterArgs A)
@@ -169,15 +172,40 @@ __global__ __launch_bounds__(256) void k_raster_tiles(VgxRasterArgs A)
 	if (inside && (clear || d != before)) { *pixel = d; }
 }
 
-// ---- vgx_raster_frame: the same four steps with the state of every mesh's draw ------------------------------------------------
-//   k_rasterf_count    also decides what the mesh does (VgxRasterMeshState: stamp / test In / test Out / untested / nothing, its region,
-//                      the target's scissor cut by its draw's) and keeps that per mesh of the range; the tiles are those of the box
-//                      inside that rectangle. A draw index outside the table marks the mesh, the scan's third lane carries the mark
-//                      to finish(), which ends the call with VGX_E_INVALID_ARG before anything is written
-//   k_rasterf_tiles    k_raster_tiles with one more register per pixel, the stamp S, carried across all batches; the state of the
-//                      meshes in hand lies in LDS beside s_mesh (12 bytes: mode and the rectangle cut to the tile in one word, f, n),
-//                      a setup record names its mesh's slot there and carries the mode and the rectangle as row / column masks. A triangle is tested against the tile cut by BOTH scissors, so
-//                      what a cut draw cannot write never reaches the pixel loop; clip triangles take the same ordered compaction
+// ---- the frame family: vgx_raster_frame, vgx_raster_textured, vgx_raster_painted -----------------------------------------------------
+// The same steps with the state of every mesh's draw; VgxRasterFrameArgs::level says which of the three calls runs.
+//   k_rasterf_count    also decides what the mesh does (vgx_raster_mesh_state: stamp / test In / test Out / untested / nothing, its
+//                      region, the target's scissor cut by its draw's; from the textured level on "sampled", at the painted level
+//                      "gradient" / "pattern", with the handle, in the state's pad word) and keeps that per mesh of the range; the tiles
+//                      are those of the box inside that rectangle. A draw index outside the table -- checked first, whatever the kind
+//                      -- or a handle, image or paint record that is no good marks the mesh; the scan's third lane carries the mark to
+//                      finish(), which ends the call with VGX_E_INVALID_ARG before anything is written. At the frame level a mesh of
+//                      kind TEXT / TRILIST gets no entries
+//   k_rasterf_entries  also marks, in one bit per tile of the image and class (tile_tex, tile_paint: zeroed by the host part before
+//                      the launches, null at a level that cannot set them), the tiles a sampled / a painted mesh has an entry in
+//   k_rasterf_tiles    <TEX, PAINT>: four instantiations over the same grid, of which a level launches those it can need (1, 2, 4); a
+//                      tile runs the one its two bits name, the others leave at once. <false, false> is k_raster_tiles with one more
+//                      register per pixel, the stamp S, carried across all batches; the state of the meshes in hand lies in LDS beside
+//                      s_mesh (12 bytes: mode and the rectangle cut to the tile in one word, f, n), a setup record names its mesh's slot
+//                      there and carries the mode and the rectangle as row / column masks. A triangle is tested against the tile cut by
+//                      BOTH scissors, so what a cut draw cannot write never reaches the pixel loop; clip triangles take the same ordered
+//                      compaction. TEX adds, per slot, the image record of a sampled mesh and, per setup record, the three UVs widened
+//                      to binary64 at setup (int16: the division by 32767 happens there). PAINT adds, per slot, a 48-byte paint record
+//                      (six matrix floats and either four params and the two ends packed to 8 bits, or the image record) built from the
+//                      96-byte table entry; with PAINT a sampled slot keeps its image in the same record, so TEX and PAINT together
+//                      need no second table. Slots are loaded once per batch of meshes by the lane that loads the slot. The pixel loop
+//                      reads slot and UVs from LDS -- one address for all lanes, a broadcast -- and nothing but texels from global
+//                      memory: 1 (nearest) or 4 (linear) independent loads. Every lane walks every record, so the loop stays
+//                      barrier-uniform. A frame without sampled or painted meshes pays one bit test per tile for a wide kernel, not
+//                      its LDS.
+__device__ __forceinline__ bool frame_rect(const VgxRasterFrameArgs& F, uint64_t m, const VgxRasterMeshState& st, VgxRasterRect* r)
+{
+	const VgxRasterArgs& A = F.R;
+	const float4 box = ((const float4*)A.mesh_bounds)[m];
+	const float b[4] = { box.x, box.y, box.z, box.w };
+	return vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, st.rect, F.level == VGX_RL_FRAME, r);
+}
+
 __global__ __launch_bounds__(256) void k_rasterf_count(VgxRasterFrameArgs F)
 {
 	const VgxRasterArgs& A = F.R;
@@ -191,11 +219,10 @@ __global__ __launch_bounds__(256) void k_rasterf_count(VgxRasterFrameArgs F)
 		st.mode = VGX_RF_INVALID; st.f = st.n = st.pad = 0u;
 		st.rect[0] = st.rect[1] = st.rect[2] = st.rect[3] = 0u;
 	} else {
-		vgx_raster_mesh_state(me.draw, F.draws[me.draw].state_key, F.draw_state[me.draw], A.x0, A.y0, A.scissor, &st);
-		const float4 box = ((const float4*)A.mesh_bounds)[m];
-		const float b[4] = { box.x, box.y, box.z, box.w };
+		vgx_raster_mesh_state(F.level, me, F.draws[me.draw].state_key, F.draw_state[me.draw], A.x0, A.y0, A.scissor, F.images, F.num_images,
+		                      F.gradients, F.num_gradients, F.patterns, F.num_patterns, &st);
 		VgxRasterRect r;
-		if (st.mode != VGX_RF_NOTHING && vgx_raster_mesh_tiles(me, b, A.x0, A.y0, st.rect, &r)) { entries = (r.tx1 - r.tx0 + 1u) * (r.ty1 - r.ty0 + 1u); }
+		if (st.mode != VGX_RF_NOTHING && st.mode != VGX_RF_INVALID && frame_rect(F, m, st, &r)) { entries = (r.tx1 - r.tx0 + 1u) * (r.ty1 - r.ty0 + 1u); }
 	}
 	F.mesh_state[k] = st;
 	A.mesh_entries[k] = entries;
@@ -226,6 +253,18 @@ struct OpRasterFrameBin
 	}
 };
 
+// the tiles of rectangle r in a bitmap of one bit per tile: a row's tiles are consecutive bits, one atomic per word of 32, not per tile
+__device__ __forceinline__ void mark_tiles(uint32_t* bits, const VgxRasterRect& r, uint32_t tilesW)
+{
+	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
+		const uint32_t k0 = ty * tilesW + r.tx0, k1 = ty * tilesW + r.tx1; // < sentinel: the rectangle lies inside the image
+		for (uint32_t w = k0 >> 5; w <= (k1 >> 5); ++w) {
+			const uint32_t lo = w == (k0 >> 5) ? (k0 & 31u) : 0u, hi = w == (k1 >> 5) ? (k1 & 31u) : 31u;
+			atomicOr(&bits[w], (0xFFFFFFFFu >> (31u - hi)) & (0xFFFFFFFFu << lo));
+		}
+	}
+}
+
 __global__ __launch_bounds__(256) void k_rasterf_entries(VgxRasterFrameArgs F)
 {
 	const VgxRasterArgs& A = F.R;
@@ -234,192 +273,24 @@ __global__ __launch_bounds__(256) void k_rasterf_entries(VgxRasterFrameArgs F)
 	if (k >= A.state[1] && k < A.sort_n) { A.keys[k] = A.sentinel; A.vals[k] = 0u; }
 	if (k >= A.nrange || A.mesh_entries[k] == 0u) { return; }
 	const uint64_t m = A.mesh_begin + k;
-	const float4 box = ((const float4*)A.mesh_bounds)[m];
-	const float b[4] = { box.x, box.y, box.z, box.w };
 	const VgxRasterMeshState st = F.mesh_state[k];
 	VgxRasterRect r;
-	if (!vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, st.rect, &r)) { return; } // (not taken: the count found entries)
+	if (!frame_rect(F, m, st, &r)) { return; } // (not taken: the count found entries)
 	uint64_t at = A.mesh_first[k]; // + the mesh's entries <= the total <= entry_cap: checked by finish()
 	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
 		for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx, ++at) { A.keys[at] = ty * A.tiles_w + tx; A.vals[at] = (uint32_t)m; }
 	}
+	// a level that cannot set a flag has no bitmap for it
+	if (st.pad & VGX_RT_SAMPLED) { mark_tiles(F.tile_tex, r, A.tiles_w); }
+	if (st.pad & VGX_RT_PAINTED) { mark_tiles(F.tile_paint, r, A.tiles_w); }
 }
 
-// 112 bytes: the record; its mesh's slot in s_state | mode << 8; the mesh's rectangle in this tile as a mask of columns (bits 0 .. 15)
-// and a mask of rows (bits 16 .. 31), so that a pixel's test is two shifts and an AND
+// 112 bytes: the record; its mesh's slot in s_state | mode << 8 | VGX_RT_SAMPLED / VGX_RT_GRADIENT / VGX_RT_PATTERN; the mesh's rectangle
+// in this tile as a mask of columns (bits 0 .. 15) and a mask of rows (bits 16 .. 31), so that a pixel's test is two shifts and an AND
 struct VgxRasterFrameTri { VgxRasterTri T; uint32_t slot_mode, mask; };
 struct VgxRasterTileState { uint32_t mode_rect, f, n; };          // mode << 20 | y1 << 15 | x1 << 10 | y0 << 5 | x0, tile-local, half open
-
-__global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
-{
-	__shared__ VgxRasterFrameTri s_tri[256];
-	__shared__ uint64_t s_first[257];   // exclusive prefix of the triangle counts of the (at most 256) meshes in hand
-	__shared__ uint32_t s_mesh[256];
-	__shared__ VgxRasterTileState s_state[256];
-	__shared__ Sum3 s_wave[4];
-	__shared__ uint32_t s_count[4];
-	const VgxRasterArgs& A = F.R;
-	if (A.state[0] != VGX_OK) { return; }
-	const uint32_t tid = threadIdx.x;
-	const int lane = tid & (VGX_WAVE - 1);
-	const uint32_t wave = tid >> 6;
-	const uint32_t tx = A.tile_x0 + blockIdx.x, ty = A.tile_y0 + blockIdx.y;
-	const uint32_t lx = tid & 15u, ly = tid >> 4;
-	const uint32_t ox = tx * VGX_RASTER_TILE, oy = ty * VGX_RASTER_TILE;
-	const uint32_t i = ox + lx, j = oy + ly;
-	const bool inside = i >= A.scissor[0] && i < A.scissor[2] && j >= A.scissor[1] && j < A.scissor[3];
-	const uint32_t key = ty * A.tiles_w + tx;
-	const uint32_t r0 = lower_bound_u32(A.sorted_keys, A.sort_n, key), r1 = lower_bound_u32(A.sorted_keys, A.sort_n, key + 1u);
-	const bool clear = (A.flags & VGX_RASTER_CLEAR) != 0;
-	if (r0 == r1 && !clear) { return; } // block-uniform
-	uint32_t* const pixel = A.pixels + (uint64_t)j * A.stride + i;
-	const uint32_t before = inside ? (clear ? A.clear_color : *pixel) : 0u;
-	uint32_t d = before;
-	uint32_t S = VGX_RASTER_STAMP_NONE;
-	const double px = (double)(A.x0 + (int32_t)i) + 0.5, py = (double)(A.y0 + (int32_t)j) + 0.5;
-	for (uint32_t eb = r0; eb < r1; eb += 256u) { // block-uniform loops throughout
-		const uint32_t ne = min(256u, r1 - eb);
-		Sum3 v = sum3_zero();
-		if (tid < ne) {
-			const uint32_t m = A.sorted_vals[eb + tid];
-			s_mesh[tid] = m;
-			v.a = A.meshes[m].num_indices / 3u;
-			// the mesh's rectangle cut to this tile (an entry means its box reaches the tile inside the rectangle: not empty)
-			const VgxRasterMeshState ms = F.mesh_state[m - A.mesh_begin];
-			const uint32_t cx0 = max(ox, ms.rect[0]), cx1 = min(ox + VGX_RASTER_TILE, ms.rect[2]);
-			const uint32_t cy0 = max(oy, ms.rect[1]), cy1 = min(oy + VGX_RASTER_TILE, ms.rect[3]);
-			VgxRasterTileState ts;
-			ts.f = ms.f; ts.n = ms.n;
-			ts.mode_rect = cx0 < cx1 && cy0 < cy1 ? (ms.mode << 20) | ((cy1 - oy) << 15) | ((cx1 - ox) << 10) | ((cy0 - oy) << 5) | (cx0 - ox) : (uint32_t)VGX_RF_NOTHING << 20;
-			s_state[tid] = ts;
-		}
-		Sum3 tot;
-		const Sum3 incl = block_incl_scan<256>(v, s_wave, &tot);
-		s_first[tid + 1u] = incl.a;
-		if (tid == 0u) { s_first[0] = 0; }
-		__syncthreads();
-		for (uint64_t tb = 0; tb < tot.a; tb += 256u) {
-			const uint64_t g = tb + tid;
-			bool keep = false;
-			VgxRasterFrameTri R;
-			if (g < tot.a) {
-				uint32_t lo = 0, hi = ne; // the last mesh whose first triangle is <= g
-				while (hi - lo > 1u) {
-					const uint32_t mid = (lo + hi) >> 1;
-					if (s_first[mid] <= g) { lo = mid; } else { hi = mid; }
-				}
-				const uint32_t mr = s_state[lo].mode_rect;
-				const vgx_mesh me = A.meshes[s_mesh[lo]];
-				const uint16_t* ip = A.idx + me.first_index + 3ull * (g - s_first[lo]);
-				const uint32_t i0 = ip[0], i1 = ip[1], i2 = ip[2];
-				if ((mr >> 20) != VGX_RF_NOTHING && i0 < me.num_vertices && i1 < me.num_vertices && i2 < me.num_vertices) {
-					const float2* pp = (const float2*)A.pos + me.first_vertex;
-					const uint32_t* cp = A.color + me.first_vertex;
-					const float2 p0 = pp[i0], p1 = pp[i1], p2 = pp[i2];
-					uint32_t a0, a1, b0, b1;
-					const uint32_t cols = ((1u << ((mr >> 10) & 31u)) - 1u) & ~((1u << (mr & 31u)) - 1u), rows = ((1u << ((mr >> 15) & 31u)) - 1u) & ~((1u << ((mr >> 5) & 31u)) - 1u);
-					R.slot_mode = lo | ((mr >> 20) << 8); R.mask = cols | (rows << 16);
-					keep = vgx_raster_setup(v2(p0.x, p0.y), v2(p1.x, p1.y), v2(p2.x, p2.y), cp[i0], cp[i1], cp[i2], &R.T)
-					    && vgx_raster_span(R.T.minx, R.T.maxx, A.x0, ox + (mr & 31u), ox + ((mr >> 10) & 31u), &a0, &a1)
-					    && vgx_raster_span(R.T.miny, R.T.maxy, A.y0, oy + ((mr >> 5) & 31u), oy + ((mr >> 15) & 31u), &b0, &b1);
-				}
-			}
-			const uint64_t kept = wave_ballot(keep);
-			if (lane == 0) { s_count[wave] = (uint32_t)__popcll(kept); }
-			__syncthreads();
-			uint32_t base = 0, n = 0;
-#pragma unroll
-			for (uint32_t w = 0; w < 4u; ++w) { const uint32_t c = s_count[w]; base += w < wave ? c : 0u; n += c; }
-			if (keep) { s_tri[base + (uint32_t)__popcll(kept & lanemask_lt(lane))] = R; }
-			__syncthreads();
-			for (uint32_t t = 0; t < n; ++t) { // every lane walks the records: no lane leaves between the barriers
-				const uint32_t mk = s_tri[t].mask; // beside the record: an untested mesh needs no second, dependent LDS read
-				if (((mk >> lx) & (mk >> (16u + ly)) & 1u) != 0u) {
-					const uint32_t sm = s_tri[t].slot_mode;
-					uint32_t f = 0u, n = 0u;
-					if ((sm >> 8) != VGX_RF_PLAIN) { const VgxRasterTileState ts = s_state[sm & 255u]; f = ts.f; n = ts.n; }
-					d = vgx_raster_frame_pixel(s_tri[t].T, sm >> 8, f, n, px, py, &S, d);
-				}
-			}
-			__syncthreads(); // s_tri and s_count are written again
-		}
-		__syncthreads(); // s_mesh, s_state and s_first are written again
-	}
-	if (inside && (clear || d != before)) { *pixel = d; }
-}
-
-// ---- vgx_raster_textured: the same four steps again, no kind skipped, text and user meshes sampled from an image ----------------------
-//   k_rastert_count    k_rasterf_count without the test of the kind (vgx_raster_any_mesh_tiles); a mesh of kind TEXT / TRILIST under a
-//                      draw of type 0 is sampled: its image record is checked here, a bad one marks the mesh like a draw index outside
-//                      the table (the scan's third lane, OpRasterFrameBin as it is), a good one leaves "sampled" and the handle in the
-//                      state's pad word
-//   k_rastert_entries  also marks, in one bit per tile of the image (zeroed by the host part before the launches), the tiles a sampled
-//                      mesh has an entry in
-//   k_rastert_tiles    two instantiations over the same grid; a tile belongs to the one its bit names and the other leaves at once.
-//                      <false>, the tiles no sampled mesh reaches: k_rasterf_tiles' body, its records and its LDS. <true>: with, per
-//                      slot of s_state, the image record of a sampled mesh in LDS (read from global once per batch of meshes, by
-//                      the lane that loads the slot) and, per setup record, the three UVs widened to binary64 at setup (int16: the
-//                      division by 32767 happens there). The pixel loop reads descriptor and UVs from LDS -- one address for all
-//                      lanes, a broadcast -- and nothing but texels from global memory: 1 (nearest) or 4 (linear) independent
-//                      loads. Every lane walks every record, so the loop stays barrier-uniform. A frame without sampled meshes
-//                      pays one bit test per tile for the wide kernel, not its LDS.
-__global__ __launch_bounds__(256) void k_rastert_count(VgxRasterTexArgs X)
-{
-	const VgxRasterFrameArgs& F = X.F;
-	const VgxRasterArgs& A = F.R;
-	const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (k >= A.nrange) { return; }
-	const uint64_t m = A.mesh_begin + k;
-	const vgx_mesh me = A.meshes[m];
-	VgxRasterMeshState st;
-	uint32_t entries = 0;
-	if (me.draw >= F.num_draws) {
-		st.mode = VGX_RF_INVALID; st.f = st.n = st.pad = 0u;
-		st.rect[0] = st.rect[1] = st.rect[2] = st.rect[3] = 0u;
-	} else {
-		vgx_raster_textured_mesh_state(me, F.draws[me.draw].state_key, F.draw_state[me.draw], A.x0, A.y0, A.scissor, X.images, X.num_images, &st);
-		const float4 box = ((const float4*)A.mesh_bounds)[m];
-		const float b[4] = { box.x, box.y, box.z, box.w };
-		VgxRasterRect r;
-		if (st.mode != VGX_RF_NOTHING && st.mode != VGX_RF_INVALID && vgx_raster_any_mesh_tiles(me, b, A.x0, A.y0, st.rect, &r)) {
-			entries = (r.tx1 - r.tx0 + 1u) * (r.ty1 - r.ty0 + 1u);
-		}
-	}
-	F.mesh_state[k] = st;
-	A.mesh_entries[k] = entries;
-}
-
-__global__ __launch_bounds__(256) void k_rastert_entries(VgxRasterTexArgs X)
-{
-	const VgxRasterFrameArgs& F = X.F;
-	const VgxRasterArgs& A = F.R;
-	if (A.state[0] != VGX_OK) { return; }
-	const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (k >= A.state[1] && k < A.sort_n) { A.keys[k] = A.sentinel; A.vals[k] = 0u; }
-	if (k >= A.nrange || A.mesh_entries[k] == 0u) { return; }
-	const uint64_t m = A.mesh_begin + k;
-	const float4 box = ((const float4*)A.mesh_bounds)[m];
-	const float b[4] = { box.x, box.y, box.z, box.w };
-	const VgxRasterMeshState st = F.mesh_state[k];
-	VgxRasterRect r;
-	if (!vgx_raster_any_mesh_tiles(A.meshes[m], b, A.x0, A.y0, st.rect, &r)) { return; } // (not taken: the count found entries)
-	uint64_t at = A.mesh_first[k]; // + the mesh's entries <= the total <= entry_cap: checked by finish()
-	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
-		for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx, ++at) { A.keys[at] = ty * A.tiles_w + tx; A.vals[at] = (uint32_t)m; }
-	}
-	if ((st.pad & VGX_RT_SAMPLED) == 0u) { return; }
-	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) { // the row's tiles are consecutive bits: one atomic per word of 32, not per tile
-		const uint32_t k0 = ty * A.tiles_w + r.tx0, k1 = ty * A.tiles_w + r.tx1; // < sentinel: the rectangle lies inside the image
-		for (uint32_t w = k0 >> 5; w <= (k1 >> 5); ++w) {
-			const uint32_t lo = w == (k0 >> 5) ? (k0 & 31u) : 0u, hi = w == (k1 >> 5) ? (k1 & 31u) : 31u;
-			atomicOr(&X.tile_tex[w], (0xFFFFFFFFu >> (31u - hi)) & (0xFFFFFFFFu << lo));
-		}
-	}
-}
-
-// 160 bytes: k_rasterf_tiles' record (slot_mode: bit 16 = sampled) and the three UVs, written for a sampled triangle only
+// 160 bytes with TEX: the record and the three UVs, written for a sampled triangle only
 struct VgxRasterTexTri { VgxRasterFrameTri R; double uv[6]; };
-#define VGX_RTT_SAMPLED 0x10000u
 
 struct VgxRasterTexelFetch
 {
@@ -440,222 +311,18 @@ __device__ __forceinline__ VgxRasterFrameTri& frame_part(VgxRasterFrameTri& r) {
 template <bool TEX> struct RasterTexRecord { typedef VgxRasterFrameTri type; };
 template <> struct RasterTexRecord<true> { typedef VgxRasterTexTri type; };
 
-template <bool TEX>
-__global__ __launch_bounds__(256) void k_rastert_tiles(VgxRasterTexArgs X)
-{
-	typedef typename RasterTexRecord<TEX>::type Record;
-	__shared__ Record s_tri[256];
-	__shared__ uint64_t s_first[257];   // exclusive prefix of the triangle counts of the (at most 256) meshes in hand
-	__shared__ uint32_t s_mesh[256];
-	__shared__ VgxRasterTileState s_state[256];
-	__shared__ vgx_raster_image s_image[TEX ? 256 : 1]; // the image of a sampled mesh in hand; not written for the other slots, and not read
-	__shared__ uint32_t s_sampled[TEX ? 256 : 1];       // VGX_RTT_SAMPLED or 0 per slot
-	__shared__ Sum3 s_wave[4];
-	__shared__ uint32_t s_count[4];
-	const VgxRasterFrameArgs& F = X.F;
-	const VgxRasterArgs& A = F.R;
-	if (A.state[0] != VGX_OK) { return; }
-	const uint32_t tx = A.tile_x0 + blockIdx.x, ty = A.tile_y0 + blockIdx.y;
-	const uint32_t key = ty * A.tiles_w + tx;
-	if ((((X.tile_tex[key >> 5] >> (key & 31u)) & 1u) != 0u) != TEX) { return; } // block-uniform: the other instantiation's tile
-	const uint32_t tid = threadIdx.x;
-	const int lane = tid & (VGX_WAVE - 1);
-	const uint32_t wave = tid >> 6;
-	const uint32_t lx = tid & 15u, ly = tid >> 4;
-	const uint32_t ox = tx * VGX_RASTER_TILE, oy = ty * VGX_RASTER_TILE;
-	const uint32_t i = ox + lx, j = oy + ly;
-	const bool inside = i >= A.scissor[0] && i < A.scissor[2] && j >= A.scissor[1] && j < A.scissor[3];
-	const uint32_t r0 = lower_bound_u32(A.sorted_keys, A.sort_n, key), r1 = lower_bound_u32(A.sorted_keys, A.sort_n, key + 1u);
-	const bool clear = (A.flags & VGX_RASTER_CLEAR) != 0;
-	if (r0 == r1 && !clear) { return; } // block-uniform
-	uint32_t* const pixel = A.pixels + (uint64_t)j * A.stride + i;
-	const uint32_t before = inside ? (clear ? A.clear_color : *pixel) : 0u;
-	uint32_t d = before;
-	uint32_t S = VGX_RASTER_STAMP_NONE;
-	const double px = (double)(A.x0 + (int32_t)i) + 0.5, py = (double)(A.y0 + (int32_t)j) + 0.5;
-	for (uint32_t eb = r0; eb < r1; eb += 256u) { // block-uniform loops throughout
-		const uint32_t ne = min(256u, r1 - eb);
-		Sum3 v = sum3_zero();
-		if (tid < ne) {
-			const uint32_t m = A.sorted_vals[eb + tid];
-			s_mesh[tid] = m;
-			v.a = A.meshes[m].num_indices / 3u;
-			// the mesh's rectangle cut to this tile (an entry means its box reaches the tile inside the rectangle: not empty)
-			const VgxRasterMeshState ms = F.mesh_state[m - A.mesh_begin];
-			const uint32_t cx0 = max(ox, ms.rect[0]), cx1 = min(ox + VGX_RASTER_TILE, ms.rect[2]);
-			const uint32_t cy0 = max(oy, ms.rect[1]), cy1 = min(oy + VGX_RASTER_TILE, ms.rect[3]);
-			VgxRasterTileState ts;
-			ts.f = ms.f; ts.n = ms.n;
-			ts.mode_rect = cx0 < cx1 && cy0 < cy1 ? (ms.mode << 20) | ((cy1 - oy) << 15) | ((cx1 - ox) << 10) | ((cy0 - oy) << 5) | (cx0 - ox) : (uint32_t)VGX_RF_NOTHING << 20;
-			s_state[tid] = ts;
-			if (TEX) {
-				const bool sampled = (ms.pad & VGX_RT_SAMPLED) != 0u;
-				s_sampled[tid] = sampled ? VGX_RTT_SAMPLED : 0u;
-				if (sampled) { s_image[tid] = X.images[ms.pad & 0xFFFFu]; } // the handle is inside the table and the record valid: k_rastert_count
-			}
-		}
-		Sum3 tot;
-		const Sum3 incl = block_incl_scan<256>(v, s_wave, &tot);
-		s_first[tid + 1u] = incl.a;
-		if (tid == 0u) { s_first[0] = 0; }
-		__syncthreads();
-		for (uint64_t tb = 0; tb < tot.a; tb += 256u) {
-			const uint64_t g = tb + tid;
-			bool keep = false;
-			Record R;
-			VgxRasterFrameTri& RF = frame_part(R);
-			double uv[6];
-			if (g < tot.a) {
-				uint32_t lo = 0, hi = ne; // the last mesh whose first triangle is <= g
-				while (hi - lo > 1u) {
-					const uint32_t mid = (lo + hi) >> 1;
-					if (s_first[mid] <= g) { lo = mid; } else { hi = mid; }
-				}
-				const uint32_t mr = s_state[lo].mode_rect;
-				const uint32_t sampled = TEX ? s_sampled[lo] : 0u;
-				const vgx_mesh me = A.meshes[s_mesh[lo]];
-				const uint16_t* ip = A.idx + me.first_index + 3ull * (g - s_first[lo]);
-				const uint32_t i0 = ip[0], i1 = ip[1], i2 = ip[2];
-				if ((mr >> 20) != VGX_RF_NOTHING && i0 < me.num_vertices && i1 < me.num_vertices && i2 < me.num_vertices) {
-					const float2* pp = (const float2*)A.pos + me.first_vertex;
-					const uint32_t* cp = A.color + me.first_vertex;
-					const float2 p0 = pp[i0], p1 = pp[i1], p2 = pp[i2];
-					uint32_t a0, a1, b0, b1;
-					const uint32_t cols = ((1u << ((mr >> 10) & 31u)) - 1u) & ~((1u << (mr & 31u)) - 1u), rows = ((1u << ((mr >> 15) & 31u)) - 1u) & ~((1u << ((mr >> 5) & 31u)) - 1u);
-					RF.slot_mode = lo | ((mr >> 20) << 8) | sampled; RF.mask = cols | (rows << 16);
-					keep = vgx_raster_setup(v2(p0.x, p0.y), v2(p1.x, p1.y), v2(p2.x, p2.y), cp[i0], cp[i1], cp[i2], &RF.T)
-					    && vgx_raster_span(RF.T.minx, RF.T.maxx, A.x0, ox + (mr & 31u), ox + ((mr >> 10) & 31u), &a0, &a1)
-					    && vgx_raster_span(RF.T.miny, RF.T.maxy, A.y0, oy + ((mr >> 5) & 31u), oy + ((mr >> 15) & 31u), &b0, &b1);
-					if (TEX && keep && sampled) {
-						vgx_raster_uv_widen(X.uv, X.uv_bytes, me.first_vertex + i0, uv);
-						vgx_raster_uv_widen(X.uv, X.uv_bytes, me.first_vertex + i1, uv + 2);
-						vgx_raster_uv_widen(X.uv, X.uv_bytes, me.first_vertex + i2, uv + 4);
-					}
-				}
-			}
-			const uint64_t kept = wave_ballot(keep);
-			if (lane == 0) { s_count[wave] = (uint32_t)__popcll(kept); }
-			__syncthreads();
-			uint32_t base = 0, n = 0;
-#pragma unroll
-			for (uint32_t w = 0; w < 4u; ++w) { const uint32_t c = s_count[w]; base += w < wave ? c : 0u; n += c; }
-			if (keep) {
-				Record* const dst = &s_tri[base + (uint32_t)__popcll(kept & lanemask_lt(lane))];
-				frame_part(*dst) = RF;
-				if (TEX && (RF.slot_mode & VGX_RTT_SAMPLED)) { store_uv(dst, uv); }
-			}
-			__syncthreads();
-			for (uint32_t t = 0; t < n; ++t) { // every lane walks the records: no lane leaves between the barriers
-				const VgxRasterFrameTri& rec = frame_part(s_tri[t]);
-				const uint32_t mk = rec.mask; // beside the record: an untested mesh needs no second, dependent LDS read
-				if (((mk >> lx) & (mk >> (16u + ly)) & 1u) != 0u) {
-					const uint32_t sm = rec.slot_mode;
-					const uint32_t mode = (sm >> 8) & 255u;
-					uint32_t f = 0u, n = 0u;
-					if (mode != VGX_RF_PLAIN) { const VgxRasterTileState ts = s_state[sm & 255u]; f = ts.f; n = ts.n; }
-					if (TEX && (sm & VGX_RTT_SAMPLED)) {
-						const vgx_raster_image im = s_image[sm & 255u];
-						VgxRasterTexelFetch fetch;
-						fetch.pixels = im.pixels; fetch.stride = im.stride;
-						d = vgx_raster_textured_pixel(rec.T, record_uv(s_tri[t]), im, mode, f, n, px, py, S, d, fetch);
-					} else {
-						d = vgx_raster_frame_pixel(rec.T, mode, f, n, px, py, &S, d);
-					}
-				}
-			}
-			__syncthreads(); // s_tri and s_count are written again
-		}
-		__syncthreads(); // s_mesh, s_state, s_image, s_sampled and s_first are written again
-	}
-	if (inside && (clear || d != before)) { *pixel = d; }
-}
-
-// ---- vgx_raster_painted: once more, with the meshes of gradient and image-pattern draws painted -------------------------------------
-//   k_rasterp_count    k_rastert_count, plus the paint check (handle inside the table of the draw's type, the entry of that type, a
-//                      pattern's image inside the image table and valid) with the same mark for a bad one; a good one leaves the table
-//                      and the handle in the state's pad word (a pattern's image is the entry's: read again where the slot is loaded)
-//   k_rasterp_entries  sets a second bit per tile: a painted mesh has an entry here
-//   k_rasterp_tiles    four instantiations <TEX, PAINT> over the same grid; a tile runs the one its two bits name, the others leave at
-//                      once. <false, false> is k_rasterf_tiles' body, LDS and records. PAINT adds, per slot of s_state, a 48-byte paint
-//                      record in LDS (six matrix floats and either four params and the two ends packed to 8 bits, or the image record),
-//                      built from the 96-byte table entry once per batch of meshes by the lane that loads the slot; with PAINT a sampled
-//                      slot keeps its image in the same record, so TEX and PAINT together need no second table. Nothing per triangle is
-//                      added: a record carries two more flag bits in slot_mode. The pixel loop reads the slot from LDS -- one address, a
-//                      broadcast -- and only texels from global memory; every lane walks every record, so the loop stays barrier-uniform.
-__global__ __launch_bounds__(256) void k_rasterp_count(VgxRasterPaintArgs P)
-{
-	const VgxRasterTexArgs& X = P.X;
-	const VgxRasterFrameArgs& F = X.F;
-	const VgxRasterArgs& A = F.R;
-	const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (k >= A.nrange) { return; }
-	const uint64_t m = A.mesh_begin + k;
-	const vgx_mesh me = A.meshes[m];
-	VgxRasterMeshState st;
-	uint32_t entries = 0;
-	if (me.draw >= F.num_draws) {
-		st.mode = VGX_RF_INVALID; st.f = st.n = st.pad = 0u;
-		st.rect[0] = st.rect[1] = st.rect[2] = st.rect[3] = 0u;
-	} else {
-		vgx_raster_painted_mesh_state(me, F.draws[me.draw].state_key, F.draw_state[me.draw], A.x0, A.y0, A.scissor, X.images, X.num_images,
-		                              P.gradients, P.num_gradients, P.patterns, P.num_patterns, &st);
-		const float4 box = ((const float4*)A.mesh_bounds)[m];
-		const float b[4] = { box.x, box.y, box.z, box.w };
-		VgxRasterRect r;
-		if (st.mode != VGX_RF_NOTHING && st.mode != VGX_RF_INVALID && vgx_raster_any_mesh_tiles(me, b, A.x0, A.y0, st.rect, &r)) {
-			entries = (r.tx1 - r.tx0 + 1u) * (r.ty1 - r.ty0 + 1u);
-		}
-	}
-	F.mesh_state[k] = st;
-	A.mesh_entries[k] = entries;
-}
-
-// the tiles of rectangle r in a bitmap of one bit per tile: a row's tiles are consecutive bits, one atomic per word of 32, not per tile
-__device__ __forceinline__ void mark_tiles(uint32_t* bits, const VgxRasterRect& r, uint32_t tilesW)
-{
-	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
-		const uint32_t k0 = ty * tilesW + r.tx0, k1 = ty * tilesW + r.tx1; // < sentinel: the rectangle lies inside the image
-		for (uint32_t w = k0 >> 5; w <= (k1 >> 5); ++w) {
-			const uint32_t lo = w == (k0 >> 5) ? (k0 & 31u) : 0u, hi = w == (k1 >> 5) ? (k1 & 31u) : 31u;
-			atomicOr(&bits[w], (0xFFFFFFFFu >> (31u - hi)) & (0xFFFFFFFFu << lo));
-		}
-	}
-}
-
-__global__ __launch_bounds__(256) void k_rasterp_entries(VgxRasterPaintArgs P)
-{
-	const VgxRasterFrameArgs& F = P.X.F;
-	const VgxRasterArgs& A = F.R;
-	if (A.state[0] != VGX_OK) { return; }
-	const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (k >= A.state[1] && k < A.sort_n) { A.keys[k] = A.sentinel; A.vals[k] = 0u; }
-	if (k >= A.nrange || A.mesh_entries[k] == 0u) { return; }
-	const uint64_t m = A.mesh_begin + k;
-	const float4 box = ((const float4*)A.mesh_bounds)[m];
-	const float b[4] = { box.x, box.y, box.z, box.w };
-	const VgxRasterMeshState st = F.mesh_state[k];
-	VgxRasterRect r;
-	if (!vgx_raster_any_mesh_tiles(A.meshes[m], b, A.x0, A.y0, st.rect, &r)) { return; } // (not taken: the count found entries)
-	uint64_t at = A.mesh_first[k]; // + the mesh's entries <= the total <= entry_cap: checked by finish()
-	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
-		for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx, ++at) { A.keys[at] = ty * A.tiles_w + tx; A.vals[at] = (uint32_t)m; }
-	}
-	if (st.pad & VGX_RT_SAMPLED) { mark_tiles(P.X.tile_tex, r, A.tiles_w); }
-	if (st.pad & VGX_RT_PAINTED) { mark_tiles(P.tile_paint, r, A.tiles_w); }
-}
-
 // what a slot of s_state keeps beside it: nothing, the image of a sampled mesh, or the paint record (whose image part serves a sampled mesh)
 template <bool TEX, bool PAINT> struct RasterPaintSlot { typedef uint32_t type; enum { N = 1 }; };
 template <> struct RasterPaintSlot<true, false> { typedef vgx_raster_image type; enum { N = 256 }; };
 template <bool TEX> struct RasterPaintSlot<TEX, true> { typedef VgxRasterPaint type; enum { N = 256 }; };
 __device__ __forceinline__ vgx_raster_image& slot_image(vgx_raster_image& s) { return s; }
 __device__ __forceinline__ vgx_raster_image& slot_image(VgxRasterPaint& s) { return s.im; }
-// slot_mode of a record: the slot (bits 0 .. 7), the mode (8 .. 15), VGX_RTT_SAMPLED, and the two paint bits
-#define VGX_RTP_GRADIENT 0x20000u
-#define VGX_RTP_PATTERN  0x40000u
+
+// bit `key` of a tile bitmap; a null bitmap (a level that cannot set it) has every bit clear. Block-uniform
+__device__ __forceinline__ bool tile_bit(const uint32_t* bits, uint32_t key) { return bits != nullptr && ((bits[key >> 5] >> (key & 31u)) & 1u) != 0u; }
 
 template <bool TEX, bool PAINT>
-__global__ __launch_bounds__(256) void k_rasterp_tiles(VgxRasterPaintArgs P)
+__global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
 {
 	typedef typename RasterTexRecord<TEX>::type Record;
 	typedef typename RasterPaintSlot<TEX, PAINT>::type Slot;
@@ -664,17 +331,14 @@ __global__ __launch_bounds__(256) void k_rasterp_tiles(VgxRasterPaintArgs P)
 	__shared__ uint32_t s_mesh[256];
 	__shared__ VgxRasterTileState s_state[256];
 	__shared__ Slot s_slot[RasterPaintSlot<TEX, PAINT>::N]; // written for the sampled and the painted slots only, and not read for the others
-	__shared__ uint32_t s_flags[TEX || PAINT ? 256 : 1];   // VGX_RTT_SAMPLED / VGX_RTP_* or 0 per slot
+	__shared__ uint32_t s_flags[TEX || PAINT ? 256 : 1];   // VGX_RT_SAMPLED / VGX_RT_GRADIENT / VGX_RT_PATTERN or 0 per slot
 	__shared__ Sum3 s_wave[4];
 	__shared__ uint32_t s_count[4];
-	const VgxRasterTexArgs& X = P.X;
-	const VgxRasterFrameArgs& F = X.F;
 	const VgxRasterArgs& A = F.R;
 	if (A.state[0] != VGX_OK) { return; }
 	const uint32_t tx = A.tile_x0 + blockIdx.x, ty = A.tile_y0 + blockIdx.y;
 	const uint32_t key = ty * A.tiles_w + tx;
-	// block-uniform: the tile of another instantiation
-	if ((((X.tile_tex[key >> 5] >> (key & 31u)) & 1u) != 0u) != TEX || (((P.tile_paint[key >> 5] >> (key & 31u)) & 1u) != 0u) != PAINT) { return; }
+	if (tile_bit(F.tile_tex, key) != TEX || tile_bit(F.tile_paint, key) != PAINT) { return; } // block-uniform: the tile of another instantiation
 	const uint32_t tid = threadIdx.x;
 	const int lane = tid & (VGX_WAVE - 1);
 	const uint32_t wave = tid >> 6;
@@ -707,16 +371,16 @@ __global__ __launch_bounds__(256) void k_rasterp_tiles(VgxRasterPaintArgs P)
 			s_state[tid] = ts;
 			if constexpr (TEX || PAINT) {
 				uint32_t fl = 0u;
-				// handles and records are inside their tables and valid: k_rasterp_count
+				// handles and records are inside their tables and valid: k_rasterf_count
 				if constexpr (TEX) {
-					if (ms.pad & VGX_RT_SAMPLED) { fl = VGX_RTT_SAMPLED; slot_image(s_slot[tid]) = X.images[ms.pad & 0xFFFFu]; }
+					if (ms.pad & VGX_RT_SAMPLED) { fl = VGX_RT_SAMPLED; slot_image(s_slot[tid]) = F.images[ms.pad & 0xFFFFu]; }
 				}
 				if constexpr (PAINT) {
 					if (ms.pad & VGX_RT_PAINTED) {
 						const bool grad = (ms.pad & VGX_RT_GRADIENT) != 0u;
-						fl = grad ? VGX_RTP_GRADIENT : VGX_RTP_PATTERN;
+						fl = grad ? VGX_RT_GRADIENT : VGX_RT_PATTERN;
 						VgxRasterPaint rec;
-						vgx_raster_paint_record((grad ? P.gradients : P.patterns)[ms.pad & 0xFFFFu], X.images, &rec);
+						vgx_raster_paint_record((grad ? F.gradients : F.patterns)[ms.pad & 0xFFFFu], F.images, &rec);
 						s_slot[tid] = rec;
 					}
 				}
@@ -755,10 +419,10 @@ __global__ __launch_bounds__(256) void k_rasterp_tiles(VgxRasterPaintArgs P)
 					keep = vgx_raster_setup(v2(p0.x, p0.y), v2(p1.x, p1.y), v2(p2.x, p2.y), cp[i0], cp[i1], cp[i2], &RF.T)
 					    && vgx_raster_span(RF.T.minx, RF.T.maxx, A.x0, ox + (mr & 31u), ox + ((mr >> 10) & 31u), &a0, &a1)
 					    && vgx_raster_span(RF.T.miny, RF.T.maxy, A.y0, oy + ((mr >> 5) & 31u), oy + ((mr >> 15) & 31u), &b0, &b1);
-					if (TEX && keep && (fl & VGX_RTT_SAMPLED)) {
-						vgx_raster_uv_widen(X.uv, X.uv_bytes, me.first_vertex + i0, uv);
-						vgx_raster_uv_widen(X.uv, X.uv_bytes, me.first_vertex + i1, uv + 2);
-						vgx_raster_uv_widen(X.uv, X.uv_bytes, me.first_vertex + i2, uv + 4);
+					if (TEX && keep && (fl & VGX_RT_SAMPLED)) {
+						vgx_raster_uv_widen(F.uv, F.uv_bytes, me.first_vertex + i0, uv);
+						vgx_raster_uv_widen(F.uv, F.uv_bytes, me.first_vertex + i1, uv + 2);
+						vgx_raster_uv_widen(F.uv, F.uv_bytes, me.first_vertex + i2, uv + 4);
 					}
 				}
 			}
@@ -771,7 +435,7 @@ __global__ __launch_bounds__(256) void k_rasterp_tiles(VgxRasterPaintArgs P)
 			if (keep) {
 				Record* const dst = &s_tri[base + (uint32_t)__popcll(kept & lanemask_lt(lane))];
 				frame_part(*dst) = RF;
-				if (TEX && (RF.slot_mode & VGX_RTT_SAMPLED)) { store_uv(dst, uv); }
+				if (TEX && (RF.slot_mode & VGX_RT_SAMPLED)) { store_uv(dst, uv); }
 			}
 			__syncthreads();
 			for (uint32_t t = 0; t < n; ++t) { // every lane walks the records: no lane leaves between the barriers
@@ -782,29 +446,30 @@ __global__ __launch_bounds__(256) void k_rasterp_tiles(VgxRasterPaintArgs P)
 					const uint32_t mode = (sm >> 8) & 255u;
 					uint32_t f = 0u, n = 0u;
 					if (mode != VGX_RF_PLAIN) { const VgxRasterTileState ts = s_state[sm & 255u]; f = ts.f; n = ts.n; }
-					bool done = false;
-					if constexpr (TEX) {
-						if (sm & VGX_RTT_SAMPLED) {
+					if (TEX && (sm & VGX_RT_SAMPLED)) {
+						if constexpr (TEX) {
 							const vgx_raster_image im = slot_image(s_slot[sm & 255u]);
 							VgxRasterTexelFetch fetch;
 							fetch.pixels = im.pixels; fetch.stride = im.stride;
 							d = vgx_raster_textured_pixel(rec.T, record_uv(s_tri[t]), im, mode, f, n, px, py, S, d, fetch);
-							done = true;
 						}
-					}
-					if constexpr (PAINT) {
-						if (sm & VGX_RTP_GRADIENT) {
-							d = vgx_raster_gradient_pixel(rec.T, s_slot[sm & 255u], mode, f, n, px, py, S, d);
-							done = true;
-						} else if (sm & VGX_RTP_PATTERN) {
-							const VgxRasterPaint pr = s_slot[sm & 255u];
-							VgxRasterTexelFetch fetch;
-							fetch.pixels = pr.im.pixels; fetch.stride = pr.im.stride;
-							d = vgx_raster_pattern_pixel(rec.T, pr, mode, f, n, px, py, S, d, fetch);
-							done = true;
+					} else {
+						// (this shape of the dispatch is the measured one: DESIGN.md, "the two raster kernel families")
+						bool painted = false;
+						if constexpr (PAINT) {
+							if (sm & VGX_RT_GRADIENT) {
+								d = vgx_raster_gradient_pixel(rec.T, s_slot[sm & 255u], mode, f, n, px, py, S, d);
+								painted = true;
+							} else if (sm & VGX_RT_PATTERN) {
+								const VgxRasterPaint pr = s_slot[sm & 255u];
+								VgxRasterTexelFetch fetch;
+								fetch.pixels = pr.im.pixels; fetch.stride = pr.im.stride;
+								d = vgx_raster_pattern_pixel(rec.T, pr, mode, f, n, px, py, S, d, fetch);
+								painted = true;
+							}
 						}
+						if (!painted) { d = vgx_raster_frame_pixel(rec.T, mode, f, n, px, py, &S, d); }
 					}
-					if (!done) { d = vgx_raster_frame_pixel(rec.T, mode, f, n, px, py, &S, d); }
 				}
 			}
 			__syncthreads(); // s_tri and s_count are written again
@@ -826,81 +491,45 @@ size_t vgx_raster_sort_bytes(uint64_t n, uint32_t bits)
 	return bytes ? bytes : 1;
 }
 
-hipError_t vgx_launch_raster(const VgxRasterArgs& a, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
+namespace {
+
+// count, scan, entries, sort, tiles: the one sequence of both families. `a` is the plain part of `args`, Op the family's scan operator,
+// tiles(grid) launches the family's tile kernel(s)
+template <class Op, class Args, class Tiles>
+hipError_t launch_sequence(const Args& args, const VgxRasterArgs& a, void (*count)(Args), void (*entries)(Args), Tiles tiles, void* partial, void* sortTemp,
+                           size_t sortBytes, hipStream_t s)
 {
-	if (a.nrange) { hipLaunchKernelGGL(k_raster_count, dim3((unsigned)((a.nrange + 255) / 256)), dim3(256), 0, s, a); }
-	OpRasterBin op;
-	op.A = a;
+	if (a.nrange) { hipLaunchKernelGGL(count, dim3((unsigned)((a.nrange + 255) / 256)), dim3(256), 0, s, args); }
+	const Op op = { args };
 	vgx_device_scan(op, (Sum3*)partial, s, a.nrange);
 	const uint64_t items = a.nrange > a.sort_n ? a.nrange : a.sort_n;
-	if (items) { hipLaunchKernelGGL(k_raster_entries, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a); }
+	if (items) { hipLaunchKernelGGL(entries, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, args); }
 	if (a.sort_n) {
 		const hipError_t e = rocprim::radix_sort_pairs(sortTemp, sortBytes, (const uint32_t*)a.keys, a.sorted_keys, (const uint32_t*)a.vals, a.sorted_vals,
 		                                               (size_t)a.sort_n, 0u, a.sort_bits, s);
 		if (e != hipSuccess) { return e; }
 	}
-	if (a.tiles_x && a.tiles_y) { hipLaunchKernelGGL(k_raster_tiles, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, a); }
+	if (a.tiles_x && a.tiles_y) { tiles(dim3(a.tiles_x, a.tiles_y)); }
 	return hipSuccess;
+}
+
+} // namespace
+
+hipError_t vgx_launch_raster(const VgxRasterArgs& a, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
+{
+	const auto tiles = [&](dim3 grid) { hipLaunchKernelGGL(k_raster_tiles, grid, dim3(256), 0, s, a); };
+	return launch_sequence<OpRasterBin>(a, a, k_raster_count, k_raster_entries, tiles, partial, sortTemp, sortBytes, s);
 }
 
 hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& f, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
 {
-	const VgxRasterArgs& a = f.R;
-	if (a.nrange) { hipLaunchKernelGGL(k_rasterf_count, dim3((unsigned)((a.nrange + 255) / 256)), dim3(256), 0, s, f); }
-	OpRasterFrameBin op;
-	op.F = f;
-	vgx_device_scan(op, (Sum3*)partial, s, a.nrange);
-	const uint64_t items = a.nrange > a.sort_n ? a.nrange : a.sort_n;
-	if (items) { hipLaunchKernelGGL(k_rasterf_entries, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, f); }
-	if (a.sort_n) {
-		const hipError_t e = rocprim::radix_sort_pairs(sortTemp, sortBytes, (const uint32_t*)a.keys, a.sorted_keys, (const uint32_t*)a.vals, a.sorted_vals,
-		                                               (size_t)a.sort_n, 0u, a.sort_bits, s);
-		if (e != hipSuccess) { return e; }
-	}
-	if (a.tiles_x && a.tiles_y) { hipLaunchKernelGGL(k_rasterf_tiles, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, f); }
-	return hipSuccess;
-}
-
-hipError_t vgx_launch_raster_textured(const VgxRasterTexArgs& x, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
-{
-	const VgxRasterArgs& a = x.F.R;
-	if (a.nrange) { hipLaunchKernelGGL(k_rastert_count, dim3((unsigned)((a.nrange + 255) / 256)), dim3(256), 0, s, x); }
-	OpRasterFrameBin op; // the marks of k_rastert_count are the ones of k_rasterf_count
-	op.F = x.F;
-	vgx_device_scan(op, (Sum3*)partial, s, a.nrange);
-	const uint64_t items = a.nrange > a.sort_n ? a.nrange : a.sort_n;
-	if (items) { hipLaunchKernelGGL(k_rastert_entries, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, x); }
-	if (a.sort_n) {
-		const hipError_t e = rocprim::radix_sort_pairs(sortTemp, sortBytes, (const uint32_t*)a.keys, a.sorted_keys, (const uint32_t*)a.vals, a.sorted_vals,
-		                                               (size_t)a.sort_n, 0u, a.sort_bits, s);
-		if (e != hipSuccess) { return e; }
-	}
-	if (a.tiles_x && a.tiles_y) {
-		hipLaunchKernelGGL(k_rastert_tiles<false>, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, x);
-		hipLaunchKernelGGL(k_rastert_tiles<true>, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, x);
-	}
-	return hipSuccess;
-}
-
-hipError_t vgx_launch_raster_painted(const VgxRasterPaintArgs& p, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
-{
-	const VgxRasterArgs& a = p.X.F.R;
-	if (a.nrange) { hipLaunchKernelGGL(k_rasterp_count, dim3((unsigned)((a.nrange + 255) / 256)), dim3(256), 0, s, p); }
-	OpRasterFrameBin op; // the marks of k_rasterp_count are the ones of k_rasterf_count
-	op.F = p.X.F;
-	vgx_device_scan(op, (Sum3*)partial, s, a.nrange);
-	const uint64_t items = a.nrange > a.sort_n ? a.nrange : a.sort_n;
-	if (items) { hipLaunchKernelGGL(k_rasterp_entries, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p); }
-	if (a.sort_n) {
-		const hipError_t e = rocprim::radix_sort_pairs(sortTemp, sortBytes, (const uint32_t*)a.keys, a.sorted_keys, (const uint32_t*)a.vals, a.sorted_vals,
-		                                               (size_t)a.sort_n, 0u, a.sort_bits, s);
-		if (e != hipSuccess) { return e; }
-	}
-	if (a.tiles_x && a.tiles_y) {
-		hipLaunchKernelGGL((k_rasterp_tiles<false, false>), dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, p);
-		hipLaunchKernelGGL((k_rasterp_tiles<true, false>), dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, p);
-		hipLaunchKernelGGL((k_rasterp_tiles<false, true>), dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, p);
-		hipLaunchKernelGGL((k_rasterp_tiles<true, true>), dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, p);
-	}
-	return hipSuccess;
+	const auto tiles = [&](dim3 grid) { // the instantiations whose tiles the level can have
+		hipLaunchKernelGGL((k_rasterf_tiles<false, false>), grid, dim3(256), 0, s, f);
+		if (f.level >= VGX_RL_TEXTURED) { hipLaunchKernelGGL((k_rasterf_tiles<true, false>), grid, dim3(256), 0, s, f); }
+		if (f.level >= VGX_RL_PAINTED) {
+			hipLaunchKernelGGL((k_rasterf_tiles<false, true>), grid, dim3(256), 0, s, f);
+			hipLaunchKernelGGL((k_rasterf_tiles<true, true>), grid, dim3(256), 0, s, f);
+		}
+	};
+	return launch_sequence<OpRasterFrameBin>(f, f.R, k_rasterf_count, k_rasterf_entries, tiles, partial, sortTemp, sortBytes, s);
 }
