@@ -197,7 +197,14 @@ typedef struct vgx_flat_out {
 	uint64_t cap_subpaths;
 } vgx_flat_out;
 
-/* Tessellation output: the three vg::Mesh streams concatenated mesh after mesh + a mesh table. */
+/* Tessellation output: the three vg::Mesh streams concatenated mesh after mesh + a mesh table.
+ * Alignment: that of the element types and no more -- pos 8 bytes, color 4, idx 2, meshes 8 (its records hold uint64_t). The streams
+ * may start anywhere such a pointer can: in the middle of a 16-byte word, at the last element of a cache line. Every entry that
+ * writes one of these -- vgx_tessellate, vgx_tessellate_emit, vgx_tessellate_immediate, vgx_tessellate_dashed, vgx_stroke,
+ * vgx_stroke_emit, vgx_cache_submit, vgx_merge / vgx_merge_uv / vgx_merge_uv_stream, vgx_concave_emit, vgx_text_quads -- returns
+ * VGX_E_INVALID_ARG on the host, with nothing enqueued, for a pointer below that alignment.
+ * Range: nothing outside [0, cap_vertices) of pos and color, [0, cap_indices) of idx and [0, cap_meshes) of meshes is read or
+ * written, whatever the status the call ends with. */
 typedef struct vgx_mesh_out {
 	float* pos;       /* [cap_vertices][2] */
 	uint32_t* color;  /* [cap_vertices]; non-AA meshes get the draw's colour on every vertex */

@@ -151,7 +151,25 @@ def test_concave_fringes_match_reference(rt, gpu_ctx, ref):
     _check_fills(rt, gpu_ctx, ref, _fills())
 
 
+class _Prepared:
+    pass
+
+
 def _check_fills(rt, gpu_ctx, ref, fills):
+    import torch
+    p = _prepare_fills(rt, gpu_ctx, ref, fills)
+    _emit_fills(rt, gpu_ctx, p)
+    # capacity is checked on the device
+    small = rt.MeshBuffers(p.dev, p.nv // 2, p.ni, p.nfills)
+    rt.concave_emit(gpu_ctx, p.bv_d, p.cont_d, p.ncont, p.fr_d, p.nfills, p.tp_d, p.ti_d, small)
+    torch.cuda.synchronize()
+    assert int(small.dev_status.item()) == rt.capi.VGX_E_NOSPACE
+
+
+def _prepare_fills(rt, gpu_ctx, ref, fills):
+    """Everything in front of vgx_concave_emit: the caller's two libtess2 passes around vgx_concave_move, the inputs in device
+    memory (bv_d, cont_d, fr_d, tp_d, ti_d; ncont, nfills) and the reference's mesh of every fill (refs; nv, ni in all). What it
+    returns may be emitted any number of times by _emit_fills."""
     import torch
     capi = rt.capi
     # (1) caller: boundary contours of every fill
@@ -202,23 +220,37 @@ def _check_fills(rt, gpu_ctx, ref, fills):
     fr_d = torch.from_numpy(frec.view(np.uint8).copy()).to(dev)
     tp_d = torch.from_numpy(tpos if tpos.shape[0] else np.zeros((1, 2), np.float32)).to(dev)
     ti_d = torch.from_numpy(tidx.view(np.int16) if tidx.shape[0] else np.zeros(1, np.int16)).to(dev)
-    # (2b) + (4) device: the meshes
-    refs = [_reference_mesh(ref, c, col, fr, eo) for (c, col, fr, eo) in fills]
-    nv = sum(r[0].shape[0] for r in refs)
-    ni = sum(r[2].shape[0] for r in refs)
-    bufs = rt.MeshBuffers(dev, nv, ni, len(fills))
+    p = _Prepared()
+    p.dev, p.bv_d, p.cont_d, p.fr_d, p.tp_d, p.ti_d = dev, bv_d, cont_d, fr_d, tp_d, ti_d
+    p.ncont, p.nfills = cont.shape[0], frec.shape[0]
+    p.refs = [_reference_mesh(ref, c, col, fr, eo) for (c, col, fr, eo) in fills]
+    p.nv = sum(r[0].shape[0] for r in p.refs)
+    p.ni = sum(r[2].shape[0] for r in p.refs)
+    return p
+
+
+def _emit_fills(rt, gpu_ctx, p, make_bufs=None, after_emit=None):
+    """(2b) + (4) device: the meshes of the prepared fills, compared with the reference's. make_bufs(nv, ni, nm): the output buffers
+    to emit into (default: runtime.MeshBuffers of exactly those sizes); after_emit(): called once the emit has finished, before
+    anything else is enqueued on the context. Returns the buffers and the mesh records read back from them."""
+    import torch
+    capi = rt.capi
+    nv, ni, nfills = p.nv, p.ni, p.nfills
+    bufs = make_bufs(nv, ni, nfills) if make_bufs else rt.MeshBuffers(p.dev, nv, ni, nfills)
     bufs.pos.fill_(float("nan"))
-    rt.concave_emit(gpu_ctx, bv_d, cont_d, cont.shape[0], fr_d, frec.shape[0], tp_d, ti_d, bufs)
+    rt.concave_emit(gpu_ctx, p.bv_d, p.cont_d, p.ncont, p.fr_d, nfills, p.tp_d, p.ti_d, bufs)
     torch.cuda.synchronize()
+    if after_emit:
+        after_emit()
     assert int(bufs.dev_status.item()) == 0
     sz = bufs.dev_sizes.cpu().numpy()
-    assert (int(sz[2]), int(sz[3]), int(sz[4])) == (len(fills), nv, ni)
-    meshes = bufs.meshes[:len(fills) * 32].cpu().numpy().view(capi.mesh_dtype)
+    assert (int(sz[2]), int(sz[3]), int(sz[4])) == (nfills, nv, ni)
+    meshes = bufs.meshes[:nfills * 32].cpu().numpy().view(capi.mesh_dtype)
     pos = bufs.pos[:nv].cpu().numpy()
     col = bufs.color[:nv].cpu().numpy().view(np.uint32)
     idx = bufs.idx[:ni].cpu().numpy().view(np.uint16)
     v0 = i0 = 0
-    for fi, (rp, rc, ri) in enumerate(refs):
+    for fi, (rp, rc, ri) in enumerate(p.refs):
         m = meshes[fi]
         assert (int(m["first_vertex"]), int(m["first_index"]), int(m["num_vertices"]), int(m["num_indices"])) == (v0, i0, rp.shape[0], ri.shape[0]), fi
         assert int(m["draw"]) == fi and int(m["subpath_kind"]) >> 28 == capi.MESH_CONCAVE_FILL_AA
@@ -227,8 +259,4 @@ def _check_fills(rt, gpu_ctx, ref, fills):
         assert np.array_equal(pos[v0:v0 + rp.shape[0]].view(np.uint32), rp.view(np.uint32)), ("pos", fi, np.flatnonzero((pos[v0:v0 + rp.shape[0]] != rp).any(axis=1))[:5])
         v0 += rp.shape[0]
         i0 += ri.shape[0]
-    # capacity is checked on the device
-    small = rt.MeshBuffers(dev, nv // 2, ni, len(fills))
-    rt.concave_emit(gpu_ctx, bv_d, cont_d, cont.shape[0], fr_d, frec.shape[0], tp_d, ti_d, small)
-    torch.cuda.synchronize()
-    assert int(small.dev_status.item()) == capi.VGX_E_NOSPACE
+    return bufs, meshes

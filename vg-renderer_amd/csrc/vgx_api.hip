@@ -258,6 +258,13 @@ struct DeviceGuard
 	~DeviceGuard() { if (switched) { (void)hipSetDevice(prev); } }
 };
 
+// The alignment every entry that writes a vgx_mesh_out asks of it (include/vgx.h): that of the element types -- the emit kernels
+// store whole elements, never less. A pointer below it is refused on the host, before anything is enqueued.
+static bool meshOutMisaligned(const vgx_mesh_out* out)
+{
+	return ((uintptr_t)out->pos & 7u) || ((uintptr_t)out->color & 3u) || ((uintptr_t)out->idx & 1u) || ((uintptr_t)out->meshes & 7u);
+}
+
 // Launch failures (bad configuration, device lost) surface as hipGetLastError: every entry point that enqueues kernels
 // ends with this instead of pretending success.
 int launchStatus(vgx_ctx* ctx)
@@ -2051,7 +2058,7 @@ int vgx_tessellate_count(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* dr
 int vgx_tessellate_emit(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out, void* stream)
 {
 	DeviceGuard guard(ctx);
-	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx) {
+	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx || meshOutMisaligned(out)) {
 		return VGX_E_INVALID_ARG;
 	}
 	if (ctx->lastStage != 2 || ctx->lastPs != ps || ctx->lastDraws != draws || ctx->lastNDraws != ndraws) {
@@ -2070,7 +2077,7 @@ int vgx_tessellate_emit(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* dra
 int vgx_tessellate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
-	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx) {
+	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx || meshOutMisaligned(out)) {
 		return VGX_E_INVALID_ARG;
 	}
 	if (tmplFor(ctx, ps, ndraws)) {
@@ -2161,7 +2168,7 @@ int vgx_reserve(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals)
 int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out,
                              vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
 {
-	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx) { // (before the context is touched)
+	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx || meshOutMisaligned(out)) { // (before the context is touched)
 		return VGX_E_INVALID_ARG;
 	}
 	DeviceGuard guard(ctx);
@@ -2270,7 +2277,7 @@ int vgx_stroke_emit(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths
 {
 	DeviceGuard guard(ctx);
 	(void)subpaths; (void)subpath_draw; (void)ndraws;
-	if (!ctx || !out || !out->pos || !out->color || !out->idx) {
+	if (!ctx || !out || !out->pos || !out->color || !out->idx || meshOutMisaligned(out)) {
 		return VGX_E_INVALID_ARG;
 	}
 	if (ctx->lastStage != 3 || ctx->lastDraws != draws || ctx->lastNDraws != nsubpaths) {
@@ -2289,7 +2296,7 @@ int vgx_stroke_emit(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths
 int vgx_stroke(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths, const vgx_draw* draws, uint64_t ndraws,
                const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
 {
-	if (!ctx || !out || !out->pos || !out->color || !out->idx || (nsubpaths && (!poly || !subpaths || !subpath_draw || !draws))) { // (before the context is touched)
+	if (!ctx || !out || !out->pos || !out->color || !out->idx || meshOutMisaligned(out) || (nsubpaths && (!poly || !subpaths || !subpath_draw || !draws))) { // (before the context is touched)
 		return VGX_E_INVALID_ARG;
 	}
 	DeviceGuard guard(ctx);
@@ -2476,7 +2483,7 @@ int vgx_reserve_dashed(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals, c
 int vgx_tessellate_dashed(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const struct vgx_dash* dashes, const float* pattern, uint64_t npattern,
                           const vgx_mesh_out* out, vgx_sizes* dev_sizes, vgx_sizes* dev_dash_sizes, uint32_t* dev_status, void* stream)
 {
-	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx || (npattern && !pattern)) { // (before the context is touched)
+	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx || meshOutMisaligned(out) || (npattern && !pattern)) { // (before the context is touched)
 		return VGX_E_INVALID_ARG;
 	}
 	if (((uintptr_t)dashes & 3u) || ((uintptr_t)pattern & 3u)) { return VGX_E_INVALID_ARG; }
@@ -2580,7 +2587,7 @@ int vgx_cache_localize(vgx_ctx* ctx, const vgx_draw* draws, uint64_t ndraws, flo
 int vgx_cache_submit(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_instance* instances, uint64_t ninst, const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
-	if (!ctx || !cache || !out || (!instances && ninst) || !out->pos || !out->color || !out->idx
+	if (!ctx || !cache || !out || (!instances && ninst) || !out->pos || !out->color || !out->idx || meshOutMisaligned(out)
 		|| (cache->num_meshes && (!cache->pos || !cache->color || !cache->idx || !cache->meshes))) {
 		return VGX_E_INVALID_ARG;
 	}
@@ -2921,7 +2928,7 @@ int mergeCall(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, co
 {
 	DeviceGuard guard(ctx);
 	(void)ndraws;
-	if (!ctx || !a || !b || !out || !out->pos || !out->color || !out->idx
+	if (!ctx || !a || !b || !out || !out->pos || !out->color || !out->idx || meshOutMisaligned(out)
 		|| (a->num_meshes && (!a->pos || !a->color || !a->idx || !a->meshes)) || (b->num_meshes && (!b->pos || !b->color || !b->idx || !b->meshes))) {
 		return VGX_E_INVALID_ARG;
 	}
@@ -3022,7 +3029,7 @@ int vgx_concave_emit(vgx_ctx* ctx, const float* contour_verts, uint64_t num_cont
                      const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
-	if (!ctx || !out || !out->pos || !out->color || !out->idx || (nfills && !fills) || (ncontours && (!contours || !contour_verts))) {
+	if (!ctx || !out || !out->pos || !out->color || !out->idx || meshOutMisaligned(out) || (nfills && !fills) || (ncontours && (!contours || !contour_verts))) {
 		return VGX_E_INVALID_ARG;
 	}
 	hipStream_t s = (hipStream_t)stream;
@@ -3062,7 +3069,7 @@ int vgx_text_quads(vgx_ctx* ctx, const float* quads, uint64_t nquads, const vgx_
 		return VGX_E_INVALID_ARG;
 	}
 	// the streams are written in units of their elements, the quads are read as 16-byte pairs
-	if (((uintptr_t)quads & 15u) || ((uintptr_t)out->pos & 7u) || ((uintptr_t)out->color & 3u) || ((uintptr_t)out->idx & 1u)
+	if (((uintptr_t)quads & 15u) || meshOutMisaligned(out)
 		|| (out_uv && ((uintptr_t)out_uv & (uintptr_t)(uv_bytes - 1u))) || ((uintptr_t)runs & 7u)) {
 		return VGX_E_INVALID_ARG;
 	}
