@@ -23,7 +23,6 @@
 #include <vector>
 #include <algorithm>
 #include <atomic>
-#include <unordered_map>
 #include <string.h>
 #include <math.h>
 #include <new>
@@ -73,6 +72,40 @@ template<class T> struct HostMirror
 };
 
 struct VgxGatherWire { vgx_rank_sizes z; uint64_t chunk; }; // vgx_gather_sizes: what every rank tells the others
+
+// The template the last vgx_tessellate_count built (tryTemplate). The scalar part is filled in a local value and committed to the
+// context in ONE assignment; the buffers stay where they are (a Buf is on the context's list by address).
+struct VgxTemplateState
+{
+	bool on;                 // a step may use it (tmplFor). Everything below is only read with `on` set, or by the build itself
+	bool isBatch;            // batch-wide: the whole draw list = one instance (vgx_set_static_batches)
+	const vgx_pathset* ps;
+	uint64_t psGen;          // generation id of ps when the template was built (an address can be reused by a later path set)
+	uint32_t period;
+	uint32_t classes;        // 1: every instance repeats the first period
+	VgxTmplKernel kernel;    // which emit kernel it needs (vgx_tmpl_plan.h)
+	uint32_t tileSize;       // elements per tile
+	vgx_sizes inst;          // sizes of one instance (of the first class)
+	vgx_sizes total;         // sizes of the whole batch
+	uint64_t numWg, nDraws;  // several classes: workgroups of one step; the batch size the per-instance table was built for
+	uint32_t round;          // Round-join stroke meshes per instance: their sizes, and every place behind them, are counted per step
+	uint32_t roundElems;     // their elements per instance
+	uint32_t roundLds;       // Round-join meshes of the largest class (several classes; else = round)
+	uint64_t relemWords;     // several classes: table words of the whole batch (sum over the instances of their class's Round-join elements)
+};
+struct VgxTemplate : VgxTemplateState
+{
+	Buf<VgxTmplTile> tile;   // [tiles]
+	Buf<float2> poly; Buf<VgxTmplMesh> mesh; Buf<vgx_mesh> mtab; Buf<VgxTmplElem> elem; Buf<vgx_draw> draws;
+	// several classes: one template over the concatenated class representatives, a per-instance table of output places, a
+	// per-workgroup table (instance, tile)
+	Buf<unsigned long long> hash, clsSum; Buf<uint32_t> instCls, clsRep; Buf<VgxTmplClass> cls; Buf<VgxTmplInst> iinfo; Buf<uint2> wg;
+	Buf<VgxTmplRoundMesh> trmesh; Buf<uint2> tmsz; // the Round-join meshes (mesh, first element among the Round-join elements); per mesh its sizes (VgxTmplArgs::tmsz)
+	Buf<unsigned long long> rsz, itot, iplace; Buf<uint2> relem; Buf<VgxTmplMeshPlace> mplace; // the per-step tables of a Round-join template (VgxTmplArgs)
+};
+static_assert(sizeof(VgxTmplWg) == sizeof(uint2) && offsetof(VgxTmplWg, inst) == offsetof(uint2, x) && offsetof(VgxTmplWg, tile) == offsetof(uint2, y), "the host's workgroup table is uploaded as uint2");
+static_assert(sizeof(VgxTmplClass) == 40 && offsetof(VgxTmplClass, round) == 32 && sizeof(VgxTmplClass().round) == 8, "VgxTmplClass: the named words lie where the padding did");
+static_assert(sizeof(VgxTmplMesh) == 64 && offsetof(VgxTmplMesh, fringe_bits) == 56 && offsetof(VgxTmplMesh, round_no) == 60, "VgxTmplMesh: the named words lie where the padding did");
 
 struct vgx_ctx
 {
@@ -174,31 +207,10 @@ struct vgx_ctx
 	// template mode (vgx_tmpl.hip): the first period of an instanced batch whose instances differ in transform / colours only,
 	// flattened once in local space by the last vgx_tessellate_count
 	int optTmpl; uint32_t optTmplTile;
-	uint32_t tmplTileSize;               // elements per tile of the current template
-	Buf<VgxTmplTile> tmplTile;           // [tiles]
-	bool tmplOn;
-	const vgx_pathset* tmplPs;
-	uint64_t tmplPsGen;                  // generation id of tmplPs when the template was built (an address can be reused by a later path set)
-	uint32_t tmplPeriod;
-	vgx_sizes tmplInst;                  // sizes of one instance
-	Buf<float2> tmplPoly; Buf<VgxTmplMesh> tmplMesh; Buf<vgx_mesh> tmplMtab; Buf<VgxTmplElem> tmplElem; Buf<vgx_draw> tmplDraws;
-	// ... in several flavours ("classes", e.g. the same drawing at a few scales): one template over the concatenated class
-	// representatives, a per-instance table of output places, a per-workgroup table (instance, tile)
-	int optTmplClasses;
+	int optTmplClasses;                  // VGX_TMPL_CLASSES=0: template mode only for batches whose instances all repeat the first period
 	int optTmplRound;                    // VGX_TMPL_ROUND=0: batches with Round joins keep the ordinary pipeline
 	int optTmplBatch;                    // vgx_set_static_batches / VGX_TMPL_BATCH=1: a batch without a period becomes ONE template (the whole draw list = one instance)
-	bool tmplIsBatch;                    // the current template is such a batch-wide one
-	uint32_t tmplClasses;                // 1: every instance repeats the first period
-	uint32_t tmplGeneral;                // stroke styles of the template: 0 closed Miter AA / Thin only, 1 + open Miter with Butt / Square caps, 2 + general
-	uint64_t tmplNumWg, tmplNDraws;      // several classes: workgroups of one step; the batch size the per-instance table was built for
-	vgx_sizes tmplTotal;                 // sizes of the whole batch
-	Buf<unsigned long long> tmplHash, tmplClsSum; Buf<uint32_t> tmplInstCls, tmplClsRep; Buf<VgxTmplClass> tmplCls; Buf<VgxTmplInst> tmplIinfo; Buf<uint2> tmplWg;
-	uint32_t tmplRound;                  // Round-join stroke meshes per instance (tmplGeneral == 3): their sizes, and every place behind them, are counted per step
-	uint32_t tmplRoundElems;             // their elements per instance
-	uint32_t tmplRoundLds;               // Round-join meshes of the largest class (several classes; else = tmplRound)
-	uint64_t tmplRelemWords;             // several classes: table words of the whole batch (sum over the instances of their class's Round-join elements)
-	Buf<VgxTmplRoundMesh> tmplTrmesh; Buf<uint2> tmplTmsz; // template: the Round-join meshes (mesh, first element among the Round-join elements); per mesh its sizes (VgxTmplArgs::tmsz)
-	Buf<unsigned long long> tmplRsz, tmplItot, tmplIplace; Buf<uint2> tmplRelem; Buf<VgxTmplMeshPlace> tmplMplace; // the per-step tables of such a template (VgxTmplArgs)
+	VgxTemplate tmpl;                    // the current template
 	// element capacities of the buffers above. Never lifted: only ensureMeshBuffers and ensureCmdScratch write it, from the buffers'
 	// capacities, so every launch may trust it; a launch that needs other bounds (a sizing pass, the caller's capacities) is given them
 	VgxCaps caps;
@@ -228,6 +240,9 @@ struct vgx_ctx
 };
 
 static void vgx_rccl_release(vgx_ctx* ctx);
+// Every call that takes the ground from under the current template (its scratch, its path set, its mode) ends it here: the next
+// vgx_tessellate wants a count again
+static void tmplDrop(vgx_ctx* ctx) { ctx->tmpl.on = false; }
 
 namespace {
 
@@ -551,7 +566,7 @@ uint32_t instPeriodFor(const vgx_ctx* ctx, uint64_t ndraws)
 void forgetRoutes(vgx_ctx* ctx)
 {
 	ctx->instPeriod = 0; ctx->instGrouped = 0; ctx->instClasses = 1; ctx->instPermOn = 0;
-	ctx->tmplOn = false;
+	tmplDrop(ctx);
 }
 
 // Grouped mode for this call: the count pass chose it and the sort buffers hold a batch of this size over this path set.
@@ -1316,7 +1331,7 @@ int vgx_pathset_destroy(vgx_ctx* ctx, vgx_pathset* ps)
 		return VGX_E_INVALID_ARG;
 	}
 	if (ctx->lastPs == ps) { ctx->lastPs = nullptr; ctx->lastStage = 0; }
-	if (ctx->tmplPs == ps) { ctx->tmplOn = false; ctx->tmplPs = nullptr; ctx->tmplPsGen = 0; } // a later path set at the same address must not match the template
+	if (ctx->tmpl.ps == ps) { tmplDrop(ctx); ctx->tmpl.ps = nullptr; ctx->tmpl.psGen = 0; } // a later path set at the same address must not match the template
 	// hipFree waits for everything in flight (a caller may drop a set right behind an asynchronous call that reads it); a blob that
 	// goes back to the pool instead must be as idle: the same wait, without the allocator's work
 	if (ps->blob && ps->blobBytes <= VGX_PS_POOL_MAX) { (void)hipDeviceSynchronize(); }
@@ -1446,7 +1461,7 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
 	ctx->lastStage = 0;
-	ctx->tmplOn = false;
+	tmplDrop(ctx);
 	int st;
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
 	// The kernel instance and segment bucket (f1Shape) from the batch's leaves per command, taken from the LAST call on this context with
@@ -1607,20 +1622,20 @@ static int tmplRoundSizes(vgx_ctx* ctx, VgxTmplArgs& a, hipStream_t s)
 {
 	int st;
 	const uint64_t n = a.ninst;
-	a.num_round = ctx->tmplRound; a.num_round_elems = ctx->tmplRoundElems;
-	a.trmesh = ctx->tmplTrmesh.ptr(); a.tmsz = ctx->tmplTmsz.ptr();
+	a.num_round = ctx->tmpl.round; a.num_round_elems = ctx->tmpl.roundElems;
+	a.trmesh = ctx->tmpl.trmesh.ptr(); a.tmsz = ctx->tmpl.tmsz.ptr();
 	if (n * a.num_round >= (1ull << 31)) { return VGX_E_RANGE; } // one wave (long meshes: one workgroup) per (instance, Round-join mesh)
 	const bool classes = a.cls != nullptr; // several classes: the tables' rows are the instances' own (VgxTmplInst::m / ::rel), the sizes stay in LDS
-	if (!classes && (st = ensure(ctx, ctx->tmplRsz, (n * a.num_round + 1) * 2)) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplRelem, (classes ? ctx->tmplRelemWords : n * a.num_round_elems) + 1)) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplMplace, (classes ? a.total.num_meshes : n * a.inst.num_meshes) + 1)) != VGX_OK) { return st; }
+	if (!classes && (st = ensure(ctx, ctx->tmpl.rsz, (n * a.num_round + 1) * 2)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmpl.relem, (classes ? ctx->tmpl.relemWords : n * a.num_round_elems) + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmpl.mplace, (classes ? a.total.num_meshes : n * a.inst.num_meshes) + 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
-	a.rsz = classes ? nullptr : ctx->tmplRsz.ptr(); a.relem = ctx->tmplRelem.ptr();
-	a.mplace = ctx->tmplMplace.ptr();
+	a.rsz = classes ? nullptr : ctx->tmpl.rsz.ptr(); a.relem = ctx->tmpl.relem.ptr();
+	a.mplace = ctx->tmpl.mplace.ptr();
 	if (vgx_tmpl_round_per_instance(a)) {
-		if ((st = ensure(ctx, ctx->tmplItot, (n + 1) * 2)) != VGX_OK) { return st; }
-		if ((st = ensure(ctx, ctx->tmplIplace, (n + 1) * 2)) != VGX_OK) { return st; }
-		a.itot = ctx->tmplItot.ptr(); a.iplace = ctx->tmplIplace.ptr();
+		if ((st = ensure(ctx, ctx->tmpl.itot, (n + 1) * 2)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->tmpl.iplace, (n + 1) * 2)) != VGX_OK) { return st; }
+		a.itot = ctx->tmpl.itot.ptr(); a.iplace = ctx->tmpl.iplace.ptr();
 	}
 	vgx_launch_tmpl_round_sizes(a, (Sum3*)ctx->partial.p, s);
 	mark(ctx, s, "tmpl_round_sizes");
@@ -1630,28 +1645,23 @@ static int tmplRoundSizes(vgx_ctx* ctx, VgxTmplArgs& a, hipStream_t s)
 // the step's arguments but the caller's buffers
 static void tmplArgs(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, VgxTmplArgs& a)
 {
-	a.draws = draws; a.ndraws = ndraws; a.period = ctx->tmplPeriod; a.ninst = ndraws / ctx->tmplPeriod; a.npaths = ps->dev.npaths;
-	a.tdraws = ctx->tmplDraws.ptr(); a.tpoly = ctx->tmplPoly.ptr(); a.tmesh = ctx->tmplMesh.ptr();
-	a.tmtab = ctx->tmplMtab.ptr(); a.telem = ctx->tmplElem.ptr();
-	a.inst = ctx->tmplInst;
-	a.ttile = ctx->tmplTile.ptr();
-	a.tile = ctx->tmplTileSize;
-	a.tiles_per_inst = (uint32_t)((ctx->tmplInst.num_elements + a.tile - 1) / a.tile);
+	a.draws = draws; a.ndraws = ndraws; a.period = ctx->tmpl.period; a.ninst = ndraws / ctx->tmpl.period; a.npaths = ps->dev.npaths;
+	a.tdraws = ctx->tmpl.draws.ptr(); a.tpoly = ctx->tmpl.poly.ptr(); a.tmesh = ctx->tmpl.mesh.ptr();
+	a.tmtab = ctx->tmpl.mtab.ptr(); a.telem = ctx->tmpl.elem.ptr();
+	a.inst = ctx->tmpl.inst;
+	a.ttile = ctx->tmpl.tile.ptr();
+	a.tile = ctx->tmpl.tileSize;
+	a.tiles_per_inst = (uint32_t)((ctx->tmpl.inst.num_elements + a.tile - 1) / a.tile);
 	a.caps = ctx->caps;
 	a.totals = ctx->totals.ptr();
-	a.general = ctx->tmplGeneral;
-	if (ctx->tmplClasses > 1) {
-		a.iinfo = ctx->tmplIinfo.ptr(); a.wg = ctx->tmplWg.ptr(); a.num_wg = ctx->tmplNumWg;
-		a.cls = ctx->tmplCls.ptr(); a.round_lds = ctx->tmplRoundLds;
-		a.total = ctx->tmplTotal;
+	a.kernel = ctx->tmpl.kernel;
+	if (ctx->tmpl.classes > 1) {
+		a.iinfo = ctx->tmpl.iinfo.ptr(); a.wg = ctx->tmpl.wg.ptr(); a.num_wg = ctx->tmpl.numWg;
+		a.cls = ctx->tmpl.cls.ptr(); a.round_lds = ctx->tmpl.roundLds;
+		a.total = ctx->tmpl.total;
 	} else {
-		const vgx_sizes& i1 = ctx->tmplInst;
-		vgx_sizes z;
-		z.num_poly_vertices = a.ninst * i1.num_poly_vertices; z.num_subpaths = a.ninst * i1.num_subpaths; z.num_meshes = a.ninst * i1.num_meshes;
-		z.num_vertices = a.ninst * i1.num_vertices; z.num_indices = a.ninst * i1.num_indices; z.num_serial_draws = a.ninst * i1.num_serial_draws;
-		z.num_cmd_instances = a.ninst * i1.num_cmd_instances; z.num_elements = a.ninst * i1.num_elements; z.num_fill_elements = a.ninst * i1.num_fill_elements;
-		z.num_drawcmds = 0;
-		a.total = z;
+		memset(&a.total, 0, sizeof(a.total));
+		vgx_tmpl_add_instances(a.total, a.ninst, ctx->tmpl.inst);
 		a.num_wg = a.ninst * (uint64_t)a.tiles_per_inst;
 	}
 }
@@ -1665,7 +1675,7 @@ static int runTmpl(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 	a.caps.vertices = out->cap_vertices; a.caps.indices = out->cap_indices; a.caps.meshes = out->cap_meshes;
 	if (a.num_wg > 0x7FFFFFFFull) { return VGX_E_RANGE; } // one workgroup per (instance, tile)
 	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
-	if (a.general == 3 || a.general == 5 || a.general == 6) {
+	if (vgx_tmpl_kernel_is_round(a.kernel)) {
 		// Round joins: vertices / indices are the instances' own -- counted on the device, checked against the capacities there
 		a.total.num_vertices = 0; a.total.num_indices = 0;
 		int st;
@@ -1700,8 +1710,8 @@ static int runTmpl(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 
 static bool tmplFor(const vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws)
 {
-	return ctx->tmplOn && ctx->optTmpl && ps == ctx->tmplPs && ps->gen == ctx->tmplPsGen && ctx->tmplPeriod && ndraws % ctx->tmplPeriod == 0 && ndraws >= ctx->tmplPeriod
-		&& (ctx->tmplClasses == 1 || ndraws == ctx->tmplNDraws); // several classes: the per-instance table belongs to ONE batch size
+	return ctx->tmpl.on && ctx->optTmpl && ps == ctx->tmpl.ps && ps->gen == ctx->tmpl.psGen && ctx->tmpl.period && ndraws % ctx->tmpl.period == 0 && ndraws >= ctx->tmpl.period
+		&& (ctx->tmpl.classes == 1 || ndraws == ctx->tmpl.nDraws); // several classes: the per-instance table belongs to ONE batch size
 }
 
 // The ordinary count + two-phase flatten in LOCAL space (apply_transform = 0) + mesh sizing of `n` draws: what a template is built
@@ -1723,282 +1733,271 @@ static int tmplPipeline(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* d, 
 	if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
 	return VGX_OK;
 }
-// one instance of a class: only the mesh kinds k_tmpl_emit writes, every output stream of the instance below 4 GB
-static bool tmplEligible(const VgxTotals& ht, bool roundOk)
+// ---- the template build: vgx_tessellate_count, first thing ---------------------------------------------------------------------
+// Do the draws repeat their first period in everything but transform and colours -- or a FEW flavours of it ("classes": every
+// instance equals one of at most VGX_TMPL_MAX_CLASSES representatives, e.g. one drawing at a handful of scales) --, and are the
+// meshes all of the kinds the emit kernels write? Then the representatives are flattened ONCE, in local space, by the ordinary
+// two-phase kernels and kept as the context's template. A sequence of stages (tryTemplate); the host's decisions between the
+// kernels are vgx_tmpl_plan.h's.
+// What a stage reports: go on (VGX_OK), not a template -- the caller continues with the ordinary count --, or an error.
+struct TmplStage
 {
-	const vgx_sizes& z = ht.sizes;
-	return !((ht.num_round_meshes && !roundOk) || z.num_elements == 0 || z.num_elements >= (1ull << 31) || z.num_vertices >= (1ull << 29)
-		|| z.num_indices >= (1ull << 31) || z.num_poly_vertices >= (1ull << 32) || z.num_meshes >= (1ull << 32));
-}
+	int st;
+	bool ordinary;
+	TmplStage(int status) : st(status), ordinary(false) {}
+	static TmplStage notATemplate() { TmplStage r(VGX_OK); r.ordinary = true; return r; }
+	bool stop() const { return st != VGX_OK || ordinary; }
+};
+static const TmplStage TMPL_ORDINARY = TmplStage::notATemplate();
 
-// vgx_tessellate_count, first thing: do the draws repeat their first period in everything but transform and colours -- or a FEW
-// flavours of it ("classes": every instance equals one of at most VGX_TMPL_MAX_CLASSES representatives, e.g. one drawing at a
-// handful of scales) --, and are the meshes all of the kinds k_tmpl_emit writes (fills; closed Miter AA / Thin strokes)? Then the
-// representatives are flattened ONCE, in local space, by the ordinary two-phase kernels and kept as the context's template.
-// Returns VGX_OK with ctx->tmplOn set (out_sizes filled), VGX_OK with it clear (not such a batch: the caller continues with the
-// ordinary count), or an error.
-static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, vgx_sizes* out_sizes, hipStream_t s)
+struct TmplJob // what the stages hand on
 {
-	ctx->tmplOn = false;
-	if (!ctx->optTmpl || !ctx->optInst || (ndraws <= VGX_SMALL_DRAWS && !ctx->optTmplBatch) || ndraws == 0) { return VGX_OK; } // (static batches: frame-sized draw lists too)
+	vgx_ctx* ctx; const vgx_pathset* ps; const vgx_draw* draws; uint64_t ndraws; hipStream_t s;
+	VgxTemplateState t;                    // the template's scalar part, committed to the context in one piece
+	uint64_t P, ninst;                     // period, instances
+	uint32_t T;                            // classes
+	std::vector<uint32_t> instCls, reps;   // several classes: class of every instance, first instance of every class
+	vgx_sizes all;                         // sizes of the concatenated representatives
+	VgxTmplBuild b;
+	std::vector<VgxTmplClass> cls;         // [T + 1] the class table, read back
+	std::vector<vgx_sizes> csz;            // sizes of one instance of every class
+	std::vector<uint64_t> clsRelems;       // Round-join elements of one instance of every class
+	VgxTmplPlan plan;
+};
+
+// The period the draws repeat with (k_inst_detect, k_tmpl_check), or the whole draw list as one batch-wide instance
+static TmplStage tmplDetectPeriod(TmplJob& j)
+{
+	vgx_ctx* ctx = j.ctx;
 	int st;
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
-	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
-	vgx_launch_inst_detect(draws, ndraws, ctx->totals.ptr(), s);
-	vgx_launch_tmpl_check(draws, ndraws, ps->dev.npaths, ctx->totals.ptr(), s);
-	if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), j.s));
+	vgx_launch_inst_detect(j.draws, j.ndraws, ctx->totals.ptr(), j.s);
+	vgx_launch_tmpl_check(j.draws, j.ndraws, j.ps->dev.npaths, ctx->totals.ptr(), j.s);
+	if ((st = readTotals(ctx, j.s)) != VGX_OK) { return st; }
 	if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
-	ctx->tmplIsBatch = false;
 	unsigned long long P = (ctx->hostTotals->inst_detect_inv == 0 || ctx->hostTotals->inst_detect_bad) ? 0ull : ~0ull - ctx->hostTotals->inst_detect_inv;
-	if (P == 0 || P > (1ull << 24) || ndraws % P != 0 || ndraws / P < VGX_INST_MIN_INSTANCES) {
+	if (P == 0 || P > (1ull << 24) || j.ndraws % P != 0 || j.ndraws / P < VGX_INST_MIN_INSTANCES) {
 		// no drawing repeated for many instances. A caller that keeps its batches' STRUCTURE from call to call (vgx_set_static_batches: the
 		// same paths and styles in the same order, only transforms and colours move -- a static scene under a moving camera, a culled or
 		// shuffled instanced scene) gets the whole draw list as ONE template of one instance: flattened once here, in local space; a step is
 		// then the emit kernel alone, and any structural change ends it with VGX_E_STALE (the caller counts again)
-		if (!ctx->optTmplBatch || ndraws >= (1ull << 31)) { return VGX_OK; }
-		P = ndraws;
-		ctx->tmplIsBatch = true;
+		if (!ctx->optTmplBatch || j.ndraws >= (1ull << 31)) { return TMPL_ORDINARY; }
+		P = j.ndraws;
+		j.t.isBatch = true;
 		ctx->hostTotals->tmpl_bad = 0;
 	}
-	const uint64_t ninst = ndraws / P;
-	uint32_t T = 1;
-	std::vector<uint32_t> instCls, reps(1, 0u);
-	if (ctx->hostTotals->tmpl_bad) {
-		// not ONE period repeated. A few flavours of it? Candidates by hash of the template fields, then compared bit by bit.
-		if (!ctx->optTmplClasses || ninst > (1ull << 24)) { return VGX_OK; } // (per-instance tables: 40 bytes per instance and tile on host and device)
-		if ((st = ensure(ctx, ctx->tmplHash, ninst)) != VGX_OK) { return st; }
-		noteHip(ctx, hipMemsetAsync(ctx->tmplHash.p, 0, ninst * sizeof(unsigned long long), s));
-		vgx_launch_tmpl_hash(draws, ndraws, P, ctx->tmplHash.ptr(), s);
-		std::vector<unsigned long long> hashes(ninst);
-		HIPCHK(ctx, hipMemcpyAsync(hashes.data(), ctx->tmplHash.p, ninst * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-		HIPCHK(ctx, hipStreamSynchronize(s));
-		instCls.resize(ninst);
-		reps.clear();
-		std::unordered_map<unsigned long long, uint32_t> seen;
-		for (uint64_t k = 0; k < ninst; ++k) {
-			const auto it = seen.find(hashes[k]);
-			uint32_t c;
-			if (it != seen.end()) { c = it->second; }
-			else {
-				c = (uint32_t)reps.size();
-				if (c == VGX_TMPL_MAX_CLASSES) { return VGX_OK; } // too many flavours: the ordinary pipeline
-				seen.emplace(hashes[k], c);
-				reps.push_back((uint32_t)k);
-			}
-			instCls[k] = c;
-		}
-		T = (uint32_t)reps.size();
-		if ((st = ensure(ctx, ctx->tmplInstCls, ninst)) != VGX_OK) { return st; }
-		if ((st = ensure(ctx, ctx->tmplClsRep, (size_t)T)) != VGX_OK) { return st; }
-		HIPCHK(ctx, hipMemcpyAsync(ctx->tmplInstCls.p, instCls.data(), ninst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-		HIPCHK(ctx, hipMemcpyAsync(ctx->tmplClsRep.p, reps.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-		noteHip(ctx, hipMemsetAsync(&ctx->totals.ptr()->tmpl_bad, 0, sizeof(uint32_t), s));
-		vgx_launch_tmpl_check_cls(draws, ndraws, P, ctx->tmplInstCls.ptr(), ctx->tmplClsRep.ptr(), ctx->totals.ptr(), s);
-		if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
-		if (ctx->hostTotals->tmpl_bad) { return VGX_OK; } // equal hashes, different records
+	j.P = P; j.ninst = j.ndraws / P;
+	return VGX_OK;
+}
+
+// Not ONE period repeated: a few flavours of it? Candidates by hash of the template fields, then compared bit by bit.
+static TmplStage tmplClassify(TmplJob& j)
+{
+	vgx_ctx* ctx = j.ctx;
+	const uint64_t ninst = j.ninst;
+	j.T = 1; j.reps.assign(1, 0u);
+	if (!ctx->hostTotals->tmpl_bad) { return VGX_OK; }
+	if (!ctx->optTmplClasses || ninst > (1ull << 24)) { return TMPL_ORDINARY; } // (per-instance tables: 40 bytes per instance and tile on host and device)
+	int st;
+	if ((st = ensure(ctx, ctx->tmpl.hash, ninst)) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->tmpl.hash.p, 0, ninst * sizeof(unsigned long long), j.s));
+	vgx_launch_tmpl_hash(j.draws, j.ndraws, j.P, ctx->tmpl.hash.ptr(), j.s);
+	std::vector<unsigned long long> hashes(ninst);
+	HIPCHK(ctx, hipMemcpyAsync(hashes.data(), ctx->tmpl.hash.p, ninst * sizeof(unsigned long long), hipMemcpyDeviceToHost, j.s));
+	HIPCHK(ctx, hipStreamSynchronize(j.s));
+	if (!vgx_tmpl_group_classes(hashes.data(), ninst, j.instCls, j.reps)) { return TMPL_ORDINARY; } // too many flavours
+	j.T = (uint32_t)j.reps.size();
+	if ((st = ensure(ctx, ctx->tmpl.instCls, ninst)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmpl.clsRep, (size_t)j.T)) != VGX_OK) { return st; }
+	HIPCHK(ctx, hipMemcpyAsync(ctx->tmpl.instCls.p, j.instCls.data(), ninst * sizeof(uint32_t), hipMemcpyHostToDevice, j.s));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->tmpl.clsRep.p, j.reps.data(), (size_t)j.T * sizeof(uint32_t), hipMemcpyHostToDevice, j.s));
+	noteHip(ctx, hipMemsetAsync(&ctx->totals.ptr()->tmpl_bad, 0, sizeof(uint32_t), j.s));
+	vgx_launch_tmpl_check_cls(j.draws, j.ndraws, j.P, ctx->tmpl.instCls.ptr(), ctx->tmpl.clsRep.ptr(), ctx->totals.ptr(), j.s);
+	if ((st = readTotals(ctx, j.s)) != VGX_OK) { return st; }
+	if (ctx->hostTotals->tmpl_bad) { return TMPL_ORDINARY; } // equal hashes, different records
+	return VGX_OK;
+}
+
+// The class representatives' draw records, back to back (the saved records every step verifies the batch against), and all of
+// them through the count pipeline as ONE batch: the template. (Several classes: NOT one pipeline per representative -- their sizes
+// are differences of the prefixes the one concatenated run leaves behind, k_tmpl_class_sums; the Tiger at seven scales = 18
+// classes: count 4.2 -> ~1 ms)
+static TmplStage tmplRepresentatives(TmplJob& j)
+{
+	vgx_ctx* ctx = j.ctx;
+	const uint64_t P = j.P, PT = P * j.T;
+	int st;
+	if ((st = ensure(ctx, ctx->tmpl.draws, (size_t)PT)) != VGX_OK) { return st; }
+	for (uint32_t c = 0; c < j.T; ++c) {
+		HIPCHK(ctx, hipMemcpyAsync(ctx->tmpl.draws.ptr() + (uint64_t)c * P, j.draws + (uint64_t)j.reps[c] * P, (size_t)P * sizeof(vgx_draw), hipMemcpyDeviceToDevice, j.s));
 	}
-	// the class representatives' draw records, back to back (the saved records every step verifies the batch against)
-	const uint64_t PT = P * T;
-	if ((st = ensure(ctx, ctx->tmplDraws, (size_t)PT)) != VGX_OK) { return st; }
-	for (uint32_t c = 0; c < T; ++c) {
-		HIPCHK(ctx, hipMemcpyAsync(ctx->tmplDraws.ptr() + (uint64_t)c * P, draws + (uint64_t)reps[c] * P, (size_t)P * sizeof(vgx_draw), hipMemcpyDeviceToDevice, s));
+	j.csz.assign(j.T, vgx_sizes());
+	if ((st = tmplPipeline(ctx, j.ps, ctx->tmpl.draws.ptr(), PT, j.s)) != VGX_OK) { return st; }
+	const VgxTotals& ht = *ctx->hostTotals;
+	if (j.T == 1) {
+		if (!vgx_tmpl_eligible(ht, ctx->optTmplRound != 0)) { return TMPL_ORDINARY; }
+		j.csz[0] = ht.sizes;
+	} else if ((ht.num_round_meshes && !ctx->optTmplRound) || ht.sizes.num_poly_vertices >= (1ull << 32) || ht.sizes.num_meshes >= (1ull << 32) || ht.sizes.num_elements >= (1ull << 36)) {
+		return TMPL_ORDINARY; // (the limits of one instance: per class, tmplBuildTables)
 	}
-	const vgx_draw* rdraws = ctx->tmplDraws.ptr();
-	// sizes of one instance of every class (several classes: each representative through the pipeline on its own first)
-	// (several classes, round 6: NOT one pipeline per representative -- their sizes are differences of the prefixes the one concatenated
-	// run leaves behind, k_tmpl_class_sums below; the Tiger at seven scales = 18 classes: count 4.2 -> ~1 ms)
-	std::vector<vgx_sizes> csz(T);
-	// all representatives as one batch: the template
-	if ((st = tmplPipeline(ctx, ps, rdraws, PT, s)) != VGX_OK) { return st; }
-	{
-		const VgxTotals& ht = *ctx->hostTotals;
-		if (T == 1) {
-			// Round joins (their sizes are the instance's): templates of one class; else the ordinary pipeline
-			if (!tmplEligible(ht, ctx->optTmplRound != 0)) { return VGX_OK; }
-			csz[0] = ht.sizes;
-		} else if ((ht.num_round_meshes && !ctx->optTmplRound) || ht.sizes.num_poly_vertices >= (1ull << 32) || ht.sizes.num_meshes >= (1ull << 32) || ht.sizes.num_elements >= (1ull << 36)) {
-			return VGX_OK;
-		}
-	}
-	const vgx_sizes all = ctx->hostTotals->sizes;
+	j.all = ht.sizes;
+	return VGX_OK;
+}
+
+// Which stroke styles does the template hold (k_tmpl_styles)? They decide the emit kernel and, with it, the tile size. Leaves the
+// class table zeroed but for the style word.
+static TmplStage tmplChooseKernel(TmplJob& j)
+{
+	vgx_ctx* ctx = j.ctx;
+	const uint32_t T = j.T;
 	const bool general = ctx->hostTotals->has_general_stroke != 0;
-	const uint64_t M = all.num_meshes, E = all.num_elements, V = all.num_poly_vertices;
-	if ((st = ensure(ctx, ctx->tmplCls, (size_t)T + 1)) != VGX_OK) { return st; }
-	VgxTmplBuild b;
-	memset(&b, 0, sizeof(b));
-	// which stroke styles does the template hold? (decides the emit kernel and, with it, the tile size)
+	int st;
+	if ((st = ensure(ctx, ctx->tmpl.cls, (size_t)T + 1)) != VGX_OK) { return st; }
+	memset(&j.b, 0, sizeof(j.b));
 	uint32_t styles = 0;
+	noteHip(ctx, hipMemsetAsync(ctx->tmpl.cls.p, 0, ((size_t)T + 1) * sizeof(VgxTmplClass), j.s));
 	if (general) {
-		b.mdesc = ctx->mdesc.ptr(); b.num_meshes = M; b.nclasses = T; b.cls = ctx->tmplCls.ptr();
-		noteHip(ctx, hipMemsetAsync(ctx->tmplCls.p, 0, ((size_t)T + 1) * sizeof(VgxTmplClass), s));
-		vgx_launch_tmpl_styles(b, s);
-		HIPCHK(ctx, hipMemcpyAsync(&styles, &ctx->tmplCls.ptr()[T].pad[0], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-		HIPCHK(ctx, hipStreamSynchronize(s));
-	} else {
-		noteHip(ctx, hipMemsetAsync(ctx->tmplCls.p, 0, ((size_t)T + 1) * sizeof(VgxTmplClass), s));
+		j.b.mdesc = ctx->mdesc.ptr(); j.b.num_meshes = j.all.num_meshes; j.b.nclasses = T; j.b.cls = ctx->tmpl.cls.ptr();
+		vgx_launch_tmpl_styles(j.b, j.s);
+		HIPCHK(ctx, hipMemcpyAsync(&styles, &VGX_TMPL_STYLES(ctx->tmpl.cls.ptr(), T), sizeof(uint32_t), hipMemcpyDeviceToHost, j.s));
+		HIPCHK(ctx, hipStreamSynchronize(j.s));
 	}
-	// (bit 3: closed Bevel strokes -- a kernel of their own beside the closed Miter ones; with open strokes or anything else in the template, the general one)
-	// (bit 4: closed AA strokes with Round joins -- with nothing but closed strokes in the template, kernel 5: no general body)
-	const uint32_t kernelKind = (styles & 4u) ? ((styles & 3u) ? 3u : ((styles & 32u) ? 6u : 5u)) : ((styles & 2u) ? 2u : ((styles & 8u) ? ((styles & 1u) ? 2u : 4u) : ((styles & 1u) ? 1u : 0u)));
-	const bool roundTmpl = kernelKind == 3u || kernelKind == 5u || kernelKind == 6u;
-	// (Round joins in a template of several classes, round 6: the per-step tables are addressed per instance -- VgxTmplInst::m / ::rel --, the
-	// sizes pass runs in its workgroup-per-instance shape; a batch that does not fit that shape takes the ordinary pipeline, see below)
-	uint32_t tileSize = ((kernelKind == 2u || kernelKind == 3u) && ctx->optTmplTile > VGX_TMPL_GENERAL_TILE) ? (uint32_t)VGX_TMPL_GENERAL_TILE : ctx->optTmplTile;
-	if ((kernelKind == 5u || kernelKind == 6u) && ctx->optTmplTile == VGX_TMPL_MAX_TILE) { tileSize = VGX_TMPL_RC_TILE; } // (its own workgroup shape; a VGX_TMPL_TILE override stands)
-	b.draws = rdraws; b.poly = (const float2*)ctx->poly.p; b.mdesc = ctx->mdesc.ptr(); b.mprep = ctx->mprep.ptr(); b.mtab = ctx->mtab.ptr();
+	j.t.kernel = vgx_tmpl_kernel_for(styles);
+	// (Round joins in a template of several classes: the per-step tables are addressed per instance -- VgxTmplInst::m / ::rel --, the sizes
+	// pass runs in its workgroup-per-instance shape; a batch that does not fit that shape takes the ordinary pipeline, tmplFirstRoundSizes)
+	j.t.tileSize = vgx_tmpl_tile_for(j.t.kernel, ctx->optTmplTile);
+	return VGX_OK;
+}
+
+// The class table (k_tmpl_classes) and the sizes of one instance of every class; then the template's tables (vgx_launch_tmpl_build)
+static TmplStage tmplBuildTables(TmplJob& j)
+{
+	vgx_ctx* ctx = j.ctx;
+	const uint32_t T = j.T;
+	const uint64_t M = j.all.num_meshes, V = j.all.num_poly_vertices;
+	VgxTmplBuild& b = j.b;
+	int st;
+	b.draws = ctx->tmpl.draws.ptr(); b.poly = (const float2*)ctx->poly.p; b.mdesc = ctx->mdesc.ptr(); b.mprep = ctx->mprep.ptr(); b.mtab = ctx->mtab.ptr();
 	b.prefix_fill = ctx->elemPrefix.ptr(); b.prefix_stroke = ctx->elemPrefixS.ptr();
-	b.num_meshes = M; b.num_elems = E; b.tile = tileSize; b.period = (uint32_t)P; b.nclasses = T;
-	b.num_vertices = all.num_vertices; b.num_indices = all.num_indices; b.cls = ctx->tmplCls.ptr();
-	vgx_launch_tmpl_classes(b, s);
-	std::vector<VgxTmplClass> cls((size_t)T + 1);
+	b.num_meshes = M; b.num_elems = j.all.num_elements; b.tile = j.t.tileSize; b.period = (uint32_t)j.P; b.nclasses = T;
+	b.num_vertices = j.all.num_vertices; b.num_indices = j.all.num_indices; b.cls = ctx->tmpl.cls.ptr();
+	vgx_launch_tmpl_classes(b, j.s);
+	j.cls.resize((size_t)T + 1);
 	std::vector<unsigned long long> csum(((size_t)T + 1) * 5, 0ull);
 	if (T > 1) {
-		if ((st = ensure(ctx, ctx->tmplClsSum, ((size_t)T + 1) * 5)) != VGX_OK) { return st; }
-		vgx_launch_tmpl_class_sums(b, ctx->dinfo.ptr(), (const uint64_t*)ctx->cmdPrefix.p, PT, all, ctx->tmplClsSum.ptr(), s);
-		HIPCHK(ctx, hipMemcpyAsync(csum.data(), ctx->tmplClsSum.p, csum.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+		if ((st = ensure(ctx, ctx->tmpl.clsSum, ((size_t)T + 1) * 5)) != VGX_OK) { return st; }
+		vgx_launch_tmpl_class_sums(b, ctx->dinfo.ptr(), (const uint64_t*)ctx->cmdPrefix.p, j.P * T, j.all, ctx->tmpl.clsSum.ptr(), j.s);
+		HIPCHK(ctx, hipMemcpyAsync(csum.data(), ctx->tmpl.clsSum.p, csum.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, j.s));
 	}
-	HIPCHK(ctx, hipMemcpyAsync(cls.data(), ctx->tmplCls.p, ((size_t)T + 1) * sizeof(VgxTmplClass), hipMemcpyDeviceToHost, s));
-	HIPCHK(ctx, hipStreamSynchronize(s));
-	if (T > 1) { // sizes of ONE instance of every class = what the concatenated run holds between the class's first draw and the next class's
-		for (uint32_t c = 0; c < T; ++c) {
-			vgx_sizes q;
-			memset(&q, 0, sizeof(q));
-			q.num_meshes = cls[c + 1].mesh0 - cls[c].mesh0; q.num_elements = cls[c + 1].elem0 - cls[c].elem0;
-			q.num_vertices = cls[c + 1].v0 - cls[c].v0; q.num_indices = cls[c + 1].i0 - cls[c].i0;
-			const unsigned long long* a0 = &csum[(size_t)c * 5]; const unsigned long long* a1 = &csum[(size_t)(c + 1) * 5];
-			q.num_poly_vertices = a1[0] - a0[0]; q.num_subpaths = a1[1] - a0[1]; q.num_cmd_instances = a1[2] - a0[2];
-			q.num_fill_elements = a1[3] - a0[3]; q.num_serial_draws = a1[4]; // (entry c + 1 holds class c's own count)
-			csz[c] = q;
-			VgxTotals one; // the limits of one instance (tmplEligible), per class as before
-			memset(&one, 0, sizeof(one));
-			one.sizes = q;
-			if (!tmplEligible(one, false)) { return VGX_OK; }
-		}
-	}
-	const uint64_t tiles = cls[T].tile0;
-	if ((st = ensure(ctx, ctx->tmplPoly, V + 1)) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplMesh, M + 1)) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplMtab, M + 1)) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplElem, tiles * tileSize + 64)) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplTile, tiles + 1)) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplTrmesh, M + 2)) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->tmplTmsz, M + 1)) != VGX_OK) { return st; }
-	b.tmsz = ctx->tmplTmsz.ptr();
-	b.trmesh = ctx->tmplTrmesh.ptr();
-	b.has_round = roundTmpl ? 1u : 0u;
+	HIPCHK(ctx, hipMemcpyAsync(j.cls.data(), ctx->tmpl.cls.p, ((size_t)T + 1) * sizeof(VgxTmplClass), hipMemcpyDeviceToHost, j.s));
+	HIPCHK(ctx, hipStreamSynchronize(j.s));
+	if (T > 1 && !vgx_tmpl_class_sizes(j.cls.data(), csum.data(), T, j.csz)) { return TMPL_ORDINARY; }
+	const uint64_t tiles = j.cls[T].tile0;
+	if ((st = ensure(ctx, ctx->tmpl.poly, V + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmpl.mesh, M + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmpl.mtab, M + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmpl.elem, tiles * j.t.tileSize + 64)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmpl.tile, tiles + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmpl.trmesh, M + 2)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->tmpl.tmsz, M + 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	b.tmsz = ctx->tmpl.tmsz.ptr(); b.trmesh = ctx->tmpl.trmesh.ptr();
+	b.has_round = vgx_tmpl_kernel_is_round(j.t.kernel) ? 1u : 0u;
 	b.partial = (Sum3*)ctx->partial.p;
-	b.ttile = ctx->tmplTile.ptr();
-	b.tmesh = ctx->tmplMesh.ptr(); b.tmtab = ctx->tmplMtab.ptr(); b.telem = ctx->tmplElem.ptr();
-	vgx_launch_tmpl_build(b, s);
-	HIPCHK(ctx, hipMemcpyAsync(ctx->tmplPoly.p, ctx->poly.p, V * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-	// Round joins: how many such meshes the template holds and their elements; several classes: where each class's begin (k_tmpl_round_classes)
-	uint32_t roundWord = 0, roundElems = 0, roundLds = 0;
-	std::vector<uint64_t> clsRelems(T, 0); // Round-join elements of one instance of every class
-	if (roundTmpl) {
-		HIPCHK(ctx, hipMemcpyAsync(cls.data(), ctx->tmplCls.p, ((size_t)T + 1) * sizeof(VgxTmplClass), hipMemcpyDeviceToHost, s));
-		HIPCHK(ctx, hipStreamSynchronize(s));
-		roundWord = cls[T].pad[1];
-		if (roundWord == 0) { return VGX_OK; }
-		VgxTmplRoundMesh last;
-		HIPCHK(ctx, hipMemcpyAsync(&last, ctx->tmplTrmesh.ptr() + roundWord, sizeof(last), hipMemcpyDeviceToHost, s));
-		HIPCHK(ctx, hipStreamSynchronize(s));
-		roundElems = last.elem0;
-		roundLds = roundWord;
-		clsRelems[0] = roundElems;
-		if (T > 1) {
-			roundLds = 0;
-			for (uint32_t c = 0; c < T; ++c) {
-				const uint32_t r1 = c + 1 < T ? cls[c + 1].pad[1] : roundWord, e1 = c + 1 < T ? cls[c + 1].pad[0] : roundElems;
-				clsRelems[c] = e1 - cls[c].pad[0];
-				if (r1 - cls[c].pad[1] > roundLds) { roundLds = r1 - cls[c].pad[1]; }
-			}
-		}
+	b.ttile = ctx->tmpl.tile.ptr();
+	b.tmesh = ctx->tmpl.mesh.ptr(); b.tmtab = ctx->tmpl.mtab.ptr(); b.telem = ctx->tmpl.elem.ptr();
+	vgx_launch_tmpl_build(b, j.s);
+	HIPCHK(ctx, hipMemcpyAsync(ctx->tmpl.poly.p, ctx->poly.p, V * 2 * sizeof(float), hipMemcpyDeviceToDevice, j.s));
+	return VGX_OK;
+}
+
+// Round joins: how many such meshes the template holds and their elements; several classes: where each class's begin (k_tmpl_round_classes)
+static TmplStage tmplReadRoundLayout(TmplJob& j)
+{
+	vgx_ctx* ctx = j.ctx;
+	const uint32_t T = j.T;
+	j.clsRelems.assign(T, 0);
+	if (!vgx_tmpl_kernel_is_round(j.t.kernel)) { return VGX_OK; }
+	HIPCHK(ctx, hipMemcpyAsync(j.cls.data(), ctx->tmpl.cls.p, ((size_t)T + 1) * sizeof(VgxTmplClass), hipMemcpyDeviceToHost, j.s));
+	HIPCHK(ctx, hipStreamSynchronize(j.s));
+	j.t.round = j.cls[T].round[VGX_TC_MESH0];
+	if (j.t.round == 0) { return TMPL_ORDINARY; }
+	VgxTmplRoundMesh last;
+	HIPCHK(ctx, hipMemcpyAsync(&last, ctx->tmpl.trmesh.ptr() + j.t.round, sizeof(last), hipMemcpyDeviceToHost, j.s));
+	HIPCHK(ctx, hipStreamSynchronize(j.s));
+	j.t.roundElems = last.elem0;
+	vgx_tmpl_round_layout(j.cls.data(), T, j.t.round, j.t.roundElems, j.clsRelems, j.t.roundLds);
+	return VGX_OK;
+}
+
+// The batch: instances x their class's sizes; several classes: the per-instance and per-workgroup tables, uploaded
+static TmplStage tmplPlanBatch(TmplJob& j)
+{
+	vgx_ctx* ctx = j.ctx;
+	const uint64_t ninst = j.ninst;
+	VgxTmplPlan& p = j.plan;
+	int st;
+	if (!vgx_tmpl_plan_batch(j.csz.data(), j.cls.data(), j.T, ninst, j.instCls.data(), vgx_tmpl_kernel_is_round(j.t.kernel) ? j.clsRelems.data() : nullptr, p)) { return TMPL_ORDINARY; }
+	if (j.T > 1) {
+		if ((st = ensure(ctx, ctx->tmpl.iinfo, ninst + 1)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->tmpl.wg, (size_t)p.numWg + 1)) != VGX_OK) { return st; }
+		HIPCHK(ctx, hipMemcpyAsync(ctx->tmpl.iinfo.p, p.inst.data(), (ninst + 1) * sizeof(VgxTmplInst), hipMemcpyHostToDevice, j.s));
+		HIPCHK(ctx, hipMemcpyAsync(ctx->tmpl.wg.p, p.wg.data(), (size_t)p.numWg * sizeof(VgxTmplWg), hipMemcpyHostToDevice, j.s));
+		HIPCHK(ctx, hipStreamSynchronize(j.s)); // the copies have read the host tables
 	}
-	// the batch: instances x their class's sizes
-	std::vector<uint64_t> cnt(T, 0);
-	if (T == 1) { cnt[0] = ninst; } else { for (uint64_t k = 0; k < ninst; ++k) { ++cnt[instCls[k]]; } }
-	vgx_sizes z;
-	memset(&z, 0, sizeof(z));
-	uint64_t numWg = 0;
-	for (uint32_t c = 0; c < T; ++c) {
-		const vgx_sizes& q = csz[c];
-		z.num_poly_vertices += cnt[c] * q.num_poly_vertices; z.num_subpaths += cnt[c] * q.num_subpaths; z.num_meshes += cnt[c] * q.num_meshes;
-		z.num_vertices += cnt[c] * q.num_vertices; z.num_indices += cnt[c] * q.num_indices; z.num_serial_draws += cnt[c] * q.num_serial_draws;
-		z.num_cmd_instances += cnt[c] * q.num_cmd_instances; z.num_elements += cnt[c] * q.num_elements; z.num_fill_elements += cnt[c] * q.num_fill_elements;
-		numWg += cnt[c] * (uint64_t)(cls[c + 1].tile0 - cls[c].tile0);
-	}
-	if (T > 1) {
-		if (numWg > 0x7FFFFFFFull || z.num_meshes >= (1ull << 32)) { return VGX_OK; }
-		std::vector<VgxTmplInst> ii(ninst + 1);
-		std::vector<uint2> wg((size_t)numWg);
-		uint64_t v = 0, i = 0, m = 0, w = 0, re = 0;
-		for (uint64_t k = 0; k <= ninst; ++k) {
-			VgxTmplInst r;
-			memset(&r, 0, sizeof(r));
-			r.v = v; r.i = i; r.m = (uint32_t)m;
-			if (k < ninst) {
-				const uint32_t c = instCls[k];
-				r.cls = c; r.cmesh0 = cls[c].mesh0;
-				r.rel = roundTmpl ? re - (uint64_t)cls[c].pad[0] : 0ull; // (the element numbers in the mesh records run over the whole template)
-				v += csz[c].num_vertices; i += csz[c].num_indices; m += csz[c].num_meshes; re += clsRelems[c];
-			}
-			ii[(size_t)k] = r;
-		}
-		// Workgroup order: class after class (the instances of a class in draw order). The output places are the instances' own
-		// whatever the order; running one class's instances together keeps ONE class's tables hot in L2 instead of all of them
-		// (instances in draw order: 3.9 GB of table re-reads from HBM for Tiger x 10k in 18 classes).
-		std::vector<uint64_t> cursor(T, 0);
-		for (uint32_t c = 0; c < T; ++c) { cursor[c] = w; w += cnt[c] * (uint64_t)(cls[c + 1].tile0 - cls[c].tile0); }
-		for (uint64_t k = 0; k < ninst; ++k) {
-			const uint32_t c = instCls[k];
-			for (uint32_t t = cls[c].tile0; t < cls[c + 1].tile0; ++t) { wg[(size_t)cursor[c]++] = make_uint2((uint32_t)k, t); }
-		}
-		if ((st = ensure(ctx, ctx->tmplIinfo, ninst + 1)) != VGX_OK) { return st; }
-		if ((st = ensure(ctx, ctx->tmplWg, (size_t)numWg + 1)) != VGX_OK) { return st; }
-		HIPCHK(ctx, hipMemcpyAsync(ctx->tmplIinfo.p, ii.data(), (ninst + 1) * sizeof(VgxTmplInst), hipMemcpyHostToDevice, s));
-		HIPCHK(ctx, hipMemcpyAsync(ctx->tmplWg.p, wg.data(), (size_t)numWg * sizeof(uint2), hipMemcpyHostToDevice, s));
-		HIPCHK(ctx, hipStreamSynchronize(s)); // the host vectors go away
-	}
-	HIPCHK(ctx, hipStreamSynchronize(s));
+	HIPCHK(ctx, hipStreamSynchronize(j.s));
 	if ((st = launchStatus(ctx)) != VGX_OK) { return st; }
-	ctx->tmplRound = roundWord;
-	ctx->tmplRoundElems = roundElems;
-	ctx->tmplRoundLds = roundLds;
-	ctx->tmplRelemWords = 0;
-	for (uint32_t c = 0; c < T; ++c) { ctx->tmplRelemWords += cnt[c] * clsRelems[c]; }
-	ctx->tmplInst = csz[0];
-	ctx->tmplTileSize = tileSize;
-	ctx->tmplPeriod = (uint32_t)P;
-	ctx->tmplPs = ps;
-	ctx->tmplPsGen = ps->gen;
-	ctx->tmplClasses = T;
-	ctx->tmplNumWg = numWg;
-	ctx->tmplNDraws = ndraws;
-	ctx->tmplTotal = z;
-	ctx->tmplGeneral = kernelKind; // which instantiation of the emit kernel the template needs
-	if (roundTmpl) {
-		// Round joins: this batch's vertices / indices -- the count of one step, read back
-		VgxTmplArgs a;
-		memset(&a, 0, sizeof(a));
-		tmplArgs(ctx, ps, draws, ndraws, a);
-		a.caps.vertices = ~0ull; a.caps.indices = ~0ull; a.caps.meshes = ~0ull;
-		a.total.num_vertices = 0; a.total.num_indices = 0;
-		if (a.num_wg > 0x7FFFFFFFull || a.ninst * (uint64_t)roundWord >= (1ull << 31)) { return VGX_OK; } // beyond the sizes kernels' grids: the ordinary pipeline
-		if (T > 1) { // several classes: only the workgroup-per-instance shape of the sizes pass addresses its tables per instance
-			a.num_round = roundWord; a.num_round_elems = roundElems;
-			if (!vgx_tmpl_round_per_instance(a) || ctx->tmplRelemWords >= (1ull << 40)) { return VGX_OK; }
-		}
-		noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
-		if ((st = tmplRoundSizes(ctx, a, s)) != VGX_OK) { return st; }
-		if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
-		if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
-		z = ctx->hostTotals->sizes;
-		ctx->tmplTotal = z;
+	j.t.ps = j.ps; j.t.psGen = j.ps->gen; j.t.period = (uint32_t)j.P; j.t.classes = j.T; j.t.nDraws = j.ndraws;
+	j.t.inst = j.csz[0]; j.t.total = p.total; j.t.numWg = p.numWg; j.t.relemWords = p.relemWords;
+	return VGX_OK;
+}
+
+// Round joins: this batch's vertices / indices -- the count of one step (through the committed template, tmplArgs), read back
+static TmplStage tmplFirstRoundSizes(TmplJob& j)
+{
+	vgx_ctx* ctx = j.ctx;
+	int st;
+	VgxTmplArgs a;
+	memset(&a, 0, sizeof(a));
+	tmplArgs(ctx, j.ps, j.draws, j.ndraws, a);
+	a.caps.vertices = ~0ull; a.caps.indices = ~0ull; a.caps.meshes = ~0ull;
+	a.total.num_vertices = 0; a.total.num_indices = 0;
+	if (a.num_wg > 0x7FFFFFFFull || a.ninst * (uint64_t)j.t.round >= (1ull << 31)) { return TMPL_ORDINARY; } // beyond the sizes kernels' grids
+	if (j.T > 1) { // several classes: only the workgroup-per-instance shape of the sizes pass addresses its tables per instance
+		a.num_round = j.t.round; a.num_round_elems = j.t.roundElems;
+		if (!vgx_tmpl_round_per_instance(a) || ctx->tmpl.relemWords >= (1ull << 40)) { return TMPL_ORDINARY; }
 	}
-	ctx->tmplOn = true;
-	*out_sizes = z;
-	ctx->hostTotals->sizes = z; // what vgx_tessellate_emit checks the caller's capacities against
+	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), j.s));
+	if ((st = tmplRoundSizes(ctx, a, j.s)) != VGX_OK) { return st; }
+	if ((st = readTotals(ctx, j.s)) != VGX_OK) { return st; }
+	if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
+	ctx->tmpl.total = ctx->hostTotals->sizes;
+	return VGX_OK;
+}
+
+// Returns VGX_OK with ctx->tmpl.on set (out_sizes filled), VGX_OK with it clear (not such a batch: the caller continues with the
+// ordinary count), or an error.
+static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, vgx_sizes* out_sizes, hipStream_t s)
+{
+	tmplDrop(ctx);
+	if (!ctx->optTmpl || !ctx->optInst || (ndraws <= VGX_SMALL_DRAWS && !ctx->optTmplBatch) || ndraws == 0) { return VGX_OK; } // (static batches: frame-sized draw lists too)
+	TmplJob j;
+	j.ctx = ctx; j.ps = ps; j.draws = draws; j.ndraws = ndraws; j.s = s;
+	memset(&j.t, 0, sizeof(j.t));
+	TmplStage (*const build[])(TmplJob&) = { tmplDetectPeriod, tmplClassify, tmplRepresentatives, tmplChooseKernel, tmplBuildTables, tmplReadRoundLayout, tmplPlanBatch };
+	for (auto stage : build) {
+		const TmplStage r = stage(j);
+		if (r.stop()) { return r.st; }
+	}
+	static_cast<VgxTemplateState&>(ctx->tmpl) = j.t; // the commit (`on` still clear)
+	if (vgx_tmpl_kernel_is_round(j.t.kernel)) {
+		const TmplStage r = tmplFirstRoundSizes(j);
+		if (r.stop()) { return r.st; }
+	}
+	ctx->tmpl.on = true;
+	*out_sizes = ctx->tmpl.total;
+	ctx->hostTotals->sizes = ctx->tmpl.total; // what vgx_tessellate_emit checks the caller's capacities against
 	return VGX_OK;
 }
 
@@ -2014,7 +2013,7 @@ int vgx_tessellate_count(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* dr
 	ctx->lastStage = 0;
 	int st = tryTemplate(ctx, ps, draws, ndraws, out_sizes, s);
 	if (st != VGX_OK) { return st; }
-	if (ctx->tmplOn) {
+	if (ctx->tmpl.on) {
 		ctx->lastPs = ps; ctx->lastDraws = draws; ctx->lastNDraws = ndraws; ctx->lastStage = 2;
 		return VGX_OK;
 	}
@@ -2303,7 +2302,7 @@ int vgx_stroke(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, con
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
 	ctx->lastStage = 0; // counted state ends here
-	ctx->tmplOn = false;
+	tmplDrop(ctx);
 	int st;
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
@@ -2352,7 +2351,7 @@ int dashPrepare(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, co
 	if (((uintptr_t)poly & 7u) || ((uintptr_t)subpaths & 7u) || ((uintptr_t)subpath_draw & 3u) || ((uintptr_t)dashes & 3u) || ((uintptr_t)pattern & 3u)) { return VGX_E_INVALID_ARG; }
 	if (nsubpaths > 0x7FFFFFFFull || ndraws > 0xFFFFFFFFull) { return VGX_E_RANGE; }
 	ctx->lastStage = 0;
-	ctx->tmplOn = false;
+	tmplDrop(ctx);
 	int st;
 	if ((st = ctx->dash.create(ctx, 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
@@ -2937,7 +2936,7 @@ int mergeCall(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, co
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
 	ctx->lastStage = 0;
-	ctx->tmplOn = false; // the mesh-table scratch is re-sized below
+	tmplDrop(ctx); // the mesh-table scratch is re-sized below
 	int st;
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
@@ -3113,7 +3112,7 @@ int vgx_get_failure_info(vgx_ctx* ctx, vgx_failure_info* out, void* stream)
 	out->reason = ctx->hostTotals->fail_reason;
 	out->aux = ctx->hostTotals->fail_aux;
 	out->segment = ctx->hostTotals->fail_segment;
-	out->segment_items = ctx->tmplOn ? 5u : ctx->optInst ? (ctx->instPeriod ? (ctx->instPermOn ? 4u : 1u) : (ctx->instGrouped ? (ctx->instClasses > 1 ? 3u : 2u) : 0u)) : 0u; // flatten mode chosen by the last count call
+	out->segment_items = ctx->tmpl.on ? 5u : ctx->optInst ? (ctx->instPeriod ? (ctx->instPermOn ? 4u : 1u) : (ctx->instGrouped ? (ctx->instClasses > 1 ? 3u : 2u) : 0u)) : 0u; // flatten mode chosen by the last count call
 	if (out->segment_items == 0u && ctx->lastPs && ctx->lastPs->thinStatic && ctx->optThinStatic) { out->segment_items = 6u; } // k_flatten_thin in k_flatten_build's place
 	for (int i = 0; i < 16; ++i) { out->prof[i] = ctx->hostTotals->prof[i]; }
 	return VGX_OK;
@@ -3125,7 +3124,7 @@ int vgx_set_static_batches(vgx_ctx* ctx, int enable)
 		return VGX_E_INVALID_ARG;
 	}
 	ctx->optTmplBatch = enable ? 1 : 0;
-	if (!enable && ctx->tmplIsBatch) { ctx->tmplOn = false; } // the next vgx_tessellate wants a count again
+	if (!enable && ctx->tmpl.isBatch) { tmplDrop(ctx); } // the next vgx_tessellate wants a count again
 	return VGX_OK;
 }
 

@@ -8,6 +8,7 @@
 #include "vgx_lane.h"
 
 #include "vgx_internal_types.h"
+#include "vgx_tmpl_plan.h"
 
 struct VgxFlattenArgs
 {
@@ -77,10 +78,6 @@ struct VgxStrokeArgs
 #ifndef VGX_TMPL_THREADS
 #define VGX_TMPL_THREADS 512   /* threads per workgroup of k_tmpl_emit */
 #endif
-#ifndef VGX_TMPL_MAX_TILE
-#define VGX_TMPL_MAX_TILE 2048 /* elements per tile = per workgroup (what its LDS stages hold); a multiple of VGX_TMPL_THREADS. Tiger x10k, same
-                                * box: 256 threads x 1024 elements 2.18 ms, 512 x 2048 2.06, 512 x 3072 2.15, 1024 x 4096 2.15, 128 x 1024 2.26 */
-#endif
 struct VgxTmplBuild // count pass: the first period's ordinary count + emit results -> template tables
 {
 	const vgx_draw* draws;       // the batch's first period
@@ -133,11 +130,11 @@ struct VgxTmplArgs // one step
 	const uint2* wg;             // [num_wg]
 	uint64_t num_wg;
 	vgx_sizes total;             // sizes of the whole batch
-	uint32_t general;            // stroke styles of the template: 0 = closed Miter AA / Thin (k_tmpl_emit), 1 = + open Miter, Butt / Square caps (k_tmpl_emit_open), 2 = any (k_tmpl_emit_general), 3 = + Round joins (k_tmpl_emit_round), 4 = closed Miter + closed Bevel only (k_tmpl_emit_bevel), 5 / 6 = 4 + closed / + open AA strokes with Round joins (k_tmpl_emit_round_aa / _open)
+	VgxTmplKernel kernel;        // which emit kernel the template needs (vgx_tmpl_plan.h)
 	// Round joins (templates of ONE class): the arc of every join is counted on the instance's TRANSFORMED polyline (stroker.cpp:1146, 1592), so the
 	// sizes of those meshes -- and with them every output place behind them -- belong to the instance. Per-step tables, written by
 	// vgx_launch_tmpl_round_sizes and read by k_tmpl_emit_round:
-	uint32_t num_round;          // Round-join stroke meshes per instance (VgxTmplMesh::pad[1] = the mesh's number among them + 1)
+	uint32_t num_round;          // Round-join stroke meshes per instance (VgxTmplMesh::round_no = the mesh's number among them + 1)
 	uint32_t num_round_elems;    // their elements per instance
 	const VgxTmplRoundMesh* trmesh; // [num_round + 1]
 	const uint2* tmsz;           // [meshes of the template] vertices, indices (Round joins: 0x80000000 | number among the Round-join meshes, 0): what the scan over the meshes reads
@@ -146,8 +143,8 @@ struct VgxTmplArgs // one step
 	VgxTmplMeshPlace* mplace;    // [ninst * meshes] per mesh of the batch: first vertex, first index in the BATCH (iplace set: inside its INSTANCE); vertices, indices
 	unsigned long long* itot;    // [ninst * 2] (per-instance shape of the sizes pass only, else null) vertices, indices of the instance
 	unsigned long long* iplace;  // [ninst * 2] ... first vertex, first index of the instance in the batch
-	// Round joins, several classes (round 6; the per-instance shape of the sizes pass only): class c's Round-join meshes are trmesh[cls[c].pad[1] ..
-	// cls[c + 1].pad[1]) (entry [nclasses]: all of them), an instance's tables lie at iinfo[k].m (mplace) and iinfo[k].rel (relem)
+	// Round joins, several classes (round 6; the per-instance shape of the sizes pass only): class c's Round-join meshes are trmesh[cls[c].round[VGX_TC_MESH0] ..
+	// cls[c + 1].round[VGX_TC_MESH0]) (entry [nclasses]: all of them), an instance's tables lie at iinfo[k].m (mplace) and iinfo[k].rel (relem)
 	const VgxTmplClass* cls;     // [nclasses + 1] (null: one class)
 	uint32_t round_lds;          // Round-join meshes of the largest class (k_tmpl_round_sizes_inst's LDS table)
 };
@@ -156,7 +153,7 @@ bool vgx_tmpl_round_per_instance(const VgxTmplArgs& a); // the sizes pass places
 void vgx_launch_tmpl_round_sizes(const VgxTmplArgs& a, Sum3* partial, hipStream_t s); // Round-join templates, in front of vgx_launch_tmpl_emit: the tables above, totals->sizes, VGX_E_NOSPACE against a.caps
 void vgx_launch_tmpl_mtab(const VgxTmplArgs& a, vgx_mesh* mtab, VgxMeshDesc* mdesc, hipStream_t s); // assembly armed: the whole batch's mesh table + mesh -> draw
 void vgx_launch_tmpl_check(const vgx_draw* draws, uint64_t ndraws, uint32_t npaths, VgxTotals* totals, hipStream_t s); // after vgx_launch_inst_detect
-void vgx_launch_tmpl_styles(const VgxTmplBuild& b, hipStream_t s);  // stroke styles of the template -> b.cls[nclasses].pad[0] (zeroed by the caller), needs mdesc only
+void vgx_launch_tmpl_styles(const VgxTmplBuild& b, hipStream_t s);  // stroke styles of the template -> VGX_TMPL_STYLES(b.cls, nclasses) (zeroed by the caller), needs mdesc only
 void vgx_launch_tmpl_classes(const VgxTmplBuild& b, hipStream_t s); // fills b.cls from the representatives' count + emit results
 void vgx_launch_tmpl_class_sums(const VgxTmplBuild& b, const vgx_draw_info* dinfo, const uint64_t* cmdPrefix, uint64_t numDraws, const vgx_sizes& all, unsigned long long* sums, hipStream_t s); // after vgx_launch_tmpl_classes: [nclasses + 1][5] prefixes in front of every class
 void vgx_launch_tmpl_build(const VgxTmplBuild& b, hipStream_t s);   // after vgx_launch_tmpl_classes
@@ -164,14 +161,10 @@ void vgx_launch_tmpl_hash(const vgx_draw* draws, uint64_t ndraws, uint64_t perio
 void vgx_launch_tmpl_check_cls(const vgx_draw* draws, uint64_t ndraws, uint64_t period, const uint32_t* inst_cls, const uint32_t* cls_rep, VgxTotals* totals, hipStream_t s);
 void vgx_launch_tmpl_emit(const VgxTmplArgs& a, hipStream_t s);
 #ifndef VGX_TMPL_RC_THREADS
-#define VGX_TMPL_RC_THREADS 512 /* k_tmpl_emit_round_aa (templates of closed strokes with Round joins): threads per workgroup, */
-#define VGX_TMPL_RC_TILE 2048   /* elements per tile */
+#define VGX_TMPL_RC_THREADS 512 /* k_tmpl_emit_round_aa (templates of closed strokes with Round joins): threads per workgroup (its tile: VGX_TMPL_RC_TILE) */
 #endif
 #ifndef VGX_TMPL_RC_WAVES
 #define VGX_TMPL_RC_WAVES 6     /* waves per SIMD its registers are limited for (80 VGPRs: three workgroups per CU) */
-#endif
-#ifndef VGX_TMPL_GENERAL_TILE
-#define VGX_TMPL_GENERAL_TILE 2048 /* tile size of templates that hold general strokes (the LDS stages of k_tmpl_emit_general) */
 #endif
 
 // merging two mesh sequences of a frame (vgx_merge.hip)

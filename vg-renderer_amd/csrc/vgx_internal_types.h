@@ -184,7 +184,8 @@ struct VgxTmplMesh // one mesh of the template. 64 bytes
 	float f0, f1;        // fills: fringe / 2 (the sign is per instance), -; strokes: hsw, hswAA (thin: fringe, fringe)
 	float l0[2], l1[2], l2[2]; // its first three LOCAL vertices: the fill orientation (stroker.cpp:721-723) is the sign of their transformed triangle
 	                           // (Round-join stroke meshes: l2[0] = the arc step da, l2[1] = bits of the mesh's first element among the Round-join elements)
-	uint32_t pad[2];     // [0]: the draw's fringe (bits); [1]: Round-join stroke meshes: the mesh's number among the instance's Round-join meshes + 1, else 0
+	uint32_t fringe_bits; // the draw's fringe (bits)
+	uint32_t round_no;    // Round-join stroke meshes: the mesh's number among the instance's Round-join meshes + 1, else 0
 };
 struct VgxTmplElem // one element (polyline vertex j of template mesh `mesh`), in processing order. 16 bytes
 {
@@ -224,8 +225,14 @@ struct VgxTmplClass // 40 bytes
 	uint64_t v0, i0; // first output vertex / index
 	uint32_t mesh0;  // first mesh
 	uint32_t tile0;  // first tile
-	uint32_t pad[2];
+	uint32_t round[2]; // Round-join templates (k_tmpl_round_classes), indexed by VGX_TC_*. (An array, not two named words: separate members
+	                   // tell the compiler more about aliasing, and k_tmpl_round_classes, which stores both, compiles to other code)
 };
+enum {
+	VGX_TC_ELEM0 = 0, // the class's first element among the template's Round-join elements; entry [classes]: VGX_TMPL_STYLES
+	VGX_TC_MESH0 = 1  // the class's first Round-join mesh in trmesh; entry [classes]: how many there are
+};
+#define VGX_TMPL_STYLES(cls, nclasses) ((cls)[nclasses].round[VGX_TC_ELEM0]) // the table's last entry keeps the template's VgxTmplStyle bits there (k_tmpl_styles; vgx_tmpl_plan.h)
 struct VgxTmplInst // multi-class batches: where instance k's output lies, and its class. 40 bytes
 {
 	uint64_t v, i;   // first output vertex / index of the instance (templates with Round joins: the per-step table iplace instead)

@@ -151,7 +151,7 @@ __global__ void k_tmpl_classes(VgxTmplBuild B)
 		r.v0 = lo < M ? B.mtab[lo].first_vertex : B.num_vertices;
 		r.i0 = lo < M ? B.mtab[lo].first_index : B.num_indices;
 		r.tile0 = tile0;
-		r.pad[0] = B.cls[c].pad[0]; r.pad[1] = 0; // (entry [nclasses]: the style bits k_tmpl_styles left there)
+		r.round[VGX_TC_ELEM0] = B.cls[c].round[VGX_TC_ELEM0]; r.round[VGX_TC_MESH0] = 0; // (entry [nclasses]: the style bits k_tmpl_styles left there)
 		B.cls[c] = r;
 		if (c > 0) {
 			const uint64_t e = r.elem0 - B.cls[c - 1].elem0;
@@ -190,12 +190,10 @@ __global__ __launch_bounds__(256) void k_tmpl_class_sums(VgxTmplBuild B, const v
 }
 __device__ __forceinline__ uint32_t tmpl_class_of_draw(const VgxTmplBuild& B, uint32_t draw) { return draw / B.period; }
 
-// which stroke styles the template holds -> cls[nclasses].pad[0]: bit 0 = open Miter strokes with Butt / Square caps, bit 1 = any other
-// stroke that is not closed Miter AA / Thin, bit 2 = Round joins, bit 3 = closed Bevel AA / Thin strokes (the host zeroes the table first;
-// k_tmpl_classes keeps the word)
+// which stroke styles the template holds -> VGX_TMPL_STYLES(cls, nclasses), VgxTmplStyle bits (the host zeroes the table first; k_tmpl_classes keeps the word)
 __device__ __forceinline__ bool tmpl_stroke_is_open_fast(uint32_t kindWord);
 __device__ __forceinline__ bool tmpl_stroke_is_closed_bevel(uint32_t kindWord);
-__device__ __forceinline__ bool tmpl_stroke_is_closed_round_aa(uint32_t kindWord); // bit 4
+__device__ __forceinline__ bool tmpl_stroke_is_closed_round_aa(uint32_t kindWord);
 // the meshes whose sizes depend on the transformed geometry: Round joins count their arc points there (stroker.cpp:1146, 1592);
 // thin strokes turn Round joins into Bevel ones (:318-327)
 __device__ __forceinline__ bool tmpl_is_round(uint32_t kindWord)
@@ -213,11 +211,11 @@ __global__ __launch_bounds__(256) void k_tmpl_styles(VgxTmplBuild B)
 		const uint32_t kw = B.mdesc[m].kind;
 		const uint32_t kind = VGX_MD_KIND(kw);
 		if (kind >= VGX_MESH_STROKE && !stroke_elem_is_simple(kind, VGX_MD_CLOSED(kw) != 0, VGX_MD_JOIN(kw))) {
-			f |= tmpl_stroke_is_open_fast(kw) ? 1u : (tmpl_stroke_is_closed_bevel(kw) ? 8u : ((VGX_MD_KIND(kw) == VGX_MESH_STROKE_AA && VGX_MD_JOIN(kw) == VGX_JOIN_ROUND) ? (VGX_MD_CLOSED(kw) ? 16u : 32u) : 2u)); // (bits 4 / 5: closed / open AA strokes with Round joins)
+			f |= tmpl_stroke_is_open_fast(kw) ? VGX_TS_OPEN_MITER : (tmpl_stroke_is_closed_bevel(kw) ? VGX_TS_CLOSED_BEVEL : ((VGX_MD_KIND(kw) == VGX_MESH_STROKE_AA && VGX_MD_JOIN(kw) == VGX_JOIN_ROUND) ? (VGX_MD_CLOSED(kw) ? VGX_TS_ROUND_AA_CLOSED : VGX_TS_ROUND_AA_OPEN) : VGX_TS_OTHER));
 		}
-		if (tmpl_is_round(kw)) { f |= 4u; }
+		if (tmpl_is_round(kw)) { f |= VGX_TS_ROUND; }
 	}
-	if (f) { atomicOr(&B.cls[B.nclasses].pad[0], f); }
+	if (f) { atomicOr(&VGX_TMPL_STYLES(B.cls, B.nclasses), f); }
 }
 
 __global__ __launch_bounds__(256) void k_tmpl_meshes(VgxTmplBuild B)
@@ -242,16 +240,16 @@ __global__ __launch_bounds__(256) void k_tmpl_meshes(VgxTmplBuild B)
 		const float2* v = B.poly + md.poly_first;
 		const float2 a = v[0], b = v[md.poly_n > 1 ? 1 : 0], c = v[md.poly_n > 2 ? 2 : 0];
 		t.l0[0] = a.x; t.l0[1] = a.y; t.l1[0] = b.x; t.l1[1] = b.y; t.l2[0] = c.x; t.l2[1] = c.y;
-		t.pad[0] = __float_as_uint(pr.f2); t.pad[1] = 0; // the draw's fringe (general strokes: Butt-cap fringes, thin strokes)
+		t.fringe_bits = __float_as_uint(pr.f2); t.round_no = 0; // the draw's fringe (general strokes: Butt-cap fringes, thin strokes)
 		B.tmesh[m] = t;
 		B.tmtab[m] = mt;
 		B.tmsz[m] = make_uint2(mt.num_vertices, mt.num_indices);
 	}
 }
 
-// Round-join meshes numbered in mesh order (a device scan over the template's meshes; after k_tmpl_meshes): tmesh[m].pad[1] = number + 1,
+// Round-join meshes numbered in mesh order (a device scan over the template's meshes; after k_tmpl_meshes): tmesh[m].round_no = number + 1,
 // trmesh[number] = (mesh, its first element among the instance's Round-join elements); trmesh[count] = (~0, the total); the count ->
-// cls[nclasses].pad[1]. Only launched for templates that hold Round joins (k_tmpl_meshes leaves pad[1] = 0).
+// cls[nclasses].round[VGX_TC_MESH0]. Only launched for templates that hold Round joins (k_tmpl_meshes leaves round_no = 0).
 struct OpTmplRoundIndex
 {
 	VgxTmplBuild B;
@@ -267,7 +265,7 @@ struct OpTmplRoundIndex
 	{
 		const VgxMeshDesc md = B.mdesc[m];
 		if (!tmpl_is_round(md.kind)) { return; }
-		B.tmesh[m].pad[1] = (uint32_t)e.a + 1u;
+		B.tmesh[m].round_no = (uint32_t)e.a + 1u;
 		B.tmsz[m] = make_uint2(0x80000000u | (uint32_t)e.a, 0u);
 		VgxTmplRoundMesh r; r.mesh = (uint32_t)m; r.elem0 = (uint32_t)e.b;
 		B.trmesh[e.a] = r;
@@ -281,23 +279,23 @@ struct OpTmplRoundIndex
 	{
 		VgxTmplRoundMesh r; r.mesh = ~0u; r.elem0 = (uint32_t)tot.b;
 		B.trmesh[tot.a] = r;
-		B.cls[B.nclasses].pad[1] = (uint32_t)tot.a;
+		B.cls[B.nclasses].round[VGX_TC_MESH0] = (uint32_t)tot.a;
 	}
 };
 
-// Several classes: where each class's Round-join meshes begin in trmesh (they are numbered across the concatenated template) -> cls[c].pad[1],
-// and the element number of its first one -> cls[c].pad[0], c < nclasses (entry [nclasses] keeps the totals / the style bits). One thread.
+// Several classes: where each class's Round-join meshes begin in trmesh (they are numbered across the concatenated template) -> cls[c].round[VGX_TC_MESH0],
+// and the element number of its first one -> cls[c].round[VGX_TC_ELEM0], c < nclasses (entry [nclasses] keeps the totals / the style bits). One thread.
 __global__ void k_tmpl_round_classes(VgxTmplBuild B)
 {
-	const uint32_t R = B.cls[B.nclasses].pad[1];
+	const uint32_t R = B.cls[B.nclasses].round[VGX_TC_MESH0];
 	for (uint32_t c = 0; c < B.nclasses; ++c) {
 		uint32_t lo = 0, hi = R; // first Round-join mesh at or behind the class's first mesh
 		while (lo < hi) {
 			const uint32_t mid = (lo + hi) >> 1;
 			if (B.trmesh[mid].mesh < B.cls[c].mesh0) { lo = mid + 1; } else { hi = mid; }
 		}
-		B.cls[c].pad[1] = lo;
-		B.cls[c].pad[0] = B.trmesh[lo].elem0; // (trmesh[R] = the total)
+		B.cls[c].round[VGX_TC_MESH0] = lo;
+		B.cls[c].round[VGX_TC_ELEM0] = B.trmesh[lo].elem0; // (trmesh[R] = the total)
 	}
 }
 
@@ -544,7 +542,7 @@ __device__ __forceinline__ void tmpl_stroke_elem_open(const TmplOut& O, uint32_t
 			const V2 lh = v2mul(l, hsw);
 			const V2 lhaa = v2mul(l, hswAA);
 			if (cap == VGX_CAP_BUTT) { // :1422-1447, 1858-1886
-				const V2 daa = v2mul(d, __uint_as_float(tmm->pad[0])); // the draw's fringe
+				const V2 daa = v2mul(d, __uint_as_float(tmm->fringe_bits)); // the draw's fringe
 				q0 = first ? v2add(p1, v2sub(lhaa, daa)) : v2add(p1, v2add(lhaa, daa));
 				q1 = v2add(p1, lh);
 				q2 = v2sub(p1, lh);
@@ -1136,7 +1134,7 @@ __device__ __forceinline__ void tmpl_emit_body(const VgxTmplArgs& A)
 				const uint4 mi = minfoOf(er.mesh);
 				vOff = mi.x; iOff = mi.y;
 				if (j == 0 && A.meshes_out) { tmpl_mesh_out_placed(A, P, er.mesh, mi); }
-				if (tm.pad[1] != 0) {
+				if (tm.round_no != 0) {
 					const uint2 bk = *relemOf(__float_as_uint(tm.l2[1]) + j);
 					rpl.placed = true;
 					tmpl_round_unword(bk.x, bk.y, &rpl.b, &rpl.k, &rpl.nvPrev, &rpl.prevInner);
@@ -1146,7 +1144,7 @@ __device__ __forceinline__ void tmpl_emit_body(const VgxTmplArgs& A)
 			} else if (j == 0 && A.meshes_out) { tmpl_mesh_out(A, P, er.mesh); }
 			const uint32_t ibase = meshBase ? meshBase[er.mesh - P.cmesh0] : 0u;
 			tmpl_elem_emit<KIND, 0>(O, j, tm.kind, N, vOff, iOff, ibase, kind < VGX_MESH_STROKE ? dr.fill_color : dr.stroke_color, f0, tm.f1, tmpl_xf(xf, vt[j]), dir(j), dir, vtx,
-				__uint_as_float(tm.pad[0]), P.tdraws + tm.drawk, A.tmesh + er.mesh, rpl);
+				__uint_as_float(tm.fringe_bits), P.tdraws + tm.drawk, A.tmesh + er.mesh, rpl);
 		}
 		return;
 	}
@@ -1187,9 +1185,9 @@ __device__ __forceinline__ void tmpl_emit_body(const VgxTmplArgs& A)
 		TmplRec r;
 		r.ibase = ibase; r.n = tm.n; r.v_off = tm.v_off; r.i_off = tm.i_off;
 		r.kind = (tm.kind & 0xFFFFu) | ((tm.drawk - dA) << 16); r.color = kind < VGX_MESH_STROKE ? d->fill_color : d->stroke_color; r.f0 = tm.f0; r.f1 = tm.f1;
-		if (KIND >= 2) { s_fringe[tid] = __uint_as_float(tm.pad[0]); }
+		if (KIND >= 2) { s_fringe[tid] = __uint_as_float(tm.fringe_bits); }
 		if (ROUND) { // Round-join meshes: the mesh's sizes (closing bridge), arc step (stroker.cpp:1398; the closed-stroke kernel's routine) and first table word, once per mesh
-			const bool rj = tm.pad[1] != 0; // (both from the mesh record: no load behind the first barrier)
+			const bool rj = tm.round_no != 0; // (both from the mesh record: no load behind the first barrier)
 			s_rmesh[tid] = make_float4(__uint_as_float(mi.z), __uint_as_float(mi.w), rj ? tm.l2[0] : 0.0f, rj ? tm.l2[1] : __uint_as_float(~0u));
 		}
 		if (kind == VGX_MESH_FILL_AA) { r.f0 = tmpl_fill_aa(tmpl_draw_xf(d), make_float2(tm.l0[0], tm.l0[1]), make_float2(tm.l1[0], tm.l1[1]), make_float2(tm.l2[0], tm.l2[1]), tm.f0); }
@@ -1478,7 +1476,7 @@ __global__ __launch_bounds__(256) void k_tmpl_round_sizes_inst(VgxTmplArgs A)
 	if (A.iinfo) {
 		const VgxTmplInst ii = A.iinfo[inst];
 		const VgxTmplClass c0 = A.cls[ii.cls], c1 = A.cls[ii.cls + 1];
-		R0 = c0.pad[1]; R = c1.pad[1] - R0; cmesh0 = c0.mesh0; M = c1.mesh0 - cmesh0;
+		R0 = c0.round[VGX_TC_MESH0]; R = c1.round[VGX_TC_MESH0] - R0; cmesh0 = c0.mesh0; M = c1.mesh0 - cmesh0;
 		tdraws = A.tdraws + (uint64_t)ii.cls * A.period;
 		relemAt = ii.rel; mplaceAt = ii.m;
 	}
@@ -1765,11 +1763,14 @@ void vgx_launch_tmpl_emit(const VgxTmplArgs& a, hipStream_t s)
 {
 	const uint64_t blocks = a.wg ? a.num_wg : a.ninst * a.tiles_per_inst; // the host checked < 2^31
 	if (!blocks) { return; }
-	if (a.general == 6) { hipLaunchKernelGGL(k_tmpl_emit_round_aa_open, dim3((unsigned)blocks), dim3(VGX_TMPL_RC_THREADS), 0, s, a); }
-	else if (a.general == 5) { hipLaunchKernelGGL(k_tmpl_emit_round_aa, dim3((unsigned)blocks), dim3(VGX_TMPL_RC_THREADS), 0, s, a); }
-	else if (a.general == 4) { hipLaunchKernelGGL(k_tmpl_emit_bevel, dim3((unsigned)blocks), dim3(VGX_TMPL_THREADS), 0, s, a); }
-	else if (a.general == 3) { hipLaunchKernelGGL(k_tmpl_emit_round, dim3((unsigned)blocks), dim3(VGX_TMPL_G_THREADS), 0, s, a); }
-	else if (a.general == 2) { hipLaunchKernelGGL(k_tmpl_emit_general, dim3((unsigned)blocks), dim3(VGX_TMPL_G_THREADS), 0, s, a); }
-	else if (a.general == 1) { hipLaunchKernelGGL(k_tmpl_emit_open, dim3((unsigned)blocks), dim3(VGX_TMPL_THREADS), 0, s, a); }
-	else { hipLaunchKernelGGL(k_tmpl_emit, dim3((unsigned)blocks), dim3(VGX_TMPL_THREADS), 0, s, a); }
+	const dim3 grid((unsigned)blocks);
+	switch (a.kernel) {
+	case VGX_TK_EMIT: hipLaunchKernelGGL(k_tmpl_emit, grid, dim3(VGX_TMPL_THREADS), 0, s, a); break;
+	case VGX_TK_OPEN: hipLaunchKernelGGL(k_tmpl_emit_open, grid, dim3(VGX_TMPL_THREADS), 0, s, a); break;
+	case VGX_TK_GENERAL: hipLaunchKernelGGL(k_tmpl_emit_general, grid, dim3(VGX_TMPL_G_THREADS), 0, s, a); break;
+	case VGX_TK_ROUND: hipLaunchKernelGGL(k_tmpl_emit_round, grid, dim3(VGX_TMPL_G_THREADS), 0, s, a); break;
+	case VGX_TK_BEVEL: hipLaunchKernelGGL(k_tmpl_emit_bevel, grid, dim3(VGX_TMPL_THREADS), 0, s, a); break;
+	case VGX_TK_ROUND_AA: hipLaunchKernelGGL(k_tmpl_emit_round_aa, grid, dim3(VGX_TMPL_RC_THREADS), 0, s, a); break;
+	case VGX_TK_ROUND_AA_OPEN: hipLaunchKernelGGL(k_tmpl_emit_round_aa_open, grid, dim3(VGX_TMPL_RC_THREADS), 0, s, a); break;
+	}
 }
