@@ -84,10 +84,11 @@ enum { VGX_JOIN_MITER = 0, VGX_JOIN_ROUND = 1, VGX_JOIN_BEVEL = 2 };
  * same counts, same vertices; for callers that compare index streams with an SSE build of the reference. Positions stay
  * the scalar build's (the SSE variant computes them with rcpps / rsqrtps approximations). */
 #define VGX_FILL_INDEX_ORDER_SSE 0x100u
-/* PathType::Concave fills (VG_FILL_FLAGS, include/vg/vg.h:229; ctxFillPath* src/vg.cpp:3133-3178): libtess2 triangulates them on
- * the CPU side of the caller, so a draw with VGX_FILL_CONCAVE and WITHOUT VGX_FILL_ENABLE produces no mesh in vgx_tessellate; its
- * mesh is built with vgx_flatten_* (contours) + libtess2 + vgx_concave_move / vgx_concave_emit and put at the draw's place in
- * the frame by vgx_merge. vgx_cmdlist_decode emits concave FillPath* commands as such draws (VGX_FILL_AA / VGX_FILL_EVEN_ODD say
+/* PathType::Concave fills (VG_FILL_FLAGS, include/vg/vg.h:229; ctxFillPath* src/vg.cpp:3133-3178): a draw with VGX_FILL_CONCAVE and
+ * WITHOUT VGX_FILL_ENABLE produces no mesh in vgx_tessellate. Two routes build it and vgx_merge puts it at the draw's place in the
+ * frame: triangles, as the reference makes them -- vgx_flatten_* (contours) + libtess2 on the CPU side of the caller + vgx_concave_move
+ * / vgx_concave_emit --, or, for a frame that goes to vgx_raster_concave, contour meshes without libtess2 and without leaving the
+ * device -- vgx_flatten + vgx_concave_contours. vgx_cmdlist_decode emits concave FillPath* commands as such draws (VGX_FILL_AA / VGX_FILL_EVEN_ODD say
  * which strokerConcaveFillEnd[AA] call and FillRule the reference would use). */
 #define VGX_FILL_CONCAVE 0x10u
 #define VGX_FILL_EVEN_ODD 0x20u
@@ -172,7 +173,15 @@ typedef struct vgx_mesh {
 } vgx_mesh;
 enum { VGX_MESH_FILL = 0, VGX_MESH_FILL_AA = 1, VGX_MESH_STROKE = 2, VGX_MESH_STROKE_AA = 3, VGX_MESH_STROKE_AA_THIN = 4,
        VGX_MESH_CONCAVE_FILL_AA = 5 /* vgx_concave_emit */, VGX_MESH_TRILIST = 6 /* vgx_cmdlist_out::tri_meshes */,
-       VGX_MESH_TEXT = 7 /* vgx_text_quads */ };
+       VGX_MESH_TEXT = 7 /* vgx_text_quads */, VGX_MESH_CONTOURS = 8 /* vgx_concave_contours: directed edges, below */ };
+/* A mesh of kind VGX_MESH_CONTOURS holds the contours of a concave fill as an edge soup, for a consumer that fills by winding number
+ * (vgx_raster_concave). Vertices are contour points in pos, colours in color. idx holds one directed edge per PAIR of mesh-local
+ * indices: edge e is idx[first_index + 2e] -> idx[first_index + 2e + 1], e < num_indices / 2; a trailing odd index is ignored and an
+ * edge with an index >= num_vertices is skipped. Bit 0 of the low 28 bits of subpath_kind is the fill rule: 0 = NonZero, 1 = EvenOdd.
+ * No contour structure is stored: winding needs none. Everything that treats meshes as vertex and index ranges (vgx_mesh_bounds,
+ * vgx_merge*, vgx_cache_localize / _submit / _update) handles the kind like any other; the consumers of TRIANGLES -- vgx_pick,
+ * vgx_raster, vgx_raster_frame, vgx_raster_textured, vgx_raster_painted -- skip such a mesh whole. */
+#define VGX_CONTOUR_EVEN_ODD 0x1u
 
 /* Totals of a batch. Filled by the *_count calls (host struct). */
 typedef struct vgx_sizes {
@@ -886,6 +895,48 @@ int vgx_raster_painted(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* m
 int vgx_paint_tables(const struct vgx_paint* paints, uint32_t n, struct vgx_paint* gradients, uint32_t cap_gradients,
                      struct vgx_paint* patterns, uint32_t cap_patterns);
 
+/* ---- concave fills in the image: vgx_concave_contours -> vgx_merge -> vgx_raster_concave ------------------------------------------------
+ * The calls above draw triangles and skip a mesh of kind VGX_MESH_CONTOURS whole (no bin entry, no stamp). vgx_raster_concave is
+ * vgx_raster_painted word for word -- sample, triangle coverage, colour, blend, order, draw scissor, stamp, In / Out, sampled and painted
+ * meshes, mesh_bounds, target, and the VGX_E_GROWN / VGX_E_RANGE / VGX_E_INVALID_ARG protocol and ranking -- with ONE difference: a mesh
+ * of kind VGX_MESH_CONTOURS is filled by the winding number of its edges, below. It is the compute form of stencil-then-cover, exact in
+ * integers. A frame without such a mesh gives vgx_raster_painted's bytes and status. As everywhere in this section every implementation
+ * gives the same bytes; there is no tolerance.
+ *
+ * Edges. Edge e of mesh m is idx[first_index + 2e] -> idx[first_index + 2e + 1], e < num_indices / 2. A trailing odd index is ignored;
+ *   an edge with an index >= num_vertices is skipped, so nothing outside the mesh's own vertex range is ever read.
+ * Winding at the sample (px, py). Binary64 WITHOUT FMA, coordinates widened first. W is a signed 32-bit sum over the valid edges u -> v:
+ *   up = u.y < py && py <= v.y, dn = v.y < py && py <= u.y. Neither holds for a horizontal edge or with a NaN in y: the edge adds 0.
+ *   E = the canonical edge value of u -> v exactly as the triangle rule of vgx_raster defines it: lo, hi ordered by (x, then y),
+ *   g = (hi.x-lo.x)*(py-lo.y) - (hi.y-lo.y)*(px-lo.x), E = g when u is lo, else -g, and 0 when u == v bit for bit. An edge and its
+ *   reverse give exact negatives. up && E < 0 adds +1; dn && E > 0 adds -1 (a NaN E adds 0). Integer addition is associative, so every
+ *   decomposition of the work gives the same W, and coincident opposite edges cancel exactly, whatever rounds.
+ * Covered iff both hold:
+ *   - the sample lies in the closed box B of the mesh: px >= B.minx && px <= B.maxx && py >= B.miny && py <= B.maxy, a NaN bound making
+ *     it false. B is the mesh's entry of mesh_bounds. A caller's table is therefore part of the input here, not only a prefilter: it must
+ *     hold what vgx_mesh_bounds gives for the stream -- as the parameter has always required -- and what it holds decides. With
+ *     mesh_bounds == NULL the call computes exactly those boxes. For closed rings (what vgx_concave_contours writes) the clause changes
+ *     nothing, every sample with W != 0 lies inside; it is there because an open edge soup would otherwise cover a half-line to its right;
+ *   - W != 0 (NonZero), or (W & 1) != 0 (EvenOdd: bit 0 of the low 28 bits of subpath_kind, VGX_CONTOUR_EVEN_ODD).
+ * Why these inequalities. They make the rule the triangle rule's twin: the region takes ties on its right and bottom edges, as the tie
+ *   rule of vgx_raster does, and in exact arithmetic the winding of a triangle's three edges equals the triangle's coverage at EVERY
+ *   sample, on edges, at vertices and on horizontal edges included. So the interior of vgx_concave_contours' AA pair and its fringe
+ *   share every inner edge bit for bit, and a sample on that seam is drawn exactly once.
+ * Colour. The mesh is flat: c = color[first_vertex]; a mesh with no vertices does nothing. A covered sample is treated as a covered
+ *   sample of vertex colour c in every rule downstream: blended under a colour draw; stamping S = d under a Clip draw (type 3); tested
+ *   In / Out like any sample; painted under a draw of type 1 / 2 with vc = c; drawn with c under a Textured draw (type 0), since the
+ *   kind carries no UV and is never a sampled mesh. Both scissors apply as to any mesh.
+ * Order. The mesh takes ONE place in painter's order, at its mesh index: a pixel sees at most one sample of it.
+ * Status. The element count of VGX_E_RANGE becomes triangles plus edges (of the contour meshes that have a bin entry); a contour mesh has
+ *   bin entries like any mesh, by its box. Everything else as vgx_raster_painted. Positions that are NaN: as vgx_mesh_bounds says, the
+ *   box of such a mesh is unspecified, and so is what the mesh covers; nothing outside image and scissor is written in any case.
+ * Host return values, out of scope (streams written under vgx_set_assembly; hit testing of contour meshes): as vgx_raster_painted.
+ * Side effects. As vgx_raster_painted, on the same scratch, and a third bit per 16 x 16 tile of the image (which tiles a contour mesh
+ *   reaches) in a buffer only this call allocates; vgx_scratch_bytes counts it. A counted state survives. */
+int vgx_raster_concave(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
+                       uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state, const vgx_raster_textures* tex,
+                       const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* dev_status, void* stream);
+
 /* ---- incremental update (beyond the reference): vgx_cache_submit -> vgx_cache_layout -> [vgx_pick -> edit -> vgx_cache_update]* ----
  * Moving or recolouring an instance of a submitted frame changes nothing of the frame's structure: a cached mesh has a fixed size, so
  * the instance keeps its vertex, index and mesh ranges; indices, mesh records, draw commands and UVs do not depend on the transform.
@@ -992,6 +1043,39 @@ int vgx_concave_emit(vgx_ctx* ctx, const float* contour_verts, uint64_t num_cont
                      const vgx_concave_fill* fills, uint64_t nfills, const float* tess_pos, const uint16_t* tess_idx,
                      const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
 
+/* ---- concave fills without libtess2 (beyond the reference): vgx_flatten -> vgx_concave_contours -> vgx_merge -> vgx_raster_concave ----
+ * A triangulation is needed only when triangles go to a graphics pipeline. A rasteriser that owns the pixel loop fills from the contours
+ * by winding number (vgx_raster_concave), so a concave fill needs no triangles, no libtess2 and no host visit: vgx_concave_contours turns
+ * the flattened sub-paths of the frame's concave draws into meshes of kind VGX_MESH_CONTOURS on the device.
+ * Inputs, all DEVICE pointers: poly, subpaths, draw_info = what vgx_flatten(..., apply_transform = 1, ...) wrote for the frame's draws
+ * (poly, subpaths and draw_info 8-byte aligned), and the ndraws vgx_draw records themselves (4-byte aligned).
+ * Which draws make meshes. Draw d with VGX_FILL_CONCAVE and without VGX_FILL_ENABLE, with at least one sub-path, of which NONE has fewer
+ *   than 3 vertices (the reference's return, src/vg.cpp:3136-3138: one short sub-path drops the whole fill). Every other draw makes
+ *   nothing. Let V be the sum of the vertex counts of d's sub-paths.
+ * Without VGX_FILL_AA: one mesh of kind VGX_MESH_CONTOURS. Its V vertices are the polyline vertices in order, every colour is fill_color;
+ *   each sub-path contributes its closed ring of edges (i, i + 1), the closing edge (last, first) included: 2V indices, the pair of
+ *   vertex i at 2i. The rule bit VGX_CONTOUR_EVEN_ODD comes from VGX_FILL_EVEN_ODD. draw = d.
+ * With VGX_FILL_AA: two meshes, in the index order of strokerConcaveFillEndAA: fringe, then interior.
+ *   Mesh 1, kind VGX_MESH_CONCAVE_FILL_AA, holds ONLY the fringe: 2V vertices and 6V indices, bit for bit what vgx_concave_emit writes
+ *   for the same contours with num_tess_vertices = num_tess_indices = 0 and the draw's fringe and fill_color; the draw's own sub-paths
+ *   play the part of the boundary contours.
+ *   Mesh 2, kind VGX_MESH_CONTOURS: its V vertices are what vgx_concave_move gives for those contours, its rings are the same rings,
+ *   its colour is fill_color, its rule bit as above. draw = d on both.
+ * Meshes come out ascending by draw, streams dense: the result is sequence `b` of vgx_merge as it stands.
+ * Where this differs from the reference. libtess2's first pass (TESS_BOUNDARY_CONTOURS) follows the boundary of the FILLED REGION; this
+ *   route follows the INPUT contours. For a simple path (no self-intersection, no overlap between sub-paths) the geometry is the same.
+ *   For the rest, fringe and half-fringe inset are per input contour, so an edge that lies inside the filled region gets a fringe too.
+ *   Non-AA fills have no such difference: the winding number of the input contours IS the fill rule's definition. A caller who needs the
+ *   reference's mesh keeps the libtess2 route (vgx_concave_move / vgx_concave_emit).
+ * Asynchronous, with the dev_sizes / dev_status protocol of vgx_concave_emit: capacities are checked on the device; on VGX_E_NOSPACE the
+ *   need is in dev_sizes (num_meshes, num_vertices, num_indices) and nothing is written past a capacity; a mesh above 65536 vertices
+ *   (V > 65536, with AA V > 32768) sets VGX_E_MESH_TOO_LARGE; sub-paths of a draw that do not lie back to back in poly (vgx_flatten
+ *   writes them so) set VGX_E_INVALID_ARG. With any status but VGX_OK no vertex and no index is written. Host return values:
+ *   VGX_E_INVALID_ARG for null pointers and for the misalignments vgx_mesh_out names, VGX_E_RANGE for ndraws >= 2^32 - 1. Ends a counted
+ *   state, like vgx_concave_emit. */
+int vgx_concave_contours(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                         const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
+
 /* ---- merging external meshes into a frame -----------------------------------------------------------------
  * The reference appends every mesh to the frame in submission order (createDrawCommand_VertexColor, src/vg.cpp:5207-5244).
  * vgx_merge builds that order from two mesh sequences that are each sorted by draw: `a` = what vgx_tessellate[_emit] wrote for
@@ -1079,7 +1163,7 @@ int vgx_text_quads(vgx_ctx* ctx, const float* quads, uint64_t nquads, const vgx_
  * compare before merging (:5359-5460); the generation changes whenever the reference sets m_ForceNewDrawCommand /
  * m_ForceNewClipCommand between two draws (scissor changes, PopState onto a different scissor, EndClip, ResetClip).
  * Concave fills (PathType::Concave) become draws with VGX_FILL_CONCAVE [| VGX_FILL_AA] [| VGX_FILL_EVEN_ODD] and no
- * VGX_FILL_ENABLE: vgx_tessellate makes no mesh for them, the caller builds it (vgx_flatten_* -> libtess2 -> vgx_concave_move /
+ * VGX_FILL_ENABLE: vgx_tessellate makes no mesh for them, the caller builds it (vgx_flatten -> vgx_concave_contours, or vgx_flatten_* -> libtess2 -> vgx_concave_move /
  * vgx_concave_emit) and vgx_merge puts it at the draw's place in the frame.
  * IndexedTriList commands become draws with VGX_FILL_TRILIST; their meshes come back in vgx_cmdlist_out::tri_*.
  * Commands without an equivalent here are counted in num_skipped and otherwise ignored: Text / TextBox (vgx_cmdlist_decode_text

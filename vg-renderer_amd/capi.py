@@ -37,6 +37,8 @@ STROKE_ENABLE, STROKE_AA, STROKE_THIN = 0x1, 0x2, 0x4
 
 MESH_FILL, MESH_FILL_AA, MESH_STROKE, MESH_STROKE_AA, MESH_STROKE_AA_THIN, MESH_CONCAVE_FILL_AA, MESH_TRILIST = 0, 1, 2, 3, 4, 5, 6
 MESH_TEXT = 7  # vgx_text_quads
+MESH_CONTOURS = 8  # vgx_concave_contours: directed edges in index pairs, filled by vgx_raster_concave alone
+CONTOUR_EVEN_ODD = 1  # vgx_mesh.subpath_kind of such a mesh: bit 0 is the fill rule
 
 
 def stroke_flags(cap, join, aa=True, thin=False):
@@ -282,6 +284,8 @@ VGX_SYMBOLS = {
                                      C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
     "vgx_raster_painted": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.POINTER(RasterTextures),
                                     C.POINTER(RasterPaints), C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
+    "vgx_raster_concave": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.POINTER(RasterTextures),
+                                    C.POINTER(RasterPaints), C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
     "vgx_paint_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "vgx_cache_layout": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_cache_update": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
@@ -318,6 +322,8 @@ VGX_SYMBOLS = {
     "vgx_concave_move": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "vgx_concave_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_concave_contours": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "vgx_cmdlist_decode": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CmdListState), C.POINTER(CmdListOut)]),
     "vgx_cmdlist_decode_text": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CmdListState), C.POINTER(CmdListOut), C.POINTER(CmdListText)]),
     "vgx_text_quads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_uint32,

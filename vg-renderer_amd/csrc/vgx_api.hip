@@ -19,6 +19,7 @@
 #include "vgx_dash.h"
 #include "vgx_update.h"
 #include "vgx_raster.h"
+#include "vgx_concave_lane.h"
 #include "vgx_scratch.h"
 #include <vector>
 #include <algorithm>
@@ -132,6 +133,7 @@ struct vgx_ctx
 	Buf<uint64_t> elemPrefix, elemPrefixS;
 	Buf<VgxMeshPrep> mprep;
 	Buf<vgx_mesh> mtab;
+	Buf<uint64_t> contourPrefix;         // vgx_concave_contours: two exclusive prefixes over the draws (contour vertices, output vertices), [ndraws + 1] each
 	Buf<VgxTotals> totals;
 	Buf<uint32_t> textTiles;             // vgx_text_quads: first run of every tile of quads (vgx_text.hip)
 	Buf<uint8_t> cullFlags; DevBuf cullPartial; // vgx_cache_cull (vgx_bounds.hip): kept flag per instance, the compaction scan's slice sums (views: as `partial`). Its own: a counted state survives the call
@@ -142,8 +144,9 @@ struct vgx_ctx
 	// whose entries outgrew the tables ends with VGX_E_GROWN and the next one grows first). Its own: a counted state survives the call
 	Buf<uint32_t> rasMeshEntries, rasKeys, rasVals, rasSortedKeys, rasSortedVals; Buf<uint64_t> rasMeshFirst; Buf<unsigned long long> rasState; Buf<float> rasBounds;
 	Buf<VgxRasterMeshState> rasFrameMesh; // the frame-level calls: what every mesh of the range does under its draw (vgx_raster.h)
-	Buf<uint32_t> rasTileTex;             // vgx_raster_textured and vgx_raster_painted: one bit per tile of the image, "a sampled mesh reaches it"
-	Buf<uint32_t> rasTilePaint;           // vgx_raster_painted alone: the same for "a painted mesh reaches it"
+	Buf<uint32_t> rasTileTex;             // vgx_raster_textured and the levels above it: one bit per tile of the image, "a sampled mesh reaches it"
+	Buf<uint32_t> rasTilePaint;           // vgx_raster_painted and vgx_raster_concave: the same for "a painted mesh reaches it"
+	Buf<uint32_t> rasTileContour;         // vgx_raster_concave alone: the same for "a contour mesh reaches it"
 	DevBuf rasSortTemp, rasPartial;      // rasPartial: slice sums (views: as `partial`)
 	HostMirror<unsigned long long> ras;
 	uint32_t optPickGrid;                // workgroups of k_pick_tris (VGX_PICK_GRID)
@@ -447,6 +450,52 @@ struct OpConcaveFills // concave fills: vertices / indices of every fill's mesh 
 		totals->sizes.num_vertices = t.a;
 		totals->sizes.num_indices = t.b;
 		if (t.a > caps.vertices || t.b > caps.indices || nfills > caps.meshes) { set_status(totals, VGX_E_NOSPACE); }
+	}
+};
+
+struct OpContourDraws // vgx_concave_contours: per draw its contour vertices, output vertices and meshes -> offsets + mesh records
+{
+	const vgx_subpath* subs;
+	const vgx_draw_info* dinfo;
+	const vgx_draw* draws;
+	uint64_t ndraws;
+	uint64_t* contourPrefix; // [ndraws + 1]
+	uint64_t* vertexPrefix;  // [ndraws + 1]
+	vgx_mesh* meshesOut;     // caller's table (may be null)
+	VgxTotals* totals;
+	VgxCaps caps;
+	__device__ uint64_t size() const { return ndraws; }
+	__device__ Sum3 load(uint64_t i) const
+	{
+		Sum3 r = sum3_zero();
+		const vgx_draw d = draws[i];
+		uint64_t V;
+		const int made = contours_draw_counts(d, dinfo[i], subs, &V);
+		if (made < 0) { set_status(totals, VGX_E_INVALID_ARG); }
+		if (made <= 0) { return r; }
+		const bool aa = (d.fill_flags & VGX_FILL_AA) != 0u;
+		if ((aa ? 2 * V : V) > 65536u) { set_status(totals, VGX_E_MESH_TOO_LARGE); } // uint16 indices
+		r.a = V; r.b = aa ? 3 * V : V; r.c = aa ? 2u : 1u;
+		return r;
+	}
+	__device__ void store(uint64_t i, Sum3 e) const
+	{
+		contourPrefix[i] = e.a; vertexPrefix[i] = e.b;
+		const vgx_draw d = draws[i];
+		uint64_t V;
+		if (contours_draw_counts(d, dinfo[i], subs, &V) <= 0 || !meshesOut) { return; }
+		vgx_mesh m[2];
+		const uint32_t n = contours_draw_meshes(d, (uint32_t)i, V, e.b, 2 * e.a + 3 * (e.b - e.a), m);
+		for (uint32_t k = 0; k < n; ++k) { if (e.c + k < caps.meshes) { meshesOut[e.c + k] = m[k]; } }
+	}
+	__device__ void finish(Sum3 t) const
+	{
+		contourPrefix[ndraws] = t.a; vertexPrefix[ndraws] = t.b;
+		const uint64_t indices = 2 * t.a + 3 * (t.b - t.a);
+		totals->sizes.num_meshes = t.c;
+		totals->sizes.num_vertices = t.b;
+		totals->sizes.num_indices = indices;
+		if (t.b > caps.vertices || indices > caps.indices || t.c > caps.meshes) { set_status(totals, VGX_E_NOSPACE); }
 	}
 };
 
@@ -2742,7 +2791,7 @@ int vgx_raster_reserve(vgx_ctx* ctx, uint64_t num_meshes, uint64_t num_bin_entri
 
 namespace {
 
-// The four calls are one body; `level` (VGX_RL_*, vgx_raster.h) says which pointers count and which kernel family runs
+// The five calls are one body; `level` (VGX_RL_*, vgx_raster.h) says which pointers count and which kernel family runs
 int rasterCall(int level, vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
                const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
@@ -2816,6 +2865,11 @@ int rasterCall(int level, vgx_ctx* ctx, const vgx_cache_desc* frame, const float
 			noteHip(ctx, hipMemsetAsync(ctx->rasTilePaint.p, 0, words * sizeof(uint32_t), s));
 			f.tile_paint = ctx->rasTilePaint.ptr();
 		}
+		if (level >= VGX_RL_CONCAVE) {
+			if ((st = ensure(ctx, ctx->rasTileContour, words + 1)) != VGX_OK) { return st; }
+			noteHip(ctx, hipMemsetAsync(ctx->rasTileContour.p, 0, words * sizeof(uint32_t), s));
+			f.tile_contour = ctx->rasTileContour.ptr();
+		}
 		noteHip(ctx, vgx_launch_raster_frame(f, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
 	}
 	// status and entry count to the mirror, for the next call (never waited for)
@@ -2851,6 +2905,13 @@ int vgx_raster_painted(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* m
 }
 
 // HOST only, no context: the decoder's paint list scattered by handle into the two tables vgx_raster_painted indexes; holes marked
+int vgx_raster_concave(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
+                       const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target,
+                       uint32_t* dev_status, void* stream)
+{
+	return rasterCall(VGX_RL_CONCAVE, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, dev_status, stream);
+}
+
 int vgx_paint_tables(const vgx_paint* paints, uint32_t n, vgx_paint* gradients, uint32_t cap_gradients, vgx_paint* patterns, uint32_t cap_patterns)
 {
 	if ((n && !paints) || (cap_gradients && !gradients) || (cap_patterns && !patterns)) { return VGX_E_INVALID_ARG; }
@@ -3054,6 +3115,44 @@ int vgx_concave_emit(vgx_ctx* ctx, const float* contour_verts, uint64_t num_cont
 	a.totals = ctx->totals.ptr();
 	vgx_launch_concave_emit(a, s);
 	mark(ctx, s, "concave_emit");
+	publish(ctx, dev_sizes, dev_status, s);
+	return launchStatus(ctx);
+}
+
+int vgx_concave_contours(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                         const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || !out || !out->pos || !out->color || !out->idx || meshOutMisaligned(out) || (ndraws && (!poly || !subpaths || !draw_info || !draws))) {
+		return VGX_E_INVALID_ARG;
+	}
+	if (((uintptr_t)poly & 7u) || ((uintptr_t)subpaths & 7u) || ((uintptr_t)draw_info & 7u) || ((uintptr_t)draws & 3u)) { return VGX_E_INVALID_ARG; }
+	if (ndraws >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	hipStream_t s = (hipStream_t)stream;
+	markBegin(ctx, s);
+	ctx->lastStage = 0;
+	int st;
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->contourPrefix, 2 * (ndraws + 1))) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
+	OpContourDraws op;
+	op.subs = subpaths; op.dinfo = draw_info; op.draws = draws; op.ndraws = ndraws;
+	op.contourPrefix = ctx->contourPrefix.ptr(); op.vertexPrefix = ctx->contourPrefix.ptr() + ndraws + 1;
+	op.meshesOut = out->meshes; op.totals = ctx->totals.ptr();
+	op.caps = ctx->caps;
+	op.caps.vertices = out->cap_vertices; op.caps.indices = out->cap_indices; op.caps.meshes = out->meshes ? out->cap_meshes : ~0ull;
+	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, ndraws);
+	mark(ctx, s, "scan_contour_draws");
+	if (ndraws) {
+		VgxContoursArgs a;
+		memset(&a, 0, sizeof(a));
+		a.poly = poly; a.subpaths = subpaths; a.draw_info = draw_info; a.draws = draws; a.ndraws = ndraws;
+		a.contour_prefix = op.contourPrefix; a.vertex_prefix = op.vertexPrefix;
+		a.pos = out->pos; a.color = out->color; a.idx = out->idx; a.totals = ctx->totals.ptr();
+		vgx_launch_concave_contours(a, s);
+		mark(ctx, s, "concave_contours");
+	}
 	publish(ctx, dev_sizes, dev_status, s);
 	return launchStatus(ctx);
 }

@@ -1,5 +1,5 @@
 // vgx_concave.hip -- the stroker's own arithmetic inside strokerConcaveFillEndAA (reference src/stroker.cpp:868-1006)
-// for a batch of concave fills; libtess2 stays with the caller on the CPU.
+// for a batch of concave fills; libtess2 stays with the caller on the CPU. At the end: vgx_concave_contours, the route without it.
 //
 // The reference alternates libtess2 and its own loops:
 //   (1) tessTesselate(TESS_BOUNDARY_CONTOURS) of the added contours                              [caller, CPU]
@@ -112,7 +112,34 @@ __global__ __launch_bounds__(256) void k_concave_interior(VgxConcaveArgs A)
 	}
 }
 
+// vgx_concave_contours: one lane per contour vertex of the mesh-making draws, whatever draw it belongs to -- the owner by a search in
+// the scan's prefix -- writes what the draw's meshes hold for that vertex (contours_emit_vertex: at most 3 vertices and 8 indices).
+// The sizes were checked against the capacities by the scan: any status but VGX_OK and nothing is written
+__global__ __launch_bounds__(256) void k_concave_contours(VgxContoursArgs A)
+{
+	if (A.totals->status != VGX_OK) { return; }
+	const uint64_t total = A.contour_prefix[A.ndraws];
+	for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (uint64_t)gridDim.x * blockDim.x) {
+		uint64_t lo = 0, hi = A.ndraws; // the last draw whose first contour vertex is <= e: draws without one share their successor's
+		while (hi - lo > 1) {
+			const uint64_t mid = (lo + hi) >> 1;
+			if (A.contour_prefix[mid] <= e) { lo = mid; } else { hi = mid; }
+		}
+		const vgx_draw d = A.draws[lo];
+		const vgx_draw_info di = A.draw_info[lo];
+		const uint64_t V = A.contour_prefix[lo + 1] - A.contour_prefix[lo], fv = A.vertex_prefix[lo];
+		// indices follow from the two prefixes: 2 per contour vertex, 6 more per contour vertex of an AA draw (which has 2 more vertices)
+		const uint64_t fi = 2 * A.contour_prefix[lo] + 3 * (fv - A.contour_prefix[lo]);
+		contours_emit_vertex(A.poly, A.subpaths + di.first_subpath, di.num_subpaths, d, e - A.contour_prefix[lo], V, fv, fi, A.pos, A.color, A.idx);
+	}
+}
+
 } // namespace
+
+void vgx_launch_concave_contours(const VgxContoursArgs& a, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_concave_contours, dim3(1024), dim3(256), 0, s, a);
+}
 
 void vgx_launch_concave_move(const VgxConcaveArgs& a, hipStream_t s)
 {

@@ -516,7 +516,7 @@ int vgxt_pick(const vgx_cache_desc* frame, const float* mesh_bounds, const vgx_p
 			const uint16_t* ip = frame->idx + me.first_index;
 			const float* pp = frame->pos + 2 * me.first_vertex;
 			const uint32_t* cp = frame->color + me.first_vertex;
-			for (uint32_t t = 0; t < me.num_indices / 3u; ++t) {
+			for (uint32_t t = 0; t < vgx_pick_mesh_triangles(me); ++t) {
 				const uint32_t i0 = ip[3 * t], i1 = ip[3 * t + 1], i2 = ip[3 * t + 2];
 				if (!vgx_pick_tri_valid(i0, i1, i2, me.num_vertices)) { continue; }
 				if ((Q.flags & VGX_PICK_SKIP_TRANSPARENT) && vgx_pick_tri_transparent(cp[i0], cp[i1], cp[i2])) { continue; }
@@ -534,8 +534,51 @@ int vgxt_pick(const vgx_cache_desc* frame, const float* mesh_bounds, const vgx_p
 }
 
 #include "vgx_raster.h"
+#include "vgx_concave_lane.h"
 
 extern "C" {
+
+// vgx_concave_contours on the host: the functions of vgx_concave_lane.h draw after draw and contour vertex after contour vertex. HOST
+// pointers. Returns what the device call returns on the host; *status and *sizes (may be NULL) receive what it leaves in dev_status and
+// dev_sizes. With a status other than VGX_OK no vertex and no index is written
+int vgxt_concave_contours(const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                          const vgx_mesh_out* out, vgx_sizes* sizes, uint32_t* status)
+{
+	if (!out || !out->pos || !out->color || !out->idx || (ndraws && (!poly || !subpaths || !draw_info || !draws))) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)out->pos & 7u) || ((uintptr_t)out->color & 3u) || ((uintptr_t)out->idx & 1u) || ((uintptr_t)out->meshes & 7u)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)poly & 7u) || ((uintptr_t)subpaths & 7u) || ((uintptr_t)draw_info & 7u) || ((uintptr_t)draws & 3u)) { return VGX_E_INVALID_ARG; }
+	if (ndraws >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	uint32_t st = VGX_OK;
+	uint64_t nc = 0, nv = 0, nm = 0;
+	for (int pass = 0; pass < 2 && st == VGX_OK; ++pass) { // sizes and records, then -- the capacities hold -- the streams
+		nc = nv = nm = 0;
+		for (uint64_t i = 0; i < ndraws; ++i) {
+			const vgx_draw& d = draws[i];
+			uint64_t V;
+			const int made = contours_draw_counts(d, draw_info[i], subpaths, &V);
+			if (made < 0 && st == VGX_OK) { st = VGX_E_INVALID_ARG; }
+			if (made <= 0) { continue; }
+			const bool aa = (d.fill_flags & VGX_FILL_AA) != 0u;
+			if ((aa ? 2 * V : V) > 65536u && st == VGX_OK) { st = VGX_E_MESH_TOO_LARGE; }
+			const uint64_t fi = 2 * nc + 3 * (nv - nc);
+			if (pass == 0) {
+				vgx_mesh m[2];
+				const uint32_t n = contours_draw_meshes(d, (uint32_t)i, V, nv, fi, m);
+				for (uint32_t k = 0; k < n; ++k) { if (out->meshes && nm + k < out->cap_meshes) { out->meshes[nm + k] = m[k]; } }
+			} else {
+				for (uint64_t c = 0; c < V; ++c) {
+					contours_emit_vertex(poly, subpaths + draw_info[i].first_subpath, draw_info[i].num_subpaths, d, c, V, nv, fi, out->pos, out->color, out->idx);
+				}
+			}
+			nc += V; nv += aa ? 3 * V : V; nm += aa ? 2u : 1u;
+		}
+		const uint64_t ni = 2 * nc + 3 * (nv - nc);
+		if (st == VGX_OK && (nv > out->cap_vertices || ni > out->cap_indices || (out->meshes && nm > out->cap_meshes))) { st = VGX_E_NOSPACE; }
+		if (sizes) { memset(sizes, 0, sizeof(*sizes)); sizes->num_meshes = nm; sizes->num_vertices = nv; sizes->num_indices = ni; }
+	}
+	if (status) { *status = st; }
+	return VGX_OK;
+}
 
 // vgx_raster on the host: the functions of vgx_raster.h in a plain loop over the meshes of the range, their triangles and the pixels
 // of each triangle's box inside the scissor; with the call's contract (mesh_bounds may be NULL: the boxes are computed first; given,
@@ -564,7 +607,7 @@ int vgxt_raster(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t 
 	for (uint64_t m = mesh_begin; m < end; ++m) {
 		const vgx_mesh me = frame->meshes[m];
 		VgxRasterRect r;
-		if (!vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, t.scissor, true, &r)) { continue; }
+		if (!vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, t.scissor, VGX_RL_PLAIN, &r)) { continue; }
 		const uint16_t* ip = frame->idx + me.first_index;
 		const float* pp = frame->pos + 2 * me.first_vertex;
 		const uint32_t* cp = frame->color + me.first_vertex;
@@ -593,6 +636,35 @@ int vgxt_raster(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t 
 // The frame-level calls on the host: vgxt_raster's loop with the per-draw state of vgx_raster.h, a stamp image of its own and, as far as
 // the level (VGX_RL_*) goes, the sampling and the paint functions. HOST pointers throughout, the images' pixels, the UV stream and the
 // paint tables included. The meshes are looked at twice: first for an invalid one (nothing may be written then), then drawn.
+// One contour mesh of vgx_raster_concave: per pixel of the box inside the mesh's rectangle, W over the valid edges, then the flush
+static void raster_contour_mesh(const vgx_cache_desc* frame, const vgx_mesh& me, const float* box, const VgxRasterMeshState& ms, const VgxRasterPaint& pr,
+                                const vgx_raster_target& t, uint32_t* stamp)
+{
+	uint32_t a0, a1, b0, b1;
+	if (!vgx_raster_span(box[0], box[2], t.x0, ms.rect[0], ms.rect[2], &a0, &a1) || !vgx_raster_span(box[1], box[3], t.y0, ms.rect[1], ms.rect[3], &b0, &b1)) { return; }
+	const uint16_t* ip = frame->idx + me.first_index;
+	const float* pp = frame->pos + 2 * me.first_vertex;
+	const uint32_t c = frame->color[me.first_vertex];
+	const auto pfetch = [&pr](uint32_t x, uint32_t y) { return pr.im.pixels[(uint64_t)y * pr.im.stride + x]; };
+	for (uint32_t j = b0; j <= b1; ++j) {
+		for (uint32_t i = a0; i <= a1; ++i) {
+			const double px = (double)(t.x0 + (int32_t)i) + 0.5, py = (double)(t.y0 + (int32_t)j) + 0.5;
+			int32_t W = 0;
+			for (uint32_t k = 0; k < me.num_indices / 2u; ++k) {
+				const uint32_t i0 = ip[2 * k], i1 = ip[2 * k + 1];
+				VgxRasterTri T;
+				if (i0 < me.num_vertices && i1 < me.num_vertices && vgx_raster_contour_edge(v2(pp[2 * i0], pp[2 * i0 + 1]), v2(pp[2 * i1], pp[2 * i1 + 1]), &T)) {
+					W += vgx_raster_contour_winding(T, px, py);
+				}
+			}
+			if (!vgx_raster_contour_covered(W, me.subpath_kind, box, px, py)) { continue; }
+			uint32_t* const p = t.pixels + (uint64_t)j * t.stride + i;
+			const uint32_t d = vgx_raster_contour_pixel(c, ms.pad, pr, ms.mode, ms.f, ms.n, px, py, stamp + (size_t)j * t.width + i, *p, pfetch);
+			if (d != *p) { *p = d; }
+		}
+	}
+}
+
 static int raster_frame_loop(int level, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
                              const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status)
 {
@@ -648,7 +720,11 @@ static int raster_frame_loop(int level, const vgx_cache_desc* frame, const float
 		if (ms.pad & VGX_RT_PAINTED) { vgx_raster_paint_record(((ms.pad & VGX_RT_GRADIENT) ? gradients : patterns)[ms.pad & 0xFFFFu], images, &pr); }
 		const auto pfetch = [&pr](uint32_t x, uint32_t y) { return pr.im.pixels[(uint64_t)y * pr.im.stride + x]; };
 		VgxRasterRect r;
-		if (ms.mode == VGX_RF_NOTHING || !vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, ms.rect, level == VGX_RL_FRAME, &r)) { continue; }
+		if (ms.mode == VGX_RF_NOTHING || !vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, ms.rect, level, &r)) { continue; }
+		if (ms.pad & VGX_RT_CONTOUR) { // the winding number of every sample the box can hold, over all the mesh's edges, then rule and colour
+			raster_contour_mesh(frame, me, (mesh_bounds ? mesh_bounds : own) + 4 * m, ms, pr, t, stamp);
+			continue;
+		}
 		const uint16_t* ip = frame->idx + me.first_index;
 		const float* pp = frame->pos + 2 * me.first_vertex;
 		const uint32_t* cp = frame->color + me.first_vertex;
@@ -696,6 +772,23 @@ int vgxt_raster_textured(const vgx_cache_desc* frame, const float* mesh_bounds, 
                          const vgx_raster_textures* tex, const vgx_raster_target* target, uint32_t* status)
 {
 	return raster_frame_loop(VGX_RL_TEXTURED, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, nullptr, target, status);
+}
+
+int vgxt_raster_concave(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                        const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status)
+{
+	return raster_frame_loop(VGX_RL_CONCAVE, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, status);
+}
+
+// the winding number of the sample (px, py) over the n directed edges u[k] -> v[k] (2 floats each), for the tests of the predicate
+int32_t vgxt_raster_winding(const float* u, const float* v, uint64_t n, double px, double py)
+{
+	int32_t W = 0;
+	for (uint64_t k = 0; k < n; ++k) {
+		VgxRasterTri T;
+		if (vgx_raster_contour_edge(v2(u[2 * k], u[2 * k + 1]), v2(v[2 * k], v[2 * k + 1]), &T)) { W += vgx_raster_contour_winding(T, px, py); }
+	}
+	return W;
 }
 
 int vgxt_raster_painted(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,

@@ -211,6 +211,24 @@ struct VgxConcaveArgs
 void vgx_launch_concave_move(const VgxConcaveArgs& a, hipStream_t s);
 void vgx_launch_concave_emit(const VgxConcaveArgs& a, hipStream_t s);
 
+// vgx_concave_contours: the flatten output and the draws, the three per-draw exclusive prefixes of the size scan ([ndraws + 1] each:
+// contour vertices of the mesh-making draws, output vertices, output meshes), and the streams
+struct VgxContoursArgs
+{
+	const float* poly;
+	const vgx_subpath* subpaths;
+	const vgx_draw_info* draw_info;
+	const vgx_draw* draws;
+	uint64_t ndraws;
+	const uint64_t* contour_prefix;
+	const uint64_t* vertex_prefix;
+	float* pos;
+	uint32_t* color;
+	uint16_t* idx;
+	const VgxTotals* totals;
+};
+void vgx_launch_concave_contours(const VgxContoursArgs& a, hipStream_t s);
+
 // text runs (vgx_text.hip)
 struct VgxTextArgs
 {
@@ -472,7 +490,7 @@ struct VgxRasterMeshState;
 struct VgxRasterFrameArgs
 {
 	VgxRasterArgs R;
-	int32_t level;                    // VGX_RL_FRAME, VGX_RL_TEXTURED or VGX_RL_PAINTED
+	int32_t level;                    // VGX_RL_FRAME .. VGX_RL_CONCAVE
 	uint32_t num_draws;
 	const vgx_draw* draws; const vgx_draw_state* draw_state; // [num_draws], checked by the host
 	VgxRasterMeshState* mesh_state;   // [nrange] (context scratch)
@@ -486,6 +504,8 @@ struct VgxRasterFrameArgs
 	const vgx_paint* patterns;        // [num_patterns]
 	uint32_t num_gradients, num_patterns;
 	uint32_t* tile_paint;             // [(sentinel + 31) / 32] as tile_tex: a painted mesh has an entry there (context scratch)
+	// at VGX_RL_CONCAVE, else zero
+	uint32_t* tile_contour;           // [(sentinel + 31) / 32] as tile_tex: a contour mesh has an entry there (context scratch)
 };
 hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
 

@@ -17,6 +17,9 @@ VGX_HD bool vgx_pick_in_box(float px, float py, float minx, float miny, float ma
 	return px >= minx && px <= maxx && py >= miny && py <= maxy;
 }
 
+// ---- the triangles of a mesh: a mesh of kind VGX_MESH_CONTOURS holds edge pairs and is never hit ------------------------------
+VGX_HD uint32_t vgx_pick_mesh_triangles(const vgx_mesh& me) { return (me.subpath_kind >> 28) == VGX_MESH_CONTOURS ? 0u : me.num_indices / 3u; }
+
 // ---- point in triangle -------------------------------------------------------------------------------------------------
 // The triangle's own box first (cheap, and what makes the mesh-box prefilter exact), then the signs of the three edge expressions
 // against the sign of the area, in binary64. A NaN vertex passes or fails the box test depending on which side of min / max it sits,

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void k_pick_meshes(VgxPickArgs A)
 	__syncthreads();
 	const uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (m >= A.num_meshes) { return; }
-	const uint32_t tris = A.meshes[m].num_indices / 3u;
+	const uint32_t tris = vgx_pick_mesh_triangles(A.meshes[m]);
 	const float4 box = ((const float4*)A.mesh_bounds)[m];
 	bool cand = false;
 	if (tris) {

@@ -153,23 +153,30 @@ VGX_HD bool vgx_raster_kind_has_uv(uint32_t subpathKind)
 	return k == VGX_MESH_TEXT || k == VGX_MESH_TRILIST;
 }
 
-// Bin entries of a mesh: the tiles its box can reach inside the scissor (a rectangle of tiles). skipUvKinds: a mesh of kind TEXT /
-// TRILIST has none
+// the kind that holds directed edges, not triangles: drawn by vgx_raster_concave, skipped whole by every call below it
+VGX_HD bool vgx_raster_kind_is_contours(uint32_t subpathKind) { return (subpathKind >> 28) == VGX_MESH_CONTOURS; }
+
+// ---- the calls: vgx_raster < vgx_raster_frame < vgx_raster_textured < vgx_raster_painted < vgx_raster_concave (include/vgx.h) -------
+// One loop on the host and one kernel family on the device serve the frame-level calls; what differs is the level: which kinds are
+// drawn, which meshes are sampled or painted, and which tables are read (vgx_raster_mesh_state below). VGX_RL_PLAIN is vgx_raster, for
+// the argument check and the kinds alone
+enum { VGX_RL_PLAIN = 0, VGX_RL_FRAME = 1, VGX_RL_TEXTURED = 2, VGX_RL_PAINTED = 3, VGX_RL_CONCAVE = 4 };
+
+// elements of a mesh: triangles, or the edges of a contour mesh
+VGX_HD uint32_t vgx_raster_mesh_elements(const vgx_mesh& me) { return vgx_raster_kind_is_contours(me.subpath_kind) ? me.num_indices / 2u : me.num_indices / 3u; }
+
+// Bin entries of a mesh: the tiles its box can reach inside the scissor (a rectangle of tiles). Below VGX_RL_TEXTURED a mesh of kind
+// TEXT / TRILIST has none, below VGX_RL_CONCAVE a mesh of kind CONTOURS has none
 struct VgxRasterRect { uint32_t tx0, ty0, tx1, ty1; }; // inclusive
-VGX_HD bool vgx_raster_mesh_tiles(const vgx_mesh& me, const float* box, int32_t x0, int32_t y0, const uint32_t* scissor, bool skipUvKinds, VgxRasterRect* r)
+VGX_HD bool vgx_raster_mesh_tiles(const vgx_mesh& me, const float* box, int32_t x0, int32_t y0, const uint32_t* scissor, int level, VgxRasterRect* r)
 {
-	if ((skipUvKinds && vgx_raster_kind_has_uv(me.subpath_kind)) || me.num_indices < 3u) { return false; }
+	if (level < VGX_RL_TEXTURED && vgx_raster_kind_has_uv(me.subpath_kind)) { return false; }
+	if (vgx_raster_kind_is_contours(me.subpath_kind) ? (level < VGX_RL_CONCAVE || me.num_vertices == 0u || me.num_indices < 2u) : me.num_indices < 3u) { return false; }
 	uint32_t i0, i1, j0, j1;
 	if (!vgx_raster_span(box[0], box[2], x0, scissor[0], scissor[2], &i0, &i1) || !vgx_raster_span(box[1], box[3], y0, scissor[1], scissor[3], &j0, &j1)) { return false; }
 	r->tx0 = i0 / VGX_RASTER_TILE; r->tx1 = i1 / VGX_RASTER_TILE; r->ty0 = j0 / VGX_RASTER_TILE; r->ty1 = j1 / VGX_RASTER_TILE;
 	return true;
 }
-
-// ---- the frame-level calls: vgx_raster_frame < vgx_raster_textured < vgx_raster_painted (include/vgx.h) --------------------------
-// One loop on the host and one kernel family on the device serve the three; what differs is the level: which kinds are drawn, which
-// meshes are sampled or painted, and which tables are read (vgx_raster_mesh_state below). VGX_RL_PLAIN is vgx_raster, for the
-// argument check alone
-enum { VGX_RL_PLAIN = 0, VGX_RL_FRAME = 1, VGX_RL_TEXTURED = 2, VGX_RL_PAINTED = 3 };
 
 // ---- per-draw scissors and clip regions (every level) ---------------------------------------------------------------------------
 #define VGX_RASTER_STAMP_NONE 0xFFFFFFFFu // S of a pixel no clip mesh has touched; clip_first_draw of a draw without a region
@@ -180,6 +187,8 @@ enum { VGX_RF_PLAIN = 0, VGX_RF_IN = 1, VGX_RF_OUT = 2, VGX_RF_STAMP = 3, VGX_RF
 #define VGX_RT_GRADIENT 0x20000u // a draw of type 1: the handle names a gradient
 #define VGX_RT_PATTERN  0x40000u // a draw of type 2: the handle names a pattern
 #define VGX_RT_PAINTED  (VGX_RT_GRADIENT | VGX_RT_PATTERN)
+#define VGX_RT_CONTOUR  0x80000u // kind CONTOURS at VGX_RL_CONCAVE: the mesh's elements are edges; beside the paint flags, never beside SAMPLED
+#define VGX_RT_FLUSH    0x100000u // in a tile record only: the element behind a contour mesh's last edge
 // Per mesh of the range (context scratch of the frame-level calls only). rect = the target's scissor cut by the draw's, in image
 // pixels, half open; f, n = the region of a tested mesh, f = the mesh's draw for VGX_RF_STAMP
 struct VgxRasterMeshState { uint32_t mode, f, n, pad; uint32_t rect[4]; }; // 32 bytes
@@ -387,12 +396,10 @@ VGX_HD void vgx_raster_paint_record(const vgx_paint& p, const vgx_raster_image* 
 
 // The triangle of a mesh of a GRADIENT draw on the pixel whose sample is (px, py): fs_color_gradient.sc, mix(inner, outer, t) with the
 // alpha times the vertex alpha; vertex RGB is not used
-VGX_HD uint32_t vgx_raster_gradient_pixel(const VgxRasterTri& T, const VgxRasterPaint& P, uint32_t mode, uint32_t f, uint32_t n, double px, double py, uint32_t S, uint32_t dst)
+// ... from the vertex alpha on: what a covered sample of vertex alpha va becomes
+VGX_HD uint32_t vgx_raster_gradient_shade(const VgxRasterPaint& P, uint32_t va, double px, double py, uint32_t dst)
 {
-	if (mode != VGX_RF_PLAIN && !vgx_raster_stamp_pass(S, f, n, mode == VGX_RF_IN ? 0u : 1u)) { return dst; }
-	double E[3], sum, qx, qy;
-	if (!vgx_raster_cover(T, px, py, E, &sum)) { return dst; }
-	const uint32_t va = vgx_raster_channel(T, 3, E, sum);
+	double qx, qy;
 	if (va == 0u) { return dst; } // a == div255(g_A * 0) == 0
 	vgx_raster_paint_coord(P.m, px, py, &qx, &qy);
 	const double t = vgx_raster_gradient_t(P.g.params, qx, qy);
@@ -401,29 +408,92 @@ VGX_HD uint32_t vgx_raster_gradient_pixel(const VgxRasterTri& T, const VgxRaster
 	return vgx_raster_blend(dst, vgx_raster_mix8(P.g.inner & 255u, P.g.outer & 255u, t), vgx_raster_mix8((P.g.inner >> 8) & 255u, (P.g.outer >> 8) & 255u, t),
 	                        vgx_raster_mix8((P.g.inner >> 16) & 255u, (P.g.outer >> 16) & 255u, t), a);
 }
+VGX_HD uint32_t vgx_raster_gradient_pixel(const VgxRasterTri& T, const VgxRasterPaint& P, uint32_t mode, uint32_t f, uint32_t n, double px, double py, uint32_t S, uint32_t dst)
+{
+	if (mode != VGX_RF_PLAIN && !vgx_raster_stamp_pass(S, f, n, mode == VGX_RF_IN ? 0u : 1u)) { return dst; }
+	double E[3], sum;
+	if (!vgx_raster_cover(T, px, py, E, &sum)) { return dst; }
+	return vgx_raster_gradient_shade(P, vgx_raster_channel(T, 3, E, sum), px, py, dst);
+}
 
 // The triangle of a mesh of an IMAGE PATTERN draw: fs_image_pattern.sc, the texel rule of vgx_raster_textured at (u, v) = the paint
 // coordinate, modulated by the interpolated vertex colour (the pattern's tint). No UV of the stream is read
+// ... at a covered sample; vc(ch) gives the vertex colour's channel ch there
+template <class Fetch, class Channel>
+VGX_HD uint32_t vgx_raster_pattern_shade(const VgxRasterPaint& P, double px, double py, uint32_t dst, Fetch fetch, Channel vc)
+{
+	double qx, qy, U, V;
+	vgx_raster_paint_coord(P.m, px, py, &qx, &qy);
+	if (!vgx_raster_texcoord(qx, P.im.width, &U) || !vgx_raster_texcoord(qy, P.im.height, &V)) { return dst; }
+	const uint32_t tc = vgx_raster_sample(P.im, U, V, fetch);
+	const uint32_t a = vgx_raster_div255(vc(3) * (tc >> 24));
+	if (a == 0u) { return dst; }
+	return vgx_raster_blend(dst, vgx_raster_div255(vc(0) * (tc & 255u)), vgx_raster_div255(vc(1) * ((tc >> 8) & 255u)), vgx_raster_div255(vc(2) * ((tc >> 16) & 255u)), a);
+}
 template <class Fetch>
 VGX_HD uint32_t vgx_raster_pattern_pixel(const VgxRasterTri& T, const VgxRasterPaint& P, uint32_t mode, uint32_t f, uint32_t n, double px, double py, uint32_t S,
                                          uint32_t dst, Fetch fetch)
 {
 	if (mode != VGX_RF_PLAIN && !vgx_raster_stamp_pass(S, f, n, mode == VGX_RF_IN ? 0u : 1u)) { return dst; }
-	double E[3], sum, qx, qy, U, V;
+	double E[3], sum;
 	if (!vgx_raster_cover(T, px, py, E, &sum)) { return dst; }
-	vgx_raster_paint_coord(P.m, px, py, &qx, &qy);
-	if (!vgx_raster_texcoord(qx, P.im.width, &U) || !vgx_raster_texcoord(qy, P.im.height, &V)) { return dst; }
-	const uint32_t tc = vgx_raster_sample(P.im, U, V, fetch);
-	const uint32_t a = vgx_raster_div255(vgx_raster_channel(T, 3, E, sum) * (tc >> 24));
-	if (a == 0u) { return dst; }
-	return vgx_raster_blend(dst, vgx_raster_div255(vgx_raster_channel(T, 0, E, sum) * (tc & 255u)), vgx_raster_div255(vgx_raster_channel(T, 1, E, sum) * ((tc >> 8) & 255u)),
-	                        vgx_raster_div255(vgx_raster_channel(T, 2, E, sum) * ((tc >> 16) & 255u)), a);
+	return vgx_raster_pattern_shade(P, px, py, dst, fetch, [&](int ch) { return vgx_raster_channel(T, ch, E, sum); });
+}
+
+// ---- at the concave level: a mesh of kind VGX_MESH_CONTOURS is filled by winding number (include/vgx.h) ---------------------------
+// The record of one directed edge u -> v lives in a VgxRasterTri: e[0] and the NEG / ZERO flags of edge 0 hold the canonical edge
+// value of u -> v (vgx_raster_edge with positive = true), miny = u.y, maxy = v.y, minx = the smaller x. false: the edge adds 0 at
+// every sample (horizontal, or a NaN in y)
+VGX_HD bool vgx_raster_contour_edge(V2 u, V2 v, VgxRasterTri* T)
+{
+	if (!(u.y < v.y || v.y < u.y)) { return false; }
+	T->flags = vgx_raster_edge(u, v, true, 0, &T->e[0]);
+	T->minx = u.x < v.x ? u.x : v.x; T->miny = u.y; T->maxy = v.y;
+	return true;
+}
+
+// what the edge adds to W at the sample (px, py)
+VGX_HD int32_t vgx_raster_contour_winding(const VgxRasterTri& T, double px, double py)
+{
+	const double uy = (double)T.miny, vy = (double)T.maxy;
+	const bool up = uy < py && py <= vy, dn = vy < py && py <= uy;
+	if (!up && !dn) { return 0; }
+	const double E = vgx_raster_edge_value(T.e[0], T.flags, 0, px, py);
+	return up ? (E < 0.0 ? 1 : 0) : (E > 0.0 ? -1 : 0);
+}
+
+// can the edge add anything at a sample of rows [py0, py1] and columns up to px1?
+VGX_HD bool vgx_raster_contour_edge_reaches(const VgxRasterTri& T, double py0, double py1, double px1)
+{
+	const double lo = (double)(T.miny < T.maxy ? T.miny : T.maxy), hi = (double)(T.miny < T.maxy ? T.maxy : T.miny);
+	return lo < py1 && hi >= py0 && (double)T.minx <= px1;
+}
+
+// covered: inside the closed box of the mesh's vertices, and the fill rule on W
+VGX_HD bool vgx_raster_contour_covered(int32_t W, uint32_t subpathKind, const float* box, double px, double py)
+{
+	if (!(px >= (double)box[0] && px <= (double)box[2] && py >= (double)box[1] && py <= (double)box[3])) { return false; }
+	return (subpathKind & VGX_CONTOUR_EVEN_ODD) ? (W & 1) != 0 : W != 0;
+}
+
+// A covered sample of a contour mesh of the flat colour c: a covered sample of vertex colour c in every rule of the levels below.
+// pad = the mesh state's (VGX_RT_GRADIENT / VGX_RT_PATTERN or neither); *S is the pixel's stamp
+template <class Fetch>
+VGX_HD uint32_t vgx_raster_contour_pixel(uint32_t c, uint32_t pad, const VgxRasterPaint& P, uint32_t mode, uint32_t f, uint32_t n, double px, double py, uint32_t* S,
+                                         uint32_t dst, Fetch fetch)
+{
+	if (mode == VGX_RF_STAMP) { *S = f; return dst; }
+	if (mode != VGX_RF_PLAIN && !vgx_raster_stamp_pass(*S, f, n, mode == VGX_RF_IN ? 0u : 1u)) { return dst; }
+	if (pad & VGX_RT_GRADIENT) { return vgx_raster_gradient_shade(P, c >> 24, px, py, dst); }
+	if (pad & VGX_RT_PATTERN) { return vgx_raster_pattern_shade(P, px, py, dst, fetch, [c](int ch) { return (c >> (8 * ch)) & 255u; }); }
+	if ((c >> 24) == 0u) { return dst; }
+	return vgx_raster_blend(dst, c & 255u, (c >> 8) & 255u, (c >> 16) & 255u, c >> 24);
 }
 
 // ---- what a mesh does at a level -----------------------------------------------------------------------------------------------------
 // The state of mesh `me` under its draw (me.draw < num_draws is the caller's check, at every level and whatever the kind). Every level:
 // mode, region and rectangle. From VGX_RL_TEXTURED on a sampled mesh leaves VGX_RT_SAMPLED and its handle in `pad`; at VGX_RL_PAINTED
-// a painted mesh leaves its table and handle there. VGX_RF_INVALID: the handle, the record it names or a pattern's image is no good.
+// a painted mesh leaves its table and handle there; at VGX_RL_CONCAVE a contour mesh adds VGX_RT_CONTOUR. VGX_RF_INVALID: the handle, the record it names or a pattern's image is no good.
 // A table is read only at a level that uses it, and only the record a mesh names; below that level it may be null
 VGX_HD void vgx_raster_mesh_state(int level, const vgx_mesh& me, uint32_t stateKey, const vgx_draw_state& ds, int32_t x0, int32_t y0, const uint32_t* scissor,
                                   const vgx_raster_image* images, uint32_t numImages, const vgx_paint* gradients, uint32_t numGradients,
@@ -448,8 +518,9 @@ VGX_HD void vgx_raster_mesh_state(int level, const vgx_mesh& me, uint32_t stateK
 		st->pad = VGX_RT_SAMPLED | handle;
 		return;
 	}
+	const uint32_t contour = level >= VGX_RL_CONCAVE && vgx_raster_kind_is_contours(me.subpath_kind) ? VGX_RT_CONTOUR : 0u;
 	const uint32_t painted = level >= VGX_RL_PAINTED ? vgx_raster_mesh_painted(stateKey) : 0u;
-	if (!painted) { return; }
+	if (!painted) { st->pad = contour; return; }
 	const bool grad = painted == VGX_RT_GRADIENT;
 	if (handle >= (grad ? numGradients : numPatterns)) { st->mode = VGX_RF_INVALID; return; }
 	const vgx_paint* const p = (grad ? gradients : patterns) + handle;
@@ -458,7 +529,7 @@ VGX_HD void vgx_raster_mesh_state(int level, const vgx_mesh& me, uint32_t stateK
 		const uint32_t im = p->image & 0xFFFFu;
 		if (im >= numImages || !vgx_raster_image_valid(images[im])) { st->mode = VGX_RF_INVALID; return; }
 	}
-	st->pad = painted | handle;
+	st->pad = painted | handle | contour;
 }
 
 // ---- the arguments of the four calls (host only) ---------------------------------------------------------------------------------

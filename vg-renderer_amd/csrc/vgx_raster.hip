@@ -1,7 +1,7 @@
 // vgx_raster.hip -- a frame's mesh streams to an RGBA8 image on gfx950 (include/vgx.h: vgx_raster, vgx_raster_frame, vgx_raster_textured,
-// vgx_raster_painted; the arithmetic: vgx_raster.h). Two kernel families and one launch sequence (count, scan, entries, sort, tiles):
-// the plain family (k_raster_*) serves vgx_raster and carries no draw state, which measurably keeps it the faster one; the frame family
-// (k_rasterf_*, further down) serves the three frame-level calls, which differ in a level carried in the arguments.
+// vgx_raster_painted, vgx_raster_concave; the arithmetic: vgx_raster.h). Two kernel families and one launch sequence (count, scan, entries,
+// sort, tiles): the plain family (k_raster_*) serves vgx_raster and carries no draw state, which measurably keeps it the faster one; the
+// frame family (k_rasterf_*, further down) serves the four frame-level calls, which differ in a level carried in the arguments.
 //
 // Blending is not commutative: a pixel must see its triangles in ascending (mesh, triangle) order, and no atomic on a pixel gives
 // that. So a pixel belongs to ONE lane for the whole call: the image is cut into tiles of 16 x 16 pixels, a tile is one workgroup of
@@ -36,7 +36,7 @@ __device__ __forceinline__ bool raster_rect(const VgxRasterArgs& A, uint64_t k, 
 	const uint64_t m = A.mesh_begin + k;
 	const float4 box = ((const float4*)A.mesh_bounds)[m];
 	const float b[4] = { box.x, box.y, box.z, box.w };
-	return vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, A.scissor, true, r);
+	return vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, A.scissor, VGX_RL_PLAIN, r);
 }
 
 __global__ __launch_bounds__(256) void k_raster_count(VgxRasterArgs A)
@@ -172,8 +172,9 @@ __global__ __launch_bounds__(256) void k_raster_tiles(VgxRasterArgs A)
 	if (inside && (clear || d != before)) { *pixel = d; }
 }
 
-// ---- the frame family: vgx_raster_frame, vgx_raster_textured, vgx_raster_painted -----------------------------------------------------
-// The same steps with the state of every mesh's draw; VgxRasterFrameArgs::level says which of the three calls runs.
+// ---- the frame family: vgx_raster_frame, vgx_raster_textured, vgx_raster_painted, vgx_raster_concave ---------------------------------
+// The same steps with the state of every mesh's draw; VgxRasterFrameArgs::level says which of the four calls runs. (What the concave
+// level adds -- a third tile bit and the CONTOUR instantiation -- is described at k_rasterf_tiles.)
 //   k_rasterf_count    also decides what the mesh does (vgx_raster_mesh_state: stamp / test In / test Out / untested / nothing, its
 //                      region, the target's scissor cut by its draw's; from the textured level on "sampled", at the painted level
 //                      "gradient" / "pattern", with the handle, in the state's pad word) and keeps that per mesh of the range; the tiles
@@ -203,7 +204,7 @@ __device__ __forceinline__ bool frame_rect(const VgxRasterFrameArgs& F, uint64_t
 	const VgxRasterArgs& A = F.R;
 	const float4 box = ((const float4*)A.mesh_bounds)[m];
 	const float b[4] = { box.x, box.y, box.z, box.w };
-	return vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, st.rect, F.level == VGX_RL_FRAME, r);
+	return vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, st.rect, F.level, r);
 }
 
 __global__ __launch_bounds__(256) void k_rasterf_count(VgxRasterFrameArgs F)
@@ -236,7 +237,7 @@ struct OpRasterFrameBin
 	{
 		Sum3 r = sum3_zero();
 		r.a = F.R.mesh_entries[i];
-		r.b = r.a ? F.R.meshes[F.R.mesh_begin + i].num_indices / 3u : 0u;
+		r.b = r.a ? vgx_raster_mesh_elements(F.R.meshes[F.R.mesh_begin + i]) : 0u; // a contour mesh has entries at VGX_RL_CONCAVE only
 		r.c = F.mesh_state[i].mode == VGX_RF_INVALID ? 1u : 0u;
 		return r;
 	}
@@ -283,6 +284,7 @@ __global__ __launch_bounds__(256) void k_rasterf_entries(VgxRasterFrameArgs F)
 	// a level that cannot set a flag has no bitmap for it
 	if (st.pad & VGX_RT_SAMPLED) { mark_tiles(F.tile_tex, r, A.tiles_w); }
 	if (st.pad & VGX_RT_PAINTED) { mark_tiles(F.tile_paint, r, A.tiles_w); }
+	if (st.pad & VGX_RT_CONTOUR) { mark_tiles(F.tile_contour, r, A.tiles_w); }
 }
 
 // 112 bytes: the record; its mesh's slot in s_state | mode << 8 | VGX_RT_SAMPLED / VGX_RT_GRADIENT / VGX_RT_PATTERN; the mesh's rectangle
@@ -321,9 +323,42 @@ __device__ __forceinline__ vgx_raster_image& slot_image(VgxRasterPaint& s) { ret
 // bit `key` of a tile bitmap; a null bitmap (a level that cannot set it) has every bit clear. Block-uniform
 __device__ __forceinline__ bool tile_bit(const uint32_t* bits, uint32_t key) { return bits != nullptr && ((bits[key >> 5] >> (key & 31u)) & 1u) != 0u; }
 
-template <bool TEX, bool PAINT>
+// Element k of the contour mesh `me` (mesh m of the frame) for the tile at (ox, oy), mr = the mesh's mode and rectangle cut to the tile:
+// edge k, or the flush behind the last edge. R->slot_mode is the caller's. false: the element is not kept
+__device__ __forceinline__ bool contour_element(const VgxRasterArgs& A, const vgx_mesh& me, uint32_t m, uint64_t k, uint32_t mr, uint32_t ox, uint32_t oy, VgxRasterFrameTri* R)
+{
+	const uint32_t cx0 = mr & 31u, cy0 = (mr >> 5) & 31u, cx1 = (mr >> 10) & 31u, cy1 = (mr >> 15) & 31u; // tile-local, half open, not empty
+	if (k == me.num_indices / 2u) { // the flush: rule, box and colour of the mesh, under its rectangle's masks
+		const float4 box = ((const float4*)A.mesh_bounds)[m];
+		R->T.minx = box.x; R->T.miny = box.y; R->T.maxx = box.z; R->T.maxy = box.w;
+		R->T.col[0] = A.color[me.first_vertex]; // num_vertices > 0: a contour mesh without a vertex has no entry
+		R->T.flags = me.subpath_kind;
+		R->slot_mode |= VGX_RT_FLUSH;
+		R->mask = (((1u << cx1) - 1u) & ~((1u << cx0) - 1u)) | ((((1u << cy1) - 1u) & ~((1u << cy0) - 1u)) << 16);
+		return true;
+	}
+	const uint16_t* ip = A.idx + me.first_index + 2ull * k;
+	const uint32_t i0 = ip[0], i1 = ip[1];
+	if (i0 >= me.num_vertices || i1 >= me.num_vertices) { return false; }
+	const float2* pp = (const float2*)A.pos + me.first_vertex;
+	const float2 u = pp[i0], v = pp[i1];
+	R->mask = 0u;
+	// the samples of the rectangle's rows, and its last column
+	return vgx_raster_contour_edge(v2(u.x, u.y), v2(v.x, v.y), &R->T)
+	    && vgx_raster_contour_edge_reaches(R->T, (double)(A.y0 + (int32_t)(oy + cy0)) + 0.5, (double)(A.y0 + (int32_t)(oy + cy1 - 1u)) + 0.5,
+	                                       (double)(A.x0 + (int32_t)(ox + cx1 - 1u)) + 0.5);
+}
+
+// CONTOUR (vgx_raster_concave; one instantiation, of the widest shape, for every tile a contour mesh reaches -- DESIGN.md): a contour
+// mesh in hand counts its edges and ONE more element, the flush. An edge is set up like a triangle's edge 0 and kept when it can add
+// to the winding number of a sample of the tile (its rows, and nothing to the right of the tile); every pixel lane adds the kept edges
+// to a private W, which lives across the batches of 256 records as d and S do. The flush is always kept -- the mesh's last edges may
+// be culled -- and applies fill rule, box and colour, then clears W for the next contour mesh. Records stay in (mesh, element) order,
+// so the mesh takes one place in painter's order
+template <bool TEX, bool PAINT, bool CONTOUR>
 __global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
 {
+	static_assert(!CONTOUR || (TEX && PAINT), "the contour instantiation serves every class of tile");
 	typedef typename RasterTexRecord<TEX>::type Record;
 	typedef typename RasterPaintSlot<TEX, PAINT>::type Slot;
 	__shared__ Record s_tri[256];
@@ -338,7 +373,8 @@ __global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
 	if (A.state[0] != VGX_OK) { return; }
 	const uint32_t tx = A.tile_x0 + blockIdx.x, ty = A.tile_y0 + blockIdx.y;
 	const uint32_t key = ty * A.tiles_w + tx;
-	if (tile_bit(F.tile_tex, key) != TEX || tile_bit(F.tile_paint, key) != PAINT) { return; } // block-uniform: the tile of another instantiation
+	if (tile_bit(F.tile_contour, key) != CONTOUR) { return; } // block-uniform: the tile of another instantiation
+	if (!CONTOUR && (tile_bit(F.tile_tex, key) != TEX || tile_bit(F.tile_paint, key) != PAINT)) { return; }
 	const uint32_t tid = threadIdx.x;
 	const int lane = tid & (VGX_WAVE - 1);
 	const uint32_t wave = tid >> 6;
@@ -353,6 +389,7 @@ __global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
 	const uint32_t before = inside ? (clear ? A.clear_color : *pixel) : 0u;
 	uint32_t d = before;
 	uint32_t S = VGX_RASTER_STAMP_NONE;
+	int32_t W = 0; // CONTOUR: the winding number of the contour mesh whose edges are being walked
 	const double px = (double)(A.x0 + (int32_t)i) + 0.5, py = (double)(A.y0 + (int32_t)j) + 0.5;
 	for (uint32_t eb = r0; eb < r1; eb += 256u) { // block-uniform loops throughout
 		const uint32_t ne = min(256u, r1 - eb);
@@ -363,6 +400,9 @@ __global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
 			v.a = A.meshes[m].num_indices / 3u;
 			// the mesh's rectangle cut to this tile (an entry means its box reaches the tile inside the rectangle: not empty)
 			const VgxRasterMeshState ms = F.mesh_state[m - A.mesh_begin];
+			if constexpr (CONTOUR) {
+				if (ms.pad & VGX_RT_CONTOUR) { v.a = (uint64_t)(A.meshes[m].num_indices / 2u) + 1u; } // its edges and the flush
+			}
 			const uint32_t cx0 = max(ox, ms.rect[0]), cx1 = min(ox + VGX_RASTER_TILE, ms.rect[2]);
 			const uint32_t cy0 = max(oy, ms.rect[1]), cy1 = min(oy + VGX_RASTER_TILE, ms.rect[3]);
 			VgxRasterTileState ts;
@@ -370,15 +410,15 @@ __global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
 			ts.mode_rect = cx0 < cx1 && cy0 < cy1 ? (ms.mode << 20) | ((cy1 - oy) << 15) | ((cx1 - ox) << 10) | ((cy0 - oy) << 5) | (cx0 - ox) : (uint32_t)VGX_RF_NOTHING << 20;
 			s_state[tid] = ts;
 			if constexpr (TEX || PAINT) {
-				uint32_t fl = 0u;
+				uint32_t fl = CONTOUR ? ms.pad & VGX_RT_CONTOUR : 0u;
 				// handles and records are inside their tables and valid: k_rasterf_count
 				if constexpr (TEX) {
-					if (ms.pad & VGX_RT_SAMPLED) { fl = VGX_RT_SAMPLED; slot_image(s_slot[tid]) = F.images[ms.pad & 0xFFFFu]; }
+					if (ms.pad & VGX_RT_SAMPLED) { fl |= VGX_RT_SAMPLED; slot_image(s_slot[tid]) = F.images[ms.pad & 0xFFFFu]; }
 				}
 				if constexpr (PAINT) {
 					if (ms.pad & VGX_RT_PAINTED) {
 						const bool grad = (ms.pad & VGX_RT_GRADIENT) != 0u;
-						fl = grad ? VGX_RT_GRADIENT : VGX_RT_PATTERN;
+						fl |= grad ? VGX_RT_GRADIENT : VGX_RT_PATTERN;
 						VgxRasterPaint rec;
 						vgx_raster_paint_record((grad ? F.gradients : F.patterns)[ms.pad & 0xFFFFu], F.images, &rec);
 						s_slot[tid] = rec;
@@ -407,8 +447,15 @@ __global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
 				const uint32_t mr = s_state[lo].mode_rect;
 				const uint32_t fl = TEX || PAINT ? s_flags[lo] : 0u;
 				const vgx_mesh me = A.meshes[s_mesh[lo]];
-				const uint16_t* ip = A.idx + me.first_index + 3ull * (g - s_first[lo]);
-				const uint32_t i0 = ip[0], i1 = ip[1], i2 = ip[2];
+				// a contour mesh's elements are its edges and the flush (contour_element); no index triple is read for it, and the
+				// indices below, ~0u >= every num_vertices, keep it out of the triangle branch. Constant false without CONTOUR
+				const bool edges = CONTOUR && (fl & VGX_RT_CONTOUR) != 0u;
+				if (edges) {
+					RF.slot_mode = lo | ((mr >> 20) << 8) | fl;
+					keep = (mr >> 20) != VGX_RF_NOTHING && contour_element(A, me, s_mesh[lo], g - s_first[lo], mr, ox, oy, &RF);
+				}
+				const uint16_t* ip = A.idx + me.first_index + (edges ? 0ull : 3ull * (g - s_first[lo]));
+				const uint32_t i0 = edges ? ~0u : ip[0], i1 = edges ? ~0u : ip[1], i2 = edges ? ~0u : ip[2];
 				if ((mr >> 20) != VGX_RF_NOTHING && i0 < me.num_vertices && i1 < me.num_vertices && i2 < me.num_vertices) {
 					const float2* pp = (const float2*)A.pos + me.first_vertex;
 					const uint32_t* cp = A.color + me.first_vertex;
@@ -440,6 +487,23 @@ __global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
 			__syncthreads();
 			for (uint32_t t = 0; t < n; ++t) { // every lane walks the records: no lane leaves between the barriers
 				const VgxRasterFrameTri& rec = frame_part(s_tri[t]);
+				if constexpr (CONTOUR) {
+					const uint32_t sm = rec.slot_mode; // block-uniform
+					if (sm & VGX_RT_CONTOUR) {
+						if (!(sm & VGX_RT_FLUSH)) { W += vgx_raster_contour_winding(rec.T, px, py); continue; }
+						const float box[4] = { rec.T.minx, rec.T.miny, rec.T.maxx, rec.T.maxy };
+						if (((rec.mask >> lx) & (rec.mask >> (16u + ly)) & 1u) != 0u && vgx_raster_contour_covered(W, rec.T.flags, box, px, py)) {
+							const VgxRasterTileState ts = s_state[sm & 255u];
+							const VgxRasterPaint& pr = s_slot[sm & 255u]; // written, and read, for a painted mesh only
+							VgxRasterTexelFetch fetch;
+							fetch.pixels = nullptr; fetch.stride = 0u;
+							if (sm & VGX_RT_PATTERN) { fetch.pixels = pr.im.pixels; fetch.stride = pr.im.stride; }
+							d = vgx_raster_contour_pixel(rec.T.col[0], sm, pr, (sm >> 8) & 255u, ts.f, ts.n, px, py, &S, d, fetch);
+						}
+						W = 0;
+						continue;
+					}
+				}
 				const uint32_t mk = rec.mask; // beside the record: an untested mesh needs no second, dependent LDS read
 				if (((mk >> lx) & (mk >> (16u + ly)) & 1u) != 0u) {
 					const uint32_t sm = rec.slot_mode;
@@ -524,12 +588,13 @@ hipError_t vgx_launch_raster(const VgxRasterArgs& a, void* partial, void* sortTe
 hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& f, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
 {
 	const auto tiles = [&](dim3 grid) { // the instantiations whose tiles the level can have
-		hipLaunchKernelGGL((k_rasterf_tiles<false, false>), grid, dim3(256), 0, s, f);
-		if (f.level >= VGX_RL_TEXTURED) { hipLaunchKernelGGL((k_rasterf_tiles<true, false>), grid, dim3(256), 0, s, f); }
+		hipLaunchKernelGGL((k_rasterf_tiles<false, false, false>), grid, dim3(256), 0, s, f);
+		if (f.level >= VGX_RL_TEXTURED) { hipLaunchKernelGGL((k_rasterf_tiles<true, false, false>), grid, dim3(256), 0, s, f); }
 		if (f.level >= VGX_RL_PAINTED) {
-			hipLaunchKernelGGL((k_rasterf_tiles<false, true>), grid, dim3(256), 0, s, f);
-			hipLaunchKernelGGL((k_rasterf_tiles<true, true>), grid, dim3(256), 0, s, f);
+			hipLaunchKernelGGL((k_rasterf_tiles<false, true, false>), grid, dim3(256), 0, s, f);
+			hipLaunchKernelGGL((k_rasterf_tiles<true, true, false>), grid, dim3(256), 0, s, f);
 		}
+		if (f.level >= VGX_RL_CONCAVE) { hipLaunchKernelGGL((k_rasterf_tiles<true, true, true>), grid, dim3(256), 0, s, f); }
 	};
 	return launch_sequence<OpRasterFrameBin>(f, f.R, k_rasterf_count, k_rasterf_entries, tiles, partial, sortTemp, sortBytes, s);
 }

@@ -772,7 +772,7 @@ def paint_tables(paints, num_gradients=None, num_patterns=None):
 
 def raster_painted(ctx, frame, draws_dev, draw_state_dev, num_draws, uv_dev, uv_bytes, images_dev, num_images, gradients_dev, num_gradients, patterns_dev,
                    num_patterns, width, height, x0=0, y0=0, scissor=None, clear_color=None, bounds_dev=None, mesh_begin=0, mesh_end=None, image=None,
-                   dev_status=None):
+                   dev_status=None, _entry="vgx_raster_painted"):
     """raster_textured() that also paints: a mesh whose draw has type 1 (ColorGradient) or 2 (ImagePattern) takes its colour from the
     vgx_paint record its draw names (state_key & 0xFFFF indexes gradients_dev / patterns_dev, the tables of paint_tables() as uint8
     device tensors; a pattern's .image indexes images_dev) by the fragment rule of vgx_raster_painted in include/vgx.h. dev_status may
@@ -791,14 +791,20 @@ def raster_painted(ctx, frame, draws_dev, draw_state_dev, num_draws, uv_dev, uv_
     tx = capi.RasterTextures(uv_dev.data_ptr() if uv_dev is not None else None, images_dev.data_ptr() if num_images else None, int(uv_bytes), int(num_images))
     pt = capi.RasterPaints(gradients_dev.data_ptr() if num_gradients else None, patterns_dev.data_ptr() if num_patterns else None, int(num_gradients),
                            int(num_patterns))
-    _check(lib().vgx_raster_painted(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
-                                    0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), C.byref(tx), C.byref(pt), C.byref(t),
-                                    dev_status.data_ptr(), _stream_ptr()), "vgx_raster_painted")
+    _check(getattr(lib(), _entry)(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
+                                  0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), C.byref(tx), C.byref(pt), C.byref(t),
+                                  dev_status.data_ptr(), _stream_ptr()), _entry)
     return image, dev_status
 
 
+def raster_concave(*args, **kwargs):
+    """raster_painted() that also fills meshes of kind capi.MESH_CONTOURS (what concave_contours() writes) by the winding number of
+    their edges: the rule of vgx_raster_concave in include/vgx.h. Same arguments and results as raster_painted()."""
+    return raster_painted(*args, _entry="vgx_raster_concave", **kwargs)
+
+
 def raster_reserve(ctx, num_meshes, num_bin_entries):
-    """Sizes the scratch of raster(), raster_frame(), raster_textured() and raster_painted() ahead, so that a first call does not end with VGX_E_GROWN."""
+    """Sizes the scratch of raster(), raster_frame(), raster_textured(), raster_painted() and raster_concave() ahead, so that a first call does not end with VGX_E_GROWN."""
     _check(lib().vgx_raster_reserve(ctx.handle, int(num_meshes), int(num_bin_entries)), "vgx_raster_reserve")
 
 
@@ -856,6 +862,16 @@ def concave_emit(ctx, contour_verts_dev, contours_dev, ncontours, fills_dev, nfi
     _check(lib().vgx_concave_emit(ctx.handle, contour_verts_dev.data_ptr(), n, contours_dev.data_ptr(), ncontours,
                                   fills_dev.data_ptr(), nfills, tess_pos_dev.data_ptr(), tess_idx_dev.data_ptr(), C.byref(out),
                                   bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_concave_emit")
+
+
+def concave_contours(ctx, poly_dev, subpaths_dev, draw_info_dev, draws_dev, ndraws, bufs):
+    """Contour meshes for the concave draws of a frame, without libtess2 (vgx_concave_contours in include/vgx.h). poly_dev,
+    subpaths_dev, draw_info_dev: what flatten wrote with apply_transform = 1, as device tensors; draws_dev: the frame's 64-byte vgx_draw
+    records. The meshes (ascending by draw: sequence b of merge()) go to `bufs`. Asynchronous; totals / status land in bufs.dev_*."""
+    out = bufs.out_struct()
+    _check(lib().vgx_concave_contours(ctx.handle, poly_dev.data_ptr() if ndraws else None, subpaths_dev.data_ptr() if ndraws else None,
+                                      draw_info_dev.data_ptr() if ndraws else None, draws_dev.data_ptr() if ndraws else None, int(ndraws), C.byref(out),
+                                      bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_concave_contours")
 
 
 # ---- text runs (vgx_text_quads): glyph layout and the atlas stay with the caller -------------------------------------
