@@ -175,7 +175,7 @@ enum { VGX_MESH_FILL = 0, VGX_MESH_FILL_AA = 1, VGX_MESH_STROKE = 2, VGX_MESH_ST
        VGX_MESH_CONCAVE_FILL_AA = 5 /* vgx_concave_emit */, VGX_MESH_TRILIST = 6 /* vgx_cmdlist_out::tri_meshes */,
        VGX_MESH_TEXT = 7 /* vgx_text_quads */, VGX_MESH_CONTOURS = 8 /* vgx_concave_contours: directed edges, below */ };
 /* A mesh of kind VGX_MESH_CONTOURS holds the contours of a concave fill as an edge soup, for a consumer that fills by winding number
- * (vgx_raster_concave). Vertices are contour points in pos, colours in color. idx holds one directed edge per PAIR of mesh-local
+ * (vgx_raster_concave draws it, vgx_pick_frame hit-tests it by the same rule). Vertices are contour points in pos, colours in color. idx holds one directed edge per PAIR of mesh-local
  * indices: edge e is idx[first_index + 2e] -> idx[first_index + 2e + 1], e < num_indices / 2; a trailing odd index is ignored and an
  * edge with an index >= num_vertices is skipped. Bit 0 of the low 28 bits of subpath_kind is the fill rule: 0 = NonZero, 1 = EvenOdd.
  * No contour structure is stored: winding needs none. Everything that treats meshes as vertex and index ranges (vgx_mesh_bounds,
@@ -930,12 +930,75 @@ int vgx_paint_tables(const struct vgx_paint* paints, uint32_t n, struct vgx_pain
  * Status. The element count of VGX_E_RANGE becomes triangles plus edges (of the contour meshes that have a bin entry); a contour mesh has
  *   bin entries like any mesh, by its box. Everything else as vgx_raster_painted. Positions that are NaN: as vgx_mesh_bounds says, the
  *   box of such a mesh is unspecified, and so is what the mesh covers; nothing outside image and scissor is written in any case.
- * Host return values, out of scope (streams written under vgx_set_assembly; hit testing of contour meshes): as vgx_raster_painted.
+ * Host return values, out of scope (streams written under vgx_set_assembly): as vgx_raster_painted. Hit testing of what this call draws,
+ *   contour meshes included, is vgx_pick_frame, below; vgx_pick still skips the kind.
  * Side effects. As vgx_raster_painted, on the same scratch, and a third bit per 16 x 16 tile of the image (which tiles a contour mesh
  *   reaches) in a buffer only this call allocates; vgx_scratch_bytes counts it. A counted state survives. */
 int vgx_raster_concave(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
                        uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state, const vgx_raster_textures* tex,
                        const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* dev_status, void* stream);
+
+/* ---- hit testing of a decoded frame: what is under the point in the image of vgx_raster_concave (... -> vgx_pick_frame) ------------------
+ * vgx_pick answers for bare triangles: it knows no draw scissor, no clip region and no contour mesh, it reports the meshes of a Clip draw,
+ * and its closed point-in-triangle rule names both triangles of a seam. vgx_pick_frame answers for the IMAGE: a mesh is hit where
+ * vgx_raster_concave would let a sample of it take effect. It takes the frame, range and `state` of vgx_raster_frame and the queries and
+ * hit records of vgx_pick; it needs no target, no textures and no paints, because a hit is a statement about geometry and draw state, not
+ * about colour. Everything below gives the same words in every implementation for every input; there is no tolerance. All pointers are
+ * DEVICE pointers; `frame` is what vgx_raster accepts.
+ *
+ * Point. px = (double)x, py = (double)y. If !(fabs(px) < 2147483648.0) or the same for py (NaN included) the hit is "none". Otherwise the
+ *   point lies in frame pixel X = (int64)floor(px), Y = (int64)floor(py).
+ * Range. The meshes m of [mesh_begin, min(mesh_end, num_meshes)) are taken in ascending order. The stamp S of the point is NONE
+ *   (0xFFFFFFFF) at the start, exactly as in a vgx_raster_frame call with that range: the range must contain the clip meshes of every
+ *   region its draws use.
+ * Draw scissor. With d = meshes[m].draw and {x, y, w, h} = draw_state[d].scissor, mesh m exists at the point iff x <= X < x + w &&
+ *   y <= Y < y + h, in 64-bit integers. Otherwise it neither stamps nor is hit.
+ * Mesh box. With B = the mesh's entry of mesh_bounds, mesh m exists at the point iff px >= B.minx && px <= B.maxx && py >= B.miny &&
+ *   py <= B.maxy in binary64, a NaN bound making it false; for every kind. As in vgx_raster_concave the caller's table is part of the input
+ *   and must hold what vgx_mesh_bounds gives for the stream; with mesh_bounds == NULL the call computes exactly those boxes (of the range)
+ *   into scratch of its own. For a triangle mesh with true boxes the clause changes nothing: the triangle rule starts with the
+ *   triangle's own box, which lies inside.
+ * Coverage at the point: the raster's rule, not vgx_pick's.
+ *   - A mesh of any kind but VGX_MESH_CONTOURS (TEXT and TRILIST included; no UV is read): some valid triangle t < num_indices / 3, all
+ *     three indices < num_vertices, satisfies the coverage rule of vgx_raster at the sample (px, py): the binary64 box, the canonical
+ *     edge values, the tie rule, S > 0.
+ *   - A mesh of kind VGX_MESH_CONTOURS: the rule of vgx_raster_concave at the sample (px, py): W over the valid edges, the fill-rule bit,
+ *     and "a mesh with no vertices does nothing".
+ *   - Flags. With VGX_PICK_SKIP_TRANSPARENT in the query's flags a triangle with a vertex of alpha 0 is skipped, as in vgx_pick, and a
+ *     contour mesh with color[first_vertex] >> 24 == 0 is skipped whole.
+ * Clip draws (type 3). A point the mesh covers -- query flags play no part here -- sets S = d. Such a mesh is never a hit.
+ * Other draws. Mesh m is a hit for query q iff m < q.mesh_end, it is covered under the query's flags, and the stamp test of
+ *   vgx_raster_frame passes with the S the meshes below m left: no test when clip_first_draw == 0xFFFFFFFF or clip_num_draws == 0, else
+ *   (S != NONE && S >= f && S - f < n) == (rule == 0).
+ * Result. The largest hit m. triangle = the largest covering t of that mesh under the flags, 0xFFFFFFFF for a contour mesh; draw and
+ *   subpath_kind come from the mesh record. No hit: all four words are 0xFFFFFFFF. q.mesh_end limits hits only; stamps always come from
+ *   every mesh of the range below m, so passing the previous hit's `mesh` walks the VISIBLE stack downward consistently.
+ * dev_status (DEVICE uint32, may be NULL). VGX_OK when done. VGX_E_INVALID_ARG when a mesh of the range (of any kind) has draw >=
+ *   num_draws: every hit record is then written as "none". Decided in one reduction over the meshes, so it does not depend on the order of
+ *   the work. There is no VGX_E_GROWN: every table is sized from the range length and nqueries, which the host knows.
+ * Host return values. VGX_OK once the work is enqueued. VGX_E_INVALID_ARG for a null ctx, frame or state, null queries or hits with
+ *   nqueries > 0, reserved != 0, null arrays with num_draws > 0, null streams with num_meshes > 0, misaligned pointers (queries, hits,
+ *   mesh_bounds 16-byte; pos, meshes 8-byte; color, draws, draw_state, dev_status 4-byte; idx 2-byte). VGX_E_RANGE for nqueries >
+ *   VGX_PICK_MAX_QUERIES or num_meshes >= 2^32 - 1. VGX_E_HIP for a HIP failure. nqueries == 0 or an empty range is valid.
+ * Side effects. Exactly nqueries hit records and dev_status are written, nothing else of the caller's. Asynchronous. Uses scratch of its
+ *   own -- 84 bytes per mesh of the range (32 its state under its draw; as a candidate 4 + 4 + 4 + 8 for its places in the lists and 32
+ *   for one covered bit per query), 16 more per mesh of the frame with mesh_bounds == NULL; vgx_scratch_bytes counts it -- so a counted
+ *   state survives: vgx_tessellate_count -> vgx_pick_frame -> vgx_tessellate_emit works, and vgx_pick's tables are not touched.
+ * Two relations follow from the rule; the tests assert both.
+ *   (a) The image is the oracle. For a query at a pixel centre (x0 + i + 0.5, y0 + j + 0.5) with flags 0 and mesh_end = 0xFFFFFFFF,
+ *       hit.mesh is the mesh whose identifier vgx_raster_concave leaves in pixel (i, j) of the ID frame: the same streams with every
+ *       vertex colour of mesh m set to 0xFF000000 | (m + 1), every non-Clip draw retyped to 0, the kinds TEXT and TRILIST rewritten to
+ *       VGX_MESH_FILL, drawn over a clear of 0 under a target scissor that cuts nothing. Opaque source alpha makes the blend a copy, so
+ *       no arithmetic of the colour path takes part.
+ *   (b) vgx_pick. On a frame with no Clip draw, no region, no contour mesh and scissors that contain the point, at a point where no edge
+ *       value of any candidate triangle is 0, vgx_pick_frame equals vgx_pick in all four words: away from the edges the closed rule and
+ *       the tie rule agree.
+ * Out of scope. Alpha of textures or paints deciding a hit (a fully transparent texel under the cursor still hits its quad), streams
+ *   written under vgx_set_assembly, more than VGX_PICK_MAX_QUERIES queries per call. */
+int vgx_pick_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
+                   uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                   const vgx_pick_query* queries, uint32_t nqueries, vgx_pick_hit* hits,
+                   uint32_t* dev_status /* may be NULL */, void* stream);
 
 /* ---- incremental update (beyond the reference): vgx_cache_submit -> vgx_cache_layout -> [vgx_pick -> edit -> vgx_cache_update]* ----
  * Moving or recolouring an instance of a submitted frame changes nothing of the frame's structure: a cached mesh has a fixed size, so

@@ -276,6 +276,8 @@ VGX_SYMBOLS = {
     "vgx_cache_cull": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
                                  C.POINTER(CullOut), C.c_void_p, C.c_void_p]),
     "vgx_pick": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vgx_pick_frame": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.c_void_p, C.c_uint32, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
     "vgx_raster": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
     "vgx_raster_reserve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
     "vgx_raster_frame": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.POINTER(RasterTarget), C.c_void_p,

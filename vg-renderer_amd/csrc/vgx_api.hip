@@ -19,6 +19,7 @@
 #include "vgx_dash.h"
 #include "vgx_update.h"
 #include "vgx_raster.h"
+#include "vgx_pick.h"
 #include "vgx_concave_lane.h"
 #include "vgx_scratch.h"
 #include <vector>
@@ -138,6 +139,10 @@ struct vgx_ctx
 	Buf<uint32_t> textTiles;             // vgx_text_quads: first run of every tile of quads (vgx_text.hip)
 	Buf<uint8_t> cullFlags; DevBuf cullPartial; // vgx_cache_cull (vgx_bounds.hip): kept flag per instance, the compaction scan's slice sums (views: as `partial`). Its own: a counted state survives the call
 	Buf<uint64_t> pickKeys, pickPrefix, pickTotals; Buf<uint32_t> pickTris, pickCand; Buf<float> pickBounds; DevBuf pickPartial; // vgx_pick (vgx_pick.hip); pickPartial: slice sums (views: as `partial`). Its own: a counted state survives the call
+	// vgx_pick_frame (vgx_pick.hip): per mesh of the range its state under its draw; per candidate its mesh, its covered bits (8 words) and its
+	// place among the triangle / contour candidates; the triangle prefix; the totals; boxes when the caller gives none; slice sums (views: as
+	// `partial`). Its own: a counted state survives the call, and vgx_pick's tables are not touched
+	Buf<VgxPickfMesh> pickfState; Buf<uint32_t> pickfCand, pickfTriCand, pickfConCand, pickfCover; Buf<uint64_t> pickfPrefix, pickfTotals; Buf<float> pickfBounds; DevBuf pickfPartial;
 	DevBuf updPrefix, updPartial;        // vgx_cache_layout / vgx_cache_update (vgx_update.hip); views: updPrefix = uint32_t flag word in 16 bytes, then 2 x uint64_t[ndirty + 1] prefix sums of the listed entries; updPartial = slice sums, as `partial`. Their own: a counted state survives the calls
 	// vgx_raster (vgx_raster.hip): per mesh of the range its bin entries and its first entry; the (tile, mesh) entries in mesh order and
 	// in tile order; the sort's temporary storage; status and entry count of the last call with their pinned mirror (as `dash`: a call
@@ -2759,6 +2764,43 @@ int vgx_pick(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds
 	a.keys = ctx->pickKeys.ptr(); a.cand_tris = ctx->pickTris.ptr(); a.cand_mesh = ctx->pickCand.ptr();
 	a.cand_prefix = ctx->pickPrefix.ptr(); a.totals = ctx->pickTotals.ptr();
 	vgx_launch_pick(a, ctx->pickPartial.p, ctx->optPickGrid, s);
+	return launchStatus(ctx);
+}
+
+// ... under per-draw scissors, clip regions and contour fills. Scratch of its own: count -> vgx_pick_frame -> emit still works, and so does
+// vgx_pick -> vgx_pick_frame -> vgx_pick.
+int vgx_pick_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                   const vgx_pick_query* queries, uint32_t nqueries, vgx_pick_hit* hits, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx) { return VGX_E_INVALID_ARG; }
+	int st = vgx_pickf_check_args(frame, mesh_bounds, state, queries, nqueries, hits, dev_status);
+	if (st != VGX_OK) { return st; }
+	hipStream_t s = (hipStream_t)stream;
+	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
+	const uint64_t nrange = mesh_begin < end ? end - mesh_begin : 0;
+	if ((st = ensure(ctx, ctx->pickfState, nrange + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickfCand, nrange + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickfTriCand, nrange + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickfConCand, nrange + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickfCover, 8 * (nrange + 1))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickfPrefix, nrange + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickfTotals, 4)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickfPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if (!mesh_bounds && nrange) {
+		if ((st = ensure(ctx, ctx->pickfBounds, frame->num_meshes * 4)) != VGX_OK) { return st; }
+		vgx_launch_mesh_bounds(frame->pos, frame->meshes + mesh_begin, nrange, ctx->pickfBounds.ptr() + 4 * mesh_begin, s); // the range's boxes only
+		mesh_bounds = ctx->pickfBounds.ptr();
+	}
+	VgxPickfArgs a;
+	memset(&a, 0, sizeof(a));
+	a.pos = frame->pos; a.color = frame->color; a.idx = frame->idx; a.meshes = frame->meshes; a.mesh_bounds = mesh_bounds;
+	a.mesh_begin = mesh_begin; a.nrange = nrange;
+	a.draws = state->draws; a.draw_state = state->draw_state; a.num_draws = state->num_draws;
+	a.queries = queries; a.nqueries = nqueries; a.hits = hits; a.status = dev_status;
+	a.mesh_state = ctx->pickfState.ptr(); a.cand_mesh = ctx->pickfCand.ptr(); a.tri_cand = ctx->pickfTriCand.ptr(); a.tri_prefix = ctx->pickfPrefix.ptr();
+	a.con_cand = ctx->pickfConCand.ptr(); a.cover = ctx->pickfCover.ptr(); a.totals = ctx->pickfTotals.ptr();
+	vgx_launch_pick_frame(a, ctx->pickfPartial.p, ctx->optPickGrid, s);
 	return launchStatus(ctx);
 }
 

@@ -531,6 +531,71 @@ int vgxt_pick(const vgx_cache_desc* frame, const float* mesh_bounds, const vgx_p
 	return VGX_OK;
 }
 
+// vgx_pick_frame on the host: the vgx_pickf_* functions of vgx_pick.h in a plain sequential loop over queries, the meshes of the range in
+// ascending order (the stamp S walks with them) and their triangles or edges, with the call's whole contract (mesh_bounds may be NULL: the
+// boxes are computed first). HOST pointers, the draw tables included. Returns the status the device call returns for these arguments;
+// *status (may be NULL) receives what it leaves in dev_status
+int vgxt_pick_frame(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                    const vgx_pick_query* queries, uint32_t nqueries, vgx_pick_hit* hits, uint32_t* status)
+{
+	const int rc = vgx_pickf_check_args(frame, mesh_bounds, state, queries, nqueries, hits, status);
+	if (rc != VGX_OK) { return rc; }
+	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
+	bool invalid = false;
+	for (uint64_t m = mesh_begin; m < end; ++m) { invalid = invalid || frame->meshes[m].draw >= state->num_draws; }
+	if (status) { *status = invalid ? VGX_E_INVALID_ARG : VGX_OK; }
+	float* own = nullptr;
+	if (!mesh_bounds && mesh_begin < end && !invalid) {
+		own = (float*)malloc(frame->num_meshes * 4 * sizeof(float));
+		if (!own) { return VGX_E_INTERNAL; }
+		vgxt_mesh_bounds(frame->pos, frame->meshes, frame->num_meshes, own);
+		mesh_bounds = own;
+	}
+	for (uint32_t q = 0; q < nqueries; ++q) {
+		const vgx_pick_query Q = queries[q];
+		double px, py;
+		int32_t X, Y;
+		const bool point = vgx_pickf_point(Q.x, Q.y, &px, &py, &X, &Y);
+		uint32_t S = VGX_RASTER_STAMP_NONE, best = VGX_PICK_NONE, bestT = VGX_PICK_NONE;
+		// a mesh at or behind the query's mesh_end is no hit, and what it stamps is seen by meshes above it only
+		for (uint64_t m = mesh_begin; m < end && m < (uint64_t)Q.mesh_end && point && !invalid; ++m) {
+			const vgx_mesh me = frame->meshes[m];
+			VgxPickfMesh st;
+			vgx_pickf_mesh_state(me, state->draws[me.draw].state_key, state->draw_state[me.draw], &st);
+			const float* box = mesh_bounds + 4 * m;
+			if (!st.elems || !vgx_pickf_in_scissor(st.rect, X, Y) || !vgx_pickf_in_box(box, px, py)) { continue; }
+			const uint16_t* ip = frame->idx + me.first_index;
+			const float* pp = frame->pos + 2 * me.first_vertex;
+			const uint32_t* cp = frame->color + me.first_vertex;
+			const bool skips = vgx_pickf_skips(st.mode, Q.flags);
+			bool covered = false;
+			uint32_t top = VGX_PICK_NONE;
+			if (vgx_raster_kind_is_contours(me.subpath_kind)) {
+				if (skips && (cp[0] >> 24) == 0u) { continue; }
+				int32_t W = 0;
+				for (uint32_t k = 0; k < st.elems; ++k) {
+					const uint32_t i0 = ip[2 * k], i1 = ip[2 * k + 1];
+					if (i0 < me.num_vertices && i1 < me.num_vertices) { W += vgx_pickf_edge(v2(pp[2 * i0], pp[2 * i0 + 1]), v2(pp[2 * i1], pp[2 * i1 + 1]), px, py); }
+				}
+				covered = vgx_raster_contour_covered(W, me.subpath_kind, box, px, py);
+			} else {
+				for (uint32_t t = 0; t < st.elems; ++t) {
+					const uint32_t i0 = ip[3 * t], i1 = ip[3 * t + 1], i2 = ip[3 * t + 2];
+					if (!vgx_pick_tri_valid(i0, i1, i2, me.num_vertices)) { continue; }
+					if (skips && vgx_pick_tri_transparent(cp[i0], cp[i1], cp[i2])) { continue; }
+					if (vgx_pickf_tri(v2(pp[2 * i0], pp[2 * i0 + 1]), v2(pp[2 * i1], pp[2 * i1 + 1]), v2(pp[2 * i2], pp[2 * i2 + 1]), px, py)) { covered = true; top = t; }
+				}
+			}
+			if (!covered) { continue; }
+			if (st.mode == VGX_RF_STAMP) { S = st.f; }
+			else if (vgx_pickf_hit(st.mode, st.f, st.n, S, m, Q.mesh_end)) { best = (uint32_t)m; bestT = top; }
+		}
+		hits[q] = vgx_pickf_record(best, bestT, frame->meshes);
+	}
+	free(own);
+	return VGX_OK;
+}
+
 }
 
 #include "vgx_raster.h"

@@ -436,6 +436,30 @@ struct VgxPickArgs
 };
 void vgx_launch_pick(const VgxPickArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, uint32_t grid, hipStream_t s);
 
+// ... under scissors, clip regions and contour fills (vgx_pick_frame). A candidate is a mesh of the range that some query's point can
+// lie in (box and draw scissor); candidates are numbered densely in ascending mesh order, and every table below is sized by the range
+struct VgxPickfMesh;
+struct VgxPickfArgs
+{
+	const float* pos; const uint32_t* color; const uint16_t* idx; const vgx_mesh* meshes; // the frame
+	const float* mesh_bounds;         // [num_meshes][4], 16-byte aligned: the caller's, or the context's own
+	uint64_t mesh_begin, nrange;      // the meshes looked at: [mesh_begin, mesh_begin + nrange), the end < 2^32 - 1
+	const vgx_draw* draws; const vgx_draw_state* draw_state; // [num_draws], checked by the host
+	uint32_t num_draws;
+	uint32_t nqueries;                // <= VGX_PICK_MAX_QUERIES
+	const vgx_pick_query* queries;
+	vgx_pick_hit* hits;
+	uint32_t* status;                 // the caller's dev_status or null
+	VgxPickfMesh* mesh_state;         // [nrange] (context scratch, as everything below): vgx_pick.h's record, VGX_PICKF_* flags beside the mode
+	uint32_t* cand_mesh;              // [nrange] the candidates (mesh - mesh_begin), dense and ascending
+	uint32_t* tri_cand;               // [nrange] the triangle candidates as candidate numbers, dense and ascending
+	uint64_t* tri_prefix;             // [nrange + 1] exclusive prefix of their triangle counts, the total behind it
+	uint32_t* con_cand;               // [nrange] the contour candidates as candidate numbers
+	uint32_t* cover;                  // [nrange][8] per candidate one bit per query: covered at the point under the query's flags; zeroed by the scan
+	uint64_t* totals;                 // candidates, candidate triangles, contour candidates, meshes with draw >= num_draws
+};
+void vgx_launch_pick_frame(const VgxPickfArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, uint32_t grid, hipStream_t s);
+
 // incremental update of a submitted frame (vgx_update.hip)
 struct VgxUpdateArgs
 {

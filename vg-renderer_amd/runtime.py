@@ -672,6 +672,27 @@ def pick(ctx, frame, queries_dev, nqueries, bounds_dev=None, hits_dev=None):
     return hits_dev
 
 
+def pick_frame(ctx, frame, draws_dev, draw_state_dev, num_draws, queries_dev, nqueries, bounds_dev=None, mesh_begin=0, mesh_end=None, hits_dev=None,
+               dev_status=None):
+    """pick() for the image raster_concave() draws: a mesh is hit where a sample of it would take effect under its draw's scissor and the
+    clip region its draw names, the meshes of Clip draws stamp and are never hit, a mesh of kind capi.MESH_CONTOURS is hit by its winding
+    rule (triangle = capi.PICK_NONE), and a point on a seam names the triangle the image draws (vgx_pick_frame in include/vgx.h).
+    draws_dev / draw_state_dev / num_draws as in raster_frame(); the mesh range must hold the clip meshes of every region it uses.
+    Returns (hits, dev_status): a uint8 device tensor of nqueries 16-byte vgx_pick_hit records (hits_dev when given) and an int32 [1]
+    tensor that holds VGX_OK, or VGX_E_INVALID_ARG when a mesh names a draw >= num_draws (every hit is "none" then). Asynchronous."""
+    import torch
+    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
+    if hits_dev is None:
+        hits_dev = torch.empty(max(int(nqueries), 1) * 16, dtype=torch.uint8, device=queries_dev.device)
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=hits_dev.device)
+    st = capi.RasterDraws(draws_dev.data_ptr() if num_draws else None, draw_state_dev.data_ptr() if num_draws else None, int(num_draws), 0)
+    _check(lib().vgx_pick_frame(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
+                                0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), queries_dev.data_ptr() if nqueries else None, int(nqueries),
+                                hits_dev.data_ptr(), dev_status.data_ptr(), _stream_ptr()), "vgx_pick_frame")
+    return hits_dev, dev_status
+
+
 # ---- rendering to an image (vgx_raster) -----------------------------------------------------------------------------------
 def raster(ctx, frame, width, height, x0=0, y0=0, scissor=None, clear_color=None, bounds_dev=None, mesh_begin=0, mesh_end=None, image=None,
            dev_status=None):
