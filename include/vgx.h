@@ -1068,6 +1068,72 @@ int vgx_cache_update(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_
                      const uint64_t* dev_ndirty /* DEVICE, may be NULL */, const vgx_update_frame* frame,
                      uint32_t* dev_status, void* stream);
 
+/* ---- damage redraw: redraw only the tiles an edit can have changed -------------------------------------------------------------
+ * vgx_cache_update rewrites a few instances; vgx_raster_concave would draw the whole frame again. Every effect a mesh has on a
+ * sample -- coverage, a contour mesh's winding rule, a clip stamp -- starts with "the sample lies in the mesh's box", so redrawing
+ * the 16 x 16 tiles the OLD and the NEW boxes of the edited meshes reach gives the image of a full redraw, byte for byte.
+ *
+ * The damage bitmap. TW = ceil(width / 16), TH = ceil(height / 16), NT = TW * TH. Tile (tx, ty) covers image pixels
+ * [16 tx, 16 tx + 16) x [16 ty, 16 ty + 16) -- aligned to pixel (0, 0) of the image, not to a scissor -- and is bit k = ty * TW + tx:
+ * word k >> 5, bit k & 31 of a DEVICE array of vgx_damage_words(width, height) = ceil(NT / 32) uint32 the caller owns and zeroes.
+ * The mark calls only OR into it; bits at or beyond NT are never set and never read. Every bit set: everything is damaged.
+ * The tiles a box B = (minx, miny, maxx, maxy) -- one vgx_mesh_bounds record -- reaches in an image of width x height at origin
+ * (x0, y0): the columns [i0, i1] of the pixels whose sample x0 + i + 0.5 may lie in [minx, maxx] and the rows [j0, j1] likewise, by
+ * the span rule of the raster (csrc/vgx_raster.h, vgx_raster_span, over [0, width) and [0, height)): with a = minx - (x0 + 0.5) and
+ * b = maxx - (x0 + 0.5) in binary64, i0 = max(0, floor(a)) and i1 = min(width - 1, ceil(b)), none if not i0 <= i1; the tiles are
+ * [i0 / 16, i1 / 16] x [j0 / 16, j1 / 16]. A superset of the pixels the box holds, never less. If either span is empty the box
+ * reaches no tile: the empty box of a 0-vertex mesh, a box outside the image. A NaN bound compares false and bounds nothing, as in
+ * the raster: its side of the span stays at the image's edge. Neither the target's scissor nor the mesh's kind or index count
+ * plays a part.
+ *
+ * vgx_damage_meshes marks the boxes mesh_bounds[m], m in [mesh_begin, min(mesh_end, num_meshes)): for a range of draws that was
+ * tessellated again, once over the old frame's table and once over the new one's. vgx_damage_instances marks the boxes of the frame
+ * meshes [slots[d].first_mesh, slots[d+1].first_mesh) of every d of the effective dirty list, whose rules are vgx_cache_update's:
+ * dirty[0 .. min(ndirty, *dev_ndirty)), any order, duplicates allowed. An entry with d >= ninst, slots[d+1].first_mesh > num_meshes or
+ * slots[d+1].first_mesh < slots[d].first_mesh is INVALID and is skipped; dev_status (DEVICE uint32, may be NULL) is
+ * VGX_E_INVALID_ARG if any entry was invalid, else VGX_OK, whatever the order of the work. ndirty == 0 writes nothing but the
+ * status. Of `target` only width, height, x0 and y0 are read (pixels may be NULL): the tile grid is the one the raster call uses.
+ * The chain, all on one stream: zero the bits; vgx_damage_instances (the old boxes); vgx_cache_update with the same table as
+ * frame->mesh_bounds; vgx_damage_instances (the new boxes); vgx_raster_damaged with VGX_RASTER_CLEAR.
+ * Host return values: VGX_OK once the work is enqueued; VGX_E_INVALID_ARG for null or misaligned pointers (mesh_bounds 16-byte;
+ * slots, dev_ndirty 8-byte; dirty, tile_bits, dev_status 4-byte) or a target wider or higher than 16384 or with |x0|, |y0| > 2^23;
+ * VGX_E_RANGE for num_meshes >= 2^32 - 1, ninst or ndirty >= 2^32; VGX_E_HIP. Asynchronous; scratch of their own (8 bytes per listed
+ * entry), so a counted state survives.
+ *
+ * vgx_raster_damaged is vgx_raster_concave word for word with ONE difference: a pixel is written, cleared or blended only if it
+ * lies inside the image, inside the target's scissor AND in a tile whose bit is set. Sample, coverage, winding rule, colour, blend,
+ * order, draw scissor, stamp, In / Out, sampled and painted meshes and the ranking of VGX_E_RANGE / VGX_E_INVALID_ARG hold as they
+ * stand; VGX_E_INVALID_ARG for a mesh with draw >= num_draws is decided over every mesh of the range, whatever the bits say. With
+ * every bit set the call leaves vgx_raster_concave's bytes and status; with no bit set it writes nothing, the clear included.
+ * The property: let I0 be the image vgx_raster_concave with VGX_RASTER_CLEAR draws of frame F0 and I1 that of F1, and let every tile
+ * be marked that the box of any mesh that differs between F0 and F1 reaches under either frame's boxes. Then vgx_raster_damaged of
+ * F1 over I0, with the same target, tables and VGX_RASTER_CLEAR, leaves I1 byte for byte. Proof:
+ *   a sample outside every such box sees the same sequence of effects in both frames, stamps included, so its pixel of I0 is I1's;
+ *   a sample in a marked tile is cleared and receives ALL meshes of the range through the tile's bin entries, as in the full call;
+ *   a sample in an unmarked tile lies outside every such box (a box's tiles hold all its samples) and is not written.
+ * A bin entry is a pair of a mesh and a MARKED tile its box reaches inside the two scissors. The call sorts a WINDOW of entries, not
+ * the capacity a full render left behind: min(max_entries, the entry tables' capacity) when max_entries != 0, else what the previous
+ * vgx_raster_damaged on this context measured plus 12.5 % + 256 once that has come back to the host, else 16384 (cut to meshes x
+ * tiles of the scissor in every case). A call with more entries than its window ends with VGX_E_GROWN as vgx_raster does: nothing
+ * is written, the need comes back to the host behind the call, and the next call -- once the need has landed -- takes a window of
+ * at least that need, max_entries or not: the same call repeated reaches VGX_OK. The count is kept apart from the full calls', so
+ * a full render in between does not widen the window. Host return values, alignment and the scratch are vgx_raster_concave's;
+ * `damage` NULL, damage->tile_bits NULL or misaligned (4-byte) or damage->reserved != 0: VGX_E_INVALID_ARG. */
+uint64_t vgx_damage_words(uint32_t width, uint32_t height); /* HOST: ceil(ceil(width / 16) * ceil(height / 16) / 32) */
+int vgx_damage_meshes(vgx_ctx* ctx, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, uint64_t num_meshes,
+                      const vgx_raster_target* target, uint32_t* tile_bits, void* stream);
+int vgx_damage_instances(vgx_ctx* ctx, const float* mesh_bounds, uint64_t num_meshes, const vgx_cache_slot* slots, uint64_t ninst,
+                         const uint32_t* dirty, uint64_t ndirty, const uint64_t* dev_ndirty /* may be NULL */,
+                         const vgx_raster_target* target, uint32_t* tile_bits, uint32_t* dev_status /* may be NULL */, void* stream);
+typedef struct vgx_raster_damage {
+	const uint32_t* tile_bits;    /* DEVICE [vgx_damage_words(width, height)] */
+	uint32_t max_entries;         /* HOST: bin entries this call sorts at most; 0 = the library chooses (above) */
+	uint32_t reserved;            /* 0 */
+} vgx_raster_damage;
+int vgx_raster_damaged(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
+                       const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints,
+                       const vgx_raster_target* target, const vgx_raster_damage* damage, uint32_t* dev_status, void* stream);
+
 /* ---- concave fills with AA fringes -------------------------------------------------
  * strokerConcaveFillEndAA (src/stroker.cpp:868-1006) alternates libtess2 and the stroker's own loops:
  *   (1) tessTesselate(TESS_BOUNDARY_CONTOURS) of the contours added with strokerConcaveFillAddContour     [caller, CPU]

@@ -187,6 +187,13 @@ class UpdateFrame(C.Structure):  # vgx_update_frame: device pointers (mesh_bound
     _fields_ = [("pos", C.c_void_p), ("color", C.c_void_p), ("num_vertices", C.c_uint64), ("num_meshes", C.c_uint64), ("mesh_bounds", C.c_void_p)]
 
 
+class RasterDamage(C.Structure):  # vgx_raster_damage: `tile_bits` is a device pointer (vgx_damage_words(width, height) uint32)
+    _fields_ = [("tile_bits", C.c_void_p), ("max_entries", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(RasterDamage) == 16
+
+
 class Assembly(C.Structure):
     _fields_ = [("drawcmds", C.c_void_p), ("cap_drawcmds", C.c_uint64), ("dev_num_drawcmds", C.c_void_p),
                 ("max_vb_vertices", C.c_uint32), ("flags", C.c_uint32), ("uv", C.c_void_p), ("uv_bytes", C.c_uint32),
@@ -292,7 +299,13 @@ VGX_SYMBOLS = {
     "vgx_cache_layout": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_cache_update": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                    C.POINTER(UpdateFrame), C.c_void_p, C.c_void_p]),
-    "vgx_last_hip_error": (C.c_int, [C.c_void_p]),
+    "vgx_damage_words": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "vgx_damage_meshes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
+    "vgx_damage_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(RasterTarget),
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_raster_damaged": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.POINTER(RasterTextures),
+                                    C.POINTER(RasterPaints), C.POINTER(RasterTarget), C.POINTER(RasterDamage), C.c_void_p, C.c_void_p]),
+    "vgx_last_hip_error":(C.c_int, [C.c_void_p]),
     "vgx_status_string": (C.c_char_p, [C.c_int]),
     "vgx_version": (C.c_uint32, []),
     "vgx_scratch_bytes": (C.c_uint64, [C.c_void_p]),

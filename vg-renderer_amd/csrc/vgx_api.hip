@@ -19,6 +19,7 @@
 #include "vgx_dash.h"
 #include "vgx_update.h"
 #include "vgx_raster.h"
+#include "vgx_damage.h"
 #include "vgx_pick.h"
 #include "vgx_concave_lane.h"
 #include "vgx_scratch.h"
@@ -154,7 +155,14 @@ struct vgx_ctx
 	Buf<uint32_t> rasTileContour;         // vgx_raster_concave alone: the same for "a contour mesh reaches it"
 	DevBuf rasSortTemp, rasPartial;      // rasPartial: slice sums (views: as `partial`)
 	HostMirror<unsigned long long> ras;
-	uint32_t optPickGrid;                // workgroups of k_pick_tris (VGX_PICK_GRID)
+	// vgx_raster_damaged: the frame calls' tables, but a mirror of its own -- status and entry count of the last DAMAGED call -- and what
+	// the host learned from it: the count (the next call's sort window, vgx_damage.h) and whether that call ended with VGX_E_GROWN (the
+	// next window holds its need whatever max_entries says). A full render in between touches neither
+	HostMirror<unsigned long long> rasDmg; bool dmgKnown, dmgGrown; uint64_t dmgNeed;
+	// vgx_damage_instances (vgx_damage.hip): the flag word (in 16 bytes) and the mesh prefix of the listed entries, the scan's slice sums
+	// (views: as `partial`). Its own: a counted state, and a vgx_cache_update in flight, survive the call
+	DevBuf dmgPrefix, dmgPartial;
+	uint32_t optPickGrid;               // workgroups of k_pick_tris (VGX_PICK_GRID)
 	// vgx_dash (vgx_dash.hip): per-draw patterns, per-list records, per-segment prefix sums (S and the overflow guard), per-range sums; the
 	// segment count of the last call in pinned memory (copied behind the call, read by the next call once its event has passed: a call
 	// whose lists outgrew dashG ends with VGX_E_GROWN and the next one grows first, as vgx_tessellate_immediate does)
@@ -1124,7 +1132,7 @@ int vgx_destroy(vgx_ctx* ctx)
 	vgx_scratch_release(ctx->scratch);
 	if (ctx->hostTotals) { (void)hipHostFree(ctx->hostTotals); }
 	if (ctx->hostF1) { (void)hipHostFree(ctx->hostF1); }
-	ctx->imm.release(); ctx->dash.release(); ctx->df.release(); ctx->ras.release();
+	ctx->imm.release(); ctx->dash.release(); ctx->df.release(); ctx->ras.release(); ctx->rasDmg.release();
 	if (ctx->hostPs) { (void)hipHostFree(ctx->hostPs); }
 	if (ctx->psImage) { (void)hipHostFree(ctx->psImage); }
 	for (int i = 0; i < VGX_PS_POOL; ++i) { if (ctx->psPool[i].p) { (void)hipFree(ctx->psPool[i].p); } }
@@ -2833,14 +2841,17 @@ int vgx_raster_reserve(vgx_ctx* ctx, uint64_t num_meshes, uint64_t num_bin_entri
 
 namespace {
 
-// The five calls are one body; `level` (VGX_RL_*, vgx_raster.h) says which pointers count and which kernel family runs
+// The five calls are one body; `level` (VGX_RL_*, vgx_raster.h) says which pointers count and which kernel family runs. `damage`
+// (vgx_raster_damaged, at VGX_RL_CONCAVE; else null) restricts the call to the marked tiles and gives it a sort window of its own
 int rasterCall(int level, vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
-               const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
+               const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, const vgx_raster_damage* damage,
+               uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
 	if (!ctx) { return VGX_E_INVALID_ARG; }
 	int st = vgx_raster_check_args(level, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, dev_status);
 	if (st != VGX_OK) { return st; }
+	if (damage && (!damage->tile_bits || ((uintptr_t)damage->tile_bits & 3u) || damage->reserved != 0u)) { return VGX_E_INVALID_ARG; }
 	const vgx_raster_target& t = *target;
 	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
 	hipStream_t s = (hipStream_t)stream;
@@ -2857,14 +2868,31 @@ int rasterCall(int level, vgx_ctx* ctx, const vgx_cache_desc* frame, const float
 	a.tiles_x = (t.scissor[2] - 1) / VGX_RASTER_TILE - a.tile_x0 + 1; a.tiles_y = (t.scissor[3] - 1) / VGX_RASTER_TILE - a.tile_y0 + 1;
 	a.sentinel = a.tiles_w * ((t.height + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE); // <= 2^20
 	for (a.sort_bits = 1; (a.sentinel >> a.sort_bits) != 0; ++a.sort_bits) { }
-	if ((st = ctx->ras.create(ctx, 2)) != VGX_OK) { return st; }
-	// the entry tables: what the last call measured (once that has arrived), else what they hold, else one entry per mesh
-	uint64_t entries = ctx->rasKeys.cap ? ctx->rasKeys.items() - 1 : nrange;
-	if (ctx->ras.landed() && ctx->ras.host[0] == VGX_E_GROWN && ctx->ras.host[1] > entries) { entries = ctx->ras.host[1]; }
-	if ((st = rasterEnsure(ctx, nrange, entries)) != VGX_OK) { return st; }
-	a.entry_cap = minOf({ ctx->rasKeys.items(), ctx->rasVals.items(), ctx->rasSortedKeys.items(), ctx->rasSortedVals.items() }) - 1;
+	HostMirror<unsigned long long>& mirror = damage ? ctx->rasDmg : ctx->ras;
+	if ((st = mirror.create(ctx, 2)) != VGX_OK) { return st; }
 	// no mesh has more entries than the scissor has tiles: the sort need not look further
 	const uint64_t bound = nrange * ((uint64_t)a.tiles_x * a.tiles_y);
+	// the entry tables: what the last call measured (once that has arrived), else what they hold, else one entry per mesh
+	uint64_t entries = ctx->rasKeys.cap ? ctx->rasKeys.items() - 1 : nrange;
+	uint64_t window = ~0ull;
+	if (!damage) {
+		if (ctx->ras.landed() && ctx->ras.host[0] == VGX_E_GROWN && ctx->ras.host[1] > entries) { entries = ctx->ras.host[1]; }
+	} else {
+		// The damaged call sorts a window (include/vgx.h), not what a full render left the tables at: the caller's, or the last damaged
+		// call's count with head room, or the initial one -- and at least the need of a damaged call that ended with VGX_E_GROWN
+		if (mirror.landed() && (mirror.host[0] == VGX_OK || mirror.host[0] == VGX_E_GROWN)) {
+			ctx->dmgKnown = true; ctx->dmgNeed = mirror.host[1]; ctx->dmgGrown = mirror.host[0] == VGX_E_GROWN;
+		}
+		window = damage->max_entries ? (damage->max_entries < entries ? damage->max_entries : entries)
+		                             : (ctx->dmgKnown ? vgx_damage_head_room(ctx->dmgNeed) : (uint64_t)VGX_DAMAGE_INITIAL_WINDOW);
+		if (ctx->dmgGrown && ctx->dmgNeed > window) { window = vgx_damage_head_room(ctx->dmgNeed); }
+		if (window > bound) { window = bound; }
+		if (window > 0xFFFFFFFFull) { window = 0xFFFFFFFFull; }
+		if (window > entries) { entries = window; }
+	}
+	if ((st = rasterEnsure(ctx, nrange, entries)) != VGX_OK) { return st; }
+	a.entry_cap = minOf({ ctx->rasKeys.items(), ctx->rasVals.items(), ctx->rasSortedKeys.items(), ctx->rasSortedVals.items() }) - 1;
+	if (window < a.entry_cap) { a.entry_cap = window; }
 	a.sort_n = bound < a.entry_cap ? bound : a.entry_cap;
 	size_t sortBytes = 0;
 	if (a.sort_n) {
@@ -2912,38 +2940,108 @@ int rasterCall(int level, vgx_ctx* ctx, const vgx_cache_desc* frame, const float
 			noteHip(ctx, hipMemsetAsync(ctx->rasTileContour.p, 0, words * sizeof(uint32_t), s));
 			f.tile_contour = ctx->rasTileContour.ptr();
 		}
+		if (damage) { f.damage = damage->tile_bits; }
 		noteHip(ctx, vgx_launch_raster_frame(f, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
 	}
 	// status and entry count to the mirror, for the next call (never waited for)
-	ctx->ras.push(ctx, a.state, s);
+	mirror.push(ctx, a.state, s);
 	return launchStatus(ctx);
 }
 
 } // namespace
 
+int vgx_raster_damaged(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
+                       const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target,
+                       const vgx_raster_damage* damage, uint32_t* dev_status, void* stream)
+{
+	if (!damage) { return VGX_E_INVALID_ARG; }
+	return rasterCall(VGX_RL_CONCAVE, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, damage, dev_status, stream);
+}
+
+// ---- damage marks (vgx_damage.hip) --------------------------------------------------------------------------------------------
+uint64_t vgx_damage_words(uint32_t width, uint32_t height)
+{
+	return ((uint64_t)vgx_damage_tiles_w(width) * vgx_damage_tiles_w(height) + 31u) / 32u;
+}
+
+namespace {
+
+// what both mark calls ask of the target and the bitmap; fills the target's part of the arguments
+static int damageTarget(const vgx_raster_target* t, const uint32_t* tile_bits, VgxDamageArgs* a)
+{
+	if (!t || !tile_bits || ((uintptr_t)tile_bits & 3u)) { return VGX_E_INVALID_ARG; }
+	if (t->width > 16384u || t->height > 16384u || t->x0 > (1 << 23) || t->x0 < -(1 << 23) || t->y0 > (1 << 23) || t->y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
+	memset(a, 0, sizeof(*a));
+	a->x0 = t->x0; a->y0 = t->y0; a->width = t->width; a->height = t->height; a->tiles_w = vgx_damage_tiles_w(t->width);
+	a->tile_bits = const_cast<uint32_t*>(tile_bits);
+	return VGX_OK;
+}
+
+} // namespace
+
+// Neither call touches a counted state, nor the scratch of vgx_cache_update: the chain mark -> update -> mark runs on one stream
+int vgx_damage_meshes(vgx_ctx* ctx, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, uint64_t num_meshes, const vgx_raster_target* target,
+                      uint32_t* tile_bits, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || (num_meshes && !mesh_bounds) || ((uintptr_t)mesh_bounds & 15u)) { return VGX_E_INVALID_ARG; }
+	VgxDamageArgs a;
+	const int st = damageTarget(target, tile_bits, &a);
+	if (st != VGX_OK) { return st; }
+	if (num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	const uint64_t end = mesh_end < num_meshes ? mesh_end : num_meshes;
+	a.mesh_bounds = mesh_bounds; a.num_meshes = num_meshes; a.mesh_begin = mesh_begin; a.nrange = mesh_begin < end ? end - mesh_begin : 0;
+	vgx_launch_damage_meshes(a, (hipStream_t)stream);
+	return launchStatus(ctx);
+}
+
+int vgx_damage_instances(vgx_ctx* ctx, const float* mesh_bounds, uint64_t num_meshes, const vgx_cache_slot* slots, uint64_t ninst, const uint32_t* dirty,
+                         uint64_t ndirty, const uint64_t* dev_ndirty, const vgx_raster_target* target, uint32_t* tile_bits, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || (ndirty && (!dirty || !slots)) || (ndirty && num_meshes && !mesh_bounds)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)slots & 7u) || ((uintptr_t)dev_ndirty & 7u) || ((uintptr_t)dirty & 3u) || ((uintptr_t)dev_status & 3u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	VgxDamageArgs a;
+	int st = damageTarget(target, tile_bits, &a);
+	if (st != VGX_OK) { return st; }
+	if (num_meshes >= 0xFFFFFFFFull || ninst > 0xFFFFFFFFull || ndirty > 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	hipStream_t s = (hipStream_t)stream;
+	// [flag word, padded to 16 bytes][mesh prefix: ndirty + 1]
+	if ((st = ensure(ctx, ctx->dmgPrefix, 16 + (ndirty + 1) * sizeof(uint64_t))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->dmgPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->dmgPrefix.p, 0, 16, s));
+	a.mesh_bounds = mesh_bounds; a.num_meshes = num_meshes; a.slots = slots; a.ninst = ninst; a.dirty = dirty; a.ndirty = ndirty; a.dev_ndirty = dev_ndirty;
+	a.flags = (uint32_t*)ctx->dmgPrefix.p; a.mesh_prefix = (uint64_t*)((char*)ctx->dmgPrefix.p + 16);
+	a.status = dev_status;
+	vgx_launch_damage_instances(a, ctx->dmgPartial.p, s);
+	return launchStatus(ctx);
+}
+
 int vgx_raster(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
-	return rasterCall(VGX_RL_PLAIN, ctx, frame, mesh_bounds, mesh_begin, mesh_end, nullptr, nullptr, nullptr, target, dev_status, stream);
+	return rasterCall(VGX_RL_PLAIN, ctx, frame, mesh_bounds, mesh_begin, mesh_end, nullptr, nullptr, nullptr, target, nullptr, dev_status, stream);
 }
 
 int vgx_raster_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                      const vgx_raster_draws* state, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
-	return rasterCall(VGX_RL_FRAME, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, nullptr, nullptr, target, dev_status, stream);
+	return rasterCall(VGX_RL_FRAME, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, nullptr, nullptr, target, nullptr, dev_status, stream);
 }
 
 int vgx_raster_textured(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                         const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_target* target, uint32_t* dev_status, void* stream)
 {
-	return rasterCall(VGX_RL_TEXTURED, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, nullptr, target, dev_status, stream);
+	return rasterCall(VGX_RL_TEXTURED, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, nullptr, target, nullptr, dev_status, stream);
 }
 
 int vgx_raster_painted(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                        const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target,
                        uint32_t* dev_status, void* stream)
 {
-	return rasterCall(VGX_RL_PAINTED, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, dev_status, stream);
+	return rasterCall(VGX_RL_PAINTED, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, nullptr, dev_status, stream);
 }
 
 // HOST only, no context: the decoder's paint list scattered by handle into the two tables vgx_raster_painted indexes; holes marked
@@ -2951,7 +3049,7 @@ int vgx_raster_concave(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* m
                        const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target,
                        uint32_t* dev_status, void* stream)
 {
-	return rasterCall(VGX_RL_CONCAVE, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, dev_status, stream);
+	return rasterCall(VGX_RL_CONCAVE, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, nullptr, dev_status, stream);
 }
 
 int vgx_paint_tables(const vgx_paint* paints, uint32_t n, vgx_paint* gradients, uint32_t cap_gradients, vgx_paint* patterns, uint32_t cap_patterns)

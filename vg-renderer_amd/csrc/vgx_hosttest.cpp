@@ -599,6 +599,7 @@ int vgxt_pick_frame(const vgx_cache_desc* frame, const float* mesh_bounds, uint6
 }
 
 #include "vgx_raster.h"
+#include "vgx_damage.h"
 #include "vgx_concave_lane.h"
 
 extern "C" {
@@ -701,9 +702,15 @@ int vgxt_raster(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t 
 // The frame-level calls on the host: vgxt_raster's loop with the per-draw state of vgx_raster.h, a stamp image of its own and, as far as
 // the level (VGX_RL_*) goes, the sampling and the paint functions. HOST pointers throughout, the images' pixels, the UV stream and the
 // paint tables included. The meshes are looked at twice: first for an invalid one (nothing may be written then), then drawn.
+// `damage` (vgxt_raster_damaged, else null = every tile): a pixel outside the marked tiles is neither cleared nor drawn to
+static bool raster_pixel_damaged(const uint32_t* damage, const vgx_raster_target& t, uint32_t i, uint32_t j)
+{
+	return !damage || vgx_damage_bit(damage, (j / VGX_RASTER_TILE) * vgx_damage_tiles_w(t.width) + i / VGX_RASTER_TILE);
+}
+
 // One contour mesh of vgx_raster_concave: per pixel of the box inside the mesh's rectangle, W over the valid edges, then the flush
 static void raster_contour_mesh(const vgx_cache_desc* frame, const vgx_mesh& me, const float* box, const VgxRasterMeshState& ms, const VgxRasterPaint& pr,
-                                const vgx_raster_target& t, uint32_t* stamp)
+                                const vgx_raster_target& t, uint32_t* stamp, const uint32_t* damage)
 {
 	uint32_t a0, a1, b0, b1;
 	if (!vgx_raster_span(box[0], box[2], t.x0, ms.rect[0], ms.rect[2], &a0, &a1) || !vgx_raster_span(box[1], box[3], t.y0, ms.rect[1], ms.rect[3], &b0, &b1)) { return; }
@@ -713,6 +720,7 @@ static void raster_contour_mesh(const vgx_cache_desc* frame, const vgx_mesh& me,
 	const auto pfetch = [&pr](uint32_t x, uint32_t y) { return pr.im.pixels[(uint64_t)y * pr.im.stride + x]; };
 	for (uint32_t j = b0; j <= b1; ++j) {
 		for (uint32_t i = a0; i <= a1; ++i) {
+			if (!raster_pixel_damaged(damage, t, i, j)) { continue; }
 			const double px = (double)(t.x0 + (int32_t)i) + 0.5, py = (double)(t.y0 + (int32_t)j) + 0.5;
 			int32_t W = 0;
 			for (uint32_t k = 0; k < me.num_indices / 2u; ++k) {
@@ -731,10 +739,13 @@ static void raster_contour_mesh(const vgx_cache_desc* frame, const vgx_mesh& me,
 }
 
 static int raster_frame_loop(int level, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
-                             const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status)
+                             const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status,
+                             const vgx_raster_damage* dmg = nullptr)
 {
 	const int rc = vgx_raster_check_args(level, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, status);
 	if (rc != VGX_OK) { return rc; }
+	if (dmg && (!dmg->tile_bits || ((uintptr_t)dmg->tile_bits & 3u) || dmg->reserved != 0u)) { return VGX_E_INVALID_ARG; }
+	const uint32_t* const damage = dmg ? dmg->tile_bits : nullptr; // (max_entries: there is no sort here, and no window to outgrow)
 	const vgx_raster_target& t = *target;
 	if (status) { *status = VGX_OK; }
 	if (t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3]) { return VGX_OK; }
@@ -769,7 +780,9 @@ static int raster_frame_loop(int level, const vgx_cache_desc* frame, const float
 	for (size_t k = 0; k < (size_t)t.width * t.height; ++k) { stamp[k] = VGX_RASTER_STAMP_NONE; }
 	if (t.flags & VGX_RASTER_CLEAR) {
 		for (uint32_t j = t.scissor[1]; j < t.scissor[3]; ++j) {
-			for (uint32_t i = t.scissor[0]; i < t.scissor[2]; ++i) { t.pixels[(uint64_t)j * t.stride + i] = t.clear_color; }
+			for (uint32_t i = t.scissor[0]; i < t.scissor[2]; ++i) {
+				if (raster_pixel_damaged(damage, t, i, j)) { t.pixels[(uint64_t)j * t.stride + i] = t.clear_color; }
+			}
 		}
 	}
 	for (uint64_t m = mesh_begin; m < end; ++m) {
@@ -787,7 +800,7 @@ static int raster_frame_loop(int level, const vgx_cache_desc* frame, const float
 		VgxRasterRect r;
 		if (ms.mode == VGX_RF_NOTHING || !vgx_raster_mesh_tiles(me, (mesh_bounds ? mesh_bounds : own) + 4 * m, t.x0, t.y0, ms.rect, level, &r)) { continue; }
 		if (ms.pad & VGX_RT_CONTOUR) { // the winding number of every sample the box can hold, over all the mesh's edges, then rule and colour
-			raster_contour_mesh(frame, me, (mesh_bounds ? mesh_bounds : own) + 4 * m, ms, pr, t, stamp);
+			raster_contour_mesh(frame, me, (mesh_bounds ? mesh_bounds : own) + 4 * m, ms, pr, t, stamp, damage);
 			continue;
 		}
 		const uint16_t* ip = frame->idx + me.first_index;
@@ -808,6 +821,7 @@ static int raster_frame_loop(int level, const vgx_cache_desc* frame, const float
 			if (!vgx_raster_span(T.minx, T.maxx, t.x0, ms.rect[0], ms.rect[2], &a0, &a1) || !vgx_raster_span(T.miny, T.maxy, t.y0, ms.rect[1], ms.rect[3], &b0, &b1)) { continue; }
 			for (uint32_t j = b0; j <= b1; ++j) {
 				for (uint32_t i = a0; i <= a1; ++i) {
+					if (!raster_pixel_damaged(damage, t, i, j)) { continue; }
 					uint32_t* const p = t.pixels + (uint64_t)j * t.stride + i;
 					const double px = (double)(t.x0 + (int32_t)i) + 0.5, py = (double)(t.y0 + (int32_t)j) + 0.5;
 					uint32_t* const sp = stamp + (size_t)j * t.width + i;
@@ -957,5 +971,45 @@ int vgxt_cache_update(const vgx_cache_desc* cache, const vgx_cache_instance* ins
 	}
 	return vgx_update_status(flags);
 }
+
+// The damage marks on the host: the functions of vgx_damage.h box after box, ORing plainly. HOST pointers. vgxt_damage_instances walks
+// the list in the order given and returns the status the device call leaves in dev_status; vgxt_damage_meshes returns VGX_OK.
+static void damage_mark_host(const float* box, const vgx_raster_target* t, uint32_t* bits)
+{
+	VgxRasterRect r;
+	if (!vgx_damage_box_tiles(box, t->x0, t->y0, t->width, t->height, &r)) { return; }
+	vgx_tile_rect_words(r, vgx_damage_tiles_w(t->width), [bits](uint32_t w, uint32_t mask) { bits[w] |= mask; });
+}
+
+int vgxt_damage_meshes(const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, uint64_t num_meshes, const vgx_raster_target* target, uint32_t* tile_bits)
+{
+	const uint64_t end = mesh_end < num_meshes ? mesh_end : num_meshes;
+	for (uint64_t m = mesh_begin; m < end; ++m) { damage_mark_host(mesh_bounds + 4 * m, target, tile_bits); }
+	return VGX_OK;
+}
+
+int vgxt_damage_instances(const float* mesh_bounds, uint64_t num_meshes, const vgx_cache_slot* slots, uint64_t ninst, const uint32_t* dirty, uint64_t ndirty,
+                          const uint64_t* ndirty_limit, const vgx_raster_target* target, uint32_t* tile_bits)
+{
+	int status = VGX_OK;
+	const uint64_t nlist = (ndirty_limit && *ndirty_limit < ndirty) ? *ndirty_limit : ndirty;
+	for (uint64_t j = 0; j < nlist; ++j) {
+		uint64_t first, count;
+		if (!vgx_damage_entry(slots, ninst, num_meshes, dirty[j], &first, &count)) { status = VGX_E_INVALID_ARG; continue; }
+		for (uint64_t k = 0; k < count; ++k) { damage_mark_host(mesh_bounds + 4 * (first + k), target, tile_bits); }
+	}
+	return status;
+}
+
+// vgx_raster_damaged on the host: the frame-level loop at the concave level, writing inside the marked tiles alone
+int vgxt_raster_damaged(const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
+                        const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target, const vgx_raster_damage* damage,
+                        uint32_t* status)
+{
+	if (!damage) { return VGX_E_INVALID_ARG; }
+	return raster_frame_loop(VGX_RL_CONCAVE, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, status, damage);
+}
+
+uint64_t vgxt_damage_words(uint32_t width, uint32_t height) { return ((uint64_t)vgx_damage_tiles_w(width) * vgx_damage_tiles_w(height) + 31u) / 32u; }
 
 }

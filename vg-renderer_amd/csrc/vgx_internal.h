@@ -530,7 +530,30 @@ struct VgxRasterFrameArgs
 	uint32_t* tile_paint;             // [(sentinel + 31) / 32] as tile_tex: a painted mesh has an entry there (context scratch)
 	// at VGX_RL_CONCAVE, else zero
 	uint32_t* tile_contour;           // [(sentinel + 31) / 32] as tile_tex: a contour mesh has an entry there (context scratch)
+	// vgx_raster_damaged (at VGX_RL_CONCAVE), else null: the kernels without the DAMAGE parameter run and never look at it
+	const uint32_t* damage;           // [(sentinel + 31) / 32] the caller's: one bit per tile of the image, "redraw it"
 };
 hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
+
+// damage marks (vgx_damage.hip): the boxes of a mesh range, or of the frame meshes of the listed instances, ORed into a tile bitmap
+struct VgxDamageArgs
+{
+	const float* mesh_bounds;         // [num_meshes][4], 16-byte aligned
+	uint64_t num_meshes;
+	uint64_t mesh_begin, nrange;      // vgx_damage_meshes: [mesh_begin, mesh_begin + nrange), inside the table
+	const vgx_cache_slot* slots;      // vgx_damage_instances: [ninst + 1]
+	uint64_t ninst;
+	const uint32_t* dirty;            // [ndirty]
+	uint64_t ndirty;
+	const uint64_t* dev_ndirty;       // or null: the list is dirty[0 .. min(ndirty, *dev_ndirty))
+	int32_t x0, y0;                   // the target
+	uint32_t width, height, tiles_w;
+	uint32_t* tile_bits;              // the caller's bitmap
+	uint64_t* mesh_prefix;            // [ndirty + 1] exclusive scan of the listed entries' mesh counts (context scratch, as the next)
+	uint32_t* flags;                  // one word, zeroed: != 0 once an entry was invalid
+	uint32_t* status;                 // the caller's dev_status or null
+};
+void vgx_launch_damage_meshes(const VgxDamageArgs& a, hipStream_t s);
+void vgx_launch_damage_instances(const VgxDamageArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, hipStream_t s);
 
 #endif

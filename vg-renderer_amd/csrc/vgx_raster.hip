@@ -1,7 +1,8 @@
 // vgx_raster.hip -- a frame's mesh streams to an RGBA8 image on gfx950 (include/vgx.h: vgx_raster, vgx_raster_frame, vgx_raster_textured,
 // vgx_raster_painted, vgx_raster_concave; the arithmetic: vgx_raster.h). Two kernel families and one launch sequence (count, scan, entries,
 // sort, tiles): the plain family (k_raster_*) serves vgx_raster and carries no draw state, which measurably keeps it the faster one; the
-// frame family (k_rasterf_*, further down) serves the four frame-level calls, which differ in a level carried in the arguments.
+// frame family (k_rasterf_*, further down) serves the four frame-level calls, which differ in a level carried in the arguments, and
+// vgx_raster_damaged, the concave level restricted to the tiles of a damage bitmap (the DAMAGE instantiations; vgx_damage.h).
 //
 // Blending is not commutative: a pixel must see its triangles in ascending (mesh, triangle) order, and no atomic on a pixel gives
 // that. So a pixel belongs to ONE lane for the whole call: the image is cut into tiles of 16 x 16 pixels, a tile is one workgroup of
@@ -27,6 +28,7 @@
 #include "vgx_wave.h"
 #include "vgx_scan.h"
 #include "vgx_raster.h"
+#include "vgx_damage.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace {
@@ -207,6 +209,11 @@ __device__ __forceinline__ bool frame_rect(const VgxRasterFrameArgs& F, uint64_t
 	return vgx_raster_mesh_tiles(A.meshes[m], b, A.x0, A.y0, st.rect, F.level, r);
 }
 
+// DAMAGE (vgx_raster_damaged; every other call runs the instantiations without it -- DESIGN.md has the resource report that chose a
+// template parameter over a null-means-all pointer): a bin entry is a pair of a mesh and a MARKED tile (F.damage, vgx_damage.h). The
+// count takes the set bits of the mesh's tile rectangle, the entries pass emits those tiles, the tile kernel leaves an unmarked tile
+// ahead of the clear. The state of every mesh, and with it VGX_E_INVALID_ARG, is decided as without it
+template <bool DAMAGE>
 __global__ __launch_bounds__(256) void k_rasterf_count(VgxRasterFrameArgs F)
 {
 	const VgxRasterArgs& A = F.R;
@@ -223,7 +230,9 @@ __global__ __launch_bounds__(256) void k_rasterf_count(VgxRasterFrameArgs F)
 		vgx_raster_mesh_state(F.level, me, F.draws[me.draw].state_key, F.draw_state[me.draw], A.x0, A.y0, A.scissor, F.images, F.num_images,
 		                      F.gradients, F.num_gradients, F.patterns, F.num_patterns, &st);
 		VgxRasterRect r;
-		if (st.mode != VGX_RF_NOTHING && st.mode != VGX_RF_INVALID && frame_rect(F, m, st, &r)) { entries = (r.tx1 - r.tx0 + 1u) * (r.ty1 - r.ty0 + 1u); }
+		if (st.mode != VGX_RF_NOTHING && st.mode != VGX_RF_INVALID && frame_rect(F, m, st, &r)) {
+			entries = DAMAGE ? vgx_damage_rect_count(F.damage, r, A.tiles_w) : (r.tx1 - r.tx0 + 1u) * (r.ty1 - r.ty0 + 1u);
+		}
 	}
 	F.mesh_state[k] = st;
 	A.mesh_entries[k] = entries;
@@ -254,18 +263,8 @@ struct OpRasterFrameBin
 	}
 };
 
-// the tiles of rectangle r in a bitmap of one bit per tile: a row's tiles are consecutive bits, one atomic per word of 32, not per tile
-__device__ __forceinline__ void mark_tiles(uint32_t* bits, const VgxRasterRect& r, uint32_t tilesW)
-{
-	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
-		const uint32_t k0 = ty * tilesW + r.tx0, k1 = ty * tilesW + r.tx1; // < sentinel: the rectangle lies inside the image
-		for (uint32_t w = k0 >> 5; w <= (k1 >> 5); ++w) {
-			const uint32_t lo = w == (k0 >> 5) ? (k0 & 31u) : 0u, hi = w == (k1 >> 5) ? (k1 & 31u) : 31u;
-			atomicOr(&bits[w], (0xFFFFFFFFu >> (31u - hi)) & (0xFFFFFFFFu << lo));
-		}
-	}
-}
-
+// (mark_tiles: vgx_damage.h)
+template <bool DAMAGE>
 __global__ __launch_bounds__(256) void k_rasterf_entries(VgxRasterFrameArgs F)
 {
 	const VgxRasterArgs& A = F.R;
@@ -279,7 +278,12 @@ __global__ __launch_bounds__(256) void k_rasterf_entries(VgxRasterFrameArgs F)
 	if (!frame_rect(F, m, st, &r)) { return; } // (not taken: the count found entries)
 	uint64_t at = A.mesh_first[k]; // + the mesh's entries <= the total <= entry_cap: checked by finish()
 	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
-		for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx, ++at) { A.keys[at] = ty * A.tiles_w + tx; A.vals[at] = (uint32_t)m; }
+		for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx) {
+			const uint32_t key = ty * A.tiles_w + tx;
+			if (DAMAGE && !vgx_damage_bit(F.damage, key)) { continue; } // as many pass as the count found: the bits do not change under the call
+			A.keys[at] = key; A.vals[at] = (uint32_t)m;
+			++at;
+		}
 	}
 	// a level that cannot set a flag has no bitmap for it
 	if (st.pad & VGX_RT_SAMPLED) { mark_tiles(F.tile_tex, r, A.tiles_w); }
@@ -355,7 +359,7 @@ __device__ __forceinline__ bool contour_element(const VgxRasterArgs& A, const vg
 // to a private W, which lives across the batches of 256 records as d and S do. The flush is always kept -- the mesh's last edges may
 // be culled -- and applies fill rule, box and colour, then clears W for the next contour mesh. Records stay in (mesh, element) order,
 // so the mesh takes one place in painter's order
-template <bool TEX, bool PAINT, bool CONTOUR>
+template <bool TEX, bool PAINT, bool CONTOUR, bool DAMAGE>
 __global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
 {
 	static_assert(!CONTOUR || (TEX && PAINT), "the contour instantiation serves every class of tile");
@@ -373,6 +377,7 @@ __global__ __launch_bounds__(256) void k_rasterf_tiles(VgxRasterFrameArgs F)
 	if (A.state[0] != VGX_OK) { return; }
 	const uint32_t tx = A.tile_x0 + blockIdx.x, ty = A.tile_y0 + blockIdx.y;
 	const uint32_t key = ty * A.tiles_w + tx;
+	if (DAMAGE && !vgx_damage_bit(F.damage, key)) { return; } // block-uniform, ahead of the clear: the tile is not redrawn
 	if (tile_bit(F.tile_contour, key) != CONTOUR) { return; } // block-uniform: the tile of another instantiation
 	if (!CONTOUR && (tile_bit(F.tile_tex, key) != TEX || tile_bit(F.tile_paint, key) != PAINT)) { return; }
 	const uint32_t tid = threadIdx.x;
@@ -585,16 +590,27 @@ hipError_t vgx_launch_raster(const VgxRasterArgs& a, void* partial, void* sortTe
 	return launch_sequence<OpRasterBin>(a, a, k_raster_count, k_raster_entries, tiles, partial, sortTemp, sortBytes, s);
 }
 
-hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& f, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
+namespace {
+
+template <bool DAMAGE>
+hipError_t launch_frame(const VgxRasterFrameArgs& f, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
 {
 	const auto tiles = [&](dim3 grid) { // the instantiations whose tiles the level can have
-		hipLaunchKernelGGL((k_rasterf_tiles<false, false, false>), grid, dim3(256), 0, s, f);
-		if (f.level >= VGX_RL_TEXTURED) { hipLaunchKernelGGL((k_rasterf_tiles<true, false, false>), grid, dim3(256), 0, s, f); }
+		hipLaunchKernelGGL((k_rasterf_tiles<false, false, false, DAMAGE>), grid, dim3(256), 0, s, f);
+		if (f.level >= VGX_RL_TEXTURED) { hipLaunchKernelGGL((k_rasterf_tiles<true, false, false, DAMAGE>), grid, dim3(256), 0, s, f); }
 		if (f.level >= VGX_RL_PAINTED) {
-			hipLaunchKernelGGL((k_rasterf_tiles<false, true, false>), grid, dim3(256), 0, s, f);
-			hipLaunchKernelGGL((k_rasterf_tiles<true, true, false>), grid, dim3(256), 0, s, f);
+			hipLaunchKernelGGL((k_rasterf_tiles<false, true, false, DAMAGE>), grid, dim3(256), 0, s, f);
+			hipLaunchKernelGGL((k_rasterf_tiles<true, true, false, DAMAGE>), grid, dim3(256), 0, s, f);
 		}
-		if (f.level >= VGX_RL_CONCAVE) { hipLaunchKernelGGL((k_rasterf_tiles<true, true, true>), grid, dim3(256), 0, s, f); }
+		if (f.level >= VGX_RL_CONCAVE) { hipLaunchKernelGGL((k_rasterf_tiles<true, true, true, DAMAGE>), grid, dim3(256), 0, s, f); }
 	};
-	return launch_sequence<OpRasterFrameBin>(f, f.R, k_rasterf_count, k_rasterf_entries, tiles, partial, sortTemp, sortBytes, s);
+	return launch_sequence<OpRasterFrameBin>(f, f.R, k_rasterf_count<DAMAGE>, k_rasterf_entries<DAMAGE>, tiles, partial, sortTemp, sortBytes, s);
+}
+
+} // namespace
+
+// f.damage set: vgx_raster_damaged (the concave level)
+hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& f, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
+{
+	return f.damage ? launch_frame<true>(f, partial, sortTemp, sortBytes, s) : launch_frame<false>(f, partial, sortTemp, sortBytes, s);
 }

@@ -194,4 +194,27 @@ static inline void vgx_device_scan(const OP& op, Sum3* partial /* [VGX_SCAN_BLOC
 	hipLaunchKernelGGL(k_scan_apply<OP>, dim3(VGX_SCAN_BLOCKS), dim3(VGX_SCAN_THREADS), 0, s, op, partial);
 }
 
+// The scans over a list of instances (vgx_update.hip, vgx_damage.hip). Up to VGX_SCAN_SINGLE_MAX items: the whole scan in one
+// workgroup, as vgx_device_scan does, but of 256 threads in four rounds. At the 1024 threads of k_scan_single (128 VGPRs a lane)
+// OpCacheLayout spills 16 bytes a lane; at 256 none of their operators needs scratch.
+template<class OP>
+__global__ __launch_bounds__(VGX_SCAN_THREADS) void k_scan_small(OP op)
+{
+	__shared__ Sum3 s_wave[VGX_SCAN_THREADS / 64];
+	block_scan_all<OP, VGX_SCAN_THREADS>(op, s_wave);
+}
+
+template<class OP>
+static inline void vgx_device_scan_small(const OP& op, Sum3* partial /* [VGX_SCAN_BLOCKS] device */, hipStream_t s, uint64_t maxItems)
+{
+	if (maxItems <= VGX_SCAN_SINGLE_MAX) {
+		hipLaunchKernelGGL(k_scan_small<OP>, dim3(1), dim3(VGX_SCAN_THREADS), 0, s, op);
+		return;
+	}
+	// the three passes of vgx_device_scan (calling it would instantiate k_scan_single for the operator as well)
+	hipLaunchKernelGGL(k_scan_reduce<OP>, dim3(VGX_SCAN_BLOCKS), dim3(VGX_SCAN_THREADS), 0, s, op, partial);
+	hipLaunchKernelGGL(k_scan_partials<OP>, dim3(1), dim3(VGX_SCAN_BLOCKS), 0, s, op, partial);
+	hipLaunchKernelGGL(k_scan_apply<OP>, dim3(VGX_SCAN_BLOCKS), dim3(VGX_SCAN_THREADS), 0, s, op, partial);
+}
+
 #endif

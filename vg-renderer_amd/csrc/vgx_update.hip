@@ -29,28 +29,7 @@
 
 namespace {
 
-// Up to VGX_SCAN_SINGLE_MAX items: the whole scan in one workgroup, as vgx_device_scan does, but of 256 threads in four rounds. At
-// the 1024 threads of k_scan_single (128 VGPRs a lane) OpCacheLayout spills 16 bytes a lane; at 256 neither operator needs scratch.
-template<class OP>
-__global__ __launch_bounds__(VGX_SCAN_THREADS) void k_update_scan_small(OP op)
-{
-	__shared__ Sum3 s_wave[VGX_SCAN_THREADS / 64];
-	block_scan_all<OP, VGX_SCAN_THREADS>(op, s_wave);
-}
-
-template<class OP>
-void update_scan(const OP& op, Sum3* partial, hipStream_t s, uint64_t maxItems)
-{
-	if (maxItems <= VGX_SCAN_SINGLE_MAX) {
-		hipLaunchKernelGGL(k_update_scan_small<OP>, dim3(1), dim3(VGX_SCAN_THREADS), 0, s, op);
-		return;
-	}
-	// the three passes of vgx_device_scan (calling it would instantiate k_scan_single for the operator as well)
-	hipLaunchKernelGGL(k_scan_reduce<OP>, dim3(VGX_SCAN_BLOCKS), dim3(VGX_SCAN_THREADS), 0, s, op, partial);
-	hipLaunchKernelGGL(k_scan_partials<OP>, dim3(1), dim3(VGX_SCAN_BLOCKS), 0, s, op, partial);
-	hipLaunchKernelGGL(k_scan_apply<OP>, dim3(VGX_SCAN_BLOCKS), dim3(VGX_SCAN_THREADS), 0, s, op, partial);
-}
-
+// (both scans: vgx_device_scan_small, vgx_scan.h)
 // ---- vgx_cache_layout ---------------------------------------------------------------------------------------------------
 struct OpCacheLayout
 {
@@ -232,14 +211,14 @@ void vgx_launch_cache_layout(const vgx_cache_desc& cache, const vgx_cache_instan
 {
 	OpCacheLayout op;
 	op.cache = cache; op.inst = inst; op.ninst = ninst; op.slots = slots; op.status = status;
-	update_scan(op, (Sum3*)partial, s, ninst);
+	vgx_device_scan_small(op, (Sum3*)partial, s, ninst);
 }
 
 void vgx_launch_cache_update(const VgxUpdateArgs& a, void* partial, hipStream_t s)
 {
 	OpUpdateList op;
 	op.A = a;
-	update_scan(op, (Sum3*)partial, s, a.ndirty);
+	vgx_device_scan_small(op, (Sum3*)partial, s, a.ndirty);
 	if (!a.ndirty) { return; }
 	// The totals stay on the device. The host knows bounds: every listed entry has at most the cache's vertices / meshes. Waves
 	// without a range exit at once.

@@ -863,6 +863,69 @@ def cache_update(ctx, cache, inst_dev, ninst, slots_dev, dirty_dev, ndirty, pos,
     return dev_status
 
 
+# ---- damage redraw (vgx_damage_* / vgx_raster_damaged) ---------------------------------------------------------------------
+def damage_words(width, height):
+    """uint32 words of the damage bitmap of a width x height image: one bit per 16 x 16 tile. Host only."""
+    return int(lib().vgx_damage_words(int(width), int(height)))
+
+
+def _damage_target(width, height, x0, y0):
+    return capi.RasterTarget(None, int(width), int(height), int(width), int(x0), int(y0), (C.c_uint32 * 4)(0, 0, int(width), int(height)), 0, 0)
+
+
+def damage_meshes(ctx, bounds_dev, num_meshes, width, height, tile_bits, x0=0, y0=0, mesh_begin=0, mesh_end=None):
+    """ORs into tile_bits (an int32 device tensor of damage_words(width, height) words the caller zeroed) the tiles the boxes of meshes
+    [mesh_begin, mesh_end) of bounds_dev (float32 [num_meshes, 4], what mesh_bounds() gave) reach in the image raster_damaged() will
+    draw: same width, height, x0, y0. Returns tile_bits. Asynchronous."""
+    t = _damage_target(width, height, x0, y0)
+    _check(lib().vgx_damage_meshes(ctx.handle, bounds_dev.data_ptr() if num_meshes else None, int(mesh_begin),
+                                   0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), int(num_meshes), C.byref(t), tile_bits.data_ptr(), _stream_ptr()),
+           "vgx_damage_meshes")
+    return tile_bits
+
+
+def damage_instances(ctx, bounds_dev, num_meshes, slots_dev, ninst, dirty_dev, ndirty, width, height, tile_bits, x0=0, y0=0, dev_ndirty=None,
+                     dev_status=None):
+    """ORs into tile_bits the tiles the boxes of the frame meshes of the listed instances reach: slots_dev / dirty_dev / ndirty /
+    dev_ndirty as in cache_update(), bounds_dev the frame's box table. Call it before cache_update() (the old boxes) and after it (the
+    new ones, the table cache_update() refreshed). Returns dev_status (int32 [1] device tensor: VGX_OK, or VGX_E_INVALID_ARG when an
+    entry was skipped). Asynchronous."""
+    import torch
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=tile_bits.device)
+    t = _damage_target(width, height, x0, y0)
+    _check(lib().vgx_damage_instances(ctx.handle, bounds_dev.data_ptr() if num_meshes else None, int(num_meshes), slots_dev.data_ptr(), int(ninst),
+                                      dirty_dev.data_ptr() if ndirty else None, int(ndirty), dev_ndirty.data_ptr() if dev_ndirty is not None else None,
+                                      C.byref(t), tile_bits.data_ptr(), dev_status.data_ptr(), _stream_ptr()), "vgx_damage_instances")
+    return dev_status
+
+
+def raster_damaged(ctx, frame, draws_dev, draw_state_dev, num_draws, uv_dev, uv_bytes, images_dev, num_images, gradients_dev, num_gradients, patterns_dev,
+                   num_patterns, width, height, tile_bits, image, max_entries=0, x0=0, y0=0, scissor=None, clear_color=None, bounds_dev=None, mesh_begin=0,
+                   mesh_end=None, dev_status=None):
+    """raster_concave() into `image` (the int32 [height, stride] device tensor an earlier render left), restricted to the tiles whose bit
+    is set in tile_bits: with clear_color given, and every tile marked that the old or the new box of an edited mesh reaches, the image
+    equals a full raster_concave() of the edited frame (vgx_raster_damaged in include/vgx.h). max_entries: the bin entries the call sorts
+    at most, 0 = what the last damaged call on this context needed. dev_status may come out as VGX_E_GROWN: call again. Returns
+    (image, dev_status). Asynchronous."""
+    import torch
+    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
+    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
+    t = capi.RasterTarget(image.data_ptr(), int(width), int(height), int(image.stride(0)) if image.dim() == 2 and height else int(width), int(x0), int(y0),
+                          (C.c_uint32 * 4)(*sc), capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
+    st = capi.RasterDraws(draws_dev.data_ptr() if num_draws else None, draw_state_dev.data_ptr() if num_draws else None, int(num_draws), 0)
+    tx = capi.RasterTextures(uv_dev.data_ptr() if uv_dev is not None else None, images_dev.data_ptr() if num_images else None, int(uv_bytes), int(num_images))
+    pt = capi.RasterPaints(gradients_dev.data_ptr() if num_gradients else None, patterns_dev.data_ptr() if num_patterns else None, int(num_gradients),
+                           int(num_patterns))
+    dm = capi.RasterDamage(tile_bits.data_ptr(), int(max_entries), 0)
+    _check(lib().vgx_raster_damaged(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
+                                    0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), C.byref(tx), C.byref(pt), C.byref(t), C.byref(dm),
+                                    dev_status.data_ptr(), _stream_ptr()), "vgx_raster_damaged")
+    return image, dev_status
+
+
 # ---- concave fills (vgx_concave_move / vgx_concave_emit): libtess2 stays with the caller -----------------------------
 def concave_move(ctx, contour_verts_dev, contours_dev, ncontours, fills_dev, nfills):
     """Inner fringe vertex of every boundary-contour vertex (what the reference writes back into the contour before the
