@@ -87,7 +87,8 @@ struct VgxTemplateState
 	uint32_t period;
 	uint32_t classes;        // 1: every instance repeats the first period
 	VgxTmplKernel kernel;    // which emit kernel it needs (vgx_tmpl_plan.h)
-	uint32_t tileSize;       // elements per tile
+	uint32_t tileSize;       // slots per tile of the element table = the most elements a tile holds
+	uint32_t tilesPerInst;   // one class: tiles of one instance (k_tmpl_classes' count: boundaries avoid the short meshes, vgx_tmpl_plan.h)
 	vgx_sizes inst;          // sizes of one instance (of the first class)
 	vgx_sizes total;         // sizes of the whole batch
 	uint64_t numWg, nDraws;  // several classes: workgroups of one step; the batch size the per-instance table was built for
@@ -102,7 +103,7 @@ struct VgxTemplate : VgxTemplateState
 	Buf<float2> poly; Buf<VgxTmplMesh> mesh; Buf<vgx_mesh> mtab; Buf<VgxTmplElem> elem; Buf<vgx_draw> draws;
 	// several classes: one template over the concatenated class representatives, a per-instance table of output places, a
 	// per-workgroup table (instance, tile)
-	Buf<unsigned long long> hash, clsSum; Buf<uint32_t> instCls, clsRep; Buf<VgxTmplClass> cls; Buf<VgxTmplInst> iinfo; Buf<uint2> wg;
+	Buf<unsigned long long> hash, clsSum; Buf<uint32_t> instCls, clsRep; Buf<VgxTmplClass> cls; Buf<uint32_t> clsLmax; Buf<uint64_t> tbound; Buf<VgxTmplInst> iinfo; Buf<uint2> wg;
 	Buf<VgxTmplRoundMesh> trmesh; Buf<uint2> tmsz; // the Round-join meshes (mesh, first element among the Round-join elements); per mesh its sizes (VgxTmplArgs::tmsz)
 	Buf<unsigned long long> rsz, itot, iplace; Buf<uint2> relem; Buf<VgxTmplMeshPlace> mplace; // the per-step tables of a Round-join template (VgxTmplArgs)
 };
@@ -1713,7 +1714,7 @@ static void tmplArgs(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws,
 	a.inst = ctx->tmpl.inst;
 	a.ttile = ctx->tmpl.tile.ptr();
 	a.tile = ctx->tmpl.tileSize;
-	a.tiles_per_inst = (uint32_t)((ctx->tmpl.inst.num_elements + a.tile - 1) / a.tile);
+	a.tiles_per_inst = ctx->tmpl.tilesPerInst;
 	a.caps = ctx->caps;
 	a.totals = ctx->totals.ptr();
 	a.kernel = ctx->tmpl.kernel;
@@ -1944,6 +1945,11 @@ static TmplStage tmplBuildTables(TmplJob& j)
 	b.prefix_fill = ctx->elemPrefix.ptr(); b.prefix_stroke = ctx->elemPrefixS.ptr();
 	b.num_meshes = M; b.num_elems = j.all.num_elements; b.tile = j.t.tileSize; b.period = (uint32_t)j.P; b.nclasses = T;
 	b.num_vertices = j.all.num_vertices; b.num_indices = j.all.num_indices; b.cls = ctx->tmpl.cls.ptr();
+	if ((st = ensure(ctx, ctx->tmpl.clsLmax, (size_t)T + 1)) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->tmpl.clsLmax.p, 0, ((size_t)T + 1) * sizeof(uint32_t), j.s));
+	b.lmax = ctx->tmpl.clsLmax.ptr();
+	if ((st = ensure(ctx, ctx->tmpl.tbound, (size_t)vgx_tmpl_max_tiles(j.all.num_elements, j.t.tileSize, T) + 1)) != VGX_OK) { return st; }
+	b.tbound = ctx->tmpl.tbound.ptr();
 	vgx_launch_tmpl_classes(b, j.s);
 	j.cls.resize((size_t)T + 1);
 	std::vector<unsigned long long> csum(((size_t)T + 1) * 5, 0ull);
@@ -1956,6 +1962,7 @@ static TmplStage tmplBuildTables(TmplJob& j)
 	HIPCHK(ctx, hipStreamSynchronize(j.s));
 	if (T > 1 && !vgx_tmpl_class_sizes(j.cls.data(), csum.data(), T, j.csz)) { return TMPL_ORDINARY; }
 	const uint64_t tiles = j.cls[T].tile0;
+	j.t.tilesPerInst = j.cls[1].tile0; // (one class: the grid of a step)
 	if ((st = ensure(ctx, ctx->tmpl.poly, V + 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->tmpl.mesh, M + 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->tmpl.mtab, M + 1)) != VGX_OK) { return st; }

@@ -88,7 +88,9 @@ struct VgxTmplBuild // count pass: the first period's ordinary count + emit resu
 	const uint64_t* prefix_fill;   // [num_meshes + 1]
 	const uint64_t* prefix_stroke; // [num_meshes + 1]
 	uint64_t num_meshes, num_elems;
-	uint32_t tile;               // elements per tile of the processing order (a multiple of 64)
+	uint32_t tile;               // slots per tile of the processing order = the most elements a tile holds (a multiple of 64)
+	uint32_t* lmax;              // [nclasses] per class its longest mesh of at most vgx_tmpl_snap_limit(tile) elements (zeroed by the caller, k_tmpl_mesh_lmax): the tile stride (vgx_tmpl_plan.h)
+	uint64_t* tbound;            // [tiles] greedily packed classes (bit 31 of lmax[class], k_tmpl_classes): the first element of every tile
 	VgxTmplMesh* tmesh;
 	vgx_mesh* tmtab;
 	VgxTmplElem* telem;

@@ -204,13 +204,14 @@ struct VgxTmplMeshPlace // Round-join templates, per step: where one mesh of one
 	uint32_t nv, ni;         // vertices / indices
 	uint32_t pad[2];
 };
-struct VgxTmplTile // one tile of an instance's element stream = one workgroup of k_tmpl_emit. 32 bytes
+struct VgxTmplTile // one tile of an instance's element stream = one workgroup of k_tmpl_emit. 32 bytes. A tile begins where the stride rule of
+                   // vgx_tmpl_plan.h puts its boundary: at a nominal place or, inside a short mesh, at that mesh's first element (then bit 31 of mesh0 is set)
 {
 	uint32_t mesh0;     // template mesh that owns the tile's first element; bit 31: that element is the mesh's element 0
 	uint32_t mesh_last; // last mesh with an element in the tile
 	uint32_t draw0;     // draws of the period whose records the tile reads (and verifies): [draw0, draw0 + ndraws)
 	uint32_t ndraws;
-	uint32_t nel;       // elements in the tile (the last tile of a class is short)
+	uint32_t nel;       // elements in the tile (<= the tile size; the table slots behind them stay unused)
 	uint32_t cmesh0;    // first template mesh of the tile's class (mesh numbers inside an instance = mesh - cmesh0)
 	uint32_t cdraw0;    // first saved draw record of the tile's class (= class * period)
 	uint32_t pad;

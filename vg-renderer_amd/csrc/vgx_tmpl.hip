@@ -132,7 +132,26 @@ __global__ __launch_bounds__(256) void k_tmpl_check_cls(const vgx_draw* draws, u
 
 // ---- count pass: the template's tables from the representatives' ordinary count + emit ------------------------------
 // (one representative = the batch's first period for a batch of one class)
-// Where each class lies in the concatenated template. One thread: the class count is tiny.
+// Per class the longest of its meshes that tile boundaries avoid (vgx_tmpl_plan.h: at most vgx_tmpl_snap_limit elements) -> B.lmax[class]
+// (zeroed by the host), in front of k_tmpl_classes: the class's tile stride. A thread keeps the maximum of the meshes it walks and
+// reports it when the class changes and at its end.
+__global__ __launch_bounds__(256) void k_tmpl_mesh_lmax(VgxTmplBuild B)
+{
+	uint32_t cur = 0, best = 0;
+	for (uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; m < B.num_meshes; m += (uint64_t)gridDim.x * blockDim.x) {
+		const uint32_t c = B.mdesc[m].draw / B.period;
+		const uint64_t len = (B.prefix_fill[m + 1] + B.prefix_stroke[m + 1]) - (B.prefix_fill[m] + B.prefix_stroke[m]);
+		if (c != cur) {
+			if (best) { atomicMax(&B.lmax[cur], best); }
+			cur = c; best = 0;
+		}
+		const uint32_t l = vgx_tmpl_snap_len(len, B.tile);
+		best = l > best ? l : best;
+	}
+	if (best) { atomicMax(&B.lmax[cur], best); }
+}
+// Where each class lies in the concatenated template, and its tiles: the closed form of the stride rule or -- a small class -- the
+// greedy walk (vgx_tmpl_plan.h). One thread: the class count is tiny.
 __global__ void k_tmpl_classes(VgxTmplBuild B)
 {
 	const uint64_t M = B.num_meshes;
@@ -155,7 +174,28 @@ __global__ void k_tmpl_classes(VgxTmplBuild B)
 		B.cls[c] = r;
 		if (c > 0) {
 			const uint64_t e = r.elem0 - B.cls[c - 1].elem0;
-			B.cls[c].tile0 = B.cls[c - 1].tile0 + (uint32_t)((e + B.tile - 1) / B.tile);
+			uint64_t nt = vgx_tmpl_tile_count(e, vgx_tmpl_stride(B.tile, B.lmax[c - 1])); // (the closed form of vgx_tmpl_plan.h)
+			const uint64_t mLo = B.cls[c - 1].mesh0, mHi = r.mesh0;
+			if (vgx_tmpl_greedy_class(mHi - mLo, e, B.tile)) {
+				// a small class: boundary after boundary, each as far as the slots reach (at most VGX_TMPL_GREEDY_MAX_TILES of them)
+				uint64_t* tb = B.tbound + B.cls[c - 1].tile0;
+				uint64_t b = B.cls[c - 1].elem0;
+				nt = 0;
+				while (b < r.elem0) {
+					tb[nt++] = b;
+					const uint64_t nom = vgx_tmpl_greedy_nominal(b, r.elem0, B.tile);
+					if (nom >= r.elem0) { break; }
+					uint64_t lo2 = mLo, hi2 = mHi; // the mesh of the class that owns element nom
+					while (hi2 - lo2 > 1) {
+						const uint64_t mid = (lo2 + hi2) >> 1;
+						if (B.prefix_fill[mid] + B.prefix_stroke[mid] <= nom) { lo2 = mid; } else { hi2 = mid; }
+					}
+					const uint64_t f0 = B.prefix_fill[lo2] + B.prefix_stroke[lo2], f1 = B.prefix_fill[lo2 + 1] + B.prefix_stroke[lo2 + 1];
+					b = vgx_tmpl_snap_boundary(nom, f0, f1 - f0, B.tile);
+				}
+				B.lmax[c - 1] |= 0x80000000u;
+			}
+			B.cls[c].tile0 = B.cls[c - 1].tile0 + (uint32_t)nt;
 		}
 		tile0 = B.cls[c].tile0;
 	}
@@ -299,7 +339,8 @@ __global__ void k_tmpl_round_classes(VgxTmplBuild B)
 	}
 }
 
-// Element table in processing order: tiles of `tile` elements of the instance's output-ordered element stream; inside a
+// Element table in processing order: tiles of at most `tile` elements of the instance's output-ordered element stream, cut at the
+// boundaries of vgx_tmpl_plan.h (short meshes whole); tile t's elements fill the table slots [t * tile, t * tile + nel). Inside a
 // tile the fill elements first, then the stroke elements (both in output order). Every class starts a tile of its own
 // (tile cls.tile0, table slot cls.tile0 * tile): a tile never holds elements of two classes.
 #define VGX_TMPL_ELEMS_MAXM 1032 /* meshes of one tile k_tmpl_elems keeps in LDS (a mesh has >= 2 elements: a 2 048-element tile holds <= 1 025) */
@@ -338,11 +379,18 @@ __global__ __launch_bounds__(256) void k_tmpl_elems(VgxTmplBuild B) // one workg
 		while (c + 1 < B.nclasses && B.cls[c + 1].tile0 <= tile) { ++c; }
 		const VgxTmplClass cl = B.cls[c];
 		const uint64_t cEnd = B.cls[c + 1].elem0;
-		const uint64_t x0 = cl.elem0 + (tile - cl.tile0) * T; // the tile's first element (output order of the concatenated template)
-		const uint64_t x1 = x0 + T < cEnd ? x0 + T : cEnd;
+		// The tile's elements [x0, x1): boundaries (tile - tile0) and the next one of its class, each found on its own (vgx_tmpl_plan.h): the
+		// nominal place, the mesh that owns it, and -- a short mesh -- down to that mesh's first element. x1 - x0 <= T.
+		const uint32_t S = vgx_tmpl_stride((uint32_t)T, B.lmax[c] & 0x7FFFFFFFu);
+		const bool greedy = (B.lmax[c] >> 31) != 0; // a small class: k_tmpl_classes walked its boundaries (snapped already: the snap below leaves them)
+		const uint64_t n0 = greedy ? B.tbound[tile] : vgx_tmpl_nominal_boundary(cl.elem0, cEnd, tile - cl.tile0, S);
+		const uint64_t n1 = greedy ? (tile + 1 < B.cls[c + 1].tile0 ? B.tbound[tile + 1] : cEnd) : vgx_tmpl_nominal_boundary(cl.elem0, cEnd, tile - cl.tile0 + 1, S);
+		auto len = [&](uint64_t m) { return first(m + 1) - first(m); };
 		// the tile's bounds: the mesh that owns its first element, and the one that owns the element behind its last (M: none)
-		const uint64_t m0 = lastLe(x0, 0, M);
-		const uint64_t m1 = x1 >= E ? M : lastLe(x1, m0, (m0 + T / 2 + 2 < M) ? m0 + T / 2 + 2 : M);
+		const uint64_t m0 = lastLe(n0, 0, M);
+		const uint64_t x0 = vgx_tmpl_snap_boundary(n0, first(m0), len(m0), (uint32_t)T); // (the tile's first element, output order of the concatenated template)
+		const uint64_t m1 = n1 >= E ? M : lastLe(n1, m0, (m0 + T / 2 + 2 < M) ? m0 + T / 2 + 2 : M);
+		const uint64_t x1 = m1 >= M ? n1 : vgx_tmpl_snap_boundary(n1, first(m1), len(m1), (uint32_t)T); // (the class's end is a mesh's first element: it stays)
 		const uint64_t hi = m1 < M ? m1 + 1 : M;
 		const bool inLds = hi - m0 <= (uint64_t)VGX_TMPL_ELEMS_MAXM;
 		__syncthreads();
@@ -439,23 +487,27 @@ __global__ __launch_bounds__(256) void k_tmpl_tiles(VgxTmplBuild B)
 }
 
 // ---- step ------------------------------------------------------------------------------------------------------------
-// One workgroup = one TILE of one instance: `tile` consecutive elements of the instance's output-ordered element stream, i.e.
-// a contiguous piece of each output stream (~40 KB), a contiguous range of the template's meshes and of the period's draws.
+// One workgroup = one TILE of one instance: at most `tile` consecutive elements of the instance's output-ordered element stream, i.e.
+// a contiguous piece of each output stream (~85 KB), a contiguous range of the template's meshes and of the period's draws. Tiles end
+// where meshes end (vgx_tmpl_plan.h: a boundary that would fall inside a mesh of at most tile / 8 elements moves down to the mesh's
+// first element), so only the meshes longer than that are ever cut by a tile border.
 // What bounds the kernel is the latency of its dependent loads (measured with -DVGX_TMPL_PROFILE: a workgroup that fetched
 // tile -> mesh records -> draw records -> vertices one after the other spent 60 % of its life waiting for them), so everything
-// is addressed from the tile record and requested at once:
+// is addressed from the tile record and requested at once -- ONE load trip per tile; a tile without a cut mesh executes no vector
+// load behind the first barrier, and no wait for loads follows a store:
 //   phase 0  a) one thread per draw of the tile: the instance's draw record (HBM) -- verified against the saved first period,
-//               transform + colours parked in LDS;  one thread per mesh: the template's mesh record and, for AA fills, the
-//               polygon's first three vertices;  every thread: its elements' records and template vertices (phase 1's loads)
+//               transform + colours parked in LDS;  one thread per mesh: the template's mesh record (for AA fills with the
+//               polygon's first three vertices) and the three words of the template's mesh table the caller's record needs beyond
+//               it, parked in LDS;  every thread: its elements' records and template vertices (phase 1's loads)
 //            b) one thread per mesh: per-mesh record in LDS -- colour, widths, output offsets, and for AA fills the orientation
-//               of the TRANSFORMED polygon's first triangle (stroker.cpp:721-723), once per mesh instead of once per corner;
-//               the caller's mesh table for the meshes that begin in this tile
+//               of the TRANSFORMED polygon's first triangle (stroker.cpp:721-723), once per mesh instead of once per corner
 //   phase 1  one lane per element: transformPos2D (vg_util.h:24-28) of its vertex ONCE, parked in LDS at the element's
 //            output-order position inside the tile ("the growing polyline staged in LDS")
 //   phase 2  one lane per element: vec2Dir(own vertex, next vertex) (stroker.cpp:31-38) once, parked in LDS
-//   phase 3  one lane per element: the edge directions around it from LDS (from L2 + transform for the handful of elements
-//            whose neighbour lies in another tile), calcExtrusionVector and the rest of the stroker's per-element arithmetic,
-//            stores at closed-form addresses (workgroup-uniform stream bases + 32-bit offsets).
+//   phase 3  one thread per mesh that begins in this tile: the caller's mesh table from the parked words (tmpl_mesh_out_parts);
+//            one lane per element: the edge directions around it from LDS (from L2 + transform for the elements of a CUT mesh
+//            whose neighbour lies in another tile: branches a tile of whole meshes skips), calcExtrusionVector and the rest of the
+//            stroker's per-element arithmetic, stores at closed-form addresses (workgroup-uniform stream bases + 32-bit offsets).
 struct TmplXf { float m0, m1, m2, m3, m4, m5; };
 __device__ __forceinline__ V2 tmpl_xf(const TmplXf& m, float2 p) // transformPos2D, vg_util.h:24-28
 {
@@ -655,6 +707,26 @@ __device__ __forceinline__ void tmpl_mesh_out_placed(const VgxTmplArgs& A, const
 	mr.num_vertices = mi.z;
 	mr.num_indices = mi.w;
 	mr.draw += P.draw0;
+	A.meshes_out[P.m + (mesh - P.cmesh0)] = mr;
+}
+
+// The tile path (tmpl_emit_body) asks the template's mesh table only for what the mesh record does not hold -- three words: vertices,
+// indices, sub-path and kind --, with the other loads of phase 0a (three more registers at the kernels' register peak, where a whole
+// record cost the Bevel kernel its third workgroup per CU); it parks them in LDS and stores the caller's record at the head of phase 3,
+// when every load of the wave has long arrived: neither a round trip of its own nor a wait for the stores' acknowledgement. The places
+// and the draw are the mesh record's (VgxTmplMesh::v_off / i_off / drawk = the table's first_vertex / first_index / draw: one instance
+// stays below 2^32, vgx_tmpl_eligible; Round joins: the instance's own places), nv / ni the table's or -- Round joins -- the step's.
+static_assert(sizeof(vgx_mesh) == 32 && offsetof(vgx_mesh, num_vertices) == 16 && offsetof(vgx_mesh, num_indices) == 20 && offsetof(vgx_mesh, subpath_kind) == 28, "the words read below");
+__device__ __forceinline__ uint2 tmpl_mesh_sizes(const VgxTmplArgs& A, uint32_t mesh) { return *(const uint2*)&A.tmtab[mesh].num_vertices; }
+__device__ __forceinline__ void tmpl_mesh_out_parts(const VgxTmplArgs& A, const TmplPlace& P, uint32_t mesh, uint32_t vOff, uint32_t iOff, uint32_t nv, uint32_t ni, uint32_t drawk, uint32_t subpathKind)
+{
+	vgx_mesh mr;
+	mr.first_vertex = P.v + vOff;
+	mr.first_index = P.i + iOff;
+	mr.num_vertices = nv;
+	mr.num_indices = ni;
+	mr.draw = drawk + P.draw0;
+	mr.subpath_kind = subpathKind;
 	A.meshes_out[P.m + (mesh - P.cmesh0)] = mr;
 }
 
@@ -1059,6 +1131,8 @@ __device__ __forceinline__ void tmpl_emit_body(const VgxTmplArgs& A)
 	__shared__ uint4 s_mi[ROUND ? VGX_TMPL_MAXM : 1];     // per mesh of the tile: first vertex / index inside the instance, vertices, indices (phase 0a -> 0b)
 	__shared__ float4 s_rmesh[ROUND ? VGX_TMPL_MAXM : 1]; // per mesh of the tile: vertices, indices (bits), arc step, first table word of a Round-join mesh (bits; ~0: none)
 	__shared__ float s_fringe[KIND >= 2 ? VGX_TMPL_MAXM : 1]; // per mesh of the tile: the draw's fringe (Bevel joins, Butt caps, thin strokes: kernels with those only)
+	__shared__ uint2 s_msz[VGX_TMPL_MAXM];                // per mesh of the tile: vertices, indices ...
+	__shared__ uint32_t s_msub[VGX_TMPL_MAXM];            // ... sub-path and kind of the template's mesh-table record (phase 0a -> the head of phase 3)
 	const uint32_t tid = threadIdx.x;
 	// workgroup -> (instance, tile of the template), all workgroup-uniform (scalar loads)
 	uint32_t inst32, t;
@@ -1164,16 +1238,22 @@ __device__ __forceinline__ void tmpl_emit_body(const VgxTmplArgs& A)
 		er[c].mesh = mA; er[c].jq = 0; er[c].lx = 0.0f; er[c].ly = 0.0f;
 		if (s < nel) { er[c] = telem[s]; }
 	}
-	VgxTmplMesh tm;
-	memset(&tm, 0, sizeof(tm));
-	tm.n = 3; tm.drawk = dA; tm.kind = VGX_MESH_FILL;
+	VgxTmplMesh tm; // (field by field: a memset made byte-wise merges of the record, unpacked -- and waited for -- in front of the draw records' loads)
+	tm.poly_first = 0; tm.n = 3; tm.v_off = 0; tm.i_off = 0; tm.drawk = dA; tm.kind = VGX_MESH_FILL; tm.f0 = 0.0f; tm.f1 = 0.0f;
+	tm.l0[0] = 0.0f; tm.l0[1] = 0.0f; tm.l1[0] = 0.0f; tm.l1[1] = 0.0f; tm.l2[0] = 0.0f; tm.l2[1] = 0.0f; tm.fringe_bits = 0; tm.round_no = 0;
 	uint32_t ibase = 0;
 	uint4 mi = make_uint4(0u, 0u, 0u, 0u);
+	// the caller's mesh table for the meshes that BEGIN in this tile (every mesh of the range but possibly the first): tmpl_mesh_out_parts
+	const bool meshOut = tid < nm && (tid > 0 || firstWhole) && A.meshes_out;
+	uint2 msz = make_uint2(0u, 0u);
+	uint32_t msub = 0;
 	if (tid < nm) {
 		tm = A.tmesh[mA + tid];
 		if (meshBase) { ibase = meshBase[mA - P.cmesh0 + tid]; }
 	}
+	if (meshOut) { msz = tmpl_mesh_sizes(A, mA + tid); msub = A.tmtab[mA + tid].subpath_kind; }
 	if (tid < nd) { s_draw[tid] = tmpl_load_draw(A, idraws, P.tdraws, dA + tid); }
+	if (meshOut) { s_msz[tid] = msz; s_msub[tid] = msub; }
 	if (tid == 0) { s_status = A.totals->status; } // an earlier workgroup may have found the batch stale; ONE value for the whole workgroup (the exit below must be uniform)
 	__syncthreads();
 	const uint32_t status = s_status;
@@ -1192,10 +1272,6 @@ __device__ __forceinline__ void tmpl_emit_body(const VgxTmplArgs& A)
 		}
 		if (kind == VGX_MESH_FILL_AA) { r.f0 = tmpl_fill_aa(tmpl_draw_xf(d), make_float2(tm.l0[0], tm.l0[1]), make_float2(tm.l1[0], tm.l1[1]), make_float2(tm.l2[0], tm.l2[1]), tm.f0); }
 		s_rec[tid] = r;
-		// the caller's mesh table for the meshes that BEGIN in this tile (every mesh of the range but possibly the first)
-		if ((tid > 0 || firstWhole) && A.meshes_out && status == VGX_OK) {
-			if (ROUND) { tmpl_mesh_out_placed(A, P, mA + tid, mi); } else { tmpl_mesh_out(A, P, mA + tid); }
-		}
 	}
 	__syncthreads();
 	TMPL_PROF(0);
@@ -1254,8 +1330,15 @@ __device__ __forceinline__ void tmpl_emit_body(const VgxTmplArgs& A)
 	}
 	__syncthreads();
 	TMPL_PROF(2);
-	// ---- phase 3: the element
-	auto element = [&](auto passTag, uint32_t s, const VgxTmplElem& e, V2 pv, V2 dv, bool placed, uint32_t wx, uint32_t wy) {
+	// ---- phase 3: the caller's mesh table (the records parked in phase 0a: every load of the wave has long arrived, no wait follows
+	// these stores), then the element
+	if (meshOut) {
+		const TmplRec* r = &s_rec[tid]; // (v_off / i_off: Round joins: the instance's own)
+		uint2 z = s_msz[tid];
+		if (ROUND) { const uint4 q = s_mi[tid]; z = make_uint2(q.z, q.w); }
+		tmpl_mesh_out_parts(A, P, mA + tid, r->v_off, r->i_off, z.x, z.y, dA + TMPL_REC_DK(r), s_msub[tid]);
+	}
+	auto element =[&](auto passTag, uint32_t s, const VgxTmplElem& e, V2 pv, V2 dv, bool placed, uint32_t wx, uint32_t wy) {
 		TmplRoundPlace rpl; // (wx, wy: the element's table words, tmpl_round_word)
 		rpl.placed = placed;
 		tmpl_round_unword(wx, wy, &rpl.b, &rpl.k, &rpl.nvPrev, &rpl.prevInner);
@@ -1729,6 +1812,8 @@ void vgx_launch_tmpl_styles(const VgxTmplBuild& b, hipStream_t s)
 
 void vgx_launch_tmpl_classes(const VgxTmplBuild& b, hipStream_t s)
 {
+	const uint64_t gm = (b.num_meshes + 255) / 256;
+	if (b.num_meshes) { hipLaunchKernelGGL(k_tmpl_mesh_lmax, dim3((unsigned)(gm > 1024 ? 1024 : gm)), dim3(256), 0, s, b); } // (b.lmax: zeroed by the caller)
 	hipLaunchKernelGGL(k_tmpl_classes, dim3(1), dim3(1), 0, s, b);
 }
 
@@ -1740,7 +1825,7 @@ void vgx_launch_tmpl_class_sums(const VgxTmplBuild& b, const vgx_draw_info* dinf
 void vgx_launch_tmpl_build(const VgxTmplBuild& b, hipStream_t s)
 {
 	const uint64_t gm = (b.num_meshes + 255) / 256;
-	const uint64_t nt = (b.num_elems + b.tile - 1) / b.tile + b.nclasses; // >= the tile count (every class rounds up on its own)
+	const uint64_t nt = vgx_tmpl_max_tiles(b.num_elems, b.tile, b.nclasses); // >= the tile count (every class rounds up on its own)
 	if (b.num_meshes) {
 		hipLaunchKernelGGL(k_tmpl_meshes, dim3((unsigned)(gm > 4096 ? 4096 : gm)), dim3(256), 0, s, b);
 		if (b.has_round) {

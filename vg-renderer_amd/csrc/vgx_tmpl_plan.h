@@ -1,4 +1,5 @@
-// vgx_tmpl_plan.h -- template mode, the host's decisions (host code only, no device and no HIP: tests/native/tmpl_plan_test.cpp).
+// vgx_tmpl_plan.h -- template mode, the host's decisions (compiles without HIP: tests/native/tmpl_plan_test.cpp), and the tile-boundary
+// arithmetic the build kernels share with the host (tests/native/tmpl_tiles_test.cpp).
 //
 // What vgx_tessellate_count decides on the host between the kernels of vgx_tmpl.hip: which instances share a class, which emit
 // kernel and tile size a template gets, the sizes of one instance of every class, and the batch's totals and tables. This is the
@@ -66,6 +67,61 @@ inline uint32_t vgx_tmpl_tile_for(VgxTmplKernel k, uint32_t optTile)
 	if ((k == VGX_TK_GENERAL || k == VGX_TK_ROUND) && optTile > VGX_TMPL_GENERAL_TILE) { return (uint32_t)VGX_TMPL_GENERAL_TILE; }
 	if ((k == VGX_TK_ROUND_AA || k == VGX_TK_ROUND_AA_OPEN) && optTile == VGX_TMPL_MAX_TILE) { return VGX_TMPL_RC_TILE; } // (its own workgroup shape; an override stands)
 	return optTile;
+}
+
+// ---- which elements a tile owns ------------------------------------------------------------------------------------------------
+// The tile size T above is the SLOT size of the element table (tile t's slots are [t * T, t * T + nel)) and the capacity of the emit
+// kernel's LDS stages. A tile's elements are cut out of its class's output-ordered element stream [elem0, end) at boundaries that avoid
+// the short meshes: boundary k is nominally elem0 + k * S (the stride S a little below T) and, when that falls strictly inside a mesh of
+// at most L = T / 8 elements, moves DOWN to that mesh's first element -- such a mesh lies whole in one tile, so none of its elements has
+// a neighbour in another tile (no load behind the emit kernel's first barrier). A longer mesh is cut where the boundary falls.
+// With Lmax = the longest mesh of the class of at most L elements (1: none) and S = T - (Lmax - 1): a boundary moves by at most
+// Lmax - 1, so a tile holds at most S + Lmax - 1 = T elements, boundaries stay strictly increasing (S - Lmax + 1 > 0), every
+// boundary is found on its own (no pass over the meshes in order), and the class has ceil(E / S) tiles.
+// These are the lines k_tmpl_mesh_lmax / k_tmpl_classes / k_tmpl_elems (vgx_tmpl.hip) run; tests/native/tmpl_tiles_test.cpp runs them on the host.
+#if defined(__HIPCC__)
+#define VGX_TMPL_HD __host__ __device__
+#else
+#define VGX_TMPL_HD
+#endif
+VGX_TMPL_HD inline uint32_t vgx_tmpl_snap_limit(uint32_t T) { return T / 8u; }
+// a mesh's contribution to Lmax (the maximum over the class's meshes; 0: the mesh is a long one)
+VGX_TMPL_HD inline uint32_t vgx_tmpl_snap_len(uint64_t meshLen, uint32_t T) { return meshLen <= (uint64_t)vgx_tmpl_snap_limit(T) ? (uint32_t)meshLen : 0u; }
+VGX_TMPL_HD inline uint32_t vgx_tmpl_stride(uint32_t T, uint32_t lmax) { return T - ((lmax ? lmax : 1u) - 1u); }
+VGX_TMPL_HD inline uint64_t vgx_tmpl_tile_count(uint64_t classElems, uint32_t stride) { return (classElems + stride - 1) / stride; }
+// boundary k of a class whose elements are [elem0, end), before the snap (k = the tile count: the class's end)
+VGX_TMPL_HD inline uint64_t vgx_tmpl_nominal_boundary(uint64_t elem0, uint64_t end, uint64_t k, uint32_t stride)
+{
+	const uint64_t b = elem0 + k * (uint64_t)stride;
+	return b < end ? b : end;
+}
+// the boundary given the mesh that owns element `nominal`: its first element and its length
+VGX_TMPL_HD inline uint64_t vgx_tmpl_snap_boundary(uint64_t nominal, uint64_t meshFirst, uint64_t meshLen, uint32_t T)
+{
+	return (meshFirst < nominal && meshLen <= (uint64_t)vgx_tmpl_snap_limit(T)) ? meshFirst : nominal;
+}
+// Small classes -- a drawing of a few thousand meshes, the instanced case -- are packed greedily instead: every boundary as far behind the
+// previous one as the slots reach (nominally start + T, then the same snap), which fills the tiles better than the stride does (the
+// Tiger: 9 tiles instead of 10). One thread walks the boundaries in order (k_tmpl_classes), hence the limits: a static batch of
+// millions of meshes keeps the stride rule, whose boundaries are found independently. Same invariants; the tile count is at most the
+// stride rule's (every tile but the last holds more than T - Lmax >= S - 1 elements).
+#ifndef VGX_TMPL_GREEDY_MAX_MESHES
+#define VGX_TMPL_GREEDY_MAX_MESHES 4096u /* 0: the stride rule for every class (measurement builds) */
+#endif
+#define VGX_TMPL_GREEDY_MAX_TILES 64u
+VGX_TMPL_HD inline bool vgx_tmpl_greedy_class(uint64_t classMeshes, uint64_t classElems, uint32_t T)
+{
+	return classMeshes <= VGX_TMPL_GREEDY_MAX_MESHES && classElems <= (uint64_t)VGX_TMPL_GREEDY_MAX_TILES * (T - vgx_tmpl_snap_limit(T));
+}
+VGX_TMPL_HD inline uint64_t vgx_tmpl_greedy_nominal(uint64_t start, uint64_t end, uint32_t T)
+{
+	const uint64_t b = start + T;
+	return b < end ? b : end;
+}
+// tiles of a template whatever its meshes (what the element table and the build kernels' grids are sized for): every class rounds up on its own
+VGX_TMPL_HD inline uint64_t vgx_tmpl_max_tiles(uint64_t elems, uint32_t T, uint32_t nclasses)
+{
+	return elems / vgx_tmpl_stride(T, vgx_tmpl_snap_limit(T)) + nclasses + 1;
 }
 
 // one instance of a class: only the mesh kinds k_tmpl_emit writes, every output stream of the instance below 4 GB
