@@ -67,3 +67,11 @@ def digest_ragged_torch(words, starts, counts, is_u16=False):
         res.append((s0, s1))
         del P, W
     return torch.stack([res[0][0], res[1][0], res[0][1], res[1][1]], dim=1).cpu().numpy()
+
+
+def fnv1a(words):
+    """The 64-bit FNV-1a digest the C++ raster examples print of their pixels (uint32 words, little-endian bytes)."""
+    h = 1469598103934665603
+    for b in np.ascontiguousarray(words, dtype="<u4").reshape(-1).view(np.uint8).tolist():
+        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return h

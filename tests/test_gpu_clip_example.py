@@ -11,7 +11,7 @@ import pytest
 
 import raster_frame_model as M
 import raster_model as R
-from test_gpu_raster_example import fnv1a
+from hashutil import fnv1a
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,36 +1,25 @@
-"""GPU: vgx_concave_contours (csrc/vgx_concave.hip: k_concave_contours behind the size scan) against its lane code on the inputs of
-tests/test_concave_contours_cpu.py -- every byte of the four streams --, the capacities with guard regions, VGX_E_MESH_TOO_LARGE, and
+"""GPU: vgx_concave_contours (csrc/vgx_concave.hip: k_concave_contours behind the size scan) against its lane code on the inputs
+tests/test_concave_contours_cpu.py takes -- every byte of the four streams --, the capacities with guard regions, VGX_E_MESH_TOO_LARGE, and
 against the two older device calls: the fringe mesh equals vgx_concave_emit with zero tess input, the moved vertices equal
 vgx_concave_move, for the same contours."""
 import ctypes as C
-import importlib
 
 import numpy as np
 import pytest
 
+import raster_harness as H
 import raster_model as R
-import test_concave_contours_cpu as cpu
 import test_gpu_concave as TC
-import test_gpu_raster as G
+from raster_harness import host, rt, to_dev  # noqa: F401 (host, rt: fixtures)
 
 pytestmark = pytest.mark.gpu
 capi = R.capi
 F = np.float32
-GUARD = cpu.GUARD
-
-
-@pytest.fixture(scope="module")
-def rt():
-    return importlib.import_module("vg-renderer_amd.runtime")
-
-
-@pytest.fixture(scope="module")
-def host():
-    return cpu.load_host()
+GUARD = H.OUT_GUARD
 
 
 class DevOut:
-    """cpu.Out in device memory: the streams between guard regions."""
+    """Out of tests/raster_harness.py in device memory: the streams between guard regions."""
 
     def __init__(self, cap_v, cap_i, cap_m, pad=64):
         import torch
@@ -47,7 +36,7 @@ class DevOut:
 
 def gpu_contours(rt, ctx, fl, out):
     import torch
-    d = [G.to_dev(a) for a in (fl.poly, fl.subs, fl.info, fl.draws)]
+    d = [to_dev(a) for a in (fl.poly, fl.subs, fl.info, fl.draws)]
     rc = rt.lib().vgx_concave_contours(ctx.handle, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), len(fl.specs), C.byref(out.struct),
                                        out.dev_sizes.data_ptr(), out.dev_status.data_ptr(), rt._stream_ptr())
     torch.cuda.synchronize()
@@ -62,38 +51,38 @@ def same_bytes(out, hout):
 
 
 def test_kernel_equals_lane_code(rt, gpu_ctx, host):
-    fl = cpu.Flat(cpu.specs())
+    fl = H.Flat(H.contour_specs())
     nm, nv, ni = fl.expected_sizes()
     for caps in ((nv, ni, nm), (nv + 5, ni + 3, nm + 2)):
-        out, hout = DevOut(*caps), cpu.Out(*caps)
+        out, hout = DevOut(*caps), H.Out(*caps)
         st, sizes = gpu_contours(rt, gpu_ctx, fl, out)
-        assert (st, sizes) == cpu.host_contours(host, fl, hout) == (capi.VGX_OK, (nm, nv, ni))
+        assert (st, sizes) == H.host_contours(host, fl, hout) == (capi.VGX_OK, (nm, nv, ni))
         assert same_bytes(out, hout)
-    cpu.check_structure(fl, *hout.streams(nm, nv, ni))
+    H.check_structure(fl, *hout.streams(nm, nv, ni))
 
 
 @pytest.mark.parametrize("short", ["vertices", "indices", "meshes"])
 def test_nospace_writes_nothing_past_a_capacity(rt, gpu_ctx, host, short):
-    fl = cpu.Flat(cpu.specs())
+    fl = H.Flat(H.contour_specs())
     nm, nv, ni = fl.expected_sizes()
     caps = (nv - (short == "vertices"), ni - (short == "indices"), nm - (short == "meshes"))
-    out, hout = DevOut(*caps), cpu.Out(*caps)
+    out, hout = DevOut(*caps), H.Out(*caps)
     st, sizes = gpu_contours(rt, gpu_ctx, fl, out)
     assert st == capi.VGX_E_NOSPACE and sizes == (nm, nv, ni)
-    assert cpu.host_contours(host, fl, hout) == (st, sizes) and same_bytes(out, hout)
+    assert H.host_contours(host, fl, hout) == (st, sizes) and same_bytes(out, hout)
     assert all((r == GUARD).all() for r in out.raw()[:3])
 
 
 def test_mesh_too_large_and_misaligned_output(rt, gpu_ctx):
     for n, want in ((32768, capi.VGX_OK), (32769, capi.VGX_E_MESH_TOO_LARGE)):
-        fl = cpu.Flat([([TC._ring(0, 0, 1000, n)], cpu.CONCAVE | cpu.AA, 0xFFFFFFFF, 1.0)])
+        fl = H.Flat([([TC._ring(0, 0, 1000, n)], H.CONCAVE | H.AA, 0xFFFFFFFF, 1.0)])
         nm, nv, ni = fl.expected_sizes()
         out = DevOut(nv, ni, nm)
         st, _ = gpu_contours(rt, gpu_ctx, fl, out)
         assert st == want and (want == capi.VGX_OK or all((r == GUARD).all() for r in out.raw()[:3]))
-    fl = cpu.Flat(cpu.specs())
+    fl = H.Flat(H.contour_specs())
     nm, nv, ni = fl.expected_sizes()
-    d = [G.to_dev(a) for a in (fl.poly, fl.subs, fl.info, fl.draws)]
+    d = [to_dev(a) for a in (fl.poly, fl.subs, fl.info, fl.draws)]
     for k, off in enumerate((4, 2, 1, 4)):
         out = DevOut(nv, ni, nm)
         ptrs = [getattr(out.struct, n) for n in ("pos", "color", "idx", "meshes")]
@@ -106,8 +95,8 @@ def test_mesh_too_large_and_misaligned_output(rt, gpu_ctx):
 def test_fringe_equals_concave_emit_and_moved_equals_concave_move(rt, gpu_ctx):
     """The draw's own sub-paths as the boundary contours of vgx_concave_move / vgx_concave_emit (zero tess input)."""
     import torch
-    specs = [s for s in cpu.specs() if s[1] & cpu.AA and s[1] & cpu.CONCAVE and len(s[0])]
-    fl = cpu.Flat(specs)
+    specs = [s for s in H.contour_specs() if s[1] & H.AA and s[1] & H.CONCAVE and len(s[0])]
+    fl = H.Flat(specs)
     nm, nv, ni = fl.expected_sizes()
     out = DevOut(nv, ni, nm)
     assert gpu_contours(rt, gpu_ctx, fl, out)[0] == capi.VGX_OK
@@ -124,7 +113,7 @@ def test_fringe_equals_concave_emit_and_moved_equals_concave_move(rt, gpu_ctx):
             at += len(c)
     cont = np.array(cont, dtype=capi.contour_dtype)
     verts = torch.from_numpy(fl.poly).to("cuda:0")
-    cd, fd = G.to_dev(cont), G.to_dev(fills)
+    cd, fd = to_dev(cont), to_dev(fills)
     moved = rt.concave_move(gpu_ctx, verts, cd, len(cont), fd, len(specs)).cpu().numpy()
     V = at
     B = rt.MeshBuffers(verts.device, 2 * V, 6 * V, len(specs))

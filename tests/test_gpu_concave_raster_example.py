@@ -13,7 +13,7 @@ import pytest
 import raster_concave_model as K
 import raster_model as R
 import raster_painted_model as P
-from test_gpu_raster_example import fnv1a
+from hashutil import fnv1a
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -2,9 +2,8 @@
 frame-level raster kernels (csrc/vgx_raster.hip, vgx_raster_damaged) -- against the numpy statement (tests/damage_model.py) and the lane
 code, with guard words around the bit array and the image; the sort window and its VGX_E_GROWN protocol; and the property that matters,
 product against product: after mark -> vgx_cache_update -> mark -> vgx_raster_damaged the image equals vgx_raster_concave of the edited
-frame on the whole buffer (check_property of tests/test_damage_cpu.py, run here over the kernels). Every comparison is np.array_equal."""
+frame on the whole buffer (check_damage_property of tests/raster_harness.py, run here over the kernels). Every comparison is np.array_equal."""
 import ctypes as C
-import importlib
 import types
 
 import numpy as np
@@ -12,52 +11,14 @@ import pytest
 
 import damage_model as DM
 import raster_concave_model as K
+import raster_harness as H
 import raster_model as R
-import test_damage_cpu as cpu
-import test_gpu_raster as G
-import test_gpu_raster_concave as GC
-import test_raster_concave_cpu as ccpu
+from raster_harness import DevBits, dev_parts, gpu_bounds, gpu_level, host, rt, to_dev, warm_ctx, where  # noqa: F401 (host, rt, warm_ctx: fixtures)
 
 pytestmark = pytest.mark.gpu
 capi = R.capi
 CLEAR = DM.CLEAR
 F = np.float32
-GUARD = cpu.GUARD
-
-
-@pytest.fixture(scope="module")
-def rt():
-    return importlib.import_module("vg-renderer_amd.runtime")
-
-
-@pytest.fixture(scope="module")
-def warm_ctx(rt):
-    ctx = rt.Context(0)
-    rt.raster_reserve(ctx, 8192, 1 << 17)
-    yield ctx
-    ctx.close()
-
-
-@pytest.fixture(scope="module")
-def host():
-    return cpu.load_host()
-
-
-class DevBits:
-    """The bit array between two guard words in device memory."""
-
-    def __init__(self, width, height, fill=None):
-        import torch
-        self.n = DM.words(width, height)
-        a = np.full(self.n + 2, GUARD, dtype=np.uint32)
-        a[1:self.n + 1] = 0 if fill is None else fill
-        self.all = torch.from_numpy(a.view(np.int32).copy()).to("cuda:0")
-        self.t = self.all[1:self.n + 1]
-
-    def read(self):
-        a = self.all.cpu().numpy().view(np.uint32)
-        assert a[0] == GUARD and a[-1] == GUARD
-        return a[1:self.n + 1].copy()
 
 
 def dev_bits(bits, width, height):
@@ -65,15 +26,15 @@ def dev_bits(bits, width, height):
 
 
 def gpu_mark_meshes(rt, ctx, bounds_dev, begin, end, nm, width, height, x0, y0, bits):
-    t = cpu.mark_target(width, height, x0, y0)
+    t = H.mark_target(width, height, x0, y0)
     assert rt.lib().vgx_damage_meshes(ctx.handle, bounds_dev.data_ptr(), begin, end, nm, C.byref(t), bits.t.data_ptr(), rt._stream_ptr()) == capi.VGX_OK
 
 
 def gpu_mark_instances(rt, ctx, bounds_dev, nm, slots_dev, ninst, dirty, limit, width, height, x0, y0, bits):
     """Returns dev_status (synchronised); a 77 in the words beside it stays."""
     import torch
-    t = cpu.mark_target(width, height, x0, y0)
-    dd = G.to_dev(np.ascontiguousarray(dirty, dtype=np.uint32))
+    t = H.mark_target(width, height, x0, y0)
+    dd = to_dev(np.ascontiguousarray(dirty, dtype=np.uint32))
     lim = None if limit is None else torch.tensor([int(limit)], dtype=torch.int64, device="cuda:0")
     status = torch.full((3,), 77, dtype=torch.int32, device="cuda:0")
     assert rt.lib().vgx_damage_instances(ctx.handle, bounds_dev.data_ptr(), nm, slots_dev.data_ptr(), ninst, dd.data_ptr() if dirty.shape[0] else None,
@@ -83,24 +44,6 @@ def gpu_mark_instances(rt, ctx, bounds_dev, nm, slots_dev, ninst, dirty, limit, 
     s = status.cpu().tolist()
     assert s[0] == 77 and s[2] == 77
     return s[1]
-
-
-def gpu_damaged(rt, ctx, df, ds, dx, dp, tgt, bits, image=None, begin=0, end=2**64 - 1, want=capi.VGX_OK, max_entries=1 << 20, bounds=None):
-    """One vgx_raster_damaged call over the target's background (or `image`, a device tensor, changed in place), synchronised; returns
-    (image tensor, image as uint32 [rows, stride]). max_entries: by default the whole of the entry tables, so that the tests of the result
-    do not meet VGX_E_GROWN; the tests of the window hand in their own."""
-    import torch
-    if image is None:
-        image = torch.from_numpy(tgt.background().view(np.int32)).to("cuda:0")
-    status = torch.full((3,), 77, dtype=torch.int32, device="cuda:0")
-    t = tgt.struct(image.data_ptr())
-    dm = capi.RasterDamage(bits.t.data_ptr(), max_entries, 0)
-    st = rt.lib().vgx_raster_damaged(ctx.handle, C.byref(df.desc), None if bounds is None else bounds.data_ptr(), begin, end, C.byref(ds.struct), C.byref(dx.struct),
-                                     C.byref(dp.struct), C.byref(t), C.byref(dm), status.data_ptr(), rt._stream_ptr())
-    torch.cuda.synchronize()
-    assert st == capi.VGX_OK
-    assert status.cpu().tolist() == [want, 77, 77]
-    return image, image.cpu().numpy().view(np.uint32)
 
 
 def sentinel_image(tgt):
@@ -124,7 +67,7 @@ def test_mark_meshes_equals_model_and_lane_code(rt, warm_ctx, host, case):
     bd = torch.from_numpy(bounds).to("cuda:0")
     want = DM.mark_meshes(np.zeros(DM.words(width, height), np.uint32), bounds, 0, nm, nm, width, height, x0, y0)
     lane = np.zeros_like(want)
-    cpu.host_mark_meshes(host, bounds, 0, nm, nm, width, height, x0, y0, lane)
+    H.host_mark_meshes(host, bounds, 0, nm, nm, width, height, x0, y0, lane)
     assert np.array_equal(lane, want)
     bits = DevBits(width, height)
     gpu_mark_meshes(rt, warm_ctx, bd, 0, 2**64 - 1, nm, width, height, x0, y0, bits)
@@ -166,8 +109,8 @@ def test_mark_instances_equals_model_and_lane_code(rt, warm_ctx, host, kind):
     want = np.zeros(DM.words(width, height), np.uint32)
     assert DM.mark_instances(want, bounds, nm, slots, ninst, dirty, limit, width, height, x0, y0) == status
     lane = np.zeros_like(want)
-    assert cpu.host_mark_instances(host, bounds, nm, slots, ninst, dirty, limit, width, height, x0, y0, lane) == status and np.array_equal(lane, want)
-    bd, sd = torch.from_numpy(bounds).to("cuda:0"), G.to_dev(slots)
+    assert H.host_mark_instances(host, bounds, nm, slots, ninst, dirty, limit, width, height, x0, y0, lane) == status and np.array_equal(lane, want)
+    bd, sd = torch.from_numpy(bounds).to("cuda:0"), to_dev(slots)
     bits = DevBits(width, height)
     assert gpu_mark_instances(rt, warm_ctx, bd, nm, sd, ninst, dirty, limit, width, height, x0, y0, bits) == status
     first = bits.read()
@@ -190,7 +133,7 @@ def test_slot_pairs_outside_the_table(rt, warm_ctx):
     want = np.zeros(DM.words(width, height), np.uint32)
     assert DM.mark_instances(want, bounds, short, slots, ninst, dirty, None, width, height, x0, y0) == capi.VGX_E_INVALID_ARG
     bits = DevBits(width, height)
-    assert gpu_mark_instances(rt, warm_ctx, bd, short, G.to_dev(slots), ninst, dirty, None, width, height, x0, y0, bits) == capi.VGX_E_INVALID_ARG
+    assert gpu_mark_instances(rt, warm_ctx, bd, short, to_dev(slots), ninst, dirty, None, width, height, x0, y0, bits) == capi.VGX_E_INVALID_ARG
     assert np.array_equal(bits.read(), want) and want.any()
     bad = slots.copy()
     bad["first_mesh"][11] = 5
@@ -198,52 +141,52 @@ def test_slot_pairs_outside_the_table(rt, warm_ctx):
     want = np.zeros_like(want)
     assert DM.mark_instances(want, bounds, bounds.shape[0], bad, ninst, d2, None, width, height, x0, y0) == capi.VGX_E_INVALID_ARG
     bits = DevBits(width, height)
-    assert gpu_mark_instances(rt, warm_ctx, bd, bounds.shape[0], G.to_dev(bad), ninst, d2, None, width, height, x0, y0, bits) == capi.VGX_E_INVALID_ARG
+    assert gpu_mark_instances(rt, warm_ctx, bd, bounds.shape[0], to_dev(bad), ninst, d2, None, width, height, x0, y0, bits) == capi.VGX_E_INVALID_ARG
     assert np.array_equal(bits.read(), want)
 
 
 # ---- the restricted raster ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", cpu.FRAMES)
+@pytest.mark.parametrize("name", H.DAMAGE_FRAMES)
 def test_all_bits_equals_the_full_call(rt, warm_ctx, name):
     f = K.frame(name)
     t = f.target
-    df, ds, dx, dp = GC.dev_parts(f)
+    df, ds, dx, dp = dev_parts(f)
     bits = dev_bits(DM.all_bits(t.width, t.height), t.width, t.height)
     for tgt in (t, t.with_clear(CLEAR)):
-        _, full = GC.gpu_level(rt, warm_ctx, "vgx_raster_concave", df, ds, dx, dp, tgt)
-        _, got = gpu_damaged(rt, warm_ctx, df, ds, dx, dp, tgt, bits)
-        assert np.array_equal(got, full), G.where(got, full)
+        _, full = gpu_level(rt, warm_ctx, "vgx_raster_concave", df, ds, dx, dp, tgt)
+        _, got = gpu_level(rt, warm_ctx, "damaged", df, ds, dx, dp, tgt, bits=bits)
+        assert np.array_equal(got, full), where(got, full)
         assert np.array_equal(got, K.expected(name, tgt.clear is not None))
-        _, given = gpu_damaged(rt, warm_ctx, df, ds, dx, dp, tgt, bits, bounds=G.gpu_bounds(rt, warm_ctx, df))
+        _, given = gpu_level(rt, warm_ctx, "damaged", df, ds, dx, dp, tgt, bits=bits, bounds=gpu_bounds(rt, warm_ctx, df))
         assert np.array_equal(given, full)
     bits.read()
     assert df.unchanged()
 
 
-@pytest.mark.parametrize("name", cpu.FRAMES)
+@pytest.mark.parametrize("name", H.DAMAGE_FRAMES)
 def test_no_bit_and_checkerboard(rt, warm_ctx, host, name):
     f = K.frame(name)
     t = f.target
     tgt = t.with_clear(CLEAR)
-    df, ds, dx, dp = GC.dev_parts(f)
+    df, ds, dx, dp = dev_parts(f)
     sentinel = np.full((t.rows(), t.stride), DM.SENTINEL, dtype=np.uint32)
-    _, got = gpu_damaged(rt, warm_ctx, df, ds, dx, dp, tgt, DevBits(t.width, t.height), image=sentinel_image(tgt))
+    _, got = gpu_level(rt, warm_ctx, "damaged", df, ds, dx, dp, tgt, bits=DevBits(t.width, t.height), image=sentinel_image(tgt))
     assert np.array_equal(got, sentinel)  # no bit set: nothing is written, the clear included
     for phase in (0, 1):
         host_bits = DM.checkerboard(t.width, t.height, phase)
         bits = dev_bits(host_bits, t.width, t.height)
-        _, got = gpu_damaged(rt, warm_ctx, df, ds, dx, dp, tgt, bits, image=sentinel_image(tgt))
+        _, got = gpu_level(rt, warm_ctx, "damaged", df, ds, dx, dp, tgt, bits=bits, image=sentinel_image(tgt))
         want = DM.render_damaged(f, tgt, sentinel.copy(), host_bits)
-        assert np.array_equal(got, want), G.where(got, want)
-        assert np.array_equal(got, cpu.host_damaged(host, f, tgt, host_bits, image=sentinel.copy()))
+        assert np.array_equal(got, want), where(got, want)
+        assert np.array_equal(got, H.host_level(host, "damaged", f, tgt, bits=host_bits, image=sentinel.copy()))
         m = DM.tile_mask(host_bits, tgt)
         sx0, sy0, sx1, sy1 = tgt.scissor
         inside = np.zeros_like(m)
         inside[sy0:sy1, sx0:sx1] = True
         assert (got[~(m & inside)] == DM.SENTINEL).all() and np.array_equal(got[m & inside], K.expected(name, True)[m & inside])
-        _, again = gpu_damaged(rt, warm_ctx, df, ds, dx, dp, tgt, bits, image=sentinel_image(tgt))
+        _, again = gpu_level(rt, warm_ctx, "damaged", df, ds, dx, dp, tgt, bits=bits, image=sentinel_image(tgt))
         assert np.array_equal(again, got)
-        _, over = gpu_damaged(rt, warm_ctx, df, ds, dx, dp, t, bits)  # without the clear, over the background
+        _, over = gpu_level(rt, warm_ctx, "damaged", df, ds, dx, dp, t, bits=bits)  # without the clear, over the background
         assert np.array_equal(over, DM.render_damaged(f, t, t.background(), host_bits))
         assert np.array_equal(bits.read(), host_bits)
     if name == "crowd":
@@ -256,7 +199,7 @@ def test_marked_tile_cut_by_the_scissor(rt, warm_ctx):
     tgt = R.Target(t.width, t.height, t.stride, t.x0, t.y0, scissor=(5, 3, 41, 27), clear=CLEAR)
     host_bits = DM.checkerboard(t.width, t.height)
     sentinel = np.full((t.rows(), t.stride), DM.SENTINEL, dtype=np.uint32)
-    _, got = gpu_damaged(rt, warm_ctx, *GC.dev_parts(f), tgt, dev_bits(host_bits, t.width, t.height), image=sentinel_image(tgt))
+    _, got = gpu_level(rt, warm_ctx, "damaged", *dev_parts(f), tgt, bits=dev_bits(host_bits, t.width, t.height), image=sentinel_image(tgt))
     assert np.array_equal(got, DM.render_damaged(f, tgt, sentinel.copy(), host_bits))
     assert (got[3:16, 5:16] != DM.SENTINEL).all() and (got[:3] == DM.SENTINEL).all() and (got[3:16, 16:32] == DM.SENTINEL).all()
 
@@ -265,21 +208,21 @@ def test_invalid_draw_with_no_bit_set_and_mesh_ranges(rt, warm_ctx):
     g = K.state_frame()
     g.meshes["draw"][4] = 99
     tgt = g.target.with_clear(CLEAR)
-    parts = GC.dev_parts(g)
+    parts = dev_parts(g)
     for host_bits in (np.zeros(DM.words(tgt.width, tgt.height), np.uint32), DM.all_bits(tgt.width, tgt.height)):
-        _, got = gpu_damaged(rt, warm_ctx, *parts, tgt, dev_bits(host_bits, tgt.width, tgt.height), want=capi.VGX_E_INVALID_ARG)
+        _, got = gpu_level(rt, warm_ctx, "damaged", *parts, tgt, bits=dev_bits(host_bits, tgt.width, tgt.height), want=capi.VGX_E_INVALID_ARG)
         assert np.array_equal(got, tgt.background())
     f = K.frame("state")
     host_bits = DM.checkerboard(f.target.width, f.target.height, 1)
     bits = dev_bits(host_bits, f.target.width, f.target.height)
     for begin, end in ((0, 3), (2, 5), (3, 99)):
-        _, got = gpu_damaged(rt, warm_ctx, *GC.dev_parts(f), f.target, bits, begin=begin, end=end)
+        _, got = gpu_level(rt, warm_ctx, "damaged", *dev_parts(f), f.target, bits=bits, begin=begin, end=end)
         assert np.array_equal(got, DM.render_damaged(f, f.target, f.target.background(), host_bits, begin, end))
 
 
 def test_host_refusals(rt, warm_ctx):
     f = K.frame("state")
-    df, ds, dx, dp = GC.dev_parts(f)
+    df, ds, dx, dp = dev_parts(f)
     import torch
     image = torch.zeros((f.target.rows(), f.target.stride), dtype=torch.int32, device="cuda:0")
     t = f.target.struct(image.data_ptr())
@@ -290,7 +233,7 @@ def test_host_refusals(rt, warm_ctx):
     assert call(C.byref(capi.RasterDamage(None, 0, 0))) == capi.VGX_E_INVALID_ARG
     assert call(C.byref(capi.RasterDamage(bits.t.data_ptr() + 2, 0, 0))) == capi.VGX_E_INVALID_ARG
     assert call(C.byref(capi.RasterDamage(bits.t.data_ptr(), 0, 1))) == capi.VGX_E_INVALID_ARG
-    mt = cpu.mark_target(40, 24, 0, 0)
+    mt = H.mark_target(40, 24, 0, 0)
     bd = torch.zeros((4, 4), dtype=torch.float32, device="cuda:0")
     lib = rt.lib()
     assert lib.vgx_damage_meshes(warm_ctx.handle, bd.data_ptr(), 0, 4, 4, C.byref(mt), None, rt._stream_ptr()) == capi.VGX_E_INVALID_ARG
@@ -310,16 +253,16 @@ def test_max_entries_too_small_grows_then_succeeds(rt):
     try:
         f = K.frame("state")
         tgt = f.target.with_clear(CLEAR)
-        parts = GC.dev_parts(f)
+        parts = dev_parts(f)
         bits = dev_bits(DM.all_bits(tgt.width, tgt.height), tgt.width, tgt.height)
-        _, got = gpu_damaged(rt, ctx, *parts, tgt, bits, want=capi.VGX_E_GROWN, max_entries=2)
+        _, got = gpu_level(rt, ctx, "damaged", *parts, tgt, bits=bits, want=capi.VGX_E_GROWN, max_entries=2)
         assert np.array_equal(got, tgt.background())
-        _, got = gpu_damaged(rt, ctx, *parts, tgt, bits, max_entries=2)
+        _, got = gpu_level(rt, ctx, "damaged", *parts, tgt, bits=bits, max_entries=2)
         assert np.array_equal(got, K.expected("state", True))
-        _, full = GC.gpu_level(rt, ctx, "vgx_raster_concave", *parts, tgt)
-        _, got = gpu_damaged(rt, ctx, *parts, tgt, bits, max_entries=0)   # the library's window: what the last damaged call measured
+        _, full = gpu_level(rt, ctx, "vgx_raster_concave", *parts, tgt)
+        _, got = gpu_level(rt, ctx, "damaged", *parts, tgt, bits=bits, max_entries=0)   # the library's window: what the last damaged call measured
         assert np.array_equal(got, full)
-        _, got = gpu_damaged(rt, ctx, *parts, tgt, bits, max_entries=1 << 20)
+        _, got = gpu_level(rt, ctx, "damaged", *parts, tgt, bits=bits, max_entries=1 << 20)
         assert np.array_equal(got, full)
     finally:
         ctx.close()
@@ -341,11 +284,11 @@ def test_library_window_on_a_fresh_context_converges_within_two_calls(rt):
         f = many_quads()
         assert f.nm * 16 > 16384
         tgt = f.target.with_clear(CLEAR)
-        parts = GC.dev_parts(f)
+        parts = dev_parts(f)
         bits = dev_bits(DM.all_bits(tgt.width, tgt.height), tgt.width, tgt.height)
-        _, got = gpu_damaged(rt, ctx, *parts, tgt, bits, want=capi.VGX_E_GROWN, max_entries=0)
+        _, got = gpu_level(rt, ctx, "damaged", *parts, tgt, bits=bits, want=capi.VGX_E_GROWN, max_entries=0)
         assert np.array_equal(got, tgt.background())
-        _, got = gpu_damaged(rt, ctx, *parts, tgt, bits, max_entries=0)
+        _, got = gpu_level(rt, ctx, "damaged", *parts, tgt, bits=bits, max_entries=0)
         status = capi.VGX_E_GROWN
         for _ in range(3):
             if status != capi.VGX_E_GROWN:
@@ -363,7 +306,7 @@ def test_library_window_on_a_fresh_context_converges_within_two_calls(rt):
         ctx2 = rt.Context(0)
         try:
             tg = g.target.with_clear(CLEAR)
-            _, got = gpu_damaged(rt, ctx2, *GC.dev_parts(g), tg, dev_bits(DM.all_bits(tg.width, tg.height), tg.width, tg.height), max_entries=0)
+            _, got = gpu_level(rt, ctx2, "damaged", *dev_parts(g), tg, bits=dev_bits(DM.all_bits(tg.width, tg.height), tg.width, tg.height), max_entries=0)
             assert np.array_equal(got, K.expected("classes", True))
         finally:
             ctx2.close()
@@ -374,7 +317,7 @@ def test_library_window_on_a_fresh_context_converges_within_two_calls(rt):
 # ---- the property, without the model ----------------------------------------------------------------------------------------------------------
 class DevCache:
     def __init__(self, c):
-        self.t = [G.to_dev(a) for a in (c.pos, c.color, c.idx, c.meshes)]
+        self.t = [to_dev(a) for a in (c.pos, c.color, c.idx, c.meshes)]
         self.nm, self.nv, self.ni = c.meshes.shape[0], c.pos.shape[0], c.idx.shape[0]
         self.bufs = types.SimpleNamespace(pos=self.t[0])
 
@@ -396,7 +339,7 @@ class DevScene:
         self.f = f
         self.tgt = f.target.with_clear(CLEAR)
         self.bufs = rt.MeshBuffers("cuda:0", f.nv, f.ni, f.nm)
-        self.inst_dev = G.to_dev(self.inst)
+        self.inst_dev = to_dev(self.inst)
         rt.cache_submit(ctx, self.cache, self.inst_dev, self.inst.shape[0], self.bufs)
         self.slots_dev, st = rt.cache_layout(ctx, self.cache, self.inst_dev, self.inst.shape[0])
         self.bounds = rt.mesh_bounds(ctx, self.bufs.pos, self.bufs.meshes, f.nm)
@@ -407,12 +350,12 @@ class DevScene:
         assert np.array_equal(self.bufs.color[:f.nv].cpu().numpy().view(np.uint32), f.color)
         gm = self.bufs.meshes[:f.nm * 32].cpu().numpy().view(capi.mesh_dtype)
         assert all(np.array_equal(gm[k], f.meshes[k]) for k in gm.dtype.names)
-        self.ds, self.dx, self.dp = GC.GF.DevState(f), GC.GT.DevTex(f), GC.GP.DevPaints(f.gradients, f.patterns)
+        self.ds, self.dx, self.dp = H.DevState(f), H.DevTex(f), H.DevPaints(f.gradients, f.patterns)
         self.df = types.SimpleNamespace(desc=rt.mesh_seq(self.bufs, f.nv, f.ni, f.nm))
         self.keep = []
 
     def full(self):
-        return GC.gpu_level(self.rt, self.ctx, "vgx_raster_concave", self.df, self.ds, self.dx, self.dp, self.tgt, bounds=self.bounds)[1]
+        return gpu_level(self.rt, self.ctx, "vgx_raster_concave", self.df, self.ds, self.dx, self.dp, self.tgt, bounds=self.bounds)[1]
 
     def zero_bits(self):
         return DevBits(self.tgt.width, self.tgt.height)
@@ -422,7 +365,7 @@ class DevScene:
 
     def mark(self, dirty, bits):
         t = self.tgt
-        dd = G.to_dev(np.ascontiguousarray(dirty, dtype=np.uint32))
+        dd = to_dev(np.ascontiguousarray(dirty, dtype=np.uint32))
         st = self.rt.damage_instances(self.ctx, self.bounds, self.f.nm, self.slots_dev, self.inst.shape[0], dd, dirty.shape[0], t.width, t.height, bits.t,
                                       x0=t.x0, y0=t.y0)
         self.keep += [dd, st]   # alive until the scene goes: the calls are asynchronous
@@ -430,7 +373,7 @@ class DevScene:
 
     def update(self, inst, dirty):
         self.inst = inst
-        di, dd = G.to_dev(inst), G.to_dev(np.ascontiguousarray(dirty, dtype=np.uint32))
+        di, dd = to_dev(inst), to_dev(np.ascontiguousarray(dirty, dtype=np.uint32))
         st = self.rt.cache_update(self.ctx, self.cache, di, inst.shape[0], self.slots_dev, dd, dirty.shape[0], self.bufs.pos, self.bufs.color, self.f.nv, self.f.nm,
                                   mesh_bounds=self.bounds)
         self.keep += [di, dd, st]
@@ -439,10 +382,10 @@ class DevScene:
     def damaged(self, image, bits):
         import torch
         dev = torch.from_numpy(np.ascontiguousarray(image).view(np.int32)).to("cuda:0")
-        _, got = gpu_damaged(self.rt, self.ctx, self.df, self.ds, self.dx, self.dp, self.tgt, bits, image=dev, bounds=self.bounds)
+        _, got = gpu_level(self.rt, self.ctx, "damaged", self.df, self.ds, self.dx, self.dp, self.tgt, bits=bits, image=dev, bounds=self.bounds)
         assert all(int(s.item()) == capi.VGX_OK for s in self.statuses)
         return got
 
 
 def test_property_through_the_kernels(rt, warm_ctx):
-    cpu.check_property(DevScene(rt, warm_ctx))
+    H.check_damage_property(DevScene(rt, warm_ctx))

@@ -6,56 +6,31 @@ The shapes are the smallest at which the kernels can go wrong: `stack_clip` puts
 resolve stage carries a stamp across a chunk), `star300` has contour meshes of more edges than a wave, the `walk` meshes (8 008 vertices)
 cross element tiles and wave windows."""
 import ctypes as C
-import importlib
 
 import numpy as np
 import pytest
 
 import pick_frame_model as PF
 import raster_frame_model as M
-import test_gpu_pick as GPK
-import test_gpu_raster as G
-import test_gpu_raster_concave as GC
-import test_gpu_raster_frame as GF
-import test_pick_frame_cpu as cpu
+import raster_harness as H
+from raster_harness import first_difference, gpu_bounds, host, rt, same, to_dev  # noqa: F401 (host, rt: fixtures)
 
 pytestmark = pytest.mark.gpu
 capi = PF.capi
 F = np.float32
 NONE = PF.NONE
-PATTERN = 0x5A5A5A5A
-ALL = 2**64 - 1
-
-
-@pytest.fixture(scope="module")
-def rt():
-    return importlib.import_module("vg-renderer_amd.runtime")
-
-
-@pytest.fixture(scope="module")
-def host():
-    return _load_host()
-
-
-def _load_host():
-    lib = cpu.ccpu.load_host()
-    lib.vgxt_pick_frame.restype = C.c_int
-    lib.vgxt_pick_frame.argtypes = [C.POINTER(capi.CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(capi.RasterDraws), C.c_void_p, C.c_uint32,
-                                    C.c_void_p, C.c_void_p]
-    lib.vgxt_mesh_bounds.restype = None
-    lib.vgxt_mesh_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-    return lib
+PATTERN = H.HITS_GUARD
+ALL = H.OPEN
 
 
 class Dev:
     """A frame and its draw table in device memory."""
 
     def __init__(self, f):
-        self.f, self.frame, self.state = f, G.DevFrame(f), GF.DevState(f)
+        self.f, self.frame, self.state = f, H.DevFrame(f), H.DevState(f)
 
     def unchanged(self):
-        return self.frame.unchanged() and all(np.array_equal(t.cpu().numpy()[:h.nbytes], np.ascontiguousarray(h).view(np.uint8).reshape(-1))
-                                              for t, h in zip(self.state.t, (self.f.draws, self.f.dstate)) if h.nbytes)
+        return self.frame.unchanged() and self.state.unchanged()
 
 
 _devs = {}
@@ -73,7 +48,7 @@ def gpu_pick_frame(rt, ctx, d, queries, bounds=None, begin=0, end=ALL, want=capi
     import torch
     out = np.zeros(queries.shape[0], dtype=capi.pick_hit_dtype)
     for a, b in PF.chunks(queries.shape[0], chunk) or [(0, 0)]:
-        q = G.to_dev(queries[a:b])
+        q = to_dev(queries[a:b])
         h = torch.full(((b - a + guard) * 4,), PATTERN, dtype=torch.int32, device="cuda:0")
         status = torch.full((3,), 77, dtype=torch.int32, device="cuda:0")
         st = rt.lib().vgx_pick_frame(ctx.handle, C.byref(d.frame.desc), None if bounds is None else bounds.data_ptr(), begin, end, C.byref(d.state.struct),
@@ -88,22 +63,19 @@ def gpu_pick_frame(rt, ctx, d, queries, bounds=None, begin=0, end=ALL, want=capi
     return out
 
 
-same, first_difference = cpu.same, cpu.first_difference
-
-
 @pytest.mark.parametrize("key", PF.ALL, ids=lambda k: "-".join(str(v) for v in k))
 def test_kernels_equal_model_and_lane_code(rt, gpu_ctx, host, key):
     f, qs = PF.frame(key), PF.query_set(key)
     PF.check_conditions(key)
     want = PF.expected(key)
     d = dev(key)
-    mb = G.gpu_bounds(rt, gpu_ctx, d.frame)
+    mb = gpu_bounds(rt, gpu_ctx, d.frame)
     with_boxes = gpu_pick_frame(rt, gpu_ctx, d, qs.queries, mb)
     assert same(with_boxes, want.hits), first_difference(with_boxes, want.hits, qs.queries)
     own_boxes = gpu_pick_frame(rt, gpu_ctx, d, qs.queries, None, with_status=False)
     assert same(own_boxes, with_boxes), first_difference(own_boxes, with_boxes, qs.queries)
     if key in PF.IMAGES:  # the reference's streams are large for a sequential loop; tests/test_pick_frame_cpu.py holds the lane code to the same model
-        assert same(cpu.host_pick_frame(host, f, qs.queries), with_boxes)
+        assert same(H.host_pick_frame(host, f, qs.queries), with_boxes)
     assert d.unchanged()
     assert np.array_equal(mb.cpu().numpy()[:f.nm], PF.CM.mesh_boxes(f.pos, f.meshes))  # mesh_bounds as it was, too
 
@@ -120,7 +92,7 @@ def test_query_counts(rt, gpu_ctx, nq):
 def device_ids(rt, ctx, f, begin=0):
     g, tgt = PF.id_frame(f)
     rt.raster_reserve(ctx, 8192, 1 << 17)  # the bin tables ahead, so that no call ends with VGX_E_GROWN
-    return PF.decode_ids(GC.gpu_level(rt, ctx, "vgx_raster_concave", *GC.dev_parts(g), tgt, begin=begin)[1], tgt)
+    return PF.decode_ids(H.gpu_level(rt, ctx, "concave", *H.dev_parts(g), tgt, begin=begin)[1], tgt)
 
 
 @pytest.mark.parametrize("key", [("concave", "state"), ("frame", "stack_clip"), ("concave", "centres"), ("concave", "star300"), ("frame", "decoded")],
@@ -136,10 +108,10 @@ def test_relation_a_the_image_is_the_oracle(rt, gpu_ctx, key):
 
 
 def test_relation_b_equals_vgx_pick_away_from_edges(rt, gpu_ctx):
-    f, q, want = cpu.relation_b_queries()
+    f, q, want = H.relation_b_queries()
     d = dev(PF.TIGER)
     got = gpu_pick_frame(rt, gpu_ctx, d, q)
-    old = GPK.gpu_pick(rt, gpu_ctx, GPK.dev_frame(f.pick), q, None)
+    old = H.gpu_pick(rt, gpu_ctx, d.frame, q)
     assert same(got, want)
     assert same(got, old), first_difference(got, old, q)
     assert int((got["mesh"] != NONE).sum()) > 100
@@ -182,12 +154,12 @@ def test_no_leak_between_calls(rt, gpu_ctx):
     """vgx_pick, vgx_pick_frame, vgx_pick on one context, then two vgx_pick_frame calls of 256 queries and of 1: each its own answers."""
     key = PF.TIGER
     f, qs, want = PF.frame(key), PF.query_set(key), PF.expected(key)
-    d, old = dev(key), GPK.dev_frame(f.pick)
+    d = dev(key)
     pq = f.pick.queries[:256]
-    first = GPK.gpu_pick(rt, gpu_ctx, old, pq, None)
+    first = H.gpu_pick(rt, gpu_ctx, d.frame, pq)
     assert same(first, f.pick.hits[:256])
     assert same(gpu_pick_frame(rt, gpu_ctx, d, qs.queries[:256]), want.hits[:256])
-    assert same(GPK.gpu_pick(rt, gpu_ctx, old, pq, None), first)
+    assert same(H.gpu_pick(rt, gpu_ctx, d.frame, pq), first)
     key = ("concave", "star300")
     qs, want = PF.query_set(key), PF.expected(key)
     hit = int(np.nonzero(want.hits["mesh"][:qs.centres] != NONE)[0][0])
@@ -208,7 +180,7 @@ def test_scratch_bytes(rt):
         lib = rt.lib()
         lib.vgx_scratch_bytes.restype = C.c_uint64
         d = Dev(f)
-        mb = G.gpu_bounds(rt, ctx, d.frame)
+        mb = gpu_bounds(rt, ctx, d.frame)
         b0 = lib.vgx_scratch_bytes(ctx.handle)
         gpu_pick_frame(rt, ctx, d, qs.queries[:256], mb)
         b1 = lib.vgx_scratch_bytes(ctx.handle)
@@ -237,7 +209,7 @@ def test_counted_state_survives(rt, gpu_ctx, wl, oracle):
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        hits, status = rt.pick_frame(gpu_ctx, d.frame.desc, d.state.t[0], d.state.t[1], d.f.draws.shape[0], G.to_dev(qs.queries[:256]), 256)
+        hits, status = rt.pick_frame(gpu_ctx, d.frame.desc, d.state.t[0], d.state.t[1], d.f.draws.shape[0], to_dev(qs.queries[:256]), 256)
     bufs = rt.MeshBuffers(dd.device, sizes["num_vertices"], sizes["num_indices"], sizes["num_meshes"])
     rt.tessellate_emit(gpu_ctx, pset, dd, dr.shape[0], bufs)
     torch.cuda.synchronize()

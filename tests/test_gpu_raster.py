@@ -2,85 +2,18 @@
 tests/test_raster_cpu.py, and against the lane code (vgxt_raster) on a 65-instance Tiger frame the model would be slow on. Every
 comparison is np.array_equal on the whole uint32 buffer: the stride padding and everything outside the scissor included."""
 import ctypes as C
-import importlib
 
 import numpy as np
 import pytest
 
+import raster_harness as H
 import raster_model as R
+from raster_harness import DevFrame, dev_frame, gpu_bounds, rt, warm_ctx, where  # noqa: F401 (rt, warm_ctx: fixtures)
 
 pytestmark = pytest.mark.gpu
 capi = R.capi
 F = np.float32
 CLEAR = 0xFF102030
-
-
-@pytest.fixture(scope="module")
-def rt():
-    return importlib.import_module("vg-renderer_amd.runtime")
-
-
-def to_dev(a):
-    import torch
-    raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    return torch.from_numpy(raw.copy() if raw.size else np.zeros(16, dtype=np.uint8)).to("cuda:0")
-
-
-class DevFrame:
-    def __init__(self, f):
-        self.f = f
-        self.host = (f.pos, f.color, f.idx, f.meshes)
-        self.t = [to_dev(a) for a in self.host]
-        self.desc = f.desc([t.data_ptr() for t in self.t])
-
-    def unchanged(self):
-        return all(np.array_equal(t.cpu().numpy()[:h.nbytes], h.view(np.uint8).reshape(-1)) for t, h in zip(self.t, self.host))
-
-
-_frames = {}
-
-
-def dev_frame(f):
-    if f.name not in _frames:
-        _frames[f.name] = DevFrame(f)
-    return _frames[f.name]
-
-
-def gpu_bounds(rt, ctx, df):
-    import torch
-    out = torch.empty((max(df.f.nm, 1), 4), dtype=torch.float32, device="cuda:0")
-    assert rt.lib().vgx_mesh_bounds(ctx.handle, df.t[0].data_ptr(), df.t[3].data_ptr(), df.f.nm, out.data_ptr(), rt._stream_ptr()) == 0
-    return out
-
-
-def gpu_raster(rt, ctx, df, tgt, image=None, bounds=None, begin=0, end=2**64 - 1, want=capi.VGX_OK):
-    """One vgx_raster call over the target's background (or `image`, a device tensor, changed in place), synchronised; returns
-    (image tensor, image as uint32 [rows, stride])."""
-    import torch
-    if image is None:
-        image = torch.from_numpy(tgt.background().view(np.int32)).to("cuda:0")
-    status = torch.full((3,), 77, dtype=torch.int32, device="cuda:0")
-    t = tgt.struct(image.data_ptr())
-    st = rt.lib().vgx_raster(ctx.handle, C.byref(df.desc), None if bounds is None else bounds.data_ptr(), begin, end, C.byref(t), status.data_ptr(),
-                             rt._stream_ptr())
-    torch.cuda.synchronize()
-    assert st == capi.VGX_OK
-    assert status.cpu().tolist() == [want, 77, 77]
-    return image, image.cpu().numpy().view(np.uint32)
-
-
-def where(a, b):
-    j, i = np.nonzero(a != b)
-    return (int(j.size), [(int(x), int(y), hex(int(a[y, x])), hex(int(b[y, x]))) for y, x in list(zip(j, i))[:6]])
-
-
-@pytest.fixture(scope="module")
-def warm_ctx(rt):
-    """A context whose raster scratch has room for every frame here: the tests of the result do not meet VGX_E_GROWN."""
-    ctx = rt.Context(0)
-    rt.raster_reserve(ctx, 8192, 1 << 17)
-    yield ctx
-    ctx.close()
 
 
 @pytest.mark.parametrize("clear", [False, True])
@@ -91,13 +24,13 @@ def test_kernels_equal_model(rt, warm_ctx, name, clear):
     df = dev_frame(f)
     tgt = f.target.with_clear(CLEAR) if clear else f.target
     want = R.expected(name, clear)
-    _, own = gpu_raster(rt, warm_ctx, df, tgt)
+    _, own = H.gpu_level(rt, warm_ctx, "raster", df, tgt=tgt)
     assert np.array_equal(own, want), where(own, want)
     assert R.guards_intact(tgt, own)
     mb = gpu_bounds(rt, warm_ctx, df)
-    _, given = gpu_raster(rt, warm_ctx, df, tgt, bounds=mb)
+    _, given = H.gpu_level(rt, warm_ctx, "raster", df, tgt=tgt, bounds=mb)
     assert np.array_equal(given, want), where(given, want)
-    _, again = gpu_raster(rt, warm_ctx, df, tgt)
+    _, again = H.gpu_level(rt, warm_ctx, "raster", df, tgt=tgt)
     assert np.array_equal(again, own)  # two runs, the same bytes
     assert df.unchanged()
 
@@ -109,14 +42,14 @@ def test_split_mesh_ranges(rt, warm_ctx, name):
     want = R.expected(name)
     mb = gpu_bounds(rt, warm_ctx, df)
     for n, k in enumerate(sorted({1, f.nm // 3, f.nm - 1})):
-        img, _ = gpu_raster(rt, warm_ctx, df, f.target, end=k, bounds=mb if n % 2 else None)
-        _, got = gpu_raster(rt, warm_ctx, df, f.target, image=img, begin=k, bounds=None if n % 2 else mb)
+        img, _ = H.gpu_level(rt, warm_ctx, "raster", df, tgt=f.target, end=k, bounds=mb if n % 2 else None)
+        _, got = H.gpu_level(rt, warm_ctx, "raster", df, tgt=f.target, image=img, begin=k, bounds=None if n % 2 else mb)
         assert np.array_equal(got, want), (k, where(got, want))
     # an empty range writes nothing, or only the clear
-    _, got = gpu_raster(rt, warm_ctx, df, f.target, begin=f.nm)
+    _, got = H.gpu_level(rt, warm_ctx, "raster", df, tgt=f.target, begin=f.nm)
     assert np.array_equal(got, f.target.background())
     tc = f.target.with_clear(0x01020304)
-    _, got = gpu_raster(rt, warm_ctx, df, tc, begin=1, end=1)
+    _, got = H.gpu_level(rt, warm_ctx, "raster", df, tgt=tc, begin=1, end=1)
     sx0, sy0, sx1, sy1 = tc.scissor
     assert np.all(got[sy0:sy1, sx0:sx1] == 0x01020304) and R.guards_intact(tc, got)
 
@@ -129,22 +62,21 @@ def tiger65():
 
 
 def test_kernels_equal_lane_code_on_65_tigers(rt, warm_ctx, tiger65):
-    import test_raster_cpu as cpu
     f = tiger65
-    host = cpu.load_host()
+    host = H.load_host()
     df = DevFrame(f)
     for tgt in (f.target, f.target.with_clear(CLEAR)):
-        want = cpu.host_render(host, f, tgt)
+        want = H.host_level(host, "raster", f, tgt)
         assert int((want != tgt.background()).sum()) > 100000
-        _, got = gpu_raster(rt, warm_ctx, df, tgt)
+        _, got = H.gpu_level(rt, warm_ctx, "raster", df, tgt=tgt)
         assert np.array_equal(got, want), where(got, want)
         assert R.guards_intact(tgt, got)
-        _, given = gpu_raster(rt, warm_ctx, df, tgt, bounds=gpu_bounds(rt, warm_ctx, df))
+        _, given = H.gpu_level(rt, warm_ctx, "raster", df, tgt=tgt, bounds=gpu_bounds(rt, warm_ctx, df))
         assert np.array_equal(given, want)
     k = f.nm // 2 + 7
-    img, _ = gpu_raster(rt, warm_ctx, df, f.target, end=k)
-    _, got = gpu_raster(rt, warm_ctx, df, f.target, image=img, begin=k)
-    assert np.array_equal(got, cpu.host_render(host, f, f.target))
+    img, _ = H.gpu_level(rt, warm_ctx, "raster", df, tgt=f.target, end=k)
+    _, got = H.gpu_level(rt, warm_ctx, "raster", df, tgt=f.target, image=img, begin=k)
+    assert np.array_equal(got, H.host_level(host, "raster", f, f.target))
     assert df.unchanged()
 
 
@@ -160,15 +92,15 @@ def test_fresh_context_grows_then_succeeds(rt):
     ctx = rt.Context(0)
     try:
         before = int(rt.lib().vgx_scratch_bytes(ctx.handle))
-        img, got = gpu_raster(rt, ctx, df, tgt, want=capi.VGX_E_GROWN)
+        img, got = H.gpu_level(rt, ctx, "raster", df, tgt=tgt, want=capi.VGX_E_GROWN)
         assert np.array_equal(got, tgt.background())
         first = int(rt.lib().vgx_scratch_bytes(ctx.handle))
         assert first - before >= 16 * f.nm
-        _, got = gpu_raster(rt, ctx, df, tgt, image=img)
+        _, got = H.gpu_level(rt, ctx, "raster", df, tgt=tgt, image=img)
         assert np.array_equal(got, R.expected("tiger", True)), where(got, R.expected("tiger", True))
         grown = int(rt.lib().vgx_scratch_bytes(ctx.handle))
         assert grown - first >= 16 * (entries // 2 - f.nm) > 0
-        _, got = gpu_raster(rt, ctx, df, tgt)
+        _, got = H.gpu_level(rt, ctx, "raster", df, tgt=tgt)
         assert np.array_equal(got, R.expected("tiger", True))
         assert int(rt.lib().vgx_scratch_bytes(ctx.handle)) == grown  # and stays
     finally:
@@ -178,7 +110,7 @@ def test_fresh_context_grows_then_succeeds(rt):
         rt.raster_reserve(ctx, f.nm, entries)
         reserved = int(rt.lib().vgx_scratch_bytes(ctx.handle))
         assert reserved >= 16 * entries + 12 * f.nm
-        _, got = gpu_raster(rt, ctx, df, tgt)
+        _, got = H.gpu_level(rt, ctx, "raster", df, tgt=tgt)
         assert np.array_equal(got, R.expected("tiger", True))
     finally:
         ctx.close()
@@ -220,29 +152,7 @@ def test_runtime_wrapper_and_refused_calls(rt, warm_ctx):
 
 def test_counted_state_survives(rt, gpu_ctx, wl, oracle):
     """vgx_tessellate_count -> vgx_raster of another stream -> vgx_tessellate_emit gives the meshes it gives without the raster call."""
-    import torch
     f = R.frame("stack")
     df = dev_frame(f)
-    ps, d = wl.tiger(3)
-    ref = oracle.tessellate(ps, d)
-    pset = rt.PathSet(gpu_ctx, ps)
-    dd = rt.upload_draws(d)
-    sizes = rt.tessellate_count(gpu_ctx, pset, dd, d.shape[0])
-    img = None
-    for _ in range(2):  # the first call of this context may end with VGX_E_GROWN; either way the counted state must survive
-        img, status = rt.raster(gpu_ctx, df.desc, f.target.width, f.target.height, clear_color=CLEAR)
-        torch.cuda.synchronize()
-    assert int(status.item()) == capi.VGX_OK
-    bufs = rt.MeshBuffers(dd.device, sizes["num_vertices"], sizes["num_indices"], sizes["num_meshes"])
-    rt.tessellate_emit(gpu_ctx, pset, dd, d.shape[0], bufs)
-    torch.cuda.synchronize()
-    pset.close()
-    nv, ni, nm = ref.sizes["num_vertices"], ref.sizes["num_indices"], ref.sizes["num_meshes"]
-    assert (sizes["num_vertices"], sizes["num_indices"], sizes["num_meshes"]) == (nv, ni, nm)
-    assert np.array_equal(bufs.pos[:nv].cpu().numpy().view(np.uint32), ref.pos.view(np.uint32))
-    assert np.array_equal(bufs.color[:nv].cpu().numpy().view(np.uint32), ref.color)
-    assert np.array_equal(bufs.idx[:ni].cpu().numpy().view(np.uint16), ref.idx)
-    gm = bufs.meshes[:nm * 32].cpu().numpy().view(capi.mesh_dtype)
-    for name in ref.meshes.dtype.names:
-        assert np.array_equal(gm[name], ref.meshes[name]), name
-    assert np.array_equal(img.cpu().numpy().view(np.uint32), R.expected("stack", True))
+    H.check_counted_state_survives(rt, gpu_ctx, wl, oracle, lambda: rt.raster(gpu_ctx, df.desc, f.target.width, f.target.height, clear_color=CLEAR),
+                                   R.expected("stack", True))

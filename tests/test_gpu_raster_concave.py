@@ -1,44 +1,23 @@
 """GPU: vgx_raster_concave (csrc/vgx_raster.hip: the frame family at the concave level, k_rasterf_tiles<true, true, true> on the tiles a
 contour mesh reaches) against the numpy statement (tests/raster_concave_model.py) and the lane code on the shared frames, against the
-checks of tests/test_raster_concave_cpu.py and tests/test_concave_contours_cpu.py that do not rest on that model (the triangle twin, the
+checks of tests/raster_harness.py that do not rest on that model (the triangle twin, the
 convex fan, libtess2's triangulations, the reference's AA mesh), run here through the kernels, and end to end from command-list bytes:
 vgx_cmdlist_decode -> the tessellator -> vgx_flatten -> vgx_concave_contours -> vgx_merge -> vgx_raster_concave, no libtess2 and no host
 visit between decode and image. Every comparison is np.array_equal on the whole uint32 buffer."""
-import ctypes as C
-import importlib
-
 import numpy as np
 import pytest
 
 import cmdlist_util as cu
 import raster_concave_model as K
-import raster_frame_model as M
+import raster_harness as H
 import raster_model as R
 import raster_painted_model as P
-import test_concave_contours_cpu as ccpu
 import test_gpu_concave as TC
-import test_gpu_raster as G
-import test_gpu_raster_frame as GF
-import test_gpu_raster_painted as GP
-import test_gpu_raster_textured as GT
-import test_raster_concave_cpu as cpu
+from raster_harness import DevRunner, dev_parts, gpu_bounds, gpu_level, host, rt, warm_ctx, where  # noqa: F401 (host, rt, warm_ctx: fixtures)
 
 pytestmark = pytest.mark.gpu
 capi = R.capi
 CLEAR = K.CLEAR
-
-
-@pytest.fixture(scope="module")
-def rt():
-    return importlib.import_module("vg-renderer_amd.runtime")
-
-
-@pytest.fixture(scope="module")
-def warm_ctx(rt):
-    ctx = rt.Context(0)
-    rt.raster_reserve(ctx, 8192, 1 << 17)
-    yield ctx
-    ctx.close()
 
 
 @pytest.fixture(scope="module")
@@ -48,47 +27,9 @@ def ref(oracle):
     return TC.load_ref(oracle)
 
 
-def gpu_level(rt, ctx, fn, df, ds, dx, dp, tgt, image=None, bounds=None, begin=0, end=2**64 - 1, want=capi.VGX_OK):
-    """One call of vgx_raster_painted or vgx_raster_concave over the target's background (or `image`, a device tensor, changed in place),
-    synchronised; returns (image tensor, image as uint32 [rows, stride])."""
-    import torch
-    if image is None:
-        image = torch.from_numpy(tgt.background().view(np.int32)).to("cuda:0")
-    status = torch.full((3,), 77, dtype=torch.int32, device="cuda:0")
-    t = tgt.struct(image.data_ptr())
-    st = getattr(rt.lib(), fn)(ctx.handle, C.byref(df.desc), None if bounds is None else bounds.data_ptr(), begin, end, C.byref(ds.struct),
-                               C.byref(dx.struct), C.byref(dp.struct), C.byref(t), status.data_ptr(), rt._stream_ptr())
-    torch.cuda.synchronize()
-    assert st == capi.VGX_OK
-    assert status.cpu().tolist() == [want, 77, 77]
-    return image, image.cpu().numpy().view(np.uint32)
-
-
-def dev_parts(f):
-    return G.DevFrame(f), GF.DevState(f), GT.DevTex(f), GP.DevPaints(f.gradients, f.patterns)
-
-
-class DevRunner:
-    """The runner of the model-independent checks over the kernels (tests/test_raster_concave_cpu.py: HostRunner)."""
-
-    def __init__(self, rt, ctx):
-        self.rt, self.ctx = rt, ctx
-
-    def concave(self, f, tgt, **kw):
-        return gpu_level(self.rt, self.ctx, "vgx_raster_concave", *dev_parts(f), tgt, **kw)[1]
-
-    def painted(self, f, tgt, **kw):
-        return gpu_level(self.rt, self.ctx, "vgx_raster_painted", *dev_parts(f), tgt, **kw)[1]
-
-
 @pytest.fixture(scope="module")
 def run(rt, warm_ctx):
     return DevRunner(rt, warm_ctx)
-
-
-@pytest.fixture(scope="module")
-def host():
-    return ccpu.load_host()
 
 
 @pytest.mark.parametrize("name", K.NAMES)
@@ -97,16 +38,16 @@ def test_kernels_equal_model_and_lane_code(rt, warm_ctx, host, name):
     K.check_conditions(name)
     f = K.frame(name)
     df, ds, dx, dp = dev_parts(f)
-    mb = G.gpu_bounds(rt, warm_ctx, df)
+    mb = gpu_bounds(rt, warm_ctx, df)
     for clear in (False, True):
         tgt = f.target.with_clear(CLEAR) if clear else f.target
         want = K.expected(name, clear)
         _, own = gpu_level(rt, warm_ctx, "vgx_raster_concave", df, ds, dx, dp, tgt)
-        assert np.array_equal(own, want), G.where(own, want)
-        assert np.array_equal(own, cpu.host_level(host, "vgxt_raster_concave", f, tgt))
+        assert np.array_equal(own, want), where(own, want)
+        assert np.array_equal(own, H.host_level(host, "concave", f, tgt))
         assert R.guards_intact(tgt, own)
         _, given = gpu_level(rt, warm_ctx, "vgx_raster_concave", df, ds, dx, dp, tgt, bounds=mb)
-        assert np.array_equal(given, want), G.where(given, want)
+        assert np.array_equal(given, want), where(given, want)
         _, again = gpu_level(rt, warm_ctx, "vgx_raster_concave", df, ds, dx, dp, tgt)
         assert np.array_equal(again, own)  # two runs, the same bytes
     assert df.unchanged() and dp.unchanged()
@@ -125,23 +66,23 @@ def test_mesh_range_and_invalid_draw(rt, warm_ctx, run):
 
 # ---- the checks that do not rest on the model --------------------------------------------------------------------------------
 def test_triangle_twin(run):
-    cpu.check_triangle_twin(run)
+    H.check_triangle_twin(run)
 
 
 def test_convex_polygon_equals_fan(run):
-    cpu.check_convex_fan(run)
+    H.check_convex_fan(run)
 
 
 def test_simple_concave_polygons_equal_libtess2(run, ref):
-    cpu.check_simple_concave(run, ref)
+    H.check_simple_concave(run, ref)
 
 
 def test_crossing_fixtures_equal_libtess2_away_from_rounded_vertices(run, ref):
-    cpu.check_crossing(run, ref)
+    H.check_crossing(run, ref)
 
 
 def test_aa_pair_image_equals_the_reference_mesh(run, host, ref):
-    ccpu.check_aa_pair_image(run, host, ref)
+    H.check_aa_pair_image(run, host, ref)
 
 
 # ---- a decoded command list through the chain of the example -------------------------------------------------------------------
@@ -231,8 +172,8 @@ def test_decoded_command_list_through_the_chain(rt, warm_ctx, host):
         tgt = f.target.with_clear(CLEAR) if clear else f.target
         want = K.render(f, tgt, tgt.background())
         _, got = gpu_level(rt, warm_ctx, "vgx_raster_concave", Dev, ds, dx, dp, tgt)
-        assert np.array_equal(got, want), G.where(got, want)
-        assert np.array_equal(got, cpu.host_level(host, "vgxt_raster_concave", f, tgt))
+        assert np.array_equal(got, want), where(got, want)
+        assert np.array_equal(got, H.host_level(host, "concave", f, tgt))
     st = P.Stats(f.target)
     K.render(f, f.target, f.target.background(), stats=st)
     for m in cm:

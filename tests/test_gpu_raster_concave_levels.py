@@ -2,41 +2,22 @@
 WITH them through vgx_raster, vgx_raster_frame, vgx_raster_textured and vgx_raster_painted gives the image of the frame with those
 meshes removed; vgx_pick never reports one; calls of different levels in alternation on one context do not leak state; VGX_E_GROWN,
 then success on the second try; vgx_scratch_bytes counts the third tile bitmap; a counted state survives."""
-import importlib
-
 import numpy as np
 import pytest
 
 import raster_concave_model as K
+import raster_harness as H
 import raster_model as R
 import raster_painted_model as P
-import raster_textured_model as T
-import test_gpu_raster as G
-import test_gpu_raster_frame as GF
-import test_gpu_raster_textured as GT
-import test_gpu_raster_concave as GC
-import test_raster_concave_cpu as cpu
+from raster_harness import DevFrame, dev_parts, gpu_level, rt, to_dev, warm_ctx, where  # noqa: F401 (rt, warm_ctx: fixtures)
 
 pytestmark = pytest.mark.gpu
 capi = R.capi
 CLEAR = K.CLEAR
 
 
-@pytest.fixture(scope="module")
-def rt():
-    return importlib.import_module("vg-renderer_amd.runtime")
-
-
-@pytest.fixture(scope="module")
-def warm_ctx(rt):
-    ctx = rt.Context(0)
-    rt.raster_reserve(ctx, 8192, 1 << 17)
-    yield ctx
-    ctx.close()
-
-
 def test_levels(rt, warm_ctx):
-    cpu.check_levels(GC.DevRunner(rt, warm_ctx))
+    H.check_levels(H.DevRunner(rt, warm_ctx))
 
 
 @pytest.mark.parametrize("name", ["state", "classes", "odd"])
@@ -45,14 +26,14 @@ def test_older_calls_skip_contour_meshes(rt, warm_ctx, name):
     g = K.without_contours(f)
     tgt = f.target
     for fr, keep in ((f, "with"), (g, "without")):
-        df, ds, dx, dp = GC.dev_parts(fr)
-        imgs = [G.gpu_raster(rt, warm_ctx, df, tgt)[1], GF.gpu_frame(rt, warm_ctx, df, ds, tgt)[1], GT.gpu_textured(rt, warm_ctx, df, ds, dx, tgt)[1],
-                GC.gpu_level(rt, warm_ctx, "vgx_raster_painted", df, ds, dx, dp, tgt)[1]]
+        df, ds, dx, dp = dev_parts(fr)
+        imgs = [gpu_level(rt, warm_ctx, "raster", df, tgt=tgt)[1], gpu_level(rt, warm_ctx, "frame", df, ds, tgt=tgt)[1], gpu_level(rt, warm_ctx, "textured", df, ds, dx, tgt=tgt)[1],
+                gpu_level(rt, warm_ctx, "vgx_raster_painted", df, ds, dx, dp, tgt)[1]]
         if keep == "with":
             got = imgs
         else:
             for a, b in zip(got, imgs):
-                assert np.array_equal(a, b), G.where(a, b)
+                assert np.array_equal(a, b), where(a, b)
     assert np.array_equal(got[3], P.render(g, tgt, tgt.background()))
     assert not np.array_equal(got[3], K.expected(name))
 
@@ -60,11 +41,11 @@ def test_older_calls_skip_contour_meshes(rt, warm_ctx, name):
 def test_pick_never_reports_a_contour_mesh(rt, warm_ctx):
     import torch
     f = K.frame("state")
-    df = G.DevFrame(f)
+    df = DevFrame(f)
     pts = [(14.0, 9.0), (48.0, 12.0), (12.0, 27.0), (48.0, 30.0), (60.0, 38.0)]   # inside contour meshes 1 / 2, 4, 5, 6, and on the backdrop alone
     q = np.zeros(len(pts), dtype=capi.pick_query_dtype)
     q["x"], q["y"], q["mesh_end"] = [p[0] for p in pts], [p[1] for p in pts], 0xFFFFFFFF
-    hits = rt.pick(warm_ctx, df.desc, G.to_dev(q), len(pts)).cpu().numpy().view(capi.pick_hit_dtype)[:len(pts)]
+    hits = rt.pick(warm_ctx, df.desc, to_dev(q), len(pts)).cpu().numpy().view(capi.pick_hit_dtype)[:len(pts)]
     torch.cuda.synchronize()
     for (x, y), m in zip(pts[:4], (2, 4, 5, 6)):
         assert K.covered(f, m, f.target)[int(y), int(x)], m   # the query lies inside a contour mesh
@@ -76,60 +57,37 @@ def test_alternating_levels_do_not_leak_state(rt):
     try:
         rt.raster_reserve(ctx, 8192, 1 << 17)
         c, p = K.frame("classes"), P.frame("classes")
-        dc, dp_ = GC.dev_parts(c), GC.dev_parts(p)
+        dc, dp_ = dev_parts(c), dev_parts(p)
         r = R.frame("lattice")
         for _ in range(2):
-            _, got = GC.gpu_level(rt, ctx, "vgx_raster_concave", *dc, c.target)
+            _, got = gpu_level(rt, ctx, "vgx_raster_concave", *dc, c.target)
             assert np.array_equal(got, K.expected("classes"))
-            _, got = GC.gpu_level(rt, ctx, "vgx_raster_painted", *dp_, p.target)
+            _, got = gpu_level(rt, ctx, "vgx_raster_painted", *dp_, p.target)
             assert np.array_equal(got, P.expected("classes"))
-            _, got = GC.gpu_level(rt, ctx, "vgx_raster_concave", *dp_, p.target)   # no contour mesh: the bitmap of the call before is cleared
+            _, got = gpu_level(rt, ctx, "vgx_raster_concave", *dp_, p.target)   # no contour mesh: the bitmap of the call before is cleared
             assert np.array_equal(got, P.expected("classes"))
-            _, got = G.gpu_raster(rt, ctx, G.dev_frame(r), r.target)
+            _, got = gpu_level(rt, ctx, "raster", DevFrame(r), tgt=r.target)
             assert np.array_equal(got, R.expected("lattice"))
     finally:
         ctx.close()
 
 
-def big_frame():
-    """`crowd` magnified four times: every mesh reaches several tiles, more bin entries than a fresh context's first guess holds."""
-    f = K.frame("crowd")
-    g = R.make("crowd_x4", (f.pos - np.float32(16.0)) * np.float32(4.0), f.color, f.idx, f.meshes, R.Target(64, 64, 64, 0, 0))
-    g.draws, g.dstate, g.uv, g.images, g.gradients, g.patterns = f.draws, f.dstate, f.uv, f.images, f.gradients, f.patterns
-    return g
-
-
 def test_fresh_context_grows_then_succeeds_and_scratch_is_counted(rt):
-    f = big_frame()
+    f = H.big_frame(K.frame("crowd"))
     tgt = f.target.with_clear(CLEAR)
-    want = cpu.host_level(cpu.load_host(), "vgxt_raster_concave", f, tgt)   # the lane code, which equals the model on the shared frames
+    want = H.host_level(H.load_host(), "concave", f, tgt)   # the lane code, which equals the model on the shared frames
     assert int((want != tgt.background()).sum()) > 3000
-    parts = GC.dev_parts(f)
-    ctx = rt.Context(0)
-    try:
-        img, got = GC.gpu_level(rt, ctx, "vgx_raster_concave", *parts, tgt, want=capi.VGX_E_GROWN)
-        assert np.array_equal(got, tgt.background())   # nothing written, the clear included
-        _, got = GC.gpu_level(rt, ctx, "vgx_raster_concave", *parts, tgt, image=img)
-        assert np.array_equal(got, want), G.where(got, want)
-    finally:
-        ctx.close()
-    ctx = rt.Context(0)
-    try:
-        rt.raster_reserve(ctx, f.nm, 1 << 15)
-        GC.gpu_level(rt, ctx, "vgx_raster_painted", *parts, tgt)   # everything vgx_raster_painted allocates
-        before = int(rt.lib().vgx_scratch_bytes(ctx.handle))
-        _, got = GC.gpu_level(rt, ctx, "vgx_raster_concave", *parts, tgt)
-        assert np.array_equal(got, want)
-        assert int(rt.lib().vgx_scratch_bytes(ctx.handle)) - before >= 4   # one word of tile bits for 4 x 4 tiles
-    finally:
-        ctx.close()
+    parts = dev_parts(f)
+    painted = lambda ctx, tgt: gpu_level(rt, ctx, "painted", *parts, tgt)   # everything vgx_raster_painted allocates
+    H.check_fresh_context_grows_then_succeeds(rt, lambda ctx, tgt, **kw: gpu_level(rt, ctx, "concave", *parts, tgt, **kw), f, lambda tgt: want, 1 << 15,
+                                              prepare=painted, min_growth=4)   # one word of tile bits for 4 x 4 tiles
 
 
 def test_counted_state_survives(rt, gpu_ctx, wl, oracle):
     """vgx_tessellate_count -> vgx_raster_concave of another stream -> vgx_tessellate_emit gives the meshes it gives without the call."""
     import torch
     f = K.frame("state")
-    parts = GC.dev_parts(f)
+    parts = dev_parts(f)
     ps, d = wl.tiger(2)
     ref = oracle.tessellate(ps, d)
     pset = rt.PathSet(gpu_ctx, ps)

@@ -9,16 +9,10 @@ import numpy as np
 import pytest
 
 import raster_model as R
+from hashutil import fnv1a
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def fnv1a(words):
-    h = 1469598103934665603
-    for b in np.ascontiguousarray(words, dtype="<u4").reshape(-1).view(np.uint8).tolist():
-        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return h
 
 
 def test_cpp_raster_example_runs(tmp_path):

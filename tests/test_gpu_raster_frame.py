@@ -4,57 +4,18 @@ the frame level) against the numpy statement
 where the new state must change nothing or amounts to a scissor. Every comparison is np.array_equal on the whole uint32 buffer: the
 stride padding and everything outside the scissor included."""
 import ctypes as C
-import importlib
 
 import numpy as np
 import pytest
 
 import raster_frame_model as M
+import raster_harness as H
 import raster_model as R
-import test_gpu_raster as G
-import test_raster_frame_cpu as cpu
+from raster_harness import DevFrame, DevState, dev_frame, gpu_bounds, rt, warm_ctx, where  # noqa: F401 (rt, warm_ctx: fixtures)
 
 pytestmark = pytest.mark.gpu
 capi = R.capi
 CLEAR = 0xFF102030
-
-
-@pytest.fixture(scope="module")
-def rt():
-    return importlib.import_module("vg-renderer_amd.runtime")
-
-
-@pytest.fixture(scope="module")
-def warm_ctx(rt):
-    ctx = rt.Context(0)
-    rt.raster_reserve(ctx, 8192, 1 << 17)
-    yield ctx
-    ctx.close()
-
-
-class DevState:
-    """The draw table of a frame in device memory."""
-
-    def __init__(self, f):
-        self.t = [G.to_dev(f.draws), G.to_dev(f.dstate)]
-        nd = f.draws.shape[0]
-        self.struct = capi.RasterDraws(self.t[0].data_ptr() if nd else None, self.t[1].data_ptr() if nd else None, nd, 0)
-
-
-def gpu_frame(rt, ctx, df, ds, tgt, image=None, bounds=None, begin=0, end=2**64 - 1, want=capi.VGX_OK):
-    """One vgx_raster_frame call over the target's background (or `image`, a device tensor, changed in place), synchronised; returns
-    (image tensor, image as uint32 [rows, stride])."""
-    import torch
-    if image is None:
-        image = torch.from_numpy(tgt.background().view(np.int32)).to("cuda:0")
-    status = torch.full((3,), 77, dtype=torch.int32, device="cuda:0")
-    t = tgt.struct(image.data_ptr())
-    st = rt.lib().vgx_raster_frame(ctx.handle, C.byref(df.desc), None if bounds is None else bounds.data_ptr(), begin, end, C.byref(ds.struct), C.byref(t),
-                                   status.data_ptr(), rt._stream_ptr())
-    torch.cuda.synchronize()
-    assert st == capi.VGX_OK
-    assert status.cpu().tolist() == [want, 77, 77]
-    return image, image.cpu().numpy().view(np.uint32)
 
 
 @pytest.mark.parametrize("clear", [False, True])
@@ -62,15 +23,15 @@ def gpu_frame(rt, ctx, df, ds, tgt, image=None, bounds=None, begin=0, end=2**64 
 def test_kernels_equal_model(rt, warm_ctx, name, clear):
     M.check_conditions(name)
     f = M.frame(name)
-    df, ds = G.DevFrame(f), DevState(f)
+    df, ds = DevFrame(f), DevState(f)
     tgt = f.target.with_clear(CLEAR) if clear else f.target
     want = M.expected(name, clear)
-    _, own = gpu_frame(rt, warm_ctx, df, ds, tgt)
-    assert np.array_equal(own, want), G.where(own, want)
+    _, own = H.gpu_level(rt, warm_ctx, "frame", df, ds, tgt=tgt)
+    assert np.array_equal(own, want), where(own, want)
     assert R.guards_intact(tgt, own)
-    _, given = gpu_frame(rt, warm_ctx, df, ds, tgt, bounds=G.gpu_bounds(rt, warm_ctx, df))
-    assert np.array_equal(given, want), G.where(given, want)
-    _, again = gpu_frame(rt, warm_ctx, df, ds, tgt)
+    _, given = H.gpu_level(rt, warm_ctx, "frame", df, ds, tgt=tgt, bounds=gpu_bounds(rt, warm_ctx, df))
+    assert np.array_equal(given, want), where(given, want)
+    _, again = H.gpu_level(rt, warm_ctx, "frame", df, ds, tgt=tgt)
     assert np.array_equal(again, own)  # two runs, the same bytes
     assert df.unchanged()
 
@@ -96,8 +57,8 @@ def test_decoded_frame_after_gpu_tessellation(rt, warm_ctx):
     for clear in (False, True):
         tgt = f.target.with_clear(CLEAR) if clear else f.target
         want = M.expected("decoded", clear, rt)
-        _, got = gpu_frame(rt, warm_ctx, Dev, ds, tgt)
-        assert np.array_equal(got, want), G.where(got, want)
+        _, got = H.gpu_level(rt, warm_ctx, "frame", Dev, ds, tgt=tgt)
+        assert np.array_equal(got, want), where(got, want)
         assert R.guards_intact(tgt, got)
     # the runtime wrapper, on an image of its own
     img, status = rt.raster_frame(warm_ctx, Dev.desc, ds.t[0], ds.t[1], f.draws.shape[0], f.target.width, f.target.height, clear_color=CLEAR)
@@ -110,13 +71,13 @@ def test_decoded_frame_after_gpu_tessellation(rt, warm_ctx):
 def test_unused_state_equals_vgx_raster(rt, warm_ctx):
     """(a) every draw's scissor the whole canvas, no regions: vgx_raster's bytes."""
     f = R.frame("tiger")
-    g = cpu.whole(f)
-    df, ds = G.dev_frame(f), DevState(g)
-    dg = G.DevFrame(g)  # the same streams, every mesh a draw of its own
-    for tgt in (cpu.tiger_window(), cpu.tiger_window().with_clear(CLEAR)):
-        _, got = gpu_frame(rt, warm_ctx, dg, ds, tgt)
-        _, want = G.gpu_raster(rt, warm_ctx, df, tgt)
-        assert np.array_equal(got, want), G.where(got, want)
+    g = H.whole(f)
+    df, ds = dev_frame(f), DevState(g)
+    dg = DevFrame(g)  # the same streams, every mesh a draw of its own
+    for tgt in (H.tiger_window(), H.tiger_window().with_clear(CLEAR)):
+        _, got = H.gpu_level(rt, warm_ctx, "frame", dg, ds, tgt=tgt)
+        _, want = H.gpu_level(rt, warm_ctx, "raster", df, tgt=tgt)
+        assert np.array_equal(got, want), where(got, want)
         assert R.guards_intact(tgt, got) and int((got != tgt.background()).sum()) > 10000
 
 
@@ -126,14 +87,14 @@ def test_three_scissors_equal_three_calls(rt, warm_ctx):
     tgt = f.target
     cuts = [(0, 0, 70, 130), (37, 21, 100, 50), (90, 3, 200, 200)]
     a, b = f.nm // 3, 2 * f.nm // 3
-    g = cpu.whole(f, [cuts[0] if m < a else (cuts[1] if m < b else cuts[2]) for m in range(f.nm)])
-    df = G.dev_frame(f)
-    _, got = gpu_frame(rt, warm_ctx, G.DevFrame(g), DevState(g), tgt)
+    g = H.whole(f, [cuts[0] if m < a else (cuts[1] if m < b else cuts[2]) for m in range(f.nm)])
+    df = dev_frame(f)
+    _, got = H.gpu_level(rt, warm_ctx, "frame", DevFrame(g), DevState(g), tgt=tgt)
     img, want = None, None
     for (lo, hi), c in zip(((0, a), (a, b), (b, f.nm)), cuts):
         sc = M.draw_rect(tgt, c)
-        img, want = G.gpu_raster(rt, warm_ctx, df, R.Target(tgt.width, tgt.height, tgt.stride, tgt.x0, tgt.y0, sc), image=img, begin=lo, end=hi)
-    assert np.array_equal(got, want), G.where(got, want)
+        img, want = H.gpu_level(rt, warm_ctx, "raster", df, tgt=R.Target(tgt.width, tgt.height, tgt.stride, tgt.x0, tgt.y0, sc), image=img, begin=lo, end=hi)
+    assert np.array_equal(got, want), where(got, want)
     assert not np.array_equal(got, R.expected("tiger")) and not np.array_equal(got, tgt.background())
 
 
@@ -142,29 +103,29 @@ def test_region_of_a_rectangle(rt, warm_ctx, rule):
     """(c) an In region made of one axis-aligned quad with integer corners is vgx_raster under the scissor of that rectangle; (d) as an
     Out region it leaves the unclipped render outside the rectangle and the background inside."""
     f = R.frame("tiger")
-    tgt = cpu.tiger_window()
+    tgt = H.tiger_window()
     rect = (20, 10, 110, 90)
-    g = cpu.clipped_tiger(rule, rect)
-    _, got = gpu_frame(rt, warm_ctx, G.DevFrame(g), DevState(g), tgt)
+    g = H.clipped_tiger(rule, rect)
+    _, got = H.gpu_level(rt, warm_ctx, "frame", DevFrame(g), DevState(g), tgt=tgt)
     x0, y0, x1, y1 = M.draw_rect(tgt, rect)
-    _, plain = G.gpu_raster(rt, warm_ctx, G.dev_frame(f), tgt)
+    _, plain = H.gpu_level(rt, warm_ctx, "raster", dev_frame(f), tgt=tgt)
     if rule == 0:
-        _, want = G.gpu_raster(rt, warm_ctx, G.dev_frame(f), R.Target(tgt.width, tgt.height, tgt.stride, tgt.x0, tgt.y0, (x0, y0, x1, y1)))
+        _, want = H.gpu_level(rt, warm_ctx, "raster", dev_frame(f), tgt=R.Target(tgt.width, tgt.height, tgt.stride, tgt.x0, tgt.y0, (x0, y0, x1, y1)))
     else:
         want = plain.copy()
         want[y0:y1, x0:x1] = tgt.background()[y0:y1, x0:x1]
-    assert np.array_equal(got, want), G.where(got, want)
+    assert np.array_equal(got, want), where(got, want)
     assert not np.array_equal(got, plain) and not np.array_equal(got, tgt.background())
 
 
 def test_mesh_range_that_does_not_start_at_0(rt, warm_ctx):
     f = M.frame("clips")
-    df, ds = G.DevFrame(f), DevState(f)
+    df, ds = DevFrame(f), DevState(f)
     want = M.render(f, f.target, f.target.background(), mesh_begin=2, mesh_end=7)
-    _, got = gpu_frame(rt, warm_ctx, df, ds, f.target, begin=2, end=7)
-    assert np.array_equal(got, want), G.where(got, want)
+    _, got = H.gpu_level(rt, warm_ctx, "frame", df, ds, tgt=f.target, begin=2, end=7)
+    assert np.array_equal(got, want), where(got, want)
     tc = f.target.with_clear(0x01020304)
-    _, got = gpu_frame(rt, warm_ctx, df, ds, tc, begin=3, end=3)  # an empty range: only the clear
+    _, got = H.gpu_level(rt, warm_ctx, "frame", df, ds, tgt=tc, begin=3, end=3)  # an empty range: only the clear
     sx0, sy0, sx1, sy1 = tc.scissor
     assert np.all(got[sy0:sy1, sx0:sx1] == 0x01020304) and R.guards_intact(tc, got)
 
@@ -173,55 +134,39 @@ def test_fresh_context_grows_then_succeeds(rt):
     """A fresh context holds one bin entry per mesh: the first call ends with VGX_E_GROWN and has written NOTHING, the clear included;
     the repeat succeeds. After vgx_raster_reserve one call is enough. vgx_scratch_bytes counts the per-mesh state of this call."""
     t = R.frame("tiger")  # moved so that its own window starts at frame pixel (0, 0): no draw scissor cuts it, its meshes reach several tiles each
-    f = R.make("tiger_moved", t.pos + np.array([-t.target.x0, -t.target.y0], dtype=np.float32), t.color, t.idx, t.meshes, cpu.tiger_window())
-    g = cpu.whole(f)
-    df, dg, ds = G.DevFrame(f), G.DevFrame(g), DevState(g)
+    f = R.make("tiger_moved", t.pos + np.array([-t.target.x0, -t.target.y0], dtype=np.float32), t.color, t.idx, t.meshes, H.tiger_window())
+    g = H.whole(f)
+    df, dg, ds = DevFrame(f), DevFrame(g), DevState(g)
     tgt = f.target.with_clear(CLEAR)
     entries = R.bin_entries(f, tgt)
-    assert entries > 2 * f.nm + 64, (entries, f.nm)  # condition on the input: the first guess cannot hold them
     ctx = rt.Context(0)
     try:
-        _, want = G.gpu_raster(rt, ctx, df, tgt, want=capi.VGX_E_GROWN)
+        _, want = H.gpu_level(rt, ctx, "raster", df, tgt=tgt, want=capi.VGX_E_GROWN)
         assert np.array_equal(want, tgt.background())
-        _, want = G.gpu_raster(rt, ctx, df, tgt)
+        _, want = H.gpu_level(rt, ctx, "raster", df, tgt=tgt)
     finally:
         ctx.close()
-    ctx = rt.Context(0)
-    try:
-        img, got = gpu_frame(rt, ctx, dg, ds, tgt, want=capi.VGX_E_GROWN)
-        assert np.array_equal(got, tgt.background())
-        _, got = gpu_frame(rt, ctx, dg, ds, tgt, image=img)
-        assert np.array_equal(got, want), G.where(got, want)
-    finally:
-        ctx.close()
-    ctx = rt.Context(0)
-    try:
-        rt.raster_reserve(ctx, f.nm, entries)
-        reserved = int(rt.lib().vgx_scratch_bytes(ctx.handle))
-        _, got = gpu_frame(rt, ctx, dg, ds, tgt)
-        assert np.array_equal(got, want)
-        assert int(rt.lib().vgx_scratch_bytes(ctx.handle)) - reserved >= 32 * f.nm  # the buffer only this call allocates
-    finally:
-        ctx.close()
+    H.check_fresh_context_grows_then_succeeds(rt, lambda ctx, tgt, **kw: H.gpu_level(rt, ctx, "frame", dg, ds, tgt=tgt, **kw), f, lambda tgt: want, entries,
+                                              min_growth=32 * f.nm)  # the buffer only this call allocates
 
 
 def test_invalid_draw_index_writes_nothing(rt, warm_ctx):
     f = M.clips()
     f.meshes["draw"][8] = f.draws.shape[0]
-    df, ds = G.DevFrame(f), DevState(f)
+    df, ds = DevFrame(f), DevState(f)
     for tgt in (f.target, f.target.with_clear(CLEAR)):
-        _, got = gpu_frame(rt, warm_ctx, df, ds, tgt, want=capi.VGX_E_INVALID_ARG)
+        _, got = H.gpu_level(rt, warm_ctx, "frame", df, ds, tgt=tgt, want=capi.VGX_E_INVALID_ARG)
         assert np.array_equal(got, tgt.background())
-    _, got = gpu_frame(rt, warm_ctx, df, ds, f.target, end=8)  # a range without the mesh is drawn
+    _, got = H.gpu_level(rt, warm_ctx, "frame", df, ds, tgt=f.target, end=8)  # a range without the mesh is drawn
     assert np.array_equal(got, M.render(M.frame("clips"), f.target, f.target.background(), mesh_end=8))
     # it ranks above VGX_E_GROWN: a fresh context, more entries than it holds, and the bad index
     t = R.frame("tiger")
-    g = cpu.whole(t)
+    g = H.whole(t)
     g.meshes["draw"][t.nm // 2] = t.nm
     ctx = rt.Context(0)
     try:
-        tgt = cpu.tiger_window().with_clear(CLEAR)
-        _, got = gpu_frame(rt, ctx, G.DevFrame(g), DevState(g), tgt, want=capi.VGX_E_INVALID_ARG)
+        tgt = H.tiger_window().with_clear(CLEAR)
+        _, got = H.gpu_level(rt, ctx, "frame", DevFrame(g), DevState(g), tgt=tgt, want=capi.VGX_E_INVALID_ARG)
         assert np.array_equal(got, tgt.background())
     finally:
         ctx.close()
@@ -230,7 +175,7 @@ def test_invalid_draw_index_writes_nothing(rt, warm_ctx):
 def test_refused_calls(rt, warm_ctx):
     import torch
     f = M.frame("lattice_clip")
-    df, ds = G.DevFrame(f), DevState(f)
+    df, ds = DevFrame(f), DevState(f)
     t = f.target
     image = torch.from_numpy(t.background().view(np.int32)).to("cuda:0")
     lib = rt.lib()
@@ -255,32 +200,10 @@ def test_refused_calls(rt, warm_ctx):
 
 def test_counted_state_survives(rt, gpu_ctx, wl, oracle):
     """vgx_tessellate_count -> vgx_raster_frame of another stream -> vgx_tessellate_emit gives the meshes it gives without the call."""
-    import torch
     f = M.frame("stack_clip")
-    df, ds = G.DevFrame(f), DevState(f)
-    ps, d = wl.tiger(3)
-    ref = oracle.tessellate(ps, d)
-    pset = rt.PathSet(gpu_ctx, ps)
-    dd = rt.upload_draws(d)
-    sizes = rt.tessellate_count(gpu_ctx, pset, dd, d.shape[0])
-    img = None
-    for _ in range(2):  # the first call of this context may end with VGX_E_GROWN; either way the counted state must survive
-        img, status = rt.raster_frame(gpu_ctx, df.desc, ds.t[0], ds.t[1], f.draws.shape[0], f.target.width, f.target.height, clear_color=CLEAR)
-        torch.cuda.synchronize()
-    assert int(status.item()) == capi.VGX_OK
-    bufs = rt.MeshBuffers(dd.device, sizes["num_vertices"], sizes["num_indices"], sizes["num_meshes"])
-    rt.tessellate_emit(gpu_ctx, pset, dd, d.shape[0], bufs)
-    torch.cuda.synchronize()
-    pset.close()
-    nv, ni, nm = ref.sizes["num_vertices"], ref.sizes["num_indices"], ref.sizes["num_meshes"]
-    assert (sizes["num_vertices"], sizes["num_indices"], sizes["num_meshes"]) == (nv, ni, nm)
-    assert np.array_equal(bufs.pos[:nv].cpu().numpy().view(np.uint32), ref.pos.view(np.uint32))
-    assert np.array_equal(bufs.color[:nv].cpu().numpy().view(np.uint32), ref.color)
-    assert np.array_equal(bufs.idx[:ni].cpu().numpy().view(np.uint16), ref.idx)
-    gm = bufs.meshes[:nm * 32].cpu().numpy().view(capi.mesh_dtype)
-    for name in ref.meshes.dtype.names:
-        assert np.array_equal(gm[name], ref.meshes[name]), name
-    assert np.array_equal(img.cpu().numpy().view(np.uint32), M.expected("stack_clip", True))
+    df, ds = DevFrame(f), DevState(f)
+    call = lambda: rt.raster_frame(gpu_ctx, df.desc, ds.t[0], ds.t[1], f.draws.shape[0], f.target.width, f.target.height, clear_color=CLEAR)
+    H.check_counted_state_survives(rt, gpu_ctx, wl, oracle, call, M.expected("stack_clip", True))
 
 
 def test_vgx_raster_after_vgx_raster_frame(rt):
@@ -290,12 +213,12 @@ def test_vgx_raster_after_vgx_raster_frame(rt):
     try:
         rt.raster_reserve(ctx, 8192, 1 << 17)
         c = M.frame("clips")
-        dc, sc = G.DevFrame(c), DevState(c)
+        dc, sc = DevFrame(c), DevState(c)
         for name in ("lattice", "stack", "tiger"):
-            _, got = gpu_frame(rt, ctx, dc, sc, c.target)
+            _, got = H.gpu_level(rt, ctx, "frame", dc, sc, tgt=c.target)
             assert np.array_equal(got, M.expected("clips"))
             f = R.frame(name)
-            _, got = G.gpu_raster(rt, ctx, G.dev_frame(f), f.target)
-            assert np.array_equal(got, R.expected(name)), (name, G.where(got, R.expected(name)))
+            _, got = H.gpu_level(rt, ctx, "raster", dev_frame(f), tgt=f.target)
+            assert np.array_equal(got, R.expected(name)), (name, where(got, R.expected(name)))
     finally:
         ctx.close()

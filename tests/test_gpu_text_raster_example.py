@@ -12,7 +12,7 @@ import pytest
 
 import raster_model as R
 import raster_textured_model as T
-from test_gpu_raster_example import fnv1a
+from hashutil import fnv1a
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -10,64 +10,15 @@ import numpy as np
 import pytest
 
 import pick_frame_model as PF
-import pick_model as PM
+import raster_harness as H
 import raster_model as R
-import test_pick_cpu as pcpu
-import test_raster_concave_cpu as ccpu
-import test_raster_cpu as rcpu
-import test_raster_frame_cpu as fcpu
+from raster_harness import draws_struct, first_difference, host, host_pick_frame, relation_b_queries, same  # noqa: F401 (host: fixture)
 
 capi = PF.capi
 F = np.float32
 D = np.float64
 NONE = PF.NONE
-GUARD = 0x5A5A5A5A
-ALL = 2**64 - 1
-
-
-@pytest.fixture(scope="module")
-def host():
-    lib = ccpu.load_host()
-    if not hasattr(lib, "vgxt_pick_frame"):  # a library from before this call: build again
-        import __graft_entry__ as g
-        g.build()
-        lib = ccpu.load_host()
-    lib.vgxt_pick_frame.restype = C.c_int
-    lib.vgxt_pick_frame.argtypes = [C.POINTER(capi.CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(capi.RasterDraws), C.c_void_p, C.c_uint32,
-                                    C.c_void_p, C.c_void_p]
-    lib.vgxt_pick.restype = C.c_int
-    lib.vgxt_pick.argtypes = [C.POINTER(capi.CacheDesc), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    lib.vgxt_mesh_bounds.restype = None
-    lib.vgxt_mesh_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-    return lib
-
-
-def host_pick_frame(host, f, queries, with_bounds=False, begin=0, end=ALL, want=capi.VGX_OK, guard=2, meshes=None, draws=None):
-    """vgxt_pick_frame in calls of at most 256 queries, each into a pattern-filled array whose records behind nqueries must stay."""
-    meshes = f.meshes if meshes is None else meshes
-    d = capi.CacheDesc(f.pos.ctypes.data, f.color.ctypes.data, f.idx.ctypes.data, meshes.ctypes.data, meshes.shape[0], f.nv, f.ni)
-    s = fcpu.draws_struct(f) if draws is None else draws
-    mb = rcpu.host_bounds(host, f) if with_bounds else None
-    out = np.zeros(queries.shape[0], dtype=capi.pick_hit_dtype)
-    for a, b in PF.chunks(queries.shape[0]) or [(0, 0)]:
-        q = np.ascontiguousarray(queries[a:b])
-        h = np.full((b - a + guard) * 4, GUARD, dtype=np.uint32)
-        status = np.full(1, 77, dtype=np.uint32)
-        assert host.vgxt_pick_frame(C.byref(d), None if mb is None else mb.ctypes.data, begin, end, C.byref(s), q.ctypes.data if b > a else None, b - a,
-                                    h.ctypes.data, status.ctypes.data) == capi.VGX_OK
-        assert status[0] == want
-        assert np.all(h[(b - a) * 4:] == GUARD)
-        out[a:b] = h[:(b - a) * 4].view(capi.pick_hit_dtype)
-    return out
-
-
-def same(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def first_difference(got, want, queries):
-    bad = np.nonzero((got.view(np.uint32).reshape(-1, 4) != want.view(np.uint32).reshape(-1, 4)).any(axis=1))[0]
-    return [(int(q), tuple(queries[q]), tuple(got[q]), tuple(want[q])) for q in bad[:5]], bad.size
+ALL = H.OPEN
 
 
 @pytest.mark.parametrize("key", PF.ALL, ids=lambda k: "-".join(str(v) for v in k))
@@ -101,7 +52,7 @@ def test_cover_many_is_raster_models_cover():
 
 def raster_ids(host, f, skip_transparent=False):
     g, tgt = PF.id_frame(f, skip_transparent)
-    return PF.decode_ids(ccpu.host_level(host, "vgxt_raster_concave", g, tgt), tgt)
+    return PF.decode_ids(H.host_level(host, "concave", g, tgt), tgt)
 
 
 @pytest.mark.parametrize("flags", [0, PF.SKIP])
@@ -118,32 +69,10 @@ def test_relation_a_the_image_is_the_oracle(host, key, flags):
         assert not np.array_equal(raster_ids(host, f), ids)
 
 
-# the seed of relation (b)'s random points: the MODEL alone, run on the CPU with this seed, stays within the cap (a random binary32 point
-# lies on the line of an edge with probability ~0). The cap is asserted all the same, on the model's output, before any product answer
-RELATION_B_SEED = 1
-RELATION_B_POINTS = 1500
-
-
-def relation_b_queries():
-    f = PF.frame(PF.TIGER)
-    x0, y0, x1, y1 = PF.frame_box(f)
-    rs = np.random.RandomState(RELATION_B_SEED)
-    q = np.zeros(RELATION_B_POINTS, dtype=capi.pick_query_dtype)
-    # inside the frame's box and inside the scissor of the all-PLAIN state: frame pixels 0 .. 65534
-    q["x"] = rs.uniform(max(x0, 0.0), min(x1, 65534.0), RELATION_B_POINTS).astype(F)
-    q["y"] = rs.uniform(max(y0, 0.0), min(y1, 65534.0), RELATION_B_POINTS).astype(F)
-    q["mesh_end"] = NONE
-    q["flags"][1::2] = PF.SKIP
-    a = PF.pick(f, q, prep=PF._prepare_cached(PF.TIGER))
-    keep = ~a.zero
-    assert int((~keep).sum()) * 100 <= RELATION_B_POINTS, int((~keep).sum())   # the cap: at most 1 % left out
-    return f, q[keep], a.hits[keep]
-
-
 def test_relation_b_equals_vgx_pick_away_from_edges(host):
     f, q, want = relation_b_queries()
     got = host_pick_frame(host, f, q)
-    old = pcpu.host_pick(host, f.pos, f.color, f.idx, f.meshes, q)
+    old = H.host_pick(host, f, q)
     assert same(got, want)
     assert same(got, old), first_difference(got, old, q)
     assert int((got["mesh"] != NONE).sum()) > 100 and int((got["mesh"] == NONE).sum()) > 100
@@ -186,7 +115,7 @@ def test_range_that_begins_behind_a_regions_clip_meshes(host):
     assert not same(whole.hits, want.hits)
     # the image of the same range says the same
     g, tgt = PF.id_frame(f)
-    ids = PF.decode_ids(ccpu.host_level(host, "vgxt_raster_concave", g, tgt, begin=begin), tgt)
+    ids = PF.decode_ids(H.host_level(host, "concave", g, tgt, begin=begin), tgt)
     assert np.array_equal(np.where(got["mesh"] == NONE, -1, got["mesh"].astype(np.int64)).reshape(ids.shape), ids)
     # a mesh_end inside the table ends the range
     assert same(host_pick_frame(host, f, q, begin=0, end=4), PF.pick(f, q, mesh_end=4, prep=PF._prepare_cached(key)).hits)
@@ -209,7 +138,7 @@ def test_mesh_with_a_draw_beyond_the_table(host):
 
 def test_host_return_values(host):
     f = PF.frame(("frame", "clips"))
-    d, s = f.desc(), fcpu.draws_struct(f)
+    d, s = f.desc(), draws_struct(f)
     q = np.zeros(257, dtype=capi.pick_query_dtype)
     h = np.zeros(257, dtype=capi.pick_hit_dtype)
     st = np.zeros(2, dtype=np.uint32)
@@ -293,7 +222,7 @@ def test_coverage_has_the_exact_sign():
         even_odd = int(f.meshes["subpath_kind"][m]) & capi.CONTOUR_EVEN_ODD
         W = PF.K.winding(u, v, q["x"].astype(D), q["y"].astype(D))
         for k in range(q.shape[0]):
-            exact = ccpu.exact_winding(u, v, float(q["x"][k]), float(q["y"][k]))
+            exact = H.exact_winding(u, v, float(q["x"][k]), float(q["y"][k]))
             assert int(W[k]) == exact, (m, k)
             inside[k] |= bool(exact & 1) if even_odd else exact != 0
         on_edge += sum(1 for p in u if (np.abs(q["x"] - p[0]) + np.abs(q["y"] - p[1]) == 0).any())

@@ -3,62 +3,18 @@ and the pixels of each triangle's box) against the numpy statement of the specif
 predicate against exact rational arithmetic. Exact everywhere: np.array_equal on the uint32 images, the stride padding and everything
 outside the scissor included. The GPU suite (tests/test_gpu_raster.py) makes the same comparison on the kernels."""
 import ctypes as C
-import os
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import raster_harness as H
 import raster_model as R
+from raster_harness import host  # noqa: F401 (fixture)
 
 capi = R.capi
 F = np.float32
 D = np.float64
-
-
-def load_host():
-    path = os.path.join(R.CM.ROOT, "vg-renderer_amd", "libvgx_hosttest.so")
-    if not os.path.exists(path):
-        import __graft_entry__ as g
-        g.build()
-    lib = C.CDLL(path)
-    lib.vgxt_raster.restype = C.c_int
-    lib.vgxt_raster.argtypes = [C.POINTER(capi.CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(capi.RasterTarget), C.c_void_p]
-    lib.vgxt_mesh_bounds.restype = None
-    lib.vgxt_mesh_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.vgxt_raster_edge.restype = C.c_double
-    lib.vgxt_raster_edge.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int)]
-    lib.vgxt_raster_cover.restype = C.c_int
-    lib.vgxt_raster_cover.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double]
-    return lib
-
-
-@pytest.fixture(scope="module")
-def host():
-    return load_host()
-
-
-def host_bounds(host, f):
-    mb = np.zeros((max(f.nm, 1), 4), dtype=F)
-    host.vgxt_mesh_bounds(f.pos.ctypes.data, f.meshes.ctypes.data, f.nm, mb.ctypes.data)
-    return mb
-
-
-def host_render(host, f, tgt, image=None, with_bounds=False, begin=0, end=2**64 - 1):
-    """vgxt_raster over the target's background (or `image`, changed in place); returns the image."""
-    img = tgt.background() if image is None else image
-    mb = host_bounds(host, f) if with_bounds else None
-    d = f.desc()
-    t = tgt.struct(img.ctypes.data)
-    status = np.full(1, 77, dtype=np.uint32)
-    assert host.vgxt_raster(C.byref(d), None if mb is None else mb.ctypes.data, begin, end, C.byref(t), status.ctypes.data) == capi.VGX_OK
-    assert status[0] == capi.VGX_OK
-    return img
-
-
-def where(a, b):
-    j, i = np.nonzero(a != b)
-    return [(int(x), int(y), hex(int(a[y, x])), hex(int(b[y, x]))) for y, x in list(zip(j, i))[:6]]
 
 
 @pytest.mark.parametrize("clear", [False, True])
@@ -68,12 +24,12 @@ def test_lane_code_equals_model(host, name, clear):
     f = R.frame(name)
     tgt = f.target.with_clear(0xFF102030) if clear else f.target
     want = R.expected(name, clear)
-    got = host_render(host, f, tgt)
-    assert np.array_equal(got, want), where(got, want)
+    got = H.host_level(host, "raster", f, tgt)
+    assert np.array_equal(got, want), H.where(got, want)
     assert R.guards_intact(tgt, got)
     assert not np.array_equal(got, tgt.background())
     # with the boxes handed in instead of computed by the call: the same bytes
-    assert np.array_equal(host_render(host, f, tgt, with_bounds=True), got)
+    assert np.array_equal(H.host_level(host, "raster", f, tgt, with_bounds=True), got)
 
 
 @pytest.mark.parametrize("name", R.NAMES)
@@ -82,19 +38,19 @@ def test_split_mesh_ranges(host, name):
     f = R.frame(name)
     want = R.expected(name)
     for k in sorted({0, 1, f.nm // 2, f.nm - 1, f.nm}):
-        img = host_render(host, f, f.target, end=k)
-        host_render(host, f, f.target, image=img, begin=k)
+        img = H.host_level(host, "raster", f, f.target, end=k)
+        H.host_level(host, "raster", f, f.target, image=img, begin=k)
         assert np.array_equal(img, want), k
     if f.nm <= 300:
         img = f.target.background()
         for m in range(f.nm):
-            host_render(host, f, f.target, image=img, begin=m, end=m + 1, with_bounds=bool(m % 2))
+            H.host_level(host, "raster", f, f.target, image=img, begin=m, end=m + 1, with_bounds=bool(m % 2))
         assert np.array_equal(img, want)
     # an empty range writes nothing, or only the clear
-    img = host_render(host, f, f.target, begin=f.nm)
+    img = H.host_level(host, "raster", f, f.target, begin=f.nm)
     assert np.array_equal(img, f.target.background())
     tc = f.target.with_clear(0x01020304)
-    img = host_render(host, f, tc, begin=3, end=3)
+    img = H.host_level(host, "raster", f, tc, begin=3, end=3)
     sx0, sy0, sx1, sy1 = tc.scissor
     assert np.all(img[sy0:sy1, sx0:sx1] == 0x01020304) and R.guards_intact(tc, img)
 

@@ -4,68 +4,19 @@ not rest on that model: a blit computed here from div255, vgxt_raster_frame on w
 a sampled mesh. Exact everywhere: np.array_equal on the uint32 images, the stride padding and everything outside the scissor
 included. tests/test_gpu_raster_textured.py makes the same comparisons on the kernels."""
 import ctypes as C
-import importlib
 
 import numpy as np
 import pytest
 
 import raster_frame_model as M
+import raster_harness as H
 import raster_model as R
 import raster_textured_model as T
-import test_raster_cpu as base
-import test_raster_frame_cpu as fcpu
+from raster_harness import div255, draws_struct, host, image_records, rt  # noqa: F401 (host, rt: fixtures)
 
 capi = R.capi
 CLEAR = T.CLEAR
 ALL = T.NAMES + ("decoded",)
-
-
-def load_host():
-    lib = fcpu.load_host()
-    if not hasattr(lib, "vgxt_raster_textured"):  # a library from before this call: build again
-        import __graft_entry__ as g
-        g.build()
-        lib = fcpu.load_host()
-    lib.vgxt_raster_textured.restype = C.c_int
-    lib.vgxt_raster_textured.argtypes = [C.POINTER(capi.CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(capi.RasterDraws),
-                                         C.POINTER(capi.RasterTextures), C.POINTER(capi.RasterTarget), C.c_void_p]
-    return lib
-
-
-@pytest.fixture(scope="module")
-def host():
-    return load_host()
-
-
-@pytest.fixture(scope="module")
-def rt():
-    return importlib.import_module("vg-renderer_amd.runtime")
-
-
-def image_records(images, ptr=lambda im: im.pixels.ctypes.data):
-    """The vgx_raster_image records of a list of model images (None: a record of zeros)."""
-    rec = np.zeros(max(len(images), 1), dtype=capi.raster_image_dtype)
-    for k, im in enumerate(images):
-        if im is not None:
-            rec[k] = (ptr(im), im.width, im.height, im.stride, im.flags)
-    return rec
-
-
-def host_textured(host, f, tgt, image=None, images=None, with_bounds=False, begin=0, end=2**64 - 1, want=capi.VGX_OK, records=None, uv=None):
-    """vgxt_raster_textured over the target's background (or `image`, changed in place); returns the image. images / records / uv:
-    instead of the frame's."""
-    img = tgt.background() if image is None else image
-    images = f.images if images is None else images
-    uv = f.uv if uv is None else uv
-    rec = image_records(images) if records is None else records
-    mb = base.host_bounds(host, f) if with_bounds else None
-    d, s, t = f.desc(), fcpu.draws_struct(f), tgt.struct(img.ctypes.data)
-    x = capi.RasterTextures(uv.ctypes.data, rec.ctypes.data if len(images) else None, 8 if uv.dtype == np.float32 else 4, len(images))
-    status = np.full(1, 77, dtype=np.uint32)
-    assert host.vgxt_raster_textured(C.byref(d), None if mb is None else mb.ctypes.data, begin, end, C.byref(s), C.byref(x), C.byref(t),
-                                     status.ctypes.data) == capi.VGX_OK
-    assert status[0] == want
-    return img
 
 
 @pytest.mark.parametrize("clear", [False, True])
@@ -75,14 +26,10 @@ def test_lane_code_equals_model(host, rt, name, clear):
     f = T.frame(name, rt)
     tgt = f.target.with_clear(CLEAR) if clear else f.target
     want = T.expected(name, clear, rt)
-    got = host_textured(host, f, tgt)
-    assert np.array_equal(got, want), base.where(got, want)
+    got = H.host_level(host, "textured", f, tgt)
+    assert np.array_equal(got, want), H.where(got, want)
     assert R.guards_intact(tgt, got)
-    assert np.array_equal(host_textured(host, f, tgt, with_bounds=True), got)  # the boxes handed in: the same bytes
-
-
-def div255(x):
-    return (x + 127) // 255
+    assert np.array_equal(H.host_level(host, "textured", f, tgt, with_bounds=True), got)  # the boxes handed in: the same bytes
 
 
 @pytest.mark.parametrize("name", ["blit_nearest", "blit_linear"])
@@ -101,8 +48,8 @@ def test_blit_is_the_clear_blended_with_the_texels(host, name):
             if a:
                 ch = [div255(((s >> (8 * k)) & 255) * a + ((CLEAR >> (8 * k)) & 255) * (255 - a)) for k in range(3)]
                 want[2 + y, 3 + x] = ch[0] | (ch[1] << 8) | (ch[2] << 16) | (div255(255 * a + (CLEAR >> 24) * (255 - a)) << 24)
-    got = host_textured(host, f, tgt)
-    assert np.array_equal(got, want), base.where(got, want)
+    got = H.host_level(host, "textured", f, tgt)
+    assert np.array_equal(got, want), H.where(got, want)
     assert int((got[:, :tgt.width] != CLEAR).sum()) >= 10
 
 
@@ -113,9 +60,9 @@ def test_white_images_give_vertex_colours(host, rt, name):
     f = T.frame(name, rt)
     g = T.as_fill(f)
     for tgt in (f.target, f.target.with_clear(CLEAR)):
-        got = host_textured(host, f, tgt, images=[im.white() for im in f.images])
-        want = fcpu.host_frame(host, g, tgt)
-        assert np.array_equal(got, want), base.where(got, want)
+        got = H.host_level(host, "textured", f, tgt, images=[im.white() for im in f.images])
+        want = H.host_level(host, "frame", g, tgt)
+        assert np.array_equal(got, want), H.where(got, want)
         assert not np.array_equal(got, T.expected(name, tgt.clear is not None, rt))  # the texels did show
 
 
@@ -128,8 +75,8 @@ def test_no_sampled_mesh_equals_vgxt_raster_frame(host, rt, name):
     assert not ((kinds == R.TEXT) | (kinds == R.TRILIST)).any()
     uv = np.full((max(f.nv, 1), 2), np.nan, dtype=np.float32)
     for tgt in (f.target, f.target.with_clear(CLEAR)):
-        got = host_textured(host, f, tgt, images=[], uv=uv)
-        assert np.array_equal(got, fcpu.host_frame(host, f, tgt))
+        got = H.host_level(host, "textured", f, tgt, images=[], uv=uv)
+        assert np.array_equal(got, H.host_level(host, "frame", f, tgt))
         assert np.array_equal(got, M.expected(name, tgt.clear is not None, rt))
 
 
@@ -150,22 +97,22 @@ def test_invalid_image_writes_nothing(host):
         bad_recs.append(rec)
     for tgt in (f.target, f.target.with_clear(CLEAR)):
         for rec in bad_recs:
-            got = host_textured(host, f, tgt, records=rec, want=capi.VGX_E_INVALID_ARG)
+            got = H.host_level(host, "textured", f, tgt, records=rec, want=capi.VGX_E_INVALID_ARG)
             assert np.array_equal(got, tgt.background())
-        got = host_textured(host, f, tgt, images=f.images[:1], want=capi.VGX_E_INVALID_ARG)  # handle 1 with one image
+        got = H.host_level(host, "textured", f, tgt, images=f.images[:1], want=capi.VGX_E_INVALID_ARG)  # handle 1 with one image
         assert np.array_equal(got, tgt.background())
         assert T.status(f, images=f.images[:1]) == capi.VGX_E_INVALID_ARG
     # the same bad image named only by meshes that are not sampled: mesh 6 (a paint draw) alone names image 1 once mesh 1's clip draw
     # and mesh 4 are left out of the range
     rec = image_records(f.images)
     rec["width"][1] = 0
-    got = host_textured(host, f, f.target, records=rec, begin=5)
+    got = H.host_level(host, "textured", f, f.target, records=rec, begin=5)
     assert np.array_equal(got, T.render(f, f.target, f.target.background(), mesh_begin=5))
     assert not np.array_equal(got, f.target.background()) and not np.array_equal(got, good)
     # ... and by a path-kind mesh of a type-0 draw: the backdrop's draw, pointed at a handle outside the table
     g = T.state_frame()
     g.draws["state_key"][0] |= 0xFFFF
-    assert np.array_equal(host_textured(host, g, g.target), good)
+    assert np.array_equal(H.host_level(host, "textured", g, g.target), good)
 
 
 def test_non_finite_and_huge_uvs_leave_the_pixel(host):
@@ -180,9 +127,9 @@ def test_non_finite_and_huge_uvs_leave_the_pixel(host):
                    (np.inf, 0), (1, 0), (1, 1), (0, 1)], dtype=np.float32)
     im = T.Image(T.texels(4, 4, 4, 9, [255]), 4, T.NEAREST)
     f = T.finish(fr, [0, 0, 0], [0], [M.state()], [0], uv, [im])
-    got = host_textured(host, f, f.target)
+    got = H.host_level(host, "textured", f, f.target)
     want = T.render(f, f.target, f.target.background())
-    assert np.array_equal(got, want), base.where(got, want)
+    assert np.array_equal(got, want), H.where(got, want)
     ch = got != f.target.background()
     assert ch[2:12, 2:7].all() and not ch[2:12, 7:12].any()                          # U = x' / 10 * 2^32 reaches 2^31 at the middle
     assert ch[2:12, 14:24].sum() > 20 and (~ch[2:12, 14:24]).sum() > 20               # the triangle without the NaN vertex is drawn
@@ -192,16 +139,16 @@ def test_non_finite_and_huge_uvs_leave_the_pixel(host):
 def test_mesh_range_and_split_calls(host):
     """Two calls over two halves of `crowd` give the bytes of one call (no stamp is in use there), and the range is the model's."""
     f = T.frame("crowd")
-    img = host_textured(host, f, f.target, end=150)
+    img = H.host_level(host, "textured", f, f.target, end=150)
     assert np.array_equal(img, T.render(f, f.target, f.target.background(), mesh_end=150))
-    img = host_textured(host, f, f.target, image=img, begin=150)
+    img = H.host_level(host, "textured", f, f.target, image=img, begin=150)
     assert np.array_equal(img, T.expected("crowd"))
 
 
 def test_host_argument_checks(host):
     f = T.frame("state")
     img = f.target.background()
-    d, s = f.desc(), fcpu.draws_struct(f)
+    d, s = f.desc(), draws_struct(f)
     rec = image_records(f.images)
     bad = capi.VGX_E_INVALID_ARG
 

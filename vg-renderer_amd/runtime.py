@@ -658,17 +658,45 @@ def cache_cull(ctx, cache, bounds_dev, inst_dev, ninst, views_dev, inst_view_dev
     return r
 
 
+# ---- what the frame consumers (vgx_pick*, vgx_raster*, vgx_damage_*) build alike -----------------------------------------
+def _desc(frame):
+    """A capi.CacheDesc of device pointers, or anything with .desc() (a MeshCache)."""
+    return frame if isinstance(frame, capi.CacheDesc) else frame.desc()
+
+
+def _ptr(t, used=True):
+    """The device pointer of a tensor; None for None and for a table of no entries."""
+    return t.data_ptr() if used and t is not None else None
+
+
+def _mesh_end(mesh_end):
+    """The end of a mesh range; None = open, every mesh from mesh_begin on."""
+    return 0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end)
+
+
+def _hits(hits_dev, nqueries, device):
+    import torch
+    return torch.empty(max(int(nqueries), 1) * 16, dtype=torch.uint8, device=device) if hits_dev is None else hits_dev
+
+
+def _raster_draws(draws_dev, draw_state_dev, num_draws):
+    return capi.RasterDraws(_ptr(draws_dev, num_draws), _ptr(draw_state_dev, num_draws), int(num_draws), 0)
+
+
+def _raster_target(pixels, width, height, stride, x0, y0, scissor=None, clear_color=None):
+    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
+    return capi.RasterTarget(pixels, int(width), int(height), int(stride), int(x0), int(y0), (C.c_uint32 * 4)(*sc),
+                             capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
+
+
 # ---- hit testing (vgx_pick) ---------------------------------------------------------------------------------------------
 def pick(ctx, frame, queries_dev, nqueries, bounds_dev=None, hits_dev=None):
     """frame: a capi.CacheDesc of device pointers, or anything with .desc() (a MeshCache); queries_dev: uint8 device tensor of 16-byte
     vgx_pick_query records; bounds_dev: what mesh_bounds gave for the frame, or None (the call computes the boxes itself). Returns a
     uint8 device tensor of nqueries 16-byte vgx_pick_hit records (hits_dev when given). Asynchronous."""
-    import torch
-    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
-    if hits_dev is None:
-        hits_dev = torch.empty(max(int(nqueries), 1) * 16, dtype=torch.uint8, device=queries_dev.device)
-    _check(lib().vgx_pick(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, queries_dev.data_ptr(), nqueries,
-                          hits_dev.data_ptr(), _stream_ptr()), "vgx_pick")
+    d = _desc(frame)
+    hits_dev = _hits(hits_dev, nqueries, queries_dev.device)
+    _check(lib().vgx_pick(ctx.handle, C.byref(d), _ptr(bounds_dev), queries_dev.data_ptr(), nqueries, hits_dev.data_ptr(), _stream_ptr()), "vgx_pick")
     return hits_dev
 
 
@@ -681,19 +709,46 @@ def pick_frame(ctx, frame, draws_dev, draw_state_dev, num_draws, queries_dev, nq
     Returns (hits, dev_status): a uint8 device tensor of nqueries 16-byte vgx_pick_hit records (hits_dev when given) and an int32 [1]
     tensor that holds VGX_OK, or VGX_E_INVALID_ARG when a mesh names a draw >= num_draws (every hit is "none" then). Asynchronous."""
     import torch
-    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
-    if hits_dev is None:
-        hits_dev = torch.empty(max(int(nqueries), 1) * 16, dtype=torch.uint8, device=queries_dev.device)
+    d = _desc(frame)
+    hits_dev = _hits(hits_dev, nqueries, queries_dev.device)
     if dev_status is None:
         dev_status = torch.empty(1, dtype=torch.int32, device=hits_dev.device)
-    st = capi.RasterDraws(draws_dev.data_ptr() if num_draws else None, draw_state_dev.data_ptr() if num_draws else None, int(num_draws), 0)
-    _check(lib().vgx_pick_frame(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
-                                0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), queries_dev.data_ptr() if nqueries else None, int(nqueries),
-                                hits_dev.data_ptr(), dev_status.data_ptr(), _stream_ptr()), "vgx_pick_frame")
+    st = _raster_draws(draws_dev, draw_state_dev, num_draws)
+    _check(lib().vgx_pick_frame(ctx.handle, C.byref(d), _ptr(bounds_dev), int(mesh_begin), _mesh_end(mesh_end), C.byref(st), _ptr(queries_dev, nqueries),
+                                int(nqueries), hits_dev.data_ptr(), dev_status.data_ptr(), _stream_ptr()), "vgx_pick_frame")
     return hits_dev, dev_status
 
 
 # ---- rendering to an image (vgx_raster) -----------------------------------------------------------------------------------
+def _raster(entry, ctx, frame, width, height, x0, y0, scissor, clear_color, bounds_dev, mesh_begin, mesh_end, image, dev_status, draws=None, textures=None,
+            paints=None, damage=None):
+    """The body of every raster call: `entry` of libvgx.so on the target and, in the order of the entry's parameters, the structs of the
+    tables it takes -- draws (draws_dev, draw_state_dev, num_draws), textures (uv_dev, uv_bytes, images_dev, num_images), paints
+    (gradients_dev, num_gradients, patterns_dev, num_patterns), damage (tile_bits, max_entries); None = not a parameter of that entry.
+    Allocates the image and the status word nobody handed in. Returns (image, dev_status)."""
+    import torch
+    d = _desc(frame)
+    if image is None:
+        image = torch.zeros((max(int(height), 1), max(int(width), 1)), dtype=torch.int32, device="cuda:%d" % ctx.device)[:height, :width]
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
+    structs = []
+    if draws is not None:
+        structs.append(_raster_draws(*draws))
+    if textures is not None:
+        uv_dev, uv_bytes, images_dev, num_images = textures
+        structs.append(capi.RasterTextures(_ptr(uv_dev), _ptr(images_dev, num_images), int(uv_bytes), int(num_images)))
+    if paints is not None:
+        gradients_dev, num_gradients, patterns_dev, num_patterns = paints
+        structs.append(capi.RasterPaints(_ptr(gradients_dev, num_gradients), _ptr(patterns_dev, num_patterns), int(num_gradients), int(num_patterns)))
+    structs.append(_raster_target(image.data_ptr(), width, height, image.stride(0) if image.dim() == 2 and height else width, x0, y0, scissor, clear_color))
+    if damage is not None:
+        structs.append(capi.RasterDamage(damage[0].data_ptr(), int(damage[1]), 0))
+    _check(getattr(lib(), entry)(ctx.handle, C.byref(d), _ptr(bounds_dev), int(mesh_begin), _mesh_end(mesh_end), *[C.byref(s) for s in structs],
+                                 dev_status.data_ptr(), _stream_ptr()), entry)
+    return image, dev_status
+
+
 def raster(ctx, frame, width, height, x0=0, y0=0, scissor=None, clear_color=None, bounds_dev=None, mesh_begin=0, mesh_end=None, image=None,
            dev_status=None):
     """Draws the meshes [mesh_begin, mesh_end) of `frame` (a capi.CacheDesc of device pointers, or anything with .desc()) into an RGBA8
@@ -702,18 +757,7 @@ def raster(ctx, frame, width, height, x0=0, y0=0, scissor=None, clear_color=None
     one); bounds_dev: what mesh_bounds gave for the frame, or None. image: an int32 [height, stride] device tensor to draw into
     (stride = its row length). Returns (image, dev_status): the int32 tensor whose words are 0xAABBGGRR and an int32 [1] tensor that
     holds VGX_OK, VGX_E_GROWN (call again) or VGX_E_RANGE once the work is done. Asynchronous."""
-    import torch
-    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
-    if image is None:
-        image = torch.zeros((max(int(height), 1), max(int(width), 1)), dtype=torch.int32, device="cuda:%d" % ctx.device)[:height, :width]
-    if dev_status is None:
-        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
-    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
-    t = capi.RasterTarget(image.data_ptr(), int(width), int(height), int(image.stride(0)) if image.dim() == 2 and height else int(width), int(x0), int(y0),
-                          (C.c_uint32 * 4)(*sc), capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
-    _check(lib().vgx_raster(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
-                            0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(t), dev_status.data_ptr(), _stream_ptr()), "vgx_raster")
-    return image, dev_status
+    return _raster("vgx_raster", ctx, frame, width, height, x0, y0, scissor, clear_color, bounds_dev, mesh_begin, mesh_end, image, dev_status)
 
 
 def raster_frame(ctx, frame, draws_dev, draw_state_dev, num_draws, width, height, x0=0, y0=0, scissor=None, clear_color=None, bounds_dev=None,
@@ -723,20 +767,8 @@ def raster_frame(ctx, frame, draws_dev, draw_state_dev, num_draws, width, height
     clip draws stamp their region, the other draws are tested against the region they name (vgx_raster_frame in include/vgx.h). The
     mesh range must hold the clip meshes of every region it uses. dev_status may also come out as VGX_E_INVALID_ARG: a mesh names a
     draw >= num_draws, nothing was written. Returns (image, dev_status) as raster() does. Asynchronous."""
-    import torch
-    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
-    if image is None:
-        image = torch.zeros((max(int(height), 1), max(int(width), 1)), dtype=torch.int32, device="cuda:%d" % ctx.device)[:height, :width]
-    if dev_status is None:
-        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
-    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
-    t = capi.RasterTarget(image.data_ptr(), int(width), int(height), int(image.stride(0)) if image.dim() == 2 and height else int(width), int(x0), int(y0),
-                          (C.c_uint32 * 4)(*sc), capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
-    st = capi.RasterDraws(draws_dev.data_ptr() if num_draws else None, draw_state_dev.data_ptr() if num_draws else None, int(num_draws), 0)
-    _check(lib().vgx_raster_frame(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
-                                  0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), C.byref(t), dev_status.data_ptr(), _stream_ptr()),
-           "vgx_raster_frame")
-    return image, dev_status
+    return _raster("vgx_raster_frame", ctx, frame, width, height, x0, y0, scissor, clear_color, bounds_dev, mesh_begin, mesh_end, image, dev_status,
+                   draws=(draws_dev, draw_state_dev, num_draws))
 
 
 def raster_images(images, device):
@@ -758,21 +790,8 @@ def raster_textured(ctx, frame, draws_dev, draw_state_dev, num_draws, uv_dev, uv
     of uv_bytes (4: int16 x 2, 8: float x 2) per vertex of the frame, read only at the vertices of sampled meshes
     (vgx_raster_textured in include/vgx.h). dev_status may also come out as VGX_E_INVALID_ARG for a sampled mesh whose handle or
     image record is no good: nothing was written. Returns (image, dev_status) as raster() does. Asynchronous."""
-    import torch
-    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
-    if image is None:
-        image = torch.zeros((max(int(height), 1), max(int(width), 1)), dtype=torch.int32, device="cuda:%d" % ctx.device)[:height, :width]
-    if dev_status is None:
-        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
-    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
-    t = capi.RasterTarget(image.data_ptr(), int(width), int(height), int(image.stride(0)) if image.dim() == 2 and height else int(width), int(x0), int(y0),
-                          (C.c_uint32 * 4)(*sc), capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
-    st = capi.RasterDraws(draws_dev.data_ptr() if num_draws else None, draw_state_dev.data_ptr() if num_draws else None, int(num_draws), 0)
-    tx = capi.RasterTextures(uv_dev.data_ptr() if uv_dev is not None else None, images_dev.data_ptr() if num_images else None, int(uv_bytes), int(num_images))
-    _check(lib().vgx_raster_textured(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
-                                     0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), C.byref(tx), C.byref(t), dev_status.data_ptr(),
-                                     _stream_ptr()), "vgx_raster_textured")
-    return image, dev_status
+    return _raster("vgx_raster_textured", ctx, frame, width, height, x0, y0, scissor, clear_color, bounds_dev, mesh_begin, mesh_end, image, dev_status,
+                   draws=(draws_dev, draw_state_dev, num_draws), textures=(uv_dev, uv_bytes, images_dev, num_images))
 
 
 def paint_tables(paints, num_gradients=None, num_patterns=None):
@@ -799,23 +818,9 @@ def raster_painted(ctx, frame, draws_dev, draw_state_dev, num_draws, uv_dev, uv_
     device tensors; a pattern's .image indexes images_dev) by the fragment rule of vgx_raster_painted in include/vgx.h. dev_status may
     also come out as VGX_E_INVALID_ARG for a painted mesh whose handle, table entry or image is no good: nothing was written.
     Returns (image, dev_status) as raster() does. Asynchronous."""
-    import torch
-    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
-    if image is None:
-        image = torch.zeros((max(int(height), 1), max(int(width), 1)), dtype=torch.int32, device="cuda:%d" % ctx.device)[:height, :width]
-    if dev_status is None:
-        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
-    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
-    t = capi.RasterTarget(image.data_ptr(), int(width), int(height), int(image.stride(0)) if image.dim() == 2 and height else int(width), int(x0), int(y0),
-                          (C.c_uint32 * 4)(*sc), capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
-    st = capi.RasterDraws(draws_dev.data_ptr() if num_draws else None, draw_state_dev.data_ptr() if num_draws else None, int(num_draws), 0)
-    tx = capi.RasterTextures(uv_dev.data_ptr() if uv_dev is not None else None, images_dev.data_ptr() if num_images else None, int(uv_bytes), int(num_images))
-    pt = capi.RasterPaints(gradients_dev.data_ptr() if num_gradients else None, patterns_dev.data_ptr() if num_patterns else None, int(num_gradients),
-                           int(num_patterns))
-    _check(getattr(lib(), _entry)(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
-                                  0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), C.byref(tx), C.byref(pt), C.byref(t),
-                                  dev_status.data_ptr(), _stream_ptr()), _entry)
-    return image, dev_status
+    return _raster(_entry, ctx, frame, width, height, x0, y0, scissor, clear_color, bounds_dev, mesh_begin, mesh_end, image, dev_status,
+                   draws=(draws_dev, draw_state_dev, num_draws), textures=(uv_dev, uv_bytes, images_dev, num_images),
+                   paints=(gradients_dev, num_gradients, patterns_dev, num_patterns))
 
 
 def raster_concave(*args, **kwargs):
@@ -870,7 +875,7 @@ def damage_words(width, height):
 
 
 def _damage_target(width, height, x0, y0):
-    return capi.RasterTarget(None, int(width), int(height), int(width), int(x0), int(y0), (C.c_uint32 * 4)(0, 0, int(width), int(height)), 0, 0)
+    return _raster_target(None, width, height, width, x0, y0)
 
 
 def damage_meshes(ctx, bounds_dev, num_meshes, width, height, tile_bits, x0=0, y0=0, mesh_begin=0, mesh_end=None):
@@ -878,9 +883,8 @@ def damage_meshes(ctx, bounds_dev, num_meshes, width, height, tile_bits, x0=0, y
     [mesh_begin, mesh_end) of bounds_dev (float32 [num_meshes, 4], what mesh_bounds() gave) reach in the image raster_damaged() will
     draw: same width, height, x0, y0. Returns tile_bits. Asynchronous."""
     t = _damage_target(width, height, x0, y0)
-    _check(lib().vgx_damage_meshes(ctx.handle, bounds_dev.data_ptr() if num_meshes else None, int(mesh_begin),
-                                   0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), int(num_meshes), C.byref(t), tile_bits.data_ptr(), _stream_ptr()),
-           "vgx_damage_meshes")
+    _check(lib().vgx_damage_meshes(ctx.handle, _ptr(bounds_dev, num_meshes), int(mesh_begin), _mesh_end(mesh_end), int(num_meshes), C.byref(t),
+                                   tile_bits.data_ptr(), _stream_ptr()), "vgx_damage_meshes")
     return tile_bits
 
 
@@ -894,9 +898,8 @@ def damage_instances(ctx, bounds_dev, num_meshes, slots_dev, ninst, dirty_dev, n
     if dev_status is None:
         dev_status = torch.empty(1, dtype=torch.int32, device=tile_bits.device)
     t = _damage_target(width, height, x0, y0)
-    _check(lib().vgx_damage_instances(ctx.handle, bounds_dev.data_ptr() if num_meshes else None, int(num_meshes), slots_dev.data_ptr(), int(ninst),
-                                      dirty_dev.data_ptr() if ndirty else None, int(ndirty), dev_ndirty.data_ptr() if dev_ndirty is not None else None,
-                                      C.byref(t), tile_bits.data_ptr(), dev_status.data_ptr(), _stream_ptr()), "vgx_damage_instances")
+    _check(lib().vgx_damage_instances(ctx.handle, _ptr(bounds_dev, num_meshes), int(num_meshes), slots_dev.data_ptr(), int(ninst), _ptr(dirty_dev, ndirty),
+                                      int(ndirty), _ptr(dev_ndirty), C.byref(t), tile_bits.data_ptr(), dev_status.data_ptr(), _stream_ptr()), "vgx_damage_instances")
     return dev_status
 
 
@@ -908,22 +911,9 @@ def raster_damaged(ctx, frame, draws_dev, draw_state_dev, num_draws, uv_dev, uv_
     equals a full raster_concave() of the edited frame (vgx_raster_damaged in include/vgx.h). max_entries: the bin entries the call sorts
     at most, 0 = what the last damaged call on this context needed. dev_status may come out as VGX_E_GROWN: call again. Returns
     (image, dev_status). Asynchronous."""
-    import torch
-    d = frame if isinstance(frame, capi.CacheDesc) else frame.desc()
-    if dev_status is None:
-        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
-    sc = (0, 0, int(width), int(height)) if scissor is None else tuple(int(v) for v in scissor)
-    t = capi.RasterTarget(image.data_ptr(), int(width), int(height), int(image.stride(0)) if image.dim() == 2 and height else int(width), int(x0), int(y0),
-                          (C.c_uint32 * 4)(*sc), capi.RASTER_CLEAR if clear_color is not None else 0, int(clear_color or 0))
-    st = capi.RasterDraws(draws_dev.data_ptr() if num_draws else None, draw_state_dev.data_ptr() if num_draws else None, int(num_draws), 0)
-    tx = capi.RasterTextures(uv_dev.data_ptr() if uv_dev is not None else None, images_dev.data_ptr() if num_images else None, int(uv_bytes), int(num_images))
-    pt = capi.RasterPaints(gradients_dev.data_ptr() if num_gradients else None, patterns_dev.data_ptr() if num_patterns else None, int(num_gradients),
-                           int(num_patterns))
-    dm = capi.RasterDamage(tile_bits.data_ptr(), int(max_entries), 0)
-    _check(lib().vgx_raster_damaged(ctx.handle, C.byref(d), bounds_dev.data_ptr() if bounds_dev is not None else None, int(mesh_begin),
-                                    0xFFFFFFFFFFFFFFFF if mesh_end is None else int(mesh_end), C.byref(st), C.byref(tx), C.byref(pt), C.byref(t), C.byref(dm),
-                                    dev_status.data_ptr(), _stream_ptr()), "vgx_raster_damaged")
-    return image, dev_status
+    return _raster("vgx_raster_damaged", ctx, frame, width, height, x0, y0, scissor, clear_color, bounds_dev, mesh_begin, mesh_end, image, dev_status,
+                   draws=(draws_dev, draw_state_dev, num_draws), textures=(uv_dev, uv_bytes, images_dev, num_images),
+                   paints=(gradients_dev, num_gradients, patterns_dev, num_patterns), damage=(tile_bits, max_entries))
 
 
 # ---- concave fills (vgx_concave_move / vgx_concave_emit): libtess2 stays with the caller -----------------------------
