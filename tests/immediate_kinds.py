@@ -50,8 +50,8 @@ MIN_INSTANCES, SMALL_DRAWS = 32, 2048  # VGX_INST_MIN_INSTANCES, VGX_SMALL_DRAWS
 
 
 def route_from_knowledge(ndraws, period, distinct, long_curves):
-    """The route block of vgx_tessellate_immediate for a batch of `ndraws` draws whose tag is known, from the mirrored knowledge:
-    periodUsable -> pathsReused -> long curves (vertices >= 10 x command instances) -> k_flatten_build."""
+    """The route of vgx_tessellate_immediate (vgx_route_choose, csrc/vgx_route_plan.h) for a batch of `ndraws` draws whose tag is known, from
+    the mirrored knowledge: period usable -> paths reused -> long curves (vertices >= 10 x command instances) -> k_flatten_build."""
     if ndraws <= SMALL_DRAWS:
         return "route_frame"
     if period and ndraws % period == 0 and ndraws // period >= MIN_INSTANCES:

@@ -2,10 +2,10 @@
 property that steers the route of vgx_tessellate_immediate. When one of these fails, the GPU sequences no longer test what they say.
 
 The three host rules the kinds are built around, written down here on purpose (nothing is imported from the product):
-  * periodUsable (vgx_api.hip): a period P is used when ndraws % P == 0 and ndraws / P >= 32 (VGX_INST_MIN_INSTANCES);
-  * pathsReused (vgx_api.hip): grouped mode when ndraws / distinct paths >= 32;
-  * the one-walk route of vgx_tessellate_immediate: polyline vertices >= 10 x command instances; its kernel shape, f1Shape
-    (vgx_api.hip): 64 x vertices / command instances <= 800 -> the 1024-entry leaf list, > 1500 -> the 3072-entry one.
+  * vgx_period_usable (vgx_route_plan.h): a period P is used when ndraws % P == 0 and ndraws / P >= 32 (VGX_INST_MIN_INSTANCES);
+  * vgx_paths_reused (vgx_route_plan.h): grouped mode when ndraws / distinct paths >= 32;
+  * the one-walk route of vgx_tessellate_immediate: polyline vertices >= 10 x command instances; its kernel shape, vgx_f1_shape
+    (vgx_route_plan.h): 64 x vertices / command instances <= 800 -> the 1024-entry leaf list, > 1500 -> the 3072-entry one.
 Batches of at most 2 048 draws (VGX_SMALL_DRAWS) take the frame-sized route whatever they hold."""
 import numpy as np
 import pytest

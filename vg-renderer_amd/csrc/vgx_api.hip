@@ -1,11 +1,10 @@
 // vgx_api.hip -- implementation of the C-ABI declared in include/vgx.h.
 //
-// Host side of the batch geometry path: context (device scratch, grow-only), path-set validation and
-// upload, the four device-wide scans and the launch sequence
-//   cmd-prefix scan -> flatten<count> -> draw scan -> flatten<emit> -> element-prefix scan
-//   -> stroke<count> -> mesh scan -> stroke<emit>
-// All lengths that are results of earlier kernels stay in device memory (VgxTotals); the asynchronous
-// entry point vgx_tessellate never synchronises with the host.
+// The host side of every entry point: the context (grow-only device scratch, options, what the last count chose), the scan operators
+// and three small kernels of no stage, and per entry the argument checks, the scratch sizing and the launch sequence over the kernels
+// of the other .hip files. Lengths that are results of earlier kernels stay in device memory (VgxTotals); the asynchronous entries never
+// synchronise with the host. In order: pipeline pieces (run*), context and path set, flatten, partition, template mode, tessellate with
+// immediate mode (rules: vgx_route_plan.h), stroker level, dashes, shape cache, culling, picking, raster, damage, updates, concave fills, text, gather.
 #include "vgx_internal.h"
 #include "vgx_scan.h"
 #include "vgx_scan_ops.h"
@@ -23,6 +22,7 @@
 #include "vgx_pick.h"
 #include "vgx_concave_lane.h"
 #include "vgx_scratch.h"
+#include "vgx_route_plan.h"
 #include <vector>
 #include <algorithm>
 #include <atomic>
@@ -30,7 +30,6 @@
 #include <math.h>
 #include <new>
 #include <stdlib.h>
-
 
 #define VGX_GRID_BLOCKS 32768 // one-wave workgroups, each owning a contiguous run of segments (>> resident waves: no tail)
 
@@ -111,6 +110,25 @@ static_assert(sizeof(VgxTmplWg) == sizeof(uint2) && offsetof(VgxTmplWg, inst) ==
 static_assert(sizeof(VgxTmplClass) == 40 && offsetof(VgxTmplClass, round) == 32 && sizeof(VgxTmplClass().round) == 8, "VgxTmplClass: the named words lie where the padding did");
 static_assert(sizeof(VgxTmplMesh) == 64 && offsetof(VgxTmplMesh, fringe_bits) == 56 && offsetof(VgxTmplMesh, round_no) == 60, "VgxTmplMesh: the named words lie where the padding did");
 
+// The ordinary pipeline's state between calls. `chosen`: what the last count (or the immediate call under way) chose; the rest: what the tables hold
+struct VgxRouteState
+{
+	VgxRoute chosen;
+	const vgx_pathset* f1Ps; uint64_t f1PsGen;               // one-walk: the path set the look-back tables were sized for
+	uint64_t instPaths, instKeys, instTasks, instDraws;      // grouped mode: what the sort buffers hold (ensureInstGroup)
+	uint64_t capDraws;                                       // draws the per-draw buffers hold (ensureDrawBuffers)
+	bool tileHint;                                           // the last ordinary vgx_tessellate_count saw fills and closed Miter AA / Thin strokes only (the tile kernel's batches)
+};
+// state of the last *_count call (what _emit continues from)
+enum VgxCountedStage { VGX_COUNTED_NONE = 0, VGX_COUNTED_FLATTEN, VGX_COUNTED_TESSELLATE, VGX_COUNTED_STROKE };
+struct VgxCounted { const vgx_pathset* ps; const vgx_draw* draws; uint64_t ndraws /* (the stroker-level count: vertex lists) */; VgxCountedStage stage; };
+// vgx_tessellate_immediate: pinned mirror of the last call's totals (read only once its copy has landed), the batch it belongs to (tag, draw
+// count, was the detection pass run), and what the host learned from the last mirror it read: the batch and, in `facts`, its sizes, period, paths
+struct VgxImmState
+{
+	HostMirror<VgxTotals> mirror; uint64_t pendTag, pendNDraws; bool pendDetect, known; uint64_t tag; VgxRouteFacts facts;
+};
+
 struct vgx_ctx
 {
 	int device;
@@ -163,7 +181,6 @@ struct vgx_ctx
 	// vgx_damage_instances (vgx_damage.hip): the flag word (in 16 bytes) and the mesh prefix of the listed entries, the scan's slice sums
 	// (views: as `partial`). Its own: a counted state, and a vgx_cache_update in flight, survive the call
 	DevBuf dmgPrefix, dmgPartial;
-	uint32_t optPickGrid;               // workgroups of k_pick_tris (VGX_PICK_GRID)
 	// vgx_dash (vgx_dash.hip): per-draw patterns, per-list records, per-segment prefix sums (S and the overflow guard), per-range sums; the
 	// segment count of the last call in pinned memory (copied behind the call, read by the next call once its event has passed: a call
 	// whose lists outgrew dashG ends with VGX_E_GROWN and the next one grows first, as vgx_tessellate_immediate does)
@@ -179,17 +196,12 @@ struct vgx_ctx
 	uint64_t pieceVerts;
 	HostMirror<unsigned long long> df;
 	Buf<VgxTileRec> tileTab;             // k_emit_tiles (vgx_tile.hip): the tile table of the current call
-	bool tileHint;                       // the last ordinary vgx_tessellate_count saw fills and closed Miter AA / Thin strokes only (the tile kernel's batches)
-	uint64_t optBigEmitMin;              // vertex capacity from which a call launches the tile kernel / k_stroke_long (2^18; VGX_BIG_EMIT_MIN: testing knob, 0 = every call)
-	int optTileEmit;                     // VGX_TILE_EMIT=0: ordinary batches through k_fill + k_stroke_simple as before round 6
 	DevBuf psTemp;                       // vgx_pathset_create: temporaries of the device-side build (vgx_pathset.hip); views: VgxPsTotals, uint32_t words, VgxPsM and Sum3 slice sums at byte offsets
 	hipStream_t psStream;                // ... its stream (created at the first call)
 	struct VgxPsTotals* hostPs;          // ... pinned: what the build reports
 	void* psImage; size_t psImageCap;    // ... pinned: the raw part of a frame-sized set, assembled here and uploaded in one copy
 	DevBuf psPool[VGX_PS_POOL];          // ... blobs of dropped frame-sized sets, recycled (hipFree synchronises). Not scratch: never grown, not on the list
-	int optPsNoSmall;                    // VGX_PS_NO_SMALL: frame-sized path sets through the large-set launch sequence
 	Buf<uint64_t> f1SegDraw; Buf<VgxF1Seg> f1Segs; // vgx_flatten (vgx_flat1.hip): segment table, look-back records
-	int optF1Waves, optF1Cap, optF1Seg;  // its grid (persistent one-wave workgroups), the leaf-list capacity of the kernel instance and the segment bucket (0 = chosen per batch)
 	// what the last vgx_flatten call produced (copied to pinned memory behind the call, read by the next call WITHOUT waiting for
 	// it): polyline vertices per command instance decide how many commands a segment may hold before its leaves overflow the list
 	unsigned long long* hostF1;          // pinned: [0] vertices, [1] command instances, [2] tag of the batch they belong to
@@ -197,53 +209,20 @@ struct vgx_ctx
 	Buf<VgxGatherWire> gatherSizes;      // vgx_gather_sizes: one record per rank
 	DevBuf partBounds;                   // vgx_partition; views: uint64_t [nparts + 1] bounds, behind them [nparts] weights
 	struct VgxRccl* rccl;                // RCCL entry points, bound at the first vgx_gather* call
-	// options, read from the environment ONCE at vgx_create (tuning / testing knobs)
-	int optBuildWaves, optNoSmall;
-	int optTessFlat1;                    // VGX_TESS_FLAT1: 1 (default) = vgx_tessellate flattens batches of long curves with the one-walk kernel (k_flat1), 0 = never, 2 = every eligible batch
-	// vgx_tessellate's one-walk route, decided and sized by the last vgx_tessellate_count (f1Route*): the path set it is for, the kernel
-	// instance / bucket size, the segments the look-back tables hold
-	bool f1Route; const vgx_pathset* f1RoutePs; uint64_t f1RoutePsGen; int f1RouteCap; uint32_t f1RouteSegMax; uint64_t f1RouteSegBound;
-	int optThinStatic;                   // VGX_THIN_STATIC=0: lineTo-only path sets through k_flatten_build like any other (default: k_flatten_thin, vgx_thin.h)
-	int optInst, optInstWaves; uint32_t optInstBlock; // instanced flatten kernel (vgx_inst.hip): on / grid / lane block
-	int optInstPerm;                                  // periodic batches of different scales: permute instances (1, default) or sort draws by (path, class) (0)
-	uint32_t optInstClasses;                          // grouped mode: tolerance classes per path when the instances differ in scale (VGX_INST_CLASSES)
-	// instanced batches: period of the path sequence found by the last vgx_tessellate_count (0 = none). vgx_tessellate
-	// re-checks it on the device for the draws it is given.
-	uint32_t instPeriod;
-	// ... or, when the draws reuse paths without repeating one sequence (at least 32 draws per used path on average): 1 =
-	// grouped mode, every vgx_tessellate sorts the draws by path first (k_inst_hist / k_inst_plan / k_inst_scatter)
-	int instGrouped;
-	// grouped mode, instances of different scales: the sort key is (path, tolerance class) with this many classes per path
-	// (1 = by path only), so that the lanes of a wave flatten with nearly the same tolerance and stay in lock-step
-	uint32_t instClasses;
+	VgxOptions opt;                      // read from the environment ONCE at vgx_create (vgx_route_plan.h)
+	VgxRouteState route;                 // the ordinary pipeline's flatten route and what its tables hold
+	// instanced batches (vgx_inst.hip), grouped mode: every vgx_tessellate sorts the draws by path first (k_inst_hist / k_inst_plan / k_inst_scatter)
 	Buf<uint32_t> instHist, instCursor, instTaskPath, instOrder; Buf<uint64_t> instKeyStart, instStart, instTaskStart;
-	// periodic mode, instances of different scales: every vgx_tessellate sorts the INSTANCES by tolerance class (vgx_launch_inst_perm)
-	int instPermOn;
-	Buf<uint32_t> instPerm, instPermHist;
-	uint64_t instCapPaths, instCapKeys, instCapTasks, instCapDraws;
+	Buf<uint32_t> instPerm, instPermHist; // periodic mode, instances of different scales: the instances sorted by tolerance class (vgx_launch_inst_perm)
 	// template mode (vgx_tmpl.hip): the first period of an instanced batch whose instances differ in transform / colours only,
 	// flattened once in local space by the last vgx_tessellate_count
-	int optTmpl; uint32_t optTmplTile;
-	int optTmplClasses;                  // VGX_TMPL_CLASSES=0: template mode only for batches whose instances all repeat the first period
-	int optTmplRound;                    // VGX_TMPL_ROUND=0: batches with Round joins keep the ordinary pipeline
-	int optTmplBatch;                    // vgx_set_static_batches / VGX_TMPL_BATCH=1: a batch without a period becomes ONE template (the whole draw list = one instance)
 	VgxTemplate tmpl;                    // the current template
 	// element capacities of the buffers above. Never lifted: only ensureMeshBuffers and ensureCmdScratch write it, from the buffers'
 	// capacities, so every launch may trust it; a launch that needs other bounds (a sizing pass, the caller's capacities) is given them
 	VgxCaps caps;
-	uint64_t capDraws;
 	VgxTotals* hostTotals; // pinned
-	// vgx_tessellate_immediate: pinned mirror of the last immediate call's totals, the event behind its copy (the next call reads the mirror
-	// only once that copy has landed) and the batch it belongs to (tag = path set generation, draw count; was the detection pass run)
-	HostMirror<VgxTotals> imm; uint64_t immPendTag; uint64_t immPendNDraws; bool immPendDetect;
-	// ... and what the host learned from the last mirror it read: the batch, its polyline vertices / command instances, the period of its
-	// paths (0: none), how many different paths it uses and, after VGX_E_GROWN, its long sub-paths
-	bool immKnown, immLongKnown; uint64_t immTag, immV, immCmd, immLong, immInstLong, immDistinct; uint32_t immPeriod;
-	// state of the last *_count call (what _emit continues from)
-	const vgx_pathset* lastPs;
-	const vgx_draw* lastDraws;
-	uint64_t lastNDraws;
-	int lastStage; // 0 none, 1 flatten counted, 2 tessellate counted
+	VgxImmState imm;
+	VgxCounted counted;
 	// profiling
 	int profiling;
 	// a ring of event sets, one per profiled call: vgx_get_stage_times reads the last call's, vgx_get_stage_times_avg the average over
@@ -262,7 +241,6 @@ static void vgx_rccl_release(vgx_ctx* ctx);
 static void tmplDrop(vgx_ctx* ctx) { ctx->tmpl.on = false; }
 
 namespace {
-
 
 #define HIPCHK(ctx, call)                                 \
 	do {                                                  \
@@ -597,52 +575,47 @@ VgxFlattenArgs flattenArgs(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* 
 	a.apply_transform = applyTransform;
 	a.sub_rec = ctx->subFirst.ptr();
 	a.build_mode = 0;
-	a.thin_static = ps->thinStatic ? ctx->optThinStatic : 0;
+	a.thin_static = ps->thinStatic ? ctx->opt.thinStatic : 0;
 	a.leaf_overflow = ctx->leafOverflow.ptr();
 	a.serial_list = ctx->serialList.ptr();
-	a.inst_period = 0; a.inst_block = ctx->optInstBlock; a.inst_waves = ctx->optInstWaves; a.inst_perm = nullptr;
+	a.inst_period = 0; a.inst_block = ctx->opt.instBlock; a.inst_waves = ctx->opt.instWaves; a.inst_perm = nullptr;
 	a.inst_order = nullptr; a.inst_start = nullptr; a.inst_task_start = nullptr; a.inst_task_path = nullptr;
 	return a;
 }
 
-// Can the instanced kernel assume that `ndraws` draws repeat a sequence of P paths (enough whole instances of it)?
-bool periodUsable(const vgx_ctx* ctx, uint64_t P, uint64_t ndraws)
-{
-	return P && ctx->optInst && ndraws % P == 0 && ndraws / P >= VGX_INST_MIN_INSTANCES;
-}
+// Period the instanced kernel may assume for `ndraws` draws (0: command-parallel kernel); the device re-checks it on every call (OpCmdPrefix)
+uint32_t instPeriodFor(const vgx_ctx* ctx, uint64_t ndraws) { return vgx_period_usable(ctx->opt, ctx->route.chosen.period, ndraws) ? ctx->route.chosen.period : 0; }
 
-// Do `ndraws` draws over `distinct` different paths reuse them (>= VGX_INST_MIN_INSTANCES draws per used path on average)? Then grouped
-// mode sorts them by path when they do not repeat one sequence.
-bool pathsReused(const vgx_ctx* ctx, uint64_t ndraws, uint64_t distinct)
-{
-	return ctx->optInst && distinct != 0 && ndraws < 0xFFFFFFFFull && ndraws / distinct >= VGX_INST_MIN_INSTANCES;
-}
-
-// Period the instanced kernel may assume for a batch of `ndraws` draws (0: command-parallel kernel). The device checks
-// draws[i].path == draws[i % period].path again on every call (OpCmdPrefix).
-uint32_t instPeriodFor(const vgx_ctx* ctx, uint64_t ndraws)
-{
-	return periodUsable(ctx, ctx->instPeriod, ndraws) ? ctx->instPeriod : 0;
-}
-
-// The flatten modes and the template the last count chose no longer hold
-void forgetRoutes(vgx_ctx* ctx)
-{
-	ctx->instPeriod = 0; ctx->instGrouped = 0; ctx->instClasses = 1; ctx->instPermOn = 0;
-	tmplDrop(ctx);
-}
+// The flatten route and the template the last count chose no longer hold
+void forgetRoutes(vgx_ctx* ctx) { ctx->route.chosen = vgx_route_none(); tmplDrop(ctx); }
 
 // Grouped mode for this call: the count pass chose it and the sort buffers hold a batch of this size over this path set.
 bool instGroupedFor(const vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws)
 {
-	return ctx->instGrouped && ctx->optInst && !instPeriodFor(ctx, ndraws) && ndraws > VGX_SMALL_DRAWS && ndraws <= ctx->instCapDraws
-		&& ps->dev.npaths <= ctx->instCapPaths && (uint64_t)ps->dev.npaths * ctx->instClasses <= ctx->instCapKeys && ndraws < 0xFFFFFFFFull;
+	const VgxRouteState& r = ctx->route;
+	return r.chosen.kind == VGX_ROUTE_GROUPED && !instPeriodFor(ctx, ndraws) && ndraws > VGX_SMALL_DRAWS && ndraws <= r.instDraws
+		&& ps->dev.npaths <= r.instPaths && (uint64_t)ps->dev.npaths * r.chosen.classes <= r.instKeys && ndraws < 0xFFFFFFFFull;
 }
 
-// scratch of the grouped mode: histogram / cursor / ranges per path, task table, draw order
+// The one-walk route for this call: what the last count decided and sized, for this path set
+bool oneWalkFor(const vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws)
+{
+	const VgxRouteState& r = ctx->route;
+	return r.chosen.kind == VGX_ROUTE_ONE_WALK && ps == r.f1Ps && ps->gen == r.f1PsGen && !instPeriodFor(ctx, ndraws)
+		&& vgx_f1_route_segments(ps->maxCmdsPerPath, ndraws, r.chosen.f1SegMax) <= r.chosen.f1SegBound;
+}
+
+// does an _emit follow its count (ctx->counted) on the same batch?
+bool followsCount(const vgx_ctx* ctx, VgxCountedStage stage, const vgx_pathset* ps, const vgx_draw* draws, uint64_t n)
+{
+	const VgxCounted& c = ctx->counted;
+	return c.stage == stage && c.ps == ps && c.draws == draws && c.ndraws == n;
+}
+
 // the smallest of several capacities: what a group of buffers that are indexed alike holds
 uint64_t minOf(std::initializer_list<uint64_t> caps) { return std::min(caps); }
 
+// scratch of the grouped mode: histogram / cursor / ranges per path, task table, draw order
 int ensureInstGroup(vgx_ctx* ctx, uint32_t npaths, uint32_t nc, uint64_t ndraws, bool full)
 {
 	int st;
@@ -656,10 +629,10 @@ int ensureInstGroup(vgx_ctx* ctx, uint32_t npaths, uint32_t nc, uint64_t ndraws,
 		if ((st = ensure(ctx, ctx->instKeyStart, nkeys + 1)) != VGX_OK) { return st; }
 		if ((st = ensure(ctx, ctx->instTaskPath, tasks)) != VGX_OK) { return st; }
 		if ((st = ensure(ctx, ctx->instOrder, ndraws + 1)) != VGX_OK) { return st; }
-		ctx->instCapTasks = ctx->instTaskPath.items();
-		ctx->instCapDraws = ctx->instOrder.items() - 1;
-		ctx->instCapKeys = minOf({ ctx->instHist.items() - 1, ctx->instCursor.items() - 1, ctx->instKeyStart.items() - 1 });
-		ctx->instCapPaths = minOf({ ctx->instStart.items() - 1, ctx->instTaskStart.items() - 1 });
+		ctx->route.instTasks = ctx->instTaskPath.items();
+		ctx->route.instDraws = ctx->instOrder.items() - 1;
+		ctx->route.instKeys = minOf({ ctx->instHist.items() - 1, ctx->instCursor.items() - 1, ctx->instKeyStart.items() - 1 });
+		ctx->route.instPaths = minOf({ ctx->instStart.items() - 1, ctx->instTaskStart.items() - 1 });
 	}
 	return VGX_OK;
 }
@@ -668,7 +641,7 @@ void setInstArgs(vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws, VgxFlatte
 {
 	a.inst_period = instPeriodFor(ctx, ndraws);
 	a.inst_perm = nullptr;
-	if (a.inst_period && ctx->instPermOn && ndraws / a.inst_period <= ctx->instPerm.items()) { a.inst_perm = ctx->instPerm.ptr(); }
+	if (a.inst_period && ctx->route.chosen.permute && ndraws / a.inst_period <= ctx->instPerm.items()) { a.inst_perm = ctx->instPerm.ptr(); }
 	if (instGroupedFor(ctx, ps, ndraws)) {
 		a.inst_order = ctx->instOrder.ptr(); a.inst_start = ctx->instStart.ptr();
 		a.inst_task_start = ctx->instTaskStart.ptr(); a.inst_task_path = ctx->instTaskPath.ptr();
@@ -685,7 +658,7 @@ int ensureDrawBuffers(vgx_ctx* ctx, uint64_t ndraws)
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	// what the grow-only buffers hold, not the last batch's size
-	ctx->capDraws = minOf({ ctx->cmdPrefix.cap / sizeof(uint64_t) - 1, ctx->dinfo.items() - 1, ctx->serialList.items() - 1, ctx->subPrefix.items() - 1 });
+	ctx->route.capDraws = minOf({ ctx->cmdPrefix.cap / sizeof(uint64_t) - 1, ctx->dinfo.items() - 1, ctx->serialList.items() - 1, ctx->subPrefix.items() - 1 });
 	return VGX_OK;
 }
 
@@ -737,17 +710,17 @@ void runFlattenBuild(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws,
 	a.build_mode = 1;
 	setInstArgs(ctx, ps, ndraws, a); // periodic: the same value runCmdPrefix checked the draws against
 	if (a.inst_perm) { // periodic mode, instances of different scales: this batch's instances sorted by tolerance class
-		vgx_launch_inst_perm(draws, ndraws / a.inst_period, a.inst_period, ctx->instClasses, ctx->instPermHist.ptr(), ctx->instPerm.ptr(), ctx->totals.ptr(), ctx->optInstPerm == 2, s);
+		vgx_launch_inst_perm(draws, ndraws / a.inst_period, a.inst_period, ctx->route.chosen.classes, ctx->instPermHist.ptr(), ctx->instPerm.ptr(), ctx->totals.ptr(), ctx->opt.instPerm == 2, s);
 		mark(ctx, s, "inst_group");
 	}
 	if (a.inst_order) { // grouped mode: this batch's draws sorted by path
-		vgx_launch_inst_group(draws, ndraws, ps->dev.npaths, ctx->instClasses, ctx->instHist.ptr(), ctx->instCursor.ptr(), ctx->instKeyStart.ptr(),
-			ctx->instStart.ptr(), ctx->instTaskStart.ptr(), ctx->instTaskPath.ptr(), ctx->instCapTasks, ctx->instOrder.ptr(),
+		vgx_launch_inst_group(draws, ndraws, ps->dev.npaths, ctx->route.chosen.classes, ctx->instHist.ptr(), ctx->instCursor.ptr(), ctx->instKeyStart.ptr(),
+			ctx->instStart.ptr(), ctx->instTaskStart.ptr(), ctx->instTaskPath.ptr(), ctx->route.instTasks, ctx->instOrder.ptr(),
 			ctx->totals.ptr(), ctx->partial.p, s);
 		mark(ctx, s, "inst_group");
 	}
 	a.mprep = ctx->mprep.ptr(); // k_flatten_gather / k_flatten_serial write the per-mesh constants with the descriptors
-	vgx_launch_flatten_build(a, ctx->optBuildWaves, s);
+	vgx_launch_flatten_build(a, ctx->opt.buildWaves, s);
 	mark(ctx, s, "flatten_build");
 	OpDrawInfo op;
 	op.dinfo = ctx->dinfo.ptr(); op.ndraws = ndraws; op.totals = ctx->totals.ptr(); op.caps = ctx->caps; op.keepPolyBase = 1;
@@ -757,42 +730,56 @@ void runFlattenBuild(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws,
 	mark(ctx, s, "flatten_gather");
 }
 
-// vgx_tessellate's flatten stage through the ordered one-walk kernel (vgx_flat1.hip; round 6): command prefix -> k_flat1
-// (tasks cut at the roots, leaves staged in LDS, places by look-back: the polyline lands dense and in draw order in the scratch, the per-draw and
-// sub-path records complete) -> the exact builder's draws -> totals -> mesh descriptors from the ordered records. No heap, no scan over the
-// draws. For batches of LONG curves, where k_flatten_build's lanes spill
-// their leaves past the LDS slots and walk in lock-step with the deepest cubic of the chunk (the count decides: >= 10 polyline vertices per command instance).
-void runFlattenOneWalk(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s)
+// flattenArgs for a call that writes the caller's ordered outputs: no mesh tables, no bounds
+VgxFlattenArgs flattenOutArgs(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, int applyTransform, float* poly, vgx_subpath* subs)
 {
-	runCmdPrefix(ctx, ps, draws, ndraws, ~0ull, s); // k_flat1 needs no per-command scratch
-	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, 1);
-	a.mprep = ctx->mprep.ptr(); // k_flatten_serial / the gather write the per-mesh constants with the descriptors
-	const uint64_t segBound = ctx->f1RouteSegBound;
-	VgxF1Args x;
+	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, applyTransform);
+	a.poly = poly; a.subs = subs;
+	a.mdesc = nullptr; a.mtab = nullptr;
+	a.caps.poly_vertices = ~0ull; a.caps.subpaths = ~0ull; a.caps.meshes = ~0ull;
+	return a;
+}
+
+// The one-walk launch sequence (vgx_flat1.hip) behind the command prefix, over the outputs of `a`: the exact builder's count, k_flat1, its draws,
+// the totals (+ the caller's device words). `x`: capacities, bucket size and tag, from the caller; tables of `segBound` segments; `cap`: the kernel instance
+void runOneWalk(vgx_ctx* ctx, const vgx_pathset* ps, const VgxFlattenArgs& a, VgxF1Args x, uint64_t segBound, int cap, vgx_sizes* dev_sizes, uint32_t* dev_status, hipStream_t s)
+{
 	x.seg_draw = ctx->f1SegDraw.ptr(); x.segs = ctx->f1Segs.ptr(); x.grps = x.segs + segBound;
-	x.cap_poly = ctx->caps.poly_vertices; x.cap_subs = ctx->caps.subpaths; x.cap_meshes = ctx->caps.meshes; x.pass = 0; x.read_flags = 0; x.has_empty = ps->hasEmpty ? 1 : 0;
-	x.seg_max = ctx->f1RouteSegMax; x.tag = 0;
+	x.pass = 0; x.read_flags = 0; x.has_empty = ps->hasEmpty ? 1 : 0;
 	if (ps->hasSerial) { // statically serial paths: the exact builder counts their draws first (it marks them in dinfo)
-		noteHip(ctx, hipMemsetAsync(ctx->dinfo.p, 0, ndraws * sizeof(vgx_draw_info), s));
+		noteHip(ctx, hipMemsetAsync(ctx->dinfo.p, 0, a.ndraws * sizeof(vgx_draw_info), s));
 		VgxFlattenArgs ac = a;
 		ac.mdesc = nullptr; ac.mtab = nullptr; ac.mprep = nullptr;
 		vgx_launch_flatten_serial(false, ac, s);
 	}
-	vgx_launch_flat1(a, x, ctx->optF1Waves ? ctx->optF1Waves : 2048, ctx->f1RouteCap, ps->hasSerial, s);
-	VgxFlattenArgs ae = a; // the exact builder's draws: vertices, sub-path records AND mesh descriptors at the places k_flat1 gave them
+	vgx_launch_flat1(a, x, ctx->opt.f1Waves ? ctx->opt.f1Waves : 2048, cap, ps->hasSerial, s);
+	// the exact builder's draws (mesh descriptors too where `a` has them): every draw when the set has serial paths, else those the kernel listed
+	VgxFlattenArgs ae = a;
 	ae.build_mode = ps->hasSerial ? 0 : 1;
 	vgx_launch_flatten_serial(true, ae, s);
-	vgx_launch_flat1_publish(a, x, nullptr, nullptr, s);
+	vgx_launch_flat1_publish(a, x, dev_sizes, dev_status, s);
 	mark(ctx, s, "flatten_one_walk");
-	vgx_launch_flatten_gather_ordered(a, s);
-	mark(ctx, s, "flatten_gather");
 }
 
-// segments the look-back tables of the one-walk route must hold for ANY draw list of `ndraws` draws on this path set
-static uint64_t f1RouteSegmentsFor(const vgx_pathset* ps, uint64_t ndraws, uint32_t segMax)
+// The flatten stage of an asynchronous call (vgx_tessellate, the immediate and the dashed call), by the route the context holds. One-walk (vgx_flat1.hip),
+// for batches of LONG curves, where k_flatten_build's lanes spill their leaves past the LDS slots: command prefix -> k_flat1 (the polyline lands dense and
+// in draw order, the per-draw and sub-path records complete) -> the exact builder's draws -> totals -> mesh descriptors. No heap, no scan over the draws
+void runFlattenStage(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s)
 {
-	const uint64_t minItems = segMax < 32 ? segMax : 32;
-	return ndraws * (uint64_t)(ps->maxCmdsPerPath ? ps->maxCmdsPerPath : 1) / minItems + 2;
+	if (!oneWalkFor(ctx, ps, ndraws)) { // command prefix (the period re-checked) -> k_flatten_build's sequence
+		runCmdPrefix(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, s, instPeriodFor(ctx, ndraws));
+		runFlattenBuild(ctx, ps, draws, ndraws, s);
+		return;
+	}
+	runCmdPrefix(ctx, ps, draws, ndraws, ~0ull, s); // k_flat1 needs no per-command scratch
+	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, 1);
+	a.mprep = ctx->mprep.ptr(); // k_flatten_serial / the gather write the per-mesh constants with the descriptors
+	const VgxRoute& r = ctx->route.chosen;
+	VgxF1Args x;
+	x.cap_poly = ctx->caps.poly_vertices; x.cap_subs = ctx->caps.subpaths; x.cap_meshes = ctx->caps.meshes; x.seg_max = r.f1SegMax; x.tag = 0;
+	runOneWalk(ctx, ps, a, x, r.f1SegBound, r.f1Cap, nullptr, nullptr, s);
+	vgx_launch_flatten_gather_ordered(a, s);
+	mark(ctx, s, "flatten_gather");
 }
 
 // the stroke / fill kernels' arguments over the context's scratch, no output buffers yet
@@ -807,6 +794,8 @@ VgxStrokeArgs strokeArgs(vgx_ctx* ctx, const vgx_draw* draws, const float* poly,
 	return a;
 }
 
+// The bounds of a count: the context's scratch, no output capacities
+VgxCaps sizingCaps(const vgx_ctx* ctx) { VgxCaps c = ctx->caps; c.vertices = ~0ull; c.indices = ~0ull; return c; }
 // The bounds of a call that writes into `out`: the context's scratch, the caller's vertex / index / mesh-table capacities
 VgxCaps outCapsFor(const vgx_ctx* ctx, const vgx_mesh_out* out)
 {
@@ -885,11 +874,11 @@ int runStrokeEmit(vgx_ctx* ctx, const vgx_draw* draws, const vgx_mesh_out* out, 
 	VgxStrokeArgs a = strokeArgs(ctx, draws, poly, ctx->caps);
 	a.mesh_base = ctx->asmArmed ? ctx->meshBase.ptr() : nullptr;
 	a.pos = out->pos; a.color = out->color; a.idx = out->idx; a.meshes_out = tableDone ? nullptr : out->meshes;
-	a.no_long = out->cap_vertices < ctx->optBigEmitMin ? 1 : 0; // frame-sized: one stroke kernel less to launch
+	a.no_long = out->cap_vertices < ctx->opt.bigEmitMin ? 1 : 0; // frame-sized: one stroke kernel less to launch
 	// Batches of fills and closed Miter AA / Thin strokes (the scan over the meshes decides, on the device): one draw-ordered tile
 	// kernel instead of k_fill + k_stroke_simple (vgx_tile.hip). Not for frame-sized calls (two more launches than they are worth).
 	uint64_t capTiles = 0;
-	if (ctx->optTileEmit && ctx->tileHint && out->cap_vertices >= ctx->optBigEmitMin && out->cap_vertices / VGX_TILE_ELEMS + 2 < 0x7FFFFFFFull) {
+	if (ctx->opt.tileEmit && ctx->route.tileHint && out->cap_vertices >= ctx->opt.bigEmitMin && out->cap_vertices / VGX_TILE_ELEMS + 2 < 0x7FFFFFFFull) {
 		capTiles = out->cap_vertices / VGX_TILE_ELEMS + 2; // every element emits at least one vertex
 		const int st = ensure(ctx, ctx->tileTab, capTiles);
 		if (st != VGX_OK) { return st; }
@@ -936,72 +925,33 @@ int ensureCmdScratch(vgx_ctx* ctx, uint64_t ncmd)
 	return VGX_OK;
 }
 
-// Polyline scratch doubles as the heap of the single-pass path (k_flatten_build), for a batch of V polyline vertices, `longV` of them in
-// sub-paths longer than VGX_LONG_SUBPATH, `ncmd` command instances. Its waves switch to a fresh block when a chunk does not fit: the unused
-// tail of the old block is smaller than that chunk (<= 1x the real vertices over the whole batch), the moved prefix of a spanning sub-path
-// is < VGX_LONG_SUBPATH per >= VGX_BUILD_BLOCK block (<= 1/4), and longer sub-paths grow geometrically (<= 4x their own size). Plus every
-// wave's last open block. k_flatten_thin (lineTo-only path sets; ps == nullptr: any set) places draw d at its command prefix -- one slot
-// per command instance -- and the exact builder's draws behind that.
-uint64_t heapBuildVerts(const vgx_pathset* ps, uint64_t V, uint64_t ncmd, uint64_t longV)
-{
-	uint64_t h = V * 9 / 4 + 4 * longV + 2 * (uint64_t)VGX_BUILD_WAVES * VGX_BUILD_BLOCK;
-	if ((!ps || ps->thinStatic) && h < 2 * ncmd + 4096) { h = 2 * ncmd + 4096; }
-	return h;
-}
-
-// ... of k_flatten_inst's lane-private blocks (vgx_inst.h; instLong = vertices in sub-paths longer than VGX_INST_LONG_SUBPATH): a block
-// left behind wastes less than the one sub-path that did not fit (< the block's useful vertices while sub-paths are at most half a block
-// long), longer sub-paths grow geometrically (<= 4x their size + a block, counted with head room), plus every lane's last open block
-uint64_t heapInstVerts(const vgx_ctx* ctx, uint64_t V, uint64_t instLong)
-{
-	const uint64_t grown = (ctx->optInstBlock >= VGX_INST_BLOCK) ? V * 9 / 4 + 8 * instLong : V * 10;
-	return grown + (uint64_t)ctx->optInstWaves * 64 * ctx->optInstBlock + 4096;
-}
-
-// Leaf-list capacity of the one-walk kernel instance and commands per segment bucket, for a batch of V polyline vertices over `ncmd`
-// command instances (ncmd == 0: not known). A 64-command chunk of ~45-segment cubics stages ~1450 leaves (the 1664-entry instance: six
-// waves per CU); lighter batches take the 1024-entry instance (eight waves per CU), heavier ones (long curves: 145 segments per cubic)
-// the 3072-entry instance with smaller buckets, so that a chunk's leaves still fit (a chunk that overflows the list is placed by walking
-// its cubics a second time). VGX_F1_CAP / VGX_F1_SEG override both.
-void f1Shape(const vgx_ctx* ctx, uint64_t V, uint64_t ncmd, int* cap, uint32_t* segMax)
-{
-	*cap = 1664; *segMax = 64;
-	if (ncmd) {
-		const double perCmd = (double)V / (double)ncmd;
-		if (perCmd * 64.0 <= 800.0) { *cap = 1024; }
-		else if (perCmd * 64.0 > 1500.0) {
-			// long curves (145 segments per cubic at box 10 000): the 3072-entry instance with buckets of a power of two -- 2^k cubics
-			// become 64 tasks after whole rounds of cutting (17 cubics would stay at 34 half-cubic tasks). Measured on 1 M such
-			// cubics: 3072 entries x 32 commands 3.4 ms, 1664 x 16 4.1 ms, 1664 x 8 6.2 ms (two-phase entry: 6.0 ms).
-			*cap = 3072;
-			const double m = 0.8 * 3072.0 / perCmd;
-			*segMax = m >= 64.0 ? 64u : (m >= 32.0 ? 32u : (m >= 16.0 ? 16u : 8u));
-		}
-	}
-	if (ctx->optF1Cap) { *cap = ctx->optF1Cap; }
-	if (ctx->optF1Seg) { *segMax = (uint32_t)ctx->optF1Seg; }
-}
-
 // look-back tables of the one-walk kernel for `segBound` segments: segment table, records (+ one group record per 64)
 int ensureF1Tables(vgx_ctx* ctx, uint64_t segBound)
 {
-	int st;
-	if ((st = ensure(ctx, ctx->f1SegDraw, segBound + 1)) != VGX_OK) { return st; }
-	return ensure(ctx, ctx->f1Segs, segBound + segBound / 64 + 2);
+	const int st = ensure(ctx, ctx->f1SegDraw, segBound + 1);
+	return st != VGX_OK ? st : ensure(ctx, ctx->f1Segs, segBound + segBound / 64 + 2);
 }
 
-// vgx_tessellate's one-walk route sized for any draw list of up to `segDraws` draws on `ps` (f1Route*); *ok = false: more than 2^24
-// segments, the route is not taken
-int f1Reserve(vgx_ctx* ctx, const vgx_pathset* ps, uint64_t segDraws, int cap, uint32_t segMax, bool* ok)
+// The context takes the route `r` (vgx_route_choose) for a batch of `ndraws` draws on `ps`: the tables it needs, then the state
+int adoptRoute(vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws, const VgxRoute& r)
 {
-	*ok = false;
-	const uint64_t segBound = f1RouteSegmentsFor(ps, segDraws, segMax);
-	if (segBound > (1ull << 24)) { return VGX_OK; }
-	const int st = ensureF1Tables(ctx, segBound);
-	if (st != VGX_OK) { return st; }
-	ctx->f1RoutePs = ps; ctx->f1RoutePsGen = ps->gen; ctx->f1RouteCap = cap; ctx->f1RouteSegMax = segMax; ctx->f1RouteSegBound = segBound;
-	*ok = true;
+	int st;
+	if (r.permute) {
+		if ((st = ensure(ctx, ctx->instPerm, ndraws / r.period + 1)) != VGX_OK) { return st; }
+		if ((st = ensure(ctx, ctx->instPermHist, (size_t)r.classes + 2)) != VGX_OK) { return st; }
+	}
+	if (r.kind == VGX_ROUTE_GROUPED && (st = ensureInstGroup(ctx, ps->dev.npaths, r.classes, ndraws, true)) != VGX_OK) { return st; }
+	if (r.kind == VGX_ROUTE_ONE_WALK && (st = ensureF1Tables(ctx, r.f1SegBound)) != VGX_OK) { return st; }
+	if (r.kind == VGX_ROUTE_ONE_WALK) { ctx->route.f1Ps = ps; ctx->route.f1PsGen = ps->gen; }
+	ctx->route.chosen = r;
 	return VGX_OK;
+}
+
+// what every route decision reads about the path set and the batch's size, on top of `known` (what is known of its content)
+VgxRouteFacts routeFacts(VgxRouteFacts f, const vgx_pathset* ps, uint64_t ndraws)
+{
+	f.ndraws = ndraws; f.npaths = ps->dev.npaths; f.maxCmdsPerPath = ps->maxCmdsPerPath; f.thinStatic = ps->thinStatic;
+	return f;
 }
 
 // A frame-sized batch (ndraws <= VGX_SMALL_DRAWS): five launches instead of seventeen (vgx_flatten.hip, "Frame-sized batches") --
@@ -1017,7 +967,7 @@ int runFrameSized(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, ui
 	VgxFlattenArgs f = flattenArgs(ctx, ps, draws, ndraws, 1);
 	f.build_mode = 1;
 	f.mprep = ctx->mprep.ptr();
-	vgx_launch_flatten_build(f, ctx->optBuildWaves, s, false);
+	vgx_launch_flatten_build(f, ctx->opt.buildWaves, s, false);
 	mark(ctx, s, "flatten_build");
 	VgxStrokeArgs sa = strokeArgs(ctx, draws, nullptr, outCaps);
 	sa.no_long = 1;
@@ -1083,43 +1033,8 @@ int vgx_create(int device, vgx_ctx** out_ctx)
 		delete ctx;
 		return VGX_E_HIP;
 	}
-	// tuning / testing knobs: read once here, never on the call path
-	ctx->optBigEmitMin = 1ull << 18;
-	if (const char* e = getenv("VGX_BIG_EMIT_MIN")) { ctx->optBigEmitMin = strtoull(e, nullptr, 10); }
-	// k_pick_tris strides a fixed grid over the candidate triangles (their count stays on the device): four workgroups per CU of a
-	// 256-CU part; workgroups without a tile exit at once. VGX_PICK_GRID=N > 0 sets another (the tests force many tiles per workgroup)
-	ctx->optPickGrid = 1024;
-	if (const char* e = getenv("VGX_PICK_GRID")) { const int v = atoi(e); if (v > 0) { ctx->optPickGrid = (uint32_t)(v > 65536 ? 65536 : v); } }
-	ctx->optTileEmit = 1;
-	if (const char* e = getenv("VGX_TILE_EMIT")) { ctx->optTileEmit = atoi(e) != 0; }
-	ctx->optPsNoSmall = getenv("VGX_PS_NO_SMALL") ? 1 : 0; // testing knob: frame-sized path sets through the large-set launch sequence
-	ctx->optBuildWaves = VGX_BUILD_WAVES;
-	ctx->optNoSmall = getenv("VGX_NO_SMALL") ? 1 : 0; // testing knob: frame-sized batches through the large-batch launch sequence
-	ctx->optInst = 1; ctx->optInstWaves = VGX_INST_WAVES; ctx->optInstBlock = VGX_INST_BLOCK; // VGX_INST=0: instanced batches through k_flatten_build as well
-	if (const char* e = getenv("VGX_INST")) { ctx->optInst = atoi(e) != 0; }
-	ctx->optInstClasses = 256; ctx->optInstPerm = 1;
-	if (const char* e = getenv("VGX_INST_PERM")) { const int v = atoi(e); ctx->optInstPerm = v == 2 ? 2 : (v != 0); } // 2: the several-kernel sort for any count (testing)
-	if (const char* e = getenv("VGX_INST_CLASSES")) { const int v = atoi(e); if (v >= 1 && v <= 65536) { uint32_t p2 = 1; while (p2 * 2 <= (uint32_t)v) { p2 *= 2; } ctx->optInstClasses = p2; } }
-	if (const char* e = getenv("VGX_INST_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 65536) { ctx->optInstWaves = v; } }
-	if (const char* e = getenv("VGX_INST_BLOCK")) { const int v = atoi(e); if (v >= 1 && v <= 65536) { ctx->optInstBlock = (uint32_t)v; } }
-	ctx->optTmpl = 1; ctx->optTmplTile = VGX_TMPL_MAX_TILE; // VGX_TMPL=0: no template mode (instanced batches through k_flatten_inst + k_fill + k_stroke)
-	if (const char* e = getenv("VGX_TMPL")) { ctx->optTmpl = atoi(e) != 0; }
-	ctx->optTmplClasses = 1; // VGX_TMPL_CLASSES=0: template mode only for batches whose instances all repeat the first period
-	if (const char* e = getenv("VGX_TMPL_CLASSES")) { ctx->optTmplClasses = atoi(e) != 0; }
-	ctx->optTmplRound = 1;
-	if (const char* e = getenv("VGX_TMPL_ROUND")) { ctx->optTmplRound = atoi(e) != 0; }
-	ctx->optTmplBatch = 0;
-	if (const char* e = getenv("VGX_TMPL_BATCH")) { ctx->optTmplBatch = atoi(e) != 0; }
-	if (const char* e = getenv("VGX_TMPL_TILE")) { const int v = atoi(e); if (v >= 64 && v <= VGX_TMPL_MAX_TILE) { ctx->optTmplTile = (uint32_t)v / 64u * 64u; } } // testing: elements per tile (<= the LDS stage of k_tmpl_emit)
-	ctx->optTessFlat1 = 1; ctx->f1Route = false; ctx->f1RoutePs = nullptr; ctx->f1RoutePsGen = 0; ctx->f1RouteCap = 1664; ctx->f1RouteSegMax = 64; ctx->f1RouteSegBound = 0;
-	if (const char* e = getenv("VGX_TESS_FLAT1")) { const int v = atoi(e); if (v >= 0 && v <= 2) { ctx->optTessFlat1 = v; } }
-	ctx->optF1Waves = 0; ctx->optF1Cap = 0; ctx->optF1Seg = 0;
-	if (const char* e = getenv("VGX_F1_SEG")) { const int v = atoi(e); if (v >= 2 && v <= 64) { ctx->optF1Seg = v; } }
-	if (const char* e = getenv("VGX_F1_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 65536) { ctx->optF1Waves = v; } }
-	if (const char* e = getenv("VGX_F1_CAP")) { ctx->optF1Cap = atoi(e); }
-	ctx->optThinStatic = 1;
-	if (const char* e = getenv("VGX_THIN_STATIC")) { ctx->optThinStatic = atoi(e) != 0; }
-	if (const char* e = getenv("VGX_BUILD_WAVES")) { const int v = atoi(e); if (v >= 1 && v < VGX_BUILD_WAVES) { ctx->optBuildWaves = v; } }
+	ctx->opt = vgx_options_read(getenv); // tuning / testing knobs: read once here, never on the call path
+	forgetRoutes(ctx);
 	*out_ctx = ctx;
 	return VGX_OK;
 }
@@ -1133,7 +1048,7 @@ int vgx_destroy(vgx_ctx* ctx)
 	vgx_scratch_release(ctx->scratch);
 	if (ctx->hostTotals) { (void)hipHostFree(ctx->hostTotals); }
 	if (ctx->hostF1) { (void)hipHostFree(ctx->hostF1); }
-	ctx->imm.release(); ctx->dash.release(); ctx->df.release(); ctx->ras.release(); ctx->rasDmg.release();
+	ctx->imm.mirror.release(); ctx->dash.release(); ctx->df.release(); ctx->ras.release(); ctx->rasDmg.release();
 	if (ctx->hostPs) { (void)hipHostFree(ctx->hostPs); }
 	if (ctx->psImage) { (void)hipHostFree(ctx->psImage); }
 	for (int i = 0; i < VGX_PS_POOL; ++i) { if (ctx->psPool[i].p) { (void)hipFree(ctx->psPool[i].p); } }
@@ -1268,7 +1183,7 @@ int vgx_pathset_create(vgx_ctx* ctx, const vgx_pathset_desc* desc, vgx_pathset**
 	if (!ps) {
 		return VGX_E_INVALID_ARG;
 	}
-	const bool small = !ctx->optPsNoSmall && vgx_pathset_is_small(ncmd, npaths, nargs);
+	const bool small = !ctx->opt.psNoSmall && vgx_pathset_is_small(ncmd, npaths, nargs);
 	ps->blob = nullptr;
 	ps->blobBytes = L.total;
 	if (small) { ps->blob = psPoolTake(ctx, L.total, &ps->blobBytes); }
@@ -1393,7 +1308,7 @@ int vgx_pathset_destroy(vgx_ctx* ctx, vgx_pathset* ps)
 	if (!ctx || !ps) {
 		return VGX_E_INVALID_ARG;
 	}
-	if (ctx->lastPs == ps) { ctx->lastPs = nullptr; ctx->lastStage = 0; }
+	if (ctx->counted.ps == ps) { ctx->counted.ps = nullptr; ctx->counted.stage = VGX_COUNTED_NONE; }
 	if (ctx->tmpl.ps == ps) { tmplDrop(ctx); ctx->tmpl.ps = nullptr; ctx->tmpl.psGen = 0; } // a later path set at the same address must not match the template
 	// hipFree waits for everything in flight (a caller may drop a set right behind an asynchronous call that reads it); a blob that
 	// goes back to the pool instead must be as idle: the same wait, without the allocator's work
@@ -1404,15 +1319,15 @@ int vgx_pathset_destroy(vgx_ctx* ctx, vgx_pathset* ps)
 }
 
 // ---- flatten ------------------------------------------------------------------------------------------
-// detectInst: look for reused paths (instanced flatten kernel of vgx_tessellate); the flatten-only entry points have no use for it
-static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s, bool detectInst)
+// facts: vgx_tessellate_count's -- look for reused paths (vgx_tessellate's instanced flatten) and report them; nullptr: a flatten-only entry
+static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, hipStream_t s, VgxRouteFacts* facts)
 {
 	int st;
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
 	forgetRoutes(ctx); // the scratch is re-sized for this batch; a template belongs to the count call that built it
 	// pass 1: command instances (sizes the per-command scratch; not known yet: no bound)
 	runCmdPrefix(ctx, ps, draws, ndraws, ~0ull, s);
-	if (detectInst && ctx->optInst && ndraws > VGX_SMALL_DRAWS) {
+	if (facts && ctx->opt.inst && ndraws > VGX_SMALL_DRAWS) {
 		vgx_launch_inst_detect(draws, ndraws, ctx->totals.ptr(), s);
 		// ... and how many different paths the draws use (grouped mode, when the sequence does not repeat)
 		if ((st = ensureInstGroup(ctx, ps->dev.npaths, 1, ndraws, false)) != VGX_OK) { return st; }
@@ -1421,35 +1336,12 @@ static int flattenCountBody(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw*
 	}
 	if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
 	if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
-	if (ctx->hostTotals->inst_detect_inv != 0 && !ctx->hostTotals->inst_detect_bad) {
-		// the draws repeat one sequence of paths (a drawing submitted for many instances): vgx_inst.hip
-		const unsigned long long P = ~0ull - ctx->hostTotals->inst_detect_inv;
-		if (P <= 0xFFFFFFFFull) { ctx->instPeriod = (uint32_t)P; }
-	}
-	const VgxTotals& ht = *ctx->hostTotals;
-	const bool reused = ndraws > VGX_SMALL_DRAWS && pathsReused(ctx, ndraws, ht.inst_distinct);
-	if (reused && ctx->optInstClasses > 1 && (instPeriodFor(ctx, ndraws) ? ht.inst_tol_varies != 0 : (uint32_t)~ht.inst_tol_lo_inv != ht.inst_tol_hi)) {
-		// The instances of a path differ in scale: in the periodic mapping (lane = instance) the lanes of a wave would
-		// disagree about nearly every cubic. Grouped mode sorted by (path, tolerance class) instead.
-		uint32_t nc = ctx->optInstClasses;
-		if (instPeriodFor(ctx, ndraws) && ctx->optInstPerm) {
-			// the sequence repeats: keep the periodic mapping (closed-form offsets, no per-draw sort) and permute the INSTANCES
-			const uint64_t ninst = ndraws / ctx->instPeriod;
-			if (nc > 1024u) { nc = 1024u; }
-			if ((st = ensure(ctx, ctx->instPerm, ninst + 1)) != VGX_OK) { return st; }
-			if ((st = ensure(ctx, ctx->instPermHist, (size_t)nc + 2)) != VGX_OK) { return st; }
-			ctx->instClasses = nc;
-			ctx->instPermOn = 1;
-		} else {
-			while (nc > 1 && (uint64_t)ps->dev.npaths * nc > (1ull << 22)) { nc >>= 1; } // scratch of at most 4 M keys
-			ctx->instClasses = nc;
-			if (nc > 1) { ctx->instPeriod = 0; }
-		}
-	}
-	if (reused && !instPeriodFor(ctx, ndraws)) {
-		// paths are reused but not as a repeating sequence: grouped mode
-		if ((st = ensureInstGroup(ctx, ps->dev.npaths, ctx->instClasses, ndraws, true)) != VGX_OK) { return st; }
-		ctx->instGrouped = 1;
+	if (facts) { // (without the detection pass the totals' words are zero: no period, no reuse)
+		const VgxTotals& ht = *ctx->hostTotals;
+		*facts = routeFacts(VgxRouteFacts(), ps, ndraws);
+		facts->period = vgx_period_decode(ht.inst_detect_inv, ht.inst_detect_bad);
+		facts->distinct = ht.inst_distinct;
+		facts->tolKnown = true; facts->tolVariesPeriodic = ht.inst_tol_varies != 0; facts->tolVariesAny = (uint32_t)~ht.inst_tol_lo_inv != ht.inst_tol_hi;
 	}
 	if ((st = ensureCmdScratch(ctx, ctx->hostTotals->sizes.num_cmd_instances)) != VGX_OK) { return st; }
 	// pass 2: per-draw counts (sizes polyline / sub-path / mesh scratch: no bound on those)
@@ -1470,13 +1362,13 @@ int vgx_flatten_count(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws
 	}
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
-	const int st = flattenCountBody(ctx, ps, draws, ndraws, s, false);
+	ctx->counted.stage = VGX_COUNTED_NONE;
+	const int st = flattenCountBody(ctx, ps, draws, ndraws, s, nullptr);
 	if (st != VGX_OK) { return st; }
 	*out_sizes = ctx->hostTotals->sizes;
 	out_sizes->num_vertices = 0;
 	out_sizes->num_indices = 0;
-	ctx->lastPs = ps; ctx->lastDraws = draws; ctx->lastNDraws = ndraws; ctx->lastStage = 1;
+	ctx->counted = VgxCounted{ ps, draws, ndraws, VGX_COUNTED_FLATTEN };
 	return VGX_OK;
 }
 
@@ -1486,7 +1378,7 @@ int vgx_flatten_emit(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws,
 	if (!ctx || !ps || !out || (!draws && ndraws)) {
 		return VGX_E_INVALID_ARG;
 	}
-	if (ctx->lastStage != 1 || ctx->lastPs != ps || ctx->lastDraws != draws || ctx->lastNDraws != ndraws) {
+	if (!followsCount(ctx, VGX_COUNTED_FLATTEN, ps, draws, ndraws)) {
 		return VGX_E_INVALID_ARG; // must follow vgx_flatten_count on the same batch (not vgx_tessellate_count: its polyline scratch is live)
 	}
 	const vgx_sizes& sz = ctx->hostTotals->sizes;
@@ -1499,12 +1391,7 @@ int vgx_flatten_emit(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws,
 	// outputs the caller does not want still need somewhere to go
 	if (!out->poly) { if ((st = ensure(ctx, ctx->poly, (sz.num_poly_vertices + 1) * 2 * sizeof(float))) != VGX_OK) { return st; } }
 	if (!out->subpaths) { if ((st = ensure(ctx, ctx->subs, sz.num_subpaths + 1)) != VGX_OK) { return st; } }
-	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, apply_transform);
-	a.poly = out->poly ? out->poly : (float*)ctx->poly.p;
-	a.subs = out->subpaths ? out->subpaths : ctx->subs.ptr();
-	a.mdesc = nullptr;
-	a.mtab = nullptr;
-	a.caps.poly_vertices = ~0ull; a.caps.subpaths = ~0ull; a.caps.meshes = ~0ull;
+	const VgxFlattenArgs a = flattenOutArgs(ctx, ps, draws, ndraws, apply_transform, out->poly ? out->poly : (float*)ctx->poly.p, out->subpaths ? out->subpaths : ctx->subs.ptr());
 	vgx_launch_flatten(true, a, VGX_GRID_BLOCKS, s);
 	mark(ctx, s, "flatten_emit");
 	if (out->draw_info && ndraws) {
@@ -1514,6 +1401,22 @@ int vgx_flatten_emit(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws,
 }
 
 // ---- vgx_flatten: the ordered one-walk flatten (vgx_flat1.hip), asynchronous ---------------------------------------------
+// What both routes of vgx_flatten end with: vertices and command instances to hostF1, for the next call's choice (never waited for; one-walk: the tag
+// lands behind the two values -- the two-walk route runs on a tag that is known already), and the caller's copy of the per-draw records
+static int flattenDone(vgx_ctx* ctx, uint64_t tag, bool withTag, const vgx_flat_out* out, uint64_t ndraws, hipStream_t s)
+{
+	if (ctx->hostF1) {
+		VgxTotals* T = ctx->totals.ptr();
+		ctx->f1Tag = tag;
+		noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[0], &T->sizes.num_poly_vertices, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+		noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[1], &T->sizes.num_cmd_instances, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+		if (withTag) { noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[2], &T->flat_tag, sizeof(unsigned long long), hipMemcpyDeviceToHost, s)); }
+	}
+	if (out->draw_info && ndraws) {
+		HIPCHK(ctx, hipMemcpyAsync(out->draw_info, ctx->dinfo.p, ndraws * sizeof(vgx_draw_info), hipMemcpyDeviceToDevice, s));
+	}
+	return launchStatus(ctx);
+}
 int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, int apply_transform, const vgx_flat_out* out,
                 vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
 {
@@ -1523,20 +1426,20 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	}
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
+	ctx->counted.stage = VGX_COUNTED_NONE;
 	tmplDrop(ctx);
 	int st;
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
-	// The kernel instance and segment bucket (f1Shape) from the batch's leaves per command, taken from the LAST call on this context with
+	// The kernel instance and segment bucket (vgx_f1_shape) from the batch's leaves per command, taken from the LAST call on this context with
 	// the same path set and draw count, when that call's result has arrived.
-	const uint64_t tag = ps->gen * 0x9E3779B97F4A7C15ull + ndraws;
+	const uint64_t tag = vgx_batch_tag(ps->gen, ndraws);
 	if (!ctx->hostF1) {
 		if (hipHostMalloc((void**)&ctx->hostF1, 4 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess) { ctx->hostF1[0] = 0; ctx->hostF1[1] = 0; ctx->hostF1[2] = 0; ctx->hostF1[3] = 0; }
 		else { ctx->hostF1 = nullptr; }
 	}
 	const bool known = ctx->hostF1 && ctx->f1Tag == tag && ctx->hostF1[1] != 0 && ctx->hostF1[2] == tag;
 	int cap; uint32_t segMax;
-	f1Shape(ctx, known ? ctx->hostF1[0] : 0, known ? ctx->hostF1[1] : 0, &cap, &segMax);
+	vgx_f1_shape(ctx->opt, known ? ctx->hostF1[0] : 0, known ? ctx->hostF1[1] : 0, &cap, &segMax);
 	// Very short curves (a handful of segments per cubic: a chunk of 64 commands yields a few hundred vertices) are bound by what
 	// a SEGMENT costs in the one-walk kernel -- its dependent loads and its place in the order, ~40 000 cycles whatever it holds --
 	// not by the walk: the two-walk kernels (count -> scan over draws -> emit, vgx_flatten.hip) are faster there (1 M cubics of
@@ -1546,7 +1449,7 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	// set (the tag only says that the set and the number of draws are the last call's -- the draws' paths may have changed).
 	// A set whose longest path is far above its mean (the bound above twice the last call's total) takes the one-walk route instead.
 	const uint64_t cmdBoundAll = ndraws * (uint64_t)(ps->maxCmdsPerPath ? ps->maxCmdsPerPath : 1);
-	if (known && !ctx->optF1Cap && !ctx->optF1Seg && !ps->hasEmpty
+	if (known && !ctx->opt.f1Cap && !ctx->opt.f1Seg && !ps->hasEmpty
 		&& (double)ctx->hostF1[0] / (double)ctx->hostF1[1] * 64.0 <= 384.0 && cmdBoundAll <= 2 * ctx->hostF1[1] + 4096) {
 		if ((st = ensure(ctx, ctx->cmdCnt, cmdBoundAll + 1)) != VGX_OK) { return st; }
 		// The device-side guard of THIS call only (a batch that grew: VGX_E_NOSPACE). The two-walk kernels write per-command words
@@ -1555,21 +1458,10 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 		VgxCaps countCaps = ctx->caps; // the scan over the draws compares the totals with the caller's capacities
 		countCaps.poly_vertices = out->cap_poly_vertices; countCaps.subpaths = out->cap_subpaths; countCaps.meshes = ~0ull;
 		runFlattenCount(ctx, ps, draws, ndraws, countCaps, s);
-		VgxFlattenArgs a2 = flattenArgs(ctx, ps, draws, ndraws, apply_transform);
-		a2.poly = out->poly; a2.subs = out->subpaths; a2.mdesc = nullptr; a2.mtab = nullptr;
-		a2.caps.poly_vertices = ~0ull; a2.caps.subpaths = ~0ull; a2.caps.meshes = ~0ull;
-		vgx_launch_flatten(true, a2, VGX_GRID_BLOCKS, s);
+		vgx_launch_flatten(true, flattenOutArgs(ctx, ps, draws, ndraws, apply_transform, out->poly, out->subpaths), VGX_GRID_BLOCKS, s);
 		mark(ctx, s, "flatten_emit");
 		publish(ctx, dev_sizes, dev_status, s);
-		{
-			VgxTotals* T = ctx->totals.ptr();
-			noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[0], &T->sizes.num_poly_vertices, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-			noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[1], &T->sizes.num_cmd_instances, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-		}
-		if (out->draw_info && ndraws) {
-			HIPCHK(ctx, hipMemcpyAsync(out->draw_info, ctx->dinfo.p, ndraws * sizeof(vgx_draw_info), hipMemcpyDeviceToDevice, s));
-		}
-		return launchStatus(ctx);
+		return flattenDone(ctx, tag, false, out, ndraws, s);
 	}
 	// Segments: buckets of at least min(32, segMax) command instances. The command total is not known on the host without a round
 	// trip; ndraws x (longest path) bounds it (a batch whose bound is absurdly far above its real size asks once, synchronously).
@@ -1583,37 +1475,10 @@ int vgx_flatten(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint
 	}
 	const uint64_t segBound = cmdBound / minItems + 2;
 	if ((st = ensureF1Tables(ctx, segBound)) != VGX_OK) { return st; }
-	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, apply_transform);
-	a.poly = out->poly;
-	a.subs = out->subpaths;
-	a.mdesc = nullptr; a.mtab = nullptr;
-	a.caps.poly_vertices = ~0ull; a.caps.subpaths = ~0ull; a.caps.meshes = ~0ull;
 	VgxF1Args x;
-	x.seg_draw = ctx->f1SegDraw.ptr(); x.segs = ctx->f1Segs.ptr(); x.grps = x.segs + segBound;
-	x.cap_poly = out->cap_poly_vertices; x.cap_subs = out->cap_subpaths; x.cap_meshes = ~0ull; x.pass = 0; x.read_flags = 0; x.has_empty = ps->hasEmpty ? 1 : 0; x.seg_max = segMax; x.tag = tag;
-	if (ps->hasSerial) { // statically serial paths: the exact builder counts their draws first (it marks them in dinfo)
-		noteHip(ctx, hipMemsetAsync(ctx->dinfo.p, 0, ndraws * sizeof(vgx_draw_info), s));
-		vgx_launch_flatten_serial(false, a, s);
-	}
-	const int waves = ctx->optF1Waves ? ctx->optF1Waves : 2048;
-	vgx_launch_flat1(a, x, waves, cap, ps->hasSerial, s);
-	// draws of the exact builder: every draw is inspected when the set has serial paths, else only the draws the kernel listed
-	VgxFlattenArgs ae = a;
-	ae.build_mode = ps->hasSerial ? 0 : 1;
-	vgx_launch_flatten_serial(true, ae, s);
-	vgx_launch_flat1_publish(a, x, dev_sizes, dev_status, s);
-	mark(ctx, s, "flatten_one_walk");
-	if (ctx->hostF1) { // for the next call's choice of instance / bucket (never waited for)
-		VgxTotals* T = ctx->totals.ptr();
-		ctx->f1Tag = tag;
-		noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[0], &T->sizes.num_poly_vertices, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-		noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[1], &T->sizes.num_cmd_instances, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-		noteHip(ctx, hipMemcpyAsync(&ctx->hostF1[2], &T->flat_tag, sizeof(unsigned long long), hipMemcpyDeviceToHost, s)); // the tag lands behind the two values
-	}
-	if (out->draw_info && ndraws) {
-		HIPCHK(ctx, hipMemcpyAsync(out->draw_info, ctx->dinfo.p, ndraws * sizeof(vgx_draw_info), hipMemcpyDeviceToDevice, s));
-	}
-	return launchStatus(ctx);
+	x.cap_poly = out->cap_poly_vertices; x.cap_subs = out->cap_subpaths; x.cap_meshes = ~0ull; x.seg_max = segMax; x.tag = tag;
+	runOneWalk(ctx, ps, flattenOutArgs(ctx, ps, draws, ndraws, apply_transform, out->poly, out->subpaths), x, segBound, cap, dev_sizes, dev_status, s);
+	return flattenDone(ctx, tag, true, out, ndraws, s);
 }
 
 // ---- partition (contiguous ranges per GPU, balanced on the count pass for heterogeneous batches) -------------
@@ -1649,10 +1514,10 @@ int vgx_partition(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, ui
 	}
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
+	ctx->counted.stage = VGX_COUNTED_NONE;
 	int st;
 	uint64_t align = 1;
-	if (ctx->optInst && ndraws > VGX_SMALL_DRAWS) { // a drawing submitted for many instances? Then the cuts fall between instances
+	if (ctx->opt.inst && ndraws > VGX_SMALL_DRAWS) { // a drawing submitted for many instances? Then the cuts fall between instances
 		if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 		noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
 		vgx_launch_inst_detect(draws, ndraws, ctx->totals.ptr(), s);
@@ -1662,7 +1527,7 @@ int vgx_partition(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, ui
 			if (P > 1 && ndraws % P == 0 && ndraws / P >= nparts) { align = P; }
 		}
 	}
-	st = flattenCountBody(ctx, ps, draws, ndraws, s, false); // per-draw polyline vertex counts in dinfo
+	st = flattenCountBody(ctx, ps, draws, ndraws, s, nullptr); // per-draw polyline vertex counts in dinfo
 	if (st != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partBounds, ((size_t)nparts + 1) * 2 * sizeof(uint64_t))) != VGX_OK) { return st; }
 	OpPartWeight op;
@@ -1773,7 +1638,7 @@ static int runTmpl(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 
 static bool tmplFor(const vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws)
 {
-	return ctx->tmpl.on && ctx->optTmpl && ps == ctx->tmpl.ps && ps->gen == ctx->tmpl.psGen && ctx->tmpl.period && ndraws % ctx->tmpl.period == 0 && ndraws >= ctx->tmpl.period
+	return ctx->tmpl.on && ctx->opt.tmpl && ps == ctx->tmpl.ps && ps->gen == ctx->tmpl.psGen && ctx->tmpl.period && ndraws % ctx->tmpl.period == 0 && ndraws >= ctx->tmpl.period
 		&& (ctx->tmpl.classes == 1 || ndraws == ctx->tmpl.nDraws); // several classes: the per-instance table belongs to ONE batch size
 }
 
@@ -1782,16 +1647,14 @@ static bool tmplFor(const vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws)
 static int tmplPipeline(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* d, uint64_t n, hipStream_t s)
 {
 	int st;
-	if ((st = flattenCountBody(ctx, ps, d, n, s, false)) != VGX_OK) { return st; }
+	if ((st = flattenCountBody(ctx, ps, d, n, s, nullptr)) != VGX_OK) { return st; }
 	const vgx_sizes fsz = ctx->hostTotals->sizes;
 	if ((st = ensureMeshBuffers(ctx, fsz.num_poly_vertices, fsz.num_subpaths, fsz.num_meshes)) != VGX_OK) { return st; }
 	{
 		VgxFlattenArgs a = flattenArgs(ctx, ps, d, n, 0);
 		vgx_launch_flatten(true, a, VGX_GRID_BLOCKS, s);
 	}
-	VgxCaps outCaps = ctx->caps;
-	outCaps.vertices = ~0ull; outCaps.indices = ~0ull;
-	runStrokeCount(ctx, d, outCaps, 0, s);
+	runStrokeCount(ctx, d, sizingCaps(ctx), 0, s);
 	if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
 	if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
 	return VGX_OK;
@@ -1845,7 +1708,7 @@ static TmplStage tmplDetectPeriod(TmplJob& j)
 		// same paths and styles in the same order, only transforms and colours move -- a static scene under a moving camera, a culled or
 		// shuffled instanced scene) gets the whole draw list as ONE template of one instance: flattened once here, in local space; a step is
 		// then the emit kernel alone, and any structural change ends it with VGX_E_STALE (the caller counts again)
-		if (!ctx->optTmplBatch || j.ndraws >= (1ull << 31)) { return TMPL_ORDINARY; }
+		if (!ctx->opt.tmplBatch || j.ndraws >= (1ull << 31)) { return TMPL_ORDINARY; }
 		P = j.ndraws;
 		j.t.isBatch = true;
 		ctx->hostTotals->tmpl_bad = 0;
@@ -1861,7 +1724,7 @@ static TmplStage tmplClassify(TmplJob& j)
 	const uint64_t ninst = j.ninst;
 	j.T = 1; j.reps.assign(1, 0u);
 	if (!ctx->hostTotals->tmpl_bad) { return VGX_OK; }
-	if (!ctx->optTmplClasses || ninst > (1ull << 24)) { return TMPL_ORDINARY; } // (per-instance tables: 40 bytes per instance and tile on host and device)
+	if (!ctx->opt.tmplClasses || ninst > (1ull << 24)) { return TMPL_ORDINARY; } // (per-instance tables: 40 bytes per instance and tile on host and device)
 	int st;
 	if ((st = ensure(ctx, ctx->tmpl.hash, ninst)) != VGX_OK) { return st; }
 	noteHip(ctx, hipMemsetAsync(ctx->tmpl.hash.p, 0, ninst * sizeof(unsigned long long), j.s));
@@ -1899,9 +1762,9 @@ static TmplStage tmplRepresentatives(TmplJob& j)
 	if ((st = tmplPipeline(ctx, j.ps, ctx->tmpl.draws.ptr(), PT, j.s)) != VGX_OK) { return st; }
 	const VgxTotals& ht = *ctx->hostTotals;
 	if (j.T == 1) {
-		if (!vgx_tmpl_eligible(ht, ctx->optTmplRound != 0)) { return TMPL_ORDINARY; }
+		if (!vgx_tmpl_eligible(ht, ctx->opt.tmplRound != 0)) { return TMPL_ORDINARY; }
 		j.csz[0] = ht.sizes;
-	} else if ((ht.num_round_meshes && !ctx->optTmplRound) || ht.sizes.num_poly_vertices >= (1ull << 32) || ht.sizes.num_meshes >= (1ull << 32) || ht.sizes.num_elements >= (1ull << 36)) {
+	} else if ((ht.num_round_meshes && !ctx->opt.tmplRound) || ht.sizes.num_poly_vertices >= (1ull << 32) || ht.sizes.num_meshes >= (1ull << 32) || ht.sizes.num_elements >= (1ull << 36)) {
 		return TMPL_ORDINARY; // (the limits of one instance: per class, tmplBuildTables)
 	}
 	j.all = ht.sizes;
@@ -1929,7 +1792,7 @@ static TmplStage tmplChooseKernel(TmplJob& j)
 	j.t.kernel = vgx_tmpl_kernel_for(styles);
 	// (Round joins in a template of several classes: the per-step tables are addressed per instance -- VgxTmplInst::m / ::rel --, the sizes
 	// pass runs in its workgroup-per-instance shape; a batch that does not fit that shape takes the ordinary pipeline, tmplFirstRoundSizes)
-	j.t.tileSize = vgx_tmpl_tile_for(j.t.kernel, ctx->optTmplTile);
+	j.t.tileSize = vgx_tmpl_tile_for(j.t.kernel, ctx->opt.tmplTile);
 	return VGX_OK;
 }
 
@@ -2050,7 +1913,7 @@ static TmplStage tmplFirstRoundSizes(TmplJob& j)
 static int tryTemplate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, vgx_sizes* out_sizes, hipStream_t s)
 {
 	tmplDrop(ctx);
-	if (!ctx->optTmpl || !ctx->optInst || (ndraws <= VGX_SMALL_DRAWS && !ctx->optTmplBatch) || ndraws == 0) { return VGX_OK; } // (static batches: frame-sized draw lists too)
+	if (!ctx->opt.tmpl || !ctx->opt.inst || (ndraws <= VGX_SMALL_DRAWS && !ctx->opt.tmplBatch) || ndraws == 0) { return VGX_OK; } // (static batches: frame-sized draw lists too)
 	TmplJob j;
 	j.ctx = ctx; j.ps = ps; j.draws = draws; j.ndraws = ndraws; j.s = s;
 	memset(&j.t, 0, sizeof(j.t));
@@ -2079,47 +1942,34 @@ int vgx_tessellate_count(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* dr
 	}
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
+	ctx->counted.stage = VGX_COUNTED_NONE;
 	int st = tryTemplate(ctx, ps, draws, ndraws, out_sizes, s);
 	if (st != VGX_OK) { return st; }
 	if (ctx->tmpl.on) {
-		ctx->lastPs = ps; ctx->lastDraws = draws; ctx->lastNDraws = ndraws; ctx->lastStage = 2;
+		ctx->counted = VgxCounted{ ps, draws, ndraws, VGX_COUNTED_TESSELLATE };
 		return VGX_OK;
 	}
-	st = flattenCountBody(ctx, ps, draws, ndraws, s, true);
-	if (st != VGX_OK) { return st; }
+	VgxRouteFacts facts;
+	if ((st = flattenCountBody(ctx, ps, draws, ndraws, s, &facts)) != VGX_OK) { return st; }
+	// the sizes are known too: the route, its heap, its tables (one-walk: beyond frame size only, tables for whatever the draw buffers hold)
 	const vgx_sizes sz = ctx->hostTotals->sizes;
-	uint64_t heapVerts = heapBuildVerts(ps, sz.num_poly_vertices, sz.num_cmd_instances, ctx->hostTotals->long_subpath_vertices);
-	if (instPeriodFor(ctx, ndraws) || instGroupedFor(ctx, ps, ndraws)) {
-		const uint64_t instVerts = heapInstVerts(ctx, sz.num_poly_vertices, ctx->hostTotals->inst_long_subpath_vertices);
-		if (instVerts > heapVerts) { heapVerts = instVerts; }
-	}
-	if ((st = ensureMeshBuffers(ctx, heapVerts, sz.num_subpaths, sz.num_meshes)) != VGX_OK) { return st; }
-	// the one-walk route for vgx_tessellate's flatten stage? Unrelated draws (no instancing), curves (not a lineTo-only set), and long ones:
-	// >= 10 polyline vertices per command instance (VGX_TESS_FLAT1=2: whatever their length; the two routes cross between 7.5 and 12.6, profiles/experiments/r06_cubics_tessellate_boxes.txt). Sized here, so that the steady state allocates nothing.
-	ctx->f1Route = false;
-	if (ctx->optTessFlat1 && ndraws > VGX_SMALL_DRAWS && !instPeriodFor(ctx, ndraws) && !instGroupedFor(ctx, ps, ndraws)
-		&& !(ps->thinStatic && ctx->optThinStatic) && sz.num_cmd_instances != 0
-		&& (ctx->optTessFlat1 == 2 || sz.num_poly_vertices >= 10 * sz.num_cmd_instances)) {
-		int cap; uint32_t segMax;
-		f1Shape(ctx, sz.num_poly_vertices, sz.num_cmd_instances, &cap, &segMax);
-		bool ok;
-		if ((st = f1Reserve(ctx, ps, ctx->capDraws > ndraws ? ctx->capDraws : ndraws, cap, segMax, &ok)) != VGX_OK) { return st; }
-		ctx->f1Route = ok;
-	}
+	facts.sizesKnown = true; facts.V = sz.num_poly_vertices; facts.ncmd = sz.num_cmd_instances;
+	facts.longKnown = true; facts.longV = ctx->hostTotals->long_subpath_vertices; facts.instLongV = ctx->hostTotals->inst_long_subpath_vertices;
+	facts.f1Draws = ndraws <= VGX_SMALL_DRAWS ? 0 : (ctx->route.capDraws > ndraws ? ctx->route.capDraws : ndraws);
+	const VgxRoute route = vgx_route_choose(facts, ctx->opt, VGX_NO_HEAP_LIMIT);
+	if ((st = ensureMeshBuffers(ctx, route.heapVerts, sz.num_subpaths, sz.num_meshes)) != VGX_OK) { return st; }
+	if ((st = adoptRoute(ctx, ps, ndraws, route)) != VGX_OK) { return st; }
 	VgxFlattenArgs a = flattenArgs(ctx, ps, draws, ndraws, 1);
 	vgx_launch_flatten(true, a, VGX_GRID_BLOCKS, s);
 	mark(ctx, s, "flatten_emit");
-	VgxCaps outCaps = ctx->caps;
-	outCaps.vertices = ~0ull; outCaps.indices = ~0ull;
-	runStrokeCount(ctx, draws, outCaps, 0, s);
+	runStrokeCount(ctx, draws, sizingCaps(ctx), 0, s);
 	if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
 	*out_sizes = ctx->hostTotals->sizes;
 	if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; } // _emit must not follow a failed count
-	ctx->lastPs = ps; ctx->lastDraws = draws; ctx->lastNDraws = ndraws; ctx->lastStage = 2;
+	ctx->counted = VgxCounted{ ps, draws, ndraws, VGX_COUNTED_TESSELLATE };
 	// what the scan over the counted meshes found: a batch with open / Bevel / Round / non-AA strokes is k_fill's and k_stroke's, and the
 	// calls that follow a count like that do not launch the tile kernel at all (its 200 000 workgroups would only find that out again)
-	ctx->tileHint = ctx->hostTotals->has_general_stroke == 0u;
+	ctx->route.tileHint = ctx->hostTotals->has_general_stroke == 0u;
 	return VGX_OK;
 }
 
@@ -2129,7 +1979,7 @@ int vgx_tessellate_emit(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* dra
 	if (!ctx || !ps || !out || (!draws && ndraws) || !out->pos || !out->color || !out->idx || meshOutMisaligned(out)) {
 		return VGX_E_INVALID_ARG;
 	}
-	if (ctx->lastStage != 2 || ctx->lastPs != ps || ctx->lastDraws != draws || ctx->lastNDraws != ndraws) {
+	if (!followsCount(ctx, VGX_COUNTED_TESSELLATE, ps, draws, ndraws)) {
 		return VGX_E_INVALID_ARG; // must follow vgx_tessellate_count on the same batch
 	}
 	const vgx_sizes& sz = ctx->hostTotals->sizes;
@@ -2151,29 +2001,22 @@ int vgx_tessellate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 	if (tmplFor(ctx, ps, ndraws)) {
 		hipStream_t s = (hipStream_t)stream;
 		markBegin(ctx, s);
-		ctx->lastStage = 0;
+		ctx->counted.stage = VGX_COUNTED_NONE;
 		return runTmpl(ctx, ps, draws, ndraws, out, dev_sizes, dev_status, s);
 	}
-	if (ndraws > ctx->capDraws || !ctx->cmdCnt.p || !ctx->subFirst.p || !ctx->poly.p || !ctx->mtab.p) {
+	if (ndraws > ctx->route.capDraws || !ctx->cmdCnt.p || !ctx->subFirst.p || !ctx->poly.p || !ctx->mtab.p) {
 		return VGX_E_NOSPACE; // scratch was never sized for a batch like this: run vgx_tessellate_count once
 	}
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
-	if (ndraws <= VGX_SMALL_DRAWS && !ctx->optNoSmall) { // (round 6: also with draw-command assembly armed -- runStrokeEmit runs the partition kernels in front of the emit either way)
+	ctx->counted.stage = VGX_COUNTED_NONE;
+	if (ndraws <= VGX_SMALL_DRAWS && !ctx->opt.noSmall) { // (round 6: also with draw-command assembly armed -- runStrokeEmit runs the partition kernels in front of the emit either way)
 		const int est = runFrameSized(ctx, ps, draws, ndraws, out, 0, dev_sizes, dev_status, s);
 		if (est != VGX_OK) { return est; }
 		if (ctx->asmArmed) { publish(ctx, dev_sizes, dev_status, s); } // the partition kernels may have ended the call (a mesh beyond any vertex buffer, the command table full): the verdict once more
 		return launchStatus(ctx);
 	}
-	const bool oneWalk = ctx->f1Route && ps == ctx->f1RoutePs && ps->gen == ctx->f1RoutePsGen && !instPeriodFor(ctx, ndraws) && !instGroupedFor(ctx, ps, ndraws)
-		&& f1RouteSegmentsFor(ps, ndraws, ctx->f1RouteSegMax) <= ctx->f1RouteSegBound; // (what the last count decided and sized, for this path set)
-	if (!oneWalk) { runCmdPrefix(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, s, instPeriodFor(ctx, ndraws)); }
-	if (oneWalk) {
-		runFlattenOneWalk(ctx, ps, draws, ndraws, s);
-	} else {
-		runFlattenBuild(ctx, ps, draws, ndraws, s);
-	}
+	runFlattenStage(ctx, ps, draws, ndraws, s);
 	runStrokeCount(ctx, draws, outCapsFor(ctx, out), 1, s, nullptr, true, out->meshes);
 	{
 		const int st = runStrokeEmit(ctx, draws, out, s, nullptr, true);
@@ -2188,33 +2031,41 @@ int vgx_tessellate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, u
 // needs -- grown here, the instanced flatten's heap included when its draws reuse paths
 static int immConsume(vgx_ctx* ctx, const vgx_pathset* ps)
 {
-	if (!ctx->imm.landed()) { return VGX_OK; }
-	const VgxTotals& h = *ctx->imm.host;
+	VgxImmState& im = ctx->imm;
+	if (!im.mirror.landed()) { return VGX_OK; }
+	const VgxTotals& h = *im.mirror.host;
 	if (h.status != VGX_OK && h.status != VGX_E_NOSPACE && h.status != VGX_E_GROWN) { return VGX_OK; } // (no totals to learn from)
-	const bool same = ctx->immKnown && ctx->immTag == ctx->immPendTag;
-	uint32_t P = 0;
-	if (ctx->immPendDetect && h.inst_detect_inv != 0 && !h.inst_detect_bad) {
-		const unsigned long long p = ~0ull - h.inst_detect_inv;
-		if (p <= 0xFFFFFFFFull) { P = (uint32_t)p; }
+	const bool same = im.known && im.tag == im.pendTag;
+	VgxRouteFacts& f = im.facts;
+	if (im.pendDetect || !same) { // (else: the period and the paths of the batch are what an earlier call found)
+		f.period = im.pendDetect ? vgx_period_decode(h.inst_detect_inv, h.inst_detect_bad) : 0;
+		f.distinct = im.pendDetect ? h.inst_distinct : 0;
 	}
-	if (ctx->immPendDetect || !same) { ctx->immPeriod = P; ctx->immDistinct = ctx->immPendDetect ? h.inst_distinct : 0; } else { P = ctx->immPeriod; }
-	ctx->immKnown = true; ctx->immTag = ctx->immPendTag;
-	ctx->immV = h.sizes.num_poly_vertices; ctx->immCmd = h.sizes.num_cmd_instances;
+	im.known = true; im.tag = im.pendTag;
+	f.ndraws = im.pendNDraws; f.thinStatic = ps->thinStatic;
+	f.sizesKnown = true; f.V = h.sizes.num_poly_vertices; f.ncmd = h.sizes.num_cmd_instances;
 	if (h.status != VGX_E_GROWN || !h.scratch_short) { // (VGX_E_GROWN without the flag: vgx_tessellate_dashed's pieces outgrew their scratch, the flatten stage fitted)
-		if (!same) { ctx->immLongKnown = false; }
+		if (!same) { f.longKnown = false; }
 		return VGX_OK;
 	}
-	ctx->immLong = h.imm_long_subpath_vertices; ctx->immInstLong = h.imm_inst_long_subpath_vertices; ctx->immLongKnown = true;
+	f.longV = h.imm_long_subpath_vertices; f.instLongV = h.imm_inst_long_subpath_vertices; f.longKnown = true;
 	if (h.sizes.num_poly_vertices > 0xFFFFFFF0ull) { return VGX_OK; } // (VGX_E_RANGE territory: nothing sensible to grow to)
 	int st;
 	if ((st = ensureCmdScratch(ctx, h.sizes.num_cmd_instances)) != VGX_OK) { return st; }
-	uint64_t heap = heapBuildVerts(ps, h.sizes.num_poly_vertices, h.sizes.num_cmd_instances, h.imm_long_subpath_vertices);
-	const uint64_t n = ctx->immPendNDraws;
-	if (periodUsable(ctx, P, n) || pathsReused(ctx, n, ctx->immDistinct)) {
-		const uint64_t hi = heapInstVerts(ctx, h.sizes.num_poly_vertices, h.imm_inst_long_subpath_vertices);
-		if (hi > heap) { heap = hi; }
-	}
-	return ensureMeshBuffers(ctx, heap, h.sizes.num_subpaths, h.sizes.num_meshes);
+	return ensureMeshBuffers(ctx, vgx_route_heap_verts(f, ctx->opt), h.sizes.num_subpaths, h.sizes.num_meshes);
+}
+
+// What vgx_tessellate_immediate and vgx_tessellate_dashed begin with: counted state ends (the _emit pairing, the template, the chosen routes); the last
+// call's need, when it has reached the mirror; the tables every route needs (a fresh context gets small ones and learns the need from VGX_E_GROWN)
+static int immBegin(vgx_ctx* ctx, const vgx_pathset* ps, uint64_t ndraws)
+{
+	int st;
+	if ((st = ctx->imm.mirror.create(ctx, 1)) != VGX_OK) { return st; }
+	ctx->counted.stage = VGX_COUNTED_NONE;
+	forgetRoutes(ctx);
+	if ((st = immConsume(ctx, ps)) != VGX_OK) { return st; }
+	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
+	return ensureCmdScratch(ctx, 4096);
 }
 
 int vgx_reserve(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals)
@@ -2225,12 +2076,12 @@ int vgx_reserve(vgx_ctx* ctx, uint64_t ndraws, const vgx_sizes* totals)
 	DeviceGuard guard(ctx);
 	if (totals->num_poly_vertices > 0xFFFFFFF0ull || totals->num_cmd_instances > 0xFFFFFFF0ull) { return VGX_E_RANGE; }
 	int st;
-	if ((st = ctx->imm.create(ctx, 1)) != VGX_OK) { return st; }
+	if ((st = ctx->imm.mirror.create(ctx, 1)) != VGX_OK) { return st; }
 	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
 	if ((st = ensureCmdScratch(ctx, totals->num_cmd_instances)) != VGX_OK) { return st; }
 	// the long sub-paths are not known: every vertex counted as one of them (the heap then holds any batch within these totals)
 	const uint64_t V = totals->num_poly_vertices;
-	return ensureMeshBuffers(ctx, heapBuildVerts(nullptr, V, totals->num_cmd_instances, V), totals->num_subpaths, totals->num_meshes);
+	return ensureMeshBuffers(ctx, vgx_heap_build_verts(true, V, totals->num_cmd_instances, V), totals->num_subpaths, totals->num_meshes);
 }
 
 int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* draws, uint64_t ndraws, const vgx_mesh_out* out,
@@ -2242,55 +2093,29 @@ int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw
 	DeviceGuard guard(ctx);
 	hipStream_t s = (hipStream_t)stream;
 	int st;
-	if ((st = ctx->imm.create(ctx, 1)) != VGX_OK) { return st; }
-	// counted state ends here (as with vgx_flatten): the _emit pairing, the template, the routes the last count chose
-	ctx->lastStage = 0; ctx->f1Route = false;
-	forgetRoutes(ctx);
-	// (1) the last immediate call's need, when it has reached the mirror; (2) the tables every route needs (a fresh context gets small ones:
-	// its first call ends with VGX_E_GROWN and the exact need)
-	if ((st = immConsume(ctx, ps)) != VGX_OK) { return st; }
-	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
-	if ((st = ensureCmdScratch(ctx, 4096)) != VGX_OK) { return st; }
+	if ((st = immBegin(ctx, ps, ndraws)) != VGX_OK) { return st; }
 	if ((st = ensureMeshBuffers(ctx, 4096, 1024, 1024)) != VGX_OK) { return st; }
 	markBegin(ctx, s);
-	const uint64_t tag = ps->gen * 0x9E3779B97F4A7C15ull + ndraws;
-	const bool known = ctx->immKnown && ctx->immTag == tag;
+	const uint64_t tag = vgx_batch_tag(ps->gen, ndraws);
+	const bool known = ctx->imm.known && ctx->imm.tag == tag;
 	VgxTotals* T = ctx->totals.ptr();
 	bool detect = false;
-	if (ndraws <= VGX_SMALL_DRAWS && !ctx->optNoSmall) {
+	// The route by vgx_tessellate_count's rules, from what the last immediate call on this batch found (a batch not seen before: only its size)
+	VgxRouteFacts f = routeFacts(known ? ctx->imm.facts : VgxRouteFacts(), ps, ndraws);
+	f.f1Draws = known ? ndraws : 0; f.oneBatch = true;
+	const VgxRoute route = vgx_route_choose(f, ctx->opt, ctx->caps.poly_vertices);
+	if (route.kind == VGX_ROUTE_FRAME) {
 		// frame-sized: vgx_tessellate's five launches; the scan over the draws flags a batch that outgrew the context's tables
 		mark(ctx, s, "route_frame"); // (a stage of no length: which route the call took, for the profile)
 		if ((st = runFrameSized(ctx, ps, draws, ndraws, out, 1, nullptr, nullptr, s)) != VGX_OK) { return st; }
 		vgx_launch_imm_size(ps->dev, draws, ndraws, T, 0, true, dev_sizes, dev_status, s); // (+ the verdict)
 		mark(ctx, s, "imm_size");
 	} else {
-		// Routes from what the last immediate call on this (path set, number of draws) found, with vgx_tessellate_count's rules: draws that
-		// repeat a sequence of paths -> k_flatten_inst (re-checked on the device: k_flatten_build takes over when they stop repeating), when
-		// the heap holds its lane-private blocks; long curves -> the one-walk flatten; else k_flatten_build
-		const bool instFits = heapInstVerts(ctx, ctx->immV, ctx->immLongKnown ? ctx->immInstLong : ctx->immV) <= ctx->caps.poly_vertices;
-		const uint32_t P = known && instFits && periodUsable(ctx, ctx->immPeriod, ndraws) ? ctx->immPeriod : 0;
-		// paths reused without a period: grouped mode, the draws sorted by path on the device every call
-		if (!P && known && instFits && pathsReused(ctx, ndraws, ctx->immDistinct)) {
-			if ((st = ensureInstGroup(ctx, ps->dev.npaths, 1, ndraws, true)) != VGX_OK) { return st; }
-			ctx->instGrouped = 1;
-			if (!instGroupedFor(ctx, ps, ndraws)) { ctx->instGrouped = 0; }
-		}
-		bool oneWalk = false;
-		if (!P && !ctx->instGrouped && known && ctx->optTessFlat1 && !(ps->thinStatic && ctx->optThinStatic) && ctx->immCmd != 0
-			&& (ctx->optTessFlat1 == 2 || ctx->immV >= 10 * ctx->immCmd)) {
-			int cap; uint32_t segMax;
-			f1Shape(ctx, ctx->immV, ctx->immCmd, &cap, &segMax);
-			if ((st = f1Reserve(ctx, ps, ndraws, cap, segMax, &oneWalk)) != VGX_OK) { return st; }
-		}
-		ctx->instPeriod = P;
-		mark(ctx, s, P ? "route_periodic" : (ctx->instGrouped ? "route_grouped" : (oneWalk ? "route_one_walk" : "route_build"))); // (no length)
-		if (oneWalk) {
-			runFlattenOneWalk(ctx, ps, draws, ndraws, s);
-		} else {
-			runCmdPrefix(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, s, P);
-			runFlattenBuild(ctx, ps, draws, ndraws, s);
-		}
-		detect = !known && ctx->optInst; // the period of the paths and how many of them the draws use, for the next call on this batch
+		if ((st = adoptRoute(ctx, ps, ndraws, route)) != VGX_OK) { return st; }
+		mark(ctx, s, route.kind == VGX_ROUTE_PERIODIC ? "route_periodic" : (route.kind == VGX_ROUTE_GROUPED ? "route_grouped" : (route.kind == VGX_ROUTE_ONE_WALK ? "route_one_walk" : "route_build"))); // (no length)
+		runFlattenStage(ctx, ps, draws, ndraws, s);
+		if (route.kind == VGX_ROUTE_ONE_WALK) { ctx->route.chosen.kind = VGX_ROUTE_BUILD; } // (this call's alone: only a count leaves a one-walk route for vgx_tessellate)
+		detect = !known && ctx->opt.inst; // the period of the paths and how many of them the draws use, for the next call on this batch
 		if (detect) {
 			vgx_launch_inst_detect(draws, ndraws, T, s);
 			if ((st = ensureInstGroup(ctx, ps->dev.npaths, 1, ndraws, false)) != VGX_OK) { return st; }
@@ -2305,12 +2130,28 @@ int vgx_tessellate_immediate(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw
 		vgx_launch_imm_publish(T, dev_sizes, dev_status, s);
 	}
 	// the totals to the mirror, for the next call (never waited for)
-	ctx->imm.push(ctx, T, s);
-	ctx->immPendTag = tag; ctx->immPendNDraws = ndraws; ctx->immPendDetect = detect;
+	ctx->imm.mirror.push(ctx, T, s);
+	ctx->imm.pendTag = tag; ctx->imm.pendNDraws = ndraws; ctx->imm.pendDetect = detect;
 	return launchStatus(ctx);
 }
 
 // ---- stroker-level entry ------------------------------------------------------------------------------
+// The mesh descriptors of the caller's vertex lists: at most two meshes per list, so the scratch is sized without a device round trip
+static int scanSubpathMeshes(vgx_ctx* ctx, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths, const vgx_draw* draws, uint64_t ndraws, hipStream_t s)
+{
+	int st;
+	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
+	if ((st = ensureMeshBuffers(ctx, 0, 0, 2 * nsubpaths)) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
+	OpSubMeshes op;
+	op.subs = subpaths; op.subDraw = subpath_draw; op.draws = draws; op.nsubs = nsubpaths; op.ndraws = ndraws;
+	op.mdesc = ctx->mdesc.ptr(); op.mtab = ctx->mtab.ptr(); op.totals = ctx->totals.ptr();
+	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, nsubpaths);
+	mark(ctx, s, "scan_subpath_meshes");
+	return VGX_OK;
+}
+
 int vgx_stroke_count(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths, const vgx_draw* draws, uint64_t ndraws, vgx_sizes* out_sizes, void* stream)
 {
 	DeviceGuard guard(ctx);
@@ -2319,25 +2160,14 @@ int vgx_stroke_count(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpath
 	}
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
+	ctx->counted.stage = VGX_COUNTED_NONE;
 	int st;
-	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
-	// at most two meshes per vertex list: scratch can be sized without a device round trip
-	if ((st = ensureMeshBuffers(ctx, 0, 0, 2 * nsubpaths)) != VGX_OK) { return st; }
-	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
-	OpSubMeshes op;
-	op.subs = subpaths; op.subDraw = subpath_draw; op.draws = draws; op.nsubs = nsubpaths; op.ndraws = ndraws;
-	op.mdesc = ctx->mdesc.ptr(); op.mtab = ctx->mtab.ptr(); op.totals = ctx->totals.ptr();
-	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, nsubpaths);
-	mark(ctx, s, "scan_subpath_meshes");
-	VgxCaps outCaps = ctx->caps;
-	outCaps.vertices = ~0ull; outCaps.indices = ~0ull;
-	runStrokeCount(ctx, draws, outCaps, 0, s, poly);
+	if ((st = scanSubpathMeshes(ctx, subpaths, subpath_draw, nsubpaths, draws, ndraws, s)) != VGX_OK) { return st; }
+	runStrokeCount(ctx, draws, sizingCaps(ctx), 0, s, poly);
 	if ((st = readTotals(ctx, s)) != VGX_OK) { return st; }
 	*out_sizes = ctx->hostTotals->sizes;
 	if (ctx->hostTotals->status != VGX_OK) { return (int)ctx->hostTotals->status; }
-	ctx->lastPs = nullptr; ctx->lastDraws = draws; ctx->lastNDraws = nsubpaths; ctx->lastStage = 3;
+	ctx->counted = VgxCounted{ nullptr, draws, nsubpaths, VGX_COUNTED_STROKE };
 	return VGX_OK;
 }
 
@@ -2348,7 +2178,7 @@ int vgx_stroke_emit(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths
 	if (!ctx || !out || !out->pos || !out->color || !out->idx || meshOutMisaligned(out)) {
 		return VGX_E_INVALID_ARG;
 	}
-	if (ctx->lastStage != 3 || ctx->lastDraws != draws || ctx->lastNDraws != nsubpaths) {
+	if (!followsCount(ctx, VGX_COUNTED_STROKE, nullptr, draws, nsubpaths)) {
 		return VGX_E_INVALID_ARG; // must follow vgx_stroke_count on the same batch
 	}
 	const vgx_sizes& sz = ctx->hostTotals->sizes;
@@ -2360,7 +2190,6 @@ int vgx_stroke_emit(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths
 	return runStrokeEmit(ctx, draws, out, s, poly);
 }
 
-
 int vgx_stroke(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const uint32_t* subpath_draw, uint64_t nsubpaths, const vgx_draw* draws, uint64_t ndraws,
                const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
 {
@@ -2370,19 +2199,10 @@ int vgx_stroke(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, con
 	DeviceGuard guard(ctx);
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0; // counted state ends here
+	ctx->counted.stage = VGX_COUNTED_NONE; // counted state ends here
 	tmplDrop(ctx);
 	int st;
-	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
-	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
-	// at most two meshes per vertex list: scratch is sized without a device round trip
-	if ((st = ensureMeshBuffers(ctx, 0, 0, 2 * nsubpaths)) != VGX_OK) { return st; }
-	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
-	OpSubMeshes op;
-	op.subs = subpaths; op.subDraw = subpath_draw; op.draws = draws; op.nsubs = nsubpaths; op.ndraws = ndraws;
-	op.mdesc = ctx->mdesc.ptr(); op.mtab = ctx->mtab.ptr(); op.totals = ctx->totals.ptr();
-	vgx_device_scan(op, (Sum3*)ctx->partial.p, s, nsubpaths);
-	mark(ctx, s, "scan_subpath_meshes");
+	if ((st = scanSubpathMeshes(ctx, subpaths, subpath_draw, nsubpaths, draws, ndraws, s)) != VGX_OK) { return st; }
 	runStrokeCount(ctx, draws, outCapsFor(ctx, out), 1, s, poly, false, out->meshes); // sizes, places, the caller's capacities, its mesh table
 	if ((st = runStrokeEmit(ctx, draws, out, s, poly, true)) != VGX_OK) { return st; }
 	publish(ctx, dev_sizes, dev_status, s);
@@ -2419,7 +2239,7 @@ int dashPrepare(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, co
 	if ((nsubpaths && (!poly || !subpaths || !subpath_draw || !dashes || !ndraws)) || (ndraws && !dashes) || (npattern && !pattern)) { return VGX_E_INVALID_ARG; }
 	if (((uintptr_t)poly & 7u) || ((uintptr_t)subpaths & 7u) || ((uintptr_t)subpath_draw & 3u) || ((uintptr_t)dashes & 3u) || ((uintptr_t)pattern & 3u)) { return VGX_E_INVALID_ARG; }
 	if (nsubpaths > 0x7FFFFFFFull || ndraws > 0xFFFFFFFFull) { return VGX_E_RANGE; }
-	ctx->lastStage = 0;
+	ctx->counted.stage = VGX_COUNTED_NONE;
 	tmplDrop(ctx);
 	int st;
 	if ((st = ctx->dash.create(ctx, 1)) != VGX_OK) { return st; }
@@ -2497,7 +2317,6 @@ int vgx_dash(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const
 	return launchStatus(ctx);
 }
 
-
 // ---- dashed strokes in frames: vgx_tessellate_dashed / vgx_reserve_dashed -------------------------------------------------------
 namespace {
 
@@ -2565,31 +2384,21 @@ int vgx_tessellate_dashed(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* d
 	DeviceGuard guard(ctx);
 	hipStream_t s = (hipStream_t)stream;
 	int st;
-	if ((st = ctx->imm.create(ctx, 1)) != VGX_OK) { return st; }
 	if ((st = ctx->df.create(ctx, 4)) != VGX_OK) { return st; }
-	// counted state ends here, as with vgx_tessellate_immediate
-	ctx->lastStage = 0; ctx->f1Route = false;
-	forgetRoutes(ctx);
-	// (1) what the last calls left in the mirrors, once it has arrived: the flatten stage's need (immConsume), the pieces', the segments'
-	// (dashPrepare); (2) the tables every call needs (a fresh context gets small ones and learns the need from its first calls)
-	if ((st = immConsume(ctx, ps)) != VGX_OK) { return st; }
+	if ((st = immBegin(ctx, ps, ndraws)) != VGX_OK) { return st; }
 	uint64_t needMeshes = 1024, needPieces = 4096, needPieceVerts = 16384;
 	if (ctx->df.landed() && ctx->df.host[3]) { needPieces = ctx->df.host[0]; needPieceVerts = ctx->df.host[1]; needMeshes = ctx->df.host[2] + ctx->df.host[0]; }
-	if ((st = ensureDrawBuffers(ctx, ndraws)) != VGX_OK) { return st; }
-	if ((st = ensureCmdScratch(ctx, 4096)) != VGX_OK) { return st; }
 	if ((st = dfEnsure(ctx, needMeshes, needPieces, needPieceVerts)) != VGX_OK) { return st; }
-	const uint64_t tag = ps->gen * 0x9E3779B97F4A7C15ull + ndraws;
-	const uint64_t segGuess = (ctx->immKnown && ctx->immTag == tag && ctx->immV > 65536) ? ctx->immV : 65536; // (segments <= vertices of the source lists)
+	const uint64_t tag = vgx_batch_tag(ps->gen, ndraws);
+	const uint64_t segGuess = (ctx->imm.known && ctx->imm.tag == tag && ctx->imm.facts.V > 65536) ? ctx->imm.facts.V : 65536; // (segments <= vertices of the source lists)
 	VgxDashArgs a;
 	if ((st = dashPrepare(ctx, (const float*)ctx->poly.p, ctx->dfLists.ptr(), ctx->dfListDraw.ptr(), ctx->caps.meshes,
 	                      dashes, ndraws, pattern, npattern, segGuess, &a)) != VGX_OK) { return st; }
 	markBegin(ctx, s);
 	VgxTotals* T = ctx->totals.ptr();
 	// the flatten stage: k_flatten_build for any number of draws (its descriptors are complete and in frame order, the exact builder's included)
-	ctx->instPeriod = 0;
 	mark(ctx, s, "route_build");
-	runCmdPrefix(ctx, ps, draws, ndraws, ctx->caps.cmd_instances, s, 0);
-	runFlattenBuild(ctx, ps, draws, ndraws, s);
+	runFlattenStage(ctx, ps, draws, ndraws, s); // (no route chosen: the build route, period 0)
 	vgx_launch_imm_size(ps->dev, draws, ndraws, T, 1, false, nullptr, nullptr, s); // (a VGX_E_NOSPACE here is the scratch's)
 	mark(ctx, s, "imm_size");
 	// the dash pass over the stroke meshes of the dashed draws, pieces into the tail of the polyline scratch
@@ -2625,8 +2434,8 @@ int vgx_tessellate_dashed(vgx_ctx* ctx, const vgx_pathset* ps, const vgx_draw* d
 	if ((st = runStrokeEmit(ctx, draws, out, s, nullptr, true)) != VGX_OK) { return st; }
 	vgx_launch_imm_publish(T, dev_sizes, dev_status, s);
 	// the totals and the pieces' need to the mirrors, for the next call (never waited for)
-	ctx->imm.push(ctx, T, s);
-	ctx->immPendTag = tag; ctx->immPendNDraws = ndraws; ctx->immPendDetect = false;
+	ctx->imm.mirror.push(ctx, T, s);
+	ctx->imm.pendTag = tag; ctx->imm.pendNDraws = ndraws; ctx->imm.pendDetect = false;
 	ctx->df.push(ctx, ctx->dfNeed.p, s);
 	return launchStatus(ctx);
 }
@@ -2661,7 +2470,7 @@ int vgx_cache_submit(vgx_ctx* ctx, const vgx_cache_desc* cache, const vgx_cache_
 	}
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
+	ctx->counted.stage = VGX_COUNTED_NONE;
 	int st;
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
@@ -2778,7 +2587,7 @@ int vgx_pick(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds
 	a.mesh_bounds = mesh_bounds; a.queries = queries; a.nqueries = nqueries; a.hits = hits;
 	a.keys = ctx->pickKeys.ptr(); a.cand_tris = ctx->pickTris.ptr(); a.cand_mesh = ctx->pickCand.ptr();
 	a.cand_prefix = ctx->pickPrefix.ptr(); a.totals = ctx->pickTotals.ptr();
-	vgx_launch_pick(a, ctx->pickPartial.p, ctx->optPickGrid, s);
+	vgx_launch_pick(a, ctx->pickPartial.p, ctx->opt.pickGrid, s);
 	return launchStatus(ctx);
 }
 
@@ -2815,7 +2624,7 @@ int vgx_pick_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_
 	a.queries = queries; a.nqueries = nqueries; a.hits = hits; a.status = dev_status;
 	a.mesh_state = ctx->pickfState.ptr(); a.cand_mesh = ctx->pickfCand.ptr(); a.tri_cand = ctx->pickfTriCand.ptr(); a.tri_prefix = ctx->pickfPrefix.ptr();
 	a.con_cand = ctx->pickfConCand.ptr(); a.cover = ctx->pickfCover.ptr(); a.totals = ctx->pickfTotals.ptr();
-	vgx_launch_pick_frame(a, ctx->pickfPartial.p, ctx->optPickGrid, s);
+	vgx_launch_pick_frame(a, ctx->pickfPartial.p, ctx->opt.pickGrid, s);
 	return launchStatus(ctx);
 }
 
@@ -3051,7 +2860,6 @@ int vgx_raster_painted(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* m
 	return rasterCall(VGX_RL_PAINTED, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, nullptr, dev_status, stream);
 }
 
-// HOST only, no context: the decoder's paint list scattered by handle into the two tables vgx_raster_painted indexes; holes marked
 int vgx_raster_concave(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                        const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints, const vgx_raster_target* target,
                        uint32_t* dev_status, void* stream)
@@ -3059,6 +2867,7 @@ int vgx_raster_concave(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* m
 	return rasterCall(VGX_RL_CONCAVE, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, nullptr, dev_status, stream);
 }
 
+// HOST only, no context: the decoder's paint list scattered by handle into the two tables vgx_raster_painted indexes; holes marked
 int vgx_paint_tables(const vgx_paint* paints, uint32_t n, vgx_paint* gradients, uint32_t cap_gradients, vgx_paint* patterns, uint32_t cap_patterns)
 {
 	if ((n && !paints) || (cap_gradients && !gradients) || (cap_patterns && !patterns)) { return VGX_E_INVALID_ARG; }
@@ -3143,7 +2952,7 @@ int mergeCall(vgx_ctx* ctx, const vgx_cache_desc* a, const vgx_cache_desc* b, co
 	if (n >= 0x7FFFFFFFull) { return VGX_E_RANGE; }
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
+	ctx->counted.stage = VGX_COUNTED_NONE;
 	tmplDrop(ctx); // the mesh-table scratch is re-sized below
 	int st;
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
@@ -3241,7 +3050,7 @@ int vgx_concave_emit(vgx_ctx* ctx, const float* contour_verts, uint64_t num_cont
 	}
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
+	ctx->counted.stage = VGX_COUNTED_NONE;
 	int st;
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
@@ -3277,7 +3086,7 @@ int vgx_concave_contours(vgx_ctx* ctx, const float* poly, const vgx_subpath* sub
 	if (ndraws >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
+	ctx->counted.stage = VGX_COUNTED_NONE;
 	int st;
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
@@ -3321,7 +3130,7 @@ int vgx_text_quads(vgx_ctx* ctx, const float* quads, uint64_t nquads, const vgx_
 	if (nquads > 0x7FFFFFFFull || nruns > 0x7FFFFFFFull) { return VGX_E_RANGE; }
 	hipStream_t s = (hipStream_t)stream;
 	markBegin(ctx, s);
-	ctx->lastStage = 0;
+	ctx->counted.stage = VGX_COUNTED_NONE;
 	int st;
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	VgxTextArgs a;
@@ -3358,8 +3167,9 @@ int vgx_get_failure_info(vgx_ctx* ctx, vgx_failure_info* out, void* stream)
 	out->reason = ctx->hostTotals->fail_reason;
 	out->aux = ctx->hostTotals->fail_aux;
 	out->segment = ctx->hostTotals->fail_segment;
-	out->segment_items = ctx->tmpl.on ? 5u : ctx->optInst ? (ctx->instPeriod ? (ctx->instPermOn ? 4u : 1u) : (ctx->instGrouped ? (ctx->instClasses > 1 ? 3u : 2u) : 0u)) : 0u; // flatten mode chosen by the last count call
-	if (out->segment_items == 0u && ctx->lastPs && ctx->lastPs->thinStatic && ctx->optThinStatic) { out->segment_items = 6u; } // k_flatten_thin in k_flatten_build's place
+	const VgxRoute& r = ctx->route.chosen;
+	out->segment_items = ctx->tmpl.on ? 5u : ctx->opt.inst ? (r.period ? (r.permute ? 4u : 1u) : (r.kind == VGX_ROUTE_GROUPED ? (r.classes > 1 ? 3u : 2u) : 0u)) : 0u; // flatten mode chosen by the last count call
+	if (out->segment_items == 0u && ctx->counted.ps && ctx->counted.ps->thinStatic && ctx->opt.thinStatic) { out->segment_items = 6u; } // k_flatten_thin in k_flatten_build's place
 	for (int i = 0; i < 16; ++i) { out->prof[i] = ctx->hostTotals->prof[i]; }
 	return VGX_OK;
 }
@@ -3369,7 +3179,7 @@ int vgx_set_static_batches(vgx_ctx* ctx, int enable)
 	if (!ctx) {
 		return VGX_E_INVALID_ARG;
 	}
-	ctx->optTmplBatch = enable ? 1 : 0;
+	ctx->opt.tmplBatch = enable ? 1 : 0;
 	if (!enable && ctx->tmpl.isBatch) { tmplDrop(ctx); } // the next vgx_tessellate wants a count again
 	return VGX_OK;
 }
