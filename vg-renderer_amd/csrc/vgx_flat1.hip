@@ -34,6 +34,7 @@
 #include "vgx_wave.h"
 #include "vgx_pathsim.h"
 #include "vgx_walk.h"
+#include "vgx_chunk.h"
 #include "vgx_flat1.h"
 
 namespace {
@@ -520,21 +521,17 @@ __global__ __launch_bounds__(VGX_WAVE, (CAP > 2048 ? 1 : F1_MIN_WAVES_PER_EU)) v
 				for (uint64_t e = d; e > 0 && A.cmd_prefix[e - 1] == ownerBase; --e) { A.dinfo[e - 1] = de; }
 			}
 			if (valid && drawLast) {
-				vgx_draw_info di;
 				if (serialDraw) {
+					vgx_draw_info di;
 					di.num_poly_vertices = serV; di.num_subpaths = serS; di.num_meshes = serM; di.flags = serF; // counts from k_flatten_serial<count>; places from here
 					di.first_poly_vertex = (uint64_t)gl;
 					di.first_subpath = subsGlobalIncl - serS;
 					di.first_mesh = meshGlobalIncl - serM;
 					A.dinfo[d] = di;
 				} else if (!slowDraw) {
-					di.first_poly_vertex = (uint64_t)(gl - (long long)inDrawBefore);
+					vgx_draw_info di = draw_info_for(false, (uint64_t)(gl - (long long)inDrawBefore), inDrawBefore + cnt, subsIncl, fillIncl, strokeIncl);
 					di.first_subpath = subsGlobalIncl - (uint64_t)subsIncl;
 					di.first_mesh = meshGlobalIncl - (uint64_t)(fillIncl + strokeIncl);
-					di.num_poly_vertices = (uint32_t)(inDrawBefore + cnt);
-					di.num_subpaths = (uint32_t)subsIncl;
-					di.num_meshes = (uint32_t)(fillIncl + strokeIncl);
-					di.flags = ((uint32_t)fillIncl << 1);
 					A.dinfo[d] = di;
 				}
 			}
@@ -567,67 +564,30 @@ __global__ __launch_bounds__(VGX_WAVE, (CAP > 2048 ? 1 : F1_MIN_WAVES_PER_EU)) v
 			const bool stage = pass == 1;
 			long long runV = 0; uint64_t runS = 0, runM = 0;  // placed in front of the current chunk, inside the segment
 			uint64_t dcur = d0;
-			int carryDrawVerts = 0, carrySpVerts = 0, carrySubs = 0, carryFill = 0, carryStroke = 0, carrySlow = 0, carrySpExists = 0;
+			ChunkCarry K;
 			wbase = d0; W = W0; // the window over the segment's first draws came with the segment's front
 
 			for (uint64_t chunk = C0; chunk < C1 || (chunk == C0 && !published && pass == 1); chunk += VGX_WAVE) {
 				const uint64_t ci = chunk + lane;
 				const bool valid = ci < C1;
-				// ---- decode my command instance (as k_flatten, vgx_flatten.hip) -----------------------------------------
-				uint64_t d = d0;
-				uint32_t type = VGX_CMD_CLOSE, cflags = 0, na = 0;
-				bool drawHead = false, drawLast = false, serialDraw = false;
-				float scale = 1.0f, tol = 0.25f;
-				uint32_t fillFlags = 0, strokeFlags = 0;
-				const vgx_draw* dr = A.draws;
-				const uint64_t lastKey = chunk + (VGX_WAVE - 1);
-				if (!(wave_bcast_u64(W.prefix, VGX_WAVE - 1) > lastKey) || dcur < wbase) {
-					wbase = dcur;
-					W = draw_window_load(A, wbase, lane);
-				}
-				const bool windowCovers = wave_bcast_u64(W.prefix, VGX_WAVE - 1) > lastKey;
-				const uint32_t wrel = window_rel(W.prefix, chunk);
-				const int ownerOfs = window_owner_rel(wrel, valid ? (uint32_t)lane : 0u);
-				const uint32_t orel = (uint32_t)__shfl((int)wrel, ownerOfs);
-				const int firstOwner = __popcll(wave_ballot(W.prefix <= chunk)) - 1;
-				uint64_t ownerBase = orel > 0 ? chunk + orel : wave_bcast_u64(W.prefix, firstOwner < 0 ? 0 : firstOwner);
-				uint32_t pc0 = (uint32_t)__shfl((int)(W.pc0 | ((W.serial & 1u) << 31)), ownerOfs);
-				uint32_t serialStatic = pc0 >> 31;
-				pc0 &= 0x7FFFFFFFu;
-				VgxCmdRec rec;
-				rec.type = VGX_CMD_CLOSE; rec.flags = 0; rec.na = 0; rec.arg_off = 0; rec.start[0] = 0.0f; rec.start[1] = 0.0f;
-				for (int i = 0; i < 8; ++i) { rec.a[i] = 0.0f; }
+				// ---- decode my command instance (vgx_chunk.h) ------------------------------------------------------------
+				bool serialDraw = false;
 				uint32_t serV = 0, serS = 0, serM = 0, serF = 0; // a serial draw's counts (k_flatten_serial<count>), at its last command
-				uint32_t recIndex = 0;
-				if (valid) {
-					if (windowCovers) {
-						d = wbase + (uint64_t)ownerOfs;
-					} else { // more than 63 draws begin inside this chunk (1-command or empty paths)
-						d = find_owner_u64(A.cmd_prefix, d0, d1, ci);
-						ownerBase = A.cmd_prefix[d];
-						const uint32_t path = A.draws[d].path;
-						pc0 = ps.path_cmd_begin[path];
-						serialStatic = ps.path_flags[path] & VGX_PF_SERIAL;
-					}
-					dr = A.draws + d;
-					const uint32_t k = (uint32_t)(ci - ownerBase);
-					recIndex = pc0 + k;
-					rec = ps.cmdrec[recIndex];
-					type = rec.type; cflags = rec.flags; na = rec.na;
-					drawHead = (k == 0);
-					drawLast = (cflags & VGX_CF_LAST_IN_PATH) != 0;
-					scale = dr->scale; tol = dr->tess_tol;
-					fillFlags = dr->fill_flags; strokeFlags = dr->stroke_flags;
-					serialDraw = serialStatic != 0;
+				const ChunkCmd C = chunk_decode<true, false>(A, W, wbase, d0, d1, C1, chunk, dcur, lane, [&](const ChunkCmd& D) {
+					serialDraw = D.serialStatic != 0;
 					if (readFlags) {
-						const uint32_t fl = A.dinfo[d].flags;
+						const uint32_t fl = A.dinfo[D.d].flags;
 						serialDraw = serialDraw || (fl & 1u) != 0;
-						if (serialDraw && drawLast) { // counted by k_flatten_serial: the draw is one opaque block here
-							const vgx_draw_info si = A.dinfo[d];
+						if (serialDraw && D.drawLast) { // counted by k_flatten_serial: the draw is one opaque block here
+							const vgx_draw_info si = A.dinfo[D.d];
 							serV = si.num_poly_vertices; serS = si.num_subpaths; serM = si.num_meshes; serF = si.flags;
 						}
 					}
-				}
+				});
+				const uint64_t d = C.d, ownerBase = C.ownerBase;
+				const VgxCmdRec& rec = C.rec;
+				const uint32_t type = rec.type, cflags = rec.flags, na = rec.na, recIndex = C.recIndex;
+				const bool drawHead = C.drawHead, drawLast = C.drawLast;
 				const float* a = rec.a;
 				const float* pa = ps.args + rec.arg_off;
 				const V2 start = v2(rec.start[0], rec.start[1]);
@@ -635,30 +595,25 @@ __global__ __launch_bounds__(VGX_WAVE, (CAP > 2048 ? 1 : F1_MIN_WAVES_PER_EU)) v
 				// across the walk (the kernel must fit two waves per SIMD): the point of a MOVE_TO / LINE_TO, and the two epsilon
 				// tests of pathClose (path.cpp:716-722) -- my end point against the sub-path's first point (a[6..7] of every record)
 				const float ptx = a[0], pty = a[1];
-				bool endNearFirst = false, startNearFirst = false, lineSlow = false;
+				bool endNearFirst = false, startNearFirst = false;
 				if (valid) {
 					const V2 firstPt = v2(rec.a[6], rec.a[7]);
-					const V2 endp = (type == VGX_CMD_POLYLINE) ? (na >= 2 ? v2(pa[na - 2], pa[na - 1]) : v2(0.0f, 0.0f)) : (type == VGX_CMD_CUBIC_TO ? v2(a[4], a[5]) : (type == VGX_CMD_QUAD_TO ? v2(a[2], a[3]) : v2(a[0], a[1])));
-					endNearFirst = (cflags & VGX_CF_NEXT_IS_CLOSE) != 0 && v2near(endp, firstPt);
+					endNearFirst = (cflags & VGX_CF_NEXT_IS_CLOSE) != 0 && v2near(cmd_end_point<true>(type, a, pa, na), firstPt);
 					startNearFirst = v2near(start, firstPt);
-					lineSlow = v2near(start, v2(a[0], a[1]));
 				}
 
 				// ---- tasks: the chunk's cubics, compacted; non-flat roots cut in two while lanes are free ----------------
-				float c1x = a[0], c1y = a[1], c2x = a[2], c2y = a[3], ex = a[4], ey = a[5];
 				const bool isCubic = valid && !serialDraw && (type == VGX_CMD_CUBIC_TO || type == VGX_CMD_QUAD_TO);
-				if (isCubic && type == VGX_CMD_QUAD_TO) {
-					ex = a[2]; ey = a[3];
-					vgx_quad_to_cubic(start.x, start.y, a[0], a[1], ex, ey, &c1x, &c1y, &c2x, &c2y);
-				}
-				const float tessTol = tol / (scale * scale);
+				float c1x, c1y, c2x, c2y, ex, ey;
+				cubic_setup(isCubic && type == VGX_CMD_QUAD_TO, start, a, &c1x, &c1y, &c2x, &c2y, &ex, &ey);
+				const float tessTol = C.tol / (C.scale * C.scale);
 				const uint64_t cubicMask = wave_ballot(isCubic);
 				const unsigned long long c1 = F1_CLK();
 				if (chunk == C0) { F1_DBG(t, 3, F1_WALL() | ((unsigned long long)blockIdx.x << 40)); }
 				F1_ACC(0, c1 - (chunk == C0 && (pass == 1) == single ? c0 : c1)); // ticket + segment table + draw window + command records (first chunk of a segment)
 				F1_ACC(6, 1ull);
 				int cnt = 0;
-				bool slow = false, exists = false, closedHere = false, deep = false;
+				bool slow = false, exists = false, deep = false;
 				uint32_t listN = 0, myTask0 = 0, myTasks = 0;
 				if (cubicMask) { // wave-uniform
 					// ---- task records: every cubic starts as one task; while at most half of the lanes hold a task, every task whose
@@ -773,80 +728,34 @@ __global__ __launch_bounds__(VGX_WAVE, (CAP > 2048 ? 1 : F1_MIN_WAVES_PER_EU)) v
 #endif
 				const unsigned long long c2 = F1_CLK();
 				F1_ACC(1, c2 - c1); // root step + task records + walk + counts back
-				if (valid && !serialDraw) {
-					switch (type) {
-					case VGX_CMD_MOVE_TO: cnt = 1; exists = true; break;
-					case VGX_CMD_LINE_TO: cnt = 1; slow = lineSlow; break;
-					case VGX_CMD_POLYLINE: {
-						const uint32_t npts = na >> 1;
-						cnt = (int)npts - ((npts > 0 && v2near(start, v2(pa[0], pa[1]))) ? 1 : 0);
-						slow = cnt == 0;
-					} break;
-					default: break;
-					}
+				if (valid && !serialDraw && !isCubic) {
+					const ChunkCount cc = chunk_count_plain(type, start, v2(ptx, pty), pa, na);
+					cnt = cc.cnt; slow = cc.slow; exists = cc.exists;
 				}
 				const int rawCnt = cnt;
 
-				// ---- segmented bookkeeping (as the count pass of k_flatten) ------------------------------------------------
-				const uint64_t drawHeads = wave_ballot(valid && drawHead);
-				const uint64_t subHeads = wave_ballot(valid && (cflags & VGX_CF_STARTS_SUB));
-				const int dh = seg_head(drawHeads, lane);
-				const int sh = seg_head(subHeads, lane);
-				{
-					const int incl1 = wave_incl_scan(cnt, lane);
-					const int spBefore1 = seg_rel(incl1 - cnt, sh, carrySpVerts);
-					if (valid && !serialDraw && type == VGX_CMD_CLOSE && spBefore1 > 2) { // pathClose, path.cpp:707-726
-						closedHere = true;
-						if (startNearFirst) { cnt = -1; }
-					}
-				}
-				const bool serialTail = valid && serialDraw && drawLast; // carries the whole serial draw's counts
-				const int cntAll = serialTail ? (int)serV : cnt;
-				const int incl = wave_incl_scan(cntAll, lane);
-				const int excl = incl - cntAll;
-				const int inDrawBefore = seg_rel(excl, dh, carryDrawVerts);
-				const int spBefore = seg_rel(excl, sh, carrySpVerts);
-				const int spTotal = spBefore + cnt;
-				const uint64_t existMask = wave_ballot(valid && exists);
-				const uint64_t mine = seg_mask_upto(dh, lane);
-				const int subsIncl = __popcll(existMask & mine) + (dh < 0 ? carrySubs : 0);
-				const int headExists = (sh < 0) ? carrySpExists : (int)((existMask >> sh) & 1ull);
-				const bool lastInSub = valid && !serialDraw && (cflags & VGX_CF_LAST_IN_SUB) && headExists;
-				const bool fillHere = lastInSub && (fillFlags & VGX_FILL_ENABLE) && spTotal >= 3;
-				const bool strokeHere = lastInSub && (strokeFlags & VGX_STROKE_ENABLE) && spTotal >= 2;
-				const uint64_t fillMask = wave_ballot(fillHere);
-				const uint64_t strokeMask = wave_ballot(strokeHere);
-				const int fillIncl = __popcll(fillMask & mine) + (dh < 0 ? carryFill : 0);
-				const int strokeIncl = __popcll(strokeMask & mine) + (dh < 0 ? carryStroke : 0);
-				const uint64_t slowMask = wave_ballot(valid && slow);
-				const bool slowDraw = ((slowMask & mine) != 0) || (dh < 0 && carrySlow);
+				// ---- segmented bookkeeping (vgx_chunk.h) -----------------------------------------------------------------
+				const ChunkBook B = chunk_book<true, true, true, true>(K, C, valid, serialDraw, cnt, slow, exists, startNearFirst, lane, false, false, (int)serV);
+				cnt = B.cnt;
+				const bool closedHere = B.closedHere, serialTail = B.serialTail, lastInSub = B.lastInSub, slowDraw = B.slowDraw;
+				const int excl = B.excl, inDrawBefore = B.inDrawBefore, spBefore = B.spBefore, spTotal = B.spTotal, subsIncl = B.subsIncl, fillIncl = B.fillIncl, strokeIncl = B.strokeIncl;
 				// sub-paths / meshes in front of me inside the chunk (serial draws count as blocks at their last command)
 				const int subAll = serialTail ? (int)serS : (exists ? 1 : 0);
-				const int meshAll = serialTail ? (int)serM : ((fillHere ? 1 : 0) + (strokeHere ? 1 : 0));
+				const int meshAll = serialTail ? (int)serM : ((B.fillHere ? 1 : 0) + (B.strokeHere ? 1 : 0));
 				const int subInclC = wave_incl_scan(subAll, lane);
 				const int meshInclC = wave_incl_scan(meshAll, lane);
 
-				const int nvalid = (int)((C1 - chunk) < (uint64_t)VGX_WAVE ? (C1 - chunk) : (uint64_t)VGX_WAVE);
+				const int nvalid = chunk_valid_lanes(C1, chunk);
 				const int LL = nvalid > 0 ? nvalid - 1 : 0;
-				const int chunkV = nvalid > 0 ? wave_bcast(incl, LL) : 0;
+				const int chunkV = nvalid > 0 ? wave_bcast(B.incl, LL) : 0;
 				const int chunkS = nvalid > 0 ? wave_bcast(subInclC, LL) : 0;
 				const int chunkM = nvalid > 0 ? wave_bcast(meshInclC, LL) : 0;
 
 				// degenerate draws found here: flagged in dinfo and listed for k_flatten_serial; the kernel runs again (pass 1)
-				{
+				if (stage) {
 					const bool newSlow = valid && drawLast && !serialDraw && slowDraw;
-					const uint64_t sm = wave_ballot(newSlow);
-					if (sm && stage) {
-						unsigned long long sbase = 0;
-						if (lane == 0) { sbase = atomicAdd(&T->num_serial_list, (unsigned long long)__popcll(sm)); T->flat_redo = 1u; }
-						sbase = wave_bcast_u64(sbase, 0);
-						if (newSlow) {
-							A.serial_list[sbase + (uint64_t)__popcll(sm & lanemask_lt(lane))] = (uint32_t)d;
-							vgx_draw_info di;
-							di.first_poly_vertex = 0; di.first_subpath = 0; di.first_mesh = 0; di.num_poly_vertices = 0; di.num_subpaths = 0; di.num_meshes = 0; di.flags = 1u;
-							A.dinfo[d] = di;
-						}
-					}
+					serial_list_append<true>(T, A.serial_list, newSlow, d, lane);
+					if (newSlow) { A.dinfo[d] = draw_info_for(true, 0, 0, 0, 0, 0); }
 				}
 
 				const unsigned long long c3 = F1_CLK();
@@ -895,26 +804,7 @@ __global__ __launch_bounds__(VGX_WAVE, (CAP > 2048 ? 1 : F1_MIN_WAVES_PER_EU)) v
 					F1_ACC(4, F1_CLK() - c4); // placement + records
 				}
 
-				// ---- carries into the next chunk (taken from the last valid lane) ---------------------------------------------
-				if (nvalid > 0) {
-					const int lastIsDrawLast = wave_bcast((int)drawLast, LL);
-					const int lastIsSubLast = wave_bcast((int)((cflags & VGX_CF_LAST_IN_SUB) != 0), LL);
-					const int nDraw = wave_bcast(inDrawBefore + cntAll, LL);
-					const int nSp = wave_bcast(spTotal, LL);
-					const int nSubs = wave_bcast(subsIncl, LL);
-					const int nFill = wave_bcast(fillIncl, LL);
-					const int nStroke = wave_bcast(strokeIncl, LL);
-					const int nSlow = wave_bcast((int)slowDraw, LL);
-					const int nHeadExists = wave_bcast(headExists, LL);
-					carryDrawVerts = lastIsDrawLast ? 0 : nDraw;
-					carrySubs = lastIsDrawLast ? 0 : nSubs;
-					carryFill = lastIsDrawLast ? 0 : nFill;
-					carryStroke = lastIsDrawLast ? 0 : nStroke;
-					carrySlow = lastIsDrawLast ? 0 : nSlow;
-					carrySpVerts = (lastIsDrawLast || lastIsSubLast) ? 0 : nSp;
-					carrySpExists = (lastIsDrawLast || lastIsSubLast) ? 0 : nHeadExists;
-					dcur = wave_bcast_u64(d, LL);
-				}
+				K.advance<true>(B, C, nvalid, &dcur);
 				__syncthreads(); // the list / task table are reused by the next chunk
 			}
 			if (pass == 0) {

@@ -27,6 +27,7 @@
 #include "vgx_wave.h"
 #include "vgx_pathsim.h"
 #include "vgx_walk.h"
+#include "vgx_chunk.h"
 #include "vgx_elem.h"
 #include "vgx_scan_ops.h"
 #include "vgx_inst.h"
@@ -76,149 +77,65 @@ __global__ __launch_bounds__(VGX_WAVE) void k_flatten(VgxFlattenArgs A)
 		const uint64_t C0 = A.cmd_prefix[d0];
 		const uint64_t C1 = A.cmd_prefix[d1];
 		uint64_t dcur = d0; // draw that owns the chunk's first command instance
-
-		// carries of the draw / sub-path that continue across 64-command chunks (wave-uniform)
-		int carryDrawVerts = 0, carrySpVerts = 0, carrySubs = 0, carryFill = 0, carryStroke = 0;
-		int carrySlow = 0, carrySpExists = 0;
+		ChunkCarry K;
 
 		for (uint64_t chunk = C0; chunk < C1; chunk += VGX_WAVE) {
 			const uint64_t ci = chunk + lane;
 			const bool valid = ci < C1;
 
-			// ---- decode my command instance ------------------------------------------------------
-			uint64_t d = d0;
-			uint32_t c = 0, type = VGX_CMD_CLOSE, cflags = 0, na = 0;
-			bool drawHead = false, drawLast = false, serialDraw = false;
-			float scale = 1.0f, tol = 0.25f;
-			uint32_t fillFlags = 0, strokeFlags = 0;
-			const vgx_draw* dr = A.draws;
-			// owner draw of every lane from the lane-resident draw window (no global binary search)
-			const uint64_t lastKey = chunk + (VGX_WAVE - 1);
-			if (!(wave_bcast_u64(W.prefix, VGX_WAVE - 1) > lastKey)) {
-				wbase = dcur;
-				W = draw_window_load(A, wbase, lane);
-			}
-			const bool windowCovers = wave_bcast_u64(W.prefix, VGX_WAVE - 1) > lastKey;
-			// owner = last window entry <= my key, searched on 32-bit offsets relative to the chunk start
-			const uint32_t wrel = window_rel(W.prefix, chunk);
-			const int ownerOfs = window_owner_rel(wrel, valid ? (uint32_t)lane : 0u);
-			const uint32_t orel = (uint32_t)__shfl((int)wrel, ownerOfs);
-			const int firstOwner = __popcll(wave_ballot(W.prefix <= chunk)) - 1; // draw that owns the chunk's first command
-			uint64_t ownerBase = orel > 0 ? chunk + orel : wave_bcast_u64(W.prefix, firstOwner < 0 ? 0 : firstOwner);
-			uint32_t pc0 = (uint32_t)__shfl((int)(W.pc0 | ((W.serial & 1u) << 31)), ownerOfs);
-			uint32_t serialStatic = pc0 >> 31;
-			pc0 &= 0x7FFFFFFFu;
-			VgxCmdRec rec;
-			rec.type = VGX_CMD_CLOSE; rec.flags = 0; rec.na = 0; rec.arg_off = 0;
-			rec.start[0] = 0.0f; rec.start[1] = 0.0f;
-			for (int i = 0; i < 8; ++i) { rec.a[i] = 0.0f; }
-			if (valid) {
-				if (windowCovers) {
-					d = wbase + (uint64_t)ownerOfs;
-				} else { // more than 63 draws begin inside this chunk (1-command or empty paths)
-					d = find_owner_u64(A.cmd_prefix, d0, d1, ci);
-					ownerBase = A.cmd_prefix[d];
-					const uint32_t path = A.draws[d].path;
-					pc0 = ps.path_cmd_begin[path];
-					serialStatic = ps.path_flags[path] & VGX_PF_SERIAL;
-				}
-				dr = A.draws + d;
-				const uint32_t k = (uint32_t)(ci - ownerBase);
-				c = pc0 + k;
-				rec = ps.cmdrec[c]; // one 64-byte record: type, flags, start point, arguments, sub-path first point
-				type = rec.type;
-				cflags = rec.flags;
-				na = rec.na;
-				drawHead = (k == 0);
-				drawLast = (cflags & VGX_CF_LAST_IN_PATH) != 0;
-				scale = dr->scale;
-				tol = dr->tess_tol;
-				fillFlags = dr->fill_flags;
-				strokeFlags = dr->stroke_flags;
-				serialDraw = EMIT ? ((A.dinfo[d].flags & 1u) != 0) : (serialStatic != 0);
-			}
+			// ---- decode my command instance (vgx_chunk.h) -------------------------------------------
+			bool serialDraw = false;
+			const ChunkCmd C = chunk_decode<false, false>(A, W, wbase, d0, d1, C1, chunk, dcur, lane, [&](const ChunkCmd& D) {
+				serialDraw = EMIT ? ((A.dinfo[D.d].flags & 1u) != 0) : (D.serialStatic != 0);
+			});
+			const uint64_t d = C.d;
+			const VgxCmdRec& rec = C.rec;
+			const uint32_t type = rec.type, cflags = rec.flags, na = rec.na;
+			const bool drawLast = C.drawLast;
+			const float scale = C.scale, tol = C.tol;
+			const uint32_t fillFlags = C.fillFlags, strokeFlags = C.strokeFlags, serialStatic = C.serialStatic;
+			const vgx_draw* dr = C.dr;
 			const float* a = rec.a;                 // arguments 0..7 (CLOSE: a[6..7] = its sub-path's first point)
 			const float* pa = ps.args + rec.arg_off; // POLYLINE's variable-length arguments
 			const float* mtx = dr->mtx;
 
 			// ---- per-lane vertex count (count pass: compute; emit pass: read back) -----------------
 			int cnt = 0;
-			bool slow = false, exists = false, closedHere = false, pop = false;
+			bool slow = false, exists = false, closedIn = false, popIn = false;
+			const V2 start = v2(rec.start[0], rec.start[1]); // previous command's end point (unused by sub-path starters)
 			if (valid && !serialDraw) {
 				if (!EMIT) {
-					const V2 start = v2(rec.start[0], rec.start[1]); // previous command's end point (unused by sub-path starters)
 					switch (type) {
-					case VGX_CMD_MOVE_TO: cnt = 1; exists = true; break;
-					case VGX_CMD_LINE_TO: cnt = 1; slow = v2near(start, v2(a[0], a[1])); break;
 					case VGX_CMD_CUBIC_TO:
 					case VGX_CMD_QUAD_TO: {
 						FastCubicSink<false, false> sink;
 						sink.prev = start; sink.n = 0; sink.slow = false;
-						float c1x = a[0], c1y = a[1], c2x = a[2], c2y = a[3], ex, ey;
-						if (type == VGX_CMD_QUAD_TO) {
-							ex = a[2]; ey = a[3];
-							vgx_quad_to_cubic(start.x, start.y, a[0], a[1], ex, ey, &c1x, &c1y, &c2x, &c2y);
-						} else {
-							ex = a[4]; ey = a[5];
-						}
+						float c1x, c1y, c2x, c2y, ex, ey;
+						cubic_setup(type == VGX_CMD_QUAD_TO, start, a, &c1x, &c1y, &c2x, &c2y, &ex, &ey);
 						wave_flatten_cubic(start.x, start.y, c1x, c1y, c2x, c2y, ex, ey, tol / (scale * scale), stack, sink);
 						sink.flush();
 						cnt = (int)sink.n;
 						slow = sink.slow;
 					} break;
-					case VGX_CMD_POLYLINE: {
-						const uint32_t npts = na >> 1;
-						cnt = (int)npts - ((npts > 0 && v2near(start, v2(pa[0], pa[1]))) ? 1 : 0);
-						slow = cnt == 0; // a fully de-duplicated polyline leaves the last vertex unchanged: not its nominal end point
+					default: { // (CLOSE: decided by chunk_book, needs the sub-path's vertex count)
+						const ChunkCount cc = chunk_count_plain(type, start, v2(a[0], a[1]), pa, na);
+						cnt = cc.cnt; slow = cc.slow; exists = cc.exists;
 					} break;
-					case VGX_CMD_CLOSE: break; // decided below, needs the sub-path's vertex count
-					default: break; // shapes / arcs only occur in serial paths (k_flatten_serial)
 					}
 				} else {
 					const uint32_t w = A.cmd_cnt[ci];
 					exists = (w & VGX_CC_EXISTS) != 0;
-					closedHere = (w & VGX_CC_CLOSED) != 0;
-					pop = (w & VGX_CC_POP) != 0;
-					cnt = pop ? -1 : (int)(w & VGX_CC_COUNT_MASK);
+					closedIn = (w & VGX_CC_CLOSED) != 0;
+					popIn = (w & VGX_CC_POP) != 0;
+					cnt = popIn ? -1 : (int)(w & VGX_CC_COUNT_MASK);
 				}
 			}
 
-			// ---- segmented bookkeeping ----------------------------------------------------------
-			const uint64_t drawHeads = wave_ballot(valid && drawHead);
-			const uint64_t subHeads = wave_ballot(valid && (cflags & VGX_CF_STARTS_SUB));
-			const int dh = seg_head(drawHeads, lane);
-			const int sh = seg_head(subHeads, lane);
-
-			if (!EMIT) {
-				// pathClose (path.cpp:707-726) needs the vertex count of its sub-path so far.
-				const int incl1 = wave_incl_scan(cnt, lane);
-				const int spBefore = seg_rel(incl1 - cnt, sh, carrySpVerts);
-				if (valid && !serialDraw && type == VGX_CMD_CLOSE && spBefore > 2) {
-					closedHere = true;
-					if (v2near(v2(rec.start[0], rec.start[1]), v2(rec.a[6], rec.a[7]))) {
-						pop = true;
-						cnt = -1;
-					}
-				}
-			}
-			const int incl = wave_incl_scan(cnt, lane);
-			const int excl = incl - cnt;
-			const int inDrawBefore = seg_rel(excl, dh, carryDrawVerts);
-			const int spBefore = seg_rel(excl, sh, carrySpVerts);
-			const int spTotal = spBefore + cnt; // vertices of my sub-path up to and including me
-
-			const uint64_t existMask = wave_ballot(valid && exists);
-			const uint64_t mine = seg_mask_upto(dh, lane);
-			const int subsIncl = __popcll(existMask & mine) + (dh < 0 ? carrySubs : 0);
-			const int headExists = (sh < 0) ? carrySpExists : (int)((existMask >> sh) & 1ull);
-
-			const bool lastInSub = valid && (cflags & VGX_CF_LAST_IN_SUB) && headExists;
-			const uint64_t fillMask = wave_ballot(lastInSub && (fillFlags & VGX_FILL_ENABLE) && spTotal >= 3);
-			const uint64_t strokeMask = wave_ballot(lastInSub && (strokeFlags & VGX_STROKE_ENABLE) && spTotal >= 2);
-			const int fillIncl = __popcll(fillMask & mine) + (dh < 0 ? carryFill : 0);
-			const int strokeIncl = __popcll(strokeMask & mine) + (dh < 0 ? carryStroke : 0);
-			const uint64_t slowMask = wave_ballot(valid && slow);
-			const bool slowDraw = ((slowMask & mine) != 0) || (dh < 0 && carrySlow);
+			// ---- segmented bookkeeping (vgx_chunk.h) ------------------------------------------------
+			const ChunkBook B = chunk_book<!EMIT, true, false, false>(K, C, valid, serialDraw, cnt, slow, exists, v2near(start, v2(rec.a[6], rec.a[7])), lane, closedIn, popIn);
+			cnt = B.cnt;
+			const bool closedHere = B.closedHere, pop = B.pop, lastInSub = B.lastInSub;
+			const int inDrawBefore = B.inDrawBefore, spBefore = B.spBefore, spTotal = B.spTotal, subsIncl = B.subsIncl, fillIncl = B.fillIncl, strokeIncl = B.strokeIncl;
 
 			if (!EMIT) {
 				if (lastInSub && spTotal > VGX_LONG_SUBPATH) { // sizing input of the single-pass heap (vgx_tessellate_count)
@@ -235,19 +152,7 @@ __global__ __launch_bounds__(VGX_WAVE) void k_flatten(VgxFlattenArgs A)
 					A.cmd_cnt[ci] = w;
 				}
 				if (valid && drawLast && !(serialStatic != 0)) {
-					vgx_draw_info di;
-					di.first_poly_vertex = 0; di.first_subpath = 0; di.first_mesh = 0;
-					if (slowDraw) {
-						// degenerate input (epsilon de-dup hit / dropped piece): k_flatten_serial redoes this draw exactly
-						di.num_poly_vertices = 0; di.num_subpaths = 0; di.num_meshes = 0;
-						di.flags = 1u;
-					} else {
-						di.num_poly_vertices = (uint32_t)(inDrawBefore + cnt);
-						di.num_subpaths = (uint32_t)subsIncl;
-						di.num_meshes = (uint32_t)(fillIncl + strokeIncl);
-						di.flags = ((uint32_t)fillIncl << 1);
-					}
-					A.dinfo[d] = di;
+					A.dinfo[d] = draw_info_for(B.slowDraw, 0, inDrawBefore + cnt, subsIncl, fillIncl, strokeIncl);
 				}
 			} else if (valid) {
 				const vgx_draw_info di = A.dinfo[d];
@@ -259,7 +164,6 @@ __global__ __launch_bounds__(VGX_WAVE) void k_flatten(VgxFlattenArgs A)
 					if ((cflags & VGX_CF_NEXT_IS_CLOSE) && limit > 0 && (A.cmd_cnt[ci + 1] & VGX_CC_POP)) {
 						--limit; // my last vertex is the one pathClose removes
 					}
-					const V2 start = v2(rec.start[0], rec.start[1]);
 					switch (type) {
 					case VGX_CMD_MOVE_TO:
 					case VGX_CMD_LINE_TO:
@@ -273,13 +177,8 @@ __global__ __launch_bounds__(VGX_WAVE) void k_flatten(VgxFlattenArgs A)
 					case VGX_CMD_QUAD_TO: {
 						FastCubicSink<true, XFORM> sink;
 						sink.prev = start; sink.n = 0; sink.slow = false; sink.out = out; sink.writeLimit = limit; sink.mtx = mtx; sink.begin();
-						float c1x = a[0], c1y = a[1], c2x = a[2], c2y = a[3], ex, ey;
-						if (type == VGX_CMD_QUAD_TO) {
-							ex = a[2]; ey = a[3];
-							vgx_quad_to_cubic(start.x, start.y, a[0], a[1], ex, ey, &c1x, &c1y, &c2x, &c2y);
-						} else {
-							ex = a[4]; ey = a[5];
-						}
+						float c1x, c1y, c2x, c2y, ex, ey;
+						cubic_setup(type == VGX_CMD_QUAD_TO, start, a, &c1x, &c1y, &c2x, &c2y, &ex, &ey);
 						wave_flatten_cubic(start.x, start.y, c1x, c1y, c2x, c2y, ex, ey, tol / (scale * scale), stack, sink);
 						sink.flush();
 					} break;
@@ -321,26 +220,7 @@ __global__ __launch_bounds__(VGX_WAVE) void k_flatten(VgxFlattenArgs A)
 				}
 			}
 
-			// ---- carries into the next chunk (taken from the last valid lane) ---------------------
-			const int nvalid = (int)((C1 - chunk) < (uint64_t)VGX_WAVE ? (C1 - chunk) : (uint64_t)VGX_WAVE);
-			const int L = nvalid - 1;
-			const int lastIsDrawLast = wave_bcast((int)drawLast, L);
-			const int lastIsSubLast = wave_bcast((int)((cflags & VGX_CF_LAST_IN_SUB) != 0), L);
-			const int nDraw = wave_bcast(inDrawBefore + cnt, L);
-			const int nSp = wave_bcast(spTotal, L);
-			const int nSubs = wave_bcast(subsIncl, L);
-			const int nFill = wave_bcast(fillIncl, L);
-			const int nStroke = wave_bcast(strokeIncl, L);
-			const int nSlow = wave_bcast((int)slowDraw, L);
-			const int nHeadExists = wave_bcast(headExists, L);
-			carryDrawVerts = lastIsDrawLast ? 0 : nDraw;
-			carrySubs = lastIsDrawLast ? 0 : nSubs;
-			carryFill = lastIsDrawLast ? 0 : nFill;
-			carryStroke = lastIsDrawLast ? 0 : nStroke;
-			carrySlow = lastIsDrawLast ? 0 : nSlow;
-			carrySpVerts = (lastIsDrawLast || lastIsSubLast) ? 0 : nSp;
-			carrySpExists = (lastIsDrawLast || lastIsSubLast) ? 0 : nHeadExists;
-			dcur = wave_bcast_u64(d, L); // draw of the last command: the next window (if needed) starts here
+			K.advance<false>(B, C, chunk_valid_lanes(C1, chunk), &dcur);
 		}
 	}
 }
@@ -370,12 +250,6 @@ __global__ __launch_bounds__(VGX_WAVE) void k_flatten(VgxFlattenArgs A)
 #define VGX_BUILD_LEAF_SLOTS 8
 #endif
 #define BLS VGX_BUILD_LEAF_SLOTS
-#ifndef VGX_BUILD_UNROLL
-#define VGX_BUILD_UNROLL 1 /* the slot leaves of a lane requested together, in front of its stores (0: one LDS round trip per leaf) */
-#endif
-#ifndef VGX_BUILD_PREFETCH
-#define VGX_BUILD_PREFETCH 0 /* 1: the next chunk's records requested in front of this chunk's stores (see `decode`): measured, not kept */
-#endif
 // -DVGX_BUILD_PROFILE: shader-clock ticks per phase of k_flatten_build summed over all waves into VgxTotals::prof (vgx_get_failure_info)
 #ifdef VGX_BUILD_PROFILE
 #define FB_CLK() ((unsigned long long)clock64())
@@ -387,18 +261,6 @@ __global__ __launch_bounds__(VGX_WAVE) void k_flatten(VgxFlattenArgs A)
 #ifndef VGX_BUILD_OCC
 #define VGX_BUILD_OCC
 #endif
-struct BuildDec // what a lane of k_flatten_build knows about its command instance before the walk
-{
-	uint64_t d;            // draw
-	const vgx_draw* dr;
-	uint64_t subBase;      // sub_prefix[d]
-	VgxCmdRec rec;
-	float mloc[6];         // the draw's matrix
-	float scale, tol;
-	uint32_t fillFlags, strokeFlags, serialStatic;
-	bool drawHead;
-};
-
 __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFlattenArgs A)
 {
 	__shared__ __attribute__((aligned(16))) unsigned char s_mem[(VGX_LDS_LEVELS * 3 + BLS) * VGX_WAVE * 8];
@@ -443,95 +305,28 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 		{
 			uint64_t cur = blockCur; // next free heap vertex
 			uint64_t dcur = d0;
-			int carryDrawVerts = 0, carrySpVerts = 0, carrySubs = 0, carryFill = 0, carryStroke = 0, carrySlow = 0;
+			ChunkCarry K;
 
-			// A chunk's records: window + owner search, command record, the draw's fields. Run for chunk k + 1 BEFORE chunk k's vertices are
-			// stored (round 6): loads and stores share one in-order counter, so records requested behind the stores waited until the last of
-			// them had reached L2 -- every chunk began with a drained memory pipeline. Requested in front of them they arrive first, and the
-			// stores drain under the next walk.
-			auto decode = [&](uint64_t chunk, uint64_t dcurAt) {
-				const uint64_t ci = chunk + lane;
-				const bool valid = ci < C1;
-				const uint64_t lastKey = chunk + (VGX_WAVE - 1);
-				if (!(wave_bcast_u64(W.prefix, VGX_WAVE - 1) > lastKey) || dcurAt < wbase) {
-					wbase = dcurAt;
-					W = draw_window_load(A, wbase, lane);
-				}
-				const bool windowCovers = wave_bcast_u64(W.prefix, VGX_WAVE - 1) > lastKey;
-				// owner = last window entry <= my key, searched on 32-bit offsets relative to the chunk start
-				const uint32_t wrel = window_rel(W.prefix, chunk);
-				const int ownerOfs = window_owner_rel(wrel, valid ? (uint32_t)lane : 0u);
-				const uint32_t orel = (uint32_t)__shfl((int)wrel, ownerOfs);
-				const int firstOwner = __popcll(wave_ballot(W.prefix <= chunk)) - 1; // draw that owns the chunk's first command
-				uint64_t ownerBase = orel > 0 ? chunk + orel : wave_bcast_u64(W.prefix, firstOwner < 0 ? 0 : firstOwner);
-				uint32_t pc0 = (uint32_t)__shfl((int)(W.pc0 | ((W.serial & 1u) << 31)), ownerOfs);
-				uint32_t serialStatic = pc0 >> 31;
-				BuildDec D;
-				D.d = d0; D.drawHead = false; D.scale = 1.0f; D.tol = 0.25f; D.fillFlags = 0; D.strokeFlags = 0; D.dr = A.draws; D.subBase = 0;
-				D.mloc[0] = 1.0f; D.mloc[1] = 0.0f; D.mloc[2] = 0.0f; D.mloc[3] = 1.0f; D.mloc[4] = 0.0f; D.mloc[5] = 0.0f;
-				pc0 &= 0x7FFFFFFFu;
-				uint32_t thinPath = ((uint32_t)__shfl((int)W.serial, ownerOfs) >> 1) & 1u; // a moveTo / lineTo / close path: 16-byte thin records
-				D.rec.type = VGX_CMD_CLOSE; D.rec.flags = 0; D.rec.na = 0; D.rec.arg_off = 0; D.rec.start[0] = 0.0f; D.rec.start[1] = 0.0f;
-				for (int i = 0; i < 8; ++i) { D.rec.a[i] = 0.0f; }
-				if (valid) {
-					if (windowCovers) {
-						D.d = wbase + (uint64_t)ownerOfs;
-					} else {
-						D.d = find_owner_u64(A.cmd_prefix, d0, d1, ci);
-						ownerBase = A.cmd_prefix[D.d];
-						const uint32_t path = A.draws[D.d].path;
-						pc0 = ps.path_cmd_begin[path];
-						serialStatic = ps.path_flags[path] & VGX_PF_SERIAL;
-						thinPath = (ps.path_flags[path] >> 1) & 1u;
-					}
-					D.dr = A.draws + D.d;
-					const uint32_t k = (uint32_t)(ci - ownerBase);
-					if (thinPath) {
-						// my record, the one in front (its point = my start point) and, in front of a CLOSE, the one behind (the
-						// sub-path's first point): neighbours of a 1 KB run the wave reads anyway
-						const VgxCmdThin t0 = ps.cmdthin[pc0 + k];
-						const VgxCmdThin tp = ps.cmdthin[(long long)(pc0 + k) - 1]; // (command 0 of the set reads the padding record; a path's first command never uses it)
-						D.rec.type = t0.meta & 0xFFu; D.rec.flags = (t0.meta >> 8) & 0xFFu;
-						D.rec.na = D.rec.type == VGX_CMD_CLOSE ? 0u : 2u;
-						D.rec.start[0] = tp.x; D.rec.start[1] = tp.y;
-						if (D.rec.type == VGX_CMD_CLOSE) { D.rec.a[6] = t0.x; D.rec.a[7] = t0.y; }
-						else {
-							D.rec.a[0] = t0.x; D.rec.a[1] = t0.y;
-							if (D.rec.flags & VGX_CF_NEXT_IS_CLOSE) { const VgxCmdThin tn = ps.cmdthin[pc0 + k + 1]; D.rec.a[6] = tn.x; D.rec.a[7] = tn.y; }
-						}
-					} else {
-						D.rec = ps.cmdrec[pc0 + k];
-					}
-					D.drawHead = (k == 0);
-					D.scale = D.dr->scale; D.tol = D.dr->tess_tol;
-					D.fillFlags = D.dr->fill_flags; D.strokeFlags = D.dr->stroke_flags;
-					// requested here, used by the placement: behind the walk they cost nothing; issued there they wait behind the stores
-					// in front of them (one counter for loads and stores, in order)
-#pragma unroll
-					for (int i = 0; i < 6; ++i) { D.mloc[i] = D.dr->mtx[i]; }
-					D.subBase = A.sub_prefix[D.d];
-				}
-				D.serialStatic = serialStatic;
-				return D;
-			};
-			BuildDec DN; // the next chunk's records (valid when haveNext)
-			bool haveNext = false;
 			for (uint64_t chunk = C0; chunk < C1; chunk += VGX_WAVE) {
 				const uint64_t ci = chunk + lane;
 				const bool valid = ci < C1;
 				const unsigned long long fc0 = FB_CLK();
-				const BuildDec DC = haveNext ? DN : decode(chunk, dcur);
-				const uint64_t d = DC.d;
-				const VgxCmdRec& rec = DC.rec;
+				// the matrix and the sub-path base are requested with the records and used by the placement: behind the walk they cost nothing;
+				// issued there they wait behind the stores in front of them (one counter for loads and stores, in order)
+				float mloc[6] = {1.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f};
+				uint64_t subBase = 0;
+				const ChunkCmd C = chunk_decode<true, true>(A, W, wbase, d0, d1, C1, chunk, dcur, lane, [&](const ChunkCmd& D) {
+#pragma unroll
+					for (int i = 0; i < 6; ++i) { mloc[i] = D.dr->mtx[i]; }
+					subBase = A.sub_prefix[D.d];
+				});
+				const uint64_t d = C.d;
+				const VgxCmdRec& rec = C.rec;
 				const uint32_t type = rec.type, cflags = rec.flags, na = rec.na;
-				const bool drawHead = DC.drawHead, drawLast = (cflags & VGX_CF_LAST_IN_PATH) != 0;
-				const float scale = DC.scale, tol = DC.tol;
-				const uint32_t fillFlags = DC.fillFlags, strokeFlags = DC.strokeFlags;
-				const vgx_draw* dr = DC.dr;
-				const float* mloc = DC.mloc;
-				const uint64_t subBase = DC.subBase;
-				const uint32_t serialStatic = DC.serialStatic;
-				const bool serialDraw = serialStatic != 0;
+				const bool drawLast = C.drawLast;
+				const float scale = C.scale, tol = C.tol;
+				const vgx_draw* dr = C.dr;
+				const bool serialDraw = C.serialStatic != 0;
 				const float* a = rec.a;
 				const float* pa = ps.args + rec.arg_off;
 				const float* mtx = dr->mtx;
@@ -544,20 +339,15 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 				FB_ACC(0, fc1 - fc0); // window + owner search + draw and command records
 				// ---- subdivide ONCE: count, detect degenerate cases, keep the first leaves in LDS -------
 				int cnt = 0;
-				bool slow = false, exists = false, closedHere = false;
-				float c1x = a[0], c1y = a[1], c2x = a[2], c2y = a[3], ex = a[4], ey = a[5];
+				bool slow = false, exists = false;
 				const bool isCubic = valid && !serialDraw && (type == VGX_CMD_CUBIC_TO || type == VGX_CMD_QUAD_TO);
-				if (isCubic && type == VGX_CMD_QUAD_TO) {
-					ex = a[2]; ey = a[3];
-					vgx_quad_to_cubic(start.x, start.y, a[0], a[1], ex, ey, &c1x, &c1y, &c2x, &c2y);
-				}
+				float c1x, c1y, c2x, c2y, ex, ey;
+				cubic_setup(isCubic && type == VGX_CMD_QUAD_TO, start, a, &c1x, &c1y, &c2x, &c2y, &ex, &ey);
 				const float tessTol = tol / (scale * scale);
 				v2f q1, q2, q3, q4;
 				q1.x = start.x; q1.y = start.y; q2.x = c1x; q2.y = c1y; q3.x = c2x; q3.y = c2y; q4.x = ex; q4.y = ey;
 				if (valid && !serialDraw) {
 					switch (type) {
-					case VGX_CMD_MOVE_TO: cnt = 1; exists = true; break;
-					case VGX_CMD_LINE_TO: cnt = 1; slow = v2near(start, v2(a[0], a[1])); break;
 					case VGX_CMD_CUBIC_TO:
 					case VGX_CMD_QUAD_TO: {
 						float2* over = (float2*)A.leaf_overflow + (size_t)blockIdx.x * VGX_BUILD_OVERFLOW * VGX_WAVE + lane;
@@ -571,50 +361,25 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 						}
 						cnt = (int)nLeaves;
 					} break;
-					case VGX_CMD_POLYLINE: {
-						const uint32_t npts = na >> 1;
-						cnt = (int)npts - ((npts > 0 && v2near(start, v2(pa[0], pa[1]))) ? 1 : 0);
-						slow = cnt == 0;
+					default: {
+						const ChunkCount cc = chunk_count_plain(type, start, v2(a[0], a[1]), pa, na);
+						cnt = cc.cnt; slow = cc.slow; exists = cc.exists;
 					} break;
-					default: break;
 					}
 				}
 				const int rawCnt = cnt;
 				const unsigned long long fc2 = FB_CLK();
 				FB_ACC(1, fc2 - fc1); // the walk
 
-				// ---- segmented bookkeeping (same as the count pass of k_flatten) ---------------------------
-				const uint64_t drawHeads = wave_ballot(valid && drawHead);
-				const uint64_t subHeads = wave_ballot(valid && (cflags & VGX_CF_STARTS_SUB));
-				const int dh = seg_head(drawHeads, lane);
-				const int sh = seg_head(subHeads, lane);
-				{
-					const int incl1 = wave_incl_scan(cnt, lane);
-					const int spBefore1 = seg_rel(incl1 - cnt, sh, carrySpVerts);
-					if (valid && !serialDraw && type == VGX_CMD_CLOSE && spBefore1 > 2) { // pathClose, path.cpp:707-726
-						closedHere = true;
-						if (v2near(start, v2(rec.a[6], rec.a[7]))) { cnt = -1; } // pop: the previous vertex is removed
-					}
-				}
-				const int incl = wave_incl_scan(cnt, lane);
-				const int excl = incl - cnt;
-				const int inDrawBefore = seg_rel(excl, dh, carryDrawVerts);
-				const int spBefore = seg_rel(excl, sh, carrySpVerts);
-				const int spTotal = spBefore + cnt;
-				const uint64_t existMask = wave_ballot(valid && exists);
-				const uint64_t mine = seg_mask_upto(dh, lane);
-				const int subsIncl = __popcll(existMask & mine) + (dh < 0 ? carrySubs : 0);
-				const bool lastInSub = valid && !serialDraw && (cflags & VGX_CF_LAST_IN_SUB);
-				const uint64_t fillMask = wave_ballot(lastInSub && (fillFlags & VGX_FILL_ENABLE) && spTotal >= 3);
-				const uint64_t strokeMask = wave_ballot(lastInSub && (strokeFlags & VGX_STROKE_ENABLE) && spTotal >= 2);
-				const int fillIncl = __popcll(fillMask & mine) + (dh < 0 ? carryFill : 0);
-				const int strokeIncl = __popcll(strokeMask & mine) + (dh < 0 ? carryStroke : 0);
-				const uint64_t slowMask = wave_ballot(valid && slow);
-				const bool slowDraw = ((slowMask & mine) != 0) || (dh < 0 && carrySlow);
+				// ---- segmented bookkeeping (vgx_chunk.h) ------------------------------------------------------
+				const ChunkBook B = chunk_book<true, false, true, false>(K, C, valid, serialDraw, cnt, slow, exists, v2near(start, v2(rec.a[6], rec.a[7])), lane);
+				cnt = B.cnt;
+				const bool closedHere = B.closedHere, lastInSub = B.lastInSub, slowDraw = B.slowDraw;
+				const int excl = B.excl, inDrawBefore = B.inDrawBefore, spBefore = B.spBefore, spTotal = B.spTotal, subsIncl = B.subsIncl;
 
-				const int nvalid = (int)((C1 - chunk) < (uint64_t)VGX_WAVE ? (C1 - chunk) : (uint64_t)VGX_WAVE);
+				const int nvalid = chunk_valid_lanes(C1, chunk);
 				const int L = nvalid - 1;
-				const int chunkTotal = wave_bcast(incl, L);
+				const int chunkTotal = wave_bcast(B.incl, L);
 				const unsigned long long fc3 = FB_CLK();
 				FB_ACC(2, fc3 - fc2); // scans + bookkeeping
 				if (cur + (uint64_t)(chunkTotal > 0 ? chunkTotal : 0) > blockEnd) {
@@ -622,7 +387,7 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 					// contiguous, so the vertices the sub-path that spans into this chunk already has are moved along;
 					// the new block has room for twice that prefix, so a very long sub-path is moved O(1) times per
 					// vertex.
-					const uint64_t carry = (uint64_t)(carrySpVerts > 0 ? carrySpVerts : 0);
+					const uint64_t carry = (uint64_t)(K.spVerts > 0 ? K.spVerts : 0);
 					const uint64_t need = carry + (uint64_t)(chunkTotal > 0 ? chunkTotal : 0);
 					const uint64_t want = need + carry > (uint64_t)VGX_BUILD_BLOCK ? need + carry : (uint64_t)VGX_BUILD_BLOCK; // doubles the spanning sub-path only
 					unsigned long long base = 0;
@@ -641,16 +406,12 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 					cur = base + carry;
 					blockEnd = base + want;
 				}
-				// the next chunk's records, requested in front of this chunk's stores
-				const uint64_t dcurNext = wave_bcast_u64(d, L); // draw of the last command: the next window (if needed) starts here
-				haveNext = VGX_BUILD_PREFETCH && chunk + VGX_WAVE < C1;
-				if (haveNext) { DN = decode(chunk + VGX_WAVE, dcurNext); }
 				{
 					const uint64_t g = cur + (uint64_t)excl; // heap index of my first vertex
 					// my last vertex is the one pathClose removes (same decision the CLOSE lane takes)
 					uint32_t limit = (valid && !serialDraw) ? (uint32_t)(rawCnt < 0 ? 0 : rawCnt) : 0u;
 					if ((cflags & VGX_CF_NEXT_IS_CLOSE) && limit > 0 && spTotal > 2) {
-						const V2 endp = (type == VGX_CMD_POLYLINE) ? v2(pa[na - 2], pa[na - 1]) : (type == VGX_CMD_CUBIC_TO ? v2(a[4], a[5]) : (type == VGX_CMD_QUAD_TO ? v2(a[2], a[3]) : v2(a[0], a[1])));
+						const V2 endp = cmd_end_point<false>(type, a, pa, na);
 						if (v2near(endp, v2(rec.a[6], rec.a[7]))) { --limit; }
 					}
 					if (valid && !serialDraw) {
@@ -663,7 +424,6 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 						} else if (type == VGX_CMD_CUBIC_TO || type == VGX_CMD_QUAD_TO) {
 							if ((uint32_t)rawCnt <= VGX_LEAF_SLOTS + VGX_BUILD_OVERFLOW) {
 								const uint32_t nl = limit < VGX_LEAF_SLOTS ? limit : VGX_LEAF_SLOTS;
-#if VGX_BUILD_UNROLL
 								float2 lq[VGX_LEAF_SLOTS]; // every slot requested before the first store (one LDS round trip instead of one per leaf)
 #pragma unroll
 								for (uint32_t i = 0; i < VGX_LEAF_SLOTS; ++i) { lq[i] = s_leaf[i * VGX_WAVE + lane]; }
@@ -671,13 +431,6 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 								for (uint32_t i = 0; i < VGX_LEAF_SLOTS; ++i) {
 									if (i < nl) { const V2 p = v2xform(v2(lq[i].x, lq[i].y), mloc); *(float2*)(out + 2 * i) = make_float2(p.x, p.y); }
 								}
-#else
-								for (uint32_t i = 0; i < nl; ++i) {
-									const float2 q = s_leaf[i * VGX_WAVE + lane];
-									const V2 p = v2xform(v2(q.x, q.y), mloc);
-									*(float2*)(out + 2 * i) = make_float2(p.x, p.y);
-								}
-#endif
 								const float2* ov = (const float2*)A.leaf_overflow + (size_t)blockIdx.x * VGX_BUILD_OVERFLOW * VGX_WAVE + lane;
 								for (uint32_t i = VGX_LEAF_SLOTS; i < limit; ++i) { // same lane wrote these during its subdivision
 									const float2 q = ov[(i - VGX_LEAF_SLOTS) * VGX_WAVE];
@@ -724,50 +477,17 @@ __global__ __launch_bounds__(VGX_WAVE) VGX_BUILD_OCC void k_flatten_build(VgxFla
 							}
 						}
 					}
-					{ // draws the serial kernel has to (re)do: static serial paths and degenerate draws, wave-aggregated append
-						const bool toSerial = valid && drawLast && (serialDraw || slowDraw);
-						const uint64_t sm = wave_ballot(toSerial);
-						if (sm) {
-							unsigned long long sbase = 0;
-							if (lane == 0) { sbase = atomicAdd(&A.totals->num_serial_list, (unsigned long long)__popcll(sm)); }
-							sbase = wave_bcast_u64(sbase, 0);
-							if (toSerial) { A.serial_list[sbase + (uint64_t)__popcll(sm & lanemask_lt(lane))] = (uint32_t)d; }
-						}
-					}
+					// draws the serial kernel has to (re)do: static serial paths and degenerate draws
+					serial_list_append<false>(A.totals, A.serial_list, valid && drawLast && (serialDraw || slowDraw), d, lane);
 					if (valid && drawLast && !serialDraw) {
-						vgx_draw_info di;
-						di.first_poly_vertex = g - (uint64_t)inDrawBefore; di.first_subpath = 0; di.first_mesh = 0;
-						if (slowDraw) {
-							di.num_poly_vertices = 0; di.num_subpaths = 0; di.num_meshes = 0; di.flags = 1u;
-						} else {
-							di.num_poly_vertices = (uint32_t)(inDrawBefore + cnt);
-							di.num_subpaths = (uint32_t)subsIncl;
-							di.num_meshes = (uint32_t)(fillIncl + strokeIncl);
-							di.flags = ((uint32_t)fillIncl << 1);
-						}
-						A.dinfo[d] = di;
+						A.dinfo[d] = draw_info_for(slowDraw, g - (uint64_t)inDrawBefore, inDrawBefore + cnt, subsIncl, B.fillIncl, B.strokeIncl);
 					}
 					cur += (uint64_t)(chunkTotal > 0 ? chunkTotal : 0);
 				}
 				FB_ACC(3, FB_CLK() - fc3); // block switch + placement (stores issued, not waited for) + records
 				FB_ACC(4, 1ull);
 
-				// carries into the next chunk
-				const int lastIsDrawLast = wave_bcast((int)drawLast, L);
-				const int lastIsSubLast = wave_bcast((int)((cflags & VGX_CF_LAST_IN_SUB) != 0), L);
-				const int nDraw = wave_bcast(inDrawBefore + cnt, L);
-				const int nSp = wave_bcast(spTotal, L);
-				const int nSubs = wave_bcast(subsIncl, L);
-				const int nFill = wave_bcast(fillIncl, L);
-				const int nStroke = wave_bcast(strokeIncl, L);
-				const int nSlow = wave_bcast((int)slowDraw, L);
-				carryDrawVerts = lastIsDrawLast ? 0 : nDraw;
-				carrySubs = lastIsDrawLast ? 0 : nSubs;
-				carryFill = lastIsDrawLast ? 0 : nFill;
-				carryStroke = lastIsDrawLast ? 0 : nStroke;
-				carrySlow = lastIsDrawLast ? 0 : nSlow;
-				carrySpVerts = (lastIsDrawLast || lastIsSubLast) ? 0 : nSp;
-				dcur = dcurNext;
+				K.advance<false>(B, C, nvalid, &dcur);
 			}
 			blockCur = cur;
 		}
