@@ -661,7 +661,7 @@ int vgx_pick(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds
  * What does this frame look like? The reference hands its triangles to bgfx (src/vg.cpp:1221-1290); a compute part has no graphics
  * pipeline, and the frame lives in device memory only. vgx_raster draws the meshes [mesh_begin, min(mesh_end, num_meshes)) of `frame`
  * into an RGBA8 image in device memory. `frame` is what vgx_pick accepts: any mesh stream the library wrote with mesh-LOCAL indices
- * (streams written under vgx_set_assembly are OUT OF SCOPE), under the ascending precondition of vgx_mesh_bounds. With the mesh range
+ * (streams written under vgx_set_assembly are drawn by vgx_raster_commands, below), under the ascending precondition of vgx_mesh_bounds. With the mesh range
  * and the scissor a caller replays draw commands one after another. The rule below is written so that every implementation gives the
  * same bytes; there is no tolerance anywhere. All pointers of the frame and the target are DEVICE pointers.
  *
@@ -819,7 +819,7 @@ int vgx_raster_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mes
  * Host return values. As vgx_raster_frame, and VGX_E_INVALID_ARG for a null `tex`, uv_bytes other than 4 or 8, a null or misaligned
  *   `uv` (uv_bytes-aligned) with a non-empty mesh range, null `images` with num_images > 0, a misaligned `images` (8-byte).
  * Out of scope. Gradients and image patterns (draw types 1 and 2, with their paint matrices: vgx_raster_painted, below), mips (the
- *   reference creates none), streams written under vgx_set_assembly, shaping and the atlas itself.
+ *   reference creates none), shaping and the atlas itself. Streams written under vgx_set_assembly: vgx_raster_commands, below.
  * Side effects. As vgx_raster_frame, on the same scratch, and one bit per 16 x 16 tile of the image (which tiles a sampled mesh reaches)
  *   in a buffer only this call allocates; vgx_scratch_bytes counts it. Texels are only read inside [0, height) x [0, width) of a
  *   valid image. */
@@ -875,7 +875,7 @@ int vgx_raster_textured(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* 
  *   not looked at.
  * Host return values. As vgx_raster_textured, and VGX_E_INVALID_ARG for a null `paints`, a null table with a count above 0, a
  *   misaligned table (4-byte).
- * Out of scope. Mips, streams written under vgx_set_assembly.
+ * Out of scope. Mips. Streams written under vgx_set_assembly are drawn by vgx_raster_commands, below.
  * Side effects. As vgx_raster_textured, on the same scratch (the 32 bytes per mesh of the range now also name the paint), and a second
  *   bit per 16 x 16 tile of the image (which tiles a painted mesh reaches) in a buffer only this call allocates; vgx_scratch_bytes
  *   counts it. A counted state survives: vgx_tessellate_count -> vgx_raster_painted -> vgx_tessellate_emit works.
@@ -930,7 +930,7 @@ int vgx_paint_tables(const struct vgx_paint* paints, uint32_t n, struct vgx_pain
  * Status. The element count of VGX_E_RANGE becomes triangles plus edges (of the contour meshes that have a bin entry); a contour mesh has
  *   bin entries like any mesh, by its box. Everything else as vgx_raster_painted. Positions that are NaN: as vgx_mesh_bounds says, the
  *   box of such a mesh is unspecified, and so is what the mesh covers; nothing outside image and scissor is written in any case.
- * Host return values, out of scope (streams written under vgx_set_assembly): as vgx_raster_painted. Hit testing of what this call draws,
+ * Host return values, out of scope (streams written under vgx_set_assembly go to vgx_raster_commands): as vgx_raster_painted. Hit testing of what this call draws,
  *   contour meshes included, is vgx_pick_frame, below; vgx_pick still skips the kind.
  * Side effects. As vgx_raster_painted, on the same scratch, and a third bit per 16 x 16 tile of the image (which tiles a contour mesh
  *   reaches) in a buffer only this call allocates; vgx_scratch_bytes counts it. A counted state survives. */
@@ -1133,6 +1133,100 @@ typedef struct vgx_raster_damage {
 int vgx_raster_damaged(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                        const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints,
                        const vgx_raster_target* target, const vgx_raster_damage* damage, uint32_t* dev_status, void* stream);
+
+/* ---- a draw-command table to an image: vgx_set_assembly -> vgx_raster_cmds_from_assembly -> vgx_raster_commands ---------------------
+ * The calls above read mesh streams with mesh-local indices. vgx_raster_commands draws the frame as the reference hands it to bgfx
+ * (src/vg.cpp:1162-1288): vertex streams, ONE index buffer with command-relative indices, and a table of draw commands, each with
+ * its scissor, its clip state and its type / handle. It plays the part bgfx plays after vg::end. It adds no pixel arithmetic: the
+ * rule is vgx_raster_painted word for word -- sample, coverage, tie rule, colour, blend, draw scissor, stamp, In / Out, texel,
+ * gradient and pattern rules, target -- with command c playing both mesh c and draw c. Every implementation gives the same bytes.
+ *
+ * Triangles. Triangle t of command c is idx[first_index + 3t .. + 3), t < num_indices / 3; a trailing remainder is ignored. A
+ *   triangle with an index >= num_vertices is skipped; vertex i of the command is first_vertex + i in pos, color and uv, so nothing
+ *   outside the command's own vertex range is ever read.
+ * Order. A pixel receives its covering triangles in ascending (command, triangle) order: painter's order.
+ * Scissor. The command's scissor is the draw scissor of vgx_raster_frame: {x, y, w, h} in frame pixels, w == 0 or h == 0 draws nothing.
+ * Type 3 (Clip). Every covered sample inside both scissors sets the stamp S = c. No colour is read: the reference leaves a clip
+ *   command's colours unwritten.
+ * Types 0 - 2. The command is tested by the stamp rule of vgx_raster_frame with f = clip_first_cmd, n = clip_num_cmds, rule =
+ *   clip_rule; f == 0xFFFFFFFF or n == 0: no test. The range is a range of COMMAND indices of this table.
+ * Type 0 (Textured). Every triangle is SAMPLED from images[handle & 0xFFFF] through the UV stream by the rule of vgx_raster_textured:
+ *   what fs_textured.sc does for every Textured command. The reference's colour meshes carry the white-pixel UV, and div255(vc * 255)
+ *   = vc gives their vertex colour back.
+ * Types 1 / 2. The command is painted as in vgx_raster_painted: handle & 0xFFFF indexes paints->gradients / paints->patterns.
+ * Precondition. None on order or overlap of the commands' vertex and index ranges; no mesh table and no mesh_bounds are involved.
+ * dev_num_cmds (DEVICE, may be NULL). The real command count, cut to num_cmds; records behind it are not looked at.
+ * dev_status (DEVICE uint32, may be NULL). All statuses are decided in one reduction before anything is written, the clear included.
+ *   VGX_E_RANGE > VGX_E_INVALID_ARG > VGX_E_GROWN.
+ *   VGX_E_INVALID_ARG  a command of the table has type > 3, reserved != 0, num_vertices > 65536, a vertex or index range beyond the
+ *                streams (in 64 bits), clip_first_cmd != 0xFFFFFFFF with clip_first_cmd + clip_num_cmds > the real count, type 0 with
+ *                uv == NULL, handle >= num_images or an image record invalid by vgx_raster_textured's test, or type 1 / 2 invalid by
+ *                vgx_raster_painted's validity rule (paints == NULL: every such command is invalid).
+ *   VGX_E_GROWN  more chunks or bin entries than the context's scratch holds. A chunk is up to 64 consecutive triangles of one command
+ *                (the last chunk of a command is shorter); a bin entry is a pair of a chunk and a 16 x 16 tile inside the union of the
+ *                tile rectangles of those of the chunk's triangles that cover something and whose box reaches the target's scissor cut
+ *                by the command's. An integer union: a NaN contributes nothing. The protocol is vgx_raster's: nothing is written, the
+ *                need goes to the context through a pinned mirror, the repeated call succeeds, and after vgx_raster_commands_reserve
+ *                the first call does. A fresh context holds num_cmds + num_indices / 192 chunks and as many entries (and the 12.5 %
+ *                head room of every scratch table).
+ *   VGX_E_RANGE  more than 2^32 - 1 chunks or bin entries.
+ * Host return values. As vgx_raster_painted, on the new structs: VGX_E_INVALID_ARG for null ctx / streams / target, null pos, color
+ *   or idx with a count above 0, null cmds with num_cmds > 0, misaligned pointers (pos, cmds, images 8-byte; color, dev_num_cmds,
+ *   dev_status, pixels, paint tables 4-byte; idx 2-byte; uv uv_bytes-aligned), uv_bytes other than 0, 4, 8 (0 only with uv == NULL),
+ *   reserved != 0, null images with num_images > 0, the target checks of vgx_raster. With an empty target scissor no command is looked
+ *   at and dev_status is VGX_OK.
+ * Side effects. Nothing but pixels inside image and scissor and dev_status is written. Asynchronous. Scratch of its own in the
+ *   context (48 bytes per command, 32 per chunk, 16 per bin entry, two bits per tile, the sort's storage; vgx_scratch_bytes counts it),
+ *   so a counted state survives: vgx_tessellate_count -> vgx_raster_commands -> vgx_tessellate_emit works.
+ *
+ * vgx_raster_cmds_from_assembly turns the product's own assembled frame into that table, on the device. Precondition: assembly was
+ * armed with VGX_ASM_SPLIT_STATE. One record per draw command k < min(cap_drawcmds, *dev_num_drawcmds): the ranges are the draw
+ * command's, type = (state_key >> 16) & 0xF, handle = state_key & 0xFFFF, scissor and clip rule are those of draw_state[d], d =
+ * meshes[first_mesh].draw. The clip region goes from draws to commands: clip_first_cmd = the first command whose d >=
+ * clip_first_draw, the end = the first command whose d >= clip_first_draw + clip_num_draws (d does not decrease over the table; a
+ * region never starts inside a command, because the generation in state_key changes at BeginClip / EndClip). An open or absent region
+ * stays 0xFFFFFFFF / 0. *dev_num_cmds receives the count. dev_status: VGX_E_INVALID_ARG for a command whose first_mesh or d lies
+ * outside its table, or when any of the num_meshes meshes has kind VGX_MESH_CONTOURS (edge pairs are not triangles: contour fills
+ * stay with vgx_raster_concave); else VGX_OK. Host: VGX_E_INVALID_ARG for null ctx / state / out / dev_num_cmds, null tables with a
+ * count above 0, misaligned pointers (8-byte; dev_num_cmds, dev_status, draw_state 4-byte), VGX_E_RANGE for cap_drawcmds > 2^32 - 1.
+ *
+ * vgx_submit_order (HOST only, no context) is the loop of src/vg.cpp:1162-1219: the reference's two tables in the order vg::end
+ * submits them. It walks draw_cmds in order; when a command's clip_first_cmd differs from the previous command's and clip_num_cmds
+ * > 0, those clip commands are appended first with type = 3; the command follows with clip_first_cmd rewritten to where the copies
+ * landed. A region met again after an interruption is appended again, as the reference redraws it. VGX_E_NOSPACE when cap is too
+ * small (*num_out is then exact), VGX_E_INVALID_ARG for a clip range beyond nclip or null arrays with a count above 0. */
+typedef struct vgx_raster_cmd {     /* the reference's DrawCommand as its submit loop reads it. 56 bytes */
+	uint64_t first_vertex;          /* ABSOLUTE, into pos / color / uv (vertex-buffer base + m_FirstVertexID) */
+	uint64_t first_index;           /* m_FirstIndexID, into idx */
+	uint32_t num_vertices;          /* <= 65536 */
+	uint32_t num_indices;
+	uint32_t type;                  /* 0 Textured, 1 ColorGradient, 2 ImagePattern, 3 Clip */
+	uint32_t handle;                /* low 16 bits: image (type 0), gradient (1), pattern (2); ignored for 3 */
+	uint16_t scissor[4];            /* x, y, w, h */
+	uint32_t clip_rule;             /* 0 In, 1 Out */
+	uint32_t clip_first_cmd;        /* index into THIS table; 0xFFFFFFFF = none */
+	uint32_t clip_num_cmds;
+	uint32_t reserved;              /* 0 */
+} vgx_raster_cmd;
+typedef struct vgx_raster_streams {
+	const float* pos;               /* DEVICE [num_vertices][2] */
+	const uint32_t* color;          /* DEVICE [num_vertices] */
+	const void* uv;                 /* DEVICE [num_vertices][uv_bytes]; may be NULL when no command has type 0 */
+	const uint16_t* idx;            /* DEVICE [num_indices], command-relative */
+	uint64_t num_vertices, num_indices;
+	uint32_t uv_bytes;              /* 0 (uv == NULL), 4 (int16 x 2) or 8 (float x 2) */
+	uint32_t reserved;              /* 0 */
+} vgx_raster_streams;
+int vgx_raster_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds /* DEVICE */, uint32_t num_cmds,
+                        const uint32_t* dev_num_cmds /* DEVICE, may be NULL: the real count, <= num_cmds */,
+                        const vgx_raster_image* images, uint32_t num_images, const vgx_raster_paints* paints /* may be NULL */,
+                        const vgx_raster_target* target, uint32_t* dev_status, void* stream);
+int vgx_raster_commands_reserve(vgx_ctx* ctx, uint32_t num_cmds, uint64_t num_chunks, uint64_t num_bin_entries);
+int vgx_raster_cmds_from_assembly(vgx_ctx* ctx, const vgx_drawcmd* drawcmds, uint64_t cap_drawcmds, const uint64_t* dev_num_drawcmds,
+                                  const vgx_mesh* meshes, uint64_t num_meshes, const vgx_raster_draws* state,
+                                  vgx_raster_cmd* out /* DEVICE [cap_drawcmds] */, uint32_t* dev_num_cmds, uint32_t* dev_status, void* stream);
+int vgx_submit_order(const vgx_raster_cmd* draw_cmds, uint32_t ndraw, const vgx_raster_cmd* clip_cmds, uint32_t nclip,
+                     vgx_raster_cmd* out, uint32_t cap, uint32_t* num_out);
 
 /* ---- concave fills with AA fringes -------------------------------------------------
  * strokerConcaveFillEndAA (src/stroker.cpp:868-1006) alternates libtess2 and the stroker's own loops:

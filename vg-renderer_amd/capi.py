@@ -179,6 +179,20 @@ RASTER_CLEAR = 1
 RASTER_TILE = 16  # a bin entry is a pair of a mesh and a tile of this many pixels a side
 
 
+raster_cmd_dtype = np.dtype([("first_vertex", "<u8"), ("first_index", "<u8"), ("num_vertices", "<u4"), ("num_indices", "<u4"), ("type", "<u4"), ("handle", "<u4"),
+                             ("scissor", "<u2", (4,)), ("clip_rule", "<u4"), ("clip_first_cmd", "<u4"), ("clip_num_cmds", "<u4"), ("reserved", "<u4")])  # struct vgx_raster_cmd
+assert raster_cmd_dtype.itemsize == 56
+RASTER_CHUNK = 64  # vgx_raster_commands: a bin entry is a pair of a chunk of this many consecutive triangles of one command and a tile
+
+
+class RasterStreams(C.Structure):  # vgx_raster_streams: device pointers; uv may be None when no command has type 0
+    _fields_ = [("pos", C.c_void_p), ("color", C.c_void_p), ("uv", C.c_void_p), ("idx", C.c_void_p), ("num_vertices", C.c_uint64), ("num_indices", C.c_uint64),
+                ("uv_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(RasterStreams) == 56
+
+
 cache_slot_dtype = np.dtype([("first_mesh", "<u8"), ("first_vertex", "<u8"), ("first_index", "<u8"), ("cache_first_mesh", "<u8")])  # struct vgx_cache_slot
 assert cache_slot_dtype.itemsize == 32
 
@@ -305,6 +319,12 @@ VGX_SYMBOLS = {
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_raster_damaged": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.POINTER(RasterTextures),
                                     C.POINTER(RasterPaints), C.POINTER(RasterTarget), C.POINTER(RasterDamage), C.c_void_p, C.c_void_p]),
+    "vgx_raster_commands": (C.c_int, [C.c_void_p, C.POINTER(RasterStreams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RasterPaints),
+                                     C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),
+    "vgx_raster_commands_reserve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "vgx_raster_cmds_from_assembly": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RasterDraws), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    "vgx_submit_order": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "vgx_last_hip_error":(C.c_int, [C.c_void_p]),
     "vgx_status_string": (C.c_char_p, [C.c_int]),
     "vgx_version": (C.c_uint32, []),

@@ -18,6 +18,7 @@
 #include "vgx_dash.h"
 #include "vgx_update.h"
 #include "vgx_raster.h"
+#include "vgx_raster_cmds.h"
 #include "vgx_damage.h"
 #include "vgx_pick.h"
 #include "vgx_concave_lane.h"
@@ -178,6 +179,15 @@ struct vgx_ctx
 	// the host learned from it: the count (the next call's sort window, vgx_damage.h) and whether that call ended with VGX_E_GROWN (the
 	// next window holds its need whatever max_entries says). A full render in between touches neither
 	HostMirror<unsigned long long> rasDmg; bool dmgKnown, dmgGrown; uint64_t dmgNeed;
+	// vgx_raster_commands (vgx_raster_cmds.hip): per command its state and its first chunk; per chunk its rectangle of tiles, its command
+	// and its first entry; the (tile, chunk) entries in chunk order and in tile order; one bit per tile a painted command reaches; the
+	// state words (VGX_RASC_*) with their pinned mirror. The capacities the kernels are told are the ones asked for with their 12.5 %,
+	// not what the allocator's rounding left behind. The sort's storage and the slice sums are vgx_raster's. Its own: a counted state
+	// survives the call. rascFlag: the one word of vgx_raster_cmds_from_assembly
+	Buf<VgxRasterMeshState> rascCmdState; Buf<uint64_t> rascCmdFirst, rascChunkFirst; Buf<VgxRasterRect> rascChunkRect;
+	Buf<uint32_t> rascChunkCmd, rascKeys, rascVals, rascSortedKeys, rascSortedVals, rascTilePaint, rascFlag; Buf<unsigned long long> rascState;
+	uint64_t rascChunkCap, rascEntryCap;
+	HostMirror<unsigned long long> rasc;
 	// vgx_damage_instances (vgx_damage.hip): the flag word (in 16 bytes) and the mesh prefix of the listed entries, the scan's slice sums
 	// (views: as `partial`). Its own: a counted state, and a vgx_cache_update in flight, survive the call
 	DevBuf dmgPrefix, dmgPartial;
@@ -1048,7 +1058,7 @@ int vgx_destroy(vgx_ctx* ctx)
 	vgx_scratch_release(ctx->scratch);
 	if (ctx->hostTotals) { (void)hipHostFree(ctx->hostTotals); }
 	if (ctx->hostF1) { (void)hipHostFree(ctx->hostF1); }
-	ctx->imm.mirror.release(); ctx->dash.release(); ctx->df.release(); ctx->ras.release(); ctx->rasDmg.release();
+	ctx->imm.mirror.release(); ctx->dash.release(); ctx->df.release(); ctx->ras.release(); ctx->rasDmg.release(); ctx->rasc.release();
 	if (ctx->hostPs) { (void)hipHostFree(ctx->hostPs); }
 	if (ctx->psImage) { (void)hipHostFree(ctx->psImage); }
 	for (int i = 0; i < VGX_PS_POOL; ++i) { if (ctx->psPool[i].p) { (void)hipFree(ctx->psPool[i].p); } }
@@ -2865,6 +2875,134 @@ int vgx_raster_concave(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* m
                        uint32_t* dev_status, void* stream)
 {
 	return rasterCall(VGX_RL_CONCAVE, ctx, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, nullptr, dev_status, stream);
+}
+
+// ---- a draw-command table to an image (vgx_raster_cmds.hip) -------------------------------------------------------------------
+namespace {
+
+// chunks and entries the tables hold at least; the capacity the kernels see grows with them and never shrinks
+int rasterCmdsEnsure(vgx_ctx* ctx, uint64_t cmds, uint64_t chunks, uint64_t entries)
+{
+	int st;
+	const uint64_t chunkCap = chunks + chunks / 8, entryCap = entries + entries / 8;
+	if (chunkCap > ctx->rascChunkCap) { ctx->rascChunkCap = chunkCap; }
+	if (entryCap > ctx->rascEntryCap) { ctx->rascEntryCap = entryCap; }
+	if ((st = ensure(ctx, ctx->rascState, VGX_RASC_WORDS)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rasPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rascCmdState, cmds + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rascCmdFirst, cmds + 2)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rascChunkRect, ctx->rascChunkCap + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rascChunkCmd, ctx->rascChunkCap + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rascChunkFirst, ctx->rascChunkCap + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rascKeys, ctx->rascEntryCap + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rascVals, ctx->rascEntryCap + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->rascSortedKeys, ctx->rascEntryCap + 1)) != VGX_OK) { return st; }
+	return ensure(ctx, ctx->rascSortedVals, ctx->rascEntryCap + 1);
+}
+
+} // namespace
+
+int vgx_raster_commands_reserve(vgx_ctx* ctx, uint32_t num_cmds, uint64_t num_chunks, uint64_t num_bin_entries)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx) { return VGX_E_INVALID_ARG; }
+	if (num_chunks > 0xFFFFFFFFull || num_bin_entries > 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	return rasterCmdsEnsure(ctx, num_cmds, num_chunks, num_bin_entries);
+}
+
+int vgx_raster_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
+                        const vgx_raster_image* images, uint32_t num_images, const vgx_raster_paints* paints, const vgx_raster_target* target,
+                        uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx) { return VGX_E_INVALID_ARG; }
+	int st = vgx_rasterc_check_args(streams, cmds, num_cmds, dev_num_cmds, images, num_images, paints, target, dev_status);
+	if (st != VGX_OK) { return st; }
+	const vgx_raster_target& t = *target;
+	hipStream_t s = (hipStream_t)stream;
+	if (t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3]) { // no pixel to write
+		if (dev_status) { noteHip(ctx, hipMemsetAsync(dev_status, 0, sizeof(uint32_t), s)); } // VGX_OK
+		return launchStatus(ctx);
+	}
+	VgxRasterCmdArgs a;
+	memset(&a, 0, sizeof(a));
+	a.tiles_w = (t.width + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE;
+	a.tile_x0 = t.scissor[0] / VGX_RASTER_TILE; a.tile_y0 = t.scissor[1] / VGX_RASTER_TILE;
+	a.tiles_x = (t.scissor[2] - 1) / VGX_RASTER_TILE - a.tile_x0 + 1; a.tiles_y = (t.scissor[3] - 1) / VGX_RASTER_TILE - a.tile_y0 + 1;
+	a.sentinel = a.tiles_w * ((t.height + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE); // <= 2^20
+	for (a.sort_bits = 1; (a.sentinel >> a.sort_bits) != 0; ++a.sort_bits) { }
+	if ((st = ctx->rasc.create(ctx, VGX_RASC_WORDS)) != VGX_OK) { return st; }
+	// the tables: what they hold, at least the first guess of one chunk per command and per 64 triangles of the index stream and as
+	// many entries, and what the last call measured once that has arrived
+	uint64_t chunks = (uint64_t)num_cmds + streams->num_indices / (3u * VGX_RASTERC_CHUNK), entries = chunks;
+	if (ctx->rasc.landed() && ctx->rasc.host[VGX_RASC_STATUS] == VGX_E_GROWN) {
+		if (ctx->rasc.host[VGX_RASC_CHUNKS] > chunks) { chunks = ctx->rasc.host[VGX_RASC_CHUNKS]; }
+		if (ctx->rasc.host[VGX_RASC_ENTRIES] > entries) { entries = ctx->rasc.host[VGX_RASC_ENTRIES]; }
+	}
+	if (chunks > 0xFFFFFFFFull) { chunks = 0xFFFFFFFFull; }
+	if (entries > 0xFFFFFFFFull) { entries = 0xFFFFFFFFull; }
+	if ((st = rasterCmdsEnsure(ctx, num_cmds, chunks, entries)) != VGX_OK) { return st; }
+	a.chunk_cap = ctx->rascChunkCap < 0xFFFFFFFFull ? ctx->rascChunkCap : 0xFFFFFFFFull;
+	a.entry_cap = ctx->rascEntryCap < 0xFFFFFFFFull ? ctx->rascEntryCap : 0xFFFFFFFFull;
+	// no chunk has more entries than the scissor has tiles: the sort need not look further
+	const uint64_t bound = a.chunk_cap * ((uint64_t)a.tiles_x * a.tiles_y);
+	a.sort_n = num_cmds ? (bound < a.entry_cap ? bound : a.entry_cap) : 0;
+	size_t sortBytes = 0;
+	if (a.sort_n) {
+		sortBytes = vgx_raster_sort_bytes(a.sort_n, a.sort_bits);
+		if (!sortBytes) { return VGX_E_INTERNAL; }
+		if ((st = ensure(ctx, ctx->rasSortTemp, sortBytes)) != VGX_OK) { return st; }
+	}
+	const uint64_t words = ((uint64_t)a.sentinel + 31u) / 32u;
+	if ((st = ensure(ctx, ctx->rascTilePaint, words + 1)) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->rascTilePaint.p, 0, words * sizeof(uint32_t), s));
+	a.pos = streams->pos; a.color = streams->color; a.uv = streams->uv; a.idx = streams->idx;
+	a.num_vertices = streams->num_vertices; a.num_indices = streams->num_indices; a.uv_bytes = streams->uv_bytes;
+	a.cmds = cmds; a.num_cmds = num_cmds; a.dev_num_cmds = dev_num_cmds;
+	a.images = images; a.num_images = num_images;
+	if (paints) { a.gradients = paints->gradients; a.patterns = paints->patterns; a.num_gradients = paints->num_gradients; a.num_patterns = paints->num_patterns; }
+	a.pixels = t.pixels; a.stride = t.stride; a.x0 = t.x0; a.y0 = t.y0;
+	for (int k = 0; k < 4; ++k) { a.scissor[k] = t.scissor[k]; }
+	a.flags = t.flags; a.clear_color = t.clear_color;
+	a.cmd_state = ctx->rascCmdState.ptr(); a.cmd_first = ctx->rascCmdFirst.ptr();
+	a.chunk_rect = ctx->rascChunkRect.ptr(); a.chunk_cmd = ctx->rascChunkCmd.ptr(); a.chunk_first = ctx->rascChunkFirst.ptr();
+	a.keys = ctx->rascKeys.ptr(); a.vals = ctx->rascVals.ptr(); a.sorted_keys = ctx->rascSortedKeys.ptr(); a.sorted_vals = ctx->rascSortedVals.ptr();
+	a.tile_paint = ctx->rascTilePaint.ptr();
+	a.state = ctx->rascState.ptr(); a.status = dev_status;
+	noteHip(ctx, vgx_launch_raster_commands(a, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
+	// status and need to the mirror, for the next call (never waited for)
+	ctx->rasc.push(ctx, a.state, s);
+	return launchStatus(ctx);
+}
+
+int vgx_raster_cmds_from_assembly(vgx_ctx* ctx, const vgx_drawcmd* drawcmds, uint64_t cap_drawcmds, const uint64_t* dev_num_drawcmds, const vgx_mesh* meshes,
+                                  uint64_t num_meshes, const vgx_raster_draws* state, vgx_raster_cmd* out, uint32_t* dev_num_cmds, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || !state || !dev_num_cmds || (cap_drawcmds && (!drawcmds || !out)) || (num_meshes && !meshes)) { return VGX_E_INVALID_ARG; }
+	if (state->reserved != 0u || (state->num_draws && !state->draw_state)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)drawcmds & 7u) || ((uintptr_t)dev_num_drawcmds & 7u) || ((uintptr_t)meshes & 7u) || ((uintptr_t)out & 7u) || ((uintptr_t)state->draw_state & 3u)
+		|| ((uintptr_t)dev_num_cmds & 3u) || ((uintptr_t)dev_status & 3u)) {
+		return VGX_E_INVALID_ARG;
+	}
+	if (cap_drawcmds > 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	hipStream_t s = (hipStream_t)stream;
+	int st;
+	if ((st = ensure(ctx, ctx->rascFlag, 4)) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->rascFlag.p, 0, sizeof(uint32_t), s));
+	VgxCmdsFromAsmArgs a;
+	memset(&a, 0, sizeof(a));
+	a.drawcmds = drawcmds; a.cap_drawcmds = cap_drawcmds; a.dev_num_drawcmds = dev_num_drawcmds; a.meshes = meshes; a.num_meshes = num_meshes;
+	a.draw_state = state->draw_state; a.num_draws = state->num_draws; a.out = out; a.dev_num_cmds = dev_num_cmds; a.flag = ctx->rascFlag.ptr(); a.status = dev_status;
+	vgx_launch_cmds_from_assembly(a, s);
+	return launchStatus(ctx);
+}
+
+// HOST only, no context (vgx_raster_cmds.h)
+int vgx_submit_order(const vgx_raster_cmd* draw_cmds, uint32_t ndraw, const vgx_raster_cmd* clip_cmds, uint32_t nclip, vgx_raster_cmd* out, uint32_t cap,
+                     uint32_t* num_out)
+{
+	return vgx_rasterc_submit_order(draw_cmds, ndraw, clip_cmds, nclip, out, cap, num_out);
 }
 
 // HOST only, no context: the decoder's paint list scattered by handle into the two tables vgx_raster_painted indexes; holes marked

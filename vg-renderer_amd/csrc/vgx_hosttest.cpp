@@ -1013,3 +1013,163 @@ int vgxt_raster_damaged(const vgx_cache_desc* frame, const float* mesh_bounds, u
 uint64_t vgxt_damage_words(uint32_t width, uint32_t height) { return ((uint64_t)vgx_damage_tiles_w(width) * vgx_damage_tiles_w(height) + 31u) / 32u; }
 
 }
+
+#include "vgx_raster_cmds.h"
+
+extern "C" {
+
+// vgx_raster_commands on the host, in the kernels' own decomposition (vgx_raster_cmds.h): the state of every command, the rectangle of
+// tiles of every chunk of 64 triangles, then tile after tile the chunks whose rectangle holds the tile, in ascending order, their
+// triangles tested against the tile cut by both scissors as the tile kernel tests them. HOST pointers, the table, the real count
+// (real_cmds, may be NULL), the images' pixels and the paint tables included. totals (may be NULL) receives the chunks and the bin
+// entries the device call counts. There is no scratch to outgrow here: *status is VGX_OK, VGX_E_INVALID_ARG or VGX_E_RANGE
+int vgxt_raster_commands(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, const vgx_raster_image* images,
+                         uint32_t num_images, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status, uint64_t* totals)
+{
+	const int rc = vgx_rasterc_check_args(streams, cmds, num_cmds, real_cmds, images, num_images, paints, target, status);
+	if (rc != VGX_OK) { return rc; }
+	const vgx_raster_target& t = *target;
+	if (status) { *status = VGX_OK; }
+	if (totals) { totals[0] = totals[1] = 0; }
+	if (t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3]) { return VGX_OK; }
+	const uint32_t n = real_cmds && *real_cmds < num_cmds ? *real_cmds : num_cmds;
+	VgxRastercTables tb;
+	tb.num_vertices = streams->num_vertices; tb.num_indices = streams->num_indices; tb.real_cmds = n; tb.has_uv = streams->uv ? 1u : 0u;
+	tb.images = images; tb.num_images = num_images;
+	tb.gradients = paints ? paints->gradients : nullptr; tb.num_gradients = paints ? paints->num_gradients : 0u;
+	tb.patterns = paints ? paints->patterns : nullptr; tb.num_patterns = paints ? paints->num_patterns : 0u;
+	std::vector<VgxRasterMeshState> state(n);
+	std::vector<VgxRasterRect> rect;   // per chunk
+	std::vector<uint32_t> chunkCmd, chunkTri;
+	bool invalid = false;
+	uint64_t entries = 0;
+	for (uint32_t c = 0; c < n; ++c) {
+		vgx_rasterc_cmd_state(cmds[c], c, tb, t.x0, t.y0, t.scissor, &state[c]);
+		invalid = invalid || state[c].mode == VGX_RF_INVALID;
+		const uint32_t chunks = vgx_rasterc_state_chunks(cmds[c], state[c]);
+		for (uint32_t k = 0; k < chunks; ++k) {
+			VgxRasterRect r = vgx_rasterc_rect_empty();
+			for (uint32_t q = 0; q < VGX_RASTERC_CHUNK; ++q) {
+				uint64_t v[3];
+				if (!vgx_rasterc_triangle(cmds[c], streams->idx, k * VGX_RASTERC_CHUNK + q, v)) { continue; }
+				const float* pp = streams->pos;
+				r = vgx_rasterc_rect_union(r, vgx_rasterc_triangle_tiles(v2(pp[2 * v[0]], pp[2 * v[0] + 1]), v2(pp[2 * v[1]], pp[2 * v[1] + 1]), v2(pp[2 * v[2]], pp[2 * v[2] + 1]),
+				                                                         t.x0, t.y0, state[c].rect));
+			}
+			rect.push_back(r); chunkCmd.push_back(c); chunkTri.push_back(k * VGX_RASTERC_CHUNK);
+			entries += vgx_rasterc_rect_entries(r);
+		}
+	}
+	if (totals) { totals[0] = rect.size(); totals[1] = entries; }
+	const uint32_t st = vgx_rasterc_status(rect.size(), entries, invalid, ~0ull, ~0ull);
+	if (status) { *status = st; }
+	if (st != VGX_OK) { return VGX_OK; }
+	const uint32_t tilesX0 = t.scissor[0] / VGX_RASTER_TILE, tilesY0 = t.scissor[1] / VGX_RASTER_TILE;
+	const uint32_t tilesX1 = (t.scissor[2] - 1u) / VGX_RASTER_TILE, tilesY1 = (t.scissor[3] - 1u) / VGX_RASTER_TILE;
+	for (uint32_t ty = tilesY0; ty <= tilesY1; ++ty) {
+		for (uint32_t tx = tilesX0; tx <= tilesX1; ++tx) {
+			const uint32_t ox = tx * VGX_RASTER_TILE, oy = ty * VGX_RASTER_TILE;
+			uint32_t S[VGX_RASTER_TILE * VGX_RASTER_TILE];
+			for (uint32_t q = 0; q < VGX_RASTER_TILE * VGX_RASTER_TILE; ++q) { S[q] = VGX_RASTER_STAMP_NONE; }
+			if (t.flags & VGX_RASTER_CLEAR) {
+				for (uint32_t j = oy > t.scissor[1] ? oy : t.scissor[1]; j < oy + VGX_RASTER_TILE && j < t.scissor[3]; ++j) {
+					for (uint32_t i = ox > t.scissor[0] ? ox : t.scissor[0]; i < ox + VGX_RASTER_TILE && i < t.scissor[2]; ++i) { t.pixels[(uint64_t)j * t.stride + i] = t.clear_color; }
+				}
+			}
+			for (size_t k = 0; k < rect.size(); ++k) { // the tile's run of entries: ascending chunk ordinal
+				const VgxRasterRect& r = rect[k];
+				if (vgx_rasterc_rect_is_empty(r) || tx < r.tx0 || tx > r.tx1 || ty < r.ty0 || ty > r.ty1) { continue; }
+				const vgx_raster_cmd& cmd = cmds[chunkCmd[k]];
+				const VgxRasterMeshState& ms = state[chunkCmd[k]];
+				// the command's rectangle cut to this tile
+				const uint32_t cx0 = ox > ms.rect[0] ? ox : ms.rect[0], cx1 = ox + VGX_RASTER_TILE < ms.rect[2] ? ox + VGX_RASTER_TILE : ms.rect[2];
+				const uint32_t cy0 = oy > ms.rect[1] ? oy : ms.rect[1], cy1 = oy + VGX_RASTER_TILE < ms.rect[3] ? oy + VGX_RASTER_TILE : ms.rect[3];
+				if (cx0 >= cx1 || cy0 >= cy1) { continue; }
+				const bool sampled = (ms.pad & VGX_RT_SAMPLED) != 0u;
+				const vgx_raster_image im = sampled ? images[ms.pad & 0xFFFFu] : vgx_raster_image();
+				const auto fetch = [&im](uint32_t x, uint32_t y) { return im.pixels[(uint64_t)y * im.stride + x]; };
+				VgxRasterPaint pr;
+				memset(&pr, 0, sizeof(pr));
+				if (ms.pad & VGX_RT_PAINTED) { vgx_raster_paint_record(((ms.pad & VGX_RT_GRADIENT) ? tb.gradients : tb.patterns)[ms.pad & 0xFFFFu], images, &pr); }
+				const auto pfetch = [&pr](uint32_t x, uint32_t y) { return pr.im.pixels[(uint64_t)y * pr.im.stride + x]; };
+				for (uint32_t q = 0; q < VGX_RASTERC_CHUNK; ++q) {
+					uint64_t v[3];
+					if (!vgx_rasterc_triangle(cmd, streams->idx, chunkTri[k] + q, v)) { continue; }
+					const float* pp = streams->pos;
+					const bool stamp = ms.mode == VGX_RF_STAMP; // a clip command's colours are not read
+					VgxRasterTri T;
+					if (!vgx_raster_setup(v2(pp[2 * v[0]], pp[2 * v[0] + 1]), v2(pp[2 * v[1]], pp[2 * v[1] + 1]), v2(pp[2 * v[2]], pp[2 * v[2] + 1]),
+					                      stamp ? 0u : streams->color[v[0]], stamp ? 0u : streams->color[v[1]], stamp ? 0u : streams->color[v[2]], &T)) { continue; }
+					uint32_t a0, a1, b0, b1;
+					if (!vgx_raster_span(T.minx, T.maxx, t.x0, cx0, cx1, &a0, &a1) || !vgx_raster_span(T.miny, T.maxy, t.y0, cy0, cy1, &b0, &b1)) { continue; }
+					double uv[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+					if (sampled) {
+						vgx_raster_uv_widen(streams->uv, streams->uv_bytes, v[0], uv);
+						vgx_raster_uv_widen(streams->uv, streams->uv_bytes, v[1], uv + 2);
+						vgx_raster_uv_widen(streams->uv, streams->uv_bytes, v[2], uv + 4);
+					}
+					for (uint32_t j = b0; j <= b1; ++j) {
+						for (uint32_t i = a0; i <= a1; ++i) {
+							uint32_t* const p = t.pixels + (uint64_t)j * t.stride + i;
+							const double px = (double)(t.x0 + (int32_t)i) + 0.5, py = (double)(t.y0 + (int32_t)j) + 0.5;
+							uint32_t* const sp = S + (j - oy) * VGX_RASTER_TILE + (i - ox);
+							const uint32_t d = sampled ? vgx_raster_textured_pixel(T, uv, im, ms.mode, ms.f, ms.n, px, py, *sp, *p, fetch)
+							                 : (ms.pad & VGX_RT_GRADIENT) ? vgx_raster_gradient_pixel(T, pr, ms.mode, ms.f, ms.n, px, py, *sp, *p)
+							                 : (ms.pad & VGX_RT_PATTERN) ? vgx_raster_pattern_pixel(T, pr, ms.mode, ms.f, ms.n, px, py, *sp, *p, pfetch)
+							                                             : vgx_raster_frame_pixel(T, ms.mode, ms.f, ms.n, px, py, sp, *p);
+							if (d != *p) { *p = d; }
+						}
+					}
+				}
+			}
+		}
+	}
+	return VGX_OK;
+}
+
+// vgx_raster_cmds_from_assembly on the host: one record per draw command, the clip region mapped from draws to commands by two searches
+int vgxt_raster_cmds_from_assembly(const vgx_drawcmd* drawcmds, uint64_t num_drawcmds, const vgx_mesh* meshes, uint64_t num_meshes, const vgx_raster_draws* state,
+                                   vgx_raster_cmd* out, uint32_t* num_cmds, uint32_t* status)
+{
+	if (!state || !num_cmds || (num_drawcmds && (!drawcmds || !out)) || (num_meshes && !meshes) || state->reserved != 0u || (state->num_draws && !state->draw_state)) {
+		return VGX_E_INVALID_ARG;
+	}
+	if (num_drawcmds > 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	bool bad = false;
+	for (uint64_t m = 0; m < num_meshes; ++m) { bad = bad || vgx_raster_kind_is_contours(meshes[m].subpath_kind); }
+	const auto draw_of = [&](uint64_t k) { const uint64_t m = drawcmds[k].first_mesh; return m < num_meshes ? meshes[m].draw : 0xFFFFFFFFu; };
+	const auto first_of = [&](uint64_t d) {
+		uint64_t lo = 0, hi = num_drawcmds;
+		while (lo < hi) {
+			const uint64_t mid = lo + ((hi - lo) >> 1);
+			if ((uint64_t)draw_of(mid) < d) { lo = mid + 1u; } else { hi = mid; }
+		}
+		return lo;
+	};
+	for (uint64_t k = 0; k < num_drawcmds; ++k) {
+		const vgx_drawcmd& dc = drawcmds[k];
+		vgx_raster_cmd c;
+		memset(&c, 0, sizeof(c));
+		c.first_vertex = dc.first_vertex; c.first_index = dc.first_index; c.num_vertices = dc.num_vertices; c.num_indices = dc.num_indices;
+		c.type = vgx_raster_draw_type(dc.state_key); c.handle = dc.state_key & 0xFFFFu;
+		c.clip_first_cmd = VGX_RASTERC_NONE;
+		const uint32_t d = draw_of(k);
+		if (dc.first_mesh >= num_meshes || d >= state->num_draws) {
+			bad = true;
+		} else {
+			const vgx_draw_state& ds = state->draw_state[d];
+			for (int q = 0; q < 4; ++q) { c.scissor[q] = ds.scissor[q]; }
+			c.clip_rule = ds.clip_rule;
+			if (ds.clip_first_draw != VGX_RASTER_STAMP_NONE && ds.clip_num_draws != 0u) {
+				const uint64_t first = first_of(ds.clip_first_draw), end = first_of((uint64_t)ds.clip_first_draw + ds.clip_num_draws);
+				c.clip_first_cmd = (uint32_t)first; c.clip_num_cmds = (uint32_t)(end - first);
+			}
+		}
+		out[k] = c;
+	}
+	*num_cmds = (uint32_t)num_drawcmds;
+	if (status) { *status = bad ? VGX_E_INVALID_ARG : VGX_OK; }
+	return VGX_OK;
+}
+
+}

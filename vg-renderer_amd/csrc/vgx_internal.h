@@ -537,6 +537,56 @@ struct VgxRasterFrameArgs
 };
 hipError_t vgx_launch_raster_frame(const VgxRasterFrameArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
 
+// a draw-command table to an image (vgx_raster_cmds.hip): vgx_raster_commands bins chunks of 64 consecutive triangles, not meshes
+struct VgxRasterRect;
+struct VgxRasterCmdArgs
+{
+	const float* pos; const uint32_t* color; const void* uv; const uint16_t* idx; // the streams, checked by the host
+	uint64_t num_vertices, num_indices;
+	const vgx_raster_cmd* cmds;       // [num_cmds]
+	const uint32_t* dev_num_cmds;     // or null: the table is cmds[0 .. min(num_cmds, *dev_num_cmds))
+	uint32_t num_cmds, uv_bytes;
+	const vgx_raster_image* images;   // [num_images]; a record is read (and checked, by k_rasterc_cmds) only when a command names it
+	const vgx_paint* gradients;       // [num_gradients], as images; null / 0 when the caller gave no paints
+	const vgx_paint* patterns;        // [num_patterns]
+	uint32_t num_images, num_gradients, num_patterns;
+	uint32_t* pixels;                 // the target, checked by the host: the fields of VgxRasterArgs
+	uint32_t stride;
+	int32_t x0, y0;
+	uint32_t scissor[4];
+	uint32_t flags, clear_color;
+	uint32_t tiles_w, tile_x0, tile_y0, tiles_x, tiles_y, sentinel, sort_bits;
+	uint64_t chunk_cap;               // chunks chunk_rect / chunk_cmd / chunk_first hold
+	uint64_t entry_cap;               // entries keys / vals hold (each of the four arrays)
+	uint64_t sort_n;                  // <= entry_cap: what the sort looks at
+	VgxRasterMeshState* cmd_state;    // [num_cmds] what every command does (context scratch, as everything below)
+	uint64_t* cmd_first;              // [num_cmds + 1] first chunk of every command, the total behind the real count
+	VgxRasterRect* chunk_rect;        // [chunk_cap] the tiles a chunk's triangles reach (empty: tx0 > tx1)
+	uint32_t* chunk_cmd;              // [chunk_cap]
+	uint64_t* chunk_first;            // [chunk_cap] first entry of every chunk
+	uint32_t* keys; uint32_t* vals;   // [entry_cap] in chunk order: tile, global chunk ordinal
+	uint32_t* sorted_keys; uint32_t* sorted_vals; // [entry_cap] in tile order
+	uint32_t* tile_paint;             // [(sentinel + 31) / 32] one bit per tile of the image, zero at the launch: a painted command has an entry there
+	unsigned long long* state;        // VGX_RASC_*: what the pinned mirror carries to the next call
+	uint32_t* status;                 // the caller's dev_status or null
+};
+enum { VGX_RASC_STATUS = 0, VGX_RASC_ENTRIES = 1, VGX_RASC_CHUNKS = 2, VGX_RASC_INVALID = 3, VGX_RASC_BEYOND = 4 /* entries of the chunks behind chunk_cap */,
+       VGX_RASC_CMDS = 5 /* the real command count */, VGX_RASC_WORDS = 6 };
+hipError_t vgx_launch_raster_commands(const VgxRasterCmdArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, void* sortTemp, size_t sortBytes, hipStream_t s);
+
+// vgx_raster_cmds_from_assembly (vgx_raster_cmds.hip)
+struct VgxCmdsFromAsmArgs
+{
+	const vgx_drawcmd* drawcmds; uint64_t cap_drawcmds; const uint64_t* dev_num_drawcmds; // the table is [0, min(cap, *dev_num)) (dev_num null: cap)
+	const vgx_mesh* meshes; uint64_t num_meshes;
+	const vgx_draw_state* draw_state; uint32_t num_draws;
+	vgx_raster_cmd* out;              // [cap_drawcmds]
+	uint32_t* dev_num_cmds;
+	uint32_t* flag;                   // one word, zeroed: != 0 once something was invalid (context scratch)
+	uint32_t* status;                 // the caller's dev_status or null
+};
+void vgx_launch_cmds_from_assembly(const VgxCmdsFromAsmArgs& a, hipStream_t s);
+
 // damage marks (vgx_damage.hip): the boxes of a mesh range, or of the frame meshes of the listed instances, ORed into a tile bitmap
 struct VgxDamageArgs
 {

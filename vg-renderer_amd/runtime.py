@@ -834,6 +834,77 @@ def raster_reserve(ctx, num_meshes, num_bin_entries):
     _check(lib().vgx_raster_reserve(ctx.handle, int(num_meshes), int(num_bin_entries)), "vgx_raster_reserve")
 
 
+# ---- a draw-command table to an image (vgx_raster_commands) ----------------------------------------------------------------
+def raster_streams(pos_dev, color_dev, idx_dev, num_vertices, num_indices, uv_dev=None, uv_bytes=0):
+    """The capi.RasterStreams of an assembled frame: pos / color / idx (and uv, uv_bytes 4 or 8 per vertex) device tensors, as
+    MeshBuffers holds them after a tessellate call under set_assembly; idx is command-relative."""
+    return capi.RasterStreams(_ptr(pos_dev, num_vertices), _ptr(color_dev, num_vertices), _ptr(uv_dev), _ptr(idx_dev, num_indices), int(num_vertices), int(num_indices),
+                              int(uv_bytes) if uv_dev is not None else 0, 0)
+
+
+def raster_commands(ctx, streams, cmds_dev, num_cmds, width, height, images_dev=None, num_images=0, gradients_dev=None, num_gradients=0, patterns_dev=None,
+                    num_patterns=0, x0=0, y0=0, scissor=None, clear_color=None, dev_num_cmds=None, image=None, dev_status=None):
+    """Draws a draw-command table into an RGBA8 image on the device: cmds_dev is a uint8 device tensor of num_cmds 56-byte vgx_raster_cmd
+    records (capi.raster_cmd_dtype; what raster_cmds_from_assembly() wrote, or the reference's tables through submit_order()), streams a
+    capi.RasterStreams (raster_streams()). Command c is cut by its scissor, stamps its index (type 3) or is tested against the command
+    range it names, and is sampled (type 0, images_dev as raster_images() gave), painted (types 1 / 2, the tables of paint_tables(); with
+    both counts 0 no paints are handed in) by the rule of vgx_raster_commands in include/vgx.h. dev_num_cmds: an int32 [1] device
+    tensor with the real count, or None. Returns (image, dev_status) as raster() does; dev_status may hold VGX_OK, VGX_E_GROWN (call
+    again), VGX_E_INVALID_ARG or VGX_E_RANGE. Asynchronous."""
+    import torch
+    if image is None:
+        image = torch.zeros((max(int(height), 1), max(int(width), 1)), dtype=torch.int32, device="cuda:%d" % ctx.device)[:height, :width]
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
+    paints = capi.RasterPaints(_ptr(gradients_dev, num_gradients), _ptr(patterns_dev, num_patterns), int(num_gradients), int(num_patterns))
+    tgt = _raster_target(image.data_ptr(), width, height, image.stride(0) if image.dim() == 2 and height else width, x0, y0, scissor, clear_color)
+    _check(lib().vgx_raster_commands(ctx.handle, C.byref(streams), _ptr(cmds_dev, num_cmds), int(num_cmds), _ptr(dev_num_cmds), _ptr(images_dev, num_images),
+                                     int(num_images), C.byref(paints) if (num_gradients or num_patterns) else None, C.byref(tgt), dev_status.data_ptr(), _stream_ptr()),
+           "vgx_raster_commands")
+    return image, dev_status
+
+
+def raster_commands_reserve(ctx, num_cmds, num_chunks, num_bin_entries):
+    """Sizes the scratch of raster_commands() ahead (chunks of capi.RASTER_CHUNK triangles, pairs of a chunk and a tile), so that a first
+    call does not end with VGX_E_GROWN."""
+    _check(lib().vgx_raster_commands_reserve(ctx.handle, int(num_cmds), int(num_chunks), int(num_bin_entries)), "vgx_raster_commands_reserve")
+
+
+def raster_cmds_from_assembly(ctx, drawcmds_dev, cap_drawcmds, dev_num_drawcmds, meshes_dev, num_meshes, draw_state_dev, num_draws, out_dev=None):
+    """The product's own assembled frame as a command table, on the device: drawcmds_dev / dev_num_drawcmds are what an assembly armed
+    with capi.ASM_SPLIT_STATE wrote (48-byte vgx_drawcmd records, an int64 [1] count or None), meshes_dev the frame's mesh table,
+    draw_state_dev the decoder's 24-byte vgx_draw_state records. Returns (cmds, dev_num_cmds, dev_status): a uint8 device tensor of
+    cap_drawcmds 56-byte vgx_raster_cmd records (out_dev when given), an int32 [1] count and an int32 [1] status (VGX_OK, or
+    VGX_E_INVALID_ARG for a command outside its tables or a frame with contour meshes). Asynchronous."""
+    import torch
+    dev = drawcmds_dev.device
+    if out_dev is None:
+        out_dev = torch.empty(max(int(cap_drawcmds), 1) * capi.raster_cmd_dtype.itemsize, dtype=torch.uint8, device=dev)
+    n, status = torch.empty(1, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    st = _raster_draws(None, draw_state_dev, num_draws)
+    _check(lib().vgx_raster_cmds_from_assembly(ctx.handle, _ptr(drawcmds_dev, cap_drawcmds), int(cap_drawcmds), _ptr(dev_num_drawcmds), _ptr(meshes_dev, num_meshes),
+                                               int(num_meshes), C.byref(st), out_dev.data_ptr(), n.data_ptr(), status.data_ptr(), _stream_ptr()),
+           "vgx_raster_cmds_from_assembly")
+    return out_dev, n, status
+
+
+def submit_order(draw_cmds, clip_cmds):
+    """vgx_submit_order: the reference's two command tables (capi.raster_cmd_dtype arrays; a draw command's clip range indexes clip_cmds)
+    as ONE table in the order vg::end submits them: the clip commands of a region, as type 3, ahead of the first command that uses it,
+    again after every interruption, and the users' ranges rewritten to where the copies landed. Host only."""
+    import numpy as np
+    d = np.ascontiguousarray(draw_cmds, dtype=capi.raster_cmd_dtype)
+    c = np.ascontiguousarray(clip_cmds, dtype=capi.raster_cmd_dtype)
+    n = C.c_uint32(0)
+    args = (d.ctypes.data if d.shape[0] else None, int(d.shape[0]), c.ctypes.data if c.shape[0] else None, int(c.shape[0]))
+    st = lib().vgx_submit_order(*args, None, 0, C.byref(n))
+    if st not in (capi.VGX_OK, capi.VGX_E_NOSPACE):
+        _check(st, "vgx_submit_order")
+    out = np.zeros(max(n.value, 1), dtype=capi.raster_cmd_dtype)
+    _check(lib().vgx_submit_order(*args, out.ctypes.data, n.value, C.byref(n)), "vgx_submit_order")
+    return out[:n.value]
+
+
 # ---- incremental update (vgx_cache_layout / vgx_cache_update) ------------------------------------------------------------
 def cache_layout(ctx, cache, inst_dev, ninst, slots_dev=None):
     """Where every instance of `inst_dev` (uint8 device tensor of 40-byte vgx_cache_instance records) lives in the frame cache_submit
