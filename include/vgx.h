@@ -611,7 +611,7 @@ int vgx_cache_cull(vgx_ctx* ctx, const vgx_cache_desc* cache, const float* mesh_
  * lives in device memory only, so the library that wrote it answers. `frame` is any mesh stream the library wrote with mesh-LOCAL
  * indices: vgx_tessellate*, vgx_stroke, vgx_cache_submit, vgx_merge and vgx_text_quads without an armed assembly, and a cache
  * (points in local space then). Streams written under vgx_set_assembly carry command-relative indices and are OUT OF SCOPE: the
- * call cannot tell and would test wrong triangles. All pointers are DEVICE pointers. The mesh table must satisfy the ascending
+ * call cannot tell and would test wrong triangles (they go to vgx_pick_commands, below). All pointers are DEVICE pointers. The mesh table must satisfy the ascending
  * precondition of vgx_mesh_bounds (it is what the boxes are computed under).
  *
  * Triangles. Triangle t of mesh m is idx[first_index + 3t .. +3), for t < num_indices / 3.
@@ -994,7 +994,7 @@ int vgx_raster_concave(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* m
  *       value of any candidate triangle is 0, vgx_pick_frame equals vgx_pick in all four words: away from the edges the closed rule and
  *       the tie rule agree.
  * Out of scope. Alpha of textures or paints deciding a hit (a fully transparent texel under the cursor still hits its quad), streams
- *   written under vgx_set_assembly, more than VGX_PICK_MAX_QUERIES queries per call. */
+ *   written under vgx_set_assembly (vgx_pick_commands, below), more than VGX_PICK_MAX_QUERIES queries per call. */
 int vgx_pick_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds /* may be NULL */,
                    uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
                    const vgx_pick_query* queries, uint32_t nqueries, vgx_pick_hit* hits,
@@ -1227,6 +1227,70 @@ int vgx_raster_cmds_from_assembly(vgx_ctx* ctx, const vgx_drawcmd* drawcmds, uin
                                   vgx_raster_cmd* out /* DEVICE [cap_drawcmds] */, uint32_t* dev_num_cmds, uint32_t* dev_status, void* stream);
 int vgx_submit_order(const vgx_raster_cmd* draw_cmds, uint32_t ndraw, const vgx_raster_cmd* clip_cmds, uint32_t nclip,
                      vgx_raster_cmd* out, uint32_t cap, uint32_t* num_out);
+
+/* ---- hit testing of a draw-command table: what is under the point in the image of vgx_raster_commands (... -> vgx_pick_commands) --------
+ * vgx_pick_frame reads mesh streams with mesh-local indices; on streams written under vgx_set_assembly it would test wrong triangles.
+ * vgx_pick_commands is its twin for the assembled frame: it takes the streams and the table of vgx_raster_commands and the kind of
+ * queries and hit records vgx_pick_frame takes. It adds no arithmetic: the rule is vgx_pick_frame's word for word with command c
+ * playing both mesh c and draw c, exactly as vgx_raster_commands states its pixel rule through vgx_raster_painted. It takes no target,
+ * no images, no paints and reads no UV: a hit is a statement about geometry and state. Every implementation gives the same words for
+ * every input; there is no tolerance. All pointers are DEVICE pointers unless marked HOST; `streams` and `owners` are HOST structs.
+ *
+ * Point. As vgx_pick_frame: px = (double)x, py = (double)y; !(fabs(px) < 2147483648.0) or the same for py (NaN included): the hit is
+ *   "none". Otherwise X = (int64)floor(px), Y = (int64)floor(py). A query with reserved != 0 is answered "none".
+ * Triangles. Those of vgx_raster_commands: triangle t of command c is idx[first_index + 3t .. + 3), t < num_indices / 3; an index >=
+ *   num_vertices skips the triangle; vertex i is first_vertex + i. No precondition on order or overlap of the commands' vertex or index
+ *   ranges; no mesh box and no mesh_bounds are involved.
+ * Scissor. Command c exists at the point iff x <= X < x + w && y <= Y < y + h of its scissor, in 64-bit integers. Otherwise it neither
+ *   stamps nor is hit.
+ * Coverage. The raster's rule at the sample (px, py), as in vgx_pick_frame: the binary64 box, the canonical edge values, the tie rule,
+ *   S > 0 (csrc/vgx_raster.h: vgx_raster_setup, vgx_raster_cover).
+ * Type 3 (Clip). A command that exists at the point and has ANY covering triangle sets the stamp S = c. Query flags and limits play no
+ *   part, and no colour is read: the reference leaves a clip command's colours unwritten. A clip command is never a hit.
+ * Types 0 - 2. Triangle (c, t) is a hit for query q iff the command exists at the point, the triangle covers, (c, t) < (q.cmd_end,
+ *   q.tri_end) lexicographically (cmd_end = 0xFFFFFFFF: everything), with VGX_PICK_SKIP_TRANSPARENT in q.flags no vertex of the triangle
+ *   has alpha 0, and the stamp test of vgx_raster_frame passes with f = clip_first_cmd, n = clip_num_cmds, rule = clip_rule and the S
+ *   the commands below c left: no test when f == 0xFFFFFFFF or n == 0, else (S != NONE && S >= f && S - f < n) == (rule == 0).
+ * Result. The largest hit (c, t): cmd = c, triangle = t. The limit cuts hits only; stamps always come from every command below c.
+ *   With `owners`, let p = cmds[c].first_index + 3t: mesh = the smallest m with meshes[m].first_index + meshes[m].num_indices > p,
+ *   provided that m also has first_index <= p; draw = meshes[mesh].draw. Precondition: the index ranges of the table ascend and are
+ *   disjoint, as in the mesh table of an assembled frame, whose first_index names the position in the index stream. With no such mesh,
+ *   or without owners, mesh = draw = 0xFFFFFFFF. No hit: all four words are 0xFFFFFFFF.
+ * Why a triangle limit. One command holds many drawings -- a whole Tiger is one command -- so click-through steps down INSIDE a command:
+ *   with owners, cmd_end = hit.cmd and tri_end = (meshes[hit.mesh].first_index - cmds[hit.cmd].first_index) / 3 reach the next drawing
+ *   below the one that was hit.
+ * dev_num_cmds (DEVICE, may be NULL). As in vgx_raster_commands: the real count, cut to num_cmds; records behind it are not looked at.
+ * dev_status (DEVICE uint32, may be NULL). Decided in one reduction; it does not depend on the order of the work. VGX_E_INVALID_ARG when
+ *   a command of the real table has type > 3, reserved != 0, num_vertices > 65536, a vertex or index range beyond the streams (in 64
+ *   bits), or clip_first_cmd != 0xFFFFFFFF with clip_first_cmd + clip_num_cmds > the real count: every hit record is then written
+ *   "none". Otherwise VGX_OK. Handles are not checked: nothing they name is read. There is no VGX_E_GROWN: overlapping index ranges
+ *   leave the number of chunks unbounded by num_indices, so nothing is kept per chunk or per triangle, and every table is sized from
+ *   num_cmds and nqueries, which the host knows.
+ * Host return values. VGX_OK once the work is enqueued. VGX_E_INVALID_ARG for a null ctx or streams, null cmds with num_cmds > 0, null
+ *   queries or hits with nqueries > 0, null pos, color or idx with a count above 0, streams->reserved != 0, uv_bytes other than 0, 4, 8
+ *   (0 only with uv == NULL) or a uv not uv_bytes-aligned (validated as vgx_raster_commands does; never read), owners with a null table
+ *   and num_meshes > 0, misaligned pointers (hits 16-byte; queries, cmds, pos, owners->meshes 8-byte; color, dev_num_cmds, dev_status
+ *   4-byte; idx 2-byte). VGX_E_RANGE for nqueries > VGX_PICK_MAX_QUERIES. VGX_E_HIP for a HIP failure. nqueries == 0 or num_cmds == 0 is
+ *   valid. A vgx_pick_cmd_query is 24 bytes and 8-byte aligned, a vgx_pick_cmd_hit 16 bytes and 16-byte aligned.
+ * Side effects. Exactly nqueries hit records and dev_status are written, nothing else of the caller's. Asynchronous. Scratch of its
+ *   own -- 40 bytes per command (32 its state, 8 its first chunk) and 4 per pair of a command and a query (the largest hit triangle);
+ *   vgx_scratch_bytes counts it -- so a counted state survives: vgx_tessellate_count -> vgx_pick_commands -> vgx_tessellate_emit works,
+ *   and the tables of vgx_pick, vgx_pick_frame and vgx_raster_commands are not touched.
+ * Two relations follow from the rule; the tests assert both.
+ *   (a) The image is the oracle. For a query at a pixel centre with flags 0 and cmd_end = 0xFFFFFFFF, (cmd, triangle) is the triangle
+ *       whose identifier vgx_raster_commands leaves in that pixel of the ID table: every triangle de-indexed to three vertices of its
+ *       own, coloured 0xFF000000 | (g + 1) with g the triangle's ordinal in (command, triangle) order, every non-Clip command retyped
+ *       to 0 on a white image with a constant UV (div255 of vc * 255 is vc: no colour arithmetic takes part), drawn over a clear of 0.
+ *   (b) vgx_pick_frame. With tri_end = 0, cmd and triangle equal mesh and triangle of vgx_pick_frame with mesh_end = cmd_end on the
+ *       one-mesh-per-command frame of the same table, boxes true (where that frame meets the ascending precondition of
+ *       vgx_mesh_bounds). */
+typedef struct vgx_pick_cmd_query { float x, y; uint32_t cmd_end, tri_end; uint32_t flags, reserved; } vgx_pick_cmd_query; /* 24 bytes */
+typedef struct vgx_pick_cmd_hit   { uint32_t cmd, triangle, mesh, draw; } vgx_pick_cmd_hit;                              /* 16 bytes */
+typedef struct vgx_pick_owners    { const vgx_mesh* meshes; uint64_t num_meshes; } vgx_pick_owners;                      /* DEVICE table, optional */
+int vgx_pick_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds,
+                      const uint32_t* dev_num_cmds /* may be NULL */, const vgx_pick_owners* owners /* may be NULL */,
+                      const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits,
+                      uint32_t* dev_status /* may be NULL */, void* stream);
 
 /* ---- concave fills with AA fringes -------------------------------------------------
  * strokerConcaveFillEndAA (src/stroker.cpp:868-1006) alternates libtess2 and the stroker's own loops:

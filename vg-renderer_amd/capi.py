@@ -191,6 +191,16 @@ class RasterStreams(C.Structure):  # vgx_raster_streams: device pointers; uv may
 
 
 assert C.sizeof(RasterStreams) == 56
+pick_cmd_query_dtype = np.dtype([("x", "<f4"), ("y", "<f4"), ("cmd_end", "<u4"), ("tri_end", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])  # struct vgx_pick_cmd_query
+pick_cmd_hit_dtype = np.dtype([("cmd", "<u4"), ("triangle", "<u4"), ("mesh", "<u4"), ("draw", "<u4")])  # struct vgx_pick_cmd_hit
+assert pick_cmd_query_dtype.itemsize == 24 and pick_cmd_hit_dtype.itemsize == 16
+
+
+class PickOwners(C.Structure):  # vgx_pick_owners: the mesh table of the assembled frame in device memory
+    _fields_ = [("meshes", C.c_void_p), ("num_meshes", C.c_uint64)]
+
+
+assert C.sizeof(PickOwners) == 16
 
 
 cache_slot_dtype = np.dtype([("first_mesh", "<u8"), ("first_vertex", "<u8"), ("first_index", "<u8"), ("cache_first_mesh", "<u8")])  # struct vgx_cache_slot
@@ -325,6 +335,8 @@ VGX_SYMBOLS = {
     "vgx_raster_cmds_from_assembly": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RasterDraws), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
     "vgx_submit_order": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "vgx_pick_commands": (C.c_int, [C.c_void_p, C.POINTER(RasterStreams), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(PickOwners), C.c_void_p, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
     "vgx_last_hip_error":(C.c_int, [C.c_void_p]),
     "vgx_status_string": (C.c_char_p, [C.c_int]),
     "vgx_version": (C.c_uint32, []),

@@ -21,6 +21,7 @@
 #include "vgx_raster_cmds.h"
 #include "vgx_damage.h"
 #include "vgx_pick.h"
+#include "vgx_pick_cmds.h"
 #include "vgx_concave_lane.h"
 #include "vgx_scratch.h"
 #include "vgx_route_plan.h"
@@ -188,6 +189,10 @@ struct vgx_ctx
 	Buf<uint32_t> rascChunkCmd, rascKeys, rascVals, rascSortedKeys, rascSortedVals, rascTilePaint, rascFlag; Buf<unsigned long long> rascState;
 	uint64_t rascChunkCap, rascEntryCap;
 	HostMirror<unsigned long long> rasc;
+	// vgx_pick_commands (vgx_pick_cmds.hip): per command its state and its first chunk; per (query, command) the largest hit triangle;
+	// the state words (VGX_PICKC_*); slice sums (views: as `partial`). Its own: a counted state survives the call, and the tables of
+	// vgx_pick, vgx_pick_frame and vgx_raster_commands are not touched
+	Buf<VgxPickfMesh> pickcState; Buf<uint64_t> pickcFirst, pickcWords; Buf<uint32_t> pickcTop; DevBuf pickcPartial;
 	// vgx_damage_instances (vgx_damage.hip): the flag word (in 16 bytes) and the mesh prefix of the listed entries, the scan's slice sums
 	// (views: as `partial`). Its own: a counted state, and a vgx_cache_update in flight, survive the call
 	DevBuf dmgPrefix, dmgPartial;
@@ -2635,6 +2640,31 @@ int vgx_pick_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_
 	a.mesh_state = ctx->pickfState.ptr(); a.cand_mesh = ctx->pickfCand.ptr(); a.tri_cand = ctx->pickfTriCand.ptr(); a.tri_prefix = ctx->pickfPrefix.ptr();
 	a.con_cand = ctx->pickfConCand.ptr(); a.cover = ctx->pickfCover.ptr(); a.totals = ctx->pickfTotals.ptr();
 	vgx_launch_pick_frame(a, ctx->pickfPartial.p, ctx->opt.pickGrid, s);
+	return launchStatus(ctx);
+}
+
+// ... of a draw-command table: the assembled frame (vgx_pick_cmds.hip). Scratch of its own, sized by the table and the queries alone
+int vgx_pick_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
+                      const vgx_pick_owners* owners, const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx) { return VGX_E_INVALID_ARG; }
+	int st = vgx_pickc_check_args(streams, cmds, num_cmds, dev_num_cmds, owners, queries, nqueries, hits, dev_status);
+	if (st != VGX_OK) { return st; }
+	hipStream_t s = (hipStream_t)stream;
+	if ((st = ensure(ctx, ctx->pickcState, (uint64_t)num_cmds + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickcFirst, (uint64_t)num_cmds + 2)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickcTop, (uint64_t)num_cmds * nqueries + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickcWords, VGX_PICKC_WORDS)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickcPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	VgxPickcArgs a;
+	memset(&a, 0, sizeof(a));
+	a.pos = streams->pos; a.color = streams->color; a.idx = streams->idx; a.num_vertices = streams->num_vertices; a.num_indices = streams->num_indices;
+	a.cmds = cmds; a.num_cmds = num_cmds; a.dev_num_cmds = dev_num_cmds;
+	if (owners) { a.meshes = owners->meshes; a.num_meshes = owners->num_meshes; }
+	a.queries = queries; a.nqueries = nqueries; a.hits = hits; a.status = dev_status;
+	a.cmd_state = ctx->pickcState.ptr(); a.cmd_first = ctx->pickcFirst.ptr(); a.top = ctx->pickcTop.ptr(); a.state = ctx->pickcWords.ptr();
+	vgx_launch_pick_commands(a, ctx->pickcPartial.p, ctx->opt.pickGrid, s);
 	return launchStatus(ctx);
 }
 

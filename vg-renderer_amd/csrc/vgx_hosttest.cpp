@@ -1173,3 +1173,58 @@ int vgxt_raster_cmds_from_assembly(const vgx_drawcmd* drawcmds, uint64_t num_dra
 }
 
 }
+
+#include "vgx_pick_cmds.h"
+
+extern "C" {
+
+// vgx_pick_commands on the host: the functions of vgx_pick_cmds.h in a plain sequential loop over queries, the commands in ascending
+// order (the stamp S walks with them) and their triangles, with the call's whole contract. HOST pointers, the owners' table included;
+// real_cmds (may be NULL) plays dev_num_cmds. Returns the status the device call returns for these arguments; *status (may be NULL)
+// receives what it leaves in dev_status
+int vgxt_pick_commands(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, const vgx_pick_owners* owners,
+                       const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits, uint32_t* status)
+{
+	const int rc = vgx_pickc_check_args(streams, cmds, num_cmds, real_cmds, owners, queries, nqueries, hits, status);
+	if (rc != VGX_OK) { return rc; }
+	const uint32_t n = real_cmds && *real_cmds < num_cmds ? *real_cmds : num_cmds;
+	std::vector<VgxPickfMesh> state(n);
+	bool invalid = false;
+	for (uint32_t c = 0; c < n; ++c) {
+		vgx_pickc_cmd_state(cmds[c], c, streams->num_vertices, streams->num_indices, n, &state[c]);
+		invalid = invalid || state[c].mode == VGX_RF_INVALID;
+	}
+	if (status) { *status = invalid ? VGX_E_INVALID_ARG : VGX_OK; }
+	for (uint32_t q = 0; q < nqueries; ++q) {
+		const vgx_pick_cmd_query Q = queries[q];
+		double px, py;
+		int32_t X, Y;
+		const bool point = vgx_pickc_point(Q, &px, &py, &X, &Y);
+		uint32_t S = VGX_RASTER_STAMP_NONE, best = VGX_PICK_NONE, bestT = VGX_PICK_NONE;
+		for (uint32_t c = 0; c < n && point && !invalid; ++c) {
+			const VgxPickfMesh& st = state[c];
+			if (!st.elems || !vgx_pickf_in_scissor(st.rect, X, Y)) { continue; }
+			bool counted = false;
+			uint32_t top = VGX_PICK_NONE;
+			for (uint32_t t = 0; t < st.elems; ++t) {
+				uint64_t v[3];
+				if (!vgx_rasterc_triangle(cmds[c], streams->idx, t, v)) { continue; }
+				const float* pp = streams->pos;
+				if (!vgx_pickf_tri(v2(pp[2 * v[0]], pp[2 * v[0] + 1]), v2(pp[2 * v[1]], pp[2 * v[1] + 1]), v2(pp[2 * v[2]], pp[2 * v[2] + 1]), px, py)) { continue; }
+				// a clip command's colours are not read
+				const bool transparent = st.mode != VGX_RF_STAMP && vgx_pick_tri_transparent(streams->color[v[0]], streams->color[v[1]], streams->color[v[2]]);
+				if (vgx_pickc_counts(st.mode, c, t, transparent, Q.cmd_end, Q.tri_end, Q.flags)) { counted = true; top = t; }
+			}
+			if (!counted) { continue; }
+			if (st.mode == VGX_RF_STAMP) { S = c; }
+			else if (vgx_pickc_hit(st.mode, st.f, st.n, S)) { best = c; bestT = top; }
+		}
+		hits[q] = vgx_pickc_record(best, bestT, cmds, owners ? owners->meshes : nullptr, owners ? owners->num_meshes : 0);
+	}
+	return VGX_OK;
+}
+
+// the owner search alone: the mesh that owns position p of the index stream, 0xFFFFFFFF: none
+uint32_t vgxt_pick_owner(const vgx_mesh* meshes, uint64_t num_meshes, uint64_t p) { return vgx_pickc_owner(meshes, num_meshes, p); }
+
+}

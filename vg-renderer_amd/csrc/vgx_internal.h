@@ -462,6 +462,29 @@ struct VgxPickfArgs
 };
 void vgx_launch_pick_frame(const VgxPickfArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, uint32_t grid, hipStream_t s);
 
+// ... of a draw-command table (vgx_pick_cmds.hip): vgx_pick_commands. Nothing is kept per chunk or per triangle: overlapping index
+// ranges leave the chunk total unbounded by the index stream, so every table is sized by num_cmds and nqueries
+struct VgxPickcArgs
+{
+	const float* pos; const uint32_t* color; const uint16_t* idx; // the streams, checked by the host
+	uint64_t num_vertices, num_indices;
+	const vgx_raster_cmd* cmds;       // [num_cmds]
+	const uint32_t* dev_num_cmds;     // or null: the table is cmds[0 .. min(num_cmds, *dev_num_cmds))
+	const vgx_mesh* meshes;           // [num_meshes] the owners, or null
+	uint64_t num_meshes;
+	uint32_t num_cmds;
+	uint32_t nqueries;                // <= VGX_PICK_MAX_QUERIES
+	const vgx_pick_cmd_query* queries;
+	vgx_pick_cmd_hit* hits;
+	uint32_t* status;                 // the caller's dev_status or null
+	VgxPickfMesh* cmd_state;          // [num_cmds] (context scratch, as everything below): vgx_pick_cmds.h's record, VGX_PICKC_CAND beside the mode
+	uint64_t* cmd_first;              // [num_cmds + 1] first chunk of every command, the total behind the real count
+	uint32_t* top;                    // [nqueries][num_cmds] the largest counting triangle + 1 of (query, command), 0: none; zeroed by k_pickc_cmds
+	uint64_t* state;                  // VGX_PICKC_*
+};
+enum { VGX_PICKC_CHUNKS = 0, VGX_PICKC_INVALID = 1, VGX_PICKC_CMDS = 2 /* the real command count */, VGX_PICKC_WORDS = 4 };
+void vgx_launch_pick_commands(const VgxPickcArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, uint32_t grid, hipStream_t s);
+
 // incremental update of a submitted frame (vgx_update.hip)
 struct VgxUpdateArgs
 {

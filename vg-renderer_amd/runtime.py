@@ -905,6 +905,25 @@ def submit_order(draw_cmds, clip_cmds):
     return out[:n.value]
 
 
+# ---- hit testing of a draw-command table (vgx_pick_commands) -----------------------------------------------------------------
+def pick_commands(ctx, streams, cmds_dev, num_cmds, queries_dev, nqueries, meshes_dev=None, num_meshes=0, dev_num_cmds=None, hits_dev=None, dev_status=None):
+    """pick_frame() for the image raster_commands() draws: streams (raster_streams()) and cmds_dev as there; queries_dev a uint8 device
+    tensor of nqueries 24-byte vgx_pick_cmd_query records (capi.pick_cmd_query_dtype: the point, the (cmd_end, tri_end) limit below which
+    hits count -- cmd_end = capi.PICK_NONE: everything -- and the flags of pick()). meshes_dev / num_meshes: the mesh table of the
+    assembled frame, which names the mesh and the draw that own the hit triangle, or None. Returns (hits, dev_status): a uint8 device
+    tensor of nqueries 16-byte vgx_pick_cmd_hit records (capi.pick_cmd_hit_dtype; hits_dev when given) and an int32 [1] tensor that holds
+    VGX_OK, or VGX_E_INVALID_ARG for an invalid record of the table (every hit is "none" then). Asynchronous."""
+    import torch
+    dev = queries_dev.device if queries_dev is not None else "cuda:%d" % ctx.device
+    hits_dev = _hits(hits_dev, nqueries, dev)
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=hits_dev.device)
+    owners = capi.PickOwners(_ptr(meshes_dev, num_meshes), int(num_meshes)) if meshes_dev is not None else None
+    _check(lib().vgx_pick_commands(ctx.handle, C.byref(streams), _ptr(cmds_dev, num_cmds), int(num_cmds), _ptr(dev_num_cmds), C.byref(owners) if owners is not None else None,
+                                   _ptr(queries_dev, nqueries), int(nqueries), hits_dev.data_ptr(), dev_status.data_ptr(), _stream_ptr()), "vgx_pick_commands")
+    return hits_dev, dev_status
+
+
 # ---- incremental update (vgx_cache_layout / vgx_cache_update) ------------------------------------------------------------
 def cache_layout(ctx, cache, inst_dev, ninst, slots_dev=None):
     """Where every instance of `inst_dev` (uint8 device tensor of 40-byte vgx_cache_instance records) lives in the frame cache_submit
