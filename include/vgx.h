@@ -1292,6 +1292,99 @@ int vgx_pick_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx
                       const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits,
                       uint32_t* dev_status /* may be NULL */, void* stream);
 
+/* ---- boxes of a draw-command table: vgx_command_bounds -> vgx_raster_commands_damaged, vgx_pick_commands_boxed -------------------------
+ * A mesh stream has vgx_mesh_bounds, and every call that takes its table skips what a box rules out. A command had no box, so
+ * vgx_pick_commands reads every triangle of the frame, and after a vgx_cache_update of one drawing of an assembled frame only a full
+ * vgx_raster_commands gave a correct image. vgx_command_bounds gives the command table its box table, computed once and refreshed over
+ * the few commands an edit touched; vgx_raster_commands_damaged and vgx_pick_commands_boxed take it. None of them adds coverage or
+ * pixel arithmetic: every rule is an existing one restricted by a box or a bit. All pointers are DEVICE pointers unless marked HOST;
+ * `streams`, `paints`, `target`, `damage` and `owners` are HOST structs.
+ *
+ * vgx_command_bounds.
+ * Range. bounds[c] is written for c in [cmd_begin, min(cmd_end, real count)), the real count being num_cmds cut by *dev_num_cmds as in
+ *   vgx_raster_commands. Entries outside the range are neither written nor read, and records outside it are not looked at: after an
+ *   edit of a few commands only those are recomputed.
+ * Box. bounds[c] = minx, miny, maxx, maxy over the corners of every triangle of command c that vgx_raster_commands draws from: triangle
+ *   t is idx[first_index + 3t .. + 3), t < num_indices / 3, a trailing remainder is ignored; a triangle with an index >= num_vertices
+ *   takes no part; vertex i is pos[first_vertex + i]. A vertex no such triangle names takes no part either. A command with no such
+ *   triangle gets the empty box (+inf, +inf, -inf, -inf).
+ * Values. As vgx_mesh_bounds: minimum and maximum do not depend on the order of evaluation, the values are the same on every run and
+ *   for every decomposition of the work; -0 and +0 compare equal and either may be stored; the result for a NaN position is
+ *   unspecified.
+ * Precondition. None on order or overlap of the commands' vertex and index ranges: that is the difference from vgx_mesh_bounds, whose
+ *   table must ascend. Where a one-mesh-per-command table does ascend and every vertex of a command is named by one of its triangles,
+ *   the two calls give the same table.
+ * dev_status (DEVICE uint32, may be NULL). Decided in one reduction over the range. VGX_E_INVALID_ARG when a record of the range has
+ *   num_vertices > 65536 or a vertex or index range beyond the streams (in 64 bits): such a record gets the empty box, every other box
+ *   is right. Otherwise VGX_OK. type, handle, scissor, the clip fields and `reserved` are not examined: nothing they name is read.
+ * Host return values. VGX_OK once the work is enqueued. VGX_E_INVALID_ARG for a null ctx or streams, null cmds with num_cmds > 0, null
+ *   bounds when [cmd_begin, min(cmd_end, num_cmds)) is not empty, the stream checks of vgx_pick_commands (color and uv are validated
+ *   and never read), misaligned pointers (bounds 16-byte; cmds, pos 8-byte; color, dev_num_cmds, dev_status 4-byte; idx 2-byte).
+ *   VGX_E_HIP for a HIP failure. An empty range is valid: dev_status alone is written.
+ * Side effects. Exactly the entries of the range and dev_status are written. Asynchronous. Scratch of its own -- 8 bytes per command of
+ *   the range, its first chunk of 64 triangles; vgx_scratch_bytes counts it -- so a counted state survives: vgx_tessellate_count ->
+ *   vgx_command_bounds -> vgx_tessellate_emit works, and no table of another call is touched.
+ *
+ * vgx_pick_commands_boxed is vgx_pick_commands word for word -- arguments, point, triangles, scissor, coverage, types, result,
+ * statuses, host return values, side effects and scratch -- with one clause added:
+ * Box. With cmd_bounds != NULL, command c exists at the point of query q only if minx <= x && x <= maxx && miny <= y && y <= maxy for
+ *   the query's x, y and the four floats of cmd_bounds[c], compared in binary32: the closed box, as in vgx_pick. Otherwise it neither
+ *   stamps nor is hit FOR THAT QUERY. An entry with a NaN, and the empty box, hold no point.
+ * cmd_bounds == NULL: vgx_pick_commands word for word. With cmd_bounds holding what vgx_command_bounds gives for the table no answer
+ *   changes: a covering triangle's corners enclose the point, and its command's box encloses them. What the table holds decides, as
+ *   mesh_bounds does in vgx_raster_concave: an entry that is too small hides its command from the points outside it, whether it draws
+ *   or clips. cmd_bounds has [num_cmds][4] floats and is 16-byte aligned (else VGX_E_INVALID_ARG); entries at and behind the real
+ *   count are not read.
+ *
+ * vgx_raster_commands_damaged is vgx_raster_commands word for word -- triangles, order, scissor, types, paints, dev_num_cmds, the
+ * ranking VGX_E_RANGE > VGX_E_INVALID_ARG > VGX_E_GROWN, host return values, side effects -- with two differences:
+ * (a) Bits. A pixel is written, cleared or blended only if it lies inside the image, inside the target's scissor AND in a tile whose
+ *   bit is set in damage->tile_bits: the bitmap of vgx_damage_meshes, with the same numbering (tile (tx, ty) of the image is bit
+ *   ty * TW + tx).
+ * (b) Boxes. With cmd_bounds != NULL, command c takes no part -- it neither draws nor stamps -- when the tiles cmd_bounds[c] reaches
+ *   over the whole image (the span rule vgx_damage_meshes marks by: vgx_damage_box_tiles, whatever the scissors) hold no set bit.
+ *   cmd_bounds must hold what vgx_command_bounds gives for the table; what it holds decides, as mesh_bounds does in
+ *   vgx_raster_concave: an entry that is too small drops its command from tiles it reaches, whether it draws or clips.
+ * VGX_E_INVALID_ARG is decided over every command of the real table, whatever bits and boxes say. With every bit set and boxes true
+ * or NULL the call leaves vgx_raster_commands' bytes and status; with no bit set it writes nothing, the clear included.
+ * The property: let I0 be the image vgx_raster_commands with VGX_RASTER_CLEAR draws of table and streams F0 and I1 that of F1, the
+ * tables of equal length, and let every tile be marked that the vgx_command_bounds box of any command that differs between F0 and F1
+ * (its record, or anything its ranges name) reaches under either frame's boxes. Then vgx_raster_commands_damaged of F1 over I0, with
+ * F1's boxes or NULL, the same target, tables and VGX_RASTER_CLEAR, leaves I1 byte for byte. Proof:
+ *   a sample outside every such box sees the same sequence of effects in both frames, stamps included, so its pixel of I0 is I1's;
+ *   a sample in a marked tile is cleared and receives ALL commands whose box reaches a marked tile -- every command that covers it --
+ *     through the tile's bin entries, as in the full call;
+ *   a sample in an unmarked tile lies outside every such box (a box's tiles hold all its samples) and is not written.
+ * The marks may be finer than the command's box: any boxes that hold every triangle that differs, under both frames, do -- the
+ * vgx_mesh_bounds boxes of the edited meshes of an assembled frame, which vgx_cache_update refreshes, mark less than the box of a
+ * command of many drawings does. The first and the third line hold for them word for word; the second needs F1's COMMAND boxes true.
+ * The chain for an assembled frame, all on one stream: zero the bits; vgx_damage_instances or vgx_damage_meshes (the old boxes:
+ * vgx_damage_meshes takes a command box table as its box table); vgx_cache_update or any edit of the streams; vgx_command_bounds over
+ * the edited commands; the marks again (the new boxes); vgx_raster_commands_damaged with VGX_RASTER_CLEAR.
+ * A bin entry is a pair of a chunk and a MARKED tile inside the chunk's tile rectangle: a chunk that reaches no marked tile costs no
+ * entry. The call sorts a WINDOW of entries by vgx_raster_damaged's rule: min(max_entries, the entry tables' capacity) when
+ * max_entries != 0, else what the previous vgx_raster_commands_damaged on this context measured plus 12.5 % + 256 once that has come
+ * back to the host, else 16384 (cut to chunks x tiles of the scissor in every case). A call with more entries than its window ends
+ * with VGX_E_GROWN: nothing is written, the need comes back to the host behind the call, and the next call -- once the need has
+ * landed -- takes a window of at least that need, max_entries or not: the same call repeated reaches VGX_OK. The count is kept apart
+ * from vgx_raster_commands' and from vgx_raster_damaged's, so a full render in between does not change the window. Chunk capacity
+ * follows vgx_raster_commands' protocol and shares its tables (vgx_raster_commands_reserve sizes both); commands skipped by their box
+ * contribute no chunks, which is the point of (b): without boxes the count pass reads every triangle of the frame.
+ * Host return values and alignment are vgx_raster_commands'; `damage` NULL, damage->tile_bits NULL or misaligned (4-byte),
+ * damage->reserved != 0 or cmd_bounds not 16-byte aligned: VGX_E_INVALID_ARG. Scratch: vgx_raster_commands' tables; a counted state
+ * survives. */
+int vgx_command_bounds(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds,
+                       const uint32_t* dev_num_cmds /* may be NULL */, uint32_t cmd_begin, uint32_t cmd_end,
+                       float* bounds /* DEVICE [num_cmds][4], 16-byte aligned */, uint32_t* dev_status /* may be NULL */, void* stream);
+int vgx_raster_commands_damaged(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds /* DEVICE */, uint32_t num_cmds,
+                                const uint32_t* dev_num_cmds /* may be NULL */, const float* cmd_bounds /* may be NULL */,
+                                const vgx_raster_image* images, uint32_t num_images, const vgx_raster_paints* paints /* may be NULL */,
+                                const vgx_raster_target* target, const vgx_raster_damage* damage, uint32_t* dev_status, void* stream);
+int vgx_pick_commands_boxed(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds,
+                            const uint32_t* dev_num_cmds /* may be NULL */, const float* cmd_bounds /* may be NULL */,
+                            const vgx_pick_owners* owners /* may be NULL */, const vgx_pick_cmd_query* queries, uint32_t nqueries,
+                            vgx_pick_cmd_hit* hits, uint32_t* dev_status /* may be NULL */, void* stream);
+
 /* ---- concave fills with AA fringes -------------------------------------------------
  * strokerConcaveFillEndAA (src/stroker.cpp:868-1006) alternates libtess2 and the stroker's own loops:
  *   (1) tessTesselate(TESS_BOUNDARY_CONTOURS) of the contours added with strokerConcaveFillAddContour     [caller, CPU]

@@ -337,6 +337,11 @@ VGX_SYMBOLS = {
     "vgx_submit_order": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "vgx_pick_commands": (C.c_int, [C.c_void_p, C.POINTER(RasterStreams), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(PickOwners), C.c_void_p, C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "vgx_raster_commands_damaged": (C.c_int, [C.c_void_p, C.POINTER(RasterStreams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.POINTER(RasterPaints), C.POINTER(RasterTarget), C.POINTER(RasterDamage), C.c_void_p, C.c_void_p]),
+    "vgx_command_bounds": (C.c_int, [C.c_void_p, C.POINTER(RasterStreams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vgx_pick_commands_boxed": (C.c_int, [C.c_void_p, C.POINTER(RasterStreams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(PickOwners), C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_last_hip_error":(C.c_int, [C.c_void_p]),
     "vgx_status_string": (C.c_char_p, [C.c_int]),
     "vgx_version": (C.c_uint32, []),

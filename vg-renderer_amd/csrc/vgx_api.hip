@@ -22,6 +22,7 @@
 #include "vgx_damage.h"
 #include "vgx_pick.h"
 #include "vgx_pick_cmds.h"
+#include "vgx_cmd_bounds.h"
 #include "vgx_concave_lane.h"
 #include "vgx_scratch.h"
 #include "vgx_route_plan.h"
@@ -189,10 +190,17 @@ struct vgx_ctx
 	Buf<uint32_t> rascChunkCmd, rascKeys, rascVals, rascSortedKeys, rascSortedVals, rascTilePaint, rascFlag; Buf<unsigned long long> rascState;
 	uint64_t rascChunkCap, rascEntryCap;
 	HostMirror<unsigned long long> rasc;
+	// vgx_raster_commands_damaged: the full call's tables, but a mirror of its own -- the state words of the last DAMAGED commands call --
+	// and what the host learned from it, as rasDmg / dmg* for vgx_raster_damaged: the entry count (the next call's sort window,
+	// vgx_damage.h) and whether that call ended with VGX_E_GROWN. Neither a full vgx_raster_commands nor a vgx_raster_damaged touches them
+	HostMirror<unsigned long long> rascDmg; bool cdmgKnown, cdmgGrown; uint64_t cdmgNeed;
 	// vgx_pick_commands (vgx_pick_cmds.hip): per command its state and its first chunk; per (query, command) the largest hit triangle;
 	// the state words (VGX_PICKC_*); slice sums (views: as `partial`). Its own: a counted state survives the call, and the tables of
 	// vgx_pick, vgx_pick_frame and vgx_raster_commands are not touched
 	Buf<VgxPickfMesh> pickcState; Buf<uint64_t> pickcFirst, pickcWords; Buf<uint32_t> pickcTop; DevBuf pickcPartial;
+	// vgx_command_bounds (vgx_cmd_bounds.hip): the first chunk of every command of the range, the state words (VGX_CMDB_*), slice sums
+	// (views: as `partial`). Its own: a counted state survives the call, and the tables of the calls that take the boxes are not touched
+	Buf<uint64_t> cmdbFirst, cmdbWords; DevBuf cmdbPartial;
 	// vgx_damage_instances (vgx_damage.hip): the flag word (in 16 bytes) and the mesh prefix of the listed entries, the scan's slice sums
 	// (views: as `partial`). Its own: a counted state, and a vgx_cache_update in flight, survive the call
 	DevBuf dmgPrefix, dmgPartial;
@@ -1063,7 +1071,7 @@ int vgx_destroy(vgx_ctx* ctx)
 	vgx_scratch_release(ctx->scratch);
 	if (ctx->hostTotals) { (void)hipHostFree(ctx->hostTotals); }
 	if (ctx->hostF1) { (void)hipHostFree(ctx->hostF1); }
-	ctx->imm.mirror.release(); ctx->dash.release(); ctx->df.release(); ctx->ras.release(); ctx->rasDmg.release(); ctx->rasc.release();
+	ctx->imm.mirror.release(); ctx->dash.release(); ctx->df.release(); ctx->ras.release(); ctx->rasDmg.release(); ctx->rasc.release(); ctx->rascDmg.release();
 	if (ctx->hostPs) { (void)hipHostFree(ctx->hostPs); }
 	if (ctx->psImage) { (void)hipHostFree(ctx->psImage); }
 	for (int i = 0; i < VGX_PS_POOL; ++i) { if (ctx->psPool[i].p) { (void)hipFree(ctx->psPool[i].p); } }
@@ -2643,14 +2651,18 @@ int vgx_pick_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_
 	return launchStatus(ctx);
 }
 
-// ... of a draw-command table: the assembled frame (vgx_pick_cmds.hip). Scratch of its own, sized by the table and the queries alone
-int vgx_pick_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
-                      const vgx_pick_owners* owners, const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits, uint32_t* dev_status, void* stream)
+// ... of a draw-command table: the assembled frame (vgx_pick_cmds.hip). Scratch of its own, sized by the table and the queries alone.
+// The two calls are one body; cmd_bounds (vgx_pick_commands_boxed; else null) picks the kernels that look at the boxes
+namespace {
+
+int pickCommandsCall(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds, const float* cmd_bounds,
+                     const vgx_pick_owners* owners, const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits, uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
 	if (!ctx) { return VGX_E_INVALID_ARG; }
 	int st = vgx_pickc_check_args(streams, cmds, num_cmds, dev_num_cmds, owners, queries, nqueries, hits, dev_status);
 	if (st != VGX_OK) { return st; }
+	if ((uintptr_t)cmd_bounds & 15u) { return VGX_E_INVALID_ARG; }
 	hipStream_t s = (hipStream_t)stream;
 	if ((st = ensure(ctx, ctx->pickcState, (uint64_t)num_cmds + 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->pickcFirst, (uint64_t)num_cmds + 2)) != VGX_OK) { return st; }
@@ -2664,7 +2676,47 @@ int vgx_pick_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx
 	if (owners) { a.meshes = owners->meshes; a.num_meshes = owners->num_meshes; }
 	a.queries = queries; a.nqueries = nqueries; a.hits = hits; a.status = dev_status;
 	a.cmd_state = ctx->pickcState.ptr(); a.cmd_first = ctx->pickcFirst.ptr(); a.top = ctx->pickcTop.ptr(); a.state = ctx->pickcWords.ptr();
+	a.cmd_bounds = num_cmds ? cmd_bounds : nullptr;
 	vgx_launch_pick_commands(a, ctx->pickcPartial.p, ctx->opt.pickGrid, s);
+	return launchStatus(ctx);
+}
+
+} // namespace
+
+int vgx_pick_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
+                      const vgx_pick_owners* owners, const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits, uint32_t* dev_status, void* stream)
+{
+	return pickCommandsCall(ctx, streams, cmds, num_cmds, dev_num_cmds, nullptr, owners, queries, nqueries, hits, dev_status, stream);
+}
+
+int vgx_pick_commands_boxed(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
+                            const float* cmd_bounds, const vgx_pick_owners* owners, const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits,
+                            uint32_t* dev_status, void* stream)
+{
+	return pickCommandsCall(ctx, streams, cmds, num_cmds, dev_num_cmds, cmd_bounds, owners, queries, nqueries, hits, dev_status, stream);
+}
+
+// ---- per-command boxes of a draw-command table (vgx_cmd_bounds.hip) ------------------------------------------------------------------
+// Scratch of its own, sized by the range alone: count -> vgx_command_bounds -> emit still works.
+int vgx_command_bounds(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
+                       uint32_t cmd_begin, uint32_t cmd_end, float* bounds, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx) { return VGX_E_INVALID_ARG; }
+	int st = vgx_cmdb_check_args(streams, cmds, num_cmds, dev_num_cmds, cmd_begin, cmd_end, bounds, dev_status);
+	if (st != VGX_OK) { return st; }
+	hipStream_t s = (hipStream_t)stream;
+	const uint32_t range = vgx_cmdb_range(num_cmds, cmd_begin, cmd_end);
+	if ((st = ensure(ctx, ctx->cmdbFirst, (uint64_t)range + 2)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->cmdbWords, VGX_CMDB_WORDS)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->cmdbPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	VgxCmdBoundsArgs a;
+	memset(&a, 0, sizeof(a));
+	a.pos = streams->pos; a.idx = streams->idx; a.num_vertices = streams->num_vertices; a.num_indices = streams->num_indices;
+	a.cmds = cmds; a.dev_num_cmds = dev_num_cmds; a.num_cmds = num_cmds; a.cmd_begin = cmd_begin; a.cmd_end = cmd_end;
+	a.bounds = (uint32_t*)bounds; a.status = dev_status;
+	a.cmd_first = ctx->cmdbFirst.ptr(); a.state = ctx->cmdbWords.ptr();
+	vgx_launch_command_bounds(a, ctx->cmdbPartial.p, ctx->opt.pickGrid, s);
 	return launchStatus(ctx);
 }
 
@@ -2940,14 +2992,19 @@ int vgx_raster_commands_reserve(vgx_ctx* ctx, uint32_t num_cmds, uint64_t num_ch
 	return rasterCmdsEnsure(ctx, num_cmds, num_chunks, num_bin_entries);
 }
 
-int vgx_raster_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
-                        const vgx_raster_image* images, uint32_t num_images, const vgx_raster_paints* paints, const vgx_raster_target* target,
-                        uint32_t* dev_status, void* stream)
+namespace {
+
+// The two calls are one body. `damage` (vgx_raster_commands_damaged; else null) restricts the call to the marked tiles and gives it a
+// sort window and a mirror of its own; cmd_bounds (with damage alone; may be null) lets a command whose box reaches no marked tile out
+int rasterCommandsCall(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
+                       const float* cmd_bounds, const vgx_raster_image* images, uint32_t num_images, const vgx_raster_paints* paints, const vgx_raster_target* target,
+                       const vgx_raster_damage* damage, uint32_t* dev_status, void* stream)
 {
 	DeviceGuard guard(ctx);
 	if (!ctx) { return VGX_E_INVALID_ARG; }
 	int st = vgx_rasterc_check_args(streams, cmds, num_cmds, dev_num_cmds, images, num_images, paints, target, dev_status);
 	if (st != VGX_OK) { return st; }
+	if (damage && (!damage->tile_bits || ((uintptr_t)damage->tile_bits & 3u) || damage->reserved != 0u || ((uintptr_t)cmd_bounds & 15u))) { return VGX_E_INVALID_ARG; }
 	const vgx_raster_target& t = *target;
 	hipStream_t s = (hipStream_t)stream;
 	if (t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3]) { // no pixel to write
@@ -2961,21 +3018,37 @@ int vgx_raster_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const v
 	a.tiles_x = (t.scissor[2] - 1) / VGX_RASTER_TILE - a.tile_x0 + 1; a.tiles_y = (t.scissor[3] - 1) / VGX_RASTER_TILE - a.tile_y0 + 1;
 	a.sentinel = a.tiles_w * ((t.height + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE); // <= 2^20
 	for (a.sort_bits = 1; (a.sentinel >> a.sort_bits) != 0; ++a.sort_bits) { }
-	if ((st = ctx->rasc.create(ctx, VGX_RASC_WORDS)) != VGX_OK) { return st; }
+	HostMirror<unsigned long long>& mirror = damage ? ctx->rascDmg : ctx->rasc;
+	if ((st = mirror.create(ctx, VGX_RASC_WORDS)) != VGX_OK) { return st; }
 	// the tables: what they hold, at least the first guess of one chunk per command and per 64 triangles of the index stream and as
-	// many entries, and what the last call measured once that has arrived
+	// many entries, and what the last call measured once that has arrived. The chunks of a damaged call follow the same protocol from
+	// its own mirror; its entries are its window's, below
 	uint64_t chunks = (uint64_t)num_cmds + streams->num_indices / (3u * VGX_RASTERC_CHUNK), entries = chunks;
-	if (ctx->rasc.landed() && ctx->rasc.host[VGX_RASC_STATUS] == VGX_E_GROWN) {
-		if (ctx->rasc.host[VGX_RASC_CHUNKS] > chunks) { chunks = ctx->rasc.host[VGX_RASC_CHUNKS]; }
-		if (ctx->rasc.host[VGX_RASC_ENTRIES] > entries) { entries = ctx->rasc.host[VGX_RASC_ENTRIES]; }
+	if (mirror.landed()) {
+		const unsigned long long last = mirror.host[VGX_RASC_STATUS];
+		if (last == VGX_E_GROWN && mirror.host[VGX_RASC_CHUNKS] > chunks) { chunks = mirror.host[VGX_RASC_CHUNKS]; }
+		if (!damage && last == VGX_E_GROWN && mirror.host[VGX_RASC_ENTRIES] > entries) { entries = mirror.host[VGX_RASC_ENTRIES]; }
+		if (damage && (last == VGX_OK || last == VGX_E_GROWN)) { ctx->cdmgKnown = true; ctx->cdmgNeed = mirror.host[VGX_RASC_ENTRIES]; ctx->cdmgGrown = last == VGX_E_GROWN; }
 	}
 	if (chunks > 0xFFFFFFFFull) { chunks = 0xFFFFFFFFull; }
 	if (entries > 0xFFFFFFFFull) { entries = 0xFFFFFFFFull; }
 	if ((st = rasterCmdsEnsure(ctx, num_cmds, chunks, entries)) != VGX_OK) { return st; }
 	a.chunk_cap = ctx->rascChunkCap < 0xFFFFFFFFull ? ctx->rascChunkCap : 0xFFFFFFFFull;
-	a.entry_cap = ctx->rascEntryCap < 0xFFFFFFFFull ? ctx->rascEntryCap : 0xFFFFFFFFull;
 	// no chunk has more entries than the scissor has tiles: the sort need not look further
 	const uint64_t bound = a.chunk_cap * ((uint64_t)a.tiles_x * a.tiles_y);
+	uint64_t window = ~0ull;
+	if (damage) {
+		// The damaged call sorts a window (include/vgx.h), not what a full render left the tables at: the caller's, or the last damaged
+		// commands call's count with head room, or the initial one -- and at least the need of one that ended with VGX_E_GROWN
+		window = damage->max_entries ? (damage->max_entries < ctx->rascEntryCap ? damage->max_entries : ctx->rascEntryCap)
+		                             : (ctx->cdmgKnown ? vgx_damage_head_room(ctx->cdmgNeed) : (uint64_t)VGX_DAMAGE_INITIAL_WINDOW);
+		if (ctx->cdmgGrown && ctx->cdmgNeed > window) { window = vgx_damage_head_room(ctx->cdmgNeed); }
+		if (window > bound) { window = bound; }
+		if (window > 0xFFFFFFFFull) { window = 0xFFFFFFFFull; }
+		if (window > ctx->rascEntryCap && (st = rasterCmdsEnsure(ctx, num_cmds, chunks, window)) != VGX_OK) { return st; }
+	}
+	a.entry_cap = ctx->rascEntryCap < 0xFFFFFFFFull ? ctx->rascEntryCap : 0xFFFFFFFFull;
+	if (window < a.entry_cap) { a.entry_cap = window; }
 	a.sort_n = num_cmds ? (bound < a.entry_cap ? bound : a.entry_cap) : 0;
 	size_t sortBytes = 0;
 	if (a.sort_n) {
@@ -2999,10 +3072,28 @@ int vgx_raster_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const v
 	a.keys = ctx->rascKeys.ptr(); a.vals = ctx->rascVals.ptr(); a.sorted_keys = ctx->rascSortedKeys.ptr(); a.sorted_vals = ctx->rascSortedVals.ptr();
 	a.tile_paint = ctx->rascTilePaint.ptr();
 	a.state = ctx->rascState.ptr(); a.status = dev_status;
+	if (damage) { a.damage = damage->tile_bits; a.cmd_bounds = cmd_bounds; a.width = t.width; a.height = t.height; }
 	noteHip(ctx, vgx_launch_raster_commands(a, ctx->rasPartial.p, ctx->rasSortTemp.p, sortBytes, s));
 	// status and need to the mirror, for the next call (never waited for)
-	ctx->rasc.push(ctx, a.state, s);
+	mirror.push(ctx, a.state, s);
 	return launchStatus(ctx);
+}
+
+} // namespace
+
+int vgx_raster_commands(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
+                        const vgx_raster_image* images, uint32_t num_images, const vgx_raster_paints* paints, const vgx_raster_target* target,
+                        uint32_t* dev_status, void* stream)
+{
+	return rasterCommandsCall(ctx, streams, cmds, num_cmds, dev_num_cmds, nullptr, images, num_images, paints, target, nullptr, dev_status, stream);
+}
+
+int vgx_raster_commands_damaged(vgx_ctx* ctx, const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
+                                const float* cmd_bounds, const vgx_raster_image* images, uint32_t num_images, const vgx_raster_paints* paints,
+                                const vgx_raster_target* target, const vgx_raster_damage* damage, uint32_t* dev_status, void* stream)
+{
+	if (!damage) { return VGX_E_INVALID_ARG; }
+	return rasterCommandsCall(ctx, streams, cmds, num_cmds, dev_num_cmds, cmd_bounds, images, num_images, paints, target, damage, dev_status, stream);
 }
 
 int vgx_raster_cmds_from_assembly(vgx_ctx* ctx, const vgx_drawcmd* drawcmds, uint64_t cap_drawcmds, const uint64_t* dev_num_drawcmds, const vgx_mesh* meshes,

@@ -1015,19 +1015,24 @@ uint64_t vgxt_damage_words(uint32_t width, uint32_t height) { return ((uint64_t)
 }
 
 #include "vgx_raster_cmds.h"
-
-extern "C" {
+#include "vgx_cmd_bounds.h"
 
 // vgx_raster_commands on the host, in the kernels' own decomposition (vgx_raster_cmds.h): the state of every command, the rectangle of
 // tiles of every chunk of 64 triangles, then tile after tile the chunks whose rectangle holds the tile, in ascending order, their
 // triangles tested against the tile cut by both scissors as the tile kernel tests them. HOST pointers, the table, the real count
 // (real_cmds, may be NULL), the images' pixels and the paint tables included. totals (may be NULL) receives the chunks and the bin
-// entries the device call counts. There is no scratch to outgrow here: *status is VGX_OK, VGX_E_INVALID_ARG or VGX_E_RANGE
-int vgxt_raster_commands(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, const vgx_raster_image* images,
-                         uint32_t num_images, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status, uint64_t* totals)
+// entries the device call counts. There is no scratch to outgrow here: *status is VGX_OK, VGX_E_INVALID_ARG or VGX_E_RANGE.
+// `dmg` (vgxt_raster_commands_damaged, else null = every tile) with cmd_bounds (may be NULL): a command whose box reaches no marked tile
+// has no chunks, a bin entry is a pair of a chunk and a MARKED tile, and an unmarked tile is neither cleared nor drawn to (max_entries:
+// there is no sort here, and no window to outgrow)
+static int raster_commands_loop(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, const float* cmd_bounds,
+                                const vgx_raster_image* images, uint32_t num_images, const vgx_raster_paints* paints, const vgx_raster_target* target,
+                                const vgx_raster_damage* dmg, uint32_t* status, uint64_t* totals)
 {
 	const int rc = vgx_rasterc_check_args(streams, cmds, num_cmds, real_cmds, images, num_images, paints, target, status);
 	if (rc != VGX_OK) { return rc; }
+	if (dmg && (!dmg->tile_bits || ((uintptr_t)dmg->tile_bits & 3u) || dmg->reserved != 0u || ((uintptr_t)cmd_bounds & 15u))) { return VGX_E_INVALID_ARG; }
+	const uint32_t* const damage = dmg ? dmg->tile_bits : nullptr;
 	const vgx_raster_target& t = *target;
 	if (status) { *status = VGX_OK; }
 	if (totals) { totals[0] = totals[1] = 0; }
@@ -1046,6 +1051,8 @@ int vgxt_raster_commands(const vgx_raster_streams* streams, const vgx_raster_cmd
 	for (uint32_t c = 0; c < n; ++c) {
 		vgx_rasterc_cmd_state(cmds[c], c, tb, t.x0, t.y0, t.scissor, &state[c]);
 		invalid = invalid || state[c].mode == VGX_RF_INVALID;
+		if (damage && cmd_bounds && state[c].mode != VGX_RF_INVALID && state[c].mode != VGX_RF_NOTHING
+		 && !vgx_cmdb_damaged(cmd_bounds + 4ull * c, damage, t.x0, t.y0, t.width, t.height)) { state[c].mode = VGX_RF_NOTHING; }
 		const uint32_t chunks = vgx_rasterc_state_chunks(cmds[c], state[c]);
 		for (uint32_t k = 0; k < chunks; ++k) {
 			VgxRasterRect r = vgx_rasterc_rect_empty();
@@ -1057,7 +1064,7 @@ int vgxt_raster_commands(const vgx_raster_streams* streams, const vgx_raster_cmd
 				                                                         t.x0, t.y0, state[c].rect));
 			}
 			rect.push_back(r); chunkCmd.push_back(c); chunkTri.push_back(k * VGX_RASTERC_CHUNK);
-			entries += vgx_rasterc_rect_entries(r);
+			entries += damage ? vgx_damage_rect_count(damage, r, vgx_damage_tiles_w(t.width)) : vgx_rasterc_rect_entries(r);
 		}
 	}
 	if (totals) { totals[0] = rect.size(); totals[1] = entries; }
@@ -1069,6 +1076,7 @@ int vgxt_raster_commands(const vgx_raster_streams* streams, const vgx_raster_cmd
 	for (uint32_t ty = tilesY0; ty <= tilesY1; ++ty) {
 		for (uint32_t tx = tilesX0; tx <= tilesX1; ++tx) {
 			const uint32_t ox = tx * VGX_RASTER_TILE, oy = ty * VGX_RASTER_TILE;
+			if (damage && !vgx_damage_bit(damage, ty * vgx_damage_tiles_w(t.width) + tx)) { continue; } // ahead of the clear: the tile is not redrawn
 			uint32_t S[VGX_RASTER_TILE * VGX_RASTER_TILE];
 			for (uint32_t q = 0; q < VGX_RASTER_TILE * VGX_RASTER_TILE; ++q) { S[q] = VGX_RASTER_STAMP_NONE; }
 			if (t.flags & VGX_RASTER_CLEAR) {
@@ -1127,6 +1135,23 @@ int vgxt_raster_commands(const vgx_raster_streams* streams, const vgx_raster_cmd
 	return VGX_OK;
 }
 
+extern "C" {
+
+int vgxt_raster_commands(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, const vgx_raster_image* images,
+                         uint32_t num_images, const vgx_raster_paints* paints, const vgx_raster_target* target, uint32_t* status, uint64_t* totals)
+{
+	return raster_commands_loop(streams, cmds, num_cmds, real_cmds, nullptr, images, num_images, paints, target, nullptr, status, totals);
+}
+
+// vgx_raster_commands_damaged on the host: the same loop inside the marked tiles alone, the commands their boxes let out skipped
+int vgxt_raster_commands_damaged(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, const float* cmd_bounds,
+                                 const vgx_raster_image* images, uint32_t num_images, const vgx_raster_paints* paints, const vgx_raster_target* target,
+                                 const vgx_raster_damage* damage, uint32_t* status, uint64_t* totals)
+{
+	if (!damage) { return VGX_E_INVALID_ARG; }
+	return raster_commands_loop(streams, cmds, num_cmds, real_cmds, cmd_bounds, images, num_images, paints, target, damage, status, totals);
+}
+
 // vgx_raster_cmds_from_assembly on the host: one record per draw command, the clip region mapped from draws to commands by two searches
 int vgxt_raster_cmds_from_assembly(const vgx_drawcmd* drawcmds, uint64_t num_drawcmds, const vgx_mesh* meshes, uint64_t num_meshes, const vgx_raster_draws* state,
                                    vgx_raster_cmd* out, uint32_t* num_cmds, uint32_t* status)
@@ -1176,17 +1201,17 @@ int vgxt_raster_cmds_from_assembly(const vgx_drawcmd* drawcmds, uint64_t num_dra
 
 #include "vgx_pick_cmds.h"
 
-extern "C" {
-
 // vgx_pick_commands on the host: the functions of vgx_pick_cmds.h in a plain sequential loop over queries, the commands in ascending
 // order (the stamp S walks with them) and their triangles, with the call's whole contract. HOST pointers, the owners' table included;
 // real_cmds (may be NULL) plays dev_num_cmds. Returns the status the device call returns for these arguments; *status (may be NULL)
 // receives what it leaves in dev_status
-int vgxt_pick_commands(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, const vgx_pick_owners* owners,
-                       const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits, uint32_t* status)
+// cmd_bounds (may be NULL) is the one clause vgx_pick_commands_boxed adds (vgx_cmd_bounds.h: vgx_cmdb_holds)
+static int pick_commands_loop(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, const float* cmd_bounds,
+                              const vgx_pick_owners* owners, const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits, uint32_t* status)
 {
 	const int rc = vgx_pickc_check_args(streams, cmds, num_cmds, real_cmds, owners, queries, nqueries, hits, status);
 	if (rc != VGX_OK) { return rc; }
+	if ((uintptr_t)cmd_bounds & 15u) { return VGX_E_INVALID_ARG; }
 	const uint32_t n = real_cmds && *real_cmds < num_cmds ? *real_cmds : num_cmds;
 	std::vector<VgxPickfMesh> state(n);
 	bool invalid = false;
@@ -1203,7 +1228,7 @@ int vgxt_pick_commands(const vgx_raster_streams* streams, const vgx_raster_cmd* 
 		uint32_t S = VGX_RASTER_STAMP_NONE, best = VGX_PICK_NONE, bestT = VGX_PICK_NONE;
 		for (uint32_t c = 0; c < n && point && !invalid; ++c) {
 			const VgxPickfMesh& st = state[c];
-			if (!st.elems || !vgx_pickf_in_scissor(st.rect, X, Y)) { continue; }
+			if (!st.elems || !vgx_pickf_in_scissor(st.rect, X, Y) || (cmd_bounds && !vgx_cmdb_holds(cmd_bounds + 4ull * c, Q.x, Q.y))) { continue; }
 			bool counted = false;
 			uint32_t top = VGX_PICK_NONE;
 			for (uint32_t t = 0; t < st.elems; ++t) {
@@ -1224,7 +1249,47 @@ int vgxt_pick_commands(const vgx_raster_streams* streams, const vgx_raster_cmd* 
 	return VGX_OK;
 }
 
+extern "C" {
+
+// vgx_pick_commands on the host: the loop above without boxes
+int vgxt_pick_commands(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, const vgx_pick_owners* owners,
+                       const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits, uint32_t* status)
+{
+	return pick_commands_loop(streams, cmds, num_cmds, real_cmds, nullptr, owners, queries, nqueries, hits, status);
+}
+
+// vgx_pick_commands_boxed on the host: the same loop with the box clause of vgx_cmd_bounds.h (vgx_cmdb_holds); cmd_bounds may be NULL
+int vgxt_pick_commands_boxed(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, const float* cmd_bounds,
+                             const vgx_pick_owners* owners, const vgx_pick_cmd_query* queries, uint32_t nqueries, vgx_pick_cmd_hit* hits, uint32_t* status)
+{
+	return pick_commands_loop(streams, cmds, num_cmds, real_cmds, cmd_bounds, owners, queries, nqueries, hits, status);
+}
+
 // the owner search alone: the mesh that owns position p of the index stream, 0xFFFFFFFF: none
 uint32_t vgxt_pick_owner(const vgx_mesh* meshes, uint64_t num_meshes, uint64_t p) { return vgx_pickc_owner(meshes, num_meshes, p); }
+
+// vgx_command_bounds on the host: the functions of vgx_cmd_bounds.h command after command and triangle after triangle over the range,
+// the order-preserving images decoded at the end as the call's last kernel does. HOST pointers; real_cmds (may be NULL) plays
+// dev_num_cmds. Returns the status the device call returns for these arguments; *status (may be NULL) receives what it leaves in
+// dev_status. Entries outside the range are not written
+int vgxt_command_bounds(const vgx_raster_streams* streams, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* real_cmds, uint32_t cmd_begin, uint32_t cmd_end,
+                        float* bounds, uint32_t* status)
+{
+	const int rc = vgx_cmdb_check_args(streams, cmds, num_cmds, real_cmds, cmd_begin, cmd_end, bounds, status);
+	if (rc != VGX_OK) { return rc; }
+	const uint32_t n = vgx_cmdb_range(real_cmds && *real_cmds < num_cmds ? *real_cmds : num_cmds, cmd_begin, cmd_end);
+	bool invalid = false;
+	for (uint32_t i = 0; i < n; ++i) {
+		const vgx_raster_cmd& c = cmds[cmd_begin + i];
+		const uint32_t chunks = vgx_cmdb_chunks(c, streams->num_vertices, streams->num_indices);
+		invalid = invalid || !vgx_cmdb_valid(c, streams->num_vertices, streams->num_indices);
+		VgxOrdBox b = vgx_ordbox_empty();
+		for (uint64_t t = 0; t < (uint64_t)chunks * VGX_RASTERC_CHUNK; ++t) { b = vgx_ordbox_union(b, vgx_cmdb_triangle(c, streams->idx, streams->pos, (uint32_t)t)); }
+		float* e = bounds + 4ull * (cmd_begin + i);
+		e[0] = vgx_float_from_ord(b.minx); e[1] = vgx_float_from_ord(b.miny); e[2] = vgx_float_from_ord(b.maxx); e[3] = vgx_float_from_ord(b.maxy);
+	}
+	if (status) { *status = invalid ? VGX_E_INVALID_ARG : VGX_OK; }
+	return VGX_OK;
+}
 
 }

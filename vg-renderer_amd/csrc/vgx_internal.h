@@ -481,9 +481,27 @@ struct VgxPickcArgs
 	uint64_t* cmd_first;              // [num_cmds + 1] first chunk of every command, the total behind the real count
 	uint32_t* top;                    // [nqueries][num_cmds] the largest counting triangle + 1 of (query, command), 0: none; zeroed by k_pickc_cmds
 	uint64_t* state;                  // VGX_PICKC_*
+	const float* cmd_bounds;          // vgx_pick_commands_boxed: [num_cmds][4], 16-byte aligned, or null. Read by the BOXED instantiations alone
 };
 enum { VGX_PICKC_CHUNKS = 0, VGX_PICKC_INVALID = 1, VGX_PICKC_CMDS = 2 /* the real command count */, VGX_PICKC_WORDS = 4 };
 void vgx_launch_pick_commands(const VgxPickcArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, uint32_t grid, hipStream_t s);
+
+// per-command boxes of a draw-command table (vgx_cmd_bounds.hip): vgx_command_bounds. The commands looked at are those of the range,
+// [cmd_begin, min(cmd_end, real count)); command i of the range is cmds[cmd_begin + i]
+struct VgxCmdBoundsArgs
+{
+	const float* pos; const uint16_t* idx; // the streams, checked by the host
+	uint64_t num_vertices, num_indices;
+	const vgx_raster_cmd* cmds;       // [num_cmds]
+	const uint32_t* dev_num_cmds;     // or null: the table is cmds[0 .. min(num_cmds, *dev_num_cmds))
+	uint32_t num_cmds, cmd_begin, cmd_end;
+	uint32_t* bounds;                 // the caller's [num_cmds][4], 16-byte aligned: order-preserving images until k_cmdb_decode
+	uint32_t* status;                 // the caller's dev_status or null
+	uint64_t* cmd_first;              // [range + 1] (context scratch, as `state`): first chunk of every command of the range, the total behind them
+	uint64_t* state;                  // VGX_CMDB_*
+};
+enum { VGX_CMDB_CHUNKS = 0, VGX_CMDB_CMDS = 1 /* the commands of the range */, VGX_CMDB_WORDS = 2 };
+void vgx_launch_command_bounds(const VgxCmdBoundsArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, uint32_t grid, hipStream_t s);
 
 // incremental update of a submitted frame (vgx_update.hip)
 struct VgxUpdateArgs
@@ -592,6 +610,9 @@ struct VgxRasterCmdArgs
 	uint32_t* tile_paint;             // [(sentinel + 31) / 32] one bit per tile of the image, zero at the launch: a painted command has an entry there
 	unsigned long long* state;        // VGX_RASC_*: what the pinned mirror carries to the next call
 	uint32_t* status;                 // the caller's dev_status or null
+	const uint32_t* damage;           // vgx_raster_commands_damaged: the tile bits (vgx_damage.h); else null. Read by the DAMAGE instantiations alone
+	const float* cmd_bounds;          // ... its [num_cmds][4] boxes, 16-byte aligned, or null: no command is skipped by its box
+	uint32_t width, height;           // ... the image, for the tiles a box reaches
 };
 enum { VGX_RASC_STATUS = 0, VGX_RASC_ENTRIES = 1, VGX_RASC_CHUNKS = 2, VGX_RASC_INVALID = 3, VGX_RASC_BEYOND = 4 /* entries of the chunks behind chunk_cap */,
        VGX_RASC_CMDS = 5 /* the real command count */, VGX_RASC_WORDS = 6 };

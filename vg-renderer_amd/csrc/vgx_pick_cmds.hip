@@ -1,4 +1,5 @@
-// vgx_pick_cmds.hip -- hit testing of a draw-command table on gfx950 (include/vgx.h: vgx_pick_commands; the rules: vgx_pick_cmds.h).
+// vgx_pick_cmds.hip -- hit testing of a draw-command table on gfx950 (include/vgx.h: vgx_pick_commands, vgx_pick_commands_boxed; the rules:
+// vgx_pick_cmds.h, vgx_cmd_bounds.h).
 //
 // vgx_pick_frame compacts candidate MESHES by their boxes and keeps one covered bit per (candidate, query). A command has no box and
 // holds tens of thousands of triangles, and the caller wants the triangle, not only the command: the limit of a click-through lies
@@ -22,10 +23,14 @@
 //                    "the last covering clip command so far", carried across blocks, then the stamp test; the answer is the highest
 //                    passing command, its triangle is the table's word. One lane does the owner search and writes the record
 // Maxima only: the result does not depend on the order of the work.
+// vgx_pick_commands_boxed runs the BOXED instantiations of k_pickc_cmds and k_pickc_tris: a command is a candidate only when some point
+// lies in its scissor AND in its entry of the caller's box table (vgx_cmd_bounds.h), so a boxed-out command gets no chunks, and the
+// per-query scalar tests of k_pickc_tris gain the same clause. vgx_pick_commands keeps the instantiations without it.
 #include "vgx_internal.h"
 #include "vgx_wave.h"
 #include "vgx_scan.h"
 #include "vgx_pick_cmds.h"
+#include "vgx_cmd_bounds.h"
 
 namespace {
 
@@ -50,6 +55,9 @@ __device__ __forceinline__ uint32_t pickc_real_cmds(const VgxPickcArgs& A)
 	return n < A.num_cmds ? n : A.num_cmds;
 }
 
+// BOXED (vgx_pick_commands_boxed): a command is a candidate only when some point also lies in its box. vgx_pick_commands launches the
+// instantiations without it, which hold none of its code
+template<bool BOXED>
 __global__ __launch_bounds__(256) void k_pickc_cmds(VgxPickcArgs A)
 {
 	__shared__ PickcQuery s_q[VGX_PICK_MAX_QUERIES];
@@ -64,9 +72,11 @@ __global__ __launch_bounds__(256) void k_pickc_cmds(VgxPickcArgs A)
 		vgx_pickc_cmd_state(A.cmds[c], (uint32_t)c, A.num_vertices, A.num_indices, n, &st);
 		if (st.mode != VGX_RF_INVALID && st.elems) {
 			bool cand = false;
+			float box[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+			if (BOXED) { const float4 b = *(const float4*)(A.cmd_bounds + 4ull * c); box[0] = b.x; box[1] = b.y; box[2] = b.z; box[3] = b.w; }
 			for (uint32_t q = 0; q < A.nqueries; ++q) {
 				const PickcQuery Q = s_q[q];
-				cand = cand || ((Q.flags & VGX_PICKC_VALID) && vgx_pickf_in_scissor(st.rect, Q.X, Q.Y));
+				cand = cand || ((Q.flags & VGX_PICKC_VALID) && vgx_pickf_in_scissor(st.rect, Q.X, Q.Y) && (!BOXED || vgx_cmdb_holds(box, Q.x, Q.y)));
 			}
 			if (cand) { st.mode |= VGX_PICKC_CAND; }
 		}
@@ -110,6 +120,7 @@ __device__ __forceinline__ float pickc_wave_max(float v)
 	return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
+template<bool BOXED>
 __global__ __launch_bounds__(256) void k_pickc_tris(VgxPickcArgs A)
 {
 	__shared__ PickcQuery s_q[VGX_PICK_MAX_QUERIES];
@@ -155,10 +166,13 @@ __global__ __launch_bounds__(256) void k_pickc_tris(VgxPickcArgs A)
 	uint64_t first = A.cmd_first[c], next = A.cmd_first[c + 1u];
 	vgx_raster_cmd cmd = A.cmds[c];
 	VgxPickfMesh st = A.cmd_state[c];
+	float box[4] = { 0.0f, 0.0f, 0.0f, 0.0f }; // BOXED: the command's entry, wave-uniform as the record and the state are
+	if (BOXED) { const float4 b = *(const float4*)(A.cmd_bounds + 4ull * c); box[0] = b.x; box[1] = b.y; box[2] = b.z; box[3] = b.w; }
 	for (uint64_t k = k0; k < k1; ++k) {
 		if (k >= next) { // cmd_first[n] = total > k: the walk ends inside the table; commands without chunks are passed over
 			do { ++c; first = next; next = A.cmd_first[c + 1u]; } while (k >= next);
 			cmd = A.cmds[c]; st = A.cmd_state[c];
+			if (BOXED) { const float4 b = *(const float4*)(A.cmd_bounds + 4ull * c); box[0] = b.x; box[1] = b.y; box[2] = b.z; box[3] = b.w; }
 		}
 		const uint32_t mode = st.mode & 0xFFu;
 		const uint32_t t0 = (uint32_t)(k - first) * VGX_RASTERC_CHUNK;
@@ -185,7 +199,7 @@ __global__ __launch_bounds__(256) void k_pickc_tris(VgxPickcArgs A)
 		for (uint32_t k2 = qa; k2 < nvalid && !any; ++k2) {
 			const PickcQuery Q = s_q[k2];
 			if (Q.x > bx1) { break; }
-			any = !(Q.y < by0) && !(Q.y > by1) && vgx_pickf_in_scissor(st.rect, Q.X, Q.Y);
+			any = !(Q.y < by0) && !(Q.y > by1) && vgx_pickf_in_scissor(st.rect, Q.X, Q.Y) && (!BOXED || vgx_cmdb_holds(box, Q.x, Q.y));
 		}
 		if (!any) { continue; }
 		VgxRasterTri Tri;
@@ -198,7 +212,7 @@ __global__ __launch_bounds__(256) void k_pickc_tris(VgxPickcArgs A)
 		for (uint32_t k2 = qa; k2 < nvalid; ++k2) {
 			const PickcQuery Q = s_q[k2];
 			if (Q.x > bx1) { break; }
-			if (Q.y < by0 || Q.y > by1 || !vgx_pickf_in_scissor(st.rect, Q.X, Q.Y)) { continue; }
+			if (Q.y < by0 || Q.y > by1 || !vgx_pickf_in_scissor(st.rect, Q.X, Q.Y) || (BOXED && !vgx_cmdb_holds(box, Q.x, Q.y))) { continue; }
 			const double px = (double)Q.x, py = (double)Q.y;
 			if (mode != VGX_RF_STAMP && !vgx_pickc_below(c, t0, Q.cmd_end, Q.tri_end)) { continue; } // the limit lies at or below the chunk's first triangle
 			double E[3], S;
@@ -268,11 +282,14 @@ void vgx_launch_pick_commands(const VgxPickcArgs& a, void* partial, uint32_t gri
 	if (a.num_cmds) {
 		const uint64_t items = (uint64_t)a.num_cmds * (a.nqueries ? a.nqueries : 1u);
 		const uint64_t blocks = (items + 255u) / 256u;
-		hipLaunchKernelGGL(k_pickc_cmds, dim3((unsigned)(blocks < 1024u ? blocks : 1024u)), dim3(256), 0, s, a);
+		const dim3 g((unsigned)(blocks < 1024u ? blocks : 1024u));
+		if (a.cmd_bounds) { hipLaunchKernelGGL(k_pickc_cmds<true>, g, dim3(256), 0, s, a); } else { hipLaunchKernelGGL(k_pickc_cmds<false>, g, dim3(256), 0, s, a); }
 	}
 	const OpPickcCmds op = { a };
 	vgx_device_scan(op, (Sum3*)partial, s, a.num_cmds); // an empty table too: it leaves the totals and the status
 	if (!a.nqueries) { return; }
-	if (a.num_cmds) { hipLaunchKernelGGL(k_pickc_tris, dim3(grid), dim3(256), 0, s, a); }
+	if (a.num_cmds) {
+		if (a.cmd_bounds) { hipLaunchKernelGGL(k_pickc_tris<true>, dim3(grid), dim3(256), 0, s, a); } else { hipLaunchKernelGGL(k_pickc_tris<false>, dim3(grid), dim3(256), 0, s, a); }
+	}
 	hipLaunchKernelGGL(k_pickc_resolve, dim3(a.nqueries), dim3(256), 0, s, a);
 }

@@ -23,11 +23,14 @@
 //                      functions of vgx_raster.h; d and the stamp S live in registers across the trips. Per-command state is kept for
 //                      the four slots of a trip. A tile a painted command reaches runs <true>, every other tile <false>, which
 //                      carries no paint code (DESIGN.md has the resource report).
+// vgx_raster_commands_damaged runs the DAMAGE instantiations of the same kernels (k_rasterc_cmds: the box test; count, scan and
+// entries: marked tiles only; tiles: an unmarked tile returns ahead of the clear); vgx_raster_commands keeps those without it.
 #include "vgx_internal.h"
 #include "vgx_wave.h"
 #include "vgx_scan.h"
 #include "vgx_raster_cmds.h"
 #include "vgx_damage.h"
+#include "vgx_cmd_bounds.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace {
@@ -48,6 +51,11 @@ __device__ __forceinline__ VgxRastercTables rasterc_tables(const VgxRasterCmdArg
 	return tb;
 }
 
+// DAMAGE (vgx_raster_commands_damaged; vgx_raster_commands runs the instantiations without it, which hold none of its code): a bin
+// entry is a pair of a chunk and a MARKED tile (A.damage, vgx_damage.h), an unmarked tile is left alone ahead of the clear, and with
+// A.cmd_bounds a VALID command whose box reaches no marked tile does nothing: no chunks, so the count pass never reads its triangles.
+// An invalid record stays invalid whatever its box says
+template <bool DAMAGE>
 __global__ __launch_bounds__(256) void k_rasterc_cmds(VgxRasterCmdArgs A)
 {
 	const uint32_t n = rasterc_real_cmds(A);
@@ -55,8 +63,20 @@ __global__ __launch_bounds__(256) void k_rasterc_cmds(VgxRasterCmdArgs A)
 	for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (uint64_t)gridDim.x * blockDim.x) {
 		VgxRasterMeshState st;
 		vgx_rasterc_cmd_state(A.cmds[c], (uint32_t)c, tb, A.x0, A.y0, A.scissor, &st);
+		if (DAMAGE && A.cmd_bounds && st.mode != VGX_RF_INVALID && st.mode != VGX_RF_NOTHING) {
+			const float4 b = *(const float4*)(A.cmd_bounds + 4ull * c);
+			const float box[4] = { b.x, b.y, b.z, b.w };
+			if (!vgx_cmdb_damaged(box, A.damage, A.x0, A.y0, A.width, A.height)) { st.mode = VGX_RF_NOTHING; }
+		}
 		A.cmd_state[c] = st;
 	}
+}
+
+// the bin entries of a chunk whose triangles reach the tiles of r
+template <bool DAMAGE>
+__device__ __forceinline__ uint32_t rasterc_entries_of(const VgxRasterCmdArgs& A, const VgxRasterRect& r)
+{
+	return DAMAGE ? vgx_damage_rect_count(A.damage, r, A.tiles_w) : vgx_rasterc_rect_entries(r);
 }
 
 struct OpRastercCmds
@@ -93,6 +113,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
 	return v;
 }
 
+template <bool DAMAGE>
 __global__ __launch_bounds__(256) void k_rasterc_count(VgxRasterCmdArgs A)
 {
 	const uint64_t total = A.state[VGX_RASC_CHUNKS];
@@ -115,7 +136,7 @@ __global__ __launch_bounds__(256) void k_rasterc_count(VgxRasterCmdArgs A)
 		r.tx0 = wave_min_u32(r.tx0); r.ty0 = wave_min_u32(r.ty0); r.tx1 = wave_max_u32(r.tx1); r.ty1 = wave_max_u32(r.ty1);
 		if (lane == 0) {
 			if (k < A.chunk_cap) { A.chunk_rect[k] = r; A.chunk_cmd[k] = c; }
-			else { atomicAdd(&A.state[VGX_RASC_BEYOND], (unsigned long long)vgx_rasterc_rect_entries(r)); }
+			else { atomicAdd(&A.state[VGX_RASC_BEYOND], (unsigned long long)rasterc_entries_of<DAMAGE>(A, r)); }
 		}
 	}
 }
@@ -126,6 +147,7 @@ __device__ __forceinline__ uint64_t rasterc_stored_chunks(const VgxRasterCmdArgs
 	return total > 0xFFFFFFFFull ? 0ull : (total < A.chunk_cap ? total : A.chunk_cap);
 }
 
+template <bool DAMAGE>
 struct OpRastercBin
 {
 	VgxRasterCmdArgs A;
@@ -133,7 +155,7 @@ struct OpRastercBin
 	__device__ Sum3 load(uint64_t i) const
 	{
 		Sum3 r = sum3_zero();
-		r.a = vgx_rasterc_rect_entries(A.chunk_rect[i]);
+		r.a = rasterc_entries_of<DAMAGE>(A, A.chunk_rect[i]);
 		return r;
 	}
 	__device__ void store(uint64_t i, Sum3 e) const { A.chunk_first[i] = e.a; }
@@ -146,6 +168,7 @@ struct OpRastercBin
 	}
 };
 
+template <bool DAMAGE>
 __global__ __launch_bounds__(256) void k_rasterc_entries(VgxRasterCmdArgs A)
 {
 	if (A.state[VGX_RASC_STATUS] != VGX_OK) { return; }
@@ -157,7 +180,12 @@ __global__ __launch_bounds__(256) void k_rasterc_entries(VgxRasterCmdArgs A)
 	if (vgx_rasterc_rect_is_empty(r)) { return; }
 	uint64_t at = A.chunk_first[k]; // + the chunk's entries <= the total <= entry_cap: checked by finish()
 	for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty) {
-		for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx, ++at) { A.keys[at] = ty * A.tiles_w + tx; A.vals[at] = (uint32_t)k; }
+		for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx) {
+			const uint32_t key = ty * A.tiles_w + tx;
+			if (DAMAGE && !vgx_damage_bit(A.damage, key)) { continue; } // as many pass as the scan found: the bits do not change under the call
+			A.keys[at] = key; A.vals[at] = (uint32_t)k;
+			++at;
+		}
 	}
 	if (A.cmd_state[A.chunk_cmd[k]].pad & VGX_RT_PAINTED) { mark_tiles(A.tile_paint, r, A.tiles_w); }
 }
@@ -196,7 +224,7 @@ template <> struct RastercPaintSlot<true> { typedef VgxRasterPaint type; };
 __device__ __forceinline__ vgx_raster_image& slot_image(vgx_raster_image& s) { return s; }
 __device__ __forceinline__ vgx_raster_image& slot_image(VgxRasterPaint& s) { return s.im; }
 
-template <bool PAINT>
+template <bool PAINT, bool DAMAGE>
 __global__ __launch_bounds__(256) void k_rasterc_tiles(VgxRasterCmdArgs A)
 {
 	typedef typename RastercPaintSlot<PAINT>::type Paint;
@@ -207,6 +235,7 @@ __global__ __launch_bounds__(256) void k_rasterc_tiles(VgxRasterCmdArgs A)
 	if (A.state[VGX_RASC_STATUS] != VGX_OK) { return; }
 	const uint32_t tx = A.tile_x0 + blockIdx.x, ty = A.tile_y0 + blockIdx.y;
 	const uint32_t key = ty * A.tiles_w + tx;
+	if (DAMAGE && !vgx_damage_bit(A.damage, key)) { return; } // block-uniform, ahead of the clear: the tile is not redrawn
 	if ((((A.tile_paint[key >> 5] >> (key & 31u)) & 1u) != 0u) != PAINT) { return; } // block-uniform: the tile of the other instantiation
 	const uint32_t tid = threadIdx.x;
 	const int lane = tid & (VGX_WAVE - 1);
@@ -404,32 +433,43 @@ __global__ void k_raster_cmds_finish(VgxCmdsFromAsmArgs a)
 
 } // namespace
 
-hipError_t vgx_launch_raster_commands(const VgxRasterCmdArgs& a, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
+namespace {
+
+template <bool DAMAGE>
+hipError_t launch_commands(const VgxRasterCmdArgs& a, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
 {
 	if (a.num_cmds) {
 		const uint64_t blocks = ((uint64_t)a.num_cmds + 255u) / 256u;
-		hipLaunchKernelGGL(k_rasterc_cmds, dim3((unsigned)(blocks < 1024u ? blocks : 1024u)), dim3(256), 0, s, a);
+		hipLaunchKernelGGL(k_rasterc_cmds<DAMAGE>, dim3((unsigned)(blocks < 1024u ? blocks : 1024u)), dim3(256), 0, s, a);
 	}
 	const OpRastercCmds cmds = { a };
 	vgx_device_scan(cmds, (Sum3*)partial, s, a.num_cmds);
 	if (a.num_cmds) { // the chunk count lives on the device: a fixed grid of waves, each striding over the chunks
 		const uint64_t blocks = (a.chunk_cap + 3u) / 4u;
-		hipLaunchKernelGGL(k_rasterc_count, dim3((unsigned)(blocks < 1u ? 1u : (blocks < 4096u ? blocks : 4096u))), dim3(256), 0, s, a);
+		hipLaunchKernelGGL(k_rasterc_count<DAMAGE>, dim3((unsigned)(blocks < 1u ? 1u : (blocks < 4096u ? blocks : 4096u))), dim3(256), 0, s, a);
 	}
-	const OpRastercBin bin = { a };
+	const OpRastercBin<DAMAGE> bin = { a };
 	vgx_device_scan(bin, (Sum3*)partial, s, a.chunk_cap);
 	const uint64_t items = a.chunk_cap > a.sort_n ? a.chunk_cap : a.sort_n;
-	if (items) { hipLaunchKernelGGL(k_rasterc_entries, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a); }
+	if (items) { hipLaunchKernelGGL(k_rasterc_entries<DAMAGE>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a); }
 	if (a.sort_n) {
 		const hipError_t e = rocprim::radix_sort_pairs(sortTemp, sortBytes, (const uint32_t*)a.keys, a.sorted_keys, (const uint32_t*)a.vals, a.sorted_vals,
 		                                               (size_t)a.sort_n, 0u, a.sort_bits, s);
 		if (e != hipSuccess) { return e; }
 	}
 	if (a.tiles_x && a.tiles_y) {
-		hipLaunchKernelGGL(k_rasterc_tiles<false>, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, a);
-		if (a.num_gradients || a.num_patterns) { hipLaunchKernelGGL(k_rasterc_tiles<true>, dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, a); }
+		hipLaunchKernelGGL((k_rasterc_tiles<false, DAMAGE>), dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, a);
+		if (a.num_gradients || a.num_patterns) { hipLaunchKernelGGL((k_rasterc_tiles<true, DAMAGE>), dim3(a.tiles_x, a.tiles_y), dim3(256), 0, s, a); }
 	}
 	return hipSuccess;
+}
+
+} // namespace
+
+// a.damage set: vgx_raster_commands_damaged
+hipError_t vgx_launch_raster_commands(const VgxRasterCmdArgs& a, void* partial, void* sortTemp, size_t sortBytes, hipStream_t s)
+{
+	return a.damage ? launch_commands<true>(a, partial, sortTemp, sortBytes, s) : launch_commands<false>(a, partial, sortTemp, sortBytes, s);
 }
 
 void vgx_launch_cmds_from_assembly(const VgxCmdsFromAsmArgs& a, hipStream_t s)

@@ -843,7 +843,7 @@ def raster_streams(pos_dev, color_dev, idx_dev, num_vertices, num_indices, uv_de
 
 
 def raster_commands(ctx, streams, cmds_dev, num_cmds, width, height, images_dev=None, num_images=0, gradients_dev=None, num_gradients=0, patterns_dev=None,
-                    num_patterns=0, x0=0, y0=0, scissor=None, clear_color=None, dev_num_cmds=None, image=None, dev_status=None):
+                    num_patterns=0, x0=0, y0=0, scissor=None, clear_color=None, dev_num_cmds=None, image=None, dev_status=None, _damage=None):
     """Draws a draw-command table into an RGBA8 image on the device: cmds_dev is a uint8 device tensor of num_cmds 56-byte vgx_raster_cmd
     records (capi.raster_cmd_dtype; what raster_cmds_from_assembly() wrote, or the reference's tables through submit_order()), streams a
     capi.RasterStreams (raster_streams()). Command c is cut by its scissor, stamps its index (type 3) or is tested against the command
@@ -858,10 +858,25 @@ def raster_commands(ctx, streams, cmds_dev, num_cmds, width, height, images_dev=
         dev_status = torch.empty(1, dtype=torch.int32, device=image.device)
     paints = capi.RasterPaints(_ptr(gradients_dev, num_gradients), _ptr(patterns_dev, num_patterns), int(num_gradients), int(num_patterns))
     tgt = _raster_target(image.data_ptr(), width, height, image.stride(0) if image.dim() == 2 and height else width, x0, y0, scissor, clear_color)
-    _check(lib().vgx_raster_commands(ctx.handle, C.byref(streams), _ptr(cmds_dev, num_cmds), int(num_cmds), _ptr(dev_num_cmds), _ptr(images_dev, num_images),
-                                     int(num_images), C.byref(paints) if (num_gradients or num_patterns) else None, C.byref(tgt), dev_status.data_ptr(), _stream_ptr()),
-           "vgx_raster_commands")
+    # _damage = (tile_bits, max_entries, bounds_dev): the arguments the damaged entry adds -- the boxes behind dev_num_cmds, the struct behind the target
+    entry = "vgx_raster_commands" if _damage is None else "vgx_raster_commands_damaged"
+    boxes = () if _damage is None else (_ptr(_damage[2], num_cmds),)
+    dmg = () if _damage is None else (C.byref(capi.RasterDamage(_damage[0].data_ptr(), int(_damage[1]), 0)),)
+    _check(getattr(lib(), entry)(ctx.handle, C.byref(streams), _ptr(cmds_dev, num_cmds), int(num_cmds), _ptr(dev_num_cmds), *boxes, _ptr(images_dev, num_images),
+                                 int(num_images), C.byref(paints) if (num_gradients or num_patterns) else None, C.byref(tgt), *dmg, dev_status.data_ptr(), _stream_ptr()),
+           entry)
     return image, dev_status
+
+
+def raster_commands_damaged(ctx, streams, cmds_dev, num_cmds, width, height, tile_bits, image, bounds_dev=None, max_entries=0, **kwargs):
+    """raster_commands() into `image` (the int32 [height, stride] device tensor an earlier render left), restricted to the tiles whose bit
+    is set in tile_bits (damage_meshes() / damage_instances() marks; damage_meshes() takes the table of command_bounds() as its box
+    table). bounds_dev: what command_bounds() gives for the table, or None; with it a command whose box reaches no marked tile is not
+    opened. With clear_color given, and every tile marked that the old or the new box of an edited command reaches, the image equals a
+    full raster_commands() of the edited table (vgx_raster_commands_damaged in include/vgx.h). max_entries: the bin entries the call
+    sorts at most, 0 = what the last damaged commands call on this context needed. dev_status may come out as VGX_E_GROWN: call again.
+    Other arguments and the results as raster_commands(). Asynchronous."""
+    return raster_commands(ctx, streams, cmds_dev, num_cmds, width, height, image=image, _damage=(tile_bits, max_entries, bounds_dev), **kwargs)
 
 
 def raster_commands_reserve(ctx, num_cmds, num_chunks, num_bin_entries):
@@ -906,7 +921,8 @@ def submit_order(draw_cmds, clip_cmds):
 
 
 # ---- hit testing of a draw-command table (vgx_pick_commands) -----------------------------------------------------------------
-def pick_commands(ctx, streams, cmds_dev, num_cmds, queries_dev, nqueries, meshes_dev=None, num_meshes=0, dev_num_cmds=None, hits_dev=None, dev_status=None):
+def pick_commands(ctx, streams, cmds_dev, num_cmds, queries_dev, nqueries, meshes_dev=None, num_meshes=0, dev_num_cmds=None, hits_dev=None, dev_status=None,
+                  _boxed=False, _bounds=None):
     """pick_frame() for the image raster_commands() draws: streams (raster_streams()) and cmds_dev as there; queries_dev a uint8 device
     tensor of nqueries 24-byte vgx_pick_cmd_query records (capi.pick_cmd_query_dtype: the point, the (cmd_end, tri_end) limit below which
     hits count -- cmd_end = capi.PICK_NONE: everything -- and the flags of pick()). meshes_dev / num_meshes: the mesh table of the
@@ -919,9 +935,39 @@ def pick_commands(ctx, streams, cmds_dev, num_cmds, queries_dev, nqueries, meshe
     if dev_status is None:
         dev_status = torch.empty(1, dtype=torch.int32, device=hits_dev.device)
     owners = capi.PickOwners(_ptr(meshes_dev, num_meshes), int(num_meshes)) if meshes_dev is not None else None
-    _check(lib().vgx_pick_commands(ctx.handle, C.byref(streams), _ptr(cmds_dev, num_cmds), int(num_cmds), _ptr(dev_num_cmds), C.byref(owners) if owners is not None else None,
-                                   _ptr(queries_dev, nqueries), int(nqueries), hits_dev.data_ptr(), dev_status.data_ptr(), _stream_ptr()), "vgx_pick_commands")
+    entry = "vgx_pick_commands_boxed" if _boxed else "vgx_pick_commands"
+    boxes = (_ptr(_bounds, num_cmds),) if _boxed else ()   # the one argument the boxed entry adds, behind dev_num_cmds
+    _check(getattr(lib(), entry)(ctx.handle, C.byref(streams), _ptr(cmds_dev, num_cmds), int(num_cmds), _ptr(dev_num_cmds), *boxes, C.byref(owners) if owners is not None else None,
+                                 _ptr(queries_dev, nqueries), int(nqueries), hits_dev.data_ptr(), dev_status.data_ptr(), _stream_ptr()), entry)
     return hits_dev, dev_status
+
+
+def pick_commands_boxed(ctx, streams, cmds_dev, num_cmds, bounds_dev, queries_dev, nqueries, **kwargs):
+    """pick_commands() that never opens a command whose box misses the point: bounds_dev is the float32 [num_cmds, 4] table
+    command_bounds() gave for the table, or None (then it is pick_commands()). True boxes change no answer; what the table holds decides
+    (the rule of vgx_pick_commands_boxed in include/vgx.h). Other arguments and the results as pick_commands()."""
+    return pick_commands(ctx, streams, cmds_dev, num_cmds, queries_dev, nqueries, _boxed=True, _bounds=bounds_dev, **kwargs)
+
+
+# ---- boxes of a draw-command table (vgx_command_bounds) -------------------------------------------------------------------------
+def command_bounds(ctx, streams, cmds_dev, num_cmds, cmd_begin=0, cmd_end=None, dev_num_cmds=None, bounds_dev=None, dev_status=None):
+    """The box of every command of a draw-command table over the corners of its triangles: streams (raster_streams()) and cmds_dev as
+    raster_commands() takes them. Writes the entries [cmd_begin, min(cmd_end, real count)) of bounds_dev, a float32 [num_cmds, 4] device
+    tensor (allocated, every entry the empty box, when None), and leaves the others alone: after an edit of a few commands only those
+    are refreshed. Returns (bounds, dev_status): minx, miny, maxx, maxy per command, (+inf, +inf, -inf, -inf) for one without a
+    triangle, and an int32 [1] tensor that holds VGX_OK, or VGX_E_INVALID_ARG for a record of the range whose ranges leave the streams
+    (it gets the empty box). No precondition on order or overlap of the commands' ranges. Asynchronous."""
+    import torch
+    dev = cmds_dev.device if cmds_dev is not None else "cuda:%d" % ctx.device
+    if bounds_dev is None:
+        inf = float("inf")
+        bounds_dev = torch.tensor([inf, inf, -inf, -inf], dtype=torch.float32, device=dev).repeat(max(int(num_cmds), 1), 1)[:int(num_cmds)]
+    if dev_status is None:
+        dev_status = torch.empty(1, dtype=torch.int32, device=dev)
+    end = 0xFFFFFFFF if cmd_end is None else int(cmd_end)
+    _check(lib().vgx_command_bounds(ctx.handle, C.byref(streams), _ptr(cmds_dev, num_cmds), int(num_cmds), _ptr(dev_num_cmds), int(cmd_begin), end,
+                                    _ptr(bounds_dev, num_cmds), dev_status.data_ptr(), _stream_ptr()), "vgx_command_bounds")
+    return bounds_dev, dev_status
 
 
 # ---- incremental update (vgx_cache_layout / vgx_cache_update) ------------------------------------------------------------
