@@ -178,9 +178,8 @@ struct vgx_ctx
 	DevBuf rasSortTemp, rasPartial;      // rasPartial: slice sums (views: as `partial`)
 	HostMirror<unsigned long long> ras;
 	// vgx_raster_damaged: the frame calls' tables, but a mirror of its own -- status and entry count of the last DAMAGED call -- and what
-	// the host learned from it: the count (the next call's sort window, vgx_damage.h) and whether that call ended with VGX_E_GROWN (the
-	// next window holds its need whatever max_entries says). A full render in between touches neither
-	HostMirror<unsigned long long> rasDmg; bool dmgKnown, dmgGrown; uint64_t dmgNeed;
+	// the host learned from it (VgxDamageWindow, vgx_damage.h). A full render in between touches neither
+	HostMirror<unsigned long long> rasDmg; VgxDamageWindow rasDmgWindow;
 	// vgx_raster_commands (vgx_raster_cmds.hip): per command its state and its first chunk; per chunk its rectangle of tiles, its command
 	// and its first entry; the (tile, chunk) entries in chunk order and in tile order; one bit per tile a painted command reaches; the
 	// state words (VGX_RASC_*) with their pinned mirror. The capacities the kernels are told are the ones asked for with their 12.5 %,
@@ -190,10 +189,8 @@ struct vgx_ctx
 	Buf<uint32_t> rascChunkCmd, rascKeys, rascVals, rascSortedKeys, rascSortedVals, rascTilePaint, rascFlag; Buf<unsigned long long> rascState;
 	uint64_t rascChunkCap, rascEntryCap;
 	HostMirror<unsigned long long> rasc;
-	// vgx_raster_commands_damaged: the full call's tables, but a mirror of its own -- the state words of the last DAMAGED commands call --
-	// and what the host learned from it, as rasDmg / dmg* for vgx_raster_damaged: the entry count (the next call's sort window,
-	// vgx_damage.h) and whether that call ended with VGX_E_GROWN. Neither a full vgx_raster_commands nor a vgx_raster_damaged touches them
-	HostMirror<unsigned long long> rascDmg; bool cdmgKnown, cdmgGrown; uint64_t cdmgNeed;
+	// vgx_raster_commands_damaged: the same pair for the commands calls. Neither a full vgx_raster_commands nor a vgx_raster_damaged touches them
+	HostMirror<unsigned long long> rascDmg; VgxDamageWindow rascDmgWindow;
 	// vgx_pick_commands (vgx_pick_cmds.hip): per command its state and its first chunk; per (query, command) the largest hit triangle;
 	// the state words (VGX_PICKC_*); slice sums (views: as `partial`). Its own: a counted state survives the call, and the tables of
 	// vgx_pick, vgx_pick_frame and vgx_raster_commands are not touched
@@ -2749,6 +2746,40 @@ int vgx_raster_reserve(vgx_ctx* ctx, uint64_t num_meshes, uint64_t num_bin_entri
 
 namespace {
 
+// ---- what the frame calls (VgxRasterArgs) and the commands calls (VgxRasterCmdArgs) fill alike: the same-named fields of the two -----
+// the scissor holds no pixel: the call writes VGX_OK and is over
+bool rasterNothingToWrite(vgx_ctx* ctx, const vgx_raster_target& t, uint32_t* dev_status, hipStream_t s)
+{
+	if (t.scissor[0] != t.scissor[2] && t.scissor[1] != t.scissor[3]) { return false; }
+	if (dev_status) { noteHip(ctx, hipMemsetAsync(dev_status, 0, sizeof(uint32_t), s)); } // VGX_OK
+	return true;
+}
+
+extern "C++" { // templates, inside the C-ABI block
+// the target as the kernels see it, and the plan of its tiles: the grid of the scissor's tiles, the sentinel key behind every tile
+template <class Args>
+void rasterTarget(Args& a, const vgx_raster_target& t)
+{
+	a.pixels = t.pixels; a.stride = t.stride; a.x0 = t.x0; a.y0 = t.y0;
+	for (int k = 0; k < 4; ++k) { a.scissor[k] = t.scissor[k]; }
+	a.flags = t.flags; a.clear_color = t.clear_color;
+	a.tiles_w = (t.width + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE;
+	a.tile_x0 = t.scissor[0] / VGX_RASTER_TILE; a.tile_y0 = t.scissor[1] / VGX_RASTER_TILE;
+	a.tiles_x = (t.scissor[2] - 1) / VGX_RASTER_TILE - a.tile_x0 + 1; a.tiles_y = (t.scissor[3] - 1) / VGX_RASTER_TILE - a.tile_y0 + 1;
+	a.sentinel = a.tiles_w * ((t.height + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE); // <= 2^20
+	for (a.sort_bits = 1; (a.sentinel >> a.sort_bits) != 0; ++a.sort_bits) { }
+}
+
+// the sort's temporary storage for a.sort_n entries, in rasSortTemp
+template <class Args>
+int rasterSortStorage(vgx_ctx* ctx, const Args& a, size_t* sortBytes)
+{
+	*sortBytes = a.sort_n ? vgx_raster_sort_bytes(a.sort_n, a.sort_bits) : 0;
+	if (!a.sort_n) { return VGX_OK; }
+	return *sortBytes ? ensure(ctx, ctx->rasSortTemp, *sortBytes) : (int)VGX_E_INTERNAL;
+}
+} // extern "C++"
+
 // The five calls are one body; `level` (VGX_RL_*, vgx_raster.h) says which pointers count and which kernel family runs. `damage`
 // (vgx_raster_damaged, at VGX_RL_CONCAVE; else null) restricts the call to the marked tiles and gives it a sort window of its own
 int rasterCall(int level, vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end, const vgx_raster_draws* state,
@@ -2759,23 +2790,15 @@ int rasterCall(int level, vgx_ctx* ctx, const vgx_cache_desc* frame, const float
 	if (!ctx) { return VGX_E_INVALID_ARG; }
 	int st = vgx_raster_check_args(level, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, dev_status);
 	if (st != VGX_OK) { return st; }
-	if (damage && (!damage->tile_bits || ((uintptr_t)damage->tile_bits & 3u) || damage->reserved != 0u)) { return VGX_E_INVALID_ARG; }
+	if (damage && vgx_damage_record_check(damage) != VGX_OK) { return VGX_E_INVALID_ARG; }
 	const vgx_raster_target& t = *target;
-	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
 	hipStream_t s = (hipStream_t)stream;
-	if (empty) { // no pixel to write
-		if (dev_status) { noteHip(ctx, hipMemsetAsync(dev_status, 0, sizeof(uint32_t), s)); } // VGX_OK
-		return launchStatus(ctx);
-	}
+	if (rasterNothingToWrite(ctx, t, dev_status, s)) { return launchStatus(ctx); }
 	const uint64_t end = mesh_end < frame->num_meshes ? mesh_end : frame->num_meshes;
 	const uint64_t nrange = mesh_begin < end ? end - mesh_begin : 0;
 	VgxRasterArgs a;
 	memset(&a, 0, sizeof(a));
-	a.tiles_w = (t.width + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE;
-	a.tile_x0 = t.scissor[0] / VGX_RASTER_TILE; a.tile_y0 = t.scissor[1] / VGX_RASTER_TILE;
-	a.tiles_x = (t.scissor[2] - 1) / VGX_RASTER_TILE - a.tile_x0 + 1; a.tiles_y = (t.scissor[3] - 1) / VGX_RASTER_TILE - a.tile_y0 + 1;
-	a.sentinel = a.tiles_w * ((t.height + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE); // <= 2^20
-	for (a.sort_bits = 1; (a.sentinel >> a.sort_bits) != 0; ++a.sort_bits) { }
+	rasterTarget(a, t);
 	HostMirror<unsigned long long>& mirror = damage ? ctx->rasDmg : ctx->ras;
 	if ((st = mirror.create(ctx, 2)) != VGX_OK) { return st; }
 	// no mesh has more entries than the scissor has tiles: the sort need not look further
@@ -2786,28 +2809,18 @@ int rasterCall(int level, vgx_ctx* ctx, const vgx_cache_desc* frame, const float
 	if (!damage) {
 		if (ctx->ras.landed() && ctx->ras.host[0] == VGX_E_GROWN && ctx->ras.host[1] > entries) { entries = ctx->ras.host[1]; }
 	} else {
-		// The damaged call sorts a window (include/vgx.h), not what a full render left the tables at: the caller's, or the last damaged
-		// call's count with head room, or the initial one -- and at least the need of a damaged call that ended with VGX_E_GROWN
-		if (mirror.landed() && (mirror.host[0] == VGX_OK || mirror.host[0] == VGX_E_GROWN)) {
-			ctx->dmgKnown = true; ctx->dmgNeed = mirror.host[1]; ctx->dmgGrown = mirror.host[0] == VGX_E_GROWN;
-		}
-		window = damage->max_entries ? (damage->max_entries < entries ? damage->max_entries : entries)
-		                             : (ctx->dmgKnown ? vgx_damage_head_room(ctx->dmgNeed) : (uint64_t)VGX_DAMAGE_INITIAL_WINDOW);
-		if (ctx->dmgGrown && ctx->dmgNeed > window) { window = vgx_damage_head_room(ctx->dmgNeed); }
-		if (window > bound) { window = bound; }
-		if (window > 0xFFFFFFFFull) { window = 0xFFFFFFFFull; }
+		// The damaged call sorts a window, not what a full render left the tables at. max_entries is clipped to what the tables hold
+		// (they grow by a measured need, never by a wish), and the tables grow to the window before it becomes the capacity
+		if (mirror.landed()) { vgx_damage_learn(&ctx->rasDmgWindow, mirror.host[0], mirror.host[1]); }
+		window = vgx_damage_window(ctx->rasDmgWindow, damage->max_entries, entries, bound);
 		if (window > entries) { entries = window; }
 	}
 	if ((st = rasterEnsure(ctx, nrange, entries)) != VGX_OK) { return st; }
 	a.entry_cap = minOf({ ctx->rasKeys.items(), ctx->rasVals.items(), ctx->rasSortedKeys.items(), ctx->rasSortedVals.items() }) - 1;
 	if (window < a.entry_cap) { a.entry_cap = window; }
 	a.sort_n = bound < a.entry_cap ? bound : a.entry_cap;
-	size_t sortBytes = 0;
-	if (a.sort_n) {
-		sortBytes = vgx_raster_sort_bytes(a.sort_n, a.sort_bits);
-		if (!sortBytes) { return VGX_E_INTERNAL; }
-		if ((st = ensure(ctx, ctx->rasSortTemp, sortBytes)) != VGX_OK) { return st; }
-	}
+	size_t sortBytes;
+	if ((st = rasterSortStorage(ctx, a, &sortBytes)) != VGX_OK) { return st; }
 	if (!mesh_bounds && nrange) {
 		if ((st = ensure(ctx, ctx->rasBounds, frame->num_meshes * 4)) != VGX_OK) { return st; }
 		vgx_launch_mesh_bounds(frame->pos, frame->meshes + mesh_begin, nrange, ctx->rasBounds.ptr() + 4 * mesh_begin, s); // the range's boxes only
@@ -2815,9 +2828,6 @@ int rasterCall(int level, vgx_ctx* ctx, const vgx_cache_desc* frame, const float
 	}
 	a.pos = frame->pos; a.color = frame->color; a.idx = frame->idx; a.meshes = frame->meshes; a.mesh_bounds = mesh_bounds;
 	a.mesh_begin = mesh_begin; a.nrange = nrange;
-	a.pixels = t.pixels; a.stride = t.stride; a.x0 = t.x0; a.y0 = t.y0;
-	for (int k = 0; k < 4; ++k) { a.scissor[k] = t.scissor[k]; }
-	a.flags = t.flags; a.clear_color = t.clear_color;
 	a.mesh_entries = ctx->rasMeshEntries.ptr(); a.mesh_first = ctx->rasMeshFirst.ptr();
 	a.keys = ctx->rasKeys.ptr(); a.vals = ctx->rasVals.ptr(); a.sorted_keys = ctx->rasSortedKeys.ptr(); a.sorted_vals = ctx->rasSortedVals.ptr();
 	a.state = ctx->rasState.ptr(); a.status = dev_status;
@@ -2878,7 +2888,7 @@ namespace {
 static int damageTarget(const vgx_raster_target* t, const uint32_t* tile_bits, VgxDamageArgs* a)
 {
 	if (!t || !tile_bits || ((uintptr_t)tile_bits & 3u)) { return VGX_E_INVALID_ARG; }
-	if (t->width > 16384u || t->height > 16384u || t->x0 > (1 << 23) || t->x0 < -(1 << 23) || t->y0 > (1 << 23) || t->y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
+	if (vgx_target_extent_check(*t) != VGX_OK) { return VGX_E_INVALID_ARG; }
 	memset(a, 0, sizeof(*a));
 	a->x0 = t->x0; a->y0 = t->y0; a->width = t->width; a->height = t->height; a->tiles_w = vgx_damage_tiles_w(t->width);
 	a->tile_bits = const_cast<uint32_t*>(tile_bits);
@@ -3004,20 +3014,13 @@ int rasterCommandsCall(vgx_ctx* ctx, const vgx_raster_streams* streams, const vg
 	if (!ctx) { return VGX_E_INVALID_ARG; }
 	int st = vgx_rasterc_check_args(streams, cmds, num_cmds, dev_num_cmds, images, num_images, paints, target, dev_status);
 	if (st != VGX_OK) { return st; }
-	if (damage && (!damage->tile_bits || ((uintptr_t)damage->tile_bits & 3u) || damage->reserved != 0u || ((uintptr_t)cmd_bounds & 15u))) { return VGX_E_INVALID_ARG; }
+	if (damage && (vgx_damage_record_check(damage) != VGX_OK || ((uintptr_t)cmd_bounds & 15u))) { return VGX_E_INVALID_ARG; }
 	const vgx_raster_target& t = *target;
 	hipStream_t s = (hipStream_t)stream;
-	if (t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3]) { // no pixel to write
-		if (dev_status) { noteHip(ctx, hipMemsetAsync(dev_status, 0, sizeof(uint32_t), s)); } // VGX_OK
-		return launchStatus(ctx);
-	}
+	if (rasterNothingToWrite(ctx, t, dev_status, s)) { return launchStatus(ctx); }
 	VgxRasterCmdArgs a;
 	memset(&a, 0, sizeof(a));
-	a.tiles_w = (t.width + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE;
-	a.tile_x0 = t.scissor[0] / VGX_RASTER_TILE; a.tile_y0 = t.scissor[1] / VGX_RASTER_TILE;
-	a.tiles_x = (t.scissor[2] - 1) / VGX_RASTER_TILE - a.tile_x0 + 1; a.tiles_y = (t.scissor[3] - 1) / VGX_RASTER_TILE - a.tile_y0 + 1;
-	a.sentinel = a.tiles_w * ((t.height + VGX_RASTER_TILE - 1) / VGX_RASTER_TILE); // <= 2^20
-	for (a.sort_bits = 1; (a.sentinel >> a.sort_bits) != 0; ++a.sort_bits) { }
+	rasterTarget(a, t);
 	HostMirror<unsigned long long>& mirror = damage ? ctx->rascDmg : ctx->rasc;
 	if ((st = mirror.create(ctx, VGX_RASC_WORDS)) != VGX_OK) { return st; }
 	// the tables: what they hold, at least the first guess of one chunk per command and per 64 triangles of the index stream and as
@@ -3028,7 +3031,7 @@ int rasterCommandsCall(vgx_ctx* ctx, const vgx_raster_streams* streams, const vg
 		const unsigned long long last = mirror.host[VGX_RASC_STATUS];
 		if (last == VGX_E_GROWN && mirror.host[VGX_RASC_CHUNKS] > chunks) { chunks = mirror.host[VGX_RASC_CHUNKS]; }
 		if (!damage && last == VGX_E_GROWN && mirror.host[VGX_RASC_ENTRIES] > entries) { entries = mirror.host[VGX_RASC_ENTRIES]; }
-		if (damage && (last == VGX_OK || last == VGX_E_GROWN)) { ctx->cdmgKnown = true; ctx->cdmgNeed = mirror.host[VGX_RASC_ENTRIES]; ctx->cdmgGrown = last == VGX_E_GROWN; }
+		if (damage) { vgx_damage_learn(&ctx->rascDmgWindow, last, mirror.host[VGX_RASC_ENTRIES]); }
 	}
 	if (chunks > 0xFFFFFFFFull) { chunks = 0xFFFFFFFFull; }
 	if (entries > 0xFFFFFFFFull) { entries = 0xFFFFFFFFull; }
@@ -3038,24 +3041,16 @@ int rasterCommandsCall(vgx_ctx* ctx, const vgx_raster_streams* streams, const vg
 	const uint64_t bound = a.chunk_cap * ((uint64_t)a.tiles_x * a.tiles_y);
 	uint64_t window = ~0ull;
 	if (damage) {
-		// The damaged call sorts a window (include/vgx.h), not what a full render left the tables at: the caller's, or the last damaged
-		// commands call's count with head room, or the initial one -- and at least the need of one that ended with VGX_E_GROWN
-		window = damage->max_entries ? (damage->max_entries < ctx->rascEntryCap ? damage->max_entries : ctx->rascEntryCap)
-		                             : (ctx->cdmgKnown ? vgx_damage_head_room(ctx->cdmgNeed) : (uint64_t)VGX_DAMAGE_INITIAL_WINDOW);
-		if (ctx->cdmgGrown && ctx->cdmgNeed > window) { window = vgx_damage_head_room(ctx->cdmgNeed); }
-		if (window > bound) { window = bound; }
-		if (window > 0xFFFFFFFFull) { window = 0xFFFFFFFFull; }
+		// The window, as in rasterCall. These tables keep a capacity apart from their size (rascEntryCap), so max_entries is clipped
+		// to that, and the first guess grew them above already: only a window past the capacity grows them again
+		window = vgx_damage_window(ctx->rascDmgWindow, damage->max_entries, ctx->rascEntryCap, bound);
 		if (window > ctx->rascEntryCap && (st = rasterCmdsEnsure(ctx, num_cmds, chunks, window)) != VGX_OK) { return st; }
 	}
 	a.entry_cap = ctx->rascEntryCap < 0xFFFFFFFFull ? ctx->rascEntryCap : 0xFFFFFFFFull;
 	if (window < a.entry_cap) { a.entry_cap = window; }
 	a.sort_n = num_cmds ? (bound < a.entry_cap ? bound : a.entry_cap) : 0;
-	size_t sortBytes = 0;
-	if (a.sort_n) {
-		sortBytes = vgx_raster_sort_bytes(a.sort_n, a.sort_bits);
-		if (!sortBytes) { return VGX_E_INTERNAL; }
-		if ((st = ensure(ctx, ctx->rasSortTemp, sortBytes)) != VGX_OK) { return st; }
-	}
+	size_t sortBytes;
+	if ((st = rasterSortStorage(ctx, a, &sortBytes)) != VGX_OK) { return st; }
 	const uint64_t words = ((uint64_t)a.sentinel + 31u) / 32u;
 	if ((st = ensure(ctx, ctx->rascTilePaint, words + 1)) != VGX_OK) { return st; }
 	noteHip(ctx, hipMemsetAsync(ctx->rascTilePaint.p, 0, words * sizeof(uint32_t), s));
@@ -3064,9 +3059,6 @@ int rasterCommandsCall(vgx_ctx* ctx, const vgx_raster_streams* streams, const vg
 	a.cmds = cmds; a.num_cmds = num_cmds; a.dev_num_cmds = dev_num_cmds;
 	a.images = images; a.num_images = num_images;
 	if (paints) { a.gradients = paints->gradients; a.patterns = paints->patterns; a.num_gradients = paints->num_gradients; a.num_patterns = paints->num_patterns; }
-	a.pixels = t.pixels; a.stride = t.stride; a.x0 = t.x0; a.y0 = t.y0;
-	for (int k = 0; k < 4; ++k) { a.scissor[k] = t.scissor[k]; }
-	a.flags = t.flags; a.clear_color = t.clear_color;
 	a.cmd_state = ctx->rascCmdState.ptr(); a.cmd_first = ctx->rascCmdFirst.ptr();
 	a.chunk_rect = ctx->rascChunkRect.ptr(); a.chunk_cmd = ctx->rascChunkCmd.ptr(); a.chunk_first = ctx->rascChunkFirst.ptr();
 	a.keys = ctx->rascKeys.ptr(); a.vals = ctx->rascVals.ptr(); a.sorted_keys = ctx->rascSortedKeys.ptr(); a.sorted_vals = ctx->rascSortedVals.ptr();

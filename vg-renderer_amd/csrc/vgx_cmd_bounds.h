@@ -12,15 +12,9 @@
 #include "vgx_raster_cmds.h"
 #include "vgx_damage.h"
 
-// A record the call can walk: its ranges lie inside the streams (in 64 bits) and it has at most 65536 vertices. Type, handle, scissor,
-// clip fields and `reserved` are not examined: nothing they name is read
-VGX_HD bool vgx_cmdb_valid(const vgx_raster_cmd& c, uint64_t numVertices, uint64_t numIndices)
-{
-	if (c.num_vertices > 65536u) { return false; }
-	if (c.first_vertex > numVertices || (uint64_t)c.num_vertices > numVertices - c.first_vertex) { return false; }
-	if (c.first_index > numIndices || (uint64_t)c.num_indices > numIndices - c.first_index) { return false; }
-	return true;
-}
+// A record the call can walk: vgx_rasterc_ranges_valid alone. Type, handle, scissor, clip fields and `reserved` are not examined:
+// nothing they name is read
+VGX_HD bool vgx_cmdb_valid(const vgx_raster_cmd& c, uint64_t numVertices, uint64_t numIndices) { return vgx_rasterc_ranges_valid(c, numVertices, numIndices); }
 
 // the chunks of 64 consecutive triangles the call walks for the record: none for an invalid one
 VGX_HD uint32_t vgx_cmdb_chunks(const vgx_raster_cmd& c, uint64_t numVertices, uint64_t numIndices)
@@ -75,20 +69,13 @@ VGX_HD bool vgx_cmdb_damaged(const float* box, const uint32_t* bits, int32_t x0,
 	return vgx_damage_rect_count(bits, r, vgx_damage_tiles_w(width)) != 0u;
 }
 
-// What vgx_command_bounds refuses before anything runs (host only): VGX_OK or VGX_E_INVALID_ARG. The streams are validated as
-// vgx_pick_commands does; color and uv are never read
+// What vgx_command_bounds refuses before anything runs (host only): VGX_OK or VGX_E_INVALID_ARG. color and uv are never read
 static inline int vgx_cmdb_check_args(const vgx_raster_streams* sm, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds, uint32_t cmd_begin,
                                       uint32_t cmd_end, const float* bounds, const uint32_t* status)
 {
-	if (!sm || (num_cmds && !cmds)) { return VGX_E_INVALID_ARG; }
+	if (vgx_streams_check(sm, cmds, num_cmds, dev_num_cmds) != VGX_OK) { return VGX_E_INVALID_ARG; }
 	if (vgx_cmdb_range(num_cmds, cmd_begin, cmd_end) && !bounds) { return VGX_E_INVALID_ARG; }
-	if ((sm->uv_bytes != 0u && sm->uv_bytes != 4u && sm->uv_bytes != 8u) || (sm->uv != nullptr && sm->uv_bytes == 0u) || sm->reserved != 0u) { return VGX_E_INVALID_ARG; }
-	if (sm->uv && ((uintptr_t)sm->uv & (sm->uv_bytes - 1u))) { return VGX_E_INVALID_ARG; }
-	if ((sm->num_vertices && (!sm->pos || !sm->color)) || (sm->num_indices && !sm->idx)) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)bounds & 15u) || ((uintptr_t)status & 3u) || ((uintptr_t)dev_num_cmds & 3u) || ((uintptr_t)cmds & 7u) || ((uintptr_t)sm->pos & 7u)
-		|| ((uintptr_t)sm->color & 3u) || ((uintptr_t)sm->idx & 1u)) {
-		return VGX_E_INVALID_ARG;
-	}
+	if (((uintptr_t)bounds & 15u) || ((uintptr_t)status & 3u)) { return VGX_E_INVALID_ARG; }
 	return VGX_OK;
 }
 

@@ -3,14 +3,13 @@
 //
 // vgx_mesh_bounds spreads its work by VERTEX, which needs ascending, disjoint vertex ranges. A command table promises neither, and a
 // command's box is over the corners of its TRIANGLES (an unreferenced vertex, and a triangle with an index outside the command, take no
-// part). So this family works on chunks of 64 consecutive triangles of one command, the decomposition k_pickc_tris arrived at:
+// part). So this family works on chunks of 64 consecutive triangles of one command, as k_pickc_tris does:
 //   scan OpCmdBounds every command's first chunk among those of the range, the chunk total and the count of invalid records; store()
 //                    also lays the empty box, as order-preserving images (vgx_bounds.h), into every entry of the range -- the
 //                    initialising pass; finish() decides dev_status
-//   k_cmdb_tris      fixed grid, one WAVE per chunk; a wave takes a contiguous run of the chunks (the total lives on the device), finds
-//                    the run's first command by find_owner_u64 over the prefix and walks the prefix from there. A lane loads three
-//                    indices and three positions; a wave reduction over the corners gives the chunk's box, which joins a running box
-//                    kept wave-uniform across the chunks of one command. The running box is flushed once per (wave, command) with
+//   k_cmdb_tris      fixed grid, one WAVE per chunk, the chunks of a wave contiguous (VgxChunkWalk, vgx_raster_cmds.h). A lane loads
+//                    three indices and three positions; a wave reduction over the corners gives the chunk's box, which joins a running
+//                    box kept wave-uniform across the chunks of one command. The running box is flushed once per (wave, command) with
 //                    four atomicMin / atomicMax on the images: integer minima and maxima, so neither the order nor the decomposition
 //                    of the work shows in the result
 //   k_cmdb_decode    images -> floats, in place, over the range only
@@ -22,17 +21,10 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t cmdb_real_cmds(const VgxCmdBoundsArgs& A)
-{
-	if (!A.dev_num_cmds) { return A.num_cmds; }
-	const uint32_t n = *A.dev_num_cmds;
-	return n < A.num_cmds ? n : A.num_cmds;
-}
-
 struct OpCmdBounds
 {
 	VgxCmdBoundsArgs A;
-	__device__ uint64_t size() const { return vgx_cmdb_range(cmdb_real_cmds(A), A.cmd_begin, A.cmd_end); }
+	__device__ uint64_t size() const { return vgx_cmdb_range(vgx_real_cmds(A.num_cmds, A.dev_num_cmds), A.cmd_begin, A.cmd_end); }
 	__device__ Sum3 load(uint64_t i) const
 	{
 		Sum3 r = sum3_zero();
@@ -59,15 +51,8 @@ struct OpCmdBounds
 // minimum / maximum of the images over the wave, on every lane, as scalars
 __device__ __forceinline__ VgxOrdBox cmdb_wave_reduce(VgxOrdBox b)
 {
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) {
-		VgxOrdBox o;
-		o.minx = (uint32_t)__shfl_xor((int)b.minx, d); o.miny = (uint32_t)__shfl_xor((int)b.miny, d);
-		o.maxx = (uint32_t)__shfl_xor((int)b.maxx, d); o.maxy = (uint32_t)__shfl_xor((int)b.maxy, d);
-		b = vgx_ordbox_union(b, o);
-	}
-	b.minx = (uint32_t)__builtin_amdgcn_readfirstlane((int)b.minx); b.miny = (uint32_t)__builtin_amdgcn_readfirstlane((int)b.miny);
-	b.maxx = (uint32_t)__builtin_amdgcn_readfirstlane((int)b.maxx); b.maxy = (uint32_t)__builtin_amdgcn_readfirstlane((int)b.maxy);
+	b.minx = wave_uniform_u32(wave_min_u32(b.minx)); b.miny = wave_uniform_u32(wave_min_u32(b.miny));
+	b.maxx = wave_uniform_u32(wave_max_u32(b.maxx)); b.maxy = wave_uniform_u32(wave_max_u32(b.maxy));
 	return b;
 }
 
@@ -83,28 +68,22 @@ __global__ __launch_bounds__(256) void k_cmdb_tris(VgxCmdBoundsArgs A)
 	const uint64_t total = A.state[VGX_CMDB_CHUNKS];
 	const uint32_t n = (uint32_t)A.state[VGX_CMDB_CMDS]; // the commands of the range; command i of it is cmds[cmd_begin + i]
 	const int lane = threadIdx.x & (VGX_WAVE - 1);
-	const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / VGX_WAVE);
-	// a wave takes a CONTIGUOUS run of chunks, as k_pickc_tris does: one search for the run's first command, then a walk over the prefix
-	const uint64_t per = (total + waves - 1u) / waves;
-	const uint64_t w = (uint64_t)blockIdx.x * (blockDim.x / VGX_WAVE) + (threadIdx.x / VGX_WAVE);
-	const uint64_t k0 = w * per < total ? w * per : total, k1 = k0 + per < total ? k0 + per : total; // wave-uniform; nothing below synchronises the workgroup
-	if (k0 >= k1) { return; }
-	uint32_t i = (uint32_t)find_owner_u64(A.cmd_first, 0, n, k0); // the last command whose first chunk is <= k0: the one with chunks
-	uint64_t first = A.cmd_first[i], next = A.cmd_first[i + 1u];
-	vgx_raster_cmd cmd = A.cmds[A.cmd_begin + i];
+	VgxChunkWalk W(A.cmd_first, n, total, (uint64_t)blockIdx.x * (blockDim.x / VGX_WAVE) + (threadIdx.x / VGX_WAVE), (uint64_t)gridDim.x * (blockDim.x / VGX_WAVE)); // a contiguous run of the chunks; command W.c of the range is cmds[cmd_begin + W.c]
+	if (W.k0 >= W.k1) { return; }
+	vgx_raster_cmd cmd = A.cmds[A.cmd_begin + W.c];
 	VgxOrdBox run = vgx_ordbox_empty();
-	for (uint64_t k = k0; k < k1; ++k) {
-		if (k >= next) { // cmd_first[n] = total > k: the walk ends inside the range; commands without chunks are passed over
-			cmdb_flush(A.bounds + 4ull * (A.cmd_begin + i), run, lane);
+	for (uint64_t k = W.k0; k < W.k1; ++k) {
+		const uint32_t left = W.c;
+		if (W.advance(k)) {
+			cmdb_flush(A.bounds + 4ull * (A.cmd_begin + left), run, lane);
 			run = vgx_ordbox_empty();
-			do { ++i; first = next; next = A.cmd_first[i + 1u]; } while (k >= next);
-			cmd = A.cmds[A.cmd_begin + i];
+			cmd = A.cmds[A.cmd_begin + W.c];
 		}
 		// inside the command's ranges, and those inside the streams: OpCmdBounds gave an invalid record no chunks
-		const VgxOrdBox b = vgx_cmdb_triangle(cmd, A.idx, A.pos, (uint32_t)(k - first) * VGX_RASTERC_CHUNK + (uint32_t)lane);
+		const VgxOrdBox b = vgx_cmdb_triangle(cmd, A.idx, A.pos, (uint32_t)(k - W.first) * VGX_RASTERC_CHUNK + (uint32_t)lane);
 		run = vgx_ordbox_union(run, cmdb_wave_reduce(b));
 	}
-	cmdb_flush(A.bounds + 4ull * (A.cmd_begin + i), run, lane);
+	cmdb_flush(A.bounds + 4ull * (A.cmd_begin + W.c), run, lane);
 }
 
 __global__ __launch_bounds__(256) void k_cmdb_decode(VgxCmdBoundsArgs A)

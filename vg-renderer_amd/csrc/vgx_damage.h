@@ -63,9 +63,37 @@ VGX_HD bool vgx_damage_entry(const vgx_cache_slot* slots, uint64_t ninst, uint64
 	return true;
 }
 
+// the vgx_raster_damage record of a damaged call (host only): VGX_OK or VGX_E_INVALID_ARG
+static inline int vgx_damage_record_check(const vgx_raster_damage* d)
+{
+	return !d || !d->tile_bits || ((uintptr_t)d->tile_bits & 3u) || d->reserved != 0u ? VGX_E_INVALID_ARG : VGX_OK;
+}
+
 // The window of entries vgx_raster_damaged sorts when the caller names none (include/vgx.h): before any call has been measured, and
 // the head room over a measured count
 #define VGX_DAMAGE_INITIAL_WINDOW 16384u
 static inline uint64_t vgx_damage_head_room(uint64_t measured) { return measured + measured / 8u + 256u; }
+
+// What the host knows of the damaged calls of one kind (vgx_raster_damaged; vgx_raster_commands_damaged) from their own mirror alone:
+// known: a call has been measured, need: its entry count, grown: it ended with VGX_E_GROWN. A full render in between teaches nothing
+struct VgxDamageWindow { bool known, grown; uint64_t need; };
+
+// a landed mirror of the last damaged call: its status and its entry count. A call that ended otherwise measured nothing
+static inline void vgx_damage_learn(VgxDamageWindow* w, uint64_t status, uint64_t entries)
+{
+	if (status != (uint64_t)VGX_OK && status != (uint64_t)VGX_E_GROWN) { return; }
+	w->known = true; w->need = entries; w->grown = status == (uint64_t)VGX_E_GROWN;
+}
+
+// The entries the next damaged call sorts (include/vgx.h): the caller's max_entries, no more than `cap` (what the call can offer);
+// without one the measured count with head room, or the initial window. At least the need of a call that ended with VGX_E_GROWN,
+// whatever max_entries says; never more than `bound` (the entries the call can have at all) nor than 2^32 - 1
+static inline uint64_t vgx_damage_window(const VgxDamageWindow& w, uint64_t max_entries, uint64_t cap, uint64_t bound)
+{
+	uint64_t window = max_entries ? (max_entries < cap ? max_entries : cap) : (w.known ? vgx_damage_head_room(w.need) : (uint64_t)VGX_DAMAGE_INITIAL_WINDOW);
+	if (w.grown && w.need > window) { window = vgx_damage_head_room(w.need); }
+	if (window > bound) { window = bound; }
+	return window > 0xFFFFFFFFull ? 0xFFFFFFFFull : window;
+}
 
 #endif

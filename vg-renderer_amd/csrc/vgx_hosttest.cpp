@@ -744,7 +744,7 @@ static int raster_frame_loop(int level, const vgx_cache_desc* frame, const float
 {
 	const int rc = vgx_raster_check_args(level, frame, mesh_bounds, mesh_begin, mesh_end, state, tex, paints, target, status);
 	if (rc != VGX_OK) { return rc; }
-	if (dmg && (!dmg->tile_bits || ((uintptr_t)dmg->tile_bits & 3u) || dmg->reserved != 0u)) { return VGX_E_INVALID_ARG; }
+	if (dmg && vgx_damage_record_check(dmg) != VGX_OK) { return VGX_E_INVALID_ARG; }
 	const uint32_t* const damage = dmg ? dmg->tile_bits : nullptr; // (max_entries: there is no sort here, and no window to outgrow)
 	const vgx_raster_target& t = *target;
 	if (status) { *status = VGX_OK; }
@@ -1031,7 +1031,7 @@ static int raster_commands_loop(const vgx_raster_streams* streams, const vgx_ras
 {
 	const int rc = vgx_rasterc_check_args(streams, cmds, num_cmds, real_cmds, images, num_images, paints, target, status);
 	if (rc != VGX_OK) { return rc; }
-	if (dmg && (!dmg->tile_bits || ((uintptr_t)dmg->tile_bits & 3u) || dmg->reserved != 0u || ((uintptr_t)cmd_bounds & 15u))) { return VGX_E_INVALID_ARG; }
+	if (dmg && (vgx_damage_record_check(dmg) != VGX_OK || ((uintptr_t)cmd_bounds & 15u))) { return VGX_E_INVALID_ARG; }
 	const uint32_t* const damage = dmg ? dmg->tile_bits : nullptr;
 	const vgx_raster_target& t = *target;
 	if (status) { *status = VGX_OK; }

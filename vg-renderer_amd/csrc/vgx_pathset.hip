@@ -64,7 +64,7 @@ __device__ __forceinline__ void ps_mark(const VgxPsBuild& A, uint32_t p)
 		else { empty = true; }
 	}
 	// one atomic per wave, not per path (a million two-command paths would queue a million atomics on one address)
-	for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(len, d); len = o > len ? o : len; }
+	len = wave_max_u32(len);
 	const uint64_t anyEmpty = wave_ballot(empty), anyBad = wave_ballot(bad);
 	if ((threadIdx.x & 63) == 0) {
 		if (len) { atomicMax(&A.tot->maxCmds, len); }

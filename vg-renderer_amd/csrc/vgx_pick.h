@@ -85,6 +85,18 @@ VGX_HD bool vgx_pickf_point(float x, float y, double* px, double* py, int32_t* X
 	return true;
 }
 
+// What vgx_pick_frame and vgx_pick_commands stage of a query in LDS: its point, and in bit 31 of its flags whether it takes part -- a
+// point, and `wellFormed` by the call's own rule. The records that extend it (24 and 32 bytes) stay apart: DESIGN.md has the LDS figures
+#define VGX_PICK_STAGED_VALID 0x80000000u
+struct VgxPickStagedPoint { float x, y; int32_t X, Y; };
+VGX_HD uint32_t vgx_pick_stage_point(float x, float y, uint32_t flags, bool wellFormed, VgxPickStagedPoint* p)
+{
+	double px, py;
+	p->x = x; p->y = y;
+	const bool point = vgx_pickf_point(x, y, &px, &py, &p->X, &p->Y);
+	return (flags & ~VGX_PICK_STAGED_VALID) | (point && wellFormed ? VGX_PICK_STAGED_VALID : 0u);
+}
+
 // Mode (VGX_RF_PLAIN / IN / OUT / STAMP), f, n of a mesh under its draw, its element count (triangles, or edges of a contour mesh; 0: the
 // mesh can cover nothing) and its draw's scissor as frame pixels [rect[0], rect[2]) x [rect[1], rect[3]). me.draw < num_draws is the caller's check
 struct VgxPickfMesh { uint32_t mode, f, n, elems; uint32_t rect[4]; }; // 32 bytes

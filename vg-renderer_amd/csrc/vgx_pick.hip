@@ -7,9 +7,8 @@
 //                   Its first workgroup resets the key table: the call cleans up after the one before it
 //   scan OpPickCand (vgx_scan.h) the dense ascending candidate list and the exclusive prefix of the candidates' triangle counts in one
 //                   pass; the totals stay on the device
-//   k_pick_tris     fixed grid, grid-stride over tiles of 256 entries of the candidate-triangle prefix. A wave finds the candidate of its
-//                   first triangle by binary search and holds the 64 prefix entries from there one per lane: every candidate has a
-//                   triangle, so its 64 triangles lie in those. A lane loads three uint16 indices, gathers three positions (and three
+//   k_pick_tris     fixed grid, grid-stride over tiles of 256 entries of the candidate-triangle prefix; a wave finds the owners of its 64
+//                   triangles by wave_owners (vgx_wave.h). A lane loads three uint16 indices, gathers three positions (and three
 //                   colours when some query asks for the transparency rule), then runs the queries from LDS in a wave-uniform loop:
 //                   mesh_end, the triangle's box, the binary64 predicate. Lanes are in ascending (mesh, triangle) order, so the highest
 //                   lane that hits holds the wave's largest key: no reduction, ONE 64-bit atomicMax per wave and query with a hit
@@ -74,20 +73,13 @@ __global__ __launch_bounds__(256) void k_pick_tris(VgxPickArgs A)
 	for (uint64_t tile = blockIdx.x; tile < numTiles; tile += gridDim.x) {
 		const uint64_t T0 = tile * VGX_PICK_TILE + (uint64_t)wave * VGX_WAVE;
 		if (T0 >= totalTris) { continue; } // the last tile's empty waves; nothing below synchronises the workgroup
-		// the candidate that owns T0 (P[0] = 0 <= T0 < P[numCand] = totalTris; P is strictly ascending), then 64 entries from there
-		const uint64_t c0 = find_owner_u64(A.cand_prefix, 0, numCand, T0);
-		const uint64_t ck = c0 + (uint64_t)lane;
-		const uint64_t w = ck <= numCand ? A.cand_prefix[ck] : ~0ull;
-		const uint64_t T = T0 + (uint64_t)lane;
-		const bool live = T < totalTris;
-		uint64_t first = 0;
-		const int k = window_owner(w, live ? T : T0, &first);
+		const WaveOwners o = wave_owners(A.cand_prefix, numCand, totalTris, T0, lane); // every candidate has a triangle: P is strictly ascending
 		uint32_t m = 0, t = 0;
 		V2 a = v2(0.0f, 0.0f), b = a, c = a;
 		bool ok = false, transparent = false;
-		if (live) {
-			m = A.cand_mesh[c0 + (uint64_t)k];
-			t = (uint32_t)(T - first);
+		if (o.live) {
+			m = A.cand_mesh[o.c0 + (uint64_t)o.k];
+			t = (uint32_t)(T0 + (uint64_t)lane - o.first);
 			const vgx_mesh me = A.meshes[m];
 			const uint16_t* ip = A.idx + me.first_index + 3ull * t;
 			const uint32_t i0 = ip[0], i1 = ip[1], i2 = ip[2];
@@ -145,29 +137,27 @@ void vgx_launch_pick(const VgxPickArgs& a, void* partial, uint32_t grid, hipStre
 //   scan OpPickfCand  (vgx_scan.h) the dense ascending candidate list, the triangle candidates with the exclusive prefix of their
 //                     triangle counts, the contour candidates, the candidates' covered rows zeroed, and the count of meshes with
 //                     draw >= num_draws: dev_status is decided there, in one reduction
-//   k_pickf_tris      k_pick_tris's traversal (a tile of 256 prefix entries per workgroup step, a 64-entry window per wave) with the
-//                     raster's coverage rule, set up once per lane. Per query and wave ONE atomicOr per candidate with a covering lane
+//   k_pickf_tris      k_pick_tris's traversal with the raster's coverage rule, set up once per lane. Per query and wave ONE atomicOr
+//                     per candidate with a covering lane
 //   k_pickf_contours  one wave per (contour candidate, 64 queries): a lane is a query, the mesh's edges are set up 64 at a time, one per
 //                     lane, and broadcast from LDS; each lane sums its own W in an int32 -- no reduction, no atomics, and integer
 //                     addition gives the same W in any order. The wave owns its two words of the candidate's row: plain stores
-//   k_pickf_resolve   one workgroup per query over the candidates in ascending chunks of 256: "the last covered clip mesh so far" is an
-//                     inclusive max-scan carried across chunks, its draw is the S a lane tests against; the answer is the highest
-//                     passing lane. The same workgroup then finds the largest covering triangle of the winner and writes the record
+//   k_pickf_resolve   one workgroup per query over the candidates in ascending chunks of 256: "the last covered clip mesh so far"
+//                     (stamper_before_me, vgx_wave.h), its draw is the S a lane tests against; the answer is the highest passing
+//                     lane. The same workgroup then finds the largest covering triangle of the winner and writes the record
 // No host round trip, no count comes back, every table is sized by the range. Bits are ORed and maxima taken: the same result every run.
 namespace {
 
 #define VGX_PICKF_CAND    0x100u // beside the mode in VgxPickfMesh::mode: the mesh is a candidate
 #define VGX_PICKF_CONTOUR 0x200u // ... and of kind VGX_MESH_CONTOURS
-#define VGX_PICKF_VALID   0x80000000u // beside the flags of a staged query: the point is one (vgx_pickf_point)
 
-struct PickfQuery { float x, y; int32_t X, Y; uint32_t mesh_end, flags; }; // 24 bytes
+struct PickfQuery : VgxPickStagedPoint { uint32_t mesh_end, flags; }; // 24 bytes
 
 __device__ __forceinline__ PickfQuery pickf_query(const vgx_pick_query Q)
 {
 	PickfQuery P;
-	double px, py;
-	P.x = Q.x; P.y = Q.y; P.mesh_end = Q.mesh_end;
-	P.flags = (Q.flags & ~VGX_PICKF_VALID) | (vgx_pickf_point(Q.x, Q.y, &px, &py, &P.X, &P.Y) ? VGX_PICKF_VALID : 0u);
+	P.mesh_end = Q.mesh_end;
+	P.flags = vgx_pick_stage_point(Q.x, Q.y, Q.flags, true, &P);
 	return P;
 }
 
@@ -191,7 +181,7 @@ __global__ __launch_bounds__(256) void k_pickf_meshes(VgxPickfArgs A)
 		if (st.elems) {
 			for (uint32_t q = 0; q < A.nqueries; ++q) {
 				const PickfQuery Q = s_q[q];
-				cand = cand || ((Q.flags & VGX_PICKF_VALID) && vgx_pickf_in_scissor(st.rect, Q.X, Q.Y) && vgx_pickf_in_box(box, (double)Q.x, (double)Q.y));
+				cand = cand || ((Q.flags & VGX_PICK_STAGED_VALID) && vgx_pickf_in_scissor(st.rect, Q.X, Q.Y) && vgx_pickf_in_box(box, (double)Q.x, (double)Q.y));
 			}
 		}
 		if (cand) { st.mode |= VGX_PICKF_CAND | (vgx_raster_kind_is_contours(me.subpath_kind) ? VGX_PICKF_CONTOUR : 0u); }
@@ -253,27 +243,20 @@ __global__ __launch_bounds__(256) void k_pickf_tris(VgxPickfArgs A)
 	for (uint64_t tile = blockIdx.x; tile < numTiles; tile += gridDim.x) {
 		const uint64_t T0 = tile * VGX_PICK_TILE + (uint64_t)wave * VGX_WAVE;
 		if (T0 >= totalTris) { continue; } // the last tile's empty waves; nothing below synchronises the workgroup
-		// the candidate that owns T0 (P[0] = 0 <= T0 < P[numTri] = totalTris; P is strictly ascending), then 64 entries from there
-		const uint64_t c0 = find_owner_u64(A.tri_prefix, 0, numTri, T0);
-		const uint64_t ck = c0 + (uint64_t)lane;
-		const uint64_t w = ck <= numTri ? A.tri_prefix[ck] : ~0ull;
-		const uint64_t T = T0 + (uint64_t)lane;
-		const bool live = T < totalTris;
-		uint64_t first = 0;
-		const int k = window_owner(w, live ? T : T0, &first);
+		const WaveOwners o = wave_owners(A.tri_prefix, numTri, totalTris, T0, lane); // every triangle candidate has a triangle: P is strictly ascending
 		// the lanes of one candidate are consecutive: my candidate's lanes as a mask, for "one atomic per candidate"
-		const int kPrev = __shfl_up(k, 1);
-		const uint64_t heads = wave_ballot(lane == 0 || k != kPrev);
+		const int kPrev = __shfl_up(o.k, 1);
+		const uint64_t heads = wave_ballot(lane == 0 || o.k != kPrev);
 		const uint64_t segBelow = lanemask_ge(seg_head(heads, lane)) & lanemask_lt(lane); // my candidate's lanes below me
 		uint32_t c = 0, mode = 0;
 		uint32_t rect[4] = { 0u, 0u, 0u, 0u };
 		float box[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
 		VgxRasterTri Tri;
 		bool ok = false, transparent = false;
-		if (live) {
-			c = A.tri_cand[c0 + (uint64_t)k];
+		if (o.live) {
+			c = A.tri_cand[o.c0 + (uint64_t)o.k];
 			const uint32_t r = A.cand_mesh[c];
-			const uint32_t t = (uint32_t)(T - first);
+			const uint32_t t = (uint32_t)(T0 + (uint64_t)lane - o.first);
 			const uint64_t m = A.mesh_begin + r;
 			const vgx_mesh me = A.meshes[m];
 			const uint16_t* ip = A.idx + me.first_index + 3ull * t;
@@ -299,7 +282,7 @@ __global__ __launch_bounds__(256) void k_pickf_tris(VgxPickfArgs A)
 		if (!wave_ballot(ok)) { continue; }
 		for (uint32_t q = 0; q < A.nqueries; ++q) {
 			const PickfQuery Q = s_q[q];
-			if (!(Q.flags & VGX_PICKF_VALID)) { continue; }
+			if (!(Q.flags & VGX_PICK_STAGED_VALID)) { continue; }
 			const double px = (double)Q.x, py = (double)Q.y;
 			double E[3], S;
 			const bool hit = ok && !(transparent && vgx_pickf_skips(mode, Q.flags)) && vgx_pickf_in_scissor(rect, Q.X, Q.Y) && vgx_pickf_in_box(box, px, py)
@@ -368,24 +351,10 @@ __global__ __launch_bounds__(VGX_WAVE) void k_pickf_contours(VgxPickfArgs A)
 	}
 }
 
-// the maximum over the workgroup of 256, on every thread; s_w holds 4 words and is free again on return
-__device__ __forceinline__ uint32_t pickf_block_max(uint32_t v, uint32_t* s_w)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, d); v = v > o ? v : o; }
-	if ((threadIdx.x & 63) == 0) { s_w[threadIdx.x >> 6] = v; }
-	__syncthreads();
-	const uint32_t a = s_w[0], b = s_w[1], c = s_w[2], d = s_w[3];
-	__syncthreads();
-	const uint32_t ab = a > b ? a : b, cd = c > d ? c : d;
-	return ab > cd ? ab : cd;
-}
-
 __global__ __launch_bounds__(256) void k_pickf_resolve(VgxPickfArgs A)
 {
 	__shared__ uint32_t s_w[4];
 	const uint32_t q = blockIdx.x, tid = threadIdx.x;
-	const int lane = tid & 63, wave = tid >> 6;
 	const vgx_pick_query Q = A.queries[q];
 	double px, py;
 	int32_t X, Y;
@@ -402,22 +371,13 @@ __global__ __launch_bounds__(256) void k_pickf_resolve(VgxPickfArgs A)
 			const uint4 s0 = *(const uint4*)(A.mesh_state + r);
 			mode = s0.x & 0xFFu; f = s0.y; n = s0.z;
 		}
-		uint32_t key = covered && mode == VGX_RF_STAMP ? (uint32_t)c + 1u : 0u;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)key, d); if (lane >= d && o > key) { key = o; } }
-		if (lane == 63) { s_w[wave] = key; }
-		__syncthreads();
-		uint32_t before = carry, total = carry;
-		for (int w = 0; w < 4; ++w) { const uint32_t t = s_w[w]; if (w < wave && t > before) { before = t; } if (t > total) { total = t; } }
-		__syncthreads();
-		const uint32_t stamper = key > before ? key : before;
-		carry = total;
+		const uint32_t stamper = stamper_before_me(covered && mode == VGX_RF_STAMP ? (uint32_t)c + 1u : 0u, &carry, s_w);
 		if (covered && mode != VGX_RF_STAMP) {
 			const uint32_t S = stamper ? A.mesh_state[A.cand_mesh[stamper - 1u]].f : VGX_RASTER_STAMP_NONE;
 			if (vgx_pickf_hit(mode, f, n, S, A.mesh_begin + r, Q.mesh_end)) { best = (uint32_t)c + 1u; }
 		}
 	}
-	best = pickf_block_max(best, s_w);
+	best = block_max_u32(best, s_w);
 	uint32_t mesh = VGX_PICK_NONE, top = 0;
 	if (best) { // uniform over the workgroup
 		const uint32_t r = A.cand_mesh[best - 1u];
@@ -437,7 +397,7 @@ __global__ __launch_bounds__(256) void k_pickf_resolve(VgxPickfArgs A)
 				if (vgx_pickf_tri(v2(p0.x, p0.y), v2(p1.x, p1.y), v2(p2.x, p2.y), px, py)) { top = t + 1u; }
 			}
 		}
-		top = pickf_block_max(top, s_w);
+		top = block_max_u32(top, s_w);
 	}
 	if (tid == 0) { A.hits[q] = vgx_pickf_record(mesh, top - 1u, A.meshes); } // top == 0: a contour mesh, or no hit: 0xFFFFFFFF
 }

@@ -21,9 +21,7 @@ VGX_HD void vgx_pickc_cmd_state(const vgx_raster_cmd& c, uint32_t index, uint64_
 {
 	st->mode = VGX_RF_INVALID; st->f = st->n = st->elems = 0u;
 	st->rect[0] = st->rect[1] = st->rect[2] = st->rect[3] = 0u;
-	if (c.type > 3u || c.reserved != 0u || c.num_vertices > 65536u) { return; }
-	if (c.first_vertex > numVertices || (uint64_t)c.num_vertices > numVertices - c.first_vertex) { return; }
-	if (c.first_index > numIndices || (uint64_t)c.num_indices > numIndices - c.first_index) { return; }
+	if (c.type > 3u || c.reserved != 0u || !vgx_rasterc_ranges_valid(c, numVertices, numIndices)) { return; }
 	if (c.clip_first_cmd != VGX_RASTERC_NONE && (uint64_t)c.clip_first_cmd + (uint64_t)c.clip_num_cmds > (uint64_t)realCmds) { return; }
 	if (c.type == 3u) {
 		st->mode = VGX_RF_STAMP; st->f = index;
@@ -88,21 +86,14 @@ VGX_HD vgx_pick_cmd_hit vgx_pickc_record(uint32_t cmd, uint32_t triangle, const 
 	return h;
 }
 
-// What vgx_pick_commands refuses before anything runs (host only): VGX_OK, VGX_E_INVALID_ARG or VGX_E_RANGE. The first failing check
-// of this order decides. uv and uv_bytes are validated as vgx_raster_commands does and never read
+// What vgx_pick_commands refuses before anything runs (host only): VGX_OK, VGX_E_INVALID_ARG or VGX_E_RANGE, the latter last
 static inline int vgx_pickc_check_args(const vgx_raster_streams* sm, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
                                        const vgx_pick_owners* owners, const vgx_pick_cmd_query* queries, uint32_t nqueries, const vgx_pick_cmd_hit* hits,
                                        const uint32_t* status)
 {
-	if (!sm || (num_cmds && !cmds) || (nqueries && (!queries || !hits))) { return VGX_E_INVALID_ARG; }
-	if ((sm->uv_bytes != 0u && sm->uv_bytes != 4u && sm->uv_bytes != 8u) || (sm->uv != nullptr && sm->uv_bytes == 0u) || sm->reserved != 0u) { return VGX_E_INVALID_ARG; }
-	if (sm->uv && ((uintptr_t)sm->uv & (sm->uv_bytes - 1u))) { return VGX_E_INVALID_ARG; }
-	if ((sm->num_vertices && (!sm->pos || !sm->color)) || (sm->num_indices && !sm->idx)) { return VGX_E_INVALID_ARG; }
+	if (vgx_streams_check(sm, cmds, num_cmds, dev_num_cmds) != VGX_OK || (nqueries && (!queries || !hits))) { return VGX_E_INVALID_ARG; }
 	if (owners && ((owners->num_meshes && !owners->meshes) || ((uintptr_t)owners->meshes & 7u))) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)queries & 7u) || ((uintptr_t)hits & 15u) || ((uintptr_t)status & 3u) || ((uintptr_t)dev_num_cmds & 3u) || ((uintptr_t)cmds & 7u)
-		|| ((uintptr_t)sm->pos & 7u) || ((uintptr_t)sm->color & 3u) || ((uintptr_t)sm->idx & 1u)) {
-		return VGX_E_INVALID_ARG;
-	}
+	if (((uintptr_t)queries & 7u) || ((uintptr_t)hits & 15u) || ((uintptr_t)status & 3u)) { return VGX_E_INVALID_ARG; }
 	if (nqueries > VGX_PICK_MAX_QUERIES) { return VGX_E_RANGE; }
 	return VGX_OK;
 }

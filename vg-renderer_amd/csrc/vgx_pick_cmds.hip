@@ -9,19 +9,18 @@
 //                    workgroup in LDS: validity of the record, mode, region and scissor (vgx_pickc_cmd_state), and whether the command
 //                    is a candidate -- it has a triangle and some point lies in its scissor. The same grid zeroes the top table
 //   scan OpPickcCmds every candidate's first chunk, the chunk total and the count of invalid records; finish() decides dev_status
-//   k_pickc_tris     the hot path. Fixed grid, one WAVE per chunk; a wave takes a contiguous run of the chunks (the total lives on the
-//                    device), finds the run's first command by find_owner_u64 over the command prefix and walks the prefix from there. A lane loads three indices and three positions once and runs
-//                    vgx_raster_setup once -- and only when some query lies in the chunk's box -- and three colours only when some
-//                    query asks for the transparency rule and the command is no Clip. A wave reduction over the corners gives the
-//                    chunk's box. The queries are staged in LDS SORTED by x (a rank count per
-//                    workgroup), so a chunk bisects to the queries inside its box's x range and loops over those alone; the loop is
-//                    wave-uniform: a query outside the command's scissor or the box's y range, or whose limit lies below the chunk,
-//                    costs scalar tests and no vector work. Lanes ascend in t, so the highest counting lane holds the chunk's
-//                    maximum: ONE atomicMax of t + 1 per wave and query. No per-chunk storage: overlapping index ranges leave the
-//                    chunk total unbounded
-//   k_pickc_resolve  one workgroup per query over the commands in ascending blocks of 256: k_pickf_resolve's inclusive max-scan of
-//                    "the last covering clip command so far", carried across blocks, then the stamp test; the answer is the highest
-//                    passing command, its triangle is the table's word. One lane does the owner search and writes the record
+//   k_pickc_tris     the hot path. Fixed grid, one WAVE per chunk, the chunks of a wave contiguous (VgxChunkWalk, vgx_raster_cmds.h). A
+//                    lane loads three indices and three positions once and runs vgx_raster_setup once -- and only when some query
+//                    lies in the chunk's box -- and three colours only when some query asks for the transparency rule and the command
+//                    is no Clip. A wave reduction over the corners (vgx_wave.h) gives the chunk's box. The queries are staged in LDS
+//                    SORTED by x (a rank count per workgroup), so a chunk bisects to the queries inside its box's x range and loops
+//                    over those alone; the loop is wave-uniform: a query outside the command's scissor or the box's y range, or whose
+//                    limit lies below the chunk, costs scalar tests and no vector work. Lanes ascend in t, so the highest counting
+//                    lane holds the chunk's maximum: ONE atomicMax of t + 1 per wave and query. No per-chunk storage: overlapping
+//                    index ranges leave the chunk total unbounded
+//   k_pickc_resolve  one workgroup per query over the commands in ascending blocks of 256: "the last covering clip command so far"
+//                    (stamper_before_me, vgx_wave.h), then the stamp test; the answer is the highest passing command, its triangle
+//                    is the table's word. One lane does the owner search and writes the record
 // Maxima only: the result does not depend on the order of the work.
 // vgx_pick_commands_boxed runs the BOXED instantiations of k_pickc_cmds and k_pickc_tris: a command is a candidate only when some point
 // lies in its scissor AND in its entry of the caller's box table (vgx_cmd_bounds.h), so a boxed-out command gets no chunks, and the
@@ -35,24 +34,15 @@
 namespace {
 
 #define VGX_PICKC_CAND  0x100u      // beside the mode in VgxPickfMesh::mode: the command has chunks
-#define VGX_PICKC_VALID 0x80000000u // beside the flags of a staged query: it takes part (vgx_pickc_point)
 
-struct PickcQuery { float x, y; int32_t X, Y; uint32_t cmd_end, tri_end, flags, q; }; // 32 bytes; q: the query's number, once the list is sorted
+struct PickcQuery : VgxPickStagedPoint { uint32_t cmd_end, tri_end, flags, q; }; // 32 bytes; q: the query's number, once the list is sorted
 
 __device__ __forceinline__ PickcQuery pickc_query(const vgx_pick_cmd_query Q)
 {
 	PickcQuery P;
-	double px, py;
-	P.x = Q.x; P.y = Q.y; P.cmd_end = Q.cmd_end; P.tri_end = Q.tri_end; P.q = 0u;
-	P.flags = (Q.flags & ~VGX_PICKC_VALID) | (vgx_pickc_point(Q, &px, &py, &P.X, &P.Y) ? VGX_PICKC_VALID : 0u);
+	P.cmd_end = Q.cmd_end; P.tri_end = Q.tri_end; P.q = 0u;
+	P.flags = vgx_pick_stage_point(Q.x, Q.y, Q.flags, Q.reserved == 0u, &P); // takes part: vgx_pickc_point
 	return P;
-}
-
-__device__ __forceinline__ uint32_t pickc_real_cmds(const VgxPickcArgs& A)
-{
-	if (!A.dev_num_cmds) { return A.num_cmds; }
-	const uint32_t n = *A.dev_num_cmds;
-	return n < A.num_cmds ? n : A.num_cmds;
 }
 
 // BOXED (vgx_pick_commands_boxed): a command is a candidate only when some point also lies in its box. vgx_pick_commands launches the
@@ -66,7 +56,7 @@ __global__ __launch_bounds__(256) void k_pickc_cmds(VgxPickcArgs A)
 	const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	const uint64_t words = (uint64_t)A.nqueries * A.num_cmds;
 	for (uint64_t w = first; w < words; w += stride) { A.top[w] = 0u; }
-	const uint32_t n = pickc_real_cmds(A);
+	const uint32_t n = vgx_real_cmds(A.num_cmds, A.dev_num_cmds);
 	for (uint64_t c = first; c < n; c += stride) {
 		VgxPickfMesh st;
 		vgx_pickc_cmd_state(A.cmds[c], (uint32_t)c, A.num_vertices, A.num_indices, n, &st);
@@ -76,7 +66,7 @@ __global__ __launch_bounds__(256) void k_pickc_cmds(VgxPickcArgs A)
 			if (BOXED) { const float4 b = *(const float4*)(A.cmd_bounds + 4ull * c); box[0] = b.x; box[1] = b.y; box[2] = b.z; box[3] = b.w; }
 			for (uint32_t q = 0; q < A.nqueries; ++q) {
 				const PickcQuery Q = s_q[q];
-				cand = cand || ((Q.flags & VGX_PICKC_VALID) && vgx_pickf_in_scissor(st.rect, Q.X, Q.Y) && (!BOXED || vgx_cmdb_holds(box, Q.x, Q.y)));
+				cand = cand || ((Q.flags & VGX_PICK_STAGED_VALID) && vgx_pickf_in_scissor(st.rect, Q.X, Q.Y) && (!BOXED || vgx_cmdb_holds(box, Q.x, Q.y)));
 			}
 			if (cand) { st.mode |= VGX_PICKC_CAND; }
 		}
@@ -87,7 +77,7 @@ __global__ __launch_bounds__(256) void k_pickc_cmds(VgxPickcArgs A)
 struct OpPickcCmds
 {
 	VgxPickcArgs A;
-	__device__ uint64_t size() const { return pickc_real_cmds(A); }
+	__device__ uint64_t size() const { return vgx_real_cmds(A.num_cmds, A.dev_num_cmds); }
 	__device__ Sum3 load(uint64_t i) const
 	{
 		Sum3 r = sum3_zero();
@@ -99,26 +89,12 @@ struct OpPickcCmds
 	__device__ void store(uint64_t i, Sum3 e) const { A.cmd_first[i] = e.a; }
 	__device__ void finish(Sum3 t) const
 	{
-		const uint32_t n = pickc_real_cmds(A);
+		const uint32_t n = vgx_real_cmds(A.num_cmds, A.dev_num_cmds);
 		A.cmd_first[n] = t.a;
 		A.state[VGX_PICKC_CHUNKS] = t.a; A.state[VGX_PICKC_INVALID] = t.c; A.state[VGX_PICKC_CMDS] = n;
 		if (A.status) { *A.status = t.c ? (uint32_t)VGX_E_INVALID_ARG : (uint32_t)VGX_OK; }
 	}
 };
-
-// minimum / maximum over the wave, on every lane, as a scalar
-__device__ __forceinline__ float pickc_wave_min(float v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) { v = fminf(v, __shfl_xor(v, d)); }
-	return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-}
-__device__ __forceinline__ float pickc_wave_max(float v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) { v = fmaxf(v, __shfl_xor(v, d)); }
-	return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-}
 
 template<bool BOXED>
 __global__ __launch_bounds__(256) void k_pickc_tris(VgxPickcArgs A)
@@ -132,7 +108,7 @@ __global__ __launch_bounds__(256) void k_pickc_tris(VgxPickcArgs A)
 	bool valid = false, wantAlpha = false;
 	if (tid < A.nqueries) {
 		P = pickc_query(A.queries[tid]);
-		valid = (P.flags & VGX_PICKC_VALID) != 0u;
+		valid = (P.flags & VGX_PICK_STAGED_VALID) != 0u;
 		wantAlpha = valid && (P.flags & VGX_PICK_SKIP_TRANSPARENT) != 0u;
 	}
 	s_x[tid] = valid ? P.x : __int_as_float(0x7FC00000); // NaN: compares false, counts for nothing below
@@ -154,28 +130,23 @@ __global__ __launch_bounds__(256) void k_pickc_tris(VgxPickcArgs A)
 	const uint64_t total = A.state[VGX_PICKC_CHUNKS];
 	const uint32_t n = (uint32_t)A.state[VGX_PICKC_CMDS];
 	const int lane = threadIdx.x & (VGX_WAVE - 1);
-	const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / VGX_WAVE);
 	const float inf = __int_as_float(0x7F800000);
-	// a wave takes a CONTIGUOUS run of chunks: one search for the run's first command, then a walk over the prefix; the command's
-	// record and state are loaded once per command, not once per chunk (a stride over the chunks paid ten dependent loads for each)
-	const uint64_t per = (total + waves - 1u) / waves;
-	const uint64_t w = (uint64_t)blockIdx.x * (blockDim.x / VGX_WAVE) + (threadIdx.x / VGX_WAVE);
-	const uint64_t k0 = w * per < total ? w * per : total, k1 = k0 + per < total ? k0 + per : total; // wave-uniform; nothing below synchronises the workgroup
-	if (k0 >= k1) { return; }
-	uint32_t c = (uint32_t)find_owner_u64(A.cmd_first, 0, n, k0); // the last command whose first chunk is <= k0: the one with chunks
-	uint64_t first = A.cmd_first[c], next = A.cmd_first[c + 1u];
-	vgx_raster_cmd cmd = A.cmds[c];
-	VgxPickfMesh st = A.cmd_state[c];
+	// a wave takes a contiguous run of chunks (VgxChunkWalk): the command's record, state and box are loaded once per command, not once
+	// per chunk (a stride over the chunks paid ten dependent loads for each)
+	VgxChunkWalk W(A.cmd_first, n, total, (uint64_t)blockIdx.x * (blockDim.x / VGX_WAVE) + (threadIdx.x / VGX_WAVE), (uint64_t)gridDim.x * (blockDim.x / VGX_WAVE));
+	if (W.k0 >= W.k1) { return; }
+	vgx_raster_cmd cmd = A.cmds[W.c];
+	VgxPickfMesh st = A.cmd_state[W.c];
 	float box[4] = { 0.0f, 0.0f, 0.0f, 0.0f }; // BOXED: the command's entry, wave-uniform as the record and the state are
-	if (BOXED) { const float4 b = *(const float4*)(A.cmd_bounds + 4ull * c); box[0] = b.x; box[1] = b.y; box[2] = b.z; box[3] = b.w; }
-	for (uint64_t k = k0; k < k1; ++k) {
-		if (k >= next) { // cmd_first[n] = total > k: the walk ends inside the table; commands without chunks are passed over
-			do { ++c; first = next; next = A.cmd_first[c + 1u]; } while (k >= next);
-			cmd = A.cmds[c]; st = A.cmd_state[c];
-			if (BOXED) { const float4 b = *(const float4*)(A.cmd_bounds + 4ull * c); box[0] = b.x; box[1] = b.y; box[2] = b.z; box[3] = b.w; }
+	if (BOXED) { const float4 b = *(const float4*)(A.cmd_bounds + 4ull * W.c); box[0] = b.x; box[1] = b.y; box[2] = b.z; box[3] = b.w; }
+	for (uint64_t k = W.k0; k < W.k1; ++k) {
+		if (W.advance(k)) {
+			cmd = A.cmds[W.c]; st = A.cmd_state[W.c];
+			if (BOXED) { const float4 b = *(const float4*)(A.cmd_bounds + 4ull * W.c); box[0] = b.x; box[1] = b.y; box[2] = b.z; box[3] = b.w; }
 		}
+		const uint32_t c = W.c;
 		const uint32_t mode = st.mode & 0xFFu;
-		const uint32_t t0 = (uint32_t)(k - first) * VGX_RASTERC_CHUNK;
+		const uint32_t t0 = (uint32_t)(k - W.first) * VGX_RASTERC_CHUNK;
 		const uint32_t t = t0 + (uint32_t)lane;
 		uint64_t v[3];
 		float2 p0 = make_float2(0.0f, 0.0f), p1 = p0, p2 = p0;
@@ -187,9 +158,9 @@ __global__ __launch_bounds__(256) void k_pickc_tris(VgxPickcArgs A)
 		if (!wave_ballot(have)) { continue; }
 		// The chunk's box over the corners of ALL its triangles, before any setup: a superset of every covering triangle's box, which is
 		// all the tests below need (fminf / fmaxf pass over a NaN; a box of NaNs alone compares false and sends the chunk on to the
-		// setup, which then finds nothing). Most chunks of a large frame end here
-		const float bx0 = pickc_wave_min(have ? fminf(fminf(p0.x, p1.x), p2.x) : inf), by0 = pickc_wave_min(have ? fminf(fminf(p0.y, p1.y), p2.y) : inf);
-		const float bx1 = pickc_wave_max(have ? fmaxf(fmaxf(p0.x, p1.x), p2.x) : -inf), by1 = pickc_wave_max(have ? fmaxf(fmaxf(p0.y, p1.y), p2.y) : -inf);
+		// setup, which then finds nothing). Most chunks of a large frame end here. Scalars: the query loops below are wave-uniform
+		const float bx0 = wave_uniform_f32(wave_min_f32(have ? fminf(fminf(p0.x, p1.x), p2.x) : inf)), by0 = wave_uniform_f32(wave_min_f32(have ? fminf(fminf(p0.y, p1.y), p2.y) : inf));
+		const float bx1 = wave_uniform_f32(wave_max_f32(have ? fmaxf(fmaxf(p0.x, p1.x), p2.x) : -inf)), by1 = wave_uniform_f32(wave_max_f32(have ? fmaxf(fmaxf(p0.y, p1.y), p2.y) : -inf));
 		uint32_t qa = 0, qb = nvalid; // the first sorted query with x >= bx0
 		while (qa < qb) {
 			const uint32_t mid = qa + ((qb - qa) >> 1);
@@ -224,24 +195,10 @@ __global__ __launch_bounds__(256) void k_pickc_tris(VgxPickcArgs A)
 	}
 }
 
-// the maximum over the workgroup of 256, on every thread; s_w holds 4 words and is free again on return
-__device__ __forceinline__ uint32_t pickc_block_max(uint32_t v, uint32_t* s_w)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, d); v = v > o ? v : o; }
-	if ((threadIdx.x & 63) == 0) { s_w[threadIdx.x >> 6] = v; }
-	__syncthreads();
-	const uint32_t a = s_w[0], b = s_w[1], c = s_w[2], d = s_w[3];
-	__syncthreads();
-	const uint32_t ab = a > b ? a : b, cd = c > d ? c : d;
-	return ab > cd ? ab : cd;
-}
-
 __global__ __launch_bounds__(256) void k_pickc_resolve(VgxPickcArgs A)
 {
 	__shared__ uint32_t s_w[4];
 	const uint32_t q = blockIdx.x, tid = threadIdx.x;
-	const int lane = tid & 63, wave = tid >> 6;
 	double px, py;
 	int32_t X, Y;
 	const bool point = vgx_pickc_point(A.queries[q], &px, &py, &X, &Y);
@@ -257,19 +214,10 @@ __global__ __launch_bounds__(256) void k_pickc_resolve(VgxPickcArgs A)
 			const uint4 s0 = *(const uint4*)(A.cmd_state + c);
 			mode = s0.x & 0xFFu; f = s0.y; nn = s0.z;
 		}
-		uint32_t key = covered && mode == VGX_RF_STAMP ? (uint32_t)c + 1u : 0u;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)key, d); if (lane >= d && o > key) { key = o; } }
-		if (lane == 63) { s_w[wave] = key; }
-		__syncthreads();
-		uint32_t before = carry, total = carry;
-		for (int w = 0; w < 4; ++w) { const uint32_t t = s_w[w]; if (w < wave && t > before) { before = t; } if (t > total) { total = t; } }
-		__syncthreads();
-		const uint32_t stamper = key > before ? key : before;
-		carry = total;
+		const uint32_t stamper = stamper_before_me(covered && mode == VGX_RF_STAMP ? (uint32_t)c + 1u : 0u, &carry, s_w);
 		if (covered && vgx_pickc_hit(mode, f, nn, stamper ? stamper - 1u : VGX_RASTER_STAMP_NONE)) { best = (uint32_t)c + 1u; } // a clip command stamps its own index
 	}
-	best = pickc_block_max(best, s_w);
+	best = block_max_u32(best, s_w);
 	if (tid == 0) {
 		A.hits[q] = vgx_pickc_record(best ? best - 1u : VGX_PICK_NONE, best ? top[best - 1u] - 1u : VGX_PICK_NONE, A.cmds, A.meshes, A.num_meshes);
 	}

@@ -532,15 +532,35 @@ VGX_HD void vgx_raster_mesh_state(int level, const vgx_mesh& me, uint32_t stateK
 	st->pad = painted | handle | contour;
 }
 
-// ---- the arguments of the four calls (host only) ---------------------------------------------------------------------------------
+// ---- the arguments of the calls (host only) ----------------------------------------------------------------------------------------
+// Every check of these functions answers VGX_E_INVALID_ARG, and the callers put their VGX_E_RANGE checks last: which of several failing
+// checks decides cannot be observed, so the checkers fold their common parts without minding the order.
+// The target's size and origin: what the damage marks ask of a target, which write no pixel
+static inline int vgx_target_extent_check(const vgx_raster_target& t)
+{
+	if (t.width > 16384u || t.height > 16384u || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
+	return VGX_OK;
+}
+
+// A target a call draws into: the extent, the stride, the scissor inside the image, and pixels unless the scissor is empty
+static inline int vgx_target_check(const vgx_raster_target* target)
+{
+	if (!target || vgx_target_extent_check(*target) != VGX_OK) { return VGX_E_INVALID_ARG; }
+	const vgx_raster_target& t = *target;
+	if (t.stride < t.width || ((uintptr_t)t.pixels & 3u)) { return VGX_E_INVALID_ARG; }
+	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
+	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
+	return !empty && !t.pixels ? VGX_E_INVALID_ARG : VGX_OK;
+}
+
 // What vgx_raster (VGX_RL_PLAIN: state, tex and paints are not looked at), vgx_raster_frame, vgx_raster_textured and vgx_raster_painted
 // refuse before anything runs, for the device calls and for the vgxt_* host loops alike: VGX_OK, VGX_E_INVALID_ARG or VGX_E_RANGE.
-// `status` is where the call leaves its status (may be null). The first failing check of this order decides
+// `status` is where the call leaves its status (may be null)
 static inline int vgx_raster_check_args(int level, const vgx_cache_desc* frame, const float* mesh_bounds, uint64_t mesh_begin, uint64_t mesh_end,
                                         const vgx_raster_draws* state, const vgx_raster_textures* tex, const vgx_raster_paints* paints,
                                         const vgx_raster_target* target, const uint32_t* status)
 {
-	if (!frame || !target || (level >= VGX_RL_FRAME && !state) || (level >= VGX_RL_TEXTURED && !tex) || (level >= VGX_RL_PAINTED && !paints)) { return VGX_E_INVALID_ARG; }
+	if (!frame || vgx_target_check(target) != VGX_OK || (level >= VGX_RL_FRAME && !state) || (level >= VGX_RL_TEXTURED && !tex) || (level >= VGX_RL_PAINTED && !paints)) { return VGX_E_INVALID_ARG; }
 	if (level >= VGX_RL_PAINTED) {
 		if ((paints->num_gradients && !paints->gradients) || (paints->num_patterns && !paints->patterns)) { return VGX_E_INVALID_ARG; }
 		if (((uintptr_t)paints->gradients & 3u) || ((uintptr_t)paints->patterns & 3u)) { return VGX_E_INVALID_ARG; }
@@ -554,16 +574,11 @@ static inline int vgx_raster_check_args(int level, const vgx_cache_desc* frame, 
 		if (state->reserved != 0u || (state->num_draws && (!state->draws || !state->draw_state))) { return VGX_E_INVALID_ARG; }
 		if (((uintptr_t)state->draws & 3u) || ((uintptr_t)state->draw_state & 3u)) { return VGX_E_INVALID_ARG; }
 	}
-	const vgx_raster_target& t = *target;
-	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
-	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
 	if (frame->num_meshes && (!frame->pos || !frame->color || !frame->idx || !frame->meshes)) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
+	if (((uintptr_t)status & 3u) || ((uintptr_t)mesh_bounds & 15u) || ((uintptr_t)frame->pos & 7u)
 		|| ((uintptr_t)frame->color & 3u) || ((uintptr_t)frame->idx & 1u) || ((uintptr_t)frame->meshes & 7u)) {
 		return VGX_E_INVALID_ARG;
 	}
-	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
-	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
 	if (frame->num_meshes >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
 	return VGX_OK;
 }

@@ -86,17 +86,6 @@ __global__ __launch_bounds__(256) void k_raster_entries(VgxRasterArgs A)
 	}
 }
 
-// first index of [0, n) whose key is >= x, else n
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t n, uint32_t x)
-{
-	uint32_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint32_t mid = lo + ((hi - lo) >> 1);
-		if (a[mid] < x) { lo = mid + 1u; } else { hi = mid; }
-	}
-	return lo;
-}
-
 __global__ __launch_bounds__(256) void k_raster_tiles(VgxRasterArgs A)
 {
 	__shared__ VgxRasterTri s_tri[256];

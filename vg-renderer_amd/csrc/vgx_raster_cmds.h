@@ -16,6 +16,13 @@
 VGX_HD uint32_t vgx_rasterc_triangles(const vgx_raster_cmd& c) { return c.num_indices / 3u; }
 VGX_HD uint32_t vgx_rasterc_chunks(const vgx_raster_cmd& c) { return (vgx_rasterc_triangles(c) + VGX_RASTERC_CHUNK - 1u) / VGX_RASTERC_CHUNK; }
 
+// The ranges of a record lie inside the streams (in 64 bits) and it has at most 65536 vertices: what every call asks before it walks one
+VGX_HD bool vgx_rasterc_ranges_valid(const vgx_raster_cmd& c, uint64_t numVertices, uint64_t numIndices)
+{
+	return c.num_vertices <= 65536u && c.first_vertex <= numVertices && (uint64_t)c.num_vertices <= numVertices - c.first_vertex
+	    && c.first_index <= numIndices && (uint64_t)c.num_indices <= numIndices - c.first_index;
+}
+
 // The tables a command may name: the streams' sizes, the real command count, the images and the two paint tables (null with a count of
 // 0 when the caller gave no paints)
 struct VgxRastercTables
@@ -35,9 +42,7 @@ VGX_HD void vgx_rasterc_cmd_state(const vgx_raster_cmd& c, uint32_t index, const
 {
 	st->mode = VGX_RF_INVALID; st->f = st->n = st->pad = 0u;
 	st->rect[0] = st->rect[1] = st->rect[2] = st->rect[3] = 0u;
-	if (c.type > 3u || c.reserved != 0u || c.num_vertices > 65536u) { return; }
-	if (c.first_vertex > tb.num_vertices || (uint64_t)c.num_vertices > tb.num_vertices - c.first_vertex) { return; }
-	if (c.first_index > tb.num_indices || (uint64_t)c.num_indices > tb.num_indices - c.first_index) { return; }
+	if (c.type > 3u || c.reserved != 0u || !vgx_rasterc_ranges_valid(c, tb.num_vertices, tb.num_indices)) { return; }
 	if (c.clip_first_cmd != VGX_RASTERC_NONE && (uint64_t)c.clip_first_cmd + (uint64_t)c.clip_num_cmds > (uint64_t)tb.real_cmds) { return; }
 	if (c.type == 0u && !tb.has_uv) { return; }
 	vgx_mesh me;
@@ -104,30 +109,71 @@ VGX_HD uint32_t vgx_rasterc_status(uint64_t chunks, uint64_t entries, bool inval
 	return st;
 }
 
+#ifdef __HIPCC__
+#include "vgx_wave.h"
+// ---- the device parts the three command-table families share (vgx_raster_cmds.hip, vgx_pick_cmds.hip, vgx_cmd_bounds.hip) -----------
+// The commands a call looks at: the host's count, clamped by the device's when the caller gave one
+__device__ __forceinline__ uint32_t vgx_real_cmds(uint32_t num_cmds, const uint32_t* dev_num_cmds)
+{
+	if (!dev_num_cmds) { return num_cmds; }
+	const uint32_t n = *dev_num_cmds;
+	return n < num_cmds ? n : num_cmds;
+}
+
+// One wave's CONTIGUOUS run [k0, k1) of the `total` chunks (wave w of `waves`, the launch's fixed grid) and its walk over the command
+// prefix cmd_first[0 .. n], cmd_first[n] = total: one search for the run's first command, then one load per command passed, where a
+// stride over the chunks pays a search and the command's loads for every chunk. Wave-uniform; nothing synchronises the workgroup. The
+// kernel works out w and waves: blockDim read in a device function is not folded with the launch bounds and costs a vector load.
+// k_pickc_tris and k_cmdb_tris walk this way; k_rasterc_count still strides with a search per chunk, and this is here for it
+struct VgxChunkWalk
+{
+	const uint64_t* cmd_first;
+	uint64_t k0, k1;      // k0 >= k1: the wave has no chunk and returns; c, first and next are not set
+	uint64_t first, next; // the chunks [first, next) of command c
+	uint32_t c;
+	__device__ __forceinline__ VgxChunkWalk(const uint64_t* cmdFirst, uint32_t n, uint64_t total, uint64_t w, uint64_t waves) : cmd_first(cmdFirst), first(0), next(0), c(0)
+	{
+		const uint64_t per = (total + waves - 1u) / waves;
+		k0 = w * per < total ? w * per : total; k1 = k0 + per < total ? k0 + per : total;
+		if (k0 >= k1) { return; }
+		c = (uint32_t)find_owner_u64(cmd_first, 0, n, k0); // the last command whose first chunk is <= k0: the one with chunks
+		first = cmd_first[c]; next = cmd_first[c + 1u];
+	}
+	// to the command of chunk k (k ascends by one); true when it is another one: the caller loads what it keeps per command.
+	// cmd_first[n] = total > k, so the walk ends inside the table; commands without chunks are passed over
+	__device__ __forceinline__ bool advance(uint64_t k)
+	{
+		if (k < next) { return false; }
+		do { ++c; first = next; next = cmd_first[c + 1u]; } while (k >= next);
+		return true;
+	}
+};
+#endif
+
 // ---- the host parts both libraries share -------------------------------------------------------------------------------------------
-// What vgx_raster_commands refuses before anything runs: VGX_OK or VGX_E_INVALID_ARG. The first failing check decides
+// A vgx_raster_streams + command-table pair, as vgx_raster_commands, vgx_pick_commands and vgx_command_bounds all ask for it: VGX_OK or
+// VGX_E_INVALID_ARG (vgx_raster.h: the order of the checks cannot be observed). uv and uv_bytes are validated whether the call reads them or not
+static inline int vgx_streams_check(const vgx_raster_streams* sm, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds)
+{
+	if (!sm || (num_cmds && !cmds)) { return VGX_E_INVALID_ARG; }
+	if ((sm->uv_bytes != 0u && sm->uv_bytes != 4u && sm->uv_bytes != 8u) || (sm->uv != nullptr && sm->uv_bytes == 0u) || sm->reserved != 0u) { return VGX_E_INVALID_ARG; }
+	if (sm->uv && ((uintptr_t)sm->uv & (sm->uv_bytes - 1u))) { return VGX_E_INVALID_ARG; }
+	if ((sm->num_vertices && (!sm->pos || !sm->color)) || (sm->num_indices && !sm->idx)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)dev_num_cmds & 3u) || ((uintptr_t)cmds & 7u) || ((uintptr_t)sm->pos & 7u) || ((uintptr_t)sm->color & 3u) || ((uintptr_t)sm->idx & 1u)) { return VGX_E_INVALID_ARG; }
+	return VGX_OK;
+}
+
+// What vgx_raster_commands refuses before anything runs: VGX_OK or VGX_E_INVALID_ARG
 static inline int vgx_rasterc_check_args(const vgx_raster_streams* sm, const vgx_raster_cmd* cmds, uint32_t num_cmds, const uint32_t* dev_num_cmds,
                                          const vgx_raster_image* images, uint32_t num_images, const vgx_raster_paints* paints, const vgx_raster_target* target,
                                          const uint32_t* status)
 {
-	if (!sm || !target || (num_cmds && !cmds)) { return VGX_E_INVALID_ARG; }
+	if (vgx_streams_check(sm, cmds, num_cmds, dev_num_cmds) != VGX_OK || vgx_target_check(target) != VGX_OK) { return VGX_E_INVALID_ARG; }
 	if (paints) {
 		if ((paints->num_gradients && !paints->gradients) || (paints->num_patterns && !paints->patterns)) { return VGX_E_INVALID_ARG; }
 		if (((uintptr_t)paints->gradients & 3u) || ((uintptr_t)paints->patterns & 3u)) { return VGX_E_INVALID_ARG; }
 	}
-	if ((sm->uv_bytes != 0u && sm->uv_bytes != 4u && sm->uv_bytes != 8u) || (sm->uv != nullptr && sm->uv_bytes == 0u) || sm->reserved != 0u) { return VGX_E_INVALID_ARG; }
-	if (sm->uv && ((uintptr_t)sm->uv & (sm->uv_bytes - 1u))) { return VGX_E_INVALID_ARG; }
-	if ((num_images && !images) || ((uintptr_t)images & 7u)) { return VGX_E_INVALID_ARG; }
-	const vgx_raster_target& t = *target;
-	if (t.width > 16384u || t.height > 16384u || t.stride < t.width || t.x0 > (1 << 23) || t.x0 < -(1 << 23) || t.y0 > (1 << 23) || t.y0 < -(1 << 23)) { return VGX_E_INVALID_ARG; }
-	if (t.scissor[0] > t.scissor[2] || t.scissor[1] > t.scissor[3] || t.scissor[2] > t.width || t.scissor[3] > t.height) { return VGX_E_INVALID_ARG; }
-	if ((sm->num_vertices && (!sm->pos || !sm->color)) || (sm->num_indices && !sm->idx)) { return VGX_E_INVALID_ARG; }
-	if (((uintptr_t)t.pixels & 3u) || ((uintptr_t)status & 3u) || ((uintptr_t)dev_num_cmds & 3u) || ((uintptr_t)cmds & 7u) || ((uintptr_t)sm->pos & 7u)
-		|| ((uintptr_t)sm->color & 3u) || ((uintptr_t)sm->idx & 1u)) {
-		return VGX_E_INVALID_ARG;
-	}
-	const bool empty = t.scissor[0] == t.scissor[2] || t.scissor[1] == t.scissor[3];
-	if (!empty && !t.pixels) { return VGX_E_INVALID_ARG; }
+	if ((num_images && !images) || ((uintptr_t)images & 7u) || ((uintptr_t)status & 3u)) { return VGX_E_INVALID_ARG; }
 	return VGX_OK;
 }
 

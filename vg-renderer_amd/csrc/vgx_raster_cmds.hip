@@ -35,13 +35,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t rasterc_real_cmds(const VgxRasterCmdArgs& A)
-{
-	if (!A.dev_num_cmds) { return A.num_cmds; }
-	const uint32_t n = *A.dev_num_cmds;
-	return n < A.num_cmds ? n : A.num_cmds;
-}
-
 __device__ __forceinline__ VgxRastercTables rasterc_tables(const VgxRasterCmdArgs& A, uint32_t real)
 {
 	VgxRastercTables tb;
@@ -58,7 +51,7 @@ __device__ __forceinline__ VgxRastercTables rasterc_tables(const VgxRasterCmdArg
 template <bool DAMAGE>
 __global__ __launch_bounds__(256) void k_rasterc_cmds(VgxRasterCmdArgs A)
 {
-	const uint32_t n = rasterc_real_cmds(A);
+	const uint32_t n = vgx_real_cmds(A.num_cmds, A.dev_num_cmds);
 	const VgxRastercTables tb = rasterc_tables(A, n);
 	for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (uint64_t)gridDim.x * blockDim.x) {
 		VgxRasterMeshState st;
@@ -82,7 +75,7 @@ __device__ __forceinline__ uint32_t rasterc_entries_of(const VgxRasterCmdArgs& A
 struct OpRastercCmds
 {
 	VgxRasterCmdArgs A;
-	__device__ uint64_t size() const { return rasterc_real_cmds(A); }
+	__device__ uint64_t size() const { return vgx_real_cmds(A.num_cmds, A.dev_num_cmds); }
 	__device__ Sum3 load(uint64_t i) const
 	{
 		Sum3 r = sum3_zero();
@@ -94,24 +87,11 @@ struct OpRastercCmds
 	__device__ void store(uint64_t i, Sum3 e) const { A.cmd_first[i] = e.a; }
 	__device__ void finish(Sum3 t) const
 	{
-		const uint32_t n = rasterc_real_cmds(A);
+		const uint32_t n = vgx_real_cmds(A.num_cmds, A.dev_num_cmds);
 		A.cmd_first[n] = t.a;
 		A.state[VGX_RASC_CHUNKS] = t.a; A.state[VGX_RASC_INVALID] = t.c; A.state[VGX_RASC_BEYOND] = 0ull; A.state[VGX_RASC_CMDS] = n;
 	}
 };
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, d); v = o < v ? o : v; }
-	return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, d); v = o > v ? o : v; }
-	return v;
-}
 
 template <bool DAMAGE>
 __global__ __launch_bounds__(256) void k_rasterc_count(VgxRasterCmdArgs A)
@@ -121,6 +101,7 @@ __global__ __launch_bounds__(256) void k_rasterc_count(VgxRasterCmdArgs A)
 	const uint32_t n = (uint32_t)A.state[VGX_RASC_CMDS];
 	const int lane = threadIdx.x & (VGX_WAVE - 1);
 	const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / VGX_WAVE);
+	// a stride over the chunks with a search per chunk; VgxChunkWalk (vgx_raster_cmds.h) is the contiguous walk, should this move to it
 	for (uint64_t k = (uint64_t)blockIdx.x * (blockDim.x / VGX_WAVE) + (threadIdx.x / VGX_WAVE); k < total; k += waves) { // wave-uniform
 		const uint32_t c = (uint32_t)find_owner_u64(A.cmd_first, 0, n, k); // the last command whose first chunk is <= k: the one with chunks
 		const vgx_raster_cmd cmd = A.cmds[c];
@@ -188,17 +169,6 @@ __global__ __launch_bounds__(256) void k_rasterc_entries(VgxRasterCmdArgs A)
 		}
 	}
 	if (A.cmd_state[A.chunk_cmd[k]].pad & VGX_RT_PAINTED) { mark_tiles(A.tile_paint, r, A.tiles_w); }
-}
-
-// first index of [0, n) whose key is >= x, else n
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t n, uint32_t x)
-{
-	uint32_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint32_t mid = lo + ((hi - lo) >> 1);
-		if (a[mid] < x) { lo = mid + 1u; } else { hi = mid; }
-	}
-	return lo;
 }
 
 // 168 bytes: the setup record; its chunk's slot | mode << 8 | VGX_RT_SAMPLED / VGX_RT_GRADIENT / VGX_RT_PATTERN; the command's rectangle in

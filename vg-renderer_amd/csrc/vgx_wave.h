@@ -87,6 +87,63 @@ __device__ __forceinline__ int seg_rel(int excl, int head, int carry)
 	return head < 0 ? carry + excl : excl - base;
 }
 
+// ---- minimum / maximum over the wave and over a workgroup of 256 ------------------------------------------------------------
+// Six butterfly steps leave the result on EVERY lane, in a vector register; a caller that wants a scalar (a wave-uniform branch)
+// applies wave_uniform_* itself, and a store from lane 0 does not pay for it. fminf / fmaxf pass over a NaN
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op)
+{
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) { v = op(v, __shfl_xor(v, d)); }
+	return v;
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return b < a ? b : a; }); }
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return b > a ? b : a; }); }
+__device__ __forceinline__ float wave_min_f32(float v) { return wave_reduce(v, [](float a, float b) { return fminf(a, b); }); }
+__device__ __forceinline__ float wave_max_f32(float v) { return wave_reduce(v, [](float a, float b) { return fmaxf(a, b); }); }
+__device__ __forceinline__ uint32_t wave_uniform_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ float wave_uniform_f32(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+// the maximum over the workgroup of 256, on every thread; s_w holds 4 words and is free again on return
+__device__ __forceinline__ uint32_t block_max_u32(uint32_t v, uint32_t* s_w)
+{
+	v = wave_max_u32(v);
+	if ((threadIdx.x & 63) == 0) { s_w[threadIdx.x >> 6] = v; }
+	__syncthreads();
+	const uint32_t a = s_w[0], b = s_w[1], c = s_w[2], d = s_w[3];
+	__syncthreads();
+	const uint32_t ab = a > b ? a : b, cd = c > d ? c : d;
+	return ab > cd ? ab : cd;
+}
+
+// The stamp scan of the pick resolvers: "the last covering clip item at or before me" over a workgroup of 256 whose threads ascend,
+// carried across successive blocks. key = my item's number + 1 when it stamps, else 0. A wave inclusive max-scan, the four wave totals
+// through s_w (4 words, free again on return), *carry = the largest key of every block so far. Two barriers: every thread calls it
+__device__ __forceinline__ uint32_t stamper_before_me(uint32_t key, uint32_t* carry, uint32_t* s_w)
+{
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)key, d); if (lane >= d && o > key) { key = o; } }
+	if (lane == 63) { s_w[wave] = key; }
+	__syncthreads();
+	uint32_t before = *carry, total = *carry;
+	for (int w = 0; w < 4; ++w) { const uint32_t t = s_w[w]; if (w < wave && t > before) { before = t; } if (t > total) { total = t; } }
+	__syncthreads();
+	*carry = total;
+	return key > before ? key : before;
+}
+
+// first index of [0, n) whose entry is >= x, else n
+__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t n, uint32_t x)
+{
+	uint32_t lo = 0, hi = n;
+	while (lo < hi) {
+		const uint32_t mid = lo + ((hi - lo) >> 1);
+		if (a[mid] < x) { lo = mid + 1u; } else { hi = mid; }
+	}
+	return lo;
+}
+
 // lower_bound over a device array of uint64 (first index i in [lo,hi) with a[i] >= key, else hi)
 __device__ __forceinline__ uint64_t lower_bound_u64(const uint64_t* a, uint64_t lo, uint64_t hi, uint64_t key)
 {
@@ -151,6 +208,23 @@ __device__ __forceinline__ int window_owner(uint64_t w, uint64_t key, uint64_t* 
 	}
 	*pv = vlo;
 	return lo;
+}
+
+// The owners of a wave's 64 consecutive items T0 + lane of a STRICTLY ascending prefix P[0 .. n] (P[0] = 0 <= T0 < P[n] = total: the
+// 64 items lie in the 64 entries from T0's owner on): one binary search for the wave, one window load, window_owner per lane. Item
+// T0 + lane is number T0 + lane - first of entry c0 + k; a lane past the total is not live and searches for T0
+struct WaveOwners { uint64_t c0, first; int k; bool live; };
+__device__ __forceinline__ WaveOwners wave_owners(const uint64_t* P, uint64_t n, uint64_t total, uint64_t T0, int lane)
+{
+	WaveOwners o;
+	o.c0 = find_owner_u64(P, 0, n, T0);
+	const uint64_t ck = o.c0 + (uint64_t)lane;
+	const uint64_t w = ck <= n ? P[ck] : ~0ull;
+	const uint64_t T = T0 + (uint64_t)lane;
+	o.live = T < total;
+	o.first = 0;
+	o.k = window_owner(w, o.live ? T : T0, &o.first);
+	return o;
 }
 
 // Same search on a window that was reduced to 32-bit offsets relative to the chunk start: rel[k] = clamp(W[k] - chunk,
