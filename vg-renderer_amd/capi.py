@@ -136,6 +136,19 @@ assert pick_query_dtype.itemsize == 16 and pick_hit_dtype.itemsize == 16
 PICK_MAX_QUERIES = 256
 PICK_SKIP_TRANSPARENT = 1
 PICK_NONE = 0xFFFFFFFF  # every word of a hit record that hit nothing; vgx_pick_query.mesh_end: all meshes
+pick_rect_query_dtype = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("mesh_begin", "<u4"), ("mesh_end", "<u4"), ("flags", "<u4"),
+                                  ("reserved", "<u4")])  # struct vgx_pick_rect_query
+assert pick_rect_query_dtype.itemsize == 32
+PICK_RECT_MAX_QUERIES = 64
+PICK_RECT_WINDOW = 2
+PICK_RECT_BY_DRAW = 4
+
+
+class PickRectOut(C.Structure):  # vgx_pick_rect_out: device pointers, each may be None (list only with list_cap == 0)
+    _fields_ = [("top", C.c_void_p), ("list", C.c_void_p), ("count", C.c_void_p), ("list_cap", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(PickRectOut) == 32
 
 
 class RasterTarget(C.Structure):  # vgx_raster_target: `pixels` is a device pointer
@@ -307,6 +320,7 @@ VGX_SYMBOLS = {
     "vgx_cache_cull": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
                                  C.POINTER(CullOut), C.c_void_p, C.c_void_p]),
     "vgx_pick": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vgx_pick_rect": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PickRectOut), C.c_void_p]),
     "vgx_pick_frame": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterDraws), C.c_void_p, C.c_uint32, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "vgx_raster": (C.c_int, [C.c_void_p, C.POINTER(CacheDesc), C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RasterTarget), C.c_void_p, C.c_void_p]),

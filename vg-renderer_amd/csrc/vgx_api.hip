@@ -22,6 +22,7 @@
 #include "vgx_damage.h"
 #include "vgx_pick.h"
 #include "vgx_pick_cmds.h"
+#include "vgx_pick_rect.h"
 #include "vgx_cmd_bounds.h"
 #include "vgx_concave_lane.h"
 #include "vgx_scratch.h"
@@ -166,6 +167,12 @@ struct vgx_ctx
 	// place among the triangle / contour candidates; the triangle prefix; the totals; boxes when the caller gives none; slice sums (views: as
 	// `partial`). Its own: a counted state survives the call, and vgx_pick's tables are not touched
 	Buf<VgxPickfMesh> pickfState; Buf<uint32_t> pickfCand, pickfTriCand, pickfConCand, pickfCover; Buf<uint64_t> pickfPrefix, pickfTotals; Buf<float> pickfBounds; DevBuf pickfPartial;
+	// vgx_pick_rect (vgx_pick_rect.hip): per mesh three words of one bit per query, its triangle count, its place among the candidates with
+	// the triangle prefix, its run, per run its first mesh and two words, per block of 64 meshes two counts per query (VgxPickrArgs): 72 bytes
+	// per mesh; boxes when the caller gives none; slice sums (views: as `partial`). Its own: a counted state survives the call, and the tables
+	// of vgx_pick and vgx_pick_frame are not touched
+	Buf<uint64_t> pickrCand, pickrInside, pickrTouch, pickrPrefix, pickrRunTouch, pickrRunInside, pickrTotals; Buf<uint32_t> pickrTris, pickrCandMesh, pickrRunOf, pickrRunFirst, pickrBlockCount, pickrBlockTop;
+	Buf<float> pickrBounds; DevBuf pickrPartial;
 	DevBuf updPrefix, updPartial;        // vgx_cache_layout / vgx_cache_update (vgx_update.hip); views: updPrefix = uint32_t flag word in 16 bytes, then 2 x uint64_t[ndirty + 1] prefix sums of the listed entries; updPartial = slice sums, as `partial`. Their own: a counted state survives the calls
 	// vgx_raster (vgx_raster.hip): per mesh of the range its bin entries and its first entry; the (tile, mesh) entries in mesh order and
 	// in tile order; the sort's temporary storage; status and entry count of the last call with their pinned mirror (as `dash`: a call
@@ -2645,6 +2652,50 @@ int vgx_pick_frame(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_
 	a.mesh_state = ctx->pickfState.ptr(); a.cand_mesh = ctx->pickfCand.ptr(); a.tri_cand = ctx->pickfTriCand.ptr(); a.tri_prefix = ctx->pickfPrefix.ptr();
 	a.con_cand = ctx->pickfConCand.ptr(); a.cover = ctx->pickfCover.ptr(); a.totals = ctx->pickfTotals.ptr();
 	vgx_launch_pick_frame(a, ctx->pickfPartial.p, ctx->opt.pickGrid, s);
+	return launchStatus(ctx);
+}
+
+// ... of rectangles: pick tolerance and marquee selection (vgx_pick_rect.hip). Scratch of its own, sized by num_meshes alone: count ->
+// vgx_pick_rect -> emit still works, and so does vgx_pick -> vgx_pick_rect -> vgx_pick.
+int vgx_pick_rect(vgx_ctx* ctx, const vgx_cache_desc* frame, const float* mesh_bounds, const vgx_pick_rect_query* queries, uint32_t nqueries,
+                  const vgx_pick_rect_out* out, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx) { return VGX_E_INVALID_ARG; }
+	int st = vgx_pickr_check_args(frame, mesh_bounds, queries, nqueries, out);
+	if (st != VGX_OK) { return st; }
+	if (!nqueries) { return VGX_OK; } // nothing to write
+	hipStream_t s = (hipStream_t)stream;
+	const uint64_t nm = frame->num_meshes, words = (nm + 63) / 64 * 64; // blocks of 64 meshes x 64 queries
+	if ((st = ensure(ctx, ctx->pickrCand, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrInside, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrTouch, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrTris, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrCandMesh, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrPrefix, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrRunOf, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrRunFirst, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrRunTouch, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrRunInside, nm + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrBlockCount, words + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrBlockTop, words + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrTotals, 3)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->pickrPartial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if (!mesh_bounds && nm) {
+		if ((st = ensure(ctx, ctx->pickrBounds, nm * 4)) != VGX_OK) { return st; }
+		vgx_launch_mesh_bounds(frame->pos, frame->meshes, nm, ctx->pickrBounds.ptr(), s);
+		mesh_bounds = ctx->pickrBounds.ptr();
+	}
+	VgxPickrArgs a;
+	memset(&a, 0, sizeof(a));
+	a.pos = frame->pos; a.color = frame->color; a.idx = frame->idx; a.meshes = frame->meshes; a.num_meshes = nm;
+	a.mesh_bounds = mesh_bounds; a.queries = queries; a.nqueries = nqueries;
+	a.top = out->top; a.list = out->list; a.count = out->count; a.list_cap = out->list_cap;
+	a.cand = ctx->pickrCand.ptr(); a.inside = ctx->pickrInside.ptr(); a.touch = ctx->pickrTouch.ptr(); a.cand_tris = ctx->pickrTris.ptr();
+	a.cand_mesh = ctx->pickrCandMesh.ptr(); a.cand_prefix = ctx->pickrPrefix.ptr(); a.run_of = ctx->pickrRunOf.ptr(); a.run_first = ctx->pickrRunFirst.ptr();
+	a.run_touch = ctx->pickrRunTouch.ptr(); a.run_inside = ctx->pickrRunInside.ptr(); a.block_count = ctx->pickrBlockCount.ptr();
+	a.block_top = ctx->pickrBlockTop.ptr(); a.totals = ctx->pickrTotals.ptr();
+	vgx_launch_pick_rect(a, ctx->pickrPartial.p, ctx->opt.pickGrid, s);
 	return launchStatus(ctx);
 }
 

@@ -598,6 +598,80 @@ int vgxt_pick_frame(const vgx_cache_desc* frame, const float* mesh_bounds, uint6
 
 }
 
+#include "vgx_pick_rect.h"
+
+extern "C" {
+
+// The predicate of vgx_pick_rect for one triangle (tri = ax, ay, bx, by, cx, cy) and one rectangle (rect = x0, y0, x1, y1): steps 1 to 4,
+// step 4 in the header's four-corner form or in the one-corner form the kernels run
+int vgxt_pick_rect_touch(const float* tri, const float* rect, int four_corners)
+{
+	vgx_pick_rect_query Q;
+	Q.x0 = rect[0]; Q.y0 = rect[1]; Q.x1 = rect[2]; Q.y1 = rect[3]; Q.mesh_begin = 0u; Q.mesh_end = VGX_PICK_NONE; Q.flags = 0u; Q.reserved = 0u;
+	VgxPickrTri T;
+	vgx_pickr_setup(v2(tri[0], tri[1]), v2(tri[2], tri[3]), v2(tri[4], tri[5]), &T);
+	return vgx_pickr_query_valid(Q) && vgx_pickr_touch(T, Q, four_corners != 0) ? 1 : 0;
+}
+
+// vgx_pick_rect on the host: the functions of vgx_pick_rect.h in a plain sequential loop over queries, the entries of the range in ascending
+// order, their meshes and their triangles, with the call's contract (mesh_bounds may be NULL: the boxes are computed first). HOST pointers.
+// Returns the status the device call returns for these arguments.
+int vgxt_pick_rect(const vgx_cache_desc* frame, const float* mesh_bounds, const vgx_pick_rect_query* queries, uint32_t nqueries, const vgx_pick_rect_out* out)
+{
+	const int rc = vgx_pickr_check_args(frame, mesh_bounds, queries, nqueries, out);
+	if (rc != VGX_OK) { return rc; }
+	const uint64_t nm = frame->num_meshes;
+	float* own = nullptr;
+	if (!mesh_bounds && nm && nqueries) {
+		own = (float*)malloc(nm * 4 * sizeof(float));
+		if (!own) { return VGX_E_INTERNAL; }
+		vgxt_mesh_bounds(frame->pos, frame->meshes, nm, own);
+		mesh_bounds = own;
+	}
+	for (uint32_t q = 0; q < nqueries; ++q) {
+		const vgx_pick_rect_query Q = queries[q];
+		const bool window = (Q.flags & VGX_PICK_RECT_WINDOW) != 0u, byDraw = (Q.flags & VGX_PICK_RECT_BY_DRAW) != 0u;
+		const uint64_t end = (uint64_t)Q.mesh_end < nm ? (uint64_t)Q.mesh_end : nm;
+		uint32_t count = 0u, bestMesh = 0u, bestTri = 0u; // + 1, 0: none
+		uint64_t m = vgx_pickr_query_valid(Q) ? (uint64_t)Q.mesh_begin : end;
+		while (m < end) {
+			uint64_t runEnd = m + 1;
+			while (byDraw && runEnd < end && frame->meshes[runEnd].draw == frame->meshes[m].draw) { ++runEnd; }
+			uint64_t touch = 0ull, inside = 1ull; // bit 0: this query
+			uint32_t lastMesh = 0u, lastTri = 0u;
+			for (uint64_t j = m; j < runEnd; ++j) {
+				const float* bx = mesh_bounds + 4 * j;
+				if (!vgx_pickr_box_inside(Q, bx[0], bx[1], bx[2], bx[3])) { inside = 0ull; }
+				const vgx_mesh me = frame->meshes[j];
+				if (!vgx_pickr_box_overlap(Q, bx[0], bx[1], bx[2], bx[3])) { continue; }
+				const uint16_t* ip = frame->idx + me.first_index;
+				const float* pp = frame->pos + 2 * me.first_vertex;
+				const uint32_t* cp = frame->color + me.first_vertex;
+				for (uint32_t t = 0; t < vgx_pick_mesh_triangles(me); ++t) {
+					const uint32_t i0 = ip[3 * t], i1 = ip[3 * t + 1], i2 = ip[3 * t + 2];
+					if (!vgx_pick_tri_valid(i0, i1, i2, me.num_vertices)) { continue; }
+					if ((Q.flags & VGX_PICK_SKIP_TRANSPARENT) && vgx_pick_tri_transparent(cp[i0], cp[i1], cp[i2])) { continue; }
+					VgxPickrTri T;
+					vgx_pickr_setup(v2(pp[2 * i0], pp[2 * i0 + 1]), v2(pp[2 * i1], pp[2 * i1 + 1]), v2(pp[2 * i2], pp[2 * i2 + 1]), &T);
+					if (vgx_pickr_touch(T, Q)) { touch = 1ull; lastMesh = (uint32_t)j + 1u; lastTri = t + 1u; }
+				}
+			}
+			if (vgx_pickr_selected(touch, inside, window ? 1ull : 0ull) & 1ull) {
+				if (count < out->list_cap) { out->list[(uint64_t)q * out->list_cap + count] = vgx_pickr_entry_value(Q, (uint32_t)m); }
+				++count;
+				bestMesh = lastMesh; bestTri = lastTri;
+			}
+			m = runEnd;
+		}
+		if (out->count) { out->count[q] = count; }
+		if (out->top) { out->top[q] = vgx_pickr_record(bestMesh, bestTri, frame->meshes); }
+	}
+	free(own);
+	return VGX_OK;
+}
+
+}
+
 #include "vgx_raster.h"
 #include "vgx_damage.h"
 #include "vgx_concave_lane.h"

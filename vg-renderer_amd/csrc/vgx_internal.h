@@ -438,6 +438,33 @@ struct VgxPickArgs
 };
 void vgx_launch_pick(const VgxPickArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, uint32_t grid, hipStream_t s);
 
+// region queries (vgx_pick_rect.hip): vgx_pick_rect. One 64-bit word per mesh and plane, one bit per query; a block is 64 consecutive
+// meshes (one wave of the selection and list kernels). Every table is sized by num_meshes
+struct VgxPickrArgs
+{
+	const float* pos; const uint32_t* color; const uint16_t* idx; const vgx_mesh* meshes; // the frame
+	uint64_t num_meshes;              // < 2^32 - 1
+	const float* mesh_bounds;         // [num_meshes][4], 16-byte aligned: the caller's, or the context's own
+	const vgx_pick_rect_query* queries;
+	uint32_t nqueries;                // 1 .. VGX_PICK_RECT_MAX_QUERIES
+	uint32_t list_cap;
+	vgx_pick_hit* top; uint32_t* list; uint32_t* count; // the caller's, each may be null
+	uint64_t* cand;                   // [num_meshes] (context scratch, as everything below) the queries the mesh is a candidate of; from k_pickr_select on: the queries that list an entry at the mesh
+	uint64_t* inside;                 // [num_meshes] inside(m), 1 for a query whose range the mesh is not in; written only when a query has VGX_PICK_RECT_WINDOW
+	uint64_t* touch;                  // [num_meshes] touch(m)
+	uint32_t* cand_tris;              // [num_meshes] triangle count of a candidate, 0 for any other mesh; bit 31: the mesh begins a run
+	uint32_t* cand_mesh;              // [num_meshes] the candidates, dense and ascending
+	uint64_t* cand_prefix;            // [num_meshes + 1] exclusive prefix of the candidates' triangle counts, the total behind it
+	uint32_t* run_of;                 // [num_meshes] the run of every mesh, runs numbered densely
+	uint32_t* run_first;              // [num_meshes] the first mesh of every run
+	uint64_t* run_touch;              // [num_meshes] per run the OR of touch ...
+	uint64_t* run_inside;             // [num_meshes] ... and the AND of inside over its meshes; both only when a query has VGX_PICK_RECT_BY_DRAW
+	uint32_t* block_count;            // [blocks][64] entries of (block, query); from k_pickr_finish on: the entries of the query in the blocks before
+	uint32_t* block_top;              // [blocks][64] the block's largest mesh + 1 with a bit in its `touch` word for the query, 0: none
+	uint64_t* totals;                 // candidates, candidate triangles, runs
+};
+void vgx_launch_pick_rect(const VgxPickrArgs& a, void* partial /* [VGX_SCAN_BLOCKS] Sum3 */, uint32_t grid, hipStream_t s);
+
 // ... under scissors, clip regions and contour fills (vgx_pick_frame). A candidate is a mesh of the range that some query's point can
 // lie in (box and draw scissor); candidates are numbered densely in ascending mesh order, and every table below is sized by the range
 struct VgxPickfMesh;

@@ -700,6 +700,32 @@ def pick(ctx, frame, queries_dev, nqueries, bounds_dev=None, hits_dev=None):
     return hits_dev
 
 
+class PickRectResult:
+    """What pick_rect() wrote, all device tensors: top (uint8, nqueries 16-byte vgx_pick_hit records, or None), list (int32
+    [nqueries, list_cap], or None with list_cap == 0) and count (int32 [nqueries])."""
+
+    def __init__(self, top, list_, count):
+        self.top, self.list, self.count = top, list_, count
+
+
+def pick_rect(ctx, frame, queries_dev, nqueries, list_cap=64, bounds_dev=None, want_top=True):
+    """Rectangles against a frame: pick tolerance and marquee selection (vgx_pick_rect in include/vgx.h). frame: a capi.CacheDesc of device
+    pointers, or anything with .desc(); queries_dev: uint8 device tensor of at most capi.PICK_RECT_MAX_QUERIES 32-byte vgx_pick_rect_query
+    records; bounds_dev: what mesh_bounds gave for the frame, or None (the call computes the boxes itself). Returns a PickRectResult of
+    device tensors: per query the number of selected entries, its list_cap lowest entries (only the first min(count, list_cap) of a row
+    are written) and, with want_top, the topmost touching triangle of a selected entry. Asynchronous."""
+    import torch
+    d = _desc(frame)
+    dev = queries_dev.device
+    n, cap = max(int(nqueries), 1), int(list_cap)
+    top = torch.empty(n * 16, dtype=torch.uint8, device=dev) if want_top else None
+    lst = torch.empty((n, cap), dtype=torch.int32, device=dev) if cap else None
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    out = capi.PickRectOut(_ptr(top), _ptr(lst), count.data_ptr(), cap, 0)
+    _check(lib().vgx_pick_rect(ctx.handle, C.byref(d), _ptr(bounds_dev), _ptr(queries_dev, nqueries), int(nqueries), C.byref(out), _stream_ptr()), "vgx_pick_rect")
+    return PickRectResult(top, lst, count)
+
+
 def pick_frame(ctx, frame, draws_dev, draw_state_dev, num_draws, queries_dev, nqueries, bounds_dev=None, mesh_begin=0, mesh_end=None, hits_dev=None,
                dev_status=None):
     """pick() for the image raster_concave() draws: a mesh is hit where a sample of it would take effect under its draw's scissor and the
