@@ -88,7 +88,8 @@ enum { VGX_JOIN_MITER = 0, VGX_JOIN_ROUND = 1, VGX_JOIN_BEVEL = 2 };
  * WITHOUT VGX_FILL_ENABLE produces no mesh in vgx_tessellate. Two routes build it and vgx_merge puts it at the draw's place in the
  * frame: triangles, as the reference makes them -- vgx_flatten_* (contours) + libtess2 on the CPU side of the caller + vgx_concave_move
  * / vgx_concave_emit --, or, for a frame that goes to vgx_raster_concave, contour meshes without libtess2 and without leaving the
- * device -- vgx_flatten + vgx_concave_contours. vgx_cmdlist_decode emits concave FillPath* commands as such draws (VGX_FILL_AA / VGX_FILL_EVEN_ODD say
+ * device -- vgx_flatten + vgx_concave_contours; vgx_concave_triangulate is that call with triangles, made on the device, for the draws
+ * that are one simple ring. vgx_cmdlist_decode emits concave FillPath* commands as such draws (VGX_FILL_AA / VGX_FILL_EVEN_ODD say
  * which strokerConcaveFillEnd[AA] call and FillRule the reference would use). */
 #define VGX_FILL_CONCAVE 0x10u
 #define VGX_FILL_EVEN_ODD 0x20u
@@ -210,7 +211,7 @@ typedef struct vgx_flat_out {
  * Alignment: that of the element types and no more -- pos 8 bytes, color 4, idx 2, meshes 8 (its records hold uint64_t). The streams
  * may start anywhere such a pointer can: in the middle of a 16-byte word, at the last element of a cache line. Every entry that
  * writes one of these -- vgx_tessellate, vgx_tessellate_emit, vgx_tessellate_immediate, vgx_tessellate_dashed, vgx_stroke,
- * vgx_stroke_emit, vgx_cache_submit, vgx_merge / vgx_merge_uv / vgx_merge_uv_stream, vgx_concave_emit, vgx_text_quads -- returns
+ * vgx_stroke_emit, vgx_cache_submit, vgx_merge / vgx_merge_uv / vgx_merge_uv_stream, vgx_concave_emit, vgx_concave_contours, vgx_concave_triangulate, vgx_text_quads -- returns
  * VGX_E_INVALID_ARG on the host, with nothing enqueued, for a pointer below that alignment.
  * Range: nothing outside [0, cap_vertices) of pos and color, [0, cap_indices) of idx and [0, cap_meshes) of meshes is read or
  * written, whatever the status the call ends with. */
@@ -1527,6 +1528,57 @@ int vgx_concave_emit(vgx_ctx* ctx, const float* contour_verts, uint64_t num_cont
  *   state, like vgx_concave_emit. */
 int vgx_concave_contours(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
                          const vgx_mesh_out* out, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream);
+
+/* ---- concave fills to TRIANGLES on the device (beyond the reference): vgx_flatten -> vgx_concave_triangulate -> vgx_merge ----------------
+ * A contour mesh is understood by vgx_raster_concave and vgx_pick_frame alone. vgx_concave_triangulate is vgx_concave_contours with one
+ * difference: a concave draw that is ONE simple closed ring (an arrow, a star, an L, a notch) comes out as triangles, by ear clipping on
+ * the device, under the rule below. Every other mesh-making draw comes out exactly as vgx_concave_contours writes it, at its place in the
+ * same dense output, so the frame is always drawable; draw_route says which draws are triangles. Holes, multi-contour fills and
+ * self-intersecting rings are out of scope: they stay with the contour route or with libtess2.
+ * Inputs, alignment, host return values, "which draws make meshes", the dev_sizes / dev_status protocol (VGX_E_NOSPACE with the exact
+ *   need and nothing written past a capacity; with any status but VGX_OK no vertex and no index is written; VGX_E_INVALID_ARG for
+ *   sub-paths that do not lie back to back), ascending dense output (sequence `b` of vgx_merge as it stands), asynchronous and
+ *   stream-ordered with no host round trip, ends a counted state: vgx_concave_contours' word for word.
+ * draw_route (DEVICE [ndraws], 4-byte aligned, may be NULL) receives per draw: 0 = the draw makes no mesh, VGX_TRI_ROUTE_TRIANGLES = it
+ *   was triangulated, or the reason it was refused (VGX_TRI_REFUSED_*): then the draw holds vgx_concave_contours' meshes. The routes
+ *   depend on the input alone and are written whatever status the call ends with (VGX_E_INVALID_ARG aside).
+ * The ring R. Without VGX_FILL_AA: the draw's polyline vertices. With VGX_FILL_AA: the moved ring, the vertices vgx_concave_move gives
+ *   (the inner fringe vertices), which is what the reference triangulates in its step (3). An inset can cross itself where the input does
+ *   not: such a draw is refused and gets the AA pair of the contour route. V = its vertex count. Refusals, tested in this order:
+ *   MULTI       the draw has more than one sub-path;
+ *   TOO_LONG    V > VGX_TRIANGULATE_MAX_VERTICES (the kernel holds R in LDS: 8 bytes of position and two 16-bit links per vertex);
+ *   NONFINITE   a coordinate of R is not finite;
+ *   DEGENERATE  the orientation s is 0;
+ *   NOT_SIMPLE  two edges of R meet;
+ *   STALLED     the clipping loop found no ear in a whole turn.
+ * The rule. c(a, b, p) = the canonical edge value E of a -> b at p exactly as the winding rule of vgx_raster_concave defines it:
+ *   coordinates widened to binary64, no FMA, lo and hi ordered by (x, then y), 0 when a == b bit for bit.
+ *   Orientation. k = the vertex of R that is smallest by (x, y, index); s = sign of c(prev k, k, next k).
+ *   Simplicity. Every pair of edges (u1 -> v1, u2 -> v2) of R that share no vertex index (V = 3 has none) MEETS when c(u1,v1,u2) and
+ *     c(u1,v1,v2) have strictly opposite signs and c(u2,v2,u1) and c(u2,v2,v1) have strictly opposite signs, or when one of the four
+ *     values is 0 and that endpoint lies in the closed coordinate box of the other edge. One pair that meets refuses the ring. This is
+ *     conservative -- a ring that touches itself is refused -- while collinear edges that do not overlap pass (a comb is triangulated).
+ *   Clipping. R is a doubly linked ring; the cursor b starts at vertex 0, misses = 0. While more than three vertices remain:
+ *     a = prev b, c = next b, t = s * c(a, b, c). b is an EAR when t == 0 (a flat ear, no containment test), or when t > 0 and no vertex
+ *     p still linked in the ring, other than a, b, c, has s * c(a,b,p) >= 0 && s * c(b,c,p) >= 0 && s * c(c,a,p) >= 0. On an ear: emit
+ *     the triangle (a, b, c), unlink b, b = next c, misses = 0. Otherwise b = c and misses grows by one; when it exceeds the number of
+ *     vertices still linked the draw is STALLED. The last three vertices are emitted as (prev b, b, next b).
+ *   So a triangulated ring always has V vertices and 3 (V - 2) indices, and its triangles' directed boundary telescopes to the ring:
+ *   by the winding rule's own words (opposite edges cancel exactly; a triangle's three edges give its coverage) vgx_raster_concave
+ *   draws every sample of the triangles exactly as often as it draws it for the contour mesh of the same ring.
+ * What a triangulated draw writes. ONE mesh of kind VGX_MESH_CONCAVE_FILL_AA (what vgx_concave_emit gives, also for a fill of zero
+ *   boundary contours), draw = d. Without AA: the V polyline vertices in order, every colour fill_color, the 3 (V - 2) mesh-local
+ *   indices in emission order. With AA, in vgx_concave_emit's layout: 2V fringe vertices and 6V indices, bit for bit vgx_concave_emit's
+ *   fringe (strokerConcaveFillEndAA's), then the interior: the V moved vertices, colour fill_color, and the 3 (V - 2) indices rebased
+ *   by 2V. 3V > 65536 sets VGX_E_MESH_TOO_LARGE; a refused draw sets it as vgx_concave_contours does.
+ * Scratch (the context's buffer list, vgx_scratch_bytes counts it): 36 bytes per draw and 6 bytes per vertex of
+ *   min(out->cap_vertices, ndraws * VGX_TRIANGULATE_MAX_VERTICES). */
+#define VGX_TRIANGULATE_MAX_VERTICES 4096u
+enum { VGX_TRI_ROUTE_TRIANGLES = 1, VGX_TRI_REFUSED_MULTI = 2, VGX_TRI_REFUSED_TOO_LONG = 3, VGX_TRI_REFUSED_NONFINITE = 4,
+       VGX_TRI_REFUSED_DEGENERATE = 5, VGX_TRI_REFUSED_NOT_SIMPLE = 6, VGX_TRI_REFUSED_STALLED = 7 };
+int vgx_concave_triangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                            const vgx_mesh_out* out, uint32_t* draw_route /* DEVICE [ndraws], may be NULL */, vgx_sizes* dev_sizes, uint32_t* dev_status,
+                            void* stream);
 
 /* ---- merging external meshes into a frame -----------------------------------------------------------------
  * The reference appends every mesh to the frame in submission order (createDrawCommand_VertexColor, src/vg.cpp:5207-5244).

@@ -39,6 +39,10 @@ MESH_FILL, MESH_FILL_AA, MESH_STROKE, MESH_STROKE_AA, MESH_STROKE_AA_THIN, MESH_
 MESH_TEXT = 7  # vgx_text_quads
 MESH_CONTOURS = 8  # vgx_concave_contours: directed edges in index pairs, filled by vgx_raster_concave alone
 CONTOUR_EVEN_ODD = 1  # vgx_mesh.subpath_kind of such a mesh: bit 0 is the fill rule
+# vgx_concave_triangulate: the largest ring it triangulates, and the words of draw_route (0 = the draw makes no mesh)
+TRIANGULATE_MAX_VERTICES = 4096
+TRI_ROUTE_TRIANGLES, TRI_REFUSED_MULTI, TRI_REFUSED_TOO_LONG, TRI_REFUSED_NONFINITE = 1, 2, 3, 4
+TRI_REFUSED_DEGENERATE, TRI_REFUSED_NOT_SIMPLE, TRI_REFUSED_STALLED = 5, 6, 7
 
 
 def stroke_flags(cap, join, aa=True, thin=False):
@@ -390,6 +394,8 @@ VGX_SYMBOLS = {
                                    C.POINTER(MeshOut), C.c_void_p, C.c_void_p, C.c_void_p]),
     "vgx_concave_contours": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+    "vgx_concave_triangulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     "vgx_cmdlist_decode": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CmdListState), C.POINTER(CmdListOut)]),
     "vgx_cmdlist_decode_text": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CmdListState), C.POINTER(CmdListOut), C.POINTER(CmdListText)]),
     "vgx_text_quads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_uint32,

@@ -159,6 +159,9 @@ struct vgx_ctx
 	Buf<VgxMeshPrep> mprep;
 	Buf<vgx_mesh> mtab;
 	Buf<uint64_t> contourPrefix;         // vgx_concave_contours: two exclusive prefixes over the draws (contour vertices, output vertices), [ndraws + 1] each
+	// vgx_concave_triangulate (vgx_triangulate.hip): per draw its route; its ring's vertex count and three exclusive prefixes, [ndraws + 1]
+	// each (VgxTriArgs); the clipping's ring-local triangles, three indices per vertex of the caller's vertex capacity
+	Buf<uint32_t> triRoute; Buf<uint64_t> triPrefix; Buf<uint16_t> triIdx;
 	Buf<VgxTotals> totals;
 	Buf<uint32_t> textTiles;             // vgx_text_quads: first run of every tile of quads (vgx_text.hip)
 	Buf<uint8_t> cullFlags; DevBuf cullPartial; // vgx_cache_cull (vgx_bounds.hip): kept flag per instance, the compaction scan's slice sums (views: as `partial`). Its own: a counted state survives the call
@@ -3411,6 +3414,46 @@ int vgx_concave_contours(vgx_ctx* ctx, const float* poly, const vgx_subpath* sub
 		vgx_launch_concave_contours(a, s);
 		mark(ctx, s, "concave_contours");
 	}
+	publish(ctx, dev_sizes, dev_status, s);
+	return launchStatus(ctx);
+}
+
+int vgx_concave_triangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                            const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+{
+	DeviceGuard guard(ctx);
+	if (!ctx || !out || !out->pos || !out->color || !out->idx || meshOutMisaligned(out) || (ndraws && (!poly || !subpaths || !draw_info || !draws))) {
+		return VGX_E_INVALID_ARG;
+	}
+	if (((uintptr_t)poly & 7u) || ((uintptr_t)subpaths & 7u) || ((uintptr_t)draw_info & 7u) || ((uintptr_t)draws & 3u) || ((uintptr_t)draw_route & 3u)) { return VGX_E_INVALID_ARG; }
+	if (ndraws >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	hipStream_t s = (hipStream_t)stream;
+	markBegin(ctx, s);
+	ctx->counted.stage = VGX_COUNTED_NONE;
+	// a ring's triangles wait in scratch for their place: three indices per ring vertex, and rings that cannot all fit into the caller's
+	// vertices (the call then ends with VGX_E_NOSPACE) keep none. A ring that is clipped has at most VGX_TRIANGULATE_MAX_VERTICES: a large
+	// output buffer behind a few draws costs no more scratch than those draws can fill
+	const uint64_t ringBound = ndraws * (uint64_t)VGX_TRIANGULATE_MAX_VERTICES;
+	const uint64_t capTri = 3 * (out->cap_vertices < ringBound ? out->cap_vertices : ringBound);
+	int st;
+	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->triRoute, ndraws + 1)) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->triPrefix, 4 * (ndraws + 1))) != VGX_OK) { return st; }
+	if ((st = ensure(ctx, ctx->triIdx, capTri + 1)) != VGX_OK) { return st; }
+	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
+	VgxTriArgs a;
+	memset(&a, 0, sizeof(a));
+	a.poly = poly; a.subpaths = subpaths; a.draw_info = draw_info; a.draws = draws; a.ndraws = ndraws;
+	a.route = ctx->triRoute.ptr(); a.draw_route = draw_route;
+	a.ring_vertices = ctx->triPrefix.ptr(); a.cand_prefix = a.ring_vertices + (ndraws + 1);
+	a.vertex_prefix = a.cand_prefix + (ndraws + 1); a.index_prefix = a.vertex_prefix + (ndraws + 1);
+	a.tri = ctx->triIdx.ptr(); a.cap_tri = capTri;
+	a.pos = out->pos; a.color = out->color; a.idx = out->idx; a.meshes = out->meshes;
+	a.cap_vertices = out->cap_vertices; a.cap_indices = out->cap_indices; a.cap_meshes = out->meshes ? out->cap_meshes : ~0ull;
+	a.totals = ctx->totals.ptr();
+	vgx_launch_concave_triangulate(a, ctx->partial.p, s);
+	mark(ctx, s, "concave_triangulate");
 	publish(ctx, dev_sizes, dev_status, s);
 	return launchStatus(ctx);
 }

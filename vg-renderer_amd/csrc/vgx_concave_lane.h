@@ -92,9 +92,12 @@ VGX_HD uint32_t contours_draw_meshes(const vgx_draw& d, uint32_t drawIndex, uint
 
 // Contour vertex c (< V) of a mesh-making draw: everything the draw's meshes hold for it. sp = the draw's nsub sub-paths. Without AA the
 // vertex and its outgoing edge; with AA the fringe pair and the six indices of its segment exactly as k_concave_fringe writes them, and
-// behind the fringe the moved vertex (k_concave_move's) and its outgoing edge. Stores are one element wide: vgx_mesh_out's alignment
-VGX_HD void contours_emit_vertex(const float* poly, const vgx_subpath* sp, uint32_t nsub, const vgx_draw& d, uint64_t c, uint64_t V,
-                                 uint64_t firstVertex, uint64_t firstIndex, float* pos, uint32_t* color, uint16_t* idx)
+// behind the fringe the moved vertex (k_concave_move's) and its outgoing edge. Stores are one element wide: vgx_mesh_out's alignment.
+// contours_emit_vertex_data writes all of it but the outgoing edge (vgx_concave_triangulate puts triangles there) and returns the
+// vertex's place: `before` contour vertices of the draw lie in front of its sub-path, whose vertex j of n it is
+struct ContourPlace { uint32_t before, j, n; };
+VGX_HD ContourPlace contours_emit_vertex_data(const float* poly, const vgx_subpath* sp, uint32_t nsub, const vgx_draw& d, uint64_t c, uint64_t V,
+                                              uint64_t firstVertex, uint64_t firstIndex, float* pos, uint32_t* color, uint16_t* idx)
 {
 	uint32_t lo = 0, hi = nsub; // the last sub-path that starts at or before c
 	while (hi - lo > 1u) {
@@ -116,12 +119,22 @@ VGX_HD void contours_emit_vertex(const float* poly, const vgx_subpath* sp, uint3
 		pi[0] = (uint16_t)id0; pi[1] = (uint16_t)id2; pi[2] = (uint16_t)id1;
 		pi[3] = (uint16_t)id2; pi[4] = (uint16_t)id3; pi[5] = (uint16_t)id1;
 		p = f.in;
-		firstVertex += 2 * V; firstIndex += 6 * V;
+		firstVertex += 2 * V;
 	}
 	pos[2 * (firstVertex + c)] = p.x; pos[2 * (firstVertex + c) + 1] = p.y;
 	color[firstVertex + c] = d.fill_color;
-	idx[firstIndex + 2 * c] = (uint16_t)(before + j);
-	idx[firstIndex + 2 * c + 1] = (uint16_t)(j + 1 < n ? before + j + 1 : before);
+	ContourPlace at;
+	at.before = before; at.j = j; at.n = n;
+	return at;
+}
+
+VGX_HD void contours_emit_vertex(const float* poly, const vgx_subpath* sp, uint32_t nsub, const vgx_draw& d, uint64_t c, uint64_t V,
+                                 uint64_t firstVertex, uint64_t firstIndex, float* pos, uint32_t* color, uint16_t* idx)
+{
+	const ContourPlace at = contours_emit_vertex_data(poly, sp, nsub, d, c, V, firstVertex, firstIndex, pos, color, idx);
+	if (d.fill_flags & VGX_FILL_AA) { firstIndex += 6 * V; }
+	idx[firstIndex + 2 * c] = (uint16_t)(at.before + at.j);
+	idx[firstIndex + 2 * c + 1] = (uint16_t)(at.j + 1 < at.n ? at.before + at.j + 1 : at.before);
 }
 
 #endif

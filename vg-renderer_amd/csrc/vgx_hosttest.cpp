@@ -675,6 +675,7 @@ int vgxt_pick_rect(const vgx_cache_desc* frame, const float* mesh_bounds, const 
 #include "vgx_raster.h"
 #include "vgx_damage.h"
 #include "vgx_concave_lane.h"
+#include "vgx_triangulate_lane.h"
 
 extern "C" {
 
@@ -716,6 +717,67 @@ int vgxt_concave_contours(const float* poly, const vgx_subpath* subpaths, const 
 		if (st == VGX_OK && (nv > out->cap_vertices || ni > out->cap_indices || (out->meshes && nm > out->cap_meshes))) { st = VGX_E_NOSPACE; }
 		if (sizes) { memset(sizes, 0, sizeof(*sizes)); sizes->num_meshes = nm; sizes->num_vertices = nv; sizes->num_indices = ni; }
 	}
+	if (status) { *status = st; }
+	return VGX_OK;
+}
+
+// vgx_concave_triangulate on the host: the rule of vgx_triangulate_lane.h ring after ring (tri_ring_route), then the draws one after the
+// other as vgxt_concave_contours walks them. HOST pointers; draw_route (may be NULL) as the device call's. Returns what the device call
+// returns on the host; *status and *sizes (may be NULL) receive what it leaves in dev_status and dev_sizes
+int vgxt_concave_triangulate(const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                             const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* sizes, uint32_t* status)
+{
+	if (!out || !out->pos || !out->color || !out->idx || (ndraws && (!poly || !subpaths || !draw_info || !draws))) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)out->pos & 7u) || ((uintptr_t)out->color & 3u) || ((uintptr_t)out->idx & 1u) || ((uintptr_t)out->meshes & 7u)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)poly & 7u) || ((uintptr_t)subpaths & 7u) || ((uintptr_t)draw_info & 7u) || ((uintptr_t)draws & 3u) || ((uintptr_t)draw_route & 3u)) { return VGX_E_INVALID_ARG; }
+	if (ndraws >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	const uint32_t cap = VGX_TRIANGULATE_MAX_VERTICES;
+	V2* ring = (V2*)malloc(cap * sizeof(V2));
+	uint16_t* links = (uint16_t*)malloc(2 * cap * sizeof(uint16_t));
+	uint16_t* tri = (uint16_t*)malloc(3 * cap * sizeof(uint16_t));
+	uint32_t* routes = (uint32_t*)malloc((ndraws + 1) * sizeof(uint32_t));
+	if (!ring || !links || !tri || !routes) { free(ring); free(links); free(tri); free(routes); return VGX_E_INTERNAL; }
+	uint32_t st = VGX_OK;
+	uint64_t nv = 0, ni = 0, nm = 0;
+	for (int pass = 0; pass < 2 && st == VGX_OK; ++pass) { // routes, sizes and records, then -- the capacities hold -- the streams
+		nv = ni = nm = 0;
+		for (uint64_t i = 0; i < ndraws; ++i) {
+			const vgx_draw& d = draws[i];
+			uint64_t V;
+			int made;
+			uint32_t route = tri_draw_class(d, draw_info[i], subpaths, &V, &made);
+			if (made < 0 && st == VGX_OK) { st = VGX_E_INVALID_ARG; }
+			const vgx_subpath* sp = subpaths + draw_info[i].first_subpath;
+			if (route == VGX_TRI_ROUTE_TRIANGLES && (pass == 0 || routes[i] == VGX_TRI_ROUTE_TRIANGLES)) { // a refusal is known from pass 0
+				for (uint32_t j = 0; j < (uint32_t)V; ++j) { ring[j] = tri_ring_vertex(poly + 2 * sp[0].first_vertex, (uint32_t)V, d, j); }
+				route = tri_ring_route(ring, (uint32_t)V, links, links + cap, tri);
+			} else if (pass == 1) {
+				route = routes[i];
+			}
+			if (pass == 0) {
+				routes[i] = route;
+				if (draw_route) { draw_route[i] = route; }
+			}
+			if (route == 0u) { continue; }
+			uint64_t dv, dn; uint32_t dm; bool big;
+			tri_draw_sizes(d, route, V, &dv, &dn, &dm, &big);
+			if (big && st == VGX_OK) { st = VGX_E_MESH_TOO_LARGE; }
+			if (pass == 0) {
+				vgx_mesh m[2];
+				const uint32_t n = tri_draw_meshes(d, (uint32_t)i, route, V, nv, ni, m);
+				for (uint32_t k = 0; k < n; ++k) { if (out->meshes && nm + k < out->cap_meshes) { out->meshes[nm + k] = m[k]; } }
+			} else if (route == VGX_TRI_ROUTE_TRIANGLES) {
+				for (uint64_t c = 0; c < V; ++c) { tri_emit_vertex(poly, sp, d, c, V, nv, ni, out->pos, out->color, out->idx); }
+				for (uint64_t k = 0; k < 3 * (V - 2); ++k) { tri_emit_index(d, tri, k, V, ni, out->idx); }
+			} else {
+				for (uint64_t c = 0; c < V; ++c) { contours_emit_vertex(poly, sp, draw_info[i].num_subpaths, d, c, V, nv, ni, out->pos, out->color, out->idx); }
+			}
+			nv += dv; ni += dn; nm += dm;
+		}
+		if (st == VGX_OK && (nv > out->cap_vertices || ni > out->cap_indices || (out->meshes && nm > out->cap_meshes))) { st = VGX_E_NOSPACE; }
+		if (sizes) { memset(sizes, 0, sizeof(*sizes)); sizes->num_meshes = nm; sizes->num_vertices = nv; sizes->num_indices = ni; }
+	}
+	free(ring); free(links); free(tri); free(routes);
 	if (status) { *status = st; }
 	return VGX_OK;
 }

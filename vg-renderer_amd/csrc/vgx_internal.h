@@ -231,6 +231,33 @@ struct VgxContoursArgs
 };
 void vgx_launch_concave_contours(const VgxContoursArgs& a, hipStream_t s);
 
+// vgx_concave_triangulate (vgx_triangulate.hip): the flatten output and the draws; per draw its route, its ring's vertex count and three
+// exclusive prefixes ([ndraws + 1] each: ring vertices of the draws whose geometry decides = their place in `tri`, output vertices, output
+// indices); the clipping's ring-local triangles; the streams with the caller's capacities
+struct VgxTriArgs
+{
+	const float* poly;
+	const vgx_subpath* subpaths;
+	const vgx_draw_info* draw_info;
+	const vgx_draw* draws;
+	uint64_t ndraws;
+	uint32_t* route;           // [ndraws] scratch
+	uint32_t* draw_route;      // the caller's, may be null
+	uint64_t* ring_vertices;   // [ndraws + 1]
+	uint64_t* cand_prefix;     // [ndraws + 1]
+	uint64_t* vertex_prefix;   // [ndraws + 1]
+	uint64_t* index_prefix;    // [ndraws + 1]
+	uint16_t* tri;             // [cap_tri]: draw d's triangles at 3 * cand_prefix[d]
+	uint64_t cap_tri;
+	float* pos;
+	uint32_t* color;
+	uint16_t* idx;
+	vgx_mesh* meshes;          // may be null
+	uint64_t cap_vertices, cap_indices, cap_meshes;
+	VgxTotals* totals;
+};
+void vgx_launch_concave_triangulate(const VgxTriArgs& a, void* partial /* Sum3[VGX_SCAN_BLOCKS] */, hipStream_t s);
+
 // text runs (vgx_text.hip)
 struct VgxTextArgs
 {

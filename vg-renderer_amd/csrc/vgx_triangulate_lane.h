@@ -1,0 +1,159 @@
+// vgx_triangulate_lane.h -- the arithmetic of vgx_concave_triangulate (include/vgx.h) for ONE ring: host + device. The predicates below
+// are what a lane of vgx_triangulate.hip evaluates; tri_ring_route runs the rule vertex after vertex on the host (libvgx_hosttest.so:
+// vgxt_concave_triangulate), so that the CPU suite pins every route and every index without a GPU. What a refused draw holds is
+// vgx_concave_lane.h's, called from both sides.
+//
+// Every decision is a sign of the canonical edge value of vgx_raster.h -- the rasteriser's own function, not a restatement of it --, so
+// "the triangles' windings sum to the ring's" is a statement about one number computed in one place.
+#ifndef VGX_TRIANGULATE_LANE_H
+#define VGX_TRIANGULATE_LANE_H
+
+#include "vgx_concave_lane.h"
+#include "vgx_raster.h"
+
+#define VGX_TRI_UNLINKED 0xFFFFu // prev[] of a clipped vertex; VGX_TRIANGULATE_MAX_VERTICES stays below it
+static_assert(VGX_TRIANGULATE_MAX_VERTICES < VGX_TRI_UNLINKED, "ring links are 16 bits wide");
+
+// c(a, b, p) of the header
+VGX_HD double tri_edge(V2 a, V2 b, V2 p)
+{
+	VgxRasterEdge e;
+	const uint32_t f = vgx_raster_edge(a, b, true, 0, &e);
+	return vgx_raster_edge_value(e, f, 0, (double)p.x, (double)p.y);
+}
+
+VGX_HD bool tri_finite(V2 p)
+{
+	union { float f; uint32_t u; } x, y;
+	x.f = p.x; y.f = p.y;
+	return (x.u & 0x7F800000u) != 0x7F800000u && (y.u & 0x7F800000u) != 0x7F800000u;
+}
+
+// vertex j of the ring of a single-sub-path draw: the polyline vertex, with AA the vertex vgx_concave_move gives
+VGX_HD V2 tri_ring_vertex(const float* v, uint32_t n, const vgx_draw& d, uint32_t j)
+{
+	return (d.fill_flags & VGX_FILL_AA) ? contour_vertex(v, n, j, d.fringe).in : ldc(v, j);
+}
+
+// What can be said of draw d without its geometry: 0 (no mesh), MULTI, TOO_LONG, or VGX_TRI_ROUTE_TRIANGLES = "the ring decides".
+// *made = contours_draw_counts' return, *V its vertex count
+VGX_HD uint32_t tri_draw_class(const vgx_draw& d, const vgx_draw_info& di, const vgx_subpath* subs, uint64_t* V, int* made)
+{
+	*made = contours_draw_counts(d, di, subs, V);
+	if (*made <= 0) { return 0u; }
+	if (di.num_subpaths > 1u) { return VGX_TRI_REFUSED_MULTI; }
+	if (*V > VGX_TRIANGULATE_MAX_VERTICES) { return VGX_TRI_REFUSED_TOO_LONG; }
+	return VGX_TRI_ROUTE_TRIANGLES;
+}
+
+// (x, y, index) order of the orientation's vertex k
+VGX_HD bool tri_before(V2 p, uint32_t i, V2 q, uint32_t j)
+{
+	return p.x < q.x || (p.x == q.x && (p.y < q.y || (p.y == q.y && i < j)));
+}
+
+VGX_HD int tri_sign(double e) { return e > 0.0 ? 1 : (e < 0.0 ? -1 : 0); }
+
+VGX_HD bool tri_in_box(V2 p, V2 a, V2 b)
+{
+	const float x0 = a.x < b.x ? a.x : b.x, x1 = a.x < b.x ? b.x : a.x, y0 = a.y < b.y ? a.y : b.y, y1 = a.y < b.y ? b.y : a.y;
+	return p.x >= x0 && p.x <= x1 && p.y >= y0 && p.y <= y1;
+}
+
+// do the edges u1 -> v1 and u2 -> v2 (no vertex index in common) meet?
+VGX_HD bool tri_edges_meet(V2 u1, V2 v1, V2 u2, V2 v2)
+{
+	const int a = tri_sign(tri_edge(u1, v1, u2)), b = tri_sign(tri_edge(u1, v1, v2));
+	const int c = tri_sign(tri_edge(u2, v2, u1)), d = tri_sign(tri_edge(u2, v2, v1));
+	if (a * b < 0 && c * d < 0) { return true; }
+	return (a == 0 && tri_in_box(u2, u1, v1)) || (b == 0 && tri_in_box(v2, u1, v1)) || (c == 0 && tri_in_box(u1, u2, v2)) || (d == 0 && tri_in_box(v1, u2, v2));
+}
+
+// does p keep (a, b, c) from being an ear of a ring of orientation s?
+VGX_HD bool tri_blocks(V2 a, V2 b, V2 c, V2 p, double s)
+{
+	return s * tri_edge(a, b, p) >= 0.0 && s * tri_edge(b, c, p) >= 0.0 && s * tri_edge(c, a, p) >= 0.0;
+}
+
+// mesh record(s) of a draw of V ring vertices under `route`, first mesh at (firstVertex, firstIndex); the sizes it adds. A refused
+// draw: contours_draw_meshes'
+VGX_HD void tri_draw_sizes(const vgx_draw& d, uint32_t route, uint64_t V, uint64_t* nv, uint64_t* ni, uint32_t* nm, bool* tooLarge)
+{
+	const bool aa = (d.fill_flags & VGX_FILL_AA) != 0u;
+	if (route == VGX_TRI_ROUTE_TRIANGLES) {
+		*nv = aa ? 3 * V : V; *ni = (aa ? 6 * V : 0u) + 3 * (V - 2); *nm = 1u;
+		*tooLarge = *nv > 65536u;
+	} else {
+		*nv = aa ? 3 * V : V; *ni = aa ? 8 * V : 2 * V; *nm = aa ? 2u : 1u;
+		*tooLarge = (aa ? 2 * V : V) > 65536u; // vgx_concave_contours' rule: per mesh
+	}
+}
+
+VGX_HD uint32_t tri_draw_meshes(const vgx_draw& d, uint32_t drawIndex, uint32_t route, uint64_t V, uint64_t firstVertex, uint64_t firstIndex, vgx_mesh* m)
+{
+	if (route != VGX_TRI_ROUTE_TRIANGLES) { return contours_draw_meshes(d, drawIndex, V, firstVertex, firstIndex, m); }
+	uint64_t nv, ni; uint32_t nm; bool big;
+	tri_draw_sizes(d, route, V, &nv, &ni, &nm, &big);
+	m[0].first_vertex = firstVertex; m[0].first_index = firstIndex; m[0].num_vertices = (uint32_t)nv; m[0].num_indices = (uint32_t)ni;
+	m[0].draw = drawIndex; m[0].subpath_kind = (uint32_t)VGX_MESH_CONCAVE_FILL_AA << 28;
+	return 1u;
+}
+
+// Vertex c of a triangulated draw: its vertex (with AA: its fringe pair, the segment's six indices and the moved vertex behind the fringe)
+VGX_HD void tri_emit_vertex(const float* poly, const vgx_subpath* sp, const vgx_draw& d, uint64_t c, uint64_t V, uint64_t firstVertex, uint64_t firstIndex,
+                            float* pos, uint32_t* color, uint16_t* idx)
+{
+	(void)contours_emit_vertex_data(poly, sp, 1u, d, c, V, firstVertex, firstIndex, pos, color, idx);
+}
+
+// Index k (< 3 (V - 2)) of a triangulated draw from the clipping's ring-local triangles
+VGX_HD void tri_emit_index(const vgx_draw& d, const uint16_t* tri, uint64_t k, uint64_t V, uint64_t firstIndex, uint16_t* idx)
+{
+	const bool aa = (d.fill_flags & VGX_FILL_AA) != 0u;
+	idx[firstIndex + (aa ? 6 * V : 0u) + k] = (uint16_t)(tri[k] + (aa ? 2 * V : 0u));
+}
+
+#ifndef __HIP_DEVICE_COMPILE__
+// The rule on the host, vertex after vertex: the route of the ring pos[0 .. V) (3 <= V <= VGX_TRIANGULATE_MAX_VERTICES) and, when it is
+// VGX_TRI_ROUTE_TRIANGLES, its 3 (V - 2) ring-local indices in tri. prev / next: V links each
+static inline uint32_t tri_ring_route(const V2* pos, uint32_t V, uint16_t* prev, uint16_t* next, uint16_t* tri)
+{
+	uint32_t k = 0;
+	for (uint32_t j = 0; j < V; ++j) {
+		if (!tri_finite(pos[j])) { return VGX_TRI_REFUSED_NONFINITE; }
+		if (tri_before(pos[j], j, pos[k], k)) { k = j; }
+		prev[j] = (uint16_t)(j ? j - 1 : V - 1); next[j] = (uint16_t)(j + 1 < V ? j + 1 : 0);
+	}
+	const int sg = tri_sign(tri_edge(pos[prev[k]], pos[k], pos[next[k]]));
+	if (sg == 0) { return VGX_TRI_REFUSED_DEGENERATE; }
+	const double s = (double)sg;
+	for (uint32_t i = 0; i + 2 < V; ++i) {
+		for (uint32_t j = i + 2; j < V; ++j) {
+			if (i == 0 && j == V - 1) { continue; } // the closing edge shares vertex 0
+			if (tri_edges_meet(pos[i], pos[i + 1], pos[j], pos[next[j]])) { return VGX_TRI_REFUSED_NOT_SIMPLE; }
+		}
+	}
+	uint32_t b = 0, size = V, misses = 0, nt = 0;
+	while (size > 3) {
+		const uint32_t a = prev[b], c = next[b];
+		const double t = s * tri_edge(pos[a], pos[b], pos[c]);
+		bool ear = t == 0.0;
+		if (t > 0.0) {
+			ear = true;
+			for (uint32_t p = next[c]; p != a && ear; p = next[p]) { ear = !tri_blocks(pos[a], pos[b], pos[c], pos[p], s); }
+		}
+		if (ear) {
+			tri[nt++] = (uint16_t)a; tri[nt++] = (uint16_t)b; tri[nt++] = (uint16_t)c;
+			next[a] = (uint16_t)c; prev[c] = (uint16_t)a; prev[b] = VGX_TRI_UNLINKED;
+			b = next[c]; --size; misses = 0;
+		} else {
+			b = c;
+			if (++misses > size) { return VGX_TRI_REFUSED_STALLED; }
+		}
+	}
+	tri[nt++] = prev[b]; tri[nt++] = (uint16_t)b; tri[nt++] = next[b];
+	return VGX_TRI_ROUTE_TRIANGLES;
+}
+#endif
+
+#endif

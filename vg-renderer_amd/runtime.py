@@ -1110,6 +1110,21 @@ def concave_contours(ctx, poly_dev, subpaths_dev, draw_info_dev, draws_dev, ndra
                                       bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_concave_contours")
 
 
+def concave_triangulate(ctx, poly_dev, subpaths_dev, draw_info_dev, draws_dev, ndraws, bufs, draw_route=None):
+    """concave_contours() whose draws of ONE simple ring come out as triangles -- ear clipping on the device, one mesh of kind
+    capi.MESH_CONCAVE_FILL_AA each -- while every other concave draw keeps its contour meshes (vgx_concave_triangulate in include/vgx.h).
+    Returns the int32 [ndraws] device tensor of routes (draw_route, or a new one): 0 = no mesh, capi.TRI_ROUTE_TRIANGLES, or a
+    capi.TRI_REFUSED_* reason. Asynchronous; totals / status land in bufs.dev_*."""
+    import torch
+    if draw_route is None:
+        draw_route = torch.zeros(max(int(ndraws), 1), dtype=torch.int32, device=bufs.dev_status.device)
+    out = bufs.out_struct()
+    _check(lib().vgx_concave_triangulate(ctx.handle, poly_dev.data_ptr() if ndraws else None, subpaths_dev.data_ptr() if ndraws else None,
+                                         draw_info_dev.data_ptr() if ndraws else None, draws_dev.data_ptr() if ndraws else None, int(ndraws), C.byref(out),
+                                         draw_route.data_ptr(), bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_concave_triangulate")
+    return draw_route
+
+
 # ---- text runs (vgx_text_quads): glyph layout and the atlas stay with the caller -------------------------------------
 def text_runs_dense(runs, first_vertex=0, first_index=0):
     """The dense layout for a vgx_text_run array (capi.text_run_dtype, first_quad / num_quads set): every run's vertices and
