@@ -1580,6 +1580,53 @@ int vgx_concave_triangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath* 
                             const vgx_mesh_out* out, uint32_t* draw_route /* DEVICE [ndraws], may be NULL */, vgx_sizes* dev_sizes, uint32_t* dev_status,
                             void* stream);
 
+/* ---- fills with HOLES to triangles on the device: vgx_flatten -> vgx_concave_triangulate_rings -> vgx_merge -----------------------------
+ * vgx_concave_triangulate_rings is vgx_concave_triangulate for draws of several sub-paths that are ONE outer ring with any number of
+ * holes directly inside it (a donut, a frame, a gear, the counters of a letter). Inputs, alignment, host return values, "which draws
+ * make meshes", the dev_sizes / dev_status protocol, ascending dense output (sequence `b` of vgx_merge), draw_route, asynchronous and
+ * stream-ordered with no host round trip, ends a counted state: vgx_concave_triangulate's word for word. A draw with ONE sub-path gets
+ * exactly the route, mesh record, vertices and indices vgx_concave_triangulate gives it; a refused draw gets vgx_concave_contours'
+ * meshes. VGX_TRI_REFUSED_MULTI is never returned. Islands inside holes, separate outlines and rings that touch stay with the contour
+ * route or with libtess2.
+ * The rule for a draw of S >= 2 sub-paths. c(a, b, p) and MEETS are those of vgx_concave_triangulate. The rings are the draw's
+ *   sub-paths: the polyline vertices, with VGX_FILL_AA the vertices vgx_concave_move gives for every contour. V = their total vertex
+ *   count, the vertices numbered 0 .. V - 1 in sub-path order; prev / next of a vertex are taken inside its ring; H = S - 1.
+ *   Refusals, tested in this order:
+ *   TOO_LONG    V + 2 H > VGX_TRIANGULATE_MAX_VERTICES;
+ *   NONFINITE   a coordinate is not finite;
+ *   DEGENERATE  the orientation s_r of some ring r is 0: k = the ring's smallest vertex by (x, y, index), s_r = sign c(prev k, k, next k);
+ *   NOT_SIMPLE  two edges u -> next u of the draw that have no vertex index in common MEET, of one ring or of two;
+ *   NESTING     the rings are not one outer ring with holes directly inside it. The outer ring o owns the draw's smallest vertex by
+ *               (x, y, index); s = s_o. Every other ring h is a hole with bridge vertex m_h, its GREATEST vertex by (x, y, index).
+ *               Without VGX_FILL_EVEN_ODD a hole needs s_h = -s; with it any orientation passes. inside(p, r) = the parity of the
+ *               number of edges u -> v of ring r with (u.y <= p.y) != (v.y <= p.y) and sign c(u, v, p) == sign (v.y - u.y). Every m_h
+ *               must be inside o and outside every other hole;
+ *   NO_BRIDGE   a hole finds no bridge (below);
+ *   STALLED     as in vgx_concave_triangulate.
+ *   Slots. The merged ring is a doubly linked ring of SLOTS: slot i < V is vertex i; slots V + 2 j and V + 2 j + 1 are second copies of
+ *     the two bridge ends of the j-th processed hole (j from 0). A slot's position is its vertex's. The merged ring starts as ring o.
+ *   Bridges. The holes are processed in DESCENDING order of m_h by (x, y, index). For hole h with M = m_h a CANDIDATE is a slot q of the
+ *     merged ring as it stands with: (position) q.x > M.x, or q.x == M.x and q.y > M.y; (cone) with a = prev q, n = next q in the merged
+ *     ring, t = s c(a,q,n), e1 = s c(a,q,M), e2 = s c(q,n,M): t > 0 ? (e1 > 0 && e2 > 0) : (e1 > 0 || e2 > 0); (visibility) the segment
+ *     M -> q MEETS no edge of any ring of the draw and no earlier bridge, those that have vertex M or q's vertex as an end aside. The
+ *     bridge goes to the candidate smallest by (d2, slot), d2 = dx * dx + dy * dy in binary64 from the widened coordinates, no FMA. No
+ *     candidate: NO_BRIDGE. The splice: q -> M -> h's vertices (forwards, by next, when s_h = -s; else backwards) -> slot V + 2 j (M
+ *     again) -> slot V + 2 j + 1 (q's vertex again) -> the old next q.
+ *   Clipping. vgx_concave_triangulate's loop over the N = V + 2 H slots, the cursor starting at slot 0, with one amendment: a slot whose
+ *     position compares equal in both coordinates to that of a, b or c does not block an ear.
+ * Why the image is the same. Each bridge is walked once in each direction, and opposite edges cancel exactly; every emitted triangle
+ *   has s c >= 0; the rings' winding is 0 or s everywhere (under even-odd with a hole traversed backwards the PARITY is that of the
+ *   rings). So every sample is covered by at most one triangle, and exactly where the contour mesh covers it.
+ * What a triangulated draw writes. ONE mesh of kind VGX_MESH_CONCAVE_FILL_AA: the V vertices in order (with AA, first the 2V fringe
+ *   vertices and 6V fringe indices of vgx_concave_contours / vgx_concave_emit for all contours, then the V moved vertices), and
+ *   3 (V + 2 H - 2) indices in emission order, each slot replaced by its vertex (rebased by 2V with AA).
+ * Scratch (the context's buffer list): 36 bytes per draw and 6 bytes per SLOT of min(5 / 3 out->cap_vertices, ndraws *
+ *   VGX_TRIANGULATE_MAX_VERTICES): a draw has fewer than V / 3 holes, so fewer than 5 V / 3 slots. */
+enum { VGX_TRI_REFUSED_NESTING = 8, VGX_TRI_REFUSED_NO_BRIDGE = 9 };
+int vgx_concave_triangulate_rings(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                                  const vgx_mesh_out* out, uint32_t* draw_route /* DEVICE [ndraws], may be NULL */, vgx_sizes* dev_sizes, uint32_t* dev_status,
+                                  void* stream);
+
 /* ---- merging external meshes into a frame -----------------------------------------------------------------
  * The reference appends every mesh to the frame in submission order (createDrawCommand_VertexColor, src/vg.cpp:5207-5244).
  * vgx_merge builds that order from two mesh sequences that are each sorted by draw: `a` = what vgx_tessellate[_emit] wrote for

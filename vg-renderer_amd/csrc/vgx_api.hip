@@ -3418,8 +3418,9 @@ int vgx_concave_contours(vgx_ctx* ctx, const float* poly, const vgx_subpath* sub
 	return launchStatus(ctx);
 }
 
-int vgx_concave_triangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
-                            const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+// vgx_concave_triangulate and vgx_concave_triangulate_rings are one body: `rings` chooses the kernels and the bound of the triangle scratch
+static int concaveTriangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                              const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream, bool rings)
 {
 	DeviceGuard guard(ctx);
 	if (!ctx || !out || !out->pos || !out->color || !out->idx || meshOutMisaligned(out) || (ndraws && (!poly || !subpaths || !draw_info || !draws))) {
@@ -3434,7 +3435,9 @@ int vgx_concave_triangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath* 
 	// vertices (the call then ends with VGX_E_NOSPACE) keep none. A ring that is clipped has at most VGX_TRIANGULATE_MAX_VERTICES: a large
 	// output buffer behind a few draws costs no more scratch than those draws can fill
 	const uint64_t ringBound = ndraws * (uint64_t)VGX_TRIANGULATE_MAX_VERTICES;
-	const uint64_t capTri = 3 * (out->cap_vertices < ringBound ? out->cap_vertices : ringBound);
+	// With holes a draw of V vertices waits in V + 2 H slots, and H < V / 3 (a ring has three vertices at least): below 5 V / 3
+	const uint64_t slotBound = rings ? out->cap_vertices + 2 * (out->cap_vertices / 3) : out->cap_vertices;
+	const uint64_t capTri = 3 * (slotBound < ringBound ? slotBound : ringBound);
 	int st;
 	if ((st = ensure(ctx, ctx->totals, 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->partial, VGX_SCAN_BLOCKS * sizeof(Sum3))) != VGX_OK) { return st; }
@@ -3452,10 +3455,22 @@ int vgx_concave_triangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath* 
 	a.pos = out->pos; a.color = out->color; a.idx = out->idx; a.meshes = out->meshes;
 	a.cap_vertices = out->cap_vertices; a.cap_indices = out->cap_indices; a.cap_meshes = out->meshes ? out->cap_meshes : ~0ull;
 	a.totals = ctx->totals.ptr();
-	vgx_launch_concave_triangulate(a, ctx->partial.p, s);
-	mark(ctx, s, "concave_triangulate");
+	if (rings) { vgx_launch_concave_triangulate_rings(a, ctx->partial.p, s); } else { vgx_launch_concave_triangulate(a, ctx->partial.p, s); }
+	mark(ctx, s, rings ? "concave_triangulate_rings" : "concave_triangulate");
 	publish(ctx, dev_sizes, dev_status, s);
 	return launchStatus(ctx);
+}
+
+int vgx_concave_triangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                            const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+{
+	return concaveTriangulate(ctx, poly, subpaths, draw_info, draws, ndraws, out, draw_route, dev_sizes, dev_status, stream, false);
+}
+
+int vgx_concave_triangulate_rings(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                                  const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+{
+	return concaveTriangulate(ctx, poly, subpaths, draw_info, draws, ndraws, out, draw_route, dev_sizes, dev_status, stream, true);
 }
 
 // ---- text runs ----------------------------------------------------------------------------------------

@@ -257,6 +257,8 @@ struct VgxTriArgs
 	VgxTotals* totals;
 };
 void vgx_launch_concave_triangulate(const VgxTriArgs& a, void* partial /* Sum3[VGX_SCAN_BLOCKS] */, hipStream_t s);
+// vgx_concave_triangulate_rings: the same arguments; cand_prefix counts SLOTS (V + 2 H per deciding draw) and `tri` holds three indices per slot
+void vgx_launch_concave_triangulate_rings(const VgxTriArgs& a, void* partial /* Sum3[VGX_SCAN_BLOCKS] */, hipStream_t s);
 
 // text runs (vgx_text.hip)
 struct VgxTextArgs

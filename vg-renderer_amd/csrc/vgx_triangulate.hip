@@ -12,6 +12,7 @@
 //   k_tri_emit  one workgroup per mesh-making draw writes the streams: a triangulated draw by tri_emit_vertex / tri_emit_index, a refused
 //               one by contours_emit_vertex
 // Nothing in the result goes through an atomic (the sticky status word aside, as everywhere): the bytes are the same every run.
+// vgx_concave_triangulate_rings (further down) is the same four steps with kernels of its own for draws of one outer ring with holes.
 #include "vgx_internal.h"
 #include "vgx_wave.h"
 #include "vgx_scan.h"
@@ -208,7 +209,344 @@ __global__ __launch_bounds__(VGX_TRI_THREADS) void k_tri_emit(VgxTriArgs A)
 	}
 }
 
+// ---- vgx_concave_triangulate_rings: the same four steps for draws of one outer ring with holes ------------------------------------------
+// The scans carry H = num_subpaths - 1 per draw (it is in the draw's info): a deciding draw takes V + 2 H slots of triangle scratch and,
+// triangulated, 3 (V + 2 H - 2) indices. k_tri_decide and k_tri_emit above are not launched by this entry and not touched by it.
+struct OpTriRingsClasses : OpTriClasses // scan 1
+{
+	__device__ uint32_t cls(uint64_t i, uint64_t* V, uint32_t* H) const
+	{
+		int made;
+		const uint32_t c = tri_rings_draw_class(A.draws[i], A.draw_info[i], A.subpaths, V, H, &made);
+		if (made < 0) { set_status(A.totals, VGX_E_INVALID_ARG); }
+		return c;
+	}
+	__device__ Sum3 load(uint64_t i) const
+	{
+		Sum3 r = sum3_zero();
+		uint64_t V; uint32_t H;
+		if (cls(i, &V, &H) == VGX_TRI_ROUTE_TRIANGLES) { r.a = V + 2ull * H; }
+		return r;
+	}
+	__device__ void store(uint64_t i, Sum3 e) const
+	{
+		uint64_t V; uint32_t H;
+		const uint32_t c = cls(i, &V, &H);
+		A.route[i] = c; A.ring_vertices[i] = V; A.cand_prefix[i] = e.a;
+		if (A.draw_route && c != VGX_TRI_ROUTE_TRIANGLES) { A.draw_route[i] = c; } // a deciding draw's word is k_tri_decide_rings'
+	}
+};
+
+struct OpTriRingsPlaces : OpTriPlaces // scan 2
+{
+	__device__ Sum3 load(uint64_t i) const
+	{
+		Sum3 r = sum3_zero();
+		const uint32_t route = A.route[i];
+		if (route == 0u) { return r; }
+		uint32_t nm; bool big;
+		tri_rings_draw_sizes(A.draws[i], route, A.ring_vertices[i], A.draw_info[i].num_subpaths - 1u, &r.a, &r.b, &nm, &big);
+		r.c = nm;
+		if (big) { set_status(A.totals, VGX_E_MESH_TOO_LARGE); } // uint16 indices
+		return r;
+	}
+	__device__ void store(uint64_t i, Sum3 e) const
+	{
+		A.vertex_prefix[i] = e.a; A.index_prefix[i] = e.b;
+		const uint32_t route = A.route[i];
+		if (route == 0u || !A.meshes) { return; }
+		vgx_mesh m[2];
+		const uint32_t n = tri_rings_draw_meshes(A.draws[i], (uint32_t)i, route, A.ring_vertices[i], A.draw_info[i].num_subpaths - 1u, e.a, e.b, m);
+		for (uint32_t k = 0; k < n; ++k) { if (e.c + k < A.cap_meshes) { A.meshes[e.c + k] = m[k]; } }
+	}
+};
+
+#define VGX_TRI_NONE 0xFFFFFFFFu
+
+// the smallest (or greatest) vertex by (x, y, index) over the wave, on every lane; i == VGX_TRI_NONE: this lane has none
+__device__ __forceinline__ uint32_t wave_extreme_vertex(V2 p, uint32_t i, bool greatest)
+{
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) {
+		const V2 o = v2(__shfl_xor(p.x, d), __shfl_xor(p.y, d));
+		const uint32_t oi = (uint32_t)__shfl_xor((int)i, d);
+		const bool take = oi != VGX_TRI_NONE && (i == VGX_TRI_NONE || (greatest ? tri_before(p, i, o, oi) : tri_before(o, oi, p, i)));
+		if (take) { p = o; i = oi; }
+	}
+	return i;
+}
+
+// the smallest key (d2, slot) over the workgroup, on every thread; slot == VGX_TRI_NONE: this thread has none. Two barriers
+__device__ __forceinline__ void block_min_key(double* d2, uint32_t* slot, double* s_d, uint32_t* s_s)
+{
+	double k = *d2; uint32_t x = *slot;
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) {
+		const double ok = __shfl_xor(k, d);
+		const uint32_t ox = (uint32_t)__shfl_xor((int)x, d);
+		if (ox != VGX_TRI_NONE && (x == VGX_TRI_NONE || tri_key_less(ok, ox, k, x))) { k = ok; x = ox; }
+	}
+	if ((threadIdx.x & 63) == 0) { s_d[threadIdx.x >> 6] = k; s_s[threadIdx.x >> 6] = x; }
+	__syncthreads();
+	k = s_d[0]; x = s_s[0];
+	for (int w = 1; w < VGX_TRI_THREADS / 64; ++w) {
+		const double ok = s_d[w]; const uint32_t ox = s_s[w];
+		if (ox != VGX_TRI_NONE && (x == VGX_TRI_NONE || tri_key_less(ok, ox, k, x))) { k = ok; x = ox; }
+	}
+	__syncthreads();
+	*d2 = k; *slot = x;
+}
+
+// One workgroup per deciding draw. LDS by the compiler's report: 61 776 bytes -- 8 bytes of position per vertex, a 16-bit slot -> vertex
+// map and two 16-bit links per slot at the cap of 4096 slots (56 KiB), three small per-ring tables and the reduction's words -- so two
+// workgroups per CU (160 KiB) whatever the draws hold. `route` is block-uniform throughout: every change comes out of a barrier
+__global__ __launch_bounds__(VGX_TRI_THREADS) void k_tri_decide_rings(VgxTriArgs A)
+{
+	__shared__ float2 s_pos[VGX_TRIANGULATE_MAX_VERTICES];
+	__shared__ uint16_t s_vert[VGX_TRIANGULATE_MAX_VERTICES], s_prev[VGX_TRIANGULATE_MAX_VERTICES], s_next[VGX_TRIANGULATE_MAX_VERTICES];
+	__shared__ uint16_t s_mh[VGX_TRI_MAX_RINGS], s_lo[VGX_TRI_MAX_RINGS]; // per ring its greatest and its smallest vertex; s_lo later: the holes in processing order
+	__shared__ int8_t s_sgn[VGX_TRI_MAX_RINGS];
+	__shared__ double s_rd[VGX_TRI_THREADS / 64];
+	__shared__ uint32_t s_rs[VGX_TRI_THREADS / 64];
+	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	for (uint64_t di = blockIdx.x; di < A.ndraws; di += gridDim.x) {
+		if (A.route[di] != VGX_TRI_ROUTE_TRIANGLES) { continue; } // block-uniform
+		__syncthreads(); // the previous draw's readers are done
+		const vgx_draw d = A.draws[di];
+		const vgx_draw_info info = A.draw_info[di];
+		const vgx_subpath* sp = A.subpaths + info.first_subpath;
+		const uint32_t S = info.num_subpaths, H = S - 1u;
+		const uint32_t V = (uint32_t)A.ring_vertices[di], N = V + 2u * H; // N <= VGX_TRIANGULATE_MAX_VERTICES, S <= VGX_TRI_MAX_RINGS (tri_rings_draw_class)
+		const uint64_t base0 = sp[0].first_vertex;
+		const bool evenOdd = (d.fill_flags & VGX_FILL_EVEN_ODD) != 0u;
+		uint32_t route = VGX_TRI_ROUTE_TRIANGLES;
+
+		// the rings by vertex, their links, the non-finite test
+		bool bad = false;
+		for (uint32_t j = tid; j < V; j += VGX_TRI_THREADS) {
+			const uint32_t r = tri_ring_of(sp, S, j);
+			const uint32_t first = (uint32_t)(sp[r].first_vertex - base0), n = sp[r].num_vertices, jl = j - first;
+			const V2 p = tri_ring_vertex(A.poly + 2 * sp[r].first_vertex, n, d, jl);
+			s_pos[j] = make_float2(p.x, p.y);
+			s_prev[j] = (uint16_t)(jl ? j - 1 : first + n - 1); s_next[j] = (uint16_t)(jl + 1 < n ? j + 1 : first);
+			s_vert[j] = VGX_TRI_UNLINKED;
+			bad = bad || !tri_finite(p);
+		}
+		if (__syncthreads_or(bad ? 1 : 0)) { route = VGX_TRI_REFUSED_NONFINITE; }
+
+		// per ring, a wave each: its smallest and greatest vertex and its orientation
+		if (route == VGX_TRI_ROUTE_TRIANGLES) {
+			for (uint32_t r = wave; r < S; r += VGX_TRI_THREADS / 64) {
+				const uint32_t first = (uint32_t)(sp[r].first_vertex - base0), n = sp[r].num_vertices;
+				uint32_t k = VGX_TRI_NONE, g = VGX_TRI_NONE;
+				V2 pk = v2(0.0f, 0.0f), pg = pk;
+				for (uint32_t j = first + lane; j < first + n; j += 64) {
+					const V2 p = lds_pos(s_pos, j);
+					if (k == VGX_TRI_NONE || tri_before(p, j, pk, k)) { k = j; pk = p; }
+					if (g == VGX_TRI_NONE || tri_before(pg, g, p, j)) { g = j; pg = p; }
+				}
+				k = wave_extreme_vertex(pk, k, false); g = wave_extreme_vertex(pg, g, true);
+				if (lane == 0) {
+					s_lo[r] = (uint16_t)k; s_mh[r] = (uint16_t)g;
+					s_sgn[r] = (int8_t)tri_sign(tri_edge(lds_pos(s_pos, s_prev[k]), lds_pos(s_pos, k), lds_pos(s_pos, s_next[k])));
+				}
+			}
+			__syncthreads();
+			bool flat = false;
+			for (uint32_t r = tid; r < S; r += VGX_TRI_THREADS) { flat = flat || s_sgn[r] == 0; }
+			if (__syncthreads_or(flat ? 1 : 0)) { route = VGX_TRI_REFUSED_DEGENERATE; }
+		}
+
+		if (route == VGX_TRI_ROUTE_TRIANGLES) { // every edge against every later edge of the draw: the j of one i spread over the threads
+			bool meet = false;
+			for (uint32_t i = 0; i + 1 < V; ++i) {
+				const uint32_t ni = s_next[i];
+				const V2 u1 = lds_pos(s_pos, i), v1 = lds_pos(s_pos, ni);
+				for (uint32_t j = i + 1 + tid; j < V; j += VGX_TRI_THREADS) {
+					const uint32_t nj = s_next[j];
+					if (ni == j || nj == i) { continue; } // a common vertex index
+					meet = meet || tri_edges_meet(u1, v1, lds_pos(s_pos, j), lds_pos(s_pos, nj));
+				}
+			}
+			if (__syncthreads_or(meet ? 1 : 0)) { route = VGX_TRI_REFUSED_NOT_SIMPLE; }
+		}
+
+		uint32_t o = 0;
+		double s = 0.0;
+		if (route == VGX_TRI_ROUTE_TRIANGLES) { // the outer ring; per hole, a wave each: its orientation and inside(m_h, r) of every other ring r
+			uint32_t k = s_lo[0]; // every thread folds the same ring minima in the same order (broadcast reads)
+			for (uint32_t r = 1; r < S; ++r) {
+				const uint32_t j = s_lo[r];
+				if (tri_before(lds_pos(s_pos, j), j, lds_pos(s_pos, k), k)) { k = j; }
+			}
+			o = tri_ring_of(sp, S, k);
+			s = (double)s_sgn[o];
+			bool wrong = false;
+			for (uint32_t h = wave; h < S; h += VGX_TRI_THREADS / 64) {
+				if (h == o) { continue; }
+				if (!evenOdd && s_sgn[h] != -s_sgn[o]) { wrong = true; }
+				const V2 m = lds_pos(s_pos, s_mh[h]);
+				for (uint32_t r = 0; r < S && !wrong; ++r) {
+					if (r == h) { continue; }
+					const uint32_t first = (uint32_t)(sp[r].first_vertex - base0), n = sp[r].num_vertices;
+					bool in = false;
+					for (uint32_t j = first + lane; j < first + n; j += 64) { in = in != tri_inside_edge(lds_pos(s_pos, j), lds_pos(s_pos, s_next[j]), m); }
+					const bool inside = (__popcll(wave_ballot(in)) & 1) != 0;
+					if (inside != (r == o)) { wrong = true; }
+				}
+			}
+			if (__syncthreads_or(wrong ? 1 : 0)) { route = VGX_TRI_REFUSED_NESTING; }
+		}
+
+		if (route == VGX_TRI_ROUTE_TRIANGLES) { // the holes in descending order of their bridge vertex (s_lo); the merged ring starts as ring o
+			for (uint32_t h = tid; h < S; h += VGX_TRI_THREADS) {
+				if (h == o) { continue; }
+				const uint32_t mine = s_mh[h];
+				const V2 pm = lds_pos(s_pos, mine);
+				uint32_t rank = 0;
+				for (uint32_t g = 0; g < S; ++g) {
+					const uint32_t other = s_mh[g];
+					if (g != o && g != h && tri_before(pm, mine, lds_pos(s_pos, other), other)) { ++rank; }
+				}
+				s_lo[rank] = (uint16_t)h;
+			}
+			const uint32_t first = (uint32_t)(sp[o].first_vertex - base0), n = sp[o].num_vertices;
+			for (uint32_t j = first + tid; j < first + n; j += VGX_TRI_THREADS) { s_vert[j] = (uint16_t)j; }
+			__syncthreads();
+		}
+
+		for (uint32_t jh = 0; jh < H && route == VGX_TRI_ROUTE_TRIANGLES; ++jh) { // one bridge per trip
+			const uint32_t h = s_lo[jh], M = s_mh[h], slots = V + 2u * jh;
+			const V2 pm = lds_pos(s_pos, M);
+			double rejected = -1.0; // the last rejected key; d2 >= 0
+			uint32_t rejectedSlot = 0, q = VGX_TRI_NONE;
+			for (;;) {
+				double best = 0.0;
+				uint32_t bestSlot = VGX_TRI_NONE;
+				for (uint32_t x = tid; x < slots; x += VGX_TRI_THREADS) {
+					const uint32_t vx = s_vert[x];
+					if (vx == VGX_TRI_UNLINKED) { continue; }
+					const V2 px = lds_pos(s_pos, vx);
+					if (!tri_after(px, pm) || !tri_cone(lds_pos(s_pos, s_vert[s_prev[x]]), px, lds_pos(s_pos, s_vert[s_next[x]]), pm, s)) { continue; }
+					const double dd = tri_d2(pm, px);
+					if (!tri_key_less(rejected, rejectedSlot, dd, x)) { continue; }
+					if (bestSlot == VGX_TRI_NONE || tri_key_less(dd, x, best, bestSlot)) { best = dd; bestSlot = x; }
+				}
+				block_min_key(&best, &bestSlot, s_rd, s_rs);
+				if (bestSlot == VGX_TRI_NONE) { break; }
+				const uint32_t vq = s_vert[bestSlot];
+				const V2 pq = lds_pos(s_pos, vq);
+				bool hidden = false; // every ring's edges and the earlier bridges are the links of the slots so far
+				for (uint32_t x = tid; x < slots; x += VGX_TRI_THREADS) {
+					const uint32_t y = s_next[x];
+					const uint32_t u = x < V ? x : s_vert[x], w = y < V ? y : s_vert[y];
+					if (u == M || w == M || u == vq || w == vq) { continue; }
+					hidden = hidden || tri_edges_meet(pm, pq, lds_pos(s_pos, u), lds_pos(s_pos, w));
+				}
+				if (!__syncthreads_or(hidden ? 1 : 0)) { q = bestSlot; break; }
+				rejected = best; rejectedSlot = bestSlot;
+			}
+			if (q == VGX_TRI_NONE) { route = VGX_TRI_REFUSED_NO_BRIDGE; break; }
+			const uint32_t first = (uint32_t)(sp[h].first_vertex - base0), n = sp[h].num_vertices;
+			const bool backwards = s_sgn[h] == s_sgn[o];
+			for (uint32_t j = first + tid; j < first + n; j += VGX_TRI_THREADS) {
+				if (backwards) { const uint16_t t = s_prev[j]; s_prev[j] = s_next[j]; s_next[j] = t; }
+				s_vert[j] = (uint16_t)j;
+			}
+			__syncthreads();
+			if (tid == 0) { // q -> M -> the hole -> second copy of M -> second copy of q -> old next q
+				const uint32_t a = slots, b = slots + 1u, qn = s_next[q], last = s_prev[M];
+				s_vert[a] = (uint16_t)M; s_vert[b] = s_vert[q];
+				s_next[q] = (uint16_t)M; s_prev[M] = (uint16_t)q;
+				s_next[last] = (uint16_t)a; s_prev[a] = (uint16_t)last;
+				s_next[a] = (uint16_t)b; s_prev[b] = (uint16_t)a;
+				s_next[b] = (uint16_t)qn; s_prev[qn] = (uint16_t)b;
+			}
+			__syncthreads();
+		}
+
+		if (tid < 64) { // one wave, every lane with the same cursor, over the N slots
+			const uint64_t first = 3 * A.cand_prefix[di];
+			const bool keep = first + 3 * (uint64_t)N <= A.cap_tri; // beyond it the call ends with VGX_E_NOSPACE: the route is still needed
+			uint16_t* tri = A.tri + first;
+			if (route == VGX_TRI_ROUTE_TRIANGLES) {
+				uint32_t b = 0, size = N, misses = 0, nt = 0;
+				while (size > 3) {
+					const uint32_t a = s_prev[b], c = s_next[b];
+					const uint32_t va = s_vert[a], vb = s_vert[b], vc = s_vert[c];
+					const V2 pa = lds_pos(s_pos, va), pb = lds_pos(s_pos, vb), pc = lds_pos(s_pos, vc);
+					const double t = s * tri_edge(pa, pb, pc);
+					bool ear = t == 0.0;
+					if (t > 0.0) {
+						ear = true;
+						for (uint32_t base = 0; base < N && ear; base += 64) {
+							const uint32_t p = base + lane;
+							bool inside = false;
+							if (p < N && p != a && p != b && p != c && s_prev[p] != VGX_TRI_UNLINKED) { inside = tri_blocks_slot(pa, pb, pc, lds_pos(s_pos, s_vert[p]), s); }
+							ear = wave_ballot(inside) == 0ull;
+						}
+					}
+					if (ear) {
+						if (lane == 0 && keep) { tri[nt] = (uint16_t)va; tri[nt + 1] = (uint16_t)vb; tri[nt + 2] = (uint16_t)vc; }
+						nt += 3;
+						s_next[a] = (uint16_t)c; s_prev[c] = (uint16_t)a; s_prev[b] = VGX_TRI_UNLINKED;
+						b = s_next[c]; --size; misses = 0;
+					} else {
+						b = c;
+						if (++misses > size) { route = VGX_TRI_REFUSED_STALLED; break; }
+					}
+				}
+				if (route == VGX_TRI_ROUTE_TRIANGLES && lane == 0 && keep) { tri[nt] = s_vert[s_prev[b]]; tri[nt + 1] = s_vert[b]; tri[nt + 2] = s_vert[s_next[b]]; }
+			}
+			if (lane == 0) {
+				A.route[di] = route;
+				if (A.draw_route) { A.draw_route[di] = route; }
+			}
+		}
+	}
+}
+
+// k_tri_emit for the rings entry: a triangulated draw holds all its sub-paths' vertices and 3 (V + 2 H - 2) triangle indices
+__global__ __launch_bounds__(VGX_TRI_THREADS) void k_tri_emit_rings(VgxTriArgs A)
+{
+	if (A.totals->status != VGX_OK) { return; }
+	for (uint64_t di = blockIdx.x; di < A.ndraws; di += gridDim.x) {
+		const uint32_t route = A.route[di];
+		if (route == 0u) { continue; }
+		const vgx_draw d = A.draws[di];
+		const vgx_draw_info info = A.draw_info[di];
+		const vgx_subpath* sp = A.subpaths + info.first_subpath;
+		const uint64_t V = A.ring_vertices[di], fv = A.vertex_prefix[di], fi = A.index_prefix[di];
+		if (route == VGX_TRI_ROUTE_TRIANGLES) {
+			const uint16_t* tri = A.tri + 3 * A.cand_prefix[di];
+			const uint64_t ni = 3 * (V + 2ull * (info.num_subpaths - 1u) - 2);
+			for (uint64_t c = threadIdx.x; c < V; c += VGX_TRI_THREADS) { (void)contours_emit_vertex_data(A.poly, sp, info.num_subpaths, d, c, V, fv, fi, A.pos, A.color, A.idx); }
+			for (uint64_t k = threadIdx.x; k < ni; k += VGX_TRI_THREADS) { tri_emit_index(d, tri, k, V, fi, A.idx); }
+		} else {
+			for (uint64_t c = threadIdx.x; c < V; c += VGX_TRI_THREADS) {
+				contours_emit_vertex(A.poly, sp, info.num_subpaths, d, c, V, fv, fi, A.pos, A.color, A.idx);
+			}
+		}
+	}
+}
+
 } // namespace
+
+void vgx_launch_concave_triangulate_rings(const VgxTriArgs& a, void* partial, hipStream_t s)
+{
+	OpTriRingsClasses classes; classes.A = a;
+	vgx_device_scan(classes, (Sum3*)partial, s, a.ndraws);
+	if (a.ndraws) {
+		const uint32_t blocks = (uint32_t)(a.ndraws < 4096u ? a.ndraws : 4096u);
+		hipLaunchKernelGGL(k_tri_decide_rings, dim3(blocks), dim3(VGX_TRI_THREADS), 0, s, a);
+	}
+	OpTriRingsPlaces places; places.A = a;
+	vgx_device_scan(places, (Sum3*)partial, s, a.ndraws);
+	if (a.ndraws) {
+		const uint32_t blocks = (uint32_t)(a.ndraws < 4096u ? a.ndraws : 4096u);
+		hipLaunchKernelGGL(k_tri_emit_rings, dim3(blocks), dim3(VGX_TRI_THREADS), 0, s, a);
+	}
+}
 
 void vgx_launch_concave_triangulate(const VgxTriArgs& a, void* partial, hipStream_t s)
 {

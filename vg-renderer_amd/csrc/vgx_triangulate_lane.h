@@ -1,7 +1,8 @@
 // vgx_triangulate_lane.h -- the arithmetic of vgx_concave_triangulate (include/vgx.h) for ONE ring: host + device. The predicates below
 // are what a lane of vgx_triangulate.hip evaluates; tri_ring_route runs the rule vertex after vertex on the host (libvgx_hosttest.so:
 // vgxt_concave_triangulate), so that the CPU suite pins every route and every index without a GPU. What a refused draw holds is
-// vgx_concave_lane.h's, called from both sides.
+// vgx_concave_lane.h's, called from both sides. Below them, the same for vgx_concave_triangulate_rings -- one outer ring with holes:
+// nesting, cone, bridge distance, the clipping amendment -- and its host walk tri_rings_route (vgxt_concave_triangulate_rings).
 //
 // Every decision is a sign of the canonical edge value of vgx_raster.h -- the rasteriser's own function, not a restatement of it --, so
 // "the triangles' windings sum to the ring's" is a statement about one number computed in one place.
@@ -113,7 +114,208 @@ VGX_HD void tri_emit_index(const vgx_draw& d, const uint16_t* tri, uint64_t k, u
 	idx[firstIndex + (aa ? 6 * V : 0u) + k] = (uint16_t)(tri[k] + (aa ? 2 * V : 0u));
 }
 
+// ---- vgx_concave_triangulate_rings: one outer ring with holes, bridged into one ring of SLOTS (include/vgx.h) ---------------------------
+// A draw of S sub-paths has V vertices (numbered in sub-path order), H = S - 1 holes and N = V + 2 H slots. Slot i < V is vertex i;
+// slots V + 2 j and V + 2 j + 1 are the second copies of the bridge ends of the j-th processed hole. vert[] is the slot -> vertex map;
+// while the bridges are built, vert[i] of a vertex slot that is not yet in the merged ring holds VGX_TRI_UNLINKED.
+#define VGX_TRI_MAX_RINGS ((VGX_TRIANGULATE_MAX_VERTICES + 2u) / 5u) // 3 S + 2 (S - 1) <= the cap
+
+// 0 (no mesh), TOO_LONG, or VGX_TRI_ROUTE_TRIANGLES = "the rings decide"; *V the vertex count, *H the holes. Never MULTI
+VGX_HD uint32_t tri_rings_draw_class(const vgx_draw& d, const vgx_draw_info& di, const vgx_subpath* subs, uint64_t* V, uint32_t* H, int* made)
+{
+	*made = contours_draw_counts(d, di, subs, V);
+	*H = 0u;
+	if (*made <= 0) { return 0u; }
+	*H = di.num_subpaths - 1u;
+	if (*V + 2ull * *H > VGX_TRIANGULATE_MAX_VERTICES) { return VGX_TRI_REFUSED_TOO_LONG; }
+	return VGX_TRI_ROUTE_TRIANGLES;
+}
+
+VGX_HD void tri_rings_draw_sizes(const vgx_draw& d, uint32_t route, uint64_t V, uint32_t H, uint64_t* nv, uint64_t* ni, uint32_t* nm, bool* tooLarge)
+{
+	tri_draw_sizes(d, route, V, nv, ni, nm, tooLarge);
+	if (route == VGX_TRI_ROUTE_TRIANGLES) { *ni += 6ull * H; } // 3 (V + 2 H - 2) triangle indices
+}
+
+VGX_HD uint32_t tri_rings_draw_meshes(const vgx_draw& d, uint32_t drawIndex, uint32_t route, uint64_t V, uint32_t H, uint64_t firstVertex, uint64_t firstIndex, vgx_mesh* m)
+{
+	const uint32_t n = tri_draw_meshes(d, drawIndex, route, V, firstVertex, firstIndex, m);
+	if (route == VGX_TRI_ROUTE_TRIANGLES) { m[0].num_indices += 6u * H; }
+	return n;
+}
+
+// the sub-path of draw-local vertex c among the draw's nsub: the last that starts at or before c
+VGX_HD uint32_t tri_ring_of(const vgx_subpath* sp, uint32_t nsub, uint32_t c)
+{
+	uint32_t lo = 0, hi = nsub;
+	while (hi - lo > 1u) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (sp[mid].first_vertex - sp[0].first_vertex <= c) { lo = mid; } else { hi = mid; }
+	}
+	return lo;
+}
+
+// draw-local vertex c of the rings: the polyline vertex, with AA the vertex vgx_concave_move gives for its contour
+VGX_HD V2 tri_rings_vertex(const float* poly, const vgx_subpath* sp, uint32_t nsub, const vgx_draw& d, uint32_t c)
+{
+	const uint32_t r = tri_ring_of(sp, nsub, c);
+	return tri_ring_vertex(poly + 2 * sp[r].first_vertex, sp[r].num_vertices, d, c - (uint32_t)(sp[r].first_vertex - sp[0].first_vertex));
+}
+
+// is p after m in (x, then y), strictly? (a bridge goes forwards)
+VGX_HD bool tri_after(V2 p, V2 m) { return p.x > m.x || (p.x == m.x && p.y > m.y); }
+
+VGX_HD bool tri_same_place(V2 p, V2 q) { return p.x == q.x && p.y == q.y; }
+
+// does the edge u -> v count for inside(p, .)?
+VGX_HD bool tri_inside_edge(V2 u, V2 v, V2 p)
+{
+	if ((u.y <= p.y) == (v.y <= p.y)) { return false; }
+	return tri_sign(tri_edge(u, v, p)) == (v.y > u.y ? 1 : -1);
+}
+
+// does the corner a -> q -> n of a ring of orientation s see m?
+VGX_HD bool tri_cone(V2 a, V2 q, V2 n, V2 m, double s)
+{
+	const double t = s * tri_edge(a, q, n), e1 = s * tri_edge(a, q, m), e2 = s * tri_edge(q, n, m);
+	return t > 0.0 ? (e1 > 0.0 && e2 > 0.0) : (e1 > 0.0 || e2 > 0.0);
+}
+
+VGX_HD double tri_d2(V2 m, V2 q)
+{
+	const double dx = (double)q.x - (double)m.x, dy = (double)q.y - (double)m.y;
+	return dx * dx + dy * dy;
+}
+
+VGX_HD bool tri_key_less(double d, uint32_t slot, double d0, uint32_t slot0) { return d < d0 || (d == d0 && slot < slot0); }
+
+// does p keep (a, b, c) from being an ear, under the amendment: a slot at the place of a, b or c does not
+VGX_HD bool tri_blocks_slot(V2 a, V2 b, V2 c, V2 p, double s)
+{
+	if (tri_same_place(p, a) || tri_same_place(p, b) || tri_same_place(p, c)) { return false; }
+	return tri_blocks(a, b, c, p, s);
+}
+
 #ifndef __HIP_DEVICE_COMPILE__
+// The rule on the host for a draw of S >= 1 rings, step after step. pos[0 .. V): the rings' vertices (with AA the moved ones); sp: the
+// draw's S sub-paths. vert / prev / next: N = V + 2 (S - 1) entries each; sgn, mh: S entries; tri receives 3 (N - 2) draw-local VERTEX
+// indices when the route is VGX_TRI_ROUTE_TRIANGLES. trips (may be null): per processed hole the candidates its search tried
+static inline uint32_t tri_rings_route(const V2* pos, uint32_t V, const vgx_subpath* sp, uint32_t S, bool evenOdd, uint16_t* vert, uint16_t* prev, uint16_t* next,
+                                       int8_t* sgn, uint16_t* mh, uint16_t* tri, uint32_t* trips)
+{
+	const uint32_t H = S - 1u, N = V + 2u * H;
+	for (uint32_t j = 0; j < V; ++j) { if (!tri_finite(pos[j])) { return VGX_TRI_REFUSED_NONFINITE; } }
+	uint32_t lowest = 0; // the draw's smallest vertex
+	for (uint32_t r = 0; r < S; ++r) {
+		const uint32_t first = (uint32_t)(sp[r].first_vertex - sp[0].first_vertex), n = sp[r].num_vertices;
+		uint32_t k = first, g = first;
+		for (uint32_t j = first; j < first + n; ++j) {
+			prev[j] = (uint16_t)(j > first ? j - 1 : first + n - 1); next[j] = (uint16_t)(j + 1 < first + n ? j + 1 : first);
+			vert[j] = VGX_TRI_UNLINKED;
+			if (tri_before(pos[j], j, pos[k], k)) { k = j; }
+			if (tri_before(pos[g], g, pos[j], j)) { g = j; }
+		}
+		sgn[r] = (int8_t)tri_sign(tri_edge(pos[prev[k]], pos[k], pos[next[k]]));
+		mh[r] = (uint16_t)g;
+		if (tri_before(pos[k], k, pos[lowest], lowest)) { lowest = k; }
+	}
+	for (uint32_t r = 0; r < S; ++r) { if (sgn[r] == 0) { return VGX_TRI_REFUSED_DEGENERATE; } }
+	for (uint32_t i = 0; i + 1 < V; ++i) {
+		for (uint32_t j = i + 1; j < V; ++j) {
+			if (next[i] == j || next[j] == i) { continue; } // a common vertex index
+			if (tri_edges_meet(pos[i], pos[next[i]], pos[j], pos[next[j]])) { return VGX_TRI_REFUSED_NOT_SIMPLE; }
+		}
+	}
+	const uint32_t o = tri_ring_of(sp, S, lowest);
+	const double s = (double)sgn[o];
+	for (uint32_t h = 0; h < S; ++h) {
+		if (h == o) { continue; }
+		if (!evenOdd && sgn[h] != -sgn[o]) { return VGX_TRI_REFUSED_NESTING; }
+		const V2 m = pos[mh[h]];
+		for (uint32_t r = 0; r < S; ++r) {
+			if (r == h) { continue; }
+			const uint32_t first = (uint32_t)(sp[r].first_vertex - sp[0].first_vertex);
+			bool in = false;
+			for (uint32_t j = first; j < first + sp[r].num_vertices; ++j) { in = in != tri_inside_edge(pos[j], pos[next[j]], m); }
+			if (in != (r == o)) { return VGX_TRI_REFUSED_NESTING; }
+		}
+	}
+	{
+		const uint32_t first = (uint32_t)(sp[o].first_vertex - sp[0].first_vertex);
+		for (uint32_t j = first; j < first + sp[o].num_vertices; ++j) { vert[j] = (uint16_t)j; }
+	}
+	uint32_t lastHole = 0xFFFFFFFFu; // holes in descending order of their bridge vertex
+	for (uint32_t jh = 0; jh < H; ++jh) {
+		uint32_t h = 0xFFFFFFFFu;
+		for (uint32_t r = 0; r < S; ++r) {
+			if (r == o) { continue; }
+			if (lastHole != 0xFFFFFFFFu && !tri_before(pos[mh[r]], mh[r], pos[mh[lastHole]], mh[lastHole])) { continue; }
+			if (h == 0xFFFFFFFFu || tri_before(pos[mh[h]], mh[h], pos[mh[r]], mh[r])) { h = r; }
+		}
+		lastHole = h;
+		const uint32_t M = mh[h], slots = V + 2u * jh;
+		const V2 pm = pos[M];
+		double rejected = -1.0; uint32_t rejectedSlot = 0; // the last rejected key; d2 >= 0
+		uint32_t q = 0xFFFFFFFFu, tried = 0;
+		for (;;) {
+			double best = 0.0; uint32_t bestSlot = 0xFFFFFFFFu;
+			for (uint32_t x = 0; x < slots; ++x) {
+				if (vert[x] == VGX_TRI_UNLINKED) { continue; }
+				const V2 px = pos[vert[x]];
+				if (!tri_after(px, pm) || !tri_cone(pos[vert[prev[x]]], px, pos[vert[next[x]]], pm, s)) { continue; }
+				const double d = tri_d2(pm, px);
+				if (!tri_key_less(rejected, rejectedSlot, d, x)) { continue; }
+				if (bestSlot == 0xFFFFFFFFu || tri_key_less(d, x, best, bestSlot)) { best = d; bestSlot = x; }
+			}
+			if (bestSlot == 0xFFFFFFFFu) { break; }
+			++tried;
+			const uint32_t vq = vert[bestSlot];
+			bool hidden = false;
+			for (uint32_t x = 0; x < slots && !hidden; ++x) { // every ring's edges and the earlier bridges are the links of the slots so far
+				const uint32_t u = x < V ? x : vert[x], y = next[x], w = y < V ? y : vert[y];
+				if (u == M || w == M || u == vq || w == vq) { continue; }
+				hidden = tri_edges_meet(pm, pos[vq], pos[u], pos[w]);
+			}
+			if (!hidden) { q = bestSlot; break; }
+			rejected = best; rejectedSlot = bestSlot;
+		}
+		if (trips) { trips[jh] = tried; }
+		if (q == 0xFFFFFFFFu) { return VGX_TRI_REFUSED_NO_BRIDGE; }
+		const uint32_t first = (uint32_t)(sp[h].first_vertex - sp[0].first_vertex), A = slots, B = slots + 1u;
+		for (uint32_t j = first; j < first + sp[h].num_vertices; ++j) {
+			if (sgn[h] == sgn[o]) { const uint16_t t = prev[j]; prev[j] = next[j]; next[j] = t; } // traversed backwards
+			vert[j] = (uint16_t)j;
+		}
+		const uint32_t qn = next[q], last = prev[M];
+		vert[A] = (uint16_t)M; vert[B] = vert[q];
+		next[q] = (uint16_t)M; prev[M] = (uint16_t)q;
+		next[last] = (uint16_t)A; prev[A] = (uint16_t)last;
+		next[A] = (uint16_t)B; prev[B] = (uint16_t)A;
+		next[B] = (uint16_t)qn; prev[qn] = (uint16_t)B;
+	}
+	uint32_t b = 0, size = N, misses = 0, nt = 0;
+	while (size > 3) {
+		const uint32_t a = prev[b], c = next[b];
+		const V2 pa = pos[vert[a]], pb = pos[vert[b]], pc = pos[vert[c]];
+		const double t = s * tri_edge(pa, pb, pc);
+		bool ear = t == 0.0;
+		if (t > 0.0) {
+			ear = true;
+			for (uint32_t p = next[c]; p != a && ear; p = next[p]) { ear = !tri_blocks_slot(pa, pb, pc, pos[vert[p]], s); }
+		}
+		if (ear) {
+			tri[nt++] = vert[a]; tri[nt++] = vert[b]; tri[nt++] = vert[c];
+			next[a] = (uint16_t)c; prev[c] = (uint16_t)a; prev[b] = VGX_TRI_UNLINKED;
+			b = next[c]; --size; misses = 0;
+		} else {
+			b = c;
+			if (++misses > size) { return VGX_TRI_REFUSED_STALLED; }
+		}
+	}
+	tri[nt++] = vert[prev[b]]; tri[nt++] = vert[b]; tri[nt++] = vert[next[b]];
+	return VGX_TRI_ROUTE_TRIANGLES;
+}
+
 // The rule on the host, vertex after vertex: the route of the ring pos[0 .. V) (3 <= V <= VGX_TRIANGULATE_MAX_VERTICES) and, when it is
 // VGX_TRI_ROUTE_TRIANGLES, its 3 (V - 2) ring-local indices in tri. prev / next: V links each
 static inline uint32_t tri_ring_route(const V2* pos, uint32_t V, uint16_t* prev, uint16_t* next, uint16_t* tri)

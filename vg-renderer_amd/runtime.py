@@ -1125,6 +1125,20 @@ def concave_triangulate(ctx, poly_dev, subpaths_dev, draw_info_dev, draws_dev, n
     return draw_route
 
 
+def concave_triangulate_rings(ctx, poly_dev, subpaths_dev, draw_info_dev, draws_dev, ndraws, bufs, draw_route=None):
+    """concave_triangulate() that also triangulates a draw of several sub-paths when they are one outer ring with holes directly inside
+    it (vgx_concave_triangulate_rings in include/vgx.h). The routes never hold capi.TRI_REFUSED_MULTI; such a draw is triangulated or
+    refused as capi.TRI_REFUSED_NESTING / TRI_REFUSED_NO_BRIDGE or one of the single-ring reasons."""
+    import torch
+    if draw_route is None:
+        draw_route = torch.zeros(max(int(ndraws), 1), dtype=torch.int32, device=bufs.dev_status.device)
+    out = bufs.out_struct()
+    _check(lib().vgx_concave_triangulate_rings(ctx.handle, poly_dev.data_ptr() if ndraws else None, subpaths_dev.data_ptr() if ndraws else None,
+                                               draw_info_dev.data_ptr() if ndraws else None, draws_dev.data_ptr() if ndraws else None, int(ndraws), C.byref(out),
+                                               draw_route.data_ptr(), bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_concave_triangulate_rings")
+    return draw_route
+
+
 # ---- text runs (vgx_text_quads): glyph layout and the atlas stay with the caller -------------------------------------
 def text_runs_dense(runs, first_vertex=0, first_index=0):
     """The dense layout for a vgx_text_run array (capi.text_run_dtype, first_quad / num_quads set): every run's vertices and
