@@ -1627,6 +1627,46 @@ int vgx_concave_triangulate_rings(vgx_ctx* ctx, const float* poly, const vgx_sub
                                   const vgx_mesh_out* out, uint32_t* draw_route /* DEVICE [ndraws], may be NULL */, vgx_sizes* dev_sizes, uint32_t* dev_status,
                                   void* stream);
 
+/* ---- SEVERAL OUTLINES and ISLANDS IN HOLES to triangles: vgx_flatten -> vgx_concave_triangulate_nested -> vgx_merge ---------------------
+ * vgx_concave_triangulate_nested is vgx_concave_triangulate_rings for draws whose sub-paths are any number of outlines, each with holes,
+ * each hole with islands, and so on (a word converted to outlines, "i", "%", a target, a gear with a hub). Such a draw is a disjoint
+ * union of draws the rings entry triangulates: the rings are classified by containment depth, cut into GROUPS of one even-depth ring
+ * and the odd-depth rings directly inside it, and every group is triangulated by the rings rule. Inputs, alignment, host return values,
+ * "which draws make meshes", the dev_sizes / dev_status protocol, ascending dense output (sequence `b` of vgx_merge), draw_route,
+ * asynchronous and stream-ordered with no host round trip, ends a counted state: vgx_concave_triangulate_rings' word for word. A draw
+ * with ONE sub-path gets vgx_concave_triangulate's words; a refused draw gets vgx_concave_contours' meshes. No new route code.
+ * The rule for a draw of S >= 2 sub-paths. c, MEETS, inside(p, r), the rings (moved with VGX_FILL_AA), V, m_r (the GREATEST vertex of
+ *   ring r by (x, y, index)) and s_r are those of the two sections above. Refusals, tested in this order:
+ *   TOO_LONG    V + 2 (S - 1) > VGX_TRIANGULATE_MAX_VERTICES: the rings entry's test, known without geometry; it bounds the slots of
+ *               any grouping;
+ *   NONFINITE, DEGENERATE, NOT_SIMPLE   as in the rings entry, over the whole draw, pairs of edges of different groups included;
+ *   NESTING     the containment is not a forest this rule can use. C(r) = { r' != r : inside(m_r, r') }, depth(r) = |C(r)|. For
+ *               depth(r) > 0, parent(r) is the ring of C(r) whose depth is depth(r) - 1: not exactly one such ring is NESTING. A ring of
+ *               even depth is the OUTER ring of a group, in any orientation under either fill rule; a ring of odd depth is a HOLE of its
+ *               parent's group. Without VGX_FILL_EVEN_ODD a hole needs s_h = -s_parent, else NESTING (at depth 1 as at depth 3);
+ *   NO_BRIDGE, STALLED   the refusal of the lowest-numbered group that has one.
+ *   Groups are numbered ascending by the sub-path index of their outer ring; G = their number, H_g = the holes of group g, B_g = the
+ *     holes of the groups before g. Group g goes through the rings entry's Slots / Bridges / Clipping with: "the draw's rings" = the
+ *     group's rings; o = the group's outer ring, s = s_o; its vertex slots are its rings' vertices; the two bridge slots of its j-th
+ *     processed hole are V + 2 (B_g + j) and V + 2 (B_g + j) + 1; the cursor starts at the group's lowest slot; in the visibility test
+ *     and in the ear test "every slot / edge / earlier bridge" ranges over the GROUP's slots only. A group of one ring is clipped by
+ *     vgx_concave_triangulate's loop, with no amendment and the cursor at its first vertex.
+ *   So the triangles of a group are the ones vgx_concave_triangulate_rings gives a draw made of that group's sub-paths alone, in their
+ *   order, with the indices translated; and a draw with G = 1 gets the rings entry's bytes.
+ * Why the image is the same. Inside a group, bridges cancel and the triangles telescope to the group's rings (the rings section); a
+ *   group's region -- inside its outer ring, outside its holes -- has winding 0 or s_o (parity under even-odd). No two edges of the
+ *   draw meet, so rings nest or lie apart, and the regions of two groups are disjoint: an island lies in a hole of the group around it.
+ *   The draw's winding (or parity) is non-zero exactly on the union of the groups' regions. So every sample is covered by at most one
+ *   triangle, and exactly where the contour mesh covers it.
+ * What a triangulated draw writes. ONE mesh of kind VGX_MESH_CONCAVE_FILL_AA: the V vertices in order (with AA behind the 2V fringe
+ *   vertices and 6V fringe indices of all contours, exactly as the rings entry writes them), then the triangles group after group, each
+ *   group's V_g + 2 H_g - 2 in emission order: 3 (V + 2 S - 4 G) indices in all.
+ * Scratch (the context's buffer list): the rings entry's -- 36 bytes per draw and 6 bytes per SLOT of min(5 / 3 out->cap_vertices,
+ *   ndraws * VGX_TRIANGULATE_MAX_VERTICES) -- and 4 bytes per draw for G. */
+int vgx_concave_triangulate_nested(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                                   const vgx_mesh_out* out, uint32_t* draw_route /* DEVICE [ndraws], may be NULL */, vgx_sizes* dev_sizes, uint32_t* dev_status,
+                                   void* stream);
+
 /* ---- merging external meshes into a frame -----------------------------------------------------------------
  * The reference appends every mesh to the frame in submission order (createDrawCommand_VertexColor, src/vg.cpp:5207-5244).
  * vgx_merge builds that order from two mesh sequences that are each sorted by draw: `a` = what vgx_tessellate[_emit] wrote for

@@ -43,7 +43,7 @@ CONTOUR_EVEN_ODD = 1  # vgx_mesh.subpath_kind of such a mesh: bit 0 is the fill 
 TRIANGULATE_MAX_VERTICES = 4096
 TRI_ROUTE_TRIANGLES, TRI_REFUSED_MULTI, TRI_REFUSED_TOO_LONG, TRI_REFUSED_NONFINITE = 1, 2, 3, 4
 TRI_REFUSED_DEGENERATE, TRI_REFUSED_NOT_SIMPLE, TRI_REFUSED_STALLED = 5, 6, 7
-TRI_REFUSED_NESTING, TRI_REFUSED_NO_BRIDGE = 8, 9  # vgx_concave_triangulate_rings alone
+TRI_REFUSED_NESTING, TRI_REFUSED_NO_BRIDGE = 8, 9  # vgx_concave_triangulate_rings and vgx_concave_triangulate_nested
 
 
 def stroke_flags(cap, join, aa=True, thin=False):
@@ -399,6 +399,8 @@ VGX_SYMBOLS = {
                                           C.c_void_p, C.c_void_p]),
     "vgx_concave_triangulate_rings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),
+    "vgx_concave_triangulate_nested": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
     "vgx_cmdlist_decode": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CmdListState), C.POINTER(CmdListOut)]),
     "vgx_cmdlist_decode_text": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CmdListState), C.POINTER(CmdListOut), C.POINTER(CmdListText)]),
     "vgx_text_quads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(MeshOut), C.c_void_p, C.c_uint32,

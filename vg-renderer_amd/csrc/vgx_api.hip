@@ -162,6 +162,7 @@ struct vgx_ctx
 	// vgx_concave_triangulate (vgx_triangulate.hip): per draw its route; its ring's vertex count and three exclusive prefixes, [ndraws + 1]
 	// each (VgxTriArgs); the clipping's ring-local triangles, three indices per vertex of the caller's vertex capacity
 	Buf<uint32_t> triRoute; Buf<uint64_t> triPrefix; Buf<uint16_t> triIdx;
+	Buf<uint32_t> triGroups;             // vgx_concave_triangulate_nested alone: per draw its group count, [ndraws + 1]
 	Buf<VgxTotals> totals;
 	Buf<uint32_t> textTiles;             // vgx_text_quads: first run of every tile of quads (vgx_text.hip)
 	Buf<uint8_t> cullFlags; DevBuf cullPartial; // vgx_cache_cull (vgx_bounds.hip): kept flag per instance, the compaction scan's slice sums (views: as `partial`). Its own: a counted state survives the call
@@ -3418,10 +3419,13 @@ int vgx_concave_contours(vgx_ctx* ctx, const float* poly, const vgx_subpath* sub
 	return launchStatus(ctx);
 }
 
-// vgx_concave_triangulate and vgx_concave_triangulate_rings are one body: `rings` chooses the kernels and the bound of the triangle scratch
+// vgx_concave_triangulate, vgx_concave_triangulate_rings and vgx_concave_triangulate_nested are one body: `entry` chooses the kernels, the
+// bound of the triangle scratch and (nested alone) a word per draw for its group count
+enum TriEntry { TRI_ENTRY_RING, TRI_ENTRY_RINGS, TRI_ENTRY_NESTED };
 static int concaveTriangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
-                              const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream, bool rings)
+                              const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream, TriEntry entry)
 {
+	const bool rings = entry != TRI_ENTRY_RING;
 	DeviceGuard guard(ctx);
 	if (!ctx || !out || !out->pos || !out->color || !out->idx || meshOutMisaligned(out) || (ndraws && (!poly || !subpaths || !draw_info || !draws))) {
 		return VGX_E_INVALID_ARG;
@@ -3444,6 +3448,7 @@ static int concaveTriangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath
 	if ((st = ensure(ctx, ctx->triRoute, ndraws + 1)) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->triPrefix, 4 * (ndraws + 1))) != VGX_OK) { return st; }
 	if ((st = ensure(ctx, ctx->triIdx, capTri + 1)) != VGX_OK) { return st; }
+	if (entry == TRI_ENTRY_NESTED && (st = ensure(ctx, ctx->triGroups, ndraws + 1)) != VGX_OK) { return st; }
 	noteHip(ctx, hipMemsetAsync(ctx->totals.p, 0, sizeof(VgxTotals), s));
 	VgxTriArgs a;
 	memset(&a, 0, sizeof(a));
@@ -3455,8 +3460,9 @@ static int concaveTriangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath
 	a.pos = out->pos; a.color = out->color; a.idx = out->idx; a.meshes = out->meshes;
 	a.cap_vertices = out->cap_vertices; a.cap_indices = out->cap_indices; a.cap_meshes = out->meshes ? out->cap_meshes : ~0ull;
 	a.totals = ctx->totals.ptr();
-	if (rings) { vgx_launch_concave_triangulate_rings(a, ctx->partial.p, s); } else { vgx_launch_concave_triangulate(a, ctx->partial.p, s); }
-	mark(ctx, s, rings ? "concave_triangulate_rings" : "concave_triangulate");
+	if (entry == TRI_ENTRY_NESTED) { vgx_launch_concave_triangulate_nested(a, ctx->triGroups.ptr(), ctx->partial.p, s); }
+	else if (rings) { vgx_launch_concave_triangulate_rings(a, ctx->partial.p, s); } else { vgx_launch_concave_triangulate(a, ctx->partial.p, s); }
+	mark(ctx, s, entry == TRI_ENTRY_NESTED ? "concave_triangulate_nested" : rings ? "concave_triangulate_rings" : "concave_triangulate");
 	publish(ctx, dev_sizes, dev_status, s);
 	return launchStatus(ctx);
 }
@@ -3464,13 +3470,19 @@ static int concaveTriangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath
 int vgx_concave_triangulate(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
                             const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
 {
-	return concaveTriangulate(ctx, poly, subpaths, draw_info, draws, ndraws, out, draw_route, dev_sizes, dev_status, stream, false);
+	return concaveTriangulate(ctx, poly, subpaths, draw_info, draws, ndraws, out, draw_route, dev_sizes, dev_status, stream, TRI_ENTRY_RING);
 }
 
 int vgx_concave_triangulate_rings(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
                                   const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
 {
-	return concaveTriangulate(ctx, poly, subpaths, draw_info, draws, ndraws, out, draw_route, dev_sizes, dev_status, stream, true);
+	return concaveTriangulate(ctx, poly, subpaths, draw_info, draws, ndraws, out, draw_route, dev_sizes, dev_status, stream, TRI_ENTRY_RINGS);
+}
+
+int vgx_concave_triangulate_nested(vgx_ctx* ctx, const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                                   const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* dev_sizes, uint32_t* dev_status, void* stream)
+{
+	return concaveTriangulate(ctx, poly, subpaths, draw_info, draws, ndraws, out, draw_route, dev_sizes, dev_status, stream, TRI_ENTRY_NESTED);
 }
 
 // ---- text runs ----------------------------------------------------------------------------------------

@@ -848,6 +848,75 @@ int vgxt_concave_triangulate_rings(const float* poly, const vgx_subpath* subpath
 	return VGX_OK;
 }
 
+// vgx_concave_triangulate_nested on the host: vgxt_concave_triangulate_rings with tri_nested_route and the sizes of a draw of G groups.
+// trips as there
+int vgxt_concave_triangulate_nested(const float* poly, const vgx_subpath* subpaths, const vgx_draw_info* draw_info, const vgx_draw* draws, uint64_t ndraws,
+                                    const vgx_mesh_out* out, uint32_t* draw_route, vgx_sizes* sizes, uint32_t* status, uint32_t* trips)
+{
+	if (!out || !out->pos || !out->color || !out->idx || (ndraws && (!poly || !subpaths || !draw_info || !draws))) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)out->pos & 7u) || ((uintptr_t)out->color & 3u) || ((uintptr_t)out->idx & 1u) || ((uintptr_t)out->meshes & 7u)) { return VGX_E_INVALID_ARG; }
+	if (((uintptr_t)poly & 7u) || ((uintptr_t)subpaths & 7u) || ((uintptr_t)draw_info & 7u) || ((uintptr_t)draws & 3u) || ((uintptr_t)draw_route & 3u)) { return VGX_E_INVALID_ARG; }
+	if (ndraws >= 0xFFFFFFFFull) { return VGX_E_RANGE; }
+	const uint32_t cap = VGX_TRIANGULATE_MAX_VERTICES;
+	V2* ring = (V2*)malloc(cap * sizeof(V2));
+	uint16_t* links = (uint16_t*)malloc((3 * cap + 7 * VGX_TRI_MAX_RINGS) * sizeof(uint16_t)); // vert, prev, next, mh, tri_nested_route's six tables
+	uint16_t* tri = (uint16_t*)malloc(3 * cap * sizeof(uint16_t));
+	uint32_t* routes = (uint32_t*)malloc(2 * (ndraws + 1) * sizeof(uint32_t)); // and G per draw
+	uint32_t* tried = (uint32_t*)malloc(VGX_TRI_MAX_RINGS * sizeof(uint32_t));
+	int8_t* sgn = (int8_t*)malloc(VGX_TRI_MAX_RINGS);
+	if (!ring || !links || !tri || !routes || !tried || !sgn) { free(ring); free(links); free(tri); free(routes); free(tried); free(sgn); return VGX_E_INTERNAL; }
+	uint32_t* groups = routes + (ndraws + 1);
+	uint32_t st = VGX_OK;
+	uint64_t nv = 0, ni = 0, nm = 0;
+	for (int pass = 0; pass < 2 && st == VGX_OK; ++pass) { // routes, sizes and records, then -- the capacities hold -- the streams
+		nv = ni = nm = 0;
+		for (uint64_t i = 0; i < ndraws; ++i) {
+			const vgx_draw& d = draws[i];
+			uint64_t V;
+			uint32_t H;
+			int made;
+			uint32_t route = tri_rings_draw_class(d, draw_info[i], subpaths, &V, &H, &made);
+			if (made < 0 && st == VGX_OK) { st = VGX_E_INVALID_ARG; }
+			const vgx_subpath* sp = subpaths + draw_info[i].first_subpath;
+			const uint32_t S = H + 1u;
+			if (pass == 0) { groups[i] = 0; if (trips) { trips[i] = 0; } }
+			if (route == VGX_TRI_ROUTE_TRIANGLES && (pass == 0 || routes[i] == VGX_TRI_ROUTE_TRIANGLES)) { // a refusal is known from pass 0
+				for (uint32_t j = 0; j < (uint32_t)V; ++j) { ring[j] = tri_rings_vertex(poly, sp, S, d, j); }
+				for (uint32_t j = 0; j < H; ++j) { tried[j] = 0; }
+				route = tri_nested_route(ring, (uint32_t)V, sp, S, (d.fill_flags & VGX_FILL_EVEN_ODD) != 0u, links, links + cap, links + 2 * cap, sgn, links + 3 * cap,
+				                         links + 3 * cap + VGX_TRI_MAX_RINGS, tri, &groups[i], tried);
+				if (pass == 0 && trips) { for (uint32_t j = 0; j < H; ++j) { if (tried[j] > trips[i]) { trips[i] = tried[j]; } } }
+			} else if (pass == 1) {
+				route = routes[i];
+			}
+			if (pass == 0) {
+				routes[i] = route;
+				if (draw_route) { draw_route[i] = route; }
+			}
+			if (route == 0u) { continue; }
+			uint64_t dv, dn; uint32_t dm; bool big;
+			tri_nested_draw_sizes(d, route, V, S, groups[i], &dv, &dn, &dm, &big);
+			if (big && st == VGX_OK) { st = VGX_E_MESH_TOO_LARGE; }
+			if (pass == 0) {
+				vgx_mesh m[2];
+				const uint32_t n = tri_nested_draw_meshes(d, (uint32_t)i, route, V, S, groups[i], nv, ni, m);
+				for (uint32_t k = 0; k < n; ++k) { if (out->meshes && nm + k < out->cap_meshes) { out->meshes[nm + k] = m[k]; } }
+			} else if (route == VGX_TRI_ROUTE_TRIANGLES) {
+				for (uint64_t c = 0; c < V; ++c) { (void)contours_emit_vertex_data(poly, sp, S, d, c, V, nv, ni, out->pos, out->color, out->idx); }
+				for (uint64_t k = 0; k < 3 * (V + 2ull * S - 4ull * groups[i]); ++k) { tri_emit_index(d, tri, k, V, ni, out->idx); }
+			} else {
+				for (uint64_t c = 0; c < V; ++c) { contours_emit_vertex(poly, sp, S, d, c, V, nv, ni, out->pos, out->color, out->idx); }
+			}
+			nv += dv; ni += dn; nm += dm;
+		}
+		if (st == VGX_OK && (nv > out->cap_vertices || ni > out->cap_indices || (out->meshes && nm > out->cap_meshes))) { st = VGX_E_NOSPACE; }
+		if (sizes) { memset(sizes, 0, sizeof(*sizes)); sizes->num_meshes = nm; sizes->num_vertices = nv; sizes->num_indices = ni; }
+	}
+	free(ring); free(links); free(tri); free(routes); free(tried); free(sgn);
+	if (status) { *status = st; }
+	return VGX_OK;
+}
+
 // vgx_raster on the host: the functions of vgx_raster.h in a plain loop over the meshes of the range, their triangles and the pixels
 // of each triangle's box inside the scissor; with the call's contract (mesh_bounds may be NULL: the boxes are computed first; given,
 // they are the prefilter they are on the device). HOST pointers, the target's pixels included. Returns the status the device call

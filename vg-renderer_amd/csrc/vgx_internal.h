@@ -259,6 +259,8 @@ struct VgxTriArgs
 void vgx_launch_concave_triangulate(const VgxTriArgs& a, void* partial /* Sum3[VGX_SCAN_BLOCKS] */, hipStream_t s);
 // vgx_concave_triangulate_rings: the same arguments; cand_prefix counts SLOTS (V + 2 H per deciding draw) and `tri` holds three indices per slot
 void vgx_launch_concave_triangulate_rings(const VgxTriArgs& a, void* partial /* Sum3[VGX_SCAN_BLOCKS] */, hipStream_t s);
+// vgx_concave_triangulate_nested: as the rings entry's; groups: [ndraws] scratch, per triangulated draw its group count G (3 (V + 2 S - 4 G) indices)
+void vgx_launch_concave_triangulate_nested(const VgxTriArgs& a, uint32_t* groups, void* partial /* Sum3[VGX_SCAN_BLOCKS] */, hipStream_t s);
 
 // text runs (vgx_text.hip)
 struct VgxTextArgs

@@ -1139,6 +1139,20 @@ def concave_triangulate_rings(ctx, poly_dev, subpaths_dev, draw_info_dev, draws_
     return draw_route
 
 
+def concave_triangulate_nested(ctx, poly_dev, subpaths_dev, draw_info_dev, draws_dev, ndraws, bufs, draw_route=None):
+    """concave_triangulate_rings() that also triangulates several outlines in one path and islands inside holes: the rings are cut by
+    containment depth into groups of one outer ring with its holes, each triangulated by the rings rule
+    (vgx_concave_triangulate_nested in include/vgx.h). A draw of one group gets concave_triangulate_rings()' bytes."""
+    import torch
+    if draw_route is None:
+        draw_route = torch.zeros(max(int(ndraws), 1), dtype=torch.int32, device=bufs.dev_status.device)
+    out = bufs.out_struct()
+    _check(lib().vgx_concave_triangulate_nested(ctx.handle, poly_dev.data_ptr() if ndraws else None, subpaths_dev.data_ptr() if ndraws else None,
+                                                draw_info_dev.data_ptr() if ndraws else None, draws_dev.data_ptr() if ndraws else None, int(ndraws), C.byref(out),
+                                                draw_route.data_ptr(), bufs.dev_sizes.data_ptr(), bufs.dev_status.data_ptr(), _stream_ptr()), "vgx_concave_triangulate_nested")
+    return draw_route
+
+
 # ---- text runs (vgx_text_quads): glyph layout and the atlas stay with the caller -------------------------------------
 def text_runs_dense(runs, first_vertex=0, first_index=0):
     """The dense layout for a vgx_text_run array (capi.text_run_dtype, first_quad / num_quads set): every run's vertices and
